@@ -14,10 +14,18 @@ batch of synthetic QPs whose inputs are already resident in HBM.  Consecutive st
   --config 4 (configs[4]): ragged fleet, 16,384 QPs per GPU with N in {8, 12, 16, 24} drawn per QP and per-QP mixed-gait
         contact schedules, through srbdqp_solve_ragged_device_f64 (bucketed launch)
 
-The one JSON line of the default run (`python bench.py`) carries, beside the configs[1] headline:
+A plain run (`python bench.py`) sets up, warms up, times the K steps, writes what the last timed step computed if
+--dump-outputs DIR is given (u, x, status, iters as DIR/<name>.npy; a seeded sample of QPs beyond 64 MB), and prints the
+one JSON line with the headline.  The warm-up is the W steps (at least one per output set) followed by the solves one at a
+time that --full's roofline times (50 / 5 / 8 / 3 of configs 1 / 2 / 3 / 4, milliseconds in all): a plain run makes them too
+and drops their figure, because without them the GPU is not at its sustained clocks when a short timed region starts (20 steps
+of configs[1]: 5 % lower).  The headline:
   value             2 HIP streams, natural QP order, tails deferred (SRBDQP_FLAG_DEFER_TAIL: a QP that reaches a rho-restart mark
                     unconverged -- 4 % of a batch -- rides in the next solve on its stream instead of holding its own launch up;
                     srbdqp_flush() INSIDE the timed region completes the last ones, so all K batches are solved when the clock stops)
+  ms_per_step       wall time of one timed step
+
+`python bench.py --full` adds everything else to the same line (the --no-* switches trim it):
   value_plain       1 stream, no hint, tails deferred: strictly serial steps in natural QP order
   value_stale_hint  2 streams, tails deferred, a longest-first hint taken from a DIFFERENT batch (a wrong hint)
   in_place          round 3's modes for comparison: every solve complete at its own launch (rho restart in place): value = 2 streams +
@@ -32,7 +40,7 @@ The one JSON line of the default run (`python bench.py`) carries, beside the con
 
 With N > 1 ranks each rank owns its own batch (weak scaling, no data-path collective) and the first-step contact forces
 u_opt0 are all-gathered over RCCL/xGMI every step, as north_star specifies; the same run also times the steps without
-the collective (`value_without_allgather`; --no-allgather makes that the headline).
+the collective (`value_without_allgather`, with --full; --no-allgather makes that the headline).
 
     python bench.py [--gpus N --steps K --warmup W]          # N > 1 without a launcher: starts its own N ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -133,7 +141,9 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=0, help="timed steps (default: 500 / 40 / 100 / 10 for config 1 / 2 / 3 / 4)")
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=10,
+                    help="untimed steps before the timed ones (at least one per output set); then the isolated solves of the roofline, "
+                         "with or without --full, end the warm-up")
     ap.add_argument("--config", type=int, choices=sorted(CONFIGS), default=0,
                     help="default: 1 on one GPU, 3 (65,536 QPs per GPU, N = 10) on several")
     ap.add_argument("--batch", type=int, default=0, help="QPs per GPU per step (default: the config's)")
@@ -157,10 +167,18 @@ def parse_args(argv=None):
     ap.add_argument("--rho-restart-count", type=int, default=0, help="override srbdqp_config.rho_restart_count (0 = library default)")
     ap.add_argument("--rho", type=float, default=0.0, help="override srbdqp_config.rho (0 = library default)")
     ap.add_argument("--rho-fz-scale", type=float, default=0.0, help="override srbdqp_config.rho_fz_scale (0 = library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the value_plain / value_stale_hint variants and the configs[2] / configs[4] legs")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the configs[2] / configs[4] legs only")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline: the isolated-kernel roofline, the value_plain / value_stale_hint / in_place / "
+                         "without_rho_restart variants, the steps timed again with / without the all-gather, latency_batch1, the configs[2] / "
+                         "configs[4] legs and the CPU baseline (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (u, x, status, iters; u0_all with the all-gather) as "
+                         "DIR/<name>.npy in float32 / float64, at most 64 MB in all (beyond that a fixed, seeded sample of QPs, the same QPs in every "
+                         "file, their indices in qp_index.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip latency_batch1")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the value_plain / value_stale_hint variants and the configs[2] / configs[4] legs")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the configs[2] / configs[4] legs only")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (tests: gloo)")
     ap.add_argument("--stub-solve", action="store_true", help="tests of the launcher path only: no GPU, the solve is a stub")
     return ap.parse_args(argv)
@@ -485,6 +503,59 @@ def library_sha256():
     return _LIB_SHA
 
 
+DUMP_BUDGET = 60 << 20           # bytes of array data --dump-outputs may write (under 64 MB with the .npy headers)
+
+
+def step_outputs(leg, i):
+    """the device arrays step i wrote -- what a caller of the timed path receives (forces, trajectory, status, iteration counts) -- and, for the
+    arrays that do not hold one row per QP, which rows belong to which QP (QP index array -> row index array)"""
+    if isinstance(leg, RaggedLeg):
+        s = leg.sets[i % leg.nb]
+        o = s["outs"][(i // leg.nb) % 2]
+        off, Nq = s["off"], s["Nq"]
+        # packed step-major rows (srbdqp.h): u of QP b = rows off_b .. off_b + N_b - 1, x of QP b = rows off_b + b .. off_b + b + N_b
+        rows_of = {"u": lambda q: np.concatenate([np.arange(off[b], off[b] + Nq[b]) for b in q]),
+                   "x": lambda q: np.concatenate([np.arange(off[b] + b, off[b] + b + Nq[b] + 1) for b in q])}
+        return {"u": o["u"], "x": o["x"], "status": o["st"], "iters": o["it"]}, rows_of
+    o = i % leg.NO
+    return {"u": leg.d_u[o], "x": leg.d_x[o], "status": leg.d_st[o], "iters": leg.d_it[o]}, {}
+
+
+def dump_outputs(path, arrays, n_qp, rows_of=None, budget=DUMP_BUDGET):
+    """arrays (torch tensors or numpy) -> path/<name>.npy in float32 / float64 (integer arrays as float64, exact).  An array holds one row per
+    QP (axis 0, n_qp rows) unless rows_of[name] maps QP indices to its rows.  Above `budget` bytes one sample of QPs, drawn with a fixed seed,
+    is kept in EVERY array (the rows of the same QPs, in QP order), and its QP indices are written as qp_index.npy: the same sample from run to
+    run and from build to build."""
+    rows_of = dict(rows_of or {})
+    host = {}
+    for k, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        host[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+        if k not in rows_of:
+            assert a.shape[0] == n_qp, (k, a.shape, n_qp)
+            rows_of[k] = lambda q: q
+
+    def nbytes(q):
+        return sum(len(rows_of[k](q)) * (a.nbytes // max(a.shape[0], 1)) for k, a in host.items())
+
+    q = np.arange(n_qp)
+    total = nbytes(q)
+    sampled = total > budget
+    if sampled:
+        n = max(1, int(n_qp * budget / total))
+        while True:
+            q = np.sort(np.random.default_rng(20240901).choice(n_qp, n, replace=False))
+            if n == 1 or nbytes(q) <= budget:
+                break
+            n = max(1, int(n * 0.98))
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a[rows_of[k](q)] if sampled else a))
+    if sampled:
+        np.save(os.path.join(path, "qp_index.npy"), q.astype(np.float64))
+    return len(q) / n_qp
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse_args(argv)
@@ -587,23 +658,33 @@ def main(argv=None):
     sync()
     base = max(args.warmup, NO)
     base += (-base) % (S * NO)      # keep the (step -> stream, batch, output set) phase
-    # ---- the dominant kernel in isolation: roofline numbers
+    # ---- the dominant kernel in isolation: roofline numbers (--full).  A plain run makes the same solves and drops the figure: they end the
+    #      warm-up (milliseconds), so the timed steps start at sustained clocks (without them 20 steps of configs[1] time 5 % slower)
     kernel_ms, n_iso = None, 0
     if not stub:
-        kernel_ms, n_iso = isolated_kernel_ms(leg, torch, {1: 50, 2: 5, 3: 8, 4: 3}[cid], base)
+        iso = isolated_kernel_ms(leg, torch, {1: 50, 2: 5, 3: 8, 4: 3}[cid], base)
+        if args.full:
+            kernel_ms, n_iso = iso
         if cid != 4:
             leg.kname = leg.eng.kernel_name()
     kname = leg.kname
-    # ---- timed region: exactly K steps (the headline), and the same K steps with / without the collective
+    # ---- timed region: exactly K steps (the headline); with --full the same K steps again with / without the collective
     use_ag = dist is not None and not args.no_allgather and d_u0_all is not None
     elapsed = timed(leg, base, steps, use_ag, S, hint)
-    elapsed_other = timed(leg, base, steps, not use_ag, S, hint) if (dist is not None and d_u0_all is not None) else None
+    if args.dump_outputs and rank == 0:         # what the last timed step computed (complete: flushed and synchronised inside the region)
+        last = base + steps - 1
+        arrays, rows_of = step_outputs(leg, last)
+        if use_ag:          # rank-major: QP b of rank r is row r B + b
+            arrays["u0_all"] = d_u0_all[last % NO]
+            rows_of["u0_all"] = lambda q: (np.arange(world)[:, None] * B + q[None, :]).reshape(-1)
+        dump_outputs(args.dump_outputs, arrays, B, rows_of)
+    elapsed_other = timed(leg, base, steps, not use_ag, S, hint) if (args.full and dist is not None and d_u0_all is not None) else None
     mean_iters, solved_frac, _ = leg.stats(SOLVED)
     if dist is not None and use_ag:            # the collective really moved this rank's forces
         o = (base + steps - 1) % NO
         mine = d_u0_all[o][rank * B:(rank + 1) * B]
         assert torch.equal(mine, leg.d_u[o][:, 0, :]), "all-gather result does not hold this rank's forces"
-    # ---- the same K steps without the two things that shape the headline (configs[1] at one GPU)
+    # ---- the same K steps without the two things that shape the headline (configs[1] at one GPU; --full)
     extra = {}
     def variants(lg):
         el_plain = timed(lg, base, steps, False, 1, "none")
@@ -614,7 +695,7 @@ def main(argv=None):
         el_stale = timed(lg, base, steps, False, S, "stale")
         return B * steps / el_plain, B * steps / el_stale
 
-    if world == 1 and not stub and cid in (1, 3) and not args.no_also and (hint == "own" or defer):     # (configs[1] / the configs[3] shard on one GPU)
+    if args.full and world == 1 and not stub and cid in (1, 3) and not args.no_also and (hint == "own" or defer):     # (configs[1] / the configs[3] shard on one GPU)
         extra["value_plain"], extra["value_stale_hint"] = variants(leg)
         if defer:
             extra["value_variants_note"] = ("value: %d streams, natural QP order, tails deferred to the next solve on the stream (SRBDQP_FLAG_DEFER_TAIL), flushed inside "
@@ -688,7 +769,7 @@ def main(argv=None):
             fl, by = leg.flops_bytes(mean_iters)
             out["roofline"] = roofline(kname, fl, by, B, kernel_ms, n_iso, peak, 1e3 * elapsed / max(steps, 1), S, N, defer=leg.defer,
                                        useful_launch=leg.useful_flops_launch())
-        if world == 1 and not args.no_latency and not stub and cid == 1:
+        if args.full and world == 1 and not args.no_latency and not stub and cid == 1:
             from g1_locomotion_amd import synth
             out["latency_batch1"] = lat = latency_batch1(synth)
             # the p50 / p99 pairs again where the driver's record keeps them whole (north_star: single-QP p50 <= 50 us at batch 1)
@@ -698,9 +779,9 @@ def main(argv=None):
         host_batch0 = leg.host_batches[0] if cid != 4 else None
         leg.close()
         leg = None
-        if world == 1 and not stub and cid == 1 and not args.no_also and not args.no_other_configs:
+        if args.full and world == 1 and not stub and cid == 1 and not args.no_also and not args.no_other_configs:
             out["also"] = also_legs(args, rank, local_rank, dev, torch, SOLVED)
-        if world == 1 and not args.no_cpu_baseline and not stub and cid != 4:
+        if args.full and world == 1 and not args.no_cpu_baseline and not stub and cid != 4:
             out["cpu_baseline"] = cpu_baseline(cid, N, host_batch0)
         print(json.dumps(out), flush=True)
     if leg is not None:

@@ -17,9 +17,9 @@ run() {   # run <output file> <seconds> <command ...>
     if ! $T $secs "$@" > "$O/$out" 2> "$O/$out.err"; then echo "FAILED: $out ($*)"; tail -3 "$O/$out.err"; rm -f "$O/$out"; FAILED="$FAILED $out"; fi
 }
 if [ "$PART" = all ] || [ "$PART" = bench ]; then
-run ${RR}_bench_config1_wave_n10_s2.json 500 python bench.py
-run ${RR}_bench_config2_wrench_f32_n20.json 400 python bench.py --config 2
-run ${RR}_bench_config1_compact_n10_s2.json 200 python bench.py --kernel compact --no-cpu-baseline --no-latency
+run ${RR}_bench_config1_wave_n10_s2.json 500 python bench.py --full
+run ${RR}_bench_config2_wrench_f32_n20.json 400 python bench.py --full --config 2
+run ${RR}_bench_config1_compact_n10_s2.json 200 python bench.py --full --kernel compact --no-cpu-baseline --no-latency
 run ${RR}_latency_batch1.json 500 python tools/latency_probe.py 10000
 run ${RR}_error_distribution_config1.json 300 python tools/error_distribution.py 1
 run ${RR}_error_distribution_config2.json 400 python tools/error_distribution.py 2
