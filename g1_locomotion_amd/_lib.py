@@ -34,7 +34,7 @@ EXPORTS = (
     "srbdqp_assemble_f64", "srbdqp_assemble_wrench_f64",
     "srbdqp_ragged_create", "srbdqp_ragged_destroy", "srbdqp_ragged_last_error", "srbdqp_ragged_flush", "srbdqp_solve_ragged_device_f64", "srbdqp_solve_ragged_f64",
     "srbdqp_solve_ragged_device_f32", "srbdqp_solve_ragged_f32", "srbdqp_solve_ragged_warm_device_f64", "srbdqp_solve_ragged_warm_device_f32",
-    "srbdqp_set_schedule_hint", "srbdqp_flush", "srbdqp_shard_range", "srbdqp_gather_u0_f64", "srbdqp_stage_ptrs", "srbdqp_solve_staged_f64", "srbdqp_update_f64", "srbdqp_prepare_staged_f64", "srbdqp_solve_prepared_f64", "srbdqp_set_stamp_buffer", "srbdqp_synchronize", "srbdqp_last_kernel_ms", "srbdqp_last_kernel_parts_ms", "srbdqp_kernel_name", "srbdqp_batch1_launch_path", "srbdqp_version",
+    "srbdqp_set_schedule_hint", "srbdqp_set_robots", "srbdqp_set_robots_device", "srbdqp_ragged_set_robots", "srbdqp_ragged_set_robots_device", "srbdqp_flush", "srbdqp_shard_range", "srbdqp_gather_u0_f64", "srbdqp_stage_ptrs", "srbdqp_solve_staged_f64", "srbdqp_update_f64", "srbdqp_prepare_staged_f64", "srbdqp_solve_prepared_f64", "srbdqp_set_stamp_buffer", "srbdqp_synchronize", "srbdqp_last_kernel_ms", "srbdqp_last_kernel_parts_ms", "srbdqp_kernel_name", "srbdqp_batch1_launch_path", "srbdqp_version",
     # include/srbdqp_cascade.h
     "srbdqp_swing_f64", "srbdqp_swing_device_f64", "srbdqp_wbid_reference_f64", "srbdqp_wbid_reference_device_f64",
     "srbdqp_mpc_inputs_f64", "srbdqp_mpc_inputs_device_f64",
@@ -61,6 +61,43 @@ class Config(C.Structure):
         ("force_scale", C.c_double), ("rho", C.c_double), ("rho_eq_scale", C.c_double), ("sigma", C.c_double),
         ("alpha", C.c_double), ("eps_abs", C.c_double), ("eps_rel", C.c_double), ("rho_fz_scale", C.c_double),
     ]
+
+
+class Robot(C.Structure):
+    """srbdqp_robot (include/srbdqp.h): one QP's robot, 64 bytes -- the row layout of robots_array()."""
+    _fields_ = [("mass", C.c_double), ("inertia", C.c_double * 3), ("mu", C.c_double), ("fz_min", C.c_double), ("fz_max", C.c_double),
+                ("reserved", C.c_double)]
+
+
+ROBOT_DOUBLES = 8   # C.sizeof(Robot) // 8: mass, inertia[3], mu, fz_min, fz_max, reserved
+
+
+def robots_array(B, mass=None, inertia=None, mu=None, fz_min=None, fz_max=None, cfg=None):
+    """(B, 8) float64 array of srbdqp_robot records for BatchMPC.set_robots / RaggedMPC.set_robots.  Each value is a scalar (every robot) or one per
+    robot -- mass, mu, fz_min, fz_max of shape (B,), inertia of shape (3,) (every robot) or (B, 3); a value not given is the config's (cfg, default:
+    default_config()).  reserved = 0.  Raises ValueError on a shape that does not broadcast."""
+    import numpy as np
+    B = int(B)
+    if B < 0:
+        raise ValueError("B must be >= 0")
+    if cfg is None:
+        cfg = default_config()
+    out = np.zeros((B, ROBOT_DOUBLES), np.float64)
+
+    def col(name, v, default, width):
+        v = np.asarray(default if v is None else v, np.float64)
+        want = (B, width) if width > 1 else (B,)
+        ok = v.shape in ((), want) or (width > 1 and v.shape == (width,))
+        if not ok:
+            raise ValueError(f"{name}: expected a scalar or shape {want}" + (f" or ({width},)" if width > 1 else "") + f", got {v.shape}")
+        return np.broadcast_to(v, want)
+
+    out[:, 0] = col("mass", mass, cfg.mass, 1)
+    out[:, 1:4] = col("inertia", inertia, list(cfg.inertia), 3)
+    out[:, 4] = col("mu", mu, cfg.mu, 1)
+    out[:, 5] = col("fz_min", fz_min, cfg.fz_min, 1)
+    out[:, 6] = col("fz_max", fz_max, cfg.fz_max, 1)
+    return out
 
 
 class Stage(C.Structure):
@@ -152,6 +189,9 @@ def load():
     lib.srbdqp_solve_ragged_f64.restype = C.c_int
     lib.srbdqp_set_schedule_hint.argtypes = [H, C.c_void_p, C.c_int32]
     lib.srbdqp_set_schedule_hint.restype = C.c_int
+    for _fn in (lib.srbdqp_set_robots, lib.srbdqp_set_robots_device, lib.srbdqp_ragged_set_robots, lib.srbdqp_ragged_set_robots_device):
+        _fn.argtypes = [H, C.c_void_p, C.c_int32]
+        _fn.restype = C.c_int
     lib.srbdqp_flush.argtypes = [H, C.c_void_p]
     lib.srbdqp_flush.restype = C.c_int
     lib.srbdqp_shard_range.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]

@@ -4,6 +4,7 @@
 
 #include <cmath>
 #include <cstdio>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -101,6 +102,11 @@ struct srbdqp_handle {
     srbdqp::AqlQueue* aql = nullptr;
     bool aql_tried = false;
     std::string aql_why;
+    // per-QP robot records (srbdqp_set_robots / _device): what the solves read, or null (the config's robot for every QP)
+    const srbdqp_robot* robots = nullptr;
+    size_t robots_len = 0;
+    srbdqp_robot* robots_own = nullptr;    // the library's device copy of host records (srbdqp_set_robots)
+    size_t robots_cap = 0;
 };
 
 // slot of a launch stream (at most kMaxSlots distinct streams per handle; null when exhausted)
@@ -213,7 +219,7 @@ constexpr int kTileClassMinBatch = 512;
 // does a solve of B QPs on this handle go to the general kernel (srbdqp_wrench.hpp)?  launch() / launch_long() ask this.
 inline bool uses_wrench(const srbdqp_handle* h, int maxs, int B) {
     const int N = h->cfg.horizon;
-    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || h->io_f32 || N == 24) return true;
+    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || h->io_f32 || N == 24 || h->robots) return true;   // (per-QP records: only the general kernel reads them)
     // N = 20 single support too, for batches: the general kernel holds 2 workgroups per CU there, the compact one 1
     // (tools/schedule_bench.py, 16,384 QPs: 2.85 M QP/s against 1.95 M; at N = 12 / 16 the compact kernel wins, 7.1 / 4.9 M
     // against 5.7 / 4.2 M)
@@ -552,6 +558,24 @@ int launch_wrench_t(srbdqp_handle* h, const KArgs& a, hipStream_t st) {
             hipLaunchKernelGGL((srbdqp::srbdqp_wrench_kernel<N, double, double, 1, WPS>), dim3((unsigned)a.B), dim3(S::BT), lds, st, a);
         } else { h->err = "the assembly dump is fp64 only"; return SRBDQP_E_INVALID; }
     } else {
+        if constexpr (sizeof(R) == 8 && N != 24) {
+            // per-QP robot records (srbdqp_set_robots / _device): the MODE = 2 instantiation, the records as its second argument -- every launch of a solve
+            // (first pass, restart passes, deferred passes on the tail stream, ragged buckets) comes through here with this handle.  (The entry points refuse
+            // the staged, fp32 and dump calls while records are set, and the setters refuse N = 24: kRobotsMaxHorizon.)
+            if (h->robots) {
+                constexpr size_t lds2 = lds + 8 * sizeof(double);          // + the QP's robot behind the layout (srbdqp_wrench.hpp qp_robot_to_lds)
+                constexpr int by_lds2 = (S::wgs_of(S::o_end + 8) * S::NW + 3) / 4;   // (waves per SIMD the LDS admits, as WrenchTraits::by_lds)
+                static_assert((by_lds2 < WPS ? by_lds2 : WPS) == WPS, "the record's 64 bytes of LDS cost no occupancy");
+                void (*k2)(KArgs, const double*) = &srbdqp::srbdqp_wrench_kernel<N, double, double, 2, WPS, double, 5, 0>;
+                int rc2 = set_lds_once(h, k2, lds2);
+                if (rc2 != SRBDQP_OK) return rc2;
+                static const std::string nm2 = nm + "_rb";
+                h->kname = nm2.c_str();
+                hipLaunchKernelGGL(k2, dim3((unsigned)a.B), dim3(S::BT), lds2, st, a, reinterpret_cast<const double*>(h->robots));
+                HIP_TRY(h, hipGetLastError());
+                return SRBDQP_OK;
+            }
+        }
         if constexpr (sizeof(R) == 8 && N <= 10) {
             // staged batch-1 path (completion word): the low-latency instantiation -- two extra waves for the set-up (tables, T
             // assembly, tile phases) that end before the iterations, one workgroup's worth of registers (no scratch, V in
@@ -817,6 +841,70 @@ int srbdqp_restart_pass(srbdqp_handle* h, const KArgs& a1, hipStream_t st, int m
     return launch(h, a2, st, maxs, 2);
 }
 
+// ---- per-QP robot records (srbdqp_set_robots) ----
+static_assert(sizeof(srbdqp_robot) == 64 && offsetof(srbdqp_robot, inertia) == 8 && offsetof(srbdqp_robot, mu) == 32 &&
+              offsetof(srbdqp_robot, fz_min) == 40 && offsetof(srbdqp_robot, fz_max) == 48 && offsetof(srbdqp_robot, reserved) == 56,
+              "the kernels read a record as 8 doubles (srbdqp_wrench.hpp qp_robot)");
+
+// the rules of include/srbdqp.h (the same ones the kernel applies to device records, srbdqp_wrench.hpp qp_robot); null = valid, else what is wrong
+const char* robot_fault(const srbdqp_robot& r) {
+    auto fin = [](double v) { return std::isfinite(v); };
+    if (!fin(r.mass) || !(r.mass > 0.0)) return "mass must be finite and > 0";
+    for (int i = 0; i < 3; ++i) if (!fin(r.inertia[i]) || !(r.inertia[i] > 0.0)) return "inertia must be finite and > 0";
+    if (!fin(r.mu) || !(r.mu > 0.0)) return "mu must be finite and > 0";
+    if (!fin(r.fz_min) || !fin(r.fz_max) || !(r.fz_min >= 0.0) || !(r.fz_min <= r.fz_max)) return "need finite 0 <= fz_min <= fz_max";
+    if (r.reserved != 0.0) return "reserved must be 0";
+    return nullptr;
+}
+
+int robots_validate(const srbdqp_robot* host, int32_t length, const char* fn, std::string& err) {
+    for (int32_t i = 0; i < length; ++i)
+        if (const char* why = robot_fault(host[i])) { err = std::string(fn) + ": record " + std::to_string(i) + " is invalid (" + why + "); the previous setting is kept"; return SRBDQP_E_INVALID; }
+    return SRBDQP_OK;
+}
+
+// a call that cannot read per-QP records while they are set on this handle
+int robots_refuse(srbdqp_handle* h, const char* what) {
+    h->err = std::string(what) + ": refused while per-QP robot records are set (srbdqp_set_robots): only the fp64 batch and ragged solves on the general kernel read "
+             "them -- one robot for every QP goes in srbdqp_config";
+    return SRBDQP_E_INVALID;
+}
+
+// Horizons whose general kernel has a per-QP-record instantiation (MODE = 2) without scratch memory: N = 24 has none -- the MODE = 0 kernel that ships keeps
+// 20 bytes per lane in scratch with its three extra set-up waves, and a MODE = 2 copy without them (XW = 0) 24 bytes -- so the setters refuse an N = 24
+// handle / a ragged object with an N = 24 bucket.
+constexpr int kRobotsMaxHorizon = 20;
+const char* const robots_n24 = "per-QP robot records: not at N = 24 (no instantiation of the general kernel reads them there without scratch memory, DESIGN.md section 11)";
+
+// fp64 batch solve of B QPs with records set: the general kernel, and a record for every QP
+int robots_check_batch(srbdqp_handle* h, int32_t B) {
+    if (!h->robots) return SRBDQP_OK;
+    if (h->cfg.kernel != SRBDQP_KERNEL_AUTO && h->cfg.kernel != SRBDQP_KERNEL_WRENCH) {
+        h->err = "per-QP robot records are read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH while they are set";
+        return SRBDQP_E_INVALID;
+    }
+    if ((size_t)B > h->robots_len) {
+        h->err = "solve of " + std::to_string(B) + " QPs with " + std::to_string(h->robots_len) + " robot records set (srbdqp_set_robots): every QP needs its record";
+        return SRBDQP_E_INVALID;
+    }
+    return SRBDQP_OK;
+}
+
+// before the library's own copy of the records is replaced: every solve that may still read it has completed (srbdqp_synchronize, then every other launch
+// stream of the handle and its tail streams -- deferred restart passes read the records too)
+int robots_quiesce(srbdqp_handle* h) {
+    int rc = srbdqp_synchronize(h);
+    if (rc != SRBDQP_OK) return rc;
+    rc = srbdqp_flush(h, nullptr);
+    if (rc != SRBDQP_OK) return rc;
+    for (auto& sl : h->slots) {
+        if (!sl.used) continue;
+        HIP_TRY(h, hipStreamSynchronize(sl.st));
+        if (sl.tail_st) HIP_TRY(h, hipStreamSynchronize(sl.tail_st));
+    }
+    return SRBDQP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -938,6 +1026,7 @@ int srbdqp_destroy(srbdqp_handle* h) {
         for (auto& r : sl.rsets) if (r.ev_tail) (void)hipEventDestroy(r.ev_tail);
     }
     if (h->done_count) (void)hipFree(h->done_count);
+    if (h->robots_own) (void)hipFree(h->robots_own);
     if (h->stage_host) (void)hipHostFree(h->stage_host);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -967,6 +1056,7 @@ int srbdqp_stage_ptrs(srbdqp_handle* h, srbdqp_stage* out) {
 
 int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y) {
     if (!h) return SRBDQP_E_INVALID;
+    if (h->robots) return robots_refuse(h, "srbdqp_solve_staged_f64");
     if (B < 0 || B > h->stage_h.capacity) { h->err = "staged batch exceeds the staging capacity"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
     {   // (the kernel of the call before this one published its completion word before it ended)
@@ -1072,6 +1162,7 @@ int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32
 int srbdqp_update_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact,
                       const double* pcom, double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters) {
     if (!h) return SRBDQP_E_INVALID;
+    if (h->robots) return robots_refuse(h, "srbdqp_update_f64");
     if (!x0 || !x_ref || !foot || !contact || !u0_out) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
     const size_t N = (size_t)h->cfg.horizon;
     const srbdqp_stage& s = h->stage_h;
@@ -1117,6 +1208,7 @@ KArgs staged_args(srbdqp_handle* h, int32_t B, bool use_pcom, bool want_x, bool 
 
 int srbdqp_prepare_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom) {
     if (!h) return SRBDQP_E_INVALID;
+    if (h->robots) return robots_refuse(h, "srbdqp_prepare_staged_f64");
     if (B < 0 || B > h->stage_h.capacity) { h->err = "staged batch exceeds the staging capacity"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1134,6 +1226,7 @@ int srbdqp_prepare_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom) {
 
 int srbdqp_solve_prepared_f64(srbdqp_handle* h, int32_t B, int32_t want_x, int32_t want_y) {
     if (!h) return SRBDQP_E_INVALID;
+    if (h->robots) return robots_refuse(h, "srbdqp_solve_prepared_f64");
     if (B <= 0 || B != h->prepared_B) { h->err = "srbdqp_solve_prepared_f64: no set-up of this batch size is pending (srbdqp_prepare_staged_f64)"; return SRBDQP_E_INVALID; }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const bool spin = !(h->cfg.flags & SRBDQP_FLAG_NO_SPIN);
@@ -1166,6 +1259,41 @@ int srbdqp_set_schedule_hint(srbdqp_handle* h, const int32_t* device_iters_prev,
     if (device_iters_prev && length < 0) { h->err = "negative hint length"; return SRBDQP_E_INVALID; }
     h->sched_hint = device_iters_prev;
     h->sched_hint_len = device_iters_prev ? (size_t)length : 0;
+    return SRBDQP_OK;
+}
+
+int srbdqp_set_robots(srbdqp_handle* h, const srbdqp_robot* host, int32_t length) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (host && length < 0) { h->err = "srbdqp_set_robots: negative length"; return SRBDQP_E_INVALID; }
+    const bool clear = !host || length == 0;
+    if (!clear && h->cfg.horizon > kRobotsMaxHorizon) { h->err = robots_n24; return SRBDQP_E_INVALID; }
+    if (!clear) {
+        const int rv = robots_validate(host, length, "srbdqp_set_robots", h->err);
+        if (rv != SRBDQP_OK) return rv;
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    int rc = robots_quiesce(h);                     // (deferred passes may still read the records this call replaces)
+    if (rc != SRBDQP_OK) return rc;
+    if (clear) { h->robots = nullptr; h->robots_len = 0; return SRBDQP_OK; }
+    if ((size_t)length > h->robots_cap) {
+        if (h->robots_own) HIP_TRY(h, hipFree(h->robots_own));
+        h->robots_own = nullptr; h->robots_cap = 0; h->robots = nullptr; h->robots_len = 0;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->robots_own), sizeof(srbdqp_robot) * (size_t)length);
+        if (e != hipSuccess) { h->err = std::string("hipMalloc robot records: ") + hipGetErrorString(e); return SRBDQP_E_NOMEM; }
+        h->robots_cap = (size_t)length;
+    }
+    HIP_TRY(h, hipMemcpy(h->robots_own, host, sizeof(srbdqp_robot) * (size_t)length, hipMemcpyHostToDevice));
+    h->robots = h->robots_own; h->robots_len = (size_t)length;
+    return SRBDQP_OK;
+}
+
+int srbdqp_set_robots_device(srbdqp_handle* h, const srbdqp_robot* dev, int32_t length) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (dev && length < 0) { h->err = "srbdqp_set_robots_device: negative length"; return SRBDQP_E_INVALID; }
+    const bool clear = !dev || length == 0;
+    if (!clear && h->cfg.horizon > kRobotsMaxHorizon) { h->err = robots_n24; return SRBDQP_E_INVALID; }
+    h->robots = clear ? nullptr : dev;
+    h->robots_len = clear ? 0 : (size_t)length;
     return SRBDQP_OK;
 }
 
@@ -1481,6 +1609,8 @@ int srbdqp_solve_batch_device_f64(srbdqp_handle* h, int32_t B, const double* x0,
                                   const double* warm_u, const double* warm_y, double* u_out, double* x_out,
                                   double* y_out, int32_t* status, int32_t* iters, void* stream) {
     if (!h) return SRBDQP_E_INVALID;
+    const int rr = robots_check_batch(h, B);
+    if (rr != SRBDQP_OK) return rr;
     h->io_f32 = false;
     return solve_device_impl(h, B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
 }
@@ -1490,6 +1620,7 @@ int srbdqp_solve_batch_device_f32(srbdqp_handle* h, int32_t B, const float* x0, 
                                   const float* warm_u, const float* warm_y, float* u_out, float* x_out,
                                   float* y_out, int32_t* status, int32_t* iters, void* stream) {
     if (!h) return SRBDQP_E_INVALID;
+    if (h->robots) return robots_refuse(h, "srbdqp_solve_batch_device_f32");
     h->io_f32 = true;
     const int rc = solve_device_impl(h, B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
     h->io_f32 = false;
@@ -1500,6 +1631,8 @@ int srbdqp_solve_batch_f64(srbdqp_handle* h, int32_t B, const double* x0, const 
                            const uint8_t* contact, const double* pcom, const double* warm_u, const double* warm_y,
                            double* u_out, double* x_out, double* y_out, int32_t* status, int32_t* iters) {
     if (!h) return SRBDQP_E_INVALID;
+    const int rr = robots_check_batch(h, B);
+    if (rr != SRBDQP_OK) return rr;
     h->io_f32 = false;
     return solve_host_impl(h, B, sizeof(double), x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters);
 }
@@ -1508,6 +1641,7 @@ int srbdqp_solve_batch_f32(srbdqp_handle* h, int32_t B, const float* x0, const f
                            const uint8_t* contact, const float* pcom, const float* warm_u, const float* warm_y,
                            float* u_out, float* x_out, float* y_out, int32_t* status, int32_t* iters) {
     if (!h) return SRBDQP_E_INVALID;
+    if (h->robots) return robots_refuse(h, "srbdqp_solve_batch_f32");
     h->io_f32 = true;
     const int rc = solve_host_impl(h, B, sizeof(float), x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters);
     h->io_f32 = false;
@@ -1518,6 +1652,7 @@ int srbdqp_assemble_f64(srbdqp_handle* h, int32_t B, const double* x0, const dou
                         const uint8_t* contact, const double* pcom, double* P_out, double* q_out, double* l_out,
                         double* ub_out) {
     if (!h) return SRBDQP_E_INVALID;
+    if (h->robots) return robots_refuse(h, "srbdqp_assemble_f64");
     if (B < 0 || (B > 0 && (!x0 || !x_ref || !foot || !contact || !P_out || !q_out || !l_out || !ub_out))) { h->err = "null pointer"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1617,6 +1752,7 @@ int srbdqp_assemble_wrench_f64(srbdqp_handle* h, int32_t B, const double* x0, co
                                const uint8_t* contact, const double* pcom, double* T_out, double* q_out, double* blocks_out,
                                double* goff_out) {
     if (!h) return SRBDQP_E_INVALID;
+    if (h->robots) return robots_refuse(h, "srbdqp_assemble_wrench_f64");
     if (B < 0 || (B > 0 && (!x0 || !x_ref || !foot || !contact || !T_out || !q_out || !blocks_out || !goff_out))) { h->err = "null pointer"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1697,6 +1833,11 @@ struct srbdqp_ragged {
     std::vector<hipEvent_t> last_tail;        // per bucket: closes the passes of the last call that had any (srbdqp_ragged_flush), or null
     char* ws = nullptr; size_t ws_bytes = 0;  // host-buffer entry point: device copies of the caller's arrays
     hipStream_t stream = nullptr;             // ... and the stream its copies run on
+    // per-QP robot records in the caller's QP order (srbdqp_ragged_set_robots / _device), forwarded to every bucket engine: a bucket's workgroup reads the record
+    // of the caller's index its dispatch order names
+    const srbdqp_robot* robots = nullptr;
+    size_t robots_len = 0;
+    srbdqp_robot* robots_own = nullptr; size_t robots_cap = 0;
     std::string err;
 };
 
@@ -1783,6 +1924,7 @@ int srbdqp_ragged_destroy(srbdqp_ragged* r) {
     if (r->h_perm) (void)hipHostFree(r->h_perm);
     if (r->h_off) (void)hipHostFree(r->h_off);
     if (r->ws) (void)hipFree(r->ws);
+    if (r->robots_own) (void)hipFree(r->robots_own);
     delete r;
     return SRBDQP_OK;
 }
@@ -1799,6 +1941,11 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
                        int32_t* status, int32_t* iters, void* stream, bool f32) {
     if (!r) return SRBDQP_E_INVALID;
     if (B < 0 || (B > 0 && (!N_per_qp || !x0 || !x_ref || !foot || !contact || !u_out))) { r->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (r->robots && f32) { r->err = "fp32 ragged solve: refused while per-QP robot records are set (srbdqp_ragged_set_robots): only the fp64 solves read them"; return SRBDQP_E_INVALID; }
+    if (r->robots && (size_t)B > r->robots_len) {
+        r->err = "ragged solve of " + std::to_string(B) + " QPs with " + std::to_string(r->robots_len) + " robot records set: every QP needs its record";
+        return SRBDQP_E_INVALID;
+    }
     if (B == 0) return SRBDQP_OK;
     RAG_TRY(r, hipSetDevice(r->device));
     hipStream_t sin = stream ? reinterpret_cast<hipStream_t>(stream) : r->stream;
@@ -1982,6 +2129,54 @@ int ragged_host_impl(srbdqp_ragged* r, int32_t B, size_t esz, const int32_t* N_p
 
 extern "C" {
 
+namespace {
+int ragged_forward_robots(srbdqp_ragged* r) {
+    for (size_t i = 0; i < r->hs.size(); ++i) {
+        const int rc = srbdqp_set_robots_device(r->hs[i], r->robots, (int32_t)r->robots_len);
+        if (rc != SRBDQP_OK) { r->err = std::string("bucket N=") + std::to_string(r->horizons[i]) + ": " + r->hs[i]->err; return rc; }
+    }
+    return SRBDQP_OK;
+}
+}  // namespace
+
+int srbdqp_ragged_set_robots(srbdqp_ragged* r, const srbdqp_robot* host, int32_t length) {
+    if (!r) return SRBDQP_E_INVALID;
+    if (host && length < 0) { r->err = "srbdqp_ragged_set_robots: negative length"; return SRBDQP_E_INVALID; }
+    const bool clear = !host || length == 0;
+    if (!clear) for (int hz : r->horizons) if (hz > kRobotsMaxHorizon) { r->err = std::string("bucket N=") + std::to_string(hz) + ": " + robots_n24; return SRBDQP_E_INVALID; }
+    if (!clear) {
+        const int rv = robots_validate(host, length, "srbdqp_ragged_set_robots", r->err);
+        if (rv != SRBDQP_OK) return rv;
+    }
+    RAG_TRY(r, hipSetDevice(r->device));
+    // every pass that may still read the records this call replaces has completed: the buckets' streams (and their handles' slots), the deferred passes on the
+    // tail streams, the object's own stream
+    for (auto* h : r->hs) { const int rq = robots_quiesce(h); if (rq != SRBDQP_OK) { r->err = h->err; return rq; } }
+    for (auto ts : r->tail_st) RAG_TRY(r, hipStreamSynchronize(ts));
+    RAG_TRY(r, hipStreamSynchronize(r->stream));
+    if (clear) { r->robots = nullptr; r->robots_len = 0; return ragged_forward_robots(r); }
+    if ((size_t)length > r->robots_cap) {
+        if (r->robots_own) RAG_TRY(r, hipFree(r->robots_own));
+        r->robots_own = nullptr; r->robots_cap = 0; r->robots = nullptr; r->robots_len = 0;
+        (void)ragged_forward_robots(r);
+        RAG_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->robots_own), sizeof(srbdqp_robot) * (size_t)length));
+        r->robots_cap = (size_t)length;
+    }
+    RAG_TRY(r, hipMemcpy(r->robots_own, host, sizeof(srbdqp_robot) * (size_t)length, hipMemcpyHostToDevice));
+    r->robots = r->robots_own; r->robots_len = (size_t)length;
+    return ragged_forward_robots(r);
+}
+
+int srbdqp_ragged_set_robots_device(srbdqp_ragged* r, const srbdqp_robot* dev, int32_t length) {
+    if (!r) return SRBDQP_E_INVALID;
+    if (dev && length < 0) { r->err = "srbdqp_ragged_set_robots_device: negative length"; return SRBDQP_E_INVALID; }
+    const bool clear = !dev || length == 0;
+    if (!clear) for (int hz : r->horizons) if (hz > kRobotsMaxHorizon) { r->err = std::string("bucket N=") + std::to_string(hz) + ": " + robots_n24; return SRBDQP_E_INVALID; }
+    r->robots = clear ? nullptr : dev;
+    r->robots_len = clear ? 0 : (size_t)length;
+    return ragged_forward_robots(r);
+}
+
 int srbdqp_ragged_flush(srbdqp_ragged* r, void* stream) {
     if (!r) return SRBDQP_E_INVALID;
     RAG_TRY(r, hipSetDevice(r->device));
@@ -2100,6 +2295,13 @@ int srbdqp_wbid_reference_device_f64(srbdqp_handle* h, int64_t B, const double* 
     a.x_next = x_next; a.u0 = u0; a.foot = foot; a.R = R; a.base_vel = base_vel; a.base_acc = base_acc; a.com_acc = com_acc;
     for (int i = 0; i < 3; ++i) a.iinv[i] = 1.0 / h->cfg.inertia[i];
     a.mass = h->cfg.mass;
+    if (h->robots) {        // robot b's own mass and inertia (srbdqp_set_robots): the fleet chain stays consistent with the QPs it solved
+        if ((size_t)B > h->robots_len) {
+            h->err = "srbdqp_wbid_reference: " + std::to_string(B) + " robots with " + std::to_string(h->robots_len) + " robot records set";
+            return SRBDQP_E_INVALID;
+        }
+        a.robots = reinterpret_cast<const double*>(h->robots);
+    }
     a.gravity = -9.80665;   // wbid.py:286
     a.as_written = as_written ? 1 : 0;
     a.B = (long long)B;

@@ -71,6 +71,7 @@ struct WbidRefArgs {
     double* com_acc;         // [B][3]   sum of forces / mass + gravity
     double iinv[3];          // inverse torso inertia diagonal (wbid.py:262-269)
     double mass, gravity;
+    const double* robots;    // per-robot records (srbdqp_robot, 8 doubles: mass, inertia[3], ...) in place of mass / iinv, or null
     int32_t as_written;      // 1: sum the forces exactly as wbid.py:290 does (reshape (3,4), see below); 0: per axis
     long long B;
 };
@@ -104,8 +105,10 @@ __global__ __launch_bounds__(256) void srbdqp_wbid_reference_kernel(WbidRefArgs 
             s2 += rx * x[7] - ry * x[6];
         }
         double* ba = a.base_acc + 6 * i;
+        double ji0 = a.iinv[0], ji1 = a.iinv[1], ji2 = a.iinv[2], mass = a.mass;
+        if (a.robots) { const double* rec = a.robots + 8 * i; mass = rec[0]; ji0 = 1.0 / rec[1]; ji1 = 1.0 / rec[2]; ji2 = 1.0 / rec[3]; }
         ba[0] = 0.0; ba[1] = 0.0; ba[2] = 0.0;
-        ba[3] = a.iinv[0] * s0; ba[4] = a.iinv[1] * s1; ba[5] = a.iinv[2] * s2;
+        ba[3] = ji0 * s0; ba[4] = ji1 * s1; ba[5] = ji2 * s2;
         // CoM linear acceleration = sum of forces / mass + gravity (wbid.py:287-291).  As written the reference sums
         // np.reshape(u_opt0, (3, 4)) along axis 1, i.e. the three groups of four CONSECUTIVE entries u[0:4], u[4:8],
         // u[8:12] rather than the x, y, z components of the four contacts; as_written = 1 reproduces that.
@@ -119,9 +122,9 @@ __global__ __launch_bounds__(256) void srbdqp_wbid_reference_kernel(WbidRefArgs 
             f1 = ((u[1] + u[4]) + u[7]) + u[10];
             f2 = ((u[2] + u[5]) + u[8]) + u[11];
         }
-        a.com_acc[3 * i] = f0 / a.mass;
-        a.com_acc[3 * i + 1] = f1 / a.mass;
-        a.com_acc[3 * i + 2] = f2 / a.mass + a.gravity;
+        a.com_acc[3 * i] = f0 / mass;
+        a.com_acc[3 * i + 1] = f1 / mass;
+        a.com_acc[3 * i + 2] = f2 / mass + a.gravity;
     }
 }
 

@@ -630,9 +630,30 @@ __device__ __forceinline__ void latp_dispatch(const int w, double* T, const doub
     else latp_run<3, NTC>(T, D0, acc0, acc1, acc2, misc, lane, stamps);
 }
 
+// A QP's own robot (MODE = 2, srbdqp_set_robots): its record -- srbdqp_robot of include/srbdqp.h as 8 doubles: mass, inertia[3], mu, fz_min, fz_max, reserved --
+// turned into what the launch-wide KArgs scalars hold for every other QP, and written to LDS behind the workgroup's layout (WrenchSmem::o_end, 8 doubles the
+// launcher adds): dst = [1 / mass, 1 / inertia[0 .. 2], mu, fz_min / s, fz_max / s, bad].  Read there where they are used, as the KArgs scalars are read from
+// the argument segment: held in scalar registers through the kernel they pushed the N = 20 / 24 instantiations (at the SGPR and VGPR limits already) into
+// scratch.  A record that does not describe a robot (srbdqp_set_robots' rules: every value finite, mass, inertia and mu > 0, 0 <= fz_min <= fz_max, reserved 0;
+// NaN fails every one) sets bad = 1: the QP is reported as SRBDQP_NUMERICAL with zero forces, and the values stored are the KArgs ones, so that nothing
+// computed on the way (J, the roll-out of zero forces) is non-finite.
+__device__ __forceinline__ void qp_robot_to_lds(const KArgs& a, const double* rec, double* dst) {
+    const double m = rec[0], j0 = rec[1], j1 = rec[2], j2 = rec[3], mu = rec[4], lo = rec[5], hi = rec[6], rs = rec[7];
+    constexpr double big = 1.0e300;
+    const bool ok = m > 0.0 && m < big && j0 > 0.0 && j0 < big && j1 > 0.0 && j1 < big && j2 > 0.0 && j2 < big && mu > 0.0 && mu < big &&
+                    lo >= 0.0 && lo <= hi && hi < big && rs == 0.0;
+    dst[0] = ok ? 1.0 / m : a.inv_mass;
+    dst[1] = ok ? 1.0 / j0 : a.iinv[0]; dst[2] = ok ? 1.0 / j1 : a.iinv[1]; dst[3] = ok ? 1.0 / j2 : a.iinv[2];
+    dst[4] = ok ? mu : a.mu;
+    dst[5] = ok ? lo / a.s : a.fzmin_s; dst[6] = ok ? hi / a.s : a.fzmax_s;
+    dst[7] = ok ? 0.0 : 1.0;
+}
+
 // One QP (index b) on one workgroup of NW waves.  TIO = element type of the caller's buffers, R = iteration type.
+// MODE: 0 = solve, 1 = assembly dump (srbdqp_assemble_wrench_f64), 2 = solve with the QP's own robot record robots[8 b .. 8 b + 8) (qp_robot_to_lds) in place
+// of KArgs::inv_mass / iinv / mu / fzmin_s / fzmax_s -- every use below reads (RB ? RBV[k] : a.<value>), so MODE 0 compiles to what it did without it.
 template <int N, typename R, typename TIO, int MODE, typename TT = double, int SPW = 5, int XW = 0>
-__device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* sm) {
+__device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* sm, const double* robots = nullptr) {
     using S = WrenchSmem<N, (int)sizeof(TT), SPW, XW>;
     typedef TT v4t __attribute__((ext_vector_type(4)));
     static_assert(sizeof(TT) == 8 || (sizeof(R) == 4 && MODE == 0), "fp32 tiles belong to the fp32 path");
@@ -641,6 +662,9 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     static_assert((S::o_R % 2) == 0 && (S::o_wb % 2) == 0 && (S::o_tb % 2) == 0 && (S::o_vb % 2) == 0, "16-byte alignment");
     static_assert(S::NT <= 2 * NW || S::WQ >= 1, "");
     const double rho_b = unis(SRBDQP_RHO_OF(a, b));   // (per-QP values are wave-uniform: scalar registers, see uni())
+    constexpr bool RB = MODE == 2;
+    static_assert(!RB || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && XW == 0), "per-QP robot records: the fp64 batch instantiation");
+    [[maybe_unused]] const double* const RBV = sm + S::o_end;        // MODE 2: the QP's robot (qp_robot_to_lds), from the first barrier on
     const int t = threadIdx.x, lane = t & 63;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     constexpr bool CSUM = XW > 0 && sizeof(TIO) == 8 && MODE == 0 && S::LT <= 256;   // the low-latency instantiations: the completion word may carry a checksum (KArgs::done_cs)
@@ -687,6 +711,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         if (t < N * 4) sct[t] = v_ct ? 1 : 0;
         if (a.pcom && t < N * 3) sm[S::o_pcom + t] = (double)v_pc;
         if (t == 0) { sm[S::o_misc] = 0.0; sm[S::o_misc + 1] = 0.0; }
+        if constexpr (RB) { if (t == 0) qp_robot_to_lds(a, robots + (size_t)b * 8, sm + S::o_end); }
         __syncthreads();
         if (!a.pcom && t < N * 3) sm[S::o_pcom + t] = sm[S::o_xref + (t / 3) * 13 + 3 + (t % 3)];
         if (t < N) {
@@ -727,7 +752,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             const int i = t;
             const int k = i / 12, cc = i - 12 * k, ci = cc / 3, ax = cc - 3 * ci;
             const double cs = sm[S::o_tm + k * 9 + 0], sn = sm[S::o_tm + k * 9 + 1];
-            const double i0 = a.iinv[0], i1 = a.iinv[1], i2 = a.iinv[2];
+            const double i0 = RB ? RBV[1] : a.iinv[0], i1 = RB ? RBV[2] : a.iinv[1], i2 = RB ? RBV[3] : a.iinv[2];
             const double w00 = cs * cs * i0 + sn * sn * i1, w01 = cs * sn * (i0 - i1), w11 = sn * sn * i0 + cs * cs * i1;
             const double rx = sm[S::o_foot + k * 12 + 3 * ci + 0] - sm[S::o_pcom + k * 3 + 0];
             const double ry = sm[S::o_foot + k * 12 + 3 * ci + 1] - sm[S::o_pcom + k * 3 + 1];
@@ -770,15 +795,17 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     lane_roles(lane);
 
     if constexpr (MODE == 1) { if (na == 0) return; }   // assembly dump of an empty problem: all zeros (the host cleared the buffers)
-    if (na == 0) {   // nothing to solve: all forces 0
+    [[maybe_unused]] bool rb_bad = false;
+    if constexpr (RB) rb_bad = unis(RBV[7]) != 0.0;
+    if (na == 0 || (RB && rb_bad)) {   // nothing to solve: all forces 0 (MODE 2, a record that is not a robot: the same, reported as SRBDQP_NUMERICAL)
         for (int c = t; c < n; c += BT) sm[S::o_xs + c] = 0.0;
         if (a.y_out) for (int i = t; i < m; i += BT) reinterpret_cast<TIO*>(a.y_out)[row0 * 20 + i] = TIO(0);
-        if (t == 0) { if (a.status) a.status[b] = 1; if (a.iters) a.iters[b] = 0; cs_host = done_cs_pack(1, 0); }
+        if (t == 0) { const int st0 = (RB && rb_bad) ? -1 : 1; if (a.status) a.status[b] = st0; if (a.iters) a.iters[b] = 0; cs_host = done_cs_pack(st0, 0); }
         __syncthreads();
     } else {
 
     // ================= tables of the closed-form assembly (a6 + a7; srbdqp_compact.hpp has the derivation) =================
-    const double dt = a.dt, dt2 = unis(a.dt * a.dt), dtm = unis(a.dt * a.inv_mass), dt2m = unis(dt2 * a.inv_mass);
+    const double dt = a.dt, dt2 = unis(a.dt * a.dt), dtm = unis(a.dt * (RB ? RBV[0] : a.inv_mass)), dt2m = unis(dt2 * (RB ? RBV[0] : a.inv_mass));
     double* T1 = sm + S::o_t1;
     double* T2 = sm + S::o_t2;
     double* MT = sm + S::o_mt;
@@ -994,7 +1021,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     }
 
     // ================= per-step wrench blocks: E^-1, V, Bd (registers of the step's lanes) =================
-    const double dxy = unis(a.rs2 + a.sigma + 2.0 * rho_b), dz = unis(a.rs2 + a.sigma + (4.0 * a.mu * a.mu + a.rho_fz) * rho_b);
+    const double dxy = unis(a.rs2 + a.sigma + 2.0 * rho_b), dz = unis(a.rs2 + a.sigma + (4.0 * (RB ? unis(RBV[4]) : a.mu) * (RB ? unis(RBV[4]) : a.mu) + a.rho_fz) * rho_b);
     const double idxy = unis(1.0 / dxy), idz = unis(1.0 / dz);
     // fp32 tiles (3 workgroups per CU, 168 registers): the rows / columns of V and Bd are formed AFTER the factorisation, from
     // the triangle of E^-1 kept in LDS behind the tiles, and held in fp32 from then on.  Formed here they waited in scratch
@@ -1002,7 +1029,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     // (rocprofv3 FETCH_SIZE / WRITE_SIZE, round 2).
     // (round 5: fp64 tiles too, for the instantiations compiled at 3 waves per SIMD -- N <= 12 in fp64, every fp32 instantiation on fp64 tiles -- where the
     //  triangle fits the LDS the workgroup has anyway, WrenchSmem::E4_FITS)
-    constexpr bool VBD_LATE = sizeof(TT) == 4 || (S::E4_FITS && MODE == 0 && (CHMAX <= 36 || sizeof(R) == 4));
+    constexpr bool VBD_LATE = sizeof(TT) == 4 || (S::E4_FITS && MODE != 1 && (CHMAX <= 36 || sizeof(R) == 4));
     typedef double VS;   // (x_q and its refinement need V and Bd in fp64: rounded to fp32 the refinement contracts 10 x slower)
     VS vrow[6], vcol[6];
     double bjv[4];                                                   // bjv: J[:, u] of the lane's variable and 1 / D_u (apply_kinv)
@@ -1784,10 +1811,10 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         for (int i = 0; i < BDN; ++i) bd[i] = BD_EXPLICIT ? (R)bdrow[i] : (R)bjv[i < 4 ? i : 0];
         const R xqr = (R)xq;
         const bool rowA = active_u, rowB = active_u && ax < 2;
-        const R sigma = uni((R)a.sigma), alpha = uni((R)a.alpha), oma = uni((R)(1.0 - a.alpha)), mu = uni((R)a.mu), irho = uni((R)(1.0 / rho_b));
+        const R sigma = uni((R)a.sigma), alpha = uni((R)a.alpha), oma = uni((R)(1.0 - a.alpha)), mu = uni((R)(RB ? RBV[4] : a.mu)), irho = uni((R)(1.0 / rho_b));
         const R irhoz = uni((R)(1.0 / (rho_b * a.rho_fz)));                  // slot A of the fz lane = the normal-force row: its own penalty
         const R rhoA = rowA ? ((ax < 2) ? (R)rho_b : (R)(rho_b * a.rho_fz)) : R(0), rhoB = rowB ? (R)rho_b : R(0);
-        const R loA = !rowA ? R(0) : (ax < 2 ? (R)-kInf : (R)a.fzmin_s), hiA = !rowA ? R(0) : (ax < 2 ? R(0) : (R)a.fzmax_s);
+        const R loA = !rowA ? R(0) : (ax < 2 ? (R)-kInf : (R)(RB ? RBV[5] : a.fzmin_s)), hiA = !rowA ? R(0) : (ax < 2 ? R(0) : (R)(RB ? RBV[6] : a.fzmax_s));
         const R loB = rowB ? (R)-kInf : R(0), hiB = R(0);
         const R mucA = (ax < 2) ? mu : R(0);
         auto At = [&](R wA, R wB) -> R {
@@ -1878,7 +1905,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                 if constexpr (VL) {   // (168 registers: the row classes as selects on scalar bounds -- eight registers of per-lane bounds less in the loop, which reloaded four values per iteration)
                     const R vA = fma(yA, (ax < 2) ? irho : irhoz, zhA), vB = fma(yB, irho, zhB);
                     znB = rowB ? rmin(vB, R(0)) : R(0);
-                    znA = rowA ? ((ax < 2) ? rmin(vA, R(0)) : rmin(rmax(vA, (R)a.fzmin_s), (R)a.fzmax_s)) : R(0);
+                    znA = rowA ? ((ax < 2) ? rmin(vA, R(0)) : rmin(rmax(vA, (R)(RB ? RBV[5] : a.fzmin_s)), (R)(RB ? RBV[6] : a.fzmax_s))) : R(0);
                 } else {
                     znA = rmin(rmax(fma(yA, (ax < 2) ? irho : irhoz, zhA), loA), hiA); znB = rmin(rmax(fma(yB, irho, zhB), loB), hiB);
                 }
@@ -1992,7 +2019,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     for (int c = 0; c < 12; ++c) s += J[c] * u[c];
                 } else {
                     const int ax2 = comp - 3;
-                    s = (u[ax2] + u[3 + ax2] + u[6 + ax2] + u[9 + ax2]) * a.inv_mass;
+                    s = (u[ax2] + u[3 + ax2] + u[6 + ax2] + u[9 + ax2]) * (RB ? RBV[0] : a.inv_mass);
                 }
                 sj[idx] = s;
             }
@@ -2079,6 +2106,29 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, SPW, XW>::BT), WPS) void srbdqp_w
     if ((!a.count_ptr || (int)blockIdx.x < *a.count_ptr) && !SRBDQP_RESTART_SKIP(a, SRBDQP_QP_INDEX(a)))
         wrench_qp<N, R, TIO, MODE, TT, SPW, XW>(a, SRBDQP_QP_INDEX(a), sm);
     signal_done(a);   // staged path: every workgroup of the launch reports once, with or without work (done_cs is for the *_in kernels only)
+}
+
+// ... MODE = 2: every QP with its own robot (srbdqp_set_robots / _device): robots = the handle's records, 8 doubles per QP in the CALLER's QP order (b, not the
+// workgroup: the same under a dispatch order, in a restart pass and in a ragged bucket).  A second kernel argument: KArgs keeps its size (the batch-1 *_in
+// kernels' argument segment, tests/test_aql_contract_cpu.py), and the restart, deferred and ragged launches that copy a KArgs reach it through the launcher.
+// (enable_if: the name with MODE = 0 / 1 keeps naming the one-argument kernel alone)
+template <int N, typename R, typename TIO, int MODE, int WPS, typename TT = double, int SPW = 5, int XW = 0, typename = std::enable_if_t<MODE == 2>>
+__global__ __launch_bounds__((WrenchSmem<N, 8, SPW, XW>::BT), WPS) void srbdqp_wrench_kernel(KArgs a, const double* __restrict__ robots) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    if ((int)blockIdx.x >= a.B) return;
+    // (the one-argument kernel's prologue, word for word, though an fp64 launch never sets tile_sel: without it hipcc allocates the N = 20 instantiation
+    //  -- 256 VGPRs, 106 SGPRs, like its MODE = 0 twin -- with 12 bytes per lane in scratch memory)
+    if (a.tile_sel) {
+        const uint32_t* cf = reinterpret_cast<const uint32_t*>(a.contact + (size_t)SRBDQP_QP_INDEX(a) * (N * 4));   // 4 flags per step
+        const int lane = threadIdx.x & 63;
+        const uint32_t v = cf[lane < N ? lane : 0];
+        const int nc = ((v & 0xffu) ? 1 : 0) + ((v & 0xff00u) ? 1 : 0) + ((v & 0xff0000u) ? 1 : 0) + ((v & 0xff000000u) ? 1 : 0);
+        const bool wrench_only = __ballot(lane < N && (nc == 1 || nc == 2)) == 0ull;
+        if (wrench_only != (a.tile_sel == 1)) return;
+    }
+    if ((!a.count_ptr || (int)blockIdx.x < *a.count_ptr) && !SRBDQP_RESTART_SKIP(a, SRBDQP_QP_INDEX(a)))
+        wrench_qp<N, R, TIO, MODE, TT, SPW, XW>(a, SRBDQP_QP_INDEX(a), sm, robots);
+    signal_done(a);
 }
 
 // ... the low-latency instantiation with the QP's inputs in the kernel-argument segment (StagedIn, srbdqp_common.hpp): one staged QP, first pass

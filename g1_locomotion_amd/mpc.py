@@ -25,7 +25,7 @@ try:                                    # CPython binding of the two batch-1 cal
     from . import _fastcall
 except ImportError:                     # pragma: no cover
     _fastcall = None
-from ._lib import NX, NU, NC, SrbdqpError
+from ._lib import NX, NU, NC, SrbdqpError, robots_array  # noqa: F401  (robots_array: the rows of set_robots)
 
 
 def _ptr(a: Optional[np.ndarray]):
@@ -37,6 +37,26 @@ _p = _ptr
 
 def _c(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _robots_arg(robots):
+    """set_robots' argument -> (address or None, length, object to keep alive or None, is_device).  A NumPy array (L, 8) float64 goes to the host setter
+    (copied), a CUDA float64 torch tensor (L, 8) to the device setter (read at every solve: the engine holds a reference to it), None clears."""
+    if robots is None:
+        return None, 0, None, False
+    if hasattr(robots, "data_ptr") and hasattr(robots, "is_cuda"):
+        import torch
+        if not robots.is_cuda or robots.dtype != torch.float64 or robots.dim() != 2 or robots.shape[1] != _lib.ROBOT_DOUBLES:
+            raise ValueError(f"set_robots: a torch tensor must be CUDA float64 of shape (L, {_lib.ROBOT_DOUBLES}), got {robots.dtype} {tuple(robots.shape)} "
+                             f"on {robots.device}")
+        if not robots.is_contiguous():
+            raise ValueError("set_robots: the tensor must be contiguous (its rows are read in place)")
+        return (C.c_void_p(robots.data_ptr()) if robots.shape[0] else None), int(robots.shape[0]), robots, True
+    arr = np.asarray(robots)
+    if arr.ndim != 2 or arr.shape[1] != _lib.ROBOT_DOUBLES:
+        raise ValueError(f"set_robots: expected shape (L, {_lib.ROBOT_DOUBLES}) (robots_array()), got {arr.shape}")
+    arr = np.ascontiguousarray(arr, dtype=np.float64)
+    return (_ptr(arr) if arr.shape[0] else None), int(arr.shape[0]), arr, False
 
 
 def _as(a, dtype, shape, name):
@@ -185,6 +205,16 @@ class BatchMPC:
             raise ValueError("set_schedule_hint: pass the number of entries of iters_prev (length > 0) with the pointer")
         _lib.check(self._lib.srbdqp_set_schedule_hint(self._h, C.c_void_p(int(iters_prev_ptr)) if iters_prev_ptr else None,
                                                       int(length) if iters_prev_ptr else 0), self._h)
+
+    def set_robots(self, robots):
+        """One robot per QP (include/srbdqp.h srbdqp_set_robots): robots = robots_array(...) rows (NumPy, copied by the library), a CUDA float64 torch
+        tensor (L, 8) (kept and read at every solve: leave it untouched until those solves have completed), or None (back to the config's robot).
+        While set, QP b of a solve uses row b; the fp64 solves run on the general kernel, wbid_reference() uses each robot's mass and inertia, and the
+        fp32, staged and assembly calls raise SrbdqpError."""
+        ptr, n, keep, dev = _robots_arg(robots)
+        fn = self._lib.srbdqp_set_robots_device if dev else self._lib.srbdqp_set_robots
+        _lib.check(fn(self._h, ptr, n), self._h)
+        self._robots = keep if dev else None
 
     def flush(self, stream=0):
         """FLAG_DEFER_TAIL: enqueue the continuations no later solve has picked up (srbdqp_flush); stream = a hipStream_t address, 0 = every
@@ -389,6 +419,13 @@ class RaggedMPC:
         else:
             fn = self._lib.srbdqp_solve_ragged_device_f32 if f32 else self._lib.srbdqp_solve_ragged_device_f64
             self._check(fn(self._h, int(B), _ptr(Nq), v(x0), v(x_ref), v(foot), v(contact), v(u_out), v(x_out), v(status), v(iters), v(stream)))
+
+    def set_robots(self, robots):
+        """One robot per QP, in the CALLER's QP order (srbdqp_ragged_set_robots): as BatchMPC.set_robots."""
+        ptr, n, keep, dev = _robots_arg(robots)
+        fn = self._lib.srbdqp_ragged_set_robots_device if dev else self._lib.srbdqp_ragged_set_robots
+        self._check(fn(self._h, ptr, n))
+        self._robots = keep if dev else None
 
     def flush(self, stream=0):
         """flags=FLAG_DEFER_TAIL: make `stream` (0 = the object's own) wait for the restart passes still running on the buckets' tail streams

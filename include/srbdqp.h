@@ -223,6 +223,17 @@ int srbdqp_assemble_wrench_f64(srbdqp_handle* h, int32_t B,
                                const uint8_t* contact, const double* pcom,
                                double* T_out, double* q_out, double* blocks_out, double* goff_out);
 
+/* Heterogeneous fleets: one robot per QP.  srbdqp_config holds ONE robot (mass, inertia, mu, fz_min, fz_max) for every QP of a
+ * handle; a record per QP overrides those five values for that QP (the reference reads the mass from its model, wbid.py:291, and
+ * takes mu as a constructor argument, wbid.py:17: they belong to the robot).  64 bytes, 8 doubles: */
+typedef struct srbdqp_robot {
+    double mass;          /* kg, > 0 */
+    double inertia[3];    /* torso inertia diagonal, > 0 */
+    double mu;            /* friction-pyramid coefficient, > 0 */
+    double fz_min, fz_max;/* stance normal-force bounds, 0 <= fz_min <= fz_max */
+    double reserved;      /* 0 */
+} srbdqp_robot;           /* every value finite */
+
 /* Ragged batches (BASELINE.json configs[4]: "Mixed horizon N in {8,12,16,24} with per-QP contact schedule (ragged batch,
  * bucketed kernel launch)").  One object holds an engine per horizon; a call takes the QPs in ANY order with their horizon
  * in N_per_qp[] (HOST array), sorts them into horizon buckets and launches every non-empty bucket on its own HIP stream --
@@ -269,6 +280,12 @@ int srbdqp_solve_ragged_warm_device_f32(srbdqp_ragged* r, int32_t B, const int32
                                         const float* x0, const float* x_ref, const float* foot, const uint8_t* contact,
                                         const float* warm_u, const float* warm_y,
                                         float* u_out, float* x_out, float* y_out, int32_t* status, int32_t* iters, void* stream);
+/* Per-QP robot records on a ragged object (srbdqp_robot, srbdqp_set_robots below: the same rules, checks and refusals).  Record b belongs to QP b of the
+ * CALLER's order -- not the bucket order -- and every bucket engine reads the same array.  An object with an N = 24 bucket is refused.  The host form copies once into a buffer of the object and waits for
+ * every bucket stream and tail stream before it replaces earlier records.  While records are set the fp64 ragged calls read them; a call of B > length
+ * QPs and the _f32 ragged calls return SRBDQP_E_INVALID. */
+int srbdqp_ragged_set_robots(srbdqp_ragged* r, const srbdqp_robot* host, int32_t length);
+int srbdqp_ragged_set_robots_device(srbdqp_ragged* r, const srbdqp_robot* dev, int32_t length);
 
 /* Longest-first scheduling hint for the DEVICE-buffer API only (the host-buffer and the staged calls ignore it):
  * `device_iters_prev` = the iters[] array (device memory, `length` entries) of the previous control step of the same
@@ -278,6 +295,29 @@ int srbdqp_solve_ragged_warm_device_f32(srbdqp_ragged* r, int32_t B, const int32
  * loop consecutive steps of a robot are strongly correlated; a wrong hint costs nothing but the reordering.  The
  * pointer is read at every solve; results, status[] and iters[] stay in the caller's QP order. */
 int srbdqp_set_schedule_hint(srbdqp_handle* h, const int32_t* device_iters_prev, int32_t length);
+
+/* Per-QP robot records (srbdqp_robot above).  srbdqp_set_robots: HOST records, `length` of them, copied into a device buffer the library owns.  Every record is checked first: on a bad one the call
+ * returns SRBDQP_E_INVALID, srbdqp_last_error names the first bad index, and the previous setting stays.  Before it replaces earlier records it does what
+ * srbdqp_synchronize does (flush, then wait) -- and waits for every other stream the handle has launched on: deferred restart passes read the old buffer.
+ * srbdqp_set_robots_device: DEVICE records the caller owns; the pointer is kept and read at every solve, so the array must stay untouched until the solves
+ * that read it have completed in stream order (the contract of the input arrays under SRBDQP_FLAG_DEFER_TAIL).  The kernel checks each record: a QP whose
+ * record breaks the rules above ends with SRBDQP_NUMERICAL and zero forces; the other QPs of the batch are not affected.
+ * host / dev NULL or length 0: back to srbdqp_config's robot for every QP.
+ *
+ * While records are set:
+ *   - QP b of a solve uses record b -- b the CALLER's index: the same under the schedule hint's dispatch order, in every restart or deferred pass;
+ *   - a solve of B > length QPs returns SRBDQP_E_INVALID and launches nothing;
+ *   - srbdqp_solve_batch_f64 / _device_f64 run on the general kernel (SRBDQP_KERNEL_WRENCH; AUTO routes every such call there: the 4-wave, split and
+ *     one-wave kernels do not read records, and an explicit SRBDQP_KERNEL_COMPACT / _SPLIT / _WAVE returns SRBDQP_E_INVALID with a message);
+ *   - these return SRBDQP_E_INVALID with a message: the _f32 calls (their instantiations hold no per-QP copy), the staged batch-1 calls
+ *     (srbdqp_solve_staged_f64, srbdqp_prepare_staged_f64 / srbdqp_solve_prepared_f64, srbdqp_update_f64: a single robot sets srbdqp_config instead), and
+ *     srbdqp_assemble_f64 / srbdqp_assemble_wrench_f64;
+ *   - srbdqp_wbid_reference_f64 / _device_f64 (srbdqp_cascade.h) use records[b].mass and .inertia for robot b (B > length: SRBDQP_E_INVALID);
+ *     srbdqp_mpc_inputs_* reads none of the five values and is unchanged.
+ * Without records every call behaves as it always has.  Horizons 4 ... 20: the setters refuse an N = 24 handle with SRBDQP_E_INVALID (no instantiation of
+ * the general kernel reads records there without scratch memory). */
+int srbdqp_set_robots(srbdqp_handle* h, const srbdqp_robot* host, int32_t length);
+int srbdqp_set_robots_device(srbdqp_handle* h, const srbdqp_robot* dev, int32_t length);
 
 /* SRBDQP_FLAG_DEFER_TAIL: complete what earlier device-buffer solves on `stream` (a hipStream_t; NULL = every stream this handle has
  * launched on) left for later -- the one-wave kernel's continuations that no later solve has picked up (one launch of the

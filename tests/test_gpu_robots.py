@@ -1,0 +1,370 @@
+"""GPU tests of the per-QP robot records (include/srbdqp.h srbdqp_robot, srbdqp_set_robots / _device, srbdqp_ragged_set_robots / _device):
+every QP of a batch with its own mass, inertia, friction coefficient and normal-force bounds, on the general kernel's MODE = 2 instantiation.
+
+Tolerances are the ones of tests/test_gpu_wrench.py::test_wrench_f64_matches_oracle_and_exact_optimum, per QP against the oracle run with THAT QP's
+parameters: same status, iterations within one check interval, forces <= 2e-3 N from the twin (orc.update), roll-out <= 1e-5, solved QPs <= 5e-2 N from
+the exact optimum (orc.solve_reference; or within 2e-3 N of the twin's own distance from it where that is larger) with its KKT bars, swing forces and
+duals exactly 0.  The engine keeps its default rho restart; the oracle runs
+the same one (orc.default_restart)."""
+import numpy as np
+import pytest
+
+import srbd_oracle as orc
+
+pytestmark = pytest.mark.gpu
+
+TOL_TWIN_N = 2e-3
+TOL_EXACT_N = 5e-2
+HORIZONS = (4, 8, 10, 12, 16, 20)          # (N = 24: the setters refuse it, test_n24_is_refused)
+SCHEDULES = ("single", "double", "mixed", "three")
+
+
+@pytest.fixture(scope="module")
+def torch_first():
+    import torch  # load torch's HIP runtime before libsrbdqp.so so both share one
+    assert torch.cuda.is_available()
+    return torch
+
+
+def _batch(B, N, seed, schedule):
+    """As tests/test_gpu_wrench.py::_batch builds them ("three": steps with exactly 3 stance contacts)."""
+    x0, xr, ft, ct = orc.synthetic_batch(B, N, seed=seed, schedule="mixed" if schedule == "three" else schedule)
+    if schedule == "three":
+        rng = np.random.default_rng(seed)
+        for b in range(B):
+            for k in range(N):
+                if ct[b, k].sum() == 4 or rng.random() < 0.3:
+                    ct[b, k] = 1
+                    ct[b, k, rng.integers(0, 4)] = 0
+    return x0, xr, ft, ct
+
+
+def _draw(B, seed):
+    """B records: mass 0.7 - 1.5 x nominal, each inertia axis 0.6 - 1.6 x, mu 0.3 - 1.0, fz_min 0 - 20 N, fz_max 150 - 1200 N."""
+    from g1_locomotion_amd.mpc import robots_array
+    p = orc.SrbdParams()
+    rng = np.random.default_rng(seed)
+    return robots_array(B, mass=p.mass * rng.uniform(0.7, 1.5, B), inertia=np.asarray(p.inertia) * rng.uniform(0.6, 1.6, (B, 3)),
+                        mu=rng.uniform(0.3, 1.0, B), fz_min=rng.uniform(0.0, 20.0, B), fz_max=rng.uniform(150.0, 1200.0, B))
+
+
+def _params(N, rec):
+    r_iter, r_count = orc.default_restart(N)
+    return orc.params_for(N, mass=float(rec[0]), inertia=tuple(float(v) for v in rec[1:4]), mu=float(rec[4]), fz_min=float(rec[5]),
+                          fz_max=float(rec[6]), rho_restart_iter=r_iter, rho_restart_count=r_count)
+
+
+def _check_qp(out, b, N, p, x0, xr, ft, ct):
+    ref = orc.update(p, x0[b], xr[b], ft[b], ct[b])
+    assert out["status"][b] == ref["status"] and ref["status"] in (orc.STATUS_SOLVED, orc.STATUS_MAX_ITER), (b, out["status"][b], ref["status"])
+    assert abs(int(out["iters"][b]) - ref["iters"]) <= p.check_every, (b, out["iters"][b], ref["iters"])
+    assert np.abs(out["u"][b] - ref["u"]).max() <= TOL_TWIN_N, (b, np.abs(out["u"][b] - ref["u"]).max())
+    assert np.abs(out["x"][b] - ref["x"]).max() <= 1e-5
+    kq, vi, ri = orc.presolve(ref["qp"], ct[b])
+    if ref["status"] == orc.STATUS_SOLVED:
+        xs, ys = orc.solve_reference(p, ref["qp"])
+        # (a drawn robot whose ADMM solution -- the oracle twin's too -- stops farther than 5e-2 N from the optimum at eps 1e-6 is held to the twin's
+        #  own distance: one QP of N = 20 single support, 0.0503 N on the GPU and the twin alike)
+        twin_gap = np.abs(ref["u"].reshape(-1) - xs * p.force_scale).max()
+        assert np.abs(out["u"][b].reshape(-1) - xs * p.force_scale).max() <= max(TOL_EXACT_N, twin_gap + TOL_TWIN_N)
+        kr = orc.kkt_residuals(kq["P"], kq["q"], kq["A"], kq["l"], kq["u"], out["u"][b].reshape(-1)[vi] / p.force_scale, out["y"][b][ri])
+        assert kr["primal"] <= 1e-4 and kr["stationarity"] <= 1e-3 * max(1.0, np.abs(ref["qp"]["q"]).max()), kr
+    off = np.setdiff1d(np.arange(12 * N), vi)
+    assert np.all(out["u"][b].reshape(-1)[off] == 0.0)
+    offr = np.setdiff1d(np.arange(20 * N), ri)
+    assert np.all(out["y"][b][offr] == 0.0)
+
+
+def _bound_active(u, ct, rec, tol=0.05):
+    """A stance contact of some step on a friction-pyramid row (|f_x| or |f_y| = mu f_z) or on fz_max."""
+    f = u.reshape(-1, 4, 3)
+    st = ct.reshape(-1, 4) != 0
+    fz = f[..., 2]
+    fric = (np.maximum(np.abs(f[..., 0]), np.abs(f[..., 1])) >= rec[4] * fz - tol) & (fz > tol)
+    top = fz >= rec[6] - tol
+    return bool(np.any(st & (fric | top)))
+
+
+@pytest.mark.parametrize("schedule", SCHEDULES)
+@pytest.mark.parametrize("N", HORIZONS)
+def test_per_qp_records_match_the_oracle(torch_first, built_lib, N, schedule):
+    from g1_locomotion_amd import BatchMPC
+    B = 32
+    x0, xr, ft, ct = _batch(B, N, 900 + N, schedule)
+    rec = _draw(B, 1900 + N)
+    with BatchMPC(horizon=N) as eng:
+        out0 = eng.solve(x0, xr, ft, ct)                             # nominal robot (the config's) for every QP
+        eng.set_robots(rec)
+        out = eng.solve(x0, xr, ft, ct, want_y=True)
+        assert eng.kernel_name() == f"wrench_f64_n{N}_rb", eng.kernel_name()
+    moved = 0
+    for b in range(B):
+        _check_qp(out, b, N, _params(N, rec[b]), x0, xr, ft, ct)
+        moved += int(np.abs(out["u"][b] - out0["u"][b]).max() > 1.0)
+    assert moved >= B // 4, f"only {moved} of {B} QPs moved by > 1 N from the nominal robot's solution"
+
+
+def test_records_reach_the_kernel_through_the_bounds(torch_first, built_lib):
+    """In at least a quarter of the QPs the solution moves by > 1 N from the nominal robot's AND a friction-pyramid or fz_max row of the QP's own record is
+    active in it (N = 4 alone has few of those: its short horizon rarely pushes a force to a bound; 4 - 8 of 32 QPs in the oracle)."""
+    from g1_locomotion_amd import BatchMPC
+    B, moved, total = 32, 0, 0
+    for N in (8, 10, 12, 16):
+        for schedule in ("double", "mixed"):
+            x0, xr, ft, ct = _batch(B, N, 900 + N, schedule)
+            rec = _draw(B, 1900 + N)
+            with BatchMPC(horizon=N) as eng:
+                out0 = eng.solve(x0, xr, ft, ct)
+                eng.set_robots(rec)
+                out = eng.solve(x0, xr, ft, ct)
+            for b in range(B):
+                total += 1
+                moved += int(np.abs(out["u"][b] - out0["u"][b]).max() > 1.0 and _bound_active(out["u"][b], ct[b], rec[b]))
+    assert moved >= total // 4, (moved, total)
+
+
+@pytest.mark.parametrize("N,schedule", [(4, "double"), (10, "mixed"), (10, "single"), (16, "double"), (20, "three")])
+def test_uniform_records_equal_the_config(torch_first, built_lib, N, schedule):
+    """Every record = the handle's config: the same QPs as a KERNEL_WRENCH solve without records (statuses and iteration counts identical, forces within
+    1e-9 N).  The MODE = 2 kernel computes 1 / mass, fz / s ... with the same operations fill_args() uses on the host, so the forces come out bit-identical."""
+    from g1_locomotion_amd import BatchMPC, _lib
+    from g1_locomotion_amd.mpc import robots_array
+    B = 48
+    x0, xr, ft, ct = _batch(B, N, 700 + N, schedule)
+    with BatchMPC(horizon=N, kernel=_lib.KERNEL_WRENCH) as eng:
+        ref = eng.solve(x0, xr, ft, ct, want_y=True)
+        eng.set_robots(robots_array(B, cfg=eng.cfg))
+        out = eng.solve(x0, xr, ft, ct, want_y=True)
+        assert eng.kernel_name() == f"wrench_f64_n{N}_rb"
+    assert np.array_equal(out["status"], ref["status"]) and np.array_equal(out["iters"], ref["iters"])
+    assert np.abs(out["u"] - ref["u"]).max() <= 1e-9 and np.abs(out["x"] - ref["x"]).max() <= 1e-9
+    assert np.array_equal(out["u"], ref["u"]) and np.array_equal(out["x"], ref["x"]) and np.array_equal(out["y"], ref["y"])   # bit-identical
+
+
+def _device_solve(torch, eng, t, B, stream=None):
+    o = dict(u=torch.empty((B, eng.N, 12), dtype=torch.float64, device="cuda"), x=torch.empty((B, eng.N + 1, 13), dtype=torch.float64, device="cuda"),
+             status=torch.empty(B, dtype=torch.int32, device="cuda"), iters=torch.empty(B, dtype=torch.int32, device="cuda"))
+    eng.solve_device(B, t["x0"].data_ptr(), t["xr"].data_ptr(), t["ft"].data_ptr(), t["ct"].data_ptr(), o["u"].data_ptr(), o["x"].data_ptr(),
+                     status=o["status"].data_ptr(), iters=o["iters"].data_ptr(), stream=stream or torch.cuda.current_stream().cuda_stream)
+    return o
+
+
+def _to_dev(torch, x0, xr, ft, ct):
+    return dict(x0=torch.from_numpy(x0).cuda(), xr=torch.from_numpy(xr).cuda(), ft=torch.from_numpy(ft).cuda(), ct=torch.from_numpy(ct.astype(np.uint8)).cuda())
+
+
+def test_schedule_hint_keeps_records_by_qp_index(torch_first, built_lib):
+    torch = torch_first
+    from g1_locomotion_amd import BatchMPC
+    B, N = 256, 10
+    x0, xr, ft, ct = _batch(B, N, 31, "mixed")
+    rec = _draw(B, 32)
+    t = _to_dev(torch, x0, xr, ft, ct)
+    with BatchMPC(horizon=N) as eng:
+        eng.set_robots(rec)
+        plain = _device_solve(torch, eng, t, B)
+        torch.cuda.synchronize()
+        hint = torch.from_numpy(np.random.default_rng(5).integers(0, 250, B).astype(np.int32)).cuda()   # a hint that reorders
+        eng.set_schedule_hint(hint.data_ptr(), B)
+        hinted = _device_solve(torch, eng, t, B)
+        torch.cuda.synchronize()
+        eng.set_schedule_hint(0, 0)
+    for k in ("u", "x", "status", "iters"):
+        assert torch.equal(plain[k], hinted[k]), k
+
+
+def _ragged_inputs(B, horizons, seed):
+    rng = np.random.default_rng(seed)
+    Nq = rng.choice(horizons, B).astype(np.int32)
+    X0, XR, FT, CT = [], [], [], []
+    for i, N in enumerate(Nq):
+        x0, xr, ft, ct = _batch(1, int(N), seed * 1000 + i, ("single", "double", "mixed", "three")[i % 4])
+        X0.append(x0[0]); XR.append(xr[0]); FT.append(ft[0]); CT.append(ct[0])
+    return Nq, np.stack(X0), np.concatenate(XR), np.concatenate(FT), np.concatenate(CT)
+
+
+def _ragged_run(torch, rg, Nq, t, B, rows):
+    u = torch.empty((rows, 12), dtype=torch.float64, device="cuda"); x = torch.empty((rows + B, 13), dtype=torch.float64, device="cuda")
+    st = torch.empty(B, dtype=torch.int32, device="cuda"); it = torch.empty(B, dtype=torch.int32, device="cuda")
+    rg.solve_device(B, Nq, t["x0"].data_ptr(), t["xr"].data_ptr(), t["ft"].data_ptr(), t["ct"].data_ptr(), u.data_ptr(), x.data_ptr(), st.data_ptr(),
+                    it.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    return dict(u=u, x=x, status=st, iters=it)
+
+
+@pytest.mark.parametrize("defer", [False, True])
+def test_ragged_records_follow_the_callers_order(torch_first, built_lib, defer):
+    """Horizons {8, 12, 16}, the QPs shuffled across the buckets: QP b of the caller's order solves with record b (against the oracle per QP); with
+    SRBDQP_FLAG_DEFER_TAIL the same call equals it after the flush."""
+    torch = torch_first
+    from g1_locomotion_amd import RaggedMPC, _lib
+    horizons = (8, 12, 16)
+    B = 40
+    Nq, x0, xr, ft, ct = _ragged_inputs(B, horizons, 77)
+    rec = _draw(B, 78)
+    off = np.concatenate([[0], np.cumsum(Nq)])
+    rows = int(off[-1])
+    t = _to_dev(torch, x0, xr, ft, ct)
+    rg = RaggedMPC(horizons=horizons)
+    try:
+        rg.set_robots(rec)
+        out = _ragged_run(torch, rg, Nq, t, B, rows)
+        torch.cuda.synchronize()
+    finally:
+        rg.close()
+    out = {k: v.cpu().numpy() for k, v in out.items()}
+    if defer:
+        rgd = RaggedMPC(horizons=horizons, flags=_lib.FLAG_DEFER_TAIL)
+        try:
+            rgd.set_robots(torch.from_numpy(rec).cuda())              # (the device setter: read in place, beside the deferred passes too)
+            dout = _ragged_run(torch, rgd, Nq, t, B, rows)
+            rgd.flush(torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+        finally:
+            rgd.close()
+        for k in ("u", "x", "status", "iters"):
+            assert np.array_equal(dout[k].cpu().numpy(), out[k]), k
+        return
+    for b in range(B):
+        N = int(Nq[b])
+        p = _params(N, rec[b])
+        ref = orc.update(p, x0[b], xr[off[b]:off[b + 1]], ft[off[b]:off[b + 1]], ct[off[b]:off[b + 1]])
+        assert out["status"][b] == ref["status"], (b, N, out["status"][b], ref["status"])
+        assert abs(int(out["iters"][b]) - ref["iters"]) <= p.check_every, (b, N, out["iters"][b], ref["iters"])
+        assert np.abs(out["u"][off[b]:off[b + 1]] - ref["u"]).max() <= TOL_TWIN_N, (b, N)
+        assert np.abs(out["x"][off[b] + b:off[b + 1] + b + 1] - ref["x"]).max() <= 1e-5, (b, N)
+
+
+def test_host_and_device_setters_agree_and_a_bad_device_record_stays_local(torch_first, built_lib):
+    torch = torch_first
+    from g1_locomotion_amd import BatchMPC, _lib
+    B, N = 64, 12
+    x0, xr, ft, ct = _batch(B, N, 41, "mixed")
+    rec = _draw(B, 42)
+    with BatchMPC(horizon=N) as eng:
+        eng.set_robots(rec)
+        host = eng.solve(x0, xr, ft, ct, want_y=True)
+        dev_rec = torch.from_numpy(rec).cuda()
+        eng.set_robots(dev_rec)
+        dev = eng.solve(x0, xr, ft, ct, want_y=True)
+        for k in ("u", "x", "y", "status", "iters"):
+            assert np.array_equal(host[k], dev[k]), k
+        bad = rec.copy()
+        bad[3, 0] = 0.0                 # mass <= 0
+        bad[17, 4] = np.nan             # mu NaN
+        bad[40, 6] = 5.0                # fz_max < fz_min
+        dev_bad = torch.from_numpy(bad).cuda()
+        eng.set_robots(dev_bad)
+        out = eng.solve(x0, xr, ft, ct, want_y=True)
+    for b in range(B):
+        if b in (3, 17, 40):
+            assert out["status"][b] == _lib.NUMERICAL and out["iters"][b] == 0, (b, out["status"][b])
+            assert np.all(out["u"][b] == 0.0) and np.all(out["y"][b] == 0.0) and np.all(np.isfinite(out["x"][b]))
+        else:
+            assert out["status"][b] == host["status"][b] and np.array_equal(out["u"][b], host["u"][b]), b
+
+
+def test_refusals_and_clearing(torch_first, built_lib):
+    from g1_locomotion_amd import BatchMPC, RaggedMPC, SrbdqpError, _lib
+    from g1_locomotion_amd.mpc import robots_array
+    B, N = 16, 10
+    x0, xr, ft, ct = _batch(B, N, 51, "double")
+    rec = _draw(B, 52)
+    with BatchMPC(horizon=N) as fresh:
+        ref = fresh.solve(x0, xr, ft, ct, want_y=True)
+        ref_name = fresh.kernel_name()
+    with BatchMPC(horizon=N) as eng:
+        eng.set_robots(rec[:B - 1])
+        with pytest.raises(SrbdqpError, match="robot records"):          # B > length
+            eng.solve(x0, xr, ft, ct)
+        bad = rec.copy()
+        bad[5, 1] = -1.0
+        with pytest.raises(SrbdqpError, match="record 5 is invalid"):
+            eng.set_robots(bad)
+        eng.solve(x0[:B - 1], xr[:B - 1], ft[:B - 1], ct[:B - 1])         # the previous setting was kept
+        eng.set_robots(rec)
+        with pytest.raises(SrbdqpError, match="refused"):
+            eng.solve(x0, xr, ft, ct, dtype=np.float32)
+        with pytest.raises(SrbdqpError, match="refused"):
+            eng.assemble_wrench(x0, xr, ft, ct)
+        with pytest.raises(SrbdqpError, match="refused"):
+            eng.solve_staged(1)
+        with pytest.raises(SrbdqpError, match="refused"):
+            eng.prepare_staged(1)
+        st = eng.stage()
+        assert st is not None
+        raw = _lib.load()
+        u0 = np.zeros(12)
+        assert raw.srbdqp_update_f64(eng._h, x0[0].ctypes.data, xr[0].ctypes.data, ft[0].ctypes.data, ct[0].astype(np.uint8).ctypes.data, None,
+                                     u0.ctypes.data, None, None, None, None) == _lib.E_INVALID
+        eng.set_robots(None)
+        out = eng.solve(x0, xr, ft, ct, want_y=True)                      # after clearing: exactly as a fresh handle
+        assert eng.kernel_name() == ref_name
+        for k in ("u", "x", "y", "status", "iters"):
+            assert np.array_equal(out[k], ref[k]), k
+    with BatchMPC(horizon=N) as eng:
+        with pytest.raises(SrbdqpError, match="refused"):
+            eng.set_robots(rec)
+            eng.assemble(x0, xr, ft, ct)
+    for kern in (_lib.KERNEL_COMPACT, _lib.KERNEL_SPLIT, _lib.KERNEL_WAVE):
+        with BatchMPC(horizon=N, kernel=kern) as eng:
+            eng.set_robots(rec)
+            with pytest.raises(SrbdqpError, match="general kernel only"):
+                eng.solve(x0, xr, ft, ct)
+    rg = RaggedMPC(horizons=(8, 12))
+    try:
+        Nq, rx0, rxr, rft, rct = _ragged_inputs(6, (8, 12), 53)
+        rg.set_robots(robots_array(5))
+        with pytest.raises(SrbdqpError, match="robot records"):
+            rg.solve_packed(Nq, rx0, rxr, rft, rct)
+        rg.set_robots(robots_array(6))
+        with pytest.raises(SrbdqpError, match="refused"):
+            rg.solve_packed(Nq, rx0, rxr, rft, rct, dtype=np.float32)
+        bad = robots_array(6)
+        bad[2, 7] = 1.0
+        with pytest.raises(SrbdqpError, match="record 2 is invalid"):
+            rg.set_robots(bad)
+        rg.set_robots(None)
+        rg.solve_packed(Nq, rx0, rxr, rft, rct, dtype=np.float32)
+    finally:
+        rg.close()
+
+
+def test_wbid_reference_uses_each_robots_mass_and_inertia(torch_first, built_lib):
+    import cascade_oracle as co
+    from g1_locomotion_amd import BatchMPC
+    B = 24
+    rng = np.random.default_rng(61)
+    x = rng.normal(size=(B, 13)); x[:, 12] = -9.81
+    u = rng.uniform(-50, 300, size=(B, 12)); f = rng.normal(size=(B, 12))
+    rec = _draw(B, 62)
+    with BatchMPC(horizon=10) as eng:
+        eng.set_robots(rec)
+        got = eng.wbid_reference(x, u, f)
+    for b in range(B):
+        ref = co.wbid_reference(x[b], u[b], f[b].reshape(4, 3), rec[b, 0], tuple(rec[b, 1:4]))
+        for k in ("R", "base_vel", "base_acc", "com_acc"):
+            np.testing.assert_allclose(got[k][b].reshape(ref[k].shape), ref[k], rtol=1e-12, atol=1e-12, err_msg=f"{k} of robot {b}")
+
+
+def test_n24_is_refused(torch_first, built_lib):
+    """No instantiation of the general kernel reads records at N = 24 without scratch memory: the setters refuse an N = 24 handle and a ragged object
+    with an N = 24 bucket, and nothing changes on either."""
+    torch = torch_first
+    from g1_locomotion_amd import BatchMPC, RaggedMPC, SrbdqpError
+    from g1_locomotion_amd.mpc import robots_array
+    rec = robots_array(4)
+    with BatchMPC(horizon=24) as eng:
+        with pytest.raises(SrbdqpError, match="N = 24"):
+            eng.set_robots(rec)
+        with pytest.raises(SrbdqpError, match="N = 24"):
+            eng.set_robots(torch.from_numpy(rec).cuda())
+        eng.set_robots(None)
+        x0, xr, ft, ct = _batch(4, 24, 3, "mixed")
+        assert eng.solve(x0, xr, ft, ct)["status"].shape == (4,)
+        assert eng.kernel_name() == "wrench_f64_n24"
+    rg = RaggedMPC(horizons=(8, 24))
+    try:
+        with pytest.raises(SrbdqpError, match="N=24"):
+            rg.set_robots(rec)
+    finally:
+        rg.close()
