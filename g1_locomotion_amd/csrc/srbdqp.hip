@@ -11,6 +11,8 @@
 #include <atomic>
 #include <chrono>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <unordered_set>
 #include <vector>
 
@@ -29,8 +31,6 @@ using srbdqp::KArgs;
 
 struct srbdqp_handle {
     srbdqp_config cfg;
-    int maxs_override = 0;         // set by the host-buffer API after scanning the contact flags
-    bool io_f32 = false;           // set around a launch by the _f32 entry points: the caller's buffers are float
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_mid = nullptr;   // ev_mid: between the two kernels of the split pipeline
     bool ev_valid = false, ev_mid_valid = false;
@@ -84,17 +84,9 @@ struct srbdqp_handle {
     int32_t* done_dev = nullptr;
     int32_t* done_count = nullptr;
     int32_t done_seq = 0;
-    bool signal_next = false;      // set by srbdqp_solve_staged_f64 around its launch
     bool done_cs = false;          // the last launch publishes its completion word with the checksum of its outputs (KArgs::done_cs): wait_done() verifies it
     bool done_cs_x = false;        // ... which cover x_out
-    bool staged_call = false;      // inside srbdqp_solve_staged_f64 (with or without the completion word)
-    int staged_neff = 0;           // ... with the largest number of presolved variables (3 x stance contacts) among its QPs
-    bool lazy_restart = false;     // staged path: run only the first pass; the host starts the second one if a status asks for it
-    bool lazy_pending = false;     // ... and the last solve really was such a first pass: last_args are its arguments,
-    int lazy_rcount = 1;           //     this many restart passes may follow it,
-    StreamSlot* lazy_slot = nullptr;   //  with the buffers of this launch-stream slot
     int32_t prepared_B = 0; int prepared_maxs = 4; bool prepared_pcom = false;   // two-phase call: a set-up is pending
-    KArgs last_args;               // arguments of that first pass (for the lazily started second pass)
     // kernels whose dynamic-LDS limit has been raised on this handle's device (function attributes are per device, and a
     // process may hold handles on several)
     std::unordered_set<const void*> lds_attr_done;
@@ -145,18 +137,89 @@ __global__ __launch_bounds__(1024) void srbdqp_schedule_kernel(const int32_t* it
 
 std::string g_create_err;
 
-#define HIP_TRY(h, call)                                                                         \
+// a HIP call that must succeed; on failure o->err (a handle or a ragged object) names it
+#define HIP_TRY(o, call)                                                                         \
     do {                                                                                         \
         hipError_t e_ = (call);                                                                  \
         if (e_ != hipSuccess) {                                                                  \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                        \
+            (o)->err = std::string(#call) + ": " + hipGetErrorString(e_);                        \
             return SRBDQP_E_HIP;                                                                 \
         }                                                                                        \
     } while (0)
 
 // horizons with an instantiation (the 4-wave compact kernel: N in {4, 8, 10} with up to 4 stance contacts per step, N in
 // {12, 16, 20} with at most 2; the one-wave kernel: <= 64 presolved variables; the general kernel: every horizon and pattern)
-bool horizon_supported(int N) { return N == 4 || N == 8 || N == 10 || N == 12 || N == 16 || N == 20 || N == 24; }
+using Horizons = std::integer_sequence<int, 4, 8, 10, 12, 16, 20, 24>;
+
+template <int... Ns>
+constexpr bool horizon_in(int N, std::integer_sequence<int, Ns...>) { return ((N == Ns) || ...); }
+bool horizon_supported(int N) { return horizon_in(N, Horizons{}); }
+
+// f(std::integral_constant<int, N>{}) for the handle's horizon N: the one place a run-time horizon becomes a template argument
+template <class F, int... Ns>
+int with_horizon_in(srbdqp_handle* h, F&& f, std::integer_sequence<int, Ns...>) {
+    int rc = SRBDQP_E_INVALID;
+    if (!((h->cfg.horizon == Ns && ((rc = f(std::integral_constant<int, Ns>{})), true)) || ...)) h->err = "unsupported horizon";
+    return rc;
+}
+template <class F>
+int with_horizon(srbdqp_handle* h, F&& f) { return with_horizon_in(h, f, Horizons{}); }
+
+// staged path, a multi-pass solve of which only the first pass ran: its arguments, how many restart passes may follow it, the launch-stream slot whose
+// buffers they use (the host starts the next pass if a status asks for it)
+struct Lazy {
+    KArgs a1;
+    int rcount = 1;
+    srbdqp_handle::StreamSlot* slot = nullptr;
+    bool pending = false;          // the solve really was such a first pass (not: restarted in place, or no restart at all)
+};
+
+// what one call decides, on the caller's stack: every launch of the call -- restart passes included -- reads the same one, so a later pass chooses the
+// kernel the first one did
+struct Call {
+    bool f32 = false;              // the caller's buffers are float
+    int maxs = 4;                  // bound on the stance contacts per step the instantiation is chosen for
+    bool staged = false;           // srbdqp_solve_staged_f64 (with or without the completion word)
+    int neff = 0;                  // ... with the largest number of presolved variables (3 x stance contacts) among its QPs
+    bool signal = false;           // the launch publishes the completion word
+    bool use_hint = false;         // the dispatch hint applies (it belongs to the device-buffer API)
+    Lazy* lazy = nullptr;          // staged path: run only the first pass of a multi-pass solve and hand it back here
+};
+
+inline int maxs_or(const srbdqp_config& c, int fallback) { return c.max_contacts_per_step > 0 ? c.max_contacts_per_step : fallback; }
+
+// stance contacts of B QPs' host-side flags: the most in one step, and the most presolved variables (3 per stance contact) of one QP.  !want_neff: stops
+// once a step has more than 2 (all the instantiation choice needs)
+struct Contacts {
+    int worst = 0, neff = 0;
+    int maxs() const { return worst <= 2 ? 2 : 4; }
+};
+Contacts scan_contacts(const uint8_t* c, size_t B, size_t N, bool want_neff) {
+    Contacts r;
+    for (size_t b = 0; b < B && (want_neff || r.worst <= 2); ++b) {
+        int na = 0;
+        for (size_t q = b * N; q < (b + 1) * N; ++q) {
+            const int cnt = (c[4 * q] != 0) + (c[4 * q + 1] != 0) + (c[4 * q + 2] != 0) + (c[4 * q + 3] != 0);
+            if (cnt > r.worst) r.worst = cnt;
+            na += cnt;
+        }
+        if (3 * na > r.neff) r.neff = 3 * na;
+    }
+    return r;
+}
+
+// grow a device buffer to at least `want` elements (its contents are not kept); `busy`: a stream that may still use the old one
+template <class O, class T>
+int grow(O* o, T*& buf, size_t& cap, size_t want, hipStream_t busy, const char* what) {
+    if (want <= cap) return SRBDQP_OK;
+    if (busy) HIP_TRY(o, hipStreamSynchronize(busy));
+    if (buf) HIP_TRY(o, hipFree(buf));
+    buf = nullptr; cap = 0;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), want * sizeof(T));
+    if (e != hipSuccess) { o->err = std::string(what) + ": " + hipGetErrorString(e); return SRBDQP_E_NOMEM; }
+    cap = want;
+    return SRBDQP_OK;
+}
 
 int resolve_kernel(const srbdqp_config& c) {
     if (c.kernel == SRBDQP_KERNEL_WRENCH) return SRBDQP_KERNEL_WRENCH;
@@ -184,6 +247,18 @@ void fill_args(const srbdqp_config& c, KArgs& a) {
     a.eps_rel = c.eps_rel;
 }
 
+// arguments of a solve of B QPs: the config's constants and the inputs, everything else zero
+KArgs base_args(const srbdqp_config& c, int32_t B, const void* x0 = nullptr, const void* x_ref = nullptr, const void* foot = nullptr,
+                const uint8_t* contact = nullptr, const void* pcom = nullptr) {
+    KArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_args(c, a);
+    a.x0 = static_cast<const double*>(x0); a.xref = static_cast<const double*>(x_ref); a.foot = static_cast<const double*>(foot);
+    a.contact = contact; a.pcom = static_cast<const double*>(pcom);
+    a.B = B;
+    return a;
+}
+
 template <typename K>
 int set_lds_once(srbdqp_handle* h, K kernel, size_t lds) {
     const void* fn = reinterpret_cast<const void*>(kernel);
@@ -206,7 +281,6 @@ constexpr int kSplitMinBatch = 1;
 // mixed gait 13.9 M against 6.5 M); smaller ones stay on the 4-wave kernel (lowest latency).
 constexpr int kWrenchMinBatch = 512;      // re-measured in round 4 (uniform rho restart; tools/schedule_bench.py, M QP/s 4-wave / general): N = 10 mixed gait 256 QPs 1.72 / 1.63,
                                           // 512 3.10 / 3.28, 768 3.98 / 4.67, 1024 4.63 / 6.06; double support 256 1.70 / 2.45, 512 2.61 / 4.28 (round 2: 768)
-constexpr int kRestartMinBatch = 4096;         // the one-wave kernel's automatic rho restart in place: batches that fill the chip twice over (restart_iter_of)
 constexpr int kTail1MaxBatch = 8;              // staged calls of up to this many QPs on <= 2 stance contacts per step: the 4-wave set-up + one-wave iteration kernel
 constexpr int kStagedWrenchMinVars = 60;   // staged call: presolved variables (3 per stance contact) above which the wrench-space kernel's low-latency
                                           // instantiation wins (B = 1, N = 10: mixed gait, 72 variables, 74 us compact / 69 us; double support, 120, 107 / 69)
@@ -216,27 +290,27 @@ constexpr int kWrenchMinBatchN20 = 256;   // N = 20: one workgroup per CU on the
 // ones run on fp64 tiles, where the third workgroup per CU would stay empty anyway.
 constexpr int kTileClassMinBatch = 512;
 
-// does a solve of B QPs on this handle go to the general kernel (srbdqp_wrench.hpp)?  launch() / launch_long() ask this.
-inline bool uses_wrench(const srbdqp_handle* h, int maxs, int B) {
+// does a solve of B QPs on this handle go to the general kernel (srbdqp_wrench.hpp)?  launch() asks this.
+inline bool uses_wrench(const srbdqp_handle* h, const Call& c, int maxs, int B) {
     const int N = h->cfg.horizon;
-    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || h->io_f32 || N == 24 || h->robots) return true;   // (per-QP records: only the general kernel reads them)
+    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || h->robots) return true;   // (per-QP records: only the general kernel reads them)
     // N = 20 single support too, for batches: the general kernel holds 2 workgroups per CU there, the compact one 1
     // (tools/schedule_bench.py, 16,384 QPs: 2.85 M QP/s against 1.95 M; at N = 12 / 16 the compact kernel wins, 7.1 / 4.9 M
     // against 5.7 / 4.2 M)
-    if (N > 10) return maxs > 2 || (N == 20 && h->cfg.kernel == SRBDQP_KERNEL_AUTO && B >= kWrenchMinBatchN20 && !h->stamps && !h->staged_call);
+    if (N > 10) return maxs > 2 || (N == 20 && h->cfg.kernel == SRBDQP_KERNEL_AUTO && B >= kWrenchMinBatchN20 && !h->stamps && !c.staged);
     // N <= 10 with more than 2 stance contacts in a step: batches (the 4-wave kernel wins up to two QPs per CU) AND the staged
     // low-latency path -- the reference's own call feeds full double support on every step (run_simulation.py:100-101), where the
     // wrench-space problem is 60 x 60 against the 120 x 120 dense K of the compact kernel (round 3, tools/latency_patterns.py:
     // B = 1 double support p50 82 us against 112 us)
     if (h->cfg.kernel != SRBDQP_KERNEL_AUTO || maxs <= 2 || h->stamps) return false;
     // (the low-latency instantiation is one workgroup per CU, tuned and measured at B = 1: the same bound as the compact kernel's TAIL1 path)
-    return B >= kWrenchMinBatch || (h->staged_call && B <= kTail1MaxBatch && N >= 8 && h->staged_neff > kStagedWrenchMinVars);
+    return B >= kWrenchMinBatch || (c.staged && B <= kTail1MaxBatch && N >= 8 && c.neff > kStagedWrenchMinVars);
 }
 
 // does a solve of B QPs on this handle run on the one-wave kernel (launch_wave)?  launch_compact() and the restart plan (solve_device_impl) ask this.
-inline bool uses_wave(const srbdqp_handle* h, int maxs, int B, bool stamps, bool signalled) {
+inline bool uses_wave(const srbdqp_handle* h, const Call& c, int maxs, int B, bool stamps, bool signalled) {
     const int N = h->cfg.horizon, k = h->cfg.kernel;
-    if (N > 10 || !(N == 4 || maxs <= 2) || uses_wrench(h, maxs, B)) return false;     // (<= 64 presolved variables: Setup1Smem::supported)
+    if (N > 10 || !(N == 4 || maxs <= 2) || uses_wrench(h, c, maxs, B)) return false;     // (<= 64 presolved variables: Setup1Smem::supported)
     const bool want = k == SRBDQP_KERNEL_WAVE || (k == SRBDQP_KERNEL_AUTO && B >= kSplitMinBatch);
     return want && (!stamps || k == SRBDQP_KERNEL_WAVE) && !signalled;
 }
@@ -249,17 +323,12 @@ int launch_split(srbdqp_handle* h, KArgs a, hipStream_t st) {
     const size_t need = (size_t)(a.qp_span > a.B ? a.qp_span : a.B) * W::doubles;   // indexed by QP, not by workgroup
     auto* slot = stream_slot(h, st);
     if (!slot) return SRBDQP_E_INVALID;
-    if (need > slot->ws_doubles) {
-        HIP_TRY(h, hipStreamSynchronize(st));               // a previous launch on this stream may still use the old buffer
-        if (slot->ws) { HIP_TRY(h, hipFree(slot->ws)); slot->ws = nullptr; slot->ws_doubles = 0; }
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&slot->ws), need * sizeof(double));
-        if (e != hipSuccess) { h->err = std::string("hipMalloc split workspace: ") + hipGetErrorString(e); return SRBDQP_E_NOMEM; }
-        slot->ws_doubles = need;
-    }
+    int rc = grow(h, slot->ws, slot->ws_doubles, need, st, "hipMalloc split workspace");   // (a previous launch on this stream may still use the old buffer)
+    if (rc != SRBDQP_OK) return rc;
     a.ws = slot->ws;
     h->prepared_B = 0;                                      // the split pipeline overwrites the workspace a pending two-phase set-up lives in
     constexpr size_t ldsA = srbdqp::CompactTraits<N, MAXS>::lds_bytes, ldsB = srbdqp::SplitSmem<N, MAXS>::bytes;
-    int rc = set_lds_once(h, &srbdqp::srbdqp_compact_kernel<N, MAXS, true>, ldsA);
+    rc = set_lds_once(h, &srbdqp::srbdqp_compact_kernel<N, MAXS, true>, ldsA);
     if (rc != SRBDQP_OK) return rc;
     static const std::string nm = "split_f64_n" + std::to_string(N) + "_s" + std::to_string(MAXS);
     h->kname = nm.c_str();
@@ -288,14 +357,9 @@ int launch_two_phase(srbdqp_handle* h, KArgs a, hipStream_t st, int phase) {
         const size_t need = (size_t)a.B * W::doubles;
         auto* slot = stream_slot(h, st);
         if (!slot) return SRBDQP_E_INVALID;
-        if (need > slot->ws_doubles) {
-            if (phase == 1) { h->err = "srbdqp_solve_prepared_f64 without a matching srbdqp_prepare_staged_f64"; return SRBDQP_E_INVALID; }
-            HIP_TRY(h, hipStreamSynchronize(st));
-            if (slot->ws) { HIP_TRY(h, hipFree(slot->ws)); slot->ws = nullptr; slot->ws_doubles = 0; }
-            hipError_t e = hipMalloc(reinterpret_cast<void**>(&slot->ws), need * sizeof(double));
-            if (e != hipSuccess) { h->err = std::string("hipMalloc split workspace: ") + hipGetErrorString(e); return SRBDQP_E_NOMEM; }
-            slot->ws_doubles = need;
-        }
+        if (need > slot->ws_doubles && phase == 1) { h->err = "srbdqp_solve_prepared_f64 without a matching srbdqp_prepare_staged_f64"; return SRBDQP_E_INVALID; }
+        const int rc = grow(h, slot->ws, slot->ws_doubles, need, st, "hipMalloc split workspace");
+        if (rc != SRBDQP_OK) return rc;
         a.ws = slot->ws;
         if (phase == 0) {
             constexpr size_t lds1 = srbdqp::Setup1Smem<N, MAXS>::bytes;
@@ -318,12 +382,12 @@ int launch_two_phase(srbdqp_handle* h, KArgs a, hipStream_t st, int phase) {
 }
 
 int launch_two_phase_any(srbdqp_handle* h, const KArgs& a, hipStream_t st, int maxs, int phase) {
-    switch (h->cfg.horizon) {
-        case 4: return maxs <= 2 ? launch_two_phase<4, 2>(h, a, st, phase) : launch_two_phase<4, 4>(h, a, st, phase);
-        case 8: return maxs <= 2 ? launch_two_phase<8, 2>(h, a, st, phase) : launch_two_phase<8, 4>(h, a, st, phase);
-        case 10: return maxs <= 2 ? launch_two_phase<10, 2>(h, a, st, phase) : launch_two_phase<10, 4>(h, a, st, phase);
-        default: h->err = "the two-phase call is built for N in {4, 8, 10}"; return SRBDQP_E_INVALID;
-    }
+    return with_horizon(h, [&](auto n) -> int {
+        constexpr int N = decltype(n)::value;
+        if constexpr (N <= 10) return maxs <= 2 ? launch_two_phase<N, 2>(h, a, st, phase) : launch_two_phase<N, 4>(h, a, st, phase);
+        h->err = "the two-phase call is built for N in {4, 8, 10}";
+        return SRBDQP_E_INVALID;
+    });
 }
 
 // One wave per QP for the whole solve (srbdqp_setup1.hpp, FUSED): the default for large batches of the small
@@ -383,23 +447,24 @@ int launch_wave_defer(srbdqp_handle* h, KArgs a, hipStream_t st, srbdqp_handle::
 }
 
 int launch_wave_defer_any(srbdqp_handle* h, const KArgs& a, hipStream_t st, srbdqp_handle::StreamSlot* slot, int maxs) {
-    const bool s2 = maxs <= 2;
-    switch (h->cfg.horizon) {
+    return with_horizon(h, [&](auto n) -> int {
+        constexpr int N = decltype(n)::value;
         // N = 4: ONE instantiation for every launch and for the flush, whatever bound on the stance contacts the call came with -- a record written by a <4, 4>
         // launch and continued by a <4, 2> one (the flush used to pick its MAXS from cfg.max_contacts_per_step, 0 -> 2, while the device API assumes 4 and the
         // host API scans the flags per call) rebuilt the QP with the wrong bound and returned SRBDQP_CONTACT_BOUND with zero forces
-        case 4: return launch_wave_defer<4, 4>(h, a, st, slot);
-        case 8: if (s2) return launch_wave_defer<8, 2>(h, a, st, slot); break;
-        case 10: if (s2) return launch_wave_defer<10, 2>(h, a, st, slot); break;
-        default: break;
-    }
-    h->err = "deferred tails exist for the one-wave kernel only (N <= 10, at most 2 stance contacts per step)";
-    return SRBDQP_E_INVALID;
+        if constexpr (N == 4) return launch_wave_defer<4, 4>(h, a, st, slot);
+        if constexpr (N == 8 || N == 10) if (maxs <= 2) return launch_wave_defer<N, 2>(h, a, st, slot);
+        h->err = "deferred tails exist for the one-wave kernel only (N <= 10, at most 2 stance contacts per step)";
+        return SRBDQP_E_INVALID;
+    });
 }
 
 // lists for launches of up to B QPs that may re-balance up to rmax times (sized for the share that really continues; a full list is not an error)
 int ensure_tail_lists(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStream_t st, size_t B, int rmax);
 int flush_slot(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStream_t st);
+int solve_device_impl(srbdqp_handle* h, const Call& c, int32_t B, const void* x0, const void* x_ref, const void* foot, const uint8_t* contact,
+                      const void* pcom, const void* warm_u, const void* warm_y, void* u_out, void* x_out, void* y_out,
+                      int32_t* status, int32_t* iters, void* stream);
 
 // the handle's AQL queue, made at the first staged one-QP call (a 5 MB code object goes through the HSA loader once per process and device)
 srbdqp::AqlQueue* aql_queue(srbdqp_handle* h) {
@@ -422,11 +487,55 @@ int aql_quiesce(srbdqp_handle* h) {
     return SRBDQP_E_HIP;
 }
 
+// (a word that came with a checksum -- KArgs::done_cs -- counts once the outputs read back agree with it: they travel without a fence in front of the word)
+bool outputs_there(const srbdqp_handle* h) {
+    if (!h->done_cs) return true;
+    const size_t Nn = (size_t)h->cfg.horizon;
+    const volatile uint64_t* u = reinterpret_cast<const volatile uint64_t*>(h->stage_h.u);
+    uint64_t x = 0;
+    for (size_t i = 0; i < 12 * Nn; ++i) x ^= u[i];
+    if (h->done_cs_x) {
+        const volatile uint64_t* xs = reinterpret_cast<const volatile uint64_t*>(h->stage_h.x);
+        for (size_t i = 0; i < 13 * (Nn + 1); ++i) x ^= xs[i];
+    }
+    x ^= (uint64_t)(uint32_t)*reinterpret_cast<const volatile int32_t*>(h->stage_h.status) | ((uint64_t)(uint32_t)*reinterpret_cast<const volatile int32_t*>(h->stage_h.iters) << 32);
+    // the records: {sequence number, how many records, XOR of one row of 16 lanes} every 16 bytes (srbdqp_common.hpp signal_done_checksum)
+    const volatile int32_t* rec = h->done_host;
+    const int32_t nrec = rec[1];
+    if (nrec < 1 || nrec > 16) return false;
+    for (int32_t r = 0; r < nrec; ++r) {
+        if (rec[4 * r] != h->done_seq || rec[4 * r + 1] != nrec) return false;
+        x ^= (uint64_t)(uint32_t)rec[4 * r + 2] | ((uint64_t)(uint32_t)rec[4 * r + 3] << 32);
+    }
+    return x == 0;
+}
+
+// the end of the last launch on the handle's stream: spin on its completion word (sequence number h->done_seq), or synchronise the stream
+int wait_done(srbdqp_handle* h, bool spin) {
+    if (spin) {
+        const auto t0 = std::chrono::steady_clock::now();
+        unsigned polls = 0;
+        while (*h->done_host != h->done_seq || !outputs_there(h)) {
+            if ((++polls & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
+                // slow or failed launch: hand over to the runtime (reports a fault, or returns once the kernel is done)
+                const int rq = aql_quiesce(h);
+                if (rq != SRBDQP_OK) return rq;
+                HIP_TRY(h, hipStreamSynchronize(h->stream));
+                break;
+            }
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+        return SRBDQP_OK;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SRBDQP_OK;
+}
+
 // one workgroup of a *_kernel_in instantiation (arguments: KArgs, then StagedIn<N>) through the handle's own queue; false: the caller launches through HIP
 template <class In>
-bool aql_launch_in(srbdqp_handle* h, hipStream_t st, const char* kd_format, int n, int x, const KArgs& a, const In& in, unsigned block, size_t lds) {
+bool aql_launch_in(srbdqp_handle* h, const Call& c, hipStream_t st, const char* kd_format, int n, int x, const KArgs& a, const In& in, unsigned block, size_t lds) {
     // (events and tail passes live on HIP streams; a call that does not spin on the completion word waits on its stream)
-    if (!h->staged_call || st != h->stream || !a.done_flag || (h->cfg.flags & (SRBDQP_FLAG_DEFER_TAIL | SRBDQP_FLAG_TIMING | SRBDQP_FLAG_NO_SPIN))) return false;
+    if (!c.staged || st != h->stream || !a.done_flag || (h->cfg.flags & (SRBDQP_FLAG_DEFER_TAIL | SRBDQP_FLAG_TIMING | SRBDQP_FLAG_NO_SPIN))) return false;
     srbdqp::AqlQueue* q = aql_queue(h);
     if (!q) return false;
     char name[160];
@@ -449,8 +558,8 @@ void staged_done_checksum(srbdqp_handle* h, KArgs& ai) {
 
 // one staged QP whose inputs still sit in the library's own staging arrays: they ride in the kernel-argument segment (srbdqp_common.hpp StagedIn)
 template <int N>
-bool staged_inline_inputs(const srbdqp_handle* h, const KArgs& a, srbdqp::StagedIn<N>& in) {
-    if (!(h->staged_call && a.B == 1 && a.x0 == h->stage_d.x0 && a.xref == h->stage_d.x_ref && a.foot == h->stage_d.foot && a.contact == h->stage_d.contact) ||
+bool staged_inline_inputs(const srbdqp_handle* h, const Call& c, const KArgs& a, srbdqp::StagedIn<N>& in) {
+    if (!(c.staged && a.B == 1 && a.x0 == h->stage_d.x0 && a.xref == h->stage_d.x_ref && a.foot == h->stage_d.foot && a.contact == h->stage_d.contact) ||
         a.perm || a.row_off || (a.pcom && a.pcom != h->stage_d.pcom)) return false;     // (a restart pass of the staged call too: the host starts it only for a QP at the cap)
     std::memcpy(in.x0, h->stage_h.x0, sizeof(in.x0));
     std::memcpy(in.xref, h->stage_h.x_ref, sizeof(in.xref));
@@ -461,9 +570,9 @@ bool staged_inline_inputs(const srbdqp_handle* h, const KArgs& a, srbdqp::Staged
 }
 
 template <int N, int MAXS>
-int launch_compact(srbdqp_handle* h, const KArgs& a, hipStream_t st) {
+int launch_compact(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t st) {
     if constexpr (srbdqp::Setup1Smem<N, MAXS>::supported) {
-        if (uses_wave(h, MAXS, a.B, a.stamps != nullptr, a.done_flag != nullptr)) return launch_wave<N, MAXS>(h, a, st);
+        if (uses_wave(h, c, MAXS, a.B, a.stamps != nullptr, a.done_flag != nullptr)) return launch_wave<N, MAXS>(h, a, st);
     }
     if constexpr (srbdqp::SplitWs<N, MAXS>::supported) {
         if (h->cfg.kernel == SRBDQP_KERNEL_SPLIT && a.mode == 0 && !a.stamps && !a.done_flag) return launch_split<N, MAXS>(h, a, st);
@@ -488,13 +597,13 @@ int launch_compact(srbdqp_handle* h, const KArgs& a, hipStream_t st) {
             static const std::string nml = nm + "_lat";
             h->kname = nml.c_str();
             srbdqp::StagedIn<N> in;
-            if (!a.count_ptr && staged_inline_inputs<N>(h, a, in)) {
+            if (!a.count_ptr && staged_inline_inputs<N>(h, c, a, in)) {
                 rc1 = set_lds_once(h, &srbdqp::srbdqp_compact_kernel_in<N, MAXS>, lds1);
                 if (rc1 != SRBDQP_OK) return rc1;
                 KArgs ai = a;
                 ai.inline_in = 1;
                 staged_done_checksum(h, ai);
-                if (aql_launch_in(h, st, "_ZN6srbdqp24srbdqp_compact_kernel_inILi%dELi%dEEEvNS_5KArgsENS_8StagedInIXT_EEE.kd", N, MAXS, ai, in, srbdqp::kThreads, lds1)) return SRBDQP_OK;
+                if (aql_launch_in(h, c, st, "_ZN6srbdqp24srbdqp_compact_kernel_inILi%dELi%dEEEvNS_5KArgsENS_8StagedInIXT_EEE.kd", N, MAXS, ai, in, srbdqp::kThreads, lds1)) return SRBDQP_OK;
                 rc1 = aql_quiesce(h);
                 if (rc1 != SRBDQP_OK) return rc1;
                 hipLaunchKernelGGL((srbdqp::srbdqp_compact_kernel_in<N, MAXS>), dim3(1), dim3(srbdqp::kThreads), lds1, st, ai, in);
@@ -507,14 +616,6 @@ int launch_compact(srbdqp_handle* h, const KArgs& a, hipStream_t st) {
     int rc = set_lds_once(h, &srbdqp::srbdqp_compact_kernel<N, MAXS>, lds);
     if (rc != SRBDQP_OK) return rc;
     hipLaunchKernelGGL((srbdqp::srbdqp_compact_kernel<N, MAXS>), dim3((unsigned)a.B), dim3(srbdqp::kThreads), lds, st, a);
-    return SRBDQP_OK;
-}
-
-template <int N>
-int launch_n(srbdqp_handle* h, const KArgs& a, hipStream_t st, int maxs) {
-    int rc = (maxs <= 2) ? launch_compact<N, 2>(h, a, st) : launch_compact<N, 4>(h, a, st);
-    if (rc != SRBDQP_OK) return rc;
-    HIP_TRY(h, hipGetLastError());
     return SRBDQP_OK;
 }
 
@@ -538,7 +639,7 @@ struct WrenchTraits {
 };
 
 template <int N, typename R, typename TIO>
-int launch_wrench_t(srbdqp_handle* h, const KArgs& a, hipStream_t st) {
+int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t st) {
     using S = srbdqp::WrenchSmem<N>;
     constexpr int WPS = WrenchTraits<N, R>::wps;
     constexpr size_t lds = S::bytes;
@@ -590,13 +691,13 @@ int launch_wrench_t(srbdqp_handle* h, const KArgs& a, hipStream_t st) {
                 h->kname = nml.c_str();
                 if constexpr (std::is_same<TIO, double>::value) {
                     srbdqp::StagedIn<N> in;
-                    if (!a.count_ptr && !a.tile_sel && staged_inline_inputs<N>(h, a, in)) {
+                    if (!a.count_ptr && !a.tile_sel && staged_inline_inputs<N>(h, c, a, in)) {
                         rcl = set_lds_once(h, &srbdqp::srbdqp_wrench_kernel_in<N, XW>, ldsl);
                         if (rcl != SRBDQP_OK) return rcl;
                         KArgs ai = a;
                         ai.inline_in = 1;
                         staged_done_checksum(h, ai);
-                        if (aql_launch_in(h, st, "_ZN6srbdqp23srbdqp_wrench_kernel_inILi%dELi%dEEEvNS_5KArgsENS_8StagedInIXT_EEE.kd", N, XW, ai, in, SL::BT, ldsl)) return SRBDQP_OK;
+                        if (aql_launch_in(h, c, st, "_ZN6srbdqp23srbdqp_wrench_kernel_inILi%dELi%dEEEvNS_5KArgsENS_8StagedInIXT_EEE.kd", N, XW, ai, in, SL::BT, ldsl)) return SRBDQP_OK;
                         rcl = aql_quiesce(h);
                         if (rcl != SRBDQP_OK) return rcl;
                         hipLaunchKernelGGL((srbdqp::srbdqp_wrench_kernel_in<N, XW>), dim3(1), dim3(SL::BT), ldsl, st, ai, in);
@@ -638,55 +739,38 @@ int launch_wrench_t(srbdqp_handle* h, const KArgs& a, hipStream_t st) {
     return SRBDQP_OK;
 }
 
-template <int N>
-int launch_wrench(srbdqp_handle* h, const KArgs& a, hipStream_t st) {
-    if (h->io_f32) return launch_wrench_t<N, float, float>(h, a, st);
-    return launch_wrench_t<N, double, double>(h, a, st);
-}
-
-template <int N>
-int launch_long(srbdqp_handle* h, const KArgs& a, hipStream_t st, int maxs) {
-    // the compact kernel exists only with <= 2 stance contacts per step at these horizons; anything else (and every
-    // fp32 call) goes to the general kernel
-    if (uses_wrench(h, maxs, a.qp_span > a.B ? a.qp_span : a.B)) return launch_wrench<N>(h, a, st);
-    int rc = launch_compact<N, 2>(h, a, st);
-    if (rc != SRBDQP_OK) return rc;
-    HIP_TRY(h, hipGetLastError());
-    return SRBDQP_OK;
+// the general kernel at the handle's horizon, on the call's element type
+int launch_wrench(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t st) {
+    return with_horizon(h, [&](auto n) -> int {
+        constexpr int N = decltype(n)::value;
+        if (c.f32) return launch_wrench_t<N, float, float>(h, c, a, st);
+        return launch_wrench_t<N, double, double>(h, c, a, st);
+    });
 }
 
 // pass: 0 = the only launch of a solve, 1 = first of two (restart follows), 2 = second of two
-int launch(srbdqp_handle* h, const KArgs& a, hipStream_t st, int maxs = 4, int pass = 0) {
+int launch(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t st, int pass = 0) {
     if (a.B <= 0) return SRBDQP_OK;
-    const bool force_wrench = uses_wrench(h, maxs, a.qp_span > a.B ? a.qp_span : a.B);
     const bool timing = (h->cfg.flags & SRBDQP_FLAG_TIMING) != 0;
     if (timing && pass != 2) { HIP_TRY(h, hipEventRecord(h->ev0, st)); h->ev_mid_valid = false; }
     int rc;
-    switch (h->cfg.horizon) {
-        case 4: rc = force_wrench ? launch_wrench<4>(h, a, st) : launch_n<4>(h, a, st, maxs); break;
-        case 8: rc = force_wrench ? launch_wrench<8>(h, a, st) : launch_n<8>(h, a, st, maxs); break;
-        case 10: rc = force_wrench ? launch_wrench<10>(h, a, st) : launch_n<10>(h, a, st, maxs); break;
-        case 12: rc = launch_long<12>(h, a, st, maxs); break;
-        case 16: rc = launch_long<16>(h, a, st, maxs); break;
-        case 20: rc = launch_long<20>(h, a, st, maxs); break;
-        case 24: rc = launch_wrench<24>(h, a, st); break;
-        default: h->err = "unsupported horizon"; return SRBDQP_E_INVALID;
-    }
+    // the compact kernel exists with up to 4 stance contacts per step at N <= 10, with at most 2 at N = 12 - 20; anything else (and every fp32 call) goes to
+    // the general kernel
+    if (uses_wrench(h, c, c.maxs, a.qp_span > a.B ? a.qp_span : a.B)) rc = launch_wrench(h, c, a, st);
+    else rc = with_horizon(h, [&](auto n) -> int {
+        constexpr int N = decltype(n)::value;
+        int rcc = SRBDQP_OK;
+        if constexpr (N <= 10) rcc = (c.maxs <= 2) ? launch_compact<N, 2>(h, c, a, st) : launch_compact<N, 4>(h, c, a, st);
+        else if constexpr (N <= 20) rcc = launch_compact<N, 2>(h, c, a, st);
+        if (rcc != SRBDQP_OK) return rcc;
+        HIP_TRY(h, hipGetLastError());
+        return SRBDQP_OK;
+    });
     if (rc != SRBDQP_OK) return rc;
     if (timing && pass != 1) {
         HIP_TRY(h, hipEventRecord(h->ev1, st));
         h->ev_valid = true;
     }
-    return SRBDQP_OK;
-}
-
-int ensure_ws(srbdqp_handle* h, size_t bytes) {
-    if (bytes <= h->ws_bytes) return SRBDQP_OK;
-    if (h->ws) { HIP_TRY(h, hipFree(h->ws)); h->ws = nullptr; h->ws_bytes = 0; }
-    size_t want = bytes + bytes / 4;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->ws), want);
-    if (e != hipSuccess) { h->err = std::string("hipMalloc workspace: ") + hipGetErrorString(e); return SRBDQP_E_NOMEM; }
-    h->ws_bytes = want;
     return SRBDQP_OK;
 }
 
@@ -699,6 +783,55 @@ struct Carver {
         return p;
     }
 };
+
+// The arrays of a host-buffer call (a handle's or a ragged object's): in() one the call uploads, out() one it downloads, zeroed() one it clears first (and
+// downloads, given a host pointer).  A null host pointer means no array, except for out(..., true): status / iters, which the kernels write either way.
+struct HostIo {
+    struct Arr { void* dev; const void* in; void* out; size_t bytes; bool zero; };
+    Carver c;
+    Arr arr[16];                   // (at most 12: solve_host_impl)
+    int n = 0;
+    explicit HostIo(char* base) : c(base) {}
+    template <typename T = char> T* in(const void* host, size_t bytes) { return host ? add<T>(host, nullptr, bytes, false) : nullptr; }
+    template <typename T = char> T* out(void* host, size_t bytes, bool always = false) { return (host || always) ? add<T>(nullptr, host, bytes, false) : nullptr; }
+    template <typename T = char> T* zeroed(void* host, size_t bytes) { return add<T>(nullptr, host, bytes, true); }
+    template <typename T> T* add(const void* in, void* out, size_t bytes, bool zero) {
+        char* d = c.take<char>(bytes);
+        arr[n++] = {d, in, out, bytes, zero};
+        return reinterpret_cast<T*>(d);
+    }
+};
+
+template <class O>
+int ensure_ws(O* o, size_t bytes) {
+    return bytes <= o->ws_bytes ? SRBDQP_OK : grow(o, o->ws, o->ws_bytes, bytes + bytes / 4, o->stream, "hipMalloc workspace");
+}
+
+// a host-buffer call on o's stream: arrays(io) names its arrays (run twice: a dry run for the size, then carved from o's workspace), then upload, clear,
+// run(stream) -- the device entry point --, download, synchronise
+template <class O, class Arrays, class Run>
+int host_call(O* o, Arrays&& arrays, Run&& run) {
+    HostIo sz(nullptr);
+    arrays(sz);
+    int rc = ensure_ws(o, sz.c.off);
+    if (rc != SRBDQP_OK) return rc;
+    HostIo io(o->ws);
+    arrays(io);
+    hipStream_t st = o->stream;
+    for (int i = 0; i < io.n; ++i) {
+        const HostIo::Arr& x = io.arr[i];
+        if (x.in) HIP_TRY(o, hipMemcpyAsync(x.dev, x.in, x.bytes, hipMemcpyHostToDevice, st));
+        if (x.zero) HIP_TRY(o, hipMemsetAsync(x.dev, 0, x.bytes, st));
+    }
+    rc = run(st);
+    if (rc != SRBDQP_OK) return rc;
+    for (int i = 0; i < io.n; ++i) {
+        const HostIo::Arr& x = io.arr[i];
+        if (x.out) HIP_TRY(o, hipMemcpyAsync(x.out, x.dev, x.bytes, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(o, hipStreamSynchronize(st));
+    return SRBDQP_OK;
+}
 
 // Iteration at which a solve of this handle re-balances rho (0 = never), and how many times it may (*count).  srbdqp_config.rho_restart_iter: > 0 that
 // iteration, < 0 off, 0 = automatic:
@@ -718,8 +851,7 @@ struct Carver {
 //    staged (batch-1) call: the host starts a further pass only when a status[] asks for it (4 % of the calls take a second launch, 1 % a third).
 // The price where a call is small: it cannot end before its slowest QP, and a restarted one is a chain of up to three set-ups and 250 iterations (0.22 ms
 // against 0.16 ms for 250 iterations at one rho): 512 QPs per call on the one-wave kernel 7.2 -> 5.2 M QP/s.  rho_restart_iter = -1 buys that back.
-inline int restart_iter_of(const srbdqp_handle* h, int maxs, int B, bool wave = false, int* count = nullptr) {
-    (void)maxs; (void)B; (void)wave;
+inline int restart_iter_of(const srbdqp_handle* h, int* count = nullptr) {
     const srbdqp_config& c = h->cfg;
     const int rk = resolve_kernel(c);
     if (count) *count = 1;
@@ -801,12 +933,10 @@ int ensure_tail_lists(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStre
 int flush_slot(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStream_t st) {
     if (!slot->tail || !slot->tail_live) return SRBDQP_OK;
     int rcount = 1;
-    const int maxs = h->cfg.max_contacts_per_step > 0 ? h->cfg.max_contacts_per_step : 2;
-    const int restart = restart_iter_of(h, maxs, kRestartMinBatch, true, &rcount);
-    KArgs a;
-    std::memset(&a, 0, sizeof(a));
-    fill_args(h->cfg, a);
-    a.B = 0; a.restart_every = restart; a.restart_max = rcount;
+    const int maxs = maxs_or(h->cfg, 2);
+    const int restart = restart_iter_of(h, &rcount);
+    KArgs a = base_args(h->cfg, 0);
+    a.restart_every = restart; a.restart_max = rcount;
     {   // ONE launch: a flush workgroup runs every pass its QP has left (srbdqp_setup1.hpp, FLUSH)
         const int rc = launch_wave_defer_any(h, a, st, slot, maxs <= 2 ? 2 : 4);
         if (rc != SRBDQP_OK) return rc;
@@ -819,13 +949,14 @@ int flush_slot(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStream_t st
 // period): the same grid again; the workgroup of a QP that the pass before left at its cap re-balances its rho from the maxima of its last check -- from the rho of
 // THAT pass -- and continues from its own (x, y), every other workgroup leaves at once.  No selection kernel and no list between the passes: a one-workgroup kernel
 // queued behind a chip-filling launch of another stream waits ~150 us for its turn at the dispatcher (rocprofv3 timeline, round 2), which cost more than the
-// pass itself.  *last_out: no further pass may follow (p = rcount, or the cap on the total comes first: oracle solve_with_restart).
-int srbdqp_restart_pass(srbdqp_handle* h, const KArgs& a1, hipStream_t st, int maxs, bool signal, srbdqp_handle::StreamSlot* slot, int p, int rcount, bool* last_out) {
+// pass itself.  last: no further pass may follow (p = rcount, or the cap on the total comes first: oracle solve_with_restart).  rho: the two buffers through
+// which the rho of a pass reaches the one behind it.  Every multi-pass solve builds its passes here; the callers add only what is theirs.
+struct Pass { KArgs a; bool last; };
+Pass restart_pass(const KArgs& a1, int p, int rcount, int max_iter, double* const rho[2]) {
     const int every = a1.max_iter;
     const int done = p * every;                             // iterations of a QP that every pass so far left at its cap
-    const int left = h->cfg.max_iter - done;                // the cap is on the total
+    const int left = max_iter - done;                       // the cap is on the total
     const bool last = p >= rcount || every >= left;
-    if (last_out) *last_out = last;
     KArgs a2 = a1;
     a2.resid_in = a1.resid_out;
     a2.warm_u = a1.u_dev ? a1.u_dev : a1.u_out;             // newtons, as a caller's warm start would be (the device copy of a staged first pass)
@@ -834,12 +965,14 @@ int srbdqp_restart_pass(srbdqp_handle* h, const KArgs& a1, hipStream_t st, int m
     a2.max_iter = last ? left : every;
     a2.iters_base = done;
     a2.resid_out = last ? nullptr : a1.resid_out;           // (a workgroup reads its entry when it starts and writes it when it ends)
-    a2.rho_qp = (p == 1) ? a1.rho_qp : slot->rhobuf[p % 2];
-    a2.rho_out = last ? nullptr : slot->rhobuf[(p + 1) % 2];
-    if (signal) { a2.done_flag = h->done_dev; a2.done_count = h->done_count; a2.done_value = h->done_seq; }
-    else { a2.done_flag = nullptr; a2.done_count = nullptr; }
-    return launch(h, a2, st, maxs, 2);
+    a2.rho_qp = (p == 1) ? a1.rho_qp : rho[p % 2];
+    a2.rho_out = last ? nullptr : rho[(p + 1) % 2];
+    return {a2, last};
 }
+
+// the launch publishes the completion word with the handle's current sequence number
+void signal_args(const srbdqp_handle* h, KArgs& a) { a.done_flag = h->done_dev; a.done_count = h->done_count; a.done_value = h->done_seq; }
+int32_t next_seq(srbdqp_handle* h) { return h->done_seq = (h->done_seq == INT32_MAX) ? 1 : h->done_seq + 1; }
 
 // ---- per-QP robot records (srbdqp_set_robots) ----
 static_assert(sizeof(srbdqp_robot) == 64 && offsetof(srbdqp_robot, inertia) == 8 && offsetof(srbdqp_robot, mu) == 32 &&
@@ -1064,97 +1197,33 @@ int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32
         if (rq != SRBDQP_OK) return rq;
     }
     const srbdqp_stage& d = h->stage_d;
-    h->staged_neff = 0;
-    h->staged_call = true;
     h->done_cs = false;            // (set again by a launch that publishes a checksum)
-    struct Reset { srbdqp_handle* h; ~Reset() { h->signal_next = false; h->staged_call = false; h->maxs_override = 0; h->staged_neff = 0; } } reset_on_return{h};
-    {   // same per-batch kernel choice as the host-buffer API, from the staged contact flags
-        int worst = 0;
-        const uint8_t* c = h->stage_h.contact;
-        const size_t N = (size_t)h->cfg.horizon;
-        for (size_t b = 0; b < (size_t)B; ++b) {
-            int na = 0;
-            for (size_t q = b * N; q < (b + 1) * N; ++q) {
-                const int cnt = (c[4 * q] != 0) + (c[4 * q + 1] != 0) + (c[4 * q + 2] != 0) + (c[4 * q + 3] != 0);
-                if (cnt > worst) worst = cnt;
-                na += cnt;
-            }
-            if (3 * na > h->staged_neff) h->staged_neff = 3 * na;
-        }
-        if (h->cfg.max_contacts_per_step <= 0) h->maxs_override = (worst <= 2) ? 2 : 4;
-    }
-    // completion: the compact kernel publishes a sequence number in host memory after its outputs (signal_done());
-    // spinning on it skips the stream's completion interrupt (~15 us).  Other kernel variants: stream synchronise.
-    const int rk = resolve_kernel(h->cfg);
-    const bool spin = (rk == SRBDQP_KERNEL_COMPACT || rk == SRBDQP_KERNEL_WRENCH) && !(h->cfg.flags & SRBDQP_FLAG_NO_SPIN);
-    // (a word that came with a checksum -- KArgs::done_cs -- counts once the outputs read back agree with it: they travel without a fence in front of the word)
-    auto outputs_there = [&]() -> bool {
-        if (!h->done_cs) return true;
-        const size_t Nn = (size_t)h->cfg.horizon;
-        const volatile uint64_t* u = reinterpret_cast<const volatile uint64_t*>(h->stage_h.u);
-        uint64_t x = 0;
-        for (size_t i = 0; i < 12 * Nn; ++i) x ^= u[i];
-        if (h->done_cs_x) {
-            const volatile uint64_t* xs = reinterpret_cast<const volatile uint64_t*>(h->stage_h.x);
-            for (size_t i = 0; i < 13 * (Nn + 1); ++i) x ^= xs[i];
-        }
-        x ^= (uint64_t)(uint32_t)*reinterpret_cast<const volatile int32_t*>(h->stage_h.status) | ((uint64_t)(uint32_t)*reinterpret_cast<const volatile int32_t*>(h->stage_h.iters) << 32);
-        // the records: {sequence number, how many records, XOR of one row of 16 lanes} every 16 bytes (srbdqp_common.hpp signal_done_checksum)
-        const volatile int32_t* rec = h->done_host;
-        const int32_t nrec = rec[1];
-        if (nrec < 1 || nrec > 16) return false;
-        for (int32_t r = 0; r < nrec; ++r) {
-            if (rec[4 * r] != h->done_seq || rec[4 * r + 1] != nrec) return false;
-            x ^= (uint64_t)(uint32_t)rec[4 * r + 2] | ((uint64_t)(uint32_t)rec[4 * r + 3] << 32);
-        }
-        return x == 0;
-    };
-    auto wait_done = [&]() -> int {
-        if (spin) {
-            const auto t0 = std::chrono::steady_clock::now();
-            unsigned polls = 0;
-            while (*h->done_host != h->done_seq || !outputs_there()) {
-                if ((++polls & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
-                    // slow or failed launch: hand over to the runtime (reports a fault, or returns once the kernel is done)
-                    const int rq = aql_quiesce(h);
-                    if (rq != SRBDQP_OK) return rq;
-                    HIP_TRY(h, hipStreamSynchronize(h->stream));
-                    break;
-                }
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-            return SRBDQP_OK;
-        }
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        return SRBDQP_OK;
-    };
-    if (spin) { h->done_seq = (h->done_seq == INT32_MAX) ? 1 : h->done_seq + 1; h->signal_next = true; }
-    const int maxs = h->maxs_override ? h->maxs_override : (h->cfg.max_contacts_per_step > 0 ? h->cfg.max_contacts_per_step : 4);
-    h->lazy_restart = true;                                 // the rho restart costs two more launches: only when needed
-    const int32_t* hint_keep = h->sched_hint;               // the dispatch hint belongs to the device-buffer API
-    h->sched_hint = nullptr;
-    int rc = srbdqp_solve_batch_device_f64(h, B, d.x0, d.x_ref, d.foot, d.contact, use_pcom ? d.pcom : nullptr,
-                                           use_warm ? d.warm_u : nullptr, use_warm ? d.warm_y : nullptr, d.u,
-                                           want_x ? d.x : nullptr, want_y ? d.y : nullptr, d.status, d.iters, h->stream);
-    h->sched_hint = hint_keep;
-    h->lazy_restart = false;
-    // (staged_call / maxs_override / staged_neff stay set until this call returns: a restart pass below must choose the same kernel)
+    Lazy lazy;
+    Call c;                        // same per-batch kernel choice as the host-buffer API, from the staged contact flags
+    const Contacts k = scan_contacts(h->stage_h.contact, (size_t)B, (size_t)h->cfg.horizon, true);
+    c.maxs = maxs_or(h->cfg, k.maxs());
+    c.staged = true;
+    c.neff = k.neff;
+    c.lazy = &lazy;                // the rho restart costs two more launches: only when needed
+    // completion: the kernel publishes a sequence number in host memory after its outputs (signal_done()); spinning on it skips the stream's completion
+    // interrupt (~15 us)
+    c.signal = !(h->cfg.flags & SRBDQP_FLAG_NO_SPIN);
+    if (c.signal) next_seq(h);
+    int rc = solve_device_impl(h, c, B, d.x0, d.x_ref, d.foot, d.contact, use_pcom ? d.pcom : nullptr, use_warm ? d.warm_u : nullptr,
+                               use_warm ? d.warm_y : nullptr, d.u, want_x ? d.x : nullptr, want_y ? d.y : nullptr, d.status, d.iters, h->stream);
     if (rc != SRBDQP_OK) return rc;
-    rc = wait_done();
-    if (rc != SRBDQP_OK) return rc;
-    if (h->lazy_pending) {          // the solve above was the first pass of a multi-pass solve (not: restarted in place, or no restart at all)
-        h->lazy_pending = false;
-        for (int p = 1; p <= h->lazy_rcount; ++p) {         // a further pass only when a status asks for it
-            bool capped = false;
-            for (int32_t q = 0; q < B; ++q) capped |= (h->stage_h.status[q] == SRBDQP_MAX_ITER);
-            if (!capped) break;
-            if (spin) h->done_seq = (h->done_seq == INT32_MAX) ? 1 : h->done_seq + 1;
-            bool last = true;
-            rc = srbdqp_restart_pass(h, h->last_args, h->stream, maxs, spin, h->lazy_slot, p, h->lazy_rcount, &last);
-            if (rc != SRBDQP_OK) return rc;
-            rc = wait_done();
-            if (rc != SRBDQP_OK || last) break;
-        }
+    rc = wait_done(h, c.signal);
+    if (rc != SRBDQP_OK || !lazy.pending) return rc;
+    for (int p = 1; p <= lazy.rcount; ++p) {                // the first pass of a multi-pass solve ran: a further pass only when a status asks for it
+        bool capped = false;
+        for (int32_t q = 0; q < B; ++q) capped |= (h->stage_h.status[q] == SRBDQP_MAX_ITER);
+        if (!capped) break;
+        Pass pass = restart_pass(lazy.a1, p, lazy.rcount, h->cfg.max_iter, lazy.slot->rhobuf);
+        if (c.signal) { next_seq(h); signal_args(h, pass.a); }
+        rc = launch(h, c, pass.a, h->stream, 2);            // (with the first pass's Call: the same kernel)
+        if (rc != SRBDQP_OK) return rc;
+        rc = wait_done(h, c.signal);
+        if (rc != SRBDQP_OK || pass.last) break;
     }
     return rc;
 }
@@ -1183,25 +1252,11 @@ int srbdqp_update_f64(srbdqp_handle* h, const double* x0, const double* x_ref, c
 }
 
 namespace {
-int staged_maxs(srbdqp_handle* h, int32_t B) {
-    if (h->cfg.max_contacts_per_step > 0) return h->cfg.max_contacts_per_step;
-    int worst = 0;
-    const uint8_t* c = h->stage_h.contact;
-    for (size_t q = 0; q < (size_t)B * h->cfg.horizon; ++q) {
-        const int cnt = (c[4 * q] != 0) + (c[4 * q + 1] != 0) + (c[4 * q + 2] != 0) + (c[4 * q + 3] != 0);
-        if (cnt > worst) worst = cnt;
-    }
-    return (worst <= 2) ? 2 : 4;
-}
 KArgs staged_args(srbdqp_handle* h, int32_t B, bool use_pcom, bool want_x, bool want_y) {
     const srbdqp_stage& d = h->stage_d;
-    KArgs a;
-    std::memset(&a, 0, sizeof(a));
-    fill_args(h->cfg, a);
-    a.x0 = d.x0; a.xref = d.x_ref; a.foot = d.foot; a.contact = d.contact; a.pcom = use_pcom ? d.pcom : nullptr;
+    KArgs a = base_args(h->cfg, B, d.x0, d.x_ref, d.foot, d.contact, use_pcom ? d.pcom : nullptr);
     a.u_out = d.u; a.x_out = want_x ? d.x : nullptr; a.y_out = want_y ? d.y : nullptr;
     a.status = d.status; a.iters = d.iters;
-    a.B = B; a.mode = 0;
     return a;
 }
 }  // namespace
@@ -1216,7 +1271,7 @@ int srbdqp_prepare_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom) {
         const int rq = aql_quiesce(h);
         if (rq != SRBDQP_OK) return rq;
     }
-    const int maxs = staged_maxs(h, B);
+    const int maxs = maxs_or(h->cfg, scan_contacts(h->stage_h.contact, (size_t)B, (size_t)h->cfg.horizon, false).maxs());
     KArgs a = staged_args(h, B, use_pcom != 0, true, false);
     const int rc = launch_two_phase_any(h, a, h->stream, maxs, 0);
     if (rc != SRBDQP_OK) return rc;
@@ -1231,27 +1286,12 @@ int srbdqp_solve_prepared_f64(srbdqp_handle* h, int32_t B, int32_t want_x, int32
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const bool spin = !(h->cfg.flags & SRBDQP_FLAG_NO_SPIN);
     KArgs a = staged_args(h, B, h->prepared_pcom, want_x != 0, want_y != 0);
-    if (spin) {
-        h->done_seq = (h->done_seq == INT32_MAX) ? 1 : h->done_seq + 1;
-        a.done_flag = h->done_dev; a.done_count = h->done_count; a.done_value = h->done_seq;
-    }
+    if (spin) { next_seq(h); signal_args(h, a); }
     h->prepared_B = 0;
+    h->done_cs = false;            // (the two-phase kernels publish the word without a checksum)
     const int rc = launch_two_phase_any(h, a, h->stream, h->prepared_maxs, 1);
     if (rc != SRBDQP_OK) return rc;
-    if (spin) {
-        const auto t0 = std::chrono::steady_clock::now();
-        unsigned polls = 0;
-        while (*h->done_host != h->done_seq) {
-            if ((++polls & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
-                HIP_TRY(h, hipStreamSynchronize(h->stream));
-                break;
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        return SRBDQP_OK;
-    }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SRBDQP_OK;
+    return wait_done(h, spin);
 }
 
 int srbdqp_set_schedule_hint(srbdqp_handle* h, const int32_t* device_iters_prev, int32_t length) {
@@ -1275,13 +1315,9 @@ int srbdqp_set_robots(srbdqp_handle* h, const srbdqp_robot* host, int32_t length
     int rc = robots_quiesce(h);                     // (deferred passes may still read the records this call replaces)
     if (rc != SRBDQP_OK) return rc;
     if (clear) { h->robots = nullptr; h->robots_len = 0; return SRBDQP_OK; }
-    if ((size_t)length > h->robots_cap) {
-        if (h->robots_own) HIP_TRY(h, hipFree(h->robots_own));
-        h->robots_own = nullptr; h->robots_cap = 0; h->robots = nullptr; h->robots_len = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->robots_own), sizeof(srbdqp_robot) * (size_t)length);
-        if (e != hipSuccess) { h->err = std::string("hipMalloc robot records: ") + hipGetErrorString(e); return SRBDQP_E_NOMEM; }
-        h->robots_cap = (size_t)length;
-    }
+    if ((size_t)length > h->robots_cap) { h->robots = nullptr; h->robots_len = 0; }
+    rc = grow(h, h->robots_own, h->robots_cap, (size_t)length, nullptr, "hipMalloc robot records");
+    if (rc != SRBDQP_OK) return rc;
     HIP_TRY(h, hipMemcpy(h->robots_own, host, sizeof(srbdqp_robot) * (size_t)length, hipMemcpyHostToDevice));
     h->robots = h->robots_own; h->robots_len = (size_t)length;
     return SRBDQP_OK;
@@ -1404,7 +1440,7 @@ namespace {
 // behind an event -- beside whatever the caller enqueues next, e.g. the next batch's first pass -- each taking the list of QPs the pass before it left at its cap
 // as its dispatch order (working workgroups first; the rest of the grid leaves after one scalar load).  Outputs of the continued QPs arrive when the tail
 // stream gets there; srbdqp_flush() makes the caller's stream wait for it.
-int solve_deferred_passes(srbdqp_handle* h, const KArgs& a, hipStream_t lst, int maxs, int restart, int rcount) {
+int solve_deferred_passes(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t lst, int restart, int rcount) {
     auto* slot = stream_slot(h, lst);
     if (!slot) return SRBDQP_E_INVALID;
     const size_t m = 20 * (size_t)h->cfg.horizon;
@@ -1426,24 +1462,17 @@ int solve_deferred_passes(srbdqp_handle* h, const KArgs& a, hipStream_t lst, int
     if (!a1.y_out) { a1.y_out = set.ybuf; a1.y_capped_only = 1; }
     if (!a1.status) a1.status = set.stbuf;
     a1.cap_list = set.list[0]; a1.cap_count = set.cnt;
-    rc = launch(h, a1, lst, maxs, 1);
+    rc = launch(h, c, a1, lst, 1);
     if (rc != SRBDQP_OK) return rc;
     HIP_TRY(h, hipEventRecord(slot->ev_main, lst));
     HIP_TRY(h, hipStreamWaitEvent(slot->tail_st, slot->ev_main, 0));
     for (int p = 1; p <= rcount; ++p) {
-        const int done = p * restart, left = h->cfg.max_iter - done;
-        const bool last = p >= rcount || restart >= left;
-        KArgs a2 = a1;
-        a2.resid_in = set.resid; a2.resid_out = last ? nullptr : set.resid;
-        a2.warm_u = a1.u_out; a2.warm_y = a1.y_out;
-        a2.max_iter = last ? left : restart; a2.iters_base = done;
-        a2.rho_qp = (p == 1) ? a1.rho_qp : set.rhobuf[p % 2];
-        a2.rho_out = last ? nullptr : set.rhobuf[(p + 1) % 2];
-        a2.perm = set.list[p - 1]; a2.count_ptr = set.cnt + (p - 1);
-        a2.cap_list = last ? nullptr : set.list[p]; a2.cap_count = last ? nullptr : set.cnt + p;
-        rc = launch(h, a2, slot->tail_st, maxs, 2);
+        Pass pass = restart_pass(a1, p, rcount, h->cfg.max_iter, set.rhobuf);
+        pass.a.perm = set.list[p - 1]; pass.a.count_ptr = set.cnt + (p - 1);
+        pass.a.cap_list = pass.last ? nullptr : set.list[p]; pass.a.cap_count = pass.last ? nullptr : set.cnt + p;
+        rc = launch(h, c, pass.a, slot->tail_st, 2);
         if (rc != SRBDQP_OK) return rc;
-        if (last) break;
+        if (pass.last) break;
     }
     HIP_TRY(h, hipEventRecord(set.ev_tail, slot->tail_st));
     set.ev_used = true;
@@ -1451,47 +1480,37 @@ int solve_deferred_passes(srbdqp_handle* h, const KArgs& a, hipStream_t lst, int
     return SRBDQP_OK;
 }
 
-// common body of the device-buffer entry points; the element type of the caller's buffers is h->io_f32 ? float : double
-int solve_device_impl(srbdqp_handle* h, int32_t B, const void* x0, const void* x_ref, const void* foot, const uint8_t* contact,
+// common body of the device-buffer entry points; the element type of the caller's buffers is c.f32 ? float : double
+int solve_device_impl(srbdqp_handle* h, const Call& c, int32_t B, const void* x0, const void* x_ref, const void* foot, const uint8_t* contact,
                       const void* pcom, const void* warm_u, const void* warm_y, void* u_out, void* x_out, void* y_out,
                       int32_t* status, int32_t* iters, void* stream) {
     if (B < 0 || (B > 0 && (!x0 || !x_ref || !foot || !contact || !u_out))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (!h->staged_call) {
+    if (!c.staged) {
         const int rq = aql_quiesce(h);
         if (rq != SRBDQP_OK) return rq;
     }
-    KArgs a;
-    std::memset(&a, 0, sizeof(a));
-    fill_args(h->cfg, a);
-    a.x0 = static_cast<const double*>(x0); a.xref = static_cast<const double*>(x_ref); a.foot = static_cast<const double*>(foot);
-    a.contact = contact; a.pcom = static_cast<const double*>(pcom);
+    KArgs a = base_args(h->cfg, B, x0, x_ref, foot, contact, pcom);
     a.warm_u = static_cast<const double*>(warm_u); a.warm_y = static_cast<const double*>(warm_y);
     a.u_out = static_cast<double*>(u_out); a.x_out = static_cast<double*>(x_out); a.y_out = static_cast<double*>(y_out);
     a.status = status; a.iters = iters;
-    a.B = B; a.mode = 0; a.stamps = h->stamps;
-    if (h->signal_next) { a.done_flag = h->done_dev; a.done_count = h->done_count; a.done_value = h->done_seq; }
+    a.stamps = h->stamps;
+    if (c.signal) signal_args(h, a);
     hipStream_t lst = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
-    if (h->sched_hint && B > 1 && (size_t)B <= h->sched_hint_len) {
+    if (c.use_hint && h->sched_hint && B > 1 && (size_t)B <= h->sched_hint_len) {
         auto* slot = stream_slot(h, lst);
         if (!slot) return SRBDQP_E_INVALID;
-        if ((size_t)B > slot->perm_cap) {
-            HIP_TRY(h, hipStreamSynchronize(lst));          // a previous launch on this stream may still read the old order
-            if (slot->perm) HIP_TRY(h, hipFree(slot->perm));
-            slot->perm = nullptr; slot->perm_cap = 0;
-            HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&slot->perm), sizeof(int32_t) * (size_t)B));
-            slot->perm_cap = (size_t)B;
-        }
+        const int rc = grow(h, slot->perm, slot->perm_cap, (size_t)B, lst, "hipMalloc dispatch order");   // (a previous launch on this stream may still read the old order)
+        if (rc != SRBDQP_OK) return rc;
         hipLaunchKernelGGL(srbdqp_schedule_kernel, dim3(1), dim3(1024), 0, lst, h->sched_hint, slot->perm, (int)B);
         a.perm = slot->perm;
     }
-    int maxs = h->maxs_override ? h->maxs_override : (h->cfg.max_contacts_per_step > 0 ? h->cfg.max_contacts_per_step : 4);
-    h->lazy_pending = false;
-    const bool wave = uses_wave(h, maxs, B, a.stamps != nullptr, a.done_flag != nullptr);
+    const int maxs = c.maxs;
+    const bool wave = uses_wave(h, c, maxs, B, a.stamps != nullptr, a.done_flag != nullptr);
     int rcount = 1;
-    const int restart = (h->stamps || B < 1) ? 0 : restart_iter_of(h, maxs, B, wave, &rcount);
+    const int restart = (h->stamps || B < 1) ? 0 : restart_iter_of(h, &rcount);
     if (restart && wave) { a.restart_every = restart; a.restart_max = rcount; }   // the one-wave kernel restarts in place
-    if (restart && wave && (h->cfg.flags & SRBDQP_FLAG_DEFER_TAIL) && !a.stamps && !a.done_flag && !h->io_f32 && rcount <= srbdqp_handle::StreamSlot::kTailHist) {
+    if (restart && wave && (h->cfg.flags & SRBDQP_FLAG_DEFER_TAIL) && !a.stamps && !a.done_flag && !c.f32 && rcount <= srbdqp_handle::StreamSlot::kTailHist) {
         // ... or not at all: continuations deferred to the next launch on this stream (srbdqp_flush() completes them)
         auto* slot = stream_slot(h, lst);
         if (!slot) return SRBDQP_E_INVALID;
@@ -1499,8 +1518,8 @@ int solve_device_impl(srbdqp_handle* h, int32_t B, const void* x0, const void* x
         if (rc != SRBDQP_OK) return rc;
         return launch_wave_defer_any(h, a, lst, slot, maxs);
     }
-    if (!restart || wave) return launch(h, a, lst, maxs);
-    if ((h->cfg.flags & SRBDQP_FLAG_DEFER_TAIL) && !h->lazy_restart && !a.stamps && !a.done_flag && rcount <= 3) return solve_deferred_passes(h, a, lst, maxs, restart, rcount);
+    if (!restart || wave) return launch(h, c, a, lst);
+    if ((h->cfg.flags & SRBDQP_FLAG_DEFER_TAIL) && !c.lazy && !a.stamps && !a.done_flag && rcount <= 3) return solve_deferred_passes(h, c, a, lst, restart, rcount);
 
     // ---- several passes: cap the first at rho_restart_iter, re-balance rho for the QPs that reach it, continue those (up to rcount times)
     auto* slot = stream_slot(h, lst);
@@ -1512,29 +1531,27 @@ int solve_device_impl(srbdqp_handle* h, int32_t B, const void* x0, const void* x
     //  rotation, and a staged or completion-word solve on the same stream comes through here -- it must not overwrite what a tail pass still reads)
     if (slot->rs_nsets > 1)
         for (auto& r : slot->rsets) if (r.ev_used) HIP_TRY(h, hipStreamWaitEvent(lst, r.ev_tail, 0));
-    const bool lazy = h->lazy_restart;                      // staged path: the host looks at status[] before a second pass
     KArgs a1 = a;
     a1.max_iter = restart;
     a1.resid_out = slot->resid;
     if (!a1.y_out) { a1.y_out = slot->ybuf; a1.y_capped_only = 1; }
     if (!a1.status) a1.status = slot->stbuf;
-    if (!lazy) { a1.done_flag = nullptr; a1.done_count = nullptr; }
-    if (lazy && slot->ubuf && !h->io_f32) a1.u_dev = slot->ubuf;   // (the staged arrays are host memory: the pass behind this one reads its warm start on the device)
-    rc = launch(h, a1, lst, maxs, lazy ? 0 : 1);
-    if (lazy) { h->last_args = a1; h->lazy_pending = (rc == SRBDQP_OK); h->lazy_rcount = rcount; h->lazy_slot = slot; }
-    if (rc != SRBDQP_OK || lazy) return rc;
+    if (!c.lazy) { a1.done_flag = nullptr; a1.done_count = nullptr; }
+    if (c.lazy && slot->ubuf && !c.f32) a1.u_dev = slot->ubuf;   // (the staged arrays are host memory: the pass behind this one reads its warm start on the device)
+    rc = launch(h, c, a1, lst, c.lazy ? 0 : 1);
+    if (c.lazy) { c.lazy->a1 = a1; c.lazy->rcount = rcount; c.lazy->slot = slot; c.lazy->pending = (rc == SRBDQP_OK); }   // (staged path: the host looks at status[] before a second pass)
+    if (rc != SRBDQP_OK || c.lazy) return rc;
     for (int p = 1; p <= rcount; ++p) {
-        bool last = true;
-        const int every = a1.max_iter;
-        const bool is_last = p >= rcount || every >= h->cfg.max_iter - p * every;
-        rc = srbdqp_restart_pass(h, a1, lst, maxs, is_last && a.done_flag != nullptr, slot, p, rcount, &last);
-        if (rc != SRBDQP_OK || last) break;
+        Pass pass = restart_pass(a1, p, rcount, h->cfg.max_iter, slot->rhobuf);
+        if (pass.last && a.done_flag) signal_args(h, pass.a);
+        rc = launch(h, c, pass.a, lst, 2);
+        if (rc != SRBDQP_OK || pass.last) break;
     }
     return rc;
 }
 
 // common body of the host-buffer entry points (esz = sizeof the caller's element type)
-int solve_host_impl(srbdqp_handle* h, int32_t B, size_t esz, const void* x0, const void* x_ref, const void* foot,
+int solve_host_impl(srbdqp_handle* h, bool f32, int32_t B, const void* x0, const void* x_ref, const void* foot,
                     const uint8_t* contact, const void* pcom, const void* warm_u, const void* warm_y, void* u_out,
                     void* x_out, void* y_out, int32_t* status, int32_t* iters) {
     if (B < 0 || (B > 0 && (!x0 || !x_ref || !foot || !contact || !u_out))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
@@ -1544,60 +1561,32 @@ int solve_host_impl(srbdqp_handle* h, int32_t B, size_t esz, const void* x0, con
         const int rq = aql_quiesce(h);
         if (rq != SRBDQP_OK) return rq;
     }
-    const size_t N = (size_t)h->cfg.horizon, n = 12 * N, m = 20 * N, b = (size_t)B;
-    Carver sz(nullptr);
-    auto carve = [&](Carver& c, char*& dx0, char*& dxr, char*& dft, uint8_t*& dct, char*& dpc, char*& dwu,
-                     char*& dwy, char*& du, char*& dx, char*& dy, int32_t*& dst, int32_t*& dit) {
-        dx0 = c.take<char>(b * 13 * esz); dxr = c.take<char>(b * N * 13 * esz); dft = c.take<char>(b * N * 12 * esz);
-        dct = c.take<uint8_t>(b * N * 4);
-        dpc = pcom ? c.take<char>(b * N * 3 * esz) : nullptr;
-        dwu = warm_u ? c.take<char>(b * n * esz) : nullptr;
-        dwy = warm_y ? c.take<char>(b * m * esz) : nullptr;
-        du = c.take<char>(b * n * esz);
-        dx = x_out ? c.take<char>(b * (N + 1) * 13 * esz) : nullptr;
-        dy = y_out ? c.take<char>(b * m * esz) : nullptr;
-        dst = c.take<int32_t>(b); dit = c.take<int32_t>(b);
-    };
+    const size_t N = (size_t)h->cfg.horizon, n = 12 * N, m = 20 * N, b = (size_t)B, esz = f32 ? sizeof(float) : sizeof(double);
+    Call c;                        // (no dispatch hint: it belongs to the device-buffer API)
+    c.f32 = f32;
+    c.maxs = h->cfg.max_contacts_per_step > 0 ? h->cfg.max_contacts_per_step
+                                              : scan_contacts(contact, b, N, false).maxs();   // the instantiation from the batch's own contact flags
     char *dx0, *dxr, *dft, *dpc, *dwu, *dwy, *du, *dx, *dy; uint8_t* dct; int32_t *dst, *dit;
-    carve(sz, dx0, dxr, dft, dct, dpc, dwu, dwy, du, dx, dy, dst, dit);
-    int rc = ensure_ws(h, sz.off);
-    if (rc != SRBDQP_OK) return rc;
-    Carver cv(h->ws);
-    carve(cv, dx0, dxr, dft, dct, dpc, dwu, dwy, du, dx, dy, dst, dit);
-    hipStream_t st = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(dx0, x0, b * 13 * esz, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dxr, x_ref, b * N * 13 * esz, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dft, foot, b * N * 12 * esz, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dct, contact, b * N * 4, hipMemcpyHostToDevice, st));
-    if (pcom) HIP_TRY(h, hipMemcpyAsync(dpc, pcom, b * N * 3 * esz, hipMemcpyHostToDevice, st));
-    if (warm_u) HIP_TRY(h, hipMemcpyAsync(dwu, warm_u, b * n * esz, hipMemcpyHostToDevice, st));
-    if (warm_y) HIP_TRY(h, hipMemcpyAsync(dwy, warm_y, b * m * esz, hipMemcpyHostToDevice, st));
-    if (h->cfg.max_contacts_per_step <= 0) {   // pick the kernel instantiation from the batch's own contact flags
-        int worst = 0;
-        for (size_t q = 0; q < b * N && worst <= 2; ++q) {
-            const uint8_t* c = contact + 4 * q;
-            const int cnt = (c[0] != 0) + (c[1] != 0) + (c[2] != 0) + (c[3] != 0);
-            if (cnt > worst) worst = cnt;
-        }
-        h->maxs_override = (worst <= 2) ? 2 : 4;
-    }
-    const int32_t* hint_keep = h->sched_hint;               // the dispatch hint belongs to the device-buffer API
-    h->sched_hint = nullptr;
-    rc = solve_device_impl(h, B, dx0, dxr, dft, dct, dpc, dwu, dwy, du, dx, dy, dst, dit, st);
-    h->sched_hint = hint_keep;
-    h->maxs_override = 0;
-    if (rc != SRBDQP_OK) return rc;
-    if (h->cfg.flags & SRBDQP_FLAG_DEFER_TAIL) {            // a host-buffer call returns finished results: whatever was deferred runs now
-        rc = srbdqp_flush(h, st);
-        if (rc != SRBDQP_OK) return rc;
-    }
-    HIP_TRY(h, hipMemcpyAsync(u_out, du, b * n * esz, hipMemcpyDeviceToHost, st));
-    if (x_out) HIP_TRY(h, hipMemcpyAsync(x_out, dx, b * (N + 1) * 13 * esz, hipMemcpyDeviceToHost, st));
-    if (y_out) HIP_TRY(h, hipMemcpyAsync(y_out, dy, b * m * esz, hipMemcpyDeviceToHost, st));
-    if (status) HIP_TRY(h, hipMemcpyAsync(status, dst, b * 4, hipMemcpyDeviceToHost, st));
-    if (iters) HIP_TRY(h, hipMemcpyAsync(iters, dit, b * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    return SRBDQP_OK;
+    return host_call(h, [&](HostIo& io) {
+        dx0 = io.in(x0, b * 13 * esz); dxr = io.in(x_ref, b * N * 13 * esz); dft = io.in(foot, b * N * 12 * esz);
+        dct = io.in<uint8_t>(contact, b * N * 4);
+        dpc = io.in(pcom, b * N * 3 * esz); dwu = io.in(warm_u, b * n * esz); dwy = io.in(warm_y, b * m * esz);
+        du = io.out(u_out, b * n * esz); dx = io.out(x_out, b * (N + 1) * 13 * esz); dy = io.out(y_out, b * m * esz);
+        dst = io.out<int32_t>(status, b * 4, true); dit = io.out<int32_t>(iters, b * 4, true);
+    }, [&](hipStream_t st) {
+        int rc = solve_device_impl(h, c, B, dx0, dxr, dft, dct, dpc, dwu, dwy, du, dx, dy, dst, dit, st);
+        if (rc == SRBDQP_OK && (h->cfg.flags & SRBDQP_FLAG_DEFER_TAIL)) rc = srbdqp_flush(h, st);   // a host-buffer call returns finished results: whatever was deferred runs now
+        return rc;
+    });
+}
+
+// a device-buffer solve: the dispatch hint applies, the stance-contact bound is the config's (4 where it leaves it open)
+Call device_call(const srbdqp_handle* h, bool f32) {
+    Call c;
+    c.f32 = f32;
+    c.maxs = maxs_or(h->cfg, 4);
+    c.use_hint = true;
+    return c;
 }
 
 }  // namespace
@@ -1611,8 +1600,7 @@ int srbdqp_solve_batch_device_f64(srbdqp_handle* h, int32_t B, const double* x0,
     if (!h) return SRBDQP_E_INVALID;
     const int rr = robots_check_batch(h, B);
     if (rr != SRBDQP_OK) return rr;
-    h->io_f32 = false;
-    return solve_device_impl(h, B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
+    return solve_device_impl(h, device_call(h, false), B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
 }
 
 int srbdqp_solve_batch_device_f32(srbdqp_handle* h, int32_t B, const float* x0, const float* x_ref,
@@ -1621,10 +1609,7 @@ int srbdqp_solve_batch_device_f32(srbdqp_handle* h, int32_t B, const float* x0, 
                                   float* y_out, int32_t* status, int32_t* iters, void* stream) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_solve_batch_device_f32");
-    h->io_f32 = true;
-    const int rc = solve_device_impl(h, B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
-    h->io_f32 = false;
-    return rc;
+    return solve_device_impl(h, device_call(h, true), B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
 }
 
 int srbdqp_solve_batch_f64(srbdqp_handle* h, int32_t B, const double* x0, const double* x_ref, const double* foot,
@@ -1633,8 +1618,7 @@ int srbdqp_solve_batch_f64(srbdqp_handle* h, int32_t B, const double* x0, const 
     if (!h) return SRBDQP_E_INVALID;
     const int rr = robots_check_batch(h, B);
     if (rr != SRBDQP_OK) return rr;
-    h->io_f32 = false;
-    return solve_host_impl(h, B, sizeof(double), x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters);
+    return solve_host_impl(h, false, B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters);
 }
 
 int srbdqp_solve_batch_f32(srbdqp_handle* h, int32_t B, const float* x0, const float* x_ref, const float* foot,
@@ -1642,10 +1626,7 @@ int srbdqp_solve_batch_f32(srbdqp_handle* h, int32_t B, const float* x0, const f
                            float* u_out, float* x_out, float* y_out, int32_t* status, int32_t* iters) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_solve_batch_f32");
-    h->io_f32 = true;
-    const int rc = solve_host_impl(h, B, sizeof(float), x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters);
-    h->io_f32 = false;
-    return rc;
+    return solve_host_impl(h, true, B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters);
 }
 
 int srbdqp_assemble_f64(srbdqp_handle* h, int32_t B, const double* x0, const double* x_ref, const double* foot,
@@ -1657,51 +1638,26 @@ int srbdqp_assemble_f64(srbdqp_handle* h, int32_t B, const double* x0, const dou
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t N = (size_t)h->cfg.horizon, n = 12 * N, m = 20 * N, b = (size_t)B;
-    int maxs = h->cfg.max_contacts_per_step > 0 ? h->cfg.max_contacts_per_step : 4;
-    if (h->cfg.max_contacts_per_step <= 0) {   // as the host-buffer solve: the instantiation follows the batch's own contact flags
-        int worst = 0;
-        for (size_t q = 0; q < b * N && worst <= 2; ++q) {
-            const uint8_t* c = contact + 4 * q;
-            const int cnt = (c[0] != 0) + (c[1] != 0) + (c[2] != 0) + (c[3] != 0);
-            if (cnt > worst) worst = cnt;
-        }
-        maxs = (worst <= 2) ? 2 : 4;
-    }
-    h->io_f32 = false;
-    if (uses_wrench(h, maxs, B)) { h->err = "this configuration solves on the general kernel: use srbdqp_assemble_wrench_f64"; return SRBDQP_E_INVALID; }
-    auto carve = [&](Carver& c, double*& dx0, double*& dxr, double*& dft, uint8_t*& dct, double*& dpc, double*& dP,
-                     double*& dq, double*& dl, double*& du) {
-        dx0 = c.take<double>(b * 13); dxr = c.take<double>(b * N * 13); dft = c.take<double>(b * N * 12);
-        dct = c.take<uint8_t>(b * N * 4);
-        dpc = pcom ? c.take<double>(b * N * 3) : nullptr;
-        dP = c.take<double>(b * n * n); dq = c.take<double>(b * n); dl = c.take<double>(b * m); du = c.take<double>(b * m);
-    };
+    Call c;                        // as the host-buffer solve: the instantiation follows the batch's own contact flags
+    c.maxs = h->cfg.max_contacts_per_step > 0 ? h->cfg.max_contacts_per_step : scan_contacts(contact, b, N, false).maxs();
+    if (uses_wrench(h, c, c.maxs, B)) { h->err = "this configuration solves on the general kernel: use srbdqp_assemble_wrench_f64"; return SRBDQP_E_INVALID; }
     double *dx0, *dxr, *dft, *dpc, *dP, *dq, *dl, *du; uint8_t* dct;
-    Carver sz(nullptr);
-    carve(sz, dx0, dxr, dft, dct, dpc, dP, dq, dl, du);
-    int rc = ensure_ws(h, sz.off);
+    int rc = host_call(h, [&](HostIo& io) {
+        dx0 = io.in<double>(x0, b * 13 * 8); dxr = io.in<double>(x_ref, b * N * 13 * 8); dft = io.in<double>(foot, b * N * 12 * 8);
+        dct = io.in<uint8_t>(contact, b * N * 4); dpc = io.in<double>(pcom, b * N * 3 * 8);
+        dP = io.zeroed<double>(nullptr, b * n * n * 8); dq = io.zeroed<double>(nullptr, b * n * 8);
+        dl = io.zeroed<double>(nullptr, b * m * 8); du = io.zeroed<double>(nullptr, b * m * 8);
+    }, [&](hipStream_t st) {
+        KArgs a = base_args(h->cfg, B, dx0, dxr, dft, dct, dpc);
+        a.P_out = dP; a.q_out = dq; a.l_out = dl; a.ub_out = du;
+        a.mode = 1;
+        const int rl = launch(h, c, a, st);              // the kernel a solve of this batch would run, stopped before its factorisation
+        if (rl != SRBDQP_OK) return rl;
+        HIP_TRY(h, hipGetLastError());
+        return SRBDQP_OK;
+    });
     if (rc != SRBDQP_OK) return rc;
-    Carver cv(h->ws);
-    carve(cv, dx0, dxr, dft, dct, dpc, dP, dq, dl, du);
     hipStream_t st = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(dx0, x0, b * 13 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dxr, x_ref, b * N * 13 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dft, foot, b * N * 12 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dct, contact, b * N * 4, hipMemcpyHostToDevice, st));
-    if (pcom) HIP_TRY(h, hipMemcpyAsync(dpc, pcom, b * N * 3 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemsetAsync(dP, 0, b * n * n * 8, st));
-    HIP_TRY(h, hipMemsetAsync(dq, 0, b * n * 8, st));
-    HIP_TRY(h, hipMemsetAsync(dl, 0, b * m * 8, st));
-    HIP_TRY(h, hipMemsetAsync(du, 0, b * m * 8, st));
-    KArgs a;
-    std::memset(&a, 0, sizeof(a));
-    fill_args(h->cfg, a);
-    a.x0 = dx0; a.xref = dxr; a.foot = dft; a.contact = dct; a.pcom = dpc;
-    a.P_out = dP; a.q_out = dq; a.l_out = dl; a.ub_out = du;
-    a.B = B; a.mode = 1;
-    rc = launch(h, a, st, maxs);                 // the kernel a solve of this batch would run, stopped before its factorisation
-    if (rc != SRBDQP_OK) return rc;
-    HIP_TRY(h, hipGetLastError());
     // compact K, q, map -> full-size P, q in the original variable order (on the host: bookkeeping, not the hot path)
     std::vector<double> K(n * n), qc(n), mp(m);
     const double rho = h->cfg.rho, aa = 4.0 * h->cfg.mu * h->cfg.mu + h->cfg.rho_fz_scale, sc = h->cfg.force_scale;
@@ -1757,54 +1713,18 @@ int srbdqp_assemble_wrench_f64(srbdqp_handle* h, int32_t B, const double* x0, co
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t N = (size_t)h->cfg.horizon, n = 12 * N, ng = 6 * N, b = (size_t)B;
-    auto carve = [&](Carver& c, double*& dx0, double*& dxr, double*& dft, uint8_t*& dct, double*& dpc, double*& dT,
-                     double*& dq, double*& dbl, double*& dgo) {
-        dx0 = c.take<double>(b * 13); dxr = c.take<double>(b * N * 13); dft = c.take<double>(b * N * 12);
-        dct = c.take<uint8_t>(b * N * 4);
-        dpc = pcom ? c.take<double>(b * N * 3) : nullptr;
-        dT = c.take<double>(b * ng * ng); dq = c.take<double>(b * n); dbl = c.take<double>(b * n * 24); dgo = c.take<double>(b * (N + 1));
-    };
     double *dx0, *dxr, *dft, *dpc, *dT, *dq, *dbl, *dgo; uint8_t* dct;
-    Carver sz(nullptr);
-    carve(sz, dx0, dxr, dft, dct, dpc, dT, dq, dbl, dgo);
-    int rc = ensure_ws(h, sz.off);
-    if (rc != SRBDQP_OK) return rc;
-    Carver cv(h->ws);
-    carve(cv, dx0, dxr, dft, dct, dpc, dT, dq, dbl, dgo);
-    hipStream_t st = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(dx0, x0, b * 13 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dxr, x_ref, b * N * 13 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dft, foot, b * N * 12 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dct, contact, b * N * 4, hipMemcpyHostToDevice, st));
-    if (pcom) HIP_TRY(h, hipMemcpyAsync(dpc, pcom, b * N * 3 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemsetAsync(dT, 0, b * ng * ng * 8, st));
-    HIP_TRY(h, hipMemsetAsync(dq, 0, b * n * 8, st));
-    HIP_TRY(h, hipMemsetAsync(dbl, 0, b * n * 24 * 8, st));
-    HIP_TRY(h, hipMemsetAsync(dgo, 0, b * (N + 1) * 8, st));
-    KArgs a;
-    std::memset(&a, 0, sizeof(a));
-    fill_args(h->cfg, a);
-    a.x0 = dx0; a.xref = dxr; a.foot = dft; a.contact = dct; a.pcom = dpc;
-    a.P_out = dT; a.q_out = dq; a.l_out = dbl; a.ub_out = dgo;
-    a.B = B; a.mode = 1;
-    h->io_f32 = false;
-    switch (h->cfg.horizon) {
-        case 4: rc = launch_wrench<4>(h, a, st); break;
-        case 8: rc = launch_wrench<8>(h, a, st); break;
-        case 10: rc = launch_wrench<10>(h, a, st); break;
-        case 12: rc = launch_wrench<12>(h, a, st); break;
-        case 16: rc = launch_wrench<16>(h, a, st); break;
-        case 20: rc = launch_wrench<20>(h, a, st); break;
-        case 24: rc = launch_wrench<24>(h, a, st); break;
-        default: h->err = "unsupported horizon"; return SRBDQP_E_INVALID;
-    }
-    if (rc != SRBDQP_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(T_out, dT, b * ng * ng * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(q_out, dq, b * n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(blocks_out, dbl, b * n * 24 * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(goff_out, dgo, b * (N + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    return SRBDQP_OK;
+    return host_call(h, [&](HostIo& io) {
+        dx0 = io.in<double>(x0, b * 13 * 8); dxr = io.in<double>(x_ref, b * N * 13 * 8); dft = io.in<double>(foot, b * N * 12 * 8);
+        dct = io.in<uint8_t>(contact, b * N * 4); dpc = io.in<double>(pcom, b * N * 3 * 8);
+        dT = io.zeroed<double>(T_out, b * ng * ng * 8); dq = io.zeroed<double>(q_out, b * n * 8);
+        dbl = io.zeroed<double>(blocks_out, b * n * 24 * 8); dgo = io.zeroed<double>(goff_out, b * (N + 1) * 8);
+    }, [&](hipStream_t st) {
+        KArgs a = base_args(h->cfg, B, dx0, dxr, dft, dct, dpc);
+        a.P_out = dT; a.q_out = dq; a.l_out = dbl; a.ub_out = dgo;
+        a.mode = 1;
+        return launch_wrench(h, Call(), a, st);
+    });
 }
 
 // ---- ragged batches (BASELINE.json configs[4]): mixed horizons, one launch per horizon bucket, all in flight together ----
@@ -1843,22 +1763,6 @@ struct srbdqp_ragged {
 
 namespace {
 std::string g_ragged_err;
-#define RAG_TRY(r, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (r)->err = std::string(#call) + ": " + hipGetErrorString(e_); return SRBDQP_E_HIP; } } while (0)
-
-int ragged_launch_bucket(srbdqp_handle* bh, const KArgs& a, hipStream_t st, bool f32) {
-    bh->io_f32 = f32;
-    struct Reset { srbdqp_handle* h; ~Reset() { h->io_f32 = false; } } reset_on_return{bh};
-    switch (bh->cfg.horizon) {
-        case 4: return launch_wrench<4>(bh, a, st);
-        case 8: return launch_wrench<8>(bh, a, st);
-        case 10: return launch_wrench<10>(bh, a, st);
-        case 12: return launch_wrench<12>(bh, a, st);
-        case 16: return launch_wrench<16>(bh, a, st);
-        case 20: return launch_wrench<20>(bh, a, st);
-        case 24: return launch_wrench<24>(bh, a, st);
-        default: bh->err = "unsupported horizon"; return SRBDQP_E_INVALID;
-    }
-}
 }  // namespace
 
 int srbdqp_ragged_create(const srbdqp_config* cfg, const int32_t* horizons, int32_t n_horizons, srbdqp_ragged** out) {
@@ -1947,13 +1851,13 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
         return SRBDQP_E_INVALID;
     }
     if (B == 0) return SRBDQP_OK;
-    RAG_TRY(r, hipSetDevice(r->device));
+    HIP_TRY(r, hipSetDevice(r->device));
     hipStream_t sin = stream ? reinterpret_cast<hipStream_t>(stream) : r->stream;
     const size_t nb = r->hs.size();
     if ((size_t)B > r->cap) {   // (re)allocate the index arrays: the only point that waits, and only for earlier solves of this object
-        for (auto* h : r->hs) RAG_TRY(r, hipStreamSynchronize(h->stream));
-        for (auto ts : r->tail_st) RAG_TRY(r, hipStreamSynchronize(ts));
-        RAG_TRY(r, hipStreamSynchronize(sin));
+        for (auto* h : r->hs) HIP_TRY(r, hipStreamSynchronize(h->stream));
+        for (auto ts : r->tail_st) HIP_TRY(r, hipStreamSynchronize(ts));
+        HIP_TRY(r, hipStreamSynchronize(sin));
         std::fill(r->ev_tail_used.begin(), r->ev_tail_used.end(), 0);
         if (r->d_perm) (void)hipFree(r->d_perm);
         if (r->d_off) (void)hipFree(r->d_off);
@@ -1962,21 +1866,21 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
         r->d_perm = r->d_off = r->h_perm = r->h_off = nullptr; r->cap = 0;
         const size_t want = (size_t)B + (size_t)B / 4 + 64;
         const size_t ns = r->defer ? (size_t)srbdqp_ragged::kSets : 1;
-        RAG_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_perm), ns * want * 4));
-        RAG_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_off), ns * want * 4));
-        RAG_TRY(r, hipHostMalloc(reinterpret_cast<void**>(&r->h_perm), want * 4, hipHostMallocDefault));
-        RAG_TRY(r, hipHostMalloc(reinterpret_cast<void**>(&r->h_off), want * 4, hipHostMallocDefault));
+        HIP_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_perm), ns * want * 4));
+        HIP_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_off), ns * want * 4));
+        HIP_TRY(r, hipHostMalloc(reinterpret_cast<void**>(&r->h_perm), want * 4, hipHostMallocDefault));
+        HIP_TRY(r, hipHostMalloc(reinterpret_cast<void**>(&r->h_off), want * 4, hipHostMallocDefault));
         if (r->d_resid) (void)hipFree(r->d_resid);
         if (r->d_status) (void)hipFree(r->d_status);
         if (r->d_rho) (void)hipFree(r->d_rho);
         r->d_resid = nullptr; r->d_status = nullptr; r->d_rho = nullptr;
-        RAG_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_resid), ns * want * 16));
-        RAG_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_status), ns * want * 4));
-        RAG_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_rho), ns * 2 * want * sizeof(double)));
+        HIP_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_resid), ns * want * 16));
+        HIP_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_status), ns * want * 4));
+        HIP_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_rho), ns * 2 * want * sizeof(double)));
         r->cap = want;
         r->ev_in_pending = false;
     }
-    if (r->ev_in_pending) RAG_TRY(r, hipEventSynchronize(r->ev_in));   // the previous call's index upload has left the pinned mirrors
+    if (r->ev_in_pending) HIP_TRY(r, hipEventSynchronize(r->ev_in));   // the previous call's index upload has left the pinned mirrors
     // bucket permutation (counting sort by horizon) and the packed row offsets
     std::vector<int> cnt(nb, 0), start(nb + 1, 0), which((size_t)B);
     long long rows = 0;
@@ -1991,94 +1895,86 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
     }
     for (size_t i = 0; i < nb; ++i) start[i + 1] = start[i] + cnt[i];
     bool any_restart = false;
-    for (size_t i = 0; i < nb; ++i) any_restart = any_restart || (cnt[i] > 0 && restart_iter_of(r->hs[i], 4, cnt[i]) > 0);
+    for (size_t i = 0; i < nb; ++i) any_restart = any_restart || (cnt[i] > 0 && restart_iter_of(r->hs[i]) > 0);
     if (any_restart && (size_t)rows > r->row_cap) {   // dual buffer of the restart (waits for earlier solves of this object only)
-        for (auto* h : r->hs) RAG_TRY(r, hipStreamSynchronize(h->stream));
-        for (auto ts : r->tail_st) RAG_TRY(r, hipStreamSynchronize(ts));
+        for (auto* h : r->hs) HIP_TRY(r, hipStreamSynchronize(h->stream));
+        for (auto ts : r->tail_st) HIP_TRY(r, hipStreamSynchronize(ts));
         if (r->d_y) (void)hipFree(r->d_y);
         r->d_y = nullptr; r->row_cap = 0;
         const size_t want = (size_t)rows + (size_t)rows / 4 + 64;
-        RAG_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_y), (r->defer ? (size_t)srbdqp_ragged::kSets : 1) * want * 20 * sizeof(double)));
+        HIP_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_y), (r->defer ? (size_t)srbdqp_ragged::kSets : 1) * want * 20 * sizeof(double)));
         r->row_cap = want;
     }
     std::vector<int> fill(start.begin(), start.end() - 1);
     for (int32_t b = 0; b < B; ++b) r->h_perm[fill[(size_t)which[(size_t)b]]++] = b;
     // the index arrays (and the restart buffers) are shared by the calls of this object: the upload below must not overtake the
     // bucket kernels of an earlier call made on ANOTHER caller stream (calls on one stream are ordered through ev_out already)
-    for (size_t i = 0; i < nb; ++i) if (r->ev_out_used[i]) RAG_TRY(r, hipStreamWaitEvent(sin, r->ev_out[i], 0));
+    for (size_t i = 0; i < nb; ++i) if (r->ev_out_used[i]) HIP_TRY(r, hipStreamWaitEvent(sin, r->ev_out[i], 0));
     // this call's set of the shared arrays (deferred restart passes: three in rotation; behind the passes of the set's last user)
     const size_t set = r->defer ? (size_t)(r->call_k++ % srbdqp_ragged::kSets) : 0;
     if (r->defer)
         for (size_t i = 0; i < nb; ++i)
-            if (r->ev_tail_used[set * nb + i]) RAG_TRY(r, hipStreamWaitEvent(sin, r->ev_tail[set * nb + i], 0));
+            if (r->ev_tail_used[set * nb + i]) HIP_TRY(r, hipStreamWaitEvent(sin, r->ev_tail[set * nb + i], 0));
     int32_t* const d_off = r->d_off + set * r->cap;
     int32_t* const d_perm = r->d_perm + set * r->cap;
     float* const d_resid = r->d_resid + set * r->cap * 4;
     int32_t* const d_status = r->d_status + set * r->cap;
     double* const d_rho = r->d_rho + set * 2 * r->cap;
     double* const d_y = r->d_y ? r->d_y + set * r->row_cap * 20 : nullptr;
-    RAG_TRY(r, hipMemcpyAsync(d_off, r->h_off, (size_t)B * 4, hipMemcpyHostToDevice, sin));
-    RAG_TRY(r, hipMemcpyAsync(d_perm, r->h_perm, (size_t)B * 4, hipMemcpyHostToDevice, sin));
-    RAG_TRY(r, hipEventRecord(r->ev_in, sin));
+    HIP_TRY(r, hipMemcpyAsync(d_off, r->h_off, (size_t)B * 4, hipMemcpyHostToDevice, sin));
+    HIP_TRY(r, hipMemcpyAsync(d_perm, r->h_perm, (size_t)B * 4, hipMemcpyHostToDevice, sin));
+    HIP_TRY(r, hipEventRecord(r->ev_in, sin));
     r->ev_in_pending = true;
     // one launch per non-empty bucket, each on its engine's own stream behind the upload; the caller's stream then waits for all
+    Call c;
+    c.f32 = f32;
+    double* const rho[2] = {d_rho, d_rho + r->cap};
     for (size_t i = 0; i < nb; ++i) {
         if (cnt[i] == 0) continue;
         srbdqp_handle* bh = r->hs[i];
         hipStream_t bs = bh->stream;
-        RAG_TRY(r, hipStreamWaitEvent(bs, r->ev_in, 0));
-        KArgs a;
-        std::memset(&a, 0, sizeof(a));
-        fill_args(bh->cfg, a);
-        a.x0 = static_cast<const double*>(x0); a.xref = static_cast<const double*>(x_ref); a.foot = static_cast<const double*>(foot); a.contact = contact;
+        HIP_TRY(r, hipStreamWaitEvent(bs, r->ev_in, 0));
+        KArgs a = base_args(bh->cfg, cnt[i], x0, x_ref, foot, contact);
         a.warm_u = static_cast<const double*>(warm_u); a.warm_y = static_cast<const double*>(warm_y);
         a.u_out = static_cast<double*>(u_out); a.x_out = static_cast<double*>(x_out); a.y_out = static_cast<double*>(y_out);
         a.status = status; a.iters = iters;
         a.perm = d_perm + start[i]; a.row_off = d_off;
-        a.B = cnt[i]; a.mode = 0;
         int rcount = 1;
-        const int restart = restart_iter_of(bh, 4, cnt[i], false, &rcount);
+        const int restart = restart_iter_of(bh, &rcount);
         int rc;
         if (restart > 0) {   // several passes over the bucket, as srbdqp_solve_batch_* does (the later ones select their QPs in-kernel)
             KArgs a1 = a;
             a1.max_iter = restart; a1.resid_out = d_resid;
             if (!a1.y_out) { a1.y_out = d_y; a1.y_capped_only = 1; }   // (a later pass warm-starts from the duals of the pass before it)
             if (!a1.status) a1.status = d_status;
-            rc = ragged_launch_bucket(bh, a1, bs, f32);
+            rc = launch_wrench(bh, c, a1, bs);
             hipStream_t ps = bs;                                          // the stream the restart passes run on
             if (r->defer && rc == SRBDQP_OK) {
                 // ... the bucket's tail stream, behind its first pass: the caller's stream waits for the first pass only, the passes run beside what it enqueues next
-                RAG_TRY(r, hipEventRecord(r->ev_out[i], bs));
+                HIP_TRY(r, hipEventRecord(r->ev_out[i], bs));
                 r->ev_out_used[i] = 1;
-                RAG_TRY(r, hipStreamWaitEvent(sin, r->ev_out[i], 0));
+                HIP_TRY(r, hipStreamWaitEvent(sin, r->ev_out[i], 0));
                 ps = r->tail_st[i];
-                RAG_TRY(r, hipStreamWaitEvent(ps, r->ev_out[i], 0));
+                HIP_TRY(r, hipStreamWaitEvent(ps, r->ev_out[i], 0));
             }
-            for (int p = 1; rc == SRBDQP_OK && p <= rcount; ++p) {        // (srbdqp_restart_pass, on the ragged object's own buffers)
-                const int done = p * restart, left = bh->cfg.max_iter - done;
-                const bool last = p >= rcount || restart >= left;
-                KArgs a2 = a1;
-                a2.resid_in = d_resid; a2.resid_out = last ? nullptr : d_resid;
-                a2.warm_u = a1.u_out; a2.warm_y = a1.y_out;
-                a2.max_iter = last ? left : restart; a2.iters_base = done;
-                a2.rho_qp = (p == 1) ? nullptr : d_rho + (size_t)(p % 2) * r->cap;
-                a2.rho_out = last ? nullptr : d_rho + (size_t)((p + 1) % 2) * r->cap;
-                rc = ragged_launch_bucket(bh, a2, ps, f32);
-                if (last) break;
+            for (int p = 1; rc == SRBDQP_OK && p <= rcount; ++p) {        // (restart_pass, on the ragged object's own buffers)
+                const Pass pass = restart_pass(a1, p, rcount, bh->cfg.max_iter, rho);
+                rc = launch_wrench(bh, c, pass.a, ps);
+                if (pass.last) break;
             }
             if (r->defer && rc == SRBDQP_OK) {
-                RAG_TRY(r, hipEventRecord(r->ev_tail[set * nb + i], ps));
+                HIP_TRY(r, hipEventRecord(r->ev_tail[set * nb + i], ps));
                 r->ev_tail_used[set * nb + i] = 1;
                 r->last_tail[i] = r->ev_tail[set * nb + i];
                 continue;                                                 // (ev_out was recorded behind the first pass)
             }
         } else {
-            rc = ragged_launch_bucket(bh, a, bs, f32);
+            rc = launch_wrench(bh, c, a, bs);
         }
         if (rc != SRBDQP_OK) { r->err = std::string("bucket N=") + std::to_string(r->horizons[i]) + ": " + bh->err; return rc; }
-        RAG_TRY(r, hipEventRecord(r->ev_out[i], bs));
+        HIP_TRY(r, hipEventRecord(r->ev_out[i], bs));
         r->ev_out_used[i] = 1;
-        RAG_TRY(r, hipStreamWaitEvent(sin, r->ev_out[i], 0));
+        HIP_TRY(r, hipStreamWaitEvent(sin, r->ev_out[i], 0));
     }
     return SRBDQP_OK;
 }
@@ -2089,41 +1985,19 @@ int ragged_host_impl(srbdqp_ragged* r, int32_t B, size_t esz, const int32_t* N_p
     if (!r) return SRBDQP_E_INVALID;
     if (B < 0 || (B > 0 && (!N_per_qp || !x0 || !x_ref || !foot || !contact || !u_out))) { r->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
-    RAG_TRY(r, hipSetDevice(r->device));
+    HIP_TRY(r, hipSetDevice(r->device));
     size_t rows = 0;
     for (int32_t b = 0; b < B; ++b) { if (N_per_qp[b] < 1 || N_per_qp[b] > SRBDQP_MAX_HORIZON) { r->err = "bad horizon in N_per_qp"; return SRBDQP_E_INVALID; } rows += (size_t)N_per_qp[b]; }
     const size_t b = (size_t)B;
-    Carver sz(nullptr);
     char *dx0, *dxr, *dft, *du, *dx; uint8_t* dct; int32_t *dst, *dit;
-    auto carve = [&](Carver& c) {
-        dx0 = c.take<char>(b * 13 * esz); dxr = c.take<char>(rows * 13 * esz); dft = c.take<char>(rows * 12 * esz); dct = c.take<uint8_t>(rows * 4);
-        du = c.take<char>(rows * 12 * esz); dx = x_out ? c.take<char>((rows + b) * 13 * esz) : nullptr;
-        dst = c.take<int32_t>(b); dit = c.take<int32_t>(b);
-    };
-    carve(sz);
-    if (sz.off > r->ws_bytes) {
-        RAG_TRY(r, hipStreamSynchronize(r->stream));
-        if (r->ws) { (void)hipFree(r->ws); r->ws = nullptr; r->ws_bytes = 0; }
-        RAG_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->ws), sz.off + sz.off / 4));
-        r->ws_bytes = sz.off + sz.off / 4;
-    }
-    Carver cv(r->ws);
-    carve(cv);
-    hipStream_t st = r->stream;
-    RAG_TRY(r, hipMemcpyAsync(dx0, x0, b * 13 * esz, hipMemcpyHostToDevice, st));
-    RAG_TRY(r, hipMemcpyAsync(dxr, x_ref, rows * 13 * esz, hipMemcpyHostToDevice, st));
-    RAG_TRY(r, hipMemcpyAsync(dft, foot, rows * 12 * esz, hipMemcpyHostToDevice, st));
-    RAG_TRY(r, hipMemcpyAsync(dct, contact, rows * 4, hipMemcpyHostToDevice, st));
-    int rc = ragged_device_impl(r, B, N_per_qp, dx0, dxr, dft, dct, nullptr, nullptr, du, dx, nullptr, dst, dit, st, esz == 4);
-    if (rc != SRBDQP_OK) return rc;
-    rc = srbdqp_ragged_flush(r, st);                     // (deferred restart passes: the copies below need every QP finished)
-    if (rc != SRBDQP_OK) return rc;
-    RAG_TRY(r, hipMemcpyAsync(u_out, du, rows * 12 * esz, hipMemcpyDeviceToHost, st));
-    if (x_out) RAG_TRY(r, hipMemcpyAsync(x_out, dx, (rows + b) * 13 * esz, hipMemcpyDeviceToHost, st));
-    if (status) RAG_TRY(r, hipMemcpyAsync(status, dst, b * 4, hipMemcpyDeviceToHost, st));
-    if (iters) RAG_TRY(r, hipMemcpyAsync(iters, dit, b * 4, hipMemcpyDeviceToHost, st));
-    RAG_TRY(r, hipStreamSynchronize(st));
-    return SRBDQP_OK;
+    return host_call(r, [&](HostIo& io) {
+        dx0 = io.in(x0, b * 13 * esz); dxr = io.in(x_ref, rows * 13 * esz); dft = io.in(foot, rows * 12 * esz); dct = io.in<uint8_t>(contact, rows * 4);
+        du = io.out(u_out, rows * 12 * esz); dx = io.out(x_out, (rows + b) * 13 * esz);
+        dst = io.out<int32_t>(status, b * 4, true); dit = io.out<int32_t>(iters, b * 4, true);
+    }, [&](hipStream_t st) {
+        const int rc = ragged_device_impl(r, B, N_per_qp, dx0, dxr, dft, dct, nullptr, nullptr, du, dx, nullptr, dst, dit, st, esz == 4);
+        return rc != SRBDQP_OK ? rc : srbdqp_ragged_flush(r, st);   // (deferred restart passes: the copies behind it need every QP finished)
+    });
 }
 }  // namespace
 
@@ -2148,21 +2022,17 @@ int srbdqp_ragged_set_robots(srbdqp_ragged* r, const srbdqp_robot* host, int32_t
         const int rv = robots_validate(host, length, "srbdqp_ragged_set_robots", r->err);
         if (rv != SRBDQP_OK) return rv;
     }
-    RAG_TRY(r, hipSetDevice(r->device));
+    HIP_TRY(r, hipSetDevice(r->device));
     // every pass that may still read the records this call replaces has completed: the buckets' streams (and their handles' slots), the deferred passes on the
     // tail streams, the object's own stream
     for (auto* h : r->hs) { const int rq = robots_quiesce(h); if (rq != SRBDQP_OK) { r->err = h->err; return rq; } }
-    for (auto ts : r->tail_st) RAG_TRY(r, hipStreamSynchronize(ts));
-    RAG_TRY(r, hipStreamSynchronize(r->stream));
+    for (auto ts : r->tail_st) HIP_TRY(r, hipStreamSynchronize(ts));
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
     if (clear) { r->robots = nullptr; r->robots_len = 0; return ragged_forward_robots(r); }
-    if ((size_t)length > r->robots_cap) {
-        if (r->robots_own) RAG_TRY(r, hipFree(r->robots_own));
-        r->robots_own = nullptr; r->robots_cap = 0; r->robots = nullptr; r->robots_len = 0;
-        (void)ragged_forward_robots(r);
-        RAG_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->robots_own), sizeof(srbdqp_robot) * (size_t)length));
-        r->robots_cap = (size_t)length;
-    }
-    RAG_TRY(r, hipMemcpy(r->robots_own, host, sizeof(srbdqp_robot) * (size_t)length, hipMemcpyHostToDevice));
+    if ((size_t)length > r->robots_cap) { r->robots = nullptr; r->robots_len = 0; (void)ragged_forward_robots(r); }   // (the buckets let go of the old copy)
+    const int rc = grow(r, r->robots_own, r->robots_cap, (size_t)length, nullptr, "hipMalloc robot records");
+    if (rc != SRBDQP_OK) return rc;
+    HIP_TRY(r, hipMemcpy(r->robots_own, host, sizeof(srbdqp_robot) * (size_t)length, hipMemcpyHostToDevice));
     r->robots = r->robots_own; r->robots_len = (size_t)length;
     return ragged_forward_robots(r);
 }
@@ -2179,12 +2049,12 @@ int srbdqp_ragged_set_robots_device(srbdqp_ragged* r, const srbdqp_robot* dev, i
 
 int srbdqp_ragged_flush(srbdqp_ragged* r, void* stream) {
     if (!r) return SRBDQP_E_INVALID;
-    RAG_TRY(r, hipSetDevice(r->device));
+    HIP_TRY(r, hipSetDevice(r->device));
     hipStream_t sin = stream ? reinterpret_cast<hipStream_t>(stream) : r->stream;
     // (the events stay: they are re-recorded by every call, waiting for a completed one costs nothing, and a caller that issued calls on two streams
     //  flushes each of them -- a flush of the other stream must still find the passes that write ITS outputs)
     for (auto& ev : r->last_tail)
-        if (ev) RAG_TRY(r, hipStreamWaitEvent(sin, ev, 0));
+        if (ev) HIP_TRY(r, hipStreamWaitEvent(sin, ev, 0));
     return SRBDQP_OK;
 }
 
@@ -2256,31 +2126,10 @@ int srbdqp_swing_f64(srbdqp_handle* h, int64_t B, const double* p_start, const d
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t b = (size_t)B;
     double *ds, *df, *dm, *dt, *dp, *dv, *da, *dc;
-    auto carve = [&](Carver& c) {
-        ds = c.take<double>(b * 3); df = c.take<double>(b * 3); dm = c.take<double>(b); dt = c.take<double>(b);
-        dp = c.take<double>(b * 3);
-        dv = vel_z ? c.take<double>(b) : nullptr; da = acc_z ? c.take<double>(b) : nullptr;
-        dc = coeff ? c.take<double>(b * 7) : nullptr;
-    };
-    Carver sz(nullptr);
-    carve(sz);
-    int rc = ensure_ws(h, sz.off);
-    if (rc != SRBDQP_OK) return rc;
-    Carver cv(h->ws);
-    carve(cv);
-    hipStream_t st = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(ds, p_start, b * 24, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(df, p_final, b * 24, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dm, z_middle, b * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dt, progress, b * 8, hipMemcpyHostToDevice, st));
-    rc = srbdqp_swing_device_f64(h, B, ds, df, dm, dt, final_velocity_z, first_half_share, dp, dv, da, dc, st);
-    if (rc != SRBDQP_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(pos, dp, b * 24, hipMemcpyDeviceToHost, st));
-    if (vel_z) HIP_TRY(h, hipMemcpyAsync(vel_z, dv, b * 8, hipMemcpyDeviceToHost, st));
-    if (acc_z) HIP_TRY(h, hipMemcpyAsync(acc_z, da, b * 8, hipMemcpyDeviceToHost, st));
-    if (coeff) HIP_TRY(h, hipMemcpyAsync(coeff, dc, b * 56, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    return SRBDQP_OK;
+    return host_call(h, [&](HostIo& io) {
+        ds = io.in<double>(p_start, b * 24); df = io.in<double>(p_final, b * 24); dm = io.in<double>(z_middle, b * 8); dt = io.in<double>(progress, b * 8);
+        dp = io.out<double>(pos, b * 24); dv = io.out<double>(vel_z, b * 8); da = io.out<double>(acc_z, b * 8); dc = io.out<double>(coeff, b * 56);
+    }, [&](hipStream_t st) { return srbdqp_swing_device_f64(h, B, ds, df, dm, dt, final_velocity_z, first_half_share, dp, dv, da, dc, st); });
 }
 
 int srbdqp_wbid_reference_device_f64(srbdqp_handle* h, int64_t B, const double* x_next, const double* u0,
@@ -2320,28 +2169,10 @@ int srbdqp_wbid_reference_f64(srbdqp_handle* h, int64_t B, const double* x_next,
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t b = (size_t)B;
     double *dx, *du, *df, *dR, *dv, *da, *dc;
-    auto carve = [&](Carver& c) {
-        dx = c.take<double>(b * 13); du = c.take<double>(b * 12); df = c.take<double>(b * 12);
-        dR = c.take<double>(b * 9); dv = c.take<double>(b * 6); da = c.take<double>(b * 6); dc = c.take<double>(b * 3);
-    };
-    Carver sz(nullptr);
-    carve(sz);
-    int rc = ensure_ws(h, sz.off);
-    if (rc != SRBDQP_OK) return rc;
-    Carver cv(h->ws);
-    carve(cv);
-    hipStream_t st = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(dx, x_next, b * 13 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(du, u0, b * 12 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(df, foot, b * 12 * 8, hipMemcpyHostToDevice, st));
-    rc = srbdqp_wbid_reference_device_f64(h, B, dx, du, df, as_written, dR, dv, da, dc, st);
-    if (rc != SRBDQP_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(R, dR, b * 9 * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(base_vel, dv, b * 6 * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(base_acc, da, b * 6 * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(com_acc, dc, b * 3 * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    return SRBDQP_OK;
+    return host_call(h, [&](HostIo& io) {
+        dx = io.in<double>(x_next, b * 13 * 8); du = io.in<double>(u0, b * 12 * 8); df = io.in<double>(foot, b * 12 * 8);
+        dR = io.out<double>(R, b * 9 * 8); dv = io.out<double>(base_vel, b * 6 * 8); da = io.out<double>(base_acc, b * 6 * 8); dc = io.out<double>(com_acc, b * 3 * 8);
+    }, [&](hipStream_t st) { return srbdqp_wbid_reference_device_f64(h, B, dx, du, df, as_written, dR, dv, da, dc, st); });
 }
 
 int srbdqp_mpc_inputs_device_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp,
@@ -2364,16 +2195,11 @@ int srbdqp_mpc_inputs_device_f64(srbdqp_handle* h, int64_t B, const double* x0, 
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
     const long long tiles = ((long long)B + 31) / 32;                   // one tile of 32 robots per workgroup pass
     const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
-    switch (h->cfg.horizon) {
-        case 4: hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<4>, grid, dim3(256), 0, st, a); break;
-        case 8: hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<8>, grid, dim3(256), 0, st, a); break;
-        case 10: hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<10>, grid, dim3(256), 0, st, a); break;
-        case 12: hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<12>, grid, dim3(256), 0, st, a); break;
-        case 16: hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<16>, grid, dim3(256), 0, st, a); break;
-        case 20: hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<20>, grid, dim3(256), 0, st, a); break;
-        case 24: hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<24>, grid, dim3(256), 0, st, a); break;
-        default: h->err = "unsupported horizon"; return SRBDQP_E_INVALID;
-    }
+    const int rc = with_horizon(h, [&](auto n) -> int {
+        hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<decltype(n)::value>, grid, dim3(256), 0, st, a);
+        return SRBDQP_OK;
+    });
+    if (rc != SRBDQP_OK) return rc;
     HIP_TRY(h, hipGetLastError());
     h->kname = "mpc_inputs_f64";
     return SRBDQP_OK;
@@ -2389,33 +2215,12 @@ int srbdqp_mpc_inputs_f64(srbdqp_handle* h, int64_t B, const double* x0, const d
     const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
     double *dx0, *dfe, *dst, *dv, *dxr, *dft, *dpc, *dlp;
     uint8_t *dsd, *dct;
-    auto carve = [&](Carver& c) {
-        dx0 = c.take<double>(b * 13); dfe = c.take<double>(b * 12); dst = c.take<double>(b); dv = c.take<double>(b * 2);
-        dsd = standing ? c.take<uint8_t>(b) : nullptr;
-        dxr = c.take<double>(b * N * 13); dft = c.take<double>(b * N * 12); dct = c.take<uint8_t>(b * N * 4);
-        dpc = c.take<double>(b * N * 3); dlp = landing ? c.take<double>(b * 3) : nullptr;
-    };
-    Carver sz(nullptr);
-    carve(sz);
-    int rc = ensure_ws(h, sz.off);
-    if (rc != SRBDQP_OK) return rc;
-    Carver cv(h->ws);
-    carve(cv);
-    hipStream_t st = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(dx0, x0, b * 13 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dfe, feet, b * 12 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dst, stamp, b * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dv, v_ref, b * 16, hipMemcpyHostToDevice, st));
-    if (standing) HIP_TRY(h, hipMemcpyAsync(dsd, standing, b, hipMemcpyHostToDevice, st));
-    rc = srbdqp_mpc_inputs_device_f64(h, B, dx0, dfe, dst, dv, dsd, gait, dxr, dft, dct, dpc, dlp, st);
-    if (rc != SRBDQP_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(x_ref, dxr, b * N * 13 * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(foot, dft, b * N * 12 * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(contact, dct, b * N * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(pcom, dpc, b * N * 3 * 8, hipMemcpyDeviceToHost, st));
-    if (landing) HIP_TRY(h, hipMemcpyAsync(landing, dlp, b * 3 * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    return SRBDQP_OK;
+    return host_call(h, [&](HostIo& io) {
+        dx0 = io.in<double>(x0, b * 13 * 8); dfe = io.in<double>(feet, b * 12 * 8); dst = io.in<double>(stamp, b * 8); dv = io.in<double>(v_ref, b * 16);
+        dsd = io.in<uint8_t>(standing, b);
+        dxr = io.out<double>(x_ref, b * N * 13 * 8); dft = io.out<double>(foot, b * N * 12 * 8); dct = io.out<uint8_t>(contact, b * N * 4);
+        dpc = io.out<double>(pcom, b * N * 3 * 8); dlp = io.out<double>(landing, b * 3 * 8);
+    }, [&](hipStream_t st) { return srbdqp_mpc_inputs_device_f64(h, B, dx0, dfe, dst, dv, dsd, gait, dxr, dft, dct, dpc, dlp, st); });
 }
 
 }  // extern "C"
