@@ -431,6 +431,42 @@ __device__ __forceinline__ double free_response(const KArgs& a, const double* sm
     }
 }
 
+// ... the same entry without the branch over kk (the one-wave kernel, where lanes of one instruction hold every kind of row): all three forms from clamped reads,
+// then a select.  Same expressions as free_response.
+template <int N, class L>
+__device__ __forceinline__ double free_response_sel(const KArgs& a, const double* sm, int i, int kk) {
+    const double* x0 = sm + L::o_x0;
+    const double* C = sm + L::o_cp + i * 9 + (kk < 3 ? kk : 0) * 3;
+    const double xk = x0[kk];
+    const double vr = xk + a.dt * (C[0] * x0[6] + C[1] * x0[7] + C[2] * x0[8]);                       // kk < 3
+    const double vp = xk + (double)(i + 1) * a.dt * x0[(kk >= 3 && kk < 6) ? kk + 6 : 6];             // 3 <= kk < 6
+    const double vz = vp + a.dt * a.dt * x0[12] * (double)((i * (i + 1)) / 2);                        // kk == 5
+    const double vw = xk + (double)(i + 1) * a.dt * x0[12];                                           // kk == 11
+    return (kk < 3) ? vr : (kk < 5) ? vp : (kk == 5) ? vz : (kk == 11) ? vw : xk;
+}
+
+// D_m, E_m of ONE step (de_tables' arithmetic) from C_m, T1(m), T2(m) in registers: de[0..8] = D_m, de[9..17] = E_m
+template <int N>
+__device__ __forceinline__ void de_step(const double (&Cm)[9], const double (&t1)[9], const double (&t2)[9], const double* SQ, const double dt2, const int m, double* de) {
+    const double d4 = dt2 * dt2;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int p = k / 3, q = k - 3 * p;
+        const double e0 = SQ[0] * SQ[0] * t1[q], e1 = SQ[1] * SQ[1] * t1[3 + q], e2 = SQ[2] * SQ[2] * t1[6 + q];
+        double v = t2[k] + Cm[p] * e0 + Cm[3 + p] * e1 + Cm[6 + p] * e2;
+        v *= d4;
+        if (p == q) v += (double)(N - m) * dt2 * SQ[6 + p] * SQ[6 + p];
+        de[k] = v;
+        de[9 + k] = d4 * ((p == 0) ? e0 : (p == 1) ? e1 : e2);
+    }
+}
+
+// value of lane l (a compile-time or wave-uniform index), as a wave-uniform value
+__device__ __forceinline__ double lane_bcast(double v, int l) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+    return __hiloint2double(hi, lo);
+}
+
 // block-wide max of up to NV values per thread; result broadcast to all threads.  2 barriers.
 template <int NV>
 __device__ __forceinline__ void block_max(double (&v)[NV], double* red) {

@@ -102,78 +102,110 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
     const double* CP = sm + L1::o_cp;
 
     // ================= load + linearise (a5) =================
+    // Round 6: on the whole wave, from registers, behind ONE barrier.  Every global load is issued first (each lane also fetches the foot / CoM operands of its
+    // own J entries and the x_ref entries of its own error-vector rows, so that neither goes through LDS); lane k < N forms cos / sin of yaw_k, the wave reads
+    // them back as uniform values (v_readlane) and C_k = sum_{l<=k} T_l -- only two of its nine entries are not constant: C_k = [[cc_k, cs_k, 0], [-cs_k, cc_k, 0],
+    // [0, 0, k + 1]] -- is summed in registers in the order of the serial loop it replaces.  (Until round 6: inputs -> LDS, three barriers, a 9-lane prefix loop
+    // of ten dependent LDS round trips and a J loop reading its operands back from LDS.)
     WSTAMP(a, b, 0);
     WSTAMP_RT(a, b, 12);
+    constexpr int JT = (12 * N + 63) / 64;                   // trips of the wave over the 12 N entries of J (and of the error vector: n = 12 N as well)
+    double yc, ys;                                           // lane k < N: cos / sin of yaw_k
+    [[maybe_unused]] double v_xr[JT];                        // x_ref entry of error-vector row lane + 64 t
     if constexpr (RP == 2) {   // the strip (contact lists, T, J, x0, q) is in place; the prefix sums were overwritten by the K^-1 staging
-        if (lane < 9) {
-            double acc = 0.0;
-            for (int k = 0; k < N; ++k) { acc += sm[S::o_tm + k * 9 + lane]; sm[L1::o_cp + k * 9 + lane] = acc; }
-        }
-        __syncthreads();
+        const int k = lane < N ? lane : 0;
+        yc = sm[S::o_tm + k * 9 + 0];
+        ys = sm[S::o_tm + k * 9 + 1];
     } else {
         const double* gx0 = io.x0 + (size_t)b * 13;
         const double* gxr = io.xref + (size_t)b * N * 13;
         const double* gft = io.foot + (size_t)b * N * 12;
         const uint8_t* gct = io.contact + (size_t)b * N * 4;
-        if (lane < 13) sm[S::o_x0 + lane] = gx0[lane];
-        if (lane >= 32 && lane < 44) sm[S::o_sq + lane - 32] = a.sqrtq[lane - 32];
-        for (int i = lane; i < N * 13; i += 64) sm[L1::o_xref + i] = gxr[i];
-        for (int i = lane; i < N * 12; i += 64) sm[L1::o_foot + i] = gft[i];
-        if (lane < N * 4) sct[lane] = gct[lane] ? 1 : 0;
-        if (io.pcom) {
-            const double* gpc = io.pcom + (size_t)b * N * 3;
-            if (lane < N * 3) sm[L1::o_pcom + lane] = gpc[lane];
+        const double* gpc = io.pcom ? io.pcom + (size_t)b * N * 3 : nullptr;
+        // (clamped indices, no branch: the loads of every lane travel together)
+        const double v_x0 = gx0[lane < 13 ? lane : 0];
+        const uint8_t v_ct = gct[lane < 4 * N ? lane : 0];
+        const double v_yaw = gxr[(lane < N ? lane : 0) * 13 + 2];
+        double v_f[JT][3], v_p[JT][3];
+#pragma unroll
+        for (int t = 0; t < JT; ++t) {
+            const int tt = (lane + 64 * t < 12 * N) ? lane + 64 * t : 0;
+            const int k = tt / 12, ci = (tt % 12) / 3;
+            const double* pc = gpc ? gpc + k * 3 : gxr + k * 13 + 3;     // no CoM path: the CoM of x_ref
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { v_f[t][c] = gft[k * 12 + 3 * ci + c]; v_p[t][c] = pc[c]; }
+            v_xr[t] = gxr[k * 13 + (tt - 12 * k)];
         }
-        __syncthreads();
-        if (!io.pcom && lane < N * 3) sm[L1::o_pcom + lane] = sm[L1::o_xref + (lane / 3) * 13 + 3 + (lane % 3)];
+        sincos(v_yaw, &ys, &yc);
+        if (lane < 13) sm[S::o_x0 + lane] = v_x0;
+        if (lane >= 32 && lane < 44) sm[S::o_sq + lane - 32] = a.sqrtq[lane - 32];
+        if (lane < N * 4) sct[lane] = v_ct ? 1 : 0;
         if (lane < N) {   // Rz(yaw_k)'
-            double sn, cs;
-            sincos(sm[L1::o_xref + lane * 13 + 2], &sn, &cs);
             double* T = sm + S::o_tm + lane * 9;
-            T[0] = cs;  T[1] = sn;  T[2] = 0.0;
-            T[3] = -sn; T[4] = cs;  T[5] = 0.0;
+            T[0] = yc;  T[1] = ys;  T[2] = 0.0;
+            T[3] = -ys; T[4] = yc;  T[5] = 0.0;
             T[6] = 0.0; T[7] = 0.0; T[8] = 1.0;
         }
-        {   // presolve: compact the stance contacts
-            const bool flag = (lane < 4 * N) && sct[lane < 4 * N ? lane : 0] != 0;
+        {   // presolve: compact the stance contacts; per-step bound check from the same ballot
+            const bool flag = (lane < 4 * N) && v_ct != 0;
             const unsigned long long bal = __ballot(flag);
             if (flag) act[__popcll(bal & ((1ull << lane) - 1ull))] = (uint8_t)lane;
             if (lane < N) icnt[lane] = __popcll(bal & ((4 * (lane + 1) >= 64) ? ~0ull : ((1ull << (4 * (lane + 1))) - 1ull)));
+            const bool over = lane < N && __popcll((bal >> (4 * (lane < N ? lane : 0))) & 0xFull) > MAXS;
+            const unsigned long long viol = __ballot(over);
             if (lane == 0) {
                 imisc[0] = __popcll(bal);
+                imisc[1] = viol != 0ull;
                 sm[S::o_misc] = 0.0;
                 sm[S::o_misc + 1] = 0.0;
             }
         }
-        __syncthreads();
-        if (lane < 9) {   // prefix sums C_k = sum_{l<=k} T_l
-            double acc = 0.0;
-            for (int k = 0; k < N; ++k) { acc += sm[S::o_tm + k * 9 + lane]; sm[L1::o_cp + k * 9 + lane] = acc; }
-        }
-        if (lane == 16) {   // per-step bound check
-            int viol = 0;
-            for (int i = 0; i < N; ++i) viol |= ((icnt[i] - (i ? icnt[i - 1] : 0)) > MAXS);
-            imisc[1] = viol;
-        }
-        for (int tt = lane; tt < N * 12; tt += 64) {   // J_k[:, 3 ci + ax] = Iw^-1 * skew(r)[:, ax]
-            const int k = tt / 12, cc = tt % 12, ci = cc / 3, ax = cc % 3;
-            const double cs = sm[S::o_tm + k * 9 + 0], sn = sm[S::o_tm + k * 9 + 1];
+#pragma unroll
+        for (int t = 0; t < JT; ++t) {   // J_k[:, 3 ci + ax] = Iw^-1 * skew(r)[:, ax]
+            const int tt = lane + 64 * t;
+            const int k = (tt < 12 * N ? tt : 0) / 12, cc = tt - 12 * k, ax = cc % 3;
+            const double cs = __shfl(yc, k), sn = __shfl(ys, k);    // (every lane takes part: the shuffles sit outside the store's condition)
             const double i0 = a.iinv[0], i1 = a.iinv[1], i2 = a.iinv[2];
             const double w00 = cs * cs * i0 + sn * sn * i1, w01 = cs * sn * (i0 - i1), w11 = sn * sn * i0 + cs * cs * i1;
-            const double rx = sm[L1::o_foot + k * 12 + 3 * ci + 0] - sm[L1::o_pcom + k * 3 + 0];
-            const double ry = sm[L1::o_foot + k * 12 + 3 * ci + 1] - sm[L1::o_pcom + k * 3 + 1];
-            const double rz = sm[L1::o_foot + k * 12 + 3 * ci + 2] - sm[L1::o_pcom + k * 3 + 2];
+            const double rx = v_f[t][0] - v_p[t][0];
+            const double ry = v_f[t][1] - v_p[t][1];
+            const double rz = v_f[t][2] - v_p[t][2];
             // column ax of skew(r) as selects (a three-way if chain on this value was miscompiled in srbdqp_wrench.hpp)
             const double s0 = (ax == 0) ? 0.0 : ((ax == 1) ? -rz : ry);
             const double s1 = (ax == 0) ? rz : ((ax == 1) ? 0.0 : -rx);
             const double s2 = (ax == 0) ? -ry : ((ax == 1) ? rx : 0.0);
-            double* J = sm + S::o_J + k * 36;
-            J[0 * 12 + cc] = w00 * s0 + w01 * s1;
-            J[1 * 12 + cc] = w01 * s0 + w11 * s1;
-            J[2 * 12 + cc] = i2 * s2;
+            if (tt < 12 * N) {
+                double* J = sm + S::o_J + k * 36;
+                J[0 * 12 + cc] = w00 * s0 + w01 * s1;
+                J[1 * 12 + cc] = w01 * s0 + w11 * s1;
+                J[2 * 12 + cc] = i2 * s2;
+            }
         }
-        __syncthreads();
     }
+    // prefix sums C_k, wave-uniform (cc_k = sum_{l<=k} cos yaw_l, cs_k = sum_{l<=k} sin yaw_l: the serial loop's order), and C_k to LDS from lane k
+    // (lane m < N: C_m from the same sum with the steps past m adding exact zeros -- a select of ccu[lane] instead is turned back into an indexed load by the
+    // compiler, and the arrays into scratch memory)
+    double ccu[N], csu[N], ccm = 0.0, csm = 0.0;
+    {
+        double ac = 0.0, as = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const double c = lane_bcast(yc, k), s = lane_bcast(ys, k);
+            ac += c;
+            as += s;
+            ccu[k] = ac;
+            csu[k] = as;
+            ccm += (k <= lane) ? c : 0.0;
+            csm += (k <= lane) ? s : 0.0;
+        }
+    }
+    if (lane < N) {
+        double* C = sm + L1::o_cp + lane * 9;
+        C[0] = ccm;  C[1] = csm; C[2] = 0.0;
+        C[3] = -csm; C[4] = ccm; C[5] = 0.0;
+        C[6] = 0.0;  C[7] = 0.0; C[8] = (double)(lane + 1);
+    }
+    __syncthreads();
     const int na = imisc[0];
     const int n_eff = 3 * na;
     double* xs0 = sm + L1::o_mt;                             // scratch vectors of the early exit (n + 12N doubles; M is not built)
@@ -195,45 +227,44 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
     WSTAMP(a, b, 1);
     // ================= closed-form tables, gradient, warm-start P x^0 (see srbdqp_compact.hpp, phase A) =================
     const double dt = a.dt, dt2 = a.dt * a.dt, dtm = a.dt * a.inv_mass, dt2m = dt2 * a.inv_mass;
-    double* T1 = sm + L1::o_t1;
-    double* T2 = sm + L1::o_t2;
     double* DE = sm + L1::o_mt;
     double* GV = sm + L1::o_gv;
     if constexpr (RP != 2) {
-        for (int k = lane; k < n; k += 64) {
-            const int i = k / 12, kk = k - 12 * i;
-            sm[L1::o_eh + k] = SQ[kk] * (free_response<N, L1>(a, sm, i, kk) - sm[L1::o_xref + i * 13 + kk]);
-        }
-    }
-    // T2(m) is symmetric: one lane per (m, p <= q) -- 6 N entries, one round of the wave at N = 10 instead of two -- which also forms
-    // both T1 entries of its pair
-    for (int tt = lane; tt < 6 * N; tt += 64) {
-        const int mm = tt / 6, u = tt - 6 * mm;
-        const int p = (u < 3) ? 0 : ((u < 5) ? 1 : 2), q = (u < 3) ? u : ((u < 5) ? u - 2 : 2);   // (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
-        const int pq = 3 * p + q, qp = 3 * q + p;
-        const double* Cm = CP + mm * 9;
-        const double w0 = SQ[0] * SQ[0], w1 = SQ[1] * SQ[1], w2 = SQ[2] * SQ[2];
-        double s1 = 0.0, s1t = 0.0, s2 = 0.0;
-        // (all N steps, the ones before m adding exact zeros: a loop from m has a trip count per lane, is not unrolled, and every trip waits for its own eight LDS
-        // reads -- ten round trips; this way the reads of all trips are in flight together)
 #pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const double* Ci = CP + i * 9;
-            const bool on = i >= mm;
-            const double a1 = Ci[pq] - Cm[pq], a1t = Ci[qp] - Cm[qp];
-            const double d0p = Ci[p] - Cm[p], d1p = Ci[3 + p] - Cm[3 + p], d2p = Ci[6 + p] - Cm[6 + p];
-            const double d0q = Ci[q] - Cm[q], d1q = Ci[3 + q] - Cm[3 + q], d2q = Ci[6 + q] - Cm[6 + q];
-            const double a2 = (w0 * d0p) * d0q + (w1 * d1p) * d1q + (w2 * d2p) * d2q;
-            s1 += on ? a1 : 0.0;
-            s1t += on ? a1t : 0.0;
-            s2 += on ? a2 : 0.0;
+        for (int t = 0; t < JT; ++t) {   // error vector: one row per lane and trip, every kind of row in the same instructions (free_response_sel)
+            const int k = lane + 64 * t;
+            const int kc = k < n ? k : 0, i = kc / 12, kk = kc - 12 * i;
+            const double v = SQ[kk] * (free_response_sel<N, L1>(a, sm, i, kk) - v_xr[t]);
+            if (k < n) sm[L1::o_eh + k] = v;
         }
-        T1[9 * mm + pq] = s1;
-        T1[9 * mm + qp] = s1t;
-        T2[9 * mm + pq] = s2;
-        T2[9 * mm + qp] = s2;
     }
-    __syncthreads();
+    // T1(m) = sum_{i>=m} (C_i - C_m), T2(m) = sum_{i>=m} (C_i - C_m)' W (C_i - C_m) (W = diag(q_0..2)) and from them D_m, E_m of the rank-6 assembly: lane m, in
+    // registers, from the wave-uniform prefix sums.  C has two non-constant entries, so T1 has two (t1a, t1b: [[t1a, t1b, 0], [-t1b, t1a, 0], [0, 0, t1z]]) and T2
+    // three ([[t2aa, t2ab, 0], [t2ab, t2bb, 0], [0, 0, t2zz]]).  The sums stay in the differences-first form (every term formed from C_i - C_m, as the loop over LDS
+    // it replaces did): the suffix-sum form S(m) - (N - m) C_m, Q(m) - C_m'W S(m) - ... is O(1) per entry but cancels -- C_i grows like i, and T2 near the end
+    // of the horizon comes out ~250 ulps off at N = 10 against a few for this form (tests/test_suffix_tables_cpu.py) --, and here the O(N) loop is N
+    // multiply-adds of registers, no memory access.  (Until round 6: 6 N lanes with 8 LDS reads per step each, a barrier, de_tables over LDS.)
+    if (lane < N) {
+        const int mm = lane;
+        const double w0 = SQ[0] * SQ[0], w1 = SQ[1] * SQ[1], w2 = SQ[2] * SQ[2];
+        double t1a = 0.0, t1b = 0.0, t2aa = 0.0, t2ab = 0.0, t2bb = 0.0, t2zz = 0.0;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {   // (all N steps, the ones before m adding exact zeros)
+            const bool on = i >= mm;
+            const double da = ccu[i] - ccm, db = csu[i] - csm, dz = (double)(i - mm);
+            t1a += on ? da : 0.0;
+            t1b += on ? db : 0.0;
+            t2aa += on ? (w0 * da) * da + (w1 * db) * db : 0.0;
+            t2ab += on ? (w0 * da) * db - (w1 * db) * da : 0.0;
+            t2bb += on ? (w0 * db) * db + (w1 * da) * da : 0.0;
+            t2zz += on ? (w2 * dz) * dz : 0.0;
+        }
+        const double t1z = (double)(((N - mm) * (N - mm - 1)) / 2);
+        const double Cm[9] = {ccm, csm, 0.0, -csm, ccm, 0.0, 0.0, 0.0, (double)(mm + 1)};
+        const double t1[9] = {t1a, t1b, 0.0, -t1b, t1a, 0.0, 0.0, 0.0, t1z};
+        const double t2[9] = {t2aa, t2ab, 0.0, t2ab, t2bb, 0.0, 0.0, 0.0, t2zz};
+        de_step<N>(Cm, t1, t2, SQ, dt2, mm, DE + 18 * mm);
+    }
     auto gt_tables = [&](const double* vec) {
         // the 3 torque entries of a step (an O(N) loop of 7 LDS reads) first, then the 6 force entries (1 read), the latter starting on
         // the lanes the former leave free: entry by entry every round of the wave ran all three loops (N = 10: 2 x 3 loops -> 1 + 2)
@@ -272,8 +303,8 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
         const double* g = GV + 9 * j;
         return a.s * (J[0] * g[0] + J[12] * g[1] + J[24] * g[2] + SQ[3 + ax] * dt2m * g[3 + ax] + SQ[9 + ax] * dtm * g[6 + ax]);
     };
+    __syncthreads();
     if constexpr (RP != 2) gt_tables(sm + L1::o_eh);
-    de_tables<N>(CP, T1, T2, SQ, dt2, DE, lane, 64);
     __syncthreads();
     WSTAMP(a, b, 2);
     if constexpr (RP != 2) for (int c = lane; c < n_eff; c += 64) sm[S::o_q + c] = gt_eval(c);      // (a continued pass: q stays)
@@ -491,21 +522,24 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
             }
         }
     } else {
-        // one K^-1 row per lane: for every block column cb all NT blocks (g, cb) are produced directly in C layout
-        // ((g, cb) with g > cb is the same product with the operands swapped -- no transposes), staged as NT row-major
-        // tiles in the dead phase-A arrays, and lane (g, i) pulls row i of tile g with 16-byte reads (rows 18 doubles apart: with 16 the sixteen lanes of a
-        // read pass hit two banks, an 8-way conflict on every one of the 32 reads)
+        // one K^-1 row per lane, block column by block column from the LAST: column cb forms only its blocks on and above the diagonal, (g, cb) for g <= cb,
+        // in C layout -- 20 tile products at NT = 4 instead of the 30 of all NT blocks (round 6; K^-1 is symmetric) -- and stages them as row-major tiles in the
+        // dead phase-A arrays.  The blocks below the diagonal are transposes of blocks an EARLIER (later-numbered) column formed: (g, cb) = (cb, g)' for g > cb.
+        // Those wait in registers (Ku: up to five tiles at NT = 4, while the W tiles of the columns done die) and are staged transposed, so that lane (g, i)
+        // pulls row i of tile g with the same 16-byte reads whichever kind it is (rows 18 doubles apart: with 16 the sixteen lanes of a read pass hit two banks,
+        // an 8-way conflict on every one of the 32 reads; the transposed store, 16 lanes of a row 144 bytes apart, is free of conflicts as well).
         double* stg = sm + L1::o_cp;
         static_assert(L1::o_end - L1::o_cp >= NT * L1::kStgTile, "staging of one block column of K^-1");
         const int grp = lane >> 4;
+        v4d Ku[NT][NT];                                      // Ku[g][c], g < c: block (g, c), from column c to column g
 #pragma unroll
-        for (int cb = 0; cb < NT; ++cb) {
+        for (int cb = NT - 1; cb >= 0; --cb) {
             asm volatile("" ::: "memory");
 #pragma unroll
-            for (int g = 0; g < NT; ++g) {
-                v4d o = zero4;                               // sum_{k >= max(g, cb)} W_kg' W_k,cb
+            for (int g = 0; g <= cb; ++g) {
+                v4d o = zero4;                               // sum_{k >= cb} W_kg' W_k,cb
 #pragma unroll
-                for (int k = (g > cb ? g : cb); k < NT; ++k) {
+                for (int k = cb; k < NT; ++k) {
                     const v4d& wkg = (k == g) ? Kt[g][g] : Kt[g][k];
                     const v4d& wkc = (k == cb) ? Kt[cb][cb] : Kt[cb][k];
 #pragma unroll
@@ -513,7 +547,12 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
                 }
 #pragma unroll
                 for (int q = 0; q < 4; ++q) stg[g * L1::kStgTile + (kq + 4 * q) * L1::kStgRow + mcol] = o[q];
+                if (g < cb) Ku[g][cb] = o;
             }
+#pragma unroll
+            for (int g = cb + 1; g < NT; ++g)                // (g, cb) = (cb, g)': row mcol of the staged tile = column mcol of the block
+#pragma unroll
+                for (int q = 0; q < 4; ++q) stg[g * L1::kStgTile + mcol * L1::kStgRow + kq + 4 * q] = Ku[cb][g][q];
             asm volatile("" ::: "memory");
             const double2* rowp = reinterpret_cast<const double2*>(stg + grp * L1::kStgTile + mcol * L1::kStgRow);
 #pragma unroll
