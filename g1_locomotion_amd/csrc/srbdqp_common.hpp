@@ -431,6 +431,14 @@ __device__ __forceinline__ double free_response(const KArgs& a, const double* sm
     }
 }
 
+// Row k < 12 N of the error vector Q^1/2 (A_qp x0 - x_ref) into o_eh of the layout L: the multi-wave kernels' (srbdqp_compact.hpp, srbdqp_wrench.hpp), whose loops
+// over the rows differ in stride (the workgroup, or one set-up helper wave)
+template <int N, class L>
+__device__ __forceinline__ void eh_entry(const KArgs& a, double* sm, const double* SQ, const int k) {
+    const int i = k / 12, kk = k - 12 * i;
+    sm[L::o_eh + k] = SQ[kk] * (free_response<N, L>(a, sm, i, kk) - sm[L::o_xref + i * 13 + kk]);
+}
+
 // ... the same entry without the branch over kk (the one-wave kernel, where lanes of one instruction hold every kind of row): all three forms from clamped reads,
 // then a select.  Same expressions as free_response.
 template <int N, class L>

@@ -42,11 +42,7 @@ struct CompactSmem {
     static constexpr int TS = (NTT + 3) / 4;
     // lanes per K^-1 row in the ADMM mat-vec: 4 when 4 nmax lanes fit the workgroup (a row fragment of nmax/4 doubles
     // keeps the kernel inside the 128-register budget of 4 workgroups per CU), else 2
-#ifdef SRBDQP_FORCE_LPR2
-    static constexpr int LPR = 2;
-#else
     static constexpr int LPR = (4 * nmax <= kThreads) ? 4 : 2;
-#endif
     static constexpr int CHMAX = 2 * ((nmax + 2 * LPR - 1) / (2 * LPR));   // columns per mat-vec part (even)
     static constexpr int up2(int v) { return (v + 1) & ~1; }
     static constexpr int cmax(int a, int b) { return a > b ? a : b; }
@@ -91,11 +87,7 @@ struct CompactSmem {
     // workgroups per CU that LDS admits (160 KiB per CU), capped at 3: the register budget the kernel is compiled for
     // (3 only for the small problems: a 168-register budget cannot hold a K^-1 row fragment of more than 30 doubles)
     static constexpr int lds_wgs = 163840 / (int)bytes;
-#ifdef SRBDQP_COMPACT_WPS   // experiments: one register budget for every instantiation
-    static constexpr int waves_per_simd = SRBDQP_COMPACT_WPS;
-#else
     static constexpr int waves_per_simd = (lds_wgs >= 4 && LPR == 4 && nmax <= 60) ? 4 : (lds_wgs >= 3 && nmax <= 72) ? 3 : (lds_wgs >= 2 ? 2 : 1);
-#endif
 };
 
 // Lane mapping of the presolved ADMM: a contact owns 3 LPR consecutive lanes (variable ax on lanes LPR ax .. LPR ax +
@@ -482,10 +474,7 @@ __device__ __forceinline__ void compact_qp(const KArgs& a, const int b, double* 
     double* GV = sm + S::o_gv;
     const double* CP = sm + S::o_cp;
     const double* SQ = sm + S::o_sq;
-    for (int k = t; k < n; k += kThreads) {   // Q^1/2 (A_qp x0 - x_ref), all 12 N rows
-        const int i = k / 12, kk = k - 12 * i;
-        sm[S::o_eh + k] = SQ[kk] * (free_response<N, S>(a, sm, i, kk) - sm[S::o_xref + i * 13 + kk]);
-    }
+    for (int k = t; k < n; k += kThreads) eh_entry<N, S>(a, sm, SQ, k);   // Q^1/2 (A_qp x0 - x_ref), all 12 N rows
     if (t < 9 * N) {
         const int mm = t / 9, pq = t - 9 * mm, p = pq / 3, q = pq - 3 * p;
         const double* Cm = CP + mm * 9;

@@ -59,6 +59,22 @@ __device__ __forceinline__ void store_tile(double* tile, const v4d& v, int lane)
     }
 }
 
+// the same two for either tile type (the general kernel, srbdqp_wrench.hpp: fp64 tiles on v_mfma_f64_16x16x4_f64, fp32 tiles on v_mfma_f32_16x16x4_f32)
+typedef float v4f __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ v4d mma16(double a, double b, v4d c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ v4f mma16(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+// row of accumulator register q in the MFMA C/D layout: fp64 16x16x4: (lane >> 4) + 4 q; fp32 16x16x4: 4 (lane >> 4) + q
+template <typename TT> __device__ __forceinline__ int crow(int kq, int q) { return (sizeof(TT) == 8) ? kq + 4 * q : 4 * kq + q; }
+template <typename TT, bool SWZ, typename V4>
+__device__ __forceinline__ void store_tile_t(TT* tile, const V4& v, int lane) {
+    const int col = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int row = crow<TT>(g, q);
+        tile[row * 16 + (SWZ ? (col ^ row) : col)] = v[q];
+    }
+}
+
 // 1/sqrt(d) of a positive, normal pivot: v_rsq_f64 seed + ONE Newton step.  Measured on gfx950 (tools/rsq_probe.hip, 4 M random
 // doubles over 40 binades): seed 5.2e-8 relative, one step 4.1e-15, two steps 1.4e-16 -- the second step (four more dependent
 // fp64 instructions per pivot, 16 pivots per diagonal tile, on the critical path of every factorisation) bought nothing the

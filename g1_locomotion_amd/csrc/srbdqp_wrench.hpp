@@ -117,22 +117,11 @@ struct WrenchSmem {
     static constexpr int o_ws = o_T + NTT * 256 * TB / 8;   // fp32 tiles: one 16 x 16 scratch tile per wave (operand re-layout)
     // fp64 iterations with a half row longer than 60 (N = 24): its last KTAIL entries per lane, entry-major [KTAIL][BT] (the tiles
     // are dead by then and their region is far larger)
-#ifndef SRBDQP_WRENCH_KTAIL36
-#define SRBDQP_WRENCH_KTAIL36 12
-#endif
-#ifndef SRBDQP_WRENCH_VLDS
-#define SRBDQP_WRENCH_VLDS 1
-#endif
-#ifndef SRBDQP_WRENCH_JLDS
-#define SRBDQP_WRENCH_JLDS 1
-#endif
-#ifndef SRBDQP_WRENCH_KREG64
-#define SRBDQP_WRENCH_KREG64 56   // entries of the fp64 half row kept in registers when it is longer than 60 (N = 24 mixed gait: 56 -> 1.06 M QP/s with 2 reloads from scratch left in the iteration, 48 -> 1.03 M with none, 40 -> 1.01 M)
-#endif
-    static constexpr int KTAIL = (TB == 8 && CHMAX > 60) ? CHMAX - SRBDQP_WRENCH_KREG64 : ((TB == 8 && CHMAX == 36) ? SRBDQP_WRENCH_KTAIL36 : 0);   // N = 12: 3 waves per SIMD
+    static constexpr int KREG64 = 56;   // entries of the fp64 half row kept in registers when it is longer than 60 (N = 24 mixed gait: 56 -> 1.06 M QP/s with 2 reloads from scratch left in the iteration, 48 -> 1.03 M with none, 40 -> 1.01 M)
+    static constexpr int KTAIL = (TB == 8 && CHMAX > 60) ? CHMAX - KREG64 : ((TB == 8 && CHMAX == 36) ? 12 : 0);   // N = 12: 3 waves per SIMD
     static constexpr int o_kt = up2(endC);
     static constexpr int o_vl = o_kt + KTAIL * BT;        // VL: row and column of V per lane, entry-major [12][BT]
-    static constexpr int endC2 = o_vl + ((TB == 8 && SRBDQP_WRENCH_VLDS && CHMAX <= 36) ? 12 * BT : 0);
+    static constexpr int endC2 = o_vl + ((TB == 8 && CHMAX <= 36) ? 12 * BT : 0);
     static constexpr int wgs_of(int doubles) { return 163840 / (((doubles * 8 + 1279) / 1280) * 1280); }   // (LDS is handed out in blocks of 320 dwords on gfx950)
     // fp32 tiles: the lower triangle of E^-1 per step (21 N doubles: the very values that went into T -- V and Bd formed from a
     // rounded copy break the Woodbury identity 100 times worse than rounding V and Bd themselves), written in phase E and kept
@@ -150,12 +139,9 @@ struct WrenchSmem {
     // fp32 tiles, long horizons: the lane's fp64 row and column of V wait in the dead tile region while x_q and its refinement run
     // (entry-major [6][n] each, indexed by the lane's variable; two free regions: behind the ADMM vectors up to the G'v tables the
     // refinement still needs, and the 6-vectors + E^-1 blocks of the assembly) -- they were the larger half of the kernel's spills
-#ifndef SRBDQP_WRENCH_VPARK
-#define SRBDQP_WRENCH_VPARK 1
-#endif
     static constexpr int o_vpr = up2(endC);
     static constexpr int o_vpc = o_zt;
-    static constexpr bool VPARK = TB == 4 && SRBDQP_WRENCH_VPARK && (o_gv - o_vpr >= 6 * n) && (o_vpc + 6 * n <= o_e4);
+    static constexpr bool VPARK = TB == 4 && (o_gv - o_vpr >= 6 * n) && (o_vpc + 6 * n <= o_e4);
     static_assert(!GX_LATE || o_gx == o_vpr + 6 * n, "fp32 tiles: G x^0 right behind the parked V rows");
     static constexpr int o_pre = cmax(endA, cmax(endB, endC2));   // low-latency instantiation: the scratch tile of the diagonal tile that is inverted beside the assembly (the tile store still holds tables then)
     static constexpr int o_hand = o_pre + (XW > 0 ? 256 : 0);   // ... and, with the tile phases pipelined (XW = 2, below), the two tiles assembled for wave 0 by waves 1 and 3
@@ -198,21 +184,6 @@ __device__ __forceinline__ double rmin(double a, double b) { return fmin(a, b); 
 __device__ __forceinline__ double rmax(double a, double b) { return fmax(a, b); }
 __device__ __forceinline__ float rabs(float a) { return fabsf(a); }
 __device__ __forceinline__ double rabs(double a) { return fabs(a); }
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ v4d mma16(double a, double b, v4d c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ v4f mma16(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-// row of accumulator register q in the MFMA C/D layout: fp64 16x16x4: (lane >> 4) + 4 q; fp32 16x16x4: 4 (lane >> 4) + q
-template <typename TT> __device__ __forceinline__ int crow(int kq, int q) { return (sizeof(TT) == 8) ? kq + 4 * q : 4 * kq + q; }
-template <typename TT, bool SWZ, typename V4>
-__device__ __forceinline__ void store_tile_t(TT* tile, const V4& v, int lane) {
-    const int col = lane & 15, g = lane >> 4;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int row = crow<TT>(g, q);
-        tile[row * 16 + (SWZ ? (col ^ row) : col)] = v[q];
-    }
-}
 
 // workgroup-wide max of one non-negative value (NW waves); two barriers
 template <int NW>
@@ -437,9 +408,6 @@ __device__ __forceinline__ R apply_kinv(R wv, R* wbw, R* tbw, R* vb, int lane, i
 //   T^-1 tiles (accumulators): wave 0: (0,0) (0,2) (1,2)    wave 1: (0,1) (1,1)    wave 2: (2,2) (3,3)    wave 3: (0,3) (1,3) (2,3)
 // NTC = number of 16 x 16 block columns (the schedule of fewer columns is the same one without the tiles that do not exist).  Same products, same operand order
 // as the phases of the batch instantiations: the tiles of T^-1 agree to rounding.  The slots of the tile store hold, in turn, U_ab, W_b<-a and T^-1_ab.
-#ifndef SRBDQP_LATP_SPLIT
-#define SRBDQP_LATP_SPLIT 5
-#endif
 #ifdef SRBDQP_LATP_STAMPS
 #define ESTAMP(a, i) do { if ((a).stamps && (a).B == 1 && threadIdx.x == 0) (a).stamps[16 * 5 + (i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
 #else
@@ -458,7 +426,7 @@ __device__ __forceinline__ R apply_kinv(R wv, R* wbw, R* tbw, R* vb, int lane, i
 template <int W, int NTC>
 __device__ __forceinline__ void latp_run(double* T, const double* D0, v4d& acc0, v4d& acc1, v4d& acc2, double* misc, const int lane, long long* stamps) {
     (void)stamps;
-    constexpr int KSPLIT = SRBDQP_LATP_SPLIT;
+    constexpr int KSPLIT = 5;                    // pivots of a diagonal-tile inversion in front of barrier M (inv_first), the other 11 behind it
     const int mcol = lane & 15, kq = lane >> 4;
     const v4d zero4 = (v4d){0.0, 0.0, 0.0, 0.0};
     auto TL = [&](int a_, int b_) __attribute__((always_inline)) -> double* { return T + tile_id(a_, b_) * 256; };
@@ -628,6 +596,16 @@ __device__ __forceinline__ void latp_dispatch(const int w, double* T, const doub
     else if (w == 1) latp_run<1, NTC>(T, D0, acc0, acc1, acc2, misc, lane, stamps);
     else if (w == 2) latp_run<2, NTC>(T, D0, acc0, acc1, acc2, misc, lane, stamps);
     else latp_run<3, NTC>(T, D0, acc0, acc1, acc2, misc, lane, stamps);
+}
+
+// The want-th stance contact (0 .. 3) of a step with contact flags f0 .. f3; -1 when the step has no more than `want` of them.
+__device__ __forceinline__ int nth_stance(const int f0, const int f1, const int f2, const int f3, const int want) {
+    int cc = -1, seen = 0;
+    if (f0) { if (seen == want && cc < 0) cc = 0; ++seen; }
+    if (f1) { if (seen == want && cc < 0) cc = 1; ++seen; }
+    if (f2) { if (seen == want && cc < 0) cc = 2; ++seen; }
+    if (f3) { if (seen == want && cc < 0) cc = 3; ++seen; }
+    return cc;
 }
 
 // A QP's own robot (MODE = 2, srbdqp_set_robots): its record -- srbdqp_robot of include/srbdqp.h as 8 doubles: mass, inertia[3], mu, fz_min, fz_max, reserved --
@@ -820,10 +798,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     const int tt = TSPLIT ? lane : t;
     constexpr int TSTR = TSPLIT ? 64 : BT;
     if (tab_a)
-    for (int k = tt; k < n; k += TSTR) {
-        const int i = k / 12, kk = k - 12 * i;
-        sm[S::o_eh + k] = SQ[kk] * (free_response<N, S>(a, sm, i, kk) - sm[S::o_xref + i * 13 + kk]);
-    }
+    for (int k = tt; k < n; k += TSTR) eh_entry<N, S>(a, sm, SQ, k);
     if (tab_b)
     for (int idx = tt; idx < 9 * N; idx += TSTR) {
         const int mm = idx / 9, pq = idx - 9 * mm, p = pq / 3, q = pq - 3 * p;
@@ -930,11 +905,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             const int g0 = sct[4 * j], g1 = sct[4 * j + 1], g2 = sct[4 * j + 2], g3 = sct[4 * j + 3];
             const bool wr = (g0 + g1 + g2 + g3) >= 3;
             const int want = l / 3, lm = l - 3 * want;
-            int cc = -1, seen = 0;
-            if (g0) { if (seen == want && cc < 0) cc = 0; ++seen; }
-            if (g1) { if (seen == want && cc < 0) cc = 1; ++seen; }
-            if (g2) { if (seen == want && cc < 0) cc = 2; ++seen; }
-            if (g3) { if (seen == want && cc < 0) cc = 3; ++seen; }
+            const int cc = nth_stance(g0, g1, g2, g3, want);
             const int ug = (cc >= 0 ? 3 * cc : 0) + lm;
             const double* Jj = sm + S::o_J + j * 36;
             const double z0 = wr ? ((l == 0) ? 1.0 : 0.0) : Jj[ug], z1 = wr ? ((l == 1) ? 1.0 : 0.0) : Jj[12 + ug], z2 = wr ? ((l == 2) ? 1.0 : 0.0) : Jj[24 + ug];
@@ -1034,10 +1005,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     VS vrow[6], vcol[6];
     double bjv[4];                                                   // bjv: J[:, u] of the lane's variable and 1 / D_u (apply_kinv)
     constexpr bool BD_EXPLICIT = (sizeof(R) == 4) || (MODE == 1);     // fp32 iterations and the assembly dump: Bd rows (apply_kinv)
-#ifndef SRBDQP_WRENCH_BD_LAST
-#define SRBDQP_WRENCH_BD_LAST 1
-#endif
-    constexpr bool BD_LAST = SRBDQP_WRENCH_BD_LAST && VBD_LATE && BD_EXPLICIT;   // ... formed after x_q and its refinement (form_bd)
+    constexpr bool BD_LAST = VBD_LATE && BD_EXPLICIT;   // ... formed after x_q and its refinement (form_bd)
     // explicit Bd rows: fp32 from the start in the fp32-tile kernel (only the iterations use them there; x_q and its refinement
     // run in fp64, where the implicit form is exact enough) -- 12 registers instead of 24 next to the T^-1 row
     typedef typename std::conditional<(sizeof(TT) == 4 || (VBD_LATE && sizeof(R) == 4)), float, double>::type BS;
@@ -1047,15 +1015,23 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     int ug_id = 0;                                                   // force-variable step: variable (0..11) of g row rl
     auto lane_roles2 = [&]() __attribute__((always_inline)) {
         before_ci = (ci > 0 ? f0 : 0) + (ci > 1 ? f1 : 0) + (ci > 2 ? f2 : 0);
-        const int want = rl / 3;
-        int cc = -1, seen = 0;
-        if (f0) { if (seen == want && cc < 0) cc = 0; ++seen; }
-        if (f1) { if (seen == want && cc < 0) cc = 1; ++seen; }
-        if (f2) { if (seen == want && cc < 0) cc = 2; ++seen; }
-        if (f3) { if (seen == want && cc < 0) cc = 3; ++seen; }
+        const int cc = nth_stance(f0, f1, f2, f3, rl / 3);
         ug_id = (cc >= 0 ? 3 * cc : 0) + (rl % 3);
     };
     lane_roles2();
+    // the explicit Bd row D^-1 - D^-1 Y' V of the lane's variable from yv (static index: select chains).  On its own where the row is formed late (BD_LAST: after
+    // x_q and its refinement, which use the implicit form -- 12 registers less across those two fp64 applications of K^-1)
+    [[maybe_unused]] auto form_bd = [&](const double (&yv)[6]) __attribute__((always_inline)) {
+        const double* Jj = sm + S::o_J + js * 36;
+        const int fl[4] = {f0, f1, f2, f3};                        // (selects, not factors: the flags as doubles were kept -- spilled -- across the whole kernel)
+        const double wu = active_u ? ((ax < 2) ? idxy : idz) : 0.0;
+#pragma unroll
+        for (int u2 = 0; u2 < 12; ++u2) {
+            const double wgt2 = fl[u2 / 3] ? (((u2 % 3) < 2) ? idxy : idz) : 0.0;
+            const double dotv = yv[0] * Jj[u2] + yv[1] * Jj[12 + u2] + yv[2] * Jj[24 + u2] + yv[3 + (u2 % 3)];
+            bdrow[u2] = (BS)(((u2 == ul) ? wu : 0.0) - wu * wgt2 * dotv);
+        }
+    };
     // registers of V and Bd of a wrench step from er = row rl of E^-1 and yv = E^-1 omega_u, omega_u = [J[:, ul]; e_ax]
     // (the callers form the two from the register matrix in phase E, from the LDS triangle for the late formation; E^-1
     // itself must not be captured here: a by-reference capture turns its select chains into an indexed scratch array)
@@ -1075,27 +1051,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
 #pragma unroll
         for (int r = 0; r < 6; ++r) vcol[r] = (VS)(wu * yv[r]);
         bjv[0] = j0; bjv[1] = j1; bjv[2] = j2; bjv[3] = wu; bsel = 3 + ax;
-        if constexpr (BD_EXPLICIT && !BD_LAST) {
-#pragma unroll
-            for (int u2 = 0; u2 < 12; ++u2) {
-                const double wgt2 = fl[u2 / 3] ? (((u2 % 3) < 2) ? idxy : idz) : 0.0;
-                const double dotv = yv[0] * Jj[u2] + yv[1] * Jj[12 + u2] + yv[2] * Jj[24 + u2] + yv[3 + (u2 % 3)];
-                bdrow[u2] = (BS)(((u2 == ul) ? wu : 0.0) - wu * wgt2 * dotv);   // D^-1 - D^-1 Y' V (static index: select chain)
-            }
-        }
-    };
-    // the explicit Bd row alone (fp32 tiles: formed after x_q and its refinement, which use the implicit form -- 12 registers
-    // less across those two fp64 applications of K^-1)
-    [[maybe_unused]] auto form_bd = [&](const double (&yv)[6]) __attribute__((always_inline)) {
-        const double* Jj = sm + S::o_J + js * 36;
-        const int fl[4] = {f0, f1, f2, f3};
-        const double wu = active_u ? ((ax < 2) ? idxy : idz) : 0.0;
-#pragma unroll
-        for (int u2 = 0; u2 < 12; ++u2) {
-            const double wgt2 = fl[u2 / 3] ? (((u2 % 3) < 2) ? idxy : idz) : 0.0;
-            const double dotv = yv[0] * Jj[u2] + yv[1] * Jj[12 + u2] + yv[2] * Jj[24 + u2] + yv[3 + (u2 % 3)];
-            bdrow[u2] = (BS)(((u2 == ul) ? wu : 0.0) - wu * wgt2 * dotv);
-        }
+        if constexpr (BD_EXPLICIT && !BD_LAST) form_bd(yv);
     };
     // ... of a force-variable step: V = the selection of the stance variables, Bd = 0
     auto form_vbd_identity = [&]() __attribute__((always_inline)) {
@@ -1627,10 +1583,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     SRBDQP_STAMP(a, b, 6);
     }   // !LATP
 
-#ifndef SRBDQP_WRENCH_REROLE
-#define SRBDQP_WRENCH_REROLE 1
-#endif
-    if constexpr (SRBDQP_WRENCH_REROLE && (VBD_LATE || SRBDQP_WRENCH_REROLE > 1)) {
+    if constexpr (VBD_LATE) {
         // the lane roles again, from a lane index the compiler cannot trace: the first set is dead from the last use in phase E on
         // instead of waiting in scratch memory across phases F / W / I (24 registers of the 168; the flags come from LDS again)
         int ln = lane;
@@ -1639,17 +1592,23 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         lane_roles2();
     }
     constexpr bool VPARK = VBD_LATE && S::VPARK;
-    auto late_vbd = [&]() __attribute__((always_inline)) {   // rows / columns of V and Bd now that the accumulator tiles are gone (see phase E)
-        if (wrench) {
-            const double* E4 = sm + S::o_e4 + 21 * js;
-            auto tri = [&](int r, int c) -> double { const int hi = r > c ? r : c, lo = r > c ? c : r; return E4[(hi * (hi + 1)) / 2 + lo]; };
-            const double* Jj = sm + S::o_J + js * 36;
-            const double j0 = Jj[ul], j1 = Jj[12 + ul], j2 = Jj[24 + ul];
-            double er[6], yv[6];
+    // E^-1 of the lane's (wrench) step back from its LDS triangle: yv = E^-1 omega_u and, where asked for, er = its row rl (form_vbd)
+    [[maybe_unused]] auto e4_read = [&](double (&yv)[6], double* er = nullptr) __attribute__((always_inline)) {
+        const double* E4 = sm + S::o_e4 + 21 * js;
+        auto tri = [&](int r, int c) -> double { const int hi = r > c ? r : c, lo = r > c ? c : r; return E4[(hi * (hi + 1)) / 2 + lo]; };
+        const double* Jj = sm + S::o_J + js * 36;
+        const double j0 = Jj[ul], j1 = Jj[12 + ul], j2 = Jj[24 + ul];
+        if (er) {
 #pragma unroll
             for (int c = 0; c < 6; ++c) er[c] = tri(rl, c);
+        }
 #pragma unroll
-            for (int r = 0; r < 6; ++r) yv[r] = tri(r, 0) * j0 + tri(r, 1) * j1 + tri(r, 2) * j2 + tri(r, 3 + ax);
+        for (int r = 0; r < 6; ++r) yv[r] = tri(r, 0) * j0 + tri(r, 1) * j1 + tri(r, 2) * j2 + tri(r, 3 + ax);
+    };
+    auto late_vbd = [&]() __attribute__((always_inline)) {   // rows / columns of V and Bd now that the accumulator tiles are gone (see phase E)
+        if (wrench) {
+            double er[6], yv[6];
+            e4_read(yv, er);
             form_vbd(er, yv);
         } else {
             form_vbd_identity();
@@ -1771,13 +1730,8 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
 
         if constexpr (BD_LAST) {
             if (wrench) {
-                const double* E4 = sm + S::o_e4 + 21 * js;
-                auto tri = [&](int r, int c) -> double { const int hi = r > c ? r : c, lo = r > c ? c : r; return E4[(hi * (hi + 1)) / 2 + lo]; };
-                const double* Jj = sm + S::o_J + js * 36;
-                const double j0 = Jj[ul], j1 = Jj[12 + ul], j2 = Jj[24 + ul];
                 double yv[6];
-#pragma unroll
-                for (int r = 0; r < 6; ++r) yv[r] = tri(r, 0) * j0 + tri(r, 1) * j1 + tri(r, 2) * j2 + tri(r, 3 + ax);
+                e4_read(yv);
                 form_bd(yv);
             } else {
 #pragma unroll
@@ -1798,7 +1752,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         for (int cc = 0; cc < CHMAX; ++cc) kin[cc] = (R)kin64[cc];
 #pragma unroll
         for (int i = 0; i < 6; ++i) { vr[i] = VPARK ? (R)vpr[i * n] : (R)vrow[i]; vc[i] = VPARK ? (R)vpc[i * n] : (R)vcol[i]; }
-        constexpr bool VL = SRBDQP_WRENCH_VLDS && sizeof(R) == 8 && sizeof(TT) == 8 && CHMAX <= 36 && XW == 0;   // (the low-latency instantiation has the registers)
+        constexpr bool VL = sizeof(R) == 8 && sizeof(TT) == 8 && CHMAX <= 36 && XW == 0;   // (the low-latency instantiation has the registers)
         [[maybe_unused]] const R* vlds = nullptr;
         [[maybe_unused]] const double* jlds = sm + S::o_J + js * 36 + ul;
         if constexpr (VL) {
@@ -1846,7 +1800,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         for (int k = 1; k <= a.max_iter + 1 && !done; ++k) {
             WADMM_T(0);
             R* vb = vbuf + (k & 1) * S::VB;
-            const R kw = apply_kinv<R, CHMAX, KREG, VL, (XW > 0 && CHMAX <= 36), (VL && sizeof(R) == 8 && CHMAX > 30 && SRBDQP_WRENCH_JLDS != 0)>(wv, wbw, tbw, vb, lane, sg, ul, active_g, Rrow, CH, kin, vr, vc, bd, vsoff, vssel, [&] {
+            const R kw = apply_kinv<R, CHMAX, KREG, VL, (XW > 0 && CHMAX <= 36), (VL && CHMAX > 30)>(wv, wbw, tbw, vb, lane, sg, ul, active_g, Rrow, CH, kin, vr, vc, bd, vsoff, vssel, [&] {
                 if (pending) {   // decision of the check made at iteration k - 1 (its maxima were published by this barrier)
                     const float* buf = redf + ((nchk - 1) & 1) * 4 * NWS;
                     float v0 = buf[0], v1 = buf[1], v2 = buf[2], v3 = buf[3];
@@ -1958,7 +1912,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     }
     SRBDQP_STAMP(a, b, 8);
     __syncthreads();
-    if constexpr (SRBDQP_WRENCH_REROLE && VBD_LATE) {   // the roles the stores below need, derived again instead of waiting in scratch memory across the iterations
+    if constexpr (VBD_LATE) {   // the roles the stores below need, derived again instead of waiting in scratch memory across the iterations
         int ln = lane;
         asm volatile("" : "+v"(ln));
         lane_roles(ln);
