@@ -99,6 +99,10 @@ struct srbdqp_handle {
     size_t robots_len = 0;
     srbdqp_robot* robots_own = nullptr;    // the library's device copy of host records (srbdqp_set_robots)
     size_t robots_cap = 0;
+    // SRBDQP_FLAG_ANY_HORIZON with a horizon that has no instantiation: cfg.horizon stays the live horizon n (every array has the caller's shape for n) and the
+    // solves run the general kernel instantiated for live_nstar, the smallest tabulated horizon >= n, in its live-horizon mode (srbdqp_wrench.hpp, MODE = 3)
+    int live_nstar = 0;                    // 0: the horizon has its own instantiations
+    std::string live_name;                 // srbdqp_kernel_name of such a handle: wrench_f64_n<N*>_h<n>
 };
 
 // slot of a launch stream (at most kMaxSlots distinct streams per handle; null when exhausted)
@@ -155,11 +159,17 @@ template <int... Ns>
 constexpr bool horizon_in(int N, std::integer_sequence<int, Ns...>) { return ((N == Ns) || ...); }
 bool horizon_supported(int N) { return horizon_in(N, Horizons{}); }
 
-// f(std::integral_constant<int, N>{}) for the handle's horizon N: the one place a run-time horizon becomes a template argument
+// smallest horizon with an instantiation that is >= n (0: none)
+template <int... Ns>
+constexpr int horizon_above(int n, std::integer_sequence<int, Ns...>) { int r = 0; ((r = (r == 0 && Ns >= n) ? Ns : r), ...); return r; }
+
+// f(std::integral_constant<int, N>{}) for the handle's horizon N: the one place a run-time horizon becomes a template argument (a live horizon, SRBDQP_FLAG_ANY_HORIZON:
+// the instantiation it runs on, N* -- only the general kernel's launcher and the refusals get that far)
 template <class F, int... Ns>
 int with_horizon_in(srbdqp_handle* h, F&& f, std::integer_sequence<int, Ns...>) {
     int rc = SRBDQP_E_INVALID;
-    if (!((h->cfg.horizon == Ns && ((rc = f(std::integral_constant<int, Ns>{})), true)) || ...)) h->err = "unsupported horizon";
+    const int N = h->live_nstar ? h->live_nstar : h->cfg.horizon;
+    if (!((N == Ns && ((rc = f(std::integral_constant<int, Ns>{})), true)) || ...)) h->err = "unsupported horizon";
     return rc;
 }
 template <class F>
@@ -293,7 +303,7 @@ constexpr int kTileClassMinBatch = 512;
 // does a solve of B QPs on this handle go to the general kernel (srbdqp_wrench.hpp)?  launch() asks this.
 inline bool uses_wrench(const srbdqp_handle* h, const Call& c, int maxs, int B) {
     const int N = h->cfg.horizon;
-    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || h->robots) return true;   // (per-QP records: only the general kernel reads them)
+    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || h->robots || h->live_nstar) return true;   // (per-QP records, a live horizon: only the general kernel reads them)
     // N = 20 single support too, for batches: the general kernel holds 2 workgroups per CU there, the compact one 1
     // (tools/schedule_bench.py, 16,384 QPs: 2.85 M QP/s against 1.95 M; at N = 12 / 16 the compact kernel wins, 7.1 / 4.9 M
     // against 5.7 / 4.2 M)
@@ -619,6 +629,13 @@ int launch_compact(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t 
     return SRBDQP_OK;
 }
 
+// a call that has no live-horizon form, on a handle whose horizon has no instantiation of its own (SRBDQP_FLAG_ANY_HORIZON; include/srbdqp.h has the reasons)
+int live_refuse(srbdqp_handle* h, const char* what) {
+    h->err = std::string(what) + ": refused on a handle whose horizon " + std::to_string(h->cfg.horizon) + " was admitted by SRBDQP_FLAG_ANY_HORIZON: only the fp64 batch, "
+             "ragged and staged solves run a live horizon (the general kernel's fp64 batch instantiation for N = " + std::to_string(h->live_nstar) + ")";
+    return SRBDQP_E_INVALID;
+}
+
 // The general kernel (srbdqp_wrench.hpp): any contact pattern, fp64 or fp32 iterations / buffers.
 template <int N, typename R, int TB = 8>
 struct WrenchTraits {
@@ -643,6 +660,26 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
     constexpr size_t ldsb = SB::bytes;
     static_assert(ldsb <= 163840, "one QP must fit the LDS of a CU");
     static const std::string nm = std::string("wrench_") + (sizeof(R) == 4 ? "f32" : "f64") + "_n" + std::to_string(N);
+    if (h->live_nstar) {
+        // a live horizon n = cfg.horizon < N (SRBDQP_FLAG_ANY_HORIZON): the MODE = 3 instantiation of the fp64 batch kernel, n as its second argument -- every launch of
+        // a solve (first pass, restart passes, deferred passes on the tail stream, ragged buckets, the staged calls with their completion word) comes through here
+        // with this handle.  (The entry points refuse the fp32, dump and two-phase calls and the robot records on such a handle.)
+        if constexpr (sizeof(R) == 8) {
+            if (a.mode == 1) return live_refuse(h, "the assembly dump");
+            // (the layout of the MODE = 0 twin -- the live horizon itself takes no LDS --, except N* = 24: four more entries of every lane's T^-1 half row in LDS
+            //  instead of registers, srbdqp_wrench.hpp wrench_kreg64; still the twin's one workgroup per CU)
+            using S3 = srbdqp::WrenchSmem<N, 8, 5, BXW, srbdqp::wrench_kreg64(N, 3)>;
+            constexpr size_t lds3 = S3::bytes;
+            static_assert(lds3 <= 163840 && S3::lds_wgs == SB::lds_wgs && (N == 24 || lds3 == ldsb), "a live horizon costs no workgroup per CU: the occupancy of the MODE = 0 twin");
+            void (*k3)(KArgs, int) = &srbdqp::srbdqp_wrench_kernel<N, double, double, 3, WPS, double, 5, BXW>;
+            int rc3 = set_lds_once(h, k3, lds3);
+            if (rc3 != SRBDQP_OK) return rc3;
+            h->kname = h->live_name.c_str();
+            hipLaunchKernelGGL(k3, dim3((unsigned)a.B), dim3(S3::BT), lds3, st, a, (int)h->cfg.horizon);
+            HIP_TRY(h, hipGetLastError());
+            return SRBDQP_OK;
+        } else return live_refuse(h, "an fp32 solve");
+    }
     if (a.mode == 1) {
         if constexpr (sizeof(R) == 8) {
             int rc = set_lds_once(h, &srbdqp::srbdqp_wrench_kernel<N, double, double, 1, WPS>, lds);
@@ -856,7 +893,7 @@ inline int restart_iter_of(const srbdqp_handle* h, int* count = nullptr) {
     //   0.13 -> 0.22 events; 80 x 3 would give 99.6 / 99.9 % for 0.32 events: a set-up is two thirds of a solve there)
     const int N = c.horizon;
     if (automatic) r = (N <= 10) ? 55 : (N == 12 ? 70 : (N == 16 ? 80 : (N == 24 ? 100 : 125)));
-    if (count) *count = c.rho_restart_count > 0 ? c.rho_restart_count : (!automatic ? 1 : ((N <= 12) ? 2 : (N == 16 ? 3 : (N == 24 ? 2 : 1))));
+    if (count) *count = c.rho_restart_count > 0 ? c.rho_restart_count : (!automatic ? 1 : ((N <= 10 || N == 12) ? 2 : (N == 16 ? 3 : (N == 24 ? 2 : 1))));   // (every other N > 10 -- the live horizons 11, 13 ... -- as N = 20: oracle default_restart)
     // at most three re-balancings, on every kernel (round 5): the one-wave kernel runs its continued passes as three straight copies of the body -- a loop around it
     // costs the whole kernel 30 registers and puts 52 - 72 bytes per lane in scratch memory -- and the rule is the same for every kernel and batch size
     if (count && *count > 3) *count = 3;
@@ -1069,7 +1106,15 @@ int srbdqp_create(const srbdqp_config* cfg, srbdqp_handle** out) {
     if (!cfg || !out) { g_create_err = "null argument"; return SRBDQP_E_INVALID; }
     *out = nullptr;
     if (cfg->struct_size != (int32_t)sizeof(srbdqp_config)) { g_create_err = "srbdqp_config.struct_size mismatch"; return SRBDQP_E_INVALID; }
-    if (!horizon_supported(cfg->horizon)) { g_create_err = "unsupported horizon (N in {4, 8, 10, 12, 16, 20, 24})"; return SRBDQP_E_INVALID; }
+    const bool live = !horizon_supported(cfg->horizon) && (cfg->flags & SRBDQP_FLAG_ANY_HORIZON) && cfg->horizon >= 1 && cfg->horizon <= SRBDQP_MAX_HORIZON;
+    if (!horizon_supported(cfg->horizon) && !live) {
+        g_create_err = "unsupported horizon (N in {4, 8, 10, 12, 16, 20, 24}; with SRBDQP_FLAG_ANY_HORIZON every N from 1 to 24)";
+        return SRBDQP_E_INVALID;
+    }
+    if (live && cfg->kernel != SRBDQP_KERNEL_AUTO && cfg->kernel != SRBDQP_KERNEL_WRENCH) {
+        g_create_err = "SRBDQP_FLAG_ANY_HORIZON: a horizon outside {4, 8, 10, 12, 16, 20, 24} runs on the general kernel only (srbdqp_config.kernel = SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH)";
+        return SRBDQP_E_INVALID;
+    }
     if (cfg->kernel != SRBDQP_KERNEL_AUTO && cfg->kernel != SRBDQP_KERNEL_COMPACT && cfg->kernel != SRBDQP_KERNEL_SPLIT &&
         cfg->kernel != SRBDQP_KERNEL_WAVE && cfg->kernel != SRBDQP_KERNEL_WRENCH) { g_create_err = "unknown srbdqp_config.kernel (the round-1 baselines v0 / v1 are retired)"; return SRBDQP_E_INVALID; }
     if (!(cfg->dt > 0) || !(cfg->mass > 0) || !(cfg->force_scale > 0) || !(cfg->rho >= 0) || !(cfg->sigma > 0) ||
@@ -1089,6 +1134,13 @@ int srbdqp_create(const srbdqp_config* cfg, srbdqp_handle** out) {
     srbdqp_handle* h = new (std::nothrow) srbdqp_handle();
     if (!h) { g_create_err = "out of host memory"; return SRBDQP_E_NOMEM; }
     h->cfg = *cfg;
+    if (live) {
+        h->live_nstar = horizon_above(cfg->horizon, Horizons{});
+        h->live_name = "wrench_f64_n" + std::to_string(h->live_nstar) + "_h" + std::to_string(cfg->horizon);
+        // the staged calls run the batch instantiation through the HIP launch, as SRBDQP_FLAG_NO_LAT does (no _lat / *_in kernel reads a live horizon): no AQL queue
+        h->aql_tried = true;
+        h->aql_why = "SRBDQP_FLAG_ANY_HORIZON: a live horizon runs the batch instantiation of the general kernel";
+    }
     if (h->cfg.rho == 0.0) h->cfg.rho = 0.7;                    // auto (oracle auto_rho()): friction rows
     if (h->cfg.rho_fz_scale == 0.0) h->cfg.rho_fz_scale = 4.0;   // auto (oracle auto_rho_fz_scale()): normal-force rows at 4 rho
     auto fail = [&](const char* what, hipError_t er) {
@@ -1256,6 +1308,7 @@ KArgs staged_args(srbdqp_handle* h, int32_t B, bool use_pcom, bool want_x, bool 
 int srbdqp_prepare_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_prepare_staged_f64");
+    if (h->live_nstar) return live_refuse(h, "srbdqp_prepare_staged_f64");
     if (B < 0 || B > h->stage_h.capacity) { h->err = "staged batch exceeds the staging capacity"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1274,6 +1327,7 @@ int srbdqp_prepare_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom) {
 int srbdqp_solve_prepared_f64(srbdqp_handle* h, int32_t B, int32_t want_x, int32_t want_y) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_solve_prepared_f64");
+    if (h->live_nstar) return live_refuse(h, "srbdqp_solve_prepared_f64");
     if (B <= 0 || B != h->prepared_B) { h->err = "srbdqp_solve_prepared_f64: no set-up of this batch size is pending (srbdqp_prepare_staged_f64)"; return SRBDQP_E_INVALID; }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const bool spin = !(h->cfg.flags & SRBDQP_FLAG_NO_SPIN);
@@ -1298,6 +1352,7 @@ int srbdqp_set_robots(srbdqp_handle* h, const srbdqp_robot* host, int32_t length
     if (!h) return SRBDQP_E_INVALID;
     if (host && length < 0) { h->err = "srbdqp_set_robots: negative length"; return SRBDQP_E_INVALID; }
     const bool clear = !host || length == 0;
+    if (!clear && h->live_nstar) return live_refuse(h, "srbdqp_set_robots");
     if (!clear && h->cfg.horizon > kRobotsMaxHorizon) { h->err = robots_n24; return SRBDQP_E_INVALID; }
     if (!clear) {
         const int rv = robots_validate(host, length, "srbdqp_set_robots", h->err);
@@ -1319,6 +1374,7 @@ int srbdqp_set_robots_device(srbdqp_handle* h, const srbdqp_robot* dev, int32_t 
     if (!h) return SRBDQP_E_INVALID;
     if (dev && length < 0) { h->err = "srbdqp_set_robots_device: negative length"; return SRBDQP_E_INVALID; }
     const bool clear = !dev || length == 0;
+    if (!clear && h->live_nstar) return live_refuse(h, "srbdqp_set_robots_device");
     if (!clear && h->cfg.horizon > kRobotsMaxHorizon) { h->err = robots_n24; return SRBDQP_E_INVALID; }
     h->robots = clear ? nullptr : dev;
     h->robots_len = clear ? 0 : (size_t)length;
@@ -1601,6 +1657,7 @@ int srbdqp_solve_batch_device_f32(srbdqp_handle* h, int32_t B, const float* x0, 
                                   float* y_out, int32_t* status, int32_t* iters, void* stream) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_solve_batch_device_f32");
+    if (h->live_nstar) return live_refuse(h, "srbdqp_solve_batch_device_f32");
     return solve_device_impl(h, device_call(h, true), B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
 }
 
@@ -1618,6 +1675,7 @@ int srbdqp_solve_batch_f32(srbdqp_handle* h, int32_t B, const float* x0, const f
                            float* u_out, float* x_out, float* y_out, int32_t* status, int32_t* iters) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_solve_batch_f32");
+    if (h->live_nstar) return live_refuse(h, "srbdqp_solve_batch_f32");
     return solve_host_impl(h, true, B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters);
 }
 
@@ -1626,6 +1684,7 @@ int srbdqp_assemble_f64(srbdqp_handle* h, int32_t B, const double* x0, const dou
                         double* ub_out) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_assemble_f64");
+    if (h->live_nstar) return live_refuse(h, "srbdqp_assemble_f64");
     if (B < 0 || (B > 0 && (!x0 || !x_ref || !foot || !contact || !P_out || !q_out || !l_out || !ub_out))) { h->err = "null pointer"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1701,6 +1760,7 @@ int srbdqp_assemble_wrench_f64(srbdqp_handle* h, int32_t B, const double* x0, co
                                double* goff_out) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_assemble_wrench_f64");
+    if (h->live_nstar) return live_refuse(h, "srbdqp_assemble_wrench_f64");
     if (B < 0 || (B > 0 && (!x0 || !x_ref || !foot || !contact || !T_out || !q_out || !blocks_out || !goff_out))) { h->err = "null pointer"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1837,6 +1897,7 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
                        int32_t* status, int32_t* iters, void* stream, bool f32) {
     if (!r) return SRBDQP_E_INVALID;
     if (B < 0 || (B > 0 && (!N_per_qp || !x0 || !x_ref || !foot || !contact || !u_out))) { r->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (f32) for (auto* bh : r->hs) if (bh->live_nstar) { live_refuse(bh, "an fp32 ragged solve"); r->err = bh->err; return SRBDQP_E_INVALID; }
     if (r->robots && f32) { r->err = "fp32 ragged solve: refused while per-QP robot records are set (srbdqp_ragged_set_robots): only the fp64 solves read them"; return SRBDQP_E_INVALID; }
     if (r->robots && (size_t)B > r->robots_len) {
         r->err = "ragged solve of " + std::to_string(B) + " QPs with " + std::to_string(r->robots_len) + " robot records set: every QP needs its record";
@@ -2009,6 +2070,7 @@ int srbdqp_ragged_set_robots(srbdqp_ragged* r, const srbdqp_robot* host, int32_t
     if (!r) return SRBDQP_E_INVALID;
     if (host && length < 0) { r->err = "srbdqp_ragged_set_robots: negative length"; return SRBDQP_E_INVALID; }
     const bool clear = !host || length == 0;
+    if (!clear) for (auto* bh : r->hs) if (bh->live_nstar) { live_refuse(bh, "per-QP robot records on a ragged object"); r->err = bh->err; return SRBDQP_E_INVALID; }
     if (!clear) for (int hz : r->horizons) if (hz > kRobotsMaxHorizon) { r->err = std::string("bucket N=") + std::to_string(hz) + ": " + robots_n24; return SRBDQP_E_INVALID; }
     if (!clear) {
         const int rv = robots_validate(host, length, "srbdqp_ragged_set_robots", r->err);
@@ -2033,6 +2095,7 @@ int srbdqp_ragged_set_robots_device(srbdqp_ragged* r, const srbdqp_robot* dev, i
     if (!r) return SRBDQP_E_INVALID;
     if (dev && length < 0) { r->err = "srbdqp_ragged_set_robots_device: negative length"; return SRBDQP_E_INVALID; }
     const bool clear = !dev || length == 0;
+    if (!clear) for (auto* bh : r->hs) if (bh->live_nstar) { live_refuse(bh, "per-QP robot records on a ragged object"); r->err = bh->err; return SRBDQP_E_INVALID; }
     if (!clear) for (int hz : r->horizons) if (hz > kRobotsMaxHorizon) { r->err = std::string("bucket N=") + std::to_string(hz) + ": " + robots_n24; return SRBDQP_E_INVALID; }
     r->robots = clear ? nullptr : dev;
     r->robots_len = clear ? 0 : (size_t)length;
@@ -2187,7 +2250,9 @@ int srbdqp_mpc_inputs_device_f64(srbdqp_handle* h, int64_t B, const double* x0, 
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
     const long long tiles = ((long long)B + 31) / 32;                   // one tile of 32 robots per workgroup pass
     const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
-    const int rc = with_horizon(h, [&](auto n) -> int {
+    int rc = SRBDQP_OK;
+    if (h->live_nstar) hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<0>, grid, dim3(256), 0, st, a);   // (a live horizon: a.N at run time)
+    else rc = with_horizon(h, [&](auto n) -> int {
         hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<decltype(n)::value>, grid, dim3(256), 0, st, a);
         return SRBDQP_OK;
     });

@@ -152,10 +152,11 @@ struct MpcInputsArgs {
 // of 13 + 12 + 3 doubles: 1.2 TB/s; one thread per output element with the inputs re-read through L2: 2.4 TB/s.)  Every
 // product and sum is a single rounded operation in the order of msgs.MpcNode.step (no fused multiply-add: the oracle is
 // compared bit for bit).
-template <int NH>   // the horizon as a compile-time constant: every index division becomes a multiply-shift
+template <int NH>   // the horizon as a compile-time constant: every index division becomes a multiply-shift (NH = 0: a.N at run time -- SRBDQP_FLAG_ANY_HORIZON)
 __global__ __launch_bounds__(256) void srbdqp_mpc_inputs_kernel(MpcInputsArgs a) {
 #pragma clang fp contract(off)   // no fused multiply-add in this kernel (HIP's __dmul_rn / __dadd_rn do not prevent it)
-    constexpr int R = 32, N = NH;
+    constexpr int R = 32;
+    const int N = NH > 0 ? NH : a.N;
     __shared__ double sx0[R * 13], sft[R * 12], sv[R * 2];
     __shared__ int sph[R];                                               // phase of step 0 in [0, 2 period), or -1 = standing
     const int t = threadIdx.x;

@@ -179,7 +179,8 @@ __device__ __forceinline__ double unis(double v) {
 // Valid for step(r) <= step(c): the upper triangle; the entries of a diagonal tile below the diagonal are never read (diag16_invert reads the upper triangle).
 constexpr int kAbStride = 18;   // doubles per table row (16 + 2: rows 144 bytes apart, 16-byte aligned)
 template <int N>
-__device__ __forceinline__ void de_tables(const double* CP, const double* T1, const double* T2, const double* SQ, const double dt2, double* DE, const int t, const int nthreads) {
+__device__ __forceinline__ void de_tables(const double* CP, const double* T1, const double* T2, const double* SQ, const double dt2, double* DE, const int t, const int nthreads, const int nl = N) {
+    // nl: the live horizon (the general kernel's MODE = 3): the number of steps the velocity weights of step m are counted over is nl - m
     for (int it = t; it < 9 * N; it += nthreads) {
         const int m = it / 9, k = it - 9 * m, p = k / 3, q = k - 3 * p;
         const double* Cm = CP + 9 * m;
@@ -188,7 +189,7 @@ __device__ __forceinline__ void de_tables(const double* CP, const double* T1, co
         const double e0 = SQ[0] * SQ[0] * t1[q], e1 = SQ[1] * SQ[1] * t1[3 + q], e2 = SQ[2] * SQ[2] * t1[6 + q];
         double v = T2[9 * m + k] + Cm[p] * e0 + Cm[3 + p] * e1 + Cm[6 + p] * e2;
         v *= d4;
-        v += (p == q) ? (double)(N - m) * dt2 * SQ[6 + p] * SQ[6 + p] : 0.0;
+        v += (p == q) ? (double)(nl - m) * dt2 * SQ[6 + p] * SQ[6 + p] : 0.0;
         DE[18 * m + k] = v;                                                  // D_m[p][q]
         DE[18 * m + 9 + k] = d4 * ((p == 0) ? e0 : (p == 1) ? e1 : e2);      // E_m[p][q]
     }

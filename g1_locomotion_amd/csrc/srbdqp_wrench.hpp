@@ -40,6 +40,11 @@
 
 namespace srbdqp {
 
+// live horizons 21 ... 23 (MODE = 3 at N = 24): entries of a lane's fp64 T^-1 half row kept in registers.  The MODE = 0 kernel keeps 56 and 20 bytes per lane in
+// scratch memory; the live-horizon copy kept 28 bytes there with 56, and none with 54, 52 (255 registers), 48 (247) or 40 (236)
+#ifndef SRBDQP_LIVE24_KREG
+#define SRBDQP_LIVE24_KREG 52
+#endif
 #ifndef SRBDQP_PHASE_LOCAL
 #define SRBDQP_PHASE_LOCAL(...) asm volatile("" : __VA_ARGS__)
 #endif
@@ -51,7 +56,9 @@ namespace srbdqp {
 //       tile phases want as many waves as there are tiles; the iteration wants as FEW waves as hold its lanes -- every wave
 //       reads the whole vector v from LDS for its T^-1 rows, so with the steps spread over 4 waves (3 per wave, tried first) the
 //       broadcast reads alone took ~550 of an iteration's ~1950 cycles (tools/wrench_stamps_staged.py, -DSRBDQP_PROFILE_WADMM)
-template <int N, int TB = 8, int SPW = 5, int XW = 0>
+// KR64 = entries of an fp64 half row longer than 60 that stay in registers (KREG64 below; wrench_kreg64() has the one exception to 56)
+constexpr int wrench_kreg64(int N, int MODE) { return (MODE == 3 && N == 24) ? SRBDQP_LIVE24_KREG : 56; }
+template <int N, int TB = 8, int SPW = 5, int XW = 0, int KR64 = 56>
 struct WrenchSmem {
     static_assert(SPW >= 1 && SPW <= 5, "12 lanes per step");
     static constexpr int n = 12 * N, m = 20 * N;
@@ -117,7 +124,7 @@ struct WrenchSmem {
     static constexpr int o_ws = o_T + NTT * 256 * TB / 8;   // fp32 tiles: one 16 x 16 scratch tile per wave (operand re-layout)
     // fp64 iterations with a half row longer than 60 (N = 24): its last KTAIL entries per lane, entry-major [KTAIL][BT] (the tiles
     // are dead by then and their region is far larger)
-    static constexpr int KREG64 = 56;   // entries of the fp64 half row kept in registers when it is longer than 60 (N = 24 mixed gait: 56 -> 1.06 M QP/s with 2 reloads from scratch left in the iteration, 48 -> 1.03 M with none, 40 -> 1.01 M)
+    static constexpr int KREG64 = KR64;   // entries of the fp64 half row kept in registers when it is longer than 60 (N = 24 mixed gait: 56 -> 1.06 M QP/s with 2 reloads from scratch left in the iteration, 48 -> 1.03 M with none, 40 -> 1.01 M)
     static constexpr int KTAIL = (TB == 8 && CHMAX > 60) ? CHMAX - KREG64 : ((TB == 8 && CHMAX == 36) ? 12 : 0);   // N = 12: 3 waves per SIMD
     static constexpr int o_kt = up2(endC);
     static constexpr int o_vl = o_kt + KTAIL * BT;        // VL: row and column of V per lane, entry-major [12][BT]
@@ -629,18 +636,23 @@ __device__ __forceinline__ void qp_robot_to_lds(const KArgs& a, const double* re
 
 // One QP (index b) on one workgroup of NW waves.  TIO = element type of the caller's buffers, R = iteration type.
 // MODE: 0 = solve, 1 = assembly dump (srbdqp_assemble_wrench_f64), 2 = solve with the QP's own robot record robots[8 b .. 8 b + 8) (qp_robot_to_lds) in place
-// of KArgs::inv_mass / iinv / mu / fzmin_s / fzmax_s -- every use below reads (RB ? RBV[k] : a.<value>), so MODE 0 compiles to what it did without it.
+// of KArgs::inv_mass / iinv / mu / fzmin_s / fzmax_s -- every use below reads (RB ? RBV[k] : a.<value>), so MODE 0 compiles to what it did without it;
+// 3 = solve of a LIVE horizon nl <= N (SRBDQP_FLAG_ANY_HORIZON): the caller's arrays hold nl rows per QP, steps >= nl have no contacts, no error rows and no
+// part in any sum over the horizon, and nothing is stored past row nl -- every such place below reads (LH ? ... : ...) or (!LH || ...), constant in the other modes.
 template <int N, typename R, typename TIO, int MODE, typename TT = double, int SPW = 5, int XW = 0>
-__device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* sm, const double* robots = nullptr) {
-    using S = WrenchSmem<N, (int)sizeof(TT), SPW, XW>;
+__device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* sm, const double* robots = nullptr, const int nl = N) {
+    using S = WrenchSmem<N, (int)sizeof(TT), SPW, XW, wrench_kreg64(N, MODE)>;
     typedef TT v4t __attribute__((ext_vector_type(4)));
     static_assert(sizeof(TT) == 8 || (sizeof(R) == 4 && MODE == 0), "fp32 tiles belong to the fp32 path");
     constexpr int n = S::n, m = S::m, NW = S::NW, NWS = S::NWS, BT = S::BT, LT = S::LT, TS = S::TS, CHMAX = S::CHMAX;
-    static_assert(XW == 0 || (sizeof(TT) == 8 && MODE == 0), "extra set-up waves: fp64 tiles, solve mode");
+    static_assert(XW == 0 || (sizeof(TT) == 8 && (MODE == 0 || MODE == 3)), "extra set-up waves: fp64 tiles, solve mode");
     static_assert((S::o_R % 2) == 0 && (S::o_wb % 2) == 0 && (S::o_tb % 2) == 0 && (S::o_vb % 2) == 0, "16-byte alignment");
     static_assert(S::NT <= 2 * NW || S::WQ >= 1, "");
     const double rho_b = unis(SRBDQP_RHO_OF(a, b));   // (per-QP values are wave-uniform: scalar registers, see uni())
     constexpr bool RB = MODE == 2;
+    constexpr bool LH = MODE == 3;
+    static_assert(!LH || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && (XW == 0 || N == 24)), "live horizons: the fp64 batch instantiation");
+    const int NL = LH ? nl : N;                                      // the live horizon (wave-uniform: a kernel argument)
     static_assert(!RB || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && XW == 0), "per-QP robot records: the fp64 batch instantiation");
     [[maybe_unused]] const double* const RBV = sm + S::o_end;        // MODE 2: the QP's robot (qp_robot_to_lds), from the first barrier on
     const int t = threadIdx.x, lane = t & 63;
@@ -657,7 +669,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     uint8_t* gstep = reinterpret_cast<uint8_t*>(sm + S::o_gs);
     const double* SQ = sm + S::o_sq;
     const double* CP = sm + S::o_cp;
-    const size_t row0 = a.row_off ? (size_t)a.row_off[b] : (size_t)b * N;   // first horizon row of this QP in the step-major arrays
+    const size_t row0 = a.row_off ? (size_t)a.row_off[b] : (size_t)b * NL;   // first horizon row of this QP in the step-major arrays
     const TIO* gwu = reinterpret_cast<const TIO*>(a.warm_u) + row0 * 12;
     const TIO* gwy = reinterpret_cast<const TIO*>(a.warm_y) + row0 * 20;
 
@@ -671,23 +683,23 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         const uint8_t* gct = kin_ ? reinterpret_cast<const uint8_t*>(kin_ + offsetof(StagedIn<N>, contact)) : a.contact + row0 * 4;
         constexpr int RX = (N * 13 + BT - 1) / BT, RF = (N * 12 + BT - 1) / BT;
         static_assert(N * 4 <= BT && N * 3 <= BT, "one thread per contact flag / pcom entry");
-        const TIO* gpc = a.pcom ? (kin_ ? reinterpret_cast<const TIO*>(kin_ + offsetof(StagedIn<N>, pcom)) : reinterpret_cast<const TIO*>(a.pcom) + (size_t)b * N * 3) : gx0;
+        const TIO* gpc = a.pcom ? (kin_ ? reinterpret_cast<const TIO*>(kin_ + offsetof(StagedIn<N>, pcom)) : reinterpret_cast<const TIO*>(a.pcom) + (size_t)b * NL * 3) : gx0;
         const TIO v_x0 = gx0[t < 13 ? t : 0];
-        const uint8_t v_ct = gct[t < N * 4 ? t : 0];
-        const TIO v_pc = gpc[(a.pcom && t < N * 3) ? t : 0];
+        const uint8_t v_ct = gct[t < NL * 4 ? t : 0];
+        const TIO v_pc = gpc[(a.pcom && t < NL * 3) ? t : 0];
         TIO v_xr[RX], v_ft[RF];
 #pragma unroll
-        for (int r = 0; r < RX; ++r) { const int i = t + r * BT; v_xr[r] = gxr[i < N * 13 ? i : 0]; }
+        for (int r = 0; r < RX; ++r) { const int i = t + r * BT; v_xr[r] = gxr[i < NL * 13 ? i : 0]; }
 #pragma unroll
-        for (int r = 0; r < RF; ++r) { const int i = t + r * BT; v_ft[r] = gft[i < N * 12 ? i : 0]; }
+        for (int r = 0; r < RF; ++r) { const int i = t + r * BT; v_ft[r] = gft[i < NL * 12 ? i : 0]; }
         if (t < 13) sm[S::o_x0 + t] = (double)v_x0;
         if (t >= 32 && t < 44) sm[S::o_sq + t - 32] = a.sqrtq[t - 32];
 #pragma unroll
-        for (int r = 0; r < RX; ++r) { const int i = t + r * BT; if (i < N * 13) sm[S::o_xref + i] = (double)v_xr[r]; }
+        for (int r = 0; r < RX; ++r) { const int i = t + r * BT; if (i < N * 13) sm[S::o_xref + i] = (LH && i >= NL * 13) ? 0.0 : (double)v_xr[r]; }   // (live horizon: the rows behind it are zero -- finite tables, no contacts)
 #pragma unroll
-        for (int r = 0; r < RF; ++r) { const int i = t + r * BT; if (i < N * 12) sm[S::o_foot + i] = (double)v_ft[r]; }
-        if (t < N * 4) sct[t] = v_ct ? 1 : 0;
-        if (a.pcom && t < N * 3) sm[S::o_pcom + t] = (double)v_pc;
+        for (int r = 0; r < RF; ++r) { const int i = t + r * BT; if (i < N * 12) sm[S::o_foot + i] = (LH && i >= NL * 12) ? 0.0 : (double)v_ft[r]; }
+        if (t < N * 4) sct[t] = (v_ct && (!LH || t < NL * 4)) ? 1 : 0;
+        if (a.pcom && t < N * 3) sm[S::o_pcom + t] = (LH && t >= NL * 3) ? 0.0 : (double)v_pc;
         if (t == 0) { sm[S::o_misc] = 0.0; sm[S::o_misc + 1] = 0.0; }
         if constexpr (RB) { if (t == 0) qp_robot_to_lds(a, robots + (size_t)b * 8, sm + S::o_end); }
         __syncthreads();
@@ -777,7 +789,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     if constexpr (RB) rb_bad = unis(RBV[7]) != 0.0;
     if (na == 0 || (RB && rb_bad)) {   // nothing to solve: all forces 0 (MODE 2, a record that is not a robot: the same, reported as SRBDQP_NUMERICAL)
         for (int c = t; c < n; c += BT) sm[S::o_xs + c] = 0.0;
-        if (a.y_out) for (int i = t; i < m; i += BT) reinterpret_cast<TIO*>(a.y_out)[row0 * 20 + i] = TIO(0);
+        if (a.y_out) for (int i = t; i < (LH ? 20 * NL : m); i += BT) reinterpret_cast<TIO*>(a.y_out)[row0 * 20 + i] = TIO(0);
         if (t == 0) { const int st0 = (RB && rb_bad) ? -1 : 1; if (a.status) a.status[b] = st0; if (a.iters) a.iters[b] = 0; cs_host = done_cs_pack(st0, 0); }
         __syncthreads();
     } else {
@@ -798,7 +810,10 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     const int tt = TSPLIT ? lane : t;
     constexpr int TSTR = TSPLIT ? 64 : BT;
     if (tab_a)
-    for (int k = tt; k < n; k += TSTR) eh_entry<N, S>(a, sm, SQ, k);
+    for (int k = tt; k < n; k += TSTR) {
+        if (LH && k >= 12 * NL) sm[S::o_eh + k] = 0.0;               // (no error rows behind the live horizon: the gradient's suffix sums and the G'v tables add exact zeros there)
+        else eh_entry<N, S>(a, sm, SQ, k);
+    }
     if (tab_b)
     for (int idx = tt; idx < 9 * N; idx += TSTR) {
         const int mm = idx / 9, pq = idx - 9 * mm, p = pq / 3, q = pq - 3 * p;
@@ -809,7 +824,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
 #pragma unroll TUNR
         for (int i = 0; i < N; ++i) {
             const double* Ci = CP + i * 9;
-            const double on = (i >= mm) ? 1.0 : 0.0;
+            const double on = (i >= mm && (!LH || i < NL)) ? 1.0 : 0.0;
             const double d0p = Ci[p] - m0p, d1p = Ci[3 + p] - m1p, d2p = Ci[6 + p] - m2p;
             const double d0q = Ci[q] - m0q, d1q = Ci[3 + q] - m1q, d2q = Ci[6 + q] - m2q;
             s1 = fma(on, Ci[pq] - mpq, s1);
@@ -930,7 +945,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         }
     } else {
         gt_tables(sm + S::o_eh);
-        de_tables<N>(CP, T1, T2, SQ, dt2, MT, t, BT);
+        de_tables<N>(CP, T1, T2, SQ, dt2, MT, t, BT, NL);
         __syncthreads();
     }
     SRBDQP_STAMP(a, b, 1);
@@ -961,7 +976,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         for (int k = t; k < n; k += BT) {   // G x^0, row kk of step i
             const int i = k / 12, kk = k - 12 * i;
             const double acc = gx_row<N>(CP, TF, i, kk, dt, dt2, dtm, dt2m);
-            sm[S::o_gx + k] = SQ[kk] * a.s * acc;
+            sm[S::o_gx + k] = (LH && i >= NL) ? 0.0 : SQ[kk] * a.s * acc;
         }
         __syncthreads();
         gt_tables(sm + S::o_gx);
@@ -1224,7 +1239,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     if constexpr (MODE == 1) { if (sm[S::o_misc] != 0.0) { if (t == 0) a.ub_out[(size_t)b * (N + 1) + N] = -1.0; return; } }
     if (sm[S::o_misc] != 0.0) {   // degenerate contact geometry: report, return zero forces
         for (int c = t; c < n; c += BT) sm[S::o_xs + c] = 0.0;
-        if (a.y_out) for (int i = t; i < m; i += BT) reinterpret_cast<TIO*>(a.y_out)[row0 * 20 + i] = TIO(0);
+        if (a.y_out) for (int i = t; i < (LH ? 20 * NL : m); i += BT) reinterpret_cast<TIO*>(a.y_out)[row0 * 20 + i] = TIO(0);
         if (t == 0) { if (a.status) a.status[b] = -1; if (a.iters) a.iters[b] = 0; cs_host = done_cs_pack(-1, 0); }
         __syncthreads();
     } else {
@@ -1330,7 +1345,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     for (int i = 0; i < 6; ++i) Bv[i] = s2 * (D[3 * i] * c0 + D[3 * i + 1] * c1 + D[3 * i + 2] * c2);      // D_m z_ang (3), E_m z_ang (3)
                     gc = s2 * ((cm3 == 0) ? zc[3] : (cm3 == 1) ? zc[4] : zc[5]);
                 }
-                const int Ls = N - mm;
+                const int Ls = NL - mm;
                 const double al = (double)(((Ls - 1) * Ls * (2 * Ls - 1)) / 6), be = (double)(((Ls - 1) * Ls) / 2);
                 const double fa = SQ[3 + cm3] * SQ[3 + cm3] * dt4m2, fb = SQ[9 + cm3] * SQ[9 + cm3] * dt2m2;
                 const double f0 = gc * (fa * (al + (double)mm * be) + fb * (double)Ls), f1 = gc * fa * be;
@@ -1920,7 +1935,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     if (stepok) sm[S::o_xs + uvar] = (double)x;
     if (a.y_out && (!a.y_capped_only || status == 2)) {
         TIO* yo = reinterpret_cast<TIO*>(a.y_out) + row0 * 20;
-        if (stepok) {
+        if (stepok && (!LH || js < NL)) {
             const bool on = active_u;
             yo[irowA] = on ? (TIO)yA : TIO(0);
             if (ax < 2) yo[irowB] = on ? (TIO)yB : TIO(0);
@@ -1941,16 +1956,16 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     {
         const double* uh = sm + S::o_xs;
         double* scratch = sm + S::o_scr;
-        const size_t row0 = a.row_off ? (size_t)a.row_off[b] : (size_t)b * N;
+        const size_t row0 = a.row_off ? (size_t)a.row_off[b] : (size_t)b * NL;
         TIO* uo = reinterpret_cast<TIO*>(a.u_out) + row0 * 12;
         ESTAMP(a, 4);
-        for (int c = t; c < n; c += LT) {
+        for (int c = t; c < (LH ? 12 * NL : n); c += LT) {
             const TIO v = (TIO)(a.s * uh[c]);
             uo[c] = v;
             if constexpr (CSUM) cs_host ^= (unsigned long long)__double_as_longlong((double)v);
         }
         ESTAMP(a, 5);
-        if constexpr (sizeof(TIO) == 8) { if (a.u_dev) for (int c = t; c < n; c += LT) a.u_dev[row0 * 12 + c] = a.s * uh[c]; }
+        if constexpr (sizeof(TIO) == 8) { if (a.u_dev) for (int c = t; c < (LH ? 12 * NL : n); c += LT) a.u_dev[row0 * 12 + c] = a.s * uh[c]; }
         // (the completion word's address and value in scalar registers now: left to the end, their loads from the argument segment are two more round trips)
         int32_t* dflag = a.done_flag;
         int32_t dval = a.done_value, dcs = a.done_cs;
@@ -2031,7 +2046,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             }
             __syncthreads();
             TIO* xo = reinterpret_cast<TIO*>(a.x_out) + (row0 + (size_t)b) * 13;      // N + 1 rows per QP
-            for (int idx = t; idx < 13 * (N + 1); idx += LT) {
+            for (int idx = t; idx < 13 * (NL + 1); idx += LT) {
                 const TIO v = (TIO)xrow[idx];
                 xo[idx] = v;
                 if constexpr (CSUM) cs_host ^= (unsigned long long)__double_as_longlong((double)v);
@@ -2082,6 +2097,25 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, SPW, XW>::BT), WPS) void srbdqp_w
     }
     if ((!a.count_ptr || (int)blockIdx.x < *a.count_ptr) && !SRBDQP_RESTART_SKIP(a, SRBDQP_QP_INDEX(a)))
         wrench_qp<N, R, TIO, MODE, TT, SPW, XW>(a, SRBDQP_QP_INDEX(a), sm, robots);
+    signal_done(a);
+}
+
+// ... MODE = 3: a live horizon nl <= N (SRBDQP_FLAG_ANY_HORIZON), as the second kernel argument for the same reasons: KArgs keeps its size, and every launch of a
+// solve -- restart, deferred and ragged passes included -- reaches it through the launcher.  (The prologue word for word, as above.)
+template <int N, typename R, typename TIO, int MODE, int WPS, typename TT = double, int SPW = 5, int XW = 0, typename = std::enable_if_t<MODE == 3>>
+__global__ __launch_bounds__((WrenchSmem<N, 8, SPW, XW>::BT), WPS) void srbdqp_wrench_kernel(KArgs a, const int nl) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    if ((int)blockIdx.x >= a.B) return;
+    if (a.tile_sel) {
+        const uint32_t* cf = reinterpret_cast<const uint32_t*>(a.contact + (size_t)SRBDQP_QP_INDEX(a) * (N * 4));   // 4 flags per step
+        const int lane = threadIdx.x & 63;
+        const uint32_t v = cf[lane < N ? lane : 0];
+        const int nc = ((v & 0xffu) ? 1 : 0) + ((v & 0xff00u) ? 1 : 0) + ((v & 0xff0000u) ? 1 : 0) + ((v & 0xff000000u) ? 1 : 0);
+        const bool wrench_only = __ballot(lane < N && (nc == 1 || nc == 2)) == 0ull;
+        if (wrench_only != (a.tile_sel == 1)) return;
+    }
+    if ((!a.count_ptr || (int)blockIdx.x < *a.count_ptr) && !SRBDQP_RESTART_SKIP(a, SRBDQP_QP_INDEX(a)))
+        wrench_qp<N, R, TIO, MODE, TT, SPW, XW>(a, SRBDQP_QP_INDEX(a), sm, nullptr, nl);
     signal_done(a);
 }
 

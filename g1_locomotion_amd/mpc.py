@@ -92,6 +92,8 @@ class BatchMPC:
                     arr[i] = float(x)
             else:
                 setattr(cfg, k, type(getattr(cfg, k))(v))
+        if cfg.horizon not in _lib.HORIZONS:        # any other horizon 1 ... 24: the general kernel's live-horizon mode (include/srbdqp.h, SRBDQP_FLAG_ANY_HORIZON)
+            cfg.flags |= _lib.FLAG_ANY_HORIZON
         self.cfg = cfg
         self._lib = lib
         self._h = C.c_void_p()
@@ -374,6 +376,8 @@ class RaggedMPC:
                 raise TypeError(f"unknown srbdqp_config field {k!r}")
             setattr(cfg, k, type(getattr(cfg, k))(v))
         self.horizons = tuple(int(h) for h in horizons)
+        if any(h not in _lib.HORIZONS for h in self.horizons):   # buckets at any horizon 1 ... 24 (SRBDQP_FLAG_ANY_HORIZON)
+            cfg.flags |= _lib.FLAG_ANY_HORIZON
         hz = np.ascontiguousarray(self.horizons, dtype=np.int32)
         self._lib = lib
         self._h = C.c_void_p()

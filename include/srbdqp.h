@@ -31,7 +31,7 @@ extern "C" {
 #define SRBDQP_NU 12
 #define SRBDQP_NC 4
 #define SRBDQP_ROWS_PER_STEP 20   /* 4 contacts x (4 friction-pyramid rows + 1 normal-force row) */
-#define SRBDQP_MAX_HORIZON 24     /* instantiations: N in {4, 8, 10, 12, 16, 20, 24} */
+#define SRBDQP_MAX_HORIZON 24     /* instantiations: N in {4, 8, 10, 12, 16, 20, 24}; every N from 1 with SRBDQP_FLAG_ANY_HORIZON */
 
 /* return codes */
 #define SRBDQP_OK 0
@@ -70,6 +70,23 @@ extern "C" {
                                      with no error).  For pipelines of independent batches in their own buffers; see srbdqp_flush */
 #define SRBDQP_FLAG_NO_SPIN 2     /* srbdqp_solve_staged_f64: wait with hipStreamSynchronize instead of spinning on the
                                      completion word the kernel writes to host memory */
+#define SRBDQP_FLAG_ANY_HORIZON 128 /* srbdqp_create / srbdqp_ragged_create admit every horizon from 1 to SRBDQP_MAX_HORIZON.  A horizon with instantiations of
+                                     its own (4, 8, 10, 12, 16, 20, 24) behaves exactly as without the flag.  Any other n is a LIVE horizon:
+                                     cfg.horizon stays n and every array has the caller's shape for n (x_ref [B][n][13], u_out [B][n][12], x_out
+                                     [B][n+1][13], y / warm_y [B][20 n], ...: nothing is padded), and the solves run the general kernel instantiated for
+                                     N* = the smallest tabulated horizon >= n with n as a run-time argument (srbdqp_kernel_name: wrench_f64_n<N*>_h<n>).
+                                     SRBDQP_KERNEL_AUTO and _WRENCH route there; an explicit _COMPACT / _SPLIT / _WAVE returns SRBDQP_E_INVALID from
+                                     srbdqp_create.  The automatic rho restart is the oracle's rule for n (n <= 10: 55 x 2, every other live n: 125 x 1).
+                                     On such a handle
+                                       - srbdqp_solve_batch_f64 / _device_f64 work as at every horizon (warm starts, y_out, the schedule hint, SRBDQP_FLAG_DEFER_TAIL);
+                                       - srbdqp_solve_staged_f64 / srbdqp_update_f64 run the batch instantiation through the HIP launch, as SRBDQP_FLAG_NO_LAT
+                                         does (srbdqp_batch1_launch_path: "hip: ..." with this reason);
+                                       - srbdqp_mpc_inputs_*, srbdqp_wbid_reference_*, srbdqp_swing_* and srbdqp_gather_u0_f64 take n as they take every horizon;
+                                       - these return SRBDQP_E_INVALID with a message that names the flag: the _f32 calls (the fp32 instantiations have no
+                                         live-horizon form: twelve more kernels for buffers nobody asked for at these horizons), srbdqp_prepare_staged_f64 /
+                                         srbdqp_solve_prepared_f64 (the two-phase call is the one-wave pipeline, built per horizon), srbdqp_assemble_f64 /
+                                         srbdqp_assemble_wrench_f64 (the dumps describe an instantiation's own layout: dump at a tabulated horizon), and
+                                         srbdqp_set_robots / _device with records (robots with a live horizon would be a fourth copy of every instantiation). */
 
 /* srbdqp_config.kernel: which implementation of the hot path runs */
 #define SRBDQP_KERNEL_AUTO  0     /* the fastest parity-green kernel */
@@ -243,7 +260,9 @@ typedef struct srbdqp_robot {
  *   (x_out of QP b starts at row off_b + b: N_b + 1 rows), status / iters [B] in the caller's QP order.
  * Every bucket runs the general kernel (any per-QP contact schedule); cfg is the template of the per-horizon engines
  * (horizon ignored, rho = 0 picks each horizon's own penalty, rho_restart_iter as for a homogeneous batch of that horizon:
- * by default the N > 10 buckets take the two-pass rho restart).  Warm starts: srbdqp_solve_ragged_warm_device_*. */
+ * by default the N > 10 buckets take the two-pass rho restart).  Warm starts: srbdqp_solve_ragged_warm_device_*.
+ * With SRBDQP_FLAG_ANY_HORIZON in cfg->flags the list may hold any distinct horizons from 1 to 24: each keeps its own bucket and engine (a live
+ * horizon's engine runs the general kernel of the next tabulated horizon); the fp32 calls and the robot records are refused on such an object. */
 typedef struct srbdqp_ragged srbdqp_ragged;
 int srbdqp_ragged_create(const srbdqp_config* cfg, const int32_t* horizons, int32_t n_horizons, srbdqp_ragged** out);
 int srbdqp_ragged_destroy(srbdqp_ragged* r);
