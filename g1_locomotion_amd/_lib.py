@@ -36,7 +36,7 @@ EXPORTS = (
     "srbdqp_assemble_f64", "srbdqp_assemble_wrench_f64",
     "srbdqp_ragged_create", "srbdqp_ragged_destroy", "srbdqp_ragged_last_error", "srbdqp_ragged_flush", "srbdqp_solve_ragged_device_f64", "srbdqp_solve_ragged_f64",
     "srbdqp_solve_ragged_device_f32", "srbdqp_solve_ragged_f32", "srbdqp_solve_ragged_warm_device_f64", "srbdqp_solve_ragged_warm_device_f32",
-    "srbdqp_set_schedule_hint", "srbdqp_set_robots", "srbdqp_set_robots_device", "srbdqp_ragged_set_robots", "srbdqp_ragged_set_robots_device", "srbdqp_flush", "srbdqp_shard_range", "srbdqp_gather_u0_f64", "srbdqp_stage_ptrs", "srbdqp_solve_staged_f64", "srbdqp_update_f64", "srbdqp_prepare_staged_f64", "srbdqp_solve_prepared_f64", "srbdqp_set_stamp_buffer", "srbdqp_synchronize", "srbdqp_last_kernel_ms", "srbdqp_last_kernel_parts_ms", "srbdqp_kernel_name", "srbdqp_batch1_launch_path", "srbdqp_version",
+    "srbdqp_set_schedule_hint", "srbdqp_set_robots", "srbdqp_set_robots_device", "srbdqp_set_contact_normals", "srbdqp_set_contact_normals_device", "srbdqp_ragged_set_robots", "srbdqp_ragged_set_robots_device", "srbdqp_flush", "srbdqp_shard_range", "srbdqp_gather_u0_f64", "srbdqp_stage_ptrs", "srbdqp_solve_staged_f64", "srbdqp_update_f64", "srbdqp_prepare_staged_f64", "srbdqp_solve_prepared_f64", "srbdqp_set_stamp_buffer", "srbdqp_synchronize", "srbdqp_last_kernel_ms", "srbdqp_last_kernel_parts_ms", "srbdqp_kernel_name", "srbdqp_batch1_launch_path", "srbdqp_version",
     # include/srbdqp_cascade.h
     "srbdqp_swing_f64", "srbdqp_swing_device_f64", "srbdqp_wbid_reference_f64", "srbdqp_wbid_reference_device_f64",
     "srbdqp_mpc_inputs_f64", "srbdqp_mpc_inputs_device_f64",
@@ -100,6 +100,23 @@ def robots_array(B, mass=None, inertia=None, mu=None, fz_min=None, fz_max=None, 
     out[:, 5] = col("fz_min", fz_min, cfg.fz_min, 1)
     out[:, 6] = col("fz_max", fz_max, cfg.fz_max, 1)
     return out
+
+
+def contact_frames(normals):
+    """Contact frames R = [t1 t2 n] of surface normals (..., 3) -> (..., 3, 3): the host mirror of the convention of srbdqp_set_contact_normals
+    (include/srbdqp.h; csrc/srbdqp_wrench.hpp contact_frame_to_lds computes the same on the device):
+        n = normal / |normal|,   t1 = (e_x - n_x n) / |e_x - n_x n|,   t2 = n x t1.
+    The columns are t1, t2, n in the world frame, so f_world = R f_local and f_local = R' f_world; (0, 0, 1) gives the identity exactly."""
+    import numpy as np
+    nr = np.asarray(normals, np.float64)
+    if nr.shape[-1:] != (3,):
+        raise ValueError(f"contact_frames: expected (..., 3) normals, got {nr.shape}")
+    n = nr * (1.0 / np.sqrt((nr * nr).sum(-1, keepdims=True)))
+    a = np.stack([1.0 - n[..., 0] * n[..., 0], 0.0 - n[..., 0] * n[..., 1], 0.0 - n[..., 0] * n[..., 2]], -1)
+    t1 = a * (1.0 / np.sqrt((a * a).sum(-1, keepdims=True)))
+    t2 = np.stack([n[..., 1] * t1[..., 2] - n[..., 2] * t1[..., 1], n[..., 2] * t1[..., 0] - n[..., 0] * t1[..., 2],
+                   n[..., 0] * t1[..., 1] - n[..., 1] * t1[..., 0]], -1)
+    return np.stack([t1, t2, n], -1)
 
 
 class Stage(C.Structure):
@@ -191,7 +208,8 @@ def load():
     lib.srbdqp_solve_ragged_f64.restype = C.c_int
     lib.srbdqp_set_schedule_hint.argtypes = [H, C.c_void_p, C.c_int32]
     lib.srbdqp_set_schedule_hint.restype = C.c_int
-    for _fn in (lib.srbdqp_set_robots, lib.srbdqp_set_robots_device, lib.srbdqp_ragged_set_robots, lib.srbdqp_ragged_set_robots_device):
+    for _fn in (lib.srbdqp_set_robots, lib.srbdqp_set_robots_device, lib.srbdqp_ragged_set_robots, lib.srbdqp_ragged_set_robots_device,
+                lib.srbdqp_set_contact_normals, lib.srbdqp_set_contact_normals_device):
         _fn.argtypes = [H, C.c_void_p, C.c_int32]
         _fn.restype = C.c_int
     lib.srbdqp_flush.argtypes = [H, C.c_void_p]

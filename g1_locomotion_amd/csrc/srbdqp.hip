@@ -99,6 +99,11 @@ struct srbdqp_handle {
     size_t robots_len = 0;
     srbdqp_robot* robots_own = nullptr;    // the library's device copy of host records (srbdqp_set_robots)
     size_t robots_cap = 0;
+    // contact normals (srbdqp_set_contact_normals / _device): [normals_len][N][12] doubles the fp64 batch solves read, or null (flat ground under every contact)
+    const double* normals = nullptr;
+    size_t normals_len = 0;                // QPs
+    double* normals_own = nullptr;         // the library's device copy of a host array (srbdqp_set_contact_normals)
+    size_t normals_cap = 0;                // doubles
     // SRBDQP_FLAG_ANY_HORIZON with a horizon that has no instantiation: cfg.horizon stays the live horizon n (every array has the caller's shape for n) and the
     // solves run the general kernel instantiated for live_nstar, the smallest tabulated horizon >= n, in its live-horizon mode (srbdqp_wrench.hpp, MODE = 3)
     int live_nstar = 0;                    // 0: the horizon has its own instantiations
@@ -303,7 +308,7 @@ constexpr int kTileClassMinBatch = 512;
 // does a solve of B QPs on this handle go to the general kernel (srbdqp_wrench.hpp)?  launch() asks this.
 inline bool uses_wrench(const srbdqp_handle* h, const Call& c, int maxs, int B) {
     const int N = h->cfg.horizon;
-    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || h->robots || h->live_nstar) return true;   // (per-QP records, a live horizon: only the general kernel reads them)
+    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || h->robots || h->normals || h->live_nstar) return true;   // (per-QP records, contact normals, a live horizon: only the general kernel reads them)
     // N = 20 single support too, for batches: the general kernel holds 2 workgroups per CU there, the compact one 1
     // (tools/schedule_bench.py, 16,384 QPs: 2.85 M QP/s against 1.95 M; at N = 12 / 16 the compact kernel wins, 7.1 / 4.9 M
     // against 5.7 / 4.2 M)
@@ -647,6 +652,16 @@ struct WrenchTraits {
     static constexpr int wps = by_lds < want ? by_lds : want;
 };
 
+// ... with contact normals (MODE = 4, fp64 batch form): waves per SIMD of the instantiation -- what its LDS (the MODE = 0 layout + the table L) admits and
+// the register budget of the MODE = 0 twin, whichever is lower (DESIGN.md section 13 has the table)
+template <int N>
+struct NormalsTraits {
+    using S = srbdqp::WrenchSmem<N, 8, 5, 0, srbdqp::wrench_kreg64(N, 4), true>;
+    static constexpr int by_lds = (S::lds_wgs * S::NW + 3) / 4 > 0 ? (S::lds_wgs * S::NW + 3) / 4 : 1;
+    static constexpr int want = WrenchTraits<N, double>::want;
+    static constexpr int wps = by_lds < want ? by_lds : want;
+};
+
 template <int N, typename R, typename TIO>
 int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t st) {
     using S = srbdqp::WrenchSmem<N>;
@@ -702,6 +717,25 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
                 static const std::string nm2 = nm + "_rb";
                 h->kname = nm2.c_str();
                 hipLaunchKernelGGL(k2, dim3((unsigned)a.B), dim3(S::BT), lds2, st, a, reinterpret_cast<const double*>(h->robots));
+                HIP_TRY(h, hipGetLastError());
+                return SRBDQP_OK;
+            }
+        }
+        if constexpr (sizeof(R) == 8 && N != 24) {
+            // contact normals (srbdqp_set_contact_normals / _device): the MODE = 4 instantiation, the normals as its second argument -- every launch of a solve (first
+            // pass, restart passes, deferred passes on the tail stream) comes through here with this handle.  (The entry points refuse the staged, fp32 and dump
+            // calls while normals are set, and the setters an N = 24 handle and one with robot records.)  L, the frames' columns, is 288 N more bytes of LDS.
+            if (h->normals) {
+                using SN = srbdqp::WrenchSmem<N, 8, 5, 0, srbdqp::wrench_kreg64(N, 4), true>;
+                constexpr size_t ldsn = SN::bytes;
+                constexpr int WPSN = NormalsTraits<N>::wps;
+                static_assert(ldsn <= 163840 && SN::BT == S::BT, "one QP must fit the LDS of a CU");
+                void (*k4)(KArgs, const double*) = &srbdqp::srbdqp_wrench_cn_kernel<N, WPSN>;
+                int rc4 = set_lds_once(h, k4, ldsn);
+                if (rc4 != SRBDQP_OK) return rc4;
+                static const std::string nm4 = nm + "_cn";
+                h->kname = nm4.c_str();
+                hipLaunchKernelGGL(k4, dim3((unsigned)a.B), dim3(SN::BT), ldsn, st, a, h->normals);
                 HIP_TRY(h, hipGetLastError());
                 return SRBDQP_OK;
             }
@@ -1067,6 +1101,46 @@ int robots_quiesce(srbdqp_handle* h) {
     return SRBDQP_OK;
 }
 
+// ---- contact normals (srbdqp_set_contact_normals) ----
+// the rules of include/srbdqp.h (the same ones the kernel applies to a device array, srbdqp_wrench.hpp contact_frame_to_lds); null = valid, else what is wrong
+const char* normal_fault(const double* n) {
+    if (!std::isfinite(n[0]) || !std::isfinite(n[1]) || !std::isfinite(n[2])) return "every entry must be finite";
+    const double nn = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    if (!(nn >= 0.5 && nn <= 2.0)) return "need 0.5 <= |n| <= 2";
+    if (!(n[2] * (1.0 / nn) >= 0.5)) return "need n_z >= 0.5 |n| (slopes to 60 degrees)";
+    return nullptr;
+}
+
+// a call that cannot read contact normals while they are set on this handle
+int normals_refuse(srbdqp_handle* h, const char* what) {
+    h->err = std::string(what) + ": refused while contact normals are set (srbdqp_set_contact_normals): only the fp64 batch solves on the general kernel read them "
+             "-- srbdqp_set_contact_normals(h, NULL, 0) goes back to flat ground";
+    return SRBDQP_E_INVALID;
+}
+
+// may this handle take normals?  (N = 24: no instantiation of the general kernel without scratch memory, as for robot records; a live horizon or robot records:
+// a combined mode would be another copy of every instantiation)
+int normals_check_handle(srbdqp_handle* h, const char* fn) {
+    if (h->live_nstar) return live_refuse(h, fn);
+    if (h->cfg.horizon > kRobotsMaxHorizon) { h->err = std::string(fn) + ": contact normals: not at N = 24 (no instantiation of the general kernel reads them there, DESIGN.md section 13)"; return SRBDQP_E_INVALID; }
+    if (h->robots) { h->err = std::string(fn) + ": refused while per-QP robot records are set (srbdqp_set_robots): no instantiation reads both (DESIGN.md section 13)"; return SRBDQP_E_INVALID; }
+    return SRBDQP_OK;
+}
+
+// fp64 batch solve of B QPs with normals set: the general kernel, and a block of normals for every QP
+int normals_check_batch(srbdqp_handle* h, int32_t B) {
+    if (!h->normals) return SRBDQP_OK;
+    if (h->cfg.kernel != SRBDQP_KERNEL_AUTO && h->cfg.kernel != SRBDQP_KERNEL_WRENCH) {
+        h->err = "contact normals (srbdqp_set_contact_normals) are read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH while they are set";
+        return SRBDQP_E_INVALID;
+    }
+    if ((size_t)B > h->normals_len) {
+        h->err = "solve of " + std::to_string(B) + " QPs with contact normals for " + std::to_string(h->normals_len) + " set (srbdqp_set_contact_normals): every QP needs its block";
+        return SRBDQP_E_INVALID;
+    }
+    return SRBDQP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1204,6 +1278,7 @@ int srbdqp_destroy(srbdqp_handle* h) {
     }
     if (h->done_count) (void)hipFree(h->done_count);
     if (h->robots_own) (void)hipFree(h->robots_own);
+    if (h->normals_own) (void)hipFree(h->normals_own);
     if (h->stage_host) (void)hipHostFree(h->stage_host);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1234,6 +1309,7 @@ int srbdqp_stage_ptrs(srbdqp_handle* h, srbdqp_stage* out) {
 int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_solve_staged_f64");
+    if (h->normals) return normals_refuse(h, "srbdqp_solve_staged_f64");
     if (B < 0 || B > h->stage_h.capacity) { h->err = "staged batch exceeds the staging capacity"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
     {   // (the kernel of the call before this one published its completion word before it ended)
@@ -1276,6 +1352,7 @@ int srbdqp_update_f64(srbdqp_handle* h, const double* x0, const double* x_ref, c
                       const double* pcom, double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_update_f64");
+    if (h->normals) return normals_refuse(h, "srbdqp_update_f64");
     if (!x0 || !x_ref || !foot || !contact || !u0_out) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
     const size_t N = (size_t)h->cfg.horizon;
     const srbdqp_stage& s = h->stage_h;
@@ -1308,6 +1385,7 @@ KArgs staged_args(srbdqp_handle* h, int32_t B, bool use_pcom, bool want_x, bool 
 int srbdqp_prepare_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_prepare_staged_f64");
+    if (h->normals) return normals_refuse(h, "srbdqp_prepare_staged_f64");
     if (h->live_nstar) return live_refuse(h, "srbdqp_prepare_staged_f64");
     if (B < 0 || B > h->stage_h.capacity) { h->err = "staged batch exceeds the staging capacity"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
@@ -1327,6 +1405,7 @@ int srbdqp_prepare_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom) {
 int srbdqp_solve_prepared_f64(srbdqp_handle* h, int32_t B, int32_t want_x, int32_t want_y) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_solve_prepared_f64");
+    if (h->normals) return normals_refuse(h, "srbdqp_solve_prepared_f64");
     if (h->live_nstar) return live_refuse(h, "srbdqp_solve_prepared_f64");
     if (B <= 0 || B != h->prepared_B) { h->err = "srbdqp_solve_prepared_f64: no set-up of this batch size is pending (srbdqp_prepare_staged_f64)"; return SRBDQP_E_INVALID; }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1354,6 +1433,7 @@ int srbdqp_set_robots(srbdqp_handle* h, const srbdqp_robot* host, int32_t length
     const bool clear = !host || length == 0;
     if (!clear && h->live_nstar) return live_refuse(h, "srbdqp_set_robots");
     if (!clear && h->cfg.horizon > kRobotsMaxHorizon) { h->err = robots_n24; return SRBDQP_E_INVALID; }
+    if (!clear && h->normals) return normals_refuse(h, "srbdqp_set_robots");
     if (!clear) {
         const int rv = robots_validate(host, length, "srbdqp_set_robots", h->err);
         if (rv != SRBDQP_OK) return rv;
@@ -1376,8 +1456,50 @@ int srbdqp_set_robots_device(srbdqp_handle* h, const srbdqp_robot* dev, int32_t 
     const bool clear = !dev || length == 0;
     if (!clear && h->live_nstar) return live_refuse(h, "srbdqp_set_robots_device");
     if (!clear && h->cfg.horizon > kRobotsMaxHorizon) { h->err = robots_n24; return SRBDQP_E_INVALID; }
+    if (!clear && h->normals) return normals_refuse(h, "srbdqp_set_robots_device");
     h->robots = clear ? nullptr : dev;
     h->robots_len = clear ? 0 : (size_t)length;
+    return SRBDQP_OK;
+}
+
+int srbdqp_set_contact_normals(srbdqp_handle* h, const double* host, int32_t length) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (host && length < 0) { h->err = "srbdqp_set_contact_normals: negative length"; return SRBDQP_E_INVALID; }
+    const bool clear = !host || length == 0;
+    const size_t N = (size_t)h->cfg.horizon;
+    if (!clear) {
+        const int rh = normals_check_handle(h, "srbdqp_set_contact_normals");
+        if (rh != SRBDQP_OK) return rh;
+        for (size_t i = 0; i < (size_t)length * N * 4; ++i)
+            if (const char* why = normal_fault(host + 3 * i)) {
+                h->err = "srbdqp_set_contact_normals: the normal of (qp " + std::to_string(i / (4 * N)) + ", step " + std::to_string((i / 4) % N) + ", contact " + std::to_string(i % 4) +
+                         ") is invalid (" + why + "); the previous setting is kept";
+                return SRBDQP_E_INVALID;
+            }
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    int rc = robots_quiesce(h);                     // (deferred passes may still read the array this call replaces)
+    if (rc != SRBDQP_OK) return rc;
+    if (clear) { h->normals = nullptr; h->normals_len = 0; return SRBDQP_OK; }
+    const size_t want = (size_t)length * N * 12;
+    if (want > h->normals_cap) { h->normals = nullptr; h->normals_len = 0; }
+    rc = grow(h, h->normals_own, h->normals_cap, want, nullptr, "hipMalloc contact normals");
+    if (rc != SRBDQP_OK) return rc;
+    HIP_TRY(h, hipMemcpy(h->normals_own, host, sizeof(double) * want, hipMemcpyHostToDevice));
+    h->normals = h->normals_own; h->normals_len = (size_t)length;
+    return SRBDQP_OK;
+}
+
+int srbdqp_set_contact_normals_device(srbdqp_handle* h, const double* dev, int32_t length) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (dev && length < 0) { h->err = "srbdqp_set_contact_normals_device: negative length"; return SRBDQP_E_INVALID; }
+    const bool clear = !dev || length == 0;
+    if (!clear) {
+        const int rh = normals_check_handle(h, "srbdqp_set_contact_normals_device");
+        if (rh != SRBDQP_OK) return rh;
+    }
+    h->normals = clear ? nullptr : dev;
+    h->normals_len = clear ? 0 : (size_t)length;
     return SRBDQP_OK;
 }
 
@@ -1648,6 +1770,8 @@ int srbdqp_solve_batch_device_f64(srbdqp_handle* h, int32_t B, const double* x0,
     if (!h) return SRBDQP_E_INVALID;
     const int rr = robots_check_batch(h, B);
     if (rr != SRBDQP_OK) return rr;
+    const int rn = normals_check_batch(h, B);
+    if (rn != SRBDQP_OK) return rn;
     return solve_device_impl(h, device_call(h, false), B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
 }
 
@@ -1657,6 +1781,7 @@ int srbdqp_solve_batch_device_f32(srbdqp_handle* h, int32_t B, const float* x0, 
                                   float* y_out, int32_t* status, int32_t* iters, void* stream) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_solve_batch_device_f32");
+    if (h->normals) return normals_refuse(h, "srbdqp_solve_batch_device_f32");
     if (h->live_nstar) return live_refuse(h, "srbdqp_solve_batch_device_f32");
     return solve_device_impl(h, device_call(h, true), B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
 }
@@ -1667,6 +1792,8 @@ int srbdqp_solve_batch_f64(srbdqp_handle* h, int32_t B, const double* x0, const 
     if (!h) return SRBDQP_E_INVALID;
     const int rr = robots_check_batch(h, B);
     if (rr != SRBDQP_OK) return rr;
+    const int rn = normals_check_batch(h, B);
+    if (rn != SRBDQP_OK) return rn;
     return solve_host_impl(h, false, B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters);
 }
 
@@ -1675,6 +1802,7 @@ int srbdqp_solve_batch_f32(srbdqp_handle* h, int32_t B, const float* x0, const f
                            float* u_out, float* x_out, float* y_out, int32_t* status, int32_t* iters) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_solve_batch_f32");
+    if (h->normals) return normals_refuse(h, "srbdqp_solve_batch_f32");
     if (h->live_nstar) return live_refuse(h, "srbdqp_solve_batch_f32");
     return solve_host_impl(h, true, B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters);
 }
@@ -1684,6 +1812,7 @@ int srbdqp_assemble_f64(srbdqp_handle* h, int32_t B, const double* x0, const dou
                         double* ub_out) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_assemble_f64");
+    if (h->normals) return normals_refuse(h, "srbdqp_assemble_f64");
     if (h->live_nstar) return live_refuse(h, "srbdqp_assemble_f64");
     if (B < 0 || (B > 0 && (!x0 || !x_ref || !foot || !contact || !P_out || !q_out || !l_out || !ub_out))) { h->err = "null pointer"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
@@ -1760,6 +1889,7 @@ int srbdqp_assemble_wrench_f64(srbdqp_handle* h, int32_t B, const double* x0, co
                                double* goff_out) {
     if (!h) return SRBDQP_E_INVALID;
     if (h->robots) return robots_refuse(h, "srbdqp_assemble_wrench_f64");
+    if (h->normals) return normals_refuse(h, "srbdqp_assemble_wrench_f64");
     if (h->live_nstar) return live_refuse(h, "srbdqp_assemble_wrench_f64");
     if (B < 0 || (B > 0 && (!x0 || !x_ref || !foot || !contact || !T_out || !q_out || !blocks_out || !goff_out))) { h->err = "null pointer"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;

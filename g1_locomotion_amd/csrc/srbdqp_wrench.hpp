@@ -58,7 +58,8 @@ namespace srbdqp {
 //       broadcast reads alone took ~550 of an iteration's ~1950 cycles (tools/wrench_stamps_staged.py, -DSRBDQP_PROFILE_WADMM)
 // KR64 = entries of an fp64 half row longer than 60 that stay in registers (KREG64 below; wrench_kreg64() has the one exception to 56)
 constexpr int wrench_kreg64(int N, int MODE) { return (MODE == 3 && N == 24) ? SRBDQP_LIVE24_KREG : 56; }
-template <int N, int TB = 8, int SPW = 5, int XW = 0, int KR64 = 56>
+// CN  = contact normals (MODE = 4): the table L of the contact frames' columns beside J in the persistent strip
+template <int N, int TB = 8, int SPW = 5, int XW = 0, int KR64 = 56, bool CN = false>
 struct WrenchSmem {
     static_assert(SPW >= 1 && SPW <= 5, "12 lanes per step");
     static constexpr int n = 12 * N, m = 20 * N;
@@ -79,9 +80,10 @@ struct WrenchSmem {
     static constexpr int o_x0 = 0;                        // 13 (+1)
     static constexpr int o_tm = o_x0 + 14;                // 9N   Rz' per step
     static constexpr int o_J = o_tm + up2(N * 9);         // 36N  I_w^-1 [r]x per step
-    static constexpr int o_red = o_J + N * 36;            // 32   reductions / check maxima / vote flags
+    static constexpr int o_L = o_J + N * 36;              // CN: 36N  L_k[b][3 ci + ax] = R_ci[b][ax], the linear part of a local force variable's wrench column
+    static constexpr int o_red = o_L + (CN ? N * 36 : 0); // 32   reductions / check maxima / vote flags
     static constexpr int o_ct = o_red + 32;               // 4N bytes of contact flags
-    static constexpr int o_misc = o_ct + up2((N * 4 + 7) / 8);   // [0] numerical failure
+    static constexpr int o_misc = o_ct + up2((N * 4 + 7) / 8);   // [0] numerical failure, [1] CN: a contact normal that is not one
     static constexpr int o_sq = o_misc + 4;               // 12   sqrt(q_diag)
     static constexpr int o_int = o_sq + 12;               // ints: gsz[N], goff[N + 1], n_g, na, wrench flag[N]
     static constexpr int o_R = o_int + up2((3 * N + 6) / 2 + 1);
@@ -125,7 +127,9 @@ struct WrenchSmem {
     // fp64 iterations with a half row longer than 60 (N = 24): its last KTAIL entries per lane, entry-major [KTAIL][BT] (the tiles
     // are dead by then and their region is far larger)
     static constexpr int KREG64 = KR64;   // entries of the fp64 half row kept in registers when it is longer than 60 (N = 24 mixed gait: 56 -> 1.06 M QP/s with 2 reloads from scratch left in the iteration, 48 -> 1.03 M with none, 40 -> 1.01 M)
-    static constexpr int KTAIL = (TB == 8 && CHMAX > 60) ? CHMAX - KREG64 : ((TB == 8 && CHMAX == 36) ? 12 : 0);   // N = 12: 3 waves per SIMD
+    // (CN at N = 10, half rows of 30: the last 2 -- with all 30 in registers the MODE = 4 instantiation kept 12 bytes per lane in scratch memory at 3 waves per SIMD, two
+    //  of them stored and reloaded in every iteration; 2, 4 and 6 entries in LDS all compile to none)
+    static constexpr int KTAIL = (TB == 8 && CHMAX > 60) ? CHMAX - KREG64 : ((TB == 8 && CHMAX == 36) ? 12 : ((CN && CHMAX == 30) ? 2 : 0));   // N = 12: 3 waves per SIMD
     static constexpr int o_kt = up2(endC);
     static constexpr int o_vl = o_kt + KTAIL * BT;        // VL: row and column of V per lane, entry-major [12][BT]
     static constexpr int endC2 = o_vl + ((TB == 8 && CHMAX <= 36) ? 12 * BT : 0);
@@ -218,6 +222,9 @@ __device__ __forceinline__ double wg_max1(double v, double* red) {
 //             short of the 2e-6 tolerance (0.06 % with the explicit rows);
 //   BDN = 4:  {J[0..2][u], 1 / D_u}: Bd w = D^-1 (w - Y' v) from the step's own v = V w -- the fp64 iterations: 8 registers
 //             instead of 24, 6 multiply-adds instead of 12, and only the lane's half of the step's right-hand sides is read.
+//             With contact normals (MODE = 4; ll is a pointer, not nullptr_t) the linear part of Y'[:, u] is L[:, u] -- column ax of the contact's frame, read from
+//             the persistent strip (ll[0], ll[12], ll[24]) -- instead of the unit vector e_ax: the step's v[3 .. 5] meet it where the flat kernel picks v[3 + ax].
+//             (In registers -- three more doubles beside the T^-1 half row -- the N = 10 instantiation kept 12 bytes per lane in scratch memory.)
 // KREG < CHMAX (fp64 iterations at N = 24): the last CHMAX - KREG entries of the lane's T^-1 half row are read from LDS
 // (ktail[(c - KREG) kts], lane-contiguous per entry) instead of registers -- a 5-wave workgroup puts two waves on one SIMD,
 // so a wave has 256 registers, and the 72-double half row + V + state spilled 8 values per iteration to scratch memory.
@@ -226,15 +233,17 @@ __device__ __forceinline__ double wg_max1(double v, double* red) {
 // WIDE (the low-latency instantiation: one workgroup's worth of registers): every broadcast read of the T^-1 product in flight
 // at once instead of blocks of four (each block was one more LDS round trip in the iteration's chain), and the 6-term
 // products on two accumulators.
-template <typename R, int CHMAX, int KREG = CHMAX, bool VL = false, bool WIDE = false, bool JL = false, typename KT, int BDN, class Hook>
+template <typename R, int CHMAX, int KREG = CHMAX, bool VL = false, bool WIDE = false, bool JL = false, typename KT, int BDN, class Hook, typename LL = std::nullptr_t>
 __device__ __forceinline__ R apply_kinv(R wv, R* wbw, R* tbw, R* vb, int lane, int sg, int ul, bool active_g, int Rrow, int CH,
                                         const KT (&kin)[CHMAX], const R (&vrow_)[6], const R (&vcol_)[6], const R (&bj)[BDN], int vsoff, int vssel,
-                                        Hook&& hook, const R* ktail = nullptr, int kts = 0, const R* vlds = nullptr, const R* vldc = nullptr, const double* jl = nullptr WADMM_PARAMS) {
+                                        Hook&& hook, const R* ktail = nullptr, int kts = 0, const R* vlds = nullptr, const R* vldc = nullptr, const double* jl = nullptr, LL ll = LL() WADMM_PARAMS) {
     auto KIN = [&](int c) -> R { return (c < KREG) ? (R)kin[c] : ktail[(c - KREG) * kts]; };
     R vrow[6], vcol[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) { vrow[i] = VL ? vlds[i * kts] : vrow_[i]; }
     static_assert(BDN == 4 || BDN == 12, "Bd: implicit (4) or explicit row (12)");
+    constexpr bool CN = !std::is_same<LL, std::nullptr_t>::value;
+    static_assert(!CN || BDN == 4, "contact normals: the implicit form");
     typedef R R4 __attribute__((ext_vector_type(4)));
     typedef R R2 __attribute__((ext_vector_type(2)));
     const int h = ul & 1;
@@ -266,11 +275,13 @@ __device__ __forceinline__ R apply_kinv(R wv, R* wbw, R* tbw, R* vb, int lane, i
         // order): no barrier needed.  Y' column of the variable: [J[:, u]; e_ax] on a wrench step, the unit vector of its g
         // row on a force-variable step (where the whole term is w - w = 0).
         const R* vs = vb + vsoff;
+        [[maybe_unused]] R vlin = R(0);
+        if constexpr (CN) vlin = fma((R)ll[0], vs[3], fma((R)ll[12], vs[4], (R)ll[24] * vs[5]));   // (a force-variable step reads three finite entries behind its own and has bj[3] = 0)
         if constexpr (JL) {   // (the iterations of the fp64 N = 12 instantiation: +1.5 %; N = 8: -2 %, N = 10: nothing)
               // ... J[:, u] from the persistent strip (jl[0], jl[12], jl[24]) instead of three more registers: they were reloaded from scratch
-            xb = bj[3] * (wv - fma(jl[0], vs[0], fma(jl[12], vs[1], fma(jl[24], vs[2], vb[vssel]))));   // memory every iteration (a force-variable step has bj[3] = 0: its J does not matter)
+            xb = bj[3] * (wv - fma(jl[0], vs[0], fma(jl[12], vs[1], fma(jl[24], vs[2], CN ? vlin : vb[vssel]))));   // memory every iteration (a force-variable step has bj[3] = 0: its J does not matter)
         } else {
-            xb = bj[3] * (wv - fma(bj[0], vs[0], fma(bj[1], vs[1], fma(bj[2], vs[2], vb[vssel]))));
+            xb = bj[3] * (wv - fma(bj[0], vs[0], fma(bj[1], vs[1], fma(bj[2], vs[2], CN ? vlin : vb[vssel]))));
         }
     } else {
         R wg[12];
@@ -634,14 +645,40 @@ __device__ __forceinline__ void qp_robot_to_lds(const KArgs& a, const double* re
     dst[7] = ok ? 0.0 : 1.0;
 }
 
+// The frame R = [t1 t2 n] of one contact normal (MODE = 4, srbdqp_set_contact_normals; g1_locomotion_amd.contact_frames is the host mirror):
+//     n = nr / |nr|,   t1 = (e_x - n_x n) / |e_x - n_x n|,   t2 = n x t1        (R = I exactly for nr = e_z)
+// into the step's table L, L[12 r + a] = R[r][a] for the contact's columns a = 0 .. 2.  The setters' rules -- every entry finite, 0.5 <= |nr| <= 2, n_z >= 0.5
+// after normalising (slopes to 60 degrees keep t1 well defined); NaN fails every one -- or *bad = 1 and R = I: the QP is reported as SRBDQP_NUMERICAL with zero
+// forces, and nothing computed on the way is non-finite.
+__device__ __forceinline__ void contact_frame_to_lds(const double (&nr)[3], double* L, double* bad) {
+    constexpr double big = 1.0e300;
+    const double nn = sqrt(nr[0] * nr[0] + nr[1] * nr[1] + nr[2] * nr[2]);
+    bool ok = fabs(nr[0]) < big && fabs(nr[1]) < big && fabs(nr[2]) < big && nn >= 0.5 && nn <= 2.0;
+    const double inn = ok ? 1.0 / nn : 1.0;
+    double n0 = nr[0] * inn, n1 = nr[1] * inn, n2 = nr[2] * inn;
+    ok = ok && n2 >= 0.5;
+    if (!ok) { n0 = 0.0; n1 = 0.0; n2 = 1.0; *bad = 1.0; }
+    const double a0 = 1.0 - n0 * n0, a1 = 0.0 - n0 * n1, a2 = 0.0 - n0 * n2;
+    const double ia = 1.0 / sqrt(a0 * a0 + a1 * a1 + a2 * a2);
+    const double t0 = a0 * ia, t1 = a1 * ia, t2 = a2 * ia;
+    L[0] = t0;  L[1] = n1 * t2 - n2 * t1;  L[2] = n0;
+    L[12] = t1; L[13] = n2 * t0 - n0 * t2; L[14] = n1;
+    L[24] = t2; L[25] = n0 * t1 - n1 * t0; L[26] = n2;
+}
+
 // One QP (index b) on one workgroup of NW waves.  TIO = element type of the caller's buffers, R = iteration type.
 // MODE: 0 = solve, 1 = assembly dump (srbdqp_assemble_wrench_f64), 2 = solve with the QP's own robot record robots[8 b .. 8 b + 8) (qp_robot_to_lds) in place
 // of KArgs::inv_mass / iinv / mu / fzmin_s / fzmax_s -- every use below reads (RB ? RBV[k] : a.<value>), so MODE 0 compiles to what it did without it;
 // 3 = solve of a LIVE horizon nl <= N (SRBDQP_FLAG_ANY_HORIZON): the caller's arrays hold nl rows per QP, steps >= nl have no contacts, no error rows and no
-// part in any sum over the horizon, and nothing is stored past row nl -- every such place below reads (LH ? ... : ...) or (!LH || ...), constant in the other modes.
+// part in any sum over the horizon, and nothing is stored past row nl -- every such place below reads (LH ? ... : ...) or (!LH || ...), constant in the other modes;
+// 4 = solve with contact normals normals[12 N b .. 12 N (b + 1)) (srbdqp_set_contact_normals: one per step and contact, world frame): the QP in the LOCAL force
+// variables f_loc = R' f of every contact's frame R = [t1 t2 n] (contact_frame_to_lds).  The cone rows, D = diag(d_xy, d_xy, d_z), the projection and the whole
+// iteration are the flat ones in those variables; what changes is the wrench column of variable (i, ax), [I_w^-1 (r x R[:, ax]); R[:, ax]] instead of
+// [J[:, u]; e_ax]: J holds the first part, the table L beside it the second, and every place that used e_ax reads (CN ? <L> : <today's expression>).  warm_u
+// comes in and u_out goes out in the world frame.
 template <int N, typename R, typename TIO, int MODE, typename TT = double, int SPW = 5, int XW = 0>
-__device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* sm, const double* robots = nullptr, const int nl = N) {
-    using S = WrenchSmem<N, (int)sizeof(TT), SPW, XW, wrench_kreg64(N, MODE)>;
+__device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* sm, const double* robots = nullptr, const int nl = N, const double* normals = nullptr) {
+    using S = WrenchSmem<N, (int)sizeof(TT), SPW, XW, wrench_kreg64(N, MODE), MODE == 4>;
     typedef TT v4t __attribute__((ext_vector_type(4)));
     static_assert(sizeof(TT) == 8 || (sizeof(R) == 4 && MODE == 0), "fp32 tiles belong to the fp32 path");
     constexpr int n = S::n, m = S::m, NW = S::NW, NWS = S::NWS, BT = S::BT, LT = S::LT, TS = S::TS, CHMAX = S::CHMAX;
@@ -655,6 +692,9 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     const int NL = LH ? nl : N;                                      // the live horizon (wave-uniform: a kernel argument)
     static_assert(!RB || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && XW == 0), "per-QP robot records: the fp64 batch instantiation");
     [[maybe_unused]] const double* const RBV = sm + S::o_end;        // MODE 2: the QP's robot (qp_robot_to_lds), from the first barrier on
+    constexpr bool CN = MODE == 4;
+    static_assert(!CN || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && XW == 0), "contact normals: the fp64 batch instantiation");
+    [[maybe_unused]] const double* const LT_ = sm + S::o_L;          // MODE 4: L of every step, from the second barrier on
     const int t = threadIdx.x, lane = t & 63;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     constexpr bool CSUM = XW > 0 && sizeof(TIO) == 8 && MODE == 0 && S::LT <= 256;   // the low-latency instantiations: the completion word may carry a checksum (KArgs::done_cs)
@@ -688,6 +728,11 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         const uint8_t v_ct = gct[t < NL * 4 ? t : 0];
         const TIO v_pc = gpc[(a.pcom && t < NL * 3) ? t : 0];
         TIO v_xr[RX], v_ft[RF];
+        [[maybe_unused]] double v_nr[3] = {0.0, 0.0, 1.0};           // CN: the normal of contact t % 4 of step t / 4
+        if constexpr (CN) {
+            const double* gn = normals + (size_t)b * (N * 12) + 3 * (t < N * 4 ? t : 0);
+            v_nr[0] = gn[0]; v_nr[1] = gn[1]; v_nr[2] = gn[2];
+        }
 #pragma unroll
         for (int r = 0; r < RX; ++r) { const int i = t + r * BT; v_xr[r] = gxr[i < NL * 13 ? i : 0]; }
 #pragma unroll
@@ -704,6 +749,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         if constexpr (RB) { if (t == 0) qp_robot_to_lds(a, robots + (size_t)b * 8, sm + S::o_end); }
         __syncthreads();
         if (!a.pcom && t < N * 3) sm[S::o_pcom + t] = sm[S::o_xref + (t / 3) * 13 + 3 + (t % 3)];
+        if constexpr (CN) { if (t < N * 4) contact_frame_to_lds(v_nr, sm + S::o_L + (t >> 2) * 36 + 3 * (t & 3), sm + S::o_misc + 1); }
         if (t < N) {
             double sn, cs;
             sincos(sm[S::o_xref + t * 13 + 2], &sn, &cs);
@@ -749,9 +795,12 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             const double rz = sm[S::o_foot + k * 12 + 3 * ci + 2] - sm[S::o_pcom + k * 3 + 2];
             // column ax of skew(r), as selects: hipcc (ROCm 7.2) lowers the three-way if / else-if / else on this 16-bit
             // value as a switch and loses the "s1 = -rx" of the last arm for some instantiations (seen in the ISA at N = 12)
-            const double s0 = (ax == 0) ? 0.0 : ((ax == 1) ? -rz : ry);
-            const double s1 = (ax == 0) ? rz : ((ax == 1) ? 0.0 : -rx);
-            const double s2 = (ax == 0) ? -ry : ((ax == 1) ? rx : 0.0);
+            // (CN: column ax of skew(r) R = r x R[:, ax])
+            [[maybe_unused]] const double* Lc = sm + S::o_L + k * 36 + cc;
+            [[maybe_unused]] const double e0 = CN ? Lc[0] : 0.0, e1 = CN ? Lc[12] : 0.0, e2 = CN ? Lc[24] : 0.0;
+            const double s0 = CN ? ry * e2 - rz * e1 : ((ax == 0) ? 0.0 : ((ax == 1) ? -rz : ry));
+            const double s1 = CN ? rz * e0 - rx * e2 : ((ax == 0) ? rz : ((ax == 1) ? 0.0 : -rx));
+            const double s2 = CN ? rx * e1 - ry * e0 : ((ax == 0) ? -ry : ((ax == 1) ? rx : 0.0));
             double* J = sm + S::o_J + k * 36;
             J[0 * 12 + cc] = w00 * s0 + w01 * s1;
             J[1 * 12 + cc] = w01 * s0 + w11 * s1;
@@ -787,10 +836,11 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     if constexpr (MODE == 1) { if (na == 0) return; }   // assembly dump of an empty problem: all zeros (the host cleared the buffers)
     [[maybe_unused]] bool rb_bad = false;
     if constexpr (RB) rb_bad = unis(RBV[7]) != 0.0;
-    if (na == 0 || (RB && rb_bad)) {   // nothing to solve: all forces 0 (MODE 2, a record that is not a robot: the same, reported as SRBDQP_NUMERICAL)
+    if constexpr (CN) rb_bad = unis(sm[S::o_misc + 1]) != 0.0;      // (MODE 4: a normal that is not one, the same way)
+    if (na == 0 || ((RB || CN) && rb_bad)) {   // nothing to solve: all forces 0 (MODE 2, a record that is not a robot: the same, reported as SRBDQP_NUMERICAL)
         for (int c = t; c < n; c += BT) sm[S::o_xs + c] = 0.0;
         if (a.y_out) for (int i = t; i < (LH ? 20 * NL : m); i += BT) reinterpret_cast<TIO*>(a.y_out)[row0 * 20 + i] = TIO(0);
-        if (t == 0) { const int st0 = (RB && rb_bad) ? -1 : 1; if (a.status) a.status[b] = st0; if (a.iters) a.iters[b] = 0; cs_host = done_cs_pack(st0, 0); }
+        if (t == 0) { const int st0 = ((RB || CN) && rb_bad) ? -1 : 1; if (a.status) a.status[b] = st0; if (a.iters) a.iters[b] = 0; cs_host = done_cs_pack(st0, 0); }
         __syncthreads();
     } else {
 
@@ -901,6 +951,13 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         if constexpr (sizeof(TT) == 4) asm volatile("" : "+v"(axl), "+v"(ull));
         const double* J = sm + S::o_J + js * 36 + ull;
         const double* g = GV + 9 * js;
+        if constexpr (CN) {   // the linear part against L[:, u] instead of e_ax
+            const double* Lu = LT_ + js * 36 + ull;
+            double lin = 0.0;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) lin = fma(Lu[12 * r], SQ[3 + r] * dt2m * g[3 + r] + SQ[9 + r] * dtm * g[6 + r], lin);
+            return a.s * (J[0] * g[0] + J[12] * g[1] + J[24] * g[2] + lin);
+        }
         return a.s * (J[0] * g[0] + J[12] * g[1] + J[24] * g[2] + SQ[3 + axl] * dt2m * g[3 + axl] + SQ[9 + axl] * dtm * g[6 + axl]);
     };
     if constexpr (TSPLIT) {
@@ -967,6 +1024,9 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             if (comp < 3) {
                 const double* J = sm + S::o_J + j * 36 + comp * 12;
                 for (int c = 0; c < 12; ++c) acc += J[c] * x[c];
+            } else if constexpr (CN) {
+                const double* Lr = LT_ + j * 36 + (comp - 3) * 12;
+                for (int c = 0; c < 12; ++c) acc += Lr[c] * x[c];
             } else {
                 acc = x[comp - 3] + x[comp] + x[comp + 3] + x[comp + 6];
             }
@@ -990,6 +1050,11 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     auto gradient_and_warm_start = [&]() __attribute__((always_inline)) {
         qv = active_u ? gt_eval_u() : 0.0;
         if (!WARM_LATE && a.warm_u) {   // P x^0 = G'(G x^0) + R s^2 x^0
+            if constexpr (CN) {   // world -> local: R' f of the lane's contact
+                const double* Lu = LT_ + js * 36 + ul;
+                const TIO* fw = gwu + 12 * js + 3 * ci;
+                x_init = active_u ? (Lu[0] * (double)fw[0] + Lu[12] * (double)fw[1] + Lu[24] * (double)fw[2]) / a.s : 0.0;
+            } else
             x_init = active_u ? (double)gwu[uvar] / a.s : 0.0;
             if (stepok) sm[S::o_x0c + uvar] = x_init;
             __syncthreads();
@@ -1043,7 +1108,8 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
 #pragma unroll
         for (int u2 = 0; u2 < 12; ++u2) {
             const double wgt2 = fl[u2 / 3] ? (((u2 % 3) < 2) ? idxy : idz) : 0.0;
-            const double dotv = yv[0] * Jj[u2] + yv[1] * Jj[12 + u2] + yv[2] * Jj[24 + u2] + yv[3 + (u2 % 3)];
+            const double* Lj = LT_ + js * 36;
+            const double dotv = yv[0] * Jj[u2] + yv[1] * Jj[12 + u2] + yv[2] * Jj[24 + u2] + (CN ? yv[3] * Lj[u2] + yv[4] * Lj[12 + u2] + yv[5] * Lj[24 + u2] : yv[3 + (u2 % 3)]);
             bdrow[u2] = (BS)(((u2 == ul) ? wu : 0.0) - wu * wgt2 * dotv);
         }
     };
@@ -1059,7 +1125,8 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             const int u2 = 6 * h + i;
             const int flc = (u2 / 3 == 0) ? fl[0] : (u2 / 3 == 1) ? fl[1] : (u2 / 3 == 2) ? fl[2] : fl[3];
             const double wgt = flc ? (((i % 3) < 2) ? idxy : idz) : 0.0;
-            vrow[i] = (VS)(wgt * (er[0] * Jj[u2] + er[1] * Jj[12 + u2] + er[2] * Jj[24 + u2] + er[3 + (i % 3)]));
+            const double* Lj = LT_ + js * 36;
+            vrow[i] = (VS)(wgt * (er[0] * Jj[u2] + er[1] * Jj[12 + u2] + er[2] * Jj[24 + u2] + (CN ? er[3] * Lj[u2] + er[4] * Lj[12 + u2] + er[5] * Lj[24 + u2] : er[3 + (i % 3)])));
         }
         const double wu = active_u ? ((ax < 2) ? idxy : idz) : 0.0;
         const double j0 = Jj[ul], j1 = Jj[12 + ul], j2 = Jj[24 + ul];
@@ -1102,12 +1169,20 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     const double wgt = fl[c] ? ((a2 < 2) ? idxy : idz) : 0.0;
                     const double j0 = Jj[u2], j1 = Jj[12 + u2], j2 = Jj[24 + u2];
                     const double jw[3] = {j0 * wgt, j1 * wgt, j2 * wgt};
+                    [[maybe_unused]] const double* Lu = LT_ + js * 36 + u2;
+                    [[maybe_unused]] const double lv[3] = {CN ? Lu[0] : 0.0, CN ? Lu[12] : 0.0, CN ? Lu[24] : 0.0};
 #pragma unroll
                     for (int p = 0; p < 3; ++p) {
                         Em[p][0] = fma(jw[p], j0, Em[p][0]); Em[p][1] = fma(jw[p], j1, Em[p][1]); Em[p][2] = fma(jw[p], j2, Em[p][2]);
+                        if constexpr (CN) {   // the cross block against L[:, u2], the force block G = sum_c R_c D^-1 R_c' (its upper triangle): no selections
+#pragma unroll
+                            for (int q = 0; q < 3; ++q) Em[p][3 + q] = fma(jw[p], lv[q], Em[p][3 + q]);
+#pragma unroll
+                            for (int q = p; q < 3; ++q) Em[3 + p][3 + q] = fma(wgt * lv[p], lv[q], Em[3 + p][3 + q]);
+                        } else
                         Em[p][3 + a2] += jw[p];
                     }
-                    Em[3 + a2][3 + a2] += wgt;
+                    if constexpr (!CN) Em[3 + a2][3 + a2] += wgt;
                 }
             }
 #pragma unroll
@@ -1117,7 +1192,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             // (the J entries are read again below rather than kept: 36 doubles per lane across this phase were spilled)
             asm volatile("" ::: "memory");
             ESTAMP(a, 1);
-            // E^-1 through its structure (round 5): E = [A B; B' G] with G = S D^-1 S' DIAGONAL (S = [I I I I]: the force rows of W), so
+            // E^-1 through its structure (round 5): E = [A B; B' G] with G = S D^-1 S' DIAGONAL (S = [I I I I]: the force rows of W; CN: S = [R_0 R_1 R_2 R_3], G full), so
             //     E^-1 = [ Sc^-1, -Sc^-1 B G^-1 ; sym, G^-1 + G^-1 B' Sc^-1 B G^-1 ],   Sc = A - B G^-1 B'   (3 x 3, SPD)
             // -- a 3 x 3 Cholesky and three reciprocals instead of the 6 x 6 Cholesky + triangular inverse + L^-T L^-1 every lane of the step ran redundantly
             // (three dependent rsqrt chains instead of six, ~120 instead of ~270 fp64 instructions: 7.8 k -> cycles of the batch-1 set-up were this block).
@@ -1127,11 +1202,30 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                 // G = n_c diag(1 / d_xy, 1 / d_xy, 1 / d_z) with n_c = 3 or 4 stance contacts (a wrench step): its inverse without a division
                 const double inc = ((f0 + f1 + f2 + f3) == 4) ? 0.25 : (1.0 / 3.0);
                 const double ig[3] = {dxy * inc, dxy * inc, dz * inc};
+                // CN: G = sum_c R_c D^-1 R_c' is a full SPD 3 x 3 (the frames differ from contact to contact): a second 3 x 3 Cholesky, as the one of Sc below
+                [[maybe_unused]] double Gi[3][3];
+                if constexpr (CN) {
+                    const double g00 = Em[3][3], g01 = Em[3][4], g02 = Em[3][5], g11 = Em[4][4], g12 = Em[4][5], g22 = Em[5][5];   // (the upper triangle: what the assembly formed)
+                    okE = okE && (g00 > 0.0);
+                    const double r0 = 1.0 / sqrt(g00);
+                    const double l10 = g01 * r0, l20 = g02 * r0;
+                    const double d1 = fma(-l10, l10, g11);
+                    okE = okE && (d1 > 0.0);
+                    const double r1 = 1.0 / sqrt(d1);
+                    const double l21 = fma(-l20, l10, g12) * r1;
+                    const double d2 = fma(-l21, l21, fma(-l20, l20, g22));
+                    okE = okE && (d2 > 0.0);
+                    const double r2 = 1.0 / sqrt(d2);
+                    const double m10 = -l10 * r0 * r1, m21 = -l21 * r1 * r2, m20 = -(l20 * r0 + l21 * m10) * r2;
+                    Gi[0][0] = fma(r0, r0, fma(m10, m10, m20 * m20)); Gi[0][1] = fma(m10, r1, m20 * m21); Gi[0][2] = m20 * r2;
+                    Gi[1][1] = fma(r1, r1, m21 * m21); Gi[1][2] = m21 * r2; Gi[2][2] = r2 * r2;
+                    Gi[1][0] = Gi[0][1]; Gi[2][0] = Gi[0][2]; Gi[2][1] = Gi[1][2];
+                }
                 double BG[3][3];                                         // B G^-1
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
 #pragma unroll
-                    for (int q = 0; q < 3; ++q) BG[p][q] = Em[p][3 + q] * ig[q];
+                    for (int q = 0; q < 3; ++q) BG[p][q] = CN ? Em[p][3] * Gi[0][q] + Em[p][4] * Gi[1][q] + Em[p][5] * Gi[2][q] : Em[p][3 + q] * ig[q];
                 double Sc[3][3];
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
@@ -1177,7 +1271,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                 for (int p = 0; p < 3; ++p)
 #pragma unroll
                     for (int q = p; q < 3; ++q) {
-                        double v = (p == q) ? ig[p] : 0.0;                 // G^-1 - (B G^-1)' C12
+                        double v = CN ? Gi[p][q] : ((p == q) ? ig[p] : 0.0);   // G^-1 - (B G^-1)' C12
 #pragma unroll
                         for (int k2 = 0; k2 < 3; ++k2) v = fma(-BG[k2][p], C12[k2][q], v);
                         Ei[3 + p][3 + q] = v; Ei[3 + q][3 + p] = v;
@@ -1215,7 +1309,10 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
 #pragma unroll
                 for (int c = 0; c < 6; ++c) er[c] = EI[6 * rl + c];
 #pragma unroll
-                for (int r = 0; r < 6; ++r) yv[r] = Ei[r][0] * j0 + Ei[r][1] * j1 + Ei[r][2] * j2 + EI[6 * r + 3 + ax];
+                for (int r = 0; r < 6; ++r) {
+                    if constexpr (CN) { const double* Lu = LT_ + js * 36 + ul; yv[r] = Ei[r][0] * j0 + Ei[r][1] * j1 + Ei[r][2] * j2 + EI[6 * r + 3] * Lu[0] + EI[6 * r + 4] * Lu[12] + EI[6 * r + 5] * Lu[24]; }
+                    else yv[r] = Ei[r][0] * j0 + Ei[r][1] * j1 + Ei[r][2] * j2 + EI[6 * r + 3 + ax];
+                }
                 form_vbd(er, yv);
             }
             ESTAMP(a, 3);
@@ -1228,7 +1325,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
                     EI[6 * rl + 3 * h + i] = (3 * h + i == rl) ? dd : 0.0;
-                    ZT[6 * Rrow + 3 * h + i] = h ? (((rl % 3) == i) ? 1.0 : 0.0) : Jj[12 * i + ug];
+                    ZT[6 * Rrow + 3 * h + i] = h ? (CN ? LT_[js * 36 + 12 * i + ug] : (((rl % 3) == i) ? 1.0 : 0.0)) : Jj[12 * i + ug];
                 }
             }
         }
@@ -1349,6 +1446,15 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                 const double al = (double)(((Ls - 1) * Ls * (2 * Ls - 1)) / 6), be = (double)(((Ls - 1) * Ls) / 2);
                 const double fa = SQ[3 + cm3] * SQ[3 + cm3] * dt4m2, fb = SQ[9 + cm3] * SQ[9 + cm3] * dt2m2;
                 const double f0 = gc * (fa * (al + (double)mm * be) + fb * (double)Ls), f1 = gc * fa * be;
+                // CN: the linear part of a force-variable step's coordinate is a column of its contact frame, not a unit vector: all three axes of z_lin meet
+                [[maybe_unused]] double F0v[3], F1v[3];
+                if constexpr (CN) {
+#pragma unroll
+                    for (int ab = 0; ab < 3; ++ab) {
+                        const double cl = s2 * ZT[6 * cc + 3 + ab], fa_ = SQ[3 + ab] * SQ[3 + ab] * dt4m2, fb_ = SQ[9 + ab] * SQ[9 + ab] * dt2m2;
+                        F0v[ab] = cl * (fa_ * (al + (double)mm * be) + fb_ * (double)Ls); F1v[ab] = cl * fa_ * be;
+                    }
+                }
                 const double* EI = sm + S::o_ei + l2;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -1360,6 +1466,10 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     v = fma(a01[1], Bv[1], v); v = fma(a23[0], Bv[2], v); v = fma(a23[1], Bv[3], v); v = fma(a45[0], Bv[4], v); v = fma(a45[1], Bv[5], v);
                     const double ft = a67[0] * fma(-(double)cj, f1, f0);
                     const int d = r + 3 * 1024 - c, dm3 = d - 3 * ((d * 0xAAAB) >> 17);
+                    if constexpr (CN) {
+                        const double* zr = ZT + 6 * (r < n_g ? r : 0) + 3;
+                        v += zr[0] * fma(-(double)cj, F1v[0], F0v[0]) + zr[1] * fma(-(double)cj, F1v[1], F0v[1]) + zr[2] * fma(-(double)cj, F1v[2], F0v[2]);
+                    } else
                     v += (dm3 == 0) ? ft : 0.0;                                   // same axis
                     const bool same_step = cj == mm;
                     const double ei = EI[same_step ? ce : 0];
@@ -1618,7 +1728,10 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             for (int c = 0; c < 6; ++c) er[c] = tri(rl, c);
         }
 #pragma unroll
-        for (int r = 0; r < 6; ++r) yv[r] = tri(r, 0) * j0 + tri(r, 1) * j1 + tri(r, 2) * j2 + tri(r, 3 + ax);
+        for (int r = 0; r < 6; ++r) {
+            if constexpr (CN) { const double* Lu = LT_ + js * 36 + ul; yv[r] = tri(r, 0) * j0 + tri(r, 1) * j1 + tri(r, 2) * j2 + tri(r, 3) * Lu[0] + tri(r, 4) * Lu[12] + tri(r, 5) * Lu[24]; }
+            else yv[r] = tri(r, 0) * j0 + tri(r, 1) * j1 + tri(r, 2) * j2 + tri(r, 3 + ax);
+        }
     };
     auto late_vbd = [&]() __attribute__((always_inline)) {   // rows / columns of V and Bd now that the accumulator tiles are gone (see phase E)
         if (wrench) {
@@ -1666,6 +1779,8 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         }
     }
     const int vssel = vsoff + bsel;
+    typename std::conditional<CN, const double*, std::nullptr_t>::type llds = nullptr;   // CN: L[:, u] of the lane's variable (apply_kinv)
+    if constexpr (CN) llds = LT_ + js * 36 + ul;
     constexpr int KREG = (sizeof(R) == 8 && S::KTAIL > 0) ? CHMAX - S::KTAIL : CHMAX;
     [[maybe_unused]] const R* ktail = nullptr;
     if constexpr (KREG < CHMAX) {
@@ -1695,6 +1810,8 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
 #pragma unroll
                 for (int i = 0; i < 12; ++i) bdd[i] = (double)bdrow[i];
                 xq = apply_kinv<double, CHMAX>(-qv, wbw, tbw, vb, lane, sg, ul, active_g, Rrow, CH, kin64, vrd, vcd, bdd, vsoff, vssel, [] {});
+            } else if constexpr (CN) {   // (L[:, u] behind the defaults; ktail / LT unused where the whole half row is in registers)
+                xq = apply_kinv<double, CHMAX, KREG>(-qv, wbw, tbw, vb, lane, sg, ul, active_g, Rrow, CH, kin64, vrd, vcd, bjv, vsoff, vssel, [] {}, ktail, LT, nullptr, nullptr, nullptr, llds);
             } else if constexpr (KREG < CHMAX) {
                 xq = apply_kinv<double, CHMAX, KREG>(-qv, wbw, tbw, vb, lane, sg, ul, active_g, Rrow, CH, kin64, vrd, vcd, bjv, vsoff, vssel, [] {}, ktail, LT);
             } else {
@@ -1837,7 +1954,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     for (int q = 0; q < NWS; ++q) vsum |= vflag[q];
                     vote_ok = (vsum == 0);
                 }
-            }, ktail, LT, vlds, nullptr, jlds WADMM_ARGS);
+            }, ktail, LT, vlds, nullptr, jlds, llds WADMM_ARGS);
             WADMM_T(4);
             if (done || k > a.max_iter) break;
             const bool check = ((ph == 0) && vote_ok) || (k == a.max_iter);
@@ -1959,13 +2076,20 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         const size_t row0 = a.row_off ? (size_t)a.row_off[b] : (size_t)b * NL;
         TIO* uo = reinterpret_cast<TIO*>(a.u_out) + row0 * 12;
         ESTAMP(a, 4);
+        // CN: u_hat holds the local forces; entry c of the world-frame plan is row c % 3 of its contact's frame against the contact's three lanes
+        [[maybe_unused]] auto u_world = [&](const int c) -> double {
+            const int k = c / 12, c12 = c - 12 * k, cw = c12 / 3, aw = c12 - 3 * cw;
+            const double* Lr = LT_ + 36 * k + 12 * aw + 3 * cw;
+            const double* uk = uh + 12 * k + 3 * cw;
+            return Lr[0] * uk[0] + Lr[1] * uk[1] + Lr[2] * uk[2];
+        };
         for (int c = t; c < (LH ? 12 * NL : n); c += LT) {
-            const TIO v = (TIO)(a.s * uh[c]);
+            const TIO v = (TIO)(a.s * (CN ? u_world(c) : uh[c]));
             uo[c] = v;
             if constexpr (CSUM) cs_host ^= (unsigned long long)__double_as_longlong((double)v);
         }
         ESTAMP(a, 5);
-        if constexpr (sizeof(TIO) == 8) { if (a.u_dev) for (int c = t; c < (LH ? 12 * NL : n); c += LT) a.u_dev[row0 * 12 + c] = a.s * uh[c]; }
+        if constexpr (sizeof(TIO) == 8) { if (a.u_dev) for (int c = t; c < (LH ? 12 * NL : n); c += LT) a.u_dev[row0 * 12 + c] = a.s * (CN ? u_world(c) : uh[c]); }
         // (the completion word's address and value in scalar registers now: left to the end, their loads from the argument segment are two more round trips)
         int32_t* dflag = a.done_flag;
         int32_t dval = a.done_value, dcs = a.done_cs;
@@ -1986,6 +2110,11 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     const double* J = sm + S::o_J + j * 36 + comp * 12;
                     s = 0.0;
                     for (int c = 0; c < 12; ++c) s += J[c] * u[c];
+                } else if constexpr (CN) {
+                    const double* Lr = LT_ + j * 36 + (comp - 3) * 12;
+                    s = 0.0;
+                    for (int c = 0; c < 12; ++c) s += Lr[c] * u[c];
+                    s *= a.inv_mass;
                 } else {
                     const int ax2 = comp - 3;
                     s = (u[ax2] + u[3 + ax2] + u[6 + ax2] + u[9 + ax2]) * (RB ? RBV[0] : a.inv_mass);
@@ -2116,6 +2245,25 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, SPW, XW>::BT), WPS) void srbdqp_w
     }
     if ((!a.count_ptr || (int)blockIdx.x < *a.count_ptr) && !SRBDQP_RESTART_SKIP(a, SRBDQP_QP_INDEX(a)))
         wrench_qp<N, R, TIO, MODE, TT, SPW, XW>(a, SRBDQP_QP_INDEX(a), sm, nullptr, nl);
+    signal_done(a);
+}
+
+// ... MODE = 4: contact normals (srbdqp_set_contact_normals / _device): normals = the handle's array, 12 N doubles per QP in the CALLER's QP order, as the second
+// kernel argument for the same reasons.  fp64, batch form only, so the kernel has a name of its own with two template arguments.  (The prologue word for word, as above.)
+template <int N, int WPS>
+__global__ __launch_bounds__((WrenchSmem<N, 8, 5, 0>::BT), WPS) void srbdqp_wrench_cn_kernel(KArgs a, const double* __restrict__ normals) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    if ((int)blockIdx.x >= a.B) return;
+    if (a.tile_sel) {
+        const uint32_t* cf = reinterpret_cast<const uint32_t*>(a.contact + (size_t)SRBDQP_QP_INDEX(a) * (N * 4));   // 4 flags per step
+        const int lane = threadIdx.x & 63;
+        const uint32_t v = cf[lane < N ? lane : 0];
+        const int nc = ((v & 0xffu) ? 1 : 0) + ((v & 0xff00u) ? 1 : 0) + ((v & 0xff0000u) ? 1 : 0) + ((v & 0xff000000u) ? 1 : 0);
+        const bool wrench_only = __ballot(lane < N && (nc == 1 || nc == 2)) == 0ull;
+        if (wrench_only != (a.tile_sel == 1)) return;
+    }
+    if ((!a.count_ptr || (int)blockIdx.x < *a.count_ptr) && !SRBDQP_RESTART_SKIP(a, SRBDQP_QP_INDEX(a)))
+        wrench_qp<N, double, double, 4, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm, nullptr, N, normals);
     signal_done(a);
 }
 

@@ -25,7 +25,7 @@ try:                                    # CPython binding of the two batch-1 cal
     from . import _fastcall
 except ImportError:                     # pragma: no cover
     _fastcall = None
-from ._lib import NX, NU, NC, SrbdqpError, robots_array  # noqa: F401  (robots_array: the rows of set_robots)
+from ._lib import NX, NU, NC, SrbdqpError, robots_array, contact_frames  # noqa: F401  (robots_array: the rows of set_robots; contact_frames: set_contact_normals' convention)
 
 
 def _ptr(a: Optional[np.ndarray]):
@@ -55,6 +55,28 @@ def _robots_arg(robots):
     arr = np.asarray(robots)
     if arr.ndim != 2 or arr.shape[1] != _lib.ROBOT_DOUBLES:
         raise ValueError(f"set_robots: expected shape (L, {_lib.ROBOT_DOUBLES}) (robots_array()), got {arr.shape}")
+    arr = np.ascontiguousarray(arr, dtype=np.float64)
+    return (_ptr(arr) if arr.shape[0] else None), int(arr.shape[0]), arr, False
+
+
+def _normals_arg(normals, N):
+    """set_contact_normals' argument -> (address or None, length, object to keep alive or None, is_device).  A NumPy array (L, N, 12) or (L, N, 4, 3) float64
+    goes to the host setter (checked and copied), a CUDA float64 torch tensor of either shape to the device setter (read at every solve: the engine holds a
+    reference to it), None clears."""
+    if normals is None:
+        return None, 0, None, False
+    if hasattr(normals, "data_ptr") and hasattr(normals, "is_cuda"):
+        import torch
+        shp = tuple(normals.shape)
+        if not normals.is_cuda or normals.dtype != torch.float64 or shp[1:] not in ((N, NU), (N, NC, 3)):
+            raise ValueError(f"set_contact_normals: a torch tensor must be CUDA float64 of shape (L, {N}, 12) or (L, {N}, 4, 3), got {normals.dtype} {shp} "
+                             f"on {normals.device}")
+        if not normals.is_contiguous():
+            raise ValueError("set_contact_normals: the tensor must be contiguous (it is read in place)")
+        return (C.c_void_p(normals.data_ptr()) if shp[0] else None), int(shp[0]), normals, True
+    arr = np.asarray(normals)
+    if arr.shape[1:] not in ((N, NU), (N, NC, 3)):
+        raise ValueError(f"set_contact_normals: expected shape (L, {N}, 12) or (L, {N}, 4, 3), got {arr.shape}")
     arr = np.ascontiguousarray(arr, dtype=np.float64)
     return (_ptr(arr) if arr.shape[0] else None), int(arr.shape[0]), arr, False
 
@@ -127,9 +149,17 @@ class BatchMPC:
 
     # -- host-buffer API -------------------------------------------------------------------------------
     def solve(self, x0, x_ref, foot, contact, pcom=None, warm_u=None, warm_y=None, want_x=True, want_y=False,
-              dtype=np.float64):
+              dtype=np.float64, normals=None):
         """Solve B QPs.  Returns dict(u (B,N,12) [N], x (B,N+1,13), y (B,20N), status (B,), iters (B,)).
-        dtype=np.float32 goes through srbdqp_solve_batch_f32: fp32 buffers and fp32 ADMM iterations (fp64 set-up)."""
+        dtype=np.float32 goes through srbdqp_solve_batch_f32: fp32 buffers and fp32 ADMM iterations (fp64 set-up).
+        normals: contact normals for this call alone (set_contact_normals' argument); the engine's previous setting is restored afterwards."""
+        if normals is not None:
+            prev = getattr(self, "_normals_set", None)
+            self.set_contact_normals(normals)
+            try:
+                return self.solve(x0, x_ref, foot, contact, pcom, warm_u, warm_y, want_x, want_y, dtype)
+            finally:
+                self.set_contact_normals(prev)
         N, n, m = self.N, self.n, self.m
         dt = np.dtype(dtype)
         if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
@@ -217,6 +247,17 @@ class BatchMPC:
         fn = self._lib.srbdqp_set_robots_device if dev else self._lib.srbdqp_set_robots
         _lib.check(fn(self._h, ptr, n), self._h)
         self._robots = keep if dev else None
+
+    def set_contact_normals(self, normals):
+        """Friction pyramids on sloped ground (include/srbdqp.h srbdqp_set_contact_normals): normals (L, N, 12) or (L, N, 4, 3), the world-frame surface normal
+        under contact i of step k of QP b -- a NumPy array (checked and copied by the library), a CUDA float64 torch tensor (kept and read at every solve: leave
+        it untouched until those solves have completed), or None (flat ground again).  While set, the five cone rows of a contact act on R' f with R =
+        contact_frames(normal); forces, states and duals keep their frames and units; the fp64 solves run on the general kernel (wrench_f64_n<N>_cn), and
+        the fp32, staged and assembly calls raise SrbdqpError."""
+        ptr, n, keep, dev = _normals_arg(normals, self.N)
+        fn = self._lib.srbdqp_set_contact_normals_device if dev else self._lib.srbdqp_set_contact_normals
+        _lib.check(fn(self._h, ptr, n), self._h)
+        self._normals_set = keep if n else None      # (what solve(normals=) restores; a device tensor stays referenced while the library reads it)
 
     def flush(self, stream=0):
         """FLAG_DEFER_TAIL: enqueue the continuations no later solve has picked up (srbdqp_flush); stream = a hipStream_t address, 0 = every
@@ -632,14 +673,18 @@ class MPC:
         return self._u_opt[0].reshape(NU, 1).copy(), (self._x_opt.copy() if one_rollout else self._x_opt[:2].copy())
 
     def update(self, contact_horizon: Sequence, c_horizon: Sequence, p_com_horizon, x_current=None,
-               one_rollout: bool = True):
+               one_rollout: bool = True, contact_normals=None):
         """run_simulation.py:106.  Returns (u_opt0 (12,1), x_opt1) where x_opt1[1] is the next state.
         one_rollout=True -> x_opt1 has the whole roll-out (N+1, 13); False -> only rows 0..1.
+        contact_normals: (N, 12) / (N, 4, 3) array or a per-step list of world-frame surface normals (BatchMPC.set_contact_normals): the friction pyramids
+        of sloped ground.  Such a call goes through the host-batch solve with B = 1 (the staged batch-1 path keeps its layout and has no normals).
 
         One C call (srbdqp_update_f64) with every argument bound once: the inputs go straight into the library's pinned staging arrays,
         the results are copied out of them once.  What Python adds to the C call is what NumPy needs to gather the reference's per-step
         lists (two np.concatenate of N small arrays: ~2.4 us of ~4.5 us in total); (N, 12) / (N, 4) arrays instead of lists cost
         ~2 us less."""
+        if contact_normals is not None:
+            return self._update_normals(contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals)
         upd = self._upd
         if upd is None:
             upd = self._bind()
@@ -693,6 +738,23 @@ class MPC:
         u_opt0 = u[0].reshape(NU, 1).copy()
         x_opt1 = x.copy() if one_rollout else x[:2].copy()
         return u_opt0, x_opt1
+
+    def _update_normals(self, contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals):
+        if self._engine is None:
+            self.init_matrices()
+        eng, N = self._engine, self.HORIZON_LENGTH
+        self._last_fast = self._last_fc = False
+        x_cur = np.asarray(self.x0 if x_current is None else x_current, dtype=np.float64).reshape(1, NX)
+        pc = None if p_com_horizon is None else np.asarray(p_com_horizon, dtype=np.float64).reshape(1, N, 3)
+        t0 = time.perf_counter()
+        out = eng.solve(x_cur, np.asarray(self.x_ref_hor, dtype=np.float64).reshape(1, N, NX), np.asarray(c_horizon, dtype=np.float64).reshape(1, N, NU),
+                        np.asarray(contact_horizon).reshape(1, N, NC), pcom=pc, normals=np.asarray(contact_normals, dtype=np.float64).reshape(1, N, NU))
+        self._solve_time = time.perf_counter() - t0
+        self._status, self._iters = int(out["status"][0]), int(out["iters"][0])
+        if self._status != _lib.SOLVED:
+            self._not_solved(self._status, self._iters, 4)
+        self._u_opt, self._x_opt = out["u"][0], out["x"][0]
+        return self._u_opt[0].reshape(NU, 1).copy(), (self._x_opt.copy() if one_rollout else self._x_opt[:2].copy())
 
     def close(self):
         self._upd = None

@@ -338,6 +338,34 @@ int srbdqp_set_schedule_hint(srbdqp_handle* h, const int32_t* device_iters_prev,
 int srbdqp_set_robots(srbdqp_handle* h, const srbdqp_robot* host, int32_t length);
 int srbdqp_set_robots_device(srbdqp_handle* h, const srbdqp_robot* dev, int32_t length);
 
+/* Contact normals: the friction pyramid of every contact point on sloped ground.  normals = [length][N][12] doubles: for QP b, step k, contact i the unit normal n of
+ * the surface under the contact, in the WORLD frame, at [b][k][3 i .. 3 i + 3).  The contact frame is R = [t1 t2 n] with
+ *     t1 = (e_x - n_x n) / |e_x - n_x n|,   t2 = n x t1            (n = (0, 0, 1): R = I exactly)
+ * and the five rows 20 k + 5 i + j of the contact act on the local force f_loc = R' f:  +-f_loc,x <= mu f_loc,z,  +-f_loc,y <= mu f_loc,z,
+ * fz_min <= f_loc,z <= fz_max.  Dynamics, cost, the row order and the units of u_out, x_out, warm_u (world frame, newtons) and warm_y / y_out (per row) do
+ * not change.  Rules for every normal, swing contacts included (whose normal has no effect): every entry finite, 0.5 <= |n| <= 2 (it is normalised),
+ * n_z >= 0.5 after normalising (slopes to 60 degrees).
+ *
+ * srbdqp_set_contact_normals: a HOST array, copied into a device buffer the library owns after the waits srbdqp_set_robots makes.  Every normal is checked
+ * first: on a bad one the call returns SRBDQP_E_INVALID, srbdqp_last_error names the first bad (qp, step, contact), and the previous setting stays.
+ * srbdqp_set_contact_normals_device: a DEVICE array the caller owns; the pointer is kept and read at every solve, so the array must stay untouched until the
+ * solves that read it have completed in stream order (the contract of the input arrays under SRBDQP_FLAG_DEFER_TAIL).  The kernel checks each normal: a QP
+ * with a bad one ends with SRBDQP_NUMERICAL and zero forces; the other QPs of the batch are not affected.
+ * host / dev NULL or length 0: back to flat ground.
+ *
+ * While normals are set:
+ *   - QP b of a solve reads block b -- b the CALLER's index: the same under the schedule hint's dispatch order, in every restart or deferred pass;
+ *   - a solve of B > length QPs returns SRBDQP_E_INVALID and launches nothing;
+ *   - srbdqp_solve_batch_f64 / _device_f64 run on the general kernel's contact-normal instantiation (srbdqp_kernel_name: wrench_f64_n<N>_cn; AUTO and
+ *     SRBDQP_KERNEL_WRENCH route there, an explicit SRBDQP_KERNEL_COMPACT / _SPLIT / _WAVE returns SRBDQP_E_INVALID with a message);
+ *   - these return SRBDQP_E_INVALID with a message that names the setter: the _f32 calls, the staged batch-1 calls (srbdqp_solve_staged_f64,
+ *     srbdqp_prepare_staged_f64 / srbdqp_solve_prepared_f64, srbdqp_update_f64: srbdqp_stage keeps its layout) and srbdqp_assemble_f64 / _wrench_f64.
+ * The setters refuse (SRBDQP_E_INVALID) an N = 24 handle, a handle whose horizon was admitted by SRBDQP_FLAG_ANY_HORIZON, and a handle that has robot records
+ * set; srbdqp_set_robots / _device refuse records while normals are set (a combined mode would be another copy of every instantiation).  Ragged objects have
+ * no such setter.  Without normals every call behaves as it always has. */
+int srbdqp_set_contact_normals(srbdqp_handle* h, const double* host /* [length][N][12] */, int32_t length);
+int srbdqp_set_contact_normals_device(srbdqp_handle* h, const double* dev, int32_t length);
+
 /* SRBDQP_FLAG_DEFER_TAIL: complete what earlier device-buffer solves on `stream` (a hipStream_t; NULL = every stream this handle has
  * launched on) left for later -- the one-wave kernel's continuations that no later solve has picked up (one launch of the
  * continuations alone, enqueued on that stream, in which every such QP runs all the passes it has left), and the restart passes running on the library's own tail stream (the
