@@ -567,8 +567,14 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
         }
     }
     if constexpr (FUSED) {
+        // The lane's K^-1 row is masked to the presolved block only where there is something to mask (wave-uniform: n_eff comes out of LDS, the same for every
+        // lane).  With n_eff == KS (configs[1]: 60 of 60) the column test holds for every c, and the row test concerns lanes KS..63 alone: their entries are
+        // K^-1 between a padded and a real variable -- K has zero rows (kasm_rows) and an identity diagonal (dcol) there, F, W and I reach those positions only
+        // through products with exact zeros -- and the iterations read neither the right-hand side nor any maximum of a lane past KS.  ~120 v_cndmask_b32 per pass.
+        if (__builtin_amdgcn_readfirstlane(n_eff) < W::KS) {
 #pragma unroll
-        for (int c = 0; c < W::KS; ++c) kin[c] = (lane < n_eff && c < n_eff) ? kin[c] : 0.0;
+            for (int c = 0; c < W::KS; ++c) kin[c] = (lane < n_eff && c < n_eff) ? kin[c] : 0.0;
+        }
         __syncthreads();
         WSTAMP(a, b, 8);
         WSTAMP(a, b, 9);
