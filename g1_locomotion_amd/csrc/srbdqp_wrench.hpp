@@ -59,6 +59,12 @@ namespace srbdqp {
 // KR64 = entries of an fp64 half row longer than 60 that stay in registers (KREG64 below; wrench_kreg64() has the one exception to 56)
 constexpr int wrench_kreg64(int N, int MODE) { return (MODE == 3 && N == 24) ? SRBDQP_LIVE24_KREG : 56; }
 // CN  = contact normals (MODE = 4): the table L of the contact frames' columns beside J in the persistent strip
+// Conditioning guard of a wrench step (phase E below; DESIGN.md, "Nearly collinear stance contacts"): the step is refused -- the QP ends with SRBDQP_NUMERICAL and
+// zero forces -- when a Cholesky pivot of the 3 x 3 Schur complement of its E = Y D^-1 Y' (CN: or of the force block G) is not above this fraction of the diagonal
+// entry of E in the pivot's row.  E loses rank when the stance contact points of the step lie on one line, and the ratio falls as the square of their distance
+// from it.  Two thresholds: the fp64 iterations, and the fp32 iterations, which carry E^-1's size into float32 V and Bd.  oracle/srbd_oracle.py holds the same two.
+constexpr double kGuardRatioF64 = 2.5e-7, kGuardRatioF32 = 3.0e-5;
+
 template <int N, int TB = 8, int SPW = 5, int XW = 0, int KR64 = 56, bool CN = false>
 struct WrenchSmem {
     static_assert(SPW >= 1 && SPW <= 5, "12 lanes per step");
@@ -1198,6 +1204,8 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             // (three dependent rsqrt chains instead of six, ~120 instead of ~270 fp64 instructions: 7.8 k -> cycles of the batch-1 set-up were this block).
             double Ei[6][6];
             bool okE = true;
+            // the conditioning guard: every pivot against GR times the diagonal entry of E in its row (orc.step_pivot_ratio: the same quantity, the same constants)
+            constexpr double GR = (sizeof(R) == 4) ? kGuardRatioF32 : kGuardRatioF64;
             {
                 // G = n_c diag(1 / d_xy, 1 / d_xy, 1 / d_z) with n_c = 3 or 4 stance contacts (a wrench step): its inverse without a division
                 const double inc = ((f0 + f1 + f2 + f3) == 4) ? 0.25 : (1.0 / 3.0);
@@ -1210,11 +1218,11 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     const double r0 = 1.0 / sqrt(g00);
                     const double l10 = g01 * r0, l20 = g02 * r0;
                     const double d1 = fma(-l10, l10, g11);
-                    okE = okE && (d1 > 0.0);
+                    okE = okE && (d1 > GR * g11);
                     const double r1 = 1.0 / sqrt(d1);
                     const double l21 = fma(-l20, l10, g12) * r1;
                     const double d2 = fma(-l21, l21, fma(-l20, l20, g22));
-                    okE = okE && (d2 > 0.0);
+                    okE = okE && (d2 > GR * g22);
                     const double r2 = 1.0 / sqrt(d2);
                     const double m10 = -l10 * r0 * r1, m21 = -l21 * r1 * r2, m20 = -(l20 * r0 + l21 * m10) * r2;
                     Gi[0][0] = fma(r0, r0, fma(m10, m10, m20 * m20)); Gi[0][1] = fma(m10, r1, m20 * m21); Gi[0][2] = m20 * r2;
@@ -1241,15 +1249,15 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     if constexpr (XW > 0) return (d > 0.0) ? fast_rsqrt2(d) : 0.0;
                     else return 1.0 / sqrt(d);
                 };
-                okE = okE && (Sc[0][0] > 0.0);
+                okE = okE && (Sc[0][0] > GR * Em[0][0]);
                 const double r0 = rs(Sc[0][0]);
                 const double l10 = Sc[0][1] * r0, l20 = Sc[0][2] * r0;
                 const double d1 = fma(-l10, l10, Sc[1][1]);
-                okE = okE && (d1 > 0.0);
+                okE = okE && (d1 > GR * Em[1][1]);
                 const double r1 = rs(d1);
                 const double l21 = fma(-l20, l10, Sc[1][2]) * r1;
                 const double d2 = fma(-l21, l21, fma(-l20, l20, Sc[2][2]));
-                okE = okE && (d2 > 0.0);
+                okE = okE && (d2 > GR * Em[2][2]);
                 const double r2 = rs(d2);
                 const double m10 = -l10 * r0 * r1;                       // Li[1][0]
                 const double m21 = -l21 * r1 * r2;                       // Li[2][1]
@@ -1278,7 +1286,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     }
             }
             ESTAMP(a, 2);
-            if (!okE && stepok && ul == 0) sm[S::o_misc] = 1.0;   // 4 collinear contact points: E singular
+            if (!okE && stepok && ul == 0) sm[S::o_misc] = 1.0;   // stance contact points on or near one line: E singular or too ill conditioned to invert
             // E^-1 goes to LDS WHOLE, from the first lane of the step, and every lane reads what it needs back (its row; one column entry per row) behind a
             // wave-local wait -- the 12 lanes of a step sit in one wave.  Until round 5 each lane picked row rl and column 3 + ax out of its register copy with
             // select chains: hipcc turned them into divergent branches around the entries' own arithmetic (37 exec-masked blocks, each run by every wave for every

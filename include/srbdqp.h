@@ -44,7 +44,11 @@ extern "C" {
 #define SRBDQP_SOLVED    1        /* primal and dual residual below tolerance */
 #define SRBDQP_MAX_ITER  2        /* iteration cap reached; best iterate returned */
 #define SRBDQP_PENDING   0        /* SRBDQP_FLAG_DEFER_TAIL only: the QP's continuation is deferred to the next solve on the stream / srbdqp_flush() */
-#define SRBDQP_NUMERICAL (-1)     /* non-finite residual / non-positive pivot (e.g. NaN inputs); forces returned as 0 */
+#define SRBDQP_NUMERICAL (-1)     /* non-finite residual / non-positive pivot (e.g. NaN inputs); forces returned as 0.
+                                     On the general kernel (SRBDQP_KERNEL_WRENCH) also: the stance contact points of a step with three or four
+                                     stance contacts lie on or near one line (feet in tandem, heel and toe at one point).  The QP is rejected before
+                                     its factorisation: u, y and iters are 0, x is the roll-out of zero forces, the other QPs of the batch are not
+                                     affected, and no restart pass or deferred continuation runs it again.  See SRBDQP_KERNEL_WRENCH. */
 #define SRBDQP_CONTACT_BOUND (-2) /* more stance contacts in a step than srbdqp_config.max_contacts_per_step allows; forces 0 */
 
 /* srbdqp_config.flags */
@@ -101,7 +105,14 @@ extern "C" {
 #define SRBDQP_KERNEL_WRENCH 6    /* the general kernel: any contact pattern at every horizon (4 ... 24), wrench-space presolve
                                      (a step with >= 3 stance contacts contributes 6 coordinates instead of 3 per contact),
                                      fp64 or fp32 iterations; AUTO picks it for > 2 stance contacts per step at N > 10 and -- batches of
-                                     512 QPs and more, and the staged batch-1 call -- at N <= 10, for N = 24 and for every _f32 call */
+                                     512 QPs and more, and the staged batch-1 call -- at N <= 10, for N = 24 and for every _f32 call.
+                                     Limit: a step with >= 3 stance contacts is held in 6 wrench coordinates, which lose rank when its stance
+                                     contact points lie on one line (the torque about the line is fixed by the total force) although the QP stays
+                                     well posed.  The kernel compares every pivot of the step's 3 x 3 Schur complement with the diagonal entry it
+                                     came from and ends the QP with SRBDQP_NUMERICAL below 2.5e-7 (fp64 calls) or 3e-5 (_f32 calls): the ratio is
+                                     about 0.3 ... 3 times the square of the points' distance from the line in metres (0.9 mm / 1 cm for feet in
+                                     tandem).  A QP that comes back SOLVED keeps the usual accuracy (MAX_ITER is the best iterate, as ever).  The dense kernels (COMPACT, SPLIT, WAVE, with
+                                     max_contacts_per_step set to the schedule's) have no such limit and solve these inputs. */
 
 /* Everything `MPC.__init__(dt)` / `MPC.init_matrices()` hold (run_simulation.py:169-170).  Values the
  * reference keeps inside the absent module are this build's documented choices. */
@@ -233,7 +244,9 @@ int srbdqp_assemble_f64(srbdqp_handle* h, int32_t B,
  *   q_out      [B][12N]      gradient in the scaled force variables (0 for swing contacts)
  *   blocks_out [B][12N][24]  per force variable u (index 12 k + 3 i + a): row u of Bd within its step (12), column u of
  *                            V (6), and -- as lane (row r = (u % 12) / 2, half h = u % 2) of the step -- V[r][6h .. 6h+5] (6)
- *   goff_out   [B][N+1]      offset of step j's coordinates in T (as doubles); goff[N] = n_g
+ *   goff_out   [B][N+1]      offset of step j's coordinates in T (as doubles); goff[N] = n_g.  goff[N] = -1 marks a QP the kernel rejects
+ *                            (SRBDQP_NUMERICAL in a solve: non-finite inputs, nearly collinear stance contacts): the call still returns
+ *                            SRBDQP_OK, and NOTHING else of that QP's outputs is written -- test goff[N] first.
  * HOST buffers; parity tests of rows a5-a8 on the kernel that ships (tests/test_gpu_wrench.py). */
 int srbdqp_assemble_wrench_f64(srbdqp_handle* h, int32_t B,
                                const double* x0, const double* x_ref, const double* foot,

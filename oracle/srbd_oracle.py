@@ -308,6 +308,40 @@ def closed_form_hessian_rank6(p: SrbdParams, x_ref, foot_hor, contact_hor, pcom_
     return P + p.r_diag * s * s * np.eye(n)
 
 
+# The general kernel's conditioning guard (srbdqp_wrench.hpp, DESIGN.md section "Nearly collinear stance contacts"): a wrench step is rejected when a pivot of its
+# 3 x 3 Schur complement Sc = A - B G^-1 B' of E = [A B; B' G] (or of the force block G) falls to GUARD_RATIO times the diagonal entry of E it came from.
+# Two thresholds: the fp64 instantiations, and the stricter one of the fp32 iterations (V and Bd rounded to float32 carry E^-1's size into the loop).
+GUARD_RATIO_F64 = 2.5e-7
+GUARD_RATIO_F32 = 3.0e-5
+
+
+def guard_ratio(dtype) -> float:
+    return GUARD_RATIO_F32 if np.dtype(dtype) == np.dtype(np.float32) else GUARD_RATIO_F64
+
+
+def step_pivot_ratio(E):
+    """The quantity the guard compares, for one wrench step's 6 x 6 E: min over the Cholesky pivots of G = E[3:, 3:] and of Sc = E[:3, :3] - B G^-1 B' of
+    pivot / (the diagonal entry of E in that row).  Healthy stances of the suite: 4e-4 ... 2e-2; contact points within eps metres of one line: 0.3 ... 3 eps^2; <= 0 when a pivot is."""
+    def pivots(M, ref):
+        L = np.zeros((3, 3))
+        out = []
+        for j in range(3):
+            d = M[j, j] - L[j, :j] @ L[j, :j]
+            out.append(d / ref[j])
+            if not d > 0.0:
+                return out, None
+            L[j, j] = np.sqrt(d)
+            L[j + 1:, j] = (M[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+        return out, L
+    A, Bm, G = E[:3, :3], E[:3, 3:], E[3:, 3:]
+    rg, Lg = pivots(G, np.diag(G))
+    if Lg is None:
+        return float(min(rg))
+    X = np.linalg.solve(Lg, Bm.T)                 # Lg^-1 B'
+    rs, _ = pivots(A - X.T @ X, np.diag(A))
+    return float(min(rg + rs))
+
+
 def wrench_reduce(p: SrbdParams, x_ref, foot_hor, contact_hor, pcom_hor=None, rho=None):
     """The presolve of the general (any contact pattern) HIP kernel, restated in NumPy for the tests: the reduced-KKT
     matrix K = P + sigma I + A' rho A of the stance-contact QP, inverted through the rank structure of the SRBD.
@@ -321,7 +355,8 @@ def wrench_reduce(p: SrbdParams, x_ref, foot_hor, contact_hor, pcom_hor=None, rh
         K^-1 = Bd + V' T^-1 V,   T = S + E^-1,  E = Y D^-1 Y' (block diagonal),  V = E^-1 Y D^-1,
         Bd = D^-1 - D^-1 Y' V   (block diagonal; zero on the identity steps)
     (Woodbury twice).  Only T (n_g x n_g, n_g <= 6N) is factored: double support at N = 20 is a 120 x 120 problem
-    instead of 240 x 240.  Returns dict(T, V, Bd, D, gsz, goff, n_g, vi, contacts)."""
+    instead of 240 x 240.  Returns dict(T, V, Bd, D, gsz, goff, n_g, vi, contacts, pivot_ratio): pivot_ratio = the smallest step_pivot_ratio() of the
+    wrench steps (inf without one), what the kernel's conditioning guard compares with GUARD_RATIO_*.  An E that NumPy cannot invert leaves NaN blocks."""
     x_ref = np.asarray(x_ref, dtype=np.float64)
     N = x_ref.shape[0]
     foot_hor = np.asarray(foot_hor, dtype=np.float64).reshape(N, NC, 3)
@@ -380,18 +415,24 @@ def wrench_reduce(p: SrbdParams, x_ref, foot_hor, contact_hor, pcom_hor=None, rh
     T = S.copy()
     V = np.zeros((n_g, nu_))
     Bd = np.zeros((nu_, nu_))
+    pivot_ratio = np.inf
     for k in range(N):
         if gsz[k] == 0:
             continue
         us = slice(uoff[k], uoff[k] + 3 * csz[k]); gs = slice(goff[k], goff[k + 1])
         Dk = D[us]
         E = (Y[k] / Dk) @ Y[k].T
-        Einv = np.linalg.inv(E)
+        if csz[k] >= 3:
+            pivot_ratio = min(pivot_ratio, step_pivot_ratio(E))
+        try:
+            Einv = np.linalg.inv(E)
+        except np.linalg.LinAlgError:             # exactly singular: what the unguarded kernel turns into non-finite blocks
+            Einv = np.full_like(E, np.nan)
         Einv = 0.5 * (Einv + Einv.T)
         T[gs, gs] += Einv
         V[gs, us] = Einv @ (Y[k] / Dk)
         Bd[us, us] = np.diag(1.0 / Dk) - (Y[k] / Dk).T @ V[gs, us]
-    return dict(T=T, V=V, Bd=Bd, D=D, S=S, gsz=gsz, goff=goff, n_g=n_g, vi=vi, contacts=contacts, csz=np.array(csz))
+    return dict(T=T, V=V, Bd=Bd, D=D, S=S, gsz=gsz, goff=goff, n_g=n_g, vi=vi, contacts=contacts, csz=np.array(csz), pivot_ratio=float(pivot_ratio))
 
 
 def wrench_kinv_op(wr):
@@ -611,11 +652,14 @@ def fp32_tiles_ok(contact_hor) -> bool:
     return bool(np.all((c == 0) | (c >= 3)))
 
 
-def update_split(p: SrbdParams, x0, x_ref, foot_hor, contact_hor, pcom_hor=None, warm=None, dtype=np.float32, tile_dtype=np.float64):
+def update_split(p: SrbdParams, x0, x_ref, foot_hor, contact_hor, pcom_hor=None, warm=None, dtype=np.float32, tile_dtype=np.float64, guard=True):
     """Oracle twin of the general kernel's fp32 (or fp64) path: like update(), through wrench_reduce() +
     admm_solve_split().  With dtype=float32 the inputs are first rounded to float32, as the _f32 entry points see them.
     tile_dtype: np.float64, np.float32 or "auto" (float32 where fp32_tiles_ok(), as the engine does for batches >= 512);
-    the pass after a rho restart always factors in float64 tiles."""
+    the pass after a rho restart always factors in float64 tiles.
+    guard: the kernel's conditioning guard -- a wrench step whose pivot ratio (step_pivot_ratio) is not above guard_ratio(dtype), in the first or in a
+    restart pass, ends the QP with STATUS_NUMERICAL, zero forces, zero duals and iters = 0.  guard=False is the algorithm without it (the reference that
+    says which QPs the wrench coordinates can answer at all): a factorisation NumPy refuses then gives STATUS_NUMERICAL with NaN forces."""
     if isinstance(tile_dtype, str):
         tile_dtype = np.float32 if (dtype == np.float32 and fp32_tiles_ok(contact_hor)) else np.float64
     if dtype == np.float32:
@@ -625,34 +669,53 @@ def update_split(p: SrbdParams, x0, x_ref, foot_hor, contact_hor, pcom_hor=None,
     n, m = qp["P"].shape[0], qp["A"].shape[0]
     red, vi, ri = presolve(qp, contact_hor)
     uh = np.zeros(n); y = np.zeros(m)
+    thr = guard_ratio(dtype)
+    pivot_ratio = np.inf
+
+    def reduce_(pc):
+        nonlocal pivot_ratio
+        w = wrench_reduce(pc, x_ref, foot_hor, contact_hor, pcom_hor)
+        pivot_ratio = min(pivot_ratio, w["pivot_ratio"])
+        return w, bool(guard) and not (w["pivot_ratio"] > thr)
+
     if len(vi) == 0:
         iters, status = 0, STATUS_SOLVED
     else:
-        wr = wrench_reduce(p, x_ref, foot_hor, contact_hor, pcom_hor)
         xi, yi = (None, None) if warm is None else (np.asarray(warm[0])[vi], np.asarray(warm[1])[ri])
         args = (red["P"], red["q"], red["A"], red["l"], red["u"])
-        if 0 < p.rho_restart_iter < p.max_iter:   # the general kernel's rho restart passes (same rule as solve_with_restart: up to rho_restart_count
-            # re-balancings, each from the rho of the pass before it, the cap on the total; every pass after the first factors in float64 tiles)
-            nre = max(int(p.rho_restart_count), 1)
-            pc, w, td, xs_, ys_, iters = p, wr, tile_dtype, xi, yi, 0
-            for k in range(nre + 1):
-                left = p.max_iter - iters
-                cap = p.rho_restart_iter if (k < nre and p.rho_restart_iter < left) else left
-                info = {}
-                xr_, _, yr_, it, status = admm_solve_split(replace(pc, max_iter=cap), *args, w, xs_, ys_, dtype=dtype, info=info, tile_dtype=td)
-                iters += it
-                if status != STATUS_MAX_ITER or cap == left:
-                    break
-                pc = replace(pc, rho=restart_rho(pc, info))
-                w = wrench_reduce(pc, x_ref, foot_hor, contact_hor, pcom_hor)
-                xs_, ys_, td = xr_, yr_, np.float64
-        else:
-            xr_, _, yr_, iters, status = admm_solve_split(p, *args, wr, xi, yi, dtype=dtype, tile_dtype=tile_dtype)
+        xr_ = yr_ = None
+        try:
+            wr, rejected = reduce_(p)
+            if rejected:
+                raise np.linalg.LinAlgError("conditioning guard")
+            if 0 < p.rho_restart_iter < p.max_iter:   # the general kernel's rho restart passes (same rule as solve_with_restart: up to rho_restart_count
+                # re-balancings, each from the rho of the pass before it, the cap on the total; every pass after the first factors in float64 tiles)
+                nre = max(int(p.rho_restart_count), 1)
+                pc, w, td, xs_, ys_, iters = p, wr, tile_dtype, xi, yi, 0
+                for k in range(nre + 1):
+                    left = p.max_iter - iters
+                    cap = p.rho_restart_iter if (k < nre and p.rho_restart_iter < left) else left
+                    info = {}
+                    xr_, _, yr_, it, status = admm_solve_split(replace(pc, max_iter=cap), *args, w, xs_, ys_, dtype=dtype, info=info, tile_dtype=td)
+                    iters += it
+                    if status != STATUS_MAX_ITER or cap == left:
+                        break
+                    pc = replace(pc, rho=restart_rho(pc, info))
+                    w, rejected = reduce_(pc)
+                    if rejected:
+                        raise np.linalg.LinAlgError("conditioning guard")
+                    xs_, ys_, td = xr_, yr_, np.float64
+            else:
+                xr_, _, yr_, iters, status = admm_solve_split(p, *args, wr, xi, yi, dtype=dtype, tile_dtype=tile_dtype)
+        except np.linalg.LinAlgError:                 # the guard, or a T that has no Cholesky factor (the kernel's ok flags): zero forces, zero duals
+            iters, status = 0, STATUS_NUMERICAL
+            xr_ = np.zeros(len(vi)) if guard else np.full(len(vi), np.nan)
+            yr_ = np.zeros(len(ri)) if guard else np.full(len(ri), np.nan)
         uh[vi] = xr_
         y[ri] = yr_
     N = np.asarray(x_ref).shape[0]
     return dict(u=(uh * p.force_scale).reshape(N, NU), x=rollout(qp, x0, uh, p.force_scale), iters=iters, status=status,
-                u_hat=uh, y=y, qp=qp)
+                u_hat=uh, y=y, qp=qp, pivot_ratio=float(pivot_ratio))
 
 
 def _chol(K):

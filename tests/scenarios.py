@@ -183,3 +183,51 @@ def yaw_of_next_step(xr):
 def foothold_of_step0(ft):
     """foot with the row of step 0 on every step."""
     return np.broadcast_to(ft[..., 0:1, :], ft.shape).copy()
+
+
+# ---- nearly collinear stance contacts: where the general kernel's wrench coordinates lose rank ------------------------------------------
+EPS_LADDER = (1e-1, 3e-2, 1e-2, 3e-3, 1e-3, 1e-4, 1e-5, 1e-6, 1e-8, 0.0)
+COLLINEAR_KINDS = ("tandem", "point")
+
+
+def wrench_steps(contact):
+    """Indices of the steps the general kernel keeps in wrench coordinates: three or four stance contacts."""
+    return [int(k) for k in np.nonzero((np.asarray(contact).reshape(-1, 4) != 0).sum(axis=1) >= 3)[0]]
+
+
+def collinear_contacts(foot, contact, eps, kind, steps=None):
+    """foot (N, 12) of ONE QP with the contact points of `steps` (default: every wrench step) moved to within eps metres of one line; a copy.
+
+    kind: "tandem" the right foot is put on the line through the left foot's heel and toe, 3 cm ahead of the left toe, offset sideways by eps
+          "point"  point feet: each toe is put at its heel + eps sideways of the line through the two heels
+    All four points of a step are moved whether they stand or swing (a swing point's position never enters the QP); heights are kept.  With eps = 0 the
+    stance points of a deformed step lie exactly on one line: E = Y D^-1 Y' of that step has rank 5, while the QP itself stays well posed."""
+    if kind not in COLLINEAR_KINDS:
+        raise ValueError(f"kind must be one of {COLLINEAR_KINDS}")
+    ft = np.array(foot, dtype=np.float64).reshape(-1, 4, 3)
+    for k in (wrench_steps(contact) if steps is None else steps):
+        a, b = (ft[k, 0, :2], ft[k, 1, :2]) if kind == "tandem" else (ft[k, 0, :2], ft[k, 2, :2])
+        d = (b - a) / np.linalg.norm(b - a)
+        side = np.array([-d[1], d[0]])
+        if kind == "tandem":
+            length = np.linalg.norm(ft[k, 3, :2] - ft[k, 2, :2])
+            ft[k, 2, :2] = b + 0.03 * d + eps * side
+            ft[k, 3, :2] = ft[k, 2, :2] + length * d
+        else:
+            ft[k, 1, :2] = ft[k, 0, :2] + eps * side
+            ft[k, 3, :2] = ft[k, 2, :2] + eps * side
+    return ft.reshape(np.shape(foot))
+
+
+def collinear_ladder(N, schedule, seed, kind, placement="all", rungs=EPS_LADDER):
+    """One base QP of synthetic_batch() ("three": "mixed" footholds, contacts through three_contacts()) deformed at every eps of `rungs`.
+    placement: "all" wrench steps, only the "first" or only the "last" one.  Returns x0 (R,13), x_ref (R,N,13), foot (R,N,12), contact (R,N,4)."""
+    x0, xr, ft, ct = synthetic_batch(1, N, seed, "mixed" if schedule == "three" else schedule)
+    if schedule == "three":
+        ct = three_contacts(ct, seed)
+    ws = wrench_steps(ct[0])
+    assert ws, "the base QP has no wrench step"
+    steps = {"all": ws, "first": ws[:1], "last": ws[-1:]}[placement]
+    R = len(rungs)
+    foot = np.stack([collinear_contacts(ft[0], ct[0], e, kind, steps) for e in rungs])
+    return np.repeat(x0, R, 0), np.repeat(xr, R, 0), foot, np.repeat(ct, R, 0)

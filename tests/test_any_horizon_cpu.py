@@ -138,6 +138,8 @@ def test_live_horizon_kernels_cost_what_their_twins_cost(rows, N):
 
 
 # (VGPRs, AGPRs, SGPRs, scratch bytes per lane, waves per SIMD) of every instantiation of the general kernel that existed before the flag
+# (three entries re-pinned with the conditioning guard of phase E, which changed the kernels themselves: N = 16 fp32 on fp64 tiles 224 -> 216 bytes of scratch,
+#  the N = 4 low-latency pair 174 -> 176 VGPRs; occupancy as before)
 BEFORE = {
     "srbdqp_wrench_kernel<24, float, float, 0, 2, double, 5, 3>": (256, 0, 106, 92, 2),
     "srbdqp_wrench_kernel<24, float, float, 0, 3, float, 5, 0>": (168, 0, 106, 64, 3),
@@ -148,7 +150,7 @@ BEFORE = {
     "srbdqp_wrench_kernel<20, double, double, 1, 2, double, 5, 0>": (194, 0, 55, 0, 2),
     "srbdqp_wrench_kernel<20, double, double, 2, 2, double, 5, 0, void>": (256, 0, 106, 0, 2),
     "srbdqp_wrench_kernel<20, double, double, 0, 2, double, 5, 0>": (256, 0, 106, 0, 2),
-    "srbdqp_wrench_kernel<16, float, float, 0, 3, double, 5, 0>": (168, 0, 106, 224, 3),
+    "srbdqp_wrench_kernel<16, float, float, 0, 3, double, 5, 0>": (168, 0, 106, 216, 3),
     "srbdqp_wrench_kernel<16, float, float, 0, 3, float, 5, 0>": (168, 0, 106, 0, 3),
     "srbdqp_wrench_kernel<16, double, double, 1, 2, double, 5, 0>": (158, 0, 53, 0, 3),
     "srbdqp_wrench_kernel<16, double, double, 2, 2, double, 5, 0, void>": (230, 0, 106, 0, 2),
@@ -176,8 +178,8 @@ BEFORE = {
     "srbdqp_wrench_kernel<4, float, float, 0, 3, float, 5, 0>": (142, 0, 106, 0, 3),
     "srbdqp_wrench_kernel<4, double, double, 1, 3, double, 5, 0>": (124, 0, 61, 0, 4),
     "srbdqp_wrench_kernel<4, double, double, 2, 3, double, 5, 0, void>": (130, 0, 104, 0, 3),
-    "srbdqp_wrench_kernel<4, double, double, 0, 1, double, 5, 1>": (174, 24, 94, 0, 2),
-    "srbdqp_wrench_kernel_in<4, 1>": (174, 24, 90, 0, 2),
+    "srbdqp_wrench_kernel<4, double, double, 0, 1, double, 5, 1>": (176, 24, 94, 0, 2),
+    "srbdqp_wrench_kernel_in<4, 1>": (176, 24, 90, 0, 2),
     "srbdqp_wrench_kernel<4, double, double, 0, 3, double, 5, 0>": (130, 0, 102, 0, 3),
 }
 
