@@ -26,6 +26,7 @@ FLAG_F32_TILES = 16    # _f32 calls: fp32 tiles for the eligible QPs of small ba
 FLAG_NO_LAT = 32       # staged calls on the general kernel: the batch instantiation instead of the low-latency one
 FLAG_DEFER_TAIL = 64   # one-wave kernel: continuations of unconverged QPs ride in the next solve on the stream (srbdqp_flush completes them)
 FLAG_ANY_HORIZON = 128  # admit every horizon 1 ... 24: one without instantiations of its own runs the general kernel's live-horizon mode
+FLAG_RANK_AWARE = 256  # general kernel, fp64: steps with stance contact points on or near one line take rank-aware coordinates instead of ending the QP with status -1
 HORIZONS = (4, 8, 10, 12, 16, 20, 24)   # horizons with instantiations of their own (no flag needed)
 PENDING = 0
 KERNEL_AUTO, KERNEL_COMPACT, KERNEL_SPLIT, KERNEL_WAVE, KERNEL_WRENCH = 0, 3, 4, 5, 6   # 1, 2: the retired round-1 baselines

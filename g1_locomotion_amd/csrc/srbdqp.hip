@@ -641,6 +641,16 @@ int live_refuse(srbdqp_handle* h, const char* what) {
     return SRBDQP_E_INVALID;
 }
 
+// a call that has no rank-aware form, on a handle created with SRBDQP_FLAG_RANK_AWARE (include/srbdqp.h has the list)
+int rank_aware_refuse(srbdqp_handle* h, const char* what) {
+    h->err = std::string(what) + ": refused on a handle created with SRBDQP_FLAG_RANK_AWARE: only the fp64 batch and staged solves have rank-aware wrench steps "
+             "(the general kernel's fp64 batch instantiation, flat ground, srbdqp_config's single robot)";
+    return SRBDQP_E_INVALID;
+}
+// Horizons with a rank-aware instantiation (MODE = 5) of the general kernel: every tabulated one below 24 builds without scratch memory at the waves per SIMD of
+// its MODE = 0 twin ("Rank-aware wrench steps", has the table); N = 24 -- whose MODE = 0 kernel keeps 20 bytes per lane there already -- has none.
+constexpr int kRankAwareMaxHorizon = 20;
+
 // The general kernel (srbdqp_wrench.hpp): any contact pattern, fp64 or fp32 iterations / buffers.
 template <int N, typename R, int TB = 8>
 struct WrenchTraits {
@@ -675,6 +685,24 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
     constexpr size_t ldsb = SB::bytes;
     static_assert(ldsb <= 163840, "one QP must fit the LDS of a CU");
     static const std::string nm = std::string("wrench_") + (sizeof(R) == 4 ? "f32" : "f64") + "_n" + std::to_string(N);
+    if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) {
+        // rank-aware wrench steps: the MODE = 5 instantiation of the fp64 batch kernel -- every launch of a solve (first pass, restart passes, deferred passes on the
+        // tail stream, a dispatch order, the staged calls with their completion word) comes through here with this handle.  (srbdqp_create refuses the flag at
+        // N = 24 and at a live horizon, and the entry points the fp32 and dump calls, robot records and contact normals.)  The layout of the MODE = 0 twin.
+        if constexpr (sizeof(R) == 8 && N <= kRankAwareMaxHorizon) {
+            if (a.mode == 1) return rank_aware_refuse(h, "the assembly dump");
+            using S5 = srbdqp::WrenchSmem<N, 8, 5, 0, srbdqp::wrench_kreg64(N, 5)>;
+            static_assert(S5::bytes == lds && S5::BT == S::BT && WrenchTraits<N, double>::wps == WPS, "rank-aware steps cost no occupancy: the LDS and the waves per SIMD of the MODE = 0 twin");
+            void (*k5)(KArgs) = &srbdqp::srbdqp_wrench_ra_kernel<N, WPS>;
+            int rc5 = set_lds_once(h, k5, lds);
+            if (rc5 != SRBDQP_OK) return rc5;
+            static const std::string nm5 = nm + "_ra";
+            h->kname = nm5.c_str();
+            hipLaunchKernelGGL(k5, dim3((unsigned)a.B), dim3(S::BT), lds, st, a);
+            HIP_TRY(h, hipGetLastError());
+            return SRBDQP_OK;
+        } else return rank_aware_refuse(h, sizeof(R) == 4 ? "an fp32 solve" : "a solve at this horizon");
+    }
     if (h->live_nstar) {
         // a live horizon n = cfg.horizon < N (SRBDQP_FLAG_ANY_HORIZON): the MODE = 3 instantiation of the fp64 batch kernel, n as its second argument -- every launch of
         // a solve (first pass, restart passes, deferred passes on the tail stream, ragged buckets, the staged calls with their completion word) comes through here
@@ -1122,6 +1150,7 @@ int normals_refuse(srbdqp_handle* h, const char* what) {
 // a combined mode would be another copy of every instantiation)
 int normals_check_handle(srbdqp_handle* h, const char* fn) {
     if (h->live_nstar) return live_refuse(h, fn);
+    if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) return rank_aware_refuse(h, fn);
     if (h->cfg.horizon > kRobotsMaxHorizon) { h->err = std::string(fn) + ": contact normals: not at N = 24 (no instantiation of the general kernel reads them there, DESIGN.md section 13)"; return SRBDQP_E_INVALID; }
     if (h->robots) { h->err = std::string(fn) + ": refused while per-QP robot records are set (srbdqp_set_robots): no instantiation reads both (DESIGN.md section 13)"; return SRBDQP_E_INVALID; }
     return SRBDQP_OK;
@@ -1189,6 +1218,11 @@ int srbdqp_create(const srbdqp_config* cfg, srbdqp_handle** out) {
         g_create_err = "SRBDQP_FLAG_ANY_HORIZON: a horizon outside {4, 8, 10, 12, 16, 20, 24} runs on the general kernel only (srbdqp_config.kernel = SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH)";
         return SRBDQP_E_INVALID;
     }
+    if ((cfg->flags & SRBDQP_FLAG_RANK_AWARE) && (live || cfg->horizon > kRankAwareMaxHorizon)) {
+        g_create_err = live ? "SRBDQP_FLAG_RANK_AWARE: not at a live horizon of SRBDQP_FLAG_ANY_HORIZON (the rank-aware instantiations are built for N in {4, 8, 10, 12, 16, 20})"
+                            : "SRBDQP_FLAG_RANK_AWARE: not at N = 24 (no instantiation of the general kernel without scratch memory there; N in {4, 8, 10, 12, 16, 20})";
+        return SRBDQP_E_INVALID;
+    }
     if (cfg->kernel != SRBDQP_KERNEL_AUTO && cfg->kernel != SRBDQP_KERNEL_COMPACT && cfg->kernel != SRBDQP_KERNEL_SPLIT &&
         cfg->kernel != SRBDQP_KERNEL_WAVE && cfg->kernel != SRBDQP_KERNEL_WRENCH) { g_create_err = "unknown srbdqp_config.kernel (the round-1 baselines v0 / v1 are retired)"; return SRBDQP_E_INVALID; }
     if (!(cfg->dt > 0) || !(cfg->mass > 0) || !(cfg->force_scale > 0) || !(cfg->rho >= 0) || !(cfg->sigma > 0) ||
@@ -1214,6 +1248,11 @@ int srbdqp_create(const srbdqp_config* cfg, srbdqp_handle** out) {
         // the staged calls run the batch instantiation through the HIP launch, as SRBDQP_FLAG_NO_LAT does (no _lat / *_in kernel reads a live horizon): no AQL queue
         h->aql_tried = true;
         h->aql_why = "SRBDQP_FLAG_ANY_HORIZON: a live horizon runs the batch instantiation of the general kernel";
+    }
+    if (cfg->flags & SRBDQP_FLAG_RANK_AWARE) {
+        // the staged calls of such a handle go through the HIP launch: on the general kernel they run the batch instantiation _ra (no _lat / *_in kernel has rank-aware steps)
+        h->aql_tried = true;
+        h->aql_why = "SRBDQP_FLAG_RANK_AWARE: the staged calls run the batch instantiation of the general kernel";
     }
     if (h->cfg.rho == 0.0) h->cfg.rho = 0.7;                    // auto (oracle auto_rho()): friction rows
     if (h->cfg.rho_fz_scale == 0.0) h->cfg.rho_fz_scale = 4.0;   // auto (oracle auto_rho_fz_scale()): normal-force rows at 4 rho
@@ -1432,6 +1471,7 @@ int srbdqp_set_robots(srbdqp_handle* h, const srbdqp_robot* host, int32_t length
     if (host && length < 0) { h->err = "srbdqp_set_robots: negative length"; return SRBDQP_E_INVALID; }
     const bool clear = !host || length == 0;
     if (!clear && h->live_nstar) return live_refuse(h, "srbdqp_set_robots");
+    if (!clear && (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE)) return rank_aware_refuse(h, "srbdqp_set_robots");
     if (!clear && h->cfg.horizon > kRobotsMaxHorizon) { h->err = robots_n24; return SRBDQP_E_INVALID; }
     if (!clear && h->normals) return normals_refuse(h, "srbdqp_set_robots");
     if (!clear) {
@@ -1455,6 +1495,7 @@ int srbdqp_set_robots_device(srbdqp_handle* h, const srbdqp_robot* dev, int32_t 
     if (dev && length < 0) { h->err = "srbdqp_set_robots_device: negative length"; return SRBDQP_E_INVALID; }
     const bool clear = !dev || length == 0;
     if (!clear && h->live_nstar) return live_refuse(h, "srbdqp_set_robots_device");
+    if (!clear && (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE)) return rank_aware_refuse(h, "srbdqp_set_robots_device");
     if (!clear && h->cfg.horizon > kRobotsMaxHorizon) { h->err = robots_n24; return SRBDQP_E_INVALID; }
     if (!clear && h->normals) return normals_refuse(h, "srbdqp_set_robots_device");
     h->robots = clear ? nullptr : dev;
@@ -1783,6 +1824,7 @@ int srbdqp_solve_batch_device_f32(srbdqp_handle* h, int32_t B, const float* x0, 
     if (h->robots) return robots_refuse(h, "srbdqp_solve_batch_device_f32");
     if (h->normals) return normals_refuse(h, "srbdqp_solve_batch_device_f32");
     if (h->live_nstar) return live_refuse(h, "srbdqp_solve_batch_device_f32");
+    if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) return rank_aware_refuse(h, "srbdqp_solve_batch_device_f32");
     return solve_device_impl(h, device_call(h, true), B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
 }
 
@@ -1804,6 +1846,7 @@ int srbdqp_solve_batch_f32(srbdqp_handle* h, int32_t B, const float* x0, const f
     if (h->robots) return robots_refuse(h, "srbdqp_solve_batch_f32");
     if (h->normals) return normals_refuse(h, "srbdqp_solve_batch_f32");
     if (h->live_nstar) return live_refuse(h, "srbdqp_solve_batch_f32");
+    if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) return rank_aware_refuse(h, "srbdqp_solve_batch_f32");
     return solve_host_impl(h, true, B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters);
 }
 
@@ -1891,6 +1934,7 @@ int srbdqp_assemble_wrench_f64(srbdqp_handle* h, int32_t B, const double* x0, co
     if (h->robots) return robots_refuse(h, "srbdqp_assemble_wrench_f64");
     if (h->normals) return normals_refuse(h, "srbdqp_assemble_wrench_f64");
     if (h->live_nstar) return live_refuse(h, "srbdqp_assemble_wrench_f64");
+    if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) return rank_aware_refuse(h, "srbdqp_assemble_wrench_f64");
     if (B < 0 || (B > 0 && (!x0 || !x_ref || !foot || !contact || !T_out || !q_out || !blocks_out || !goff_out))) { h->err = "null pointer"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1950,6 +1994,7 @@ std::string g_ragged_err;
 int srbdqp_ragged_create(const srbdqp_config* cfg, const int32_t* horizons, int32_t n_horizons, srbdqp_ragged** out) {
     if (!cfg || !horizons || !out || n_horizons < 1 || n_horizons > 16) { g_ragged_err = "bad argument"; return SRBDQP_E_INVALID; }
     *out = nullptr;
+    if (cfg->flags & SRBDQP_FLAG_RANK_AWARE) { g_ragged_err = "SRBDQP_FLAG_RANK_AWARE: ragged objects have no rank-aware form (the flag is read by srbdqp_create's handles only)"; return SRBDQP_E_INVALID; }
     srbdqp_ragged* r = new (std::nothrow) srbdqp_ragged();
     if (!r) { g_ragged_err = "out of host memory"; return SRBDQP_E_NOMEM; }
     r->device = cfg->device;

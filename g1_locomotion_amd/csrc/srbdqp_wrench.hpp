@@ -64,6 +64,13 @@ constexpr int wrench_kreg64(int N, int MODE) { return (MODE == 3 && N == 24) ? S
 // entry of E in the pivot's row.  E loses rank when the stance contact points of the step lie on one line, and the ratio falls as the square of their distance
 // from it.  Two thresholds: the fp64 iterations, and the fp32 iterations, which carry E^-1's size into float32 V and Bd.  oracle/srbd_oracle.py holds the same two.
 constexpr double kGuardRatioF64 = 2.5e-7, kGuardRatioF32 = 3.0e-5;
+// MODE = 5 (rank-aware steps): a pivot of Sc is dropped -- its column of L zero -- only at rounding level: about ten times the rounding of the pivot's own cancellation
+constexpr double kDropRatio = 1.0e-14;
+// ... and a step takes the normalised coordinates when the guard's quantity is not above this: 400 x kGuardRatioF64.  At the guard's own threshold the steps just
+// above it stay on E^-1, whose error grows as 1 / ratio: the forces keep the suite's 5e-2 N there, but the stationarity residual P x + q + A'y does not -- 20
+// double-support steps at ratio 2.5e-6 (N = 20, point feet 1 mm wide) left 227 against the suite's bound 1e-3 max|q| = 49 (the CPU twin: 53), 1.3 at ratio 1.7e-3.
+// 1e-4 keeps a factor 10 below that bound and lies under every healthy stance of the suite (4e-4 ... 2e-2), which therefore run exactly as without the flag.
+constexpr double kRankAwareRatio = 1.0e-4;
 
 template <int N, int TB = 8, int SPW = 5, int XW = 0, int KR64 = 56, bool CN = false>
 struct WrenchSmem {
@@ -239,7 +246,9 @@ __device__ __forceinline__ double wg_max1(double v, double* red) {
 // WIDE (the low-latency instantiation: one workgroup's worth of registers): every broadcast read of the T^-1 product in flight
 // at once instead of blocks of four (each block was one more LDS round trip in the iteration's chain), and the 6-term
 // products on two accumulators.
-template <typename R, int CHMAX, int KREG = CHMAX, bool VL = false, bool WIDE = false, bool JL = false, typename KT, int BDN, class Hook, typename LL = std::nullptr_t>
+// RA (MODE = 5, rank-aware steps): a lane whose step took the normalised coordinates E = R R' (phase E) comes with vssel < 0.  Its step's part of K^-1 is
+// D^-1 + V'(T^-1 - I) V: the block-diagonal term is bj[3] w alone, and the step's t = T^-1 v goes on as t - v, v the lane's own row of V w.
+template <typename R, int CHMAX, int KREG = CHMAX, bool VL = false, bool WIDE = false, bool JL = false, bool RA = false, typename KT, int BDN, class Hook, typename LL = std::nullptr_t>
 __device__ __forceinline__ R apply_kinv(R wv, R* wbw, R* tbw, R* vb, int lane, int sg, int ul, bool active_g, int Rrow, int CH,
                                         const KT (&kin)[CHMAX], const R (&vrow_)[6], const R (&vcol_)[6], const R (&bj)[BDN], int vsoff, int vssel,
                                         Hook&& hook, const R* ktail = nullptr, int kts = 0, const R* vlds = nullptr, const R* vldc = nullptr, const double* jl = nullptr, LL ll = LL() WADMM_PARAMS) {
@@ -250,6 +259,9 @@ __device__ __forceinline__ R apply_kinv(R wv, R* wbw, R* tbw, R* vb, int lane, i
     static_assert(BDN == 4 || BDN == 12, "Bd: implicit (4) or explicit row (12)");
     constexpr bool CN = !std::is_same<LL, std::nullptr_t>::value;
     static_assert(!CN || BDN == 4, "contact normals: the implicit form");
+    static_assert(!RA || (BDN == 4 && !CN), "rank-aware steps: the implicit form, flat ground");
+    [[maybe_unused]] const bool ra = RA && vssel < 0;
+    [[maybe_unused]] const int vsx = RA ? (vssel < 0 ? 0 : vssel) : vssel;
     typedef R R4 __attribute__((ext_vector_type(4)));
     typedef R R2 __attribute__((ext_vector_type(2)));
     const int h = ul & 1;
@@ -285,9 +297,11 @@ __device__ __forceinline__ R apply_kinv(R wv, R* wbw, R* tbw, R* vb, int lane, i
         if constexpr (CN) vlin = fma((R)ll[0], vs[3], fma((R)ll[12], vs[4], (R)ll[24] * vs[5]));   // (a force-variable step reads three finite entries behind its own and has bj[3] = 0)
         if constexpr (JL) {   // (the iterations of the fp64 N = 12 instantiation: +1.5 %; N = 8: -2 %, N = 10: nothing)
               // ... J[:, u] from the persistent strip (jl[0], jl[12], jl[24]) instead of three more registers: they were reloaded from scratch
-            xb = bj[3] * (wv - fma(jl[0], vs[0], fma(jl[12], vs[1], fma(jl[24], vs[2], CN ? vlin : vb[vssel]))));   // memory every iteration (a force-variable step has bj[3] = 0: its J does not matter)
+            const R yv_ = fma(jl[0], vs[0], fma(jl[12], vs[1], fma(jl[24], vs[2], CN ? vlin : vb[vsx])));   // memory every iteration (a force-variable step has bj[3] = 0: its J does not matter)
+            xb = bj[3] * (wv - ((RA && ra) ? R(0) : yv_));
         } else {
-            xb = bj[3] * (wv - fma(bj[0], vs[0], fma(bj[1], vs[1], fma(bj[2], vs[2], CN ? vlin : vb[vssel]))));
+            const R yv_ = fma(bj[0], vs[0], fma(bj[1], vs[1], fma(bj[2], vs[2], CN ? vlin : vb[vsx])));
+            xb = bj[3] * (wv - ((RA && ra) ? R(0) : yv_));
         }
     } else {
         R wg[12];
@@ -383,7 +397,9 @@ __device__ __forceinline__ R apply_kinv(R wv, R* wbw, R* tbw, R* vb, int lane, i
     }
     const R tv = tp + dpp_swap1(tp);
     WADMM_T(3);
-    if (h == 0) tbw[6 * sg + (ul >> 1)] = active_g ? tv : R(0);
+    [[maybe_unused]] R vown = R(0);                         // RA: the lane's own row of v = V w, back from the buffer it was published in
+    if constexpr (RA) { const R vo = vb[Rrow]; vown = ra ? vo : R(0); }
+    if (h == 0) tbw[6 * sg + (ul >> 1)] = active_g ? (RA ? tv - vown : tv) : R(0);
     asm volatile("" ::: "memory");
 #pragma unroll
     for (int i = 0; i < 6; ++i) { vcol[i] = VL ? (vldc ? vldc[i * kts] : vlds[(6 + i) * kts]) : vcol_[i]; }
@@ -681,7 +697,11 @@ __device__ __forceinline__ void contact_frame_to_lds(const double (&nr)[3], doub
 // variables f_loc = R' f of every contact's frame R = [t1 t2 n] (contact_frame_to_lds).  The cone rows, D = diag(d_xy, d_xy, d_z), the projection and the whole
 // iteration are the flat ones in those variables; what changes is the wrench column of variable (i, ax), [I_w^-1 (r x R[:, ax]); R[:, ax]] instead of
 // [J[:, u]; e_ax]: J holds the first part, the table L beside it the second, and every place that used e_ax reads (CN ? <L> : <today's expression>).  warm_u
-// comes in and u_out goes out in the world frame.
+// comes in and u_out goes out in the world frame;
+// 5 = solve with rank-aware wrench steps (SRBDQP_FLAG_RANK_AWARE; DESIGN.md, "Rank-aware wrench steps"): a wrench step whose conditioning-guard quantity is not above kRankAwareRatio
+// -- its stance contact points on or near one line -- is never refused: it takes the normalised coordinates of E = R R', R = [L, B G^-1/2; 0, G^1/2] with Sc = L L'
+// (phase E): its g coordinates are the columns of R, its diagonal block of T is R' S R + I, V = R^-1 Y D^-1 and its part of K^-1 is D^-1 + V'(T^-1 - I) V
+// (apply_kinv, RA).  Nothing inverts E.  Steps above that ratio are what they are in MODE 0, and every such place below reads (RA ? ... : ...) or if constexpr (RA).
 template <int N, typename R, typename TIO, int MODE, typename TT = double, int SPW = 5, int XW = 0>
 __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* sm, const double* robots = nullptr, const int nl = N, const double* normals = nullptr) {
     using S = WrenchSmem<N, (int)sizeof(TT), SPW, XW, wrench_kreg64(N, MODE), MODE == 4>;
@@ -691,6 +711,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     static_assert(XW == 0 || (sizeof(TT) == 8 && (MODE == 0 || MODE == 3)), "extra set-up waves: fp64 tiles, solve mode");
     static_assert((S::o_R % 2) == 0 && (S::o_wb % 2) == 0 && (S::o_tb % 2) == 0 && (S::o_vb % 2) == 0, "16-byte alignment");
     static_assert(S::NT <= 2 * NW || S::WQ >= 1, "");
+    static_assert((S::o_zt % 2) == 0, "16-byte alignment of the 6-vectors");
     const double rho_b = unis(SRBDQP_RHO_OF(a, b));   // (per-QP values are wave-uniform: scalar registers, see uni())
     constexpr bool RB = MODE == 2;
     constexpr bool LH = MODE == 3;
@@ -701,6 +722,8 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     constexpr bool CN = MODE == 4;
     static_assert(!CN || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && XW == 0), "contact normals: the fp64 batch instantiation");
     [[maybe_unused]] const double* const LT_ = sm + S::o_L;          // MODE 4: L of every step, from the second barrier on
+    constexpr bool RA = MODE == 5;
+    static_assert(!RA || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && XW == 0), "rank-aware steps: the fp64 batch instantiation");
     const int t = threadIdx.x, lane = t & 63;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     constexpr bool CSUM = XW > 0 && sizeof(TIO) == 8 && MODE == 0 && S::LT <= 256;   // the low-latency instantiations: the completion word may carry a checksum (KArgs::done_cs)
@@ -710,7 +733,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     int* igsz = reinterpret_cast<int*>(sm + S::o_int);            // gsz[N]
     int* igoff = igsz + N;                                        // goff[N + 1]
     int* imisc = igoff + N + 1;                                   // [0] n_g, [1] na
-    int* iwr = imisc + 2;                                         // [N] 1 = the step uses its 6 wrench coordinates
+    int* iwr = imisc + 2;                                         // [N] 1 = the step uses its 6 wrench coordinates (MODE 5: 2 = the normalised ones, set in phase E)
     uint8_t* sct = reinterpret_cast<uint8_t*>(sm + S::o_ct);
     uint8_t* gstep = reinterpret_cast<uint8_t*>(sm + S::o_gs);
     const double* SQ = sm + S::o_sq;
@@ -1122,6 +1145,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     // registers of V and Bd of a wrench step from er = row rl of E^-1 and yv = E^-1 omega_u, omega_u = [J[:, ul]; e_ax]
     // (the callers form the two from the register matrix in phase E, from the LDS triangle for the late formation; E^-1
     // itself must not be captured here: a by-reference capture turns its select chains into an indexed scratch array)
+    [[maybe_unused]] bool ra_step = false;                           // MODE 5: the lane's step took the normalised coordinates
     auto form_vbd = [&](const double (&er)[6], const double (&yv)[6]) __attribute__((always_inline)) {
         const double* Jj = sm + S::o_J + js * 36;
         const int fl[4] = {f0, f1, f2, f3};                        // (selects, not factors: the flags as doubles were kept -- spilled -- across the whole kernel)
@@ -1139,6 +1163,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
 #pragma unroll
         for (int r = 0; r < 6; ++r) vcol[r] = (VS)(wu * yv[r]);
         bjv[0] = j0; bjv[1] = j1; bjv[2] = j2; bjv[3] = wu; bsel = 3 + ax;
+        if constexpr (RA) { if (ra_step) bsel = -4096; }   // (vssel < 0: apply_kinv's mark of a lane on a normalised step)
         if constexpr (BD_EXPLICIT && !BD_LAST) form_bd(yv);
     };
     // ... of a force-variable step: V = the selection of the stance variables, Bd = 0
@@ -1154,6 +1179,14 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             for (int u2 = 0; u2 < 12; ++u2) bdrow[u2] = BS(0);
         }
     };
+    if constexpr (RA) {
+        // the gradient and the warm start's two values wait in LDS while the blocks are formed, in tables that are dead by now (G x^0, T1 / T2, the warm start itself;
+        // own entries only: no barrier): in registers across this phase they ended in scratch memory (20 bytes per lane at N = 10, 12 at N = 20)
+        static_assert(S::o_t1 + n <= S::o_mt && !S::GX_LATE, "three dead tables of 12 N doubles");
+        if (stepok) { sm[S::o_gx + uvar] = qv; sm[S::o_t1 + uvar] = px0; sm[S::o_eh + uvar] = x_init; }
+        qv = 0.0; px0 = 0.0; x_init = 0.0;
+        asm volatile("" ::: "memory");
+    }
     if (!TSPLIT || w < NWS) {
         const double* Jj = sm + S::o_J + js * 36;
         const int fl[4] = {f0, f1, f2, f3};
@@ -1205,7 +1238,8 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             double Ei[6][6];
             bool okE = true;
             // the conditioning guard: every pivot against GR times the diagonal entry of E in its row (orc.step_pivot_ratio: the same quantity, the same constants)
-            constexpr double GR = (sizeof(R) == 4) ? kGuardRatioF32 : kGuardRatioF64;
+            // (MODE 5: nothing is refused here -- the same quantity against kRankAwareRatio decides which steps take the normalised coordinates)
+            constexpr double GR = RA ? kRankAwareRatio : ((sizeof(R) == 4) ? kGuardRatioF32 : kGuardRatioF64);
             {
                 // G = n_c diag(1 / d_xy, 1 / d_xy, 1 / d_z) with n_c = 3 or 4 stance contacts (a wrench step): its inverse without a division
                 const double inc = ((f0 + f1 + f2 + f3) == 4) ? 0.25 : (1.0 / 3.0);
@@ -1245,27 +1279,57 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                         Sc[p][q] = v;
                     }
                 // Sc = L L' (lower), Li = L^-1
-                auto rs = [&](double d) -> double {
+                // (MODE 5: a pivot at rounding level -- not above kDropRatio times the diagonal entry of E in its row -- takes reciprocal root 0: a zero column of L)
+                auto rs = [&](double d, [[maybe_unused]] double ref) -> double {
                     if constexpr (XW > 0) return (d > 0.0) ? fast_rsqrt2(d) : 0.0;
+                    else if constexpr (RA) return (d > kDropRatio * ref) ? 1.0 / sqrt(d) : 0.0;
                     else return 1.0 / sqrt(d);
                 };
                 okE = okE && (Sc[0][0] > GR * Em[0][0]);
-                const double r0 = rs(Sc[0][0]);
+                const double r0 = rs(Sc[0][0], Em[0][0]);
                 const double l10 = Sc[0][1] * r0, l20 = Sc[0][2] * r0;
                 const double d1 = fma(-l10, l10, Sc[1][1]);
                 okE = okE && (d1 > GR * Em[1][1]);
-                const double r1 = rs(d1);
+                const double r1 = rs(d1, Em[1][1]);
                 const double l21 = fma(-l20, l10, Sc[1][2]) * r1;
                 const double d2 = fma(-l21, l21, fma(-l20, l20, Sc[2][2]));
                 okE = okE && (d2 > GR * Em[2][2]);
-                const double r2 = rs(d2);
+                const double r2 = rs(d2, Em[2][2]);
                 const double m10 = -l10 * r0 * r1;                       // Li[1][0]
                 const double m21 = -l21 * r1 * r2;                       // Li[2][1]
                 const double m20 = -(l20 * r0 + l21 * m10) * r2;         // Li[2][0]
+                if constexpr (RA) {
+                    // a step at or below kRankAwareRatio: the columns of R = [L, B G^-1/2; 0, G^1/2] go to ZT from the step's first lane (the 6-vectors of the step's g
+                    // coordinates: phase H needs nothing else; B G^-1/2 = (B G^-1) G^1/2), and Ei below becomes R^-1 = [L^-1, -L^-1 B G^-1; 0, G^-1/2] -- Li in
+                    // the place of Sc^-1 = Li' Li (forward substitution through L; a dropped pivot's row is 0) -- so that what follows -- row rl and (row r) . omega_u
+                    // of the matrix -- forms V = R^-1 Y D^-1 as it forms E^-1 Y D^-1
+                    ra_step = !okE;
+                    if (ra_step && stepok && ul == 0) {
+                        typedef double dv2 __attribute__((ext_vector_type(2)));
+                        const double gxy = 1.0 / sqrt(ig[0]), gq_[3] = {gxy, gxy, 1.0 / sqrt(ig[2])};   // G^1/2
+                        const double l00 = Sc[0][0] * r0, l11 = d1 * r1, l22 = d2 * r2;
+                        dv2* Z2 = reinterpret_cast<dv2*>(ZT + 6 * igoff[js]);                     // (6-vectors of the step's 6 coordinates: 16-byte aligned)
+                        Z2[0] = (dv2){l00, l10}; Z2[1] = (dv2){l20, 0.0}; Z2[2] = (dv2){0.0, 0.0};
+                        Z2[3] = (dv2){0.0, l11}; Z2[4] = (dv2){l21, 0.0}; Z2[5] = (dv2){0.0, 0.0};
+                        Z2[6] = (dv2){0.0, 0.0}; Z2[7] = (dv2){l22, 0.0}; Z2[8] = (dv2){0.0, 0.0};
+#pragma unroll
+                        for (int a2 = 0; a2 < 3; ++a2) {
+                            Z2[9 + 3 * a2] = (dv2){BG[0][a2] * gq_[a2], BG[1][a2] * gq_[a2]};
+                            Z2[10 + 3 * a2] = (dv2){BG[2][a2] * gq_[a2], (a2 == 0) ? gq_[a2] : 0.0};
+                            Z2[11 + 3 * a2] = (dv2){(a2 == 1) ? gq_[a2] : 0.0, (a2 == 2) ? gq_[a2] : 0.0};
+                        }
+                        iwr[js] = 2;
+                    }
+                }
                 double Si[3][3];                                         // Sc^-1 = Li' Li
                 Si[0][0] = fma(r0, r0, fma(m10, m10, m20 * m20)); Si[0][1] = fma(m10, r1, m20 * m21); Si[0][2] = m20 * r2;
                 Si[1][1] = fma(r1, r1, m21 * m21); Si[1][2] = m21 * r2; Si[2][2] = r2 * r2;
                 Si[1][0] = Si[0][1]; Si[2][0] = Si[0][2]; Si[2][1] = Si[1][2];
+                if constexpr (RA) {   // (Li, lower triangular)
+                    Si[0][0] = ra_step ? r0 : Si[0][0]; Si[1][1] = ra_step ? r1 : Si[1][1]; Si[2][2] = ra_step ? r2 : Si[2][2];
+                    Si[1][0] = ra_step ? m10 : Si[1][0]; Si[2][0] = ra_step ? m20 : Si[2][0]; Si[2][1] = ra_step ? m21 : Si[2][1];
+                    Si[0][1] = ra_step ? 0.0 : Si[0][1]; Si[0][2] = ra_step ? 0.0 : Si[0][2]; Si[1][2] = ra_step ? 0.0 : Si[1][2];
+                }
                 double C12[3][3];                                        // -Sc^-1 B G^-1
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
@@ -1274,7 +1338,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
 #pragma unroll
-                    for (int q = 0; q < 3; ++q) { Ei[p][q] = Si[p][q]; Ei[p][3 + q] = C12[p][q]; Ei[3 + q][p] = C12[p][q]; }
+                    for (int q = 0; q < 3; ++q) { Ei[p][q] = Si[p][q]; Ei[p][3 + q] = C12[p][q]; Ei[3 + q][p] = C12[p][q]; }   // (MODE 5, a normalised step: R^-1 has no lower left block -- masked where it is stored and read, below)
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
 #pragma unroll
@@ -1282,11 +1346,12 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                         double v = CN ? Gi[p][q] : ((p == q) ? ig[p] : 0.0);   // G^-1 - (B G^-1)' C12
 #pragma unroll
                         for (int k2 = 0; k2 < 3; ++k2) v = fma(-BG[k2][p], C12[k2][q], v);
+                        if constexpr (RA) v = ra_step ? ((p == q) ? sqrt(ig[p]) : 0.0) : v;   // G^-1/2
                         Ei[3 + p][3 + q] = v; Ei[3 + q][3 + p] = v;
                     }
             }
             ESTAMP(a, 2);
-            if (!okE && stepok && ul == 0) sm[S::o_misc] = 1.0;   // stance contact points on or near one line: E singular or too ill conditioned to invert
+            if constexpr (!RA) { if (!okE && stepok && ul == 0) sm[S::o_misc] = 1.0; }   // stance contact points on or near one line: E singular or too ill conditioned to invert
             // E^-1 goes to LDS WHOLE, from the first lane of the step, and every lane reads what it needs back (its row; one column entry per row) behind a
             // wave-local wait -- the 12 lanes of a step sit in one wave.  Until round 5 each lane picked row rl and column 3 + ax out of its register copy with
             // select chains: hipcc turned them into divergent branches around the entries' own arithmetic (37 exec-masked blocks, each run by every wave for every
@@ -1297,16 +1362,21 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
 #pragma unroll
                 for (int r = 0; r < 6; ++r)
 #pragma unroll
-                    for (int c2 = 0; c2 < 3; ++c2) EI2[3 * r + c2] = (d2){Ei[r][2 * c2], Ei[r][2 * c2 + 1]};
+                    for (int c2 = 0; c2 < 3; ++c2) {
+                        // (MODE 5, a normalised step: its block of T is R' S R + I -- the identity where E^-1 goes; formed early, the rows of V first read R^-1 here, below)
+                        if constexpr (RA && VBD_LATE) { const d2 id_ = (d2){(2 * c2 == r) ? 1.0 : 0.0, (2 * c2 + 1 == r) ? 1.0 : 0.0}, ei_ = (d2){Ei[r][2 * c2], Ei[r][2 * c2 + 1]}; EI2[3 * r + c2] = ra_step ? id_ : ei_; }
+                        else if constexpr (RA) EI2[3 * r + c2] = (r >= 3 && c2 < 2) ? (d2){(2 * c2 < 3 && ra_step) ? 0.0 : Ei[r][2 * c2], (2 * c2 + 1 < 3 && ra_step) ? 0.0 : Ei[r][2 * c2 + 1]} : (d2){Ei[r][2 * c2], Ei[r][2 * c2 + 1]};
+                        else EI2[3 * r + c2] = (d2){Ei[r][2 * c2], Ei[r][2 * c2 + 1]};
+                    }
                 if constexpr (VBD_LATE) {
                     double* E4 = sm + S::o_e4 + 21 * js;
 #pragma unroll
                     for (int r = 0; r < 6; ++r)
 #pragma unroll
-                        for (int c = 0; c <= r; ++c) E4[(r * (r + 1)) / 2 + c] = Ei[r][c];
+                        for (int c = 0; c <= r; ++c) E4[(r * (r + 1)) / 2 + c] = (RA && r >= 3 && c < 3) ? Ei[c][r] : Ei[r][c];   // (MODE 5: the upper right block -- R^-1 has no lower left one, and E^-1 is symmetric)
                 }
             }
-            if (stepok) {
+            if (stepok && !(RA && ra_step)) {
 #pragma unroll
                 for (int i = 0; i < 3; ++i) ZT[6 * Rrow + 3 * h + i] = (3 * h + i == rl) ? 1.0 : 0.0;
             }
@@ -1319,9 +1389,20 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
 #pragma unroll
                 for (int r = 0; r < 6; ++r) {
                     if constexpr (CN) { const double* Lu = LT_ + js * 36 + ul; yv[r] = Ei[r][0] * j0 + Ei[r][1] * j1 + Ei[r][2] * j2 + EI[6 * r + 3] * Lu[0] + EI[6 * r + 4] * Lu[12] + EI[6 * r + 5] * Lu[24]; }
+                    else if constexpr (RA) yv[r] = (r >= 3 && ra_step) ? EI[6 * r + 3 + ax] : Ei[r][0] * j0 + Ei[r][1] * j1 + Ei[r][2] * j2 + EI[6 * r + 3 + ax];
                     else yv[r] = Ei[r][0] * j0 + Ei[r][1] * j1 + Ei[r][2] * j2 + EI[6 * r + 3 + ax];
                 }
                 form_vbd(er, yv);
+                if constexpr (RA) {   // R^-1 is read (every lane of the step is in this wave, and its LDS operations complete in order): the identity for phase H
+                    if (ra_step && stepok && ul == 0) {
+                        typedef double d2 __attribute__((ext_vector_type(2)));
+                        d2* EI2 = reinterpret_cast<d2*>(EI);
+#pragma unroll
+                        for (int r = 0; r < 6; ++r)
+#pragma unroll
+                            for (int c2 = 0; c2 < 3; ++c2) EI2[3 * r + c2] = (d2){(2 * c2 == r) ? 1.0 : 0.0, (2 * c2 + 1 == r) ? 1.0 : 0.0};
+                    }
+                }
             }
             ESTAMP(a, 3);
         } else {
@@ -1339,6 +1420,10 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         }
     }
     WAVE_ARRIVE(a, w, lane, 13);
+    if constexpr (RA) {
+        asm volatile("" ::: "memory");
+        if (stepok) { qv = sm[S::o_gx + uvar]; px0 = sm[S::o_t1 + uvar]; x_init = sm[S::o_eh + uvar]; }
+    }
     __syncthreads();
     if constexpr (TSPLIT) gradient_and_warm_start();
     if constexpr (MODE == 1) { if (sm[S::o_misc] != 0.0) { if (t == 0) a.ub_out[(size_t)b * (N + 1) + N] = -1.0; return; } }
@@ -1731,6 +1816,23 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         auto tri = [&](int r, int c) -> double { const int hi = r > c ? r : c, lo = r > c ? c : r; return E4[(hi * (hi + 1)) / 2 + lo]; };
         const double* Jj = sm + S::o_J + js * 36;
         const double j0 = Jj[ul], j1 = Jj[12 + ul], j2 = Jj[24 + ul];
+        if constexpr (RA) {
+            // a normalised step's triangle holds R^-1 = [L^-1, X; 0, G^-1/2] -- L^-1 and the diagonal where they are, X transposed in the lower left block:
+            // entry (r, c) is the triangle's where R^-1 has one, and 0 in the lower left block and above the diagonal of L^-1
+            ra_step = iwr[js] == 2;
+            if (er) {
+#pragma unroll
+                for (int c = 0; c < 6; ++c) { const double v = tri(rl, c); er[c] = (ra_step && c < 3 && (rl >= 3 || rl < c)) ? 0.0 : v; }
+            }
+#pragma unroll
+            for (int r = 0; r < 6; ++r) {
+                double tm[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { const double jc = (c == 0) ? j0 : ((c == 1) ? j1 : j2), v = tri(r, c) * jc; tm[c] = (r >= 3 || c > r) ? (ra_step ? 0.0 : v) : v; }
+                yv[r] = tm[0] + tm[1] + tm[2] + tri(r, 3 + ax);
+            }
+            return;
+        }
         if (er) {
 #pragma unroll
             for (int c = 0; c < 6; ++c) er[c] = tri(rl, c);
@@ -1786,6 +1888,14 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             for (int i = 0; i < 6; ++i) { pr[i * n] = vrow[i]; pc[i * n] = vcol[i]; }   // own entries only: no barrier needed
         }
     }
+    if constexpr (RA && !VBD_LATE) {
+        // (the long horizons, V and Bd formed in phase E: J[:, u] and 1 / D_u of the lane's variable are formed again here -- a read of the persistent strip and a
+        //  select -- instead of waiting in eight registers across the tile phases: the N = 20 instantiation, at the register limit like its MODE = 0 twin, kept one
+        //  of them in scratch memory)
+        const double* Jj = sm + S::o_J + js * 36 + ul;
+        const double wu = (active_u && wrench) ? ((ax < 2) ? idxy : idz) : 0.0;
+        bjv[0] = wrench ? Jj[0] : 0.0; bjv[1] = wrench ? Jj[12] : 0.0; bjv[2] = wrench ? Jj[24] : 0.0; bjv[3] = wu;
+    }
     const int vssel = vsoff + bsel;
     typename std::conditional<CN, const double*, std::nullptr_t>::type llds = nullptr;   // CN: L[:, u] of the lane's variable (apply_kinv)
     if constexpr (CN) llds = LT_ + js * 36 + ul;
@@ -1818,6 +1928,8 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
 #pragma unroll
                 for (int i = 0; i < 12; ++i) bdd[i] = (double)bdrow[i];
                 xq = apply_kinv<double, CHMAX>(-qv, wbw, tbw, vb, lane, sg, ul, active_g, Rrow, CH, kin64, vrd, vcd, bdd, vsoff, vssel, [] {});
+            } else if constexpr (RA) {   // (vssel < 0 marks the lanes of a normalised step)
+                xq = apply_kinv<double, CHMAX, KREG, false, false, false, true>(-qv, wbw, tbw, vb, lane, sg, ul, active_g, Rrow, CH, kin64, vrd, vcd, bjv, vsoff, vssel, [] {}, ktail, LT);
             } else if constexpr (CN) {   // (L[:, u] behind the defaults; ktail / LT unused where the whole half row is in registers)
                 xq = apply_kinv<double, CHMAX, KREG>(-qv, wbw, tbw, vb, lane, sg, ul, active_g, Rrow, CH, kin64, vrd, vcd, bjv, vsoff, vssel, [] {}, ktail, LT, nullptr, nullptr, nullptr, llds);
             } else if constexpr (KREG < CHMAX) {
@@ -1940,7 +2052,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         for (int k = 1; k <= a.max_iter + 1 && !done; ++k) {
             WADMM_T(0);
             R* vb = vbuf + (k & 1) * S::VB;
-            const R kw = apply_kinv<R, CHMAX, KREG, VL, (XW > 0 && CHMAX <= 36), (VL && CHMAX > 30)>(wv, wbw, tbw, vb, lane, sg, ul, active_g, Rrow, CH, kin, vr, vc, bd, vsoff, vssel, [&] {
+            const R kw = apply_kinv<R, CHMAX, KREG, VL, (XW > 0 && CHMAX <= 36), (VL && CHMAX > 30), RA>(wv, wbw, tbw, vb, lane, sg, ul, active_g, Rrow, CH, kin, vr, vc, bd, vsoff, vssel, [&] {
                 if (pending) {   // decision of the check made at iteration k - 1 (its maxima were published by this barrier)
                     const float* buf = redf + ((nchk - 1) & 1) * 4 * NWS;
                     float v0 = buf[0], v1 = buf[1], v2 = buf[2], v3 = buf[3];
@@ -2272,6 +2384,25 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, 5, 0>::BT), WPS) void srbdqp_wren
     }
     if ((!a.count_ptr || (int)blockIdx.x < *a.count_ptr) && !SRBDQP_RESTART_SKIP(a, SRBDQP_QP_INDEX(a)))
         wrench_qp<N, double, double, 4, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm, nullptr, N, normals);
+    signal_done(a);
+}
+
+// ... MODE = 5: rank-aware wrench steps (SRBDQP_FLAG_RANK_AWARE).  fp64, batch form only, one argument; a name of its own with two template arguments, as MODE = 4
+// (tests/test_any_horizon_cpu.py pins the list of srbdqp_wrench_kernel's instantiations).  (The prologue word for word, as above.)
+template <int N, int WPS>
+__global__ __launch_bounds__((WrenchSmem<N, 8, 5, 0>::BT), WPS) void srbdqp_wrench_ra_kernel(KArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    if ((int)blockIdx.x >= a.B) return;
+    if (a.tile_sel) {
+        const uint32_t* cf = reinterpret_cast<const uint32_t*>(a.contact + (size_t)SRBDQP_QP_INDEX(a) * (N * 4));   // 4 flags per step
+        const int lane = threadIdx.x & 63;
+        const uint32_t v = cf[lane < N ? lane : 0];
+        const int nc = ((v & 0xffu) ? 1 : 0) + ((v & 0xff00u) ? 1 : 0) + ((v & 0xff0000u) ? 1 : 0) + ((v & 0xff000000u) ? 1 : 0);
+        const bool wrench_only = __ballot(lane < N && (nc == 1 || nc == 2)) == 0ull;
+        if (wrench_only != (a.tile_sel == 1)) return;
+    }
+    if ((!a.count_ptr || (int)blockIdx.x < *a.count_ptr) && !SRBDQP_RESTART_SKIP(a, SRBDQP_QP_INDEX(a)))
+        wrench_qp<N, double, double, 5, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm);
     signal_done(a);
 }
 

@@ -95,7 +95,10 @@ class BatchMPC:
     """B independent SRBD convex-MPC QPs per call.  One instance <-> one HIP stream <-> one thread."""
 
     def __init__(self, horizon: int = 10, dt: float = 0.04, device: int = 0, kernel: int = _lib.KERNEL_AUTO,
-                 timing: bool = False, **overrides):
+                 timing: bool = False, rank_aware: bool = False, **overrides):
+        """rank_aware=True sets SRBDQP_FLAG_RANK_AWARE (include/srbdqp.h): on the general kernel, steps whose stance contact points lie on or near one line --
+        feet in tandem, point feet -- are solved in rank-aware coordinates instead of ending the QP with status -1 (fp64 solves, N <= 20, flat ground, one
+        robot).  flags=_lib.FLAG_RANK_AWARE does the same."""
         lib = _lib.load()
         cfg = _lib.default_config()
         cfg.horizon = int(horizon)
@@ -116,6 +119,8 @@ class BatchMPC:
                 setattr(cfg, k, type(getattr(cfg, k))(v))
         if cfg.horizon not in _lib.HORIZONS:        # any other horizon 1 ... 24: the general kernel's live-horizon mode (include/srbdqp.h, SRBDQP_FLAG_ANY_HORIZON)
             cfg.flags |= _lib.FLAG_ANY_HORIZON
+        if rank_aware:                              # (after the overrides: flags= and the keyword add up)
+            cfg.flags |= _lib.FLAG_RANK_AWARE
         self.cfg = cfg
         self._lib = lib
         self._h = C.c_void_p()
@@ -508,8 +513,10 @@ class RaggedMPC:
 class MPC:
     """Drop-in for ``srbd_mpc.mpc.MPC`` on the hot path (run_simulation.py:169-170,73-82,96,103,106)."""
 
-    def __init__(self, dt: float = 0.04, horizon: int = 10, device: int = 0, strict: bool = True, **overrides):
-        """Every solve starts from zero.  (Rounds 1-4 had `warm_start=True`: the previous plan and duals shifted by one step.  Removed in round 5 -- on this
+    def __init__(self, dt: float = 0.04, horizon: int = 10, device: int = 0, strict: bool = True, rank_aware: bool = False, **overrides):
+        """rank_aware=True: the engine is created with SRBDQP_FLAG_RANK_AWARE (BatchMPC) -- a horizon with feet in tandem or point feet on every step gets an
+        answer from update() (the general kernel's batch instantiation through the HIP launch, at its latency) instead of status -1.
+        Every solve starts from zero.  (Rounds 1-4 had `warm_start=True`: the previous plan and duals shifted by one step.  Removed in round 5 -- on this
         ADMM (sigma -> 0, alpha = 1.6) an error of the starting point decays by |1 - alpha| = 0.6 per iteration whatever else happens, and the dual residual
         sees it through P: the shifted plan is 0.2 |x*| from the new optimum but ~400 |q| from it through P (zero: 1 |q|), i.e. log(400) / log(1 / 0.6) = 12
         iterations WORSE than zero: 41 against 30 on closed loops, profiles/r05_warm_start_sweep.txt, DESIGN.md section 2.  The C-ABI keeps warm_u / warm_y.)
@@ -531,7 +538,7 @@ class MPC:
         self._solve_time = 0.0                  # seconds spent in the last solve (the node's solve-time statistic)
         self._fcb = None                        # the CPython binding of srbdqp_update_f64 (csrc/fastcall.c), once bound
         self._device = device
-        self._overrides = overrides
+        self._overrides = dict(overrides, rank_aware=True) if rank_aware else overrides
         self._engine: Optional[BatchMPC] = None
         self._u_opt = None
         self._x_opt = None

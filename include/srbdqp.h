@@ -48,7 +48,8 @@ extern "C" {
                                      On the general kernel (SRBDQP_KERNEL_WRENCH) also: the stance contact points of a step with three or four
                                      stance contacts lie on or near one line (feet in tandem, heel and toe at one point).  The QP is rejected before
                                      its factorisation: u, y and iters are 0, x is the roll-out of zero forces, the other QPs of the batch are not
-                                     affected, and no restart pass or deferred continuation runs it again.  See SRBDQP_KERNEL_WRENCH. */
+                                     affected, and no restart pass or deferred continuation runs it again.  See SRBDQP_KERNEL_WRENCH;
+                                     SRBDQP_FLAG_RANK_AWARE is the way past this limit (fp64 calls). */
 #define SRBDQP_CONTACT_BOUND (-2) /* more stance contacts in a step than srbdqp_config.max_contacts_per_step allows; forces 0 */
 
 /* srbdqp_config.flags */
@@ -91,6 +92,21 @@ extern "C" {
                                          srbdqp_solve_prepared_f64 (the two-phase call is the one-wave pipeline, built per horizon), srbdqp_assemble_f64 /
                                          srbdqp_assemble_wrench_f64 (the dumps describe an instantiation's own layout: dump at a tabulated horizon), and
                                          srbdqp_set_robots / _device with records (robots with a live horizon would be a fourth copy of every instantiation). */
+#define SRBDQP_FLAG_RANK_AWARE 256 /* the general kernel solves steps whose stance contact points lie on or near one line (feet in tandem, point feet) instead of
+                                     ending the QP with SRBDQP_NUMERICAL: a wrench step whose pivot ratio (the conditioning guard's quantity, see
+                                     SRBDQP_KERNEL_WRENCH) is not above 1e-4 -- everything the guard refuses, and the steps within a factor 400 above it, where
+                                     E^-1 still gives the forces but no longer the dual residual -- takes rank-aware coordinates: E = R R', T = R' S R + I,
+                                     nothing inverts E.  The steps above that ratio (every healthy stance) stay exactly as they are; a QP may mix both.  N in {4, 8, 10, 12, 16, 20}, flat ground, srbdqp_config's single robot.  Without the flag nothing changes.  With it
+                                       - srbdqp_solve_batch_f64 / _device_f64 calls that run on the general kernel (SRBDQP_KERNEL_WRENCH, and what AUTO sends there)
+                                         launch its rank-aware instantiation in every pass -- first pass, restart passes, SRBDQP_FLAG_DEFER_TAIL passes, a
+                                         schedule hint's dispatch order -- (srbdqp_kernel_name: wrench_f64_n<N>_ra); calls that AUTO sends to the dense kernels are
+                                         unchanged (they never had the limit);
+                                       - srbdqp_solve_staged_f64 / srbdqp_update_f64, when they run the general kernel, run that batch instantiation through the HIP
+                                         launch, at its latency (srbdqp_batch1_launch_path: "hip: ..." with this reason);
+                                       - these return SRBDQP_E_INVALID with a message that names the flag: the _f32 calls, srbdqp_assemble_wrench_f64,
+                                         srbdqp_set_robots / _device and srbdqp_set_contact_normals / _device with data, srbdqp_create at N = 24 and at a live
+                                         horizon of SRBDQP_FLAG_ANY_HORIZON, and srbdqp_ragged_create.
+                                     The other causes of SRBDQP_NUMERICAL stay: non-finite inputs, a non-positive pivot of T. */
 
 /* srbdqp_config.kernel: which implementation of the hot path runs */
 #define SRBDQP_KERNEL_AUTO  0     /* the fastest parity-green kernel */
@@ -112,7 +128,8 @@ extern "C" {
                                      came from and ends the QP with SRBDQP_NUMERICAL below 2.5e-7 (fp64 calls) or 3e-5 (_f32 calls): the ratio is
                                      about 0.3 ... 3 times the square of the points' distance from the line in metres (0.9 mm / 1 cm for feet in
                                      tandem).  A QP that comes back SOLVED keeps the usual accuracy (MAX_ITER is the best iterate, as ever).  The dense kernels (COMPACT, SPLIT, WAVE, with
-                                     max_contacts_per_step set to the schedule's) have no such limit and solve these inputs. */
+                                     max_contacts_per_step set to the schedule's) have no such limit and solve these inputs, and so does the general kernel
+                                     itself on a handle created with SRBDQP_FLAG_RANK_AWARE (fp64 calls, N <= 20). */
 
 /* Everything `MPC.__init__(dt)` / `MPC.init_matrices()` hold (run_simulation.py:169-170).  Values the
  * reference keeps inside the absent module are this build's documented choices. */
