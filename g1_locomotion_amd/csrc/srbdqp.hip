@@ -284,6 +284,17 @@ int set_lds_once(srbdqp_handle* h, K kernel, size_t lds) {
     return SRBDQP_OK;
 }
 
+// one launch through HIP: the kernel's dynamic-LDS limit (set_lds_once), the name srbdqp_kernel_name reports (nullptr: as it is), the launch, its error
+template <typename K, typename... A>
+int launch_kernel(srbdqp_handle* h, K kernel, const char* kname, dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+    const int rc = set_lds_once(h, kernel, lds);
+    if (rc != SRBDQP_OK) return rc;
+    if (kname) h->kname = kname;
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    HIP_TRY(h, hipGetLastError());
+    return SRBDQP_OK;
+}
+
 // Batches of at least this many QPs of the small instantiations (<= 64 presolved variables) run with one wave per QP
 // (launch_wave); the staged (completion-word) path and the big instantiations use the 4-wave kernel.  Until round 4 the cross-over of the per-call time was 512
 // QPs; with the rho restart on at every batch size (in place on the one-wave kernel, one more launch per pass on the 4-wave one) the one-wave kernel is the
@@ -594,59 +605,107 @@ int launch_compact(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t 
     }
     constexpr size_t lds = srbdqp::CompactTraits<N, MAXS>::lds_bytes;
     static const std::string nm = "compact_f64_n" + std::to_string(N) + "_s" + std::to_string(MAXS);
-    h->kname = nm.c_str();
-    if (a.mode == 1) {   // assembly dump: the same kernel, stopped before its factorisation
-        int rc = set_lds_once(h, &srbdqp::srbdqp_compact_kernel<N, MAXS, false, true>, lds);
-        if (rc != SRBDQP_OK) return rc;
-        hipLaunchKernelGGL((srbdqp::srbdqp_compact_kernel<N, MAXS, false, true>), dim3((unsigned)a.B), dim3(srbdqp::kThreads), lds, st, a);
-        return SRBDQP_OK;
-    }
+    const dim3 grid((unsigned)a.B), block(srbdqp::kThreads);
+    if (a.mode == 1)     // assembly dump: the same kernel, stopped before its factorisation
+        return launch_kernel(h, &srbdqp::srbdqp_compact_kernel<N, MAXS, false, true>, nm.c_str(), grid, block, lds, st, a);
     if constexpr (MAXS == 2 && srbdqp::SplitWs<N, MAXS>::supported) {
         // staged batch-1 path (completion word): four waves for the set-up, then the one-wave iteration on wave 0 (srbdqp_compact.hpp, TAIL1) --
         // compiled for one workgroup's worth of registers.  tools/latency_patterns.py, tools/batch1_kernel_probe.py
         if (a.done_flag && a.B <= kTail1MaxBatch && !(h->cfg.flags & SRBDQP_FLAG_NO_LAT)) {
             constexpr size_t lds1 = srbdqp::CompactTraits<N, MAXS>::lds_bytes_tail1;
             static_assert(lds1 <= 163840 && srbdqp::SplitWs<N, MAXS>::KS <= 64, "TAIL1: K^-1 rows behind the kernel's own LDS");
-            int rc1 = set_lds_once(h, &srbdqp::srbdqp_compact_kernel<N, MAXS, false, false, true>, lds1);
-            if (rc1 != SRBDQP_OK) return rc1;
             static const std::string nml = nm + "_lat";
-            h->kname = nml.c_str();
             srbdqp::StagedIn<N> in;
             if (!a.count_ptr && staged_inline_inputs<N>(h, c, a, in)) {
-                rc1 = set_lds_once(h, &srbdqp::srbdqp_compact_kernel_in<N, MAXS>, lds1);
-                if (rc1 != SRBDQP_OK) return rc1;
+                // (both kernels' LDS limits and the name BEFORE the AQL attempt, which needs none of them: HIP has loaded the kernels whichever way a later
+                //  launch of this handle goes)
+                int rc = set_lds_once(h, &srbdqp::srbdqp_compact_kernel<N, MAXS, false, false, true>, lds1);
+                if (rc == SRBDQP_OK) rc = set_lds_once(h, &srbdqp::srbdqp_compact_kernel_in<N, MAXS>, lds1);
+                if (rc != SRBDQP_OK) return rc;
+                h->kname = nml.c_str();
                 KArgs ai = a;
                 ai.inline_in = 1;
                 staged_done_checksum(h, ai);
                 if (aql_launch_in(h, c, st, "_ZN6srbdqp24srbdqp_compact_kernel_inILi%dELi%dEEEvNS_5KArgsENS_8StagedInIXT_EEE.kd", N, MAXS, ai, in, srbdqp::kThreads, lds1)) return SRBDQP_OK;
-                rc1 = aql_quiesce(h);
-                if (rc1 != SRBDQP_OK) return rc1;
-                hipLaunchKernelGGL((srbdqp::srbdqp_compact_kernel_in<N, MAXS>), dim3(1), dim3(srbdqp::kThreads), lds1, st, ai, in);
-                return SRBDQP_OK;
+                rc = aql_quiesce(h);
+                if (rc != SRBDQP_OK) return rc;
+                return launch_kernel(h, &srbdqp::srbdqp_compact_kernel_in<N, MAXS>, nullptr, dim3(1), block, lds1, st, ai, in);
             }
-            hipLaunchKernelGGL((srbdqp::srbdqp_compact_kernel<N, MAXS, false, false, true>), dim3((unsigned)a.B), dim3(srbdqp::kThreads), lds1, st, a);
-            return SRBDQP_OK;
+            return launch_kernel(h, &srbdqp::srbdqp_compact_kernel<N, MAXS, false, false, true>, nml.c_str(), grid, block, lds1, st, a);
         }
     }
-    int rc = set_lds_once(h, &srbdqp::srbdqp_compact_kernel<N, MAXS>, lds);
-    if (rc != SRBDQP_OK) return rc;
-    hipLaunchKernelGGL((srbdqp::srbdqp_compact_kernel<N, MAXS>), dim3((unsigned)a.B), dim3(srbdqp::kThreads), lds, st, a);
-    return SRBDQP_OK;
+    return launch_kernel(h, &srbdqp::srbdqp_compact_kernel<N, MAXS>, nm.c_str(), grid, block, lds, st, a);
 }
 
-// a call that has no live-horizon form, on a handle whose horizon has no instantiation of its own (SRBDQP_FLAG_ANY_HORIZON; include/srbdqp.h has the reasons)
-int live_refuse(srbdqp_handle* h, const char* what) {
-    h->err = std::string(what) + ": refused on a handle whose horizon " + std::to_string(h->cfg.horizon) + " was admitted by SRBDQP_FLAG_ANY_HORIZON: only the fp64 batch, "
-             "ragged and staged solves run a live horizon (the general kernel's fp64 batch instantiation for N = " + std::to_string(h->live_nstar) + ")";
+// ---- the variants of the general kernel: which one a handle is in, and which call has a form for it ----
+// A handle is in exactly one of five states.  Live and RankAware are fixed by srbdqp_create; Robots and Normals come and go with the setters (a clearing call --
+// NULL, 0 -- is accepted in every state).  No two hold at once:
+//   Live x RankAware                      srbdqp_create refuses SRBDQP_FLAG_RANK_AWARE at a live horizon
+//   Robots x Live, Robots x RankAware     robots_check_handle (srbdqp_set_robots / _device, and the ragged pair for every bucket)
+//   Normals x Live, Normals x RankAware   normals_check_handle (srbdqp_set_contact_normals / _device)
+//   Robots x Normals                      each of the two checks refuses while the other is set
+// (srbdqp_ragged_create refuses SRBDQP_FLAG_RANK_AWARE, and a ragged object has no normals: its buckets are Plain, Robots or Live.)
+enum class Variant { Plain, Robots, Normals, Live, RankAware };
+
+inline Variant variant_of(const srbdqp_handle* h) {
+    if (h->robots) return Variant::Robots;
+    if (h->normals) return Variant::Normals;
+    if (h->live_nstar) return Variant::Live;
+    if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) return Variant::RankAware;
+    return Variant::Plain;
+}
+
+// `what` -- a C-ABI call by its name, or a kind of solve -- has no form for a handle in state v: the message (include/srbdqp.h has the reasons and the lists;
+// the four texts are quoted in INTEGRATION.md and matched by the tests) and SRBDQP_E_INVALID
+int refuse(srbdqp_handle* h, Variant v, const char* what) {
+    const std::string w(what);
+    switch (v) {
+    case Variant::Plain: h->err = w + ": refused"; break;            // (never: every call has the plain form)
+    case Variant::Robots:
+        h->err = w + ": refused while per-QP robot records are set (srbdqp_set_robots): only the fp64 batch and ragged solves on the general kernel read "
+                     "them -- one robot for every QP goes in srbdqp_config";
+        break;
+    case Variant::Normals:
+        h->err = w + ": refused while contact normals are set (srbdqp_set_contact_normals): only the fp64 batch solves on the general kernel read them "
+                     "-- srbdqp_set_contact_normals(h, NULL, 0) goes back to flat ground";
+        break;
+    case Variant::Live:
+        h->err = w + ": refused on a handle whose horizon " + std::to_string(h->cfg.horizon) + " was admitted by SRBDQP_FLAG_ANY_HORIZON: only the fp64 batch, "
+                     "ragged and staged solves run a live horizon (the general kernel's fp64 batch instantiation for N = " + std::to_string(h->live_nstar) + ")";
+        break;
+    case Variant::RankAware:
+        h->err = w + ": refused on a handle created with SRBDQP_FLAG_RANK_AWARE: only the fp64 batch and staged solves have rank-aware wrench steps "
+                     "(the general kernel's fp64 batch instantiation, flat ground, srbdqp_config's single robot)";
+        break;
+    }
     return SRBDQP_E_INVALID;
 }
 
-// a call that has no rank-aware form, on a handle created with SRBDQP_FLAG_RANK_AWARE (include/srbdqp.h has the list)
-int rank_aware_refuse(srbdqp_handle* h, const char* what) {
-    h->err = std::string(what) + ": refused on a handle created with SRBDQP_FLAG_RANK_AWARE: only the fp64 batch and staged solves have rank-aware wrench steps "
-             "(the general kernel's fp64 batch instantiation, flat ground, srbdqp_config's single robot)";
-    return SRBDQP_E_INVALID;
+// The table: the variants, besides Plain, that each C-ABI call has a form for.  Every call below opens with require_form(h, "<its name>", <its row>); the fp64
+// batch solves (host, device, ragged) have every form and no row.  (Inside the general kernel's launcher a rank-aware or live handle further refuses the
+// assembly dump and an fp32 solve, which no entry point lets through; the ragged calls refuse an fp32 solve and robot records with a live bucket.)
+constexpr unsigned form(Variant v) { return 1u << (unsigned)v; }
+// srbdqp_solve_staged_f64, srbdqp_update_f64 (a live handle passes here and not below: the staged solve runs its batch instantiation through the HIP launch)
+constexpr unsigned kFormsStaged = form(Variant::Live) | form(Variant::RankAware);
+// srbdqp_prepare_staged_f64, srbdqp_solve_prepared_f64 (a rank-aware handle passes: the one-wave kernels of the two-phase call have no wrench steps)
+constexpr unsigned kFormsTwoPhase = form(Variant::RankAware);
+// srbdqp_solve_batch_f32, srbdqp_solve_batch_device_f32
+constexpr unsigned kFormsF32 = 0;
+// srbdqp_assemble_f64 (a rank-aware handle passes: the dump of the compact kernels, which have no wrench steps)
+constexpr unsigned kFormsAssemble = form(Variant::RankAware);
+// srbdqp_assemble_wrench_f64
+constexpr unsigned kFormsAssembleWrench = 0;
+// srbdqp_set_robots / _device with records (robots_check_handle, which refuses N = 24 as well)
+constexpr unsigned kFormsSetRobots = form(Variant::Robots);
+// srbdqp_set_contact_normals / _device with normals (normals_check_handle, which refuses N = 24 as well, and records in words of its own)
+constexpr unsigned kFormsSetNormals = form(Variant::Normals) | form(Variant::Robots);
+
+// a few field tests on the way of a call that has the form (srbdqp_solve_staged_f64 is the batch-1 latency path); a string only when the refusal fires
+inline int require_form(srbdqp_handle* h, const char* fn, unsigned forms) {
+    const Variant v = variant_of(h);
+    return (v == Variant::Plain || ((forms >> (unsigned)v) & 1u)) ? SRBDQP_OK : refuse(h, v, fn);
 }
+
 // Horizons with a rank-aware instantiation (MODE = 5) of the general kernel: every tabulated one below 24 builds without scratch memory at the waves per SIMD of
 // its MODE = 0 twin ("Rank-aware wrench steps", has the table); N = 24 -- whose MODE = 0 kernel keeps 20 bytes per lane there already -- has none.
 constexpr int kRankAwareMaxHorizon = 20;
@@ -685,68 +744,49 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
     constexpr size_t ldsb = SB::bytes;
     static_assert(ldsb <= 163840, "one QP must fit the LDS of a CU");
     static const std::string nm = std::string("wrench_") + (sizeof(R) == 4 ? "f32" : "f64") + "_n" + std::to_string(N);
+    const dim3 grid((unsigned)a.B);
     if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) {
         // rank-aware wrench steps: the MODE = 5 instantiation of the fp64 batch kernel -- every launch of a solve (first pass, restart passes, deferred passes on the
         // tail stream, a dispatch order, the staged calls with their completion word) comes through here with this handle.  (srbdqp_create refuses the flag at
         // N = 24 and at a live horizon, and the entry points the fp32 and dump calls, robot records and contact normals.)  The layout of the MODE = 0 twin.
         if constexpr (sizeof(R) == 8 && N <= kRankAwareMaxHorizon) {
-            if (a.mode == 1) return rank_aware_refuse(h, "the assembly dump");
+            if (a.mode == 1) return refuse(h, Variant::RankAware, "the assembly dump");
             using S5 = srbdqp::WrenchSmem<N, 8, 5, 0, srbdqp::wrench_kreg64(N, 5)>;
             static_assert(S5::bytes == lds && S5::BT == S::BT && WrenchTraits<N, double>::wps == WPS, "rank-aware steps cost no occupancy: the LDS and the waves per SIMD of the MODE = 0 twin");
-            void (*k5)(KArgs) = &srbdqp::srbdqp_wrench_ra_kernel<N, WPS>;
-            int rc5 = set_lds_once(h, k5, lds);
-            if (rc5 != SRBDQP_OK) return rc5;
-            static const std::string nm5 = nm + "_ra";
-            h->kname = nm5.c_str();
-            hipLaunchKernelGGL(k5, dim3((unsigned)a.B), dim3(S::BT), lds, st, a);
-            HIP_TRY(h, hipGetLastError());
-            return SRBDQP_OK;
-        } else return rank_aware_refuse(h, sizeof(R) == 4 ? "an fp32 solve" : "a solve at this horizon");
+            static const std::string nm_ra = nm + "_ra";
+            return launch_kernel(h, &srbdqp::srbdqp_wrench_ra_kernel<N, WPS>, nm_ra.c_str(), grid, dim3(S::BT), lds, st, a);
+        } else return refuse(h, Variant::RankAware, sizeof(R) == 4 ? "an fp32 solve" : "a solve at this horizon");
     }
     if (h->live_nstar) {
         // a live horizon n = cfg.horizon < N (SRBDQP_FLAG_ANY_HORIZON): the MODE = 3 instantiation of the fp64 batch kernel, n as its second argument -- every launch of
         // a solve (first pass, restart passes, deferred passes on the tail stream, ragged buckets, the staged calls with their completion word) comes through here
         // with this handle.  (The entry points refuse the fp32, dump and two-phase calls and the robot records on such a handle.)
         if constexpr (sizeof(R) == 8) {
-            if (a.mode == 1) return live_refuse(h, "the assembly dump");
+            if (a.mode == 1) return refuse(h, Variant::Live, "the assembly dump");
             // (the layout of the MODE = 0 twin -- the live horizon itself takes no LDS --, except N* = 24: four more entries of every lane's T^-1 half row in LDS
             //  instead of registers, srbdqp_wrench.hpp wrench_kreg64; still the twin's one workgroup per CU)
             using S3 = srbdqp::WrenchSmem<N, 8, 5, BXW, srbdqp::wrench_kreg64(N, 3)>;
             constexpr size_t lds3 = S3::bytes;
             static_assert(lds3 <= 163840 && S3::lds_wgs == SB::lds_wgs && (N == 24 || lds3 == ldsb), "a live horizon costs no workgroup per CU: the occupancy of the MODE = 0 twin");
-            void (*k3)(KArgs, int) = &srbdqp::srbdqp_wrench_kernel<N, double, double, 3, WPS, double, 5, BXW>;
-            int rc3 = set_lds_once(h, k3, lds3);
-            if (rc3 != SRBDQP_OK) return rc3;
-            h->kname = h->live_name.c_str();
-            hipLaunchKernelGGL(k3, dim3((unsigned)a.B), dim3(S3::BT), lds3, st, a, (int)h->cfg.horizon);
-            HIP_TRY(h, hipGetLastError());
-            return SRBDQP_OK;
-        } else return live_refuse(h, "an fp32 solve");
+            void (*k_live)(KArgs, int) = &srbdqp::srbdqp_wrench_kernel<N, double, double, 3, WPS, double, 5, BXW>;
+            return launch_kernel(h, k_live, h->live_name.c_str(), grid, dim3(S3::BT), lds3, st, a, (int)h->cfg.horizon);
+        } else return refuse(h, Variant::Live, "an fp32 solve");
     }
     if (a.mode == 1) {
-        if constexpr (sizeof(R) == 8) {
-            int rc = set_lds_once(h, &srbdqp::srbdqp_wrench_kernel<N, double, double, 1, WPS>, lds);
-            if (rc != SRBDQP_OK) return rc;
-            h->kname = nm.c_str();
-            hipLaunchKernelGGL((srbdqp::srbdqp_wrench_kernel<N, double, double, 1, WPS>), dim3((unsigned)a.B), dim3(S::BT), lds, st, a);
-        } else { h->err = "the assembly dump is fp64 only"; return SRBDQP_E_INVALID; }
+        if constexpr (sizeof(R) == 8) return launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, double, double, 1, WPS>, nm.c_str(), grid, dim3(S::BT), lds, st, a);
+        else { h->err = "the assembly dump is fp64 only"; return SRBDQP_E_INVALID; }
     } else {
         if constexpr (sizeof(R) == 8 && N != 24) {
             // per-QP robot records (srbdqp_set_robots / _device): the MODE = 2 instantiation, the records as its second argument -- every launch of a solve
             // (first pass, restart passes, deferred passes on the tail stream, ragged buckets) comes through here with this handle.  (The entry points refuse
             // the staged, fp32 and dump calls while records are set, and the setters refuse N = 24: kRobotsMaxHorizon.)
             if (h->robots) {
-                constexpr size_t lds2 = lds + 8 * sizeof(double);          // + the QP's robot behind the layout (srbdqp_wrench.hpp qp_robot_to_lds)
-                constexpr int by_lds2 = (S::wgs_of(S::o_end + 8) * S::NW + 3) / 4;   // (waves per SIMD the LDS admits, as WrenchTraits::by_lds)
-                static_assert((by_lds2 < WPS ? by_lds2 : WPS) == WPS, "the record's 64 bytes of LDS cost no occupancy");
-                void (*k2)(KArgs, const double*) = &srbdqp::srbdqp_wrench_kernel<N, double, double, 2, WPS, double, 5, 0>;
-                int rc2 = set_lds_once(h, k2, lds2);
-                if (rc2 != SRBDQP_OK) return rc2;
-                static const std::string nm2 = nm + "_rb";
-                h->kname = nm2.c_str();
-                hipLaunchKernelGGL(k2, dim3((unsigned)a.B), dim3(S::BT), lds2, st, a, reinterpret_cast<const double*>(h->robots));
-                HIP_TRY(h, hipGetLastError());
-                return SRBDQP_OK;
+                constexpr size_t lds_rb = lds + 8 * sizeof(double);          // + the QP's robot behind the layout (srbdqp_wrench.hpp qp_robot_to_lds)
+                constexpr int by_lds_rb = (S::wgs_of(S::o_end + 8) * S::NW + 3) / 4;   // (waves per SIMD the LDS admits, as WrenchTraits::by_lds)
+                static_assert((by_lds_rb < WPS ? by_lds_rb : WPS) == WPS, "the record's 64 bytes of LDS cost no occupancy");
+                void (*k_rb)(KArgs, const double*) = &srbdqp::srbdqp_wrench_kernel<N, double, double, 2, WPS, double, 5, 0>;
+                static const std::string nm_rb = nm + "_rb";
+                return launch_kernel(h, k_rb, nm_rb.c_str(), grid, dim3(S::BT), lds_rb, st, a, reinterpret_cast<const double*>(h->robots));
             }
         }
         if constexpr (sizeof(R) == 8 && N != 24) {
@@ -758,14 +798,8 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
                 constexpr size_t ldsn = SN::bytes;
                 constexpr int WPSN = NormalsTraits<N>::wps;
                 static_assert(ldsn <= 163840 && SN::BT == S::BT, "one QP must fit the LDS of a CU");
-                void (*k4)(KArgs, const double*) = &srbdqp::srbdqp_wrench_cn_kernel<N, WPSN>;
-                int rc4 = set_lds_once(h, k4, ldsn);
-                if (rc4 != SRBDQP_OK) return rc4;
-                static const std::string nm4 = nm + "_cn";
-                h->kname = nm4.c_str();
-                hipLaunchKernelGGL(k4, dim3((unsigned)a.B), dim3(SN::BT), ldsn, st, a, h->normals);
-                HIP_TRY(h, hipGetLastError());
-                return SRBDQP_OK;
+                static const std::string nm_cn = nm + "_cn";
+                return launch_kernel(h, &srbdqp::srbdqp_wrench_cn_kernel<N, WPSN>, nm_cn.c_str(), grid, dim3(SN::BT), ldsn, st, a, h->normals);
             }
         }
         if constexpr (sizeof(R) == 8 && N <= 10) {
@@ -776,34 +810,28 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
                 constexpr int XW = (N >= 8) ? 2 : 1;
                 using SL = srbdqp::WrenchSmem<N, 8, 5, XW>;
                 constexpr size_t ldsl = SL::bytes;
-                int rcl = set_lds_once(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, 1, double, 5, XW>, ldsl);
-                if (rcl != SRBDQP_OK) return rcl;
-                static const std::string nml = nm + "_lat";
-                h->kname = nml.c_str();
+                static const std::string nm_lat = nm + "_lat";
                 if constexpr (std::is_same<TIO, double>::value) {
                     srbdqp::StagedIn<N> in;
                     if (!a.count_ptr && !a.tile_sel && staged_inline_inputs<N>(h, c, a, in)) {
-                        rcl = set_lds_once(h, &srbdqp::srbdqp_wrench_kernel_in<N, XW>, ldsl);
-                        if (rcl != SRBDQP_OK) return rcl;
+                        // (both kernels' LDS limits and the name BEFORE the AQL attempt, which needs none of them: HIP has loaded the kernels whichever way a
+                        //  later launch of this handle goes)
+                        int rc = set_lds_once(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, 1, double, 5, XW>, ldsl);
+                        if (rc == SRBDQP_OK) rc = set_lds_once(h, &srbdqp::srbdqp_wrench_kernel_in<N, XW>, ldsl);
+                        if (rc != SRBDQP_OK) return rc;
+                        h->kname = nm_lat.c_str();
                         KArgs ai = a;
                         ai.inline_in = 1;
                         staged_done_checksum(h, ai);
                         if (aql_launch_in(h, c, st, "_ZN6srbdqp23srbdqp_wrench_kernel_inILi%dELi%dEEEvNS_5KArgsENS_8StagedInIXT_EEE.kd", N, XW, ai, in, SL::BT, ldsl)) return SRBDQP_OK;
-                        rcl = aql_quiesce(h);
-                        if (rcl != SRBDQP_OK) return rcl;
-                        hipLaunchKernelGGL((srbdqp::srbdqp_wrench_kernel_in<N, XW>), dim3(1), dim3(SL::BT), ldsl, st, ai, in);
-                        HIP_TRY(h, hipGetLastError());
-                        return SRBDQP_OK;
+                        rc = aql_quiesce(h);
+                        if (rc != SRBDQP_OK) return rc;
+                        return launch_kernel(h, &srbdqp::srbdqp_wrench_kernel_in<N, XW>, nullptr, dim3(1), dim3(SL::BT), ldsl, st, ai, in);
                     }
                 }
-                hipLaunchKernelGGL((srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, 1, double, 5, XW>), dim3((unsigned)a.B), dim3(SL::BT), ldsl, st, a);
-                HIP_TRY(h, hipGetLastError());
-                return SRBDQP_OK;
+                return launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, 1, double, 5, XW>, nm_lat.c_str(), grid, dim3(SL::BT), ldsl, st, a);
             }
         }
-        int rc = set_lds_once(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, WPS, double, 5, BXW>, ldsb);
-        if (rc != SRBDQP_OK) return rc;
-        h->kname = nm.c_str();
         if constexpr (sizeof(R) == 4) {
             // fp32 iterations: QPs whose steps all have 0 or >= 3 stance contacts (every g coordinate a wrench coordinate,
             // cond(T) ~ 5e4) factor T in fp32 tiles -- half the LDS, one more workgroup per CU; a step kept in force
@@ -814,20 +842,15 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
                 using S4 = srbdqp::WrenchSmem<N, 4>;
                 constexpr int WPS4 = WrenchTraits<N, R, 4>::wps;
                 constexpr size_t lds4 = S4::bytes;
-                rc = set_lds_once(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, WPS4, float>, lds4);
-                if (rc != SRBDQP_OK) return rc;
                 KArgs a4 = a, a8 = a;
                 a4.tile_sel = 1; a8.tile_sel = 2;
-                hipLaunchKernelGGL((srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, WPS4, float>), dim3((unsigned)a.B), dim3(S::BT), lds4, st, a4);
-                hipLaunchKernelGGL((srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, WPS, double, 5, BXW>), dim3((unsigned)a.B), dim3(SB::BT), ldsb, st, a8);
-                HIP_TRY(h, hipGetLastError());
-                return SRBDQP_OK;
+                const int rc = launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, WPS4, float>, nm.c_str(), grid, dim3(S::BT), lds4, st, a4);
+                if (rc != SRBDQP_OK) return rc;
+                return launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, WPS, double, 5, BXW>, nullptr, grid, dim3(SB::BT), ldsb, st, a8);
             }
         }
-        hipLaunchKernelGGL((srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, WPS, double, 5, BXW>), dim3((unsigned)a.B), dim3(SB::BT), ldsb, st, a);
+        return launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, WPS, double, 5, BXW>, nm.c_str(), grid, dim3(SB::BT), ldsb, st, a);
     }
-    HIP_TRY(h, hipGetLastError());
-    return SRBDQP_OK;
 }
 
 // the general kernel at the handle's horizon, on the call's element type
@@ -850,12 +873,9 @@ int launch(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t st, int 
     if (uses_wrench(h, c, c.maxs, a.qp_span > a.B ? a.qp_span : a.B)) rc = launch_wrench(h, c, a, st);
     else rc = with_horizon(h, [&](auto n) -> int {
         constexpr int N = decltype(n)::value;
-        int rcc = SRBDQP_OK;
-        if constexpr (N <= 10) rcc = (c.maxs <= 2) ? launch_compact<N, 2>(h, c, a, st) : launch_compact<N, 4>(h, c, a, st);
-        else if constexpr (N <= 20) rcc = launch_compact<N, 2>(h, c, a, st);
-        if (rcc != SRBDQP_OK) return rcc;
-        HIP_TRY(h, hipGetLastError());
-        return SRBDQP_OK;
+        if constexpr (N <= 10) return (c.maxs <= 2) ? launch_compact<N, 2>(h, c, a, st) : launch_compact<N, 4>(h, c, a, st);
+        else if constexpr (N <= 20) return launch_compact<N, 2>(h, c, a, st);
+        else return SRBDQP_OK;     // (N = 24 never gets here: uses_wrench)
     });
     if (rc != SRBDQP_OK) return rc;
     if (timing && pass != 1) {
@@ -1087,36 +1107,22 @@ int robots_validate(const srbdqp_robot* host, int32_t length, const char* fn, st
     return SRBDQP_OK;
 }
 
-// a call that cannot read per-QP records while they are set on this handle
-int robots_refuse(srbdqp_handle* h, const char* what) {
-    h->err = std::string(what) + ": refused while per-QP robot records are set (srbdqp_set_robots): only the fp64 batch and ragged solves on the general kernel read "
-             "them -- one robot for every QP goes in srbdqp_config";
-    return SRBDQP_E_INVALID;
-}
-
 // Horizons whose general kernel has a per-QP-record instantiation (MODE = 2) without scratch memory: N = 24 has none -- the MODE = 0 kernel that ships keeps
 // 20 bytes per lane in scratch with its three extra set-up waves, and a MODE = 2 copy without them (XW = 0) 24 bytes -- so the setters refuse an N = 24
 // handle / a ragged object with an N = 24 bucket.
 constexpr int kRobotsMaxHorizon = 20;
 const char* const robots_n24 = "per-QP robot records: not at N = 24 (no instantiation of the general kernel reads them there without scratch memory, DESIGN.md section 11)";
 
-// fp64 batch solve of B QPs with records set: the general kernel, and a record for every QP
-int robots_check_batch(srbdqp_handle* h, int32_t B) {
-    if (!h->robots) return SRBDQP_OK;
-    if (h->cfg.kernel != SRBDQP_KERNEL_AUTO && h->cfg.kernel != SRBDQP_KERNEL_WRENCH) {
-        h->err = "per-QP robot records are read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH while they are set";
-        return SRBDQP_E_INVALID;
-    }
-    if ((size_t)B > h->robots_len) {
-        h->err = "solve of " + std::to_string(B) + " QPs with " + std::to_string(h->robots_len) + " robot records set (srbdqp_set_robots): every QP needs its record";
-        return SRBDQP_E_INVALID;
-    }
+// may this handle take records?  (a live horizon, rank-aware steps or contact normals: a combined mode would be another copy of every instantiation)
+int robots_check_handle(srbdqp_handle* h, const char* fn) {
+    if (const int rc = require_form(h, fn, kFormsSetRobots)) return rc;
+    if (h->cfg.horizon > kRobotsMaxHorizon) { h->err = robots_n24; return SRBDQP_E_INVALID; }
     return SRBDQP_OK;
 }
 
-// before the library's own copy of the records is replaced: every solve that may still read it has completed (srbdqp_synchronize, then every other launch
-// stream of the handle and its tail streams -- deferred restart passes read the records too)
-int robots_quiesce(srbdqp_handle* h) {
+// before the library's own copy of the records or of the normals is replaced: every solve that may still read it has completed (srbdqp_synchronize, then every
+// other launch stream of the handle and its tail streams -- deferred restart passes read them too)
+int quiesce_all_streams(srbdqp_handle* h) {
     int rc = srbdqp_synchronize(h);
     if (rc != SRBDQP_OK) return rc;
     rc = srbdqp_flush(h, nullptr);
@@ -1139,32 +1145,29 @@ const char* normal_fault(const double* n) {
     return nullptr;
 }
 
-// a call that cannot read contact normals while they are set on this handle
-int normals_refuse(srbdqp_handle* h, const char* what) {
-    h->err = std::string(what) + ": refused while contact normals are set (srbdqp_set_contact_normals): only the fp64 batch solves on the general kernel read them "
-             "-- srbdqp_set_contact_normals(h, NULL, 0) goes back to flat ground";
-    return SRBDQP_E_INVALID;
-}
-
 // may this handle take normals?  (N = 24: no instantiation of the general kernel without scratch memory, as for robot records; a live horizon or robot records:
 // a combined mode would be another copy of every instantiation)
 int normals_check_handle(srbdqp_handle* h, const char* fn) {
-    if (h->live_nstar) return live_refuse(h, fn);
-    if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) return rank_aware_refuse(h, fn);
+    if (const int rc = require_form(h, fn, kFormsSetNormals)) return rc;
     if (h->cfg.horizon > kRobotsMaxHorizon) { h->err = std::string(fn) + ": contact normals: not at N = 24 (no instantiation of the general kernel reads them there, DESIGN.md section 13)"; return SRBDQP_E_INVALID; }
     if (h->robots) { h->err = std::string(fn) + ": refused while per-QP robot records are set (srbdqp_set_robots): no instantiation reads both (DESIGN.md section 13)"; return SRBDQP_E_INVALID; }
     return SRBDQP_OK;
 }
 
-// fp64 batch solve of B QPs with normals set: the general kernel, and a block of normals for every QP
-int normals_check_batch(srbdqp_handle* h, int32_t B) {
-    if (!h->normals) return SRBDQP_OK;
+// fp64 batch solve of B QPs with records or normals set: the general kernel, and a record / a block of normals for every QP
+int variant_check_batch(srbdqp_handle* h, int32_t B) {
+    const Variant v = variant_of(h);
+    if (v != Variant::Robots && v != Variant::Normals) return SRBDQP_OK;
+    const bool rb = v == Variant::Robots;
     if (h->cfg.kernel != SRBDQP_KERNEL_AUTO && h->cfg.kernel != SRBDQP_KERNEL_WRENCH) {
-        h->err = "contact normals (srbdqp_set_contact_normals) are read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH while they are set";
+        h->err = std::string(rb ? "per-QP robot records" : "contact normals (srbdqp_set_contact_normals)") +
+                 " are read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH while they are set";
         return SRBDQP_E_INVALID;
     }
-    if ((size_t)B > h->normals_len) {
-        h->err = "solve of " + std::to_string(B) + " QPs with contact normals for " + std::to_string(h->normals_len) + " set (srbdqp_set_contact_normals): every QP needs its block";
+    const size_t len = rb ? h->robots_len : h->normals_len;
+    if ((size_t)B > len) {
+        h->err = "solve of " + std::to_string(B) + " QPs with " + (rb ? std::to_string(len) + " robot records set (srbdqp_set_robots): every QP needs its record"
+                                                                      : "contact normals for " + std::to_string(len) + " set (srbdqp_set_contact_normals): every QP needs its block");
         return SRBDQP_E_INVALID;
     }
     return SRBDQP_OK;
@@ -1347,8 +1350,7 @@ int srbdqp_stage_ptrs(srbdqp_handle* h, srbdqp_stage* out) {
 
 int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y) {
     if (!h) return SRBDQP_E_INVALID;
-    if (h->robots) return robots_refuse(h, "srbdqp_solve_staged_f64");
-    if (h->normals) return normals_refuse(h, "srbdqp_solve_staged_f64");
+    if (const int rc = require_form(h, "srbdqp_solve_staged_f64", kFormsStaged)) return rc;
     if (B < 0 || B > h->stage_h.capacity) { h->err = "staged batch exceeds the staging capacity"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
     {   // (the kernel of the call before this one published its completion word before it ended)
@@ -1390,8 +1392,7 @@ int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32
 int srbdqp_update_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact,
                       const double* pcom, double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters) {
     if (!h) return SRBDQP_E_INVALID;
-    if (h->robots) return robots_refuse(h, "srbdqp_update_f64");
-    if (h->normals) return normals_refuse(h, "srbdqp_update_f64");
+    if (const int rc = require_form(h, "srbdqp_update_f64", kFormsStaged)) return rc;
     if (!x0 || !x_ref || !foot || !contact || !u0_out) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
     const size_t N = (size_t)h->cfg.horizon;
     const srbdqp_stage& s = h->stage_h;
@@ -1423,9 +1424,7 @@ KArgs staged_args(srbdqp_handle* h, int32_t B, bool use_pcom, bool want_x, bool 
 
 int srbdqp_prepare_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom) {
     if (!h) return SRBDQP_E_INVALID;
-    if (h->robots) return robots_refuse(h, "srbdqp_prepare_staged_f64");
-    if (h->normals) return normals_refuse(h, "srbdqp_prepare_staged_f64");
-    if (h->live_nstar) return live_refuse(h, "srbdqp_prepare_staged_f64");
+    if (const int rc = require_form(h, "srbdqp_prepare_staged_f64", kFormsTwoPhase)) return rc;
     if (B < 0 || B > h->stage_h.capacity) { h->err = "staged batch exceeds the staging capacity"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1443,9 +1442,7 @@ int srbdqp_prepare_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom) {
 
 int srbdqp_solve_prepared_f64(srbdqp_handle* h, int32_t B, int32_t want_x, int32_t want_y) {
     if (!h) return SRBDQP_E_INVALID;
-    if (h->robots) return robots_refuse(h, "srbdqp_solve_prepared_f64");
-    if (h->normals) return normals_refuse(h, "srbdqp_solve_prepared_f64");
-    if (h->live_nstar) return live_refuse(h, "srbdqp_solve_prepared_f64");
+    if (const int rc = require_form(h, "srbdqp_solve_prepared_f64", kFormsTwoPhase)) return rc;
     if (B <= 0 || B != h->prepared_B) { h->err = "srbdqp_solve_prepared_f64: no set-up of this batch size is pending (srbdqp_prepare_staged_f64)"; return SRBDQP_E_INVALID; }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const bool spin = !(h->cfg.flags & SRBDQP_FLAG_NO_SPIN);
@@ -1470,16 +1467,13 @@ int srbdqp_set_robots(srbdqp_handle* h, const srbdqp_robot* host, int32_t length
     if (!h) return SRBDQP_E_INVALID;
     if (host && length < 0) { h->err = "srbdqp_set_robots: negative length"; return SRBDQP_E_INVALID; }
     const bool clear = !host || length == 0;
-    if (!clear && h->live_nstar) return live_refuse(h, "srbdqp_set_robots");
-    if (!clear && (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE)) return rank_aware_refuse(h, "srbdqp_set_robots");
-    if (!clear && h->cfg.horizon > kRobotsMaxHorizon) { h->err = robots_n24; return SRBDQP_E_INVALID; }
-    if (!clear && h->normals) return normals_refuse(h, "srbdqp_set_robots");
     if (!clear) {
-        const int rv = robots_validate(host, length, "srbdqp_set_robots", h->err);
+        int rv = robots_check_handle(h, "srbdqp_set_robots");
+        if (rv == SRBDQP_OK) rv = robots_validate(host, length, "srbdqp_set_robots", h->err);
         if (rv != SRBDQP_OK) return rv;
     }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    int rc = robots_quiesce(h);                     // (deferred passes may still read the records this call replaces)
+    int rc = quiesce_all_streams(h);                // (deferred passes may still read the records this call replaces)
     if (rc != SRBDQP_OK) return rc;
     if (clear) { h->robots = nullptr; h->robots_len = 0; return SRBDQP_OK; }
     if ((size_t)length > h->robots_cap) { h->robots = nullptr; h->robots_len = 0; }
@@ -1494,10 +1488,7 @@ int srbdqp_set_robots_device(srbdqp_handle* h, const srbdqp_robot* dev, int32_t 
     if (!h) return SRBDQP_E_INVALID;
     if (dev && length < 0) { h->err = "srbdqp_set_robots_device: negative length"; return SRBDQP_E_INVALID; }
     const bool clear = !dev || length == 0;
-    if (!clear && h->live_nstar) return live_refuse(h, "srbdqp_set_robots_device");
-    if (!clear && (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE)) return rank_aware_refuse(h, "srbdqp_set_robots_device");
-    if (!clear && h->cfg.horizon > kRobotsMaxHorizon) { h->err = robots_n24; return SRBDQP_E_INVALID; }
-    if (!clear && h->normals) return normals_refuse(h, "srbdqp_set_robots_device");
+    if (!clear) if (const int rc = robots_check_handle(h, "srbdqp_set_robots_device")) return rc;
     h->robots = clear ? nullptr : dev;
     h->robots_len = clear ? 0 : (size_t)length;
     return SRBDQP_OK;
@@ -1519,7 +1510,7 @@ int srbdqp_set_contact_normals(srbdqp_handle* h, const double* host, int32_t len
             }
     }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    int rc = robots_quiesce(h);                     // (deferred passes may still read the array this call replaces)
+    int rc = quiesce_all_streams(h);                // (deferred passes may still read the array this call replaces)
     if (rc != SRBDQP_OK) return rc;
     if (clear) { h->normals = nullptr; h->normals_len = 0; return SRBDQP_OK; }
     const size_t want = (size_t)length * N * 12;
@@ -1809,10 +1800,7 @@ int srbdqp_solve_batch_device_f64(srbdqp_handle* h, int32_t B, const double* x0,
                                   const double* warm_u, const double* warm_y, double* u_out, double* x_out,
                                   double* y_out, int32_t* status, int32_t* iters, void* stream) {
     if (!h) return SRBDQP_E_INVALID;
-    const int rr = robots_check_batch(h, B);
-    if (rr != SRBDQP_OK) return rr;
-    const int rn = normals_check_batch(h, B);
-    if (rn != SRBDQP_OK) return rn;
+    if (const int rc = variant_check_batch(h, B)) return rc;
     return solve_device_impl(h, device_call(h, false), B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
 }
 
@@ -1821,10 +1809,7 @@ int srbdqp_solve_batch_device_f32(srbdqp_handle* h, int32_t B, const float* x0, 
                                   const float* warm_u, const float* warm_y, float* u_out, float* x_out,
                                   float* y_out, int32_t* status, int32_t* iters, void* stream) {
     if (!h) return SRBDQP_E_INVALID;
-    if (h->robots) return robots_refuse(h, "srbdqp_solve_batch_device_f32");
-    if (h->normals) return normals_refuse(h, "srbdqp_solve_batch_device_f32");
-    if (h->live_nstar) return live_refuse(h, "srbdqp_solve_batch_device_f32");
-    if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) return rank_aware_refuse(h, "srbdqp_solve_batch_device_f32");
+    if (const int rc = require_form(h, "srbdqp_solve_batch_device_f32", kFormsF32)) return rc;
     return solve_device_impl(h, device_call(h, true), B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
 }
 
@@ -1832,10 +1817,7 @@ int srbdqp_solve_batch_f64(srbdqp_handle* h, int32_t B, const double* x0, const 
                            const uint8_t* contact, const double* pcom, const double* warm_u, const double* warm_y,
                            double* u_out, double* x_out, double* y_out, int32_t* status, int32_t* iters) {
     if (!h) return SRBDQP_E_INVALID;
-    const int rr = robots_check_batch(h, B);
-    if (rr != SRBDQP_OK) return rr;
-    const int rn = normals_check_batch(h, B);
-    if (rn != SRBDQP_OK) return rn;
+    if (const int rc = variant_check_batch(h, B)) return rc;
     return solve_host_impl(h, false, B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters);
 }
 
@@ -1843,10 +1825,7 @@ int srbdqp_solve_batch_f32(srbdqp_handle* h, int32_t B, const float* x0, const f
                            const uint8_t* contact, const float* pcom, const float* warm_u, const float* warm_y,
                            float* u_out, float* x_out, float* y_out, int32_t* status, int32_t* iters) {
     if (!h) return SRBDQP_E_INVALID;
-    if (h->robots) return robots_refuse(h, "srbdqp_solve_batch_f32");
-    if (h->normals) return normals_refuse(h, "srbdqp_solve_batch_f32");
-    if (h->live_nstar) return live_refuse(h, "srbdqp_solve_batch_f32");
-    if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) return rank_aware_refuse(h, "srbdqp_solve_batch_f32");
+    if (const int rc = require_form(h, "srbdqp_solve_batch_f32", kFormsF32)) return rc;
     return solve_host_impl(h, true, B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters);
 }
 
@@ -1854,9 +1833,7 @@ int srbdqp_assemble_f64(srbdqp_handle* h, int32_t B, const double* x0, const dou
                         const uint8_t* contact, const double* pcom, double* P_out, double* q_out, double* l_out,
                         double* ub_out) {
     if (!h) return SRBDQP_E_INVALID;
-    if (h->robots) return robots_refuse(h, "srbdqp_assemble_f64");
-    if (h->normals) return normals_refuse(h, "srbdqp_assemble_f64");
-    if (h->live_nstar) return live_refuse(h, "srbdqp_assemble_f64");
+    if (const int rc = require_form(h, "srbdqp_assemble_f64", kFormsAssemble)) return rc;
     if (B < 0 || (B > 0 && (!x0 || !x_ref || !foot || !contact || !P_out || !q_out || !l_out || !ub_out))) { h->err = "null pointer"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -1931,10 +1908,7 @@ int srbdqp_assemble_wrench_f64(srbdqp_handle* h, int32_t B, const double* x0, co
                                const uint8_t* contact, const double* pcom, double* T_out, double* q_out, double* blocks_out,
                                double* goff_out) {
     if (!h) return SRBDQP_E_INVALID;
-    if (h->robots) return robots_refuse(h, "srbdqp_assemble_wrench_f64");
-    if (h->normals) return normals_refuse(h, "srbdqp_assemble_wrench_f64");
-    if (h->live_nstar) return live_refuse(h, "srbdqp_assemble_wrench_f64");
-    if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) return rank_aware_refuse(h, "srbdqp_assemble_wrench_f64");
+    if (const int rc = require_form(h, "srbdqp_assemble_wrench_f64", kFormsAssembleWrench)) return rc;
     if (B < 0 || (B > 0 && (!x0 || !x_ref || !foot || !contact || !T_out || !q_out || !blocks_out || !goff_out))) { h->err = "null pointer"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -2072,7 +2046,7 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
                        int32_t* status, int32_t* iters, void* stream, bool f32) {
     if (!r) return SRBDQP_E_INVALID;
     if (B < 0 || (B > 0 && (!N_per_qp || !x0 || !x_ref || !foot || !contact || !u_out))) { r->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
-    if (f32) for (auto* bh : r->hs) if (bh->live_nstar) { live_refuse(bh, "an fp32 ragged solve"); r->err = bh->err; return SRBDQP_E_INVALID; }
+    if (f32) for (auto* bh : r->hs) if (bh->live_nstar) { const int rc = refuse(bh, Variant::Live, "an fp32 ragged solve"); r->err = bh->err; return rc; }
     if (r->robots && f32) { r->err = "fp32 ragged solve: refused while per-QP robot records are set (srbdqp_ragged_set_robots): only the fp64 solves read them"; return SRBDQP_E_INVALID; }
     if (r->robots && (size_t)B > r->robots_len) {
         r->err = "ragged solve of " + std::to_string(B) + " QPs with " + std::to_string(r->robots_len) + " robot records set: every QP needs its record";
@@ -2239,22 +2213,31 @@ int ragged_forward_robots(srbdqp_ragged* r) {
     }
     return SRBDQP_OK;
 }
+
+// may every bucket take records?  (robots_check_handle; r->err: the bucket's refusal, with the bucket in front unless the text names its live horizon itself)
+int ragged_robots_check(srbdqp_ragged* r) {
+    for (auto* bh : r->hs)
+        if (const int rc = robots_check_handle(bh, "per-QP robot records on a ragged object")) {
+            r->err = (bh->live_nstar ? std::string() : "bucket N=" + std::to_string(bh->cfg.horizon) + ": ") + bh->err;
+            return rc;
+        }
+    return SRBDQP_OK;
+}
 }  // namespace
 
 int srbdqp_ragged_set_robots(srbdqp_ragged* r, const srbdqp_robot* host, int32_t length) {
     if (!r) return SRBDQP_E_INVALID;
     if (host && length < 0) { r->err = "srbdqp_ragged_set_robots: negative length"; return SRBDQP_E_INVALID; }
     const bool clear = !host || length == 0;
-    if (!clear) for (auto* bh : r->hs) if (bh->live_nstar) { live_refuse(bh, "per-QP robot records on a ragged object"); r->err = bh->err; return SRBDQP_E_INVALID; }
-    if (!clear) for (int hz : r->horizons) if (hz > kRobotsMaxHorizon) { r->err = std::string("bucket N=") + std::to_string(hz) + ": " + robots_n24; return SRBDQP_E_INVALID; }
     if (!clear) {
-        const int rv = robots_validate(host, length, "srbdqp_ragged_set_robots", r->err);
+        int rv = ragged_robots_check(r);
+        if (rv == SRBDQP_OK) rv = robots_validate(host, length, "srbdqp_ragged_set_robots", r->err);
         if (rv != SRBDQP_OK) return rv;
     }
     HIP_TRY(r, hipSetDevice(r->device));
     // every pass that may still read the records this call replaces has completed: the buckets' streams (and their handles' slots), the deferred passes on the
     // tail streams, the object's own stream
-    for (auto* h : r->hs) { const int rq = robots_quiesce(h); if (rq != SRBDQP_OK) { r->err = h->err; return rq; } }
+    for (auto* h : r->hs) { const int rq = quiesce_all_streams(h); if (rq != SRBDQP_OK) { r->err = h->err; return rq; } }
     for (auto ts : r->tail_st) HIP_TRY(r, hipStreamSynchronize(ts));
     HIP_TRY(r, hipStreamSynchronize(r->stream));
     if (clear) { r->robots = nullptr; r->robots_len = 0; return ragged_forward_robots(r); }
@@ -2270,8 +2253,7 @@ int srbdqp_ragged_set_robots_device(srbdqp_ragged* r, const srbdqp_robot* dev, i
     if (!r) return SRBDQP_E_INVALID;
     if (dev && length < 0) { r->err = "srbdqp_ragged_set_robots_device: negative length"; return SRBDQP_E_INVALID; }
     const bool clear = !dev || length == 0;
-    if (!clear) for (auto* bh : r->hs) if (bh->live_nstar) { live_refuse(bh, "per-QP robot records on a ragged object"); r->err = bh->err; return SRBDQP_E_INVALID; }
-    if (!clear) for (int hz : r->horizons) if (hz > kRobotsMaxHorizon) { r->err = std::string("bucket N=") + std::to_string(hz) + ": " + robots_n24; return SRBDQP_E_INVALID; }
+    if (!clear) if (const int rc = ragged_robots_check(r)) return rc;
     r->robots = clear ? nullptr : dev;
     r->robots_len = clear ? 0 : (size_t)length;
     return ragged_forward_robots(r);

@@ -2307,21 +2307,39 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     SRBDQP_STAMP(a, b, 9);
 }
 
-template <int N, typename R, typename TIO, int MODE, int WPS, typename TT = double, int SPW = 5, int XW = 0>
-__global__ __launch_bounds__((WrenchSmem<N, 8, SPW, XW>::BT), WPS) void srbdqp_wrench_kernel(KArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    if ((int)blockIdx.x >= a.B) return;
+// The prologue that every __global__ wrapper below shares, as two predicates.  Only these are factored: each wrapper keeps its own wrench_qp<...>(...) call and
+// signal_done(a).  (One forceinline entry function around the prologue AND the wrench_qp call was tried: it changed the text of all 25 solve instantiations --
+// 256 -> 254 VGPRs at N = 20, 230 -> 229 at N = 16, wrench_f32 N = 24 on fp64 tiles 92 -> 84 bytes of scratch -- which breaks the exact pins of
+// tests/test_any_horizon_cpu.py and would need the speed measured again.  With the two predicates every kernel's text is what the five literal copies gave.)
+//
+// ... is this workgroup part of the launch: inside the batch, and, in an fp32 call (tile_sel), of the half that this launch takes.  MODE = 2 to 5 keep the tile_sel
+// block though an fp64 launch never sets it: without it hipcc allocates the MODE = 2, N = 20 instantiation -- 256 VGPRs, 106 SGPRs, like its MODE = 0 twin -- with
+// 12 bytes per lane in scratch memory.
+template <int N>
+__device__ __forceinline__ bool wrench_block_in_launch(const KArgs& a) {
+    if ((int)blockIdx.x >= a.B) return false;
     if (a.tile_sel) {   // fp32 calls: this launch takes the QPs with (1) / without (2) wrench coordinates only
         const uint32_t* cf = reinterpret_cast<const uint32_t*>(a.contact + (size_t)SRBDQP_QP_INDEX(a) * (N * 4));   // 4 flags per step
         const int lane = threadIdx.x & 63;
         const uint32_t v = cf[lane < N ? lane : 0];
         const int nc = ((v & 0xffu) ? 1 : 0) + ((v & 0xff00u) ? 1 : 0) + ((v & 0xff0000u) ? 1 : 0) + ((v & 0xff000000u) ? 1 : 0);
         const bool wrench_only = __ballot(lane < N && (nc == 1 || nc == 2)) == 0ull;
-        if (wrench_only != (a.tile_sel == 1)) return;
+        if (wrench_only != (a.tile_sel == 1)) return false;
     }
-    // restart pass: the workgroup of a QP that did not end at the cap leaves at once; no loop over QPs here -- any loop around the body makes hipcc
-    // hoist the body's lane-index expressions out of it and spill them (750 bytes of scratch per lane at N = 20)
-    if ((!a.count_ptr || (int)blockIdx.x < *a.count_ptr) && !SRBDQP_RESTART_SKIP(a, SRBDQP_QP_INDEX(a)))
+    return true;
+}
+
+// ... has its QP work in this pass: in a restart pass the workgroup of a QP that did not end at the cap leaves at once.  A test, not a loop over QPs: any loop
+// around the body makes hipcc hoist the body's lane-index expressions out of it and spill them (750 bytes of scratch per lane at N = 20).
+__device__ __forceinline__ bool wrench_block_has_work(const KArgs& a) {
+    return (!a.count_ptr || (int)blockIdx.x < *a.count_ptr) && !SRBDQP_RESTART_SKIP(a, SRBDQP_QP_INDEX(a));
+}
+
+template <int N, typename R, typename TIO, int MODE, int WPS, typename TT = double, int SPW = 5, int XW = 0>
+__global__ __launch_bounds__((WrenchSmem<N, 8, SPW, XW>::BT), WPS) void srbdqp_wrench_kernel(KArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    if (!wrench_block_in_launch<N>(a)) return;
+    if (wrench_block_has_work(a))
         wrench_qp<N, R, TIO, MODE, TT, SPW, XW>(a, SRBDQP_QP_INDEX(a), sm);
     signal_done(a);   // staged path: every workgroup of the launch reports once, with or without work (done_cs is for the *_in kernels only)
 }
@@ -2333,75 +2351,41 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, SPW, XW>::BT), WPS) void srbdqp_w
 template <int N, typename R, typename TIO, int MODE, int WPS, typename TT = double, int SPW = 5, int XW = 0, typename = std::enable_if_t<MODE == 2>>
 __global__ __launch_bounds__((WrenchSmem<N, 8, SPW, XW>::BT), WPS) void srbdqp_wrench_kernel(KArgs a, const double* __restrict__ robots) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    if ((int)blockIdx.x >= a.B) return;
-    // (the one-argument kernel's prologue, word for word, though an fp64 launch never sets tile_sel: without it hipcc allocates the N = 20 instantiation
-    //  -- 256 VGPRs, 106 SGPRs, like its MODE = 0 twin -- with 12 bytes per lane in scratch memory)
-    if (a.tile_sel) {
-        const uint32_t* cf = reinterpret_cast<const uint32_t*>(a.contact + (size_t)SRBDQP_QP_INDEX(a) * (N * 4));   // 4 flags per step
-        const int lane = threadIdx.x & 63;
-        const uint32_t v = cf[lane < N ? lane : 0];
-        const int nc = ((v & 0xffu) ? 1 : 0) + ((v & 0xff00u) ? 1 : 0) + ((v & 0xff0000u) ? 1 : 0) + ((v & 0xff000000u) ? 1 : 0);
-        const bool wrench_only = __ballot(lane < N && (nc == 1 || nc == 2)) == 0ull;
-        if (wrench_only != (a.tile_sel == 1)) return;
-    }
-    if ((!a.count_ptr || (int)blockIdx.x < *a.count_ptr) && !SRBDQP_RESTART_SKIP(a, SRBDQP_QP_INDEX(a)))
+    if (!wrench_block_in_launch<N>(a)) return;
+    if (wrench_block_has_work(a))
         wrench_qp<N, R, TIO, MODE, TT, SPW, XW>(a, SRBDQP_QP_INDEX(a), sm, robots);
     signal_done(a);
 }
 
 // ... MODE = 3: a live horizon nl <= N (SRBDQP_FLAG_ANY_HORIZON), as the second kernel argument for the same reasons: KArgs keeps its size, and every launch of a
-// solve -- restart, deferred and ragged passes included -- reaches it through the launcher.  (The prologue word for word, as above.)
+// solve -- restart, deferred and ragged passes included -- reaches it through the launcher.
 template <int N, typename R, typename TIO, int MODE, int WPS, typename TT = double, int SPW = 5, int XW = 0, typename = std::enable_if_t<MODE == 3>>
 __global__ __launch_bounds__((WrenchSmem<N, 8, SPW, XW>::BT), WPS) void srbdqp_wrench_kernel(KArgs a, const int nl) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    if ((int)blockIdx.x >= a.B) return;
-    if (a.tile_sel) {
-        const uint32_t* cf = reinterpret_cast<const uint32_t*>(a.contact + (size_t)SRBDQP_QP_INDEX(a) * (N * 4));   // 4 flags per step
-        const int lane = threadIdx.x & 63;
-        const uint32_t v = cf[lane < N ? lane : 0];
-        const int nc = ((v & 0xffu) ? 1 : 0) + ((v & 0xff00u) ? 1 : 0) + ((v & 0xff0000u) ? 1 : 0) + ((v & 0xff000000u) ? 1 : 0);
-        const bool wrench_only = __ballot(lane < N && (nc == 1 || nc == 2)) == 0ull;
-        if (wrench_only != (a.tile_sel == 1)) return;
-    }
-    if ((!a.count_ptr || (int)blockIdx.x < *a.count_ptr) && !SRBDQP_RESTART_SKIP(a, SRBDQP_QP_INDEX(a)))
+    if (!wrench_block_in_launch<N>(a)) return;
+    if (wrench_block_has_work(a))
         wrench_qp<N, R, TIO, MODE, TT, SPW, XW>(a, SRBDQP_QP_INDEX(a), sm, nullptr, nl);
     signal_done(a);
 }
 
 // ... MODE = 4: contact normals (srbdqp_set_contact_normals / _device): normals = the handle's array, 12 N doubles per QP in the CALLER's QP order, as the second
-// kernel argument for the same reasons.  fp64, batch form only, so the kernel has a name of its own with two template arguments.  (The prologue word for word, as above.)
+// kernel argument for the same reasons.  fp64, batch form only, so the kernel has a name of its own with two template arguments.
 template <int N, int WPS>
 __global__ __launch_bounds__((WrenchSmem<N, 8, 5, 0>::BT), WPS) void srbdqp_wrench_cn_kernel(KArgs a, const double* __restrict__ normals) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    if ((int)blockIdx.x >= a.B) return;
-    if (a.tile_sel) {
-        const uint32_t* cf = reinterpret_cast<const uint32_t*>(a.contact + (size_t)SRBDQP_QP_INDEX(a) * (N * 4));   // 4 flags per step
-        const int lane = threadIdx.x & 63;
-        const uint32_t v = cf[lane < N ? lane : 0];
-        const int nc = ((v & 0xffu) ? 1 : 0) + ((v & 0xff00u) ? 1 : 0) + ((v & 0xff0000u) ? 1 : 0) + ((v & 0xff000000u) ? 1 : 0);
-        const bool wrench_only = __ballot(lane < N && (nc == 1 || nc == 2)) == 0ull;
-        if (wrench_only != (a.tile_sel == 1)) return;
-    }
-    if ((!a.count_ptr || (int)blockIdx.x < *a.count_ptr) && !SRBDQP_RESTART_SKIP(a, SRBDQP_QP_INDEX(a)))
+    if (!wrench_block_in_launch<N>(a)) return;
+    if (wrench_block_has_work(a))
         wrench_qp<N, double, double, 4, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm, nullptr, N, normals);
     signal_done(a);
 }
 
 // ... MODE = 5: rank-aware wrench steps (SRBDQP_FLAG_RANK_AWARE).  fp64, batch form only, one argument; a name of its own with two template arguments, as MODE = 4
-// (tests/test_any_horizon_cpu.py pins the list of srbdqp_wrench_kernel's instantiations).  (The prologue word for word, as above.)
+// (tests/test_any_horizon_cpu.py pins the list of srbdqp_wrench_kernel's instantiations).
 template <int N, int WPS>
 __global__ __launch_bounds__((WrenchSmem<N, 8, 5, 0>::BT), WPS) void srbdqp_wrench_ra_kernel(KArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    if ((int)blockIdx.x >= a.B) return;
-    if (a.tile_sel) {
-        const uint32_t* cf = reinterpret_cast<const uint32_t*>(a.contact + (size_t)SRBDQP_QP_INDEX(a) * (N * 4));   // 4 flags per step
-        const int lane = threadIdx.x & 63;
-        const uint32_t v = cf[lane < N ? lane : 0];
-        const int nc = ((v & 0xffu) ? 1 : 0) + ((v & 0xff00u) ? 1 : 0) + ((v & 0xff0000u) ? 1 : 0) + ((v & 0xff000000u) ? 1 : 0);
-        const bool wrench_only = __ballot(lane < N && (nc == 1 || nc == 2)) == 0ull;
-        if (wrench_only != (a.tile_sel == 1)) return;
-    }
-    if ((!a.count_ptr || (int)blockIdx.x < *a.count_ptr) && !SRBDQP_RESTART_SKIP(a, SRBDQP_QP_INDEX(a)))
+    if (!wrench_block_in_launch<N>(a)) return;
+    if (wrench_block_has_work(a))
         wrench_qp<N, double, double, 5, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm);
     signal_done(a);
 }

@@ -1,0 +1,183 @@
+"""Which C-ABI call has a form for which variant of the general kernel (srbdqp.hip, `Variant` and the masks of `require_form`): a handle is plain, or has robot
+records set, or contact normals set, or a live horizon (SRBDQP_FLAG_ANY_HORIZON), or rank-aware steps (SRBDQP_FLAG_RANK_AWARE) -- never two of them.  Through the
+Python bindings, on one handle per variant, every entry point of the table below either returns SRBDQP_E_INVALID with a message that names the call and ends in
+the variant's fixed text, or returns SRBDQP_OK.  Nothing here looks at numbers: the variants' own suites do (test_gpu_robots.py, test_gpu_contact_normals.py,
+test_gpu_any_horizon.py, test_gpu_rank_aware.py).  The smallest shapes that reach every branch: N = 4 (a live horizon: 3, which runs on N* = 4), two QPs of full
+double support."""
+import numpy as np
+import pytest
+
+import srbd_oracle as orc
+import normals_twin as nt
+
+pytestmark = pytest.mark.gpu
+B = 2
+VARIANTS = ("robots", "normals", "live", "rank_aware")
+
+# the fixed text behind "<call>: " in a refusal, per variant of the handle
+TAIL = dict(
+    robots="refused while per-QP robot records are set (srbdqp_set_robots): only the fp64 batch and ragged solves on the general kernel read them "
+           "-- one robot for every QP goes in srbdqp_config",
+    normals="refused while contact normals are set (srbdqp_set_contact_normals): only the fp64 batch solves on the general kernel read them "
+            "-- srbdqp_set_contact_normals(h, NULL, 0) goes back to flat ground",
+    live="refused on a handle whose horizon 3 was admitted by SRBDQP_FLAG_ANY_HORIZON: only the fp64 batch, ragged and staged solves run a live horizon "
+         "(the general kernel's fp64 batch instantiation for N = 4)",
+    rank_aware="refused on a handle created with SRBDQP_FLAG_RANK_AWARE: only the fp64 batch and staged solves have rank-aware wrench steps "
+               "(the general kernel's fp64 batch instantiation, flat ground, srbdqp_config's single robot)")
+# (the normals setters say why records and normals do not combine, not what reads the records)
+NORMALS_ON_ROBOTS = "refused while per-QP robot records are set (srbdqp_set_robots): no instantiation reads both (DESIGN.md section 13)"
+
+ALL = frozenset(VARIANTS)
+# call -> the variants whose handle it refuses; every other variant's handle it accepts.  In the order the calls are made (prepare before solve_prepared).
+REFUSES = {
+    "srbdqp_solve_batch_f64": frozenset(),
+    "srbdqp_solve_batch_device_f64": frozenset(),
+    "srbdqp_solve_staged_f64": frozenset({"robots", "normals"}),
+    "srbdqp_update_f64": frozenset({"robots", "normals"}),
+    "srbdqp_prepare_staged_f64": frozenset({"robots", "normals", "live"}),
+    "srbdqp_solve_prepared_f64": frozenset({"robots", "normals", "live"}),
+    "srbdqp_solve_batch_f32": ALL,
+    "srbdqp_solve_batch_device_f32": ALL,
+    "srbdqp_assemble_f64": frozenset({"robots", "normals", "live"}),
+    "srbdqp_assemble_wrench_f64": ALL,
+    "srbdqp_set_robots": frozenset({"normals", "live", "rank_aware"}),
+    "srbdqp_set_robots_device": frozenset({"normals", "live", "rank_aware"}),
+    "srbdqp_set_contact_normals": frozenset({"robots", "live", "rank_aware"}),
+    "srbdqp_set_contact_normals_device": frozenset({"robots", "live", "rank_aware"}),
+}
+
+
+@pytest.fixture(scope="module")
+def torch_first():
+    import torch  # load torch's HIP runtime before libsrbdqp.so so both share one
+    assert torch.cuda.is_available()
+    return torch
+
+
+def _engine(variant):
+    """-> (engine, its horizon); records and normals are set by the test."""
+    from g1_locomotion_amd import BatchMPC
+    if variant == "live":
+        return BatchMPC(horizon=3), 3
+    return BatchMPC(horizon=4, rank_aware=(variant == "rank_aware")), 4
+
+
+def _calls(torch, eng, N):
+    """call name -> a function that makes the call on eng with two QPs of full double support (raises SrbdqpError unless the call returns SRBDQP_OK)."""
+    from g1_locomotion_amd import _lib
+    from g1_locomotion_amd.mpc import robots_array
+    x0, xr, ft, ct = orc.synthetic_batch(B, N, seed=610 + N, schedule="double")
+    assert ct.all()
+    ct8 = np.ascontiguousarray(ct != 0, dtype=np.uint8)
+    st = eng.stage()
+    st["x0"][:B], st["x_ref"][:B], st["foot"][:B], st["contact"][:B] = x0, xr, ft, ct8
+    dev = {dt: [torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).cuda() for a in (x0, xr, ft)] + [torch.from_numpy(ct8).cuda(),
+                torch.empty((B, N, 12), dtype=getattr(torch, np.dtype(dt).name), device="cuda")] for dt in (np.float64, np.float32)}
+    rb, nr = robots_array(B, mass=[30.0, 40.0]), nt.wedge_normals(B, N)
+    rb_dev, nr_dev = torch.from_numpy(rb).cuda(), torch.from_numpy(nr).cuda()
+    raw = _lib.load()
+
+    def device(dt):
+        a = [t.data_ptr() for t in dev[dt]]
+        eng.solve_device(B, a[0], a[1], a[2], a[3], a[4], f32=(dt == np.float32))
+        eng.synchronize()
+
+    def update():
+        u0 = np.zeros(12)
+        _lib.check(raw.srbdqp_update_f64(eng._h, x0[0].ctypes.data, xr[0].ctypes.data, ft[0].ctypes.data, ct8[0].ctypes.data, None, u0.ctypes.data,
+                                         None, None, None, None), eng._h)
+
+    return {
+        "srbdqp_solve_batch_f64": lambda: eng.solve(x0, xr, ft, ct),
+        "srbdqp_solve_batch_device_f64": lambda: device(np.float64),
+        "srbdqp_solve_staged_f64": lambda: eng.solve_staged(B),
+        "srbdqp_update_f64": update,
+        "srbdqp_prepare_staged_f64": lambda: eng.prepare_staged(B),
+        "srbdqp_solve_prepared_f64": lambda: eng.solve_prepared(B),
+        "srbdqp_solve_batch_f32": lambda: eng.solve(x0, xr, ft, ct, dtype=np.float32),
+        "srbdqp_solve_batch_device_f32": lambda: device(np.float32),
+        "srbdqp_assemble_f64": lambda: eng.assemble(x0, xr, ft, ct),
+        "srbdqp_assemble_wrench_f64": lambda: eng.assemble_wrench(x0, xr, ft, ct),
+        "srbdqp_set_robots": lambda: eng.set_robots(rb),
+        "srbdqp_set_robots_device": lambda: eng.set_robots(rb_dev),
+        "srbdqp_set_contact_normals": lambda: eng.set_contact_normals(nr),
+        "srbdqp_set_contact_normals_device": lambda: eng.set_contact_normals(nr_dev),
+    }
+
+
+def _refusal(fn):
+    """The message of the SrbdqpError that fn() raises, or None when it returns."""
+    from g1_locomotion_amd import SrbdqpError
+    try:
+        fn()
+    except SrbdqpError as e:
+        return str(e)
+    return None
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+def test_every_call_refuses_or_accepts_the_variant(torch_first, built_lib, variant):
+    from g1_locomotion_amd import _lib
+    eng, N = _engine(variant)
+    with eng:
+        calls = _calls(torch_first, eng, N)
+        assert list(calls) == list(REFUSES)
+        if variant == "robots":
+            calls["srbdqp_set_robots"]()
+        if variant == "normals":
+            calls["srbdqp_set_contact_normals"]()
+        for name, refusing in REFUSES.items():
+            msg = _refusal(calls[name])
+            print(f"{variant:10s} {name:34s} -> {msg or 'SRBDQP_OK'}")
+            if variant in refusing:
+                tail = NORMALS_ON_ROBOTS if (variant == "robots" and "contact_normals" in name) else TAIL[variant]
+                assert msg == f"srbdqp error {_lib.E_INVALID}: {name}: {tail}", (variant, name, msg)
+            else:
+                assert msg is None, (variant, name, msg)
+        if variant == "live":
+            return
+        # the clearing calls succeed on every handle, and leave it in its base state: plain (what records or normals refused runs again, and the other setter
+        # is accepted), or rank-aware still
+        eng.set_robots(None)
+        eng.set_contact_normals(None)
+        eng.set_robots(torch_first.empty((0, 8), dtype=torch_first.float64, device="cuda"))
+        eng.set_contact_normals(torch_first.empty((0, N, 12), dtype=torch_first.float64, device="cuda"))
+        if variant == "rank_aware":
+            assert _refusal(calls["srbdqp_solve_batch_f32"]) == f"srbdqp error {_lib.E_INVALID}: srbdqp_solve_batch_f32: {TAIL[variant]}"
+            assert _refusal(calls["srbdqp_set_robots"]) == f"srbdqp error {_lib.E_INVALID}: srbdqp_set_robots: {TAIL[variant]}"
+        else:
+            for name in ("srbdqp_solve_staged_f64", "srbdqp_solve_batch_f32", "srbdqp_assemble_wrench_f64"):
+                assert _refusal(calls[name]) is None, (variant, name)
+            other = "srbdqp_set_contact_normals" if variant == "robots" else "srbdqp_set_robots"
+            assert _refusal(calls[other]) is None
+            assert _refusal(calls["srbdqp_solve_batch_f64"]) is None and eng.kernel_name() == ("wrench_f64_n4_cn" if variant == "robots" else "wrench_f64_n4_rb")
+        assert _refusal(calls["srbdqp_solve_batch_f64"]) is None
+
+
+def test_ragged_objects(torch_first, built_lib):
+    """The ragged rows of the table: no fp32 solve and no robot records with a live bucket, no records with an N = 24 bucket, no rank-aware object."""
+    from g1_locomotion_amd import RaggedMPC, SrbdqpError, _lib
+    from g1_locomotion_amd.mpc import robots_array
+    rb = robots_array(B)
+    with pytest.raises(SrbdqpError, match="SRBDQP_FLAG_RANK_AWARE: ragged objects have no rank-aware form"):
+        RaggedMPC(horizons=(4, 8), flags=_lib.FLAG_RANK_AWARE)
+    rag = RaggedMPC(horizons=(3, 4))
+    try:
+        qp = [orc.synthetic_batch(1, n, seed=620 + n, schedule="double") for n in (3, 4)]
+        packed = ([3, 4], np.concatenate([q[0] for q in qp]), np.concatenate([q[1][0] for q in qp]), np.concatenate([q[2][0] for q in qp]),
+                  np.concatenate([q[3][0] for q in qp]))
+        assert _refusal(lambda: rag.solve_packed(*packed, dtype=np.float32)) == f"srbdqp error {_lib.E_INVALID}: an fp32 ragged solve: {TAIL['live']}"
+        for arg in (rb, torch_first.from_numpy(rb).cuda()):
+            assert _refusal(lambda: rag.set_robots(arg)) == f"srbdqp error {_lib.E_INVALID}: per-QP robot records on a ragged object: {TAIL['live']}"
+        rag.set_robots(None)
+        rag.solve_packed(*packed)
+    finally:
+        rag.close()
+    rag = RaggedMPC(horizons=(4, 24))
+    try:
+        for arg in (rb, torch_first.from_numpy(rb).cuda()):
+            msg = _refusal(lambda: rag.set_robots(arg))
+            assert msg is not None and msg.startswith(f"srbdqp error {_lib.E_INVALID}: bucket N=24: per-QP robot records: not at N = 24"), msg
+        rag.set_robots(None)
+    finally:
+        rag.close()
