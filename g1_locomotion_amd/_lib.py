@@ -37,7 +37,7 @@ EXPORTS = (
     "srbdqp_assemble_f64", "srbdqp_assemble_wrench_f64",
     "srbdqp_ragged_create", "srbdqp_ragged_destroy", "srbdqp_ragged_last_error", "srbdqp_ragged_flush", "srbdqp_solve_ragged_device_f64", "srbdqp_solve_ragged_f64",
     "srbdqp_solve_ragged_device_f32", "srbdqp_solve_ragged_f32", "srbdqp_solve_ragged_warm_device_f64", "srbdqp_solve_ragged_warm_device_f32",
-    "srbdqp_set_schedule_hint", "srbdqp_set_robots", "srbdqp_set_robots_device", "srbdqp_set_contact_normals", "srbdqp_set_contact_normals_device", "srbdqp_ragged_set_robots", "srbdqp_ragged_set_robots_device", "srbdqp_flush", "srbdqp_shard_range", "srbdqp_gather_u0_f64", "srbdqp_stage_ptrs", "srbdqp_solve_staged_f64", "srbdqp_update_f64", "srbdqp_prepare_staged_f64", "srbdqp_solve_prepared_f64", "srbdqp_set_stamp_buffer", "srbdqp_synchronize", "srbdqp_last_kernel_ms", "srbdqp_last_kernel_parts_ms", "srbdqp_kernel_name", "srbdqp_batch1_launch_path", "srbdqp_version",
+    "srbdqp_set_schedule_hint", "srbdqp_set_robots", "srbdqp_set_robots_device", "srbdqp_set_contact_normals", "srbdqp_set_contact_normals_device", "srbdqp_ragged_set_robots", "srbdqp_ragged_set_robots_device", "srbdqp_set_weights", "srbdqp_set_weights_device", "srbdqp_ragged_set_weights", "srbdqp_ragged_set_weights_device", "srbdqp_flush", "srbdqp_shard_range", "srbdqp_gather_u0_f64", "srbdqp_stage_ptrs", "srbdqp_solve_staged_f64", "srbdqp_update_f64", "srbdqp_prepare_staged_f64", "srbdqp_solve_prepared_f64", "srbdqp_set_stamp_buffer", "srbdqp_synchronize", "srbdqp_last_kernel_ms", "srbdqp_last_kernel_parts_ms", "srbdqp_kernel_name", "srbdqp_batch1_launch_path", "srbdqp_version",
     # include/srbdqp_cascade.h
     "srbdqp_swing_f64", "srbdqp_swing_device_f64", "srbdqp_wbid_reference_f64", "srbdqp_wbid_reference_device_f64",
     "srbdqp_mpc_inputs_f64", "srbdqp_mpc_inputs_device_f64",
@@ -100,6 +100,36 @@ def robots_array(B, mass=None, inertia=None, mu=None, fz_min=None, fz_max=None, 
     out[:, 4] = col("mu", mu, cfg.mu, 1)
     out[:, 5] = col("fz_min", fz_min, cfg.fz_min, 1)
     out[:, 6] = col("fz_max", fz_max, cfg.fz_max, 1)
+    return out
+
+
+class Weights(C.Structure):
+    """srbdqp_weights (include/srbdqp.h): one QP's cost weights, 128 bytes -- the row layout of weights_array()."""
+    _fields_ = [("q_diag", C.c_double * NX), ("r_diag", C.c_double), ("reserved", C.c_double * 2)]
+
+
+WEIGHTS_DOUBLES = 16   # C.sizeof(Weights) // 8: q_diag[13], r_diag, reserved[2]
+
+
+def weights_array(B, q_diag=None, r_diag=None, cfg=None):
+    """(B, 16) float64 array of srbdqp_weights records for BatchMPC.set_weights / RaggedMPC.set_weights.  q_diag is a scalar (every entry of every QP), of
+    shape (13,) (every QP) or (B, 13); r_diag a scalar or of shape (B,); a value not given is the config's (cfg, default: default_config()).
+    reserved = 0.  Raises ValueError on a shape that does not broadcast."""
+    import numpy as np
+    B = int(B)
+    if B < 0:
+        raise ValueError("B must be >= 0")
+    if cfg is None:
+        cfg = default_config()
+    out = np.zeros((B, WEIGHTS_DOUBLES), np.float64)
+    q = np.asarray(list(cfg.q_diag) if q_diag is None else q_diag, np.float64)
+    if q.shape not in ((), (NX,), (B, NX)):
+        raise ValueError(f"q_diag: expected a scalar or shape ({NX},) or ({B}, {NX}), got {q.shape}")
+    r = np.asarray(cfg.r_diag if r_diag is None else r_diag, np.float64)
+    if r.shape not in ((), (B,)):
+        raise ValueError(f"r_diag: expected a scalar or shape ({B},), got {r.shape}")
+    out[:, :NX] = np.broadcast_to(q, (B, NX))
+    out[:, NX] = np.broadcast_to(r, (B,))
     return out
 
 
@@ -210,6 +240,7 @@ def load():
     lib.srbdqp_set_schedule_hint.argtypes = [H, C.c_void_p, C.c_int32]
     lib.srbdqp_set_schedule_hint.restype = C.c_int
     for _fn in (lib.srbdqp_set_robots, lib.srbdqp_set_robots_device, lib.srbdqp_ragged_set_robots, lib.srbdqp_ragged_set_robots_device,
+                lib.srbdqp_set_weights, lib.srbdqp_set_weights_device, lib.srbdqp_ragged_set_weights, lib.srbdqp_ragged_set_weights_device,
                 lib.srbdqp_set_contact_normals, lib.srbdqp_set_contact_normals_device):
         _fn.argtypes = [H, C.c_void_p, C.c_int32]
         _fn.restype = C.c_int

@@ -99,6 +99,11 @@ struct srbdqp_handle {
     size_t robots_len = 0;
     srbdqp_robot* robots_own = nullptr;    // the library's device copy of host records (srbdqp_set_robots)
     size_t robots_cap = 0;
+    // per-QP cost weights (srbdqp_set_weights / _device): what the solves read, or null (the config's q_diag and r_diag for every QP)
+    const srbdqp_weights* weights = nullptr;
+    size_t weights_len = 0;
+    srbdqp_weights* weights_own = nullptr; // the library's device copy of host records (srbdqp_set_weights)
+    size_t weights_cap = 0;
     // contact normals (srbdqp_set_contact_normals / _device): [normals_len][N][12] doubles the fp64 batch solves read, or null (flat ground under every contact)
     const double* normals = nullptr;
     size_t normals_len = 0;                // QPs
@@ -319,7 +324,7 @@ constexpr int kTileClassMinBatch = 512;
 // does a solve of B QPs on this handle go to the general kernel (srbdqp_wrench.hpp)?  launch() asks this.
 inline bool uses_wrench(const srbdqp_handle* h, const Call& c, int maxs, int B) {
     const int N = h->cfg.horizon;
-    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || h->robots || h->normals || h->live_nstar) return true;   // (per-QP records, contact normals, a live horizon: only the general kernel reads them)
+    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || h->robots || h->weights || h->normals || h->live_nstar) return true;   // (per-QP records and weights, contact normals, a live horizon: only the general kernel reads them)
     // N = 20 single support too, for batches: the general kernel holds 2 workgroups per CU there, the compact one 1
     // (tools/schedule_bench.py, 16,384 QPs: 2.85 M QP/s against 1.95 M; at N = 12 / 16 the compact kernel wins, 7.1 / 4.9 M
     // against 5.7 / 4.2 M)
@@ -638,17 +643,21 @@ int launch_compact(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t 
 }
 
 // ---- the variants of the general kernel: which one a handle is in, and which call has a form for it ----
-// A handle is in exactly one of five states.  Live and RankAware are fixed by srbdqp_create; Robots and Normals come and go with the setters (a clearing call --
-// NULL, 0 -- is accepted in every state).  No two hold at once:
+// A handle is in exactly one of six states.  Live and RankAware are fixed by srbdqp_create; Robots, Weights and Normals come and go with the setters (a clearing
+// call -- NULL, 0 -- is accepted in every state).  No two hold at once, except that robot records and weights combine -- such a handle is Robots here, and
+// Weights is the handle with weights alone:
 //   Live x RankAware                      srbdqp_create refuses SRBDQP_FLAG_RANK_AWARE at a live horizon
 //   Robots x Live, Robots x RankAware     robots_check_handle (srbdqp_set_robots / _device, and the ragged pair for every bucket)
 //   Normals x Live, Normals x RankAware   normals_check_handle (srbdqp_set_contact_normals / _device)
 //   Robots x Normals                      each of the two checks refuses while the other is set
-// (srbdqp_ragged_create refuses SRBDQP_FLAG_RANK_AWARE, and a ragged object has no normals: its buckets are Plain, Robots or Live.)
-enum class Variant { Plain, Robots, Normals, Live, RankAware };
+//   Weights x Live, Weights x RankAware, Weights x Normals      weights_check_handle (srbdqp_set_weights / _device, and the ragged pair for every bucket) and
+//                                         normals_check_handle
+// (srbdqp_ragged_create refuses SRBDQP_FLAG_RANK_AWARE, and a ragged object has no normals: its buckets are Plain, Robots, Weights or Live.)
+enum class Variant { Plain, Robots, Normals, Live, RankAware, Weights };
 
 inline Variant variant_of(const srbdqp_handle* h) {
     if (h->robots) return Variant::Robots;
+    if (h->weights) return Variant::Weights;
     if (h->normals) return Variant::Normals;
     if (h->live_nstar) return Variant::Live;
     if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) return Variant::RankAware;
@@ -677,6 +686,10 @@ int refuse(srbdqp_handle* h, Variant v, const char* what) {
         h->err = w + ": refused on a handle created with SRBDQP_FLAG_RANK_AWARE: only the fp64 batch and staged solves have rank-aware wrench steps "
                      "(the general kernel's fp64 batch instantiation, flat ground, srbdqp_config's single robot)";
         break;
+    case Variant::Weights:
+        h->err = w + ": refused while per-QP cost weights are set (srbdqp_set_weights): only the fp64 batch and ragged solves on the general kernel read "
+                     "them -- one pair of weights for every QP goes in srbdqp_config";
+        break;
     }
     return SRBDQP_E_INVALID;
 }
@@ -696,7 +709,9 @@ constexpr unsigned kFormsAssemble = form(Variant::RankAware);
 // srbdqp_assemble_wrench_f64
 constexpr unsigned kFormsAssembleWrench = 0;
 // srbdqp_set_robots / _device with records (robots_check_handle, which refuses N = 24 as well)
-constexpr unsigned kFormsSetRobots = form(Variant::Robots);
+constexpr unsigned kFormsSetRobots = form(Variant::Robots) | form(Variant::Weights);
+// srbdqp_set_weights / _device with records (weights_check_handle, which refuses N = 24 as well): beside robot records or in place of earlier weights
+constexpr unsigned kFormsSetWeights = form(Variant::Weights) | form(Variant::Robots);
 // srbdqp_set_contact_normals / _device with normals (normals_check_handle, which refuses N = 24 as well, and records in words of its own)
 constexpr unsigned kFormsSetNormals = form(Variant::Normals) | form(Variant::Robots);
 
@@ -777,6 +792,19 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
         else { h->err = "the assembly dump is fp64 only"; return SRBDQP_E_INVALID; }
     } else {
         if constexpr (sizeof(R) == 8 && N != 24) {
+            // per-QP cost weights (srbdqp_set_weights / _device), with or without robot records: the MODE = 6 instantiation, the weights and the records (or null)
+            // as its second and third arguments -- every launch of a solve comes through here, as below.  (The weight setters refuse what the record setters do.)
+            if (h->weights) {
+                constexpr size_t lds_wt = lds + 10 * sizeof(double);         // + the QP's robot, r_diag s^2 and the bad-weights mark behind the layout (qp_weights_to_lds)
+                constexpr int by_lds_wt = (S::wgs_of(S::o_end + 10) * S::NW + 3) / 4;
+                constexpr int by_waves = WPS * 4 / S::NW;                     // (workgroups per CU the waves per SIMD admit)
+                static_assert((by_lds_wt < WPS ? by_lds_wt : WPS) == WPS &&
+                              (S::wgs_of(S::o_end + 10) < by_waves ? S::wgs_of(S::o_end + 10) : by_waves) == (S::lds_wgs < by_waves ? S::lds_wgs : by_waves),
+                              "the 80 bytes of LDS cost no workgroup per CU");
+                static const std::string nm_wt = nm + "_wt";
+                return launch_kernel(h, &srbdqp::srbdqp_wrench_wt_kernel<N, WPS>, nm_wt.c_str(), grid, dim3(S::BT), lds_wt, st, a,
+                                     reinterpret_cast<const double*>(h->weights), reinterpret_cast<const double*>(h->robots));
+            }
             // per-QP robot records (srbdqp_set_robots / _device): the MODE = 2 instantiation, the records as its second argument -- every launch of a solve
             // (first pass, restart passes, deferred passes on the tail stream, ragged buckets) comes through here with this handle.  (The entry points refuse
             // the staged, fp32 and dump calls while records are set, and the setters refuse N = 24: kRobotsMaxHorizon.)
@@ -1120,6 +1148,34 @@ int robots_check_handle(srbdqp_handle* h, const char* fn) {
     return SRBDQP_OK;
 }
 
+// ---- per-QP cost weights (srbdqp_set_weights) ----
+static_assert(sizeof(srbdqp_weights) == 128 && offsetof(srbdqp_weights, r_diag) == 104 && offsetof(srbdqp_weights, reserved) == 112,
+              "the kernels read a record as 16 doubles (srbdqp_wrench.hpp qp_weights_to_lds)");
+
+// the rules of include/srbdqp.h (the same ones the kernel applies to device records, srbdqp_wrench.hpp qp_weights_to_lds); null = valid, else what is wrong
+// ("finite" is < SRBDQP_WEIGHT_MAX = 1e300 on both sides: the kernel tests one bound, and r_diag s s must not overflow)
+const char* weights_fault(const srbdqp_weights& r) {
+    for (int i = 0; i < SRBDQP_NX; ++i) if (!(r.q_diag[i] >= 0.0 && r.q_diag[i] < SRBDQP_WEIGHT_MAX)) return "q_diag must be finite (< 1e300) and >= 0";
+    if (!(r.r_diag > 0.0 && r.r_diag < SRBDQP_WEIGHT_MAX)) return "r_diag must be finite (< 1e300) and > 0";
+    if (r.reserved[0] != 0.0 || r.reserved[1] != 0.0) return "reserved must be 0";
+    return nullptr;
+}
+
+int weights_validate(const srbdqp_weights* host, int32_t length, const char* fn, std::string& err) {
+    for (int32_t i = 0; i < length; ++i)
+        if (const char* why = weights_fault(host[i])) { err = std::string(fn) + ": record " + std::to_string(i) + " is invalid (" + why + "); the previous setting is kept"; return SRBDQP_E_INVALID; }
+    return SRBDQP_OK;
+}
+
+// may this handle take weights?  (contact normals, a live horizon, rank-aware steps: refused with their own texts; N = 24 as for robot records -- the MODE = 6
+// instantiation is the MODE = 2 one with one more LDS slot)
+const char* const weights_n24 = "per-QP cost weights: not at N = 24 (no instantiation of the general kernel reads them there without scratch memory, DESIGN.md section 15)";
+int weights_check_handle(srbdqp_handle* h, const char* fn) {
+    if (const int rc = require_form(h, fn, kFormsSetWeights)) return rc;
+    if (h->cfg.horizon > kRobotsMaxHorizon) { h->err = weights_n24; return SRBDQP_E_INVALID; }
+    return SRBDQP_OK;
+}
+
 // before the library's own copy of the records or of the normals is replaced: every solve that may still read it has completed (srbdqp_synchronize, then every
 // other launch stream of the handle and its tail streams -- deferred restart passes read them too)
 int quiesce_all_streams(srbdqp_handle* h) {
@@ -1157,13 +1213,18 @@ int normals_check_handle(srbdqp_handle* h, const char* fn) {
 // fp64 batch solve of B QPs with records or normals set: the general kernel, and a record / a block of normals for every QP
 int variant_check_batch(srbdqp_handle* h, int32_t B) {
     const Variant v = variant_of(h);
-    if (v != Variant::Robots && v != Variant::Normals) return SRBDQP_OK;
+    if (v != Variant::Robots && v != Variant::Normals && v != Variant::Weights) return SRBDQP_OK;
     const bool rb = v == Variant::Robots;
     if (h->cfg.kernel != SRBDQP_KERNEL_AUTO && h->cfg.kernel != SRBDQP_KERNEL_WRENCH) {
-        h->err = std::string(rb ? "per-QP robot records" : "contact normals (srbdqp_set_contact_normals)") +
+        h->err = std::string(rb ? "per-QP robot records" : v == Variant::Weights ? "per-QP cost weights (srbdqp_set_weights)" : "contact normals (srbdqp_set_contact_normals)") +
                  " are read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH while they are set";
         return SRBDQP_E_INVALID;
     }
+    if (h->weights && (size_t)B > h->weights_len) {      // (weights alone, or beside robot records: each length on its own)
+        h->err = "solve of " + std::to_string(B) + " QPs with " + std::to_string(h->weights_len) + " weight records set (srbdqp_set_weights): every QP needs its record";
+        return SRBDQP_E_INVALID;
+    }
+    if (v == Variant::Weights) return SRBDQP_OK;
     const size_t len = rb ? h->robots_len : h->normals_len;
     if ((size_t)B > len) {
         h->err = "solve of " + std::to_string(B) + " QPs with " + (rb ? std::to_string(len) + " robot records set (srbdqp_set_robots): every QP needs its record"
@@ -1320,6 +1381,7 @@ int srbdqp_destroy(srbdqp_handle* h) {
     }
     if (h->done_count) (void)hipFree(h->done_count);
     if (h->robots_own) (void)hipFree(h->robots_own);
+    if (h->weights_own) (void)hipFree(h->weights_own);
     if (h->normals_own) (void)hipFree(h->normals_own);
     if (h->stage_host) (void)hipHostFree(h->stage_host);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1491,6 +1553,37 @@ int srbdqp_set_robots_device(srbdqp_handle* h, const srbdqp_robot* dev, int32_t 
     if (!clear) if (const int rc = robots_check_handle(h, "srbdqp_set_robots_device")) return rc;
     h->robots = clear ? nullptr : dev;
     h->robots_len = clear ? 0 : (size_t)length;
+    return SRBDQP_OK;
+}
+
+int srbdqp_set_weights(srbdqp_handle* h, const srbdqp_weights* host, int32_t length) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (host && length < 0) { h->err = "srbdqp_set_weights: negative length"; return SRBDQP_E_INVALID; }
+    const bool clear = !host || length == 0;
+    if (!clear) {
+        int rv = weights_check_handle(h, "srbdqp_set_weights");
+        if (rv == SRBDQP_OK) rv = weights_validate(host, length, "srbdqp_set_weights", h->err);
+        if (rv != SRBDQP_OK) return rv;
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    int rc = quiesce_all_streams(h);                // (deferred passes may still read the records this call replaces)
+    if (rc != SRBDQP_OK) return rc;
+    if (clear) { h->weights = nullptr; h->weights_len = 0; return SRBDQP_OK; }
+    if ((size_t)length > h->weights_cap) { h->weights = nullptr; h->weights_len = 0; }
+    rc = grow(h, h->weights_own, h->weights_cap, (size_t)length, nullptr, "hipMalloc weight records");
+    if (rc != SRBDQP_OK) return rc;
+    HIP_TRY(h, hipMemcpy(h->weights_own, host, sizeof(srbdqp_weights) * (size_t)length, hipMemcpyHostToDevice));
+    h->weights = h->weights_own; h->weights_len = (size_t)length;
+    return SRBDQP_OK;
+}
+
+int srbdqp_set_weights_device(srbdqp_handle* h, const srbdqp_weights* dev, int32_t length) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (dev && length < 0) { h->err = "srbdqp_set_weights_device: negative length"; return SRBDQP_E_INVALID; }
+    const bool clear = !dev || length == 0;
+    if (!clear) if (const int rc = weights_check_handle(h, "srbdqp_set_weights_device")) return rc;
+    h->weights = clear ? nullptr : dev;
+    h->weights_len = clear ? 0 : (size_t)length;
     return SRBDQP_OK;
 }
 
@@ -1958,6 +2051,10 @@ struct srbdqp_ragged {
     const srbdqp_robot* robots = nullptr;
     size_t robots_len = 0;
     srbdqp_robot* robots_own = nullptr; size_t robots_cap = 0;
+    // per-QP cost weights in the caller's QP order (srbdqp_ragged_set_weights / _device), forwarded the same way
+    const srbdqp_weights* weights = nullptr;
+    size_t weights_len = 0;
+    srbdqp_weights* weights_own = nullptr; size_t weights_cap = 0;
     std::string err;
 };
 
@@ -2030,6 +2127,7 @@ int srbdqp_ragged_destroy(srbdqp_ragged* r) {
     if (r->h_off) (void)hipHostFree(r->h_off);
     if (r->ws) (void)hipFree(r->ws);
     if (r->robots_own) (void)hipFree(r->robots_own);
+    if (r->weights_own) (void)hipFree(r->weights_own);
     delete r;
     return SRBDQP_OK;
 }
@@ -2050,6 +2148,11 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
     if (r->robots && f32) { r->err = "fp32 ragged solve: refused while per-QP robot records are set (srbdqp_ragged_set_robots): only the fp64 solves read them"; return SRBDQP_E_INVALID; }
     if (r->robots && (size_t)B > r->robots_len) {
         r->err = "ragged solve of " + std::to_string(B) + " QPs with " + std::to_string(r->robots_len) + " robot records set: every QP needs its record";
+        return SRBDQP_E_INVALID;
+    }
+    if (r->weights && f32) { r->err = "fp32 ragged solve: refused while per-QP cost weights are set (srbdqp_ragged_set_weights): only the fp64 solves read them"; return SRBDQP_E_INVALID; }
+    if (r->weights && (size_t)B > r->weights_len) {
+        r->err = "ragged solve of " + std::to_string(B) + " QPs with " + std::to_string(r->weights_len) + " weight records set: every QP needs its record";
         return SRBDQP_E_INVALID;
     }
     if (B == 0) return SRBDQP_OK;
@@ -2257,6 +2360,59 @@ int srbdqp_ragged_set_robots_device(srbdqp_ragged* r, const srbdqp_robot* dev, i
     r->robots = clear ? nullptr : dev;
     r->robots_len = clear ? 0 : (size_t)length;
     return ragged_forward_robots(r);
+}
+
+namespace {
+int ragged_forward_weights(srbdqp_ragged* r) {
+    for (size_t i = 0; i < r->hs.size(); ++i) {
+        const int rc = srbdqp_set_weights_device(r->hs[i], r->weights, (int32_t)r->weights_len);
+        if (rc != SRBDQP_OK) { r->err = std::string("bucket N=") + std::to_string(r->horizons[i]) + ": " + r->hs[i]->err; return rc; }
+    }
+    return SRBDQP_OK;
+}
+
+// may every bucket take weights?  (weights_check_handle; r->err as ragged_robots_check writes it)
+int ragged_weights_check(srbdqp_ragged* r) {
+    for (auto* bh : r->hs)
+        if (const int rc = weights_check_handle(bh, "per-QP cost weights on a ragged object")) {
+            r->err = (bh->live_nstar ? std::string() : "bucket N=" + std::to_string(bh->cfg.horizon) + ": ") + bh->err;
+            return rc;
+        }
+    return SRBDQP_OK;
+}
+}  // namespace
+
+int srbdqp_ragged_set_weights(srbdqp_ragged* r, const srbdqp_weights* host, int32_t length) {
+    if (!r) return SRBDQP_E_INVALID;
+    if (host && length < 0) { r->err = "srbdqp_ragged_set_weights: negative length"; return SRBDQP_E_INVALID; }
+    const bool clear = !host || length == 0;
+    if (!clear) {
+        int rv = ragged_weights_check(r);
+        if (rv == SRBDQP_OK) rv = weights_validate(host, length, "srbdqp_ragged_set_weights", r->err);
+        if (rv != SRBDQP_OK) return rv;
+    }
+    HIP_TRY(r, hipSetDevice(r->device));
+    // (the waits of srbdqp_ragged_set_robots: every pass that may still read the records this call replaces has completed)
+    for (auto* h : r->hs) { const int rq = quiesce_all_streams(h); if (rq != SRBDQP_OK) { r->err = h->err; return rq; } }
+    for (auto ts : r->tail_st) HIP_TRY(r, hipStreamSynchronize(ts));
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    if (clear) { r->weights = nullptr; r->weights_len = 0; return ragged_forward_weights(r); }
+    if ((size_t)length > r->weights_cap) { r->weights = nullptr; r->weights_len = 0; (void)ragged_forward_weights(r); }   // (the buckets let go of the old copy)
+    const int rc = grow(r, r->weights_own, r->weights_cap, (size_t)length, nullptr, "hipMalloc weight records");
+    if (rc != SRBDQP_OK) return rc;
+    HIP_TRY(r, hipMemcpy(r->weights_own, host, sizeof(srbdqp_weights) * (size_t)length, hipMemcpyHostToDevice));
+    r->weights = r->weights_own; r->weights_len = (size_t)length;
+    return ragged_forward_weights(r);
+}
+
+int srbdqp_ragged_set_weights_device(srbdqp_ragged* r, const srbdqp_weights* dev, int32_t length) {
+    if (!r) return SRBDQP_E_INVALID;
+    if (dev && length < 0) { r->err = "srbdqp_ragged_set_weights_device: negative length"; return SRBDQP_E_INVALID; }
+    const bool clear = !dev || length == 0;
+    if (!clear) if (const int rc = ragged_weights_check(r)) return rc;
+    r->weights = clear ? nullptr : dev;
+    r->weights_len = clear ? 0 : (size_t)length;
+    return ragged_forward_weights(r);
 }
 
 int srbdqp_ragged_flush(srbdqp_ragged* r, void* stream) {

@@ -667,6 +667,33 @@ __device__ __forceinline__ void qp_robot_to_lds(const KArgs& a, const double* re
     dst[7] = ok ? 0.0 : 1.0;
 }
 
+// A QP's own cost weights (MODE = 6, srbdqp_set_weights): its record -- srbdqp_weights of include/srbdqp.h as 16 doubles: q_diag[13], r_diag, reserved[2] --
+// turned into what KArgs::sqrtq and KArgs::rs2 hold for every other QP, by the operations of the host's fill_args(): sq[0 .. 11] = sqrt(q_diag[0 .. 11])
+// (WrenchSmem::o_sq, where a.sqrtq goes in the other modes) and dst = [r_diag s s, bad] behind the robot's 8 doubles.  Lanes 32 .. 47 of wave 0 hold one double
+// of the record each (one coalesced load) and test it; the ballot makes the verdict the wave's.  A record that is not one (srbdqp_set_weights' rules: every
+// value finite -- below SRBDQP_WEIGHT_MAX, as weights_fault() of srbdqp.hip tests it --, q_diag >= 0, r_diag > 0, reserved 0; NaN fails every one) sets bad = 1: the QP is reported as SRBDQP_NUMERICAL with zero forces, and the values
+// stored are the KArgs ones.  Called by every lane of wave 0.
+__device__ __forceinline__ void qp_weights_to_lds(const KArgs& a, const double* rec, const int lane, double* sq, double* dst) {
+    const int e = lane - 32;
+    const bool mine = e >= 0 && e < 16;
+    const double v = rec[mine ? e : 0];
+    constexpr double big = SRBDQP_WEIGHT_MAX;
+    const bool good = e < 13 ? (v >= 0.0 && v < big) : (e == 13 ? (v > 0.0 && v < big) : v == 0.0);
+    const bool ok = __ballot(mine && !good) == 0ull;
+    if (e >= 0 && e < 12) sq[e] = ok ? sqrt(v) : a.sqrtq[e];
+    if (e == 13) dst[0] = ok ? v * a.s * a.s : a.rs2;
+    if (e == 14) dst[1] = ok ? 0.0 : 1.0;
+}
+
+// The launch-wide robot of KArgs in the LDS slots of qp_robot_to_lds (MODE = 6 without robot records): the values fill_args() computed, copied.
+__device__ __forceinline__ void args_robot_to_lds(const KArgs& a, double* dst) {
+    dst[0] = a.inv_mass;
+    dst[1] = a.iinv[0]; dst[2] = a.iinv[1]; dst[3] = a.iinv[2];
+    dst[4] = a.mu;
+    dst[5] = a.fzmin_s; dst[6] = a.fzmax_s;
+    dst[7] = 0.0;
+}
+
 // The frame R = [t1 t2 n] of one contact normal (MODE = 4, srbdqp_set_contact_normals; g1_locomotion_amd.contact_frames is the host mirror):
 //     n = nr / |nr|,   t1 = (e_x - n_x n) / |e_x - n_x n|,   t2 = n x t1        (R = I exactly for nr = e_z)
 // into the step's table L, L[12 r + a] = R[r][a] for the contact's columns a = 0 .. 2.  The setters' rules -- every entry finite, 0.5 <= |nr| <= 2, n_z >= 0.5
@@ -701,9 +728,13 @@ __device__ __forceinline__ void contact_frame_to_lds(const double (&nr)[3], doub
 // 5 = solve with rank-aware wrench steps (SRBDQP_FLAG_RANK_AWARE; DESIGN.md, "Rank-aware wrench steps"): a wrench step whose conditioning-guard quantity is not above kRankAwareRatio
 // -- its stance contact points on or near one line -- is never refused: it takes the normalised coordinates of E = R R', R = [L, B G^-1/2; 0, G^1/2] with Sc = L L'
 // (phase E): its g coordinates are the columns of R, its diagonal block of T is R' S R + I, V = R^-1 Y D^-1 and its part of K^-1 is D^-1 + V'(T^-1 - I) V
-// (apply_kinv, RA).  Nothing inverts E.  Steps above that ratio are what they are in MODE 0, and every such place below reads (RA ? ... : ...) or if constexpr (RA).
+// (apply_kinv, RA).  Nothing inverts E.  Steps above that ratio are what they are in MODE 0, and every such place below reads (RA ? ... : ...) or if constexpr (RA);
+// 6 = solve with the QP's own cost weights weights[16 b .. 16 b + 16) (srbdqp_set_weights, qp_weights_to_lds): sqrt(q_diag) where a.sqrtq goes, r_diag s^2 in an
+// LDS slot that the three uses of a.rs2 read (WT ? RBV[8] : a.rs2).  The robot comes from the LDS slots as in MODE 2 -- the QP's record where `robots` is set,
+// the KArgs values otherwise (args_robot_to_lds) -- so records and weights combine in one instantiation.
 template <int N, typename R, typename TIO, int MODE, typename TT = double, int SPW = 5, int XW = 0>
-__device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* sm, const double* robots = nullptr, const int nl = N, const double* normals = nullptr) {
+__device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* sm, const double* robots = nullptr, const int nl = N, const double* normals = nullptr,
+                                          const double* weights = nullptr) {
     using S = WrenchSmem<N, (int)sizeof(TT), SPW, XW, wrench_kreg64(N, MODE), MODE == 4>;
     typedef TT v4t __attribute__((ext_vector_type(4)));
     static_assert(sizeof(TT) == 8 || (sizeof(R) == 4 && MODE == 0), "fp32 tiles belong to the fp32 path");
@@ -713,12 +744,13 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     static_assert(S::NT <= 2 * NW || S::WQ >= 1, "");
     static_assert((S::o_zt % 2) == 0, "16-byte alignment of the 6-vectors");
     const double rho_b = unis(SRBDQP_RHO_OF(a, b));   // (per-QP values are wave-uniform: scalar registers, see uni())
-    constexpr bool RB = MODE == 2;
+    constexpr bool WT = MODE == 6;
+    constexpr bool RB = MODE == 2 || WT;                             // (MODE 6 reads the robot from LDS too)
     constexpr bool LH = MODE == 3;
     static_assert(!LH || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && (XW == 0 || N == 24)), "live horizons: the fp64 batch instantiation");
     const int NL = LH ? nl : N;                                      // the live horizon (wave-uniform: a kernel argument)
     static_assert(!RB || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && XW == 0), "per-QP robot records: the fp64 batch instantiation");
-    [[maybe_unused]] const double* const RBV = sm + S::o_end;        // MODE 2: the QP's robot (qp_robot_to_lds), from the first barrier on
+    [[maybe_unused]] const double* const RBV = sm + S::o_end;        // MODE 2: the QP's robot (qp_robot_to_lds), from the first barrier on (MODE 6: [8] r_diag s^2, [9] bad weights)
     constexpr bool CN = MODE == 4;
     static_assert(!CN || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && XW == 0), "contact normals: the fp64 batch instantiation");
     [[maybe_unused]] const double* const LT_ = sm + S::o_L;          // MODE 4: L of every step, from the second barrier on
@@ -767,7 +799,8 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
 #pragma unroll
         for (int r = 0; r < RF; ++r) { const int i = t + r * BT; v_ft[r] = gft[i < NL * 12 ? i : 0]; }
         if (t < 13) sm[S::o_x0 + t] = (double)v_x0;
-        if (t >= 32 && t < 44) sm[S::o_sq + t - 32] = a.sqrtq[t - 32];
+        if constexpr (!WT) { if (t >= 32 && t < 44) sm[S::o_sq + t - 32] = a.sqrtq[t - 32]; }
+        else { if (w == 0) qp_weights_to_lds(a, weights + (size_t)b * 16, lane, sm + S::o_sq, sm + S::o_end + 8); }
 #pragma unroll
         for (int r = 0; r < RX; ++r) { const int i = t + r * BT; if (i < N * 13) sm[S::o_xref + i] = (LH && i >= NL * 13) ? 0.0 : (double)v_xr[r]; }   // (live horizon: the rows behind it are zero -- finite tables, no contacts)
 #pragma unroll
@@ -775,7 +808,8 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         if (t < N * 4) sct[t] = (v_ct && (!LH || t < NL * 4)) ? 1 : 0;
         if (a.pcom && t < N * 3) sm[S::o_pcom + t] = (LH && t >= NL * 3) ? 0.0 : (double)v_pc;
         if (t == 0) { sm[S::o_misc] = 0.0; sm[S::o_misc + 1] = 0.0; }
-        if constexpr (RB) { if (t == 0) qp_robot_to_lds(a, robots + (size_t)b * 8, sm + S::o_end); }
+        if constexpr (RB && !WT) { if (t == 0) qp_robot_to_lds(a, robots + (size_t)b * 8, sm + S::o_end); }
+        if constexpr (WT) { if (t == 0) { if (robots) qp_robot_to_lds(a, robots + (size_t)b * 8, sm + S::o_end); else args_robot_to_lds(a, sm + S::o_end); } }
         __syncthreads();
         if (!a.pcom && t < N * 3) sm[S::o_pcom + t] = sm[S::o_xref + (t / 3) * 13 + 3 + (t % 3)];
         if constexpr (CN) { if (t < N * 4) contact_frame_to_lds(v_nr, sm + S::o_L + (t >> 2) * 36 + 3 * (t & 3), sm + S::o_misc + 1); }
@@ -865,6 +899,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     if constexpr (MODE == 1) { if (na == 0) return; }   // assembly dump of an empty problem: all zeros (the host cleared the buffers)
     [[maybe_unused]] bool rb_bad = false;
     if constexpr (RB) rb_bad = unis(RBV[7]) != 0.0;
+    if constexpr (WT) rb_bad = rb_bad || unis(RBV[9]) != 0.0;       // (MODE 6: weights that are none, the same way)
     if constexpr (CN) rb_bad = unis(sm[S::o_misc + 1]) != 0.0;      // (MODE 4: a normal that is not one, the same way)
     if (na == 0 || ((RB || CN) && rb_bad)) {   // nothing to solve: all forces 0 (MODE 2, a record that is not a robot: the same, reported as SRBDQP_NUMERICAL)
         for (int c = t; c < n; c += BT) sm[S::o_xs + c] = 0.0;
@@ -1088,7 +1123,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             if (stepok) sm[S::o_x0c + uvar] = x_init;
             __syncthreads();
             const double gtg = gtg_of_x0c();
-            px0 = active_u ? gtg + a.rs2 * x_init : 0.0;
+            px0 = active_u ? gtg + (WT ? RBV[8] : a.rs2) * x_init : 0.0;
         }
     };
     if constexpr (!TSPLIT) gradient_and_warm_start();   // (XW = 2: behind the barrier that joins the tables and E)
@@ -1101,7 +1136,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     }
 
     // ================= per-step wrench blocks: E^-1, V, Bd (registers of the step's lanes) =================
-    const double dxy = unis(a.rs2 + a.sigma + 2.0 * rho_b), dz = unis(a.rs2 + a.sigma + (4.0 * (RB ? unis(RBV[4]) : a.mu) * (RB ? unis(RBV[4]) : a.mu) + a.rho_fz) * rho_b);
+    const double dxy = unis((WT ? RBV[8] : a.rs2) + a.sigma + 2.0 * rho_b), dz = unis((WT ? RBV[8] : a.rs2) + a.sigma + (4.0 * (RB ? unis(RBV[4]) : a.mu) * (RB ? unis(RBV[4]) : a.mu) + a.rho_fz) * rho_b);
     const double idxy = unis(1.0 / dxy), idz = unis(1.0 / dz);
     // fp32 tiles (3 workgroups per CU, 168 registers): the rows / columns of V and Bd are formed AFTER the factorisation, from
     // the triangle of E^-1 kept in LDS behind the tiles, and held in fp32 from then on.  Formed here they waited in scratch
@@ -1973,7 +2008,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     if (stepok) sm[S::o_x0c + uvar] = x_init;
                     __syncthreads();
                     const double gtg = gtg_of_x0c();
-                    px0 = active_u ? gtg + a.rs2 * x_init : 0.0;
+                    px0 = active_u ? gtg + (WT ? RBV[8] : a.rs2) * x_init : 0.0;
                     __syncthreads();
                 }
             }
@@ -2376,6 +2411,17 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, 5, 0>::BT), WPS) void srbdqp_wren
     if (!wrench_block_in_launch<N>(a)) return;
     if (wrench_block_has_work(a))
         wrench_qp<N, double, double, 4, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm, nullptr, N, normals);
+    signal_done(a);
+}
+
+// ... MODE = 6: every QP with its own cost weights (srbdqp_set_weights / _device): weights = the handle's records, 16 doubles per QP in the CALLER's QP order, and
+// robots = the handle's robot records or null (the robot of KArgs for every QP), as further kernel arguments for the same reasons.  fp64, batch form only.
+template <int N, int WPS>
+__global__ __launch_bounds__((WrenchSmem<N, 8, 5, 0>::BT), WPS) void srbdqp_wrench_wt_kernel(KArgs a, const double* __restrict__ weights, const double* __restrict__ robots) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    if (!wrench_block_in_launch<N>(a)) return;
+    if (wrench_block_has_work(a))
+        wrench_qp<N, double, double, 6, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm, robots, N, nullptr, weights);
     signal_done(a);
 }
 

@@ -25,7 +25,7 @@ try:                                    # CPython binding of the two batch-1 cal
     from . import _fastcall
 except ImportError:                     # pragma: no cover
     _fastcall = None
-from ._lib import NX, NU, NC, SrbdqpError, robots_array, contact_frames  # noqa: F401  (robots_array: the rows of set_robots; contact_frames: set_contact_normals' convention)
+from ._lib import NX, NU, NC, SrbdqpError, robots_array, weights_array, contact_frames  # noqa: F401  (robots_array, weights_array: the rows of set_robots, set_weights; contact_frames: set_contact_normals' convention)
 
 
 def _ptr(a: Optional[np.ndarray]):
@@ -39,24 +39,28 @@ def _c(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
-def _robots_arg(robots):
-    """set_robots' argument -> (address or None, length, object to keep alive or None, is_device).  A NumPy array (L, 8) float64 goes to the host setter
-    (copied), a CUDA float64 torch tensor (L, 8) to the device setter (read at every solve: the engine holds a reference to it), None clears."""
-    if robots is None:
+def _records_arg(what, rec, width, maker):
+    """set_<what>'s argument (what = "robots", "weights": rows of `width` doubles, made by `maker`) -> (address or None, length, object to keep alive or None,
+    is_device).  A NumPy array (L, width) float64 goes to the host setter (copied), a CUDA float64 torch tensor (L, width) to the device setter (read at every
+    solve: the engine holds a reference to it), None clears."""
+    if rec is None:
         return None, 0, None, False
-    if hasattr(robots, "data_ptr") and hasattr(robots, "is_cuda"):
+    if hasattr(rec, "data_ptr") and hasattr(rec, "is_cuda"):
         import torch
-        if not robots.is_cuda or robots.dtype != torch.float64 or robots.dim() != 2 or robots.shape[1] != _lib.ROBOT_DOUBLES:
-            raise ValueError(f"set_robots: a torch tensor must be CUDA float64 of shape (L, {_lib.ROBOT_DOUBLES}), got {robots.dtype} {tuple(robots.shape)} "
-                             f"on {robots.device}")
-        if not robots.is_contiguous():
-            raise ValueError("set_robots: the tensor must be contiguous (its rows are read in place)")
-        return (C.c_void_p(robots.data_ptr()) if robots.shape[0] else None), int(robots.shape[0]), robots, True
-    arr = np.asarray(robots)
-    if arr.ndim != 2 or arr.shape[1] != _lib.ROBOT_DOUBLES:
-        raise ValueError(f"set_robots: expected shape (L, {_lib.ROBOT_DOUBLES}) (robots_array()), got {arr.shape}")
+        if not rec.is_cuda or rec.dtype != torch.float64 or rec.dim() != 2 or rec.shape[1] != width:
+            raise ValueError(f"set_{what}: a torch tensor must be CUDA float64 of shape (L, {width}), got {rec.dtype} {tuple(rec.shape)} on {rec.device}")
+        if not rec.is_contiguous():
+            raise ValueError(f"set_{what}: the tensor must be contiguous (its rows are read in place)")
+        return (C.c_void_p(rec.data_ptr()) if rec.shape[0] else None), int(rec.shape[0]), rec, True
+    arr = np.asarray(rec)
+    if arr.ndim != 2 or arr.shape[1] != width:
+        raise ValueError(f"set_{what}: expected shape (L, {width}) ({maker}()), got {arr.shape}")
     arr = np.ascontiguousarray(arr, dtype=np.float64)
     return (_ptr(arr) if arr.shape[0] else None), int(arr.shape[0]), arr, False
+
+
+def _robots_arg(robots):
+    return _records_arg("robots", robots, _lib.ROBOT_DOUBLES, "robots_array")
 
 
 def _normals_arg(normals, N):
@@ -252,6 +256,16 @@ class BatchMPC:
         fn = self._lib.srbdqp_set_robots_device if dev else self._lib.srbdqp_set_robots
         _lib.check(fn(self._h, ptr, n), self._h)
         self._robots = keep if dev else None
+
+    def set_weights(self, weights):
+        """One pair of cost weights (q_diag, r_diag) per QP (include/srbdqp.h srbdqp_set_weights): weights = weights_array(...) rows (NumPy, checked and
+        copied by the library), a CUDA float64 torch tensor (L, 16) (kept and read at every solve: leave it untouched until those solves have completed), or
+        None (back to the config's weights).  While set, QP b of a solve uses row b; the fp64 solves run on the general kernel (wrench_f64_n<N>_wt), with
+        or without set_robots() records, and the fp32, staged and assembly calls raise SrbdqpError."""
+        ptr, n, keep, dev = _records_arg("weights", weights, _lib.WEIGHTS_DOUBLES, "weights_array")
+        fn = self._lib.srbdqp_set_weights_device if dev else self._lib.srbdqp_set_weights
+        _lib.check(fn(self._h, ptr, n), self._h)
+        self._weights = keep if dev else None
 
     def set_contact_normals(self, normals):
         """Friction pyramids on sloped ground (include/srbdqp.h srbdqp_set_contact_normals): normals (L, N, 12) or (L, N, 4, 3), the world-frame surface normal
@@ -476,6 +490,13 @@ class RaggedMPC:
         fn = self._lib.srbdqp_ragged_set_robots_device if dev else self._lib.srbdqp_ragged_set_robots
         self._check(fn(self._h, ptr, n))
         self._robots = keep if dev else None
+
+    def set_weights(self, weights):
+        """One pair of cost weights per QP, in the CALLER's QP order (srbdqp_ragged_set_weights): as BatchMPC.set_weights."""
+        ptr, n, keep, dev = _records_arg("weights", weights, _lib.WEIGHTS_DOUBLES, "weights_array")
+        fn = self._lib.srbdqp_ragged_set_weights_device if dev else self._lib.srbdqp_ragged_set_weights
+        self._check(fn(self._h, ptr, n))
+        self._weights = keep if dev else None
 
     def flush(self, stream=0):
         """flags=FLAG_DEFER_TAIL: make `stream` (0 = the object's own) wait for the restart passes still running on the buckets' tail streams

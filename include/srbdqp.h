@@ -281,6 +281,16 @@ typedef struct srbdqp_robot {
     double reserved;      /* 0 */
 } srbdqp_robot;           /* every value finite */
 
+/* Per-QP cost weights: srbdqp_config holds ONE pair (q_diag, r_diag) for every QP of a handle; a record per QP overrides them for that QP (a weight sweep in
+ * one launch, gain scheduling inside a fleet, tracking weights that follow each robot's mass).  force_scale, rho, rho_fz_scale, sigma and the tolerances stay
+ * the handle's.  128 bytes, 16 doubles: */
+typedef struct srbdqp_weights {
+    double q_diag[SRBDQP_NX];  /* state tracking weights, >= 0 ([12], the gravity state, is read by no kernel: finite, >= 0) */
+    double r_diag;             /* force regularisation, > 0 */
+    double reserved[2];        /* 0 */
+} srbdqp_weights;              /* every value finite: below SRBDQP_WEIGHT_MAX, the one bound the host setters and the kernel both test */
+#define SRBDQP_WEIGHT_MAX 1.0e300
+
 /* Ragged batches (BASELINE.json configs[4]: "Mixed horizon N in {8,12,16,24} with per-QP contact schedule (ragged batch,
  * bucketed kernel launch)").  One object holds an engine per horizon; a call takes the QPs in ANY order with their horizon
  * in N_per_qp[] (HOST array), sorts them into horizon buckets and launches every non-empty bucket on its own HIP stream --
@@ -335,6 +345,13 @@ int srbdqp_solve_ragged_warm_device_f32(srbdqp_ragged* r, int32_t B, const int32
  * QPs and the _f32 ragged calls return SRBDQP_E_INVALID. */
 int srbdqp_ragged_set_robots(srbdqp_ragged* r, const srbdqp_robot* host, int32_t length);
 int srbdqp_ragged_set_robots_device(srbdqp_ragged* r, const srbdqp_robot* dev, int32_t length);
+/* Per-QP cost weights on a ragged object (srbdqp_weights, srbdqp_set_weights below: the same rules, checks and refusals).  Record b belongs to QP b of the
+ * CALLER's order -- not the bucket order -- and every bucket engine reads the same array.  An object with an N = 24 bucket or a live bucket is refused.  The
+ * host form copies once into a buffer of the object and waits for every bucket stream and tail stream before it replaces earlier records.  While weights are
+ * set the fp64 ragged calls read them; a call of B > length QPs and the _f32 ragged calls return SRBDQP_E_INVALID.  Weights and robot records combine: either
+ * order, independent lengths, clearing one leaves the other. */
+int srbdqp_ragged_set_weights(srbdqp_ragged* r, const srbdqp_weights* host, int32_t length);
+int srbdqp_ragged_set_weights_device(srbdqp_ragged* r, const srbdqp_weights* dev, int32_t length);
 
 /* Longest-first scheduling hint for the DEVICE-buffer API only (the host-buffer and the staged calls ignore it):
  * `device_iters_prev` = the iters[] array (device memory, `length` entries) of the previous control step of the same
@@ -367,6 +384,30 @@ int srbdqp_set_schedule_hint(srbdqp_handle* h, const int32_t* device_iters_prev,
  * the general kernel reads records there without scratch memory). */
 int srbdqp_set_robots(srbdqp_handle* h, const srbdqp_robot* host, int32_t length);
 int srbdqp_set_robots_device(srbdqp_handle* h, const srbdqp_robot* dev, int32_t length);
+
+/* Per-QP cost weights (srbdqp_weights above).  srbdqp_set_weights: HOST records, `length` of them, copied into a device buffer the library owns.  Every record
+ * is checked first: on a bad one the call returns SRBDQP_E_INVALID, srbdqp_last_error names the first bad index, and the previous setting stays.  Before it
+ * replaces earlier records it makes the waits srbdqp_set_robots makes.
+ * srbdqp_set_weights_device: DEVICE records the caller owns; the pointer is kept and read at every solve, so the array must stay untouched until the solves
+ * that read it have completed in stream order.  The kernel checks each record: a QP whose record breaks the rules above ends with SRBDQP_NUMERICAL and zero
+ * forces; the other QPs of the batch are not affected.
+ * host / dev NULL or length 0: back to srbdqp_config's q_diag and r_diag for every QP.
+ *
+ * While weights are set:
+ *   - QP b of a solve uses record b -- b the CALLER's index: the same under the schedule hint's dispatch order, in every restart or deferred pass;
+ *   - a solve of B > length QPs returns SRBDQP_E_INVALID and launches nothing;
+ *   - srbdqp_solve_batch_f64 / _device_f64 run on the general kernel's per-QP-weights instantiation (srbdqp_kernel_name: wrench_f64_n<N>_wt; AUTO and
+ *     SRBDQP_KERNEL_WRENCH route there, an explicit SRBDQP_KERNEL_COMPACT / _SPLIT / _WAVE returns SRBDQP_E_INVALID with a message);
+ *   - these return SRBDQP_E_INVALID with a message that names the setter: the _f32 calls, the staged batch-1 calls (srbdqp_solve_staged_f64,
+ *     srbdqp_prepare_staged_f64 / srbdqp_solve_prepared_f64, srbdqp_update_f64: one pair of weights sets srbdqp_config instead) and
+ *     srbdqp_assemble_f64 / _wrench_f64.
+ * Weights and robot records combine: both may be set on one handle, in either order, with independent lengths (a solve needs B no larger than each), and
+ * clearing one leaves the other in force; the same instantiation reads both.  A handle with both answers every refused call with the robot records' text.
+ * The setters refuse (SRBDQP_E_INVALID) an N = 24 handle, a handle whose horizon was admitted by SRBDQP_FLAG_ANY_HORIZON, a handle created with
+ * SRBDQP_FLAG_RANK_AWARE and a handle that has contact normals set; srbdqp_set_contact_normals / _device refuse normals while weights are set.  Without
+ * weights every call behaves as it always has. */
+int srbdqp_set_weights(srbdqp_handle* h, const srbdqp_weights* host, int32_t length);
+int srbdqp_set_weights_device(srbdqp_handle* h, const srbdqp_weights* dev, int32_t length);
 
 /* Contact normals: the friction pyramid of every contact point on sloped ground.  normals = [length][N][12] doubles: for QP b, step k, contact i the unit normal n of
  * the surface under the contact, in the WORLD frame, at [b][k][3 i .. 3 i + 3).  The contact frame is R = [t1 t2 n] with
