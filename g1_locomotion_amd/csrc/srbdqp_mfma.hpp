@@ -180,6 +180,7 @@ __device__ __forceinline__ v4d diag16_invert_mfma(v4d s, int lane, bool& ok) {
 // row-major, XOR-swizzled as the consumers read it); the four DPP rows work redundantly.  Used by the general kernel and by the 4-wave kernel's batch-1
 // instantiation (N = 10 double support 14.75 -> 14.99 M QP/s, configs[4] 2.83 -> 2.88 M, the batch-1 call -0.8 us); NOT by the one-wave kernel: its 64 live
 // registers beside that kernel's ten register tiles end in scratch memory (256 VGPRs + 88 bytes; configs[1] at 35 fixed iterations 1.775 -> 1.852 ms per 65,536 QPs).
+// (The one-wave kernel runs the PACKED form further down, diag16_invert_dpp_packed: half the registers.)
 // ---------------------------------------------------------------------------------------------------------
 template <int I>
 __device__ __forceinline__ void fmac_newbcast(double& acc, double nu, double m) {   // acc += nu[lane I of the row] * m
@@ -242,6 +243,140 @@ __device__ __forceinline__ v4d diag16_invert_dpp(v4d s, int lane, bool& ok, doub
     asm volatile("" ::: "memory");
     return w;
 }
+// ---------------------------------------------------------------------------------------------------------
+// The DPP elimination with S and R PACKED into the same 16 registers: the EVEN 16-lane DPP rows of register X_i hold row i of S (lane c: S[i][c]), the ODD
+// rows hold row i of R.  A row_newbcast operand is broadcast inside each DPP row on its own, so with nu = -L[:, k] in EVERY row and Y = X_k / sqrt(d) (u in
+// the even rows, W_k in the odd ones: one multiply) the ONE instruction  X_i += nu[lane i] * Y  is S_i -= L[i][k] u in the even rows and R_i -= L[i][k] W_k in the odd
+// ones: 120 DPP multiply-adds a tile instead of 240, 16 live register pairs instead of 32 -- which is what lets the one-wave kernel use it (the unpacked routine
+// spills there, see above).  Every entry goes through the arithmetic of diag16_pivot, operation by operation: the two return the same bits.  The price is one row
+// exchange per pivot: S_k has to reach the odd rows for nu (v_permlane16_swap of two copies: [S R S R] x 2 -> [S S S S], [R R R R]).
+// Wait states (the hazard recogniser does not see into the asm statements, and pads one state behind them): a VGPR written by a vector instruction needs two
+// before a DPP operand or a v_permlane*_swap reads it -- the s_nop 1 in front of every such read below; the multiply-adds of a pivot are at most three statements
+// (first row | rows up to 7 | rows 8 .. 15), each with its operands pinned and its own s_nop, as fmac_row_bcast_block (srbdqp_admm.hpp).
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double pk_even_rows(double x) {   // the even DPP rows of x (rows 0, 2), each also in the odd row behind it
+    int alo, ahi, blo, bhi;                                   // (b: the swap's second operand, a register pair the statement needs and nobody reads afterwards -- it ends as [R R R R])
+    asm("v_mov_b32 %0, %4\n\tv_mov_b32 %2, %4\n\tv_mov_b32 %1, %5\n\tv_mov_b32 %3, %5\n\ts_nop 1\n\t"
+        "v_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3"
+        : "=&v"(alo), "=&v"(ahi), "=&v"(blo), "=&v"(bhi) : "v"(__double2loint(x)), "v"(__double2hiint(x)));
+    return __hiloint2double(ahi, alo);
+}
+#define SRBDQP_PK(P, I) "v_fmac_f64_dpp %" #P ", %8, %9 row_newbcast:" #I " row_mask:0xf bank_mask:0xf\n\t"
+#define SRBDQP_PK_LO7 SRBDQP_PK(7, 7)
+#define SRBDQP_PK_LO6 SRBDQP_PK(6, 6) SRBDQP_PK_LO7
+#define SRBDQP_PK_LO5 SRBDQP_PK(5, 5) SRBDQP_PK_LO6
+#define SRBDQP_PK_LO4 SRBDQP_PK(4, 4) SRBDQP_PK_LO5
+#define SRBDQP_PK_LO3 SRBDQP_PK(3, 3) SRBDQP_PK_LO4
+#define SRBDQP_PK_LO2 SRBDQP_PK(2, 2) SRBDQP_PK_LO3
+#define SRBDQP_PK_HI15 SRBDQP_PK(7, 15)
+#define SRBDQP_PK_HI14 SRBDQP_PK(6, 14) SRBDQP_PK_HI15
+#define SRBDQP_PK_HI13 SRBDQP_PK(5, 13) SRBDQP_PK_HI14
+#define SRBDQP_PK_HI12 SRBDQP_PK(4, 12) SRBDQP_PK_HI13
+#define SRBDQP_PK_HI11 SRBDQP_PK(3, 11) SRBDQP_PK_HI12
+#define SRBDQP_PK_HI10 SRBDQP_PK(2, 10) SRBDQP_PK_HI11
+#define SRBDQP_PK_HI9 SRBDQP_PK(1, 9) SRBDQP_PK_HI10
+#define SRBDQP_PK_HI8 SRBDQP_PK(0, 8) SRBDQP_PK_HI9
+#define SRBDQP_PK_ASM(TAIL, B) asm("s_nop 1\n\t" TAIL : "+v"(X[B]), "+v"(X[B + 1]), "+v"(X[B + 2]), "+v"(X[B + 3]), "+v"(X[B + 4]), "+v"(X[B + 5]), "+v"(X[B + 6]), "+v"(X[B + 7]) : "v"(nu), "v"(y))
+// X_i += nu[lane i of the row] * y for the rows FROM .. 15 (all 8 registers of a half are operands of its statement: the finished ones are simply not named in it)
+template <int FROM>
+__device__ __forceinline__ void pk_rows(double (&X)[16], double nu, double y) {
+    if constexpr (FROM == 2) SRBDQP_PK_ASM(SRBDQP_PK_LO2, 0);
+    else if constexpr (FROM == 3) SRBDQP_PK_ASM(SRBDQP_PK_LO3, 0);
+    else if constexpr (FROM == 4) SRBDQP_PK_ASM(SRBDQP_PK_LO4, 0);
+    else if constexpr (FROM == 5) SRBDQP_PK_ASM(SRBDQP_PK_LO5, 0);
+    else if constexpr (FROM == 6) SRBDQP_PK_ASM(SRBDQP_PK_LO6, 0);
+    else if constexpr (FROM == 7) SRBDQP_PK_ASM(SRBDQP_PK_LO7, 0);
+    if constexpr (FROM <= 8) SRBDQP_PK_ASM(SRBDQP_PK_HI8, 8);
+    else if constexpr (FROM == 9) SRBDQP_PK_ASM(SRBDQP_PK_HI9, 8);
+    else if constexpr (FROM == 10) SRBDQP_PK_ASM(SRBDQP_PK_HI10, 8);
+    else if constexpr (FROM == 11) SRBDQP_PK_ASM(SRBDQP_PK_HI11, 8);
+    else if constexpr (FROM == 12) SRBDQP_PK_ASM(SRBDQP_PK_HI12, 8);
+    else if constexpr (FROM == 13) SRBDQP_PK_ASM(SRBDQP_PK_HI13, 8);
+    else if constexpr (FROM == 14) SRBDQP_PK_ASM(SRBDQP_PK_HI14, 8);
+    else if constexpr (FROM == 15) SRBDQP_PK_ASM(SRBDQP_PK_HI15, 8);
+}
+#undef SRBDQP_PK_ASM
+#undef SRBDQP_PK_HI8
+#undef SRBDQP_PK_HI9
+#undef SRBDQP_PK_HI10
+#undef SRBDQP_PK_HI11
+#undef SRBDQP_PK_HI12
+#undef SRBDQP_PK_HI13
+#undef SRBDQP_PK_HI14
+#undef SRBDQP_PK_HI15
+#undef SRBDQP_PK_LO2
+#undef SRBDQP_PK_LO3
+#undef SRBDQP_PK_LO4
+#undef SRBDQP_PK_LO5
+#undef SRBDQP_PK_LO6
+#undef SRBDQP_PK_LO7
+#undef SRBDQP_PK
+template <int I>
+struct PkLoad {
+    static __device__ __forceinline__ void run(double (&X)[16], const double* colp, int one_hi) {
+        if constexpr (I < 16) {
+            const double t = colp[I * 16];
+            const int lo = __builtin_amdgcn_update_dpp(__double2loint(t), 0, 0xE4, 0xA, 0xF, false);
+            const int hi = __builtin_amdgcn_update_dpp(__double2hiint(t), one_hi, I == 0 ? 0xE4 : 0x110 + I, 0xA, 0xF, true);
+            X[I] = __hiloint2double(hi, lo);
+            PkLoad<I + 1>::run(X, colp, one_hi);
+        }
+    }
+};
+template <int K>
+__device__ __forceinline__ void diag16_pivot_packed(double (&X)[16], unsigned& worst) {
+    const double sk = pk_even_rows(X[K]);         // row k of S in every DPP row
+    const double d = mov_newbcast<K>(sk);
+    // a pivot is good when it is positive and finite, its high word in [1, 0x7ff00000): what d > 0.0 accepts in the other routines, less the subnormals below
+    // 2^-1042 and +infinity (a NaN fails here as there) -- one unsigned maximum per pivot, decided once per tile (as sixteen fp64 comparisons the compiler gathers
+    // them behind the elimination and keeps every pivot in registers until then)
+    const unsigned dh = (unsigned)__double2hiint(d) - 1u;
+    worst = dh > worst ? dh : worst;
+    const double r = fast_rsqrt(d);
+    const double y = X[K] * r;                    // even rows: u = row k of L'; odd rows: W_k
+    if constexpr (K < 15) {
+        double nu;                                // -u in every row; the first row below the pivot in the same statement: the next pivot's chain hangs on it alone
+        asm("v_mul_f64 %1, %3, -%4\n\ts_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%5 row_mask:0xf bank_mask:0xf"
+            : "+v"(X[K + 1]), "=&v"(nu) : "v"(y), "v"(sk), "v"(r), "n"(K + 1));
+        if constexpr (K < 14) pk_rows<K + 2>(X, nu, y);
+        X[K] = y;                                 // (behind the statements that name y as an input: assigned ahead of them, X[K] is a second register and a copy)
+        diag16_pivot_packed<K + 1>(X, worst);
+    } else {
+        X[K] = y;
+    }
+}
+// tile: 256 doubles of LDS owned by this wave.  In: S in C layout.  On return the tile holds W = L^-1 row-major with the column XOR-swizzled
+// (tile[row * 16 + (col ^ row)]), exact zeros above the diagonal -- the form a_operand (srbdqp_setup1.hpp) leaves there, so the A operand of W is read straight from
+// it --; the return value is the same W in C layout.
+__device__ __forceinline__ v4d diag16_invert_dpp_packed(v4d s, int lane, bool& ok, double* tile) {
+    const int col = lane & 15, g = lane >> 4;
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int r = 0; r < 4; ++r) tile[(g + 4 * r) * 16 + col] = s[r];
+    asm volatile("" ::: "memory");
+    // every lane reads row i of S (of the upper triangle; below the diagonal the lanes carry values nobody reads); the odd rows then take the identity, two DPP
+    // moves with row_mask 0xa a register: the low word 0, the high word that of 1.0 shifted from lane 0 of the row to lane i (bound_ctrl: 0 to the lanes left of it)
+    const int one_hi = (col == 0) ? 0x3ff00000 : 0;
+    double X[16];
+    PkLoad<0>::run(X, tile + col, one_hi);
+    asm volatile("" ::: "memory");
+    unsigned worst = 0u;
+    diag16_pivot_packed<0>(X, worst);
+    ok = worst < 0x7fefffffu;                     // (zero, negative, NaN and infinite pivots fail, and subnormal ones with a zero high word)
+    int colw = col;
+    asm("" : "+v"(colw) : "v"(X[15]));            // (the sixteen swizzled addresses are formed behind the elimination, not held in registers through it)
+    if (g == 1) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) tile[i * 16 + (colw ^ i)] = X[i];
+    }
+    asm volatile("" ::: "memory");
+    v4d w;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { const int row = g + 4 * q; w[q] = tile[row * 16 + (col ^ row)]; }
+    asm volatile("" ::: "memory");
+    return w;
+}
+
 // ... from a row-major 16 x 16 tile `in` (float or double, not swizzled; this wave's own writes, complete) into the swizzled tile `out` (may be the same memory when
 // the types agree): the form the tile phases use -- the inverse of a diagonal tile is only ever read back from LDS.
 template <typename TI, typename TO>

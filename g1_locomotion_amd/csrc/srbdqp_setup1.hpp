@@ -5,8 +5,8 @@
 // per CU, because a QP owns 4 waves x 118 registers and 38 KB of LDS (mostly the tile store).  Since the assembly is
 // closed form (srbdqp_compact.hpp) nothing needs 256 threads: here the 10 upper 16x16 tiles of K are 80 registers of one
 // wave in MFMA C layout and the whole factorisation stays in that wave's registers --
-//   F  right-looking Cholesky K = U'U: diagonal tile inverted on the matrix cores (diag16_invert_mfma), panel
-//      U_jb = L_jj^-1 K_jb (the A operand L_jj^-1 goes through a 2 KB wave-private LDS tile to be transposed),
+//   F  right-looking Cholesky K = U'U: diagonal tile inverted by the packed DPP elimination (diag16_invert_dpp_packed: no matrix-core
+//      instruction, no v_readlane), panel U_jb = L_jj^-1 K_jb (the A operand L_jj^-1 is read from the 2 KB wave-private LDS tile the inversion leaves it in),
 //      trailing update K_ab -= U_ja' U_jb with both operands straight from registers (register r of a C-layout tile is
 //      the A operand of K-step r of a product that contracts over the tile's row index, and the B operand as well);
 //   W  L^-1 block row by block row, in place over the U tiles (W_ij takes the slot of U_ji);
@@ -428,6 +428,12 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
 
     // A-operand form of a C-layout tile X (operand[r] at lane (i, k') = X[i][4r + k']): through the wave-private tile
     double* scr = sm + L1::o_scr;
+    // (the read half on its own: of a tile that is in scr already in the swizzled form -- what diag16_invert_dpp_packed leaves there)
+    auto a_operand_read = [&](double (&op)[4]) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) op[r] = scr[mcol * 16 + ((4 * r + kq) ^ mcol)];
+        asm volatile("" ::: "memory");
+    };
     auto a_operand = [&](const v4d& x, double (&op)[4]) {
         asm volatile("" ::: "memory");
 #pragma unroll
@@ -436,9 +442,7 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
             scr[row * 16 + (mcol ^ row)] = x[q];
         }
         asm volatile("" ::: "memory");
-#pragma unroll
-        for (int r = 0; r < 4; ++r) op[r] = scr[mcol * 16 + ((4 * r + kq) ^ mcol)];
-        asm volatile("" ::: "memory");
+        a_operand_read(op);
     };
     const v4d zero4 = (v4d){0.0, 0.0, 0.0, 0.0};
 
@@ -447,14 +451,14 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         bool ok;
-        v4d w = diag16_invert_mfma(Kt[j][j], lane, ok);
+        // (the packed DPP elimination, srbdqp_mfma.hpp: no matrix-core instruction and no v_readlane; exact zeros above the diagonal, and W is left in the tile in
+        //  the form a_operand stores: the A operand is read straight from it)
+        const v4d w = diag16_invert_dpp_packed(Kt[j][j], lane, ok, scr);
         all_ok = all_ok && ok;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) w[q] = (mcol <= kq + 4 * q) ? w[q] : 0.0;     // exact zeros above the diagonal
         Kt[j][j] = w;
         if (j + 1 < NT) {
             double wa[4];
-            a_operand(w, wa);
+            a_operand_read(wa);
 #pragma unroll
             for (int bb = j + 1; bb < NT; ++bb) {   // panel: U_jb = L_jj^-1 K_jb
                 v4d o = zero4;

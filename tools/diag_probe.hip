@@ -1,5 +1,6 @@
 // 16 x 16 diagonal-tile inversion (S SPD -> W = L^-1, S = L L'): the blocked matrix-core routine the kernels use (diag16_invert_mfma) against the
-// column-per-lane DPP elimination (diag16_invert_dpp), one wave alone and eight waves per CU.
+// column-per-lane DPP elimination (diag16_invert_dpp) and its packed form (diag16_invert_dpp_packed: S and R in alternate DPP rows of the same registers, the
+// one-wave kernel's routine), one wave alone and eight waves per CU (two per SIMD); then max |W L - I| of the three over 64 random SPD tiles, L from a host Cholesky.
 //   hipcc -O3 --offload-arch=gfx950 -Iinclude -Ig1_locomotion_amd/csrc -o tools/diag_probe tools/diag_probe.hip && tools/diag_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -22,11 +23,28 @@ __global__ __launch_bounds__(64, 2) void k(const double* A, double* W, long long
         v4d in = s;
         in[0] += 1e-30 * w[0];      // dependency between repetitions
         if constexpr (VAR == 0) w = diag16_invert_mfma(in, lane, ok);
-        else w = diag16_invert_dpp(in, lane, ok, tile);
+        else if constexpr (VAR == 1) w = diag16_invert_dpp(in, lane, ok, tile);
+        else w = diag16_invert_dpp_packed(in, lane, ok, tile);
     }
     const long long t1 = __builtin_amdgcn_s_memtime();
     if (blockIdx.x == 0) for (int r = 0; r < 4; ++r) W[(g + 4 * r) * 16 + col] = w[r];
     if (lane == 0 && blockIdx.x == 0) { cyc[0] = t1 - t0; cyc[1] = ok; }
+}
+// accuracy: workgroup t inverts tile t
+template <int VAR>
+__global__ __launch_bounds__(64, 2) void acc(const double* A, double* W, int* okout) {
+    __shared__ __attribute__((aligned(16))) double tile[256];
+    const int lane = threadIdx.x, col = lane & 15, g = lane >> 4;
+    const double* At = A + 256 * blockIdx.x;
+    v4d s;
+    for (int r = 0; r < 4; ++r) s[r] = At[(g + 4 * r) * 16 + col];
+    bool ok = true;
+    v4d w;
+    if constexpr (VAR == 0) w = diag16_invert_mfma(s, lane, ok);
+    else if constexpr (VAR == 1) w = diag16_invert_dpp(s, lane, ok, tile);
+    else w = diag16_invert_dpp_packed(s, lane, ok, tile);
+    for (int r = 0; r < 4; ++r) W[256 * blockIdx.x + (g + 4 * r) * 16 + col] = w[r];
+    if (lane == 0) okout[blockIdx.x] = ok;
 }
 int main() {
     std::vector<double> A(256), W(256);
@@ -37,10 +55,12 @@ int main() {
     hipMalloc(&dA, 2048); hipMalloc(&dW, 2048); hipMalloc(&dc, 16);
     hipMemcpy(dA, A.data(), 2048, hipMemcpyHostToDevice);
     const int reps = 1000;
-    for (int var = 0; var < 2; ++var) for (int grid : {1, 2048}) {
+    const char* names[3] = {"diag16_invert_mfma      ", "diag16_invert_dpp       ", "diag16_invert_dpp_packed"};
+    for (int var = 0; var < 3; ++var) for (int grid : {1, 2048}) {
         for (int it = 0; it < 2; ++it) {
             if (var == 0) hipLaunchKernelGGL(k<0>, dim3(grid), dim3(64), 0, 0, dA, dW, dc, reps);
-            else hipLaunchKernelGGL(k<1>, dim3(grid), dim3(64), 0, 0, dA, dW, dc, reps);
+            else if (var == 1) hipLaunchKernelGGL(k<1>, dim3(grid), dim3(64), 0, 0, dA, dW, dc, reps);
+            else hipLaunchKernelGGL(k<2>, dim3(grid), dim3(64), 0, 0, dA, dW, dc, reps);
         }
         hipDeviceSynchronize();
         long long c[2]; hipMemcpy(c, dc, 16, hipMemcpyDeviceToHost); hipMemcpy(W.data(), dW, 2048, hipMemcpyDeviceToHost);
@@ -52,8 +72,43 @@ int main() {
             err = fmax(err, fabs(v - (i == j ? 1.0 : 0.0)));
             if (j > i) up = fmax(up, fabs(W[i * 16 + j]));
         }
-        printf("%s, %4d workgroups (%s): %.0f cycles per 16x16 inversion, ok=%lld, |W A W' - I| = %.2e, max above the diagonal %.1e\n", var ? "diag16_invert_dpp " : "diag16_invert_mfma", grid,
+        printf("%s, %4d workgroups (%s): %.0f cycles per 16x16 inversion, ok=%lld, |W A W' - I| = %.2e, max above the diagonal %.1e\n", names[var], grid,
                grid == 1 ? "one wave alone" : "8 waves per CU", (double)c[0] / reps, c[1], err, up);
+    }
+    // accuracy on NT random SPD tiles (G G' + shift I, the shift from 4 down to 1e-3: condition numbers up to ~1e4)
+    const int NT = 64;
+    std::vector<double> As(256 * NT), Ls(256 * NT, 0.0), Ws(256 * NT);
+    for (int t = 0; t < NT; ++t) {
+        const double shift = 4.0 * pow(10.0, -3.6 * t / (NT - 1));
+        for (auto& v : G) v = rnd();
+        double* a = &As[256 * t]; double* l = &Ls[256 * t];
+        for (int i = 0; i < 16; ++i) for (int j = 0; j < 16; ++j) { double v = (i == j) ? shift : 0.0; for (int k2 = 0; k2 < 16; ++k2) v += G[i * 16 + k2] * G[j * 16 + k2]; a[i * 16 + j] = v; }
+        for (int j = 0; j < 16; ++j) {
+            long double d = a[j * 16 + j]; for (int p = 0; p < j; ++p) d -= (long double)l[j * 16 + p] * l[j * 16 + p];
+            l[j * 16 + j] = (double)sqrtl(d);
+            for (int i = j + 1; i < 16; ++i) { long double v = a[i * 16 + j]; for (int p = 0; p < j; ++p) v -= (long double)l[i * 16 + p] * l[j * 16 + p]; l[i * 16 + j] = (double)(v / l[j * 16 + j]); }
+        }
+    }
+    double *dAs, *dWs; int* dok;
+    hipMalloc(&dAs, 2048 * NT); hipMalloc(&dWs, 2048 * NT); hipMalloc(&dok, 4 * NT);
+    hipMemcpy(dAs, As.data(), 2048 * NT, hipMemcpyHostToDevice);
+    for (int var = 0; var < 3; ++var) {
+        if (var == 0) hipLaunchKernelGGL(acc<0>, dim3(NT), dim3(64), 0, 0, dAs, dWs, dok);
+        else if (var == 1) hipLaunchKernelGGL(acc<1>, dim3(NT), dim3(64), 0, 0, dAs, dWs, dok);
+        else hipLaunchKernelGGL(acc<2>, dim3(NT), dim3(64), 0, 0, dAs, dWs, dok);
+        hipDeviceSynchronize();
+        std::vector<int> oks(NT);
+        hipMemcpy(Ws.data(), dWs, 2048 * NT, hipMemcpyDeviceToHost); hipMemcpy(oks.data(), dok, 4 * NT, hipMemcpyDeviceToHost);
+        double err = 0; int nok = 0;
+        for (int t = 0; t < NT; ++t) {
+            nok += oks[t];
+            for (int i = 0; i < 16; ++i) for (int j = 0; j <= i; ++j) {   // (W L is lower triangular: the routines' entries above the diagonal are not part of W)
+                long double v = 0;
+                for (int p = j; p <= i; ++p) v += (long double)Ws[256 * t + i * 16 + p] * Ls[256 * t + p * 16 + j];
+                err = fmax(err, fabs((double)v - (i == j ? 1.0 : 0.0)));
+            }
+        }
+        printf("%s: max |W L - I| over %d random SPD tiles = %.3e, ok on %d\n", names[var], NT, err, nok);
     }
     return 0;
 }

@@ -61,6 +61,16 @@ def main():
               "wave_time_split": {"issuing": g("SQ_ACTIVE_INST_ANY") / max(g("SQ_WAVE_CYCLES"), 1.0), "issue_stalled": g("SQ_WAIT_INST_ANY") / max(g("SQ_WAVE_CYCLES"), 1.0),
                                   "parked_waitcnt_or_barrier": 1.0 - (g("SQ_ACTIVE_INST_ANY") + g("SQ_WAIT_INST_ANY")) / max(g("SQ_WAVE_CYCLES"), 1.0)}}
         kk["clock_GHz"] = xcd_cycles / (stats[k]["avg_us"] * 1e3) if xcd_cycles else None
+        # Shares of the SIMD time the dispatch OWNS (not of the machine: a dispatch that shares the chip with another stream's is not charged for that one's
+        # cycles): its waves' cycles over the waves resident per SIMD (PMC_WAVES_PER_SIMD, default 2: the one-wave kernels).  VALU active + MFMA busy near 1 with
+        # little co-execution = the vector and matrix pipes are saturated: only issuing less helps (profiles/r12_wave_vector_diet.txt).
+        wps = float(os.environ.get("PMC_WAVES_PER_SIMD", "2"))
+        owned = g("SQ_WAVE_CYCLES") * 4.0 / wps
+        kk["simd_time_owned"] = {"waves_per_simd_assumed": wps, "simd_cycles": owned,
+                                 "share_of_machine": owned / (1024 * xcd_cycles) if xcd_cycles else None,
+                                 "valu_active": g("SQ_ACTIVE_INST_VALU") * 4.0 / owned if owned else None,
+                                 "mfma_busy": g("SQ_VALU_MFMA_BUSY_CYCLES") / owned if owned else None,
+                                 "valu_mfma_coexec": g("SQ_VALU_MFMA_COEXEC_CYCLES") / owned if owned and "SQ_VALU_MFMA_COEXEC_CYCLES" in c else None}
         # per solve (= per bench step) this kernel may run more or less than once (restart pass: once per step, on few QPs)
         kernels[short[k]] = kk
         if dom is None:
