@@ -29,6 +29,18 @@
 
 using srbdqp::KArgs;
 
+// An optional per-QP device array, indexed by the caller's QP index: what the solves read (null: not set) and for how many QPs, and the library's own device
+// copy of a host array (the host setters) with its capacity in elements
+template <typename T>
+struct PerQp {
+    const T* dev = nullptr;
+    size_t len = 0;
+    T* own = nullptr;
+    size_t cap = 0;
+    void clear() { dev = nullptr; len = 0; }
+    void release() { if (own) (void)hipFree(own); }
+};
+
 struct srbdqp_handle {
     srbdqp_config cfg;
     hipStream_t stream = nullptr;
@@ -94,21 +106,11 @@ struct srbdqp_handle {
     srbdqp::AqlQueue* aql = nullptr;
     bool aql_tried = false;
     std::string aql_why;
-    // per-QP robot records (srbdqp_set_robots / _device): what the solves read, or null (the config's robot for every QP)
-    const srbdqp_robot* robots = nullptr;
-    size_t robots_len = 0;
-    srbdqp_robot* robots_own = nullptr;    // the library's device copy of host records (srbdqp_set_robots)
-    size_t robots_cap = 0;
-    // per-QP cost weights (srbdqp_set_weights / _device): what the solves read, or null (the config's q_diag and r_diag for every QP)
-    const srbdqp_weights* weights = nullptr;
-    size_t weights_len = 0;
-    srbdqp_weights* weights_own = nullptr; // the library's device copy of host records (srbdqp_set_weights)
-    size_t weights_cap = 0;
-    // contact normals (srbdqp_set_contact_normals / _device): [normals_len][N][12] doubles the fp64 batch solves read, or null (flat ground under every contact)
-    const double* normals = nullptr;
-    size_t normals_len = 0;                // QPs
-    double* normals_own = nullptr;         // the library's device copy of a host array (srbdqp_set_contact_normals)
-    size_t normals_cap = 0;                // doubles
+    // the per-QP side inputs (one descriptor each below: RobotsIn, WeightsIn, NormalsIn).  The fp64 batch and ragged solves on the general kernel read them; null:
+    // the config's robot / the config's q_diag and r_diag / flat ground for every QP
+    PerQp<srbdqp_robot> robots;            // srbdqp_set_robots / _device
+    PerQp<srbdqp_weights> weights;         // srbdqp_set_weights / _device
+    PerQp<double> normals;                 // srbdqp_set_contact_normals / _device: [len][N][12] doubles (NormalsIn::per_qp), fp64 batch solves only
     // SRBDQP_FLAG_ANY_HORIZON with a horizon that has no instantiation: cfg.horizon stays the live horizon n (every array has the caller's shape for n) and the
     // solves run the general kernel instantiated for live_nstar, the smallest tabulated horizon >= n, in its live-horizon mode (srbdqp_wrench.hpp, MODE = 3)
     int live_nstar = 0;                    // 0: the horizon has its own instantiations
@@ -324,7 +326,7 @@ constexpr int kTileClassMinBatch = 512;
 // does a solve of B QPs on this handle go to the general kernel (srbdqp_wrench.hpp)?  launch() asks this.
 inline bool uses_wrench(const srbdqp_handle* h, const Call& c, int maxs, int B) {
     const int N = h->cfg.horizon;
-    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || h->robots || h->weights || h->normals || h->live_nstar) return true;   // (per-QP records and weights, contact normals, a live horizon: only the general kernel reads them)
+    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || h->robots.dev || h->weights.dev || h->normals.dev || h->live_nstar) return true;   // (per-QP records and weights, contact normals, a live horizon: only the general kernel reads them)
     // N = 20 single support too, for batches: the general kernel holds 2 workgroups per CU there, the compact one 1
     // (tools/schedule_bench.py, 16,384 QPs: 2.85 M QP/s against 1.95 M; at N = 12 / 16 the compact kernel wins, 7.1 / 4.9 M
     // against 5.7 / 4.2 M)
@@ -647,18 +649,18 @@ int launch_compact(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t 
 // call -- NULL, 0 -- is accepted in every state).  No two hold at once, except that robot records and weights combine -- such a handle is Robots here, and
 // Weights is the handle with weights alone:
 //   Live x RankAware                      srbdqp_create refuses SRBDQP_FLAG_RANK_AWARE at a live horizon
-//   Robots x Live, Robots x RankAware     robots_check_handle (srbdqp_set_robots / _device, and the ragged pair for every bucket)
-//   Normals x Live, Normals x RankAware   normals_check_handle (srbdqp_set_contact_normals / _device)
+//   Robots x Live, Robots x RankAware     check_handle<RobotsIn> (srbdqp_set_robots / _device, and the ragged pair for every bucket)
+//   Normals x Live, Normals x RankAware   check_handle<NormalsIn> (srbdqp_set_contact_normals / _device)
 //   Robots x Normals                      each of the two checks refuses while the other is set
-//   Weights x Live, Weights x RankAware, Weights x Normals      weights_check_handle (srbdqp_set_weights / _device, and the ragged pair for every bucket) and
-//                                         normals_check_handle
+//   Weights x Live, Weights x RankAware, Weights x Normals      check_handle<WeightsIn> (srbdqp_set_weights / _device, and the ragged pair for every bucket)
+//                                         and check_handle<NormalsIn>
 // (srbdqp_ragged_create refuses SRBDQP_FLAG_RANK_AWARE, and a ragged object has no normals: its buckets are Plain, Robots, Weights or Live.)
 enum class Variant { Plain, Robots, Normals, Live, RankAware, Weights };
 
 inline Variant variant_of(const srbdqp_handle* h) {
-    if (h->robots) return Variant::Robots;
-    if (h->weights) return Variant::Weights;
-    if (h->normals) return Variant::Normals;
+    if (h->robots.dev) return Variant::Robots;
+    if (h->weights.dev) return Variant::Weights;
+    if (h->normals.dev) return Variant::Normals;
     if (h->live_nstar) return Variant::Live;
     if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) return Variant::RankAware;
     return Variant::Plain;
@@ -708,11 +710,11 @@ constexpr unsigned kFormsF32 = 0;
 constexpr unsigned kFormsAssemble = form(Variant::RankAware);
 // srbdqp_assemble_wrench_f64
 constexpr unsigned kFormsAssembleWrench = 0;
-// srbdqp_set_robots / _device with records (robots_check_handle, which refuses N = 24 as well)
+// srbdqp_set_robots / _device with records (check_handle<RobotsIn>, which refuses N = 24 as well)
 constexpr unsigned kFormsSetRobots = form(Variant::Robots) | form(Variant::Weights);
-// srbdqp_set_weights / _device with records (weights_check_handle, which refuses N = 24 as well): beside robot records or in place of earlier weights
+// srbdqp_set_weights / _device with records (check_handle<WeightsIn>, which refuses N = 24 as well): beside robot records or in place of earlier weights
 constexpr unsigned kFormsSetWeights = form(Variant::Weights) | form(Variant::Robots);
-// srbdqp_set_contact_normals / _device with normals (normals_check_handle, which refuses N = 24 as well, and records in words of its own)
+// srbdqp_set_contact_normals / _device with normals (check_handle<NormalsIn>, which refuses N = 24 as well, and records in words of its own)
 constexpr unsigned kFormsSetNormals = form(Variant::Normals) | form(Variant::Robots);
 
 // a few field tests on the way of a call that has the form (srbdqp_solve_staged_f64 is the batch-1 latency path); a string only when the refusal fires
@@ -794,7 +796,7 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
         if constexpr (sizeof(R) == 8 && N != 24) {
             // per-QP cost weights (srbdqp_set_weights / _device), with or without robot records: the MODE = 6 instantiation, the weights and the records (or null)
             // as its second and third arguments -- every launch of a solve comes through here, as below.  (The weight setters refuse what the record setters do.)
-            if (h->weights) {
+            if (h->weights.dev) {
                 constexpr size_t lds_wt = lds + 10 * sizeof(double);         // + the QP's robot, r_diag s^2 and the bad-weights mark behind the layout (qp_weights_to_lds)
                 constexpr int by_lds_wt = (S::wgs_of(S::o_end + 10) * S::NW + 3) / 4;
                 constexpr int by_waves = WPS * 4 / S::NW;                     // (workgroups per CU the waves per SIMD admit)
@@ -803,31 +805,31 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
                               "the 80 bytes of LDS cost no workgroup per CU");
                 static const std::string nm_wt = nm + "_wt";
                 return launch_kernel(h, &srbdqp::srbdqp_wrench_wt_kernel<N, WPS>, nm_wt.c_str(), grid, dim3(S::BT), lds_wt, st, a,
-                                     reinterpret_cast<const double*>(h->weights), reinterpret_cast<const double*>(h->robots));
+                                     reinterpret_cast<const double*>(h->weights.dev), reinterpret_cast<const double*>(h->robots.dev));
             }
             // per-QP robot records (srbdqp_set_robots / _device): the MODE = 2 instantiation, the records as its second argument -- every launch of a solve
             // (first pass, restart passes, deferred passes on the tail stream, ragged buckets) comes through here with this handle.  (The entry points refuse
             // the staged, fp32 and dump calls while records are set, and the setters refuse N = 24: kRobotsMaxHorizon.)
-            if (h->robots) {
+            if (h->robots.dev) {
                 constexpr size_t lds_rb = lds + 8 * sizeof(double);          // + the QP's robot behind the layout (srbdqp_wrench.hpp qp_robot_to_lds)
                 constexpr int by_lds_rb = (S::wgs_of(S::o_end + 8) * S::NW + 3) / 4;   // (waves per SIMD the LDS admits, as WrenchTraits::by_lds)
                 static_assert((by_lds_rb < WPS ? by_lds_rb : WPS) == WPS, "the record's 64 bytes of LDS cost no occupancy");
                 void (*k_rb)(KArgs, const double*) = &srbdqp::srbdqp_wrench_kernel<N, double, double, 2, WPS, double, 5, 0>;
                 static const std::string nm_rb = nm + "_rb";
-                return launch_kernel(h, k_rb, nm_rb.c_str(), grid, dim3(S::BT), lds_rb, st, a, reinterpret_cast<const double*>(h->robots));
+                return launch_kernel(h, k_rb, nm_rb.c_str(), grid, dim3(S::BT), lds_rb, st, a, reinterpret_cast<const double*>(h->robots.dev));
             }
         }
         if constexpr (sizeof(R) == 8 && N != 24) {
             // contact normals (srbdqp_set_contact_normals / _device): the MODE = 4 instantiation, the normals as its second argument -- every launch of a solve (first
             // pass, restart passes, deferred passes on the tail stream) comes through here with this handle.  (The entry points refuse the staged, fp32 and dump
             // calls while normals are set, and the setters an N = 24 handle and one with robot records.)  L, the frames' columns, is 288 N more bytes of LDS.
-            if (h->normals) {
+            if (h->normals.dev) {
                 using SN = srbdqp::WrenchSmem<N, 8, 5, 0, srbdqp::wrench_kreg64(N, 4), true>;
                 constexpr size_t ldsn = SN::bytes;
                 constexpr int WPSN = NormalsTraits<N>::wps;
                 static_assert(ldsn <= 163840 && SN::BT == S::BT, "one QP must fit the LDS of a CU");
                 static const std::string nm_cn = nm + "_cn";
-                return launch_kernel(h, &srbdqp::srbdqp_wrench_cn_kernel<N, WPSN>, nm_cn.c_str(), grid, dim3(SN::BT), ldsn, st, a, h->normals);
+                return launch_kernel(h, &srbdqp::srbdqp_wrench_cn_kernel<N, WPSN>, nm_cn.c_str(), grid, dim3(SN::BT), ldsn, st, a, h->normals.dev);
             }
         }
         if constexpr (sizeof(R) == 8 && N <= 10) {
@@ -1113,10 +1115,15 @@ Pass restart_pass(const KArgs& a1, int p, int rcount, int max_iter, double* cons
 void signal_args(const srbdqp_handle* h, KArgs& a) { a.done_flag = h->done_dev; a.done_count = h->done_count; a.done_value = h->done_seq; }
 int32_t next_seq(srbdqp_handle* h) { return h->done_seq = (h->done_seq == INT32_MAX) ? 1 : h->done_seq + 1; }
 
-// ---- per-QP robot records (srbdqp_set_robots) ----
+// ---- the per-QP side inputs: robot records, cost weights, contact normals ----
+// To the host each is one thing: an optional per-QP device array (PerQp) that the general kernel reads and every other call refuses, owned by the library (host
+// setter) or borrowed (_device setter).  One descriptor per kind says what differs; the setters themselves exist once ("the setters of the per-QP side inputs"
+// below).  A further side input is one more descriptor, one more member and its extern "C" lines.
 static_assert(sizeof(srbdqp_robot) == 64 && offsetof(srbdqp_robot, inertia) == 8 && offsetof(srbdqp_robot, mu) == 32 &&
               offsetof(srbdqp_robot, fz_min) == 40 && offsetof(srbdqp_robot, fz_max) == 48 && offsetof(srbdqp_robot, reserved) == 56,
               "the kernels read a record as 8 doubles (srbdqp_wrench.hpp qp_robot)");
+static_assert(sizeof(srbdqp_weights) == 128 && offsetof(srbdqp_weights, r_diag) == 104 && offsetof(srbdqp_weights, reserved) == 112,
+              "the kernels read a record as 16 doubles (srbdqp_wrench.hpp qp_weights_to_lds)");
 
 // the rules of include/srbdqp.h (the same ones the kernel applies to device records, srbdqp_wrench.hpp qp_robot); null = valid, else what is wrong
 const char* robot_fault(const srbdqp_robot& r) {
@@ -1129,29 +1136,6 @@ const char* robot_fault(const srbdqp_robot& r) {
     return nullptr;
 }
 
-int robots_validate(const srbdqp_robot* host, int32_t length, const char* fn, std::string& err) {
-    for (int32_t i = 0; i < length; ++i)
-        if (const char* why = robot_fault(host[i])) { err = std::string(fn) + ": record " + std::to_string(i) + " is invalid (" + why + "); the previous setting is kept"; return SRBDQP_E_INVALID; }
-    return SRBDQP_OK;
-}
-
-// Horizons whose general kernel has a per-QP-record instantiation (MODE = 2) without scratch memory: N = 24 has none -- the MODE = 0 kernel that ships keeps
-// 20 bytes per lane in scratch with its three extra set-up waves, and a MODE = 2 copy without them (XW = 0) 24 bytes -- so the setters refuse an N = 24
-// handle / a ragged object with an N = 24 bucket.
-constexpr int kRobotsMaxHorizon = 20;
-const char* const robots_n24 = "per-QP robot records: not at N = 24 (no instantiation of the general kernel reads them there without scratch memory, DESIGN.md section 11)";
-
-// may this handle take records?  (a live horizon, rank-aware steps or contact normals: a combined mode would be another copy of every instantiation)
-int robots_check_handle(srbdqp_handle* h, const char* fn) {
-    if (const int rc = require_form(h, fn, kFormsSetRobots)) return rc;
-    if (h->cfg.horizon > kRobotsMaxHorizon) { h->err = robots_n24; return SRBDQP_E_INVALID; }
-    return SRBDQP_OK;
-}
-
-// ---- per-QP cost weights (srbdqp_set_weights) ----
-static_assert(sizeof(srbdqp_weights) == 128 && offsetof(srbdqp_weights, r_diag) == 104 && offsetof(srbdqp_weights, reserved) == 112,
-              "the kernels read a record as 16 doubles (srbdqp_wrench.hpp qp_weights_to_lds)");
-
 // the rules of include/srbdqp.h (the same ones the kernel applies to device records, srbdqp_wrench.hpp qp_weights_to_lds); null = valid, else what is wrong
 // ("finite" is < SRBDQP_WEIGHT_MAX = 1e300 on both sides: the kernel tests one bound, and r_diag s s must not overflow)
 const char* weights_fault(const srbdqp_weights& r) {
@@ -1161,23 +1145,115 @@ const char* weights_fault(const srbdqp_weights& r) {
     return nullptr;
 }
 
-int weights_validate(const srbdqp_weights* host, int32_t length, const char* fn, std::string& err) {
-    for (int32_t i = 0; i < length; ++i)
-        if (const char* why = weights_fault(host[i])) { err = std::string(fn) + ": record " + std::to_string(i) + " is invalid (" + why + "); the previous setting is kept"; return SRBDQP_E_INVALID; }
+// the rules of include/srbdqp.h (the same ones the kernel applies to a device array, srbdqp_wrench.hpp contact_frame_to_lds); null = valid, else what is wrong
+const char* normal_fault(const double* n) {
+    if (!std::isfinite(n[0]) || !std::isfinite(n[1]) || !std::isfinite(n[2])) return "every entry must be finite";
+    const double nn = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    if (!(nn >= 0.5 && nn <= 2.0)) return "need 0.5 <= |n| <= 2";
+    if (!(n[2] * (1.0 / nn) >= 0.5)) return "need n_z >= 0.5 |n| (slopes to 60 degrees)";
+    return nullptr;
+}
+
+// Horizons whose general kernel has a per-QP-record instantiation (MODE = 2) without scratch memory: N = 24 has none -- the MODE = 0 kernel that ships keeps
+// 20 bytes per lane in scratch with its three extra set-up waves, and a MODE = 2 copy without them (XW = 0) 24 bytes -- so the setters refuse an N = 24
+// handle / a ragged object with an N = 24 bucket.  The MODE = 6 instantiation of the weights is the MODE = 2 one with one more LDS slot
+// (DESIGN.md section 15), and the one of the normals (MODE = 4) has no N = 24 form either (section 13).
+constexpr int kRobotsMaxHorizon = 20;
+
+// A descriptor: the owner's member (of), the element type T, the per-element test (fault), the handle check (forms: the kForms* row; n24: the N = 24 text), the
+// hipMalloc label (alloc), and the words of the messages (name: srbdqp_set_<name>, srbdqp_ragged_set_<name>; what, which " on a ragged object" follows; count
+// and unit: the "B > length" messages).  RecordIn has what a kind of one record per QP need not say again: the elements per QP (per_qp), the elements one
+// fault test covers (stride), how a message locates element group i (where), and a refusal of the kind's own beside the table's (beside, or null).
+struct RecordIn {
+    static constexpr const char* unit = "record";
+    static constexpr size_t stride = 1;
+    template <class O> static size_t per_qp(const O*) { return 1; }
+    template <class O> static std::string where(const O*, size_t i) { return "record " + std::to_string(i); }
+    static const char* beside(const srbdqp_handle*) { return nullptr; }
+};
+
+struct RobotsIn : RecordIn {
+    using T = srbdqp_robot;
+    static constexpr const char* name = "robots";
+    static constexpr const char* what = "per-QP robot records";
+    static constexpr const char* alloc = "hipMalloc robot records";
+    static constexpr unsigned forms = kFormsSetRobots;
+    template <class O> static PerQp<T>& of(O* o) { return o->robots; }
+    static const char* fault(const T* e) { return robot_fault(*e); }
+    static std::string count(size_t len) { return std::to_string(len) + " robot records"; }
+    static std::string n24(const char*) { return "per-QP robot records: not at N = 24 (no instantiation of the general kernel reads them there without scratch memory, DESIGN.md section 11)"; }
+};
+
+struct WeightsIn : RecordIn {
+    using T = srbdqp_weights;
+    static constexpr const char* name = "weights";
+    static constexpr const char* what = "per-QP cost weights";
+    static constexpr const char* alloc = "hipMalloc weight records";
+    static constexpr unsigned forms = kFormsSetWeights;
+    template <class O> static PerQp<T>& of(O* o) { return o->weights; }
+    static const char* fault(const T* e) { return weights_fault(*e); }
+    static std::string count(size_t len) { return std::to_string(len) + " weight records"; }
+    static std::string n24(const char*) { return "per-QP cost weights: not at N = 24 (no instantiation of the general kernel reads them there without scratch memory, DESIGN.md section 15)"; }
+};
+
+struct NormalsIn {
+    using T = double;                                   // a QP has 4 N normals of 3 doubles: [len][N][12]
+    static constexpr const char* name = "contact_normals";
+    static constexpr const char* what = "contact normals";
+    static constexpr const char* alloc = "hipMalloc contact normals";
+    static constexpr const char* unit = "block";
+    static constexpr unsigned forms = kFormsSetNormals;
+    static constexpr size_t stride = 3;
+    static PerQp<T>& of(srbdqp_handle* h) { return h->normals; }
+    static size_t per_qp(const srbdqp_handle* h) { return 12 * (size_t)h->cfg.horizon; }
+    static const char* fault(const T* e) { return normal_fault(e); }
+    static std::string where(const srbdqp_handle* h, size_t i) {
+        const size_t N = (size_t)h->cfg.horizon;
+        return "the normal of (qp " + std::to_string(i / (4 * N)) + ", step " + std::to_string((i / 4) % N) + ", contact " + std::to_string(i % 4) + ")";
+    }
+    static std::string count(size_t len) { return "contact normals for " + std::to_string(len); }
+    static std::string n24(const char* fn) { return std::string(fn) + ": contact normals: not at N = 24 (no instantiation of the general kernel reads them there, DESIGN.md section 13)"; }
+    // (robot records pass kFormsSetNormals to be refused in words of their own)
+    static const char* beside(const srbdqp_handle* h) { return h->robots.dev ? ": refused while per-QP robot records are set (srbdqp_set_robots): no instantiation reads both (DESIGN.md section 13)" : nullptr; }
+};
+
+// may this handle take side input K?  (a live horizon, rank-aware steps, another side input it does not combine with: a combined mode would be another copy of
+// every instantiation)
+template <class K>
+int check_handle(srbdqp_handle* h, const char* fn) {
+    if (const int rc = require_form(h, fn, K::forms)) return rc;
+    if (h->cfg.horizon > kRobotsMaxHorizon) { h->err = K::n24(fn); return SRBDQP_E_INVALID; }
+    if (const char* why = K::beside(h)) { h->err = std::string(fn) + why; return SRBDQP_E_INVALID; }
     return SRBDQP_OK;
 }
 
-// may this handle take weights?  (contact normals, a live horizon, rank-aware steps: refused with their own texts; N = 24 as for robot records -- the MODE = 6
-// instantiation is the MODE = 2 one with one more LDS slot)
-const char* const weights_n24 = "per-QP cost weights: not at N = 24 (no instantiation of the general kernel reads them there without scratch memory, DESIGN.md section 15)";
-int weights_check_handle(srbdqp_handle* h, const char* fn) {
-    if (const int rc = require_form(h, fn, kFormsSetWeights)) return rc;
-    if (h->cfg.horizon > kRobotsMaxHorizon) { h->err = weights_n24; return SRBDQP_E_INVALID; }
+// a host array of side input K for `length` QPs: every element by the rules of include/srbdqp.h
+template <class K, class O>
+int validate(O* o, const typename K::T* host, int32_t length, const char* fn) {
+    const size_t groups = (size_t)length * K::per_qp(o) / K::stride;
+    for (size_t i = 0; i < groups; ++i)
+        if (const char* why = K::fault(host + K::stride * i)) {
+            o->err = std::string(fn) + ": " + K::where(o, i) + " is invalid (" + why + "); the previous setting is kept";
+            return SRBDQP_E_INVALID;
+        }
     return SRBDQP_OK;
 }
 
-// before the library's own copy of the records or of the normals is replaced: every solve that may still read it has completed (srbdqp_synchronize, then every
-// other launch stream of the handle and its tail streams -- deferred restart passes read them too)
+// a call over B QPs while side input K is set for fewer: lead + "<B>" + mid + "<K's count> set", then the setter's name (by_setter) and what every QP needs
+// (needs), as each owner's wording has them.  A pointer and a length test on the way of a solve; a string only when the refusal fires.
+template <class K, class O>
+int covers(O* o, long long B, const char* lead, const char* mid, bool by_setter, bool needs) {
+    const auto& s = K::of(o);
+    if (!s.dev || (size_t)B <= s.len) return SRBDQP_OK;
+    o->err = lead + std::to_string(B) + mid + K::count(s.len) + " set";
+    if (by_setter) o->err += std::string(" (srbdqp_set_") + K::name + ")";
+    if (needs) o->err += std::string(": every QP needs its ") + K::unit;
+    return SRBDQP_E_INVALID;
+}
+template <class K> int covers_batch(srbdqp_handle* h, int32_t B) { return covers<K>(h, B, "solve of ", " QPs with ", true, true); }
+
+// before the library's own copy of a side input is replaced: every solve that may still read it has completed (srbdqp_synchronize, then every other launch
+// stream of the handle and its tail streams -- deferred restart passes read them too)
 int quiesce_all_streams(srbdqp_handle* h) {
     int rc = srbdqp_synchronize(h);
     if (rc != SRBDQP_OK) return rc;
@@ -1191,47 +1267,18 @@ int quiesce_all_streams(srbdqp_handle* h) {
     return SRBDQP_OK;
 }
 
-// ---- contact normals (srbdqp_set_contact_normals) ----
-// the rules of include/srbdqp.h (the same ones the kernel applies to a device array, srbdqp_wrench.hpp contact_frame_to_lds); null = valid, else what is wrong
-const char* normal_fault(const double* n) {
-    if (!std::isfinite(n[0]) || !std::isfinite(n[1]) || !std::isfinite(n[2])) return "every entry must be finite";
-    const double nn = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-    if (!(nn >= 0.5 && nn <= 2.0)) return "need 0.5 <= |n| <= 2";
-    if (!(n[2] * (1.0 / nn) >= 0.5)) return "need n_z >= 0.5 |n| (slopes to 60 degrees)";
-    return nullptr;
-}
-
-// may this handle take normals?  (N = 24: no instantiation of the general kernel without scratch memory, as for robot records; a live horizon or robot records:
-// a combined mode would be another copy of every instantiation)
-int normals_check_handle(srbdqp_handle* h, const char* fn) {
-    if (const int rc = require_form(h, fn, kFormsSetNormals)) return rc;
-    if (h->cfg.horizon > kRobotsMaxHorizon) { h->err = std::string(fn) + ": contact normals: not at N = 24 (no instantiation of the general kernel reads them there, DESIGN.md section 13)"; return SRBDQP_E_INVALID; }
-    if (h->robots) { h->err = std::string(fn) + ": refused while per-QP robot records are set (srbdqp_set_robots): no instantiation reads both (DESIGN.md section 13)"; return SRBDQP_E_INVALID; }
-    return SRBDQP_OK;
-}
-
-// fp64 batch solve of B QPs with records or normals set: the general kernel, and a record / a block of normals for every QP
+// fp64 batch solve of B QPs with a side input set: the general kernel, and a record / a block of normals for every QP
 int variant_check_batch(srbdqp_handle* h, int32_t B) {
     const Variant v = variant_of(h);
     if (v != Variant::Robots && v != Variant::Normals && v != Variant::Weights) return SRBDQP_OK;
-    const bool rb = v == Variant::Robots;
     if (h->cfg.kernel != SRBDQP_KERNEL_AUTO && h->cfg.kernel != SRBDQP_KERNEL_WRENCH) {
-        h->err = std::string(rb ? "per-QP robot records" : v == Variant::Weights ? "per-QP cost weights (srbdqp_set_weights)" : "contact normals (srbdqp_set_contact_normals)") +
+        h->err = std::string(v == Variant::Robots ? "per-QP robot records" : v == Variant::Weights ? "per-QP cost weights (srbdqp_set_weights)" : "contact normals (srbdqp_set_contact_normals)") +
                  " are read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH while they are set";
         return SRBDQP_E_INVALID;
     }
-    if (h->weights && (size_t)B > h->weights_len) {      // (weights alone, or beside robot records: each length on its own)
-        h->err = "solve of " + std::to_string(B) + " QPs with " + std::to_string(h->weights_len) + " weight records set (srbdqp_set_weights): every QP needs its record";
-        return SRBDQP_E_INVALID;
-    }
-    if (v == Variant::Weights) return SRBDQP_OK;
-    const size_t len = rb ? h->robots_len : h->normals_len;
-    if ((size_t)B > len) {
-        h->err = "solve of " + std::to_string(B) + " QPs with " + (rb ? std::to_string(len) + " robot records set (srbdqp_set_robots): every QP needs its record"
-                                                                      : "contact normals for " + std::to_string(len) + " set (srbdqp_set_contact_normals): every QP needs its block");
-        return SRBDQP_E_INVALID;
-    }
-    return SRBDQP_OK;
+    if (const int rc = covers_batch<WeightsIn>(h, B)) return rc;      // (weights alone, or beside robot records: each length on its own)
+    if (const int rc = covers_batch<RobotsIn>(h, B)) return rc;
+    return covers_batch<NormalsIn>(h, B);
 }
 
 }  // namespace
@@ -1380,9 +1427,7 @@ int srbdqp_destroy(srbdqp_handle* h) {
         for (auto& r : sl.rsets) if (r.ev_tail) (void)hipEventDestroy(r.ev_tail);
     }
     if (h->done_count) (void)hipFree(h->done_count);
-    if (h->robots_own) (void)hipFree(h->robots_own);
-    if (h->weights_own) (void)hipFree(h->weights_own);
-    if (h->normals_own) (void)hipFree(h->normals_own);
+    h->robots.release(); h->weights.release(); h->normals.release();
     if (h->stage_host) (void)hipHostFree(h->stage_host);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1522,109 +1567,6 @@ int srbdqp_set_schedule_hint(srbdqp_handle* h, const int32_t* device_iters_prev,
     if (device_iters_prev && length < 0) { h->err = "negative hint length"; return SRBDQP_E_INVALID; }
     h->sched_hint = device_iters_prev;
     h->sched_hint_len = device_iters_prev ? (size_t)length : 0;
-    return SRBDQP_OK;
-}
-
-int srbdqp_set_robots(srbdqp_handle* h, const srbdqp_robot* host, int32_t length) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (host && length < 0) { h->err = "srbdqp_set_robots: negative length"; return SRBDQP_E_INVALID; }
-    const bool clear = !host || length == 0;
-    if (!clear) {
-        int rv = robots_check_handle(h, "srbdqp_set_robots");
-        if (rv == SRBDQP_OK) rv = robots_validate(host, length, "srbdqp_set_robots", h->err);
-        if (rv != SRBDQP_OK) return rv;
-    }
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    int rc = quiesce_all_streams(h);                // (deferred passes may still read the records this call replaces)
-    if (rc != SRBDQP_OK) return rc;
-    if (clear) { h->robots = nullptr; h->robots_len = 0; return SRBDQP_OK; }
-    if ((size_t)length > h->robots_cap) { h->robots = nullptr; h->robots_len = 0; }
-    rc = grow(h, h->robots_own, h->robots_cap, (size_t)length, nullptr, "hipMalloc robot records");
-    if (rc != SRBDQP_OK) return rc;
-    HIP_TRY(h, hipMemcpy(h->robots_own, host, sizeof(srbdqp_robot) * (size_t)length, hipMemcpyHostToDevice));
-    h->robots = h->robots_own; h->robots_len = (size_t)length;
-    return SRBDQP_OK;
-}
-
-int srbdqp_set_robots_device(srbdqp_handle* h, const srbdqp_robot* dev, int32_t length) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (dev && length < 0) { h->err = "srbdqp_set_robots_device: negative length"; return SRBDQP_E_INVALID; }
-    const bool clear = !dev || length == 0;
-    if (!clear) if (const int rc = robots_check_handle(h, "srbdqp_set_robots_device")) return rc;
-    h->robots = clear ? nullptr : dev;
-    h->robots_len = clear ? 0 : (size_t)length;
-    return SRBDQP_OK;
-}
-
-int srbdqp_set_weights(srbdqp_handle* h, const srbdqp_weights* host, int32_t length) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (host && length < 0) { h->err = "srbdqp_set_weights: negative length"; return SRBDQP_E_INVALID; }
-    const bool clear = !host || length == 0;
-    if (!clear) {
-        int rv = weights_check_handle(h, "srbdqp_set_weights");
-        if (rv == SRBDQP_OK) rv = weights_validate(host, length, "srbdqp_set_weights", h->err);
-        if (rv != SRBDQP_OK) return rv;
-    }
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    int rc = quiesce_all_streams(h);                // (deferred passes may still read the records this call replaces)
-    if (rc != SRBDQP_OK) return rc;
-    if (clear) { h->weights = nullptr; h->weights_len = 0; return SRBDQP_OK; }
-    if ((size_t)length > h->weights_cap) { h->weights = nullptr; h->weights_len = 0; }
-    rc = grow(h, h->weights_own, h->weights_cap, (size_t)length, nullptr, "hipMalloc weight records");
-    if (rc != SRBDQP_OK) return rc;
-    HIP_TRY(h, hipMemcpy(h->weights_own, host, sizeof(srbdqp_weights) * (size_t)length, hipMemcpyHostToDevice));
-    h->weights = h->weights_own; h->weights_len = (size_t)length;
-    return SRBDQP_OK;
-}
-
-int srbdqp_set_weights_device(srbdqp_handle* h, const srbdqp_weights* dev, int32_t length) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (dev && length < 0) { h->err = "srbdqp_set_weights_device: negative length"; return SRBDQP_E_INVALID; }
-    const bool clear = !dev || length == 0;
-    if (!clear) if (const int rc = weights_check_handle(h, "srbdqp_set_weights_device")) return rc;
-    h->weights = clear ? nullptr : dev;
-    h->weights_len = clear ? 0 : (size_t)length;
-    return SRBDQP_OK;
-}
-
-int srbdqp_set_contact_normals(srbdqp_handle* h, const double* host, int32_t length) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (host && length < 0) { h->err = "srbdqp_set_contact_normals: negative length"; return SRBDQP_E_INVALID; }
-    const bool clear = !host || length == 0;
-    const size_t N = (size_t)h->cfg.horizon;
-    if (!clear) {
-        const int rh = normals_check_handle(h, "srbdqp_set_contact_normals");
-        if (rh != SRBDQP_OK) return rh;
-        for (size_t i = 0; i < (size_t)length * N * 4; ++i)
-            if (const char* why = normal_fault(host + 3 * i)) {
-                h->err = "srbdqp_set_contact_normals: the normal of (qp " + std::to_string(i / (4 * N)) + ", step " + std::to_string((i / 4) % N) + ", contact " + std::to_string(i % 4) +
-                         ") is invalid (" + why + "); the previous setting is kept";
-                return SRBDQP_E_INVALID;
-            }
-    }
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    int rc = quiesce_all_streams(h);                // (deferred passes may still read the array this call replaces)
-    if (rc != SRBDQP_OK) return rc;
-    if (clear) { h->normals = nullptr; h->normals_len = 0; return SRBDQP_OK; }
-    const size_t want = (size_t)length * N * 12;
-    if (want > h->normals_cap) { h->normals = nullptr; h->normals_len = 0; }
-    rc = grow(h, h->normals_own, h->normals_cap, want, nullptr, "hipMalloc contact normals");
-    if (rc != SRBDQP_OK) return rc;
-    HIP_TRY(h, hipMemcpy(h->normals_own, host, sizeof(double) * want, hipMemcpyHostToDevice));
-    h->normals = h->normals_own; h->normals_len = (size_t)length;
-    return SRBDQP_OK;
-}
-
-int srbdqp_set_contact_normals_device(srbdqp_handle* h, const double* dev, int32_t length) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (dev && length < 0) { h->err = "srbdqp_set_contact_normals_device: negative length"; return SRBDQP_E_INVALID; }
-    const bool clear = !dev || length == 0;
-    if (!clear) {
-        const int rh = normals_check_handle(h, "srbdqp_set_contact_normals_device");
-        if (rh != SRBDQP_OK) return rh;
-    }
-    h->normals = clear ? nullptr : dev;
-    h->normals_len = clear ? 0 : (size_t)length;
     return SRBDQP_OK;
 }
 
@@ -2046,15 +1988,10 @@ struct srbdqp_ragged {
     std::vector<hipEvent_t> last_tail;        // per bucket: closes the passes of the last call that had any (srbdqp_ragged_flush), or null
     char* ws = nullptr; size_t ws_bytes = 0;  // host-buffer entry point: device copies of the caller's arrays
     hipStream_t stream = nullptr;             // ... and the stream its copies run on
-    // per-QP robot records in the caller's QP order (srbdqp_ragged_set_robots / _device), forwarded to every bucket engine: a bucket's workgroup reads the record
-    // of the caller's index its dispatch order names
-    const srbdqp_robot* robots = nullptr;
-    size_t robots_len = 0;
-    srbdqp_robot* robots_own = nullptr; size_t robots_cap = 0;
-    // per-QP cost weights in the caller's QP order (srbdqp_ragged_set_weights / _device), forwarded the same way
-    const srbdqp_weights* weights = nullptr;
-    size_t weights_len = 0;
-    srbdqp_weights* weights_own = nullptr; size_t weights_cap = 0;
+    // per-QP robot records and cost weights in the caller's QP order (srbdqp_ragged_set_robots, srbdqp_ragged_set_weights / _device), forwarded to every bucket
+    // engine: a bucket's workgroup reads the record of the caller's index its dispatch order names
+    PerQp<srbdqp_robot> robots;
+    PerQp<srbdqp_weights> weights;
     std::string err;
 };
 
@@ -2126,8 +2063,7 @@ int srbdqp_ragged_destroy(srbdqp_ragged* r) {
     if (r->h_perm) (void)hipHostFree(r->h_perm);
     if (r->h_off) (void)hipHostFree(r->h_off);
     if (r->ws) (void)hipFree(r->ws);
-    if (r->robots_own) (void)hipFree(r->robots_own);
-    if (r->weights_own) (void)hipFree(r->weights_own);
+    r->robots.release(); r->weights.release();
     delete r;
     return SRBDQP_OK;
 }
@@ -2138,6 +2074,16 @@ const char* srbdqp_ragged_last_error(const srbdqp_ragged* r) { return r ? r->err
 
 extern "C" int srbdqp_ragged_flush(srbdqp_ragged* r, void* stream);
 namespace {
+// a ragged solve of B QPs while side input K is set: fp64 only, and a record for every QP
+template <class K>
+int ragged_side_check(srbdqp_ragged* r, int32_t B, bool f32) {
+    if (K::of(r).dev && f32) {
+        r->err = std::string("fp32 ragged solve: refused while ") + K::what + " are set (srbdqp_ragged_set_" + K::name + "): only the fp64 solves read them";
+        return SRBDQP_E_INVALID;
+    }
+    return covers<K>(r, B, "ragged solve of ", " QPs with ", false, true);
+}
+
 // common body of the ragged device entry points; esz = element size of the caller's buffers (8 or 4)
 int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, const void* x0, const void* x_ref, const void* foot,
                        const uint8_t* contact, const void* warm_u, const void* warm_y, void* u_out, void* x_out, void* y_out,
@@ -2145,16 +2091,8 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
     if (!r) return SRBDQP_E_INVALID;
     if (B < 0 || (B > 0 && (!N_per_qp || !x0 || !x_ref || !foot || !contact || !u_out))) { r->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
     if (f32) for (auto* bh : r->hs) if (bh->live_nstar) { const int rc = refuse(bh, Variant::Live, "an fp32 ragged solve"); r->err = bh->err; return rc; }
-    if (r->robots && f32) { r->err = "fp32 ragged solve: refused while per-QP robot records are set (srbdqp_ragged_set_robots): only the fp64 solves read them"; return SRBDQP_E_INVALID; }
-    if (r->robots && (size_t)B > r->robots_len) {
-        r->err = "ragged solve of " + std::to_string(B) + " QPs with " + std::to_string(r->robots_len) + " robot records set: every QP needs its record";
-        return SRBDQP_E_INVALID;
-    }
-    if (r->weights && f32) { r->err = "fp32 ragged solve: refused while per-QP cost weights are set (srbdqp_ragged_set_weights): only the fp64 solves read them"; return SRBDQP_E_INVALID; }
-    if (r->weights && (size_t)B > r->weights_len) {
-        r->err = "ragged solve of " + std::to_string(B) + " QPs with " + std::to_string(r->weights_len) + " weight records set: every QP needs its record";
-        return SRBDQP_E_INVALID;
-    }
+    if (const int rc = ragged_side_check<RobotsIn>(r, B, f32)) return rc;
+    if (const int rc = ragged_side_check<WeightsIn>(r, B, f32)) return rc;
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(r, hipSetDevice(r->device));
     hipStream_t sin = stream ? reinterpret_cast<hipStream_t>(stream) : r->stream;
@@ -2306,114 +2244,99 @@ int ragged_host_impl(srbdqp_ragged* r, int32_t B, size_t esz, const int32_t* N_p
 }
 }  // namespace
 
+// ---- the setters of the per-QP side inputs (the descriptors RobotsIn, WeightsIn, NormalsIn above) ----
+// One skeleton for the host form and one for the device form, over the kind K and the owner O, a handle or a ragged object.  The owner supplies its device, how
+// to quiesce, how to check (owner_check) and what follows a change of the pointer (owner_changed).
+namespace {
+int owner_device(const srbdqp_handle* h) { return h->cfg.device; }
+int owner_device(const srbdqp_ragged* r) { return r->device; }
+
+int quiesce(srbdqp_handle* h) { return quiesce_all_streams(h); }
+// every pass that may still read the array this call replaces has completed: the buckets' streams (and their handles' slots), the deferred passes on the tail
+// streams, the object's own stream
+int quiesce(srbdqp_ragged* r) {
+    for (auto* h : r->hs) { const int rq = quiesce_all_streams(h); if (rq != SRBDQP_OK) { r->err = h->err; return rq; } }
+    for (auto ts : r->tail_st) HIP_TRY(r, hipStreamSynchronize(ts));
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    return SRBDQP_OK;
+}
+
+template <class K> int owner_check(srbdqp_handle* h, const char* fn) { return check_handle<K>(h, fn); }
+// may every bucket take it?  (r->err: the bucket's refusal, with the bucket in front unless the text names its live horizon itself)
+template <class K> int owner_check(srbdqp_ragged* r, const char*) {
+    const std::string fn = std::string(K::what) + " on a ragged object";
+    for (auto* bh : r->hs)
+        if (const int rc = check_handle<K>(bh, fn.c_str())) {
+            r->err = (bh->live_nstar ? std::string() : "bucket N=" + std::to_string(bh->cfg.horizon) + ": ") + bh->err;
+            return rc;
+        }
+    return SRBDQP_OK;
+}
+
+template <class K, class O> int set_device(O* o, const char* fn, const typename K::T* dev, int32_t length);
+template <class K> int owner_changed(srbdqp_handle*) { return SRBDQP_OK; }
+// the buckets read the object's array: the device setter of every bucket engine
+template <class K> int owner_changed(srbdqp_ragged* r) {
+    const std::string fn = std::string("srbdqp_set_") + K::name + "_device";
+    for (size_t i = 0; i < r->hs.size(); ++i) {
+        const int rc = set_device<K>(r->hs[i], fn.c_str(), K::of(r).dev, (int32_t)K::of(r).len);
+        if (rc != SRBDQP_OK) { r->err = std::string("bucket N=") + std::to_string(r->horizons[i]) + ": " + r->hs[i]->err; return rc; }
+    }
+    return SRBDQP_OK;
+}
+
+// The host form: the library's own device copy.  Clearing (NULL with any length, or length 0) is accepted in every state; an invalid array leaves the previous
+// setting as it was; a failed allocation leaves the owner cleared.
+template <class K, class O>
+int set_host(O* o, const char* fn, const typename K::T* host, int32_t length) {
+    if (!o) return SRBDQP_E_INVALID;
+    if (host && length < 0) { o->err = std::string(fn) + ": negative length"; return SRBDQP_E_INVALID; }
+    const bool clear = !host || length == 0;
+    if (!clear) {
+        int rv = owner_check<K>(o, fn);
+        if (rv == SRBDQP_OK) rv = validate<K>(o, host, length, fn);
+        if (rv != SRBDQP_OK) return rv;
+    }
+    HIP_TRY(o, hipSetDevice(owner_device(o)));
+    int rc = quiesce(o);                            // (deferred passes may still read the array this call replaces)
+    if (rc != SRBDQP_OK) return rc;
+    PerQp<typename K::T>& s = K::of(o);
+    if (clear) { s.clear(); return owner_changed<K>(o); }
+    const size_t want = (size_t)length * K::per_qp(o);
+    if (want > s.cap) { s.clear(); (void)owner_changed<K>(o); }   // (grow frees the old copy: nobody reads it from here on)
+    rc = grow(o, s.own, s.cap, want, nullptr, K::alloc);
+    if (rc != SRBDQP_OK) return rc;
+    HIP_TRY(o, hipMemcpy(s.own, host, sizeof(typename K::T) * want, hipMemcpyHostToDevice));
+    s.dev = s.own; s.len = (size_t)length;
+    return owner_changed<K>(o);
+}
+
+// The device form: the caller's array, which the caller keeps alive and unchanged while solves read it -- no device call, no wait.
+template <class K, class O>
+int set_device(O* o, const char* fn, const typename K::T* dev, int32_t length) {
+    if (!o) return SRBDQP_E_INVALID;
+    if (dev && length < 0) { o->err = std::string(fn) + ": negative length"; return SRBDQP_E_INVALID; }
+    const bool clear = !dev || length == 0;
+    if (!clear) if (const int rc = owner_check<K>(o, fn)) return rc;
+    PerQp<typename K::T>& s = K::of(o);
+    s.dev = clear ? nullptr : dev;
+    s.len = clear ? 0 : (size_t)length;
+    return owner_changed<K>(o);
+}
+}  // namespace
+
 extern "C" {
 
-namespace {
-int ragged_forward_robots(srbdqp_ragged* r) {
-    for (size_t i = 0; i < r->hs.size(); ++i) {
-        const int rc = srbdqp_set_robots_device(r->hs[i], r->robots, (int32_t)r->robots_len);
-        if (rc != SRBDQP_OK) { r->err = std::string("bucket N=") + std::to_string(r->horizons[i]) + ": " + r->hs[i]->err; return rc; }
-    }
-    return SRBDQP_OK;
-}
-
-// may every bucket take records?  (robots_check_handle; r->err: the bucket's refusal, with the bucket in front unless the text names its live horizon itself)
-int ragged_robots_check(srbdqp_ragged* r) {
-    for (auto* bh : r->hs)
-        if (const int rc = robots_check_handle(bh, "per-QP robot records on a ragged object")) {
-            r->err = (bh->live_nstar ? std::string() : "bucket N=" + std::to_string(bh->cfg.horizon) + ": ") + bh->err;
-            return rc;
-        }
-    return SRBDQP_OK;
-}
-}  // namespace
-
-int srbdqp_ragged_set_robots(srbdqp_ragged* r, const srbdqp_robot* host, int32_t length) {
-    if (!r) return SRBDQP_E_INVALID;
-    if (host && length < 0) { r->err = "srbdqp_ragged_set_robots: negative length"; return SRBDQP_E_INVALID; }
-    const bool clear = !host || length == 0;
-    if (!clear) {
-        int rv = ragged_robots_check(r);
-        if (rv == SRBDQP_OK) rv = robots_validate(host, length, "srbdqp_ragged_set_robots", r->err);
-        if (rv != SRBDQP_OK) return rv;
-    }
-    HIP_TRY(r, hipSetDevice(r->device));
-    // every pass that may still read the records this call replaces has completed: the buckets' streams (and their handles' slots), the deferred passes on the
-    // tail streams, the object's own stream
-    for (auto* h : r->hs) { const int rq = quiesce_all_streams(h); if (rq != SRBDQP_OK) { r->err = h->err; return rq; } }
-    for (auto ts : r->tail_st) HIP_TRY(r, hipStreamSynchronize(ts));
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    if (clear) { r->robots = nullptr; r->robots_len = 0; return ragged_forward_robots(r); }
-    if ((size_t)length > r->robots_cap) { r->robots = nullptr; r->robots_len = 0; (void)ragged_forward_robots(r); }   // (the buckets let go of the old copy)
-    const int rc = grow(r, r->robots_own, r->robots_cap, (size_t)length, nullptr, "hipMalloc robot records");
-    if (rc != SRBDQP_OK) return rc;
-    HIP_TRY(r, hipMemcpy(r->robots_own, host, sizeof(srbdqp_robot) * (size_t)length, hipMemcpyHostToDevice));
-    r->robots = r->robots_own; r->robots_len = (size_t)length;
-    return ragged_forward_robots(r);
-}
-
-int srbdqp_ragged_set_robots_device(srbdqp_ragged* r, const srbdqp_robot* dev, int32_t length) {
-    if (!r) return SRBDQP_E_INVALID;
-    if (dev && length < 0) { r->err = "srbdqp_ragged_set_robots_device: negative length"; return SRBDQP_E_INVALID; }
-    const bool clear = !dev || length == 0;
-    if (!clear) if (const int rc = ragged_robots_check(r)) return rc;
-    r->robots = clear ? nullptr : dev;
-    r->robots_len = clear ? 0 : (size_t)length;
-    return ragged_forward_robots(r);
-}
-
-namespace {
-int ragged_forward_weights(srbdqp_ragged* r) {
-    for (size_t i = 0; i < r->hs.size(); ++i) {
-        const int rc = srbdqp_set_weights_device(r->hs[i], r->weights, (int32_t)r->weights_len);
-        if (rc != SRBDQP_OK) { r->err = std::string("bucket N=") + std::to_string(r->horizons[i]) + ": " + r->hs[i]->err; return rc; }
-    }
-    return SRBDQP_OK;
-}
-
-// may every bucket take weights?  (weights_check_handle; r->err as ragged_robots_check writes it)
-int ragged_weights_check(srbdqp_ragged* r) {
-    for (auto* bh : r->hs)
-        if (const int rc = weights_check_handle(bh, "per-QP cost weights on a ragged object")) {
-            r->err = (bh->live_nstar ? std::string() : "bucket N=" + std::to_string(bh->cfg.horizon) + ": ") + bh->err;
-            return rc;
-        }
-    return SRBDQP_OK;
-}
-}  // namespace
-
-int srbdqp_ragged_set_weights(srbdqp_ragged* r, const srbdqp_weights* host, int32_t length) {
-    if (!r) return SRBDQP_E_INVALID;
-    if (host && length < 0) { r->err = "srbdqp_ragged_set_weights: negative length"; return SRBDQP_E_INVALID; }
-    const bool clear = !host || length == 0;
-    if (!clear) {
-        int rv = ragged_weights_check(r);
-        if (rv == SRBDQP_OK) rv = weights_validate(host, length, "srbdqp_ragged_set_weights", r->err);
-        if (rv != SRBDQP_OK) return rv;
-    }
-    HIP_TRY(r, hipSetDevice(r->device));
-    // (the waits of srbdqp_ragged_set_robots: every pass that may still read the records this call replaces has completed)
-    for (auto* h : r->hs) { const int rq = quiesce_all_streams(h); if (rq != SRBDQP_OK) { r->err = h->err; return rq; } }
-    for (auto ts : r->tail_st) HIP_TRY(r, hipStreamSynchronize(ts));
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    if (clear) { r->weights = nullptr; r->weights_len = 0; return ragged_forward_weights(r); }
-    if ((size_t)length > r->weights_cap) { r->weights = nullptr; r->weights_len = 0; (void)ragged_forward_weights(r); }   // (the buckets let go of the old copy)
-    const int rc = grow(r, r->weights_own, r->weights_cap, (size_t)length, nullptr, "hipMalloc weight records");
-    if (rc != SRBDQP_OK) return rc;
-    HIP_TRY(r, hipMemcpy(r->weights_own, host, sizeof(srbdqp_weights) * (size_t)length, hipMemcpyHostToDevice));
-    r->weights = r->weights_own; r->weights_len = (size_t)length;
-    return ragged_forward_weights(r);
-}
-
-int srbdqp_ragged_set_weights_device(srbdqp_ragged* r, const srbdqp_weights* dev, int32_t length) {
-    if (!r) return SRBDQP_E_INVALID;
-    if (dev && length < 0) { r->err = "srbdqp_ragged_set_weights_device: negative length"; return SRBDQP_E_INVALID; }
-    const bool clear = !dev || length == 0;
-    if (!clear) if (const int rc = ragged_weights_check(r)) return rc;
-    r->weights = clear ? nullptr : dev;
-    r->weights_len = clear ? 0 : (size_t)length;
-    return ragged_forward_weights(r);
-}
+int srbdqp_set_robots(srbdqp_handle* h, const srbdqp_robot* host, int32_t length) { return set_host<RobotsIn>(h, "srbdqp_set_robots", host, length); }
+int srbdqp_set_robots_device(srbdqp_handle* h, const srbdqp_robot* dev, int32_t length) { return set_device<RobotsIn>(h, "srbdqp_set_robots_device", dev, length); }
+int srbdqp_set_weights(srbdqp_handle* h, const srbdqp_weights* host, int32_t length) { return set_host<WeightsIn>(h, "srbdqp_set_weights", host, length); }
+int srbdqp_set_weights_device(srbdqp_handle* h, const srbdqp_weights* dev, int32_t length) { return set_device<WeightsIn>(h, "srbdqp_set_weights_device", dev, length); }
+int srbdqp_set_contact_normals(srbdqp_handle* h, const double* host, int32_t length) { return set_host<NormalsIn>(h, "srbdqp_set_contact_normals", host, length); }
+int srbdqp_set_contact_normals_device(srbdqp_handle* h, const double* dev, int32_t length) { return set_device<NormalsIn>(h, "srbdqp_set_contact_normals_device", dev, length); }
+int srbdqp_ragged_set_robots(srbdqp_ragged* r, const srbdqp_robot* host, int32_t length) { return set_host<RobotsIn>(r, "srbdqp_ragged_set_robots", host, length); }
+int srbdqp_ragged_set_robots_device(srbdqp_ragged* r, const srbdqp_robot* dev, int32_t length) { return set_device<RobotsIn>(r, "srbdqp_ragged_set_robots_device", dev, length); }
+int srbdqp_ragged_set_weights(srbdqp_ragged* r, const srbdqp_weights* host, int32_t length) { return set_host<WeightsIn>(r, "srbdqp_ragged_set_weights", host, length); }
+int srbdqp_ragged_set_weights_device(srbdqp_ragged* r, const srbdqp_weights* dev, int32_t length) { return set_device<WeightsIn>(r, "srbdqp_ragged_set_weights_device", dev, length); }
 
 int srbdqp_ragged_flush(srbdqp_ragged* r, void* stream) {
     if (!r) return SRBDQP_E_INVALID;
@@ -2512,13 +2435,9 @@ int srbdqp_wbid_reference_device_f64(srbdqp_handle* h, int64_t B, const double* 
     a.x_next = x_next; a.u0 = u0; a.foot = foot; a.R = R; a.base_vel = base_vel; a.base_acc = base_acc; a.com_acc = com_acc;
     for (int i = 0; i < 3; ++i) a.iinv[i] = 1.0 / h->cfg.inertia[i];
     a.mass = h->cfg.mass;
-    if (h->robots) {        // robot b's own mass and inertia (srbdqp_set_robots): the fleet chain stays consistent with the QPs it solved
-        if ((size_t)B > h->robots_len) {
-            h->err = "srbdqp_wbid_reference: " + std::to_string(B) + " robots with " + std::to_string(h->robots_len) + " robot records set";
-            return SRBDQP_E_INVALID;
-        }
-        a.robots = reinterpret_cast<const double*>(h->robots);
-    }
+    // robot b's own mass and inertia (srbdqp_set_robots): the fleet chain stays consistent with the QPs it solved
+    if (const int rc = covers<RobotsIn>(h, B, "srbdqp_wbid_reference: ", " robots with ", false, false)) return rc;
+    a.robots = reinterpret_cast<const double*>(h->robots.dev);
     a.gravity = -9.80665;   // wbid.py:286
     a.as_written = as_written ? 1 : 0;
     a.B = (long long)B;

@@ -39,50 +39,47 @@ def _c(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
-def _records_arg(what, rec, width, maker):
-    """set_<what>'s argument (what = "robots", "weights": rows of `width` doubles, made by `maker`) -> (address or None, length, object to keep alive or None,
-    is_device).  A NumPy array (L, width) float64 goes to the host setter (copied), a CUDA float64 torch tensor (L, width) to the device setter (read at every
-    solve: the engine holds a reference to it), None clears."""
-    if rec is None:
+def _side_arg(setter, a, trailing, hint="", read="it is"):
+    """A per-QP side input as `setter` (set_robots, set_weights, set_contact_normals) takes it -> (address or None, length, object to keep alive or None,
+    is_device).  trailing: the accepted shapes behind the leading L.  A NumPy array goes to the host setter (checked and copied), a CUDA float64 torch tensor
+    to the device setter (read at every solve: the engine holds a reference to it), None clears."""
+    if a is None:
         return None, 0, None, False
-    if hasattr(rec, "data_ptr") and hasattr(rec, "is_cuda"):
+    shapes = " or ".join("(L, " + ", ".join(map(str, t)) + ")" for t in trailing)
+    if hasattr(a, "data_ptr") and hasattr(a, "is_cuda"):
         import torch
-        if not rec.is_cuda or rec.dtype != torch.float64 or rec.dim() != 2 or rec.shape[1] != width:
-            raise ValueError(f"set_{what}: a torch tensor must be CUDA float64 of shape (L, {width}), got {rec.dtype} {tuple(rec.shape)} on {rec.device}")
-        if not rec.is_contiguous():
-            raise ValueError(f"set_{what}: the tensor must be contiguous (its rows are read in place)")
-        return (C.c_void_p(rec.data_ptr()) if rec.shape[0] else None), int(rec.shape[0]), rec, True
-    arr = np.asarray(rec)
-    if arr.ndim != 2 or arr.shape[1] != width:
-        raise ValueError(f"set_{what}: expected shape (L, {width}) ({maker}()), got {arr.shape}")
+        shp = tuple(a.shape)
+        if not a.is_cuda or a.dtype != torch.float64 or shp[1:] not in trailing:
+            raise ValueError(f"{setter}: a torch tensor must be CUDA float64 of shape {shapes}, got {a.dtype} {shp} on {a.device}")
+        if not a.is_contiguous():
+            raise ValueError(f"{setter}: the tensor must be contiguous ({read} read in place)")
+        return (C.c_void_p(a.data_ptr()) if shp[0] else None), int(shp[0]), a, True
+    arr = np.asarray(a)
+    if arr.shape[1:] not in trailing:
+        raise ValueError(f"{setter}: expected shape {shapes}{hint}, got {arr.shape}")
     arr = np.ascontiguousarray(arr, dtype=np.float64)
     return (_ptr(arr) if arr.shape[0] else None), int(arr.shape[0]), arr, False
 
 
 def _robots_arg(robots):
-    return _records_arg("robots", robots, _lib.ROBOT_DOUBLES, "robots_array")
+    return _side_arg("set_robots", robots, ((_lib.ROBOT_DOUBLES,),), " (robots_array())", "its rows are")
+
+
+def _weights_arg(weights):
+    return _side_arg("set_weights", weights, ((_lib.WEIGHTS_DOUBLES,),), " (weights_array())", "its rows are")
 
 
 def _normals_arg(normals, N):
-    """set_contact_normals' argument -> (address or None, length, object to keep alive or None, is_device).  A NumPy array (L, N, 12) or (L, N, 4, 3) float64
-    goes to the host setter (checked and copied), a CUDA float64 torch tensor of either shape to the device setter (read at every solve: the engine holds a
-    reference to it), None clears."""
-    if normals is None:
-        return None, 0, None, False
-    if hasattr(normals, "data_ptr") and hasattr(normals, "is_cuda"):
-        import torch
-        shp = tuple(normals.shape)
-        if not normals.is_cuda or normals.dtype != torch.float64 or shp[1:] not in ((N, NU), (N, NC, 3)):
-            raise ValueError(f"set_contact_normals: a torch tensor must be CUDA float64 of shape (L, {N}, 12) or (L, {N}, 4, 3), got {normals.dtype} {shp} "
-                             f"on {normals.device}")
-        if not normals.is_contiguous():
-            raise ValueError("set_contact_normals: the tensor must be contiguous (it is read in place)")
-        return (C.c_void_p(normals.data_ptr()) if shp[0] else None), int(shp[0]), normals, True
-    arr = np.asarray(normals)
-    if arr.shape[1:] not in ((N, NU), (N, NC, 3)):
-        raise ValueError(f"set_contact_normals: expected shape (L, {N}, 12) or (L, {N}, 4, 3), got {arr.shape}")
-    arr = np.ascontiguousarray(arr, dtype=np.float64)
-    return (_ptr(arr) if arr.shape[0] else None), int(arr.shape[0]), arr, False
+    return _side_arg("set_contact_normals", normals, ((N, NU), (N, NC, 3)))
+
+
+def _set_side(eng, fn, attr, arg):
+    """The body of every set_* method of BatchMPC and RaggedMPC: the host or the device form of the C-ABI setter `fn`, and in eng.<attr> what was set (None once
+    cleared) -- a device tensor stays referenced while the library reads it.  One rule for the three kinds, the one solve(normals=) needs to restore a
+    setting: a host array is kept too, until the next call of its setter, though the library has copied it."""
+    ptr, n, keep, dev = arg
+    eng._check(getattr(eng._lib, fn + "_device" if dev else fn)(eng._h, ptr, n))
+    setattr(eng, attr, keep if n else None)
 
 
 def _as(a, dtype, shape, name):
@@ -155,6 +152,9 @@ class BatchMPC:
 
     def __exit__(self, *exc):
         self.close()
+
+    def _check(self, rc):
+        _lib.check(rc, self._h)
 
     # -- host-buffer API -------------------------------------------------------------------------------
     def solve(self, x0, x_ref, foot, contact, pcom=None, warm_u=None, warm_y=None, want_x=True, want_y=False,
@@ -252,20 +252,14 @@ class BatchMPC:
         tensor (L, 8) (kept and read at every solve: leave it untouched until those solves have completed), or None (back to the config's robot).
         While set, QP b of a solve uses row b; the fp64 solves run on the general kernel, wbid_reference() uses each robot's mass and inertia, and the
         fp32, staged and assembly calls raise SrbdqpError."""
-        ptr, n, keep, dev = _robots_arg(robots)
-        fn = self._lib.srbdqp_set_robots_device if dev else self._lib.srbdqp_set_robots
-        _lib.check(fn(self._h, ptr, n), self._h)
-        self._robots = keep if dev else None
+        _set_side(self, "srbdqp_set_robots", "_robots", _robots_arg(robots))
 
     def set_weights(self, weights):
         """One pair of cost weights (q_diag, r_diag) per QP (include/srbdqp.h srbdqp_set_weights): weights = weights_array(...) rows (NumPy, checked and
         copied by the library), a CUDA float64 torch tensor (L, 16) (kept and read at every solve: leave it untouched until those solves have completed), or
         None (back to the config's weights).  While set, QP b of a solve uses row b; the fp64 solves run on the general kernel (wrench_f64_n<N>_wt), with
         or without set_robots() records, and the fp32, staged and assembly calls raise SrbdqpError."""
-        ptr, n, keep, dev = _records_arg("weights", weights, _lib.WEIGHTS_DOUBLES, "weights_array")
-        fn = self._lib.srbdqp_set_weights_device if dev else self._lib.srbdqp_set_weights
-        _lib.check(fn(self._h, ptr, n), self._h)
-        self._weights = keep if dev else None
+        _set_side(self, "srbdqp_set_weights", "_weights", _weights_arg(weights))
 
     def set_contact_normals(self, normals):
         """Friction pyramids on sloped ground (include/srbdqp.h srbdqp_set_contact_normals): normals (L, N, 12) or (L, N, 4, 3), the world-frame surface normal
@@ -273,10 +267,7 @@ class BatchMPC:
         it untouched until those solves have completed), or None (flat ground again).  While set, the five cone rows of a contact act on R' f with R =
         contact_frames(normal); forces, states and duals keep their frames and units; the fp64 solves run on the general kernel (wrench_f64_n<N>_cn), and
         the fp32, staged and assembly calls raise SrbdqpError."""
-        ptr, n, keep, dev = _normals_arg(normals, self.N)
-        fn = self._lib.srbdqp_set_contact_normals_device if dev else self._lib.srbdqp_set_contact_normals
-        _lib.check(fn(self._h, ptr, n), self._h)
-        self._normals_set = keep if n else None      # (what solve(normals=) restores; a device tensor stays referenced while the library reads it)
+        _set_side(self, "srbdqp_set_contact_normals", "_normals_set", _normals_arg(normals, self.N))   # (_normals_set: what solve(normals=) restores)
 
     def flush(self, stream=0):
         """FLAG_DEFER_TAIL: enqueue the continuations no later solve has picked up (srbdqp_flush); stream = a hipStream_t address, 0 = every
@@ -486,17 +477,11 @@ class RaggedMPC:
 
     def set_robots(self, robots):
         """One robot per QP, in the CALLER's QP order (srbdqp_ragged_set_robots): as BatchMPC.set_robots."""
-        ptr, n, keep, dev = _robots_arg(robots)
-        fn = self._lib.srbdqp_ragged_set_robots_device if dev else self._lib.srbdqp_ragged_set_robots
-        self._check(fn(self._h, ptr, n))
-        self._robots = keep if dev else None
+        _set_side(self, "srbdqp_ragged_set_robots", "_robots", _robots_arg(robots))
 
     def set_weights(self, weights):
         """One pair of cost weights per QP, in the CALLER's QP order (srbdqp_ragged_set_weights): as BatchMPC.set_weights."""
-        ptr, n, keep, dev = _records_arg("weights", weights, _lib.WEIGHTS_DOUBLES, "weights_array")
-        fn = self._lib.srbdqp_ragged_set_weights_device if dev else self._lib.srbdqp_ragged_set_weights
-        self._check(fn(self._h, ptr, n))
-        self._weights = keep if dev else None
+        _set_side(self, "srbdqp_ragged_set_weights", "_weights", _weights_arg(weights))
 
     def flush(self, stream=0):
         """flags=FLAG_DEFER_TAIL: make `stream` (0 = the object's own) wait for the restart passes still running on the buckets' tail streams

@@ -9,6 +9,7 @@ through the same presolve and restarted ADMM orc.update runs; u_world = s T u_lo
 import numpy as np
 
 import srbd_oracle as orc
+from weights_twin import batch  # noqa: F401  (the batches of the robots and weights suites: one copy)
 from g1_locomotion_amd import contact_frames
 
 TOL_TWIN_N = 2e-3
@@ -20,19 +21,6 @@ SCHEDULES = ("single", "double", "mixed", "three")
 def params(N):
     r_iter, r_count = orc.default_restart(N)
     return orc.params_for(N, rho_restart_iter=r_iter, rho_restart_count=r_count)
-
-
-def batch(B, N, seed, schedule):
-    """As tests/test_gpu_robots.py::_batch builds them ("three": steps with exactly 3 stance contacts)."""
-    x0, xr, ft, ct = orc.synthetic_batch(B, N, seed=seed, schedule="mixed" if schedule == "three" else schedule)
-    if schedule == "three":
-        rng = np.random.default_rng(seed)
-        for b in range(B):
-            for k in range(N):
-                if ct[b, k].sum() == 4 or rng.random() < 0.3:
-                    ct[b, k] = 1
-                    ct[b, k, rng.integers(0, 4)] = 0
-    return x0, xr, ft, ct
 
 
 def flat_normals(B, N):

@@ -10,6 +10,7 @@ import pytest
 
 import srbd_oracle as orc
 import normals_twin as nt
+from gpu_helpers import device_solve as _device_solve, to_dev as _to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -130,18 +131,6 @@ def test_flat_normals_change_nothing(torch_first, built_lib, N, schedule):
     assert du <= 1e-6 and dx <= 1e-6, (du, dx)
     for k in ("u", "x", "y", "status", "iters"):
         assert np.array_equal(back[k], ref[k]), k
-
-
-def _to_dev(torch, x0, xr, ft, ct):
-    return dict(x0=torch.from_numpy(x0).cuda(), xr=torch.from_numpy(xr).cuda(), ft=torch.from_numpy(ft).cuda(), ct=torch.from_numpy(ct.astype(np.uint8)).cuda())
-
-
-def _device_solve(torch, eng, t, B):
-    o = dict(u=torch.empty((B, eng.N, 12), dtype=torch.float64, device="cuda"), x=torch.empty((B, eng.N + 1, 13), dtype=torch.float64, device="cuda"),
-             status=torch.empty(B, dtype=torch.int32, device="cuda"), iters=torch.empty(B, dtype=torch.int32, device="cuda"))
-    eng.solve_device(B, t["x0"].data_ptr(), t["xr"].data_ptr(), t["ft"].data_ptr(), t["ct"].data_ptr(), o["u"].data_ptr(), o["x"].data_ptr(),
-                     status=o["status"].data_ptr(), iters=o["iters"].data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
-    return o
 
 
 def test_block_b_belongs_to_qp_b_under_a_hint_and_a_deferred_tail(torch_first, built_lib):

@@ -10,13 +10,11 @@ import numpy as np
 import pytest
 
 import srbd_oracle as orc
+from gpu_helpers import device_solve as _device_solve, to_dev as _to_dev
+# the batches and the per-QP bars of the docstring: one copy, shared with the weights suite (HORIZONS stops at 20: the setters refuse N = 24, test_n24_is_refused)
+from weights_twin import HORIZONS, SCHEDULES, TOL_TWIN_N, batch as _batch, check_qp as _check_qp, ragged_inputs as _ragged_inputs
 
 pytestmark = pytest.mark.gpu
-
-TOL_TWIN_N = 2e-3
-TOL_EXACT_N = 5e-2
-HORIZONS = (4, 8, 10, 12, 16, 20)          # (N = 24: the setters refuse it, test_n24_is_refused)
-SCHEDULES = ("single", "double", "mixed", "three")
 
 
 @pytest.fixture(scope="module")
@@ -24,19 +22,6 @@ def torch_first():
     import torch  # load torch's HIP runtime before libsrbdqp.so so both share one
     assert torch.cuda.is_available()
     return torch
-
-
-def _batch(B, N, seed, schedule):
-    """As tests/test_gpu_wrench.py::_batch builds them ("three": steps with exactly 3 stance contacts)."""
-    x0, xr, ft, ct = orc.synthetic_batch(B, N, seed=seed, schedule="mixed" if schedule == "three" else schedule)
-    if schedule == "three":
-        rng = np.random.default_rng(seed)
-        for b in range(B):
-            for k in range(N):
-                if ct[b, k].sum() == 4 or rng.random() < 0.3:
-                    ct[b, k] = 1
-                    ct[b, k, rng.integers(0, 4)] = 0
-    return x0, xr, ft, ct
 
 
 def _draw(B, seed):
@@ -52,27 +37,6 @@ def _params(N, rec):
     r_iter, r_count = orc.default_restart(N)
     return orc.params_for(N, mass=float(rec[0]), inertia=tuple(float(v) for v in rec[1:4]), mu=float(rec[4]), fz_min=float(rec[5]),
                           fz_max=float(rec[6]), rho_restart_iter=r_iter, rho_restart_count=r_count)
-
-
-def _check_qp(out, b, N, p, x0, xr, ft, ct):
-    ref = orc.update(p, x0[b], xr[b], ft[b], ct[b])
-    assert out["status"][b] == ref["status"] and ref["status"] in (orc.STATUS_SOLVED, orc.STATUS_MAX_ITER), (b, out["status"][b], ref["status"])
-    assert abs(int(out["iters"][b]) - ref["iters"]) <= p.check_every, (b, out["iters"][b], ref["iters"])
-    assert np.abs(out["u"][b] - ref["u"]).max() <= TOL_TWIN_N, (b, np.abs(out["u"][b] - ref["u"]).max())
-    assert np.abs(out["x"][b] - ref["x"]).max() <= 1e-5
-    kq, vi, ri = orc.presolve(ref["qp"], ct[b])
-    if ref["status"] == orc.STATUS_SOLVED:
-        xs, ys = orc.solve_reference(p, ref["qp"])
-        # (a drawn robot whose ADMM solution -- the oracle twin's too -- stops farther than 5e-2 N from the optimum at eps 1e-6 is held to the twin's
-        #  own distance: one QP of N = 20 single support, 0.0503 N on the GPU and the twin alike)
-        twin_gap = np.abs(ref["u"].reshape(-1) - xs * p.force_scale).max()
-        assert np.abs(out["u"][b].reshape(-1) - xs * p.force_scale).max() <= max(TOL_EXACT_N, twin_gap + TOL_TWIN_N)
-        kr = orc.kkt_residuals(kq["P"], kq["q"], kq["A"], kq["l"], kq["u"], out["u"][b].reshape(-1)[vi] / p.force_scale, out["y"][b][ri])
-        assert kr["primal"] <= 1e-4 and kr["stationarity"] <= 1e-3 * max(1.0, np.abs(ref["qp"]["q"]).max()), kr
-    off = np.setdiff1d(np.arange(12 * N), vi)
-    assert np.all(out["u"][b].reshape(-1)[off] == 0.0)
-    offr = np.setdiff1d(np.arange(20 * N), ri)
-    assert np.all(out["y"][b][offr] == 0.0)
 
 
 def _bound_active(u, ct, rec, tol=0.05):
@@ -141,18 +105,6 @@ def test_uniform_records_equal_the_config(torch_first, built_lib, N, schedule):
     assert np.array_equal(out["u"], ref["u"]) and np.array_equal(out["x"], ref["x"]) and np.array_equal(out["y"], ref["y"])   # bit-identical
 
 
-def _device_solve(torch, eng, t, B, stream=None):
-    o = dict(u=torch.empty((B, eng.N, 12), dtype=torch.float64, device="cuda"), x=torch.empty((B, eng.N + 1, 13), dtype=torch.float64, device="cuda"),
-             status=torch.empty(B, dtype=torch.int32, device="cuda"), iters=torch.empty(B, dtype=torch.int32, device="cuda"))
-    eng.solve_device(B, t["x0"].data_ptr(), t["xr"].data_ptr(), t["ft"].data_ptr(), t["ct"].data_ptr(), o["u"].data_ptr(), o["x"].data_ptr(),
-                     status=o["status"].data_ptr(), iters=o["iters"].data_ptr(), stream=stream or torch.cuda.current_stream().cuda_stream)
-    return o
-
-
-def _to_dev(torch, x0, xr, ft, ct):
-    return dict(x0=torch.from_numpy(x0).cuda(), xr=torch.from_numpy(xr).cuda(), ft=torch.from_numpy(ft).cuda(), ct=torch.from_numpy(ct.astype(np.uint8)).cuda())
-
-
 def test_schedule_hint_keeps_records_by_qp_index(torch_first, built_lib):
     torch = torch_first
     from g1_locomotion_amd import BatchMPC
@@ -171,16 +123,6 @@ def test_schedule_hint_keeps_records_by_qp_index(torch_first, built_lib):
         eng.set_schedule_hint(0, 0)
     for k in ("u", "x", "status", "iters"):
         assert torch.equal(plain[k], hinted[k]), k
-
-
-def _ragged_inputs(B, horizons, seed):
-    rng = np.random.default_rng(seed)
-    Nq = rng.choice(horizons, B).astype(np.int32)
-    X0, XR, FT, CT = [], [], [], []
-    for i, N in enumerate(Nq):
-        x0, xr, ft, ct = _batch(1, int(N), seed * 1000 + i, ("single", "double", "mixed", "three")[i % 4])
-        X0.append(x0[0]); XR.append(xr[0]); FT.append(ft[0]); CT.append(ct[0])
-    return Nq, np.stack(X0), np.concatenate(XR), np.concatenate(FT), np.concatenate(CT)
 
 
 def _ragged_run(torch, rg, Nq, t, B, rows):

@@ -1,5 +1,6 @@
 """Which C-ABI call has a form for which variant of the general kernel (srbdqp.hip, `Variant` and the masks of `require_form`): a handle is plain, or has robot
-records set, or contact normals set, or a live horizon (SRBDQP_FLAG_ANY_HORIZON), or rank-aware steps (SRBDQP_FLAG_RANK_AWARE) -- never two of them.  Through the
+records set, or cost weights set, or contact normals set, or a live horizon (SRBDQP_FLAG_ANY_HORIZON), or rank-aware steps (SRBDQP_FLAG_RANK_AWARE) -- never two
+of them, except robot records beside cost weights (a robots handle here; what only weights show is in test_gpu_weights.py).  Through the
 Python bindings, on one handle per variant, every entry point of the table below either returns SRBDQP_E_INVALID with a message that names the call and ends in
 the variant's fixed text, or returns SRBDQP_OK.  Nothing here looks at numbers: the variants' own suites do (test_gpu_robots.py, test_gpu_contact_normals.py,
 test_gpu_any_horizon.py, test_gpu_rank_aware.py).  The smallest shapes that reach every branch: N = 4 (a live horizon: 3, which runs on N* = 4), two QPs of full
@@ -9,15 +10,18 @@ import pytest
 
 import srbd_oracle as orc
 import normals_twin as nt
+from gpu_helpers import refusal as _refusal
 
 pytestmark = pytest.mark.gpu
 B = 2
-VARIANTS = ("robots", "normals", "live", "rank_aware")
+VARIANTS = ("robots", "weights", "normals", "live", "rank_aware")
 
 # the fixed text behind "<call>: " in a refusal, per variant of the handle
 TAIL = dict(
     robots="refused while per-QP robot records are set (srbdqp_set_robots): only the fp64 batch and ragged solves on the general kernel read them "
            "-- one robot for every QP goes in srbdqp_config",
+    weights="refused while per-QP cost weights are set (srbdqp_set_weights): only the fp64 batch and ragged solves on the general kernel read them "
+            "-- one pair of weights for every QP goes in srbdqp_config",
     normals="refused while contact normals are set (srbdqp_set_contact_normals): only the fp64 batch solves on the general kernel read them "
             "-- srbdqp_set_contact_normals(h, NULL, 0) goes back to flat ground",
     live="refused on a handle whose horizon 3 was admitted by SRBDQP_FLAG_ANY_HORIZON: only the fp64 batch, ragged and staged solves run a live horizon "
@@ -32,19 +36,23 @@ ALL = frozenset(VARIANTS)
 REFUSES = {
     "srbdqp_solve_batch_f64": frozenset(),
     "srbdqp_solve_batch_device_f64": frozenset(),
-    "srbdqp_solve_staged_f64": frozenset({"robots", "normals"}),
-    "srbdqp_update_f64": frozenset({"robots", "normals"}),
-    "srbdqp_prepare_staged_f64": frozenset({"robots", "normals", "live"}),
-    "srbdqp_solve_prepared_f64": frozenset({"robots", "normals", "live"}),
+    "srbdqp_solve_staged_f64": frozenset({"robots", "weights", "normals"}),
+    "srbdqp_update_f64": frozenset({"robots", "weights", "normals"}),
+    "srbdqp_prepare_staged_f64": frozenset({"robots", "weights", "normals", "live"}),
+    "srbdqp_solve_prepared_f64": frozenset({"robots", "weights", "normals", "live"}),
     "srbdqp_solve_batch_f32": ALL,
     "srbdqp_solve_batch_device_f32": ALL,
-    "srbdqp_assemble_f64": frozenset({"robots", "normals", "live"}),
+    "srbdqp_assemble_f64": frozenset({"robots", "weights", "normals", "live"}),
     "srbdqp_assemble_wrench_f64": ALL,
     "srbdqp_set_robots": frozenset({"normals", "live", "rank_aware"}),
     "srbdqp_set_robots_device": frozenset({"normals", "live", "rank_aware"}),
-    "srbdqp_set_contact_normals": frozenset({"robots", "live", "rank_aware"}),
-    "srbdqp_set_contact_normals_device": frozenset({"robots", "live", "rank_aware"}),
+    "srbdqp_set_weights": frozenset({"normals", "live", "rank_aware"}),
+    "srbdqp_set_weights_device": frozenset({"normals", "live", "rank_aware"}),
+    "srbdqp_set_contact_normals": frozenset({"robots", "weights", "live", "rank_aware"}),
+    "srbdqp_set_contact_normals_device": frozenset({"robots", "weights", "live", "rank_aware"}),
 }
+# variant -> the setters its handle accepts that would add the other kind of record: made as set-then-clear, so that the walk leaves the handle's state alone
+SET_THEN_CLEAR = dict(robots=("srbdqp_set_weights", "srbdqp_set_weights_device"), weights=("srbdqp_set_robots", "srbdqp_set_robots_device"))
 
 
 @pytest.fixture(scope="module")
@@ -62,10 +70,11 @@ def _engine(variant):
     return BatchMPC(horizon=4, rank_aware=(variant == "rank_aware")), 4
 
 
-def _calls(torch, eng, N):
-    """call name -> a function that makes the call on eng with two QPs of full double support (raises SrbdqpError unless the call returns SRBDQP_OK)."""
+def _calls(torch, eng, N, then_clear=()):
+    """call name -> a function that makes the call on eng with two QPs of full double support (raises SrbdqpError unless the call returns SRBDQP_OK); the
+    setters named in then_clear clear again what they set."""
     from g1_locomotion_amd import _lib
-    from g1_locomotion_amd.mpc import robots_array
+    from g1_locomotion_amd.mpc import robots_array, weights_array
     x0, xr, ft, ct = orc.synthetic_batch(B, N, seed=610 + N, schedule="double")
     assert ct.all()
     ct8 = np.ascontiguousarray(ct != 0, dtype=np.uint8)
@@ -74,7 +83,8 @@ def _calls(torch, eng, N):
     dev = {dt: [torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).cuda() for a in (x0, xr, ft)] + [torch.from_numpy(ct8).cuda(),
                 torch.empty((B, N, 12), dtype=getattr(torch, np.dtype(dt).name), device="cuda")] for dt in (np.float64, np.float32)}
     rb, nr = robots_array(B, mass=[30.0, 40.0]), nt.wedge_normals(B, N)
-    rb_dev, nr_dev = torch.from_numpy(rb).cuda(), torch.from_numpy(nr).cuda()
+    wr = weights_array(B, r_diag=[1e-4, 3e-4])
+    rb_dev, nr_dev, wr_dev = torch.from_numpy(rb).cuda(), torch.from_numpy(nr).cuda(), torch.from_numpy(wr).cuda()
     raw = _lib.load()
 
     def device(dt):
@@ -87,6 +97,9 @@ def _calls(torch, eng, N):
         _lib.check(raw.srbdqp_update_f64(eng._h, x0[0].ctypes.data, xr[0].ctypes.data, ft[0].ctypes.data, ct8[0].ctypes.data, None, u0.ctypes.data,
                                          None, None, None, None), eng._h)
 
+    def setter(name, method, arg):
+        return (lambda: (method(arg), method(None))) if name in then_clear else (lambda: method(arg))
+
     return {
         "srbdqp_solve_batch_f64": lambda: eng.solve(x0, xr, ft, ct),
         "srbdqp_solve_batch_device_f64": lambda: device(np.float64),
@@ -98,21 +111,13 @@ def _calls(torch, eng, N):
         "srbdqp_solve_batch_device_f32": lambda: device(np.float32),
         "srbdqp_assemble_f64": lambda: eng.assemble(x0, xr, ft, ct),
         "srbdqp_assemble_wrench_f64": lambda: eng.assemble_wrench(x0, xr, ft, ct),
-        "srbdqp_set_robots": lambda: eng.set_robots(rb),
-        "srbdqp_set_robots_device": lambda: eng.set_robots(rb_dev),
+        "srbdqp_set_robots": setter("srbdqp_set_robots", eng.set_robots, rb),
+        "srbdqp_set_robots_device": setter("srbdqp_set_robots_device", eng.set_robots, rb_dev),
+        "srbdqp_set_weights": setter("srbdqp_set_weights", eng.set_weights, wr),
+        "srbdqp_set_weights_device": setter("srbdqp_set_weights_device", eng.set_weights, wr_dev),
         "srbdqp_set_contact_normals": lambda: eng.set_contact_normals(nr),
         "srbdqp_set_contact_normals_device": lambda: eng.set_contact_normals(nr_dev),
     }
-
-
-def _refusal(fn):
-    """The message of the SrbdqpError that fn() raises, or None when it returns."""
-    from g1_locomotion_amd import SrbdqpError
-    try:
-        fn()
-    except SrbdqpError as e:
-        return str(e)
-    return None
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
@@ -120,10 +125,12 @@ def test_every_call_refuses_or_accepts_the_variant(torch_first, built_lib, varia
     from g1_locomotion_amd import _lib
     eng, N = _engine(variant)
     with eng:
-        calls = _calls(torch_first, eng, N)
+        calls = _calls(torch_first, eng, N, SET_THEN_CLEAR.get(variant, ()))
         assert list(calls) == list(REFUSES)
         if variant == "robots":
             calls["srbdqp_set_robots"]()
+        if variant == "weights":
+            calls["srbdqp_set_weights"]()
         if variant == "normals":
             calls["srbdqp_set_contact_normals"]()
         for name, refusing in REFUSES.items():
@@ -136,11 +143,13 @@ def test_every_call_refuses_or_accepts_the_variant(torch_first, built_lib, varia
                 assert msg is None, (variant, name, msg)
         if variant == "live":
             return
-        # the clearing calls succeed on every handle, and leave it in its base state: plain (what records or normals refused runs again, and the other setter
-        # is accepted), or rank-aware still
+        # the clearing calls succeed on every handle, and leave it in its base state: plain (what records, weights or normals refused runs again, and another
+        # setter is accepted), or rank-aware still
         eng.set_robots(None)
+        eng.set_weights(None)
         eng.set_contact_normals(None)
         eng.set_robots(torch_first.empty((0, 8), dtype=torch_first.float64, device="cuda"))
+        eng.set_weights(torch_first.empty((0, 16), dtype=torch_first.float64, device="cuda"))
         eng.set_contact_normals(torch_first.empty((0, N, 12), dtype=torch_first.float64, device="cuda"))
         if variant == "rank_aware":
             assert _refusal(calls["srbdqp_solve_batch_f32"]) == f"srbdqp error {_lib.E_INVALID}: srbdqp_solve_batch_f32: {TAIL[variant]}"
@@ -148,9 +157,9 @@ def test_every_call_refuses_or_accepts_the_variant(torch_first, built_lib, varia
         else:
             for name in ("srbdqp_solve_staged_f64", "srbdqp_solve_batch_f32", "srbdqp_assemble_wrench_f64"):
                 assert _refusal(calls[name]) is None, (variant, name)
-            other = "srbdqp_set_contact_normals" if variant == "robots" else "srbdqp_set_robots"
+            other = "srbdqp_set_robots" if variant == "normals" else "srbdqp_set_contact_normals"
             assert _refusal(calls[other]) is None
-            assert _refusal(calls["srbdqp_solve_batch_f64"]) is None and eng.kernel_name() == ("wrench_f64_n4_cn" if variant == "robots" else "wrench_f64_n4_rb")
+            assert _refusal(calls["srbdqp_solve_batch_f64"]) is None and eng.kernel_name() == ("wrench_f64_n4_rb" if variant == "normals" else "wrench_f64_n4_cn")
         assert _refusal(calls["srbdqp_solve_batch_f64"]) is None
 
 

@@ -1,13 +1,14 @@
 """GPU tests of the per-QP cost weights (include/srbdqp.h srbdqp_weights, srbdqp_set_weights / _device, srbdqp_ragged_set_weights / _device): every QP of a
 batch with its own q_diag and r_diag, on the general kernel's MODE = 6 instantiation (srbdqp_wrench_wt_kernel), alone or beside per-QP robot records.
 
-The bars are those of tests/test_gpu_robots.py::_check_qp (tests/weights_twin.py check_qp), per QP against the oracle run with THAT QP's weights; the draw
+The bars are those of tests/test_gpu_robots.py (tests/weights_twin.py check_qp), per QP against the oracle run with THAT QP's weights; the draw
 and the seeds are described in tests/weights_twin.py.  B = 16 unless a test says otherwise."""
 import numpy as np
 import pytest
 
 import srbd_oracle as orc
 import weights_twin as wt
+from gpu_helpers import device_solve as _device_solve, refusal as _refusal, to_dev as _to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -100,18 +101,6 @@ def test_weights_and_robot_records_combine(torch_first, built_lib, N):
     for b in range(B):
         wt.check_qp(out, b, N, wt.params(N, rec[b], rob[b]), x0, xr, ft, ct)
         wt.check_qp(wt_only, b, N, wt.params(N, rec[b]), x0, xr, ft, ct)
-
-
-def _device_solve(torch, eng, t, B):
-    o = dict(u=torch.empty((B, eng.N, 12), dtype=torch.float64, device="cuda"), x=torch.empty((B, eng.N + 1, 13), dtype=torch.float64, device="cuda"),
-             status=torch.empty(B, dtype=torch.int32, device="cuda"), iters=torch.empty(B, dtype=torch.int32, device="cuda"))
-    eng.solve_device(B, t["x0"].data_ptr(), t["xr"].data_ptr(), t["ft"].data_ptr(), t["ct"].data_ptr(), o["u"].data_ptr(), o["x"].data_ptr(),
-                     status=o["status"].data_ptr(), iters=o["iters"].data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
-    return o
-
-
-def _to_dev(torch, x0, xr, ft, ct):
-    return dict(x0=torch.from_numpy(x0).cuda(), xr=torch.from_numpy(xr).cuda(), ft=torch.from_numpy(ft).cuda(), ct=torch.from_numpy(ct.astype(np.uint8)).cuda())
 
 
 def test_schedule_hint_keeps_weights_by_qp_index(torch_first, built_lib):
@@ -269,88 +258,21 @@ def test_the_host_setter_and_the_kernel_share_one_bound(torch_first, built_lib):
     assert all(s in (orc.STATUS_SOLVED, orc.STATUS_MAX_ITER) for s in out["status"][:2])
 
 
-# ---- the weights row of the refusal table (the style of tests/test_gpu_variant_refusals.py): B = 2, N = 4, full double support ----
-TAIL = ("refused while per-QP cost weights are set (srbdqp_set_weights): only the fp64 batch and ragged solves on the general kernel read them "
-        "-- one pair of weights for every QP goes in srbdqp_config")
-# call -> does a weights-only handle refuse it?  In the order the calls are made (prepare before solve_prepared; the robot setters last: they change the state).
-REFUSED = {
-    "srbdqp_solve_batch_f64": False,
-    "srbdqp_solve_batch_device_f64": False,
-    "srbdqp_solve_staged_f64": True,
-    "srbdqp_update_f64": True,
-    "srbdqp_prepare_staged_f64": True,
-    "srbdqp_solve_prepared_f64": True,
-    "srbdqp_solve_batch_f32": True,
-    "srbdqp_solve_batch_device_f32": True,
-    "srbdqp_assemble_f64": True,
-    "srbdqp_assemble_wrench_f64": True,
-    "srbdqp_set_contact_normals": True,
-    "srbdqp_set_contact_normals_device": True,
-    "srbdqp_set_robots": False,
-    "srbdqp_set_robots_device": False,
-}
-
-
-def _refusal(fn):
-    from g1_locomotion_amd import SrbdqpError
-    try:
-        fn()
-    except SrbdqpError as e:
-        return str(e)
-    return None
-
-
-def test_every_call_refuses_or_accepts_a_handle_with_weights(torch_first, built_lib):
+def test_what_the_refusal_table_does_not_say_about_weights(torch_first, built_lib):
+    """The weights column and rows of the table are in tests/test_gpu_variant_refusals.py; here, with its calls (B = 2, N = 4, full double support), what a
+    table of (call, variant) cannot express."""
     torch = torch_first
-    import normals_twin as nt
     from g1_locomotion_amd import BatchMPC, _lib
-    from g1_locomotion_amd.mpc import robots_array, weights_array
+    from g1_locomotion_amd.mpc import weights_array
+    from test_gpu_variant_refusals import TAIL as VT, _calls
     B, N = 2, 4
     x0, xr, ft, ct = orc.synthetic_batch(B, N, seed=610 + N, schedule="double")
-    assert ct.all()
-    ct8 = np.ascontiguousarray(ct != 0, dtype=np.uint8)
-    rb, nr, wr = robots_array(B, mass=[30.0, 40.0]), nt.wedge_normals(B, N), weights_array(B, r_diag=[1e-4, 3e-4])
-    rb_dev, nr_dev, wr_dev = torch.from_numpy(rb).cuda(), torch.from_numpy(nr).cuda(), torch.from_numpy(wr).cuda()
-    raw = _lib.load()
+    wr = weights_array(B, r_diag=[1e-4, 3e-4])
+    wr_dev = torch.from_numpy(wr).cuda()
     E = f"srbdqp error {_lib.E_INVALID}: "
     with BatchMPC(horizon=N) as eng:
-        st = eng.stage()
-        st["x0"][:B], st["x_ref"][:B], st["foot"][:B], st["contact"][:B] = x0, xr, ft, ct8
-        dev = {dt: [torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).cuda() for a in (x0, xr, ft)] + [torch.from_numpy(ct8).cuda(),
-                    torch.empty((B, N, 12), dtype=getattr(torch, np.dtype(dt).name), device="cuda")] for dt in (np.float64, np.float32)}
-
-        def device(dt):
-            a = [t.data_ptr() for t in dev[dt]]
-            eng.solve_device(B, a[0], a[1], a[2], a[3], a[4], f32=(dt == np.float32))
-            eng.synchronize()
-
-        def update():
-            u0 = np.zeros(12)
-            _lib.check(raw.srbdqp_update_f64(eng._h, x0[0].ctypes.data, xr[0].ctypes.data, ft[0].ctypes.data, ct8[0].ctypes.data, None, u0.ctypes.data,
-                                             None, None, None, None), eng._h)
-
-        calls = {
-            "srbdqp_solve_batch_f64": lambda: eng.solve(x0, xr, ft, ct),
-            "srbdqp_solve_batch_device_f64": lambda: device(np.float64),
-            "srbdqp_solve_staged_f64": lambda: eng.solve_staged(B),
-            "srbdqp_update_f64": update,
-            "srbdqp_prepare_staged_f64": lambda: eng.prepare_staged(B),
-            "srbdqp_solve_prepared_f64": lambda: eng.solve_prepared(B),
-            "srbdqp_solve_batch_f32": lambda: eng.solve(x0, xr, ft, ct, dtype=np.float32),
-            "srbdqp_solve_batch_device_f32": lambda: device(np.float32),
-            "srbdqp_assemble_f64": lambda: eng.assemble(x0, xr, ft, ct),
-            "srbdqp_assemble_wrench_f64": lambda: eng.assemble_wrench(x0, xr, ft, ct),
-            "srbdqp_set_contact_normals": lambda: eng.set_contact_normals(nr),
-            "srbdqp_set_contact_normals_device": lambda: eng.set_contact_normals(nr_dev),
-            "srbdqp_set_robots": lambda: (eng.set_robots(rb), eng.set_robots(None)),
-            "srbdqp_set_robots_device": lambda: (eng.set_robots(rb_dev), eng.set_robots(None)),
-        }
-        assert list(calls) == list(REFUSED)
+        calls = _calls(torch, eng, N)
         eng.set_weights(wr)
-        for name, refused in REFUSED.items():
-            msg = _refusal(calls[name])
-            print(f"weights    {name:34s} -> {msg or 'SRBDQP_OK'}")
-            assert msg == (E + f"{name}: {TAIL}" if refused else None), (name, msg)
         assert _refusal(calls["srbdqp_solve_batch_f64"]) is None and eng.kernel_name() == "wrench_f64_n4_wt"
         # B > length
         eng.set_weights(wr[:1])
@@ -365,7 +287,6 @@ def test_every_call_refuses_or_accepts_a_handle_with_weights(torch_first, built_
         for name in ("srbdqp_solve_staged_f64", "srbdqp_solve_batch_f32", "srbdqp_assemble_wrench_f64", "srbdqp_set_contact_normals"):
             assert _refusal(calls[name]) is None, name
         # with normals set (the line above), the weight setters are refused in the normals' words
-        from test_gpu_variant_refusals import TAIL as VT
         for fn, arg in (("srbdqp_set_weights", wr), ("srbdqp_set_weights_device", wr_dev)):
             assert _refusal(lambda: eng.set_weights(arg)) == E + f"{fn}: {VT['normals']}"
         eng.set_weights(None)                                        # (clearing is accepted in every state)

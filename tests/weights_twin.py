@@ -1,6 +1,6 @@
 """What the tests of the per-QP cost weights share (include/srbdqp.h srbdqp_weights, srbdqp_set_weights): the seeded draw of the records, the oracle's
-parameters for one record (orc.params_for(N, q_diag=..., r_diag=...) builds and solves the QP with any weights -- no new oracle code), the batches, and the
-per-QP bars of tests/test_gpu_robots.py::_check_qp.
+parameters for one record (orc.params_for(N, q_diag=..., r_diag=...) builds and solves the QP with any weights -- no new oracle code), and -- shared with
+the robot records' suite, tests/test_gpu_robots.py, whose docstring states the bars -- the batches and the per-QP check.
 
 The draw, per QP: every q_diag entry is the default times a log-uniform factor in [0.25, 4], r_diag the default times a log-uniform factor in [0.1, 10];
 QP 0 has zero angular weights (q[0:3] = q[6:9] = 0) and QP 1 all q = 0 (only the regularisation remains).
@@ -30,7 +30,8 @@ def weights_seed(N):
 
 
 def batch(B, N, seed, schedule):
-    """As tests/test_gpu_wrench.py::_batch builds them ("three": steps with exactly 3 stance contacts)."""
+    """The batches of the robots, weights and contact-normals suites (test_gpu_robots.py and normals_twin.py import this one), built as
+    tests/test_gpu_wrench.py::_batch builds its own ("three": steps with exactly 3 stance contacts)."""
     x0, xr, ft, ct = orc.synthetic_batch(B, N, seed=seed, schedule="mixed" if schedule == "three" else schedule)
     if schedule == "three":
         rng = np.random.default_rng(seed)
@@ -78,7 +79,7 @@ def params(N, rec, robot=None):
 
 
 def check_qp(out, b, N, p, x0, xr, ft, ct):
-    """The bars of tests/test_gpu_robots.py::_check_qp for QP b against the oracle with parameters p; -> the oracle's result."""
+    """QP b of the engine's out against the oracle with parameters p, by the bars in the docstring of tests/test_gpu_robots.py; -> the oracle's result."""
     ref = orc.update(p, x0[b], xr[b], ft[b], ct[b])
     assert out["status"][b] == ref["status"] and ref["status"] in (orc.STATUS_SOLVED, orc.STATUS_MAX_ITER), (b, out["status"][b], ref["status"])
     assert abs(int(out["iters"][b]) - ref["iters"]) <= p.check_every, (b, out["iters"][b], ref["iters"])
@@ -87,6 +88,8 @@ def check_qp(out, b, N, p, x0, xr, ft, ct):
     kq, vi, ri = orc.presolve(ref["qp"], ct[b])
     if ref["status"] == orc.STATUS_SOLVED:
         xs, ys = orc.solve_reference(p, ref["qp"])
+        # (a drawn robot whose ADMM solution -- the oracle twin's too -- stops farther than 5e-2 N from the optimum at eps 1e-6 is held to the twin's
+        #  own distance: one QP of N = 20 single support, 0.0503 N on the GPU and the twin alike)
         twin_gap = np.abs(ref["u"].reshape(-1) - xs * p.force_scale).max()
         assert np.abs(out["u"][b].reshape(-1) - xs * p.force_scale).max() <= max(TOL_EXACT_N, twin_gap + TOL_TWIN_N)
         kr = orc.kkt_residuals(kq["P"], kq["q"], kq["A"], kq["l"], kq["u"], out["u"][b].reshape(-1)[vi] / p.force_scale, out["y"][b][ri])

@@ -8,14 +8,13 @@ the two.
 import argparse
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
-import numpy as np
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 import torch
 
 from g1_locomotion_amd import BatchMPC, _lib, synth
+import benchlib as bl
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=7)
@@ -23,42 +22,17 @@ ap.add_argument("--k", type=int, default=20)
 ap.add_argument("--batch", type=int, default=4096)
 ap.add_argument("--nstar", type=int, nargs="*", default=[8, 10, 12, 16, 20, 24])
 args = ap.parse_args()
-dev = torch.device("cuda", 0)
-
-
-def timed(run):
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    for _ in range(args.k):
-        run()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t) / args.k
 
 
 def case(nstar, schedule):
     B = args.batch
-    runs, engs, keep, mean_it = {}, {}, [], {}
+    runs, engs, iters = {}, {}, {}
     for n in (nstar, nstar - 1, nstar - 3):
-        x0, xr, ft, ct = synth.synthetic_batch(B, n, seed=11, schedule=schedule)
-        d = [torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (x0, xr, ft, ct.astype(np.uint8))]
-        u = torch.empty((B, n, 12), dtype=torch.float64, device=dev)
-        st = torch.empty(B, dtype=torch.int32, device=dev); it = torch.empty(B, dtype=torch.int32, device=dev)
-        eng = BatchMPC(horizon=n, kernel=_lib.KERNEL_WRENCH)           # (the wrapper sets the flag for n outside the tabulated set, and only then)
-        keep.append((d, u, st, it))
-        engs[n] = eng
-        runs[n] = (lambda e, d, u, st, it, B=B: lambda: e.solve_device(B, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), u.data_ptr(),
-                                                                       status=st.data_ptr(), iters=it.data_ptr()))(eng, d, u, st, it)
-    for n, r in runs.items():
-        for _ in range(3):
-            r()
-        torch.cuda.synchronize()
-        mean_it[n] = float(keep[list(runs).index(n)][3].float().mean())
-    ts = {n: [] for n in runs}
-    for _ in range(args.reps):
-        for n, r in runs.items():
-            ts[n].append(timed(r))
-    med = {n: float(np.median(v)) for n, v in ts.items()}
-    spread = {n: (max(v) - min(v)) / med[n] for n, v in ts.items()}
+        d, u, st, iters[n] = bl.batch_buffers(*synth.synthetic_batch(B, n, seed=11, schedule=schedule))
+        engs[n] = BatchMPC(horizon=n, kernel=_lib.KERNEL_WRENCH)       # (the wrapper sets the flag for n outside the tabulated set, and only then)
+        runs[n] = bl.device_call(engs[n], d, u, st, iters[n])
+    med, spread = bl.wall_clock(runs, args.reps, args.k)
+    mean_it = {n: float(it.float().mean()) for n, it in iters.items()}  # (every call of a horizon solves the same QPs)
     names = {n: e.kernel_name() for n, e in engs.items()}
     for e in engs.values():
         e.close()

@@ -9,11 +9,12 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 import numpy as np
 import torch
 
 from g1_locomotion_amd import BatchMPC, _lib, synth
+import benchlib as bl
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=21)
@@ -21,7 +22,7 @@ ap.add_argument("--horizons", type=int, nargs="+", default=[10])
 ap.add_argument("--batch", type=int, default=4096)
 ap.add_argument("--schedule", default="double")
 args = ap.parse_args()
-dev = torch.device("cuda", 0)
+dev = bl.dev
 
 
 def tilted(B, N, seed, max_tilt=0.35):
@@ -32,24 +33,13 @@ def tilted(B, N, seed, max_tilt=0.35):
 
 
 def case(B, N, schedule):
-    x0, xr, ft, ct = synth.synthetic_batch(B, N, seed=11, schedule=schedule)
-    d = [torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (x0, xr, ft, ct.astype(np.uint8))]
-    u = torch.empty((B, N, 12), dtype=torch.float64, device=dev)
-    st = torch.empty(B, dtype=torch.int32, device=dev); it = torch.empty(B, dtype=torch.int32, device=dev)
+    buf = bl.batch_buffers(*synth.synthetic_batch(B, N, seed=11, schedule=schedule))
     flat = np.zeros((B, N, 4, 3)); flat[..., 2] = 1.0
     nrm = {"normals e_z": torch.from_numpy(flat.reshape(B, N, 12)).to(dev), "normals tilted": torch.from_numpy(tilted(B, N, 12)).to(dev)}
     engs = {k: BatchMPC(horizon=N, kernel=_lib.KERNEL_WRENCH, timing=True) for k in ("no normals", "normals e_z", "normals tilted")}
     for k, v in nrm.items():
         engs[k].set_contact_normals(v)
-    ms = {k: [] for k in engs}
-    its = {}
-    for r in range(args.reps + 3):
-        for k, e in engs.items():
-            e.solve_device(B, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), u.data_ptr(), status=st.data_ptr(), iters=it.data_ptr())
-            e.synchronize()
-            if r >= 3:                                # (three warm-up rounds)
-                ms[k].append(e.last_kernel_ms())
-            its[k] = (float(it.float().mean()), int((st == _lib.SOLVED).sum()))
+    ms, its = bl.kernel_ms(engs, *buf, args.reps)
     base = float(np.median(ms["no normals"]))
     for k, e in engs.items():
         med = float(np.median(ms[k]))

@@ -12,17 +12,17 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
 import numpy as np
 import torch
 
 from g1_locomotion_amd import BatchMPC, _lib, synth
+import benchlib as bl
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=21)
 ap.add_argument("--batch", type=int, default=4096)
 args = ap.parse_args()
-dev = torch.device("cuda", 0)
 
 
 def tandem_batch(B, N, seed):
@@ -36,21 +36,9 @@ def tandem_batch(B, N, seed):
 
 def case(tag, N, data, variants):
     """variants: name -> BatchMPC keywords; the first one is the base the others are compared with."""
-    x0, xr, ft, ct = data
-    B = x0.shape[0]
-    d = [torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (x0, xr, ft, ct.astype(np.uint8))]
-    u = torch.empty((B, N, 12), dtype=torch.float64, device=dev)
-    st = torch.empty(B, dtype=torch.int32, device=dev); it = torch.empty(B, dtype=torch.int32, device=dev)
+    B = data[0].shape[0]
     engs = {k: BatchMPC(horizon=N, timing=True, **kw) for k, kw in variants.items()}
-    ms = {k: [] for k in engs}
-    its = {}
-    for r in range(args.reps + 3):
-        for k, e in engs.items():
-            e.solve_device(B, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), u.data_ptr(), status=st.data_ptr(), iters=it.data_ptr())
-            e.synchronize()
-            if r >= 3:                                # (three warm-up rounds)
-                ms[k].append(e.last_kernel_ms())
-            its[k] = (float(it.float().mean()), int((st == _lib.SOLVED).sum()), int((st < 0).sum()))
+    ms, its = bl.kernel_ms(engs, *bl.batch_buffers(*data), args.reps)
     base = float(np.median(ms[next(iter(engs))]))
     for k, e in engs.items():
         med = float(np.median(ms[k]))

@@ -8,21 +8,21 @@ clock around torch.cuda.synchronize()), the variants interleaved block by block.
 import argparse
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 import numpy as np
 import torch
 
 from g1_locomotion_amd import BatchMPC, RaggedMPC, _lib, synth
 from g1_locomotion_amd.mpc import robots_array
+import benchlib as bl
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--k", type=int, default=20)
 args = ap.parse_args()
-dev = torch.device("cuda", 0)
+dev = bl.dev
 
 
 def draw(B, seed):
@@ -32,46 +32,19 @@ def draw(B, seed):
                         mu=rng.uniform(0.3, 1.0, B), fz_min=rng.uniform(0.0, 20.0, B), fz_max=rng.uniform(150.0, 1200.0, B))
 
 
-def timed(run):
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    for _ in range(args.k):
-        run()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t) / args.k
-
-
 def compare(label, B, runs):
-    """runs: {name: callable}; interleaved blocks, median per name."""
-    for r in runs.values():
-        for _ in range(3):
-            r()
-    ts = {n: [] for n in runs}
-    for _ in range(args.reps):
-        for n, r in runs.items():
-            ts[n].append(timed(r))
-    med = {n: float(np.median(v)) for n, v in ts.items()}
-    spread = {n: (max(v) - min(v)) / med[n] for n, v in ts.items()}
-    names = list(runs)
-    base = med[names[0]]
-    for n in names:
-        print(f"{label:34s} {n:22s} {med[n] * 1e3:8.3f} ms/call  {B / med[n] / 1e6:7.3f} M QP/s  spread {spread[n] * 100:4.1f} %  "
-              f"vs {names[0]}: {(med[n] / base - 1) * 100:+6.2f} %", flush=True)
+    bl.compare(label, B, runs, args.reps, args.k, 22, next(iter(runs)))
 
 
 def batch_case(schedule, B=4096, N=10):
-    x0, xr, ft, ct = synth.synthetic_batch(B, N, seed=11, schedule=schedule)
-    d = [torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (x0, xr, ft, ct.astype(np.uint8))]
-    u = torch.empty((B, N, 12), dtype=torch.float64, device=dev)
-    st = torch.empty(B, dtype=torch.int32, device=dev); it = torch.empty(B, dtype=torch.int32, device=dev)
+    buf = bl.batch_buffers(*synth.synthetic_batch(B, N, seed=11, schedule=schedule))
     engs = dict(general=BatchMPC(horizon=N, kernel=_lib.KERNEL_WRENCH), uniform=BatchMPC(horizon=N), drawn=BatchMPC(horizon=N), auto=BatchMPC(horizon=N, max_contacts_per_step=2))
     recs = dict(uniform=torch.from_numpy(robots_array(B)).to(dev), drawn=torch.from_numpy(draw(B, 12)).to(dev))
     for k, v in recs.items():
         engs[k].set_robots(v)
 
     def mk(e):
-        return lambda: e.solve_device(B, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), u.data_ptr(),
-                                      status=st.data_ptr(), iters=it.data_ptr())
+        return bl.device_call(e, *buf)
     runs = {"general (no records)": mk(engs["general"]), "records = config": mk(engs["uniform"]), "records drawn": mk(engs["drawn"])}
     if schedule == "single":                      # (AUTO with the single-support bound, as bench.py runs configs[1]: the one-wave kernel)
         runs["AUTO, bound 2 (no records)"] = mk(engs["auto"])
@@ -85,29 +58,14 @@ def batch_case(schedule, B=4096, N=10):
 
 
 def ragged_case(B=16384, HZ=(8, 12, 16)):
-    rng = np.random.default_rng(4)
-    Nq = rng.choice(HZ, size=B).astype(np.int32)
-    x0 = np.empty((B, 13)); xr, ft, ct = [], [], []
-    by, pos = {}, {N: 0 for N in HZ}
-    for N in HZ:
-        idx = np.where(Nq == N)[0]
-        by[N] = synth.synthetic_batch(len(idx), N, seed=40 + N, schedule="mixed")
-    for b in range(B):
-        N = int(Nq[b]); a, b_, c, d_ = by[N]; i = pos[N]; pos[N] += 1
-        x0[b] = a[i]; xr.append(b_[i]); ft.append(c[i].reshape(N, 12)); ct.append(d_[i].reshape(N, 4))
-    xr, ft, ct = np.concatenate(xr), np.concatenate(ft), np.concatenate(ct).astype(np.uint8)
-    rows = int(Nq.sum())
-    d = [torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (x0, xr, ft, ct)]
-    u = torch.empty((rows, 12), dtype=torch.float64, device=dev)
-    st = torch.empty(B, dtype=torch.int32, device=dev); it = torch.empty(B, dtype=torch.int32, device=dev)
+    Nq, *buf = bl.ragged_fleet(B, HZ)
     plain, uni, rec = RaggedMPC(horizons=HZ), RaggedMPC(horizons=HZ), RaggedMPC(horizons=HZ)
     r_uni, r_rec = torch.from_numpy(robots_array(B)).to(dev), torch.from_numpy(draw(B, 13)).to(dev)
     uni.set_robots(r_uni)
     rec.set_robots(r_rec)
 
     def mk(e):
-        return lambda: e.solve_device(B, Nq, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), u.data_ptr(),
-                                      status=st.data_ptr(), iters=it.data_ptr())
+        return bl.device_call(e, *buf, Nq=Nq)
     compare(f"ragged B={B} N in {HZ} mixed", B, {"general (no records)": mk(plain), "records = config": mk(uni), "records drawn": mk(rec)})
     plain.close(); uni.close(); rec.close()
 
