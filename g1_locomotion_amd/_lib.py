@@ -37,7 +37,7 @@ EXPORTS = (
     "srbdqp_assemble_f64", "srbdqp_assemble_wrench_f64",
     "srbdqp_ragged_create", "srbdqp_ragged_destroy", "srbdqp_ragged_last_error", "srbdqp_ragged_flush", "srbdqp_solve_ragged_device_f64", "srbdqp_solve_ragged_f64",
     "srbdqp_solve_ragged_device_f32", "srbdqp_solve_ragged_f32", "srbdqp_solve_ragged_warm_device_f64", "srbdqp_solve_ragged_warm_device_f32",
-    "srbdqp_set_schedule_hint", "srbdqp_set_robots", "srbdqp_set_robots_device", "srbdqp_set_contact_normals", "srbdqp_set_contact_normals_device", "srbdqp_ragged_set_robots", "srbdqp_ragged_set_robots_device", "srbdqp_set_weights", "srbdqp_set_weights_device", "srbdqp_ragged_set_weights", "srbdqp_ragged_set_weights_device", "srbdqp_flush", "srbdqp_shard_range", "srbdqp_gather_u0_f64", "srbdqp_stage_ptrs", "srbdqp_solve_staged_f64", "srbdqp_update_f64", "srbdqp_prepare_staged_f64", "srbdqp_solve_prepared_f64", "srbdqp_set_stamp_buffer", "srbdqp_synchronize", "srbdqp_last_kernel_ms", "srbdqp_last_kernel_parts_ms", "srbdqp_kernel_name", "srbdqp_batch1_launch_path", "srbdqp_version",
+    "srbdqp_set_schedule_hint", "srbdqp_set_robots", "srbdqp_set_robots_device", "srbdqp_set_contact_normals", "srbdqp_set_contact_normals_device", "srbdqp_ragged_set_robots", "srbdqp_ragged_set_robots_device", "srbdqp_set_weights", "srbdqp_set_weights_device", "srbdqp_ragged_set_weights", "srbdqp_ragged_set_weights_device", "srbdqp_set_external_wrench", "srbdqp_set_external_wrench_device", "srbdqp_ragged_set_external_wrench", "srbdqp_ragged_set_external_wrench_device", "srbdqp_flush", "srbdqp_shard_range", "srbdqp_gather_u0_f64", "srbdqp_stage_ptrs", "srbdqp_solve_staged_f64", "srbdqp_update_f64", "srbdqp_prepare_staged_f64", "srbdqp_solve_prepared_f64", "srbdqp_set_stamp_buffer", "srbdqp_synchronize", "srbdqp_last_kernel_ms", "srbdqp_last_kernel_parts_ms", "srbdqp_kernel_name", "srbdqp_batch1_launch_path", "srbdqp_version",
     # include/srbdqp_cascade.h
     "srbdqp_swing_f64", "srbdqp_swing_device_f64", "srbdqp_wbid_reference_f64", "srbdqp_wbid_reference_device_f64",
     "srbdqp_mpc_inputs_f64", "srbdqp_mpc_inputs_device_f64",
@@ -241,6 +241,7 @@ def load():
     lib.srbdqp_set_schedule_hint.restype = C.c_int
     for _fn in (lib.srbdqp_set_robots, lib.srbdqp_set_robots_device, lib.srbdqp_ragged_set_robots, lib.srbdqp_ragged_set_robots_device,
                 lib.srbdqp_set_weights, lib.srbdqp_set_weights_device, lib.srbdqp_ragged_set_weights, lib.srbdqp_ragged_set_weights_device,
+                lib.srbdqp_set_external_wrench, lib.srbdqp_set_external_wrench_device, lib.srbdqp_ragged_set_external_wrench, lib.srbdqp_ragged_set_external_wrench_device,
                 lib.srbdqp_set_contact_normals, lib.srbdqp_set_contact_normals_device):
         _fn.argtypes = [H, C.c_void_p, C.c_int32]
         _fn.restype = C.c_int

@@ -106,11 +106,12 @@ struct srbdqp_handle {
     srbdqp::AqlQueue* aql = nullptr;
     bool aql_tried = false;
     std::string aql_why;
-    // the per-QP side inputs (one descriptor each below: RobotsIn, WeightsIn, NormalsIn).  The fp64 batch and ragged solves on the general kernel read them; null:
+    // the per-QP side inputs (one descriptor each below: RobotsIn, WeightsIn, NormalsIn, ExtWrenchIn).  The fp64 batch and ragged solves on the general kernel read them; null:
     // the config's robot / the config's q_diag and r_diag / flat ground for every QP
     PerQp<srbdqp_robot> robots;            // srbdqp_set_robots / _device
     PerQp<srbdqp_weights> weights;         // srbdqp_set_weights / _device
     PerQp<double> normals;                 // srbdqp_set_contact_normals / _device: [len][N][12] doubles (NormalsIn::per_qp), fp64 batch solves only
+    PerQp<double> ext;                     // srbdqp_set_external_wrench / _device: [len][N][6] doubles (ExtWrenchIn::per_qp); a ragged bucket: the object's rows
     // SRBDQP_FLAG_ANY_HORIZON with a horizon that has no instantiation: cfg.horizon stays the live horizon n (every array has the caller's shape for n) and the
     // solves run the general kernel instantiated for live_nstar, the smallest tabulated horizon >= n, in its live-horizon mode (srbdqp_wrench.hpp, MODE = 3)
     int live_nstar = 0;                    // 0: the horizon has its own instantiations
@@ -326,7 +327,7 @@ constexpr int kTileClassMinBatch = 512;
 // does a solve of B QPs on this handle go to the general kernel (srbdqp_wrench.hpp)?  launch() asks this.
 inline bool uses_wrench(const srbdqp_handle* h, const Call& c, int maxs, int B) {
     const int N = h->cfg.horizon;
-    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || h->robots.dev || h->weights.dev || h->normals.dev || h->live_nstar) return true;   // (per-QP records and weights, contact normals, a live horizon: only the general kernel reads them)
+    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || h->robots.dev || h->weights.dev || h->ext.dev || h->normals.dev || h->live_nstar) return true;   // (per-QP records, weights and wrenches, contact normals, a live horizon: only the general kernel reads them)
     // N = 20 single support too, for batches: the general kernel holds 2 workgroups per CU there, the compact one 1
     // (tools/schedule_bench.py, 16,384 QPs: 2.85 M QP/s against 1.95 M; at N = 12 / 16 the compact kernel wins, 7.1 / 4.9 M
     // against 5.7 / 4.2 M)
@@ -645,21 +646,24 @@ int launch_compact(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t 
 }
 
 // ---- the variants of the general kernel: which one a handle is in, and which call has a form for it ----
-// A handle is in exactly one of six states.  Live and RankAware are fixed by srbdqp_create; Robots, Weights and Normals come and go with the setters (a clearing
-// call -- NULL, 0 -- is accepted in every state).  No two hold at once, except that robot records and weights combine -- such a handle is Robots here, and
-// Weights is the handle with weights alone:
+// A handle is in exactly one of seven states.  Live and RankAware are fixed by srbdqp_create; Robots, Weights and Normals come and go with the setters (a clearing
+// call -- NULL, 0 -- is accepted in every state).  No two hold at once, except that robot records, weights and an external wrench combine -- a handle with
+// records is Robots here, Weights is the handle with weights and no records, and ExtWrench the handle with a wrench alone:
 //   Live x RankAware                      srbdqp_create refuses SRBDQP_FLAG_RANK_AWARE at a live horizon
 //   Robots x Live, Robots x RankAware     check_handle<RobotsIn> (srbdqp_set_robots / _device, and the ragged pair for every bucket)
 //   Normals x Live, Normals x RankAware   check_handle<NormalsIn> (srbdqp_set_contact_normals / _device)
 //   Robots x Normals                      each of the two checks refuses while the other is set
 //   Weights x Live, Weights x RankAware, Weights x Normals      check_handle<WeightsIn> (srbdqp_set_weights / _device, and the ragged pair for every bucket)
 //                                         and check_handle<NormalsIn>
+//   ExtWrench x Live, ExtWrench x RankAware, ExtWrench x Normals   check_handle<ExtWrenchIn> (srbdqp_set_external_wrench / _device, and the ragged pair for
+//                                         every bucket) and check_handle<NormalsIn>
 // (srbdqp_ragged_create refuses SRBDQP_FLAG_RANK_AWARE, and a ragged object has no normals: its buckets are Plain, Robots, Weights or Live.)
-enum class Variant { Plain, Robots, Normals, Live, RankAware, Weights };
+enum class Variant { Plain, Robots, Normals, Live, RankAware, Weights, ExtWrench };
 
 inline Variant variant_of(const srbdqp_handle* h) {
     if (h->robots.dev) return Variant::Robots;
     if (h->weights.dev) return Variant::Weights;
+    if (h->ext.dev) return Variant::ExtWrench;
     if (h->normals.dev) return Variant::Normals;
     if (h->live_nstar) return Variant::Live;
     if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) return Variant::RankAware;
@@ -667,7 +671,7 @@ inline Variant variant_of(const srbdqp_handle* h) {
 }
 
 // `what` -- a C-ABI call by its name, or a kind of solve -- has no form for a handle in state v: the message (include/srbdqp.h has the reasons and the lists;
-// the four texts are quoted in INTEGRATION.md and matched by the tests) and SRBDQP_E_INVALID
+// the fixed texts, one per state, are quoted in INTEGRATION.md and matched by the tests) and SRBDQP_E_INVALID
 int refuse(srbdqp_handle* h, Variant v, const char* what) {
     const std::string w(what);
     switch (v) {
@@ -692,6 +696,10 @@ int refuse(srbdqp_handle* h, Variant v, const char* what) {
         h->err = w + ": refused while per-QP cost weights are set (srbdqp_set_weights): only the fp64 batch and ragged solves on the general kernel read "
                      "them -- one pair of weights for every QP goes in srbdqp_config";
         break;
+    case Variant::ExtWrench:
+        h->err = w + ": refused while an external wrench is set (srbdqp_set_external_wrench): only the fp64 batch and ragged solves on the general kernel read "
+                     "it -- srbdqp_set_external_wrench(h, NULL, 0) goes back to no wrench";
+        break;
     }
     return SRBDQP_E_INVALID;
 }
@@ -711,9 +719,11 @@ constexpr unsigned kFormsAssemble = form(Variant::RankAware);
 // srbdqp_assemble_wrench_f64
 constexpr unsigned kFormsAssembleWrench = 0;
 // srbdqp_set_robots / _device with records (check_handle<RobotsIn>, which refuses N = 24 as well)
-constexpr unsigned kFormsSetRobots = form(Variant::Robots) | form(Variant::Weights);
+constexpr unsigned kFormsSetRobots = form(Variant::Robots) | form(Variant::Weights) | form(Variant::ExtWrench);
 // srbdqp_set_weights / _device with records (check_handle<WeightsIn>, which refuses N = 24 as well): beside robot records or in place of earlier weights
-constexpr unsigned kFormsSetWeights = form(Variant::Weights) | form(Variant::Robots);
+constexpr unsigned kFormsSetWeights = form(Variant::Weights) | form(Variant::Robots) | form(Variant::ExtWrench);
+// srbdqp_set_external_wrench / _device with an array (check_handle<ExtWrenchIn>, which refuses N = 24 as well): beside records and weights or in place of an earlier wrench
+constexpr unsigned kFormsSetExtWrench = form(Variant::ExtWrench) | form(Variant::Robots) | form(Variant::Weights);
 // srbdqp_set_contact_normals / _device with normals (check_handle<NormalsIn>, which refuses N = 24 as well, and records in words of its own)
 constexpr unsigned kFormsSetNormals = form(Variant::Normals) | form(Variant::Robots);
 
@@ -794,6 +804,19 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
         else { h->err = "the assembly dump is fp64 only"; return SRBDQP_E_INVALID; }
     } else {
         if constexpr (sizeof(R) == 8 && N != 24) {
+            // an external wrench (srbdqp_set_external_wrench / _device), with or without weights and robot records: the MODE = 7 instantiation, the wrench, the
+            // weights (or null) and the records (or null) as its further arguments -- every launch of a solve comes through here, as below
+            if (h->ext.dev) {
+                constexpr size_t lds_ew = lds + 11 * sizeof(double);         // + the slots of MODE = 6 and the bad-wrench mark behind the layout (qp_ext_wrench_to_lds)
+                constexpr int by_lds_ew = (S::wgs_of(S::o_end + 11) * S::NW + 3) / 4;
+                constexpr int by_waves_ew = WPS * 4 / S::NW;
+                static_assert((by_lds_ew < WPS ? by_lds_ew : WPS) == WPS &&
+                              (S::wgs_of(S::o_end + 11) < by_waves_ew ? S::wgs_of(S::o_end + 11) : by_waves_ew) == (S::lds_wgs < by_waves_ew ? S::lds_wgs : by_waves_ew),
+                              "the 88 bytes of LDS cost no workgroup per CU");
+                static const std::string nm_ew = nm + "_ew";
+                return launch_kernel(h, &srbdqp::srbdqp_wrench_ew_kernel<N, WPS>, nm_ew.c_str(), grid, dim3(S::BT), lds_ew, st, a, h->ext.dev,
+                                     reinterpret_cast<const double*>(h->weights.dev), reinterpret_cast<const double*>(h->robots.dev));
+            }
             // per-QP cost weights (srbdqp_set_weights / _device), with or without robot records: the MODE = 6 instantiation, the weights and the records (or null)
             // as its second and third arguments -- every launch of a solve comes through here, as below.  (The weight setters refuse what the record setters do.)
             if (h->weights.dev) {
@@ -1154,6 +1177,12 @@ const char* normal_fault(const double* n) {
     return nullptr;
 }
 
+// the rule of include/srbdqp.h for one value of an external wrench (the same one the kernel applies to a device array, srbdqp_wrench.hpp
+// qp_ext_wrench_to_lds: one bound, SRBDQP_EXT_WRENCH_MAX, on both sides; NaN fails it); null = valid, else what is wrong
+const char* ext_wrench_fault(const double* v) {
+    return std::fabs(*v) <= SRBDQP_EXT_WRENCH_MAX ? nullptr : "every value must be finite with |value| <= 1e6";
+}
+
 // Horizons whose general kernel has a per-QP-record instantiation (MODE = 2) without scratch memory: N = 24 has none -- the MODE = 0 kernel that ships keeps
 // 20 bytes per lane in scratch with its three extra set-up waves, and a MODE = 2 copy without them (XW = 0) 24 bytes -- so the setters refuse an N = 24
 // handle / a ragged object with an N = 24 bucket.  The MODE = 6 instantiation of the weights is the MODE = 2 one with one more LDS slot
@@ -1217,6 +1246,28 @@ struct NormalsIn {
     static const char* beside(const srbdqp_handle* h) { return h->robots.dev ? ": refused while per-QP robot records are set (srbdqp_set_robots): no instantiation reads both (DESIGN.md section 13)" : nullptr; }
 };
 
+struct ExtWrenchIn {
+    using T = double;                                   // 6 doubles per horizon row: a handle takes [len][N][6], a ragged object [rows][6]
+    static constexpr const char* name = "external_wrench";
+    static constexpr const char* what = "external wrenches";
+    static constexpr const char* alloc = "hipMalloc external wrench";
+    static constexpr const char* unit = "block";
+    static constexpr unsigned forms = kFormsSetExtWrench;
+    static constexpr size_t stride = 1;
+    template <class O> static PerQp<T>& of(O* o) { return o->ext; }
+    static size_t per_qp(const srbdqp_handle* h) { return 6 * (size_t)h->cfg.horizon; }
+    static size_t per_qp(const srbdqp_ragged*) { return 6; }                          // (per row)
+    static const char* fault(const T* e) { return ext_wrench_fault(e); }
+    static std::string where(const srbdqp_handle* h, size_t i) {
+        const size_t N = (size_t)h->cfg.horizon;
+        return "the wrench at (qp " + std::to_string(i / (6 * N)) + ", step " + std::to_string((i / 6) % N) + ", component " + std::to_string(i % 6) + ")";
+    }
+    static std::string where(const srbdqp_ragged*, size_t i) { return "the wrench at (row " + std::to_string(i / 6) + ", component " + std::to_string(i % 6) + ")"; }
+    static std::string count(size_t len) { return "an external wrench for " + std::to_string(len); }
+    static std::string n24(const char*) { return "an external wrench: not at N = 24 (no instantiation of the general kernel reads it there, DESIGN.md section 16)"; }
+    static const char* beside(const srbdqp_handle*) { return nullptr; }
+};
+
 // may this handle take side input K?  (a live horizon, rank-aware steps, another side input it does not combine with: a combined mode would be another copy of
 // every instantiation)
 template <class K>
@@ -1270,14 +1321,16 @@ int quiesce_all_streams(srbdqp_handle* h) {
 // fp64 batch solve of B QPs with a side input set: the general kernel, and a record / a block of normals for every QP
 int variant_check_batch(srbdqp_handle* h, int32_t B) {
     const Variant v = variant_of(h);
-    if (v != Variant::Robots && v != Variant::Normals && v != Variant::Weights) return SRBDQP_OK;
+    if (v != Variant::Robots && v != Variant::Normals && v != Variant::Weights && v != Variant::ExtWrench) return SRBDQP_OK;
     if (h->cfg.kernel != SRBDQP_KERNEL_AUTO && h->cfg.kernel != SRBDQP_KERNEL_WRENCH) {
-        h->err = std::string(v == Variant::Robots ? "per-QP robot records" : v == Variant::Weights ? "per-QP cost weights (srbdqp_set_weights)" : "contact normals (srbdqp_set_contact_normals)") +
+        h->err = std::string(v == Variant::Robots ? "per-QP robot records" : v == Variant::Weights ? "per-QP cost weights (srbdqp_set_weights)" :
+                             v == Variant::ExtWrench ? "an external wrench (srbdqp_set_external_wrench)" : "contact normals (srbdqp_set_contact_normals)") +
                  " are read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH while they are set";
         return SRBDQP_E_INVALID;
     }
     if (const int rc = covers_batch<WeightsIn>(h, B)) return rc;      // (weights alone, or beside robot records: each length on its own)
     if (const int rc = covers_batch<RobotsIn>(h, B)) return rc;
+    if (const int rc = covers_batch<ExtWrenchIn>(h, B)) return rc;
     return covers_batch<NormalsIn>(h, B);
 }
 
@@ -1427,7 +1480,7 @@ int srbdqp_destroy(srbdqp_handle* h) {
         for (auto& r : sl.rsets) if (r.ev_tail) (void)hipEventDestroy(r.ev_tail);
     }
     if (h->done_count) (void)hipFree(h->done_count);
-    h->robots.release(); h->weights.release(); h->normals.release();
+    h->robots.release(); h->weights.release(); h->normals.release(); h->ext.release();
     if (h->stage_host) (void)hipHostFree(h->stage_host);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1992,6 +2045,7 @@ struct srbdqp_ragged {
     // engine: a bucket's workgroup reads the record of the caller's index its dispatch order names
     PerQp<srbdqp_robot> robots;
     PerQp<srbdqp_weights> weights;
+    PerQp<double> ext;                     // srbdqp_ragged_set_external_wrench / _device: [rows][6] doubles in the caller's row order (len = rows)
     std::string err;
 };
 
@@ -2063,7 +2117,7 @@ int srbdqp_ragged_destroy(srbdqp_ragged* r) {
     if (r->h_perm) (void)hipHostFree(r->h_perm);
     if (r->h_off) (void)hipHostFree(r->h_off);
     if (r->ws) (void)hipFree(r->ws);
-    r->robots.release(); r->weights.release();
+    r->robots.release(); r->weights.release(); r->ext.release();
     delete r;
     return SRBDQP_OK;
 }
@@ -2093,6 +2147,15 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
     if (f32) for (auto* bh : r->hs) if (bh->live_nstar) { const int rc = refuse(bh, Variant::Live, "an fp32 ragged solve"); r->err = bh->err; return rc; }
     if (const int rc = ragged_side_check<RobotsIn>(r, B, f32)) return rc;
     if (const int rc = ragged_side_check<WeightsIn>(r, B, f32)) return rc;
+    if (r->ext.dev) {   // (its length is in rows: f32 here, the rows of this call below)
+        if (const int rc = ragged_side_check<ExtWrenchIn>(r, 0, f32)) return rc;
+        long long need = 0;
+        for (int32_t b = 0; b < B && N_per_qp; ++b) need += N_per_qp[b];
+        if ((size_t)need > r->ext.len) {
+            r->err = "ragged solve of " + std::to_string(need) + " horizon rows with an external wrench for " + std::to_string(r->ext.len) + " set: every row needs its wrench";
+            return SRBDQP_E_INVALID;
+        }
+    }
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(r, hipSetDevice(r->device));
     hipStream_t sin = stream ? reinterpret_cast<hipStream_t>(stream) : r->stream;
@@ -2244,7 +2307,7 @@ int ragged_host_impl(srbdqp_ragged* r, int32_t B, size_t esz, const int32_t* N_p
 }
 }  // namespace
 
-// ---- the setters of the per-QP side inputs (the descriptors RobotsIn, WeightsIn, NormalsIn above) ----
+// ---- the setters of the per-QP side inputs (the descriptors RobotsIn, WeightsIn, NormalsIn, ExtWrenchIn above) ----
 // One skeleton for the host form and one for the device form, over the kind K and the owner O, a handle or a ragged object.  The owner supplies its device, how
 // to quiesce, how to check (owner_check) and what follows a change of the pointer (owner_changed).
 namespace {
@@ -2337,6 +2400,10 @@ int srbdqp_ragged_set_robots(srbdqp_ragged* r, const srbdqp_robot* host, int32_t
 int srbdqp_ragged_set_robots_device(srbdqp_ragged* r, const srbdqp_robot* dev, int32_t length) { return set_device<RobotsIn>(r, "srbdqp_ragged_set_robots_device", dev, length); }
 int srbdqp_ragged_set_weights(srbdqp_ragged* r, const srbdqp_weights* host, int32_t length) { return set_host<WeightsIn>(r, "srbdqp_ragged_set_weights", host, length); }
 int srbdqp_ragged_set_weights_device(srbdqp_ragged* r, const srbdqp_weights* dev, int32_t length) { return set_device<WeightsIn>(r, "srbdqp_ragged_set_weights_device", dev, length); }
+int srbdqp_set_external_wrench(srbdqp_handle* h, const double* host, int32_t length) { return set_host<ExtWrenchIn>(h, "srbdqp_set_external_wrench", host, length); }
+int srbdqp_set_external_wrench_device(srbdqp_handle* h, const double* dev, int32_t length) { return set_device<ExtWrenchIn>(h, "srbdqp_set_external_wrench_device", dev, length); }
+int srbdqp_ragged_set_external_wrench(srbdqp_ragged* r, const double* host, int32_t rows) { return set_host<ExtWrenchIn>(r, "srbdqp_ragged_set_external_wrench", host, rows); }
+int srbdqp_ragged_set_external_wrench_device(srbdqp_ragged* r, const double* dev, int32_t rows) { return set_device<ExtWrenchIn>(r, "srbdqp_ragged_set_external_wrench_device", dev, rows); }
 
 int srbdqp_ragged_flush(srbdqp_ragged* r, void* stream) {
     if (!r) return SRBDQP_E_INVALID;

@@ -96,7 +96,7 @@ struct WrenchSmem {
     static constexpr int o_L = o_J + N * 36;              // CN: 36N  L_k[b][3 ci + ax] = R_ci[b][ax], the linear part of a local force variable's wrench column
     static constexpr int o_red = o_L + (CN ? N * 36 : 0); // 32   reductions / check maxima / vote flags
     static constexpr int o_ct = o_red + 32;               // 4N bytes of contact flags
-    static constexpr int o_misc = o_ct + up2((N * 4 + 7) / 8);   // [0] numerical failure, [1] CN: a contact normal that is not one
+    static constexpr int o_misc = o_ct + up2((N * 4 + 7) / 8);   // [0] numerical failure, [1] CN: a contact normal that is not one, [2] MODE 7: the QP's wrench has a value that is not zero
     static constexpr int o_sq = o_misc + 4;               // 12   sqrt(q_diag)
     static constexpr int o_int = o_sq + 12;               // ints: gsz[N], goff[N + 1], n_g, na, wrench flag[N]
     static constexpr int o_R = o_int + up2((3 * N + 6) / 2 + 1);
@@ -694,6 +694,43 @@ __device__ __forceinline__ void args_robot_to_lds(const KArgs& a, double* dst) {
     dst[7] = 0.0;
 }
 
+// The launch-wide cost weights of KArgs in the slots of qp_weights_to_lds (MODE = 7 without weight records): the values fill_args() computed, copied by the
+// lanes that write them there.  Called by every lane of wave 0.
+__device__ __forceinline__ void args_weights_to_lds(const KArgs& a, const int lane, double* sq, double* dst) {
+    const int e = lane - 32;
+    if (e >= 0 && e < 12) sq[e] = a.sqrtq[e];
+    if (e == 13) dst[0] = a.rs2;
+    if (e == 14) dst[1] = 0.0;
+}
+
+// A QP's external wrench (MODE = 7, srbdqp_set_external_wrench): its 6 N values [step][torque(3), force(3)], world frame, which wave 0 loaded with the first
+// batch of loads (value i on lane i % 64, register i / 64), tested -- srbdqp_set_external_wrench's rule: every value finite and |value| <= SRBDQP_EXT_WRENCH_MAX,
+// as ext_wrench_fault() of srbdqp.hip tests it; NaN fails it -- and written to dst[0 .. 6 N); the ballot makes the verdict the wave's.  *pushes = 1 where a
+// valid wrench has a value that is not zero (the QP's x_q is refined then, wrench_qp), else 0.  A wrench that is none
+// sets *bad = 1 and leaves zeros: the QP is reported as SRBDQP_NUMERICAL with zero forces and the roll-out of no wrench.  Called by every lane of wave 0.
+template <int N>
+__device__ __forceinline__ void qp_ext_wrench_to_lds(const double (&v)[(6 * N + 63) / 64], const int lane, double* dst, double* bad, double* pushes) {
+    constexpr int RW = (6 * N + 63) / 64;
+    bool wrong = false, nonzero = false;
+#pragma unroll
+    for (int r = 0; r < RW; ++r) {
+        wrong = wrong || (lane + 64 * r < 6 * N && !(fabs(v[r]) <= SRBDQP_EXT_WRENCH_MAX));
+        nonzero = nonzero || (lane + 64 * r < 6 * N && v[r] != 0.0);
+    }
+    const bool ok = __ballot(wrong) == 0ull;
+    const bool any = __ballot(nonzero) != 0ull;
+#pragma unroll
+    for (int r = 0; r < RW; ++r) { const int i = lane + 64 * r; if (i < 6 * N) dst[i] = ok ? v[r] : 0.0; }
+    if (lane == 0) { *bad = ok ? 0.0 : 1.0; *pushes = (ok && any) ? 1.0 : 0.0; }
+}
+
+// Row [I_w^-1 tau; f / m] of a step's external wrench (tau, f: six doubles) for its component comp, I_w^-1 = Rz(psi) diag(iinv) Rz(psi)' from the step's
+// cs = cos(psi), sn = sin(psi) (the entries the table J is formed from)
+__device__ __forceinline__ double ext_wrench_accel(const double* wr, const int comp, const double cs, const double sn, const double i0, const double i1, const double i2, const double inv_mass) {
+    const double w00 = cs * cs * i0 + sn * sn * i1, w01 = cs * sn * (i0 - i1), w11 = sn * sn * i0 + cs * cs * i1;
+    return comp == 0 ? w00 * wr[0] + w01 * wr[1] : (comp == 1 ? w01 * wr[0] + w11 * wr[1] : (comp == 2 ? i2 * wr[2] : inv_mass * wr[comp]));
+}
+
 // The frame R = [t1 t2 n] of one contact normal (MODE = 4, srbdqp_set_contact_normals; g1_locomotion_amd.contact_frames is the host mirror):
 //     n = nr / |nr|,   t1 = (e_x - n_x n) / |e_x - n_x n|,   t2 = n x t1        (R = I exactly for nr = e_z)
 // into the step's table L, L[12 r + a] = R[r][a] for the contact's columns a = 0 .. 2.  The setters' rules -- every entry finite, 0.5 <= |nr| <= 2, n_z >= 0.5
@@ -731,10 +768,16 @@ __device__ __forceinline__ void contact_frame_to_lds(const double (&nr)[3], doub
 // (apply_kinv, RA).  Nothing inverts E.  Steps above that ratio are what they are in MODE 0, and every such place below reads (RA ? ... : ...) or if constexpr (RA);
 // 6 = solve with the QP's own cost weights weights[16 b .. 16 b + 16) (srbdqp_set_weights, qp_weights_to_lds): sqrt(q_diag) where a.sqrtq goes, r_diag s^2 in an
 // LDS slot that the three uses of a.rs2 read (WT ? RBV[8] : a.rs2).  The robot comes from the LDS slots as in MODE 2 -- the QP's record where `robots` is set,
-// the KArgs values otherwise (args_robot_to_lds) -- so records and weights combine in one instantiation.
+// the KArgs values otherwise (args_robot_to_lds) -- so records and weights combine in one instantiation;
+// 7 = solve with the QP's external wrench ext[6 row0 .. 6 row0 + 6 N) (srbdqp_set_external_wrench: a world-frame torque and force on the body per horizon step,
+// DESIGN.md section 16), built on MODE 6: robot and weights from the LDS slots, the QP's records where `robots` / `weights` are set and the KArgs values
+// otherwise (args_robot_to_lds, args_weights_to_lds).  The dynamics gain the affine term e_k = dt [0; 0; I_w^-1 tau_k; f_k / m; 0].  P, A, l, u are the same;
+// the state response D to the e_k alone (D_0 = 0, D_k+1 = A_k D_k + e_k) is subtracted from the LDS copy of x_ref behind that copy's other readers (the yaw's
+// sincos, the default pcom), so the error vector, the gradient and everything behind them are MODE 6's; the roll-out adds the step's row to its per-step sums.
+// Every such place reads if constexpr (EW).
 template <int N, typename R, typename TIO, int MODE, typename TT = double, int SPW = 5, int XW = 0>
 __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* sm, const double* robots = nullptr, const int nl = N, const double* normals = nullptr,
-                                          const double* weights = nullptr) {
+                                          const double* weights = nullptr, const double* ext = nullptr) {
     using S = WrenchSmem<N, (int)sizeof(TT), SPW, XW, wrench_kreg64(N, MODE), MODE == 4>;
     typedef TT v4t __attribute__((ext_vector_type(4)));
     static_assert(sizeof(TT) == 8 || (sizeof(R) == 4 && MODE == 0), "fp32 tiles belong to the fp32 path");
@@ -744,13 +787,14 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     static_assert(S::NT <= 2 * NW || S::WQ >= 1, "");
     static_assert((S::o_zt % 2) == 0, "16-byte alignment of the 6-vectors");
     const double rho_b = unis(SRBDQP_RHO_OF(a, b));   // (per-QP values are wave-uniform: scalar registers, see uni())
-    constexpr bool WT = MODE == 6;
-    constexpr bool RB = MODE == 2 || WT;                             // (MODE 6 reads the robot from LDS too)
+    constexpr bool EW = MODE == 7;
+    constexpr bool WT = MODE == 6 || EW;                             // (MODE 7 reads the weights from LDS too)
+    constexpr bool RB = MODE == 2 || WT;                             // (MODE 6 and 7 read the robot from LDS too)
     constexpr bool LH = MODE == 3;
     static_assert(!LH || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && (XW == 0 || N == 24)), "live horizons: the fp64 batch instantiation");
     const int NL = LH ? nl : N;                                      // the live horizon (wave-uniform: a kernel argument)
     static_assert(!RB || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && XW == 0), "per-QP robot records: the fp64 batch instantiation");
-    [[maybe_unused]] const double* const RBV = sm + S::o_end;        // MODE 2: the QP's robot (qp_robot_to_lds), from the first barrier on (MODE 6: [8] r_diag s^2, [9] bad weights)
+    [[maybe_unused]] const double* const RBV = sm + S::o_end;        // MODE 2: the QP's robot (qp_robot_to_lds), from the first barrier on (MODE 6: [8] r_diag s^2, [9] bad weights; MODE 7: [10] bad wrench)
     constexpr bool CN = MODE == 4;
     static_assert(!CN || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && XW == 0), "contact normals: the fp64 batch instantiation");
     [[maybe_unused]] const double* const LT_ = sm + S::o_L;          // MODE 4: L of every step, from the second barrier on
@@ -794,13 +838,29 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             const double* gn = normals + (size_t)b * (N * 12) + 3 * (t < N * 4 ? t : 0);
             v_nr[0] = gn[0]; v_nr[1] = gn[1]; v_nr[2] = gn[2];
         }
+        constexpr int RW = (6 * N + 63) / 64;
+        [[maybe_unused]] double v_ew[RW];                            // EW: the QP's wrench on wave 0
+        if constexpr (EW) {
+            if (w == 0) {
+                const double* ge = ext + row0 * 6;
+#pragma unroll
+                for (int r = 0; r < RW; ++r) { const int i = lane + 64 * r; v_ew[r] = ge[i < 6 * N ? i : 0]; }
+            }
+        }
 #pragma unroll
         for (int r = 0; r < RX; ++r) { const int i = t + r * BT; v_xr[r] = gxr[i < NL * 13 ? i : 0]; }
 #pragma unroll
         for (int r = 0; r < RF; ++r) { const int i = t + r * BT; v_ft[r] = gft[i < NL * 12 ? i : 0]; }
         if (t < 13) sm[S::o_x0 + t] = (double)v_x0;
         if constexpr (!WT) { if (t >= 32 && t < 44) sm[S::o_sq + t - 32] = a.sqrtq[t - 32]; }
-        else { if (w == 0) qp_weights_to_lds(a, weights + (size_t)b * 16, lane, sm + S::o_sq, sm + S::o_end + 8); }
+        else if constexpr (!EW) { if (w == 0) qp_weights_to_lds(a, weights + (size_t)b * 16, lane, sm + S::o_sq, sm + S::o_end + 8); }
+        else {
+            if (w == 0) {
+                if (weights) qp_weights_to_lds(a, weights + (size_t)b * 16, lane, sm + S::o_sq, sm + S::o_end + 8);
+                else args_weights_to_lds(a, lane, sm + S::o_sq, sm + S::o_end + 8);
+                qp_ext_wrench_to_lds<N>(v_ew, lane, sm + S::o_eh, sm + S::o_end + 10, sm + S::o_misc + 2);   // (o_eh: free until the error vector is formed)
+            }
+        }
 #pragma unroll
         for (int r = 0; r < RX; ++r) { const int i = t + r * BT; if (i < N * 13) sm[S::o_xref + i] = (LH && i >= NL * 13) ? 0.0 : (double)v_xr[r]; }   // (live horizon: the rows behind it are zero -- finite tables, no contacts)
 #pragma unroll
@@ -869,7 +929,44 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             J[1 * 12 + cc] = w01 * s0 + w11 * s1;
             J[2 * 12 + cc] = i2 * s2;
         }
+        if constexpr (EW) {   // e_k = dt [I_w^-1 tau_k; f_k / m], behind the raw values
+            static_assert(6 * N <= BT, "one thread per entry of the wrench");
+            if (t < 6 * N) {
+                const int k = t / 6, comp = t - 6 * k;
+                sm[S::o_eh + 6 * N + t] = a.dt * ext_wrench_accel(sm + S::o_eh + 6 * k, comp, sm[S::o_tm + k * 9], sm[S::o_tm + k * 9 + 1], RBV[1], RBV[2], RBV[3], RBV[0]);
+            }
+        }
         __syncthreads();
+        if constexpr (EW) {
+            // D, the state response to the e_k alone, as the roll-out's prefix stages: the velocities of the states 1 .. N (over the raw values, dead by now), then
+            // the Euler angles through Tm and the positions.  Row k of x_ref stands against state k + 1: x_ref[k] -= D_k+1, an entry or two per thread.  (No one
+            // reads the copy of x_ref from here on but the error vector: a restart pass is a launch of its own and starts from the caller's array.)
+            double* E = sm + S::o_eh + 6 * N;
+            double* WD = sm + S::o_eh;
+            if (t < 6 * N) {
+                const int k = t / 6, comp = t - 6 * k;
+                double acc = 0.0;
+                for (int j = 0; j <= k; ++j) acc += E[6 * j + comp];
+                WD[t] = acc;
+            }
+            __syncthreads();
+            if (t < 6 * N) {
+                const int k = t / 6, comp = t - 6 * k;
+                double acc = 0.0;
+                if (comp < 3) {
+                    for (int l = 1; l <= k; ++l) {
+                        const double* Tm = sm + S::o_tm + l * 9 + comp * 3;
+                        const double* wv = WD + 6 * (l - 1);
+                        acc += Tm[0] * wv[0] + Tm[1] * wv[1] + Tm[2] * wv[2];
+                    }
+                } else {
+                    for (int l = 1; l <= k; ++l) acc += WD[6 * (l - 1) + comp];
+                }
+                sm[S::o_xref + k * 13 + comp] -= a.dt * acc;
+                sm[S::o_xref + k * 13 + 6 + comp] -= WD[t];
+            }
+            __syncthreads();
+        }
     }
     const int n_g = __builtin_amdgcn_readfirstlane(imisc[0]);
     const int na = __builtin_amdgcn_readfirstlane(imisc[1]);
@@ -900,6 +997,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     [[maybe_unused]] bool rb_bad = false;
     if constexpr (RB) rb_bad = unis(RBV[7]) != 0.0;
     if constexpr (WT) rb_bad = rb_bad || unis(RBV[9]) != 0.0;       // (MODE 6: weights that are none, the same way)
+    if constexpr (EW) rb_bad = rb_bad || unis(RBV[10]) != 0.0;      // (MODE 7: a wrench that is none, the same way)
     if constexpr (CN) rb_bad = unis(sm[S::o_misc + 1]) != 0.0;      // (MODE 4: a normal that is not one, the same way)
     if (na == 0 || ((RB || CN) && rb_bad)) {   // nothing to solve: all forces 0 (MODE 2, a record that is not a robot: the same, reported as SRBDQP_NUMERICAL)
         for (int c = t; c < n; c += BT) sm[S::o_xs + c] = 0.0;
@@ -1997,6 +2095,44 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                 xq = active_u ? xq + dxq : 0.0;
                 __syncthreads();
             }
+            if constexpr (EW) {
+                // MODE 7: the same refinement step on fp64 tiles.  It is applied to a QP that is pushed: a wrench of zeros leaves the twin's q, and with the
+                // correction dropped the twin's bits (every QP runs the step -- a branch around it cost the N = 10 and N = 20 instantiations a spill).  A drawn torque makes |q| 1e6 - 1e7 in the scaled variables (1e4 without a wrench), and x_q
+                // carries cond(T) ulps of it through every iteration: 1e-5 - 1e-4 N in the forces, and ten times that in the yaw of the roll-out.  One
+                // step with the fp64 residual leaves the rounding of q itself.  The tiles are dead, so the tables of G'(G x) have
+                // their phase-A places again; of the ADMM vectors only the half rows' tails (N = 12) are live, and those under the tables are written again.
+                if (t < 9) {
+                    double accp = 0.0;
+                    for (int k = 0; k < N; ++k) { accp += sm[S::o_tm + k * 9 + t]; sm[S::o_cp + k * 9 + t] = accp; }
+                }
+                if (stepok) sm[S::o_x0c + uvar] = xq;
+                __syncthreads();
+                const double gtg = gtg_of_x0c();
+                // (K's diagonal part formed again from the slots, behind the barriers: held from dxy / dz above it cost a register pair across K^-1)
+                const double mu_l = RB ? RBV[4] : a.mu;
+                const double dl = RBV[8] + a.sigma + ((ax < 2) ? 2.0 : fma(4.0 * mu_l, mu_l, a.rho_fz)) * rho_b;
+                const double rres = active_u ? fma(dl, xq, gtg + qv) : 0.0;
+                __syncthreads();   // (the tables' last readers, in front of the v buffers that overlay them)
+                for (int i = t; i < 2 * S::VB; i += LT) vb[i] = 0.0;
+                // x_q and the gradient wait in the roll-out's vectors, free until the iterations end (own entries: the registers of the first application of
+                // K^-1 are all the instantiations have), and the tails that lay under the tables are written again from the registers they came from
+                double* park = sm + S::o_xs + (stepok ? uvar : 0);
+                if (stepok) { park[0] = xq; park[n] = qv; }
+                static_assert(S::o_scr == S::o_xs + n && S::o_eh + n <= S::o_kt && S::o_cp >= S::o_R && S::o_gv >= S::o_kt, "MODE 7: what the refinement's tables overlay");
+                if constexpr (KREG < CHMAX) {
+                    constexpr int E0 = (S::o_gv - S::o_kt) / LT, E1 = (S::o_tf + 6 * N - 1 - S::o_kt) / LT;
+                    R* kt = reinterpret_cast<R*>(sm + S::o_kt) + t;
+#pragma unroll
+                    for (int e = E0; e <= E1; ++e) if (e < CHMAX - KREG) kt[e * LT] = (R)kin64[KREG + e];
+                }
+                __syncthreads();
+                double dxq;
+                if constexpr (KREG < CHMAX) dxq = apply_kinv<double, CHMAX, KREG>(-rres, wbw, tbw, vb, lane, sg, ul, active_g, Rrow, CH, kin64, vrd, vcd, bjv, vsoff, vssel, [] {}, ktail, LT);
+                else dxq = apply_kinv<double, CHMAX>(-rres, wbw, tbw, vb, lane, sg, ul, active_g, Rrow, CH, kin64, vrd, vcd, bjv, vsoff, vssel, [] {});
+                __syncthreads();
+                xq = active_u ? park[0] + (sm[S::o_misc + 2] != 0.0 ? dxq : 0.0) : 0.0;
+                qv = active_u ? park[n] : 0.0;
+            }
             if constexpr (WARM_LATE) {
                 if (a.warm_u) {
                     if constexpr (sizeof(R) == 4) {   // x_q is only used in the iteration type from here on: one register instead of two across the tables
@@ -2274,6 +2410,14 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     const int ax2 = comp - 3;
                     s = (u[ax2] + u[3 + ax2] + u[6 + ax2] + u[9 + ax2]) * (RB ? RBV[0] : a.inv_mass);
                 }
+                if constexpr (EW) {   // the step's [I_w^-1 tau; f / m] from the caller's array again (sj is in scaled newtons); none for a QP whose wrench or records are none
+                    // (`pushed` is one value per QP, three broadcast reads of the slots.  A QP with a bad wrench forms e from the caller's raw values, NaN perhaps,
+                    //  and the select drops it: IEEE semantics, which the library is built with -- no -ffast-math, under which a select on NaN is no barrier)
+                    const bool pushed = RBV[7] == 0.0 && RBV[9] == 0.0 && RBV[10] == 0.0;
+                    const double* ge = ext + (row0 + (size_t)j) * 6;
+                    const double e = ext_wrench_accel(ge, comp, sm[S::o_tm + j * 9], sm[S::o_tm + j * 9 + 1], RBV[1], RBV[2], RBV[3], RBV[0]);
+                    s += pushed ? e / a.s : 0.0;
+                }
                 sj[idx] = s;
             }
             __syncthreads();
@@ -2422,6 +2566,19 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, 5, 0>::BT), WPS) void srbdqp_wren
     if (!wrench_block_in_launch<N>(a)) return;
     if (wrench_block_has_work(a))
         wrench_qp<N, double, double, 6, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm, robots, N, nullptr, weights);
+    signal_done(a);
+}
+
+// ... MODE = 7: every QP with its own external wrench (srbdqp_set_external_wrench / _device): ext = the handle's array, 6 doubles per horizon row in the CALLER's
+// row order (6 N per QP of a batch, the caller's row_off on a ragged object), weights and robots = the handle's records or null (the KArgs values for every QP),
+// as further kernel arguments for the same reasons.  fp64, batch form only.
+template <int N, int WPS>
+__global__ __launch_bounds__((WrenchSmem<N, 8, 5, 0>::BT), WPS) void srbdqp_wrench_ew_kernel(KArgs a, const double* __restrict__ ext, const double* __restrict__ weights,
+                                                                                             const double* __restrict__ robots) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    if (!wrench_block_in_launch<N>(a)) return;
+    if (wrench_block_has_work(a))
+        wrench_qp<N, double, double, 7, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm, robots, N, nullptr, weights, ext);
     signal_done(a);
 }
 

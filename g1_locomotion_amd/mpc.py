@@ -73,6 +73,10 @@ def _normals_arg(normals, N):
     return _side_arg("set_contact_normals", normals, ((N, NU), (N, NC, 3)))
 
 
+def _ext_wrench_arg(w, trailing):
+    return _side_arg("set_external_wrench", w, (trailing,))
+
+
 def _set_side(eng, fn, attr, arg):
     """The body of every set_* method of BatchMPC and RaggedMPC: the host or the device form of the C-ABI setter `fn`, and in eng.<attr> what was set (None once
     cleared) -- a device tensor stays referenced while the library reads it.  One rule for the three kinds, the one solve(normals=) needs to restore a
@@ -268,6 +272,14 @@ class BatchMPC:
         contact_frames(normal); forces, states and duals keep their frames and units; the fp64 solves run on the general kernel (wrench_f64_n<N>_cn), and
         the fp32, staged and assembly calls raise SrbdqpError."""
         _set_side(self, "srbdqp_set_contact_normals", "_normals_set", _normals_arg(normals, self.N))   # (_normals_set: what solve(normals=) restores)
+
+    def set_external_wrench(self, w):
+        """A known wrench on the body per horizon step (include/srbdqp.h srbdqp_set_external_wrench): w (L, N, 6), [b, k, 0:3] a world-frame torque about
+        the CoM in N m and [b, k, 3:6] a world-frame force in N acting on QP b during step k -- a NumPy array (checked and copied by the library), a CUDA
+        float64 torch tensor (kept and read at every solve: leave it untouched until those solves have completed), or None (no wrench again).  While set,
+        the fp64 solves run on the general kernel (wrench_f64_n<N>_ew), with or without set_robots() records and set_weights() weights, and the fp32,
+        staged and assembly calls raise SrbdqpError."""
+        _set_side(self, "srbdqp_set_external_wrench", "_ext_wrench", _ext_wrench_arg(w, (self.N, 6)))
 
     def flush(self, stream=0):
         """FLAG_DEFER_TAIL: enqueue the continuations no later solve has picked up (srbdqp_flush); stream = a hipStream_t address, 0 = every
@@ -483,6 +495,11 @@ class RaggedMPC:
         """One pair of cost weights per QP, in the CALLER's QP order (srbdqp_ragged_set_weights): as BatchMPC.set_weights."""
         _set_side(self, "srbdqp_ragged_set_weights", "_weights", _weights_arg(weights))
 
+    def set_external_wrench(self, w):
+        """A known wrench per horizon row, (rows, 6), packed step-major like x_ref in the CALLER's QP order (srbdqp_ragged_set_external_wrench): as
+        BatchMPC.set_external_wrench."""
+        _set_side(self, "srbdqp_ragged_set_external_wrench", "_ext_wrench", _ext_wrench_arg(w, (6,)))
+
     def flush(self, stream=0):
         """flags=FLAG_DEFER_TAIL: make `stream` (0 = the object's own) wait for the restart passes still running on the buckets' tail streams
         (srbdqp_ragged_flush).  Does not synchronise.  The input and output arrays of the earlier solve_device() calls must stay untouched until the
@@ -686,18 +703,23 @@ class MPC:
         return self._u_opt[0].reshape(NU, 1).copy(), (self._x_opt.copy() if one_rollout else self._x_opt[:2].copy())
 
     def update(self, contact_horizon: Sequence, c_horizon: Sequence, p_com_horizon, x_current=None,
-               one_rollout: bool = True, contact_normals=None):
+               one_rollout: bool = True, contact_normals=None, external_wrench=None):
         """run_simulation.py:106.  Returns (u_opt0 (12,1), x_opt1) where x_opt1[1] is the next state.
         one_rollout=True -> x_opt1 has the whole roll-out (N+1, 13); False -> only rows 0..1.
         contact_normals: (N, 12) / (N, 4, 3) array or a per-step list of world-frame surface normals (BatchMPC.set_contact_normals): the friction pyramids
         of sloped ground.  Such a call goes through the host-batch solve with B = 1 (the staged batch-1 path keeps its layout and has no normals).
+        external_wrench: (N, 6) world-frame [torque, force] on the body per horizon step (BatchMPC.set_external_wrench), for this call alone; it goes the
+        same way, through the host setter (set before the solve, cleared after it: two waits for the handle's streams per call).  Both together raise
+        ValueError: no instantiation reads both.
 
         One C call (srbdqp_update_f64) with every argument bound once: the inputs go straight into the library's pinned staging arrays,
         the results are copied out of them once.  What Python adds to the C call is what NumPy needs to gather the reference's per-step
         lists (two np.concatenate of N small arrays: ~2.4 us of ~4.5 us in total); (N, 12) / (N, 4) arrays instead of lists cost
         ~2 us less."""
-        if contact_normals is not None:
-            return self._update_normals(contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals)
+        if contact_normals is not None and external_wrench is not None:
+            raise ValueError("update: contact_normals and external_wrench together are not supported (no instantiation of the general kernel reads both)")
+        if contact_normals is not None or external_wrench is not None:
+            return self._update_via_batch(contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals, external_wrench)
         upd = self._upd
         if upd is None:
             upd = self._bind()
@@ -752,16 +774,26 @@ class MPC:
         x_opt1 = x.copy() if one_rollout else x[:2].copy()
         return u_opt0, x_opt1
 
-    def _update_normals(self, contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals):
+    def _update_via_batch(self, contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals=None, external_wrench=None):
+        """update() with contact normals or an external wrench (at most one of them): the host-batch solve with B = 1.  The wrench is set through the host
+        setter before the solve and cleared after it, and each of the two calls waits for every stream of the handle first: fine for one QP per control
+        step, and a fleet sets its wrenches once per solve on a BatchMPC instead."""
         if self._engine is None:
             self.init_matrices()
         eng, N = self._engine, self.HORIZON_LENGTH
         self._last_fast = self._last_fc = False
         x_cur = np.asarray(self.x0 if x_current is None else x_current, dtype=np.float64).reshape(1, NX)
         pc = None if p_com_horizon is None else np.asarray(p_com_horizon, dtype=np.float64).reshape(1, N, 3)
+        nr = None if contact_normals is None else np.asarray(contact_normals, dtype=np.float64).reshape(1, N, NU)
         t0 = time.perf_counter()
-        out = eng.solve(x_cur, np.asarray(self.x_ref_hor, dtype=np.float64).reshape(1, N, NX), np.asarray(c_horizon, dtype=np.float64).reshape(1, N, NU),
-                        np.asarray(contact_horizon).reshape(1, N, NC), pcom=pc, normals=np.asarray(contact_normals, dtype=np.float64).reshape(1, N, NU))
+        if external_wrench is not None:            # for this call alone: cleared again below, whatever the solve does
+            eng.set_external_wrench(np.asarray(external_wrench, dtype=np.float64).reshape(1, N, 6))
+        try:
+            out = eng.solve(x_cur, np.asarray(self.x_ref_hor, dtype=np.float64).reshape(1, N, NX), np.asarray(c_horizon, dtype=np.float64).reshape(1, N, NU),
+                            np.asarray(contact_horizon).reshape(1, N, NC), pcom=pc, normals=nr)
+        finally:
+            if external_wrench is not None:
+                eng.set_external_wrench(None)
         self._solve_time = time.perf_counter() - t0
         self._status, self._iters = int(out["status"][0]), int(out["iters"][0])
         if self._status != _lib.SOLVED:

@@ -291,6 +291,15 @@ typedef struct srbdqp_weights {
 } srbdqp_weights;              /* every value finite: below SRBDQP_WEIGHT_MAX, the one bound the host setters and the kernel both test */
 #define SRBDQP_WEIGHT_MAX 1.0e300
 
+/* External wrench: a KNOWN wrench on the body besides the contact forces and gravity -- a push estimated by a momentum observer, a carried payload, the
+ * inertial wrench of a heavy swing leg, the random pushes of a perturbed fleet.  Six doubles per horizon step k = 0 .. N-1 of a QP, torque first like the
+ * kernel's wrench coordinates: [0..3) a world-frame torque tau_k about the CoM in N m, [3..6) a world-frame force f_k in N, both acting during step k:
+ *     omega' = I_w^-1 (sum r_i x f_i + tau_k),   v' = (sum f_i + f_k) / m + g e_z,   I_w = R_z(psi_k) I_b R_z(psi_k)',   psi_k = x_ref[k][2]
+ * Forward Euler as everywhere: x_{k+1} = A_k x_k + B_k u_k + e_k with e_k = dt [0; 0; I_w,k^-1 tau_k; f_k / m; 0].  The QP's P, A, l, u do not change; its
+ * gradient and the roll-out x_out gain the state response to the e_k.  f_k / m uses the QP's own mass and I_w its own inertia where robot records are set.
+ * Every value finite with |value| <= SRBDQP_EXT_WRENCH_MAX, the one bound the host setters and the kernel both test. */
+#define SRBDQP_EXT_WRENCH_MAX 1.0e6
+
 /* Ragged batches (BASELINE.json configs[4]: "Mixed horizon N in {8,12,16,24} with per-QP contact schedule (ragged batch,
  * bucketed kernel launch)").  One object holds an engine per horizon; a call takes the QPs in ANY order with their horizon
  * in N_per_qp[] (HOST array), sorts them into horizon buckets and launches every non-empty bucket on its own HIP stream --
@@ -352,6 +361,14 @@ int srbdqp_ragged_set_robots_device(srbdqp_ragged* r, const srbdqp_robot* dev, i
  * order, independent lengths, clearing one leaves the other. */
 int srbdqp_ragged_set_weights(srbdqp_ragged* r, const srbdqp_weights* host, int32_t length);
 int srbdqp_ragged_set_weights_device(srbdqp_ragged* r, const srbdqp_weights* dev, int32_t length);
+/* An external wrench on a ragged object (srbdqp_set_external_wrench below: the same model, checks and refusals).  host / dev = [rows][6] doubles, packed
+ * step-major like x_ref: the QP's N rows start at the row offset of the CALLER's order (the sum of N_per_qp in front of it) -- not the bucket order -- and
+ * every bucket engine reads the same array.  An object with an N = 24 bucket or a live bucket is refused.  The host form names the first bad (row, component),
+ * copies once into a buffer of the object and waits for every bucket stream and tail stream before it replaces an earlier array.  While a wrench is set the
+ * fp64 ragged calls read it; a call whose horizons sum to more than `rows` and the _f32 ragged calls return SRBDQP_E_INVALID and launch nothing.  It combines
+ * with robot records and weights: any order, independent lengths, clearing one leaves the others. */
+int srbdqp_ragged_set_external_wrench(srbdqp_ragged* r, const double* host, int32_t rows);
+int srbdqp_ragged_set_external_wrench_device(srbdqp_ragged* r, const double* dev, int32_t rows);
 
 /* Longest-first scheduling hint for the DEVICE-buffer API only (the host-buffer and the staged calls ignore it):
  * `device_iters_prev` = the iters[] array (device memory, `length` entries) of the previous control step of the same
@@ -408,6 +425,36 @@ int srbdqp_set_robots_device(srbdqp_handle* h, const srbdqp_robot* dev, int32_t 
  * weights every call behaves as it always has. */
 int srbdqp_set_weights(srbdqp_handle* h, const srbdqp_weights* host, int32_t length);
 int srbdqp_set_weights_device(srbdqp_handle* h, const srbdqp_weights* dev, int32_t length);
+
+/* External wrench per horizon step (the model: SRBDQP_EXT_WRENCH_MAX above).  srbdqp_set_external_wrench: HOST array [length][N][6] doubles, copied into a
+ * device buffer the library owns.  Every value is checked first: on a bad one the call returns SRBDQP_E_INVALID, srbdqp_last_error names the first bad
+ * (qp, step, component), and the previous setting stays.  Before it replaces an earlier array it makes the waits srbdqp_set_robots makes.
+ * srbdqp_set_external_wrench_device: a DEVICE array the caller owns; the pointer is kept and read at every solve, so the array must stay untouched until the
+ * solves that read it have completed in stream order (under SRBDQP_FLAG_DEFER_TAIL: until the flush).  The kernel checks each QP's block: a QP with a value
+ * that breaks the rule ends with SRBDQP_NUMERICAL, zero forces and the roll-out of no wrench; the other QPs of the batch are not affected.
+ * host / dev NULL or length 0: back to no wrench.
+ * A QP whose block is all zeros is solved to the bits of a solve without a wrench on the same kernel.  A QP with any value that is not zero gets one step of
+ * iterative refinement on the gradient's part of the solution (a push makes the gradient 100 - 1000 times larger), so its forces move
+ * by the solver's rounding, 1e-8 - 1e-7 N, when a value goes from 0 to the smallest number: zero is special in that sense, and in no other.
+ *
+ * While a wrench is set:
+ *   - QP b of a solve reads block b -- b the CALLER's index: the same under the schedule hint's dispatch order, in every restart or deferred pass;
+ *   - a solve of B > length QPs returns SRBDQP_E_INVALID and launches nothing;
+ *   - srbdqp_solve_batch_f64 / _device_f64 run on the general kernel's external-wrench instantiation (srbdqp_kernel_name: wrench_f64_n<N>_ew; AUTO and
+ *     SRBDQP_KERNEL_WRENCH route there, an explicit SRBDQP_KERNEL_COMPACT / _SPLIT / _WAVE returns SRBDQP_E_INVALID with a message);
+ *   - a QP without any stance contact, and one whose step the conditioning guard refuses, get zero forces and the roll-out under the wrench: a body in flight
+ *     is pushed too;
+ *   - these return SRBDQP_E_INVALID with a message that names the setter: the _f32 calls, the staged batch-1 calls (srbdqp_solve_staged_f64,
+ *     srbdqp_prepare_staged_f64 / srbdqp_solve_prepared_f64, srbdqp_update_f64) and srbdqp_assemble_f64 / _wrench_f64.
+ * The wrench combines with robot records and weights: any of the three may be set on one handle, in any order, with independent lengths (a solve needs B no
+ * larger than each), and clearing one leaves the others in force; the same instantiation reads all three.  A handle that also has records or weights answers
+ * every refused call with their text.  The setters refuse (SRBDQP_E_INVALID) an N = 24 handle, a handle whose horizon was admitted by
+ * SRBDQP_FLAG_ANY_HORIZON, a handle created with SRBDQP_FLAG_RANK_AWARE and a handle that has contact normals set; srbdqp_set_contact_normals / _device
+ * refuse normals while a wrench is set.  Without a wrench every call behaves as it always has.
+ * srbdqp_wbid_reference_* and srbdqp_mpc_inputs_* (srbdqp_cascade.h) know no wrench and stay as they are: a caller that feeds a whole-body controller adds
+ * f_0 / m to com_acc itself. */
+int srbdqp_set_external_wrench(srbdqp_handle* h, const double* host, int32_t length);
+int srbdqp_set_external_wrench_device(srbdqp_handle* h, const double* dev, int32_t length);
 
 /* Contact normals: the friction pyramid of every contact point on sloped ground.  normals = [length][N][12] doubles: for QP b, step k, contact i the unit normal n of
  * the surface under the contact, in the WORLD frame, at [b][k][3 i .. 3 i + 3).  The contact frame is R = [t1 t2 n] with
