@@ -143,7 +143,7 @@ def zero_rollout(qp, x0):
 
 def check_contract(tag, u, x, y, status, iters, ref, ct, p, mode, x0, must_status=True, frames=None, world_qp=None):
     """The either-or contract on one QP; returns "answered" or "rejected".  frames, world_qp: a solve with contact normals -- ref["qp"] is the QP in the
-    contacts' own frames T = frames (normals_twin), u stays in the world frame."""
+    contacts' own frames T = frames (side_inputs.frames_matrix), u stays in the world frame."""
     bound = BOUND[mode]
     u64 = np.asarray(u, np.float64).reshape(-1)
     assert np.all(np.isfinite(u64)), (tag, "non-finite forces")

@@ -1,14 +1,15 @@
 """CPU-side tests of contact normals (include/srbdqp.h srbdqp_set_contact_normals): the host mirror of the frame convention (contact_frames), the oracle twin
-the GPU tests compare against (tests/normals_twin.py), and the library's exports.
+the GPU tests compare against (tests/side_inputs.py; with flat normals it is the oracle: tests/test_side_inputs_cpu.py), and the library's exports.
 
 No refusal of the two setters can be reached without a device -- every one of them needs a handle, and srbdqp_create returns SRBDQP_E_NO_DEVICE here (as the
 other CPU C-ABI tests find) -- except the null handle; tests/test_gpu_contact_normals.py covers them all."""
 import numpy as np
 import pytest
 
+import side_inputs as si
 import srbd_oracle as orc
-import normals_twin as nt
 from g1_locomotion_amd import contact_frames
+from test_side_inputs_cpu import NEUTRAL_CASES, check_neutral_twin
 
 
 def test_contact_frames_follow_the_convention():
@@ -28,17 +29,9 @@ def test_contact_frames_follow_the_convention():
         contact_frames(np.zeros((4, 2)))
 
 
-@pytest.mark.parametrize("N,schedule", [(4, "double"), (10, "mixed"), (20, "single")])
+@pytest.mark.parametrize("N,schedule", NEUTRAL_CASES)
 def test_the_twin_with_flat_normals_is_the_oracle_update(N, schedule):
-    B = 3
-    x0, xr, ft, ct = nt.batch(B, N, 4200 + N, schedule)
-    p = nt.params(N)
-    nr = nt.flat_normals(B, N)
-    for b in range(B):
-        ref = orc.update(p, x0[b], xr[b], ft[b], ct[b])
-        tw = nt.twin(p, x0[b], xr[b], ft[b], ct[b], nr[b])
-        assert tw["status"] == ref["status"] and tw["iters"] == ref["iters"]
-        assert np.array_equal(tw["u"], ref["u"]) and np.array_equal(tw["x"], ref["x"]) and np.array_equal(tw["y"], ref["y"])
+    check_neutral_twin("flat_normals", N, schedule)
 
 
 def test_the_twin_on_a_ridge_respects_the_tilted_pyramid():
@@ -46,17 +39,17 @@ def test_the_twin_on_a_ridge_respects_the_tilted_pyramid():
     the local QP (5e-2 N); a friction row of the tilted pyramid is active, and the flat-ground optimum of the same inputs leaves that pyramid by more than 0.5 N."""
     B, N = 4, 10
     x0, xr, ft, ct = orc.synthetic_batch(B, N, seed=5100 + N, schedule="double")
-    p = nt.params(N)
-    nr = nt.ridge_normals(B, N)
+    p = si.params(N)
+    nr = si.ridge_normals(B, N)
     for b in range(B):
-        tw = nt.twin(p, x0[b], xr[b], ft[b], ct[b], nr[b])
+        tw = si.twin(p, x0[b], xr[b], ft[b], ct[b], normals=nr[b])
         assert tw["status"] == orc.STATUS_SOLVED
-        assert nt.cone_violation(p, tw["qp"], tw["T"], tw["u"]) <= 1e-4
+        assert si.cone_violation(p, tw["qp"], tw["T"], tw["u"]) <= 1e-4
         xs, _ = orc.solve_reference(p, tw["qp_loc"])
         assert np.abs(tw["u_loc"] - xs).max() * p.force_scale <= 5e-2
-        assert nt.friction_row_active(p, tw["T"], tw["u"], ct[b])
+        assert si.friction_row_active(p, tw["T"], tw["u"], ct[b])
         flat = orc.update(p, x0[b], xr[b], ft[b], ct[b])
-        assert nt.cone_violation(p, tw["qp"], tw["T"], flat["u"]) * p.force_scale > 0.5, b
+        assert si.cone_violation(p, tw["qp"], tw["T"], flat["u"]) * p.force_scale > 0.5, b
 
 
 def test_library_exports_and_binds_both_setters(built_lib):

@@ -14,6 +14,7 @@ import pytest
 
 import srbd_oracle as orc
 from test_gpu_wrench import TOL_EXACT_N, TOL_TWIN_N, _batch
+from gpu_helpers import torch_first  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,13 +25,6 @@ SCHEDULES = ("single", "double", "mixed", "three")
 
 def nstar(n):
     return min(N for N in TABULATED if N >= n)
-
-
-@pytest.fixture(scope="module")
-def torch_first():
-    import torch  # load torch's HIP runtime before libsrbdqp.so so both share one
-    assert torch.cuda.is_available()
-    return torch
 
 
 @pytest.mark.parametrize("schedule", SCHEDULES)

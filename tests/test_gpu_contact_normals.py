@@ -1,57 +1,40 @@
-"""GPU tests of contact normals (include/srbdqp.h srbdqp_set_contact_normals / _device): friction pyramids on sloped ground, on the general kernel's MODE = 4
-instantiation (wrench_f64_n<N>_cn).
+"""GPU tests of what is particular to contact normals (include/srbdqp.h srbdqp_set_contact_normals / _device): friction pyramids on sloped ground, on the
+general kernel's MODE = 4 instantiation (wrench_f64_n<N>_cn).  What the normals share with the other per-QP side inputs -- parity per QP on drawn normals, flat
+normals, bad device values -- is in tests/test_gpu_side_inputs.py.
 
-The reference is the oracle twin of tests/normals_twin.py -- orc.build_qp's QP in the local force variables of every contact's frame, through the presolve and
-the restarted ADMM orc.update runs -- with the per-QP checks and tolerances of tests/test_gpu_robots.py::_check_qp applied to that local QP: same status,
-iterations within one check interval, forces <= 2e-3 N from the twin, roll-out <= 1e-5, solved QPs <= 5e-2 N from the exact optimum (orc.solve_reference; or
-within 2e-3 N of the twin's own distance from it where that is larger) with its KKT bars on T' u / s and y_out, swing forces and duals exactly 0."""
+The reference is the twin of tests/side_inputs.py -- orc.build_qp's QP in the local force variables of every contact's frame, through the presolve and the
+restarted ADMM orc.update runs -- with its per-QP bars (si.check_qp) applied to that local QP: the KKT bars on T' u / s and y_out."""
 import numpy as np
 import pytest
 
+import side_inputs as si
 import srbd_oracle as orc
-import normals_twin as nt
-from gpu_helpers import device_solve as _device_solve, to_dev as _to_dev
+from gpu_helpers import device_solve as _device_solve, to_dev as _to_dev, torch_first  # noqa: F401  (torch_first: the fixture)
+from test_gpu_side_inputs import NEUTRAL_CASES, check_neutral, check_parity
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def torch_first():
-    import torch  # load torch's HIP runtime before libsrbdqp.so so both share one
-    assert torch.cuda.is_available()
-    return torch
+@pytest.mark.parametrize("schedule", si.SCHEDULES)
+@pytest.mark.parametrize("N", si.HORIZONS)
+def test_tilted_pyramids_match_the_twin(torch_first, built_lib, N, schedule):
+    check_parity(si.NORMALS, N, schedule)
 
 
-def _case(B, N, schedule):
-    """The inputs of the parity test: one normal per foot, tilt uniform in [0, 0.35] rad, any azimuth -- constant over the horizon for single / double support,
-    redrawn at every step for the mixed and three-contact gaits."""
-    x0, xr, ft, ct = nt.batch(B, N, 4200 + N, schedule)
-    nr = nt.drawn_normals(B, N, np.random.default_rng(77 + N), per_step=schedule in ("mixed", "three"))
-    return x0, xr, ft, ct, nr
+@pytest.mark.parametrize("N,schedule", NEUTRAL_CASES)
+def test_flat_normals_change_nothing(torch_first, built_lib, N, schedule):
+    """Every normal e_z against a KERNEL_WRENCH solve without normals: 1e-6 and one check interval (the general 3 x 3 inverse of G rounds differently from
+    the flat kernel's reciprocals: ~1e-8 N expected)."""
+    check_neutral(si.NORMALS, N, schedule)
 
 
 def _parity(out, N, x0, xr, ft, ct, nr):
     """check_qp for every QP of the batch against its twin; returns the twins."""
-    p = nt.params(N)
-    refs = [nt.twin(p, x0[b], xr[b], ft[b], ct[b], nr[b]) for b in range(len(x0))]
+    p = si.params(N)
+    refs = [si.twin(p, x0[b], xr[b], ft[b], ct[b], normals=nr[b]) for b in range(len(x0))]
     for b, ref in enumerate(refs):
-        nt.check_qp(out, b, N, p, ref, ct[b])
+        si.check_qp(out, b, N, p, ref, ct[b])
     return p, refs
-
-
-@pytest.mark.parametrize("schedule", nt.SCHEDULES)
-@pytest.mark.parametrize("N", nt.HORIZONS)
-def test_tilted_pyramids_match_the_twin(torch_first, built_lib, N, schedule):
-    from g1_locomotion_amd import BatchMPC
-    B = 16
-    x0, xr, ft, ct, nr = _case(B, N, schedule)
-    with BatchMPC(horizon=N) as eng:
-        eng.set_contact_normals(nr)
-        out = eng.solve(x0, xr, ft, ct, want_y=True)
-        assert eng.kernel_name() == f"wrench_f64_n{N}_cn", eng.kernel_name()
-    _, refs = _parity(out, N, x0, xr, ft, ct, nr)
-    solved = sum(r["status"] == orc.STATUS_SOLVED for r in refs)
-    assert solved >= (3 * B) // 4, f"only {solved} of {B} QPs are solved in the twin"
 
 
 def test_the_normals_move_the_solutions(torch_first, built_lib):
@@ -60,8 +43,8 @@ def test_the_normals_move_the_solutions(torch_first, built_lib):
     B, moved, total = 16, 0, 0
     for N in (10, 12, 16, 20):
         with BatchMPC(horizon=N) as eng:
-            for schedule in nt.SCHEDULES:
-                x0, xr, ft, ct, nr = _case(B, N, schedule)
+            for schedule in si.SCHEDULES:
+                x0, xr, ft, ct, nr = si.NORMALS.case(B, N, schedule)
                 flat = eng.solve(x0, xr, ft, ct)
                 out = eng.solve(x0, xr, ft, ct, normals=nr)
                 assert eng.kernel_name() == f"wrench_f64_n{N}_cn"
@@ -78,7 +61,7 @@ def test_the_cone_reaches_the_kernel_on_a_ridge(torch_first, built_lib, N):
     from g1_locomotion_amd import BatchMPC
     B = 16
     x0, xr, ft, ct = orc.synthetic_batch(B, N, seed=5100 + N, schedule="double")
-    nr = nt.ridge_normals(B, N)
+    nr = si.ridge_normals(B, N)
     with BatchMPC(horizon=N) as eng:
         out = eng.solve(x0, xr, ft, ct, want_y=True, normals=nr)
         assert eng.kernel_name() == f"wrench_f64_n{N}_cn"
@@ -86,9 +69,9 @@ def test_the_cone_reaches_the_kernel_on_a_ridge(torch_first, built_lib, N):
     assert all(r["status"] == orc.STATUS_SOLVED for r in refs)
     active = 0
     for b, ref in enumerate(refs):
-        viol = nt.cone_violation(p, ref["qp"], ref["T"], out["u"][b])
+        viol = si.cone_violation(p, ref["qp"], ref["T"], out["u"][b])
         assert viol <= 1e-4, (b, viol)
-        active += int(nt.friction_row_active(p, ref["T"], out["u"][b], ct[b]))
+        active += int(si.friction_row_active(p, ref["T"], out["u"][b], ct[b]))
     assert active >= 12, active
 
 
@@ -98,39 +81,11 @@ def test_wedge_parity(torch_first, built_lib, schedule):
     from g1_locomotion_amd import BatchMPC
     B, N = 16, 10
     x0, xr, ft, ct = orc.synthetic_batch(B, N, seed=5100 + N, schedule=schedule)
-    nr = nt.wedge_normals(B, N)
+    nr = si.wedge_normals(B, N)
     with BatchMPC(horizon=N) as eng:
         out = eng.solve(x0, xr, ft, ct, want_y=True, normals=nr)
     _, refs = _parity(out, N, x0, xr, ft, ct, nr)
     assert all(r["status"] == orc.STATUS_SOLVED for r in refs)
-
-
-@pytest.mark.parametrize("N,schedule", [(4, "double"), (10, "mixed"), (10, "single"), (16, "double"), (20, "three")])
-def test_flat_normals_change_nothing(torch_first, built_lib, N, schedule):
-    """Every normal e_z against a KERNEL_WRENCH solve without normals: statuses equal, iterations within one check interval, forces and roll-out within 1e-6
-    (the general 3 x 3 inverse of G rounds differently from the flat kernel's reciprocals: ~1e-8 N expected).  After set_contact_normals(None) the handle
-    launches wrench_f64_n<N> again and reproduces its earlier outputs bit for bit."""
-    from g1_locomotion_amd import BatchMPC, _lib
-    B = 48
-    x0, xr, ft, ct = nt.batch(B, N, 700 + N, schedule)
-    with BatchMPC(horizon=N, kernel=_lib.KERNEL_WRENCH) as eng:
-        ref = eng.solve(x0, xr, ft, ct, want_y=True)
-        assert eng.kernel_name() == f"wrench_f64_n{N}"
-        eng.set_contact_normals(nt.flat_normals(B, N))
-        out = eng.solve(x0, xr, ft, ct, want_y=True)
-        assert eng.kernel_name() == f"wrench_f64_n{N}_cn"
-        eng.set_contact_normals(None)
-        back = eng.solve(x0, xr, ft, ct, want_y=True)
-        assert eng.kernel_name() == f"wrench_f64_n{N}"
-        check_every = eng.cfg.check_every
-    du, dx = np.abs(out["u"] - ref["u"]).max(), np.abs(out["x"] - ref["x"]).max()
-    print(f"N={N} {schedule}: flat normals against no normals: max |du| = {du:.3e} N, max |dx| = {dx:.3e}, "
-          f"max |d iters| = {np.abs(out['iters'] - ref['iters']).max()}")
-    assert np.array_equal(out["status"], ref["status"])
-    assert np.abs(out["iters"] - ref["iters"]).max() <= check_every
-    assert du <= 1e-6 and dx <= 1e-6, (du, dx)
-    for k in ("u", "x", "y", "status", "iters"):
-        assert np.array_equal(back[k], ref[k]), k
 
 
 def test_block_b_belongs_to_qp_b_under_a_hint_and_a_deferred_tail(torch_first, built_lib):
@@ -138,8 +93,8 @@ def test_block_b_belongs_to_qp_b_under_a_hint_and_a_deferred_tail(torch_first, b
     torch = torch_first
     from g1_locomotion_amd import BatchMPC, _lib
     B, N = 256, 10
-    x0, xr, ft, ct = nt.batch(B, N, 31, "mixed")
-    nr = nt.drawn_normals(B, N, np.random.default_rng(33), per_step=True)
+    x0, xr, ft, ct = si.batch(B, N, 31, "mixed")
+    nr = si.drawn_normals(B, N, np.random.default_rng(33), per_step=True)
     t = _to_dev(torch, x0, xr, ft, ct)
     dnr = torch.from_numpy(nr).cuda()
     with BatchMPC(horizon=N) as eng:
@@ -170,49 +125,13 @@ def test_block_b_belongs_to_qp_b_under_a_hint_and_a_deferred_tail(torch_first, b
         assert torch.equal(plain[k], deferred[k]), k
 
 
-def test_a_bad_normal_stays_local(torch_first, built_lib):
-    torch = torch_first
-    from g1_locomotion_amd import BatchMPC, SrbdqpError, _lib
-    B, N = 64, 12
-    x0, xr, ft, ct = nt.batch(B, N, 41, "mixed")
-    nr = nt.drawn_normals(B, N, np.random.default_rng(42), per_step=True)
-    bad = nr.copy().reshape(B, N, 4, 3)
-    bad[3, 5, 1, 0] = np.nan                                         # an entry that is not finite
-    bad[17, 0, 0] *= 3.0 / np.linalg.norm(bad[17, 0, 0])             # |n| = 3
-    bad[40, 11, 3] = (np.sqrt(1.0 - 0.09), 0.0, 0.3)                 # n_z = 0.3: steeper than 60 degrees
-    bad = bad.reshape(B, N, 12)
-    with BatchMPC(horizon=N) as eng:
-        eng.set_contact_normals(nr)
-        good = eng.solve(x0, xr, ft, ct, want_y=True)
-        with pytest.raises(SrbdqpError, match=r"\(qp 3, step 5, contact 1\) is invalid"):
-            eng.set_contact_normals(bad)
-        kept = eng.solve(x0, xr, ft, ct, want_y=True)                 # the previous setting stays
-        for k in ("u", "x", "y", "status", "iters"):
-            assert np.array_equal(kept[k], good[k]), k
-        only = bad.copy()
-        only[3] = nr[3]
-        with pytest.raises(SrbdqpError, match=r"\(qp 17, step 0, contact 0\) is invalid"):
-            eng.set_contact_normals(only)
-        only[17] = nr[17]
-        with pytest.raises(SrbdqpError, match=r"\(qp 40, step 11, contact 3\) is invalid"):
-            eng.set_contact_normals(only)
-        eng.set_contact_normals(torch.from_numpy(bad).cuda())         # the device setter: the kernel checks
-        out = eng.solve(x0, xr, ft, ct, want_y=True)
-    for b in range(B):
-        if b in (3, 17, 40):
-            assert out["status"][b] == _lib.NUMERICAL and out["iters"][b] == 0, (b, out["status"][b])
-            assert np.all(out["u"][b] == 0.0) and np.all(out["y"][b] == 0.0) and np.all(np.isfinite(out["x"][b]))
-        else:
-            assert out["status"][b] == good["status"][b] and np.array_equal(out["u"][b], good["u"][b]) and np.array_equal(out["x"][b], good["x"][b]), b
-
-
 def test_refusals(torch_first, built_lib):
     torch = torch_first
     from g1_locomotion_amd import BatchMPC, SrbdqpError, _lib
     from g1_locomotion_amd.mpc import robots_array
     B, N = 16, 10
-    x0, xr, ft, ct = nt.batch(B, N, 51, "double")
-    nr = nt.wedge_normals(B, N)
+    x0, xr, ft, ct = si.batch(B, N, 51, "double")
+    nr = si.wedge_normals(B, N)
     setter = "srbdqp_set_contact_normals"
     with BatchMPC(horizon=N) as eng:
         eng.set_contact_normals(nr[:B - 1])
@@ -260,14 +179,14 @@ def test_refusals(torch_first, built_lib):
             with pytest.raises(SrbdqpError, match="general kernel only"):
                 eng.solve(x0, xr, ft, ct)
     with BatchMPC(horizon=24) as eng:
-        n24 = nt.flat_normals(2, 24)
+        n24 = si.flat_normals(2, 24)
         with pytest.raises(SrbdqpError, match="srbdqp_set_contact_normals: contact normals: not at N = 24"):
             eng.set_contact_normals(n24)
         with pytest.raises(SrbdqpError, match="srbdqp_set_contact_normals_device: contact normals: not at N = 24"):
             eng.set_contact_normals(torch.from_numpy(n24).cuda())
         eng.set_contact_normals(None)
     with BatchMPC(horizon=7) as eng:                                  # a live horizon (SRBDQP_FLAG_ANY_HORIZON)
-        n7 = nt.flat_normals(2, 7)
+        n7 = si.flat_normals(2, 7)
         with pytest.raises(SrbdqpError, match="srbdqp_set_contact_normals: refused on a handle whose horizon 7"):
             eng.set_contact_normals(n7)
         with pytest.raises(SrbdqpError, match="srbdqp_set_contact_normals_device: refused on a handle whose horizon 7"):
@@ -281,7 +200,7 @@ def test_mpc_update_with_contact_normals_equals_the_batch_solve(torch_first, bui
     from g1_locomotion_amd import BatchMPC, MPC
     N = 10
     x0, xr, ft, ct = orc.synthetic_batch(1, N, seed=5100 + N, schedule="double")
-    nr = nt.ridge_normals(1, N)
+    nr = si.ridge_normals(1, N)
     with BatchMPC(horizon=N) as eng:
         ref = eng.solve(x0, xr, ft, ct, normals=nr)
         flat = eng.solve(x0, xr, ft, ct)
@@ -296,6 +215,6 @@ def test_mpc_update_with_contact_normals_equals_the_batch_solve(torch_first, bui
                           contact_normals=[nr[0][k] for k in range(N)])                         # per-step lists
         assert np.array_equal(u0l, u0)
         u0f, _ = m.update(ct[0], ft[0], None, x_current=x0[0])                                   # and without: the staged batch-1 path, flat ground
-        assert np.abs(u0f.reshape(-1) - flat["u"][0][0]).max() <= nt.TOL_EXACT_N and np.abs(u0f - u0).max() > 0.25
+        assert np.abs(u0f.reshape(-1) - flat["u"][0][0]).max() <= si.TOL_EXACT_N and np.abs(u0f - u0).max() > 0.25
     finally:
         m.close()

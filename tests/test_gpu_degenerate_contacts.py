@@ -32,17 +32,11 @@ import pytest
 import srbd_oracle as orc
 import scenarios as sc
 import degenerate_twin as dt
-import normals_twin as nt
+import side_inputs as si
+from gpu_helpers import torch_first  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 KEYS = ("u", "x", "y", "status", "iters")
-
-
-@pytest.fixture(scope="module")
-def torch_first():
-    import torch  # load torch's HIP runtime before libsrbdqp.so so both share one
-    assert torch.cuda.is_available()
-    return torch
 
 
 def _host(eng, x0, xr, ft, ct, dtype=np.float64):
@@ -149,7 +143,7 @@ def path_live_horizon(torch):
 
 
 def path_cn_flat(torch):
-    return run_batch("n10_three", "f64", _wrench(10), prepare=lambda eng, B: eng.set_contact_normals(nt.flat_normals(B, 10)), kernel="wrench_f64_n10_cn")
+    return run_batch("n10_three", "f64", _wrench(10), prepare=lambda eng, B: eng.set_contact_normals(si.flat_normals(B, 10)), kernel="wrench_f64_n10_cn")
 
 
 LAT_RUNGS = (1e-1, 1e-2, 1e-3, 1e-5, 1e-8, 0.0)
@@ -216,7 +210,7 @@ def test_mpc_update_raises_on_a_rejected_rung(torch_first, built_lib):
 
 def test_tilted_normals(torch_first, built_lib):
     """wrench_f64_n10_cn with every normal tilted by 10 degrees: the G block is full there and has its own pivots.  The exact optimum is that of the QP in the
-    contacts' own frames (normals_twin); a rung is must-answer here when its flat-ground ratio is 16 x above the threshold (the tilt turns the frames, not
+    contacts' own frames (side_inputs.frames_matrix); a rung is must-answer here when its flat-ground ratio is 16 x above the threshold (the tilt turns the frames, not
     the contact points: the ratio moves by a factor near one)."""
     from g1_locomotion_amd import BatchMPC, _lib
     name, N = "n10_three", 10
@@ -224,7 +218,7 @@ def test_tilted_normals(torch_first, built_lib):
     refs, p = dt.reference(name, "f64")
     B = x0.shape[0]
     a = np.deg2rad(10.0)
-    nr = nt.foot_normals(B, N, (np.sin(a), 0.0, np.cos(a)), (np.sin(a), 0.0, np.cos(a)))
+    nr = si.foot_normals(B, N, (np.sin(a), 0.0, np.cos(a)), (np.sin(a), 0.0, np.cos(a)))
     with BatchMPC(horizon=N, kernel=_lib.KERNEL_WRENCH, rho_restart_iter=-1) as eng:
         eng.set_contact_normals(nr)
         out = eng.solve(x0, xr, ft, ct, want_y=True)
@@ -233,7 +227,7 @@ def test_tilted_normals(torch_first, built_lib):
         alone = eng.solve(x0[1::2], xr[1::2], ft[1::2], ct[1::2], want_y=True)
     assert all(np.array_equal(out[k][1::2], alone[k]) for k in KEYS)
     assert np.all(alone["status"] == orc.STATUS_SOLVED)
-    T = nt.frames_matrix(nr[0])
+    T = si.frames_matrix(nr[0])
     kinds = set()
     for b, r in enumerate(refs):
         i = 2 * b

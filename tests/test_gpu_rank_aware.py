@@ -18,16 +18,10 @@ import pytest
 import srbd_oracle as orc
 import degenerate_twin as dt
 import rank_aware_twin as rt
+from gpu_helpers import torch_first  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 KEYS = ("u", "x", "y", "status", "iters")
-
-
-@pytest.fixture(scope="module")
-def torch_first():
-    import torch  # load torch's HIP runtime before libsrbdqp.so so both share one
-    assert torch.cuda.is_available()
-    return torch
 
 
 @functools.lru_cache(maxsize=None)
@@ -140,7 +134,7 @@ def test_mpc_update_on_feet_in_tandem(torch_first, built_lib):
 def test_calls_without_a_rank_aware_form_are_refused(torch_first, built_lib):
     from g1_locomotion_amd import BatchMPC, RaggedMPC, SrbdqpError, _lib
     from g1_locomotion_amd.mpc import robots_array
-    import normals_twin as nt
+    import side_inputs as si
     x0, xr, ft, ct = orc.synthetic_batch(2, 10, seed=3, schedule="double")
     flag = "SRBDQP_FLAG_RANK_AWARE"
     with _engine(10) as eng:
@@ -151,7 +145,7 @@ def test_calls_without_a_rank_aware_form_are_refused(torch_first, built_lib):
         with pytest.raises(SrbdqpError, match=flag):
             eng.set_robots(robots_array(2))
         with pytest.raises(SrbdqpError, match=flag):
-            eng.set_contact_normals(nt.flat_normals(2, 10))
+            eng.set_contact_normals(si.flat_normals(2, 10))
         eng.set_robots(None); eng.set_contact_normals(None)         # clearing what was never set stays allowed
         out = eng.solve(x0, xr, ft, ct)                             # ... and the handle still solves
         assert np.all(out["status"] == orc.STATUS_SOLVED) and eng.kernel_name() == "wrench_f64_n10_ra"

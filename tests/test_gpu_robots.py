@@ -1,42 +1,28 @@
-"""GPU tests of the per-QP robot records (include/srbdqp.h srbdqp_robot, srbdqp_set_robots / _device, srbdqp_ragged_set_robots / _device):
-every QP of a batch with its own mass, inertia, friction coefficient and normal-force bounds, on the general kernel's MODE = 2 instantiation.
-
-Tolerances are the ones of tests/test_gpu_wrench.py::test_wrench_f64_matches_oracle_and_exact_optimum, per QP against the oracle run with THAT QP's
-parameters: same status, iterations within one check interval, forces <= 2e-3 N from the twin (orc.update), roll-out <= 1e-5, solved QPs <= 5e-2 N from
-the exact optimum (orc.solve_reference; or within 2e-3 N of the twin's own distance from it where that is larger) with its KKT bars, swing forces and
-duals exactly 0.  The engine keeps its default rho restart; the oracle runs
-the same one (orc.default_restart)."""
+"""GPU tests of what is particular to the per-QP robot records (include/srbdqp.h srbdqp_robot, srbdqp_set_robots / _device, srbdqp_ragged_set_robots / _device):
+every QP of a batch with its own mass, inertia, friction coefficient and normal-force bounds, on the general kernel's MODE = 2 instantiation.  What the
+records share with the other per-QP side inputs -- parity per QP, the neutral records, the schedule hint, the ragged order, bad device records -- is in
+tests/test_gpu_side_inputs.py; the bars, the draw and the seeds are described in tests/side_inputs.py."""
 import numpy as np
 import pytest
 
-import srbd_oracle as orc
-from gpu_helpers import device_solve as _device_solve, to_dev as _to_dev
-# the batches and the per-QP bars of the docstring: one copy, shared with the weights suite (HORIZONS stops at 20: the setters refuse N = 24, test_n24_is_refused)
-from weights_twin import HORIZONS, SCHEDULES, TOL_TWIN_N, batch as _batch, check_qp as _check_qp, ragged_inputs as _ragged_inputs
+from gpu_helpers import torch_first  # noqa: F401  (the fixture)
+import side_inputs as si
+from side_inputs import batch as _batch, draw_robots as _draw, ragged_inputs as _ragged_inputs
+from test_gpu_side_inputs import NEUTRAL_CASES, check_neutral, check_parity
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def torch_first():
-    import torch  # load torch's HIP runtime before libsrbdqp.so so both share one
-    assert torch.cuda.is_available()
-    return torch
+@pytest.mark.parametrize("schedule", si.SCHEDULES)
+@pytest.mark.parametrize("N", si.HORIZONS)
+def test_per_qp_records_match_the_oracle(torch_first, built_lib, N, schedule):
+    check_parity(si.ROBOTS, N, schedule)
 
 
-def _draw(B, seed):
-    """B records: mass 0.7 - 1.5 x nominal, each inertia axis 0.6 - 1.6 x, mu 0.3 - 1.0, fz_min 0 - 20 N, fz_max 150 - 1200 N."""
-    from g1_locomotion_amd.mpc import robots_array
-    p = orc.SrbdParams()
-    rng = np.random.default_rng(seed)
-    return robots_array(B, mass=p.mass * rng.uniform(0.7, 1.5, B), inertia=np.asarray(p.inertia) * rng.uniform(0.6, 1.6, (B, 3)),
-                        mu=rng.uniform(0.3, 1.0, B), fz_min=rng.uniform(0.0, 20.0, B), fz_max=rng.uniform(150.0, 1200.0, B))
-
-
-def _params(N, rec):
-    r_iter, r_count = orc.default_restart(N)
-    return orc.params_for(N, mass=float(rec[0]), inertia=tuple(float(v) for v in rec[1:4]), mu=float(rec[4]), fz_min=float(rec[5]),
-                          fz_max=float(rec[6]), rho_restart_iter=r_iter, rho_restart_count=r_count)
+@pytest.mark.parametrize("N,schedule", NEUTRAL_CASES)
+def test_uniform_records_equal_the_config(torch_first, built_lib, N, schedule):
+    """Every record = the handle's config: the same QPs as a KERNEL_WRENCH solve without records, bit for bit."""
+    check_neutral(si.ROBOTS, N, schedule)
 
 
 def _bound_active(u, ct, rec, tol=0.05):
@@ -47,25 +33,6 @@ def _bound_active(u, ct, rec, tol=0.05):
     fric = (np.maximum(np.abs(f[..., 0]), np.abs(f[..., 1])) >= rec[4] * fz - tol) & (fz > tol)
     top = fz >= rec[6] - tol
     return bool(np.any(st & (fric | top)))
-
-
-@pytest.mark.parametrize("schedule", SCHEDULES)
-@pytest.mark.parametrize("N", HORIZONS)
-def test_per_qp_records_match_the_oracle(torch_first, built_lib, N, schedule):
-    from g1_locomotion_amd import BatchMPC
-    B = 32
-    x0, xr, ft, ct = _batch(B, N, 900 + N, schedule)
-    rec = _draw(B, 1900 + N)
-    with BatchMPC(horizon=N) as eng:
-        out0 = eng.solve(x0, xr, ft, ct)                             # nominal robot (the config's) for every QP
-        eng.set_robots(rec)
-        out = eng.solve(x0, xr, ft, ct, want_y=True)
-        assert eng.kernel_name() == f"wrench_f64_n{N}_rb", eng.kernel_name()
-    moved = 0
-    for b in range(B):
-        _check_qp(out, b, N, _params(N, rec[b]), x0, xr, ft, ct)
-        moved += int(np.abs(out["u"][b] - out0["u"][b]).max() > 1.0)
-    assert moved >= B // 4, f"only {moved} of {B} QPs moved by > 1 N from the nominal robot's solution"
 
 
 def test_records_reach_the_kernel_through_the_bounds(torch_first, built_lib):
@@ -85,124 +52,6 @@ def test_records_reach_the_kernel_through_the_bounds(torch_first, built_lib):
                 total += 1
                 moved += int(np.abs(out["u"][b] - out0["u"][b]).max() > 1.0 and _bound_active(out["u"][b], ct[b], rec[b]))
     assert moved >= total // 4, (moved, total)
-
-
-@pytest.mark.parametrize("N,schedule", [(4, "double"), (10, "mixed"), (10, "single"), (16, "double"), (20, "three")])
-def test_uniform_records_equal_the_config(torch_first, built_lib, N, schedule):
-    """Every record = the handle's config: the same QPs as a KERNEL_WRENCH solve without records (statuses and iteration counts identical, forces within
-    1e-9 N).  The MODE = 2 kernel computes 1 / mass, fz / s ... with the same operations fill_args() uses on the host, so the forces come out bit-identical."""
-    from g1_locomotion_amd import BatchMPC, _lib
-    from g1_locomotion_amd.mpc import robots_array
-    B = 48
-    x0, xr, ft, ct = _batch(B, N, 700 + N, schedule)
-    with BatchMPC(horizon=N, kernel=_lib.KERNEL_WRENCH) as eng:
-        ref = eng.solve(x0, xr, ft, ct, want_y=True)
-        eng.set_robots(robots_array(B, cfg=eng.cfg))
-        out = eng.solve(x0, xr, ft, ct, want_y=True)
-        assert eng.kernel_name() == f"wrench_f64_n{N}_rb"
-    assert np.array_equal(out["status"], ref["status"]) and np.array_equal(out["iters"], ref["iters"])
-    assert np.abs(out["u"] - ref["u"]).max() <= 1e-9 and np.abs(out["x"] - ref["x"]).max() <= 1e-9
-    assert np.array_equal(out["u"], ref["u"]) and np.array_equal(out["x"], ref["x"]) and np.array_equal(out["y"], ref["y"])   # bit-identical
-
-
-def test_schedule_hint_keeps_records_by_qp_index(torch_first, built_lib):
-    torch = torch_first
-    from g1_locomotion_amd import BatchMPC
-    B, N = 256, 10
-    x0, xr, ft, ct = _batch(B, N, 31, "mixed")
-    rec = _draw(B, 32)
-    t = _to_dev(torch, x0, xr, ft, ct)
-    with BatchMPC(horizon=N) as eng:
-        eng.set_robots(rec)
-        plain = _device_solve(torch, eng, t, B)
-        torch.cuda.synchronize()
-        hint = torch.from_numpy(np.random.default_rng(5).integers(0, 250, B).astype(np.int32)).cuda()   # a hint that reorders
-        eng.set_schedule_hint(hint.data_ptr(), B)
-        hinted = _device_solve(torch, eng, t, B)
-        torch.cuda.synchronize()
-        eng.set_schedule_hint(0, 0)
-    for k in ("u", "x", "status", "iters"):
-        assert torch.equal(plain[k], hinted[k]), k
-
-
-def _ragged_run(torch, rg, Nq, t, B, rows):
-    u = torch.empty((rows, 12), dtype=torch.float64, device="cuda"); x = torch.empty((rows + B, 13), dtype=torch.float64, device="cuda")
-    st = torch.empty(B, dtype=torch.int32, device="cuda"); it = torch.empty(B, dtype=torch.int32, device="cuda")
-    rg.solve_device(B, Nq, t["x0"].data_ptr(), t["xr"].data_ptr(), t["ft"].data_ptr(), t["ct"].data_ptr(), u.data_ptr(), x.data_ptr(), st.data_ptr(),
-                    it.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
-    return dict(u=u, x=x, status=st, iters=it)
-
-
-@pytest.mark.parametrize("defer", [False, True])
-def test_ragged_records_follow_the_callers_order(torch_first, built_lib, defer):
-    """Horizons {8, 12, 16}, the QPs shuffled across the buckets: QP b of the caller's order solves with record b (against the oracle per QP); with
-    SRBDQP_FLAG_DEFER_TAIL the same call equals it after the flush."""
-    torch = torch_first
-    from g1_locomotion_amd import RaggedMPC, _lib
-    horizons = (8, 12, 16)
-    B = 40
-    Nq, x0, xr, ft, ct = _ragged_inputs(B, horizons, 77)
-    rec = _draw(B, 78)
-    off = np.concatenate([[0], np.cumsum(Nq)])
-    rows = int(off[-1])
-    t = _to_dev(torch, x0, xr, ft, ct)
-    rg = RaggedMPC(horizons=horizons)
-    try:
-        rg.set_robots(rec)
-        out = _ragged_run(torch, rg, Nq, t, B, rows)
-        torch.cuda.synchronize()
-    finally:
-        rg.close()
-    out = {k: v.cpu().numpy() for k, v in out.items()}
-    if defer:
-        rgd = RaggedMPC(horizons=horizons, flags=_lib.FLAG_DEFER_TAIL)
-        try:
-            rgd.set_robots(torch.from_numpy(rec).cuda())              # (the device setter: read in place, beside the deferred passes too)
-            dout = _ragged_run(torch, rgd, Nq, t, B, rows)
-            rgd.flush(torch.cuda.current_stream().cuda_stream)
-            torch.cuda.synchronize()
-        finally:
-            rgd.close()
-        for k in ("u", "x", "status", "iters"):
-            assert np.array_equal(dout[k].cpu().numpy(), out[k]), k
-        return
-    for b in range(B):
-        N = int(Nq[b])
-        p = _params(N, rec[b])
-        ref = orc.update(p, x0[b], xr[off[b]:off[b + 1]], ft[off[b]:off[b + 1]], ct[off[b]:off[b + 1]])
-        assert out["status"][b] == ref["status"], (b, N, out["status"][b], ref["status"])
-        assert abs(int(out["iters"][b]) - ref["iters"]) <= p.check_every, (b, N, out["iters"][b], ref["iters"])
-        assert np.abs(out["u"][off[b]:off[b + 1]] - ref["u"]).max() <= TOL_TWIN_N, (b, N)
-        assert np.abs(out["x"][off[b] + b:off[b + 1] + b + 1] - ref["x"]).max() <= 1e-5, (b, N)
-
-
-def test_host_and_device_setters_agree_and_a_bad_device_record_stays_local(torch_first, built_lib):
-    torch = torch_first
-    from g1_locomotion_amd import BatchMPC, _lib
-    B, N = 64, 12
-    x0, xr, ft, ct = _batch(B, N, 41, "mixed")
-    rec = _draw(B, 42)
-    with BatchMPC(horizon=N) as eng:
-        eng.set_robots(rec)
-        host = eng.solve(x0, xr, ft, ct, want_y=True)
-        dev_rec = torch.from_numpy(rec).cuda()
-        eng.set_robots(dev_rec)
-        dev = eng.solve(x0, xr, ft, ct, want_y=True)
-        for k in ("u", "x", "y", "status", "iters"):
-            assert np.array_equal(host[k], dev[k]), k
-        bad = rec.copy()
-        bad[3, 0] = 0.0                 # mass <= 0
-        bad[17, 4] = np.nan             # mu NaN
-        bad[40, 6] = 5.0                # fz_max < fz_min
-        dev_bad = torch.from_numpy(bad).cuda()
-        eng.set_robots(dev_bad)
-        out = eng.solve(x0, xr, ft, ct, want_y=True)
-    for b in range(B):
-        if b in (3, 17, 40):
-            assert out["status"][b] == _lib.NUMERICAL and out["iters"][b] == 0, (b, out["status"][b])
-            assert np.all(out["u"][b] == 0.0) and np.all(out["y"][b] == 0.0) and np.all(np.isfinite(out["x"][b]))
-        else:
-            assert out["status"][b] == host["status"][b] and np.array_equal(out["u"][b], host["u"][b]), b
 
 
 def test_refusals_and_clearing(torch_first, built_lib):

@@ -42,6 +42,7 @@ import pytest
 
 import scenarios as sc
 import srbd_oracle as orc
+from gpu_helpers import torch_first  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -66,13 +67,6 @@ def _report():
     print("\nworst observed deviation / bound, per group")
     for g in sorted(_worst):
         print(f"  {g:44s} {_worst[g][0]:.3e} / {_worst[g][1]:.0e}")
-
-
-@pytest.fixture(scope="module")
-def torch_first():
-    import torch  # load torch's HIP runtime before libsrbdqp.so so both share one
-    assert torch.cuda.is_available()
-    return torch
 
 
 def _engine(N, **kw):
@@ -524,13 +518,13 @@ def test_ragged_horizons_bucketed_launch(torch_first, built_lib):
 
 @pytest.mark.parametrize("N,schedule,yaw", [(12, "mixed", "wrap"), (20, "three", "turn")])
 def test_per_qp_records_match_the_oracle(torch_first, built_lib, N, schedule, yaw):
-    """set_robots() (the general kernel's MODE = 2 instantiation) on turning inputs, through tests/test_gpu_robots.py::_check_qp: per QP against
+    """set_robots() (the general kernel's MODE = 2 instantiation) on turning inputs, through tests/side_inputs.py check_qp: per QP against
     the oracle with THAT QP's mass, inertia, mu and fz bounds; engine and oracle with the default rho restart."""
     from g1_locomotion_amd import BatchMPC
-    from test_gpu_robots import _check_qp, _draw, _params
+    import side_inputs as si
     B = 8
     x0, xr, ft, ct, pc = _inputs(N, schedule, yaw, B)
-    rec = _draw(B, 2900 + N)
+    rec = si.draw_robots(B, 2900 + N)
     with BatchMPC(horizon=N) as eng:
         out0 = eng.solve(x0, xr, ft, ct)
         eng.set_robots(rec)
@@ -538,7 +532,8 @@ def test_per_qp_records_match_the_oracle(torch_first, built_lib, N, schedule, ya
         assert eng.kernel_name() == f"wrench_f64_n{N}_rb", eng.kernel_name()
     moved = 0
     for b in range(B):
-        _check_qp(out, b, N, _params(N, rec[b]), x0, xr, ft, ct)
+        p = si.params(N, robot=rec[b])
+        si.check_qp(out, b, N, p, si.twin(p, x0[b], xr[b], ft[b], ct[b]), ct[b])
         moved += int(np.abs(out["u"][b] - out0["u"][b]).max() > 1.0)
     assert moved >= B // 4, moved
 

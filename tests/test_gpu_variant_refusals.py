@@ -1,20 +1,23 @@
 """Which C-ABI call has a form for which variant of the general kernel (srbdqp.hip, `Variant` and the masks of `require_form`): a handle is plain, or has robot
-records set, or cost weights set, or contact normals set, or a live horizon (SRBDQP_FLAG_ANY_HORIZON), or rank-aware steps (SRBDQP_FLAG_RANK_AWARE) -- never two
-of them, except robot records beside cost weights (a robots handle here; what only weights show is in test_gpu_weights.py).  Through the
+records set, or cost weights set, or contact normals set, or an external wrench set, or a live horizon (SRBDQP_FLAG_ANY_HORIZON), or rank-aware steps
+(SRBDQP_FLAG_RANK_AWARE) -- never two of them, except robot records, cost weights and the wrench beside one another (what only weights or only the wrench
+show is in test_gpu_weights.py and test_gpu_ext_wrench.py).  Through the
 Python bindings, on one handle per variant, every entry point of the table below either returns SRBDQP_E_INVALID with a message that names the call and ends in
-the variant's fixed text, or returns SRBDQP_OK.  Nothing here looks at numbers: the variants' own suites do (test_gpu_robots.py, test_gpu_contact_normals.py,
+the variant's fixed text, or returns SRBDQP_OK.  Nothing here looks at numbers: the variants' own suites do (test_gpu_side_inputs.py, test_gpu_contact_normals.py,
 test_gpu_any_horizon.py, test_gpu_rank_aware.py).  The smallest shapes that reach every branch: N = 4 (a live horizon: 3, which runs on N* = 4), two QPs of full
 double support."""
 import numpy as np
 import pytest
 
 import srbd_oracle as orc
-import normals_twin as nt
-from gpu_helpers import refusal as _refusal
+import side_inputs as si
+from gpu_helpers import refusal as _refusal, torch_first  # noqa: F401  (torch_first: the fixture)
 
 pytestmark = pytest.mark.gpu
 B = 2
-VARIANTS = ("robots", "weights", "normals", "live", "rank_aware")
+VARIANTS = ("robots", "weights", "normals", "ext_wrench", "live", "rank_aware")
+# the suffix of the kernel a variant's fp64 batch solves launch
+SUFFIX = dict(robots="_rb", weights="_wt", normals="_cn", ext_wrench="_ew")
 
 # the fixed text behind "<call>: " in a refusal, per variant of the handle
 TAIL = dict(
@@ -24,6 +27,8 @@ TAIL = dict(
             "-- one pair of weights for every QP goes in srbdqp_config",
     normals="refused while contact normals are set (srbdqp_set_contact_normals): only the fp64 batch solves on the general kernel read them "
             "-- srbdqp_set_contact_normals(h, NULL, 0) goes back to flat ground",
+    ext_wrench="refused while an external wrench is set (srbdqp_set_external_wrench): only the fp64 batch and ragged solves on the general kernel read it "
+               "-- srbdqp_set_external_wrench(h, NULL, 0) goes back to no wrench",
     live="refused on a handle whose horizon 3 was admitted by SRBDQP_FLAG_ANY_HORIZON: only the fp64 batch, ragged and staged solves run a live horizon "
          "(the general kernel's fp64 batch instantiation for N = 4)",
     rank_aware="refused on a handle created with SRBDQP_FLAG_RANK_AWARE: only the fp64 batch and staged solves have rank-aware wrench steps "
@@ -36,30 +41,26 @@ ALL = frozenset(VARIANTS)
 REFUSES = {
     "srbdqp_solve_batch_f64": frozenset(),
     "srbdqp_solve_batch_device_f64": frozenset(),
-    "srbdqp_solve_staged_f64": frozenset({"robots", "weights", "normals"}),
-    "srbdqp_update_f64": frozenset({"robots", "weights", "normals"}),
-    "srbdqp_prepare_staged_f64": frozenset({"robots", "weights", "normals", "live"}),
-    "srbdqp_solve_prepared_f64": frozenset({"robots", "weights", "normals", "live"}),
+    "srbdqp_solve_staged_f64": frozenset({"robots", "weights", "normals", "ext_wrench"}),
+    "srbdqp_update_f64": frozenset({"robots", "weights", "normals", "ext_wrench"}),
+    "srbdqp_prepare_staged_f64": frozenset({"robots", "weights", "normals", "ext_wrench", "live"}),
+    "srbdqp_solve_prepared_f64": frozenset({"robots", "weights", "normals", "ext_wrench", "live"}),
     "srbdqp_solve_batch_f32": ALL,
     "srbdqp_solve_batch_device_f32": ALL,
-    "srbdqp_assemble_f64": frozenset({"robots", "weights", "normals", "live"}),
+    "srbdqp_assemble_f64": frozenset({"robots", "weights", "normals", "ext_wrench", "live"}),
     "srbdqp_assemble_wrench_f64": ALL,
     "srbdqp_set_robots": frozenset({"normals", "live", "rank_aware"}),
     "srbdqp_set_robots_device": frozenset({"normals", "live", "rank_aware"}),
     "srbdqp_set_weights": frozenset({"normals", "live", "rank_aware"}),
     "srbdqp_set_weights_device": frozenset({"normals", "live", "rank_aware"}),
-    "srbdqp_set_contact_normals": frozenset({"robots", "weights", "live", "rank_aware"}),
-    "srbdqp_set_contact_normals_device": frozenset({"robots", "weights", "live", "rank_aware"}),
+    "srbdqp_set_contact_normals": frozenset({"robots", "weights", "ext_wrench", "live", "rank_aware"}),
+    "srbdqp_set_contact_normals_device": frozenset({"robots", "weights", "ext_wrench", "live", "rank_aware"}),
+    "srbdqp_set_external_wrench": frozenset({"normals", "live", "rank_aware"}),
+    "srbdqp_set_external_wrench_device": frozenset({"normals", "live", "rank_aware"}),
 }
-# variant -> the setters its handle accepts that would add the other kind of record: made as set-then-clear, so that the walk leaves the handle's state alone
-SET_THEN_CLEAR = dict(robots=("srbdqp_set_weights", "srbdqp_set_weights_device"), weights=("srbdqp_set_robots", "srbdqp_set_robots_device"))
-
-
-@pytest.fixture(scope="module")
-def torch_first():
-    import torch  # load torch's HIP runtime before libsrbdqp.so so both share one
-    assert torch.cuda.is_available()
-    return torch
+# variant -> the setters its handle accepts that would add another kind of input: made as set-then-clear, so that the walk leaves the handle's state alone
+_RB, _WT, _EW = (tuple(f"srbdqp_set_{k}{d}" for d in ("", "_device")) for k in ("robots", "weights", "external_wrench"))
+SET_THEN_CLEAR = dict(robots=_WT + _EW, weights=_RB + _EW, ext_wrench=_RB + _WT)
 
 
 def _engine(variant):
@@ -82,9 +83,9 @@ def _calls(torch, eng, N, then_clear=()):
     st["x0"][:B], st["x_ref"][:B], st["foot"][:B], st["contact"][:B] = x0, xr, ft, ct8
     dev = {dt: [torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).cuda() for a in (x0, xr, ft)] + [torch.from_numpy(ct8).cuda(),
                 torch.empty((B, N, 12), dtype=getattr(torch, np.dtype(dt).name), device="cuda")] for dt in (np.float64, np.float32)}
-    rb, nr = robots_array(B, mass=[30.0, 40.0]), nt.wedge_normals(B, N)
+    rb, nr, ew = robots_array(B, mass=[30.0, 40.0]), si.wedge_normals(B, N), si.draw_wrench(B, N, 71)
     wr = weights_array(B, r_diag=[1e-4, 3e-4])
-    rb_dev, nr_dev, wr_dev = torch.from_numpy(rb).cuda(), torch.from_numpy(nr).cuda(), torch.from_numpy(wr).cuda()
+    rb_dev, nr_dev, wr_dev, ew_dev = (torch.from_numpy(a).cuda() for a in (rb, nr, wr, ew))
     raw = _lib.load()
 
     def device(dt):
@@ -117,6 +118,8 @@ def _calls(torch, eng, N, then_clear=()):
         "srbdqp_set_weights_device": setter("srbdqp_set_weights_device", eng.set_weights, wr_dev),
         "srbdqp_set_contact_normals": lambda: eng.set_contact_normals(nr),
         "srbdqp_set_contact_normals_device": lambda: eng.set_contact_normals(nr_dev),
+        "srbdqp_set_external_wrench": setter("srbdqp_set_external_wrench", eng.set_external_wrench, ew),
+        "srbdqp_set_external_wrench_device": setter("srbdqp_set_external_wrench_device", eng.set_external_wrench, ew_dev),
     }
 
 
@@ -133,6 +136,8 @@ def test_every_call_refuses_or_accepts_the_variant(torch_first, built_lib, varia
             calls["srbdqp_set_weights"]()
         if variant == "normals":
             calls["srbdqp_set_contact_normals"]()
+        if variant == "ext_wrench":
+            calls["srbdqp_set_external_wrench"]()
         for name, refusing in REFUSES.items():
             msg = _refusal(calls[name])
             print(f"{variant:10s} {name:34s} -> {msg or 'SRBDQP_OK'}")
@@ -141,16 +146,20 @@ def test_every_call_refuses_or_accepts_the_variant(torch_first, built_lib, varia
                 assert msg == f"srbdqp error {_lib.E_INVALID}: {name}: {tail}", (variant, name, msg)
             else:
                 assert msg is None, (variant, name, msg)
+                if name in ("srbdqp_solve_batch_f64", "srbdqp_solve_batch_device_f64") and variant in SUFFIX:
+                    assert eng.kernel_name() == f"wrench_f64_n4{SUFFIX[variant]}", (variant, name, eng.kernel_name())
         if variant == "live":
             return
-        # the clearing calls succeed on every handle, and leave it in its base state: plain (what records, weights or normals refused runs again, and another
+        # the clearing calls succeed on every handle, and leave it in its base state: plain (what records, weights, normals or a wrench refused runs again, and another
         # setter is accepted), or rank-aware still
         eng.set_robots(None)
         eng.set_weights(None)
         eng.set_contact_normals(None)
+        eng.set_external_wrench(None)
         eng.set_robots(torch_first.empty((0, 8), dtype=torch_first.float64, device="cuda"))
         eng.set_weights(torch_first.empty((0, 16), dtype=torch_first.float64, device="cuda"))
         eng.set_contact_normals(torch_first.empty((0, N, 12), dtype=torch_first.float64, device="cuda"))
+        eng.set_external_wrench(torch_first.empty((0, N, 6), dtype=torch_first.float64, device="cuda"))
         if variant == "rank_aware":
             assert _refusal(calls["srbdqp_solve_batch_f32"]) == f"srbdqp error {_lib.E_INVALID}: srbdqp_solve_batch_f32: {TAIL[variant]}"
             assert _refusal(calls["srbdqp_set_robots"]) == f"srbdqp error {_lib.E_INVALID}: srbdqp_set_robots: {TAIL[variant]}"

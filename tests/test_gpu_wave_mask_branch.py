@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import srbd_oracle as orc
+from gpu_helpers import torch_first  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,13 +24,6 @@ def mask_branch_batch():
         if b >= 48:
             ct[b, (b + 3) % N, :] = 0
     return x0, xr, ft, ct
-
-
-@pytest.fixture(scope="module")
-def torch_first():
-    import torch  # load torch's HIP runtime before libsrbdqp.so so both share one
-    assert torch.cuda.is_available()
-    return torch
 
 
 @pytest.fixture(scope="module")

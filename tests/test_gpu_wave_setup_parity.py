@@ -7,17 +7,11 @@ import numpy as np
 import pytest
 
 import srbd_oracle as orc
+from gpu_helpers import torch_first  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 TOL_TWIN_N = 2e-3
-
-
-@pytest.fixture(scope="module")
-def torch_first():
-    import torch  # load torch's HIP runtime before libsrbdqp.so so both share one
-    assert torch.cuda.is_available()
-    return torch
 
 
 def test_wave_kernel_4096_single_support_against_oracle_and_golden(torch_first, built_lib):

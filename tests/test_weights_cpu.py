@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 
 import scenarios as sc
+import side_inputs as si
 import srbd_oracle as orc
-import weights_twin as wt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -80,7 +80,7 @@ def test_weights_array_broadcasts_and_fills_the_config(built_lib):
     a = weights_array(2, r_diag=[1e-3, 2e-3])
     recs = (_lib.Weights * 2).from_buffer_copy(a.tobytes())
     assert recs[1].r_diag == 2e-3 and list(recs[0].q_diag) == list(_lib.default_config().q_diag) and list(recs[0].reserved) == [0.0, 0.0]
-    d = wt.draw(4, 1)
+    d = si.draw_weights(4, 1)
     assert d.shape == (4, 16) and np.all(d[:, 14:] == 0.0) and np.all(d[0, 0:3] == 0.0) and np.all(d[0, 6:9] == 0.0) and np.all(d[1, :13] == 0.0) and np.all(d[:, 13] > 0.0)
 
 
@@ -91,10 +91,10 @@ def test_the_closed_forms_hold_for_arbitrary_weights(N, schedule):
     the 1e-8 of the refined inverse that tests/test_oracle_turning.py::test_wrench_reduction_is_the_inverse_of_the_dense_k asks.  (This exercises the oracle
     alone -- the twin the GPU tests compare against --, so it does not depend on the setters: it passes with or without them.)"""
     B = 4
-    x0, xr, ft, ct = wt.batch(B, N, wt.batch_seed(N, schedule), schedule)
-    rec = wt.draw(B, wt.weights_seed(N))
+    x0, xr, ft, ct = si.batch(B, N, si.batch_seed(N, schedule), schedule)
+    rec = si.draw_weights(B, si.weights_seed(N))
     for b in range(B):
-        p = wt.params(N, rec[b])
+        p = si.params(N, weights=rec[b])
         red, vi, ri = orc.presolve(orc.build_qp(p, x0[b], xr[b], ft[b], ct[b]), ct[b])
         P, q, vi2 = orc.closed_form_hessian_gradient(p, x0[b], xr[b], ft[b], ct[b])
         np.testing.assert_array_equal(vi, vi2)
@@ -127,7 +127,7 @@ def rows(built_lib):
     return resource_table.parse(log)
 
 
-@pytest.mark.parametrize("N", wt.HORIZONS)
+@pytest.mark.parametrize("N", si.HORIZONS)
 def test_weight_kernels_keep_nothing_in_scratch_and_their_occupancy(rows, N):
     """One srbdqp_wrench_wt_kernel per horizon the setters accept, with 0 bytes of scratch and the occupancy of its MODE = 0 twin (the batch kernel of the
     same N and waves per SIMD)."""
