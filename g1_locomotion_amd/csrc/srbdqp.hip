@@ -41,6 +41,44 @@ struct PerQp {
     void release() { if (own) (void)hipFree(own); }
 };
 
+struct Carver {
+    char* base; size_t off = 0;
+    explicit Carver(char* b) : base(b) {}
+    template <typename T> T* take(size_t count) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += (count * sizeof(T) + 255) & ~size_t(255);
+        return p;
+    }
+};
+
+// ---- what a solve that restarts by further LAUNCHES needs beside its arguments: one structure for a handle's launch streams and for a ragged object ----
+// RestartSet: the buffers through which a pass hands over to the one behind it.  RestartBufs: an owner's sets, carved from one allocation (carve_restart_sets) -- one
+// set, or kRestartSets in rotation under SRBDQP_FLAG_DEFER_TAIL, where the passes of a solve run on a tail stream beside the owner's next solves.  Tail: such a
+// stream with the event that closes each set's passes on it -- a set is reused only behind the event that closed its last user's passes (tail_wait).
+constexpr int kRestartSets = 3;
+struct RestartSet {
+    float* resid = nullptr;                   // [items][4]: fp32 maxima of the last check of the QPs a pass left at its cap
+    double* ybuf = nullptr;                   // [duals]: y when the caller passes none (a pass warm-starts from the outputs of the one before it)
+    int32_t* stbuf = nullptr;                 // [items]: status when the caller passes none
+    double* rho[2] = {nullptr, nullptr};      // [items] each: the rho a restart pass ran its QPs with, for the pass behind it (alternating)
+    // index lists, [items] each, and their counters.  A launch stream under the defer flag: list[p] holds the QPs pass p left at its cap (cnt[p] of them), the
+    // dispatch order of pass p + 1.  A ragged object: list[0] is the call's bucket permutation, list[1] its row offsets.
+    int32_t* list[4] = {nullptr, nullptr, nullptr, nullptr}; int32_t* cnt = nullptr;
+};
+struct RestartBufs {
+    char* mem = nullptr; size_t bytes = 0;
+    size_t items = 0, duals = 0; int nsets = 0;   // the sets, and what each holds: QPs and dual doubles (a launch stream: B x 20 N; a ragged object: 20 per horizon row)
+    RestartSet set[kRestartSets];
+    double* ubuf = nullptr;                   // staged first pass: device copy of u for the pass behind it (KArgs::u_dev)
+    bool fits(size_t n, size_t d, int sets) const { return mem && items >= n && duals >= d && nsets >= sets; }
+};
+struct Tail {
+    hipStream_t st = nullptr;                 // highest priority, non-blocking
+    hipEvent_t close[kRestartSets] = {nullptr, nullptr, nullptr};   // behind the last pass of the last solve that used set k on this stream
+    bool used[kRestartSets] = {false, false, false};
+    hipEvent_t last = nullptr;                // closes the passes of the last deferred solve on this stream (srbdqp_flush / srbdqp_ragged_flush wait for it), or null
+};
+
 struct srbdqp_handle {
     srbdqp_config cfg;
     hipStream_t stream = nullptr;
@@ -60,23 +98,12 @@ struct srbdqp_handle {
         hipStream_t st = nullptr; bool used = false;
         int32_t* perm = nullptr; size_t perm_cap = 0;
         double* ws = nullptr; size_t ws_doubles = 0;
-        // rho restart: fp32 maxima of the last check of the QPs that end at the cap of the first pass, and y / status when
-        // the caller passes none (the second pass warm-starts from the first pass's outputs)
-        char* rs = nullptr; size_t rs_items = 0, rs_rows = 0;
-        float* resid = nullptr; double* ybuf = nullptr;
-        double* ubuf = nullptr;                   // staged first pass: device copy of u for the pass behind it (KArgs::u_dev)
-        int32_t* stbuf = nullptr;
-        double* rhobuf[2] = {nullptr, nullptr};   // rho a restart pass ran its QPs with, for the pass behind it (alternating)
-        // SRBDQP_FLAG_DEFER_TAIL on the kernels that restart by further LAUNCHES: three sets of the buffers above in rotation (a solve's restart passes run on
-        // tail_st, beside the next solves of this stream; a set is reused only behind the event that closes its last user's passes), + per set the lists through
-        // which a pass hands its capped QPs to the next one (so that the working workgroups of a pass come first in its grid)
-        struct RSet { float* resid = nullptr; double* ybuf = nullptr; int32_t* stbuf = nullptr; double* rhobuf[2] = {nullptr, nullptr};
-                      int32_t* list[4] = {nullptr, nullptr, nullptr, nullptr}; int32_t* cnt = nullptr; hipEvent_t ev_tail = nullptr; bool ev_used = false; };
-        RSet rsets[3];
-        int rs_nsets = 0;
+        // rho restart by further launches: this stream's sets (one; three once a solve deferred its passes: solve_deferred_passes), their rotation and the tail
+        // stream the deferred passes run on.  An in-stream solve uses set 0.
+        RestartBufs rb;
         unsigned long long rs_k = 0;
-        hipStream_t tail_st = nullptr; hipEvent_t ev_main = nullptr;
-        hipEvent_t last_tail = nullptr;    // closes the restart passes of the last deferred solve on this stream (srbdqp_flush waits for it), or null
+        Tail rtail;
+        hipEvent_t ev_main = nullptr;      // behind a deferred solve's first pass: the tail stream waits for it
         // deferred tails (SRBDQP_FLAG_DEFER_TAIL): three rotating lists of continuation records and their counts
         char* tail = nullptr; int32_t* tail_cnt = nullptr; size_t tail_cap = 0;
         unsigned long long tail_k = 0;     // launches so far: list k % 3 is appended to, (k + 2) % 3 read, (k + 1) % 3 zeroed
@@ -188,12 +215,12 @@ int with_horizon_in(srbdqp_handle* h, F&& f, std::integer_sequence<int, Ns...>) 
 template <class F>
 int with_horizon(srbdqp_handle* h, F&& f) { return with_horizon_in(h, f, Horizons{}); }
 
-// staged path, a multi-pass solve of which only the first pass ran: its arguments, how many restart passes may follow it, the launch-stream slot whose
-// buffers they use (the host starts the next pass if a status asks for it)
+// staged path, a multi-pass solve of which only the first pass ran: its arguments, how many restart passes may follow it, the set whose buffers they use
+// (the host starts the next pass if a status asks for it)
 struct Lazy {
     KArgs a1;
     int rcount = 1;
-    srbdqp_handle::StreamSlot* slot = nullptr;
+    const RestartSet* set = nullptr;
     bool pending = false;          // the solve really was such a first pass (not: restarted in place, or no restart at all)
 };
 
@@ -241,6 +268,62 @@ int grow(O* o, T*& buf, size_t& cap, size_t want, hipStream_t busy, const char* 
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), want * sizeof(T));
     if (e != hipSuccess) { o->err = std::string(what) + ": " + hipGetErrorString(e); return SRBDQP_E_NOMEM; }
     cap = want;
+    return SRBDQP_OK;
+}
+
+// (re)carve rb from one allocation: nsets sets for `items` QPs and `duals` dual doubles, `nlists` index lists per set (with their counters), u_doubles of ubuf.  The
+// old contents are not kept: the caller has waited for everything that used them -- earlier work of this owner only -- and drained its tails (tail_drain).
+template <class O>
+int carve_restart_sets(O* o, RestartBufs& rb, size_t items, size_t duals, int nsets, int nlists, size_t u_doubles) {
+    auto carve = [&](Carver c) {
+        for (int i = 0; i < nsets; ++i) {
+            RestartSet& r = rb.set[i];
+            r.resid = c.take<float>(items * 4); r.ybuf = c.take<double>(duals); r.stbuf = c.take<int32_t>(items);
+            r.rho[0] = c.take<double>(items); r.rho[1] = c.take<double>(items);
+            for (int j = 0; j < nlists; ++j) r.list[j] = c.take<int32_t>(items);
+            r.cnt = nlists ? c.take<int32_t>(16) : nullptr;
+        }
+        rb.ubuf = u_doubles ? c.take<double>(u_doubles) : nullptr;
+        return c.off;
+    };
+    rb.items = rb.duals = 0; rb.nsets = 0;
+    const int rc = grow(o, rb.mem, rb.bytes, carve(Carver(nullptr)), nullptr, "hipMalloc restart buffers");   // (a dry run for the size)
+    if (rc != SRBDQP_OK) return rc;
+    carve(Carver(rb.mem));
+    rb.items = items; rb.duals = duals; rb.nsets = nsets;
+    return SRBDQP_OK;
+}
+
+// ---- the tail-stream rotation of SRBDQP_FLAG_DEFER_TAIL (a launch stream has one Tail, a ragged object one per bucket) ----
+template <class O>
+int tail_create(O* o, Tail& t) {
+    int least = 0, greatest = 0;
+    HIP_TRY(o, hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIP_TRY(o, hipStreamCreateWithPriority(&t.st, hipStreamNonBlocking, greatest));
+    for (auto& ev : t.close) HIP_TRY(o, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    return SRBDQP_OK;
+}
+void tail_destroy(Tail& t) {
+    if (t.st) { (void)hipStreamSynchronize(t.st); (void)hipStreamDestroy(t.st); }
+    for (auto ev : t.close) if (ev) (void)hipEventDestroy(ev);
+}
+// the set a solve takes: the next of the rotation, or the only one
+inline int next_set(unsigned long long& k, int nsets) { return nsets > 1 ? (int)(k++ % (unsigned long long)nsets) : 0; }
+// before anything on stream `on` overwrites set k: its last user on this tail has finished its passes
+template <class O>
+int tail_wait(O* o, const Tail& t, int k, hipStream_t on) { if (t.used[k]) HIP_TRY(o, hipStreamWaitEvent(on, t.close[k], 0)); return SRBDQP_OK; }
+// behind the last pass of a solve on set k: its closing event, which a flush of the owner waits for too
+template <class O>
+int tail_close(O* o, Tail& t, int k) { HIP_TRY(o, hipEventRecord(t.close[k], t.st)); t.used[k] = true; t.last = t.close[k]; return SRBDQP_OK; }
+// a flush: stream `on` waits for the passes of the last deferred solve
+template <class O>
+int tail_join(O* o, const Tail& t, hipStream_t on) { if (t.last) HIP_TRY(o, hipStreamWaitEvent(on, t.last, 0)); return SRBDQP_OK; }
+// before the sets are carved anew: nothing is pending on the tail stream, no set has a last user
+template <class O>
+int tail_drain(O* o, Tail& t) {
+    if (t.st) HIP_TRY(o, hipStreamSynchronize(t.st));
+    t.last = nullptr;
+    for (auto& u : t.used) u = false;
     return SRBDQP_OK;
 }
 
@@ -938,16 +1021,6 @@ int launch(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t st, int 
     return SRBDQP_OK;
 }
 
-struct Carver {
-    char* base; size_t off = 0;
-    explicit Carver(char* b) : base(b) {}
-    template <typename T> T* take(size_t count) {
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += (count * sizeof(T) + 255) & ~size_t(255);
-        return p;
-    }
-};
-
 // The arrays of a host-buffer call (a handle's or a ragged object's): in() one the call uploads, out() one it downloads, zeroed() one it clears first (and
 // downloads, given a host pointer).  A null host pointer means no array, except for out(..., true): status / iters, which the kernels write either way.
 struct HostIo {
@@ -1011,7 +1084,7 @@ int host_call(O* o, Arrays&& arrays, Run&& run) {
 // could end SOLVED in a large batch and MAX_ITER alone): what differs is how the passes run --
 //    one-wave kernel:      in place, inside the kernel (srbdqp_setup1.hpp RST), or handed to the next launch on the stream (SRBDQP_FLAG_DEFER_TAIL);
 //    every other kernel:   one more launch over the same grid per pass, in which only the workgroups of the QPs the pass before left at its cap do anything
-//                          (the rho of a pass reaches the next one through StreamSlot::rhobuf);
+//                          (the rho of a pass reaches the next one through RestartSet::rho);
 //    staged (batch-1) call: the host starts a further pass only when a status[] asks for it (4 % of the calls take a second launch, 1 % a third).
 // The price where a call is small: it cannot end before its slowest QP, and a restarted one is a chain of up to three set-ups and 250 iterations (0.22 ms
 // against 0.16 ms for 250 iterations at one rho): 512 QPs per call on the one-wave kernel 7.2 -> 5.2 M QP/s.  rho_restart_iter = -1 buys that back.
@@ -1035,33 +1108,13 @@ inline int restart_iter_of(const srbdqp_handle* h, int* count = nullptr) {
     return (r > 0 && r < c.max_iter) ? r : 0;
 }
 
-// per-stream restart buffers for batches of up to B QPs with m rows
-int ensure_restart_buffers(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStream_t st, size_t B, size_t m, int nsets = 1) {
-    if (slot->rs && slot->rs_items >= B && slot->rs_rows >= m && slot->rs_nsets >= nsets) return SRBDQP_OK;
+// a launch stream's restart sets for batches of up to B QPs (nsets = 3: with the lists of the deferred passes); growing waits for this stream and its tail only
+int ensure_restart_buffers(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStream_t st, size_t B, int nsets = 1) {
+    const size_t N = (size_t)h->cfg.horizon;
+    if (slot->rb.fits(B, B * 20 * N, nsets)) return SRBDQP_OK;
     HIP_TRY(h, hipStreamSynchronize(st));
-    if (slot->tail_st) HIP_TRY(h, hipStreamSynchronize(slot->tail_st));
-    if (slot->rs) { HIP_TRY(h, hipFree(slot->rs)); slot->rs = nullptr; }
-    auto carve = [&](Carver& c) {
-        for (int i = 0; i < nsets; ++i) {
-            auto& r = slot->rsets[i];
-            r.resid = c.take<float>(B * 4); r.ybuf = c.take<double>(B * m); r.stbuf = c.take<int32_t>(B);
-            r.rhobuf[0] = c.take<double>(B); r.rhobuf[1] = c.take<double>(B);
-            if (nsets > 1) { for (int j = 0; j < 4; ++j) r.list[j] = c.take<int32_t>(B); r.cnt = c.take<int32_t>(16); }
-            r.ev_used = false;
-        }
-        const auto& r0 = slot->rsets[0];
-        slot->resid = r0.resid; slot->ybuf = r0.ybuf; slot->stbuf = r0.stbuf; slot->rhobuf[0] = r0.rhobuf[0]; slot->rhobuf[1] = r0.rhobuf[1];
-        slot->ubuf = (B <= 64) ? c.take<double>(B * (m * 12 / 20)) : nullptr;       // (only the staged path uses it: small batches)
-    };
-    slot->rs_nsets = nsets; slot->last_tail = nullptr;
-    Carver sz(nullptr);
-    carve(sz);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&slot->rs), sz.off);
-    if (e != hipSuccess) { h->err = std::string("hipMalloc restart buffers: ") + hipGetErrorString(e); return SRBDQP_E_NOMEM; }
-    Carver cv(slot->rs);
-    carve(cv);
-    slot->rs_items = B; slot->rs_rows = m;
-    return SRBDQP_OK;
+    if (const int rc = tail_drain(h, slot->rtail)) return rc;
+    return carve_restart_sets(h, slot->rb, B, B * 20 * N, nsets, nsets > 1 ? 4 : 0, B <= 64 ? B * 12 * N : 0);   // (ubuf: only the staged path uses it: small batches)
 }
 
 int ensure_tail_lists(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStream_t st, size_t B, int rmax) {
@@ -1114,7 +1167,7 @@ int flush_slot(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStream_t st
 // THAT pass -- and continues from its own (x, y), every other workgroup leaves at once.  No selection kernel and no list between the passes: a one-workgroup kernel
 // queued behind a chip-filling launch of another stream waits ~150 us for its turn at the dispatcher (rocprofv3 timeline, round 2), which cost more than the
 // pass itself.  last: no further pass may follow (p = rcount, or the cap on the total comes first: oracle solve_with_restart).  rho: the two buffers through
-// which the rho of a pass reaches the one behind it.  Every multi-pass solve builds its passes here; the callers add only what is theirs.
+// which the rho of a pass reaches the one behind it.  Every multi-pass solve builds its passes here (run_restart_passes, and the staged call's host-driven loop).
 struct Pass { KArgs a; bool last; };
 Pass restart_pass(const KArgs& a1, int p, int rcount, int max_iter, double* const rho[2]) {
     const int every = a1.max_iter;
@@ -1132,6 +1185,32 @@ Pass restart_pass(const KArgs& a1, int p, int rcount, int max_iter, double* cons
     a2.rho_qp = (p == 1) ? a1.rho_qp : rho[p % 2];
     a2.rho_out = last ? nullptr : rho[(p + 1) % 2];
     return {a2, last};
+}
+
+// The first pass of such a solve with the arguments a: capped at the restart period, its maxima into the set, and the set's y / status where the caller passes none
+// (the pass behind it warm-starts from them).
+KArgs first_pass_args(const KArgs& a, int restart, const RestartSet& set) {
+    KArgs a1 = a;
+    a1.max_iter = restart;
+    a1.resid_out = set.resid;
+    if (!a1.y_out) { a1.y_out = set.ybuf; a1.y_capped_only = 1; }
+    if (!a1.status) a1.status = set.stbuf;
+    return a1;
+}
+
+// ... and the passes behind it, enqueued on st: launch_pass(pass, p, st) adds what is its owner's and launches pass p.  What differs between the owners:
+//  * batch, deferred (solve_deferred_passes): the list of QPs the pass before left at its cap is the dispatch order -- working workgroups first;
+//  * ragged (ragged_device_impl): the bucket's whole grid again through launch_wrench on the bucket's handle -- perm holds the bucket's members there;
+//  * batch, in the caller's stream (solve_device_impl): the whole grid again, the completion word on the last pass;
+//  * the staged call is host-driven (srbdqp_solve_staged_f64): its first pass writes u_dev, and a pass follows only when a status asks for it -- its own loop.
+template <class LaunchPass>
+int run_restart_passes(const KArgs& a1, int rcount, int max_iter, const RestartSet& set, hipStream_t st, LaunchPass&& launch_pass) {
+    for (int p = 1; p <= rcount; ++p) {
+        Pass pass = restart_pass(a1, p, rcount, max_iter, set.rho);
+        const int rc = launch_pass(pass, p, st);
+        if (rc != SRBDQP_OK || pass.last) return rc;
+    }
+    return SRBDQP_OK;
 }
 
 // the launch publishes the completion word with the handle's current sequence number
@@ -1313,7 +1392,7 @@ int quiesce_all_streams(srbdqp_handle* h) {
     for (auto& sl : h->slots) {
         if (!sl.used) continue;
         HIP_TRY(h, hipStreamSynchronize(sl.st));
-        if (sl.tail_st) HIP_TRY(h, hipStreamSynchronize(sl.tail_st));
+        if (sl.rtail.st) HIP_TRY(h, hipStreamSynchronize(sl.rtail.st));
     }
     return SRBDQP_OK;
 }
@@ -1473,11 +1552,10 @@ int srbdqp_destroy(srbdqp_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->ws) (void)hipFree(h->ws);
     for (auto& sl : h->slots) {
-        if (sl.perm) (void)hipFree(sl.perm); if (sl.ws) (void)hipFree(sl.ws); if (sl.rs) (void)hipFree(sl.rs);
+        tail_destroy(sl.rtail);                          // (waits for its last pass: before the sets go)
+        if (sl.perm) (void)hipFree(sl.perm); if (sl.ws) (void)hipFree(sl.ws); if (sl.rb.mem) (void)hipFree(sl.rb.mem);
         if (sl.tail) (void)hipFree(sl.tail); if (sl.tail_cnt) (void)hipFree(sl.tail_cnt);
-        if (sl.tail_st) { (void)hipStreamSynchronize(sl.tail_st); (void)hipStreamDestroy(sl.tail_st); }
         if (sl.ev_main) (void)hipEventDestroy(sl.ev_main);
-        for (auto& r : sl.rsets) if (r.ev_tail) (void)hipEventDestroy(r.ev_tail);
     }
     if (h->done_count) (void)hipFree(h->done_count);
     h->robots.release(); h->weights.release(); h->normals.release(); h->ext.release();
@@ -1539,7 +1617,7 @@ int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32
         bool capped = false;
         for (int32_t q = 0; q < B; ++q) capped |= (h->stage_h.status[q] == SRBDQP_MAX_ITER);
         if (!capped) break;
-        Pass pass = restart_pass(lazy.a1, p, lazy.rcount, h->cfg.max_iter, lazy.slot->rhobuf);
+        Pass pass = restart_pass(lazy.a1, p, lazy.rcount, h->cfg.max_iter, lazy.set->rho);
         if (c.signal) { next_seq(h); signal_args(h, pass.a); }
         rc = launch(h, c, pass.a, h->stream, 2);            // (with the first pass's Call: the same kernel)
         if (rc != SRBDQP_OK) return rc;
@@ -1681,7 +1759,8 @@ int srbdqp_flush(srbdqp_handle* h, void* stream) {
     for (auto& sl : h->slots) {
         if (!sl.used) continue;
         if (stream && sl.st != reinterpret_cast<hipStream_t>(stream)) continue;
-        if (sl.last_tail) { HIP_TRY(h, hipStreamWaitEvent(sl.st, sl.last_tail, 0)); sl.last_tail = nullptr; }   // restart passes on the slot's tail stream
+        if (const int rc = tail_join(h, sl.rtail, sl.st)) return rc;              // restart passes on the slot's tail stream
+        sl.rtail.last = nullptr;
         if (!sl.tail_live) continue;
         const int rc = flush_slot(h, &sl, sl.st);
         if (rc != SRBDQP_OK) return rc;
@@ -1694,7 +1773,8 @@ int srbdqp_synchronize(srbdqp_handle* h) {
     HIP_TRY(h, hipSetDevice(h->cfg.device));       // (the flush below launches a kernel: a thread that drives several devices may have another one current)
     for (auto& sl : h->slots) {                    // deferred tails of the handle's own stream are part of "everything enqueued"
         if (!sl.used || sl.st != h->stream) continue;
-        if (sl.last_tail) { HIP_TRY(h, hipStreamWaitEvent(sl.st, sl.last_tail, 0)); sl.last_tail = nullptr; }
+        if (const int rc = tail_join(h, sl.rtail, sl.st)) return rc;
+        sl.rtail.last = nullptr;
         if (sl.tail_live) { const int rc = flush_slot(h, &sl, sl.st); if (rc != SRBDQP_OK) return rc; }
     }
     const int rq = aql_quiesce(h);
@@ -1733,41 +1813,27 @@ namespace {
 int solve_deferred_passes(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t lst, int restart, int rcount) {
     auto* slot = stream_slot(h, lst);
     if (!slot) return SRBDQP_E_INVALID;
-    const size_t m = 20 * (size_t)h->cfg.horizon;
-    int rc = ensure_restart_buffers(h, slot, lst, (size_t)a.B, m, 3);
-    if (rc != SRBDQP_OK) return rc;
-    if (!slot->tail_st) {
-        int least = 0, greatest = 0;
-        HIP_TRY(h, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(h, hipStreamCreateWithPriority(&slot->tail_st, hipStreamNonBlocking, greatest));
+    if (const int rc = ensure_restart_buffers(h, slot, lst, (size_t)a.B, kRestartSets)) return rc;
+    Tail& tail = slot->rtail;
+    if (!tail.st) {
+        if (const int rc = tail_create(h, tail)) return rc;
         HIP_TRY(h, hipEventCreateWithFlags(&slot->ev_main, hipEventDisableTiming));
-        for (auto& r : slot->rsets) HIP_TRY(h, hipEventCreateWithFlags(&r.ev_tail, hipEventDisableTiming));
     }
-    auto& set = slot->rsets[slot->rs_k++ % 3];
-    if (set.ev_used) HIP_TRY(h, hipStreamWaitEvent(lst, set.ev_tail, 0));      // the set's last user (three solves ago) has finished its passes
+    const int k = next_set(slot->rs_k, kRestartSets);
+    const RestartSet& set = slot->rb.set[k];
+    if (const int rc = tail_wait(h, tail, k, lst)) return rc;   // the set's last user (three solves ago) has finished its passes
     HIP_TRY(h, hipMemsetAsync(set.cnt, 0, 16 * sizeof(int32_t), lst));
-    KArgs a1 = a;
-    a1.max_iter = restart;
-    a1.resid_out = set.resid;
-    if (!a1.y_out) { a1.y_out = set.ybuf; a1.y_capped_only = 1; }
-    if (!a1.status) a1.status = set.stbuf;
+    KArgs a1 = first_pass_args(a, restart, set);
     a1.cap_list = set.list[0]; a1.cap_count = set.cnt;
-    rc = launch(h, c, a1, lst, 1);
-    if (rc != SRBDQP_OK) return rc;
+    if (const int rc = launch(h, c, a1, lst, 1)) return rc;
     HIP_TRY(h, hipEventRecord(slot->ev_main, lst));
-    HIP_TRY(h, hipStreamWaitEvent(slot->tail_st, slot->ev_main, 0));
-    for (int p = 1; p <= rcount; ++p) {
-        Pass pass = restart_pass(a1, p, rcount, h->cfg.max_iter, set.rhobuf);
+    HIP_TRY(h, hipStreamWaitEvent(tail.st, slot->ev_main, 0));
+    const int rc = run_restart_passes(a1, rcount, h->cfg.max_iter, set, tail.st, [&](Pass& pass, int p, hipStream_t st) {
         pass.a.perm = set.list[p - 1]; pass.a.count_ptr = set.cnt + (p - 1);
         pass.a.cap_list = pass.last ? nullptr : set.list[p]; pass.a.cap_count = pass.last ? nullptr : set.cnt + p;
-        rc = launch(h, c, pass.a, slot->tail_st, 2);
-        if (rc != SRBDQP_OK) return rc;
-        if (pass.last) break;
-    }
-    HIP_TRY(h, hipEventRecord(set.ev_tail, slot->tail_st));
-    set.ev_used = true;
-    slot->last_tail = set.ev_tail;
-    return SRBDQP_OK;
+        return launch(h, c, pass.a, st, 2);
+    });
+    return rc != SRBDQP_OK ? rc : tail_close(h, tail, k);
 }
 
 // common body of the device-buffer entry points; the element type of the caller's buffers is c.f32 ? float : double
@@ -1814,30 +1880,21 @@ int solve_device_impl(srbdqp_handle* h, const Call& c, int32_t B, const void* x0
     // ---- several passes: cap the first at rho_restart_iter, re-balance rho for the QPs that reach it, continue those (up to rcount times)
     auto* slot = stream_slot(h, lst);
     if (!slot) return SRBDQP_E_INVALID;
-    const size_t m = 20 * (size_t)h->cfg.horizon;
-    int rc = ensure_restart_buffers(h, slot, lst, (size_t)B, m);
-    if (rc != SRBDQP_OK) return rc;
-    // (a handle with SRBDQP_FLAG_DEFER_TAIL whose device-buffer solves ran their passes on the tail stream: slot->resid / ybuf / stbuf / rhobuf alias set 0 of the
-    //  rotation, and a staged or completion-word solve on the same stream comes through here -- it must not overwrite what a tail pass still reads)
-    if (slot->rs_nsets > 1)
-        for (auto& r : slot->rsets) if (r.ev_used) HIP_TRY(h, hipStreamWaitEvent(lst, r.ev_tail, 0));
-    KArgs a1 = a;
-    a1.max_iter = restart;
-    a1.resid_out = slot->resid;
-    if (!a1.y_out) { a1.y_out = slot->ybuf; a1.y_capped_only = 1; }
-    if (!a1.status) a1.status = slot->stbuf;
+    if (const int rc = ensure_restart_buffers(h, slot, lst, (size_t)B)) return rc;
+    // in the caller's stream: set 0 -- on a handle with SRBDQP_FLAG_DEFER_TAIL (a staged or completion-word solve comes through here) behind the passes of the
+    // deferred solve that used it last, as that path does: it must not overwrite what a tail pass still reads
+    const RestartSet& set = slot->rb.set[0];
+    if (const int rc = tail_wait(h, slot->rtail, 0, lst)) return rc;
+    KArgs a1 = first_pass_args(a, restart, set);
     if (!c.lazy) { a1.done_flag = nullptr; a1.done_count = nullptr; }
-    if (c.lazy && slot->ubuf && !c.f32) a1.u_dev = slot->ubuf;   // (the staged arrays are host memory: the pass behind this one reads its warm start on the device)
-    rc = launch(h, c, a1, lst, c.lazy ? 0 : 1);
-    if (c.lazy) { c.lazy->a1 = a1; c.lazy->rcount = rcount; c.lazy->slot = slot; c.lazy->pending = (rc == SRBDQP_OK); }   // (staged path: the host looks at status[] before a second pass)
+    if (c.lazy && slot->rb.ubuf && !c.f32) a1.u_dev = slot->rb.ubuf;   // (the staged arrays are host memory: the pass behind this one reads its warm start on the device)
+    const int rc = launch(h, c, a1, lst, c.lazy ? 0 : 1);
+    if (c.lazy) { c.lazy->a1 = a1; c.lazy->rcount = rcount; c.lazy->set = &set; c.lazy->pending = (rc == SRBDQP_OK); }   // (staged path: the host looks at status[] before a second pass)
     if (rc != SRBDQP_OK || c.lazy) return rc;
-    for (int p = 1; p <= rcount; ++p) {
-        Pass pass = restart_pass(a1, p, rcount, h->cfg.max_iter, slot->rhobuf);
+    return run_restart_passes(a1, rcount, h->cfg.max_iter, set, lst, [&](Pass& pass, int, hipStream_t st) {
         if (pass.last && a.done_flag) signal_args(h, pass.a);
-        rc = launch(h, c, pass.a, lst, 2);
-        if (rc != SRBDQP_OK || pass.last) break;
-    }
-    return rc;
+        return launch(h, c, pass.a, st, 2);
+    });
 }
 
 // common body of the host-buffer entry points (esz = sizeof the caller's element type)
@@ -1948,7 +2005,7 @@ int srbdqp_assemble_f64(srbdqp_handle* h, int32_t B, const double* x0, const dou
     hipStream_t st = h->stream;
     // compact K, q, map -> full-size P, q in the original variable order (on the host: bookkeeping, not the hot path)
     std::vector<double> K(n * n), qc(n), mp(m);
-    const double rho = h->cfg.rho, aa = 4.0 * h->cfg.mu * h->cfg.mu + h->cfg.rho_fz_scale, sc = h->cfg.force_scale;
+    const double rho = h->cfg.rho, aa = 4.0 * h->cfg.mu * h->cfg.mu + h->cfg.rho_fz_scale;
     for (size_t q = 0; q < b; ++q) {
         HIP_TRY(h, hipMemcpyAsync(K.data(), dP + q * n * n, n * n * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipMemcpyAsync(qc.data(), dq + q * n, n * 8, hipMemcpyDeviceToHost, st));
@@ -1987,7 +2044,6 @@ int srbdqp_assemble_f64(srbdqp_handle* h, int32_t B, const double* x0, const dou
             l_out[q * m + 5 * gc + 4] = mp[4 * N + e];
             ub_out[q * m + 5 * gc + 4] = mp[8 * N + e];
         }
-        (void)sc;
     }
     return SRBDQP_OK;
 }
@@ -2024,21 +2080,14 @@ struct srbdqp_ragged {
     hipEvent_t ev_in = nullptr;
     bool ev_in_pending = false;
     int device = 0;
-    int32_t *d_perm = nullptr, *d_off = nullptr, *h_perm = nullptr, *h_off = nullptr;   // device arrays + pinned mirrors
-    size_t cap = 0;
-    // rho restart of the long-horizon buckets: fp32 maxima of a QP's last check [cap][4], status when the caller passes none
-    // [cap], duals of the first pass [row_cap][20] (the second pass warm-starts from them)
-    float* d_resid = nullptr; int32_t* d_status = nullptr; double* d_y = nullptr; size_t row_cap = 0;
-    double* d_rho = nullptr;                  // [2][cap]: the rho a restart pass ran its QPs with, for the pass behind it
-    // SRBDQP_FLAG_DEFER_TAIL: every array above exists kSets times (set = call number mod kSets) and the restart passes of a bucket run on the bucket's own tail
-    // stream behind its first pass, beside the next calls; a set is reused only behind the events that close its last user's passes
-    static constexpr int kSets = 3;
+    int32_t *h_perm = nullptr, *h_off = nullptr;   // pinned mirrors of a call's bucket permutation and row offsets [rb.items]
+    // The device arrays the calls of this object share, as a launch stream of a handle has them: restart sets of rb.items QPs and 20 dual doubles per horizon
+    // row, each with the call's index arrays as its two lists.  One set; under SRBDQP_FLAG_DEFER_TAIL kRestartSets in rotation (set = call number mod kRestartSets),
+    // and the restart passes of a bucket run on the bucket's own tail stream behind its first pass, beside the next calls.
+    RestartBufs rb;
     bool defer = false;
     unsigned long long call_k = 0;
-    std::vector<hipStream_t> tail_st;         // per bucket
-    std::vector<hipEvent_t> ev_tail;          // [kSets][nb]
-    std::vector<char> ev_tail_used;           // [kSets][nb]
-    std::vector<hipEvent_t> last_tail;        // per bucket: closes the passes of the last call that had any (srbdqp_ragged_flush), or null
+    std::vector<Tail> tails;                  // per bucket (defer only): its closing event per set, and the one srbdqp_ragged_flush waits for
     char* ws = nullptr; size_t ws_bytes = 0;  // host-buffer entry point: device copies of the caller's arrays
     hipStream_t stream = nullptr;             // ... and the stream its copies run on
     // per-QP robot records and cost weights in the caller's QP order (srbdqp_ragged_set_robots, srbdqp_ragged_set_weights / _device), forwarded to every bucket
@@ -2080,20 +2129,8 @@ int srbdqp_ragged_create(const srbdqp_config* cfg, const int32_t* horizons, int3
     if (hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) return fail(SRBDQP_E_HIP, "hipStreamCreate");
     r->defer = (cfg->flags & SRBDQP_FLAG_DEFER_TAIL) != 0;
     if (r->defer) {
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return fail(SRBDQP_E_HIP, "hipDeviceGetStreamPriorityRange");
-        for (int i = 0; i < n_horizons; ++i) {
-            hipStream_t ts = nullptr;
-            if (hipStreamCreateWithPriority(&ts, hipStreamNonBlocking, greatest) != hipSuccess) return fail(SRBDQP_E_HIP, "hipStreamCreate");
-            r->tail_st.push_back(ts);
-            r->last_tail.push_back(nullptr);
-        }
-        for (int i = 0; i < srbdqp_ragged::kSets * n_horizons; ++i) {
-            hipEvent_t ev = nullptr;
-            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return fail(SRBDQP_E_HIP, "hipEventCreate");
-            r->ev_tail.push_back(ev);
-            r->ev_tail_used.push_back(0);
-        }
+        r->tails.resize((size_t)n_horizons);
+        for (auto& t : r->tails) if (const int rc = tail_create(r, t)) return fail(rc, r->err);
     }
     *out = r;
     return SRBDQP_OK;
@@ -2103,17 +2140,11 @@ int srbdqp_ragged_destroy(srbdqp_ragged* r) {
     if (!r) return SRBDQP_OK;
     (void)hipSetDevice(r->device);
     for (auto* h : r->hs) srbdqp_destroy(h);
-    for (auto ts : r->tail_st) if (ts) { (void)hipStreamSynchronize(ts); (void)hipStreamDestroy(ts); }
-    for (auto ev : r->ev_tail) if (ev) (void)hipEventDestroy(ev);
+    for (auto& t : r->tails) tail_destroy(t);
     for (auto ev : r->ev_out) if (ev) (void)hipEventDestroy(ev);
     if (r->ev_in) (void)hipEventDestroy(r->ev_in);
     if (r->stream) { (void)hipStreamSynchronize(r->stream); (void)hipStreamDestroy(r->stream); }
-    if (r->d_perm) (void)hipFree(r->d_perm);
-    if (r->d_off) (void)hipFree(r->d_off);
-    if (r->d_resid) (void)hipFree(r->d_resid);
-    if (r->d_status) (void)hipFree(r->d_status);
-    if (r->d_rho) (void)hipFree(r->d_rho);
-    if (r->d_y) (void)hipFree(r->d_y);
+    if (r->rb.mem) (void)hipFree(r->rb.mem);
     if (r->h_perm) (void)hipHostFree(r->h_perm);
     if (r->h_off) (void)hipHostFree(r->h_off);
     if (r->ws) (void)hipFree(r->ws);
@@ -2160,34 +2191,7 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
     HIP_TRY(r, hipSetDevice(r->device));
     hipStream_t sin = stream ? reinterpret_cast<hipStream_t>(stream) : r->stream;
     const size_t nb = r->hs.size();
-    if ((size_t)B > r->cap) {   // (re)allocate the index arrays: the only point that waits, and only for earlier solves of this object
-        for (auto* h : r->hs) HIP_TRY(r, hipStreamSynchronize(h->stream));
-        for (auto ts : r->tail_st) HIP_TRY(r, hipStreamSynchronize(ts));
-        HIP_TRY(r, hipStreamSynchronize(sin));
-        std::fill(r->ev_tail_used.begin(), r->ev_tail_used.end(), 0);
-        if (r->d_perm) (void)hipFree(r->d_perm);
-        if (r->d_off) (void)hipFree(r->d_off);
-        if (r->h_perm) (void)hipHostFree(r->h_perm);
-        if (r->h_off) (void)hipHostFree(r->h_off);
-        r->d_perm = r->d_off = r->h_perm = r->h_off = nullptr; r->cap = 0;
-        const size_t want = (size_t)B + (size_t)B / 4 + 64;
-        const size_t ns = r->defer ? (size_t)srbdqp_ragged::kSets : 1;
-        HIP_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_perm), ns * want * 4));
-        HIP_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_off), ns * want * 4));
-        HIP_TRY(r, hipHostMalloc(reinterpret_cast<void**>(&r->h_perm), want * 4, hipHostMallocDefault));
-        HIP_TRY(r, hipHostMalloc(reinterpret_cast<void**>(&r->h_off), want * 4, hipHostMallocDefault));
-        if (r->d_resid) (void)hipFree(r->d_resid);
-        if (r->d_status) (void)hipFree(r->d_status);
-        if (r->d_rho) (void)hipFree(r->d_rho);
-        r->d_resid = nullptr; r->d_status = nullptr; r->d_rho = nullptr;
-        HIP_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_resid), ns * want * 16));
-        HIP_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_status), ns * want * 4));
-        HIP_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_rho), ns * 2 * want * sizeof(double)));
-        r->cap = want;
-        r->ev_in_pending = false;
-    }
-    if (r->ev_in_pending) HIP_TRY(r, hipEventSynchronize(r->ev_in));   // the previous call's index upload has left the pinned mirrors
-    // bucket permutation (counting sort by horizon) and the packed row offsets
+    // the bucket of every QP (counting sort by horizon) and the rows of the call
     std::vector<int> cnt(nb, 0), start(nb + 1, 0), which((size_t)B);
     long long rows = 0;
     for (int32_t b = 0; b < B; ++b) {
@@ -2196,37 +2200,45 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
         if (k < 0) { r->err = "N_per_qp holds a horizon this object was not created for"; return SRBDQP_E_INVALID; }
         which[(size_t)b] = k; ++cnt[(size_t)k];
         if (rows > 2000000000LL) { r->err = "more than 2^31 horizon rows in one call"; return SRBDQP_E_INVALID; }
-        r->h_off[b] = (int32_t)rows;
         rows += N_per_qp[b];
     }
     for (size_t i = 0; i < nb; ++i) start[i + 1] = start[i] + cnt[i];
     bool any_restart = false;
     for (size_t i = 0; i < nb; ++i) any_restart = any_restart || (cnt[i] > 0 && restart_iter_of(r->hs[i]) > 0);
-    if (any_restart && (size_t)rows > r->row_cap) {   // dual buffer of the restart (waits for earlier solves of this object only)
+    const int nsets = r->defer ? kRestartSets : 1;
+    const size_t duals = any_restart ? 20 * (size_t)rows : 0;                  // (the duals of a pass, for the one behind it: by rows, where everything else is by QPs)
+    if (!r->rb.fits((size_t)B, duals, nsets)) {
+        // more QPs or more rows than the sets hold: the only point that waits, and only for earlier solves of this object
         for (auto* h : r->hs) HIP_TRY(r, hipStreamSynchronize(h->stream));
-        for (auto ts : r->tail_st) HIP_TRY(r, hipStreamSynchronize(ts));
-        if (r->d_y) (void)hipFree(r->d_y);
-        r->d_y = nullptr; r->row_cap = 0;
-        const size_t want = (size_t)rows + (size_t)rows / 4 + 64;
-        HIP_TRY(r, hipMalloc(reinterpret_cast<void**>(&r->d_y), (r->defer ? (size_t)srbdqp_ragged::kSets : 1) * want * 20 * sizeof(double)));
-        r->row_cap = want;
+        for (auto& t : r->tails) if (const int rc = tail_drain(r, t)) return rc;
+        size_t items = r->rb.items;
+        if ((size_t)B > items) {                                                 // ... the pinned mirrors with them
+            HIP_TRY(r, hipStreamSynchronize(sin));
+            if (r->h_perm) (void)hipHostFree(r->h_perm);
+            if (r->h_off) (void)hipHostFree(r->h_off);
+            r->h_perm = r->h_off = nullptr; r->rb.items = 0;
+            items = (size_t)B + (size_t)B / 4 + 64;
+            HIP_TRY(r, hipHostMalloc(reinterpret_cast<void**>(&r->h_perm), items * 4, hipHostMallocDefault));
+            HIP_TRY(r, hipHostMalloc(reinterpret_cast<void**>(&r->h_off), items * 4, hipHostMallocDefault));
+            r->ev_in_pending = false;
+        }
+        const size_t want_duals = duals > r->rb.duals ? duals + duals / 4 + 64 * 20 : r->rb.duals;
+        if (const int rc = carve_restart_sets(r, r->rb, items, want_duals, nsets, 2, 0)) return rc;
     }
+    if (r->ev_in_pending) HIP_TRY(r, hipEventSynchronize(r->ev_in));   // the previous call's index upload has left the pinned mirrors
+    // the packed row offsets and the bucket permutation
+    int32_t row = 0;
+    for (int32_t b = 0; b < B; ++b) { r->h_off[b] = row; row += N_per_qp[b]; }
     std::vector<int> fill(start.begin(), start.end() - 1);
     for (int32_t b = 0; b < B; ++b) r->h_perm[fill[(size_t)which[(size_t)b]]++] = b;
     // the index arrays (and the restart buffers) are shared by the calls of this object: the upload below must not overtake the
     // bucket kernels of an earlier call made on ANOTHER caller stream (calls on one stream are ordered through ev_out already)
     for (size_t i = 0; i < nb; ++i) if (r->ev_out_used[i]) HIP_TRY(r, hipStreamWaitEvent(sin, r->ev_out[i], 0));
-    // this call's set of the shared arrays (deferred restart passes: three in rotation; behind the passes of the set's last user)
-    const size_t set = r->defer ? (size_t)(r->call_k++ % srbdqp_ragged::kSets) : 0;
-    if (r->defer)
-        for (size_t i = 0; i < nb; ++i)
-            if (r->ev_tail_used[set * nb + i]) HIP_TRY(r, hipStreamWaitEvent(sin, r->ev_tail[set * nb + i], 0));
-    int32_t* const d_off = r->d_off + set * r->cap;
-    int32_t* const d_perm = r->d_perm + set * r->cap;
-    float* const d_resid = r->d_resid + set * r->cap * 4;
-    int32_t* const d_status = r->d_status + set * r->cap;
-    double* const d_rho = r->d_rho + set * 2 * r->cap;
-    double* const d_y = r->d_y ? r->d_y + set * r->row_cap * 20 : nullptr;
+    // this call's set of the shared arrays (deferred restart passes: three in rotation; behind the passes of the set's last user in every bucket)
+    const int k = next_set(r->call_k, nsets);
+    const RestartSet& set = r->rb.set[k];
+    for (auto& t : r->tails) if (const int rc = tail_wait(r, t, k, sin)) return rc;
+    int32_t *const d_perm = set.list[0], *const d_off = set.list[1];
     HIP_TRY(r, hipMemcpyAsync(d_off, r->h_off, (size_t)B * 4, hipMemcpyHostToDevice, sin));
     HIP_TRY(r, hipMemcpyAsync(d_perm, r->h_perm, (size_t)B * 4, hipMemcpyHostToDevice, sin));
     HIP_TRY(r, hipEventRecord(r->ev_in, sin));
@@ -2234,7 +2246,6 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
     // one launch per non-empty bucket, each on its engine's own stream behind the upload; the caller's stream then waits for all
     Call c;
     c.f32 = f32;
-    double* const rho[2] = {d_rho, d_rho + r->cap};
     for (size_t i = 0; i < nb; ++i) {
         if (cnt[i] == 0) continue;
         srbdqp_handle* bh = r->hs[i];
@@ -2247,40 +2258,26 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
         a.perm = d_perm + start[i]; a.row_off = d_off;
         int rcount = 1;
         const int restart = restart_iter_of(bh, &rcount);
-        int rc;
-        if (restart > 0) {   // several passes over the bucket, as srbdqp_solve_batch_* does (the later ones select their QPs in-kernel)
-            KArgs a1 = a;
-            a1.max_iter = restart; a1.resid_out = d_resid;
-            if (!a1.y_out) { a1.y_out = d_y; a1.y_capped_only = 1; }   // (a later pass warm-starts from the duals of the pass before it)
-            if (!a1.status) a1.status = d_status;
-            rc = launch_wrench(bh, c, a1, bs);
-            hipStream_t ps = bs;                                          // the stream the restart passes run on
-            if (r->defer && rc == SRBDQP_OK) {
-                // ... the bucket's tail stream, behind its first pass: the caller's stream waits for the first pass only, the passes run beside what it enqueues next
-                HIP_TRY(r, hipEventRecord(r->ev_out[i], bs));
-                r->ev_out_used[i] = 1;
-                HIP_TRY(r, hipStreamWaitEvent(sin, r->ev_out[i], 0));
-                ps = r->tail_st[i];
-                HIP_TRY(r, hipStreamWaitEvent(ps, r->ev_out[i], 0));
+        // several passes over the bucket, as srbdqp_solve_batch_* does (the later ones select their QPs in-kernel), or one.  Under the defer flag the caller's
+        // stream waits for the first pass only: the others run on the bucket's tail stream behind it, beside what the caller enqueues next
+        const KArgs a1 = restart > 0 ? first_pass_args(a, restart, set) : a;
+        const bool deferred = r->defer && restart > 0;
+        auto passes = [&](hipStream_t ps) {
+            return run_restart_passes(a1, rcount, bh->cfg.max_iter, set, ps, [&](Pass& pass, int, hipStream_t st) { return launch_wrench(bh, c, pass.a, st); });
+        };
+        int rc = launch_wrench(bh, c, a1, bs);
+        if (rc == SRBDQP_OK && restart > 0 && !deferred) rc = passes(bs);
+        if (rc == SRBDQP_OK) {
+            HIP_TRY(r, hipEventRecord(r->ev_out[i], bs));
+            r->ev_out_used[i] = 1;
+            HIP_TRY(r, hipStreamWaitEvent(sin, r->ev_out[i], 0));
+            if (deferred) {
+                HIP_TRY(r, hipStreamWaitEvent(r->tails[i].st, r->ev_out[i], 0));
+                rc = passes(r->tails[i].st);
             }
-            for (int p = 1; rc == SRBDQP_OK && p <= rcount; ++p) {        // (restart_pass, on the ragged object's own buffers)
-                const Pass pass = restart_pass(a1, p, rcount, bh->cfg.max_iter, rho);
-                rc = launch_wrench(bh, c, pass.a, ps);
-                if (pass.last) break;
-            }
-            if (r->defer && rc == SRBDQP_OK) {
-                HIP_TRY(r, hipEventRecord(r->ev_tail[set * nb + i], ps));
-                r->ev_tail_used[set * nb + i] = 1;
-                r->last_tail[i] = r->ev_tail[set * nb + i];
-                continue;                                                 // (ev_out was recorded behind the first pass)
-            }
-        } else {
-            rc = launch_wrench(bh, c, a, bs);
         }
         if (rc != SRBDQP_OK) { r->err = std::string("bucket N=") + std::to_string(r->horizons[i]) + ": " + bh->err; return rc; }
-        HIP_TRY(r, hipEventRecord(r->ev_out[i], bs));
-        r->ev_out_used[i] = 1;
-        HIP_TRY(r, hipStreamWaitEvent(sin, r->ev_out[i], 0));
+        if (deferred) if (const int rt = tail_close(r, r->tails[i], k)) return rt;
     }
     return SRBDQP_OK;
 }
@@ -2319,7 +2316,7 @@ int quiesce(srbdqp_handle* h) { return quiesce_all_streams(h); }
 // streams, the object's own stream
 int quiesce(srbdqp_ragged* r) {
     for (auto* h : r->hs) { const int rq = quiesce_all_streams(h); if (rq != SRBDQP_OK) { r->err = h->err; return rq; } }
-    for (auto ts : r->tail_st) HIP_TRY(r, hipStreamSynchronize(ts));
+    for (auto& t : r->tails) HIP_TRY(r, hipStreamSynchronize(t.st));
     HIP_TRY(r, hipStreamSynchronize(r->stream));
     return SRBDQP_OK;
 }
@@ -2411,8 +2408,7 @@ int srbdqp_ragged_flush(srbdqp_ragged* r, void* stream) {
     hipStream_t sin = stream ? reinterpret_cast<hipStream_t>(stream) : r->stream;
     // (the events stay: they are re-recorded by every call, waiting for a completed one costs nothing, and a caller that issued calls on two streams
     //  flushes each of them -- a flush of the other stream must still find the passes that write ITS outputs)
-    for (auto& ev : r->last_tail)
-        if (ev) HIP_TRY(r, hipStreamWaitEvent(sin, ev, 0));
+    for (auto& t : r->tails) if (const int rc = tail_join(r, t, sin)) return rc;
     return SRBDQP_OK;
 }
 

@@ -1146,6 +1146,22 @@ def test_deferred_restart_passes_on_the_tail_stream(torch_first, built_lib, N, s
         assert torch.equal(o["u"], r["u"]) and torch.equal(o["x"], r["x"]), j
 
 
+def _ragged_fleet(dev, HZ, B, j):
+    """B QPs with horizons drawn from HZ, packed row by row in the caller's order, on the device (draw j)."""
+    import torch
+    rng = np.random.default_rng(50 + j)
+    Nq = rng.choice(HZ, size=B).astype(np.int32)
+    rows = int(Nq.sum()); off = np.concatenate([[0], np.cumsum(Nq)])
+    x0 = np.empty((B, 13)); xr = np.empty((rows, 13)); ft = np.empty((rows, 12)); ct = np.empty((rows, 4), np.uint8)
+    for N in HZ:
+        idx = np.where(Nq == N)[0]
+        a, b_, c, d = orc.synthetic_batch(len(idx), N, seed=60 + N + j, schedule="mixed")
+        x0[idx] = a
+        dst = (off[idx][:, None] + np.arange(N)[None, :]).reshape(-1)
+        xr[dst] = b_.reshape(-1, 13); ft[dst] = c.reshape(-1, 12); ct[dst] = d.reshape(-1, 4)
+    return dict(B=B, Nq=Nq, rows=rows, d=[torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (x0, xr, ft, ct)])
+
+
 def test_ragged_restart_passes_on_the_tail_streams(torch_first, built_lib):
     """srbdqp_ragged_create with SRBDQP_FLAG_DEFER_TAIL: the restart passes of every bucket run on the bucket's tail stream beside the next calls (three sets of the
     shared arrays in rotation); after srbdqp_ragged_flush() a pipeline of six calls (two fleets alternating, each with its own outputs) equals the same calls with
@@ -1154,20 +1170,7 @@ def test_ragged_restart_passes_on_the_tail_streams(torch_first, built_lib):
     from g1_locomotion_amd import RaggedMPC, _lib
     dev = torch.device("cuda", 0)
     HZ = (8, 12, 16, 24)
-    fleets = []
-    for j in range(2):
-        rng = np.random.default_rng(50 + j)
-        B = 600 + 100 * j
-        Nq = rng.choice(HZ, size=B).astype(np.int32)
-        rows = int(Nq.sum()); off = np.concatenate([[0], np.cumsum(Nq)])
-        x0 = np.empty((B, 13)); xr = np.empty((rows, 13)); ft = np.empty((rows, 12)); ct = np.empty((rows, 4), np.uint8)
-        for N in HZ:
-            idx = np.where(Nq == N)[0]
-            a, b_, c, d = orc.synthetic_batch(len(idx), N, seed=60 + N + j, schedule="mixed")
-            x0[idx] = a
-            dst = (off[idx][:, None] + np.arange(N)[None, :]).reshape(-1)
-            xr[dst] = b_.reshape(-1, 13); ft[dst] = c.reshape(-1, 12); ct[dst] = d.reshape(-1, 4)
-        fleets.append(dict(B=B, Nq=Nq, rows=rows, d=[torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (x0, xr, ft, ct)]))
+    fleets = [_ragged_fleet(dev, HZ, 600 + 100 * j, j) for j in range(2)]
 
     def run(flags):
         outs = []
@@ -1189,6 +1192,66 @@ def test_ragged_restart_passes_on_the_tail_streams(torch_first, built_lib):
     assert sum(int((o["it"] > 40).sum()) for o in ref) >= 20
     for k, (o, r) in enumerate(zip(got, ref)):
         assert torch.equal(o["st"], r["st"]) and torch.equal(o["it"], r["it"]) and torch.equal(o["u"], r["u"]) and torch.equal(o["x"], r["x"]), k
+
+
+def _assert_deferred_equals_in_stream(torch, ref, got, mark):
+    """every call of a DEFER_TAIL pipeline equals the same call with flags = 0, and the case is honest: at least a quarter of each reference call's QPs pass the mark"""
+    for j, (o, r) in enumerate(zip(got, ref)):
+        assert 4 * int((r["it"] > mark).sum()) >= r["it"].numel(), (j, int((r["it"] > mark).sum()), r["it"].numel())
+        assert torch.equal(o["st"], r["st"]) and torch.equal(o["it"], r["it"]), j
+        assert torch.equal(o["u"], r["u"]) and torch.equal(o["x"], r["x"]), j
+
+
+def test_deferred_restart_passes_survive_growing_buffers(torch_first, built_lib):
+    """SRBDQP_FLAG_DEFER_TAIL, calls of 48, 160 and 48 QPs on one stream without a wait in between: the second call outgrows the restart buffers of the first
+    while the first call's passes may still be pending on the tail stream, the third reuses the grown buffers.  After one flush every output equals the same
+    pipeline with the passes on the caller's stream."""
+    torch = torch_first
+    from g1_locomotion_amd import BatchMPC, _lib
+    dev = torch.device("cuda", 0)
+    N, sizes = 10, (48, 160, 48)
+    batches = [orc.synthetic_batch(B, N, seed=2000 + 7 * j, schedule="mixed") for j, B in enumerate(sizes)]
+    d_in = [[torch.from_numpy(v).to(dev) for v in hb] for hb in batches]
+
+    def run(flags):
+        outs = [dict(u=torch.zeros((B, N, 12), dtype=torch.float64, device=dev), x=torch.zeros((B, N + 1, 13), dtype=torch.float64, device=dev),
+                     st=torch.full((B,), -77, dtype=torch.int32, device=dev), it=torch.zeros(B, dtype=torch.int32, device=dev)) for B in sizes]
+        s0 = torch.cuda.Stream(device=dev)
+        with BatchMPC(horizon=N, flags=flags, max_contacts_per_step=4, rho_restart_iter=25, rho_restart_count=2) as eng:
+            for B, d, o in zip(sizes, d_in, outs):
+                eng.solve_device(B, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), o["u"].data_ptr(), x_out=o["x"].data_ptr(),
+                                 status=o["st"].data_ptr(), iters=o["it"].data_ptr(), stream=s0.cuda_stream)
+            eng.flush()
+            s0.synchronize()
+        return outs
+    _assert_deferred_equals_in_stream(torch, run(0), run(_lib.FLAG_DEFER_TAIL), 25)
+
+
+def test_ragged_restart_passes_survive_growing_buffers(torch_first, built_lib):
+    """The ragged twin: calls of 48, 160 and 48 QPs over the horizons (8, 12).  The first call reserves 48 + 12 + 64 = 124 QPs, so the second re-allocates the
+    index arrays, the restart buffers and the dual buffer while the first call's passes may still be pending on the buckets' tail streams."""
+    torch = torch_first
+    from g1_locomotion_amd import RaggedMPC, _lib
+    dev = torch.device("cuda", 0)
+    HZ = (8, 12)
+    fleets = [_ragged_fleet(dev, HZ, B, j) for j, B in enumerate((48, 160, 48))]
+
+    def run(flags):
+        outs = []
+        s0 = torch.cuda.Stream(device=dev)
+        eng = RaggedMPC(horizons=HZ, rho_restart_iter=25, rho_restart_count=2, **({"flags": flags} if flags else {}))
+        for f in fleets:
+            o = dict(u=torch.zeros((f["rows"], 12), dtype=torch.float64, device=dev), x=torch.zeros((f["rows"] + f["B"], 13), dtype=torch.float64, device=dev),
+                     st=torch.zeros(f["B"], dtype=torch.int32, device=dev), it=torch.zeros(f["B"], dtype=torch.int32, device=dev))
+            d = f["d"]
+            eng.solve_device(f["B"], f["Nq"], d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), o["u"].data_ptr(), x_out=o["x"].data_ptr(),
+                             status=o["st"].data_ptr(), iters=o["it"].data_ptr(), stream=s0.cuda_stream)
+            outs.append(o)
+        eng.flush(s0.cuda_stream)
+        s0.synchronize()
+        eng.close()
+        return outs
+    _assert_deferred_equals_in_stream(torch, run(0), run(_lib.FLAG_DEFER_TAIL), 25)
 
 
 @pytest.mark.parametrize("schedule,B,mcs", [("single", 1024, 2), ("mixed", 1024, 4), ("single", 64, 2)])
