@@ -125,7 +125,7 @@ struct srbdqp_handle {
     int32_t done_seq = 0;
     bool done_cs = false;          // the last launch publishes its completion word with the checksum of its outputs (KArgs::done_cs): wait_done() verifies it
     bool done_cs_x = false;        // ... which cover x_out
-    int32_t prepared_B = 0; int prepared_maxs = 4; bool prepared_pcom = false;   // two-phase call: a set-up is pending
+    int32_t prepared_B = 0; int prepared_maxs = 4; bool prepared_pcom = false;   // two-phase call: a set-up is pending, on the instantiation plan_two_phase chose
     // kernels whose dynamic-LDS limit has been raised on this handle's device (function attributes are per device, and a
     // process may hold handles on several)
     std::unordered_set<const void*> lds_attr_done;
@@ -224,16 +224,30 @@ struct Lazy {
     bool pending = false;          // the solve really was such a first pass (not: restarted in place, or no restart at all)
 };
 
-// what one call decides, on the caller's stack: every launch of the call -- restart passes included -- reads the same one, so a later pass chooses the
-// kernel the first one did
+// ---- which kernel a solve runs: a Plan, decided once per solve by plan_solve() (behind restart_iter_of) and executed by launch() and the launchers ----
+enum class Family { Wave, WaveDefer, Split, Compact, General };   // one wave per QP, ... with deferred tails, the split pipeline, the 4-wave compact kernel, the general kernel
+enum class Form { Plain, Lat, Live, RankAware, Robots, Weights, ExtWrench, Normals };   // General: any; Compact: Plain or Lat (the dump is a pass's a.mode == 1)
+// the rho restart of restart_iter_of: none, inside the kernel, further launches on the caller's stream (the staged call: started by the host), or off that stream
+// -- the next launch on it (WaveDefer) or a tail stream (solve_deferred_passes, the ragged buckets)
+enum class Restart { Off, InPlace, Launches, Deferred };
+struct Plan {
+    Family family = Family::General;
+    int maxs = 4;                  // the presolved families: the MAXS instantiation, 2 or 4 stance contacts per step
+    Form form = Form::Plain;
+    bool tile_classes = false;     // General, fp32: the first pass is split by tile precision
+    bool wave_setup = false;       // Split: the set-up with one wave per QP (not SRBDQP_FLAG_SETUP4, at most 64 presolved variables)
+    Restart restart = Restart::Off;
+};
+
+// what one call decides, on the caller's stack: every launch of the call -- restart passes included -- reads the same one, so a later pass runs the
+// kernel the first one did (plan)
 struct Call {
     bool f32 = false;              // the caller's buffers are float
-    int maxs = 4;                  // bound on the stance contacts per step the instantiation is chosen for
     bool staged = false;           // srbdqp_solve_staged_f64 (with or without the completion word)
-    int neff = 0;                  // ... with the largest number of presolved variables (3 x stance contacts) among its QPs
     bool signal = false;           // the launch publishes the completion word
     bool use_hint = false;         // the dispatch hint applies (it belongs to the device-buffer API)
     Lazy* lazy = nullptr;          // staged path: run only the first pass of a multi-pass solve and hand it back here
+    Plan plan;                     // plan_solve(h, c, B, ...), once the fields above are set
 };
 
 inline int maxs_or(const srbdqp_config& c, int fallback) { return c.max_contacts_per_step > 0 ? c.max_contacts_per_step : fallback; }
@@ -256,6 +270,11 @@ Contacts scan_contacts(const uint8_t* c, size_t B, size_t N, bool want_neff) {
         if (3 * na > r.neff) r.neff = 3 * na;
     }
     return r;
+}
+
+// the bound on the stance contacts per step of a batch whose flags the host sees: the config's, or the batch's own
+inline int host_maxs(const srbdqp_handle* h, const uint8_t* contact, size_t B) {
+    return h->cfg.max_contacts_per_step > 0 ? h->cfg.max_contacts_per_step : scan_contacts(contact, B, (size_t)h->cfg.horizon, false).maxs();
 }
 
 // grow a device buffer to at least `want` elements (its contents are not kept); `busy`: a stream that may still use the old one
@@ -386,58 +405,12 @@ int launch_kernel(srbdqp_handle* h, K kernel, const char* kname, dim3 grid, dim3
     return SRBDQP_OK;
 }
 
-// Batches of at least this many QPs of the small instantiations (<= 64 presolved variables) run with one wave per QP
-// (launch_wave); the staged (completion-word) path and the big instantiations use the 4-wave kernel.  Until round 4 the cross-over of the per-call time was 512
-// QPs; with the rho restart on at every batch size (in place on the one-wave kernel, one more launch per pass on the 4-wave one) the one-wave kernel is the
-// faster one at EVERY size (tools/threshold_probe.py, us per synchronised call, 4-wave / one-wave: B = 1 60 / 55, 32 67 / 61, 128 72 / 64, 256 163 / 149,
-// 512 238 / 192, 4096 483 / 289).
-constexpr int kSplitMinBatch = 1;
-
-// Batches of at least this many QPs with more than 2 stance contacts in a step go to the general kernel at N <= 10 too
-// (measured, tools/schedule_bench.py, 4096 QPs: N = 10 double support 13.5 M QP/s against 4.2 M on the 4-wave compact kernel,
-// mixed gait 13.9 M against 6.5 M); smaller ones stay on the 4-wave kernel (lowest latency).
-constexpr int kWrenchMinBatch = 512;      // re-measured in round 4 (uniform rho restart; tools/schedule_bench.py, M QP/s 4-wave / general): N = 10 mixed gait 256 QPs 1.72 / 1.63,
-                                          // 512 3.10 / 3.28, 768 3.98 / 4.67, 1024 4.63 / 6.06; double support 256 1.70 / 2.45, 512 2.61 / 4.28 (round 2: 768)
-constexpr int kTail1MaxBatch = 8;              // staged calls of up to this many QPs on <= 2 stance contacts per step: the 4-wave set-up + one-wave iteration kernel
-constexpr int kStagedWrenchMinVars = 60;   // staged call: presolved variables (3 per stance contact) above which the wrench-space kernel's low-latency
-                                          // instantiation wins (B = 1, N = 10: mixed gait, 72 variables, 74 us compact / 69 us; double support, 120, 107 / 69)
-constexpr int kWrenchMinBatchN20 = 256;   // N = 20: one workgroup per CU on the compact kernel, two on the general one
-
-// fp32 calls of at least this many QPs are split by tile precision (two launches + the classification kernel); smaller
-// ones run on fp64 tiles, where the third workgroup per CU would stay empty anyway.
-constexpr int kTileClassMinBatch = 512;
-
-// does a solve of B QPs on this handle go to the general kernel (srbdqp_wrench.hpp)?  launch() asks this.
-inline bool uses_wrench(const srbdqp_handle* h, const Call& c, int maxs, int B) {
-    const int N = h->cfg.horizon;
-    if (h->cfg.kernel == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || h->robots.dev || h->weights.dev || h->ext.dev || h->normals.dev || h->live_nstar) return true;   // (per-QP records, weights and wrenches, contact normals, a live horizon: only the general kernel reads them)
-    // N = 20 single support too, for batches: the general kernel holds 2 workgroups per CU there, the compact one 1
-    // (tools/schedule_bench.py, 16,384 QPs: 2.85 M QP/s against 1.95 M; at N = 12 / 16 the compact kernel wins, 7.1 / 4.9 M
-    // against 5.7 / 4.2 M)
-    if (N > 10) return maxs > 2 || (N == 20 && h->cfg.kernel == SRBDQP_KERNEL_AUTO && B >= kWrenchMinBatchN20 && !h->stamps && !c.staged);
-    // N <= 10 with more than 2 stance contacts in a step: batches (the 4-wave kernel wins up to two QPs per CU) AND the staged
-    // low-latency path -- the reference's own call feeds full double support on every step (run_simulation.py:100-101), where the
-    // wrench-space problem is 60 x 60 against the 120 x 120 dense K of the compact kernel (round 3, tools/latency_patterns.py:
-    // B = 1 double support p50 82 us against 112 us)
-    if (h->cfg.kernel != SRBDQP_KERNEL_AUTO || maxs <= 2 || h->stamps) return false;
-    // (the low-latency instantiation is one workgroup per CU, tuned and measured at B = 1: the same bound as the compact kernel's TAIL1 path)
-    return B >= kWrenchMinBatch || (c.staged && B <= kTail1MaxBatch && N >= 8 && c.neff > kStagedWrenchMinVars);
-}
-
-// does a solve of B QPs on this handle run on the one-wave kernel (launch_wave)?  launch_compact() and the restart plan (solve_device_impl) ask this.
-inline bool uses_wave(const srbdqp_handle* h, const Call& c, int maxs, int B, bool stamps, bool signalled) {
-    const int N = h->cfg.horizon, k = h->cfg.kernel;
-    if (N > 10 || !(N == 4 || maxs <= 2) || uses_wrench(h, c, maxs, B)) return false;     // (<= 64 presolved variables: Setup1Smem::supported)
-    const bool want = k == SRBDQP_KERNEL_WAVE || (k == SRBDQP_KERNEL_AUTO && B >= kSplitMinBatch);
-    return want && (!stamps || k == SRBDQP_KERNEL_WAVE) && !signalled;
-}
-
 // KERNEL_SPLIT (A/B): the one-wave set-up and the one-wave ADMM as two kernels with the hand-over through HBM.
 
 template <int N, int MAXS>
-int launch_split(srbdqp_handle* h, KArgs a, hipStream_t st) {
+int launch_split(srbdqp_handle* h, const Call& c, KArgs a, hipStream_t st) {
     using W = srbdqp::SplitWs<N, MAXS>;
-    const size_t need = (size_t)(a.qp_span > a.B ? a.qp_span : a.B) * W::doubles;   // indexed by QP, not by workgroup
+    const size_t need = (size_t)a.B * W::doubles;   // indexed by QP, not by workgroup
     auto* slot = stream_slot(h, st);
     if (!slot) return SRBDQP_E_INVALID;
     int rc = grow(h, slot->ws, slot->ws_doubles, need, st, "hipMalloc split workspace");   // (a previous launch on this stream may still use the old buffer)
@@ -449,16 +422,9 @@ int launch_split(srbdqp_handle* h, KArgs a, hipStream_t st) {
     if (rc != SRBDQP_OK) return rc;
     static const std::string nm = "split_f64_n" + std::to_string(N) + "_s" + std::to_string(MAXS);
     h->kname = nm.c_str();
-    if constexpr (srbdqp::Setup1Smem<N, MAXS>::supported) {
-        if (!(h->cfg.flags & SRBDQP_FLAG_SETUP4)) {          // set-up with one wave per QP (default)
-            constexpr size_t lds1 = srbdqp::Setup1Smem<N, MAXS>::bytes;
-            hipLaunchKernelGGL((srbdqp::srbdqp_setup1_kernel<N, MAXS, false>), dim3((unsigned)a.B), dim3(64), lds1, st, a);
-        } else {
-            hipLaunchKernelGGL((srbdqp::srbdqp_compact_kernel<N, MAXS, true>), dim3((unsigned)a.B), dim3(srbdqp::kThreads), ldsA, st, a);
-        }
-    } else {
-        hipLaunchKernelGGL((srbdqp::srbdqp_compact_kernel<N, MAXS, true>), dim3((unsigned)a.B), dim3(srbdqp::kThreads), ldsA, st, a);
-    }
+    bool wave_setup = false;                                 // set-up with one wave per QP (default where the QP fits one) or with four
+    if constexpr (srbdqp::Setup1Smem<N, MAXS>::supported) if ((wave_setup = c.plan.wave_setup)) hipLaunchKernelGGL((srbdqp::srbdqp_setup1_kernel<N, MAXS, false>), dim3((unsigned)a.B), dim3(64), (srbdqp::Setup1Smem<N, MAXS>::bytes), st, a);
+    if (!wave_setup) hipLaunchKernelGGL((srbdqp::srbdqp_compact_kernel<N, MAXS, true>), dim3((unsigned)a.B), dim3(srbdqp::kThreads), ldsA, st, a);
     if ((h->cfg.flags & SRBDQP_FLAG_TIMING) && !a.count_ptr) { HIP_TRY(h, hipEventRecord(h->ev_mid, st)); h->ev_mid_valid = true; }
     hipLaunchKernelGGL((srbdqp::srbdqp_admm_kernel<N, MAXS>), dim3((unsigned)a.B), dim3(64), ldsB, st, a);
     HIP_TRY(h, hipGetLastError());
@@ -498,10 +464,10 @@ int launch_two_phase(srbdqp_handle* h, KArgs a, hipStream_t st, int phase) {
     }
 }
 
-int launch_two_phase_any(srbdqp_handle* h, const KArgs& a, hipStream_t st, int maxs, int phase) {
+int launch_two_phase_any(srbdqp_handle* h, const KArgs& a, hipStream_t st, int MAXS, int phase) {
     return with_horizon(h, [&](auto n) -> int {
         constexpr int N = decltype(n)::value;
-        if constexpr (N <= 10) return maxs <= 2 ? launch_two_phase<N, 2>(h, a, st, phase) : launch_two_phase<N, 4>(h, a, st, phase);
+        if constexpr (N <= 10) return MAXS == 2 ? launch_two_phase<N, 2>(h, a, st, phase) : launch_two_phase<N, 4>(h, a, st, phase);
         h->err = "the two-phase call is built for N in {4, 8, 10}";
         return SRBDQP_E_INVALID;
     });
@@ -510,12 +476,12 @@ int launch_two_phase_any(srbdqp_handle* h, const KArgs& a, hipStream_t st, int m
 // One wave per QP for the whole solve (srbdqp_setup1.hpp, FUSED): the default for large batches of the small
 // instantiations; nothing but inputs and outputs touches HBM.
 template <int N, int MAXS>
-int launch_wave(srbdqp_handle* h, const KArgs& a, hipStream_t st) {
+int launch_wave(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t st) {
     constexpr size_t lds1 = srbdqp::Setup1Smem<N, MAXS>::bytes;
     static const std::string nm = "wave_f64_n" + std::to_string(N) + "_s" + std::to_string(MAXS);
     h->kname = nm.c_str();
     if (a.mode == 1) hipLaunchKernelGGL((srbdqp::srbdqp_setup1_kernel<N, MAXS, true, true>), dim3((unsigned)a.B), dim3(64), lds1, st, a);
-    else if (a.restart_every > 0) {   // the rho restart in place: (x, y) of a pass wait in [3][64] doubles behind the kernel's own LDS
+    else if (c.plan.restart == Restart::InPlace) {   // the rho restart in place: (x, y) of a pass wait in [3][64] doubles behind the kernel's own LDS
         constexpr size_t ldsr = lds1 + 3 * 64 * sizeof(double);
         static_assert(8 * ((ldsr + 1279) / 1280) * 1280 <= 163840, "eight QPs per CU");
         hipLaunchKernelGGL((srbdqp::srbdqp_setup1_kernel<N, MAXS, true, false, false, true>), dim3((unsigned)a.B), dim3(64), ldsr, st, a);
@@ -563,25 +529,18 @@ int launch_wave_defer(srbdqp_handle* h, KArgs a, hipStream_t st, srbdqp_handle::
     return SRBDQP_OK;
 }
 
-int launch_wave_defer_any(srbdqp_handle* h, const KArgs& a, hipStream_t st, srbdqp_handle::StreamSlot* slot, int maxs) {
+// SRBDQP_FLAG_DEFER_TAIL on the one-wave kernel: ONE instantiation per horizon for every launch and for the flush, whatever bound on the stance contacts a call came
+// with -- a record written by a <4, 4> launch and continued by a <4, 2> one (the flush used to pick its MAXS from cfg.max_contacts_per_step, 0 -> 2, while the
+// device API assumes 4 and the host API scans the flags per call) rebuilt the QP with the wrong bound and returned SRBDQP_CONTACT_BOUND with zero forces
+constexpr int wave_defer_maxs(int N) { return N == 4 ? 4 : 2; }
+int launch_wave_defer_any(srbdqp_handle* h, const KArgs& a, hipStream_t st, srbdqp_handle::StreamSlot* slot) {
     return with_horizon(h, [&](auto n) -> int {
         constexpr int N = decltype(n)::value;
-        // N = 4: ONE instantiation for every launch and for the flush, whatever bound on the stance contacts the call came with -- a record written by a <4, 4>
-        // launch and continued by a <4, 2> one (the flush used to pick its MAXS from cfg.max_contacts_per_step, 0 -> 2, while the device API assumes 4 and the
-        // host API scans the flags per call) rebuilt the QP with the wrong bound and returned SRBDQP_CONTACT_BOUND with zero forces
-        if constexpr (N == 4) return launch_wave_defer<4, 4>(h, a, st, slot);
-        if constexpr (N == 8 || N == 10) if (maxs <= 2) return launch_wave_defer<N, 2>(h, a, st, slot);
+        if constexpr (N <= 10) return launch_wave_defer<N, wave_defer_maxs(N)>(h, a, st, slot);
         h->err = "deferred tails exist for the one-wave kernel only (N <= 10, at most 2 stance contacts per step)";
         return SRBDQP_E_INVALID;
     });
 }
-
-// lists for launches of up to B QPs that may re-balance up to rmax times (sized for the share that really continues; a full list is not an error)
-int ensure_tail_lists(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStream_t st, size_t B, int rmax);
-int flush_slot(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStream_t st);
-int solve_device_impl(srbdqp_handle* h, const Call& c, int32_t B, const void* x0, const void* x_ref, const void* foot, const uint8_t* contact,
-                      const void* pcom, const void* warm_u, const void* warm_y, void* u_out, void* x_out, void* y_out,
-                      int32_t* status, int32_t* iters, void* stream);
 
 // the handle's AQL queue, made at the first staged one-QP call (a 5 MB code object goes through the HSA loader once per process and device)
 srbdqp::AqlQueue* aql_queue(srbdqp_handle* h) {
@@ -686,13 +645,37 @@ bool staged_inline_inputs(const srbdqp_handle* h, const Call& c, const KArgs& a,
     return true;
 }
 
+// The staged low-latency door of the 4-wave and the general kernel: k_lat over the pass's grid, or -- one staged QP whose inputs ride in the argument segment --
+// its *_kernel_in twin k_in through the handle's own AQL queue (code object: kd_format % (N, x)) or, failing that, through HIP.  Both kernels' LDS limits and the
+// name BEFORE the AQL attempt, which needs none of them: HIP has loaded the kernels whichever way a later launch of this handle goes.
+template <int N, typename KLat, typename KIn>
+int launch_staged_lat(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t st, KLat k_lat, KIn k_in, const char* kd_format, int x, unsigned block, size_t lds, const char* name) {
+    srbdqp::StagedIn<N> in;
+    if (a.count_ptr || a.tile_sel || !staged_inline_inputs<N>(h, c, a, in)) return launch_kernel(h, k_lat, name, dim3((unsigned)a.B), dim3(block), lds, st, a);
+    if (const int rc = set_lds_once(h, k_lat, lds)) return rc;
+    if (const int rc = set_lds_once(h, k_in, lds)) return rc;
+    h->kname = name;
+    KArgs ai = a; ai.inline_in = 1;
+    staged_done_checksum(h, ai);
+    if (aql_launch_in(h, c, st, kd_format, N, x, ai, in, block, lds)) return SRBDQP_OK;
+    if (const int rc = aql_quiesce(h)) return rc;
+    return launch_kernel(h, k_in, nullptr, dim3(1), dim3(block), lds, st, ai, in);
+}
+
+// The launchers execute c.plan: no cfg.kernel, no threshold and no side-input pointer chooses anything in them (the handle's arrays go on as kernel arguments).
+// What a launcher still reads from the PASS's KArgs, because it differs between the passes of one solve:
+//  * a.mode == 1: the assembly dump of the planned kernel (srbdqp_assemble_f64 / _wrench_f64 launch nothing else);
+//  * the *_kernel_in twin of a _lat kernel (launch_staged_lat): !count_ptr, !tile_sel and staged_inline_inputs -- the pass's inputs are the staging arrays' own;
+//  * an fp32 solve planned with tile classes splits its FIRST pass only (no resid_in, no count_ptr) and never a ragged bucket's (row_off): restart passes run
+//    their few QPs on fp64 tiles in one launch; the two launches of the split carry tile_sel 1 and 2.
 template <int N, int MAXS>
 int launch_compact(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t st) {
+    const Plan& p = c.plan;
     if constexpr (srbdqp::Setup1Smem<N, MAXS>::supported) {
-        if (uses_wave(h, c, MAXS, a.B, a.stamps != nullptr, a.done_flag != nullptr)) return launch_wave<N, MAXS>(h, a, st);
+        if (p.family == Family::Wave) return launch_wave<N, MAXS>(h, c, a, st);
     }
     if constexpr (srbdqp::SplitWs<N, MAXS>::supported) {
-        if (h->cfg.kernel == SRBDQP_KERNEL_SPLIT && a.mode == 0 && !a.stamps && !a.done_flag) return launch_split<N, MAXS>(h, a, st);
+        if (p.family == Family::Split) return launch_split<N, MAXS>(h, c, a, st);
     }
     constexpr size_t lds = srbdqp::CompactTraits<N, MAXS>::lds_bytes;
     static const std::string nm = "compact_f64_n" + std::to_string(N) + "_s" + std::to_string(MAXS);
@@ -702,27 +685,12 @@ int launch_compact(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t 
     if constexpr (MAXS == 2 && srbdqp::SplitWs<N, MAXS>::supported) {
         // staged batch-1 path (completion word): four waves for the set-up, then the one-wave iteration on wave 0 (srbdqp_compact.hpp, TAIL1) --
         // compiled for one workgroup's worth of registers.  tools/latency_patterns.py, tools/batch1_kernel_probe.py
-        if (a.done_flag && a.B <= kTail1MaxBatch && !(h->cfg.flags & SRBDQP_FLAG_NO_LAT)) {
+        if (p.form == Form::Lat) {
             constexpr size_t lds1 = srbdqp::CompactTraits<N, MAXS>::lds_bytes_tail1;
             static_assert(lds1 <= 163840 && srbdqp::SplitWs<N, MAXS>::KS <= 64, "TAIL1: K^-1 rows behind the kernel's own LDS");
             static const std::string nml = nm + "_lat";
-            srbdqp::StagedIn<N> in;
-            if (!a.count_ptr && staged_inline_inputs<N>(h, c, a, in)) {
-                // (both kernels' LDS limits and the name BEFORE the AQL attempt, which needs none of them: HIP has loaded the kernels whichever way a later
-                //  launch of this handle goes)
-                int rc = set_lds_once(h, &srbdqp::srbdqp_compact_kernel<N, MAXS, false, false, true>, lds1);
-                if (rc == SRBDQP_OK) rc = set_lds_once(h, &srbdqp::srbdqp_compact_kernel_in<N, MAXS>, lds1);
-                if (rc != SRBDQP_OK) return rc;
-                h->kname = nml.c_str();
-                KArgs ai = a;
-                ai.inline_in = 1;
-                staged_done_checksum(h, ai);
-                if (aql_launch_in(h, c, st, "_ZN6srbdqp24srbdqp_compact_kernel_inILi%dELi%dEEEvNS_5KArgsENS_8StagedInIXT_EEE.kd", N, MAXS, ai, in, srbdqp::kThreads, lds1)) return SRBDQP_OK;
-                rc = aql_quiesce(h);
-                if (rc != SRBDQP_OK) return rc;
-                return launch_kernel(h, &srbdqp::srbdqp_compact_kernel_in<N, MAXS>, nullptr, dim3(1), block, lds1, st, ai, in);
-            }
-            return launch_kernel(h, &srbdqp::srbdqp_compact_kernel<N, MAXS, false, false, true>, nml.c_str(), grid, block, lds1, st, a);
+            return launch_staged_lat<N>(h, c, a, st, &srbdqp::srbdqp_compact_kernel<N, MAXS, false, false, true>, &srbdqp::srbdqp_compact_kernel_in<N, MAXS>,
+                                        "_ZN6srbdqp24srbdqp_compact_kernel_inILi%dELi%dEEEvNS_5KArgsENS_8StagedInIXT_EEE.kd", MAXS, srbdqp::kThreads, lds1, nml.c_str());
         }
     }
     return launch_kernel(h, &srbdqp::srbdqp_compact_kernel<N, MAXS>, nm.c_str(), grid, block, lds, st, a);
@@ -841,6 +809,20 @@ struct NormalsTraits {
     static constexpr int wps = by_lds < want ? by_lds : want;
 };
 
+// One launch of a side-input form of the general kernel (fp64 batch kernel, N <= 20): the kernel over the layout S at WPS waves per SIMD with XD doubles of its own
+// behind the layout, the name's suffix, the handle's arrays as further kernel arguments -- every launch of a solve (first pass, restart passes, deferred passes on
+// the tail stream, ragged buckets) comes through here with this handle
+template <int N, class S, int WPS, int XD, typename K, typename... A>
+int launch_side_form(srbdqp_handle* h, K kernel, const char* suffix, const KArgs& a, hipStream_t st, const A&... arrays) {
+    constexpr size_t lds = S::bytes + XD * sizeof(double);
+    constexpr int wgs = S::wgs_of(S::o_end + XD), by_lds = (wgs * S::NW + 3) / 4, by_waves = WPS * 4 / S::NW;   // (workgroups per CU and waves per SIMD the LDS admits; workgroups the waves admit)
+    static_assert(lds <= 163840 && S::BT == srbdqp::WrenchSmem<N>::BT, "one QP must fit the LDS of a CU");
+    static_assert((by_lds < WPS ? by_lds : WPS) == WPS && (wgs < by_waves ? wgs : by_waves) == (S::lds_wgs < by_waves ? S::lds_wgs : by_waves),
+                  "the doubles behind the layout cost no wave per SIMD and no workgroup per CU");
+    static const std::string nm = "wrench_f64_n" + std::to_string(N) + suffix;     // (one per instantiation: the four forms differ in S, XD or the kernel's type)
+    return launch_kernel(h, kernel, nm.c_str(), dim3((unsigned)a.B), dim3(S::BT), lds, st, a, arrays...);
+}
+
 template <int N, typename R, typename TIO>
 int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t st) {
     using S = srbdqp::WrenchSmem<N>;
@@ -855,7 +837,8 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
     static_assert(ldsb <= 163840, "one QP must fit the LDS of a CU");
     static const std::string nm = std::string("wrench_") + (sizeof(R) == 4 ? "f32" : "f64") + "_n" + std::to_string(N);
     const dim3 grid((unsigned)a.B);
-    if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) {
+    const Form form = c.plan.form;
+    if (form == Form::RankAware) {
         // rank-aware wrench steps: the MODE = 5 instantiation of the fp64 batch kernel -- every launch of a solve (first pass, restart passes, deferred passes on the
         // tail stream, a dispatch order, the staged calls with their completion word) comes through here with this handle.  (srbdqp_create refuses the flag at
         // N = 24 and at a live horizon, and the entry points the fp32 and dump calls, robot records and contact normals.)  The layout of the MODE = 0 twin.
@@ -867,7 +850,7 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
             return launch_kernel(h, &srbdqp::srbdqp_wrench_ra_kernel<N, WPS>, nm_ra.c_str(), grid, dim3(S::BT), lds, st, a);
         } else return refuse(h, Variant::RankAware, sizeof(R) == 4 ? "an fp32 solve" : "a solve at this horizon");
     }
-    if (h->live_nstar) {
+    if (form == Form::Live) {
         // a live horizon n = cfg.horizon < N (SRBDQP_FLAG_ANY_HORIZON): the MODE = 3 instantiation of the fp64 batch kernel, n as its second argument -- every launch of
         // a solve (first pass, restart passes, deferred passes on the tail stream, ragged buckets, the staged calls with their completion word) comes through here
         // with this handle.  (The entry points refuse the fp32, dump and two-phase calls and the robot records on such a handle.)
@@ -885,108 +868,56 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
     if (a.mode == 1) {
         if constexpr (sizeof(R) == 8) return launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, double, double, 1, WPS>, nm.c_str(), grid, dim3(S::BT), lds, st, a);
         else { h->err = "the assembly dump is fp64 only"; return SRBDQP_E_INVALID; }
-    } else {
-        if constexpr (sizeof(R) == 8 && N != 24) {
-            // an external wrench (srbdqp_set_external_wrench / _device), with or without weights and robot records: the MODE = 7 instantiation, the wrench, the
-            // weights (or null) and the records (or null) as its further arguments -- every launch of a solve comes through here, as below
-            if (h->ext.dev) {
-                constexpr size_t lds_ew = lds + 11 * sizeof(double);         // + the slots of MODE = 6 and the bad-wrench mark behind the layout (qp_ext_wrench_to_lds)
-                constexpr int by_lds_ew = (S::wgs_of(S::o_end + 11) * S::NW + 3) / 4;
-                constexpr int by_waves_ew = WPS * 4 / S::NW;
-                static_assert((by_lds_ew < WPS ? by_lds_ew : WPS) == WPS &&
-                              (S::wgs_of(S::o_end + 11) < by_waves_ew ? S::wgs_of(S::o_end + 11) : by_waves_ew) == (S::lds_wgs < by_waves_ew ? S::lds_wgs : by_waves_ew),
-                              "the 88 bytes of LDS cost no workgroup per CU");
-                static const std::string nm_ew = nm + "_ew";
-                return launch_kernel(h, &srbdqp::srbdqp_wrench_ew_kernel<N, WPS>, nm_ew.c_str(), grid, dim3(S::BT), lds_ew, st, a, h->ext.dev,
-                                     reinterpret_cast<const double*>(h->weights.dev), reinterpret_cast<const double*>(h->robots.dev));
-            }
-            // per-QP cost weights (srbdqp_set_weights / _device), with or without robot records: the MODE = 6 instantiation, the weights and the records (or null)
-            // as its second and third arguments -- every launch of a solve comes through here, as below.  (The weight setters refuse what the record setters do.)
-            if (h->weights.dev) {
-                constexpr size_t lds_wt = lds + 10 * sizeof(double);         // + the QP's robot, r_diag s^2 and the bad-weights mark behind the layout (qp_weights_to_lds)
-                constexpr int by_lds_wt = (S::wgs_of(S::o_end + 10) * S::NW + 3) / 4;
-                constexpr int by_waves = WPS * 4 / S::NW;                     // (workgroups per CU the waves per SIMD admit)
-                static_assert((by_lds_wt < WPS ? by_lds_wt : WPS) == WPS &&
-                              (S::wgs_of(S::o_end + 10) < by_waves ? S::wgs_of(S::o_end + 10) : by_waves) == (S::lds_wgs < by_waves ? S::lds_wgs : by_waves),
-                              "the 80 bytes of LDS cost no workgroup per CU");
-                static const std::string nm_wt = nm + "_wt";
-                return launch_kernel(h, &srbdqp::srbdqp_wrench_wt_kernel<N, WPS>, nm_wt.c_str(), grid, dim3(S::BT), lds_wt, st, a,
-                                     reinterpret_cast<const double*>(h->weights.dev), reinterpret_cast<const double*>(h->robots.dev));
-            }
-            // per-QP robot records (srbdqp_set_robots / _device): the MODE = 2 instantiation, the records as its second argument -- every launch of a solve
-            // (first pass, restart passes, deferred passes on the tail stream, ragged buckets) comes through here with this handle.  (The entry points refuse
-            // the staged, fp32 and dump calls while records are set, and the setters refuse N = 24: kRobotsMaxHorizon.)
-            if (h->robots.dev) {
-                constexpr size_t lds_rb = lds + 8 * sizeof(double);          // + the QP's robot behind the layout (srbdqp_wrench.hpp qp_robot_to_lds)
-                constexpr int by_lds_rb = (S::wgs_of(S::o_end + 8) * S::NW + 3) / 4;   // (waves per SIMD the LDS admits, as WrenchTraits::by_lds)
-                static_assert((by_lds_rb < WPS ? by_lds_rb : WPS) == WPS, "the record's 64 bytes of LDS cost no occupancy");
-                void (*k_rb)(KArgs, const double*) = &srbdqp::srbdqp_wrench_kernel<N, double, double, 2, WPS, double, 5, 0>;
-                static const std::string nm_rb = nm + "_rb";
-                return launch_kernel(h, k_rb, nm_rb.c_str(), grid, dim3(S::BT), lds_rb, st, a, reinterpret_cast<const double*>(h->robots.dev));
-            }
-        }
-        if constexpr (sizeof(R) == 8 && N != 24) {
-            // contact normals (srbdqp_set_contact_normals / _device): the MODE = 4 instantiation, the normals as its second argument -- every launch of a solve (first
-            // pass, restart passes, deferred passes on the tail stream) comes through here with this handle.  (The entry points refuse the staged, fp32 and dump
-            // calls while normals are set, and the setters an N = 24 handle and one with robot records.)  L, the frames' columns, is 288 N more bytes of LDS.
-            if (h->normals.dev) {
-                using SN = srbdqp::WrenchSmem<N, 8, 5, 0, srbdqp::wrench_kreg64(N, 4), true>;
-                constexpr size_t ldsn = SN::bytes;
-                constexpr int WPSN = NormalsTraits<N>::wps;
-                static_assert(ldsn <= 163840 && SN::BT == S::BT, "one QP must fit the LDS of a CU");
-                static const std::string nm_cn = nm + "_cn";
-                return launch_kernel(h, &srbdqp::srbdqp_wrench_cn_kernel<N, WPSN>, nm_cn.c_str(), grid, dim3(SN::BT), ldsn, st, a, h->normals.dev);
-            }
-        }
-        if constexpr (sizeof(R) == 8 && N <= 10) {
-            // staged batch-1 path (completion word): the low-latency instantiation -- two extra waves for the set-up (tables, T
-            // assembly, tile phases) that end before the iterations, one workgroup's worth of registers (no scratch, V in
-            // registers, every broadcast read of the T^-1 product in flight).  tools/latency_patterns.py
-            if (a.done_flag && a.B <= kTail1MaxBatch && !(h->cfg.flags & SRBDQP_FLAG_NO_LAT)) {
-                constexpr int XW = (N >= 8) ? 2 : 1;
-                using SL = srbdqp::WrenchSmem<N, 8, 5, XW>;
-                constexpr size_t ldsl = SL::bytes;
-                static const std::string nm_lat = nm + "_lat";
-                if constexpr (std::is_same<TIO, double>::value) {
-                    srbdqp::StagedIn<N> in;
-                    if (!a.count_ptr && !a.tile_sel && staged_inline_inputs<N>(h, c, a, in)) {
-                        // (both kernels' LDS limits and the name BEFORE the AQL attempt, which needs none of them: HIP has loaded the kernels whichever way a
-                        //  later launch of this handle goes)
-                        int rc = set_lds_once(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, 1, double, 5, XW>, ldsl);
-                        if (rc == SRBDQP_OK) rc = set_lds_once(h, &srbdqp::srbdqp_wrench_kernel_in<N, XW>, ldsl);
-                        if (rc != SRBDQP_OK) return rc;
-                        h->kname = nm_lat.c_str();
-                        KArgs ai = a;
-                        ai.inline_in = 1;
-                        staged_done_checksum(h, ai);
-                        if (aql_launch_in(h, c, st, "_ZN6srbdqp23srbdqp_wrench_kernel_inILi%dELi%dEEEvNS_5KArgsENS_8StagedInIXT_EEE.kd", N, XW, ai, in, SL::BT, ldsl)) return SRBDQP_OK;
-                        rc = aql_quiesce(h);
-                        if (rc != SRBDQP_OK) return rc;
-                        return launch_kernel(h, &srbdqp::srbdqp_wrench_kernel_in<N, XW>, nullptr, dim3(1), dim3(SL::BT), ldsl, st, ai, in);
-                    }
-                }
-                return launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, 1, double, 5, XW>, nm_lat.c_str(), grid, dim3(SL::BT), ldsl, st, a);
-            }
-        }
-        if constexpr (sizeof(R) == 4) {
-            // fp32 iterations: QPs whose steps all have 0 or >= 3 stance contacts (every g coordinate a wrench coordinate,
-            // cond(T) ~ 5e4) factor T in fp32 tiles -- half the LDS, one more workgroup per CU; a step kept in force
-            // variables carries the conditioning of K (1e8) into T and needs fp64 tiles.  Two launches over the same grid,
-            // each workgroup looks at its QP's contact flags and leaves at once if the QP belongs to the other launch.
-            // Not on the staged path (its workgroups are counted), not in the restart pass (few QPs), not for ragged batches.
-            if (!a.done_flag && !a.count_ptr && !a.resid_in && !a.row_off && !(h->cfg.flags & SRBDQP_FLAG_F64_TILES) && (a.B >= kTileClassMinBatch || (h->cfg.flags & SRBDQP_FLAG_F32_TILES))) {
-                using S4 = srbdqp::WrenchSmem<N, 4>;
-                constexpr int WPS4 = WrenchTraits<N, R, 4>::wps;
-                constexpr size_t lds4 = S4::bytes;
-                KArgs a4 = a, a8 = a;
-                a4.tile_sel = 1; a8.tile_sel = 2;
-                const int rc = launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, WPS4, float>, nm.c_str(), grid, dim3(S::BT), lds4, st, a4);
-                if (rc != SRBDQP_OK) return rc;
-                return launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, WPS, double, 5, BXW>, nullptr, grid, dim3(SB::BT), ldsb, st, a8);
-            }
-        }
-        return launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, WPS, double, 5, BXW>, nm.c_str(), grid, dim3(SB::BT), ldsb, st, a);
     }
+    if constexpr (sizeof(R) == 8 && N != 24) {
+        // The side-input forms.  (The entry points refuse the staged, fp32 and dump calls while one is set, and the setters N = 24 -- kRobotsMaxHorizon -- and what does
+        // not combine.)  An external wrench: MODE = 7, the wrench, the weights (or null) and the records (or null); behind the layout the slots of MODE = 6 and the
+        // bad-wrench mark (qp_ext_wrench_to_lds).  Cost weights: MODE = 6, the weights and the records (or null); the QP's robot, r_diag s^2 and the bad-weights mark
+        // (qp_weights_to_lds).  Robot records alone: MODE = 2; the QP's robot (qp_robot_to_lds).  Contact normals: MODE = 4 on a layout (L, the frames' columns, is
+        // 288 N more bytes of LDS) and at waves per SIMD of its own (NormalsTraits).
+        const double* const weights = reinterpret_cast<const double*>(h->weights.dev);
+        const double* const robots = reinterpret_cast<const double*>(h->robots.dev);
+        if (form == Form::ExtWrench) return launch_side_form<N, S, WPS, 11>(h, &srbdqp::srbdqp_wrench_ew_kernel<N, WPS>, "_ew", a, st, h->ext.dev, weights, robots);
+        if (form == Form::Weights) return launch_side_form<N, S, WPS, 10>(h, &srbdqp::srbdqp_wrench_wt_kernel<N, WPS>, "_wt", a, st, weights, robots);
+        if (form == Form::Robots) {
+            void (*k_rb)(KArgs, const double*) = &srbdqp::srbdqp_wrench_kernel<N, double, double, 2, WPS, double, 5, 0>;
+            return launch_side_form<N, S, WPS, 8>(h, k_rb, "_rb", a, st, robots);
+        }
+        if (form == Form::Normals) {
+            using SN = srbdqp::WrenchSmem<N, 8, 5, 0, srbdqp::wrench_kreg64(N, 4), true>;
+            return launch_side_form<N, SN, NormalsTraits<N>::wps, 0>(h, &srbdqp::srbdqp_wrench_cn_kernel<N, NormalsTraits<N>::wps>, "_cn", a, st, h->normals.dev);
+        }
+    }
+    if constexpr (sizeof(R) == 8 && N <= 10) {
+        // staged batch-1 path (completion word): the low-latency instantiation -- two extra waves for the set-up (tables, T
+        // assembly, tile phases) that end before the iterations, one workgroup's worth of registers (no scratch, V in
+        // registers, every broadcast read of the T^-1 product in flight).  tools/latency_patterns.py
+        if (form == Form::Lat) {
+            constexpr int XW = (N >= 8) ? 2 : 1;
+            using SL = srbdqp::WrenchSmem<N, 8, 5, XW>;
+            static const std::string nm_lat = nm + "_lat";
+            return launch_staged_lat<N>(h, c, a, st, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, 1, double, 5, XW>, &srbdqp::srbdqp_wrench_kernel_in<N, XW>,
+                                        "_ZN6srbdqp23srbdqp_wrench_kernel_inILi%dELi%dEEEvNS_5KArgsENS_8StagedInIXT_EEE.kd", XW, SL::BT, SL::bytes, nm_lat.c_str());
+        }
+    }
+    if constexpr (sizeof(R) == 4) {
+        // fp32 iterations: QPs whose steps all have 0 or >= 3 stance contacts (every g coordinate a wrench coordinate,
+        // cond(T) ~ 5e4) factor T in fp32 tiles -- half the LDS, one more workgroup per CU; a step kept in force
+        // variables carries the conditioning of K (1e8) into T and needs fp64 tiles.  Two launches over the same grid,
+        // each workgroup looks at its QP's contact flags and leaves at once if the QP belongs to the other launch.
+        // Not on the staged path (its workgroups are counted: plan_solve), not in the restart pass (few QPs), not for ragged batches.
+        if (c.plan.tile_classes && !a.count_ptr && !a.resid_in && !a.row_off) {
+            using S4 = srbdqp::WrenchSmem<N, 4>;
+            constexpr int WPS4 = WrenchTraits<N, R, 4>::wps;
+            constexpr size_t lds4 = S4::bytes;
+            KArgs a4 = a, a8 = a;
+            a4.tile_sel = 1; a8.tile_sel = 2;
+            const int rc = launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, WPS4, float>, nm.c_str(), grid, dim3(S::BT), lds4, st, a4);
+            if (rc != SRBDQP_OK) return rc;
+            return launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, WPS, double, 5, BXW>, nullptr, grid, dim3(SB::BT), ldsb, st, a8);
+        }
+    }
+    return launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, WPS, double, 5, BXW>, nm.c_str(), grid, dim3(SB::BT), ldsb, st, a);
 }
 
 // the general kernel at the handle's horizon, on the call's element type
@@ -998,20 +929,18 @@ int launch_wrench(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t s
     });
 }
 
-// pass: 0 = the only launch of a solve, 1 = first of two (restart follows), 2 = second of two
+// one launch of the call's plan.  pass: 0 = the only launch of a solve, 1 = first of two (restart follows), 2 = second of two
 int launch(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t st, int pass = 0) {
     if (a.B <= 0) return SRBDQP_OK;
     const bool timing = (h->cfg.flags & SRBDQP_FLAG_TIMING) != 0;
     if (timing && pass != 2) { HIP_TRY(h, hipEventRecord(h->ev0, st)); h->ev_mid_valid = false; }
     int rc;
-    // the compact kernel exists with up to 4 stance contacts per step at N <= 10, with at most 2 at N = 12 - 20; anything else (and every fp32 call) goes to
-    // the general kernel
-    if (uses_wrench(h, c, c.maxs, a.qp_span > a.B ? a.qp_span : a.B)) rc = launch_wrench(h, c, a, st);
+    if (c.plan.family == Family::General) rc = launch_wrench(h, c, a, st);
     else rc = with_horizon(h, [&](auto n) -> int {
         constexpr int N = decltype(n)::value;
-        if constexpr (N <= 10) return (c.maxs <= 2) ? launch_compact<N, 2>(h, c, a, st) : launch_compact<N, 4>(h, c, a, st);
+        if constexpr (N <= 10) return (c.plan.maxs == 2) ? launch_compact<N, 2>(h, c, a, st) : launch_compact<N, 4>(h, c, a, st);
         else if constexpr (N <= 20) return launch_compact<N, 2>(h, c, a, st);
-        else return SRBDQP_OK;     // (N = 24 never gets here: uses_wrench)
+        else return SRBDQP_OK;     // (N = 24 never gets here: plan_solve)
     });
     if (rc != SRBDQP_OK) return rc;
     if (timing && pass != 1) {
@@ -1108,6 +1037,85 @@ inline int restart_iter_of(const srbdqp_handle* h, int* count = nullptr) {
     return (r > 0 && r < c.max_iter) ? r : 0;
 }
 
+// Batches of at least this many QPs of the small instantiations (<= 64 presolved variables) run with one wave per QP
+// (launch_wave); the staged (completion-word) path and the big instantiations use the 4-wave kernel.  Until round 4 the cross-over of the per-call time was 512
+// QPs; with the rho restart on at every batch size (in place on the one-wave kernel, one more launch per pass on the 4-wave one) the one-wave kernel is the
+// faster one at EVERY size (tools/threshold_probe.py, us per synchronised call, 4-wave / one-wave: B = 1 60 / 55, 32 67 / 61, 128 72 / 64, 256 163 / 149,
+// 512 238 / 192, 4096 483 / 289).
+constexpr int kSplitMinBatch = 1;
+
+// Batches of at least this many QPs with more than 2 stance contacts in a step go to the general kernel at N <= 10 too
+// (measured, tools/schedule_bench.py, 4096 QPs: N = 10 double support 13.5 M QP/s against 4.2 M on the 4-wave compact kernel,
+// mixed gait 13.9 M against 6.5 M); smaller ones stay on the 4-wave kernel (lowest latency).
+constexpr int kWrenchMinBatch = 512;      // re-measured in round 4 (uniform rho restart; tools/schedule_bench.py, M QP/s 4-wave / general): N = 10 mixed gait 256 QPs 1.72 / 1.63,
+                                          // 512 3.10 / 3.28, 768 3.98 / 4.67, 1024 4.63 / 6.06; double support 256 1.70 / 2.45, 512 2.61 / 4.28 (round 2: 768)
+constexpr int kTail1MaxBatch = 8;              // staged calls of up to this many QPs on <= 2 stance contacts per step: the 4-wave set-up + one-wave iteration kernel
+constexpr int kStagedWrenchMinVars = 60;   // staged call: presolved variables (3 per stance contact) above which the wrench-space kernel's low-latency
+                                          // instantiation wins (B = 1, N = 10: mixed gait, 72 variables, 74 us compact / 69 us; double support, 120, 107 / 69)
+constexpr int kWrenchMinBatchN20 = 256;   // N = 20: one workgroup per CU on the compact kernel, two on the general one
+
+// fp32 calls of at least this many QPs are split by tile precision (two launches + the classification kernel); smaller
+// ones run on fp64 tiles, where the third workgroup per CU would stay empty anyway.
+constexpr int kTileClassMinBatch = 512;
+
+// ---- the planner: which kernel a solve of B QPs on this handle runs, and how its rho restart runs.  Every test that picks a kernel is here, and every threshold
+// above is read here only; launch() and the launchers execute the Plan, every pass of the call the same one. ----
+// maxs: the caller's bound on the stance contacts per step (the config's, the batch's own flags scanned, or 4); neff: the most presolved variables (3 x stance
+// contacts) of one QP (the staged call); dump: the assembly dump -- of the general kernel, whatever a solve would run, if `general` (srbdqp_assemble_wrench_f64)
+Plan plan_solve(const srbdqp_handle* h, const Call& c, int B, int maxs, int neff = 0, bool dump = false, bool general = false) {
+    const srbdqp_config& cfg = h->cfg;
+    const int N = cfg.horizon, k = cfg.kernel;
+    const bool stamps = h->stamps != nullptr, defer = (cfg.flags & SRBDQP_FLAG_DEFER_TAIL) != 0;
+    Plan p;
+    // ---- the general kernel (srbdqp_wrench.hpp)?  The compact kernel exists with up to 4 stance contacts per step at N <= 10, with at most 2 at N = 12 - 20
+    // (per-QP records, weights and wrenches, contact normals, a live horizon: only the general kernel reads them)
+    general = general || k == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || h->robots.dev || h->weights.dev || h->ext.dev || h->normals.dev || h->live_nstar;
+    // N = 20 single support too, for batches: the general kernel holds 2 workgroups per CU there, the compact one 1
+    // (tools/schedule_bench.py, 16,384 QPs: 2.85 M QP/s against 1.95 M; at N = 12 / 16 the compact kernel wins, 7.1 / 4.9 M
+    // against 5.7 / 4.2 M)
+    if (!general && N > 10) general = maxs > 2 || (N == 20 && k == SRBDQP_KERNEL_AUTO && B >= kWrenchMinBatchN20 && !stamps && !c.staged);
+    // N <= 10 with more than 2 stance contacts in a step: batches (the 4-wave kernel wins up to two QPs per CU) AND the staged
+    // low-latency path -- the reference's own call feeds full double support on every step (run_simulation.py:100-101), where the
+    // wrench-space problem is 60 x 60 against the 120 x 120 dense K of the compact kernel (round 3, tools/latency_patterns.py:
+    // B = 1 double support p50 82 us against 112 us)
+    // (the low-latency instantiation is one workgroup per CU, tuned and measured at B = 1: the same bound as the compact kernel's TAIL1 path)
+    else if (!general && k == SRBDQP_KERNEL_AUTO && maxs > 2 && !stamps)
+        general = B >= kWrenchMinBatch || (c.staged && B <= kTail1MaxBatch && N >= 8 && neff > kStagedWrenchMinVars);
+    // the staged low-latency instantiations (_lat) of the 4-wave and the general kernel: a call that publishes the completion word, a few QPs
+    const bool lat = c.signal && !dump && B <= kTail1MaxBatch && !(cfg.flags & SRBDQP_FLAG_NO_LAT);
+    if (general) {           // (p.family as it is)
+        const bool side = !c.f32 && N != 24;                 // (the side-input forms are fp64 batch kernels for N <= 20: the setters and the entry points see to it)
+        if (cfg.flags & SRBDQP_FLAG_RANK_AWARE) p.form = Form::RankAware;
+        else if (h->live_nstar) p.form = Form::Live;
+        else if (dump) p.form = Form::Plain;
+        else if (side && h->ext.dev) p.form = Form::ExtWrench;      // (with or without weights and records)
+        else if (side && h->weights.dev) p.form = Form::Weights;    // (with or without records)
+        else if (side && h->robots.dev) p.form = Form::Robots;
+        else if (side && h->normals.dev) p.form = Form::Normals;
+        else if (!c.f32 && N <= 10 && lat) p.form = Form::Lat;
+        p.tile_classes = c.f32 && !c.signal && !(cfg.flags & SRBDQP_FLAG_F64_TILES) && (B >= kTileClassMinBatch || (cfg.flags & SRBDQP_FLAG_F32_TILES));
+    } else {
+        // ---- the presolved family (srbdqp_compact.hpp): <N, 2> or, at N <= 10, <N, 4>; the one-wave kernel where the QP has at most 64 presolved variables
+        // (Setup1Smem::supported) unless a stamp buffer or the completion word needs the 4-wave one (the dump carries neither)
+        p.maxs = (N > 10 || maxs <= 2) ? 2 : 4;
+        const bool fits_wave = N <= 10 && (N == 4 || maxs <= 2);
+        const bool want_wave = k == SRBDQP_KERNEL_WAVE || (k == SRBDQP_KERNEL_AUTO && B >= kSplitMinBatch);
+        if (fits_wave && want_wave && (!stamps || dump || k == SRBDQP_KERNEL_WAVE) && !c.signal) p.family = Family::Wave;
+        else if (k == SRBDQP_KERNEL_SPLIT && !dump && !stamps && !c.signal) { p.family = Family::Split; p.wave_setup = fits_wave && !(cfg.flags & SRBDQP_FLAG_SETUP4); }
+        else { p.family = Family::Compact; if (p.maxs == 2 && lat) p.form = Form::Lat; }
+    }
+    // ---- the rho restart (periods and counts: restart_iter_of, at most three re-balancings -- what the lists of a set and of a launch stream hold)
+    if (dump || stamps || B < 1 || restart_iter_of(h) <= 0) return p;
+    // (the staged call starts its further passes itself, and only when a status asks for one: c.lazy)
+    if (p.family != Family::Wave) p.restart = (defer && !c.lazy && !c.signal) ? Restart::Deferred : Restart::Launches;
+    else if (!defer) p.restart = Restart::InPlace;
+    else { p.family = Family::WaveDefer; p.maxs = wave_defer_maxs(N); p.restart = Restart::Deferred; }   // continuations ride in the next launch on this stream (srbdqp_flush() completes them)
+    return p;
+}
+
+inline bool general_allowed(const srbdqp_config& c) { return c.kernel == SRBDQP_KERNEL_AUTO || c.kernel == SRBDQP_KERNEL_WRENCH; }   // (a side input needs the general kernel: variant_check_batch)
+inline int plan_two_phase(int maxs) { return maxs <= 2 ? 2 : 4; }   // the MAXS of the two-phase call (N <= 10): the presolved family's rule, kept from the set-up for phase 2
+
 // a launch stream's restart sets for batches of up to B QPs (nsets = 3: with the lists of the deferred passes); growing waits for this stream and its tail only
 int ensure_restart_buffers(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStream_t st, size_t B, int nsets = 1) {
     const size_t N = (size_t)h->cfg.horizon;
@@ -1117,6 +1125,21 @@ int ensure_restart_buffers(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hi
     return carve_restart_sets(h, slot->rb, B, B * 20 * N, nsets, nsets > 1 ? 4 : 0, B <= 64 ? B * 12 * N : 0);   // (ubuf: only the staged path uses it: small batches)
 }
 
+// run what the lists of this launch stream still hold: one launch, one workgroup per record the lists can hold, each running every pass its QP has left;
+// enqueued on st, no host synchronisation
+int flush_slot(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStream_t st) {
+    if (!slot->tail || !slot->tail_live) return SRBDQP_OK;
+    int rcount = 1;
+    const int restart = restart_iter_of(h, &rcount);
+    KArgs a = base_args(h->cfg, 0);
+    a.restart_every = restart; a.restart_max = rcount;
+    // ONE launch: a flush workgroup runs every pass its QP has left (srbdqp_setup1.hpp, FLUSH)
+    if (const int rc = launch_wave_defer_any(h, a, st, slot)) return rc;
+    slot->tail_live = false;
+    return SRBDQP_OK;
+}
+
+// lists for launches of up to B QPs that may re-balance up to rmax times (sized for the share that really continues; a full list is not an error)
 int ensure_tail_lists(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStream_t st, size_t B, int rmax) {
     // Round 5: sized for the share of a launch that really continues, not for every QP of it (rmax + 1) times over (1.2 GB per stream at 65,536 QPs).  About 4 % of a
     // configs[1] batch reach the first mark and 1 % the second; a list holds a QUARTER of the largest launch (at least 8192 records, never more than the
@@ -1142,23 +1165,6 @@ int ensure_tail_lists(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStre
     slot->tail_k = 0;
     for (auto& v : slot->tail_hist) v = 0;
     HIP_TRY(h, hipMemsetAsync(slot->tail_cnt, 0, 64, st));
-    return SRBDQP_OK;
-}
-
-// run what the lists of this launch stream still hold: one launch, one workgroup per record the lists can hold, each running every pass its QP has left;
-// enqueued on st, no host synchronisation
-int flush_slot(srbdqp_handle* h, srbdqp_handle::StreamSlot* slot, hipStream_t st) {
-    if (!slot->tail || !slot->tail_live) return SRBDQP_OK;
-    int rcount = 1;
-    const int maxs = maxs_or(h->cfg, 2);
-    const int restart = restart_iter_of(h, &rcount);
-    KArgs a = base_args(h->cfg, 0);
-    a.restart_every = restart; a.restart_max = rcount;
-    {   // ONE launch: a flush workgroup runs every pass its QP has left (srbdqp_setup1.hpp, FLUSH)
-        const int rc = launch_wave_defer_any(h, a, st, slot, maxs <= 2 ? 2 : 4);
-        if (rc != SRBDQP_OK) return rc;
-    }
-    slot->tail_live = false;
     return SRBDQP_OK;
 }
 
@@ -1216,6 +1222,91 @@ int run_restart_passes(const KArgs& a1, int rcount, int max_iter, const RestartS
 // the launch publishes the completion word with the handle's current sequence number
 void signal_args(const srbdqp_handle* h, KArgs& a) { a.done_flag = h->done_dev; a.done_count = h->done_count; a.done_value = h->done_seq; }
 int32_t next_seq(srbdqp_handle* h) { return h->done_seq = (h->done_seq == INT32_MAX) ? 1 : h->done_seq + 1; }
+
+// SRBDQP_FLAG_DEFER_TAIL on a kernel that restarts by further launches: the first pass on the caller's stream, the restart passes on the slot's own tail stream
+// behind an event -- beside whatever the caller enqueues next, e.g. the next batch's first pass -- each taking the list of QPs the pass before it left at its cap
+// as its dispatch order (working workgroups first; the rest of the grid leaves after one scalar load).  Outputs of the continued QPs arrive when the tail
+// stream gets there; srbdqp_flush() makes the caller's stream wait for it.
+int solve_deferred_passes(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t lst, int restart, int rcount) {
+    auto* slot = stream_slot(h, lst);
+    if (!slot) return SRBDQP_E_INVALID;
+    if (const int rc = ensure_restart_buffers(h, slot, lst, (size_t)a.B, kRestartSets)) return rc;
+    Tail& tail = slot->rtail;
+    if (!tail.st) {
+        if (const int rc = tail_create(h, tail)) return rc;
+        HIP_TRY(h, hipEventCreateWithFlags(&slot->ev_main, hipEventDisableTiming));
+    }
+    const int k = next_set(slot->rs_k, kRestartSets);
+    const RestartSet& set = slot->rb.set[k];
+    if (const int rc = tail_wait(h, tail, k, lst)) return rc;   // the set's last user (three solves ago) has finished its passes
+    HIP_TRY(h, hipMemsetAsync(set.cnt, 0, 16 * sizeof(int32_t), lst));
+    KArgs a1 = first_pass_args(a, restart, set);
+    a1.cap_list = set.list[0]; a1.cap_count = set.cnt;
+    if (const int rc = launch(h, c, a1, lst, 1)) return rc;
+    HIP_TRY(h, hipEventRecord(slot->ev_main, lst));
+    HIP_TRY(h, hipStreamWaitEvent(tail.st, slot->ev_main, 0));
+    const int rc = run_restart_passes(a1, rcount, h->cfg.max_iter, set, tail.st, [&](Pass& pass, int p, hipStream_t st) {
+        pass.a.perm = set.list[p - 1]; pass.a.count_ptr = set.cnt + (p - 1);
+        pass.a.cap_list = pass.last ? nullptr : set.list[p]; pass.a.cap_count = pass.last ? nullptr : set.cnt + p;
+        return launch(h, c, pass.a, st, 2);
+    });
+    return rc != SRBDQP_OK ? rc : tail_close(h, tail, k);
+}
+
+// common body of the device-buffer entry points; the element type of the caller's buffers is c.f32 ? float : double
+int solve_device_impl(srbdqp_handle* h, const Call& c, int32_t B, const void* x0, const void* x_ref, const void* foot, const uint8_t* contact,
+                      const void* pcom, const void* warm_u, const void* warm_y, void* u_out, void* x_out, void* y_out,
+                      int32_t* status, int32_t* iters, void* stream) {
+    if (B < 0 || (B > 0 && (!x0 || !x_ref || !foot || !contact || !u_out))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (!c.staged) if (const int rq = aql_quiesce(h)) return rq;
+    KArgs a = base_args(h->cfg, B, x0, x_ref, foot, contact, pcom);
+    a.warm_u = static_cast<const double*>(warm_u); a.warm_y = static_cast<const double*>(warm_y);
+    a.u_out = static_cast<double*>(u_out); a.x_out = static_cast<double*>(x_out); a.y_out = static_cast<double*>(y_out);
+    a.status = status; a.iters = iters;
+    a.stamps = h->stamps;
+    if (c.signal) signal_args(h, a);
+    hipStream_t lst = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+    if (c.use_hint && h->sched_hint && B > 1 && (size_t)B <= h->sched_hint_len) {
+        auto* slot = stream_slot(h, lst);
+        if (!slot) return SRBDQP_E_INVALID;
+        const int rc = grow(h, slot->perm, slot->perm_cap, (size_t)B, lst, "hipMalloc dispatch order");   // (a previous launch on this stream may still read the old order)
+        if (rc != SRBDQP_OK) return rc;
+        hipLaunchKernelGGL(srbdqp_schedule_kernel, dim3(1), dim3(1024), 0, lst, h->sched_hint, slot->perm, (int)B);
+        a.perm = slot->perm;
+    }
+    const Plan& p = c.plan;
+    int rcount = 1;
+    const int restart = p.restart == Restart::Off ? 0 : restart_iter_of(h, &rcount);
+    if (p.restart == Restart::InPlace || p.family == Family::WaveDefer) { a.restart_every = restart; a.restart_max = rcount; }   // the one-wave kernel restarts in place
+    if (p.family == Family::WaveDefer) {   // ... or not at all: continuations deferred to the next launch on this stream (srbdqp_flush() completes them)
+        auto* slot = stream_slot(h, lst);
+        if (!slot) return SRBDQP_E_INVALID;
+        if (const int rc = ensure_tail_lists(h, slot, lst, (size_t)B, rcount)) return rc;
+        return launch_wave_defer_any(h, a, lst, slot);
+    }
+    if (p.restart == Restart::Off || p.restart == Restart::InPlace) return launch(h, c, a, lst);
+    if (p.restart == Restart::Deferred) return solve_deferred_passes(h, c, a, lst, restart, rcount);
+
+    // ---- several passes: cap the first at rho_restart_iter, re-balance rho for the QPs that reach it, continue those (up to rcount times)
+    auto* slot = stream_slot(h, lst);
+    if (!slot) return SRBDQP_E_INVALID;
+    if (const int rc = ensure_restart_buffers(h, slot, lst, (size_t)B)) return rc;
+    // in the caller's stream: set 0 -- on a handle with SRBDQP_FLAG_DEFER_TAIL (a staged or completion-word solve comes through here) behind the passes of the
+    // deferred solve that used it last, as that path does: it must not overwrite what a tail pass still reads
+    const RestartSet& set = slot->rb.set[0];
+    if (const int rc = tail_wait(h, slot->rtail, 0, lst)) return rc;
+    KArgs a1 = first_pass_args(a, restart, set);
+    if (!c.lazy) { a1.done_flag = nullptr; a1.done_count = nullptr; }
+    if (c.lazy && slot->rb.ubuf && !c.f32) a1.u_dev = slot->rb.ubuf;   // (the staged arrays are host memory: the pass behind this one reads its warm start on the device)
+    const int rc = launch(h, c, a1, lst, c.lazy ? 0 : 1);
+    if (c.lazy) { c.lazy->a1 = a1; c.lazy->rcount = rcount; c.lazy->set = &set; c.lazy->pending = (rc == SRBDQP_OK); }   // (staged path: the host looks at status[] before a second pass)
+    if (rc != SRBDQP_OK || c.lazy) return rc;
+    return run_restart_passes(a1, rcount, h->cfg.max_iter, set, lst, [&](Pass& pass, int, hipStream_t st) {
+        if (pass.last && a.done_flag) signal_args(h, pass.a);
+        return launch(h, c, pass.a, st, 2);
+    });
+}
 
 // ---- the per-QP side inputs: robot records, cost weights, contact normals ----
 // To the host each is one thing: an optional per-QP device array (PerQp) that the general kernel reads and every other call refuses, owned by the library (host
@@ -1401,7 +1492,7 @@ int quiesce_all_streams(srbdqp_handle* h) {
 int variant_check_batch(srbdqp_handle* h, int32_t B) {
     const Variant v = variant_of(h);
     if (v != Variant::Robots && v != Variant::Normals && v != Variant::Weights && v != Variant::ExtWrench) return SRBDQP_OK;
-    if (h->cfg.kernel != SRBDQP_KERNEL_AUTO && h->cfg.kernel != SRBDQP_KERNEL_WRENCH) {
+    if (!general_allowed(h->cfg)) {
         h->err = std::string(v == Variant::Robots ? "per-QP robot records" : v == Variant::Weights ? "per-QP cost weights (srbdqp_set_weights)" :
                              v == Variant::ExtWrench ? "an external wrench (srbdqp_set_external_wrench)" : "contact normals (srbdqp_set_contact_normals)") +
                  " are read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH while they are set";
@@ -1457,7 +1548,7 @@ int srbdqp_create(const srbdqp_config* cfg, srbdqp_handle** out) {
         g_create_err = "unsupported horizon (N in {4, 8, 10, 12, 16, 20, 24}; with SRBDQP_FLAG_ANY_HORIZON every N from 1 to 24)";
         return SRBDQP_E_INVALID;
     }
-    if (live && cfg->kernel != SRBDQP_KERNEL_AUTO && cfg->kernel != SRBDQP_KERNEL_WRENCH) {
+    if (live && !general_allowed(*cfg)) {
         g_create_err = "SRBDQP_FLAG_ANY_HORIZON: a horizon outside {4, 8, 10, 12, 16, 20, 24} runs on the general kernel only (srbdqp_config.kernel = SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH)";
         return SRBDQP_E_INVALID;
     }
@@ -1600,14 +1691,12 @@ int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32
     Lazy lazy;
     Call c;                        // same per-batch kernel choice as the host-buffer API, from the staged contact flags
     const Contacts k = scan_contacts(h->stage_h.contact, (size_t)B, (size_t)h->cfg.horizon, true);
-    c.maxs = maxs_or(h->cfg, k.maxs());
-    c.staged = true;
-    c.neff = k.neff;
-    c.lazy = &lazy;                // the rho restart costs two more launches: only when needed
+    c.staged = true; c.lazy = &lazy;   // (lazy: the rho restart costs two more launches: only when needed)
     // completion: the kernel publishes a sequence number in host memory after its outputs (signal_done()); spinning on it skips the stream's completion
     // interrupt (~15 us)
     c.signal = !(h->cfg.flags & SRBDQP_FLAG_NO_SPIN);
     if (c.signal) next_seq(h);
+    c.plan = plan_solve(h, c, B, maxs_or(h->cfg, k.maxs()), k.neff);
     int rc = solve_device_impl(h, c, B, d.x0, d.x_ref, d.foot, d.contact, use_pcom ? d.pcom : nullptr, use_warm ? d.warm_u : nullptr,
                                use_warm ? d.warm_y : nullptr, d.u, want_x ? d.x : nullptr, want_y ? d.y : nullptr, d.status, d.iters, h->stream);
     if (rc != SRBDQP_OK) return rc;
@@ -1619,7 +1708,7 @@ int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32
         if (!capped) break;
         Pass pass = restart_pass(lazy.a1, p, lazy.rcount, h->cfg.max_iter, lazy.set->rho);
         if (c.signal) { next_seq(h); signal_args(h, pass.a); }
-        rc = launch(h, c, pass.a, h->stream, 2);            // (with the first pass's Call: the same kernel)
+        rc = launch(h, c, pass.a, h->stream, 2);            // (with the first pass's Call: the same plan)
         if (rc != SRBDQP_OK) return rc;
         rc = wait_done(h, c.signal);
         if (rc != SRBDQP_OK || pass.last) break;
@@ -1670,7 +1759,7 @@ int srbdqp_prepare_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom) {
         const int rq = aql_quiesce(h);
         if (rq != SRBDQP_OK) return rq;
     }
-    const int maxs = maxs_or(h->cfg, scan_contacts(h->stage_h.contact, (size_t)B, (size_t)h->cfg.horizon, false).maxs());
+    const int maxs = plan_two_phase(host_maxs(h, h->stage_h.contact, (size_t)B));
     KArgs a = staged_args(h, B, use_pcom != 0, true, false);
     const int rc = launch_two_phase_any(h, a, h->stream, maxs, 0);
     if (rc != SRBDQP_OK) return rc;
@@ -1806,97 +1895,6 @@ int srbdqp_last_kernel_parts_ms(srbdqp_handle* h, double* setup_ms, double* admm
 
 namespace {
 
-// SRBDQP_FLAG_DEFER_TAIL on a kernel that restarts by further launches: the first pass on the caller's stream, the restart passes on the slot's own tail stream
-// behind an event -- beside whatever the caller enqueues next, e.g. the next batch's first pass -- each taking the list of QPs the pass before it left at its cap
-// as its dispatch order (working workgroups first; the rest of the grid leaves after one scalar load).  Outputs of the continued QPs arrive when the tail
-// stream gets there; srbdqp_flush() makes the caller's stream wait for it.
-int solve_deferred_passes(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t lst, int restart, int rcount) {
-    auto* slot = stream_slot(h, lst);
-    if (!slot) return SRBDQP_E_INVALID;
-    if (const int rc = ensure_restart_buffers(h, slot, lst, (size_t)a.B, kRestartSets)) return rc;
-    Tail& tail = slot->rtail;
-    if (!tail.st) {
-        if (const int rc = tail_create(h, tail)) return rc;
-        HIP_TRY(h, hipEventCreateWithFlags(&slot->ev_main, hipEventDisableTiming));
-    }
-    const int k = next_set(slot->rs_k, kRestartSets);
-    const RestartSet& set = slot->rb.set[k];
-    if (const int rc = tail_wait(h, tail, k, lst)) return rc;   // the set's last user (three solves ago) has finished its passes
-    HIP_TRY(h, hipMemsetAsync(set.cnt, 0, 16 * sizeof(int32_t), lst));
-    KArgs a1 = first_pass_args(a, restart, set);
-    a1.cap_list = set.list[0]; a1.cap_count = set.cnt;
-    if (const int rc = launch(h, c, a1, lst, 1)) return rc;
-    HIP_TRY(h, hipEventRecord(slot->ev_main, lst));
-    HIP_TRY(h, hipStreamWaitEvent(tail.st, slot->ev_main, 0));
-    const int rc = run_restart_passes(a1, rcount, h->cfg.max_iter, set, tail.st, [&](Pass& pass, int p, hipStream_t st) {
-        pass.a.perm = set.list[p - 1]; pass.a.count_ptr = set.cnt + (p - 1);
-        pass.a.cap_list = pass.last ? nullptr : set.list[p]; pass.a.cap_count = pass.last ? nullptr : set.cnt + p;
-        return launch(h, c, pass.a, st, 2);
-    });
-    return rc != SRBDQP_OK ? rc : tail_close(h, tail, k);
-}
-
-// common body of the device-buffer entry points; the element type of the caller's buffers is c.f32 ? float : double
-int solve_device_impl(srbdqp_handle* h, const Call& c, int32_t B, const void* x0, const void* x_ref, const void* foot, const uint8_t* contact,
-                      const void* pcom, const void* warm_u, const void* warm_y, void* u_out, void* x_out, void* y_out,
-                      int32_t* status, int32_t* iters, void* stream) {
-    if (B < 0 || (B > 0 && (!x0 || !x_ref || !foot || !contact || !u_out))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (!c.staged) {
-        const int rq = aql_quiesce(h);
-        if (rq != SRBDQP_OK) return rq;
-    }
-    KArgs a = base_args(h->cfg, B, x0, x_ref, foot, contact, pcom);
-    a.warm_u = static_cast<const double*>(warm_u); a.warm_y = static_cast<const double*>(warm_y);
-    a.u_out = static_cast<double*>(u_out); a.x_out = static_cast<double*>(x_out); a.y_out = static_cast<double*>(y_out);
-    a.status = status; a.iters = iters;
-    a.stamps = h->stamps;
-    if (c.signal) signal_args(h, a);
-    hipStream_t lst = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
-    if (c.use_hint && h->sched_hint && B > 1 && (size_t)B <= h->sched_hint_len) {
-        auto* slot = stream_slot(h, lst);
-        if (!slot) return SRBDQP_E_INVALID;
-        const int rc = grow(h, slot->perm, slot->perm_cap, (size_t)B, lst, "hipMalloc dispatch order");   // (a previous launch on this stream may still read the old order)
-        if (rc != SRBDQP_OK) return rc;
-        hipLaunchKernelGGL(srbdqp_schedule_kernel, dim3(1), dim3(1024), 0, lst, h->sched_hint, slot->perm, (int)B);
-        a.perm = slot->perm;
-    }
-    const int maxs = c.maxs;
-    const bool wave = uses_wave(h, c, maxs, B, a.stamps != nullptr, a.done_flag != nullptr);
-    int rcount = 1;
-    const int restart = (h->stamps || B < 1) ? 0 : restart_iter_of(h, &rcount);
-    if (restart && wave) { a.restart_every = restart; a.restart_max = rcount; }   // the one-wave kernel restarts in place
-    if (restart && wave && (h->cfg.flags & SRBDQP_FLAG_DEFER_TAIL) && !a.stamps && !a.done_flag && !c.f32 && rcount <= srbdqp_handle::StreamSlot::kTailHist) {
-        // ... or not at all: continuations deferred to the next launch on this stream (srbdqp_flush() completes them)
-        auto* slot = stream_slot(h, lst);
-        if (!slot) return SRBDQP_E_INVALID;
-        int rc = ensure_tail_lists(h, slot, lst, (size_t)B, rcount);
-        if (rc != SRBDQP_OK) return rc;
-        return launch_wave_defer_any(h, a, lst, slot, maxs);
-    }
-    if (!restart || wave) return launch(h, c, a, lst);
-    if ((h->cfg.flags & SRBDQP_FLAG_DEFER_TAIL) && !c.lazy && !a.stamps && !a.done_flag && rcount <= 3) return solve_deferred_passes(h, c, a, lst, restart, rcount);
-
-    // ---- several passes: cap the first at rho_restart_iter, re-balance rho for the QPs that reach it, continue those (up to rcount times)
-    auto* slot = stream_slot(h, lst);
-    if (!slot) return SRBDQP_E_INVALID;
-    if (const int rc = ensure_restart_buffers(h, slot, lst, (size_t)B)) return rc;
-    // in the caller's stream: set 0 -- on a handle with SRBDQP_FLAG_DEFER_TAIL (a staged or completion-word solve comes through here) behind the passes of the
-    // deferred solve that used it last, as that path does: it must not overwrite what a tail pass still reads
-    const RestartSet& set = slot->rb.set[0];
-    if (const int rc = tail_wait(h, slot->rtail, 0, lst)) return rc;
-    KArgs a1 = first_pass_args(a, restart, set);
-    if (!c.lazy) { a1.done_flag = nullptr; a1.done_count = nullptr; }
-    if (c.lazy && slot->rb.ubuf && !c.f32) a1.u_dev = slot->rb.ubuf;   // (the staged arrays are host memory: the pass behind this one reads its warm start on the device)
-    const int rc = launch(h, c, a1, lst, c.lazy ? 0 : 1);
-    if (c.lazy) { c.lazy->a1 = a1; c.lazy->rcount = rcount; c.lazy->set = &set; c.lazy->pending = (rc == SRBDQP_OK); }   // (staged path: the host looks at status[] before a second pass)
-    if (rc != SRBDQP_OK || c.lazy) return rc;
-    return run_restart_passes(a1, rcount, h->cfg.max_iter, set, lst, [&](Pass& pass, int, hipStream_t st) {
-        if (pass.last && a.done_flag) signal_args(h, pass.a);
-        return launch(h, c, pass.a, st, 2);
-    });
-}
-
 // common body of the host-buffer entry points (esz = sizeof the caller's element type)
 int solve_host_impl(srbdqp_handle* h, bool f32, int32_t B, const void* x0, const void* x_ref, const void* foot,
                     const uint8_t* contact, const void* pcom, const void* warm_u, const void* warm_y, void* u_out,
@@ -1911,8 +1909,7 @@ int solve_host_impl(srbdqp_handle* h, bool f32, int32_t B, const void* x0, const
     const size_t N = (size_t)h->cfg.horizon, n = 12 * N, m = 20 * N, b = (size_t)B, esz = f32 ? sizeof(float) : sizeof(double);
     Call c;                        // (no dispatch hint: it belongs to the device-buffer API)
     c.f32 = f32;
-    c.maxs = h->cfg.max_contacts_per_step > 0 ? h->cfg.max_contacts_per_step
-                                              : scan_contacts(contact, b, N, false).maxs();   // the instantiation from the batch's own contact flags
+    c.plan = plan_solve(h, c, B, host_maxs(h, contact, b));      // the instantiation from the batch's own contact flags
     char *dx0, *dxr, *dft, *dpc, *dwu, *dwy, *du, *dx, *dy; uint8_t* dct; int32_t *dst, *dit;
     return host_call(h, [&](HostIo& io) {
         dx0 = io.in(x0, b * 13 * esz); dxr = io.in(x_ref, b * N * 13 * esz); dft = io.in(foot, b * N * 12 * esz);
@@ -1928,11 +1925,10 @@ int solve_host_impl(srbdqp_handle* h, bool f32, int32_t B, const void* x0, const
 }
 
 // a device-buffer solve: the dispatch hint applies, the stance-contact bound is the config's (4 where it leaves it open)
-Call device_call(const srbdqp_handle* h, bool f32) {
+Call device_call(const srbdqp_handle* h, bool f32, int32_t B) {
     Call c;
-    c.f32 = f32;
-    c.maxs = maxs_or(h->cfg, 4);
-    c.use_hint = true;
+    c.f32 = f32; c.use_hint = true;
+    c.plan = plan_solve(h, c, B, maxs_or(h->cfg, 4));
     return c;
 }
 
@@ -1946,7 +1942,7 @@ int srbdqp_solve_batch_device_f64(srbdqp_handle* h, int32_t B, const double* x0,
                                   double* y_out, int32_t* status, int32_t* iters, void* stream) {
     if (!h) return SRBDQP_E_INVALID;
     if (const int rc = variant_check_batch(h, B)) return rc;
-    return solve_device_impl(h, device_call(h, false), B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
+    return solve_device_impl(h, device_call(h, false, B), B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
 }
 
 int srbdqp_solve_batch_device_f32(srbdqp_handle* h, int32_t B, const float* x0, const float* x_ref,
@@ -1955,7 +1951,7 @@ int srbdqp_solve_batch_device_f32(srbdqp_handle* h, int32_t B, const float* x0, 
                                   float* y_out, int32_t* status, int32_t* iters, void* stream) {
     if (!h) return SRBDQP_E_INVALID;
     if (const int rc = require_form(h, "srbdqp_solve_batch_device_f32", kFormsF32)) return rc;
-    return solve_device_impl(h, device_call(h, true), B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
+    return solve_device_impl(h, device_call(h, true, B), B, x0, x_ref, foot, contact, pcom, warm_u, warm_y, u_out, x_out, y_out, status, iters, stream);
 }
 
 int srbdqp_solve_batch_f64(srbdqp_handle* h, int32_t B, const double* x0, const double* x_ref, const double* foot,
@@ -1984,8 +1980,8 @@ int srbdqp_assemble_f64(srbdqp_handle* h, int32_t B, const double* x0, const dou
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t N = (size_t)h->cfg.horizon, n = 12 * N, m = 20 * N, b = (size_t)B;
     Call c;                        // as the host-buffer solve: the instantiation follows the batch's own contact flags
-    c.maxs = h->cfg.max_contacts_per_step > 0 ? h->cfg.max_contacts_per_step : scan_contacts(contact, b, N, false).maxs();
-    if (uses_wrench(h, c, c.maxs, B)) { h->err = "this configuration solves on the general kernel: use srbdqp_assemble_wrench_f64"; return SRBDQP_E_INVALID; }
+    c.plan = plan_solve(h, c, B, host_maxs(h, contact, b), 0, true);
+    if (c.plan.family == Family::General) { h->err = "this configuration solves on the general kernel: use srbdqp_assemble_wrench_f64"; return SRBDQP_E_INVALID; }
     double *dx0, *dxr, *dft, *dpc, *dP, *dq, *dl, *du; uint8_t* dct;
     int rc = host_call(h, [&](HostIo& io) {
         dx0 = io.in<double>(x0, b * 13 * 8); dxr = io.in<double>(x_ref, b * N * 13 * 8); dft = io.in<double>(foot, b * N * 12 * 8);
@@ -2067,7 +2063,9 @@ int srbdqp_assemble_wrench_f64(srbdqp_handle* h, int32_t B, const double* x0, co
         KArgs a = base_args(h->cfg, B, dx0, dxr, dft, dct, dpc);
         a.P_out = dT; a.q_out = dq; a.l_out = dbl; a.ub_out = dgo;
         a.mode = 1;
-        return launch_wrench(h, Call(), a, st);
+        Call c;
+        c.plan = plan_solve(h, c, B, 4, 0, true, true);
+        return launch_wrench(h, c, a, st);
     });
 }
 
@@ -2244,12 +2242,12 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
     HIP_TRY(r, hipEventRecord(r->ev_in, sin));
     r->ev_in_pending = true;
     // one launch per non-empty bucket, each on its engine's own stream behind the upload; the caller's stream then waits for all
-    Call c;
-    c.f32 = f32;
     for (size_t i = 0; i < nb; ++i) {
         if (cnt[i] == 0) continue;
         srbdqp_handle* bh = r->hs[i];
         hipStream_t bs = bh->stream;
+        Call c;                    // the bucket's plan: the general kernel (srbdqp_ragged_create), in the form the bucket's handle is in
+        c.f32 = f32; c.plan = plan_solve(bh, c, cnt[i], 4);
         HIP_TRY(r, hipStreamWaitEvent(bs, r->ev_in, 0));
         KArgs a = base_args(bh->cfg, cnt[i], x0, x_ref, foot, contact);
         a.warm_u = static_cast<const double*>(warm_u); a.warm_y = static_cast<const double*>(warm_y);
@@ -2257,11 +2255,11 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
         a.status = status; a.iters = iters;
         a.perm = d_perm + start[i]; a.row_off = d_off;
         int rcount = 1;
-        const int restart = restart_iter_of(bh, &rcount);
+        const int restart = c.plan.restart == Restart::Off ? 0 : restart_iter_of(bh, &rcount);
         // several passes over the bucket, as srbdqp_solve_batch_* does (the later ones select their QPs in-kernel), or one.  Under the defer flag the caller's
         // stream waits for the first pass only: the others run on the bucket's tail stream behind it, beside what the caller enqueues next
         const KArgs a1 = restart > 0 ? first_pass_args(a, restart, set) : a;
-        const bool deferred = r->defer && restart > 0;
+        const bool deferred = c.plan.restart == Restart::Deferred;
         auto passes = [&](hipStream_t ps) {
             return run_restart_passes(a1, rcount, bh->cfg.max_iter, set, ps, [&](Pass& pass, int, hipStream_t st) { return launch_wrench(bh, c, pass.a, st); });
         };

@@ -60,7 +60,7 @@ struct KArgs {
     int32_t inline_in;       // the *_in kernels: the inputs of the one staged QP follow KArgs in the kernel-argument segment (StagedIn, below)
     int32_t y_capped_only;   // first pass, y_out = the engine's own buffer (the caller asked for no duals): only a QP that ends at the cap stores them
                              //   (20 N values per QP for every QP was a quarter of the HBM traffic of a configs[2] solve)
-    int32_t qp_span;         // host only: number of QP slots the per-QP workspaces must hold (second pass: original B)
+    int32_t qp_span;         // unused (always 0): kept so that the size and the offsets of KArgs -- the *_kernel_in argument segment -- stay where they are
     double* u_dev;           // staged first pass that a restart pass may follow: a second copy of u [B][N][12] in DEVICE memory -- the pass behind it warm-starts from
                              //   there instead of reading the staging array back over PCIe (2.4 us of the two-launch calls that make the p99), or null
     // deferred tails (SRBDQP_FLAG_DEFER_TAIL, srbdqp_wave_defer_kernel): a QP that reaches a restart mark unconverged is not continued by its own
