@@ -226,7 +226,8 @@ struct Lazy {
 
 // ---- which kernel a solve runs: a Plan, decided once per solve by plan_solve() (behind restart_iter_of) and executed by launch() and the launchers ----
 enum class Family { Wave, WaveDefer, Split, Compact, General };   // one wave per QP, ... with deferred tails, the split pipeline, the 4-wave compact kernel, the general kernel
-enum class Form { Plain, Lat, Live, RankAware, Robots, Weights, ExtWrench, Normals };   // General: any; Compact: Plain or Lat (the dump is a pass's a.mode == 1)
+// General: any (kFormRows below has a row for each but Lat, the staged low-latency instantiation); Compact: Plain or Lat (the dump is a pass's a.mode == 1)
+enum class Form { Plain, Robots, Weights, ExtWrench, Normals, Live, RankAware, Lat };
 // the rho restart of restart_iter_of: none, inside the kernel, further launches on the caller's stream (the staged call: started by the host), or off that stream
 // -- the next launch on it (WaveDefer) or a tail stream (solve_deferred_passes, the ragged buckets)
 enum class Restart { Off, InPlace, Launches, Deferred };
@@ -696,102 +697,112 @@ int launch_compact(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t 
     return launch_kernel(h, &srbdqp::srbdqp_compact_kernel<N, MAXS>, nm.c_str(), grid, block, lds, st, a);
 }
 
-// ---- the variants of the general kernel: which one a handle is in, and which call has a form for it ----
-// A handle is in exactly one of seven states.  Live and RankAware are fixed by srbdqp_create; Robots, Weights and Normals come and go with the setters (a clearing
-// call -- NULL, 0 -- is accepted in every state).  No two hold at once, except that robot records, weights and an external wrench combine -- a handle with
-// records is Robots here, Weights is the handle with weights and no records, and ExtWrench the handle with a wrench alone:
-//   Live x RankAware                      srbdqp_create refuses SRBDQP_FLAG_RANK_AWARE at a live horizon
-//   Robots x Live, Robots x RankAware     check_handle<RobotsIn> (srbdqp_set_robots / _device, and the ragged pair for every bucket)
-//   Normals x Live, Normals x RankAware   check_handle<NormalsIn> (srbdqp_set_contact_normals / _device)
-//   Robots x Normals                      each of the two checks refuses while the other is set
-//   Weights x Live, Weights x RankAware, Weights x Normals      check_handle<WeightsIn> (srbdqp_set_weights / _device, and the ragged pair for every bucket)
-//                                         and check_handle<NormalsIn>
-//   ExtWrench x Live, ExtWrench x RankAware, ExtWrench x Normals   check_handle<ExtWrenchIn> (srbdqp_set_external_wrench / _device, and the ragged pair for
-//                                         every bucket) and check_handle<NormalsIn>
-// (srbdqp_ragged_create refuses SRBDQP_FLAG_RANK_AWARE, and a ragged object has no normals: its buckets are Plain, Robots, Weights or Live.)
-enum class Variant { Plain, Robots, Normals, Live, RankAware, Weights, ExtWrench };
-
-inline Variant variant_of(const srbdqp_handle* h) {
-    if (h->robots.dev) return Variant::Robots;
-    if (h->weights.dev) return Variant::Weights;
-    if (h->ext.dev) return Variant::ExtWrench;
-    if (h->normals.dev) return Variant::Normals;
-    if (h->live_nstar) return Variant::Live;
-    if (h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) return Variant::RankAware;
-    return Variant::Plain;
-}
-
-// `what` -- a C-ABI call by its name, or a kind of solve -- has no form for a handle in state v: the message (include/srbdqp.h has the reasons and the lists;
-// the fixed texts, one per state, are quoted in INTEGRATION.md and matched by the tests) and SRBDQP_E_INVALID
-int refuse(srbdqp_handle* h, Variant v, const char* what) {
-    const std::string w(what);
-    switch (v) {
-    case Variant::Plain: h->err = w + ": refused"; break;            // (never: every call has the plain form)
-    case Variant::Robots:
-        h->err = w + ": refused while per-QP robot records are set (srbdqp_set_robots): only the fp64 batch and ragged solves on the general kernel read "
-                     "them -- one robot for every QP goes in srbdqp_config";
-        break;
-    case Variant::Normals:
-        h->err = w + ": refused while contact normals are set (srbdqp_set_contact_normals): only the fp64 batch solves on the general kernel read them "
-                     "-- srbdqp_set_contact_normals(h, NULL, 0) goes back to flat ground";
-        break;
-    case Variant::Live:
-        h->err = w + ": refused on a handle whose horizon " + std::to_string(h->cfg.horizon) + " was admitted by SRBDQP_FLAG_ANY_HORIZON: only the fp64 batch, "
-                     "ragged and staged solves run a live horizon (the general kernel's fp64 batch instantiation for N = " + std::to_string(h->live_nstar) + ")";
-        break;
-    case Variant::RankAware:
-        h->err = w + ": refused on a handle created with SRBDQP_FLAG_RANK_AWARE: only the fp64 batch and staged solves have rank-aware wrench steps "
-                     "(the general kernel's fp64 batch instantiation, flat ground, srbdqp_config's single robot)";
-        break;
-    case Variant::Weights:
-        h->err = w + ": refused while per-QP cost weights are set (srbdqp_set_weights): only the fp64 batch and ragged solves on the general kernel read "
-                     "them -- one pair of weights for every QP goes in srbdqp_config";
-        break;
-    case Variant::ExtWrench:
-        h->err = w + ": refused while an external wrench is set (srbdqp_set_external_wrench): only the fp64 batch and ragged solves on the general kernel read "
-                     "it -- srbdqp_set_external_wrench(h, NULL, 0) goes back to no wrench";
-        break;
-    }
-    return SRBDQP_E_INVALID;
-}
-
-// The table: the variants, besides Plain, that each C-ABI call has a form for.  Every call below opens with require_form(h, "<its name>", <its row>); the fp64
-// batch solves (host, device, ragged) have every form and no row.  (Inside the general kernel's launcher a rank-aware or live handle further refuses the
-// assembly dump and an fp32 solve, which no entry point lets through; the ragged calls refuse an fp32 solve and robot records with a live bucket.)
-constexpr unsigned form(Variant v) { return 1u << (unsigned)v; }
-// srbdqp_solve_staged_f64, srbdqp_update_f64 (a live handle passes here and not below: the staged solve runs its batch instantiation through the HIP launch)
-constexpr unsigned kFormsStaged = form(Variant::Live) | form(Variant::RankAware);
-// srbdqp_prepare_staged_f64, srbdqp_solve_prepared_f64 (a rank-aware handle passes: the one-wave kernels of the two-phase call have no wrench steps)
-constexpr unsigned kFormsTwoPhase = form(Variant::RankAware);
-// srbdqp_solve_batch_f32, srbdqp_solve_batch_device_f32
-constexpr unsigned kFormsF32 = 0;
-// srbdqp_assemble_f64 (a rank-aware handle passes: the dump of the compact kernels, which have no wrench steps)
-constexpr unsigned kFormsAssemble = form(Variant::RankAware);
-// srbdqp_assemble_wrench_f64
-constexpr unsigned kFormsAssembleWrench = 0;
-// srbdqp_set_robots / _device with records (check_handle<RobotsIn>, which refuses N = 24 as well)
-constexpr unsigned kFormsSetRobots = form(Variant::Robots) | form(Variant::Weights) | form(Variant::ExtWrench);
-// srbdqp_set_weights / _device with records (check_handle<WeightsIn>, which refuses N = 24 as well): beside robot records or in place of earlier weights
-constexpr unsigned kFormsSetWeights = form(Variant::Weights) | form(Variant::Robots) | form(Variant::ExtWrench);
-// srbdqp_set_external_wrench / _device with an array (check_handle<ExtWrenchIn>, which refuses N = 24 as well): beside records and weights or in place of an earlier wrench
-constexpr unsigned kFormsSetExtWrench = form(Variant::ExtWrench) | form(Variant::Robots) | form(Variant::Weights);
-// srbdqp_set_contact_normals / _device with normals (check_handle<NormalsIn>, which refuses N = 24 as well, and records in words of its own)
-constexpr unsigned kFormsSetNormals = form(Variant::Normals) | form(Variant::Robots);
-
-// a few field tests on the way of a call that has the form (srbdqp_solve_staged_f64 is the batch-1 latency path); a string only when the refusal fires
-inline int require_form(srbdqp_handle* h, const char* fn, unsigned forms) {
-    const Variant v = variant_of(h);
-    return (v == Variant::Plain || ((forms >> (unsigned)v) & 1u)) ? SRBDQP_OK : refuse(h, v, fn);
-}
-
 // Horizons with a rank-aware instantiation (MODE = 5) of the general kernel: every tabulated one below 24 builds without scratch memory at the waves per SIMD of
 // its MODE = 0 twin ("Rank-aware wrench steps", has the table); N = 24 -- whose MODE = 0 kernel keeps 20 bytes per lane there already -- has none.
 constexpr int kRankAwareMaxHorizon = 20;
+// Horizons whose general kernel has a per-QP-record instantiation (MODE = 2) without scratch memory: N = 24 has none -- the MODE = 0 kernel that ships keeps
+// 20 bytes per lane in scratch with its three extra set-up waves, and a MODE = 2 copy without them (XW = 0) 24 bytes -- so the setters refuse an N = 24
+// handle / a ragged object with an N = 24 bucket (DESIGN.md section 11).  The MODE = 6 instantiation of the weights is the MODE = 2 one with one more LDS slot
+// (DESIGN.md section 15), and the one of the normals (MODE = 4) has no N = 24 form either (section 13).
+constexpr int kRobotsMaxHorizon = 20;
 
-// The general kernel (srbdqp_wrench.hpp): any contact pattern, fp64 or fp32 iterations / buffers.
-template <int N, typename R, int TB = 8>
+// ---- the forms of the general kernel: a handle's state (state_of), one row per form (kFormRows), which form a refusal names and which one a launch runs ----
+// A handle's state is a SET of forms.  Live and RankAware are fixed by srbdqp_create, which refuses the two together; the four side inputs come and go with the
+// setters -- a clearing call (NULL, 0) is accepted in every state, a setting one only beside the forms of its row's `beside` (check_handle, and for a ragged
+// object every bucket's).  So robot records, weights and an external wrench combine, and nothing else does.  (srbdqp_ragged_create refuses
+// SRBDQP_FLAG_RANK_AWARE, and a ragged object has no normals: its buckets are Plain, Live or any of records, weights and wrench.)
+constexpr unsigned bit(Form f) { return 1u << (unsigned)f; }
+struct FormRow {
+    Form form;                     // (its state bit: bit(form))
+    int mode;                      // the MODE of wrench_qp that its launches run (srbdqp_wrench.hpp, WrenchMode: the layout, the doubles behind it)
+    const char* suffix;            // of the name a handle reports: wrench_f64_n<N><suffix> (Live: wrench_f64_n<N*><suffix><n>)
+    const char* noun;              // a side input, as variant_check_batch names it; null: a form fixed by srbdqp_create
+    unsigned beside;               // the forms that may be set beside it
+    int max_horizon;               // the largest horizon with an instantiation
+    const char* tail;              // behind "<call>: " in a refusal (include/srbdqp.h has the reasons and the lists; the texts are quoted in INTEGRATION.md and
+};                                 // matched by the tests).  Live's has two %d: the handle's horizon and its instantiation's
+constexpr FormRow kFormRows[] = {
+    {Form::Plain, srbdqp::kModeSolve, "", nullptr, 0, 24, "refused"},            // (never refused: every call has the plain form)
+    {Form::Robots, srbdqp::kModeRobots, "_rb", "per-QP robot records", bit(Form::Weights) | bit(Form::ExtWrench), kRobotsMaxHorizon,
+     "refused while per-QP robot records are set (srbdqp_set_robots): only the fp64 batch and ragged solves on the general kernel read them -- one robot for "
+     "every QP goes in srbdqp_config"},
+    {Form::Weights, srbdqp::kModeWeights, "_wt", "per-QP cost weights (srbdqp_set_weights)", bit(Form::Robots) | bit(Form::ExtWrench), kRobotsMaxHorizon,
+     "refused while per-QP cost weights are set (srbdqp_set_weights): only the fp64 batch and ragged solves on the general kernel read them -- one pair of "
+     "weights for every QP goes in srbdqp_config"},
+    {Form::ExtWrench, srbdqp::kModeExtWrench, "_ew", "an external wrench (srbdqp_set_external_wrench)", bit(Form::Robots) | bit(Form::Weights), kRobotsMaxHorizon,
+     "refused while an external wrench is set (srbdqp_set_external_wrench): only the fp64 batch and ragged solves on the general kernel read it -- "
+     "srbdqp_set_external_wrench(h, NULL, 0) goes back to no wrench"},
+    {Form::Normals, srbdqp::kModeNormals, "_cn", "contact normals (srbdqp_set_contact_normals)", 0, kRobotsMaxHorizon,
+     "refused while contact normals are set (srbdqp_set_contact_normals): only the fp64 batch solves on the general kernel read them -- "
+     "srbdqp_set_contact_normals(h, NULL, 0) goes back to flat ground"},
+    {Form::Live, srbdqp::kModeLive, "_h", nullptr, 0, 24,
+     "refused on a handle whose horizon %d was admitted by SRBDQP_FLAG_ANY_HORIZON: only the fp64 batch, ragged and staged solves run a live horizon (the "
+     "general kernel's fp64 batch instantiation for N = %d)"},
+    {Form::RankAware, srbdqp::kModeRankAware, "_ra", nullptr, 0, kRankAwareMaxHorizon,
+     "refused on a handle created with SRBDQP_FLAG_RANK_AWARE: only the fp64 batch and staged solves have rank-aware wrench steps (the general kernel's fp64 "
+     "batch instantiation, flat ground, srbdqp_config's single robot)"},
+};
+constexpr const FormRow& row(Form f) { return kFormRows[(unsigned)f]; }
+constexpr unsigned side_inputs() { unsigned s = 0; for (const FormRow& r : kFormRows) if (r.noun) s |= bit(r.form); return s; }
+constexpr unsigned kSideInputs = side_inputs();
+constexpr bool rows_in_order() { unsigned i = 0; for (const FormRow& r : kFormRows) if ((unsigned)r.form != i++) return false; return i == (unsigned)Form::Lat; }
+static_assert(rows_in_order(), "row(f) indexes kFormRows by the enum");
+static_assert(srbdqp::WrenchMode<row(Form::Robots).mode>::xd == 8 && srbdqp::WrenchMode<row(Form::Weights).mode>::xd == 10 && srbdqp::WrenchMode<row(Form::ExtWrench).mode>::xd == 11 &&
+              srbdqp::WrenchMode<row(Form::Normals).mode>::xd == 0, "the doubles launch_side_form adds behind a form's layout: one more than the highest slot its mode writes");
+
+// a handful of pointer and flag tests: no allocation, no string (srbdqp_solve_staged_f64, the batch-1 latency path, comes through here twice a call)
+inline unsigned state_of(const srbdqp_handle* h) {
+    return (h->robots.dev ? bit(Form::Robots) : 0u) | (h->weights.dev ? bit(Form::Weights) : 0u) | (h->ext.dev ? bit(Form::ExtWrench) : 0u) |
+           (h->normals.dev ? bit(Form::Normals) : 0u) | (h->live_nstar ? bit(Form::Live) : 0u) | ((h->cfg.flags & SRBDQP_FLAG_RANK_AWARE) ? bit(Form::RankAware) : 0u);
+}
+// The two precedences over a state, which differ on purpose.  A REFUSAL names the oldest input present -- records, weights, wrench, normals, then the two forms of
+// srbdqp_create -- so that a text a caller may match stays what it was when a later input learned to sit beside an earlier one.  The enum is in that order.
+inline Form refusal_form(unsigned state) { return state ? (Form)__builtin_ctz(state) : Form::Plain; }
+// A LAUNCH runs the form that reads the most: the two of srbdqp_create first (the handle has no other instantiation), then the wrench's kernel, which reads the
+// weights and the records too (or their KArgs values), then the weights', which reads the records, then the records', then the normals'.
+inline Form launch_form(unsigned state) {
+    for (const Form f : {Form::RankAware, Form::Live, Form::ExtWrench, Form::Weights, Form::Robots, Form::Normals}) if (state & bit(f)) return f;
+    return Form::Plain;
+}
+
+// `what` -- a C-ABI call by its name, or a kind of solve -- has no form for a handle with f in its state: the message and SRBDQP_E_INVALID
+int refuse(srbdqp_handle* h, Form f, const char* what) {
+    char tail[384];
+    std::snprintf(tail, sizeof(tail), row(f).tail, (int)h->cfg.horizon, (int)h->live_nstar);
+    h->err = std::string(what) + ": " + tail;
+    return SRBDQP_E_INVALID;
+}
+
+// Which forms, besides Plain, each C-ABI call admits.  Every call below opens with require_form(h, "<its name>", <its set>); the fp64 batch solves (host, device,
+// ragged) admit every form and have no set.  (Inside the general kernel's launcher a rank-aware or live handle further refuses the assembly dump and an fp32
+// solve, which no entry point lets through; the ragged calls refuse an fp32 solve and robot records with a live bucket.)
+// srbdqp_solve_staged_f64, srbdqp_update_f64 (a live handle passes here and not below: the staged solve runs its batch instantiation through the HIP launch)
+constexpr unsigned kFormsStaged = bit(Form::Live) | bit(Form::RankAware);
+// srbdqp_prepare_staged_f64, srbdqp_solve_prepared_f64 (a rank-aware handle passes: the one-wave kernels of the two-phase call have no wrench steps)
+constexpr unsigned kFormsTwoPhase = bit(Form::RankAware);
+// srbdqp_solve_batch_f32, srbdqp_solve_batch_device_f32
+constexpr unsigned kFormsF32 = 0;
+// srbdqp_assemble_f64 (a rank-aware handle passes: the dump of the compact kernels, which have no wrench steps)
+constexpr unsigned kFormsAssemble = bit(Form::RankAware);
+// srbdqp_assemble_wrench_f64
+constexpr unsigned kFormsAssembleWrench = 0;
+// the setter of side input f with an array (check_handle): in place of an earlier one, or beside what its row says.  The one exception: robot records pass the
+// normals' set, because check_handle answers them in words of its own (kNormalsOnRobots)
+constexpr unsigned forms_of_setter(Form f) { return bit(f) | row(f).beside | (f == Form::Normals ? bit(Form::Robots) : 0u); }
+constexpr const char* kNormalsOnRobots = ": refused while per-QP robot records are set (srbdqp_set_robots): no instantiation reads both (DESIGN.md section 13)";
+
+// the form a refusal would name against the set a call admits: integer tests on the way of a call that has the form; a string only when the refusal fires
+inline int require_form(srbdqp_handle* h, const char* fn, unsigned forms) {
+    const Form f = refusal_form(state_of(h));
+    return (f == Form::Plain || (forms & bit(f))) ? SRBDQP_OK : refuse(h, f, fn);
+}
+
+// The general kernel (srbdqp_wrench.hpp): any contact pattern, fp64 or fp32 iterations / buffers.  Waves per SIMD of an instantiation over the layout L: what its
+// LDS admits and the register budget, whichever is lower.  (Contact normals: the MODE = 0 layout + the table L, the budget of the MODE = 0 twin -- CHMAX is the
+// same --; DESIGN.md section 13 has the table)
+template <int N, typename R, int TB = 8, class L = srbdqp::WrenchSmem<N, TB>>
 struct WrenchTraits {
-    using S = srbdqp::WrenchSmem<N, TB>;
+    using S = L;
     static constexpr int by_lds = (S::lds_wgs * S::NW + 3) / 4 > 0 ? (S::lds_wgs * S::NW + 3) / 4 : 1;   // waves per SIMD LDS admits (rounded up: 3 workgroups of 3 waves put 3 waves on one SIMD)
     static constexpr int F32_ON_F64_WPS = 3;   // fp32 iterations on fp64 tiles, half rows longer than 30: 3 waves per SIMD with scratch beat 2 without any by 24 - 33 % (profiles/r05_f32_on_f64_tiles_wps.txt)
     static constexpr int F64_SMALL_WPS = 3;    // fp64, half rows up to 36 (N <= 12)
@@ -799,27 +810,19 @@ struct WrenchTraits {
     static constexpr int wps = by_lds < want ? by_lds : want;
 };
 
-// ... with contact normals (MODE = 4, fp64 batch form): waves per SIMD of the instantiation -- what its LDS (the MODE = 0 layout + the table L) admits and
-// the register budget of the MODE = 0 twin, whichever is lower (DESIGN.md section 13 has the table)
-template <int N>
-struct NormalsTraits {
-    using S = srbdqp::WrenchSmem<N, 8, 5, 0, srbdqp::wrench_kreg64(N, 4), true>;
-    static constexpr int by_lds = (S::lds_wgs * S::NW + 3) / 4 > 0 ? (S::lds_wgs * S::NW + 3) / 4 : 1;
-    static constexpr int want = WrenchTraits<N, double>::want;
-    static constexpr int wps = by_lds < want ? by_lds : want;
-};
-
-// One launch of a side-input form of the general kernel (fp64 batch kernel, N <= 20): the kernel over the layout S at WPS waves per SIMD with XD doubles of its own
-// behind the layout, the name's suffix, the handle's arrays as further kernel arguments -- every launch of a solve (first pass, restart passes, deferred passes on
-// the tail stream, ragged buckets) comes through here with this handle
-template <int N, class S, int WPS, int XD, typename K, typename... A>
-int launch_side_form(srbdqp_handle* h, K kernel, const char* suffix, const KArgs& a, hipStream_t st, const A&... arrays) {
+// One launch of side-input form F of the general kernel (fp64 batch kernel, N <= 20): the kernel over the layout of F's mode at WPS waves per SIMD with the mode's
+// doubles behind the layout, the name's suffix, the handle's arrays as further kernel arguments -- every launch of a solve (first pass, restart passes, deferred
+// passes on the tail stream, ragged buckets) comes through here with this handle
+template <int N, Form F, int WPS, typename K, typename... A>
+int launch_side_form(srbdqp_handle* h, K kernel, const KArgs& a, hipStream_t st, const A&... arrays) {
+    using S = srbdqp::WrenchLayout<N, row(F).mode>;
+    constexpr int XD = srbdqp::WrenchMode<row(F).mode>::xd;
     constexpr size_t lds = S::bytes + XD * sizeof(double);
     constexpr int wgs = S::wgs_of(S::o_end + XD), by_lds = (wgs * S::NW + 3) / 4, by_waves = WPS * 4 / S::NW;   // (workgroups per CU and waves per SIMD the LDS admits; workgroups the waves admit)
     static_assert(lds <= 163840 && S::BT == srbdqp::WrenchSmem<N>::BT, "one QP must fit the LDS of a CU");
     static_assert((by_lds < WPS ? by_lds : WPS) == WPS && (wgs < by_waves ? wgs : by_waves) == (S::lds_wgs < by_waves ? S::lds_wgs : by_waves),
                   "the doubles behind the layout cost no wave per SIMD and no workgroup per CU");
-    static const std::string nm = "wrench_f64_n" + std::to_string(N) + suffix;     // (one per instantiation: the four forms differ in S, XD or the kernel's type)
+    static const std::string nm = "wrench_f64_n" + std::to_string(N) + row(F).suffix;     // (one per instantiation)
     return launch_kernel(h, kernel, nm.c_str(), dim3((unsigned)a.B), dim3(S::BT), lds, st, a, arrays...);
 }
 
@@ -843,49 +846,47 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
         // tail stream, a dispatch order, the staged calls with their completion word) comes through here with this handle.  (srbdqp_create refuses the flag at
         // N = 24 and at a live horizon, and the entry points the fp32 and dump calls, robot records and contact normals.)  The layout of the MODE = 0 twin.
         if constexpr (sizeof(R) == 8 && N <= kRankAwareMaxHorizon) {
-            if (a.mode == 1) return refuse(h, Variant::RankAware, "the assembly dump");
-            using S5 = srbdqp::WrenchSmem<N, 8, 5, 0, srbdqp::wrench_kreg64(N, 5)>;
+            if (a.mode == 1) return refuse(h, Form::RankAware, "the assembly dump");
+            using S5 = srbdqp::WrenchLayout<N, row(Form::RankAware).mode>;
             static_assert(S5::bytes == lds && S5::BT == S::BT && WrenchTraits<N, double>::wps == WPS, "rank-aware steps cost no occupancy: the LDS and the waves per SIMD of the MODE = 0 twin");
-            static const std::string nm_ra = nm + "_ra";
+            static const std::string nm_ra = nm + row(Form::RankAware).suffix;
             return launch_kernel(h, &srbdqp::srbdqp_wrench_ra_kernel<N, WPS>, nm_ra.c_str(), grid, dim3(S::BT), lds, st, a);
-        } else return refuse(h, Variant::RankAware, sizeof(R) == 4 ? "an fp32 solve" : "a solve at this horizon");
+        } else return refuse(h, Form::RankAware, sizeof(R) == 4 ? "an fp32 solve" : "a solve at this horizon");
     }
     if (form == Form::Live) {
         // a live horizon n = cfg.horizon < N (SRBDQP_FLAG_ANY_HORIZON): the MODE = 3 instantiation of the fp64 batch kernel, n as its second argument -- every launch of
         // a solve (first pass, restart passes, deferred passes on the tail stream, ragged buckets, the staged calls with their completion word) comes through here
         // with this handle.  (The entry points refuse the fp32, dump and two-phase calls and the robot records on such a handle.)
         if constexpr (sizeof(R) == 8) {
-            if (a.mode == 1) return refuse(h, Variant::Live, "the assembly dump");
+            if (a.mode == 1) return refuse(h, Form::Live, "the assembly dump");
             // (the layout of the MODE = 0 twin -- the live horizon itself takes no LDS --, except N* = 24: four more entries of every lane's T^-1 half row in LDS
             //  instead of registers, srbdqp_wrench.hpp wrench_kreg64; still the twin's one workgroup per CU)
-            using S3 = srbdqp::WrenchSmem<N, 8, 5, BXW, srbdqp::wrench_kreg64(N, 3)>;
+            using S3 = srbdqp::WrenchLayout<N, row(Form::Live).mode, 8, 5, BXW>;
             constexpr size_t lds3 = S3::bytes;
             static_assert(lds3 <= 163840 && S3::lds_wgs == SB::lds_wgs && (N == 24 || lds3 == ldsb), "a live horizon costs no workgroup per CU: the occupancy of the MODE = 0 twin");
-            void (*k_live)(KArgs, int) = &srbdqp::srbdqp_wrench_kernel<N, double, double, 3, WPS, double, 5, BXW>;
+            void (*k_live)(KArgs, int) = &srbdqp::srbdqp_wrench_kernel<N, double, double, row(Form::Live).mode, WPS, double, 5, BXW>;
             return launch_kernel(h, k_live, h->live_name.c_str(), grid, dim3(S3::BT), lds3, st, a, (int)h->cfg.horizon);
-        } else return refuse(h, Variant::Live, "an fp32 solve");
+        } else return refuse(h, Form::Live, "an fp32 solve");
     }
     if (a.mode == 1) {
-        if constexpr (sizeof(R) == 8) return launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, double, double, 1, WPS>, nm.c_str(), grid, dim3(S::BT), lds, st, a);
+        if constexpr (sizeof(R) == 8) return launch_kernel(h, &srbdqp::srbdqp_wrench_kernel<N, double, double, srbdqp::kModeDump, WPS>, nm.c_str(), grid, dim3(S::BT), lds, st, a);
         else { h->err = "the assembly dump is fp64 only"; return SRBDQP_E_INVALID; }
     }
-    if constexpr (sizeof(R) == 8 && N != 24) {
-        // The side-input forms.  (The entry points refuse the staged, fp32 and dump calls while one is set, and the setters N = 24 -- kRobotsMaxHorizon -- and what does
-        // not combine.)  An external wrench: MODE = 7, the wrench, the weights (or null) and the records (or null); behind the layout the slots of MODE = 6 and the
-        // bad-wrench mark (qp_ext_wrench_to_lds).  Cost weights: MODE = 6, the weights and the records (or null); the QP's robot, r_diag s^2 and the bad-weights mark
-        // (qp_weights_to_lds).  Robot records alone: MODE = 2; the QP's robot (qp_robot_to_lds).  Contact normals: MODE = 4 on a layout (L, the frames' columns, is
-        // 288 N more bytes of LDS) and at waves per SIMD of its own (NormalsTraits).
+    if constexpr (sizeof(R) == 8 && N <= kRobotsMaxHorizon) {
+        // The side-input forms, each by its row of kFormRows.  (The entry points refuse the staged, fp32 and dump calls while one is set, and the setters N = 24 and what
+        // does not combine.)  The wrench's kernel takes the weights and the records too (or null: the KArgs values), the weights' the records (or null).  Contact
+        // normals run on a layout (L, the frames' columns, is 288 N more bytes of LDS) and at waves per SIMD of their own (WrenchTraits over that layout).
         const double* const weights = reinterpret_cast<const double*>(h->weights.dev);
         const double* const robots = reinterpret_cast<const double*>(h->robots.dev);
-        if (form == Form::ExtWrench) return launch_side_form<N, S, WPS, 11>(h, &srbdqp::srbdqp_wrench_ew_kernel<N, WPS>, "_ew", a, st, h->ext.dev, weights, robots);
-        if (form == Form::Weights) return launch_side_form<N, S, WPS, 10>(h, &srbdqp::srbdqp_wrench_wt_kernel<N, WPS>, "_wt", a, st, weights, robots);
+        if (form == Form::ExtWrench) return launch_side_form<N, Form::ExtWrench, WPS>(h, &srbdqp::srbdqp_wrench_ew_kernel<N, WPS>, a, st, h->ext.dev, weights, robots);
+        if (form == Form::Weights) return launch_side_form<N, Form::Weights, WPS>(h, &srbdqp::srbdqp_wrench_wt_kernel<N, WPS>, a, st, weights, robots);
         if (form == Form::Robots) {
-            void (*k_rb)(KArgs, const double*) = &srbdqp::srbdqp_wrench_kernel<N, double, double, 2, WPS, double, 5, 0>;
-            return launch_side_form<N, S, WPS, 8>(h, k_rb, "_rb", a, st, robots);
+            void (*k_rb)(KArgs, const double*) = &srbdqp::srbdqp_wrench_kernel<N, double, double, row(Form::Robots).mode, WPS, double, 5, 0>;
+            return launch_side_form<N, Form::Robots, WPS>(h, k_rb, a, st, robots);
         }
         if (form == Form::Normals) {
-            using SN = srbdqp::WrenchSmem<N, 8, 5, 0, srbdqp::wrench_kreg64(N, 4), true>;
-            return launch_side_form<N, SN, NormalsTraits<N>::wps, 0>(h, &srbdqp::srbdqp_wrench_cn_kernel<N, NormalsTraits<N>::wps>, "_cn", a, st, h->normals.dev);
+            constexpr int WPSN = WrenchTraits<N, double, 8, srbdqp::WrenchLayout<N, row(Form::Normals).mode>>::wps;
+            return launch_side_form<N, Form::Normals, WPSN>(h, &srbdqp::srbdqp_wrench_cn_kernel<N, WPSN>, a, st, h->normals.dev);
         }
     }
     if constexpr (sizeof(R) == 8 && N <= 10) {
@@ -1069,7 +1070,8 @@ Plan plan_solve(const srbdqp_handle* h, const Call& c, int B, int maxs, int neff
     Plan p;
     // ---- the general kernel (srbdqp_wrench.hpp)?  The compact kernel exists with up to 4 stance contacts per step at N <= 10, with at most 2 at N = 12 - 20
     // (per-QP records, weights and wrenches, contact normals, a live horizon: only the general kernel reads them)
-    general = general || k == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || h->robots.dev || h->weights.dev || h->ext.dev || h->normals.dev || h->live_nstar;
+    const unsigned state = state_of(h);                  // (rank-aware steps alone do not ask for the general kernel: the compact kernels have no wrench steps)
+    general = general || k == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || (state & ~bit(Form::RankAware));
     // N = 20 single support too, for batches: the general kernel holds 2 workgroups per CU there, the compact one 1
     // (tools/schedule_bench.py, 16,384 QPs: 2.85 M QP/s against 1.95 M; at N = 12 / 16 the compact kernel wins, 7.1 / 4.9 M
     // against 5.7 / 4.2 M)
@@ -1084,15 +1086,9 @@ Plan plan_solve(const srbdqp_handle* h, const Call& c, int B, int maxs, int neff
     // the staged low-latency instantiations (_lat) of the 4-wave and the general kernel: a call that publishes the completion word, a few QPs
     const bool lat = c.signal && !dump && B <= kTail1MaxBatch && !(cfg.flags & SRBDQP_FLAG_NO_LAT);
     if (general) {           // (p.family as it is)
-        const bool side = !c.f32 && N != 24;                 // (the side-input forms are fp64 batch kernels for N <= 20: the setters and the entry points see to it)
-        if (cfg.flags & SRBDQP_FLAG_RANK_AWARE) p.form = Form::RankAware;
-        else if (h->live_nstar) p.form = Form::Live;
-        else if (dump) p.form = Form::Plain;
-        else if (side && h->ext.dev) p.form = Form::ExtWrench;      // (with or without weights and records)
-        else if (side && h->weights.dev) p.form = Form::Weights;    // (with or without records)
-        else if (side && h->robots.dev) p.form = Form::Robots;
-        else if (side && h->normals.dev) p.form = Form::Normals;
-        else if (!c.f32 && N <= 10 && lat) p.form = Form::Lat;
+        const bool side = !dump && !c.f32 && N <= kRobotsMaxHorizon;   // (the side-input forms are fp64 batch kernels for N <= 20, and the dump has none)
+        p.form = launch_form(side ? state : state & ~kSideInputs);
+        if (p.form == Form::Plain && !c.f32 && N <= 10 && lat) p.form = Form::Lat;
         p.tile_classes = c.f32 && !c.signal && !(cfg.flags & SRBDQP_FLAG_F64_TILES) && (B >= kTileClassMinBatch || (cfg.flags & SRBDQP_FLAG_F32_TILES));
     } else {
         // ---- the presolved family (srbdqp_compact.hpp): <N, 2> or, at N <= 10, <N, 4>; the one-wave kernel where the QP has at most 64 presolved variables
@@ -1353,22 +1349,15 @@ const char* ext_wrench_fault(const double* v) {
     return std::fabs(*v) <= SRBDQP_EXT_WRENCH_MAX ? nullptr : "every value must be finite with |value| <= 1e6";
 }
 
-// Horizons whose general kernel has a per-QP-record instantiation (MODE = 2) without scratch memory: N = 24 has none -- the MODE = 0 kernel that ships keeps
-// 20 bytes per lane in scratch with its three extra set-up waves, and a MODE = 2 copy without them (XW = 0) 24 bytes -- so the setters refuse an N = 24
-// handle / a ragged object with an N = 24 bucket (DESIGN.md section 11).  The MODE = 6 instantiation of the weights is the MODE = 2 one with one more LDS slot
-// (DESIGN.md section 15), and the one of the normals (MODE = 4) has no N = 24 form either (section 13).
-constexpr int kRobotsMaxHorizon = 20;
-
-// A descriptor: the owner's member (of), the element type T, the per-element test (fault), the handle check (forms: the kForms* row; n24: the N = 24 text), the
+// A descriptor: the owner's member (of), the element type T, the per-element test (fault), the handle check (form: its row of kFormRows; n24: the N = 24 text), the
 // hipMalloc label (alloc), and the words of the messages (name: srbdqp_set_<name>, srbdqp_ragged_set_<name>; what, which " on a ragged object" follows; count
 // and unit: the "B > length" messages).  RecordIn has what a kind of one record per QP need not say again: the elements per QP (per_qp), the elements one
-// fault test covers (stride), how a message locates element group i (where), and a refusal of the kind's own beside the table's (beside, or null).
+// fault test covers (stride), how a message locates element group i (where).
 struct RecordIn {
     static constexpr const char* unit = "record";
     static constexpr size_t stride = 1;
     template <class O> static size_t per_qp(const O*) { return 1; }
     template <class O> static std::string where(const O*, size_t i) { return "record " + std::to_string(i); }
-    static const char* beside(const srbdqp_handle*) { return nullptr; }
 };
 
 struct RobotsIn : RecordIn {
@@ -1376,7 +1365,7 @@ struct RobotsIn : RecordIn {
     static constexpr const char* name = "robots";
     static constexpr const char* what = "per-QP robot records";
     static constexpr const char* alloc = "hipMalloc robot records";
-    static constexpr unsigned forms = kFormsSetRobots;
+    static constexpr Form form = Form::Robots;
     template <class O> static PerQp<T>& of(O* o) { return o->robots; }
     static const char* fault(const T* e) { return robot_fault(*e); }
     static std::string count(size_t len) { return std::to_string(len) + " robot records"; }
@@ -1388,7 +1377,7 @@ struct WeightsIn : RecordIn {
     static constexpr const char* name = "weights";
     static constexpr const char* what = "per-QP cost weights";
     static constexpr const char* alloc = "hipMalloc weight records";
-    static constexpr unsigned forms = kFormsSetWeights;
+    static constexpr Form form = Form::Weights;
     template <class O> static PerQp<T>& of(O* o) { return o->weights; }
     static const char* fault(const T* e) { return weights_fault(*e); }
     static std::string count(size_t len) { return std::to_string(len) + " weight records"; }
@@ -1401,7 +1390,7 @@ struct NormalsIn {
     static constexpr const char* what = "contact normals";
     static constexpr const char* alloc = "hipMalloc contact normals";
     static constexpr const char* unit = "block";
-    static constexpr unsigned forms = kFormsSetNormals;
+    static constexpr Form form = Form::Normals;
     static constexpr size_t stride = 3;
     static PerQp<T>& of(srbdqp_handle* h) { return h->normals; }
     static size_t per_qp(const srbdqp_handle* h) { return 12 * (size_t)h->cfg.horizon; }
@@ -1412,8 +1401,6 @@ struct NormalsIn {
     }
     static std::string count(size_t len) { return "contact normals for " + std::to_string(len); }
     static std::string n24(const char* fn) { return std::string(fn) + ": contact normals: not at N = 24 (no instantiation of the general kernel reads them there, DESIGN.md section 13)"; }
-    // (robot records pass kFormsSetNormals to be refused in words of their own)
-    static const char* beside(const srbdqp_handle* h) { return h->robots.dev ? ": refused while per-QP robot records are set (srbdqp_set_robots): no instantiation reads both (DESIGN.md section 13)" : nullptr; }
 };
 
 struct ExtWrenchIn {
@@ -1422,7 +1409,7 @@ struct ExtWrenchIn {
     static constexpr const char* what = "external wrenches";
     static constexpr const char* alloc = "hipMalloc external wrench";
     static constexpr const char* unit = "block";
-    static constexpr unsigned forms = kFormsSetExtWrench;
+    static constexpr Form form = Form::ExtWrench;
     static constexpr size_t stride = 1;
     template <class O> static PerQp<T>& of(O* o) { return o->ext; }
     static size_t per_qp(const srbdqp_handle* h) { return 6 * (size_t)h->cfg.horizon; }
@@ -1435,16 +1422,15 @@ struct ExtWrenchIn {
     static std::string where(const srbdqp_ragged*, size_t i) { return "the wrench at (row " + std::to_string(i / 6) + ", component " + std::to_string(i % 6) + ")"; }
     static std::string count(size_t len) { return "an external wrench for " + std::to_string(len); }
     static std::string n24(const char*) { return "an external wrench: not at N = 24 (no instantiation of the general kernel reads it there, DESIGN.md section 16)"; }
-    static const char* beside(const srbdqp_handle*) { return nullptr; }
 };
 
 // may this handle take side input K?  (a live horizon, rank-aware steps, another side input it does not combine with: a combined mode would be another copy of
 // every instantiation)
 template <class K>
 int check_handle(srbdqp_handle* h, const char* fn) {
-    if (const int rc = require_form(h, fn, K::forms)) return rc;
-    if (h->cfg.horizon > kRobotsMaxHorizon) { h->err = K::n24(fn); return SRBDQP_E_INVALID; }
-    if (const char* why = K::beside(h)) { h->err = std::string(fn) + why; return SRBDQP_E_INVALID; }
+    if (const int rc = require_form(h, fn, forms_of_setter(K::form))) return rc;
+    if (h->cfg.horizon > row(K::form).max_horizon) { h->err = K::n24(fn); return SRBDQP_E_INVALID; }
+    if (K::form == Form::Normals && (state_of(h) & bit(Form::Robots))) { h->err = std::string(fn) + kNormalsOnRobots; return SRBDQP_E_INVALID; }
     return SRBDQP_OK;
 }
 
@@ -1490,12 +1476,10 @@ int quiesce_all_streams(srbdqp_handle* h) {
 
 // fp64 batch solve of B QPs with a side input set: the general kernel, and a record / a block of normals for every QP
 int variant_check_batch(srbdqp_handle* h, int32_t B) {
-    const Variant v = variant_of(h);
-    if (v != Variant::Robots && v != Variant::Normals && v != Variant::Weights && v != Variant::ExtWrench) return SRBDQP_OK;
+    const unsigned side = state_of(h) & kSideInputs;
+    if (!side) return SRBDQP_OK;
     if (!general_allowed(h->cfg)) {
-        h->err = std::string(v == Variant::Robots ? "per-QP robot records" : v == Variant::Weights ? "per-QP cost weights (srbdqp_set_weights)" :
-                             v == Variant::ExtWrench ? "an external wrench (srbdqp_set_external_wrench)" : "contact normals (srbdqp_set_contact_normals)") +
-                 " are read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH while they are set";
+        h->err = std::string(row(refusal_form(side)).noun) + " are read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH while they are set";
         return SRBDQP_E_INVALID;
     }
     if (const int rc = covers_batch<WeightsIn>(h, B)) return rc;      // (weights alone, or beside robot records: each length on its own)
@@ -1552,7 +1536,7 @@ int srbdqp_create(const srbdqp_config* cfg, srbdqp_handle** out) {
         g_create_err = "SRBDQP_FLAG_ANY_HORIZON: a horizon outside {4, 8, 10, 12, 16, 20, 24} runs on the general kernel only (srbdqp_config.kernel = SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH)";
         return SRBDQP_E_INVALID;
     }
-    if ((cfg->flags & SRBDQP_FLAG_RANK_AWARE) && (live || cfg->horizon > kRankAwareMaxHorizon)) {
+    if ((cfg->flags & SRBDQP_FLAG_RANK_AWARE) && (live || cfg->horizon > row(Form::RankAware).max_horizon)) {
         g_create_err = live ? "SRBDQP_FLAG_RANK_AWARE: not at a live horizon of SRBDQP_FLAG_ANY_HORIZON (the rank-aware instantiations are built for N in {4, 8, 10, 12, 16, 20})"
                             : "SRBDQP_FLAG_RANK_AWARE: not at N = 24 (no instantiation of the general kernel without scratch memory there; N in {4, 8, 10, 12, 16, 20})";
         return SRBDQP_E_INVALID;
@@ -1578,7 +1562,7 @@ int srbdqp_create(const srbdqp_config* cfg, srbdqp_handle** out) {
     h->cfg = *cfg;
     if (live) {
         h->live_nstar = horizon_above(cfg->horizon, Horizons{});
-        h->live_name = "wrench_f64_n" + std::to_string(h->live_nstar) + "_h" + std::to_string(cfg->horizon);
+        h->live_name = "wrench_f64_n" + std::to_string(h->live_nstar) + row(Form::Live).suffix + std::to_string(cfg->horizon);
         // the staged calls run the batch instantiation through the HIP launch, as SRBDQP_FLAG_NO_LAT does (no _lat / *_in kernel reads a live horizon): no AQL queue
         h->aql_tried = true;
         h->aql_why = "SRBDQP_FLAG_ANY_HORIZON: a live horizon runs the batch instantiation of the general kernel";
@@ -2173,7 +2157,7 @@ int ragged_device_impl(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp, con
                        int32_t* status, int32_t* iters, void* stream, bool f32) {
     if (!r) return SRBDQP_E_INVALID;
     if (B < 0 || (B > 0 && (!N_per_qp || !x0 || !x_ref || !foot || !contact || !u_out))) { r->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
-    if (f32) for (auto* bh : r->hs) if (bh->live_nstar) { const int rc = refuse(bh, Variant::Live, "an fp32 ragged solve"); r->err = bh->err; return rc; }
+    if (f32) for (auto* bh : r->hs) if (state_of(bh) & bit(Form::Live)) { const int rc = refuse(bh, Form::Live, "an fp32 ragged solve"); r->err = bh->err; return rc; }
     if (const int rc = ragged_side_check<RobotsIn>(r, B, f32)) return rc;
     if (const int rc = ragged_side_check<WeightsIn>(r, B, f32)) return rc;
     if (r->ext.dev) {   // (its length is in rows: f32 here, the rows of this call below)

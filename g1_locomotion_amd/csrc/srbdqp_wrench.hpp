@@ -57,8 +57,22 @@ namespace srbdqp {
 //       reads the whole vector v from LDS for its T^-1 rows, so with the steps spread over 4 waves (3 per wave, tried first) the
 //       broadcast reads alone took ~550 of an iteration's ~1950 cycles (tools/wrench_stamps_staged.py, -DSRBDQP_PROFILE_WADMM)
 // KR64 = entries of an fp64 half row longer than 60 that stay in registers (KREG64 below; wrench_kreg64() has the one exception to 56)
-constexpr int wrench_kreg64(int N, int MODE) { return (MODE == 3 && N == 24) ? SRBDQP_LIVE24_KREG : 56; }
 // CN  = contact normals (MODE = 4): the table L of the contact frames' columns beside J in the persistent strip
+// ---- The modes of wrench_qp (the comment above it says what each computes), described ONCE: the kernel, and srbdqp.hip's planner, launcher and refusal table
+// (kFormRows there), read the numbers, the feature booleans, the LDS slots and the layout from here.
+constexpr int kModeSolve = 0, kModeDump = 1, kModeRobots = 2, kModeLive = 3, kModeNormals = 4, kModeRankAware = 5, kModeWeights = 6, kModeExtWrench = 7;
+// the doubles a mode keeps behind its layout (WrenchSmem::o_end, the launcher adds them): the robot in [0 .. 7] (qp_robot_to_lds), then the weights' and the wrench's
+constexpr int kSlotRobot = 0, kSlotRobotBad = 7, kSlotRs2 = 8, kSlotWeightsBad = 9, kSlotWrenchBad = 10;
+constexpr int wrench_kreg64(int N, int MODE) { return (MODE == kModeLive && N == 24) ? SRBDQP_LIVE24_KREG : 56; }
+template <int MODE>
+struct WrenchMode {
+    static constexpr bool EW = MODE == kModeExtWrench;
+    static constexpr bool WT = MODE == kModeWeights || EW;           // (MODE 7 reads the weights from LDS too)
+    static constexpr bool RB = MODE == kModeRobots || WT;            // (MODE 6 and 7 read the robot from LDS too)
+    static constexpr bool LH = MODE == kModeLive, CN = MODE == kModeNormals, RA = MODE == kModeRankAware;
+    static constexpr bool batch_f64 = RB || LH || CN || RA;          // a side-input or variant mode: the fp64 batch instantiation only
+    static constexpr int xd = EW ? kSlotWrenchBad + 1 : (WT ? kSlotWeightsBad + 1 : (RB ? kSlotRobotBad + 1 : 0));   // one more than the highest slot the mode writes
+};
 // Conditioning guard of a wrench step (phase E below; DESIGN.md, "Nearly collinear stance contacts"): the step is refused -- the QP ends with SRBDQP_NUMERICAL and
 // zero forces -- when a Cholesky pivot of the 3 x 3 Schur complement of its E = Y D^-1 Y' (CN: or of the force block G) is not above this fraction of the diagonal
 // entry of E in the pivot's row.  E loses rank when the stance contact points of the step lie on one line, and the ratio falls as the square of their distance
@@ -175,6 +189,9 @@ struct WrenchSmem {
     static constexpr size_t bytes = (size_t)o_end * sizeof(double);
     static constexpr int lds_wgs = wgs_of(o_end);
 };
+// the layout of mode MODE at horizon N: what wrench_qp carves its LDS by, and what the host sizes and launches it by
+template <int N, int MODE, int TB = 8, int SPW = 5, int XW = 0>
+using WrenchLayout = WrenchSmem<N, TB, SPW, XW, wrench_kreg64(N, MODE), WrenchMode<MODE>::CN>;
 
 // diagnostic builds (-DSRBDQP_PROFILE_WADMM): s_memtime stamps inside the ADMM iteration of the general kernel, summed per
 // segment by thread 0 and written to the second row of the stamp buffer of a B = 1 solve (tools/wrench_stamps_staged.py prints them)
@@ -767,7 +784,7 @@ __device__ __forceinline__ void contact_frame_to_lds(const double (&nr)[3], doub
 // (phase E): its g coordinates are the columns of R, its diagonal block of T is R' S R + I, V = R^-1 Y D^-1 and its part of K^-1 is D^-1 + V'(T^-1 - I) V
 // (apply_kinv, RA).  Nothing inverts E.  Steps above that ratio are what they are in MODE 0, and every such place below reads (RA ? ... : ...) or if constexpr (RA);
 // 6 = solve with the QP's own cost weights weights[16 b .. 16 b + 16) (srbdqp_set_weights, qp_weights_to_lds): sqrt(q_diag) where a.sqrtq goes, r_diag s^2 in an
-// LDS slot that the three uses of a.rs2 read (WT ? RBV[8] : a.rs2).  The robot comes from the LDS slots as in MODE 2 -- the QP's record where `robots` is set,
+// LDS slot that the three uses of a.rs2 read (WT ? RBV[kSlotRs2] : a.rs2).  The robot comes from the LDS slots as in MODE 2 -- the QP's record where `robots` is set,
 // the KArgs values otherwise (args_robot_to_lds) -- so records and weights combine in one instantiation;
 // 7 = solve with the QP's external wrench ext[6 row0 .. 6 row0 + 6 N) (srbdqp_set_external_wrench: a world-frame torque and force on the body per horizon step,
 // DESIGN.md section 16), built on MODE 6: robot and weights from the LDS slots, the QP's records where `robots` / `weights` are set and the KArgs values
@@ -778,31 +795,25 @@ __device__ __forceinline__ void contact_frame_to_lds(const double (&nr)[3], doub
 template <int N, typename R, typename TIO, int MODE, typename TT = double, int SPW = 5, int XW = 0>
 __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* sm, const double* robots = nullptr, const int nl = N, const double* normals = nullptr,
                                           const double* weights = nullptr, const double* ext = nullptr) {
-    using S = WrenchSmem<N, (int)sizeof(TT), SPW, XW, wrench_kreg64(N, MODE), MODE == 4>;
+    using M = WrenchMode<MODE>;
+    using S = WrenchLayout<N, MODE, (int)sizeof(TT), SPW, XW>;
     typedef TT v4t __attribute__((ext_vector_type(4)));
-    static_assert(sizeof(TT) == 8 || (sizeof(R) == 4 && MODE == 0), "fp32 tiles belong to the fp32 path");
+    static_assert(sizeof(TT) == 8 || (sizeof(R) == 4 && MODE == kModeSolve), "fp32 tiles belong to the fp32 path");
     constexpr int n = S::n, m = S::m, NW = S::NW, NWS = S::NWS, BT = S::BT, LT = S::LT, TS = S::TS, CHMAX = S::CHMAX;
-    static_assert(XW == 0 || (sizeof(TT) == 8 && (MODE == 0 || MODE == 3)), "extra set-up waves: fp64 tiles, solve mode");
+    static_assert(XW == 0 || (sizeof(TT) == 8 && (MODE == kModeSolve || MODE == kModeLive)), "extra set-up waves: fp64 tiles, solve mode");
     static_assert((S::o_R % 2) == 0 && (S::o_wb % 2) == 0 && (S::o_tb % 2) == 0 && (S::o_vb % 2) == 0, "16-byte alignment");
     static_assert(S::NT <= 2 * NW || S::WQ >= 1, "");
     static_assert((S::o_zt % 2) == 0, "16-byte alignment of the 6-vectors");
     const double rho_b = unis(SRBDQP_RHO_OF(a, b));   // (per-QP values are wave-uniform: scalar registers, see uni())
-    constexpr bool EW = MODE == 7;
-    constexpr bool WT = MODE == 6 || EW;                             // (MODE 7 reads the weights from LDS too)
-    constexpr bool RB = MODE == 2 || WT;                             // (MODE 6 and 7 read the robot from LDS too)
-    constexpr bool LH = MODE == 3;
-    static_assert(!LH || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && (XW == 0 || N == 24)), "live horizons: the fp64 batch instantiation");
+    constexpr bool EW = M::EW, WT = M::WT, RB = M::RB, LH = M::LH, CN = M::CN, RA = M::RA;
+    static_assert(!M::batch_f64 || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && (XW == 0 || (LH && N == 24))),
+                  "robot records, weights, a wrench, contact normals, live horizons, rank-aware steps: the fp64 batch instantiation");
     const int NL = LH ? nl : N;                                      // the live horizon (wave-uniform: a kernel argument)
-    static_assert(!RB || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && XW == 0), "per-QP robot records: the fp64 batch instantiation");
-    [[maybe_unused]] const double* const RBV = sm + S::o_end;        // MODE 2: the QP's robot (qp_robot_to_lds), from the first barrier on (MODE 6: [8] r_diag s^2, [9] bad weights; MODE 7: [10] bad wrench)
-    constexpr bool CN = MODE == 4;
-    static_assert(!CN || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && XW == 0), "contact normals: the fp64 batch instantiation");
+    [[maybe_unused]] const double* const RBV = sm + S::o_end;        // RB: the QP's robot (qp_robot_to_lds), from the first barrier on, and what WT and EW keep behind it (kSlot*)
     [[maybe_unused]] const double* const LT_ = sm + S::o_L;          // MODE 4: L of every step, from the second barrier on
-    constexpr bool RA = MODE == 5;
-    static_assert(!RA || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && XW == 0), "rank-aware steps: the fp64 batch instantiation");
     const int t = threadIdx.x, lane = t & 63;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-    constexpr bool CSUM = XW > 0 && sizeof(TIO) == 8 && MODE == 0 && S::LT <= 256;   // the low-latency instantiations: the completion word may carry a checksum (KArgs::done_cs)
+    constexpr bool CSUM = XW > 0 && sizeof(TIO) == 8 && MODE == kModeSolve && S::LT <= 256;   // the low-latency instantiations: the completion word may carry a checksum (KArgs::done_cs)
     unsigned long long cs_host = 0;                                  // XOR of the 64-bit patterns this thread stores for the host
     int mcol = lane & 15, kq = lane >> 4;
     TT* T = reinterpret_cast<TT*>(sm + S::o_T);
@@ -853,12 +864,12 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         for (int r = 0; r < RF; ++r) { const int i = t + r * BT; v_ft[r] = gft[i < NL * 12 ? i : 0]; }
         if (t < 13) sm[S::o_x0 + t] = (double)v_x0;
         if constexpr (!WT) { if (t >= 32 && t < 44) sm[S::o_sq + t - 32] = a.sqrtq[t - 32]; }
-        else if constexpr (!EW) { if (w == 0) qp_weights_to_lds(a, weights + (size_t)b * 16, lane, sm + S::o_sq, sm + S::o_end + 8); }
+        else if constexpr (!EW) { if (w == 0) qp_weights_to_lds(a, weights + (size_t)b * 16, lane, sm + S::o_sq, sm + S::o_end + kSlotRs2); }
         else {
             if (w == 0) {
-                if (weights) qp_weights_to_lds(a, weights + (size_t)b * 16, lane, sm + S::o_sq, sm + S::o_end + 8);
-                else args_weights_to_lds(a, lane, sm + S::o_sq, sm + S::o_end + 8);
-                qp_ext_wrench_to_lds<N>(v_ew, lane, sm + S::o_eh, sm + S::o_end + 10, sm + S::o_misc + 2);   // (o_eh: free until the error vector is formed)
+                if (weights) qp_weights_to_lds(a, weights + (size_t)b * 16, lane, sm + S::o_sq, sm + S::o_end + kSlotRs2);
+                else args_weights_to_lds(a, lane, sm + S::o_sq, sm + S::o_end + kSlotRs2);
+                qp_ext_wrench_to_lds<N>(v_ew, lane, sm + S::o_eh, sm + S::o_end + kSlotWrenchBad, sm + S::o_misc + 2);   // (o_eh: free until the error vector is formed)
             }
         }
 #pragma unroll
@@ -868,8 +879,8 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
         if (t < N * 4) sct[t] = (v_ct && (!LH || t < NL * 4)) ? 1 : 0;
         if (a.pcom && t < N * 3) sm[S::o_pcom + t] = (LH && t >= NL * 3) ? 0.0 : (double)v_pc;
         if (t == 0) { sm[S::o_misc] = 0.0; sm[S::o_misc + 1] = 0.0; }
-        if constexpr (RB && !WT) { if (t == 0) qp_robot_to_lds(a, robots + (size_t)b * 8, sm + S::o_end); }
-        if constexpr (WT) { if (t == 0) { if (robots) qp_robot_to_lds(a, robots + (size_t)b * 8, sm + S::o_end); else args_robot_to_lds(a, sm + S::o_end); } }
+        if constexpr (RB && !WT) { if (t == 0) qp_robot_to_lds(a, robots + (size_t)b * 8, sm + S::o_end + kSlotRobot); }
+        if constexpr (WT) { if (t == 0) { if (robots) qp_robot_to_lds(a, robots + (size_t)b * 8, sm + S::o_end + kSlotRobot); else args_robot_to_lds(a, sm + S::o_end + kSlotRobot); } }
         __syncthreads();
         if (!a.pcom && t < N * 3) sm[S::o_pcom + t] = sm[S::o_xref + (t / 3) * 13 + 3 + (t % 3)];
         if constexpr (CN) { if (t < N * 4) contact_frame_to_lds(v_nr, sm + S::o_L + (t >> 2) * 36 + 3 * (t & 3), sm + S::o_misc + 1); }
@@ -993,11 +1004,11 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     };
     lane_roles(lane);
 
-    if constexpr (MODE == 1) { if (na == 0) return; }   // assembly dump of an empty problem: all zeros (the host cleared the buffers)
+    if constexpr (MODE == kModeDump) { if (na == 0) return; }   // assembly dump of an empty problem: all zeros (the host cleared the buffers)
     [[maybe_unused]] bool rb_bad = false;
-    if constexpr (RB) rb_bad = unis(RBV[7]) != 0.0;
-    if constexpr (WT) rb_bad = rb_bad || unis(RBV[9]) != 0.0;       // (MODE 6: weights that are none, the same way)
-    if constexpr (EW) rb_bad = rb_bad || unis(RBV[10]) != 0.0;      // (MODE 7: a wrench that is none, the same way)
+    if constexpr (RB) rb_bad = unis(RBV[kSlotRobotBad]) != 0.0;
+    if constexpr (WT) rb_bad = rb_bad || unis(RBV[kSlotWeightsBad]) != 0.0;       // (MODE 6: weights that are none, the same way)
+    if constexpr (EW) rb_bad = rb_bad || unis(RBV[kSlotWrenchBad]) != 0.0;      // (MODE 7: a wrench that is none, the same way)
     if constexpr (CN) rb_bad = unis(sm[S::o_misc + 1]) != 0.0;      // (MODE 4: a normal that is not one, the same way)
     if (na == 0 || ((RB || CN) && rb_bad)) {   // nothing to solve: all forces 0 (MODE 2, a record that is not a robot: the same, reported as SRBDQP_NUMERICAL)
         for (int c = t; c < n; c += BT) sm[S::o_xs + c] = 0.0;
@@ -1170,7 +1181,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     SRBDQP_STAMP(a, b, 1);
     double qv = 0.0;                                                 // gradient of this lane's variable (needs the G'v tables)
 #ifdef SRBDQP_WRENCH_DEBUG
-    if constexpr (MODE == 1) {   // raw LDS image after the tables (diagnostic builds only)
+    if constexpr (MODE == kModeDump) {   // raw LDS image after the tables (diagnostic builds only)
         double* out = a.P_out + (size_t)b * (S::NG * S::NG);
         for (int i = t; i < S::NG * S::NG && i < S::o_end; i += BT) out[i] = sm[i];
         return;
@@ -1221,7 +1232,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             if (stepok) sm[S::o_x0c + uvar] = x_init;
             __syncthreads();
             const double gtg = gtg_of_x0c();
-            px0 = active_u ? gtg + (WT ? RBV[8] : a.rs2) * x_init : 0.0;
+            px0 = active_u ? gtg + (WT ? RBV[kSlotRs2] : a.rs2) * x_init : 0.0;
         }
     };
     if constexpr (!TSPLIT) gradient_and_warm_start();   // (XW = 2: behind the barrier that joins the tables and E)
@@ -1234,7 +1245,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     }
 
     // ================= per-step wrench blocks: E^-1, V, Bd (registers of the step's lanes) =================
-    const double dxy = unis((WT ? RBV[8] : a.rs2) + a.sigma + 2.0 * rho_b), dz = unis((WT ? RBV[8] : a.rs2) + a.sigma + (4.0 * (RB ? unis(RBV[4]) : a.mu) * (RB ? unis(RBV[4]) : a.mu) + a.rho_fz) * rho_b);
+    const double dxy = unis((WT ? RBV[kSlotRs2] : a.rs2) + a.sigma + 2.0 * rho_b), dz = unis((WT ? RBV[kSlotRs2] : a.rs2) + a.sigma + (4.0 * (RB ? unis(RBV[4]) : a.mu) * (RB ? unis(RBV[4]) : a.mu) + a.rho_fz) * rho_b);
     const double idxy = unis(1.0 / dxy), idz = unis(1.0 / dz);
     // fp32 tiles (3 workgroups per CU, 168 registers): the rows / columns of V and Bd are formed AFTER the factorisation, from
     // the triangle of E^-1 kept in LDS behind the tiles, and held in fp32 from then on.  Formed here they waited in scratch
@@ -1242,11 +1253,11 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     // (rocprofv3 FETCH_SIZE / WRITE_SIZE, round 2).
     // (round 5: fp64 tiles too, for the instantiations compiled at 3 waves per SIMD -- N <= 12 in fp64, every fp32 instantiation on fp64 tiles -- where the
     //  triangle fits the LDS the workgroup has anyway, WrenchSmem::E4_FITS)
-    constexpr bool VBD_LATE = sizeof(TT) == 4 || (S::E4_FITS && MODE != 1 && (CHMAX <= 36 || sizeof(R) == 4));
+    constexpr bool VBD_LATE = sizeof(TT) == 4 || (S::E4_FITS && MODE != kModeDump && (CHMAX <= 36 || sizeof(R) == 4));
     typedef double VS;   // (x_q and its refinement need V and Bd in fp64: rounded to fp32 the refinement contracts 10 x slower)
     VS vrow[6], vcol[6];
     double bjv[4];                                                   // bjv: J[:, u] of the lane's variable and 1 / D_u (apply_kinv)
-    constexpr bool BD_EXPLICIT = (sizeof(R) == 4) || (MODE == 1);     // fp32 iterations and the assembly dump: Bd rows (apply_kinv)
+    constexpr bool BD_EXPLICIT = (sizeof(R) == 4) || (MODE == kModeDump);     // fp32 iterations and the assembly dump: Bd rows (apply_kinv)
     constexpr bool BD_LAST = VBD_LATE && BD_EXPLICIT;   // ... formed after x_q and its refinement (form_bd)
     // explicit Bd rows: fp32 from the start in the fp32-tile kernel (only the iterations use them there; x_q and its refinement
     // run in fp64, where the implicit form is exact enough) -- 12 registers instead of 24 next to the T^-1 row
@@ -1559,7 +1570,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     }
     __syncthreads();
     if constexpr (TSPLIT) gradient_and_warm_start();
-    if constexpr (MODE == 1) { if (sm[S::o_misc] != 0.0) { if (t == 0) a.ub_out[(size_t)b * (N + 1) + N] = -1.0; return; } }
+    if constexpr (MODE == kModeDump) { if (sm[S::o_misc] != 0.0) { if (t == 0) a.ub_out[(size_t)b * (N + 1) + N] = -1.0; return; } }
     if (sm[S::o_misc] != 0.0) {   // degenerate contact geometry: report, return zero forces
         for (int c = t; c < n; c += BT) sm[S::o_xs + c] = 0.0;
         if (a.y_out) for (int i = t; i < (LH ? 20 * NL : m); i += BT) reinterpret_cast<TIO*>(a.y_out)[row0 * 20 + i] = TIO(0);
@@ -1575,7 +1586,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     // chain of diagonal-tile inversions (below).  Wave j owns diagonal tile (j, j) AND the tile above it, (j - 1, j) -- so the next diagonal tile is updated from
     // its owner's registers and inverted without waiting for anybody -- ; wave 0 also owns (0, 2) and (1, 3), wave 2 (0, 3).  In the assembly wave 0 holds (0, 0)
     // only (it inverts it beside the other waves' assembly): its two other tiles are assembled by waves 1 and 3 in their free slot and handed over through LDS.
-    constexpr bool LATP = XW == 2 && NW == 4 && sizeof(TT) == 8 && MODE == 0;
+    constexpr bool LATP = XW == 2 && NW == 4 && sizeof(TT) == 8 && MODE == kModeSolve;
     static_assert(!LATP || (TS <= 3 && S::NT <= 4), "pipelined tile phases: at most 4 x 4 tiles, three slots per wave");
     constexpr int TSL = LATP ? 3 : TS;                                  // tile slots per wave in these phases
     int ta[TSL], tb[TSL];
@@ -1710,7 +1721,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     // the tile store overlays the tables the other waves are still reading.
     [[maybe_unused]] v4d winv0 = (v4d){0.0, 0.0, 0.0, 0.0};
     [[maybe_unused]] bool pre0 = false;
-    if constexpr (XW > 0 && N <= 10 && sizeof(TT) == 8 && MODE == 0) {
+    if constexpr (XW > 0 && N <= 10 && sizeof(TT) == 8 && MODE == kModeSolve) {
         if (ta[0] == 0 && tb[0] == 0) {                              // (wave-uniform)
             bool ok0;
             winv0 = diag16_invert_dpp(acc[0], lane, ok0, sm + S::o_pre);
@@ -1725,7 +1736,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     SRBDQP_STAMP(a, b, 3);
     WAVE_ARRIVE(a, w, lane, 14);
     __syncthreads();
-    if constexpr (MODE == 1) {   // assembly dump (tests): T dense [NG][NG], then q[12N], V rows / Bd rows per lane, goff
+    if constexpr (MODE == kModeDump) {   // assembly dump (tests): T dense [NG][NG], then q[12N], V rows / Bd rows per lane, goff
         double* out = a.P_out + (size_t)b * (S::NG * S::NG);
 #pragma unroll
         for (int s = 0; s < TSL; ++s) {
@@ -2110,7 +2121,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                 const double gtg = gtg_of_x0c();
                 // (K's diagonal part formed again from the slots, behind the barriers: held from dxy / dz above it cost a register pair across K^-1)
                 const double mu_l = RB ? RBV[4] : a.mu;
-                const double dl = RBV[8] + a.sigma + ((ax < 2) ? 2.0 : fma(4.0 * mu_l, mu_l, a.rho_fz)) * rho_b;
+                const double dl = RBV[kSlotRs2] + a.sigma + ((ax < 2) ? 2.0 : fma(4.0 * mu_l, mu_l, a.rho_fz)) * rho_b;
                 const double rres = active_u ? fma(dl, xq, gtg + qv) : 0.0;
                 __syncthreads();   // (the tables' last readers, in front of the v buffers that overlay them)
                 for (int i = t; i < 2 * S::VB; i += LT) vb[i] = 0.0;
@@ -2144,7 +2155,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     if (stepok) sm[S::o_x0c + uvar] = x_init;
                     __syncthreads();
                     const double gtg = gtg_of_x0c();
-                    px0 = active_u ? gtg + (WT ? RBV[8] : a.rs2) * x_init : 0.0;
+                    px0 = active_u ? gtg + (WT ? RBV[kSlotRs2] : a.rs2) * x_init : 0.0;
                     __syncthreads();
                 }
             }
@@ -2413,7 +2424,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                 if constexpr (EW) {   // the step's [I_w^-1 tau; f / m] from the caller's array again (sj is in scaled newtons); none for a QP whose wrench or records are none
                     // (`pushed` is one value per QP, three broadcast reads of the slots.  A QP with a bad wrench forms e from the caller's raw values, NaN perhaps,
                     //  and the select drops it: IEEE semantics, which the library is built with -- no -ffast-math, under which a select on NaN is no barrier)
-                    const bool pushed = RBV[7] == 0.0 && RBV[9] == 0.0 && RBV[10] == 0.0;
+                    const bool pushed = RBV[kSlotRobotBad] == 0.0 && RBV[kSlotWeightsBad] == 0.0 && RBV[kSlotWrenchBad] == 0.0;
                     const double* ge = ext + (row0 + (size_t)j) * 6;
                     const double e = ext_wrench_accel(ge, comp, sm[S::o_tm + j * 9], sm[S::o_tm + j * 9 + 1], RBV[1], RBV[2], RBV[3], RBV[0]);
                     s += pushed ? e / a.s : 0.0;
@@ -2527,7 +2538,7 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, SPW, XW>::BT), WPS) void srbdqp_w
 // workgroup: the same under a dispatch order, in a restart pass and in a ragged bucket).  A second kernel argument: KArgs keeps its size (the batch-1 *_in
 // kernels' argument segment, tests/test_aql_contract_cpu.py), and the restart, deferred and ragged launches that copy a KArgs reach it through the launcher.
 // (enable_if: the name with MODE = 0 / 1 keeps naming the one-argument kernel alone)
-template <int N, typename R, typename TIO, int MODE, int WPS, typename TT = double, int SPW = 5, int XW = 0, typename = std::enable_if_t<MODE == 2>>
+template <int N, typename R, typename TIO, int MODE, int WPS, typename TT = double, int SPW = 5, int XW = 0, typename = std::enable_if_t<MODE == kModeRobots>>
 __global__ __launch_bounds__((WrenchSmem<N, 8, SPW, XW>::BT), WPS) void srbdqp_wrench_kernel(KArgs a, const double* __restrict__ robots) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     if (!wrench_block_in_launch<N>(a)) return;
@@ -2538,7 +2549,7 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, SPW, XW>::BT), WPS) void srbdqp_w
 
 // ... MODE = 3: a live horizon nl <= N (SRBDQP_FLAG_ANY_HORIZON), as the second kernel argument for the same reasons: KArgs keeps its size, and every launch of a
 // solve -- restart, deferred and ragged passes included -- reaches it through the launcher.
-template <int N, typename R, typename TIO, int MODE, int WPS, typename TT = double, int SPW = 5, int XW = 0, typename = std::enable_if_t<MODE == 3>>
+template <int N, typename R, typename TIO, int MODE, int WPS, typename TT = double, int SPW = 5, int XW = 0, typename = std::enable_if_t<MODE == kModeLive>>
 __global__ __launch_bounds__((WrenchSmem<N, 8, SPW, XW>::BT), WPS) void srbdqp_wrench_kernel(KArgs a, const int nl) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     if (!wrench_block_in_launch<N>(a)) return;
@@ -2554,7 +2565,7 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, 5, 0>::BT), WPS) void srbdqp_wren
     extern __shared__ __attribute__((aligned(16))) double sm[];
     if (!wrench_block_in_launch<N>(a)) return;
     if (wrench_block_has_work(a))
-        wrench_qp<N, double, double, 4, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm, nullptr, N, normals);
+        wrench_qp<N, double, double, kModeNormals, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm, nullptr, N, normals);
     signal_done(a);
 }
 
@@ -2565,7 +2576,7 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, 5, 0>::BT), WPS) void srbdqp_wren
     extern __shared__ __attribute__((aligned(16))) double sm[];
     if (!wrench_block_in_launch<N>(a)) return;
     if (wrench_block_has_work(a))
-        wrench_qp<N, double, double, 6, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm, robots, N, nullptr, weights);
+        wrench_qp<N, double, double, kModeWeights, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm, robots, N, nullptr, weights);
     signal_done(a);
 }
 
@@ -2578,7 +2589,7 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, 5, 0>::BT), WPS) void srbdqp_wren
     extern __shared__ __attribute__((aligned(16))) double sm[];
     if (!wrench_block_in_launch<N>(a)) return;
     if (wrench_block_has_work(a))
-        wrench_qp<N, double, double, 7, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm, robots, N, nullptr, weights, ext);
+        wrench_qp<N, double, double, kModeExtWrench, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm, robots, N, nullptr, weights, ext);
     signal_done(a);
 }
 
@@ -2589,7 +2600,7 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, 5, 0>::BT), WPS) void srbdqp_wren
     extern __shared__ __attribute__((aligned(16))) double sm[];
     if (!wrench_block_in_launch<N>(a)) return;
     if (wrench_block_has_work(a))
-        wrench_qp<N, double, double, 5, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm);
+        wrench_qp<N, double, double, kModeRankAware, double, 5, 0>(a, SRBDQP_QP_INDEX(a), sm);
     signal_done(a);
 }
 
@@ -2598,7 +2609,7 @@ template <int N, int XW>
 __global__ __launch_bounds__((WrenchSmem<N, 8, 5, XW>::BT), 1) void srbdqp_wrench_kernel_in(KArgs a, StagedIn<N> in) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     (void)in;                                            // (read through staged_in_base(): a.inline_in is set)
-    wrench_qp<N, double, double, 0, double, 5, XW>(a, 0, sm);
+    wrench_qp<N, double, double, kModeSolve, double, 5, XW>(a, 0, sm);
     if (!(XW > 0 && a.done_cs)) signal_done(a);
 }
 

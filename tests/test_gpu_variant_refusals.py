@@ -1,7 +1,7 @@
-"""Which C-ABI call has a form for which variant of the general kernel (srbdqp.hip, `Variant` and the masks of `require_form`): a handle is plain, or has robot
+"""Which C-ABI call has a form for which variant of the general kernel (srbdqp.hip, `kFormRows`, `state_of` and the sets of `require_form`): a handle is plain, or has robot
 records set, or cost weights set, or contact normals set, or an external wrench set, or a live horizon (SRBDQP_FLAG_ANY_HORIZON), or rank-aware steps
-(SRBDQP_FLAG_RANK_AWARE) -- never two of them, except robot records, cost weights and the wrench beside one another (what only weights or only the wrench
-show is in test_gpu_weights.py and test_gpu_ext_wrench.py).  Through the
+(SRBDQP_FLAG_RANK_AWARE) -- never two of them, except robot records, cost weights and the wrench beside one another (the four combined states have a walk of
+their own below; what only weights or only the wrench show is in test_gpu_weights.py and test_gpu_ext_wrench.py).  Through the
 Python bindings, on one handle per variant, every entry point of the table below either returns SRBDQP_E_INVALID with a message that names the call and ends in
 the variant's fixed text, or returns SRBDQP_OK.  Nothing here looks at numbers: the variants' own suites do (test_gpu_side_inputs.py, test_gpu_contact_normals.py,
 test_gpu_any_horizon.py, test_gpu_rank_aware.py).  The smallest shapes that reach every branch: N = 4 (a live horizon: 3, which runs on N* = 4), two QPs of full
@@ -170,6 +170,61 @@ def test_every_call_refuses_or_accepts_the_variant(torch_first, built_lib, varia
             assert _refusal(calls[other]) is None
             assert _refusal(calls["srbdqp_solve_batch_f64"]) is None and eng.kernel_name() == ("wrench_f64_n4_rb" if variant == "normals" else "wrench_f64_n4_cn")
         assert _refusal(calls["srbdqp_solve_batch_f64"]) is None
+
+
+# The four states with more than one side input, and what every call of REFUSES answers on a handle in each: None = SRBDQP_OK, a key of TAIL, or NOR =
+# NORMALS_ON_ROBOTS.  Printed by the library of the commit before the forms became one table (SRBDQP_LIB) and pasted in: a refusal names the first input
+# present in the order records, weights, wrench; the normals setters answer records in their own words; a solve runs the wrench's kernel if a wrench is set.
+COMBINED = (("robots", "weights"), ("robots", "ext_wrench"), ("weights", "ext_wrench"), ("robots", "weights", "ext_wrench"))
+COMBINED_KERNEL = ("wrench_f64_n4_wt", "wrench_f64_n4_ew", "wrench_f64_n4_ew", "wrench_f64_n4_ew")
+NOR = "normals_on_robots"
+_OK4, _FIRST = (None, None, None, None), ("robots", "robots", "weights", "robots")
+ANSWERS = {
+    "srbdqp_solve_batch_f64": _OK4,
+    "srbdqp_solve_batch_device_f64": _OK4,
+    "srbdqp_solve_staged_f64": _FIRST,
+    "srbdqp_update_f64": _FIRST,
+    "srbdqp_prepare_staged_f64": _FIRST,
+    "srbdqp_solve_prepared_f64": _FIRST,
+    "srbdqp_solve_batch_f32": _FIRST,
+    "srbdqp_solve_batch_device_f32": _FIRST,
+    "srbdqp_assemble_f64": _FIRST,
+    "srbdqp_assemble_wrench_f64": _FIRST,
+    "srbdqp_set_robots": _OK4,
+    "srbdqp_set_robots_device": _OK4,
+    "srbdqp_set_weights": _OK4,
+    "srbdqp_set_weights_device": _OK4,
+    "srbdqp_set_contact_normals": (NOR, NOR, "weights", NOR),
+    "srbdqp_set_contact_normals_device": (NOR, NOR, "weights", NOR),
+    "srbdqp_set_external_wrench": _OK4,
+    "srbdqp_set_external_wrench_device": _OK4,
+}
+
+
+@pytest.mark.parametrize("state", COMBINED, ids="+".join)
+def test_every_call_on_combined_side_inputs(torch_first, built_lib, state):
+    """One handle with two or three side inputs set: every call of REFUSES, in its order, answers exactly what ANSWERS says, and each fp64 batch solve reports
+    the kernel of COMBINED_KERNEL.  The setters of an input the state lacks are made as set-then-clear, so the state holds through the walk."""
+    from g1_locomotion_amd import _lib
+    own = dict(robots=_RB, weights=_WT, ext_wrench=_EW)
+    col = COMBINED.index(state)
+    eng, N = _engine("plain")
+    with eng:
+        calls = _calls(torch_first, eng, N, sum((own[k] for k in own if k not in state), ()))
+        assert list(calls) == list(REFUSES) == list(ANSWERS)
+        for k in state:
+            calls[own[k][0]]()
+        for name, answers in ANSWERS.items():
+            msg = _refusal(calls[name])
+            print(f"{'+'.join(state):26s} {name:34s} -> {msg or 'SRBDQP_OK'}")
+            if answers[col] is None:
+                assert msg is None, (state, name, msg)
+                if name in ("srbdqp_solve_batch_f64", "srbdqp_solve_batch_device_f64"):
+                    print(f"{'+'.join(state):26s} {'kernel_name':34s} -> {eng.kernel_name()}")
+                    assert eng.kernel_name() == COMBINED_KERNEL[col], (state, name, eng.kernel_name())
+            else:
+                tail = NORMALS_ON_ROBOTS if answers[col] == NOR else TAIL[answers[col]]
+                assert msg == f"srbdqp error {_lib.E_INVALID}: {name}: {tail}", (state, name, msg)
 
 
 def test_ragged_objects(torch_first, built_lib):
