@@ -31,19 +31,6 @@ HORIZONS = (4, 8, 10, 12, 16, 20, 24)   # horizons with instantiations of their 
 PENDING = 0
 KERNEL_AUTO, KERNEL_COMPACT, KERNEL_SPLIT, KERNEL_WAVE, KERNEL_WRENCH = 0, 3, 4, 5, 6   # 1, 2: the retired round-1 baselines
 
-EXPORTS = (
-    "srbdqp_default_config", "srbdqp_create", "srbdqp_destroy", "srbdqp_last_error",
-    "srbdqp_solve_batch_f64", "srbdqp_solve_batch_device_f64", "srbdqp_solve_batch_f32", "srbdqp_solve_batch_device_f32",
-    "srbdqp_assemble_f64", "srbdqp_assemble_wrench_f64",
-    "srbdqp_ragged_create", "srbdqp_ragged_destroy", "srbdqp_ragged_last_error", "srbdqp_ragged_flush", "srbdqp_solve_ragged_device_f64", "srbdqp_solve_ragged_f64",
-    "srbdqp_solve_ragged_device_f32", "srbdqp_solve_ragged_f32", "srbdqp_solve_ragged_warm_device_f64", "srbdqp_solve_ragged_warm_device_f32",
-    "srbdqp_set_schedule_hint", "srbdqp_set_robots", "srbdqp_set_robots_device", "srbdqp_set_contact_normals", "srbdqp_set_contact_normals_device", "srbdqp_ragged_set_robots", "srbdqp_ragged_set_robots_device", "srbdqp_set_weights", "srbdqp_set_weights_device", "srbdqp_ragged_set_weights", "srbdqp_ragged_set_weights_device", "srbdqp_set_external_wrench", "srbdqp_set_external_wrench_device", "srbdqp_ragged_set_external_wrench", "srbdqp_ragged_set_external_wrench_device", "srbdqp_flush", "srbdqp_shard_range", "srbdqp_gather_u0_f64", "srbdqp_stage_ptrs", "srbdqp_solve_staged_f64", "srbdqp_update_f64", "srbdqp_prepare_staged_f64", "srbdqp_solve_prepared_f64", "srbdqp_set_stamp_buffer", "srbdqp_synchronize", "srbdqp_last_kernel_ms", "srbdqp_last_kernel_parts_ms", "srbdqp_kernel_name", "srbdqp_batch1_launch_path", "srbdqp_version",
-    # include/srbdqp_cascade.h
-    "srbdqp_swing_f64", "srbdqp_swing_device_f64", "srbdqp_wbid_reference_f64", "srbdqp_wbid_reference_device_f64",
-    "srbdqp_mpc_inputs_f64", "srbdqp_mpc_inputs_device_f64",
-)
-
-
 class SrbdqpError(RuntimeError):
     pass
 
@@ -156,6 +143,83 @@ class Stage(C.Structure):
         "x0", "x_ref", "foot", "contact", "pcom", "warm_u", "warm_y", "u", "x", "y", "status", "iters")]
 
 
+# The C-ABI, name -> (restype, argtypes), in the order and the groups of the two headers: the one list of it on the Python side.  load() applies it,
+# EXPORTS is its keys, tools/benchlib.py binds a second build of the library from it, and tests/test_cabi_cpu.py holds every entry against its declaration.
+H = C.c_void_p                       # srbdqp_handle* / srbdqp_ragged*
+dp = u8p = i32p = C.c_void_p         # raw addresses: numpy or device pointers
+_vp, _int, _i32, _i64, _f64 = C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.c_double
+_CFG = C.POINTER(Config)
+_QP = [dp, dp, dp, u8p]                                  # x0, x_ref, foot, contact
+_BATCH = [H, _i32, *_QP, dp, dp, dp, dp, dp, dp, i32p, i32p]   # ... pcom, warm_u, warm_y, u, x, y, status, iters
+_ASSEMBLE = [H, _i32, *_QP, dp, dp, dp, dp, dp]
+_RAGGED = [H, _i32, i32p, *_QP, dp, dp, i32p, i32p]      # B, N_per_qp, ..., u, x, status, iters
+_RAGGED_WARM = [H, _i32, i32p, *_QP, dp, dp, dp, dp, dp, i32p, i32p, _vp]   # ..., warm_u, warm_y, u, x, y, status, iters, stream
+_SIDE = (_int, [H, _vp, _i32])                           # every per-QP side-input setter, host and device form: records, length
+_SWING = [H, _i64, dp, dp, dp, dp, _f64, _f64, dp, dp, dp, dp]
+_WBID = [H, _i64, dp, dp, dp, _i32, dp, dp, dp, dp]
+_INPUTS = [H, _i64, dp, dp, dp, dp, u8p, C.POINTER(Gait), dp, dp, u8p, dp, dp]
+SIGNATURES = {
+    # include/srbdqp.h -- config, handle
+    "srbdqp_default_config": (_int, [_CFG]),
+    "srbdqp_create": (_int, [_CFG, C.POINTER(H)]),
+    "srbdqp_destroy": (_int, [H]),
+    "srbdqp_last_error": (C.c_char_p, [H]),
+    # batch solves and the assembly dumps
+    "srbdqp_solve_batch_f64": (_int, _BATCH),
+    "srbdqp_solve_batch_device_f64": (_int, _BATCH + [_vp]),
+    "srbdqp_solve_batch_f32": (_int, _BATCH),
+    "srbdqp_solve_batch_device_f32": (_int, _BATCH + [_vp]),
+    "srbdqp_assemble_f64": (_int, _ASSEMBLE),
+    "srbdqp_assemble_wrench_f64": (_int, _ASSEMBLE),
+    # ragged fleets
+    "srbdqp_ragged_create": (_int, [_CFG, i32p, _i32, C.POINTER(H)]),
+    "srbdqp_ragged_destroy": (_int, [H]),
+    "srbdqp_ragged_last_error": (C.c_char_p, [H]),
+    "srbdqp_solve_ragged_device_f64": (_int, _RAGGED + [_vp]),
+    "srbdqp_solve_ragged_f64": (_int, _RAGGED),
+    "srbdqp_ragged_flush": (_int, [H, _vp]),
+    "srbdqp_solve_ragged_device_f32": (_int, _RAGGED + [_vp]),
+    "srbdqp_solve_ragged_f32": (_int, _RAGGED),
+    "srbdqp_solve_ragged_warm_device_f64": (_int, _RAGGED_WARM),
+    "srbdqp_solve_ragged_warm_device_f32": (_int, _RAGGED_WARM),
+    "srbdqp_ragged_set_robots": _SIDE, "srbdqp_ragged_set_robots_device": _SIDE,
+    "srbdqp_ragged_set_weights": _SIDE, "srbdqp_ragged_set_weights_device": _SIDE,
+    "srbdqp_ragged_set_external_wrench": _SIDE, "srbdqp_ragged_set_external_wrench_device": _SIDE,
+    # per-handle settings
+    "srbdqp_set_schedule_hint": (_int, [H, i32p, _i32]),
+    "srbdqp_set_robots": _SIDE, "srbdqp_set_robots_device": _SIDE,
+    "srbdqp_set_weights": _SIDE, "srbdqp_set_weights_device": _SIDE,
+    "srbdqp_set_external_wrench": _SIDE, "srbdqp_set_external_wrench_device": _SIDE,
+    "srbdqp_set_contact_normals": _SIDE, "srbdqp_set_contact_normals_device": _SIDE,
+    "srbdqp_flush": (_int, [H, _vp]),
+    # sharding
+    "srbdqp_shard_range": (_int, [_i64, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
+    "srbdqp_gather_u0_f64": (_int, [H, dp, _i64, dp, _vp, _vp]),
+    # staged (low-latency) calls
+    "srbdqp_stage_ptrs": (_int, [H, C.POINTER(Stage)]),
+    "srbdqp_solve_staged_f64": (_int, [H, _i32, _i32, _i32, _i32, _i32]),
+    "srbdqp_update_f64": (_int, [H, *_QP, dp, dp, dp, dp, i32p, i32p]),
+    "srbdqp_prepare_staged_f64": (_int, [H, _i32, _i32]),
+    "srbdqp_solve_prepared_f64": (_int, [H, _i32, _i32, _i32]),
+    # diagnostics
+    "srbdqp_set_stamp_buffer": (_int, [H, _vp]),
+    "srbdqp_synchronize": (_int, [H]),
+    "srbdqp_last_kernel_ms": (_f64, [H]),
+    "srbdqp_last_kernel_parts_ms": (_int, [H, C.POINTER(_f64), C.POINTER(_f64)]),
+    "srbdqp_kernel_name": (C.c_char_p, [H]),
+    "srbdqp_batch1_launch_path": (C.c_char_p, [H]),
+    "srbdqp_version": (C.c_char_p, []),
+    # include/srbdqp_cascade.h -- the steps either side of the QP
+    "srbdqp_swing_f64": (_int, _SWING),
+    "srbdqp_swing_device_f64": (_int, _SWING + [_vp]),
+    "srbdqp_wbid_reference_f64": (_int, _WBID),
+    "srbdqp_wbid_reference_device_f64": (_int, _WBID + [_vp]),
+    "srbdqp_mpc_inputs_f64": (_int, _INPUTS),
+    "srbdqp_mpc_inputs_device_f64": (_int, _INPUTS + [_vp]),
+}
+EXPORTS = tuple(SIGNATURES)
+
+
 _lib = None
 
 
@@ -196,97 +260,9 @@ def load():
             "(hipcc --offload-arch=gfx950).  g1_locomotion_amd has no CPU fallback.")
     _preload_shared_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    H = C.c_void_p
-    dp, u8p, i32p = C.c_void_p, C.c_void_p, C.c_void_p   # raw addresses: numpy or device pointers
-    lib.srbdqp_default_config.argtypes = [C.POINTER(Config)]
-    lib.srbdqp_default_config.restype = C.c_int
-    lib.srbdqp_create.argtypes = [C.POINTER(Config), C.POINTER(H)]
-    lib.srbdqp_create.restype = C.c_int
-    lib.srbdqp_destroy.argtypes = [H]
-    lib.srbdqp_destroy.restype = C.c_int
-    lib.srbdqp_last_error.argtypes = [H]
-    lib.srbdqp_last_error.restype = C.c_char_p
-    lib.srbdqp_solve_batch_f64.argtypes = [H, C.c_int32, dp, dp, dp, u8p, dp, dp, dp, dp, dp, dp, i32p, i32p]
-    lib.srbdqp_solve_batch_f64.restype = C.c_int
-    lib.srbdqp_solve_batch_device_f64.argtypes = [H, C.c_int32, dp, dp, dp, u8p, dp, dp, dp, dp, dp, dp, i32p, i32p, C.c_void_p]
-    lib.srbdqp_solve_batch_device_f64.restype = C.c_int
-    lib.srbdqp_solve_batch_f32.argtypes = [H, C.c_int32, dp, dp, dp, u8p, dp, dp, dp, dp, dp, dp, i32p, i32p]
-    lib.srbdqp_solve_batch_f32.restype = C.c_int
-    lib.srbdqp_solve_batch_device_f32.argtypes = [H, C.c_int32, dp, dp, dp, u8p, dp, dp, dp, dp, dp, dp, i32p, i32p, C.c_void_p]
-    lib.srbdqp_solve_batch_device_f32.restype = C.c_int
-    lib.srbdqp_assemble_f64.argtypes = [H, C.c_int32, dp, dp, dp, u8p, dp, dp, dp, dp, dp]
-    lib.srbdqp_assemble_f64.restype = C.c_int
-    lib.srbdqp_assemble_wrench_f64.argtypes = [H, C.c_int32, dp, dp, dp, u8p, dp, dp, dp, dp, dp]
-    lib.srbdqp_assemble_wrench_f64.restype = C.c_int
-    lib.srbdqp_ragged_create.argtypes = [C.POINTER(Config), C.c_void_p, C.c_int32, C.POINTER(H)]
-    lib.srbdqp_ragged_create.restype = C.c_int
-    lib.srbdqp_ragged_destroy.argtypes = [H]
-    lib.srbdqp_ragged_destroy.restype = C.c_int
-    lib.srbdqp_ragged_flush.argtypes = [H, C.c_void_p]
-    lib.srbdqp_ragged_flush.restype = C.c_int
-    lib.srbdqp_ragged_last_error.argtypes = [H]
-    lib.srbdqp_ragged_last_error.restype = C.c_char_p
-    lib.srbdqp_solve_ragged_device_f64.argtypes = [H, C.c_int32, C.c_void_p, dp, dp, dp, u8p, dp, dp, i32p, i32p, C.c_void_p]
-    lib.srbdqp_solve_ragged_device_f64.restype = C.c_int
-    lib.srbdqp_solve_ragged_f64.argtypes = [H, C.c_int32, C.c_void_p, dp, dp, dp, u8p, dp, dp, i32p, i32p]
-    lib.srbdqp_solve_ragged_device_f32.argtypes = [H, C.c_int32, C.c_void_p, dp, dp, dp, u8p, dp, dp, i32p, i32p, C.c_void_p]
-    lib.srbdqp_solve_ragged_device_f32.restype = C.c_int
-    lib.srbdqp_solve_ragged_f32.argtypes = [H, C.c_int32, C.c_void_p, dp, dp, dp, u8p, dp, dp, i32p, i32p]
-    lib.srbdqp_solve_ragged_f32.restype = C.c_int
-    for _fn in (lib.srbdqp_solve_ragged_warm_device_f64, lib.srbdqp_solve_ragged_warm_device_f32):
-        _fn.argtypes = [H, C.c_int32, C.c_void_p, dp, dp, dp, u8p, dp, dp, dp, dp, dp, i32p, i32p, C.c_void_p]
-        _fn.restype = C.c_int
-    lib.srbdqp_solve_ragged_f64.restype = C.c_int
-    lib.srbdqp_set_schedule_hint.argtypes = [H, C.c_void_p, C.c_int32]
-    lib.srbdqp_set_schedule_hint.restype = C.c_int
-    for _fn in (lib.srbdqp_set_robots, lib.srbdqp_set_robots_device, lib.srbdqp_ragged_set_robots, lib.srbdqp_ragged_set_robots_device,
-                lib.srbdqp_set_weights, lib.srbdqp_set_weights_device, lib.srbdqp_ragged_set_weights, lib.srbdqp_ragged_set_weights_device,
-                lib.srbdqp_set_external_wrench, lib.srbdqp_set_external_wrench_device, lib.srbdqp_ragged_set_external_wrench, lib.srbdqp_ragged_set_external_wrench_device,
-                lib.srbdqp_set_contact_normals, lib.srbdqp_set_contact_normals_device):
-        _fn.argtypes = [H, C.c_void_p, C.c_int32]
-        _fn.restype = C.c_int
-    lib.srbdqp_flush.argtypes = [H, C.c_void_p]
-    lib.srbdqp_flush.restype = C.c_int
-    lib.srbdqp_shard_range.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.srbdqp_shard_range.restype = C.c_int
-    lib.srbdqp_gather_u0_f64.argtypes = [H, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.srbdqp_gather_u0_f64.restype = C.c_int
-    lib.srbdqp_stage_ptrs.argtypes = [H, C.POINTER(Stage)]
-    lib.srbdqp_stage_ptrs.restype = C.c_int
-    lib.srbdqp_solve_staged_f64.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-    lib.srbdqp_solve_staged_f64.restype = C.c_int
-    lib.srbdqp_update_f64.argtypes = [H, dp, dp, dp, u8p, dp, dp, dp, dp, i32p, i32p]
-    lib.srbdqp_update_f64.restype = C.c_int
-    lib.srbdqp_prepare_staged_f64.argtypes = [H, C.c_int32, C.c_int32]
-    lib.srbdqp_prepare_staged_f64.restype = C.c_int
-    lib.srbdqp_solve_prepared_f64.argtypes = [H, C.c_int32, C.c_int32, C.c_int32]
-    lib.srbdqp_solve_prepared_f64.restype = C.c_int
-    lib.srbdqp_set_stamp_buffer.argtypes = [H, C.c_void_p]
-    lib.srbdqp_set_stamp_buffer.restype = C.c_int
-    lib.srbdqp_synchronize.argtypes = [H]
-    lib.srbdqp_synchronize.restype = C.c_int
-    lib.srbdqp_last_kernel_ms.argtypes = [H]
-    lib.srbdqp_last_kernel_ms.restype = C.c_double
-    lib.srbdqp_last_kernel_parts_ms.argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    lib.srbdqp_last_kernel_parts_ms.restype = C.c_int
-    lib.srbdqp_kernel_name.argtypes = [H]
-    lib.srbdqp_kernel_name.restype = C.c_char_p
-    lib.srbdqp_batch1_launch_path.argtypes = [H]
-    lib.srbdqp_batch1_launch_path.restype = C.c_char_p
-    lib.srbdqp_swing_f64.argtypes = [H, C.c_int64, dp, dp, dp, dp, C.c_double, C.c_double, dp, dp, dp, dp]
-    lib.srbdqp_swing_f64.restype = C.c_int
-    lib.srbdqp_swing_device_f64.argtypes = [H, C.c_int64, dp, dp, dp, dp, C.c_double, C.c_double, dp, dp, dp, dp, C.c_void_p]
-    lib.srbdqp_swing_device_f64.restype = C.c_int
-    lib.srbdqp_wbid_reference_f64.argtypes = [H, C.c_int64, dp, dp, dp, C.c_int32, dp, dp, dp, dp]
-    lib.srbdqp_wbid_reference_f64.restype = C.c_int
-    lib.srbdqp_wbid_reference_device_f64.argtypes = [H, C.c_int64, dp, dp, dp, C.c_int32, dp, dp, dp, dp, C.c_void_p]
-    lib.srbdqp_wbid_reference_device_f64.restype = C.c_int
-    lib.srbdqp_mpc_inputs_f64.argtypes = [H, C.c_int64, dp, dp, dp, dp, C.c_void_p, C.POINTER(Gait), dp, dp, C.c_void_p, dp, dp]
-    lib.srbdqp_mpc_inputs_f64.restype = C.c_int
-    lib.srbdqp_mpc_inputs_device_f64.argtypes = [H, C.c_int64, dp, dp, dp, dp, C.c_void_p, C.POINTER(Gait), dp, dp, C.c_void_p, dp, dp, C.c_void_p]
-    lib.srbdqp_mpc_inputs_device_f64.restype = C.c_int
-    lib.srbdqp_version.argtypes = []
-    lib.srbdqp_version.restype = C.c_char_p
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

@@ -96,53 +96,39 @@ def _as(a, dtype, shape, name):
     return arr
 
 
-class BatchMPC:
-    """B independent SRBD convex-MPC QPs per call.  One instance <-> one HIP stream <-> one thread."""
+def _apply_overrides(cfg, overrides):
+    """Keyword overrides of srbdqp_config fields, written into cfg: a scalar in the field's own type, q_diag (13) and inertia (3) element by element."""
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise TypeError(f"unknown srbdqp_config field {k!r}")
+        if k in ("q_diag", "inertia"):
+            arr = getattr(cfg, k)
+            if len(v) != len(arr):
+                raise ValueError(f"{k}: expected {len(arr)} values")
+            for i, x in enumerate(v):
+                arr[i] = float(x)
+        else:
+            setattr(cfg, k, type(getattr(cfg, k))(v))
+    return cfg
 
-    def __init__(self, horizon: int = 10, dt: float = 0.04, device: int = 0, kernel: int = _lib.KERNEL_AUTO,
-                 timing: bool = False, rank_aware: bool = False, **overrides):
-        """rank_aware=True sets SRBDQP_FLAG_RANK_AWARE (include/srbdqp.h): on the general kernel, steps whose stance contact points lie on or near one line --
-        feet in tandem, point feet -- are solved in rank-aware coordinates instead of ending the QP with status -1 (fp64 solves, N <= 20, flat ground, one
-        robot).  flags=_lib.FLAG_RANK_AWARE does the same."""
-        lib = _lib.load()
-        cfg = _lib.default_config()
-        cfg.horizon = int(horizon)
-        cfg.dt = float(dt)
-        cfg.device = int(device)
-        cfg.kernel = int(kernel)
-        cfg.flags = _lib.FLAG_TIMING if timing else 0
-        for k, v in overrides.items():
-            if not hasattr(cfg, k):
-                raise TypeError(f"unknown srbdqp_config field {k!r}")
-            if k in ("q_diag", "inertia"):
-                arr = getattr(cfg, k)
-                if len(v) != len(arr):
-                    raise ValueError(f"{k}: expected {len(arr)} values")
-                for i, x in enumerate(v):
-                    arr[i] = float(x)
-            else:
-                setattr(cfg, k, type(getattr(cfg, k))(v))
-        if cfg.horizon not in _lib.HORIZONS:        # any other horizon 1 ... 24: the general kernel's live-horizon mode (include/srbdqp.h, SRBDQP_FLAG_ANY_HORIZON)
-            cfg.flags |= _lib.FLAG_ANY_HORIZON
-        if rank_aware:                              # (after the overrides: flags= and the keyword add up)
-            cfg.flags |= _lib.FLAG_RANK_AWARE
-        self.cfg = cfg
-        self._lib = lib
+
+class _Engine:
+    """What BatchMPC and RaggedMPC share: the handle and its lifetime.  _CREATE, _DESTROY, _LAST_ERROR: the C names that differ between the two."""
+    _CREATE = _DESTROY = _LAST_ERROR = None
+
+    def _create(self, cfg, *args):
+        """<_CREATE>(&cfg, *args, &self._h), or SrbdqpError with the library's reason."""
+        self._lib = _lib.load()
         self._h = C.c_void_p()
-        rc = lib.srbdqp_create(C.byref(cfg), C.byref(self._h))
+        rc = getattr(self._lib, self._CREATE)(C.byref(cfg), *args, C.byref(self._h))
         if rc != _lib.OK:
-            msg = lib.srbdqp_last_error(None)
+            msg = getattr(self._lib, self._LAST_ERROR)(None)
             self._h = C.c_void_p()
-            raise SrbdqpError(f"srbdqp_create failed ({rc}): {msg.decode() if msg else '?'}")
-        self.N = int(horizon)
-        self.n = NU * self.N
-        self.m = _lib.ROWS_PER_STEP * self.N
+            raise SrbdqpError(f"{self._CREATE} failed ({rc}): {msg.decode() if msg else '?'}")
 
-    # -- lifetime ------------------------------------------------------------------------------------
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._stage = None                      # the views point into memory the library is about to free
-            self._lib.srbdqp_destroy(self._h)
+        if getattr(self, "_h", None):
+            getattr(self._lib, self._DESTROY)(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -158,7 +144,54 @@ class BatchMPC:
         self.close()
 
     def _check(self, rc):
-        _lib.check(rc, self._h)
+        if rc != _lib.OK:
+            msg = getattr(self._lib, self._LAST_ERROR)(self._h)
+            raise SrbdqpError(f"srbdqp error {rc}: {msg.decode() if msg else '?'}")
+
+
+class BatchMPC(_Engine):
+    """B independent SRBD convex-MPC QPs per call.  One instance <-> one HIP stream <-> one thread."""
+    _CREATE, _DESTROY, _LAST_ERROR = "srbdqp_create", "srbdqp_destroy", "srbdqp_last_error"
+    _stage = _fcb = None                    # stage(): NumPy views of the staging arrays, and the CPython binding's capsule on them
+
+    def __init__(self, horizon: int = 10, dt: float = 0.04, device: int = 0, kernel: int = _lib.KERNEL_AUTO,
+                 timing: bool = False, rank_aware: bool = False, **overrides):
+        """rank_aware=True sets SRBDQP_FLAG_RANK_AWARE (include/srbdqp.h): on the general kernel, steps whose stance contact points lie on or near one line --
+        feet in tandem, point feet -- are solved in rank-aware coordinates instead of ending the QP with status -1 (fp64 solves, N <= 20, flat ground, one
+        robot).  flags=_lib.FLAG_RANK_AWARE does the same."""
+        cfg = _lib.default_config()
+        cfg.horizon = int(horizon)
+        cfg.dt = float(dt)
+        cfg.device = int(device)
+        cfg.kernel = int(kernel)
+        cfg.flags = _lib.FLAG_TIMING if timing else 0
+        _apply_overrides(cfg, overrides)
+        if cfg.horizon not in _lib.HORIZONS:        # any other horizon 1 ... 24: the general kernel's live-horizon mode (include/srbdqp.h, SRBDQP_FLAG_ANY_HORIZON)
+            cfg.flags |= _lib.FLAG_ANY_HORIZON
+        if rank_aware:                              # (after the overrides: flags= and the keyword add up)
+            cfg.flags |= _lib.FLAG_RANK_AWARE
+        self.cfg = cfg
+        self._create(cfg)
+        self.N = int(horizon)
+        self.n = NU * self.N
+        self.m = _lib.ROWS_PER_STEP * self.N
+
+    def close(self):
+        self._stage = self._fcb = None              # the views and the capsule point into memory the library is about to free
+        super().close()
+
+    def _open(self):
+        """The staged calls' guard: their views and the bound capsule hold addresses that close() has freed."""
+        if not self._h:
+            raise SrbdqpError("engine is closed")
+
+    def _qp_inputs(self, x0, x_ref, foot, contact, pcom, dt=np.float64):
+        """The QP inputs of solve() and the two assembly dumps as contiguous arrays of their shapes -> (B, x0, x_ref, foot, contact, pcom)."""
+        N = self.N
+        x0 = np.ascontiguousarray(x0, dtype=dt)
+        B = x0.size // NX
+        return (B, _as(x0, dt, (B, NX), "x0"), _as(x_ref, dt, (B, N, NX), "x_ref"), _as(foot, dt, (B, N, NU), "foot"),
+                _as(np.asarray(contact) != 0, np.uint8, (B, N, NC), "contact"), None if pcom is None else _as(pcom, dt, (B, N, 3), "pcom"))
 
     # -- host-buffer API -------------------------------------------------------------------------------
     def solve(self, x0, x_ref, foot, contact, pcom=None, warm_u=None, warm_y=None, want_x=True, want_y=False,
@@ -177,13 +210,7 @@ class BatchMPC:
         dt = np.dtype(dtype)
         if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
             raise TypeError("dtype must be float64 or float32")
-        x0 = np.ascontiguousarray(x0, dtype=dt)
-        B = x0.size // NX
-        x0 = _as(x0, dt, (B, NX), "x0")
-        x_ref = _as(x_ref, dt, (B, N, NX), "x_ref")
-        foot = _as(foot, dt, (B, N, NU), "foot")
-        contact = _as(np.asarray(contact) != 0, np.uint8, (B, N, NC), "contact")
-        pcom = None if pcom is None else _as(pcom, dt, (B, N, 3), "pcom")
+        B, x0, x_ref, foot, contact, pcom = self._qp_inputs(x0, x_ref, foot, contact, pcom, dt)
         warm_u = None if warm_u is None else _as(warm_u, dt, (B, n), "warm_u")
         warm_y = None if warm_y is None else _as(warm_y, dt, (B, m), "warm_y")
         u = np.empty((B, N, NU), dt)
@@ -194,41 +221,29 @@ class BatchMPC:
         fn = self._lib.srbdqp_solve_batch_f64 if dt == np.dtype(np.float64) else self._lib.srbdqp_solve_batch_f32
         rc = fn(self._h, B, _ptr(x0), _ptr(x_ref), _ptr(foot), _ptr(contact), _ptr(pcom), _ptr(warm_u), _ptr(warm_y),
                 _ptr(u), _ptr(x), _ptr(y), _ptr(status), _ptr(iters))
-        _lib.check(rc, self._h)
+        self._check(rc)
         return dict(u=u, x=x, y=y, status=status, iters=iters)
 
     def assemble(self, x0, x_ref, foot, contact, pcom=None):
         """QP data in the scaled variables as the shipped compact / one-wave kernel builds it (srbdqp_assemble_f64):
         dict(P (B,n,n), q (B,n), l (B,m), u (B,m)); rows / columns of swing-contact variables are 0 (presolve)."""
         N, n, m = self.N, self.n, self.m
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        B = x0.size // NX
-        x0 = _as(x0, np.float64, (B, NX), "x0")
-        x_ref = _as(x_ref, np.float64, (B, N, NX), "x_ref")
-        foot = _as(foot, np.float64, (B, N, NU), "foot")
-        contact = _as(np.asarray(contact) != 0, np.uint8, (B, N, NC), "contact")
-        pcom = None if pcom is None else _as(pcom, np.float64, (B, N, 3), "pcom")
+        B, x0, x_ref, foot, contact, pcom = self._qp_inputs(x0, x_ref, foot, contact, pcom)
         P = np.empty((B, n, n)); q = np.empty((B, n)); lo = np.empty((B, m)); hi = np.empty((B, m))
         rc = self._lib.srbdqp_assemble_f64(self._h, B, _ptr(x0), _ptr(x_ref), _ptr(foot), _ptr(contact), _ptr(pcom),
                                            _ptr(P), _ptr(q), _ptr(lo), _ptr(hi))
-        _lib.check(rc, self._h)
+        self._check(rc)
         return dict(P=P, q=q, l=lo, u=hi)
 
     def assemble_wrench(self, x0, x_ref, foot, contact, pcom=None):
         """What the general kernel builds before its factorisation (srbdqp_assemble_wrench_f64): dict(T (B,6N,6N), q (B,12N),
         Bd (B,12N,12), Vcol (B,12N,6), Vrow (B,12N,6), goff (B,N+1) int)."""
         N, n = self.N, self.n
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        B = x0.size // NX
-        x0 = _as(x0, np.float64, (B, NX), "x0")
-        x_ref = _as(x_ref, np.float64, (B, N, NX), "x_ref")
-        foot = _as(foot, np.float64, (B, N, NU), "foot")
-        contact = _as(np.asarray(contact) != 0, np.uint8, (B, N, NC), "contact")
-        pcom = None if pcom is None else _as(pcom, np.float64, (B, N, 3), "pcom")
+        B, x0, x_ref, foot, contact, pcom = self._qp_inputs(x0, x_ref, foot, contact, pcom)
         T = np.empty((B, 6 * N, 6 * N)); q = np.empty((B, n)); bl = np.empty((B, n, 24)); go = np.empty((B, N + 1))
         rc = self._lib.srbdqp_assemble_wrench_f64(self._h, B, _ptr(x0), _ptr(x_ref), _ptr(foot), _ptr(contact), _ptr(pcom),
                                                   _ptr(T), _ptr(q), _ptr(bl), _ptr(go))
-        _lib.check(rc, self._h)
+        self._check(rc)
         return dict(T=T, q=q, Bd=bl[:, :, 0:12].copy(), Vcol=bl[:, :, 12:18].copy(), Vrow=bl[:, :, 18:24].copy(), goff=go.astype(int))
 
     # -- device-buffer API -----------------------------------------------------------------------------
@@ -241,15 +256,15 @@ class BatchMPC:
         fn = self._lib.srbdqp_solve_batch_device_f32 if f32 else self._lib.srbdqp_solve_batch_device_f64
         rc = fn(self._h, int(B), v(x0), v(x_ref), v(foot), v(contact), v(pcom), v(warm_u), v(warm_y), v(u_out), v(x_out),
                 v(y_out), v(status), v(iters), v(stream))
-        _lib.check(rc, self._h)
+        self._check(rc)
 
     def set_schedule_hint(self, iters_prev_ptr=0, length=0):
         """Device address and length of the previous step's iters[] (or 0): longest-first dispatch for the next device
         solves of at most `length` QPs.  A hint without a length is an error (it would silently never apply)."""
         if iters_prev_ptr and int(length) <= 0:
             raise ValueError("set_schedule_hint: pass the number of entries of iters_prev (length > 0) with the pointer")
-        _lib.check(self._lib.srbdqp_set_schedule_hint(self._h, C.c_void_p(int(iters_prev_ptr)) if iters_prev_ptr else None,
-                                                      int(length) if iters_prev_ptr else 0), self._h)
+        self._check(self._lib.srbdqp_set_schedule_hint(self._h, C.c_void_p(int(iters_prev_ptr)) if iters_prev_ptr else None,
+                                                       int(length) if iters_prev_ptr else 0))
 
     def set_robots(self, robots):
         """One robot per QP (include/srbdqp.h srbdqp_set_robots): robots = robots_array(...) rows (NumPy, copied by the library), a CUDA float64 torch
@@ -286,14 +301,15 @@ class BatchMPC:
         stream this engine has launched on.  Does not synchronise.  Until the flush has completed in stream order the device arrays of the earlier
         solve_device() calls -- their OUTPUTS and their INPUTS (a continuation rebuilds its QP from the pointers of the launch it came from) -- must
         stay untouched (include/srbdqp.h, SRBDQP_FLAG_DEFER_TAIL)."""
-        _lib.check(self._lib.srbdqp_flush(self._h, C.c_void_p(int(stream)) if stream else None), self._h)
+        self._check(self._lib.srbdqp_flush(self._h, C.c_void_p(int(stream)) if stream else None))
 
     # -- low-latency staged API (small batches; the single-robot control loop) --------------------------
     def stage(self):
         """NumPy views of the library's pinned, GPU-mapped staging arrays (dict; first axis = capacity)."""
-        if getattr(self, "_stage", None) is None:
+        self._open()
+        if self._stage is None:
             st = _lib.Stage()
-            _lib.check(self._lib.srbdqp_stage_ptrs(self._h, C.byref(st)), self._h)
+            self._check(self._lib.srbdqp_stage_ptrs(self._h, C.byref(st)))
             cap, N, n, m = st.capacity, self.N, self.n, self.m
 
             def view(addr, ctype, shape):
@@ -306,7 +322,6 @@ class BatchMPC:
                 pcom=view(st.pcom, d, (cap, N, 3)), warm_u=view(st.warm_u, d, (cap, n)), warm_y=view(st.warm_y, d, (cap, m)),
                 u=view(st.u, d, (cap, N, NU)), x=view(st.x, d, (cap, N + 1, NX)), y=view(st.y, d, (cap, m)),
                 status=view(st.status, i32, (cap,)), iters=view(st.iters, i32, (cap,)))
-            self._fcb = None
             if _fastcall is not None:       # the same two C entry points through their function pointers (no ctypes trampoline per call)
                 raw = _lib.load_raw()
                 addr = lambda f: C.cast(f, C.c_void_p).value
@@ -316,25 +331,29 @@ class BatchMPC:
 
     def solve_staged(self, B=1, use_pcom=False, use_warm=False, want_x=True, want_y=False):
         """One kernel launch over the first B staged QPs; inputs are read and outputs written in the staging arrays."""
-        fcb = getattr(self, "_fcb", None)
+        if not self._h:                     # (_open(), in line: this call is the control loop's)
+            raise SrbdqpError("engine is closed")
+        fcb = self._fcb
         if fcb is not None:
             rc = _fastcall.solve_staged(fcb, int(B), int(use_pcom), int(use_warm), int(want_x), int(want_y))
             if rc:
-                _lib.check(rc, self._h)
+                self._check(rc)
             return
-        _lib.check(self._lib.srbdqp_solve_staged_f64(self._h, int(B), int(use_pcom), int(use_warm), int(want_x), int(want_y)), self._h)
+        self._check(self._lib.srbdqp_solve_staged_f64(self._h, int(B), int(use_pcom), int(use_warm), int(want_x), int(want_y)))
 
     def prepare_staged(self, B=1, use_pcom=False):
         """Two-phase call, phase 1 (srbdqp_prepare_staged_f64): set-up of the first B staged QPs from a PREDICTED x0 (whatever the
         staging x0 holds); asynchronous."""
-        _lib.check(self._lib.srbdqp_prepare_staged_f64(self._h, int(B), int(use_pcom)), self._h)
+        self._open()
+        self._check(self._lib.srbdqp_prepare_staged_f64(self._h, int(B), int(use_pcom)))
 
     def solve_prepared(self, B=1, want_x=True, want_y=False):
         """Two-phase call, phase 2 (srbdqp_solve_prepared_f64): x0 is read from the staging arrays again, the rest is as prepared."""
-        _lib.check(self._lib.srbdqp_solve_prepared_f64(self._h, int(B), int(want_x), int(want_y)), self._h)
+        self._open()
+        self._check(self._lib.srbdqp_solve_prepared_f64(self._h, int(B), int(want_x), int(want_y)))
 
     def synchronize(self):
-        _lib.check(self._lib.srbdqp_synchronize(self._h), self._h)
+        self._check(self._lib.srbdqp_synchronize(self._h))
 
     # -- the steps either side of the QP (include/srbdqp_cascade.h) ----------------------------------------
     def swing(self, p_start, p_final, z_middle, progress, final_velocity_z=-0.02, first_half_share=0.80, want_coeff=False):
@@ -350,7 +369,7 @@ class BatchMPC:
         co = np.empty((B, 7)) if want_coeff else None
         rc = self._lib.srbdqp_swing_f64(self._h, B, _p(ps), _p(pf), _p(zm), _p(t), float(final_velocity_z),
                                         float(first_half_share), _p(pos), _p(vz), _p(az), _p(co))
-        _lib.check(rc, self._h)
+        self._check(rc)
         out = dict(pos=pos, vel_z=vz, acc_z=az)
         if want_coeff:
             out["coeff"] = co
@@ -365,7 +384,7 @@ class BatchMPC:
             raise ValueError("x_next, u0 and foot must have the same number of rows")
         R, bv, ba, ca = np.empty((B, 3, 3)), np.empty((B, 6)), np.empty((B, 6)), np.empty((B, 3))
         rc = self._lib.srbdqp_wbid_reference_f64(self._h, B, _p(x), _p(u), _p(f), int(bool(as_written)), _p(R), _p(bv), _p(ba), _p(ca))
-        _lib.check(rc, self._h)
+        self._check(rc)
         return dict(R=R, base_vel=bv, base_acc=ba, com_acc=ca, com_pos=x[:, 3:6].copy(), com_vel=x[:, 9:12].copy(),
                     wrench=u.reshape(B, 4, 3).copy())
 
@@ -394,7 +413,7 @@ class BatchMPC:
         xr, ft, ct = np.empty((B, N, NX)), np.empty((B, N, NU)), np.empty((B, N, NC), dtype=np.uint8)
         pc, lp = np.empty((B, N, 3)), np.empty((B, 3))
         rc = self._lib.srbdqp_mpc_inputs_f64(self._h, B, _p(x), _p(f), _p(t), _p(v), _p(sd), C.byref(g), _p(xr), _p(ft), _p(ct), _p(pc), _p(lp))
-        _lib.check(rc, self._h)
+        self._check(rc)
         return dict(x_ref=xr, foot=ft, contact=ct, pcom=pc, landing=lp)
 
     def mpc_inputs_device(self, B, x0, feet, stamp, v_ref, com_target, x_ref, foot, contact, pcom, landing=0, standing=0,
@@ -404,7 +423,7 @@ class BatchMPC:
         g = self._gait_struct(period_steps, double_support_steps, com_target, hip_offset_y)
         rc = self._lib.srbdqp_mpc_inputs_device_f64(self._h, int(B), v(x0), v(feet), v(stamp), v(v_ref), v(standing), C.byref(g),
                                                     v(x_ref), v(foot), v(contact), v(pcom), v(landing), v(stream))
-        _lib.check(rc, self._h)
+        self._check(rc)
 
     def last_kernel_ms(self) -> float:
         return float(self._lib.srbdqp_last_kernel_ms(self._h))
@@ -424,36 +443,22 @@ class BatchMPC:
         return self._lib.srbdqp_batch1_launch_path(self._h).decode()
 
 
-class RaggedMPC:
+class RaggedMPC(_Engine):
     """Mixed-horizon batches (BASELINE.json configs[4]) over srbdqp_solve_ragged_*: QPs in any order, each with its own
     horizon and contact schedule; the library sorts them into horizon buckets and launches every bucket on its own HIP
     stream, all in flight together."""
+    _CREATE, _DESTROY, _LAST_ERROR = "srbdqp_ragged_create", "srbdqp_ragged_destroy", "srbdqp_ragged_last_error"
 
     def __init__(self, horizons=(8, 12, 16, 24), dt: float = 0.04, device: int = 0, **overrides):
-        lib = _lib.load()
         cfg = _lib.default_config()
         cfg.dt = float(dt)
         cfg.device = int(device)
-        for k, v in overrides.items():
-            if not hasattr(cfg, k):
-                raise TypeError(f"unknown srbdqp_config field {k!r}")
-            setattr(cfg, k, type(getattr(cfg, k))(v))
+        _apply_overrides(cfg, overrides)
         self.horizons = tuple(int(h) for h in horizons)
         if any(h not in _lib.HORIZONS for h in self.horizons):   # buckets at any horizon 1 ... 24 (SRBDQP_FLAG_ANY_HORIZON)
             cfg.flags |= _lib.FLAG_ANY_HORIZON
         hz = np.ascontiguousarray(self.horizons, dtype=np.int32)
-        self._lib = lib
-        self._h = C.c_void_p()
-        rc = lib.srbdqp_ragged_create(C.byref(cfg), _ptr(hz), len(hz), C.byref(self._h))
-        if rc != _lib.OK:
-            msg = lib.srbdqp_ragged_last_error(None)
-            self._h = C.c_void_p()
-            raise SrbdqpError(f"srbdqp_ragged_create failed ({rc}): {msg.decode() if msg else '?'}")
-
-    def _check(self, rc):
-        if rc != _lib.OK:
-            msg = self._lib.srbdqp_ragged_last_error(self._h)
-            raise SrbdqpError(f"srbdqp error {rc}: {msg.decode() if msg else '?'}")
+        self._create(cfg, _ptr(hz), len(hz))
 
     def solve_packed(self, N_per_qp, x0, x_ref, foot, contact, want_x=True, dtype=np.float64):
         """Step-major packed host arrays (include/srbdqp.h): x0 (B,13), x_ref (sum N,13), foot (sum N,12), contact (sum N,4).
@@ -520,17 +525,6 @@ class RaggedMPC:
         off = res["off"]
         return [dict(u=res["u"][off[i]:off[i + 1]], x=res["x"][off[i] + i:off[i + 1] + i + 1], status=int(res["status"][i]),
                      iters=int(res["iters"][i])) for i in range(len(problems))]
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.srbdqp_ragged_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class MPC:
@@ -626,15 +620,11 @@ class MPC:
         self._fcb = getattr(eng, "_fcb", None)
         return self._upd
 
-    def solve(self, x_current, x_ref_hor, c_horizon, contact_horizon, p_com_horizon=None):
-        """Assemble + solve one QP on the GPU; returns (u (N,12) newtons, x (N+1,13)).
-        Inputs are written straight into the library's pinned staging arrays (no hipMemcpy on this path)."""
-        if self._engine is None:
-            self.init_matrices()
-        self._last_fast = self._last_fc = False
-        eng, N = self._engine, self.HORIZON_LENGTH
-        st = eng.stage()
-        st["x0"][0] = np.asarray(x_current, dtype=np.float64).reshape(NX)
+    def _write_staged(self, x0, x_ref_hor, c_horizon, contact_horizon, p_com_horizon):
+        """One QP into row 0 of the engine's staging arrays (no hipMemcpy on this path) -> (the arrays, whether pcom was written)."""
+        N = self.HORIZON_LENGTH
+        st = self._engine.stage()
+        st["x0"][0] = np.asarray(x0, dtype=np.float64).reshape(NX)
         st["x_ref"][0] = np.asarray(x_ref_hor, dtype=np.float64).reshape(N, NX)
         # the reference passes per-step lists (run_simulation.py:94-101): concatenating straight into the staging
         # arrays is ~1 us cheaper than np.asarray(list) + copy; anything irregular takes the general path
@@ -644,18 +634,35 @@ class MPC:
         except (ValueError, TypeError):
             st["foot"][0] = np.asarray(c_horizon, dtype=np.float64).reshape(N, NU)
             st["contact"][0] = np.asarray(contact_horizon).reshape(N, NC) != 0
-        use_pcom = p_com_horizon is not None
-        if use_pcom:
+        if p_com_horizon is not None:
             st["pcom"][0] = np.asarray(p_com_horizon, dtype=np.float64).reshape(N, 3)
-        t0 = time.perf_counter()
-        eng.solve_staged(1, use_pcom=use_pcom, use_warm=False, want_x=True, want_y=False)
-        self._solve_time = time.perf_counter() - t0
-        self._status = int(st["status"][0])
-        self._iters = int(st["iters"][0])
+        return st, p_com_horizon is not None
+
+    def _outcome(self, status, iters, u, x, one_rollout, stacklevel):
+        """The outcome of every call but update()'s bound fast path: status and iters kept, a solve that is not SOLVED raised or warned about (stacklevel as
+        warnings.warn counts it from the method that calls this one: 2 = that method's caller), the plan u (N,12) and roll-out x (N+1,13) kept as u_opt /
+        x_opt.  Returns what update() returns."""
+        self._status, self._iters = int(status), int(iters)
         if self._status != _lib.SOLVED:
-            self._not_solved(self._status, self._iters, 4)
-        self._u_opt = st["u"][0].copy()
-        self._x_opt = st["x"][0].copy()
+            self._not_solved(self._status, self._iters, stacklevel + 2)
+        self._u_opt, self._x_opt = u, x
+        return u[0].reshape(NU, 1).copy(), (x.copy() if one_rollout else x[:2].copy())
+
+    def _solve(self, x_current, x_ref_hor, c_horizon, contact_horizon, p_com_horizon, one_rollout, stacklevel):
+        """One QP through the staging arrays and srbdqp_solve_staged_f64: the body of solve() and of update()'s general path."""
+        if self._engine is None:
+            self.init_matrices()
+        self._last_fast = self._last_fc = False
+        st, use_pcom = self._write_staged(x_current, x_ref_hor, c_horizon, contact_horizon, p_com_horizon)
+        t0 = time.perf_counter()
+        self._engine.solve_staged(1, use_pcom=use_pcom, use_warm=False, want_x=True, want_y=False)
+        self._solve_time = time.perf_counter() - t0
+        return self._outcome(st["status"][0], st["iters"][0], st["u"][0].copy(), st["x"][0].copy(), one_rollout, stacklevel + 1)
+
+    def solve(self, x_current, x_ref_hor, c_horizon, contact_horizon, p_com_horizon=None):
+        """Assemble + solve one QP on the GPU; returns (u (N,12) newtons, x (N+1,13)).
+        Inputs are written straight into the library's pinned staging arrays (no hipMemcpy on this path)."""
+        self._solve(x_current, x_ref_hor, c_horizon, contact_horizon, p_com_horizon, True, 2)
         return self._u_opt, self._x_opt
 
     def _not_solved(self, status, iters, stacklevel):
@@ -677,15 +684,8 @@ class MPC:
         x_predicted: any finite guess of the state (default: self.x0)."""
         if self._engine is None:
             self.init_matrices()
-        eng, N = self._engine, self.HORIZON_LENGTH
-        st = eng.stage()
-        st["x0"][0] = np.asarray(self.x0 if x_predicted is None else x_predicted, dtype=np.float64).reshape(NX)
-        st["x_ref"][0] = np.asarray(self.x_ref_hor, dtype=np.float64).reshape(N, NX)
-        st["foot"][0] = np.asarray(c_horizon, dtype=np.float64).reshape(N, NU)
-        st["contact"][0] = np.asarray(contact_horizon).reshape(N, NC) != 0
-        if p_com_horizon is not None:
-            st["pcom"][0] = np.asarray(p_com_horizon, dtype=np.float64).reshape(N, 3)
-        eng.prepare_staged(1, use_pcom=p_com_horizon is not None)
+        _, use_pcom = self._write_staged(self.x0 if x_predicted is None else x_predicted, self.x_ref_hor, c_horizon, contact_horizon, p_com_horizon)
+        self._engine.prepare_staged(1, use_pcom=use_pcom)
 
     def update_prepared(self, x_current=None, one_rollout: bool = True):
         """Second phase of prepare(): returns what update() returns, for the measured state x_current (default: self.x0)."""
@@ -696,11 +696,7 @@ class MPC:
         t0 = time.perf_counter()
         eng.solve_prepared(1, want_x=True)
         self._solve_time = time.perf_counter() - t0
-        self._status, self._iters = int(st["status"][0]), int(st["iters"][0])
-        if self._status != _lib.SOLVED:
-            self._not_solved(self._status, self._iters, 3)
-        self._u_opt, self._x_opt = st["u"][0].copy(), st["x"][0].copy()
-        return self._u_opt[0].reshape(NU, 1).copy(), (self._x_opt.copy() if one_rollout else self._x_opt[:2].copy())
+        return self._outcome(st["status"][0], st["iters"][0], st["u"][0].copy(), st["x"][0].copy(), one_rollout, 2)
 
     def update(self, contact_horizon: Sequence, c_horizon: Sequence, p_com_horizon, x_current=None,
                one_rollout: bool = True, contact_normals=None, external_wrench=None):
@@ -720,6 +716,8 @@ class MPC:
             raise ValueError("update: contact_normals and external_wrench together are not supported (no instantiation of the general kernel reads both)")
         if contact_normals is not None or external_wrench is not None:
             return self._update_via_batch(contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals, external_wrench)
+        # From here to the end of the method: the measured ~4.5 us of Python around srbdqp_update_f64.  Its two arms keep their own copy of "write one QP" and of
+        # "take the outcome" on purpose (results stay in the staging arrays, nothing is boxed): _write_staged and _outcome serve every other call, not this one.
         upd = self._upd
         if upd is None:
             upd = self._bind()
@@ -768,11 +766,7 @@ class MPC:
         return self._s_u0.copy(), (self._s_x.copy() if one_rollout else self._s_x01.copy())
 
     def _update_general(self, contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout):
-        x_cur = self.x0 if x_current is None else x_current
-        u, x = self.solve(x_cur, self.x_ref_hor, c_horizon, contact_horizon, p_com_horizon)
-        u_opt0 = u[0].reshape(NU, 1).copy()
-        x_opt1 = x.copy() if one_rollout else x[:2].copy()
-        return u_opt0, x_opt1
+        return self._solve(self.x0 if x_current is None else x_current, self.x_ref_hor, c_horizon, contact_horizon, p_com_horizon, one_rollout, 3)
 
     def _update_via_batch(self, contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals=None, external_wrench=None):
         """update() with contact normals or an external wrench (at most one of them): the host-batch solve with B = 1.  The wrench is set through the host
@@ -795,15 +789,13 @@ class MPC:
             if external_wrench is not None:
                 eng.set_external_wrench(None)
         self._solve_time = time.perf_counter() - t0
-        self._status, self._iters = int(out["status"][0]), int(out["iters"][0])
-        if self._status != _lib.SOLVED:
-            self._not_solved(self._status, self._iters, 4)
-        self._u_opt, self._x_opt = out["u"][0], out["x"][0]
-        return self._u_opt[0].reshape(NU, 1).copy(), (self._x_opt.copy() if one_rollout else self._x_opt[:2].copy())
+        return self._outcome(out["status"][0], out["iters"][0], out["u"][0], out["x"][0], one_rollout, 3)
 
     def close(self):
-        self._upd = None
+        self._upd = self._fcb = None
         self._last_fast = self._last_fc = False
+        for k in [k for k in vars(self) if k.startswith(("_s_", "_args_"))]:    # what _bind() made: views of, and addresses in, memory the library is about to free
+            delattr(self, k)
         if self._engine is not None:
             self._engine.close()
             self._engine = None

@@ -12,15 +12,65 @@ import srbd_oracle as orc
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _headers():
+    """The text of every include/*.h, comments stripped."""
+    for hdr in sorted(os.listdir(os.path.join(ROOT, "include"))):
+        if hdr.endswith(".h"):
+            yield re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", hdr)).read(), flags=re.S)
+
+
 def _declared_functions():
     """Every function declared in include/*.h (comments stripped)."""
     names = set()
-    for hdr in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if hdr.endswith(".h"):
-            txt = open(os.path.join(ROOT, "include", hdr)).read()
-            txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-            names |= set(re.findall(r"\b(srbdqp_[a-z0-9_]+)\s*\(", txt))
+    for txt in _headers():
+        names |= set(re.findall(r"\b(srbdqp_[a-z0-9_]+)\s*\(", txt))
     return sorted(names)
+
+
+def _declared_signatures():
+    """name -> (return type, [parameter declarations]) of every function declared in include/*.h."""
+    sigs = {}
+    for txt in _headers():
+        for ret, name, params in re.findall(r"^(int|double|const char\*)\s+(srbdqp_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", txt, flags=re.M):
+            params = " ".join(params.split())
+            sigs[name] = (ret, [] if params in ("", "void") else [p.strip() for p in params.split(",")])
+    return sigs
+
+
+_POINTERS = (C.c_void_p, C._Pointer)
+_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
+_RETURNS = {"int": C.c_int, "double": C.c_double, "const char*": C.c_char_p}
+
+
+def _signature_mismatches(binding):
+    """binding(name) -> (restype, argtypes) held against the headers: what differs, as text."""
+    bad = []
+    for name, (ret, params) in _declared_signatures().items():
+        restype, argtypes = binding(name)
+        if restype is not _RETURNS[ret]:
+            bad.append(f"{name}: returns {ret}, restype {restype}")
+        if argtypes is None or len(argtypes) != len(params):
+            bad.append(f"{name}: {len(params)} parameters, argtypes {argtypes}")
+            continue
+        for i, (decl, t) in enumerate(zip(params, argtypes)):
+            if "*" in decl:
+                ok = isinstance(t, type) and issubclass(t, _POINTERS)
+            else:
+                ok = t is _SCALARS[decl.split()[-2]]      # "<type> <name>": every parameter of the two headers is named
+            if not ok:
+                bad.append(f"{name}: parameter {i} `{decl}` bound as {t}")
+    return bad
+
+
+def test_signature_table_matches_the_headers(built_lib):
+    """Every function of include/*.h: as many argtypes as parameters, a `*` parameter bound as a pointer, int32_t / int64_t / double as c_int32 / c_int64 /
+    c_double, and the return type as the restype -- in _lib.SIGNATURES, and on the functions of the library load() returns (the table, applied)."""
+    from g1_locomotion_amd import _lib
+    decl = _declared_signatures()
+    assert sorted(decl) == _declared_functions() and _lib.EXPORTS == tuple(_lib.SIGNATURES)
+    assert _signature_mismatches(lambda name: _lib.SIGNATURES[name]) == []
+    lib = _lib.load()
+    assert _signature_mismatches(lambda name: (getattr(lib, name).restype, getattr(lib, name).argtypes)) == []
 
 
 def test_library_exports_every_declared_symbol(built_lib):

@@ -89,13 +89,10 @@ class Parent:
     def __init__(self, path):
         _lib.load()                                                  # (this tree's library first: it maps the HIP runtime both use)
         self.lib = C.CDLL(path)
-        H, p = C.c_void_p, C.c_void_p
-        self.lib.srbdqp_create.argtypes = [C.POINTER(_lib.Config), C.POINTER(H)]
-        self.lib.srbdqp_ragged_create.argtypes = [C.POINTER(_lib.Config), C.c_void_p, C.c_int32, C.POINTER(H)]
-        self.lib.srbdqp_destroy.argtypes = self.lib.srbdqp_ragged_destroy.argtypes = [H]
-        self.lib.srbdqp_solve_batch_device_f64.argtypes = [H, C.c_int32] + [p] * 13
-        self.lib.srbdqp_solve_ragged_device_f64.argtypes = [H, C.c_int32] + [p] * 10
-        self.lib.srbdqp_version.restype = C.c_char_p
+        for name in ("srbdqp_create", "srbdqp_ragged_create", "srbdqp_destroy", "srbdqp_ragged_destroy", "srbdqp_solve_batch_device_f64",
+                     "srbdqp_solve_ragged_device_f64", "srbdqp_version"):
+            fn = getattr(self.lib, name)
+            fn.restype, fn.argtypes = _lib.SIGNATURES[name]
 
     def batch(self, N, kernel):
         cfg = _lib.default_config()
