@@ -828,6 +828,14 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     const size_t row0 = a.row_off ? (size_t)a.row_off[b] : (size_t)b * NL;   // first horizon row of this QP in the step-major arrays
     const TIO* gwu = reinterpret_cast<const TIO*>(a.warm_u) + row0 * 12;
     const TIO* gwy = reinterpret_cast<const TIO*>(a.warm_y) + row0 * 20;
+    // the prefix sums of Rz' (o_cp) from the per-step Rz' (o_tm, persistent): formed with the tables, and again wherever something that lay over them has run --
+    // the tiles, the K^-1 of a refinement step.  Threads 0 ... 8; the caller's next barrier publishes them.
+    auto rz_prefix_sums = [&]() __attribute__((always_inline)) {
+        if (t < 9) {
+            double acc = 0.0;
+            for (int k = 0; k < N; ++k) { acc += sm[S::o_tm + k * 9 + t]; sm[S::o_cp + k * 9 + t] = acc; }
+        }
+    };
 
     // ================= load (coalesced, one batch of loads) + linearise (a5) =================
     SRBDQP_STAMP(a, b, 0);
@@ -913,10 +921,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             if (k == N - 1) { igoff[N] = tot; imisc[0] = tot; imisc[1] = na; iwr[N] = allw; }   // iwr[N]: every step in wrench coordinates
         }
         __syncthreads();
-        if (t < 9) {
-            double acc = 0.0;
-            for (int k = 0; k < N; ++k) { acc += sm[S::o_tm + k * 9 + t]; sm[S::o_cp + k * 9 + t] = acc; }
-        }
+        rz_prefix_sums();
         static_assert(N * 12 <= BT, "one thread per entry of a J row");
         if (t < N * 12) {   // J_k[:, 3 ci + ax] = Iw^-1 skew(r)[:, ax]
             const int i = t;
@@ -2088,10 +2093,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                 // fp32 tiles: T^-1 is good to ~1e-4 only.  One step of iterative refinement with the fp64 residual
                 // r = K x_q + q = G'(G x_q) + D x_q + q (closed form, as the warm start's P x^0) takes the large gradient
                 // out of that error: what is left is 1e-4 of the iteration's own right-hand sides (oracle: admm_solve_split).
-                if (t < 9) {   // the prefix sums of Rz' lay under the tiles
-                    double accp = 0.0;
-                    for (int k = 0; k < N; ++k) { accp += sm[S::o_tm + k * 9 + t]; sm[S::o_cp + k * 9 + t] = accp; }
-                }
+                rz_prefix_sums();   // (they lay under the tiles)
                 if (stepok) sm[S::o_x0c + uvar] = xq;
                 __syncthreads();
                 const double gtg = gtg_of_x0c();
@@ -2112,10 +2114,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                 // carries cond(T) ulps of it through every iteration: 1e-5 - 1e-4 N in the forces, and ten times that in the yaw of the roll-out.  One
                 // step with the fp64 residual leaves the rounding of q itself.  The tiles are dead, so the tables of G'(G x) have
                 // their phase-A places again; of the ADMM vectors only the half rows' tails (N = 12) are live, and those under the tables are written again.
-                if (t < 9) {
-                    double accp = 0.0;
-                    for (int k = 0; k < N; ++k) { accp += sm[S::o_tm + k * 9 + t]; sm[S::o_cp + k * 9 + t] = accp; }
-                }
+                rz_prefix_sums();
                 if (stepok) sm[S::o_x0c + uvar] = xq;
                 __syncthreads();
                 const double gtg = gtg_of_x0c();
@@ -2151,6 +2150,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                         asm volatile("" : "+v"(xq_r));
                         xq = (double)xq_r;
                     }
+                    rz_prefix_sums();   // again: the refinement's K^-1 ran over them (they lie under its right-hand sides)
                     x_init = active_u ? (double)gwu[uvar] / a.s : 0.0;
                     if (stepok) sm[S::o_x0c + uvar] = x_init;
                     __syncthreads();

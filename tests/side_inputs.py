@@ -213,10 +213,12 @@ def frames_matrix(normals):
     return T
 
 
-def twin(p, x0, x_ref, foot, contact, *, normals=None, ext_wrench=None, pcom=None):
+def twin(p, x0, x_ref, foot, contact, *, normals=None, ext_wrench=None, pcom=None, warm=None):
     """The twin of one solve with parameters p, under the wrench ext_wrench (N, 6) and on the contact frames of normals (N, 12) where given:
     dict(u (N, 12) world newtons, x (N + 1, 13), iters, status, u_hat = u_loc (12 N,) scaled local forces, y (20 N,), qp -- its q with the wrench's term --,
-    qp_loc, T); without normals qp_loc is qp and T is None (the identity)."""
+    qp_loc, T); without normals qp_loc is qp and T is None (the identity).
+    warm = (u_hat (12 N,) scaled forces in the WORLD frame, y (20 N,)): the caller's start, as orc.update takes it -- the solve starts from T' u_hat on the
+    stance contacts' variables and from y on their rows; the entries of swing contacts are not read."""
     x_ref = np.asarray(x_ref, np.float64)
     N = x_ref.shape[0]
     qp = orc.build_qp(p, x0, x_ref, foot, contact, pcom)
@@ -236,7 +238,11 @@ def twin(p, x0, x_ref, foot, contact, *, normals=None, ext_wrench=None, pcom=Non
     if len(vi) == 0:
         iters, status = 0, orc.STATUS_SOLVED
     else:
-        xr_, _, yr_, iters, status = orc.solve_with_restart(p, red["P"], red["q"], red["A"], red["l"], red["u"])
+        xi = yi = None
+        if warm is not None:
+            wu, wy = np.asarray(warm[0], np.float64).reshape(-1), np.asarray(warm[1], np.float64).reshape(-1)
+            xi, yi = (wu if T is None else T.T @ wu)[vi], wy[ri]
+        xr_, _, yr_, iters, status = orc.solve_with_restart(p, red["P"], red["q"], red["A"], red["l"], red["u"], xi, yi)
         uh[vi] = xr_
         y[ri] = yr_
     uw = uh if T is None else T @ uh
