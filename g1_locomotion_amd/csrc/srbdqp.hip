@@ -2,6 +2,7 @@
 // Host side: HIP runtime only (stream, workspace, events).  No CPU fallback of any kind.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstddef>
@@ -2038,7 +2039,7 @@ int srbdqp_assemble_wrench_f64(srbdqp_handle* h, int32_t B, const double* x0, co
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t N = (size_t)h->cfg.horizon, n = 12 * N, ng = 6 * N, b = (size_t)B;
     double *dx0, *dxr, *dft, *dpc, *dT, *dq, *dbl, *dgo; uint8_t* dct;
-    return host_call(h, [&](HostIo& io) {
+    const int rc = host_call(h, [&](HostIo& io) {
         dx0 = io.in<double>(x0, b * 13 * 8); dxr = io.in<double>(x_ref, b * N * 13 * 8); dft = io.in<double>(foot, b * N * 12 * 8);
         dct = io.in<uint8_t>(contact, b * N * 4); dpc = io.in<double>(pcom, b * N * 3 * 8);
         dT = io.zeroed<double>(T_out, b * ng * ng * 8); dq = io.zeroed<double>(q_out, b * n * 8);
@@ -2051,6 +2052,22 @@ int srbdqp_assemble_wrench_f64(srbdqp_handle* h, int32_t B, const double* x0, co
         c.plan = plan_solve(h, c, B, 4, 0, true, true);
         return launch_wrench(h, c, a, st);
     });
+    if (rc != SRBDQP_OK) return rc;
+    // x0 and the entries of x_ref that are neither yaw nor lever arm enter nothing but the gradient: a solve ends such a QP at its first residual check, and the dump
+    // marks it like the QPs the kernel rejects -- here, on the host's copy (the dump kernels stay as they are): goff[N] = -1 and nothing else of the QP written
+    for (size_t q = 0; q < b; ++q) {
+        double* go = goff_out + q * (N + 1);
+        if (go[N] < 0.0) continue;
+        bool finite = true;
+        for (size_t i = 0; i < n && finite; ++i) finite = std::fabs(q_out[q * n + i]) <= srbdqp::kInf;
+        if (finite) continue;
+        std::fill(T_out + q * ng * ng, T_out + (q + 1) * ng * ng, 0.0);
+        std::fill(q_out + q * n, q_out + (q + 1) * n, 0.0);
+        std::fill(blocks_out + q * n * 24, blocks_out + (q + 1) * n * 24, 0.0);
+        std::fill(go, go + N, 0.0);
+        go[N] = -1.0;
+    }
+    return SRBDQP_OK;
 }
 
 // ---- ragged batches (BASELINE.json configs[4]): mixed horizons, one launch per horizon bucket, all in flight together ----

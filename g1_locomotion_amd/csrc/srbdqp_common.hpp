@@ -285,6 +285,12 @@ __device__ __forceinline__ double gx_row(const double* CP, const double* TF, con
     }
 }
 
+// The residual pre-test (the iteration before a check mark) lets a row whose residual is not <= the e_prim of the last full check veto the full check.  The FIRST
+// full check (none made yet: the count of checks is kFirstCheck) is never vetoed: a NaN or infinite residual -- non-finite x0, x_ref, warm start -- would otherwise
+// veto every check up to the iteration cap, and the full check is what ends such a QP with SRBDQP_NUMERICAL, at the first mark.  No finite residual ever vetoed
+// the first check (e_prim_last starts at kInf 1e10), so nothing changes for finite inputs.
+constexpr int kFirstCheck = 0;
+
 // diagnostic phase stamp (thread 0 only; leaves the kernel through a buffer nothing else reads)
 #define SRBDQP_STAMP(a, b, idx) do { if ((a).stamps && threadIdx.x == 0) (a).stamps[(size_t)(b) * 16 + (idx)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
 
@@ -523,6 +529,14 @@ __device__ void rollout_and_store_to(const KArgs& a, double* u_out, double* x_ou
             const double* J = sm + S::o_J + j * 36 + comp * 12;
             s = 0.0;
             for (int c = 0; c < 12; ++c) s += J[c] * u[c];
+            // A force of exactly zero -- a swing contact's, every force of a rejected QP -- adds nothing whatever its lever arm holds, but NaN * 0 is NaN: a sum
+            // that is not finite is formed again from the terms of the non-zero forces, in the same order (the same bits where it was finite: the terms
+            // left out are zeros).  The ballot is over the lanes of this arm; the branch is taken by the waves that hold a sum that is not finite or above
+            // kInf = 1e30 in size -- a foot position or pcom of the QP that is not finite (or absurd) -- and by no other.
+            if (__ballot(!(fabs(s) <= kInf)) != 0ull) {
+                s = 0.0;
+                for (int c = 0; c < 12; ++c) s = (u[c] != 0.0) ? fma(J[c], u[c], s) : s;   // (the multiply-add the sum above contracts to)
+            }
         } else {
             const int ax = comp - 3;
             s = (u[ax] + u[3 + ax] + u[6 + ax] + u[9 + ax]) * a.inv_mass;

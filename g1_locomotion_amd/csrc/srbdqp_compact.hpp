@@ -199,7 +199,7 @@ __device__ int admm_loop_compact(const KArgs& a, int b, double* sm, double* rhsb
         if (++ph == a.check_every) ph = 0;                  // ph = k mod check_every, without a division per iteration
         const bool at_mark = (ph == 0);
         if (at_mark) vote_ok = (vflag[0] | vflag[1] | vflag[2] | vflag[3]) == 0;   // pre-test made at iteration k - 1
-        const bool check = (at_mark && vote_ok) || (k == a.max_iter);
+        const bool check = (at_mark && (vote_ok || k == a.check_every)) || (k == a.max_iter);   // (k == check_every: no veto of the FIRST full check, srbdqp_common.hpp kFirstCheck)
         const bool pretest = (ph == a.check_every - 1);     // k + 1 is a mark
         const double* rb = rhsbuf + ((k - 1) & 1) * RB;
         double* wb = rhsbuf + (k & 1) * RB;

@@ -144,7 +144,7 @@ __device__ __forceinline__ void admm_wave_iterations(const KArgs& a, const QpIo&
             rhs = fma(sigma, x, -qv) + atw;                                // (inactive lanes: 0)
             if (pretest) {
                 const bool bad = (rowA && !(fabs(axA - zA) <= e_prim_last)) || (rowB && !(fabs(axB - zB) <= e_prim_last));
-                vote_ok = __ballot(bad) == 0ull;
+                vote_ok = __ballot(bad) == 0ull || k < a.check_every;   // (no veto of the FIRST full check: srbdqp_common.hpp, kFirstCheck)
             }
             if (check) {
                 const double aty = At(yA, yB), px = cpx - At(spxA, spxB);

@@ -940,10 +940,12 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             const double s0 = CN ? ry * e2 - rz * e1 : ((ax == 0) ? 0.0 : ((ax == 1) ? -rz : ry));
             const double s1 = CN ? rz * e0 - rx * e2 : ((ax == 0) ? rz : ((ax == 1) ? 0.0 : -rx));
             const double s2 = CN ? rx * e1 - ry * e0 : ((ax == 0) ? -ry : ((ax == 1) ? rx : 0.0));
+            // (a swing contact's column is 0 whatever its position holds: its users weigh it with a factor 0 -- E, V, Bd, G'(G x) --, and NaN * 0 is NaN)
+            const bool on = sct[4 * k + ci] != 0;
             double* J = sm + S::o_J + k * 36;
-            J[0 * 12 + cc] = w00 * s0 + w01 * s1;
-            J[1 * 12 + cc] = w01 * s0 + w11 * s1;
-            J[2 * 12 + cc] = i2 * s2;
+            J[0 * 12 + cc] = on ? w00 * s0 + w01 * s1 : 0.0;
+            J[1 * 12 + cc] = on ? w01 * s0 + w11 * s1 : 0.0;
+            J[2 * 12 + cc] = on ? i2 * s2 : 0.0;
         }
         if constexpr (EW) {   // e_k = dt [I_w^-1 tau_k; f_k / m], behind the raw values
             static_assert(6 * N <= BT, "one thread per entry of the wrench");
@@ -2254,7 +2256,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     int vsum = 0;
 #pragma unroll
                     for (int q = 0; q < NWS; ++q) vsum |= vflag[q];
-                    vote_ok = (vsum == 0);
+                    vote_ok = (vsum == 0) || nchk == kFirstCheck;
                 }
             }, ktail, LT, vlds, nullptr, jlds, llds WADMM_ARGS);
             WADMM_T(4);
@@ -2412,6 +2414,11 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     const double* J = sm + S::o_J + j * 36 + comp * 12;
                     s = 0.0;
                     for (int c = 0; c < 12; ++c) s += J[c] * u[c];
+                    // (a rejected QP: every force is 0 and the lever arm of a stance contact may hold anything -- NaN * 0 is NaN; srbdqp_common.hpp rollout_and_store_to)
+                    if (__ballot(!(fabs(s) <= kInf)) != 0ull) {
+                        s = 0.0;
+                        for (int c = 0; c < 12; ++c) s = (u[c] != 0.0) ? fma(J[c], u[c], s) : s;   // (the multiply-add the sum above contracts to)
+                    }
                 } else if constexpr (CN) {
                     const double* Lr = LT_ + j * 36 + (comp - 3) * 12;
                     s = 0.0;

@@ -49,7 +49,17 @@ extern "C" {
                                      stance contacts lie on or near one line (feet in tandem, heel and toe at one point).  The QP is rejected before
                                      its factorisation: u, y and iters are 0, x is the roll-out of zero forces, the other QPs of the batch are not
                                      affected, and no restart pass or deferred continuation runs it again.  See SRBDQP_KERNEL_WRENCH;
-                                     SRBDQP_FLAG_RANK_AWARE is the way past this limit (fp64 calls). */
+                                     SRBDQP_FLAG_RANK_AWARE is the way past this limit (fp64 calls).
+                                     Main inputs that are not finite (x0, x_ref, the foot position of a stance contact, pcom, warm_u, warm_y: NaN, +-Inf,
+                                     a value an _f32 call rounds to Inf), on every kernel and in every call:
+                                       - u and y are 0 and iters is 0 (the QP is caught before its factorisation or at a pivot: foot, pcom, the yaw and --
+                                         where no pcom is given -- the CoM columns of x_ref) or check_every (caught at the first residual check: x0, the
+                                         other entries of x_ref, warm_u, warm_y); a QP never iterates on such values to the cap, is never SRBDQP_PENDING
+                                         and never appears in a restart pass;
+                                       - x_out is the roll-out of zero forces (under the external wrench, where one is set), finite, where x0 and the yaw
+                                         column of x_ref are finite; where they are not, row 0 of x_out is the caller's x0 and the other rows are written
+                                         but carry no meaning (NaN);
+                                       - the foot position of a SWING contact is not read: any value there leaves every output bit for bit. */
 #define SRBDQP_CONTACT_BOUND (-2) /* more stance contacts in a step than srbdqp_config.max_contacts_per_step allows; forces 0 */
 
 /* srbdqp_config.flags */
@@ -248,6 +258,8 @@ int srbdqp_solve_batch_device_f32(srbdqp_handle* h, int32_t B,
  *                         are reported as the clamp 0 <= fz <= 0 they stand for
  * Configurations that solve on the general kernel (SRBDQP_KERNEL_WRENCH, or what AUTO routes to it) return
  * SRBDQP_E_INVALID: their assembly is srbdqp_assemble_wrench_f64's.
+ * A QP whose inputs are not finite is not marked: its own P, q, l, u are written and hold what the arithmetic gives (NaN among them); the dumps of
+ * the other QPs are not affected, and a swing contact's foot position is not read.
  */
 int srbdqp_assemble_f64(srbdqp_handle* h, int32_t B,
                         const double* x0, const double* x_ref, const double* foot,
@@ -263,7 +275,9 @@ int srbdqp_assemble_f64(srbdqp_handle* h, int32_t B,
  *                            V (6), and -- as lane (row r = (u % 12) / 2, half h = u % 2) of the step -- V[r][6h .. 6h+5] (6)
  *   goff_out   [B][N+1]      offset of step j's coordinates in T (as doubles); goff[N] = n_g.  goff[N] = -1 marks a QP the kernel rejects
  *                            (SRBDQP_NUMERICAL in a solve: non-finite inputs, nearly collinear stance contacts): the call still returns
- *                            SRBDQP_OK, and NOTHING else of that QP's outputs is written -- test goff[N] first.
+ *                            SRBDQP_OK, and NOTHING else of that QP's outputs is written -- test goff[N] first.  "Non-finite inputs" is every
+ *                            value of x0, x_ref, pcom and a stance contact's foot position that a solve ends with SRBDQP_NUMERICAL, those that
+ *                            only reach the gradient (x0, most of x_ref) included.
  * HOST buffers; parity tests of rows a5-a8 on the kernel that ships (tests/test_gpu_wrench.py). */
 int srbdqp_assemble_wrench_f64(srbdqp_handle* h, int32_t B,
                                const double* x0, const double* x_ref, const double* foot,
@@ -533,7 +547,9 @@ int srbdqp_update_f64(srbdqp_handle* h, const double* x0, const double* x_ref, c
  * reference horizon BEFORE the state estimate arrives.  K (and its factorisation) depends on neither x0 nor x_ref's non-yaw
  * entries, and the gradient is affine in x0:
  *   srbdqp_prepare_staged_f64  reads the staging arrays (x0 = a prediction, anything finite), runs the set-up and stores
- *                              K^-1 and dq/dx0 on the device; returns at once (asynchronous on the handle's stream);
+ *                              K^-1 and dq/dx0 on the device; returns at once (asynchronous on the handle's stream).  A prediction
+ *                              that is NOT finite ends the QP with SRBDQP_NUMERICAL in the second phase whatever the measured x0
+ *                              is (iters = check_every, u = 0, x_out = the roll-out of zero forces from the MEASURED x0);
  *   srbdqp_solve_prepared_f64  reads x0 (only) from the staging arrays again, patches the gradient, runs the ADMM iterations
  *                              and the roll-out on one wave per QP and returns with the outputs in the staging arrays.
  * Same QP, same iterates as srbdqp_solve_staged_f64 on the same inputs (the split pipeline of SRBDQP_KERNEL_SPLIT); no warm
