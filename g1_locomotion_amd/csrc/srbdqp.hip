@@ -24,6 +24,7 @@
 #include "srbdqp_split.hpp"
 #include "srbdqp_setup1.hpp"
 #include "srbdqp_wrench.hpp"
+#include "srbdqp_wrench_lat_ew.hpp"
 #include "srbdqp_cascade.hpp"
 #include "srbdqp_cascade.h"
 #include "srbdqp_aql.hpp"
@@ -126,6 +127,9 @@ struct srbdqp_handle {
     int32_t done_seq = 0;
     bool done_cs = false;          // the last launch publishes its completion word with the checksum of its outputs (KArgs::done_cs): wait_done() verifies it
     bool done_cs_x = false;        // ... which cover x_out
+    // the staged wrench calls' own staging array [capacity][N][6] (srbdqp_stage_ext_wrench), pinned and GPU-mapped like the slab; null until the first call asks
+    double* stage_ew_host = nullptr;
+    double* stage_ew_dev = nullptr;
     int32_t prepared_B = 0; int prepared_maxs = 4; bool prepared_pcom = false;   // two-phase call: a set-up is pending, on the instantiation plan_two_phase chose
     // kernels whose dynamic-LDS limit has been raised on this handle's device (function attributes are per device, and a
     // process may hold handles on several)
@@ -228,7 +232,8 @@ struct Lazy {
 // ---- which kernel a solve runs: a Plan, decided once per solve by plan_solve() (behind restart_iter_of) and executed by launch() and the launchers ----
 enum class Family { Wave, WaveDefer, Split, Compact, General };   // one wave per QP, ... with deferred tails, the split pipeline, the 4-wave compact kernel, the general kernel
 // General: any (kFormRows below has a row for each but Lat, the staged low-latency instantiation); Compact: Plain or Lat (the dump is a pass's a.mode == 1)
-enum class Form { Plain, Robots, Weights, ExtWrench, Normals, Live, RankAware, Lat };
+// (LatExtWrench: the low-latency instantiation of MODE 7, which only a staged wrench call -- Call::ext_call -- plans; no handle state has its bit)
+enum class Form { Plain, Robots, Weights, ExtWrench, Normals, Live, RankAware, Lat, LatExtWrench };
 // the rho restart of restart_iter_of: none, inside the kernel, further launches on the caller's stream (the staged call: started by the host), or off that stream
 // -- the next launch on it (WaveDefer) or a tail stream (solve_deferred_passes, the ragged buckets)
 enum class Restart { Off, InPlace, Launches, Deferred };
@@ -249,6 +254,8 @@ struct Call {
     bool signal = false;           // the launch publishes the completion word
     bool use_hint = false;         // the dispatch hint applies (it belongs to the device-buffer API)
     Lazy* lazy = nullptr;          // staged path: run only the first pass of a multi-pass solve and hand it back here
+    const double* ext_call = nullptr;   // the staged wrench calls: the wrench of THIS call (device address of the staged array), which every pass of it reads
+    const double* ext_host = nullptr;   // ... and the host address of the same memory (one staged QP: the wrench rides in the argument segment)
     Plan plan;                     // plan_solve(h, c, B, ...), once the fields above are set
 };
 
@@ -879,7 +886,8 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
         // normals run on a layout (L, the frames' columns, is 288 N more bytes of LDS) and at waves per SIMD of their own (WrenchTraits over that layout).
         const double* const weights = reinterpret_cast<const double*>(h->weights.dev);
         const double* const robots = reinterpret_cast<const double*>(h->robots.dev);
-        if (form == Form::ExtWrench) return launch_side_form<N, Form::ExtWrench, WPS>(h, &srbdqp::srbdqp_wrench_ew_kernel<N, WPS>, a, st, h->ext.dev, weights, robots);
+        // (a staged wrench call -- no side input is set then, the entry points see to it -- brings the wrench of the call: the same kernel over the staged array)
+        if (form == Form::ExtWrench) return launch_side_form<N, Form::ExtWrench, WPS>(h, &srbdqp::srbdqp_wrench_ew_kernel<N, WPS>, a, st, c.ext_call ? c.ext_call : h->ext.dev, weights, robots);
         if (form == Form::Weights) return launch_side_form<N, Form::Weights, WPS>(h, &srbdqp::srbdqp_wrench_wt_kernel<N, WPS>, a, st, weights, robots);
         if (form == Form::Robots) {
             void (*k_rb)(KArgs, const double*) = &srbdqp::srbdqp_wrench_kernel<N, double, double, row(Form::Robots).mode, WPS, double, 5, 0>;
@@ -900,6 +908,22 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
             static const std::string nm_lat = nm + "_lat";
             return launch_staged_lat<N>(h, c, a, st, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, 1, double, 5, XW>, &srbdqp::srbdqp_wrench_kernel_in<N, XW>,
                                         "_ZN6srbdqp23srbdqp_wrench_kernel_inILi%dELi%dEEEvNS_5KArgsENS_8StagedInIXT_EEE.kd", XW, SL::BT, SL::bytes, nm_lat.c_str());
+        }
+        // a staged wrench call of a few QPs: the same waves and pipeline in MODE 7, the wrench's rows for the roll-out behind the mode's slots.  Through HIP on
+        // the caller's stream, every pass: the handle's own queue stays what it is.  One staged QP whose inputs are the staging arrays' own: inputs and wrench in
+        // the argument segment, completion word with the checksum (the *_in twin, as launch_staged_lat chooses it)
+        // The kernels and their launcher live in srbdqp_wrench_lat_ew.hip, a code object of their own: this one's text stays where it is without them.
+        if (form == Form::LatExtWrench) {
+            static const std::string nm_lew = nm + "_lat" + row(Form::ExtWrench).suffix;
+            srbdqp::StagedIn<N> in;
+            const bool inl = !(a.count_ptr || a.tile_sel || !c.ext_host || !staged_inline_inputs<N>(h, c, a, in));
+            KArgs ai = a;
+            if (inl) { ai.inline_in = 1; staged_done_checksum(h, ai); }
+            const bool first = h->lds_attr_done.insert(reinterpret_cast<const void*>(uintptr_t(16 * N + (inl ? 1 : 0)))).second;   // (no function lives at such an address)
+            h->kname = nm_lew.c_str();
+            const hipError_t e = srbdqp::launch_wrench_ew_lat(N, first, ai, inl ? &in : nullptr, c.ext_host, c.ext_call, st);
+            if (e != hipSuccess) { h->err = std::string("launch of ") + nm_lew + ": " + hipGetErrorString(e); return SRBDQP_E_HIP; }
+            return SRBDQP_OK;
         }
     }
     if constexpr (sizeof(R) == 4) {
@@ -1072,7 +1096,7 @@ Plan plan_solve(const srbdqp_handle* h, const Call& c, int B, int maxs, int neff
     // ---- the general kernel (srbdqp_wrench.hpp)?  The compact kernel exists with up to 4 stance contacts per step at N <= 10, with at most 2 at N = 12 - 20
     // (per-QP records, weights and wrenches, contact normals, a live horizon: only the general kernel reads them)
     const unsigned state = state_of(h);                  // (rank-aware steps alone do not ask for the general kernel: the compact kernels have no wrench steps)
-    general = general || k == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || (state & ~bit(Form::RankAware));
+    general = general || k == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || (state & ~bit(Form::RankAware)) || c.ext_call;   // (a staged wrench call: MODE 7, for every contact pattern)
     // N = 20 single support too, for batches: the general kernel holds 2 workgroups per CU there, the compact one 1
     // (tools/schedule_bench.py, 16,384 QPs: 2.85 M QP/s against 1.95 M; at N = 12 / 16 the compact kernel wins, 7.1 / 4.9 M
     // against 5.7 / 4.2 M)
@@ -1090,6 +1114,8 @@ Plan plan_solve(const srbdqp_handle* h, const Call& c, int B, int maxs, int neff
         const bool side = !dump && !c.f32 && N <= kRobotsMaxHorizon;   // (the side-input forms are fp64 batch kernels for N <= 20, and the dump has none)
         p.form = launch_form(side ? state : state & ~kSideInputs);
         if (p.form == Form::Plain && !c.f32 && N <= 10 && lat) p.form = Form::Lat;
+        // a staged wrench call (the entry points admit it on a Plain handle only, N <= 20): the low-latency MODE 7 instantiation where the plain call has one, else the batch one
+        if (c.ext_call) p.form = (N <= 10 && lat) ? Form::LatExtWrench : Form::ExtWrench;
         p.tile_classes = c.f32 && !c.signal && !(cfg.flags & SRBDQP_FLAG_F64_TILES) && (B >= kTileClassMinBatch || (cfg.flags & SRBDQP_FLAG_F32_TILES));
     } else {
         // ---- the presolved family (srbdqp_compact.hpp): <N, 2> or, at N <= 10, <N, 4>; the one-wave kernel where the QP has at most 64 presolved variables
@@ -1636,6 +1662,7 @@ int srbdqp_destroy(srbdqp_handle* h) {
     if (h->done_count) (void)hipFree(h->done_count);
     h->robots.release(); h->weights.release(); h->normals.release(); h->ext.release();
     if (h->stage_host) (void)hipHostFree(h->stage_host);
+    if (h->stage_ew_host) (void)hipHostFree(h->stage_ew_host);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->ev_mid) (void)hipEventDestroy(h->ev_mid);
@@ -1662,11 +1689,9 @@ int srbdqp_stage_ptrs(srbdqp_handle* h, srbdqp_stage* out) {
     return SRBDQP_OK;
 }
 
-int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = require_form(h, "srbdqp_solve_staged_f64", kFormsStaged)) return rc;
-    if (B < 0 || B > h->stage_h.capacity) { h->err = "staged batch exceeds the staging capacity"; return SRBDQP_E_INVALID; }
-    if (B == 0) return SRBDQP_OK;
+namespace {
+// the staged solve of B QPs over the staging arrays, behind its entry point's checks; with_wrench: QP b under block b of the staged wrench array, in every pass
+int solve_staged_impl(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y, bool with_wrench) {
     {   // (the kernel of the call before this one published its completion word before it ended)
         const int rq = aql_quiesce(h);
         if (rq != SRBDQP_OK) return rq;
@@ -1677,6 +1702,7 @@ int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32
     Call c;                        // same per-batch kernel choice as the host-buffer API, from the staged contact flags
     const Contacts k = scan_contacts(h->stage_h.contact, (size_t)B, (size_t)h->cfg.horizon, true);
     c.staged = true; c.lazy = &lazy;   // (lazy: the rho restart costs two more launches: only when needed)
+    if (with_wrench) { c.ext_call = h->stage_ew_dev; c.ext_host = h->stage_ew_host; }   // (the restart passes below launch with this Call: they carry the wrench)
     // completion: the kernel publishes a sequence number in host memory after its outputs (signal_done()); spinning on it skips the stream's completion
     // interrupt (~15 us)
     c.signal = !(h->cfg.flags & SRBDQP_FLAG_NO_SPIN);
@@ -1701,6 +1727,71 @@ int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32
     return rc;
 }
 
+// the staging array of the staged wrench calls, made when a call first needs it (zero-filled: a block nobody wrote is no wrench)
+int ensure_stage_ext_wrench(srbdqp_handle* h) {
+    if (h->stage_ew_host) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t bytes = (size_t)h->stage_h.capacity * (size_t)h->cfg.horizon * 6 * sizeof(double);
+    void* host = nullptr; void* dev = nullptr;
+    HIP_TRY(h, hipHostMalloc(&host, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    if (hipHostGetDevicePointer(&dev, host, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipHostFree(host); h->err = "hipHostGetDevicePointer(staged wrench) failed"; return SRBDQP_E_HIP; }
+    std::memset(host, 0, bytes);
+    h->stage_ew_host = static_cast<double*>(host); h->stage_ew_dev = static_cast<double*>(dev);
+    return SRBDQP_OK;
+}
+
+// May this handle run staged wrench call `fn`?  The refusal table answers for the handle's state -- no form but Plain is admitted: a side input or a
+// handle-level wrench in the setters' texts, a live horizon, rank-aware steps --, and the wrench's own rules for what no state bit says: N = 24 has no MODE 7
+// instantiation, and only the general kernel reads a wrench (the words of srbdqp_set_external_wrench and of variant_check_batch).
+constexpr unsigned kFormsStagedWrench = 0;
+int check_staged_wrench(srbdqp_handle* h, const char* fn) {
+    if (const int rc = require_form(h, fn, kFormsStagedWrench)) return rc;
+    if (h->cfg.horizon > row(Form::ExtWrench).max_horizon) { h->err = std::string(fn) + ": " + ExtWrenchIn::n24(fn); return SRBDQP_E_INVALID; }
+    if (!general_allowed(h->cfg)) {
+        h->err = std::string(fn) + ": " + row(Form::ExtWrench).noun + " is read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH";
+        return SRBDQP_E_INVALID;
+    }
+    return SRBDQP_OK;
+}
+
+// B blocks at w (the staged wrench array, or the caller's own before it is copied there) by the rule of srbdqp_set_external_wrench, before anything is launched
+int validate_staged_wrench(srbdqp_handle* h, const double* w, int32_t B, const char* fn) {
+    const size_t count = (size_t)B * ExtWrenchIn::per_qp(h);
+    for (size_t i = 0; i < count; ++i)
+        if (const char* why = ext_wrench_fault(w + i)) {
+            h->err = std::string(fn) + ": " + ExtWrenchIn::where(h, i) + " is invalid (" + why + "); nothing was launched";
+            return SRBDQP_E_INVALID;
+        }
+    return SRBDQP_OK;
+}
+}  // namespace
+
+int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = require_form(h, "srbdqp_solve_staged_f64", kFormsStaged)) return rc;
+    if (B < 0 || B > h->stage_h.capacity) { h->err = "staged batch exceeds the staging capacity"; return SRBDQP_E_INVALID; }
+    if (B == 0) return SRBDQP_OK;
+    return solve_staged_impl(h, B, use_pcom, use_warm, want_x, want_y, false);
+}
+
+int srbdqp_stage_ext_wrench(srbdqp_handle* h, double** out) {
+    if (!h || !out) return SRBDQP_E_INVALID;
+    *out = nullptr;
+    if (const int rc = ensure_stage_ext_wrench(h)) return rc;
+    *out = h->stage_ew_host;
+    return SRBDQP_OK;
+}
+
+int srbdqp_solve_staged_wrench_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = check_staged_wrench(h, "srbdqp_solve_staged_wrench_f64")) return rc;
+    if (B < 0 || B > h->stage_h.capacity) { h->err = "staged batch exceeds the staging capacity"; return SRBDQP_E_INVALID; }
+    if (B == 0) return SRBDQP_OK;
+    if (const int rc = ensure_stage_ext_wrench(h)) return rc;
+    if (const int rc = validate_staged_wrench(h, h->stage_ew_host, B, "srbdqp_solve_staged_wrench_f64")) return rc;
+    return solve_staged_impl(h, B, use_pcom, use_warm, want_x, want_y, true);
+}
+
 int srbdqp_update_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact,
                       const double* pcom, double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters) {
     if (!h) return SRBDQP_E_INVALID;
@@ -1715,6 +1806,32 @@ int srbdqp_update_f64(srbdqp_handle* h, const double* x0, const double* x_ref, c
     if (contact != s.contact) std::memcpy(s.contact, contact, N * 4);
     if (pcom && pcom != s.pcom) std::memcpy(s.pcom, pcom, N * 3 * sizeof(double));
     const int rc = srbdqp_solve_staged_f64(h, 1, pcom != nullptr, 0, x_out != nullptr, 0);
+    if (rc != SRBDQP_OK) return rc;
+    if (u0_out != s.u) std::memcpy(u0_out, s.u, 12 * sizeof(double));
+    if (u_out && u_out != s.u) std::memcpy(u_out, s.u, N * 12 * sizeof(double));
+    if (x_out && x_out != s.x) std::memcpy(x_out, s.x, (N + 1) * 13 * sizeof(double));
+    if (status) *status = s.status[0];
+    if (iters) *iters = s.iters[0];
+    return SRBDQP_OK;
+}
+
+int srbdqp_update_wrench_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact,
+                             const double* pcom, const double* ext_wrench, double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = check_staged_wrench(h, "srbdqp_update_wrench_f64")) return rc;
+    if (!x0 || !x_ref || !foot || !contact || !ext_wrench || !u0_out) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const int rc = ensure_stage_ext_wrench(h)) return rc;
+    const size_t N = (size_t)h->cfg.horizon;
+    const srbdqp_stage& s = h->stage_h;
+    // the wrench first, where the caller has it: a value that is none returns before any staging array -- the staged wrench array included -- is written
+    if (const int rc = validate_staged_wrench(h, ext_wrench, 1, "srbdqp_update_wrench_f64")) return rc;
+    if (ext_wrench != h->stage_ew_host) std::memcpy(h->stage_ew_host, ext_wrench, N * 6 * sizeof(double));
+    if (x0 != s.x0) std::memcpy(s.x0, x0, 13 * sizeof(double));
+    if (x_ref != s.x_ref) std::memcpy(s.x_ref, x_ref, N * 13 * sizeof(double));
+    if (foot != s.foot) std::memcpy(s.foot, foot, N * 12 * sizeof(double));
+    if (contact != s.contact) std::memcpy(s.contact, contact, N * 4);
+    if (pcom && pcom != s.pcom) std::memcpy(s.pcom, pcom, N * 3 * sizeof(double));
+    const int rc = solve_staged_impl(h, 1, pcom != nullptr, 0, x_out != nullptr, 0, true);
     if (rc != SRBDQP_OK) return rc;
     if (u0_out != s.u) std::memcpy(u0_out, s.u, 12 * sizeof(double));
     if (u_out && u_out != s.u) std::memcpy(u_out, s.u, N * 12 * sizeof(double));

@@ -63,6 +63,10 @@ namespace srbdqp {
 constexpr int kModeSolve = 0, kModeDump = 1, kModeRobots = 2, kModeLive = 3, kModeNormals = 4, kModeRankAware = 5, kModeWeights = 6, kModeExtWrench = 7;
 // the doubles a mode keeps behind its layout (WrenchSmem::o_end, the launcher adds them): the robot in [0 .. 7] (qp_robot_to_lds), then the weights' and the wrench's
 constexpr int kSlotRobot = 0, kSlotRobotBad = 7, kSlotRs2 = 8, kSlotWeightsBad = 9, kSlotWrenchBad = 10;
+// ... and, in the low-latency instantiation of MODE 7 alone (XW > 0), the 6 N rows [I_w^-1 tau_k; f_k / m] of the QP's wrench for the roll-out, which the batch form reads
+// from the caller's array again: there the array is GPU-mapped host memory, and a read of it one more PCIe round trip at the end of the call
+constexpr int kSlotWrenchAcc = 12;
+constexpr int wrench_lat_ew_xd(int N) { return kSlotWrenchAcc + 6 * N; }   // the doubles that instantiation keeps behind its layout
 constexpr int wrench_kreg64(int N, int MODE) { return (MODE == kModeLive && N == 24) ? SRBDQP_LIVE24_KREG : 56; }
 template <int MODE>
 struct WrenchMode {
@@ -800,20 +804,22 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     typedef TT v4t __attribute__((ext_vector_type(4)));
     static_assert(sizeof(TT) == 8 || (sizeof(R) == 4 && MODE == kModeSolve), "fp32 tiles belong to the fp32 path");
     constexpr int n = S::n, m = S::m, NW = S::NW, NWS = S::NWS, BT = S::BT, LT = S::LT, TS = S::TS, CHMAX = S::CHMAX;
-    static_assert(XW == 0 || (sizeof(TT) == 8 && (MODE == kModeSolve || MODE == kModeLive)), "extra set-up waves: fp64 tiles, solve mode");
+    static_assert(XW == 0 || (sizeof(TT) == 8 && (MODE == kModeSolve || MODE == kModeLive || (MODE == kModeExtWrench && N <= 10))), "extra set-up waves: fp64 tiles, solve mode (MODE 7: its low-latency form)");
     static_assert((S::o_R % 2) == 0 && (S::o_wb % 2) == 0 && (S::o_tb % 2) == 0 && (S::o_vb % 2) == 0, "16-byte alignment");
     static_assert(S::NT <= 2 * NW || S::WQ >= 1, "");
     static_assert((S::o_zt % 2) == 0, "16-byte alignment of the 6-vectors");
     const double rho_b = unis(SRBDQP_RHO_OF(a, b));   // (per-QP values are wave-uniform: scalar registers, see uni())
     constexpr bool EW = M::EW, WT = M::WT, RB = M::RB, LH = M::LH, CN = M::CN, RA = M::RA;
-    static_assert(!M::batch_f64 || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && (XW == 0 || (LH && N == 24))),
-                  "robot records, weights, a wrench, contact normals, live horizons, rank-aware steps: the fp64 batch instantiation");
+    static_assert(!M::batch_f64 || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && (XW == 0 || (LH && N == 24) || (EW && N <= 10))),
+                  "robot records, weights, a wrench, contact normals, live horizons, rank-aware steps: the fp64 batch instantiation (a wrench: the low-latency one too)");
+    constexpr bool LATM = MODE == kModeSolve || EW;                   // the modes with a low-latency form (XW > 0 at N <= 10): the staged calls' and, MODE 7, the staged wrench calls'
+    constexpr bool EWL = EW && XW > 0;                                // MODE 7, low-latency form: the wrench's rows wait in LDS for the roll-out (kSlotWrenchAcc)
     const int NL = LH ? nl : N;                                      // the live horizon (wave-uniform: a kernel argument)
     [[maybe_unused]] const double* const RBV = sm + S::o_end;        // RB: the QP's robot (qp_robot_to_lds), from the first barrier on, and what WT and EW keep behind it (kSlot*)
     [[maybe_unused]] const double* const LT_ = sm + S::o_L;          // MODE 4: L of every step, from the second barrier on
     const int t = threadIdx.x, lane = t & 63;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-    constexpr bool CSUM = XW > 0 && sizeof(TIO) == 8 && MODE == kModeSolve && S::LT <= 256;   // the low-latency instantiations: the completion word may carry a checksum (KArgs::done_cs)
+    constexpr bool CSUM = XW > 0 && sizeof(TIO) == 8 && (MODE == kModeSolve || MODE == kModeExtWrench) && S::LT <= 256;   // the low-latency instantiations: the completion word may carry a checksum (KArgs::done_cs)
     unsigned long long cs_host = 0;                                  // XOR of the 64-bit patterns this thread stores for the host
     int mcol = lane & 15, kq = lane >> 4;
     TT* T = reinterpret_cast<TT*>(sm + S::o_T);
@@ -951,6 +957,11 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
             static_assert(6 * N <= BT, "one thread per entry of the wrench");
             if (t < 6 * N) {
                 const int k = t / 6, comp = t - 6 * k;
+                if constexpr (EWL) {   // (... and the row itself for the roll-out; of the values qp_ext_wrench_to_lds left: zeros for a wrench that is none)
+                    const double acc_ = ext_wrench_accel(sm + S::o_eh + 6 * k, comp, sm[S::o_tm + k * 9], sm[S::o_tm + k * 9 + 1], RBV[1], RBV[2], RBV[3], RBV[0]);
+                    sm[S::o_eh + 6 * N + t] = a.dt * acc_;
+                    sm[S::o_end + kSlotWrenchAcc + t] = acc_;
+                } else
                 sm[S::o_eh + 6 * N + t] = a.dt * ext_wrench_accel(sm + S::o_eh + 6 * k, comp, sm[S::o_tm + k * 9], sm[S::o_tm + k * 9 + 1], RBV[1], RBV[2], RBV[3], RBV[0]);
             }
         }
@@ -1067,8 +1078,10 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     else __syncthreads();
     // the 3 torque entries of a step are an O(N) loop of 7 LDS reads, the 6 force entries one of 1 read: the two kinds sit on
     // different waves where the workgroup has more than one (entry by entry over all threads every wave ran both loops)
-    constexpr int GT_HL = (64 * ((3 * N + 63) / 64) + 6 * N <= BT) ? 64 * ((3 * N + 63) / 64) : 3 * N;
-    static_assert(GT_HL + 6 * N <= BT, "one pass over the G'v tables");
+    // (MODE 7, low-latency form: the refinement of x_q forms these tables again behind the set-up helpers' end -- the step waves' threads alone)
+    constexpr int GT_TH = EWL ? LT : BT;
+    constexpr int GT_HL = (64 * ((3 * N + 63) / 64) + 6 * N <= GT_TH) ? 64 * ((3 * N + 63) / 64) : 3 * N;
+    static_assert(GT_HL + 6 * N <= GT_TH && (!EWL || (n <= LT && 6 * N <= LT)), "one pass over the G'v tables");
     [[maybe_unused]] auto gt_tables_wave = [&](const double* vec) {   // the same tables on one wave (XW = 2: helper wave NWS)
         for (int e0 = lane; e0 < 9 * N; e0 += 64) {
             if (e0 < 3 * N) {
@@ -1593,7 +1606,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     // chain of diagonal-tile inversions (below).  Wave j owns diagonal tile (j, j) AND the tile above it, (j - 1, j) -- so the next diagonal tile is updated from
     // its owner's registers and inverted without waiting for anybody -- ; wave 0 also owns (0, 2) and (1, 3), wave 2 (0, 3).  In the assembly wave 0 holds (0, 0)
     // only (it inverts it beside the other waves' assembly): its two other tiles are assembled by waves 1 and 3 in their free slot and handed over through LDS.
-    constexpr bool LATP = XW == 2 && NW == 4 && sizeof(TT) == 8 && MODE == kModeSolve;
+    constexpr bool LATP = XW == 2 && NW == 4 && sizeof(TT) == 8 && LATM;
     static_assert(!LATP || (TS <= 3 && S::NT <= 4), "pipelined tile phases: at most 4 x 4 tiles, three slots per wave");
     constexpr int TSL = LATP ? 3 : TS;                                  // tile slots per wave in these phases
     int ta[TSL], tb[TSL];
@@ -1728,7 +1741,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     // the tile store overlays the tables the other waves are still reading.
     [[maybe_unused]] v4d winv0 = (v4d){0.0, 0.0, 0.0, 0.0};
     [[maybe_unused]] bool pre0 = false;
-    if constexpr (XW > 0 && N <= 10 && sizeof(TT) == 8 && MODE == kModeSolve) {
+    if constexpr (XW > 0 && N <= 10 && sizeof(TT) == 8 && LATM) {
         if (ta[0] == 0 && tb[0] == 0) {                              // (wave-uniform)
             bool ok0;
             winv0 = diag16_invert_dpp(acc[0], lane, ok0, sm + S::o_pre);
@@ -2130,7 +2143,7 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                 // K^-1 are all the instantiations have), and the tails that lay under the tables are written again from the registers they came from
                 double* park = sm + S::o_xs + (stepok ? uvar : 0);
                 if (stepok) { park[0] = xq; park[n] = qv; }
-                static_assert(S::o_scr == S::o_xs + n && S::o_eh + n <= S::o_kt && S::o_cp >= S::o_R && S::o_gv >= S::o_kt, "MODE 7: what the refinement's tables overlay");
+                static_assert(S::o_scr == S::o_xs + n && S::o_cp >= S::o_R && (KREG == CHMAX || (S::o_eh + n <= S::o_kt && S::o_gv >= S::o_kt)), "MODE 7: what the refinement's tables overlay (the half rows' tails, where an instantiation has them)");
                 if constexpr (KREG < CHMAX) {
                     constexpr int E0 = (S::o_gv - S::o_kt) / LT, E1 = (S::o_tf + 6 * N - 1 - S::o_kt) / LT;
                     R* kt = reinterpret_cast<R*>(sm + S::o_kt) + t;
@@ -2432,9 +2445,12 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
                     // (`pushed` is one value per QP, three broadcast reads of the slots.  A QP with a bad wrench forms e from the caller's raw values, NaN perhaps,
                     //  and the select drops it: IEEE semantics, which the library is built with -- no -ffast-math, under which a select on NaN is no barrier)
                     const bool pushed = RBV[kSlotRobotBad] == 0.0 && RBV[kSlotWeightsBad] == 0.0 && RBV[kSlotWrenchBad] == 0.0;
+                    if constexpr (EWL) s += pushed ? RBV[kSlotWrenchAcc + idx] / a.s : 0.0;   // (low-latency form: the row formed at the input stage, not another trip to the caller's array)
+                    else {
                     const double* ge = ext + (row0 + (size_t)j) * 6;
                     const double e = ext_wrench_accel(ge, comp, sm[S::o_tm + j * 9], sm[S::o_tm + j * 9 + 1], RBV[1], RBV[2], RBV[3], RBV[0]);
                     s += pushed ? e / a.s : 0.0;
+                    }
                 }
                 sj[idx] = s;
             }
@@ -2618,6 +2634,32 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, 5, XW>::BT), 1) void srbdqp_wrenc
     (void)in;                                            // (read through staged_in_base(): a.inline_in is set)
     wrench_qp<N, double, double, kModeSolve, double, 5, XW>(a, 0, sm);
     if (!(XW > 0 && a.done_cs)) signal_done(a);
+}
+
+// ... MODE = 7 in the low-latency form (srbdqp_solve_staged_wrench_f64, srbdqp_update_wrench_f64: a few staged QPs, each with the wrench of its CALL): ext = the
+// staged wrench array, 6 N doubles per QP.  The launch-wide robot and weights (no records on this path); the wrench's loads travel with the other inputs'.
+// Names of their own, as MODE = 4 to 6 (tests/test_any_horizon_cpu.py pins the list of srbdqp_wrench_kernel's instantiations).
+template <int N, int XW>
+__global__ __launch_bounds__((WrenchSmem<N, 8, 5, XW>::BT), 1) void srbdqp_wrench_ew_lat_kernel(KArgs a, const double* __restrict__ ext) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    if (!wrench_block_in_launch<N>(a)) return;
+    if (wrench_block_has_work(a))
+        wrench_qp<N, double, double, kModeExtWrench, double, 5, XW>(a, SRBDQP_QP_INDEX(a), sm, nullptr, N, nullptr, nullptr, ext);
+    signal_done(a);
+}
+
+// ... and with the one staged QP's inputs AND its wrench in the kernel-argument segment: StagedIn<N> behind KArgs as in srbdqp_wrench_kernel_in, the 6 N doubles of
+// the wrench behind that (3.4 KB of the segment's 4 KB at N = 10)
+template <int N>
+struct StagedWrench { double w[6 * N]; };
+template <int N, int XW>
+__global__ __launch_bounds__((WrenchSmem<N, 8, 5, XW>::BT), 1) void srbdqp_wrench_ew_lat_kernel_in(KArgs a, StagedIn<N> in, StagedWrench<N> ew) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    (void)in; (void)ew;                                  // (read through staged_in_base(): a.inline_in is set)
+    static_assert(sizeof(KArgs) + sizeof(StagedIn<N>) + sizeof(StagedWrench<N>) <= 4096 && sizeof(StagedIn<N>) % 8 == 0, "the wrench follows StagedIn without padding, inside the segment");
+    const double* ext = reinterpret_cast<const double*>((const char*)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(KArgs) + sizeof(StagedIn<N>));
+    wrench_qp<N, double, double, kModeExtWrench, double, 5, XW>(a, 0, sm, nullptr, N, nullptr, nullptr, ext);
+    if (!a.done_cs) signal_done(a);
 }
 
 }  // namespace srbdqp

@@ -1,0 +1,46 @@
+// srbdqp_wrench_lat_ew.hip -- the low-latency MODE 7 instantiations of the general kernel (the staged wrench calls: srbdqp_solve_staged_wrench_f64,
+// srbdqp_update_wrench_f64) in a code object of their own; srbdqp_wrench_lat_ew.hpp says why.  Host side: one launcher.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "srbdqp.h"
+#include "srbdqp_common.hpp"
+#include "srbdqp_wrench.hpp"
+#include "srbdqp_wrench_lat_ew.hpp"
+
+namespace srbdqp {
+namespace {
+
+// the waves and the pipeline of the plain call's low-latency instantiation (srbdqp.hip launch_wrench_t) on the MODE 7 layout, the wrench's rows for the
+// roll-out behind the mode's slots
+template <int N>
+hipError_t launch_t(bool set_attr, const KArgs& a, const void* in, const double* ew_host, const double* ext_dev, hipStream_t st) {
+    constexpr int XW = (N >= 8) ? 2 : 1;
+    using SL = WrenchLayout<N, kModeExtWrench, 8, 5, XW>;
+    constexpr size_t lds = SL::bytes + wrench_lat_ew_xd(N) * sizeof(double);
+    static_assert(lds <= 163840 && SL::BT == WrenchSmem<N, 8, 5, XW>::BT, "one QP must fit the LDS of a CU");
+    if (!in) {
+        auto k = &srbdqp_wrench_ew_lat_kernel<N, XW>;
+        if (set_attr) if (const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+        hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(SL::BT), lds, st, a, ext_dev);
+        return hipGetLastError();
+    }
+    auto k = &srbdqp_wrench_ew_lat_kernel_in<N, XW>;
+    if (set_attr) if (const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+    StagedWrench<N> ew;
+    std::memcpy(ew.w, ew_host, sizeof(ew.w));
+    hipLaunchKernelGGL(k, dim3(1), dim3(SL::BT), lds, st, a, *static_cast<const StagedIn<N>*>(in), ew);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_wrench_ew_lat(int N, bool set_attr, const KArgs& a, const void* in, const double* ew_host, const double* ext_dev, hipStream_t st) {
+    if (N == 4) return launch_t<4>(set_attr, a, in, ew_host, ext_dev, st);
+    if (N == 8) return launch_t<8>(set_attr, a, in, ew_host, ext_dev, st);
+    if (N == 10) return launch_t<10>(set_attr, a, in, ew_host, ext_dev, st);
+    return hipErrorInvalidValue;
+}
+
+}  // namespace srbdqp

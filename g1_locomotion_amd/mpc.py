@@ -153,6 +153,7 @@ class BatchMPC(_Engine):
     """B independent SRBD convex-MPC QPs per call.  One instance <-> one HIP stream <-> one thread."""
     _CREATE, _DESTROY, _LAST_ERROR = "srbdqp_create", "srbdqp_destroy", "srbdqp_last_error"
     _stage = _fcb = None                    # stage(): NumPy views of the staging arrays, and the CPython binding's capsule on them
+    _stage_ew = None                        # stage_ext_wrench(): the view of the staged wrench array
 
     def __init__(self, horizon: int = 10, dt: float = 0.04, device: int = 0, kernel: int = _lib.KERNEL_AUTO,
                  timing: bool = False, rank_aware: bool = False, **overrides):
@@ -177,7 +178,7 @@ class BatchMPC(_Engine):
         self.m = _lib.ROWS_PER_STEP * self.N
 
     def close(self):
-        self._stage = self._fcb = None              # the views and the capsule point into memory the library is about to free
+        self._stage = self._fcb = self._stage_ew = None   # the views and the capsule point into memory the library is about to free
         super().close()
 
     def _open(self):
@@ -340,6 +341,35 @@ class BatchMPC(_Engine):
                 self._check(rc)
             return
         self._check(self._lib.srbdqp_solve_staged_f64(self._h, int(B), int(use_pcom), int(use_warm), int(want_x), int(want_y)))
+
+    def stage_ext_wrench(self):
+        """NumPy view (capacity, N, 6) of the staged wrench array (srbdqp_stage_ext_wrench): [b, k, 0:3] a world-frame torque about the CoM in N m and
+        [b, k, 3:6] a world-frame force in N on QP b during step k, as set_external_wrench() takes them.  Pinned and GPU-mapped like the arrays of stage(),
+        zero-filled, allocated by the library at the first call."""
+        self._open()
+        if self._stage_ew is None:
+            p = C.c_void_p()
+            self._check(self._lib.srbdqp_stage_ext_wrench(self._h, C.byref(p)))
+            shape = (self.stage()["capacity"], self.N, 6)
+            self._stage_ew = np.ctypeslib.as_array((C.c_double * int(np.prod(shape))).from_address(p.value)).reshape(shape)
+        return self._stage_ew
+
+    def solve_staged_wrench(self, B=1, use_pcom=False, use_warm=False, want_x=True, want_y=False):
+        """solve_staged() with QP b under block b of stage_ext_wrench(), for this call alone (srbdqp_solve_staged_wrench_f64): nothing is set on the engine,
+        and the next solve_staged() is what it would have been.  The general kernel for every contact pattern: its low-latency external-wrench
+        instantiation (wrench_f64_n<N>_lat_ew) at N <= 10 and B <= 8, the batch one (wrench_f64_n<N>_ew) otherwise.  A value that is not finite or above
+        1e6 raises SrbdqpError before anything is launched."""
+        self._open()
+        self._check(self._lib.srbdqp_solve_staged_wrench_f64(self._h, int(B), int(use_pcom), int(use_warm), int(want_x), int(want_y)))
+
+    def bind_update_wrench(self):
+        """srbdqp_update_wrench_f64 for the QP in row 0 of the staging arrays with every argument bound once, as MPC binds the plain call: inputs, wrench and
+        outputs ARE the staging arrays, so the C side copies nothing -> (fn, arguments with pcom, arguments without); rc = fn(*arguments)."""
+        st, ew = self.stage(), self.stage_ext_wrench()
+        P = lambda a: C.c_void_p(a.ctypes.data)
+        ins = (C.c_void_p(self._h.value), P(st["x0"][0]), P(st["x_ref"][0]), P(st["foot"][0]), P(st["contact"][0]))
+        outs = (P(ew[0]), P(st["u"][0]), None, P(st["x"][0]), None, None)
+        return _lib.load_raw().srbdqp_update_wrench_f64, ins + (P(st["pcom"][0]),) + outs, ins + (None,) + outs
 
     def prepare_staged(self, B=1, use_pcom=False):
         """Two-phase call, phase 1 (srbdqp_prepare_staged_f64): set-up of the first B staged QPs from a PREDICTED x0 (whatever the
@@ -530,8 +560,12 @@ class RaggedMPC(_Engine):
 class MPC:
     """Drop-in for ``srbd_mpc.mpc.MPC`` on the hot path (run_simulation.py:169-170,73-82,96,103,106)."""
 
-    def __init__(self, dt: float = 0.04, horizon: int = 10, device: int = 0, strict: bool = True, rank_aware: bool = False, **overrides):
-        """rank_aware=True: the engine is created with SRBDQP_FLAG_RANK_AWARE (BatchMPC) -- a horizon with feet in tandem or point feet on every step gets an
+    def __init__(self, dt: float = 0.04, horizon: int = 10, device: int = 0, strict: bool = True, rank_aware: bool = False, staged_wrench: bool = False,
+                 **overrides):
+        """staged_wrench=True: update(..., external_wrench=w) stays on the staged batch-1 path -- one srbdqp_update_wrench_f64 call over the staging arrays, on
+        the general kernel's low-latency external-wrench instantiation at N <= 10 -- instead of the host-batch route with its two setter calls (the default,
+        False: that route, exactly).  For the robot whose wrench estimate changes at every control step.
+        rank_aware=True: the engine is created with SRBDQP_FLAG_RANK_AWARE (BatchMPC) -- a horizon with feet in tandem or point feet on every step gets an
         answer from update() (the general kernel's batch instantiation through the HIP launch, at its latency) instead of status -1.
         Every solve starts from zero.  (Rounds 1-4 had `warm_start=True`: the previous plan and duals shifted by one step.  Removed in round 5 -- on this
         ADMM (sigma -> 0, alpha = 1.6) an error of the starting point decays by |1 - alpha| = 0.6 per iteration whatever else happens, and the dual residual
@@ -564,6 +598,8 @@ class MPC:
         self._last_fc = False                   # ... through the CPython binding (solve_time is read from it)
         self._last_fast = False                 # the last call went through update()'s bound fast path: results are read from the staging arrays
         self._upd = None                        # srbdqp_update_f64 with every argument bound (see _bind)
+        self.staged_wrench = bool(staged_wrench)
+        self._updw = None                       # srbdqp_update_wrench_f64 with every argument bound (see _update_staged_wrench)
 
     # outcome of the last call.  The fast path of update() leaves everything in the library's staging arrays and these read it there on demand.
     @property
@@ -705,8 +741,8 @@ class MPC:
         contact_normals: (N, 12) / (N, 4, 3) array or a per-step list of world-frame surface normals (BatchMPC.set_contact_normals): the friction pyramids
         of sloped ground.  Such a call goes through the host-batch solve with B = 1 (the staged batch-1 path keeps its layout and has no normals).
         external_wrench: (N, 6) world-frame [torque, force] on the body per horizon step (BatchMPC.set_external_wrench), for this call alone; it goes the
-        same way, through the host setter (set before the solve, cleared after it: two waits for the handle's streams per call).  Both together raise
-        ValueError: no instantiation reads both.
+        same way, through the host setter (set before the solve, cleared after it: two waits for the handle's streams per call) -- or, on an object made with
+        staged_wrench=True, through the staged call srbdqp_update_wrench_f64 (_update_staged_wrench).  Both together raise ValueError: no instantiation reads both.
 
         One C call (srbdqp_update_f64) with every argument bound once: the inputs go straight into the library's pinned staging arrays,
         the results are copied out of them once.  What Python adds to the C call is what NumPy needs to gather the reference's per-step
@@ -714,6 +750,8 @@ class MPC:
         ~2 us less."""
         if contact_normals is not None and external_wrench is not None:
             raise ValueError("update: contact_normals and external_wrench together are not supported (no instantiation of the general kernel reads both)")
+        if external_wrench is not None and self.staged_wrench:
+            return self._update_staged_wrench(contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, external_wrench)
         if contact_normals is not None or external_wrench is not None:
             return self._update_via_batch(contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals, external_wrench)
         # From here to the end of the method: the measured ~4.5 us of Python around srbdqp_update_f64.  Its two arms keep their own copy of "write one QP" and of
@@ -791,8 +829,28 @@ class MPC:
         self._solve_time = time.perf_counter() - t0
         return self._outcome(out["status"][0], out["iters"][0], out["u"][0], out["x"][0], one_rollout, 3)
 
+    def _update_staged_wrench(self, contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, external_wrench):
+        """update() with an external wrench on a staged_wrench=True object: the QP and its wrench into row 0 of the staging arrays, then ONE C call
+        (srbdqp_update_wrench_f64) whose arguments were bound once (BatchMPC.bind_update_wrench).  The wrench is the call's: the next update() without one is
+        the plain staged call, unchanged."""
+        if self._engine is None:
+            self.init_matrices()
+        eng, N = self._engine, self.HORIZON_LENGTH
+        if self._updw is None:
+            self._updw, self._args_w_pcom, self._args_w_nopcom = eng.bind_update_wrench()
+            self._s_ew = eng.stage_ext_wrench()[0]
+        self._last_fast = self._last_fc = False
+        st, use_pcom = self._write_staged(self.x0 if x_current is None else x_current, self.x_ref_hor, c_horizon, contact_horizon, p_com_horizon)
+        self._s_ew[:] = np.asarray(external_wrench, dtype=np.float64).reshape(N, 6)
+        t0 = time.perf_counter()
+        rc = self._updw(*(self._args_w_pcom if use_pcom else self._args_w_nopcom))
+        self._solve_time = time.perf_counter() - t0
+        if rc:
+            _lib.check(rc, eng._h)
+        return self._outcome(st["status"][0], st["iters"][0], st["u"][0].copy(), st["x"][0].copy(), one_rollout, 3)
+
     def close(self):
-        self._upd = self._fcb = None
+        self._upd = self._fcb = self._updw = None
         self._last_fast = self._last_fc = False
         for k in [k for k in vars(self) if k.startswith(("_s_", "_args_"))]:    # what _bind() made: views of, and addresses in, memory the library is about to free
             delattr(self, k)

@@ -543,6 +543,35 @@ int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32
 int srbdqp_update_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact,
                       const double* pcom, double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters);
 
+/* The external wrench of ONE CALL on the staged path: the single robot whose momentum observer estimates a push or a payload anew at every control step.
+ * The model, the layout ([N][6] per QP: torque first, world frame), the bound SRBDQP_EXT_WRENCH_MAX and the outcomes are those of srbdqp_set_external_wrench:
+ * P, A, l, u are unchanged, the gradient and x_out gain the state response to the wrench, a QP without a stance contact gets zero forces and the roll-out
+ * under the wrench.  The wrench belongs to the call and not to the handle: nothing is set and nothing is cleared, and the next srbdqp_solve_staged_f64 /
+ * srbdqp_update_f64 on the handle returns what it would have returned without the wrench call in between.
+ *   srbdqp_stage_ext_wrench          *out = a pinned, GPU-mapped staging array [capacity][N][6] that belongs with the arrays of srbdqp_stage_ptrs (srbdqp_stage
+ *                                    itself keeps its layout), zero-filled, allocated at the first call: a handle that never asks pays nothing;
+ *   srbdqp_solve_staged_wrench_f64   srbdqp_solve_staged_f64 with QP b under block b of that array;
+ *   srbdqp_update_wrench_f64         srbdqp_update_f64 with ext_wrench [N][6] (HOST pointer; the staging array itself is used in place).
+ * The host tests all B blocks before anything is launched: a value that is not finite or above the bound returns SRBDQP_E_INVALID, srbdqp_last_error names the
+ * first bad (qp, step, component), and the output staging arrays are left untouched.  Main inputs that are not finite follow the contract above (status -1,
+ * u and y 0, iters 0 or check_every); x_out is then the roll-out of zero forces under the wrench.
+ * An all-zero block gives what srbdqp_solve_staged_f64 gives on the same inputs TO ROUNDING, not to the bits: the same status, iterations within one check
+ * interval, forces within 2e-3 N.  (Measured on an MI355X: bit-identical u, x, y, status and iters where the plain call runs the general kernel too --
+ * srbdqp_kernel_name wrench_f64_n<N>_lat: more than 60 presolved variables, 3 per stance contact, at N = 8 / 10 --, and 1e-11 N apart with equal iteration
+ * counts where it runs the presolved 4-wave kernel, which sums in another order.)
+ * Kernels: the general kernel for every contact pattern.  N <= 10 and B <= 8: its low-latency MODE 7 instantiation (srbdqp_kernel_name:
+ * wrench_f64_n<N>_lat_ew; one QP: inputs and wrench ride in the kernel-argument segment); N in {12, 16, 20} or 8 < B <= 16: the batch instantiation
+ * wrench_f64_n<N>_ew over the staging arrays, with the completion word.  Every pass of a call -- the host-driven rho restart included -- runs the same one, under
+ * the wrench.  Launched through HIP on the handle's stream (srbdqp_batch1_launch_path keeps its meaning: it describes the calls without a wrench), in order with
+ * the handle's other staged calls.
+ * The two solve calls return SRBDQP_E_INVALID with a message that names the reason on: a handle with robot records, weights, contact normals or a handle-level
+ * wrench set (the setters' texts), SRBDQP_FLAG_RANK_AWARE, a live horizon of SRBDQP_FLAG_ANY_HORIZON, N = 24, and an explicit SRBDQP_KERNEL_COMPACT / _SPLIT /
+ * _WAVE. */
+int srbdqp_stage_ext_wrench(srbdqp_handle* h, double** out);
+int srbdqp_solve_staged_wrench_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y);
+int srbdqp_update_wrench_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact,
+                             const double* pcom, const double* ext_wrench, double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters);
+
 /* Two-phase form of the staged call, for control loops that know the contact schedule, the contact-point positions and the
  * reference horizon BEFORE the state estimate arrives.  K (and its factorisation) depends on neither x0 nor x_ref's non-yaw
  * entries, and the gradient is affine in x0:
