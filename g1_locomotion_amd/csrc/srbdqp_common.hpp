@@ -469,8 +469,15 @@ __device__ __forceinline__ void de_step(const double (&Cm)[9], const double (&t1
         const int p = k / 3, q = k - 3 * p;
         const double e0 = SQ[0] * SQ[0] * t1[q], e1 = SQ[1] * SQ[1] * t1[3 + q], e2 = SQ[2] * SQ[2] * t1[6 + q];
         double v = t2[k] + Cm[p] * e0 + Cm[3 + p] * e1 + Cm[6 + p] * e2;
-        v *= d4;
-        if (p == q) v += (double)(N - m) * dt2 * SQ[6 + p] * SQ[6 + p];
+        if (p == q) {
+            // d4 v + ((N - m) dt2 SQ) SQ is one multiply-add and one rounded product; WHICH product is fused the compiler decides anew with every change of the code
+            // around this line (it swapped D[1][1]'s when T1 / T2 began to arrive from LDS sums, and every force moved by some 1e-8 N).  Chosen and written out:
+            // the velocity-weight product fused for the two yaw-coupled entries, d4 v fused for D[2][2] (what the round-12 build computed).
+            const double x = (double)(N - m) * dt2 * SQ[6 + p];
+            v = (p < 2) ? fma(SQ[6 + p], x, d4 * v) : fma(d4, v, SQ[6 + p] * x);
+        } else {
+            v *= d4;
+        }
         de[k] = v;
         de[9 + k] = d4 * ((p == 0) ? e0 : (p == 1) ? e1 : e2);
     }

@@ -60,7 +60,17 @@ struct Setup1Smem {
     static constexpr int endAb = o_ab + 16 * S::NT * kAbStride;
     static constexpr int o_end = endStg > endAb ? endStg : endAb;
     static constexpr size_t bytes = (size_t)o_end * sizeof(double);
+    // The step pairs (m, i >= m) of the T1 / T2 and G'v tables, a lane each (setup1_pass): pair p = r (N + 1) + c, r < N / 2, is (m, i) = (r, r + c) for c < N - r and
+    // (N - 1 - r, N - 1 - r + c - (N - r)) behind that -- row r of the rectangle holds the N - r pairs of step r and the r + 1 pairs of step N - 1 - r --, so that
+    // the pairs of one m are neighbours in ascending i, from slot pair_base(m) on, and a lane finds its (m, i) without a table.  Slots up to pair_base(m) + N - 1
+    // are addressed (never summed) by lane m: kPairSlots of them.
+    static constexpr int kPairs = S::NPAIR;
+    static constexpr int kPairSlots = (N / 2) * N + N;
+    static constexpr int o_pd = o_t1;                      // 2 per slot: the entries a, b of C_i - C_m     (T1 / T2 sums only: x0c / tf come later)
+    static constexpr int o_pq = up2(endIn);                // 4 per slot: the T2 terms of the pair | later: its three torque terms of the G'v tables
+    static constexpr bool pairs_fit = N % 2 == 0 && kPairs <= 64 && 2 * kPairSlots <= 2 * up2(9 * N) && o_pq + 4 * kPairSlots <= o_end;   // (in LDS that is free while the tables are formed)
     static constexpr bool supported = SplitWs<N, MAXS>::supported && S::NT <= 4;
+    static_assert(!supported || pairs_fit, "a lane and an LDS slot for every step pair of a horizon the one-wave kernel takes");
     static_assert(n + 6 * N <= o_end - o_eh || true, "");
 };
 
@@ -182,22 +192,15 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
             }
         }
     }
-    // prefix sums C_k, wave-uniform (cc_k = sum_{l<=k} cos yaw_l, cs_k = sum_{l<=k} sin yaw_l: the serial loop's order), and C_k to LDS from lane k
-    // (lane m < N: C_m from the same sum with the steps past m adding exact zeros -- a select of ccu[lane] instead is turned back into an indexed load by the
-    // compiler, and the arrays into scratch memory)
-    double ccu[N], csu[N], ccm = 0.0, csm = 0.0;
-    {
-        double ac = 0.0, as = 0.0;
+    // prefix sums C_k (cc_k = sum_{l<=k} cos yaw_l, cs_k = sum_{l<=k} sin yaw_l: the serial loop's order) on lane k, and from there to LDS: lane m < N sums the
+    // wave-uniform cos / sin of all N steps, the steps past m adding exact zeros.  (Until round 13 the prefix sums were ALSO kept as twenty wave-uniform doubles
+    // for the T1 / T2 loop of lane m; the step pairs below read C_i and C_m back from LDS instead.)
+    double ccm = 0.0, csm = 0.0;
 #pragma unroll
-        for (int k = 0; k < N; ++k) {
-            const double c = lane_bcast(yc, k), s = lane_bcast(ys, k);
-            ac += c;
-            as += s;
-            ccu[k] = ac;
-            csu[k] = as;
-            ccm += (k <= lane) ? c : 0.0;
-            csm += (k <= lane) ? s : 0.0;
-        }
+    for (int k = 0; k < N; ++k) {
+        const double c = lane_bcast(yc, k), s = lane_bcast(ys, k);
+        ccm += (k <= lane) ? c : 0.0;
+        csm += (k <= lane) ? s : 0.0;
     }
     if (lane < N) {
         double* C = sm + L1::o_cp + lane * 9;
@@ -238,27 +241,62 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
             if (k < n) sm[L1::o_eh + k] = v;
         }
     }
-    // T1(m) = sum_{i>=m} (C_i - C_m), T2(m) = sum_{i>=m} (C_i - C_m)' W (C_i - C_m) (W = diag(q_0..2)) and from them D_m, E_m of the rank-6 assembly: lane m, in
-    // registers, from the wave-uniform prefix sums.  C has two non-constant entries, so T1 has two (t1a, t1b: [[t1a, t1b, 0], [-t1b, t1a, 0], [0, 0, t1z]]) and T2
+    // T1(m) = sum_{i>=m} (C_i - C_m), T2(m) = sum_{i>=m} (C_i - C_m)' W (C_i - C_m) (W = diag(q_0..2)) and from them D_m, E_m of the rank-6 assembly, on lane m
+    // (de_step).  C has two non-constant entries, so T1 has two (t1a, t1b: [[t1a, t1b, 0], [-t1b, t1a, 0], [0, 0, t1z]]) and T2
     // three ([[t2aa, t2ab, 0], [t2ab, t2bb, 0], [0, 0, t2zz]]).  The sums stay in the differences-first form (every term formed from C_i - C_m, as the loop over LDS
     // it replaces did): the suffix-sum form S(m) - (N - m) C_m, Q(m) - C_m'W S(m) - ... is O(1) per entry but cancels -- C_i grows like i, and T2 near the end
-    // of the horizon comes out ~250 ulps off at N = 10 against a few for this form (tests/test_suffix_tables_cpu.py) --, and here the O(N) loop is N
-    // multiply-adds of registers, no memory access.  (Until round 6: 6 N lanes with 8 LDS reads per step each, a barrier, de_tables over LDS.)
+    // of the horizon comes out ~250 ulps off at N = 10 against a few for this form (tests/test_suffix_tables_cpu.py).  (Until round 6: 6 N lanes with 8 LDS reads per step each, a barrier,
+    // de_tables over LDS.  Rounds 6 - 12: lane m alone, an N-step loop over wave-uniform prefix sums held in 4 N registers.)
+    // Round 13: the terms on the step PAIRS (m, i >= m), a lane each (N (N + 1) / 2 <= 64; Setup1Smem, kPairs) -- the differences and the six terms of a pair are
+    // formed once, by one instruction for all pairs, where lane m formed them in N unrolled steps of ~36 instructions with 54 lanes idle -- and lane m adds up the
+    // slots of its pairs in ascending i, which is the loop's order.  One term stays on lane m: the loop's LAST step (i = N - 1, which every m takes) went into t2zz as
+    // ONE multiply-add, fma(w2 dz, dz, t2zz) -- its select was provably true and the compiler fused the product with the accumulator --, so the pairs (m, N - 1) store
+    // +0 there and lane m ends with that multiply-add; a term rounded first gives another D_m[2][2] wherever w2 dz^2 is not exact (it is exact with the default weight).
+    // The pair lane keeps its two differences for the torque entries of gt_tables.
+    const int pair_c = lane < L1::kPairs ? lane : L1::kPairs - 1;                    // (lanes past the last pair repeat it and store nothing)
+    const int pair_r = pair_c / (N + 1), pair_k = pair_c - pair_r * (N + 1);
+    const bool pair_lo = pair_k < N - pair_r;
+    const int pair_m = pair_lo ? pair_r : N - 1 - pair_r, pair_i = pair_m + (pair_lo ? pair_k : pair_k - (N - pair_r));
+    const double pair_da = CP[9 * pair_i] - CP[9 * pair_m], pair_db = CP[9 * pair_i + 1] - CP[9 * pair_m + 1];
+    double* PD = sm + L1::o_pd;
+    double* PQ = sm + L1::o_pq;
+    {
+        const double w0 = SQ[0] * SQ[0], w1 = SQ[1] * SQ[1], w2 = SQ[2] * SQ[2];
+        const double da = pair_da, db = pair_db, dz = (double)(pair_i - pair_m);
+        if (lane < L1::kPairs) {
+            PD[2 * lane] = da;
+            PD[2 * lane + 1] = db;
+            // (w0 da) da + (w1 db) db, (w0 da) db - (w1 db) da, (w0 db) db + (w1 da) da with the multiply-adds written out, so that the rounding is chosen here and
+            // not by the compiler's contraction of the day: the first product fused, the second rounded (what lane m's loop computed until round 12)
+            PQ[4 * lane] = fma(w0 * da, da, (w1 * db) * db);
+            PQ[4 * lane + 1] = fma(w0 * da, db, -((w1 * db) * da));
+            PQ[4 * lane + 2] = fma(w0 * db, db, (w1 * da) * da);
+            PQ[4 * lane + 3] = (pair_i == N - 1) ? 0.0 : (w2 * dz) * dz;                // (the last step's term: lane m, below)
+        }
+    }
+    __syncthreads();
+    const int pair_base = (2 * lane < N) ? lane * (N + 1) : (N - lane) * N;          // lane m < N: the slot of its pair (m, m)
     if (lane < N) {
         const int mm = lane;
-        const double w0 = SQ[0] * SQ[0], w1 = SQ[1] * SQ[1], w2 = SQ[2] * SQ[2];
         double t1a = 0.0, t1b = 0.0, t2aa = 0.0, t2ab = 0.0, t2bb = 0.0, t2zz = 0.0;
 #pragma unroll
-        for (int i = 0; i < N; ++i) {   // (all N steps, the ones before m adding exact zeros)
-            const bool on = i >= mm;
-            const double da = ccu[i] - ccm, db = csu[i] - csm, dz = (double)(i - mm);
-            t1a += on ? da : 0.0;
-            t1b += on ? db : 0.0;
-            t2aa += on ? (w0 * da) * da + (w1 * db) * db : 0.0;
-            t2ab += on ? (w0 * da) * db - (w1 * db) * da : 0.0;
-            t2bb += on ? (w0 * db) * db + (w1 * da) * da : 0.0;
-            t2zz += on ? (w2 * dz) * dz : 0.0;
+        // (The guard of these sums, and of the two in gt_tables, compiles to an EXEC save + skip branch per step: 60 -> 123 s_cbranch_exec* in the front end, which is
+        //  why 5 % fewer vector instructions return 2 %.  Branch-free -- the term loaded unconditionally and selected against +0 -- costs 104 v_cndmask_b32 and measured
+        //  0.5 % slower, inside the noise: profiles/r13_wave_front_end.txt, `bf`.  Zero-padded rows of N slots would need neither; they do not fit this LDS.)
+        for (int s = 0; s < N; ++s) {   // i = m + s
+            if (s < N - mm) {
+                const double* pd = PD + 2 * (pair_base + s);
+                const double* pq = PQ + 4 * (pair_base + s);
+                t1a += pd[0];
+                t1b += pd[1];
+                t2aa += pq[0];
+                t2ab += pq[1];
+                t2bb += pq[2];
+                t2zz += pq[3];
+            }
         }
+        const double dzl = (double)(N - 1 - mm);
+        t2zz = fma((SQ[2] * SQ[2]) * dzl, dzl, t2zz);
         const double t1z = (double)(((N - mm) * (N - mm - 1)) / 2);
         const double Cm[9] = {ccm, csm, 0.0, -csm, ccm, 0.0, 0.0, 0.0, (double)(mm + 1)};
         const double t1[9] = {t1a, t1b, 0.0, -t1b, t1a, 0.0, 0.0, 0.0, t1z};
@@ -266,33 +304,45 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
         de_step<N>(Cm, t1, t2, SQ, dt2, mm, DE + 18 * mm);
     }
     auto gt_tables = [&](const double* vec) {
-        // the 3 torque entries of a step (an O(N) loop of 7 LDS reads) first, then the 6 force entries (1 read), the latter starting on
-        // the lanes the former leave free: entry by entry every round of the wave ran all three loops (N = 10: 2 x 3 loops -> 1 + 2)
-        for (int e = lane; e < 3 * N; e += 64) {
-            const int j = e / 3, comp = e - 3 * j;
-            const double* Cj = CP + j * 9;
+        // The 3 torque entries of step j are sums over i >= j of dt^2 (C_i - C_j)' (SQ v_i) + dt SQ v_i: the three terms of a pair on ITS lane, from the differences
+        // it holds (C_i - C_j = [[a, b, 0], [-b, a, 0], [0, 0, i - j]]: the products with its exact zeros are left out), then 3 N lanes add up their pairs in
+        // ascending i.  (Until round 13: 3 N lanes, each an N-step loop of 7 LDS reads, 4 subtractions and 8 multiply-adds.)
+        {
+            const double* v = vec + 12 * pair_i;
+            const double p0 = SQ[0] * v[0], p1 = SQ[1] * v[1], p2 = SQ[2] * v[2], dz = (double)(pair_i - pair_m);
+            if (lane < L1::kPairs) {
+                // (the multiply-adds written out, the rounding chosen here: inside, the first product fused and the second rounded; outside, dt^2 (...) rounded and
+                //  dt (SQ v) fused -- what the N-step loop computed until round 12)
+                PQ[4 * lane] = fma(dt, SQ[6] * v[6], dt2 * fma(pair_da, p0, (-pair_db) * p1));
+                PQ[4 * lane + 1] = fma(dt, SQ[7] * v[7], dt2 * fma(pair_db, p0, pair_da * p1));
+                PQ[4 * lane + 2] = fma(dt, SQ[8] * v[8], dt2 * (dz * p2));
+            }
+        }
+        __syncthreads();
+        if (lane < 3 * N) {
+            const int j = lane / 3, comp = lane - 3 * j;
+            const double* pq = PQ + 4 * ((2 * j < N) ? j * (N + 1) : (N - j) * N) + comp;
             double acc = 0.0;
 #pragma unroll
-            for (int i = 0; i < N; ++i) {   // (steps before j add exact zeros: see T1 / T2 above)
-                const double* Ci = CP + i * 9;
-                const double* v = vec + 12 * i;
-                const double term = dt2 * ((Ci[comp] - Cj[comp]) * (SQ[0] * v[0]) + (Ci[3 + comp] - Cj[3 + comp]) * (SQ[1] * v[1]) +
-                                           (Ci[6 + comp] - Cj[6 + comp]) * (SQ[2] * v[2])) + dt * (SQ[6 + comp] * v[6 + comp]);
-                acc += (i >= j) ? term : 0.0;
-            }
+            for (int s = 0; s < N; ++s)   // i = j + s
+                if (s < N - j) acc += pq[4 * s];
             GV[9 * j + comp] = acc;
         }
-        constexpr int HL = (3 * N) % 64;
-        for (int e = lane - HL; e < 6 * N; e += 64) {
-            if (e < 0) continue;
-            const int j = e / 6, comp = 3 + (e - 6 * j);
-            double acc = 0.0;
-            const int off = (comp < 6) ? comp : 3 + comp;
+        // The 6 force entries of step j: the plain and the (i - j)-weighted sums over i >= j of one entry of v_i, one lane each, i = j + s ascending
+        static_assert(6 * N <= 64, "the force entries of the G'v tables are one trip of the wave");
+        if (lane < 6 * N) {
+            const int j = lane / 6, comp = 3 + (lane - 6 * j);
+            const double* v = vec + 12 * j + ((comp < 6) ? comp : 3 + comp);
+            const double winc = (comp < 6) ? 1.0 : 0.0;
+            double acc = 0.0, w = (comp < 6) ? 0.0 : 1.0;                            // (double)(i - j), or 1
 #pragma unroll
-            for (int i = 0; i < N; ++i) {
-                const double v = vec[12 * i + off];
-                const double term = (comp < 6) ? (double)(i - j) * v : v;
-                acc += (i >= j) ? term : 0.0;
+            for (int s = 0; s < N; ++s) {
+                if (s < N - j) {
+                    double term = w * v[12 * s];
+                    asm volatile("" : "+v"(term));                                  // (rounded before it is added, as the loop's select had it: not one multiply-add)
+                    acc += term;
+                }
+                w += winc;
             }
             GV[9 * j + comp] = acc;
         }
