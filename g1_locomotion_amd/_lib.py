@@ -202,6 +202,9 @@ SIGNATURES = {
     "srbdqp_stage_ext_wrench": (_int, [H, C.POINTER(_vp)]),
     "srbdqp_solve_staged_wrench_f64": (_int, [H, _i32, _i32, _i32, _i32, _i32]),
     "srbdqp_update_wrench_f64": (_int, [H, *_QP, dp, dp, dp, dp, dp, i32p, i32p]),
+    "srbdqp_stage_contact_normals": (_int, [H, C.POINTER(_vp)]),
+    "srbdqp_solve_staged_normals_f64": (_int, [H, _i32, _i32, _i32, _i32, _i32]),
+    "srbdqp_update_normals_f64": (_int, [H, *_QP, dp, dp, dp, dp, dp, i32p, i32p]),
     "srbdqp_prepare_staged_f64": (_int, [H, _i32, _i32]),
     "srbdqp_solve_prepared_f64": (_int, [H, _i32, _i32, _i32]),
     # diagnostics

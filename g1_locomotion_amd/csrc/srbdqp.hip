@@ -130,6 +130,9 @@ struct srbdqp_handle {
     // the staged wrench calls' own staging array [capacity][N][6] (srbdqp_stage_ext_wrench), pinned and GPU-mapped like the slab; null until the first call asks
     double* stage_ew_host = nullptr;
     double* stage_ew_dev = nullptr;
+    // ... and the staged normals calls' [capacity][N][12] (srbdqp_stage_contact_normals), filled with (0, 0, 1): a block nobody wrote is flat ground
+    double* stage_cn_host = nullptr;
+    double* stage_cn_dev = nullptr;
     int32_t prepared_B = 0; int prepared_maxs = 4; bool prepared_pcom = false;   // two-phase call: a set-up is pending, on the instantiation plan_two_phase chose
     // kernels whose dynamic-LDS limit has been raised on this handle's device (function attributes are per device, and a
     // process may hold handles on several)
@@ -233,7 +236,8 @@ struct Lazy {
 enum class Family { Wave, WaveDefer, Split, Compact, General };   // one wave per QP, ... with deferred tails, the split pipeline, the 4-wave compact kernel, the general kernel
 // General: any (kFormRows below has a row for each but Lat, the staged low-latency instantiation); Compact: Plain or Lat (the dump is a pass's a.mode == 1)
 // (LatExtWrench: the low-latency instantiation of MODE 7, which only a staged wrench call -- Call::ext_call -- plans; no handle state has its bit)
-enum class Form { Plain, Robots, Weights, ExtWrench, Normals, Live, RankAware, Lat, LatExtWrench };
+// (LatNormals: the same for MODE 4 and a staged normals call -- Call::cn_call)
+enum class Form { Plain, Robots, Weights, ExtWrench, Normals, Live, RankAware, Lat, LatExtWrench, LatNormals };
 // the rho restart of restart_iter_of: none, inside the kernel, further launches on the caller's stream (the staged call: started by the host), or off that stream
 // -- the next launch on it (WaveDefer) or a tail stream (solve_deferred_passes, the ragged buckets)
 enum class Restart { Off, InPlace, Launches, Deferred };
@@ -256,6 +260,8 @@ struct Call {
     Lazy* lazy = nullptr;          // staged path: run only the first pass of a multi-pass solve and hand it back here
     const double* ext_call = nullptr;   // the staged wrench calls: the wrench of THIS call (device address of the staged array), which every pass of it reads
     const double* ext_host = nullptr;   // ... and the host address of the same memory (one staged QP: the wrench rides in the argument segment)
+    const double* cn_call = nullptr;    // the staged normals calls: the contact normals of THIS call (device address of the staged array), which every pass of it reads
+    const double* cn_host = nullptr;    // ... and the host address of the same memory (one staged QP: the normals ride in the argument segment)
     Plan plan;                     // plan_solve(h, c, B, ...), once the fields above are set
 };
 
@@ -895,7 +901,8 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
         }
         if (form == Form::Normals) {
             constexpr int WPSN = WrenchTraits<N, double, 8, srbdqp::WrenchLayout<N, row(Form::Normals).mode>>::wps;
-            return launch_side_form<N, Form::Normals, WPSN>(h, &srbdqp::srbdqp_wrench_cn_kernel<N, WPSN>, a, st, h->normals.dev);
+            // (a staged normals call -- no side input is set then, the entry points see to it -- brings the normals of the call: the same kernel over the staged array)
+            return launch_side_form<N, Form::Normals, WPSN>(h, &srbdqp::srbdqp_wrench_cn_kernel<N, WPSN>, a, st, c.cn_call ? c.cn_call : h->normals.dev);
         }
     }
     if constexpr (sizeof(R) == 8 && N <= 10) {
@@ -923,6 +930,20 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
             h->kname = nm_lew.c_str();
             const hipError_t e = srbdqp::launch_wrench_ew_lat(N, first, ai, inl ? &in : nullptr, c.ext_host, c.ext_call, st);
             if (e != hipSuccess) { h->err = std::string("launch of ") + nm_lew + ": " + hipGetErrorString(e); return SRBDQP_E_HIP; }
+            return SRBDQP_OK;
+        }
+        // a staged normals call of a few QPs: the same again in MODE 4, on the layout with the table L.  Same translation unit as the wrench's kernels, same
+        // launch path; one staged QP: inputs and normals in the argument segment (3,912 of its 4,096 bytes at N = 10)
+        if (form == Form::LatNormals) {
+            static const std::string nm_lcn = nm + "_lat" + row(Form::Normals).suffix;
+            srbdqp::StagedIn<N> in;
+            const bool inl = !(a.count_ptr || a.tile_sel || !c.cn_host || !staged_inline_inputs<N>(h, c, a, in));
+            KArgs ai = a;
+            if (inl) { ai.inline_in = 1; staged_done_checksum(h, ai); }
+            const bool first = h->lds_attr_done.insert(reinterpret_cast<const void*>(uintptr_t(16 * N + 2 + (inl ? 1 : 0)))).second;   // (no function lives at such an address)
+            h->kname = nm_lcn.c_str();
+            const hipError_t e = srbdqp::launch_wrench_cn_lat(N, first, ai, inl ? &in : nullptr, c.cn_host, c.cn_call, st);
+            if (e != hipSuccess) { h->err = std::string("launch of ") + nm_lcn + ": " + hipGetErrorString(e); return SRBDQP_E_HIP; }
             return SRBDQP_OK;
         }
     }
@@ -1096,7 +1117,7 @@ Plan plan_solve(const srbdqp_handle* h, const Call& c, int B, int maxs, int neff
     // ---- the general kernel (srbdqp_wrench.hpp)?  The compact kernel exists with up to 4 stance contacts per step at N <= 10, with at most 2 at N = 12 - 20
     // (per-QP records, weights and wrenches, contact normals, a live horizon: only the general kernel reads them)
     const unsigned state = state_of(h);                  // (rank-aware steps alone do not ask for the general kernel: the compact kernels have no wrench steps)
-    general = general || k == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || (state & ~bit(Form::RankAware)) || c.ext_call;   // (a staged wrench call: MODE 7, for every contact pattern)
+    general = general || k == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || (state & ~bit(Form::RankAware)) || c.ext_call || c.cn_call;   // (a staged wrench / normals call: MODE 7 / MODE 4, for every contact pattern)
     // N = 20 single support too, for batches: the general kernel holds 2 workgroups per CU there, the compact one 1
     // (tools/schedule_bench.py, 16,384 QPs: 2.85 M QP/s against 1.95 M; at N = 12 / 16 the compact kernel wins, 7.1 / 4.9 M
     // against 5.7 / 4.2 M)
@@ -1116,6 +1137,8 @@ Plan plan_solve(const srbdqp_handle* h, const Call& c, int B, int maxs, int neff
         if (p.form == Form::Plain && !c.f32 && N <= 10 && lat) p.form = Form::Lat;
         // a staged wrench call (the entry points admit it on a Plain handle only, N <= 20): the low-latency MODE 7 instantiation where the plain call has one, else the batch one
         if (c.ext_call) p.form = (N <= 10 && lat) ? Form::LatExtWrench : Form::ExtWrench;
+        // a staged normals call: the same choice between the two MODE 4 instantiations
+        if (c.cn_call) p.form = (N <= 10 && lat) ? Form::LatNormals : Form::Normals;
         p.tile_classes = c.f32 && !c.signal && !(cfg.flags & SRBDQP_FLAG_F64_TILES) && (B >= kTileClassMinBatch || (cfg.flags & SRBDQP_FLAG_F32_TILES));
     } else {
         // ---- the presolved family (srbdqp_compact.hpp): <N, 2> or, at N <= 10, <N, 4>; the one-wave kernel where the QP has at most 64 presolved variables
@@ -1663,6 +1686,7 @@ int srbdqp_destroy(srbdqp_handle* h) {
     h->robots.release(); h->weights.release(); h->normals.release(); h->ext.release();
     if (h->stage_host) (void)hipHostFree(h->stage_host);
     if (h->stage_ew_host) (void)hipHostFree(h->stage_ew_host);
+    if (h->stage_cn_host) (void)hipHostFree(h->stage_cn_host);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->ev_mid) (void)hipEventDestroy(h->ev_mid);
@@ -1690,8 +1714,9 @@ int srbdqp_stage_ptrs(srbdqp_handle* h, srbdqp_stage* out) {
 }
 
 namespace {
-// the staged solve of B QPs over the staging arrays, behind its entry point's checks; with_wrench: QP b under block b of the staged wrench array, in every pass
-int solve_staged_impl(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y, bool with_wrench) {
+// the staged solve of B QPs over the staging arrays, behind its entry point's checks; with_wrench: QP b under block b of the staged wrench array, in every pass;
+// with_normals: ... on the contact frames of block b of the staged normals array (at most one of the two: no instantiation reads both)
+int solve_staged_impl(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y, bool with_wrench, bool with_normals = false) {
     {   // (the kernel of the call before this one published its completion word before it ended)
         const int rq = aql_quiesce(h);
         if (rq != SRBDQP_OK) return rq;
@@ -1703,6 +1728,7 @@ int solve_staged_impl(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use
     const Contacts k = scan_contacts(h->stage_h.contact, (size_t)B, (size_t)h->cfg.horizon, true);
     c.staged = true; c.lazy = &lazy;   // (lazy: the rho restart costs two more launches: only when needed)
     if (with_wrench) { c.ext_call = h->stage_ew_dev; c.ext_host = h->stage_ew_host; }   // (the restart passes below launch with this Call: they carry the wrench)
+    if (with_normals) { c.cn_call = h->stage_cn_dev; c.cn_host = h->stage_cn_host; }    // (... and the normals)
     // completion: the kernel publishes a sequence number in host memory after its outputs (signal_done()); spinning on it skips the stream's completion
     // interrupt (~15 us)
     c.signal = !(h->cfg.flags & SRBDQP_FLAG_NO_SPIN);
@@ -1760,6 +1786,45 @@ int validate_staged_wrench(srbdqp_handle* h, const double* w, int32_t B, const c
     for (size_t i = 0; i < count; ++i)
         if (const char* why = ext_wrench_fault(w + i)) {
             h->err = std::string(fn) + ": " + ExtWrenchIn::where(h, i) + " is invalid (" + why + "); nothing was launched";
+            return SRBDQP_E_INVALID;
+        }
+    return SRBDQP_OK;
+}
+
+// the staging array of the staged normals calls, made when a call first needs it (every normal (0, 0, 1): a block nobody wrote is flat ground -- zeros would
+// break the rule 0.5 <= |n|)
+int ensure_stage_contact_normals(srbdqp_handle* h) {
+    if (h->stage_cn_host) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t count = (size_t)h->stage_h.capacity * NormalsIn::per_qp(h);
+    void* host = nullptr; void* dev = nullptr;
+    HIP_TRY(h, hipHostMalloc(&host, count * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+    if (hipHostGetDevicePointer(&dev, host, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipHostFree(host); h->err = "hipHostGetDevicePointer(staged normals) failed"; return SRBDQP_E_HIP; }
+    double* n = static_cast<double*>(host);
+    for (size_t i = 0; i < count; ++i) n[i] = (i % 3 == 2) ? 1.0 : 0.0;
+    h->stage_cn_host = n; h->stage_cn_dev = static_cast<double*>(dev);
+    return SRBDQP_OK;
+}
+
+// May this handle run staged normals call `fn`?  As check_staged_wrench: no form but Plain, and the normals' own rules for what no state bit says -- N = 24 has
+// no MODE 4 instantiation, and only the general kernel reads normals (the words of srbdqp_set_contact_normals and of variant_check_batch).
+constexpr unsigned kFormsStagedNormals = 0;
+int check_staged_normals(srbdqp_handle* h, const char* fn) {
+    if (const int rc = require_form(h, fn, kFormsStagedNormals)) return rc;
+    if (h->cfg.horizon > row(Form::Normals).max_horizon) { h->err = NormalsIn::n24(fn); return SRBDQP_E_INVALID; }
+    if (!general_allowed(h->cfg)) {
+        h->err = std::string(fn) + ": " + row(Form::Normals).noun + " are read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH";
+        return SRBDQP_E_INVALID;
+    }
+    return SRBDQP_OK;
+}
+
+// B blocks at n (the staged normals array, or the caller's own before it is copied there) by the rules of srbdqp_set_contact_normals, before anything is launched
+int validate_staged_normals(srbdqp_handle* h, const double* n, int32_t B, const char* fn) {
+    const size_t groups = (size_t)B * NormalsIn::per_qp(h) / NormalsIn::stride;
+    for (size_t i = 0; i < groups; ++i)
+        if (const char* why = normal_fault(n + NormalsIn::stride * i)) {
+            h->err = std::string(fn) + ": " + NormalsIn::where(h, i) + " is invalid (" + why + "); nothing was launched";
             return SRBDQP_E_INVALID;
         }
     return SRBDQP_OK;
@@ -1832,6 +1897,50 @@ int srbdqp_update_wrench_f64(srbdqp_handle* h, const double* x0, const double* x
     if (contact != s.contact) std::memcpy(s.contact, contact, N * 4);
     if (pcom && pcom != s.pcom) std::memcpy(s.pcom, pcom, N * 3 * sizeof(double));
     const int rc = solve_staged_impl(h, 1, pcom != nullptr, 0, x_out != nullptr, 0, true);
+    if (rc != SRBDQP_OK) return rc;
+    if (u0_out != s.u) std::memcpy(u0_out, s.u, 12 * sizeof(double));
+    if (u_out && u_out != s.u) std::memcpy(u_out, s.u, N * 12 * sizeof(double));
+    if (x_out && x_out != s.x) std::memcpy(x_out, s.x, (N + 1) * 13 * sizeof(double));
+    if (status) *status = s.status[0];
+    if (iters) *iters = s.iters[0];
+    return SRBDQP_OK;
+}
+
+int srbdqp_stage_contact_normals(srbdqp_handle* h, double** out) {
+    if (!h || !out) return SRBDQP_E_INVALID;
+    *out = nullptr;
+    if (const int rc = ensure_stage_contact_normals(h)) return rc;
+    *out = h->stage_cn_host;
+    return SRBDQP_OK;
+}
+
+int srbdqp_solve_staged_normals_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = check_staged_normals(h, "srbdqp_solve_staged_normals_f64")) return rc;
+    if (B < 0 || B > h->stage_h.capacity) { h->err = "staged batch exceeds the staging capacity"; return SRBDQP_E_INVALID; }
+    if (B == 0) return SRBDQP_OK;
+    if (const int rc = ensure_stage_contact_normals(h)) return rc;
+    if (const int rc = validate_staged_normals(h, h->stage_cn_host, B, "srbdqp_solve_staged_normals_f64")) return rc;
+    return solve_staged_impl(h, B, use_pcom, use_warm, want_x, want_y, false, true);
+}
+
+int srbdqp_update_normals_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact,
+                              const double* pcom, const double* normals, double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = check_staged_normals(h, "srbdqp_update_normals_f64")) return rc;
+    if (!x0 || !x_ref || !foot || !contact || !normals || !u0_out) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const int rc = ensure_stage_contact_normals(h)) return rc;
+    const size_t N = (size_t)h->cfg.horizon;
+    const srbdqp_stage& s = h->stage_h;
+    // the normals first, where the caller has them: a normal that is none returns before any staging array -- the staged normals array included -- is written
+    if (const int rc = validate_staged_normals(h, normals, 1, "srbdqp_update_normals_f64")) return rc;
+    if (normals != h->stage_cn_host) std::memcpy(h->stage_cn_host, normals, N * 12 * sizeof(double));
+    if (x0 != s.x0) std::memcpy(s.x0, x0, 13 * sizeof(double));
+    if (x_ref != s.x_ref) std::memcpy(s.x_ref, x_ref, N * 13 * sizeof(double));
+    if (foot != s.foot) std::memcpy(s.foot, foot, N * 12 * sizeof(double));
+    if (contact != s.contact) std::memcpy(s.contact, contact, N * 4);
+    if (pcom && pcom != s.pcom) std::memcpy(s.pcom, pcom, N * 3 * sizeof(double));
+    const int rc = solve_staged_impl(h, 1, pcom != nullptr, 0, x_out != nullptr, 0, false, true);
     if (rc != SRBDQP_OK) return rc;
     if (u0_out != s.u) std::memcpy(u0_out, s.u, 12 * sizeof(double));
     if (u_out && u_out != s.u) std::memcpy(u_out, s.u, N * 12 * sizeof(double));

@@ -160,7 +160,7 @@ struct WrenchSmem {
     static constexpr int KREG64 = KR64;   // entries of the fp64 half row kept in registers when it is longer than 60 (N = 24 mixed gait: 56 -> 1.06 M QP/s with 2 reloads from scratch left in the iteration, 48 -> 1.03 M with none, 40 -> 1.01 M)
     // (CN at N = 10, half rows of 30: the last 2 -- with all 30 in registers the MODE = 4 instantiation kept 12 bytes per lane in scratch memory at 3 waves per SIMD, two
     //  of them stored and reloaded in every iteration; 2, 4 and 6 entries in LDS all compile to none)
-    static constexpr int KTAIL = (TB == 8 && CHMAX > 60) ? CHMAX - KREG64 : ((TB == 8 && CHMAX == 36) ? 12 : ((CN && CHMAX == 30) ? 2 : 0));   // N = 12: 3 waves per SIMD
+    static constexpr int KTAIL = (TB == 8 && CHMAX > 60) ? CHMAX - KREG64 : ((TB == 8 && CHMAX == 36) ? 12 : ((CN && CHMAX == 30 && XW == 0) ? 2 : 0));   // N = 12: 3 waves per SIMD (the low-latency MODE 4 form, XW > 0: one workgroup's worth of registers, no tail)
     static constexpr int o_kt = up2(endC);
     static constexpr int o_vl = o_kt + KTAIL * BT;        // VL: row and column of V per lane, entry-major [12][BT]
     static constexpr int endC2 = o_vl + ((TB == 8 && CHMAX <= 36) ? 12 * BT : 0);
@@ -804,22 +804,22 @@ __device__ __forceinline__ void wrench_qp(const KArgs& a, const int b, double* s
     typedef TT v4t __attribute__((ext_vector_type(4)));
     static_assert(sizeof(TT) == 8 || (sizeof(R) == 4 && MODE == kModeSolve), "fp32 tiles belong to the fp32 path");
     constexpr int n = S::n, m = S::m, NW = S::NW, NWS = S::NWS, BT = S::BT, LT = S::LT, TS = S::TS, CHMAX = S::CHMAX;
-    static_assert(XW == 0 || (sizeof(TT) == 8 && (MODE == kModeSolve || MODE == kModeLive || (MODE == kModeExtWrench && N <= 10))), "extra set-up waves: fp64 tiles, solve mode (MODE 7: its low-latency form)");
+    static_assert(XW == 0 || (sizeof(TT) == 8 && (MODE == kModeSolve || MODE == kModeLive || ((MODE == kModeExtWrench || MODE == kModeNormals) && N <= 10))), "extra set-up waves: fp64 tiles, solve mode (MODE 4 and 7: their low-latency forms)");
     static_assert((S::o_R % 2) == 0 && (S::o_wb % 2) == 0 && (S::o_tb % 2) == 0 && (S::o_vb % 2) == 0, "16-byte alignment");
     static_assert(S::NT <= 2 * NW || S::WQ >= 1, "");
     static_assert((S::o_zt % 2) == 0, "16-byte alignment of the 6-vectors");
     const double rho_b = unis(SRBDQP_RHO_OF(a, b));   // (per-QP values are wave-uniform: scalar registers, see uni())
     constexpr bool EW = M::EW, WT = M::WT, RB = M::RB, LH = M::LH, CN = M::CN, RA = M::RA;
-    static_assert(!M::batch_f64 || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && (XW == 0 || (LH && N == 24) || (EW && N <= 10))),
-                  "robot records, weights, a wrench, contact normals, live horizons, rank-aware steps: the fp64 batch instantiation (a wrench: the low-latency one too)");
-    constexpr bool LATM = MODE == kModeSolve || EW;                   // the modes with a low-latency form (XW > 0 at N <= 10): the staged calls' and, MODE 7, the staged wrench calls'
+    static_assert(!M::batch_f64 || (sizeof(R) == 8 && sizeof(TIO) == 8 && sizeof(TT) == 8 && (XW == 0 || (LH && N == 24) || ((EW || CN) && N <= 10))),
+                  "robot records, weights, a wrench, contact normals, live horizons, rank-aware steps: the fp64 batch instantiation (a wrench, contact normals: the low-latency one too)");
+    constexpr bool LATM = MODE == kModeSolve || EW || CN;             // the modes with a low-latency form (XW > 0 at N <= 10): the staged calls' and, MODE 7 and MODE 4, the staged wrench and normals calls'
     constexpr bool EWL = EW && XW > 0;                                // MODE 7, low-latency form: the wrench's rows wait in LDS for the roll-out (kSlotWrenchAcc)
     const int NL = LH ? nl : N;                                      // the live horizon (wave-uniform: a kernel argument)
     [[maybe_unused]] const double* const RBV = sm + S::o_end;        // RB: the QP's robot (qp_robot_to_lds), from the first barrier on, and what WT and EW keep behind it (kSlot*)
     [[maybe_unused]] const double* const LT_ = sm + S::o_L;          // MODE 4: L of every step, from the second barrier on
     const int t = threadIdx.x, lane = t & 63;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-    constexpr bool CSUM = XW > 0 && sizeof(TIO) == 8 && (MODE == kModeSolve || MODE == kModeExtWrench) && S::LT <= 256;   // the low-latency instantiations: the completion word may carry a checksum (KArgs::done_cs)
+    constexpr bool CSUM = XW > 0 && sizeof(TIO) == 8 && (MODE == kModeSolve || MODE == kModeExtWrench || MODE == kModeNormals) && S::LT <= 256;   // the low-latency instantiations: the completion word may carry a checksum (KArgs::done_cs)
     unsigned long long cs_host = 0;                                  // XOR of the 64-bit patterns this thread stores for the host
     int mcol = lane & 15, kq = lane >> 4;
     TT* T = reinterpret_cast<TT*>(sm + S::o_T);
@@ -2659,6 +2659,33 @@ __global__ __launch_bounds__((WrenchSmem<N, 8, 5, XW>::BT), 1) void srbdqp_wrenc
     static_assert(sizeof(KArgs) + sizeof(StagedIn<N>) + sizeof(StagedWrench<N>) <= 4096 && sizeof(StagedIn<N>) % 8 == 0, "the wrench follows StagedIn without padding, inside the segment");
     const double* ext = reinterpret_cast<const double*>((const char*)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(KArgs) + sizeof(StagedIn<N>));
     wrench_qp<N, double, double, kModeExtWrench, double, 5, XW>(a, 0, sm, nullptr, N, nullptr, nullptr, ext);
+    if (!a.done_cs) signal_done(a);
+}
+
+// ... MODE = 4 in the low-latency form (srbdqp_solve_staged_normals_f64, srbdqp_update_normals_f64: a few staged QPs, each with the contact normals of its CALL):
+// normals = the staged normals array, 12 N doubles per QP.  The set-up helper waves and the tile pipeline of the plain staged call on the MODE 4 layout (the table L
+// in the persistent strip); the normals' loads travel with the other inputs', the frames and L are built between the first two barriers as in the batch form.
+// Names of their own, as the MODE 7 pair above.
+template <int N, int XW>
+__global__ __launch_bounds__((WrenchSmem<N, 8, 5, XW>::BT), 1) void srbdqp_wrench_cn_lat_kernel(KArgs a, const double* __restrict__ normals) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    if (!wrench_block_in_launch<N>(a)) return;
+    if (wrench_block_has_work(a))
+        wrench_qp<N, double, double, kModeNormals, double, 5, XW>(a, SRBDQP_QP_INDEX(a), sm, nullptr, N, normals);
+    signal_done(a);
+}
+
+// ... and with the one staged QP's inputs AND its normals in the kernel-argument segment: StagedIn<N> behind KArgs as in srbdqp_wrench_kernel_in, the 12 N doubles of
+// the normals behind that (3.9 KB of the segment's 4 KB at N = 10)
+template <int N>
+struct StagedNormals { double n[12 * N]; };
+template <int N, int XW>
+__global__ __launch_bounds__((WrenchSmem<N, 8, 5, XW>::BT), 1) void srbdqp_wrench_cn_lat_kernel_in(KArgs a, StagedIn<N> in, StagedNormals<N> cn) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    (void)in; (void)cn;                                  // (read through staged_in_base(): a.inline_in is set)
+    static_assert(sizeof(KArgs) + sizeof(StagedIn<N>) + sizeof(StagedNormals<N>) <= 4096 && sizeof(StagedIn<N>) % 8 == 0, "the normals follow StagedIn without padding, inside the segment");
+    const double* normals = reinterpret_cast<const double*>((const char*)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(KArgs) + sizeof(StagedIn<N>));
+    wrench_qp<N, double, double, kModeNormals, double, 5, XW>(a, 0, sm, nullptr, N, normals);
     if (!a.done_cs) signal_done(a);
 }
 

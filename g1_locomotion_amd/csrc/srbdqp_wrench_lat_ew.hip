@@ -1,5 +1,6 @@
-// srbdqp_wrench_lat_ew.hip -- the low-latency MODE 7 instantiations of the general kernel (the staged wrench calls: srbdqp_solve_staged_wrench_f64,
-// srbdqp_update_wrench_f64) in a code object of their own; srbdqp_wrench_lat_ew.hpp says why.  Host side: one launcher.
+// srbdqp_wrench_lat_ew.hip -- the low-latency side-input instantiations of the general kernel in a code object of their own: MODE 7 (the staged wrench calls:
+// srbdqp_solve_staged_wrench_f64, srbdqp_update_wrench_f64) and MODE 4 (the staged normals calls: srbdqp_solve_staged_normals_f64, srbdqp_update_normals_f64);
+// srbdqp_wrench_lat_ew.hpp says why.  Host side: one launcher per mode.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -34,12 +35,40 @@ hipError_t launch_t(bool set_attr, const KArgs& a, const void* in, const double*
     return hipGetLastError();
 }
 
+// ... and on the MODE 4 layout (the table L in the persistent strip; no doubles behind the layout)
+template <int N>
+hipError_t launch_cn_t(bool set_attr, const KArgs& a, const void* in, const double* cn_host, const double* cn_dev, hipStream_t st) {
+    constexpr int XW = (N >= 8) ? 2 : 1;
+    using SL = WrenchLayout<N, kModeNormals, 8, 5, XW>;
+    constexpr size_t lds = SL::bytes;
+    static_assert(lds <= 163840 && SL::BT == WrenchSmem<N, 8, 5, XW>::BT && WrenchMode<kModeNormals>::xd == 0, "one QP must fit the LDS of a CU");
+    if (!in) {
+        auto k = &srbdqp_wrench_cn_lat_kernel<N, XW>;
+        if (set_attr) if (const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+        hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(SL::BT), lds, st, a, cn_dev);
+        return hipGetLastError();
+    }
+    auto k = &srbdqp_wrench_cn_lat_kernel_in<N, XW>;
+    if (set_attr) if (const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+    StagedNormals<N> cn;
+    std::memcpy(cn.n, cn_host, sizeof(cn.n));
+    hipLaunchKernelGGL(k, dim3(1), dim3(SL::BT), lds, st, a, *static_cast<const StagedIn<N>*>(in), cn);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_wrench_ew_lat(int N, bool set_attr, const KArgs& a, const void* in, const double* ew_host, const double* ext_dev, hipStream_t st) {
     if (N == 4) return launch_t<4>(set_attr, a, in, ew_host, ext_dev, st);
     if (N == 8) return launch_t<8>(set_attr, a, in, ew_host, ext_dev, st);
     if (N == 10) return launch_t<10>(set_attr, a, in, ew_host, ext_dev, st);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_wrench_cn_lat(int N, bool set_attr, const KArgs& a, const void* in, const double* cn_host, const double* cn_dev, hipStream_t st) {
+    if (N == 4) return launch_cn_t<4>(set_attr, a, in, cn_host, cn_dev, st);
+    if (N == 8) return launch_cn_t<8>(set_attr, a, in, cn_host, cn_dev, st);
+    if (N == 10) return launch_cn_t<10>(set_attr, a, in, cn_host, cn_dev, st);
     return hipErrorInvalidValue;
 }
 

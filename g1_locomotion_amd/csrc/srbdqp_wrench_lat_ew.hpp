@@ -1,8 +1,8 @@
-// srbdqp_wrench_lat_ew.hpp -- the door to the low-latency MODE 7 kernels of the general kernel (srbdqp_wrench.hpp, srbdqp_wrench_ew_lat_kernel[_in]), which
-// live in a translation unit of their own, srbdqp_wrench_lat_ew.hip.
+// srbdqp_wrench_lat_ew.hpp -- the doors to the low-latency side-input kernels of the general kernel (srbdqp_wrench.hpp: MODE 7, srbdqp_wrench_ew_lat_kernel[_in],
+// and MODE 4, srbdqp_wrench_cn_lat_kernel[_in]), which live in a translation unit of their own, srbdqp_wrench_lat_ew.hip.
 //
 // Why a second translation unit: every translation unit has its own gfx950 code object in the library's fat binary.  srbdqp.hip's holds the batch-1 kernels of
-// the plain staged call, whose loop is known to care where it lies (profiles/r05_loop_alignment.txt).  With the six new kernels here, srbdqp.hip's code object
+// the plain staged call, whose loop is known to care where it lies (profiles/r05_loop_alignment.txt).  With these twelve kernels here, srbdqp.hip's code object
 // is what it was without them -- every kernel at its old address, the same text: the plain call cannot have changed on the device.
 // srbdqp.hip comes FIRST on the compiler's command line: the library's own AQL loader (srbdqp_aql.hpp) and tests/test_aql_contract_cpu.py read the first bundle.
 #pragma once
@@ -16,5 +16,8 @@ namespace srbdqp {
 //   in != nullptr: ONE workgroup with *in = the StagedIn<N> of the QP and the 6 N doubles at ew_host behind it in the kernel-argument segment (a.inline_in set).
 // set_attr: raise the kernel's dynamic-LDS limit first (once per kernel and device: the caller keeps the book, as it does for its own kernels).
 hipError_t launch_wrench_ew_lat(int N, bool set_attr, const KArgs& a, const void* in, const double* ew_host, const double* ext_dev, hipStream_t st);
+
+// The same for the staged normals calls: QP b under cn_dev[12 N b .. 12 N (b + 1)), or the 12 N doubles at cn_host behind *in in the kernel-argument segment.
+hipError_t launch_wrench_cn_lat(int N, bool set_attr, const KArgs& a, const void* in, const double* cn_host, const double* cn_dev, hipStream_t st);
 
 }  // namespace srbdqp

@@ -154,6 +154,7 @@ class BatchMPC(_Engine):
     _CREATE, _DESTROY, _LAST_ERROR = "srbdqp_create", "srbdqp_destroy", "srbdqp_last_error"
     _stage = _fcb = None                    # stage(): NumPy views of the staging arrays, and the CPython binding's capsule on them
     _stage_ew = None                        # stage_ext_wrench(): the view of the staged wrench array
+    _stage_cn = None                        # stage_contact_normals(): the view of the staged normals array
 
     def __init__(self, horizon: int = 10, dt: float = 0.04, device: int = 0, kernel: int = _lib.KERNEL_AUTO,
                  timing: bool = False, rank_aware: bool = False, **overrides):
@@ -178,7 +179,7 @@ class BatchMPC(_Engine):
         self.m = _lib.ROWS_PER_STEP * self.N
 
     def close(self):
-        self._stage = self._fcb = self._stage_ew = None   # the views and the capsule point into memory the library is about to free
+        self._stage = self._fcb = self._stage_ew = self._stage_cn = None   # the views and the capsule point into memory the library is about to free
         super().close()
 
     def _open(self):
@@ -371,6 +372,35 @@ class BatchMPC(_Engine):
         outs = (P(ew[0]), P(st["u"][0]), None, P(st["x"][0]), None, None)
         return _lib.load_raw().srbdqp_update_wrench_f64, ins + (P(st["pcom"][0]),) + outs, ins + (None,) + outs
 
+    def stage_contact_normals(self):
+        """NumPy view (capacity, N, 12) of the staged normals array (srbdqp_stage_contact_normals): [b, k, 3 i : 3 i + 3] the world-frame surface normal under
+        contact i of step k of QP b, as set_contact_normals() takes them (swing contacts included).  Pinned and GPU-mapped like the arrays of stage(), filled
+        with (0, 0, 1) -- a block nobody wrote is flat ground --, allocated by the library at the first call."""
+        self._open()
+        if self._stage_cn is None:
+            p = C.c_void_p()
+            self._check(self._lib.srbdqp_stage_contact_normals(self._h, C.byref(p)))
+            shape = (self.stage()["capacity"], self.N, 12)
+            self._stage_cn = np.ctypeslib.as_array((C.c_double * int(np.prod(shape))).from_address(p.value)).reshape(shape)
+        return self._stage_cn
+
+    def solve_staged_normals(self, B=1, use_pcom=False, use_warm=False, want_x=True, want_y=False):
+        """solve_staged() with QP b under block b of stage_contact_normals(), for this call alone (srbdqp_solve_staged_normals_f64): nothing is set on the
+        engine, and the next solve_staged() is what it would have been.  The general kernel for every contact pattern: its low-latency contact-normals
+        instantiation (wrench_f64_n<N>_lat_cn) at N <= 10 and B <= 8, the batch one (wrench_f64_n<N>_cn) otherwise.  A normal that is not finite, has a
+        length outside [0.5, 2] or n_z < 0.5 after normalising raises SrbdqpError before anything is launched."""
+        self._open()
+        self._check(self._lib.srbdqp_solve_staged_normals_f64(self._h, int(B), int(use_pcom), int(use_warm), int(want_x), int(want_y)))
+
+    def bind_update_normals(self):
+        """srbdqp_update_normals_f64 for the QP in row 0 of the staging arrays with every argument bound once, as bind_update_wrench() binds the wrench call:
+        inputs, normals and outputs ARE the staging arrays, so the C side copies nothing -> (fn, arguments with pcom, arguments without); rc = fn(*arguments)."""
+        st, cn = self.stage(), self.stage_contact_normals()
+        P = lambda a: C.c_void_p(a.ctypes.data)
+        ins = (C.c_void_p(self._h.value), P(st["x0"][0]), P(st["x_ref"][0]), P(st["foot"][0]), P(st["contact"][0]))
+        outs = (P(cn[0]), P(st["u"][0]), None, P(st["x"][0]), None, None)
+        return _lib.load_raw().srbdqp_update_normals_f64, ins + (P(st["pcom"][0]),) + outs, ins + (None,) + outs
+
     def prepare_staged(self, B=1, use_pcom=False):
         """Two-phase call, phase 1 (srbdqp_prepare_staged_f64): set-up of the first B staged QPs from a PREDICTED x0 (whatever the
         staging x0 holds); asynchronous."""
@@ -561,8 +591,11 @@ class MPC:
     """Drop-in for ``srbd_mpc.mpc.MPC`` on the hot path (run_simulation.py:169-170,73-82,96,103,106)."""
 
     def __init__(self, dt: float = 0.04, horizon: int = 10, device: int = 0, strict: bool = True, rank_aware: bool = False, staged_wrench: bool = False,
-                 **overrides):
-        """staged_wrench=True: update(..., external_wrench=w) stays on the staged batch-1 path -- one srbdqp_update_wrench_f64 call over the staging arrays, on
+                 staged_normals: bool = False, **overrides):
+        """staged_normals=True: update(..., contact_normals=n) stays on the staged batch-1 path -- one srbdqp_update_normals_f64 call over the staging arrays, on
+        the general kernel's low-latency contact-normals instantiation at N <= 10 -- instead of the host-batch route (the default, False: that route, exactly).
+        For the robot on sloped ground whose foothold normals change at every control step.
+        staged_wrench=True: update(..., external_wrench=w) stays on the staged batch-1 path -- one srbdqp_update_wrench_f64 call over the staging arrays, on
         the general kernel's low-latency external-wrench instantiation at N <= 10 -- instead of the host-batch route with its two setter calls (the default,
         False: that route, exactly).  For the robot whose wrench estimate changes at every control step.
         rank_aware=True: the engine is created with SRBDQP_FLAG_RANK_AWARE (BatchMPC) -- a horizon with feet in tandem or point feet on every step gets an
@@ -600,6 +633,8 @@ class MPC:
         self._upd = None                        # srbdqp_update_f64 with every argument bound (see _bind)
         self.staged_wrench = bool(staged_wrench)
         self._updw = None                       # srbdqp_update_wrench_f64 with every argument bound (see _update_staged_wrench)
+        self.staged_normals = bool(staged_normals)
+        self._updn = None                       # srbdqp_update_normals_f64 with every argument bound (see _update_staged_normals)
 
     # outcome of the last call.  The fast path of update() leaves everything in the library's staging arrays and these read it there on demand.
     @property
@@ -739,7 +774,8 @@ class MPC:
         """run_simulation.py:106.  Returns (u_opt0 (12,1), x_opt1) where x_opt1[1] is the next state.
         one_rollout=True -> x_opt1 has the whole roll-out (N+1, 13); False -> only rows 0..1.
         contact_normals: (N, 12) / (N, 4, 3) array or a per-step list of world-frame surface normals (BatchMPC.set_contact_normals): the friction pyramids
-        of sloped ground.  Such a call goes through the host-batch solve with B = 1 (the staged batch-1 path keeps its layout and has no normals).
+        of sloped ground.  Such a call goes through the host-batch solve with B = 1 -- or, on an object made with staged_normals=True, through the staged call
+        srbdqp_update_normals_f64 (_update_staged_normals).
         external_wrench: (N, 6) world-frame [torque, force] on the body per horizon step (BatchMPC.set_external_wrench), for this call alone; it goes the
         same way, through the host setter (set before the solve, cleared after it: two waits for the handle's streams per call) -- or, on an object made with
         staged_wrench=True, through the staged call srbdqp_update_wrench_f64 (_update_staged_wrench).  Both together raise ValueError: no instantiation reads both.
@@ -752,6 +788,8 @@ class MPC:
             raise ValueError("update: contact_normals and external_wrench together are not supported (no instantiation of the general kernel reads both)")
         if external_wrench is not None and self.staged_wrench:
             return self._update_staged_wrench(contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, external_wrench)
+        if contact_normals is not None and self.staged_normals:
+            return self._update_staged_normals(contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals)
         if contact_normals is not None or external_wrench is not None:
             return self._update_via_batch(contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals, external_wrench)
         # From here to the end of the method: the measured ~4.5 us of Python around srbdqp_update_f64.  Its two arms keep their own copy of "write one QP" and of
@@ -849,8 +887,28 @@ class MPC:
             _lib.check(rc, eng._h)
         return self._outcome(st["status"][0], st["iters"][0], st["u"][0].copy(), st["x"][0].copy(), one_rollout, 3)
 
+    def _update_staged_normals(self, contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals):
+        """update() with contact normals on a staged_normals=True object: the QP and its normals into row 0 of the staging arrays, then ONE C call
+        (srbdqp_update_normals_f64) whose arguments were bound once (BatchMPC.bind_update_normals).  The normals are the call's: the next update() without
+        them is the plain staged call, unchanged."""
+        if self._engine is None:
+            self.init_matrices()
+        eng, N = self._engine, self.HORIZON_LENGTH
+        if self._updn is None:
+            self._updn, self._args_n_pcom, self._args_n_nopcom = eng.bind_update_normals()
+            self._s_cn = eng.stage_contact_normals()[0]
+        self._last_fast = self._last_fc = False
+        st, use_pcom = self._write_staged(self.x0 if x_current is None else x_current, self.x_ref_hor, c_horizon, contact_horizon, p_com_horizon)
+        self._s_cn[:] = np.asarray(contact_normals, dtype=np.float64).reshape(N, NU)
+        t0 = time.perf_counter()
+        rc = self._updn(*(self._args_n_pcom if use_pcom else self._args_n_nopcom))
+        self._solve_time = time.perf_counter() - t0
+        if rc:
+            _lib.check(rc, eng._h)
+        return self._outcome(st["status"][0], st["iters"][0], st["u"][0].copy(), st["x"][0].copy(), one_rollout, 3)
+
     def close(self):
-        self._upd = self._fcb = self._updw = None
+        self._upd = self._fcb = self._updw = self._updn = None
         self._last_fast = self._last_fc = False
         for k in [k for k in vars(self) if k.startswith(("_s_", "_args_"))]:    # what _bind() made: views of, and addresses in, memory the library is about to free
             delattr(self, k)

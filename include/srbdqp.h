@@ -572,6 +572,33 @@ int srbdqp_solve_staged_wrench_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom
 int srbdqp_update_wrench_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact,
                              const double* pcom, const double* ext_wrench, double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters);
 
+/* The contact normals of ONE CALL on the staged path: the single robot on a ramp or a stair edge whose foothold normals change at every control step.
+ * The convention, the frames, the layout ([N][12] per QP: one world-frame normal per step and contact, swing contacts included) and the rules are those of
+ * srbdqp_set_contact_normals: normalised by the library; every entry finite, 0.5 <= |n| <= 2, n_z >= 0.5 after normalising.  warm_u and u_out stay in the
+ * world frame and in newtons, warm_y and y_out per row.  The normals belong to the call and not to the handle: nothing is set and nothing is cleared, and the
+ * next srbdqp_solve_staged_f64 / srbdqp_update_f64 on the handle returns what it would have returned without the normals call in between.
+ *   srbdqp_stage_contact_normals      *out = a pinned, GPU-mapped staging array [capacity][N][12] that belongs with the arrays of srbdqp_stage_ptrs (srbdqp_stage
+ *                                     itself keeps its layout), filled with (0, 0, 1) for every contact -- a block nobody wrote is flat ground --, allocated at the
+ *                                     first call: a handle that never asks pays nothing;
+ *   srbdqp_solve_staged_normals_f64   srbdqp_solve_staged_f64 with QP b on the contact frames of block b of that array;
+ *   srbdqp_update_normals_f64         srbdqp_update_f64 with normals [N][12] (HOST pointer; the staging array itself is used in place).
+ * The host tests all B blocks before anything is launched: a normal that breaks a rule returns SRBDQP_E_INVALID, srbdqp_last_error names the first bad
+ * (qp, step, contact), and the output staging arrays are left untouched.  Main inputs that are not finite follow the contract above (status -1, u and y 0,
+ * iters 0 or check_every).
+ * Flat normals give what srbdqp_solve_staged_f64 gives on the same inputs TO ROUNDING, not to the bits (the inverse of the full 3 x 3 force block rounds
+ * differently from the flat kernel's reciprocals): the same status, iterations within 5, forces within 1e-6 N.
+ * Kernels: the general kernel for every contact pattern.  N <= 10 and B <= 8: its low-latency MODE 4 instantiation (srbdqp_kernel_name:
+ * wrench_f64_n<N>_lat_cn; one QP: inputs and normals ride in the kernel-argument segment); N in {12, 16, 20} or 8 < B <= 16: the batch instantiation
+ * wrench_f64_n<N>_cn over the staging arrays, with the completion word.  Every pass of a call -- the host-driven rho restart included -- runs the same one, on
+ * the same normals.  Launched through HIP on the handle's stream, in order with the handle's other staged calls.
+ * The two solve calls return SRBDQP_E_INVALID with a message that names the reason on: a handle with robot records, weights, handle-level contact normals or a
+ * handle-level wrench set (the setters' texts), SRBDQP_FLAG_RANK_AWARE, a live horizon of SRBDQP_FLAG_ANY_HORIZON, N = 24, and an explicit
+ * SRBDQP_KERNEL_COMPACT / _SPLIT / _WAVE.  A wrench of the call and normals of the call together have no entry point: no instantiation reads both. */
+int srbdqp_stage_contact_normals(srbdqp_handle* h, double** out);
+int srbdqp_solve_staged_normals_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y);
+int srbdqp_update_normals_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact,
+                              const double* pcom, const double* normals, double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters);
+
 /* Two-phase form of the staged call, for control loops that know the contact schedule, the contact-point positions and the
  * reference horizon BEFORE the state estimate arrives.  K (and its factorisation) depends on neither x0 nor x_ref's non-yaw
  * entries, and the gradient is affine in x0:
