@@ -8,9 +8,11 @@
 //   F  right-looking Cholesky K = U'U: diagonal tile inverted by the packed DPP elimination (diag16_invert_dpp_packed: no matrix-core
 //      instruction, no v_readlane), panel U_jb = L_jj^-1 K_jb (the A operand L_jj^-1 is read from the 2 KB wave-private LDS tile the inversion leaves it in),
 //      trailing update K_ab -= U_ja' U_jb with both operands straight from registers (register r of a C-layout tile is
-//      the A operand of K-step r of a product that contracts over the tile's row index, and the B operand as well);
-//   W  L^-1 block row by block row, in place over the U tiles (W_ij takes the slot of U_ji);
-//   I  K^-1 = W'W tile by tile, stored to the hand-over workspace as it is produced --
+//      the A operand of K-step r of a product that contracts over the tile's row index, and the B operand as well); on the way out of block row j
+//      P_j = W_jj' W_jj (W_jj = L_jj^-1) takes the slot of the diagonal tile and -V_lj = -U_jl' W_jj the slot of U_jl, both such products;
+//   I  X = K^-1 by block recurrence from the factor, U X = L^-1: X_jb = delta_jb P_j - sum_{l>j} V_lj' X_lb, block column by block column from the last and
+//      each from its diagonal block upwards (X_lb = X_bl' for l > b comes back transposed through the staging tiles), stored to the hand-over workspace as
+//      it is produced.  (Until round 19: W = L^-1 block row by block row, then K^-1 = W'W -- 208 matrix-core instructions a pass at NT = 4 where this takes 184.) --
 // with no barrier anywhere (a workgroup is one wave) and 3x the QPs in flight per CU.  Produces exactly the workspace
 // (persistent strip + dense K^-1) the 4-wave set-up kernel produces; everything else is shared with it.
 #pragma once
@@ -476,27 +478,21 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
         return false;
     }
 
-    // A-operand form of a C-layout tile X (operand[r] at lane (i, k') = X[i][4r + k']): through the wave-private tile
+    // A-operand form of a C-layout tile X (operand[r] at lane (i, k') = X[i][4r + k']): read from the wave-private tile, where diag16_invert_dpp_packed leaves
+    // W_jj row-major with the column XOR-swizzled (the only operand that contracts over its COLUMN index since the W phase went: round 20)
     double* scr = sm + L1::o_scr;
-    // (the read half on its own: of a tile that is in scr already in the swizzled form -- what diag16_invert_dpp_packed leaves there)
     auto a_operand_read = [&](double (&op)[4]) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) op[r] = scr[mcol * 16 + ((4 * r + kq) ^ mcol)];
         asm volatile("" ::: "memory");
     };
-    auto a_operand = [&](const v4d& x, double (&op)[4]) {
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int row = kq + 4 * q;
-            scr[row * 16 + (mcol ^ row)] = x[q];
-        }
-        asm volatile("" ::: "memory");
-        a_operand_read(op);
-    };
     const v4d zero4 = (v4d){0.0, 0.0, 0.0, 0.0};
 
-    // ================= F: K = U'U, tiles (j, b > j) become U_jb, tile (j, j) becomes L_jj^-1 =================
+    // ================= F: K = U'U; on the way out tile (j, j) becomes P_j = W_jj' W_jj (W_jj = L_jj^-1) and tile (j, l > j) becomes -V_lj = -U_jl' W_jj =================
+    // (V_lj' = W_jj' U_jl = U_jj^-1 U_jl is all the K^-1 recurrence below needs of block row j: both products contract over the ROW index of their C-layout
+    //  operands, so neither leaves the register file, and they hang on nothing the next inversion waits for.  The form that saves them -- U_jj^-1 U_jb = P_j K'_jb
+    //  straight from the Schur complement, trailing update K'_ja' (P_j K'_jb), no triangular panel -- forms the Schur complements with S_jj^-1 and loses a factor
+    //  kappa: 1e-9 .. 2e-5 relative in K^-1 against 1e-12 .. 1e-10, tests/test_kinv_recurrence_cpu.py.)
     bool all_ok = true;
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
@@ -505,7 +501,6 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
         //  the form a_operand stores: the A operand is read straight from it)
         const v4d w = diag16_invert_dpp_packed(Kt[j][j], lane, ok, scr);
         all_ok = all_ok && ok;
-        Kt[j][j] = w;
         if (j + 1 < NT) {
             double wa[4];
             a_operand_read(wa);
@@ -522,102 +517,93 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
                 for (int bb = aa; bb < NT; ++bb)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) Kt[aa][bb] = mfma_f64(-Kt[j][aa][r], Kt[j][bb][r], Kt[aa][bb]);
+#pragma unroll
+            for (int l = j + 1; l < NT; ++l) {      // -V_lj = -U_jl' W_jj (U_jl is not needed any more)
+                v4d o = zero4;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o = mfma_f64(-Kt[j][l][r], w[r], o);
+                Kt[j][l] = o;
+            }
         }
+        v4d pj = zero4;                              // P_j = W_jj' W_jj = S_jj^-1
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pj = mfma_f64(w[r], w[r], pj);
+        Kt[j][j] = pj;
     }
     if (!all_ok && lane == 0) sm[S::o_misc] = 1.0;
     WSTAMP(a, b, 6);
+    WSTAMP(a, b, 7);                                 // (until round 19 behind the W phase, L^-1 block row by block row: gone, stamp 7 = stamp 6)
 
-    // ================= W = L^-1, block row by block row, W_ij (i > j) into the slot of U_ji =================
-#pragma unroll
-    for (int i = 1; i < NT; ++i) {
-        double wa[4];
-        a_operand(Kt[i][i], wa);                             // W_ii as the left factor
-#pragma unroll
-        for (int j = 0; j < i; ++j) {
-            v4d sacc = zero4;                                // sum_{k=j}^{i-1} L_ik W_kj, L_ik = U_ki'
-#pragma unroll
-            for (int k = j; k < i; ++k) {
-                const v4d& wkj = (k == j) ? Kt[j][j] : Kt[j][k];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) sacc = mfma_f64(Kt[k][i][r], wkj[r], sacc);
-            }
-            v4d o = zero4;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o = mfma_f64(-wa[r], sacc[r], o);
-            Kt[j][i] = o;                                    // U_ji is not needed any more (j' > j use U_j'i only)
-        }
-    }
-
-    WSTAMP(a, b, 7);
-    // ================= I: K^-1 = W'W tile by tile; split: stored as produced, fused: one row per lane =================
+    // ================= I: X = K^-1 by block recurrence from the factor, U X = L^-1 (block lower-triangular, W_jj on its diagonal): =================
+    //     X_jj = P_j - sum_{l>j} V_lj' X_lj,   X_jb = -sum_{l>j} V_lj' X_lb  (b > j),   X_lb = X_bl' for l > b
+    // block column by block column from the LAST, each from its diagonal block upwards: column cb forms its blocks (g, cb), g = cb .. 0, in C layout -- NT - 1 - g
+    // tile products each, 20 at NT = 4 as W'W took, but with no W phase in front (16 products and three LDS round trips; the six V products of F come back) -- from the
+    // blocks below them in the same column.  Those are the column's own down to the diagonal, and below it transposes of blocks an EARLIER (later-numbered) column
+    // formed: (l, cb) = (cb, l)' for l > cb.  These wait in registers (Ku: up to five tiles at NT = 4) and go through the staging tiles: stored transposed, read back
+    // in C layout.  split: stored as produced, both triangles; fused: one row per lane.
     double kin[W::KS];
-    if constexpr (!FUSED) {
-        for (int i = lane; i < S::o_R; i += 64) ws[i] = sm[i];
-        double* kinv = ws + W::o_kinv;
-#pragma unroll
-        for (int aa = 0; aa < NT; ++aa) {
-#pragma unroll
-            for (int bb = aa; bb < NT; ++bb) {
-                v4d o = zero4;                               // sum_{k >= b} W_ka' W_kb
-#pragma unroll
-                for (int k = bb; k < NT; ++k) {
-                    const v4d& wka = (k == aa) ? Kt[aa][aa] : Kt[aa][k];
-                    const v4d& wkb = (k == bb) ? Kt[bb][bb] : Kt[bb][k];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o = mfma_f64(wka[r], wkb[r], o);
-                }
-                const int col = 16 * bb + mcol;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int row = 16 * aa + kq + 4 * q;
-                    if (row < n_eff && col < W::KS) kinv[row * W::KS + col] = (col < n_eff) ? o[q] : 0.0;
-                    if (aa != bb && col < n_eff && row < W::KS) kinv[col * W::KS + row] = (row < n_eff) ? o[q] : 0.0;
-                }
-            }
+    {
+        if constexpr (!FUSED) {
+            for (int i = lane; i < S::o_R; i += 64) ws[i] = sm[i];
         }
-    } else {
-        // one K^-1 row per lane, block column by block column from the LAST: column cb forms only its blocks on and above the diagonal, (g, cb) for g <= cb,
-        // in C layout -- 20 tile products at NT = 4 instead of the 30 of all NT blocks (round 6; K^-1 is symmetric) -- and stages them as row-major tiles in the
-        // dead phase-A arrays.  The blocks below the diagonal are transposes of blocks an EARLIER (later-numbered) column formed: (g, cb) = (cb, g)' for g > cb.
-        // Those wait in registers (Ku: up to five tiles at NT = 4, while the W tiles of the columns done die) and are staged transposed, so that lane (g, i)
-        // pulls row i of tile g with the same 16-byte reads whichever kind it is (rows 18 doubles apart: with 16 the sixteen lanes of a read pass hit two banks,
-        // an 8-way conflict on every one of the 32 reads; the transposed store, 16 lanes of a row 144 bytes apart, is free of conflicts as well).
+        // fused: one K^-1 row per lane -- the blocks of a column are staged as row-major tiles in the dead phase-A arrays, those below the diagonal transposed (the
+        // same store the recurrence reads back), so that lane (g, i) pulls row i of tile g with the same 16-byte reads whichever kind it is (rows 18 doubles apart: with
+        // 16 the sixteen lanes of a read pass hit two banks, an 8-way conflict on every one of the 32 reads; the transposed store, 16 lanes of a row 144 bytes
+        // apart, is free of conflicts as well).
         double* stg = sm + L1::o_cp;
         static_assert(L1::o_end - L1::o_cp >= NT * L1::kStgTile, "staging of one block column of K^-1");
-        const int grp = lane >> 4;
+        [[maybe_unused]] double* kinv = FUSED ? nullptr : ws + W::o_kinv;
+        [[maybe_unused]] const int grp = lane >> 4;
         v4d Ku[NT][NT];                                      // Ku[g][c], g < c: block (g, c), from column c to column g
 #pragma unroll
         for (int cb = NT - 1; cb >= 0; --cb) {
+            v4d Xc[NT];                                      // block (l, cb) in C layout
             asm volatile("" ::: "memory");
 #pragma unroll
-            for (int g = 0; g <= cb; ++g) {
-                v4d o = zero4;                               // sum_{k >= cb} W_kg' W_k,cb
+            for (int l = cb + 1; l < NT; ++l)                // (l, cb) = (cb, l)': row mcol of the staged tile = column mcol of the block
 #pragma unroll
-                for (int k = cb; k < NT; ++k) {
-                    const v4d& wkg = (k == g) ? Kt[g][g] : Kt[g][k];
-                    const v4d& wkc = (k == cb) ? Kt[cb][cb] : Kt[cb][k];
+                for (int q = 0; q < 4; ++q) stg[l * L1::kStgTile + mcol * L1::kStgRow + kq + 4 * q] = Ku[cb][l][q];
+            asm volatile("" ::: "memory");
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) o = mfma_f64(wkg[r], wkc[r], o);
-                }
+            for (int l = cb + 1; l < NT; ++l)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) stg[g * L1::kStgTile + (kq + 4 * q) * L1::kStgRow + mcol] = o[q];
+                for (int q = 0; q < 4; ++q) Xc[l][q] = stg[l * L1::kStgTile + (kq + 4 * q) * L1::kStgRow + mcol];
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int g = cb; g >= 0; --g) {
+                v4d o = (g == cb) ? Kt[cb][cb] : zero4;
+#pragma unroll
+                for (int l = g + 1; l < NT; ++l)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) o = mfma_f64(Kt[g][l][r], Xc[l][r], o);
+                Xc[g] = o;
                 if (g < cb) Ku[g][cb] = o;
-            }
+                if constexpr (FUSED) {
 #pragma unroll
-            for (int g = cb + 1; g < NT; ++g)                // (g, cb) = (cb, g)': row mcol of the staged tile = column mcol of the block
+                    for (int q = 0; q < 4; ++q) stg[g * L1::kStgTile + (kq + 4 * q) * L1::kStgRow + mcol] = o[q];
+                } else {
+                    const int col = 16 * cb + mcol;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) stg[g * L1::kStgTile + mcol * L1::kStgRow + kq + 4 * q] = Ku[cb][g][q];
-            asm volatile("" ::: "memory");
-            const double2* rowp = reinterpret_cast<const double2*>(stg + grp * L1::kStgTile + mcol * L1::kStgRow);
-#pragma unroll
-            for (int h = 0; h < 8; ++h) {
-                if (16 * cb + 2 * h + 1 < W::KS + 1) {
-                    const double2 v = rowp[h];
-                    if (16 * cb + 2 * h < W::KS) kin[16 * cb + 2 * h] = v.x;
-                    if (16 * cb + 2 * h + 1 < W::KS) kin[16 * cb + 2 * h + 1] = v.y;
+                    for (int q = 0; q < 4; ++q) {
+                        const int row = 16 * g + kq + 4 * q;
+                        if (row < n_eff && col < W::KS) kinv[row * W::KS + col] = (col < n_eff) ? o[q] : 0.0;
+                        if (g != cb && col < n_eff && row < W::KS) kinv[col * W::KS + row] = (row < n_eff) ? o[q] : 0.0;
+                    }
                 }
             }
-            asm volatile("" ::: "memory");
+            if constexpr (FUSED) {
+                asm volatile("" ::: "memory");
+                const double2* rowp = reinterpret_cast<const double2*>(stg + grp * L1::kStgTile + mcol * L1::kStgRow);
+#pragma unroll
+                for (int h = 0; h < 8; ++h) {
+                    if (16 * cb + 2 * h + 1 < W::KS + 1) {
+                        const double2 v = rowp[h];
+                        if (16 * cb + 2 * h < W::KS) kin[16 * cb + 2 * h] = v.x;
+                        if (16 * cb + 2 * h + 1 < W::KS) kin[16 * cb + 2 * h + 1] = v.y;
+                    }
+                }
+                asm volatile("" ::: "memory");
+            }
         }
     }
     if constexpr (FUSED) {

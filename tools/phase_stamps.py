@@ -25,7 +25,10 @@ for B in (1, 4096):
     its = it.cpu().numpy()
     dlt = np.diff(s[:, :12], axis=1) * 100.0  # s_memtime ticks are shader cycles; printed 'us' column = cycles / 10
     print(f"B={B} kernel={eng.kernel_name()} mean iters {its.mean():.1f}")
-    for i, nm in enumerate(names):
+    labels = list(names)
+    if eng.kernel_name().startswith("wave_"):   # the one-wave kernel since round 20: no W phase (stamp 7 = stamp 6), K^-1 by block recurrence from the factor
+        labels[5:8] = ["F + V, P", "(W: gone)", "K^-1 rec."]
+    for i, nm in enumerate(labels):
         print(f"  {nm:10s} mean {dlt[:, i].mean() / 100:9.0f} cyc   median {np.median(dlt[:, i]) / 100:9.0f} cyc")
     tot = (s[:, 11] - s[:, 0]) * 100.0
     print(f"  total      mean {tot.mean() / 100:9.0f} cyc   per ADMM iteration {np.mean(dlt[:, 9] / np.maximum(its, 1)) / 100:.0f} cyc")
