@@ -1,0 +1,45 @@
+"""256 walking robots under random commands and random pushes for 100 control steps, in one call (BatchMPC.rollout):
+prints the share of the fleet still on its feet and how well it follows the commanded velocity.
+
+    python examples/fleet_rollout.py [--robots 256] [--steps 100] [--seed 0]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+FEET = np.array([[0.0, 0.0645, 0.0], [0.17, 0.0645, 0.0], [0.0, -0.0645, 0.0], [0.17, -0.0645, 0.0]])   # heel, toe of the left and the right foot
+COM = np.array([0.085, 0.0, 0.598])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--robots", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    from g1_locomotion_amd import BatchMPC
+    rng = np.random.default_rng(a.seed)
+    B, T, dt = a.robots, a.steps, 0.04
+    x0 = np.zeros((B, 13)); x0[:, 3:6] = COM; x0[:, 12] = -9.80665
+    feet = np.tile(FEET.reshape(12), (B, 1))
+    stamp = dt * rng.integers(0, 12, B)                                  # anywhere in the gait period
+    v_ref = rng.uniform(-1.0, 1.0, (B, 2)) * np.array([0.3, 0.1])
+    # a shove of one control period now and then: up to 40 N and 2 N m, on about one robot in twenty per step
+    push = np.where(rng.random((T, B, 1)) < 0.05, rng.uniform(-1.0, 1.0, (T, B, 6)) * np.array([2.0, 2.0, 0.0, 40.0, 40.0, 10.0]), 0.0)
+    with BatchMPC(horizon=10, dt=dt) as eng:
+        r = eng.rollout(x0, feet, stamp, v_ref, T, COM, push=push)
+    alive = r["alive"] != 0
+    half = T // 2                                                        # the mean velocity over the second half of the roll-out, robots still up
+    v = (r["x"][-1, :, 3:5] - r["x"][half, :, 3:5]) / ((T - half) * dt)
+    err = np.linalg.norm(v - v_ref, axis=1)
+    print(f"{B} robots, {T} steps: {alive.mean():.1%} alive, solved {np.mean(r['status'] == 1):.2%} of {r['status'].size} QPs at {r['iters'].mean():.1f} iterations")
+    if alive.any():
+        print(f"mean velocity error of the robots still up: {err[alive].mean():.3f} m/s (commands up to 0.3 m/s; lowest CoM {r['x'][:, alive, 5].min():.3f} m)")
+
+
+if __name__ == "__main__":
+    main()

@@ -41,6 +41,12 @@ class Gait(C.Structure):
                 ("com_target", C.c_double * 3), ("hip_offset_y", C.c_double)]
 
 
+class FleetSettings(C.Structure):
+    """srbdqp_fleet_settings (include/srbdqp_cascade.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("substeps", C.c_int32), ("foot_half_length", C.c_double), ("z_min", C.c_double),
+                ("tilt_max", C.c_double), ("gait", Gait)]
+
+
 class Config(C.Structure):
     """struct srbdqp_config (include/srbdqp.h)."""
     _fields_ = [
@@ -158,6 +164,9 @@ _SIDE = (_int, [H, _vp, _i32])                           # every per-QP side-inp
 _SWING = [H, _i64, dp, dp, dp, dp, _f64, _f64, dp, dp, dp, dp]
 _WBID = [H, _i64, dp, dp, dp, _i32, dp, dp, dp, dp]
 _INPUTS = [H, _i64, dp, dp, dp, dp, u8p, C.POINTER(Gait), dp, dp, u8p, dp, dp]
+_FLEET = C.POINTER(FleetSettings)
+_ADVANCE = [H, _i64, dp, dp, dp, dp, _i64, dp, u8p, dp, u8p, _FLEET]       # B, x, feet, stamp, u0, u0_stride, landing, standing, push, alive, settings
+_ROLLOUT = [H, _i64, _i32, dp, dp, dp, dp, u8p, dp, _FLEET, u8p, dp, dp, dp, i32p, i32p]   # B, T, x, feet, stamp, v_ref, standing, push, settings, alive, the five logs
 SIGNATURES = {
     # include/srbdqp.h -- config, handle
     "srbdqp_default_config": (_int, [_CFG]),
@@ -222,6 +231,12 @@ SIGNATURES = {
     "srbdqp_wbid_reference_device_f64": (_int, _WBID + [_vp]),
     "srbdqp_mpc_inputs_f64": (_int, _INPUTS),
     "srbdqp_mpc_inputs_device_f64": (_int, _INPUTS + [_vp]),
+    # ... and from step t to step t + 1: the fleet's plant step and the K-step loop
+    "srbdqp_fleet_default_settings": (_int, [_FLEET]),
+    "srbdqp_fleet_advance_f64": (_int, _ADVANCE),
+    "srbdqp_fleet_advance_device_f64": (_int, _ADVANCE + [_vp]),
+    "srbdqp_fleet_rollout_device_f64": (_int, _ROLLOUT + [_vp]),
+    "srbdqp_fleet_rollout_f64": (_int, _ROLLOUT),
 }
 EXPORTS = tuple(SIGNATURES)
 

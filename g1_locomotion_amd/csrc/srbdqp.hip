@@ -26,6 +26,7 @@
 #include "srbdqp_wrench.hpp"
 #include "srbdqp_wrench_lat_ew.hpp"
 #include "srbdqp_cascade.hpp"
+#include "srbdqp_fleet.hpp"
 #include "srbdqp_cascade.h"
 #include "srbdqp_aql.hpp"
 
@@ -151,6 +152,13 @@ struct srbdqp_handle {
     // solves run the general kernel instantiated for live_nstar, the smallest tabulated horizon >= n, in its live-horizon mode (srbdqp_wrench.hpp, MODE = 3)
     int live_nstar = 0;                    // 0: the horizon has its own instantiations
     std::string live_name;                 // srbdqp_kernel_name of such a handle: wrench_f64_n<N*>_h<n>
+    // the horizon buffers of srbdqp_fleet_rollout_*, for B robots, carved from one allocation; null until the first roll-out asks (ensure_fleet_buffers)
+    struct FleetBufs {
+        char* mem = nullptr; size_t bytes = 0, B = 0;
+        double *x_ref = nullptr, *foot = nullptr, *pcom = nullptr, *landing = nullptr, *u = nullptr, *x_out = nullptr;
+        uint8_t* contact = nullptr;
+        int32_t *status = nullptr, *iters = nullptr;
+    } fleet;
 };
 
 // slot of a launch stream (at most kMaxSlots distinct streams per handle; null when exhausted)
@@ -1684,6 +1692,7 @@ int srbdqp_destroy(srbdqp_handle* h) {
     }
     if (h->done_count) (void)hipFree(h->done_count);
     h->robots.release(); h->weights.release(); h->normals.release(); h->ext.release();
+    if (h->fleet.mem) (void)hipFree(h->fleet.mem);
     if (h->stage_host) (void)hipHostFree(h->stage_host);
     if (h->stage_ew_host) (void)hipHostFree(h->stage_ew_host);
     if (h->stage_cn_host) (void)hipHostFree(h->stage_cn_host);
@@ -2798,6 +2807,186 @@ int srbdqp_mpc_inputs_f64(srbdqp_handle* h, int64_t B, const double* x0, const d
         dxr = io.out<double>(x_ref, b * N * 13 * 8); dft = io.out<double>(foot, b * N * 12 * 8); dct = io.out<uint8_t>(contact, b * N * 4);
         dpc = io.out<double>(pcom, b * N * 3 * 8); dlp = io.out<double>(landing, b * 3 * 8);
     }, [&](hipStream_t st) { return srbdqp_mpc_inputs_device_f64(h, B, dx0, dfe, dst, dv, dsd, gait, dxr, dft, dct, dpc, dlp, st); });
+}
+
+}  // extern "C"
+
+// ---- from step t to step t + 1: the fleet's plant step and the K-step loop (include/srbdqp_cascade.h; the kernel: srbdqp_fleet.hpp) ----------------------
+namespace {
+
+// what is wrong with a settings struct (null: nothing)
+const char* fleet_settings_fault(const srbdqp_fleet_settings* s) {
+    if (!s || s->struct_size != (int32_t)sizeof(srbdqp_fleet_settings)) return "struct_size is not sizeof(srbdqp_fleet_settings)";
+    if (s->substeps < 1 || s->substeps > 1000) return "1 <= substeps <= 1000";
+    for (const double v : {s->foot_half_length, s->z_min, s->tilt_max})
+        if (!std::isfinite(v) || !(v > 0.0)) return "foot_half_length, z_min and tilt_max must be finite and positive";
+    const srbdqp_gait& g = s->gait;
+    if (g.struct_size != (int32_t)sizeof(srbdqp_gait) || g.period_steps < 1 || g.double_support_steps < 0 || g.double_support_steps > g.period_steps)
+        return "invalid gait (struct_size, 1 <= period_steps, 0 <= double_support_steps <= period_steps)";
+    return nullptr;
+}
+
+// the roll-out's records of one period (srbdqp::FleetArgs): all null outside a roll-out
+struct FleetLogs {
+    double *x = nullptr, *feet = nullptr, *u0 = nullptr;
+    const int32_t *status = nullptr, *iters = nullptr;
+    int32_t *status_log = nullptr, *iters_log = nullptr;
+};
+
+// one launch of the plant step; the arguments have been checked
+int fleet_advance_launch(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride, const double* landing,
+                         const uint8_t* standing, const double* push, uint8_t* alive, const srbdqp_fleet_settings* cfg, const FleetLogs& lg, hipStream_t st) {
+    srbdqp::FleetArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.x = x; a.feet = feet; a.stamp = stamp; a.u0 = u0; a.u0_stride = (long long)u0_stride; a.landing = landing; a.standing = standing; a.push = push;
+    a.alive = alive;
+    a.robots = reinterpret_cast<const double*>(h->robots.dev);   // robot b's own mass and inertia: the plant of the QP it solved
+    a.x_log = lg.x; a.feet_log = lg.feet; a.u0_log = lg.u0; a.status = lg.status; a.iters = lg.iters;
+    a.status_log = lg.status ? lg.status_log : nullptr; a.iters_log = lg.iters ? lg.iters_log : nullptr;
+    a.mass = h->cfg.mass;
+    for (int i = 0; i < 3; ++i) a.inertia[i] = h->cfg.inertia[i];
+    a.dt = h->cfg.dt; a.foot_half_length = cfg->foot_half_length; a.z_min = cfg->z_min; a.tilt_max = cfg->tilt_max;
+    a.substeps = cfg->substeps; a.period = cfg->gait.period_steps; a.ds = cfg->gait.double_support_steps;
+    a.B = (long long)B;
+    HIP_TRY(h, srbdqp::launch_fleet_advance(a, st));
+    h->kname = "fleet_advance_f64";
+    return SRBDQP_OK;
+}
+
+int fleet_advance_check(srbdqp_handle* h, int64_t B, const void* x, const void* feet, const void* stamp, const void* u0, int64_t u0_stride, const void* landing,
+                        const srbdqp_fleet_settings* cfg) {
+    if (B < 0 || (B > 0 && (!x || !feet || !stamp || !u0 || !landing))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (u0_stride < 12) { h->err = "srbdqp_fleet_advance: u0_stride must be at least 12 doubles"; return SRBDQP_E_INVALID; }
+    if (const char* why = fleet_settings_fault(cfg)) { h->err = std::string("invalid srbdqp_fleet_settings: ") + why; return SRBDQP_E_INVALID; }
+    return covers<RobotsIn>(h, B, "srbdqp_fleet_advance: ", " robots with ", false, false);
+}
+
+// the horizon buffers of a roll-out, at B robots, carved from one allocation of the handle's
+int ensure_fleet_buffers(srbdqp_handle* h, size_t B) {
+    auto& f = h->fleet;
+    if (f.mem && f.B >= B) return SRBDQP_OK;
+    const size_t N = (size_t)h->cfg.horizon;
+    auto carve = [&](char* base) {
+        Carver c(base);
+        f.x_ref = c.take<double>(B * N * 13); f.foot = c.take<double>(B * N * 12); f.pcom = c.take<double>(B * N * 3); f.landing = c.take<double>(B * 3);
+        f.u = c.take<double>(B * N * 12); f.x_out = c.take<double>(B * (N + 1) * 13); f.contact = c.take<uint8_t>(B * N * 4);
+        f.status = c.take<int32_t>(B); f.iters = c.take<int32_t>(B);
+        return c.off;
+    };
+    const size_t want = carve(nullptr);
+    if (f.mem) {   // a smaller set may still be in use by an earlier roll-out, on any stream
+        if (const int rc = quiesce_all_streams(h)) return rc;
+        HIP_TRY(h, hipDeviceSynchronize());
+    }
+    f.B = 0;
+    size_t cap = f.mem ? f.bytes : 0;
+    if (const int rc = grow(h, f.mem, cap, want, nullptr, "hipMalloc roll-out buffers")) { f.bytes = cap; return rc; }
+    f.bytes = cap;
+    carve(f.mem);
+    f.B = B;
+    return SRBDQP_OK;
+}
+
+int fleet_rollout_check(srbdqp_handle* h, int64_t B, int32_t T, const void* x, const void* feet, const void* stamp, const void* v_ref,
+                        const srbdqp_fleet_settings* cfg) {
+    if (B < 1 || T < 1 || B > 0x7fffffffLL) { h->err = "srbdqp_fleet_rollout: B and T must be at least 1 (B at most 2^31 - 1)"; return SRBDQP_E_INVALID; }
+    if (!x || !feet || !stamp || !v_ref) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const char* why = fleet_settings_fault(cfg)) { h->err = std::string("invalid srbdqp_fleet_settings: ") + why; return SRBDQP_E_INVALID; }
+    // the plant is flat ground and knows no wrench but the push: a handle whose QPs are told otherwise would roll out against another robot
+    if (h->ext.dev) { h->err = "srbdqp_fleet_rollout: the handle has an external wrench set (srbdqp_set_external_wrench): the plant does not know it -- clear it, and pass the roll-out its push"; return SRBDQP_E_INVALID; }
+    if (h->normals.dev) { h->err = "srbdqp_fleet_rollout: the handle has contact normals set (srbdqp_set_contact_normals): the plant stands on flat ground -- clear them"; return SRBDQP_E_INVALID; }
+    if (const int rc = variant_check_batch(h, (int32_t)B)) return rc;
+    return SRBDQP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srbdqp_fleet_default_settings(srbdqp_fleet_settings* s) {
+    if (!s || s->struct_size != (int32_t)sizeof(srbdqp_fleet_settings)) return SRBDQP_E_INVALID;
+    std::memset(s, 0, sizeof(*s));
+    s->struct_size = (int32_t)sizeof(srbdqp_fleet_settings);
+    s->substeps = 10; s->foot_half_length = 0.085; s->z_min = 0.3; s->tilt_max = 1.0;
+    s->gait.struct_size = (int32_t)sizeof(srbdqp_gait);
+    s->gait.period_steps = 6; s->gait.double_support_steps = 1; s->gait.hip_offset_y = 0.0645;
+    return SRBDQP_OK;
+}
+
+int srbdqp_fleet_advance_device_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
+                                    const double* landing, const uint8_t* standing, const double* push, uint8_t* alive,
+                                    const srbdqp_fleet_settings* cfg, void* stream) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = fleet_advance_check(h, B, x, feet, stamp, u0, u0_stride, landing, cfg)) return rc;
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+    return fleet_advance_launch(h, B, x, feet, stamp, u0, u0_stride, landing, standing, push, alive, cfg, FleetLogs{}, st);
+}
+
+int srbdqp_fleet_advance_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
+                             const double* landing, const uint8_t* standing, const double* push, uint8_t* alive,
+                             const srbdqp_fleet_settings* cfg) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = fleet_advance_check(h, B, x, feet, stamp, u0, u0_stride, landing, cfg)) return rc;
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)B;
+    double *dx, *dfe, *dst, *du, *dlp, *dpu;
+    uint8_t *dsd, *dal;
+    return host_call(h, [&](HostIo& io) {
+        dx = io.add<double>(x, x, b * 13 * 8, false); dfe = io.add<double>(feet, feet, b * 12 * 8, false); dst = io.add<double>(stamp, stamp, b * 8, false);
+        du = io.in<double>(u0, ((b - 1) * (size_t)u0_stride + 12) * 8); dlp = io.in<double>(landing, b * 3 * 8);
+        dsd = io.in<uint8_t>(standing, b); dpu = io.in<double>(push, b * 6 * 8);
+        dal = alive ? io.add<uint8_t>(alive, alive, b, false) : nullptr;
+    }, [&](hipStream_t st) { return srbdqp_fleet_advance_device_f64(h, B, dx, dfe, dst, du, u0_stride, dlp, dsd, dpu, dal, cfg, st); });
+}
+
+int srbdqp_fleet_rollout_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
+                                    const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                    double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log, void* stream) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = fleet_rollout_check(h, B, T, x, feet, stamp, v_ref, cfg)) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
+    if (const int rc = ensure_fleet_buffers(h, b)) return rc;
+    const auto& f = h->fleet;
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+    if (x_log) HIP_TRY(h, hipMemcpyAsync(x_log, x, b * 13 * 8, hipMemcpyDeviceToDevice, st));
+    if (feet_log) HIP_TRY(h, hipMemcpyAsync(feet_log, feet, b * 12 * 8, hipMemcpyDeviceToDevice, st));
+    for (int32_t t = 0; t < T; ++t) {
+        const size_t k = (size_t)t;
+        if (const int rc = srbdqp_mpc_inputs_device_f64(h, B, x, feet, stamp, v_ref, standing, &cfg->gait, f.x_ref, f.foot, f.contact, f.pcom, f.landing, st)) return rc;
+        if (const int rc = srbdqp_solve_batch_device_f64(h, (int32_t)B, x, f.x_ref, f.foot, f.contact, f.pcom, nullptr, nullptr, f.u, f.x_out, nullptr, f.status,
+                                                         f.iters, st)) return rc;
+        if (h->cfg.flags & SRBDQP_FLAG_DEFER_TAIL) if (const int rc = srbdqp_flush(h, st)) return rc;   // the plant needs complete forces
+        FleetLogs lg;
+        lg.x = x_log ? x_log + (k + 1) * b * 13 : nullptr; lg.feet = feet_log ? feet_log + (k + 1) * b * 12 : nullptr; lg.u0 = u0_log ? u0_log + k * b * 12 : nullptr;
+        lg.status = f.status; lg.iters = f.iters;
+        lg.status_log = status_log ? status_log + k * b : nullptr; lg.iters_log = iters_log ? iters_log + k * b : nullptr;
+        if (const int rc = fleet_advance_launch(h, B, x, feet, stamp, f.u, (int64_t)(12 * N), f.landing, standing, push ? push + k * b * 6 : nullptr, alive, cfg, lg, st))
+            return rc;
+    }
+    return SRBDQP_OK;
+}
+
+int srbdqp_fleet_rollout_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
+                             const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                             double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = fleet_rollout_check(h, B, T, x, feet, stamp, v_ref, cfg)) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)B, steps = (size_t)T;
+    double *dx, *dfe, *dst, *dv, *dpu, *dxl, *dul, *dfl;
+    uint8_t *dsd, *dal;
+    int32_t *dsl, *dil;
+    return host_call(h, [&](HostIo& io) {
+        dx = io.add<double>(x, x, b * 13 * 8, false); dfe = io.add<double>(feet, feet, b * 12 * 8, false); dst = io.add<double>(stamp, stamp, b * 8, false);
+        dv = io.in<double>(v_ref, b * 2 * 8); dsd = io.in<uint8_t>(standing, b); dpu = io.in<double>(push, steps * b * 6 * 8);
+        dal = alive ? io.add<uint8_t>(alive, alive, b, false) : nullptr;
+        dxl = io.out<double>(x_log, (steps + 1) * b * 13 * 8); dul = io.out<double>(u0_log, steps * b * 12 * 8); dfl = io.out<double>(feet_log, (steps + 1) * b * 12 * 8);
+        dsl = io.out<int32_t>(status_log, steps * b * 4); dil = io.out<int32_t>(iters_log, steps * b * 4);
+    }, [&](hipStream_t st) { return srbdqp_fleet_rollout_device_f64(h, B, T, dx, dfe, dst, dv, dsd, dpu, cfg, dal, dxl, dul, dfl, dsl, dil, st); });
 }
 
 }  // extern "C"

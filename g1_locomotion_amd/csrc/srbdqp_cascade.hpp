@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "srbdqp_gait.hpp"
+
 namespace srbdqp {
 
 struct SwingArgs {
@@ -169,18 +171,10 @@ __global__ __launch_bounds__(256) void srbdqp_mpc_inputs_kernel(MpcInputsArgs a)
         for (int i = t; i < nr * 2; i += 256) sv[i] = a.v_ref[b0 * 2 + i];
         if (t < nr) {   // alternating single support with a double-support overlap (msgs.AlternatingGait.contact_horizon)
             const bool stand = a.standing && a.standing[b0 + t];
-            const long long k0 = (long long)floor(a.stamp[b0 + t] / a.dt + 1e-9);
-            long long ph = k0 % (2LL * a.period);
-            if (ph < 0) ph += 2LL * a.period;
-            sph[t] = stand ? -1 : (int)ph;
+            sph[t] = stand ? -1 : gait_phase0(a.stamp[b0 + t], a.dt, a.period);
         }
         __syncthreads();
-        auto flags = [&](int r, int k, bool& cl, bool& cr) {
-            const int p0 = sph[r];
-            const int ph = (p0 + k) % (2 * a.period);
-            const bool stand = p0 < 0, left_stance = ph < a.period, dsup = (ph % a.period) < a.ds;
-            cl = stand || left_stance || dsup; cr = stand || !left_stance || dsup;
-        };
+        auto flags = [&](int r, int k, bool& cl, bool& cr) { gait_flags(sph[r], k, a.period, a.ds, cl, cr); };
         double* xr = a.x_ref + b0 * (N * 13);
         for (int e = t; e < nr * N * 13; e += 256) {                     // x_ref[r][k][c], reference index k + 1
             const int row = e / 13, c = e - 13 * row, r = row / N, k = row - N * r;

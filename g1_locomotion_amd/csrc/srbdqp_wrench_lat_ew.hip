@@ -9,6 +9,7 @@
 #include "srbdqp_common.hpp"
 #include "srbdqp_wrench.hpp"
 #include "srbdqp_wrench_lat_ew.hpp"
+#include "srbdqp_fleet.hpp"
 
 namespace srbdqp {
 namespace {
@@ -70,6 +71,15 @@ hipError_t launch_wrench_cn_lat(int N, bool set_attr, const KArgs& a, const void
     if (N == 8) return launch_cn_t<8>(set_attr, a, in, cn_host, cn_dev, st);
     if (N == 10) return launch_cn_t<10>(set_attr, a, in, cn_host, cn_dev, st);
     return hipErrorInvalidValue;
+}
+
+// The fleet's plant step (srbdqp_fleet.hpp) is instantiated here too, behind the low-latency kernels, for their reason: srbdqp.hip's code object stays what it
+// was, and the library keeps its two code objects (tests/test_staged_wrench_cpu.py, tests/test_staged_normals_cpu.py count them).
+hipError_t launch_fleet_advance(const FleetArgs& a, hipStream_t st) {
+    const long long tiles = (a.B + kFleetTile - 1) / kFleetTile;   // one tile of 64 robots per workgroup pass
+    const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
+    hipLaunchKernelGGL(srbdqp_fleet_advance_kernel<kFleetTile>, grid, dim3(kFleetTile), 0, st, a);
+    return hipGetLastError();
 }
 
 }  // namespace srbdqp

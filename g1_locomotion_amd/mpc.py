@@ -485,6 +485,81 @@ class BatchMPC(_Engine):
                                                     v(x_ref), v(foot), v(contact), v(pcom), v(landing), v(stream))
         self._check(rc)
 
+    # -- from step t to step t + 1: the fleet's plant step and the K-step loop (include/srbdqp_cascade.h) --------
+    def fleet_settings(self, com_target=(0.0, 0.0, 0.0), substeps=10, foot_half_length=0.085, z_min=0.3, tilt_max=1.0, period_steps=6,
+                       double_support_steps=1, hip_offset_y=0.0645):
+        """srbdqp_fleet_settings for fleet_advance() / rollout(): the plant's substeps, the touchdown's heel / toe spacing, the fallen thresholds and the gait
+        (mpc_inputs()' schedule; com_target matters to the roll-out alone)."""
+        s = _lib.FleetSettings()
+        s.struct_size = C.sizeof(_lib.FleetSettings)
+        s.substeps = int(substeps)
+        s.foot_half_length, s.z_min, s.tilt_max = float(foot_half_length), float(z_min), float(tilt_max)
+        s.gait = self._gait_struct(period_steps, double_support_steps, com_target, hip_offset_y)
+        return s
+
+    def fleet_advance(self, x, feet, stamp, u0, landing, standing=None, push=None, alive=None, **settings):
+        """One control period of B robots between two solves (srbdqp_fleet_advance_f64): the nonlinear SRBD plant under the first-step forces u0 (B,12) at
+        the contact points feet (B,12) or (B,4,3), the gait clock, the touchdown of the foot that lands around landing (B,3) (mpc_inputs()' output), the
+        robots that fell.  standing (B,) flags, push (B,6) world wrench on the body during the period (torque first; the MPC does not know it), alive (B,)
+        flags: each or None.  settings: fleet_settings()' keywords.  The inputs are not modified.
+        Returns dict(x (B,13), feet (B,12), stamp (B,), alive (B,) uint8)."""
+        x = np.array(x, dtype=np.float64).reshape(-1, NX)
+        B = x.shape[0]
+        f = np.array(feet, dtype=np.float64).reshape(B, NU)
+        t = np.array(stamp, dtype=np.float64).reshape(B)
+        u = _as(u0, np.float64, (B, NU), "u0")
+        lp = _as(landing, np.float64, (B, 3), "landing")
+        sd = None if standing is None else _as(np.asarray(standing) != 0, np.uint8, (B,), "standing")
+        pu = None if push is None else _as(push, np.float64, (B, 6), "push")
+        al = np.ones(B, np.uint8) if alive is None else np.array(np.asarray(alive) != 0, dtype=np.uint8).reshape(B)
+        s = self.fleet_settings(**settings)
+        rc = self._lib.srbdqp_fleet_advance_f64(self._h, B, _p(x), _p(f), _p(t), _p(u), NU, _p(lp), _p(sd), _p(pu), _p(al), C.byref(s))
+        self._check(rc)
+        return dict(x=x, feet=f, stamp=t, alive=al)
+
+    def fleet_advance_device(self, B, x, feet, stamp, u0, landing, u0_stride=NU, standing=0, push=0, alive=0, stream=0, **settings):
+        """Device-pointer form of fleet_advance(): raw addresses, x / feet / stamp / alive updated in place, launch enqueued behind `stream`, returns at once.
+        u0_stride (doubles between the forces of consecutive robots): 12 N reads u_out[b][0] of a solve_device() in place."""
+        v = lambda q: C.c_void_p(int(q)) if q else None
+        s = self.fleet_settings(**settings)
+        rc = self._lib.srbdqp_fleet_advance_device_f64(self._h, int(B), v(x), v(feet), v(stamp), v(u0), int(u0_stride), v(landing), v(standing), v(push),
+                                                       v(alive), C.byref(s), v(stream))
+        self._check(rc)
+
+    def rollout(self, x0, feet, stamp, v_ref, steps, com_target, standing=None, push=None, alive=None, **settings):
+        """`steps` control steps of B robots on the device (srbdqp_fleet_rollout_f64): per step mpc_inputs -> the solve -> fleet_advance, without a host
+        round trip in between.  x0 (B,13), feet (B,12) or (B,4,3), stamp (B,), v_ref (B,2) and standing (B,) flags or None (both constant over the call),
+        push (steps,B,6) world wrenches or None, alive (B,) flags or None.  settings: fleet_settings()' keywords.  Robot records and weights set on the
+        engine are honoured; an external wrench or contact normals set on it raise SrbdqpError.  A second call from the returned x, feet, stamp and alive
+        continues the first one bit for bit.
+        Returns dict(x (steps+1,B,13), u0 (steps,B,12), feet (steps+1,B,12), status (steps,B), iters (steps,B), alive (B,) uint8, stamp (B,))."""
+        x = np.array(x0, dtype=np.float64).reshape(-1, NX)
+        B, T = x.shape[0], int(steps)
+        f = np.array(feet, dtype=np.float64).reshape(B, NU)
+        t = np.array(stamp, dtype=np.float64).reshape(B)
+        v = _as(v_ref, np.float64, (B, 2), "v_ref")
+        sd = None if standing is None else _as(np.asarray(standing) != 0, np.uint8, (B,), "standing")
+        pu = None if push is None else _as(push, np.float64, (max(T, 0), B, 6), "push")
+        al = np.ones(B, np.uint8) if alive is None else np.array(np.asarray(alive) != 0, dtype=np.uint8).reshape(B)
+        s = self.fleet_settings(com_target, **settings)
+        n = max(T, 0)
+        xl, ul, fl = np.empty((n + 1, B, NX)), np.empty((n, B, NU)), np.empty((n + 1, B, NU))
+        sl, il = np.empty((n, B), np.int32), np.empty((n, B), np.int32)
+        rc = self._lib.srbdqp_fleet_rollout_f64(self._h, B, T, _p(x), _p(f), _p(t), _p(v), _p(sd), _p(pu), C.byref(s), _p(al), _p(xl), _p(ul), _p(fl),
+                                                _p(sl), _p(il))
+        self._check(rc)
+        return dict(x=xl, u0=ul, feet=fl, status=sl, iters=il, alive=al, stamp=t)
+
+    def rollout_device(self, B, steps, x, feet, stamp, v_ref, com_target, standing=0, push=0, alive=0, x_log=0, u0_log=0, feet_log=0, status_log=0,
+                       iters_log=0, stream=0, **settings):
+        """Device-pointer form of rollout(): raw addresses (0 = absent), x / feet / stamp / alive updated in place, every launch enqueued behind `stream`
+        (0 = the engine's own), returns at once without synchronising.  Logs as in include/srbdqp_cascade.h."""
+        v = lambda q: C.c_void_p(int(q)) if q else None
+        s = self.fleet_settings(com_target, **settings)
+        rc = self._lib.srbdqp_fleet_rollout_device_f64(self._h, int(B), int(steps), v(x), v(feet), v(stamp), v(v_ref), v(standing), v(push), C.byref(s),
+                                                       v(alive), v(x_log), v(u0_log), v(feet_log), v(status_log), v(iters_log), v(stream))
+        self._check(rc)
+
     def last_kernel_ms(self) -> float:
         return float(self._lib.srbdqp_last_kernel_ms(self._h))
 

@@ -76,6 +76,65 @@ int srbdqp_mpc_inputs_device_f64(srbdqp_handle* h, int64_t B, const double* x0, 
                                  const double* v_ref, const uint8_t* standing, const srbdqp_gait* gait,
                                  double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, void* stream);
 
+/* ---- from control step t to step t + 1: a fleet's roll-out on the device.
+ *
+ * srbdqp_fleet_advance_* is one control period of B robots between two solves, in this order:
+ *   1. skip       a robot with alive == 0, or with a non-finite entry in x, gets alive = 0 and nothing else written (its stamp still advances);
+ *   2. plant      `substeps` RK4 steps of h = dt / substeps of the nonlinear single rigid body: Euler-rate kinematics, I_w = R I_b R' with
+ *                 R = Rz(yaw) Ry(pitch) Rx(roll), the gyroscopic term omega x I_w omega, the forces u0 at the contact points `feet` held fixed in the
+ *                 world, v' = sum f / m + f_push / m + g e_z with g = x[12], the push's torque added to sum r x f;
+ *   3. stamp      stamp' = stamp + dt (one rounded addition);
+ *   4. touchdown  the left foot (contacts 0, 1) or the right foot (contacts 2, 3) whose first-step flag under the gait is 0 at stamp and 1 at stamp'
+ *                 moves: heel = landing - (foot_half_length, 0, 0), toe = landing + (foot_half_length, 0, 0), z as in landing (the ground plane).
+ *                 The gait is the schedule of srbdqp_mpc_inputs_*: step index floor(stamp / dt + 1e-9), gait.period_steps,
+ *                 gait.double_support_steps, standing.  Every other foot stays;
+ *   5. fallen     a new CoM height below z_min, |roll| or |pitch| above tilt_max, or a non-finite state: alive = 0.  The state of this period is still
+ *                 written; the robot holds from the next period on.  A robot handed over with such a height or tilt has fallen already: it gets
+ *                 this period like any other and alive = 0 behind it, wherever the period took it.
+ * dt, and mass and inertia where the handle has no robot records (srbdqp_set_robots: robot b's own, as srbdqp_wbid_reference_* reads them): the handle's
+ * config.  The MPC does not know the push. */
+typedef struct srbdqp_fleet_settings {
+    int32_t struct_size;          /* = sizeof(srbdqp_fleet_settings) */
+    int32_t substeps;             /* RK4 steps per control period (10) */
+    double foot_half_length;      /* heel and toe lie this far behind and ahead of the landing point (0.085: synth.py's spacing) */
+    double z_min;                 /* fallen: CoM height below it (0.3) */
+    double tilt_max;              /* fallen: |roll| or |pitch| above it, rad (1.0: keeps the Euler angles away from their singularity) */
+    srbdqp_gait gait;             /* the schedule, as srbdqp_mpc_inputs_* takes it */
+} srbdqp_fleet_settings;
+
+/* The defaults above into *s; s->struct_size says how large the caller's struct is (checked before anything is written).  gait: period_steps 6,
+ * double_support_steps 1, hip_offset_y 0.0645, com_target (0, 0, 0) -- the caller's to fill. */
+int srbdqp_fleet_default_settings(srbdqp_fleet_settings* s);
+
+/* x [B][13], feet [B][12], stamp [B]: in/out.  u0: the first-step forces, robot b's twelve doubles at u0 + b * u0_stride (u0_stride >= 12, in doubles:
+ * 12 N reads u_out[b][0] of a solve in place).  landing [B][3] as srbdqp_mpc_inputs_* wrote it.  standing [B], push [B][6] (world wrench on the body during
+ * this period, torque about the CoM first as in srbdqp_set_external_wrench), alive [B] (in/out): each may be NULL. */
+int srbdqp_fleet_advance_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
+                             const double* landing, const uint8_t* standing, const double* push, uint8_t* alive,
+                             const srbdqp_fleet_settings* cfg);
+int srbdqp_fleet_advance_device_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
+                                    const double* landing, const uint8_t* standing, const double* push, uint8_t* alive,
+                                    const srbdqp_fleet_settings* cfg, void* stream);
+
+/* T control steps of B robots: for t = 0 ... T - 1, srbdqp_mpc_inputs_device_f64 -> the solve, exactly the launches srbdqp_solve_batch_device_f64 makes
+ * for this handle, with pcom from the inputs -> srbdqp_fleet_advance_device_f64, enqueued on `stream` without a host synchronisation (plain launches: no
+ * graph, no persistent kernel).  On a SRBDQP_FLAG_DEFER_TAIL handle srbdqp_flush follows every solve: the plant needs complete forces.
+ *   x [B][13], feet [B][12], stamp [B], alive [B] (may be NULL): in/out.  v_ref [B][2], standing [B] (may be NULL): constant over the call.
+ *   push [T][B][6] or NULL.  Logs, each may be NULL: x_log [T+1][B][13] and feet_log [T+1][B][12] (entry 0: as passed in; t + 1: behind period t),
+ *   u0_log [T][B][12] (the forces period t ran under), status_log, iters_log [T][B] (of the solve of step t).
+ * Robot records and weights set on the handle are honoured (the solves read them; the plant reads mass and inertia).  A handle with an external wrench or
+ * contact normals set is refused (SRBDQP_E_INVALID): the plant is flat ground and the MPC's wrench is not the plant's.  The horizon buffers (x_ref, foot,
+ * contact, pcom, landing, u, x_out, status, iters for B robots) belong to the handle: allocated at the first roll-out, grown when a larger B asks,
+ * released by srbdqp_destroy.  Nothing is set or cleared on the handle.  B or T < 1, a bad struct_size, substeps < 1, a setting that is not finite or
+ * not positive, an invalid gait: SRBDQP_E_INVALID before any launch. */
+int srbdqp_fleet_rollout_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
+                                    const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                    double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log, void* stream);
+/* ... through host buffers: returns with the results in place. */
+int srbdqp_fleet_rollout_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
+                             const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                             double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,122 @@
+"""Throughput of the fleet roll-out (include/srbdqp_cascade.h srbdqp_fleet_rollout_device_f64): B = 4096 walking robots, N = 10, T = 100.
+
+  * robot-steps/s of ONE roll-out call (T steps enqueued without a host synchronisation);
+  * the same T steps driven from Python through the three public device calls with a synchronise after every step (what a user had to write before);
+  * the plant step alone (srbdqp_fleet_advance_device_f64): time per launch, its share of a step of the roll-out, and its GB/s beside the 4.4 TB/s DESIGN.md
+    section 8 quotes for mpc_inputs (it integrates 40 derivative evaluations per robot: it is not expected to sit at the HBM roof).
+
+    python tools/fleet_rollout_bench.py [--robots 4096] [--steps 100] [--reps 5] [--out profiles/<name>.json]
+"""
+import argparse
+import hashlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FEET = np.array([[0.0, 0.0645, 0.0], [0.17, 0.0645, 0.0], [0.0, -0.0645, 0.0], [0.17, -0.0645, 0.0]])
+COM = np.array([0.085, 0.0, 0.598])
+# bytes the plant step must move per robot: x, feet, u0, landing, stamp, push in; x, stamp out (a foothold is stored at a touchdown only: one period in six)
+ADVANCE_BYTES = (13 + 12 + 12 + 3 + 1 + 6 + 13 + 1) * 8
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--robots", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    import torch
+    from g1_locomotion_amd import BatchMPC, _lib
+    B, T, N, dt = a.robots, a.steps, 10, 0.04
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+    x0 = np.zeros((B, 13)); x0[:, 3:6] = COM + rng.normal(size=(B, 3)) * 0.003; x0[:, 12] = -9.80665
+    feet0 = np.tile(FEET.reshape(12), (B, 1))
+    stamp0 = dt * rng.integers(0, 12, B).astype(np.float64)
+    v_ref = rng.uniform(-1.0, 1.0, (B, 2)) * np.array([0.3, 0.1])
+    push = np.where(rng.random((T, B, 1)) < 0.05, rng.uniform(-1.0, 1.0, (T, B, 6)) * np.array([2.0, 2.0, 0.0, 30.0, 30.0, 10.0]), 0.0)
+    up = lambda arr: torch.from_numpy(np.ascontiguousarray(arr)).to(dev)
+    d_v, d_pu = up(v_ref), up(push)
+    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)
+    xl, ul, fl = f64(T + 1, B, 13), f64(T, B, 12), f64(T + 1, B, 12)
+    sl, il = torch.empty((T, B), dtype=torch.int32, device=dev), torch.empty((T, B), dtype=torch.int32, device=dev)
+    xr, fo, pc, lp, u, xo = f64(B, N, 13), f64(B, N, 12), f64(B, N, 3), f64(B, 3), f64(B, N, 12), f64(B, N + 1, 13)
+    ct = torch.empty((B, N, 4), dtype=torch.uint8, device=dev)
+    st, it = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+    res = dict(robots=B, steps=T, horizon=N, reps=a.reps)
+    with BatchMPC(horizon=N, dt=dt) as eng:
+        def fresh():
+            return up(x0), up(feet0), up(stamp0), torch.ones(B, dtype=torch.uint8, device=dev)
+
+        def call():
+            x, feet, stamp, al = fresh()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.rollout_device(B, T, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), d_v.data_ptr(), COM, push=d_pu.data_ptr(), alive=al.data_ptr(),
+                               x_log=xl.data_ptr(), u0_log=ul.data_ptr(), feet_log=fl.data_ptr(), status_log=sl.data_ptr(), iters_log=il.data_ptr())
+            t1 = time.perf_counter()
+            eng.synchronize()
+            return time.perf_counter() - t0, t1 - t0, al
+
+        def loop():
+            x, feet, stamp, al = fresh()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for k in range(T):
+                eng.mpc_inputs_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), d_v.data_ptr(), COM, xr.data_ptr(), fo.data_ptr(), ct.data_ptr(),
+                                      pc.data_ptr(), landing=lp.data_ptr())
+                eng.solve_device(B, x.data_ptr(), xr.data_ptr(), fo.data_ptr(), ct.data_ptr(), u.data_ptr(), x_out=xo.data_ptr(), status=st.data_ptr(),
+                                 iters=it.data_ptr(), pcom=pc.data_ptr())
+                eng.fleet_advance_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), u.data_ptr(), lp.data_ptr(), u0_stride=12 * N,
+                                         push=d_pu[k].data_ptr(), alive=al.data_ptr())
+                eng.synchronize()
+            return time.perf_counter() - t0
+
+        def advance_alone():
+            x, feet, stamp, al = fresh()
+            u.zero_(); u[:, 0, 2::3] = 85.0                               # the robot's weight on four contacts: it stays where it is
+            lp.zero_()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for k in range(T):
+                eng.fleet_advance_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), u.data_ptr(), lp.data_ptr(), u0_stride=12 * N,
+                                         push=d_pu[k].data_ptr(), alive=al.data_ptr())
+            eng.synchronize()
+            return (time.perf_counter() - t0) / T
+
+        call(); loop(); advance_alone()                                   # warm-up: buffers, code objects
+        calls = [call() for _ in range(a.reps)]
+        t_call = float(np.median([c[0] for c in calls]))
+        res["kernel"] = eng.kernel_name()
+        res["rollout_call_s"] = t_call
+        res["rollout_enqueue_s"] = float(np.median([c[1] for c in calls]))
+        res["rollout_robot_steps_per_s"] = B * T / t_call
+        t_loop = float(np.median([loop() for _ in range(a.reps)]))
+        res["python_loop_s"] = t_loop
+        res["python_loop_robot_steps_per_s"] = B * T / t_loop
+        t_adv = float(np.median([advance_alone() for _ in range(a.reps)]))
+        res["advance_us_per_launch"] = t_adv * 1e6
+        res["advance_share_of_a_rollout_step"] = t_adv / (t_call / T)
+        res["advance_gb_per_s"] = B * ADVANCE_BYTES / t_adv / 1e9
+        res["advance_bytes_per_robot"] = ADVANCE_BYTES
+        res["mpc_inputs_gb_per_s_design_8"] = 4400.0
+        res["alive_share"] = float(calls[-1][2].float().mean().item())
+        res["solved_share"] = float((sl == 1).float().mean().item())
+        res["mean_iters"] = float(il.float().mean().item())
+    res["library_sha256"] = hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
