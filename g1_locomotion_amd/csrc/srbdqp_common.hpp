@@ -489,6 +489,13 @@ __device__ __forceinline__ double lane_bcast(double v, int l) {
     return __hiloint2double(hi, lo);
 }
 
+// value of the lane before this one in its 16-lane DPP row (row_shr:1, two DPP moves); the first lane of a row reads +0.0
+__device__ __forceinline__ double row_prev(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x111, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x111, 0xF, 0xF, true);
+    return __hiloint2double(hi, lo);
+}
+
 // block-wide max of up to NV values per thread; result broadcast to all threads.  2 barriers.
 template <int NV>
 __device__ __forceinline__ void block_max(double (&v)[NV], double* red) {

@@ -311,18 +311,29 @@ __device__ __forceinline__ void pk_rows(double (&X)[16], double nu, double y) {
 #undef SRBDQP_PK_LO6
 #undef SRBDQP_PK_LO7
 #undef SRBDQP_PK
-template <int I>
-struct PkLoad {
-    static __device__ __forceinline__ void run(double (&X)[16], const double* colp, int one_hi) {
-        if constexpr (I < 16) {
-            const double t = colp[I * 16];
-            const int lo = __builtin_amdgcn_update_dpp(__double2loint(t), 0, 0xE4, 0xA, 0xF, false);
-            const int hi = __builtin_amdgcn_update_dpp(__double2hiint(t), one_hi, I == 0 ? 0xE4 : 0x110 + I, 0xA, 0xF, true);
-            X[I] = __hiloint2double(hi, lo);
-            PkLoad<I + 1>::run(X, colp, one_hi);
-        }
-    }
+// The wave-private LDS of the packed inversion, in doubles from its base: three tiles, every access of which is ONE lane base plus immediate offsets.
+//   [0, 256)          S, row-major, rows 16 apart: stored from C layout (lane l, register r: l + 64 r), read back a row per register.
+//   [0, 271)          W = L^-1 in its place once S is in registers: row i at wrow(i) = 17 i.  With immediate offsets the compiler pairs the accesses of a lane into
+//                     ds_read2_b64 / ds_write2_b64, which the LDS serves in groups of 16 consecutive lanes over 32 banks (16 doubles): the store of row i and the
+//                     C-layout read of rows g + 4 q (68 q behind the lane base 17 g + col) are the 16 lanes of one DPP row on 16 consecutive doubles, and the
+//                     A-operand read of lane (k', i) at 17 i + k' + 4 r has the lanes i = 0 .. 15 of a group on 17 i mod 16 = i: all three free of conflicts.
+//                     (Unpaired, as ds_read_b64 -- two 32-lane halves over 64 banks -- stride 17 has one two-way collision in each of the two reads, stride 18 two
+//                     in the second; stride 16 + 2 per row PAIR is free of conflicts there, and two-way in the paired A-operand read that is actually emitted:
+//                     measured, SQ_LDS_BANK_CONFLICT + 48 cycles a pass.  profiles/r23_wave_setup_diet.txt.)  (Until round 22: rows 16 apart with the column
+//                     XOR-swizzled, tile[i * 16 + (col ^ i)] -- sixteen store and eight read addresses formed in registers per tile.)
+//   [kIdent, +256)    the 16 x 16 identity, row-major, rows 16 apart: written once per pass (pk_ident_store), read by the odd DPP rows beside the even rows' S --
+//                     kIdent = 16 (mod 32), so that also unpaired reads, in which a DPP row's S shares a 32-lane half with the next row's identity, sit 32 banks apart.
+struct PkTile {
+    static constexpr int kIdent = 272;
+    static constexpr int kDoubles = kIdent + 256;
+    static constexpr __host__ __device__ int wrow(int row) { return 17 * row; }
 };
+// lane (g, col) stores its four entries of the identity, (g + 4 r, col): the C-layout store of the S tile
+__device__ __forceinline__ void pk_ident_store(double* tile, int lane) {
+    const int col = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) tile[PkTile::kIdent + lane + 64 * r] = (g + 4 * r == col) ? 1.0 : 0.0;
+}
 template <int K>
 __device__ __forceinline__ void diag16_pivot_packed(double (&X)[16], unsigned& worst) {
     const double sk = pk_even_rows(X[K]);         // row k of S in every DPP row
@@ -345,34 +356,34 @@ __device__ __forceinline__ void diag16_pivot_packed(double (&X)[16], unsigned& w
         X[K] = y;
     }
 }
-// tile: 256 doubles of LDS owned by this wave.  In: S in C layout.  On return the tile holds W = L^-1 row-major with the column XOR-swizzled
-// (tile[row * 16 + (col ^ row)]), exact zeros above the diagonal -- the form a_operand (srbdqp_setup1.hpp) leaves there, so the A operand of W is read straight from
-// it --; the return value is the same W in C layout.
+// tile: PkTile::kDoubles doubles of LDS owned by this wave, the identity in place (pk_ident_store).  In: S in C layout.  On return the tile holds W = L^-1 with
+// row i at PkTile::wrow(i), exact zeros above the diagonal -- the A operand of W is read straight from it (a_operand_read, srbdqp_setup1.hpp) --; the return value
+// is the same W in C layout.
 __device__ __forceinline__ v4d diag16_invert_dpp_packed(v4d s, int lane, bool& ok, double* tile) {
     const int col = lane & 15, g = lane >> 4;
     asm volatile("" ::: "memory");
 #pragma unroll
-    for (int r = 0; r < 4; ++r) tile[(g + 4 * r) * 16 + col] = s[r];
+    for (int r = 0; r < 4; ++r) tile[lane + 64 * r] = s[r];
     asm volatile("" ::: "memory");
-    // every lane reads row i of S (of the upper triangle; below the diagonal the lanes carry values nobody reads); the odd rows then take the identity, two DPP
-    // moves with row_mask 0xa a register: the low word 0, the high word that of 1.0 shifted from lane 0 of the row to lane i (bound_ctrl: 0 to the lanes left of it)
-    const int one_hi = (col == 0) ? 0x3ff00000 : 0;
+    // register i: row i of S on the even DPP rows (of the upper triangle; below the diagonal the lanes carry values nobody reads), row i of the identity on the odd
+    // ones -- sixteen reads off one lane base.  (Until round 22 every lane read S and the odd rows took the identity through two DPP moves a register.)
+    const double* rowp = tile + col + ((g & 1) ? PkTile::kIdent : 0);
     double X[16];
-    PkLoad<0>::run(X, tile + col, one_hi);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) X[i] = rowp[i * 16];
     asm volatile("" ::: "memory");
     unsigned worst = 0u;
     diag16_pivot_packed<0>(X, worst);
     ok = worst < 0x7fefffffu;                     // (zero, negative, NaN and infinite pivots fail, and subnormal ones with a zero high word)
-    int colw = col;
-    asm("" : "+v"(colw) : "v"(X[15]));            // (the sixteen swizzled addresses are formed behind the elimination, not held in registers through it)
     if (g == 1) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) tile[i * 16 + (colw ^ i)] = X[i];
+        for (int i = 0; i < 16; ++i) tile[PkTile::wrow(i) + col] = X[i];
     }
     asm volatile("" ::: "memory");
+    const double* cp = tile + lane + g;                 // wrow(g) + col = 17 g + col; row g + 4 q is wrow(4) q behind it
     v4d w;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) { const int row = g + 4 * q; w[q] = tile[row * 16 + (col ^ row)]; }
+    for (int q = 0; q < 4; ++q) w[q] = cp[PkTile::wrow(4) * q];
     asm volatile("" ::: "memory");
     return w;
 }

@@ -6,7 +6,7 @@
 // closed form (srbdqp_compact.hpp) nothing needs 256 threads: here the 10 upper 16x16 tiles of K are 80 registers of one
 // wave in MFMA C layout and the whole factorisation stays in that wave's registers --
 //   F  right-looking Cholesky K = U'U: diagonal tile inverted by the packed DPP elimination (diag16_invert_dpp_packed: no matrix-core
-//      instruction, no v_readlane), panel U_jb = L_jj^-1 K_jb (the A operand L_jj^-1 is read from the 2 KB wave-private LDS tile the inversion leaves it in),
+//      instruction, no v_readlane), panel U_jb = L_jj^-1 K_jb (the A operand L_jj^-1 is read from the wave-private LDS tile the inversion leaves it in: PkTile, srbdqp_mfma.hpp),
 //      trailing update K_ab -= U_ja' U_jb with both operands straight from registers (register r of a C-layout tile is
 //      the A operand of K-step r of a product that contracts over the tile's row index, and the B operand as well); on the way out of block row j
 //      P_j = W_jj' W_jj (W_jj = L_jj^-1) takes the slot of the diagonal tile and -V_lj = -U_jl' W_jj the slot of U_jl, both such products;
@@ -31,8 +31,8 @@ namespace srbdqp {
 #endif
 
 // LDS of one wave: [0, S::o_R) the persistent strip with the offsets of CompactSmem (the ADMM kernel reads it back from
-// the workspace), then the phase-A arrays with their lifetimes shared: inputs -> error vector / warm-start vectors ->
-// the transpose tile of the factorisation.
+// the workspace), then the phase-A arrays with their lifetimes shared: inputs, prefix sums and tables -> error vector / warm-start vectors -> the table rows of
+// the K assembly -> the tiles of the packed inversion (over the prefix sums and tables) -> the K^-1 staging tiles.
 template <int N, int MAXS>
 struct Setup1Smem {
     using S = CompactSmem<N, MAXS>;
@@ -48,20 +48,24 @@ struct Setup1Smem {
     static constexpr int o_x0c = o_t1;
     static constexpr int o_tf = o_x0c + up2(S::nmax) + 16;
     static constexpr int endT = (o_t2 + up2(9 * N) > o_tf + 6 * N) ? o_t2 + up2(9 * N) : o_tf + 6 * N;
-    static constexpr int o_xref = up2(endT);               // 13N  inputs          | later: the 16 x 16 transpose tile
+    static constexpr int o_xref = up2(endT);               // 13N  inputs
     static constexpr int o_foot = o_xref + up2(N * 13);    // 12N                  | later: eh (n), then G x^0 (n)
     static constexpr int o_pcom = o_foot + N * 12;         // 3N
     static constexpr int o_eh = o_foot;
     static constexpr int o_gx = o_foot;
-    static constexpr int o_scr = o_xref;
+    // the tiles of the packed inversion (PkTile, srbdqp_mfma.hpp: S / W and the constant identity, 4.1 KB) during the factorisation, when nothing behind the strip
+    // is alive: over the prefix sums and tables, which are dead with the K assembly, and under the K^-1 staging, which begins behind the factorisation.  (Until
+    // round 22 one 2 KB tile over the inputs.)  No instantiation that ships grows by it: N = 10, MAXS = 2 stays at 16,672 bytes (18,208 with the parked (x, y)).
+    static constexpr int o_scr = o_cp;
     static constexpr int endIn = o_pcom + up2(N * 3);
-    static constexpr int endIn2 = (endIn > o_scr + 258) ? endIn : o_scr + 258;   // the tile + the spare slot of the K assembly
     static constexpr int kStgRow = 18;                    // row stride of the K^-1 staging tiles (16 + 2: the 16-byte row reads of 16 lanes hit 64 different banks)
     static constexpr int kStgTile = 16 * kStgRow;
-    static constexpr int endStg = (endIn2 > o_cp + S::NT * kStgTile) ? endIn2 : o_cp + S::NT * kStgTile;   // K^-1 block-column staging (wave kernel)
+    static constexpr int endStg = (endIn > o_cp + S::NT * kStgTile) ? endIn : o_cp + S::NT * kStgTile;   // K^-1 block-column staging (wave kernel)
     static constexpr int endAb = o_ab + 16 * S::NT * kAbStride;
-    static constexpr int o_end = endStg > endAb ? endStg : endAb;
+    static constexpr int endPk = o_scr + PkTile::kDoubles;
+    static constexpr int o_end = (endStg > endAb ? endStg : endAb) > endPk ? (endStg > endAb ? endStg : endAb) : endPk;
     static constexpr size_t bytes = (size_t)o_end * sizeof(double);
+    static constexpr size_t kCuShareBytes = 20480;        // an eighth of the CU's 160 KB: eight workgroups (two waves per SIMD) fit, the parked (x, y) of the restart kernels included
     // The step pairs (m, i >= m) of the T1 / T2 and G'v tables, a lane each (setup1_pass): pair p = r (N + 1) + c, r < N / 2, is (m, i) = (r, r + c) for c < N - r and
     // (N - 1 - r, N - 1 - r + c - (N - r)) behind that -- row r of the rectangle holds the N - r pairs of step r and the r + 1 pairs of step N - 1 - r --, so that
     // the pairs of one m are neighbours in ascending i, from slot pair_base(m) on, and a lane finds its (m, i) without a table.  Slots up to pair_base(m) + N - 1
@@ -73,6 +77,7 @@ struct Setup1Smem {
     static constexpr bool pairs_fit = N % 2 == 0 && kPairs <= 64 && 2 * kPairSlots <= 2 * up2(9 * N) && o_pq + 4 * kPairSlots <= o_end;   // (in LDS that is free while the tables are formed)
     static constexpr bool supported = SplitWs<N, MAXS>::supported && S::NT <= 4;
     static_assert(!supported || pairs_fit, "a lane and an LDS slot for every step pair of a horizon the one-wave kernel takes");
+    static_assert(!supported || bytes + 3 * 64 * sizeof(double) <= kCuShareBytes, "eight workgroups of the one-wave kernel per CU");
     static_assert(n + 6 * N <= o_end - o_eh || true, "");
 };
 
@@ -115,9 +120,9 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
 
     // ================= load + linearise (a5) =================
     // Round 6: on the whole wave, from registers, behind ONE barrier.  Every global load is issued first (each lane also fetches the foot / CoM operands of its
-    // own J entries and the x_ref entries of its own error-vector rows, so that neither goes through LDS); lane k < N forms cos / sin of yaw_k, the wave reads
-    // them back as uniform values (v_readlane) and C_k = sum_{l<=k} T_l -- only two of its nine entries are not constant: C_k = [[cc_k, cs_k, 0], [-cs_k, cc_k, 0],
-    // [0, 0, k + 1]] -- is summed in registers in the order of the serial loop it replaces.  (Until round 6: inputs -> LDS, three barriers, a 9-lane prefix loop
+    // own J entries and the x_ref entries of its own error-vector rows, so that neither goes through LDS); lane k < N forms cos / sin of yaw_k, the J loop reads
+    // them from lane k (a shuffle) and C_k = sum_{l<=k} T_l -- only two of its nine entries are not constant: C_k = [[cc_k, cs_k, 0], [-cs_k, cc_k, 0],
+    // [0, 0, k + 1]] -- is summed in registers, lane to lane, in the order of the serial loop it replaces (the chain below).  (Until round 6: inputs -> LDS, three barriers, a 9-lane prefix loop
     // of ten dependent LDS round trips and a J loop reading its operands back from LDS.)
     WSTAMP(a, b, 0);
     WSTAMP_RT(a, b, 12);
@@ -142,11 +147,11 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
 #pragma unroll
         for (int t = 0; t < JT; ++t) {
             const int tt = (lane + 64 * t < 12 * N) ? lane + 64 * t : 0;
-            const int k = tt / 12, ci = (tt % 12) / 3;
+            const int t3 = (int)((unsigned)tt / 3u), k = t3 >> 2;       // entry tt = 12 k + 3 ci + ax: the contact's three coordinates start at 3 (tt / 3)
             const double* pc = gpc ? gpc + k * 3 : gxr + k * 13 + 3;     // no CoM path: the CoM of x_ref
 #pragma unroll
-            for (int c = 0; c < 3; ++c) { v_f[t][c] = gft[k * 12 + 3 * ci + c]; v_p[t][c] = pc[c]; }
-            v_xr[t] = gxr[k * 13 + (tt - 12 * k)];
+            for (int c = 0; c < 3; ++c) { v_f[t][c] = gft[3 * t3 + c]; v_p[t][c] = pc[c]; }
+            v_xr[t] = gxr[tt + k];                                       // (k * 13 + tt - 12 k)
         }
         sincos(v_yaw, &ys, &yc);
         if (lane < 13) sm[S::o_x0 + lane] = v_x0;
@@ -175,7 +180,7 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
 #pragma unroll
         for (int t = 0; t < JT; ++t) {   // J_k[:, 3 ci + ax] = Iw^-1 * skew(r)[:, ax]
             const int tt = lane + 64 * t;
-            const int k = (tt < 12 * N ? tt : 0) / 12, cc = tt - 12 * k, ax = cc % 3;
+            const int tc = tt < 12 * N ? tt : 0, t3 = (int)((unsigned)tc / 3u), k = t3 >> 2, cc = tt - 12 * k, ax = tc - 3 * t3;   // (one division: tt / 12 = (tt / 3) / 4)
             const double cs = __shfl(yc, k), sn = __shfl(ys, k);    // (every lane takes part: the shuffles sit outside the store's condition)
             const double i0 = a.iinv[0], i1 = a.iinv[1], i2 = a.iinv[2];
             const double w00 = cs * cs * i0 + sn * sn * i1, w01 = cs * sn * (i0 - i1), w11 = sn * sn * i0 + cs * cs * i1;
@@ -194,15 +199,18 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
             }
         }
     }
-    // prefix sums C_k (cc_k = sum_{l<=k} cos yaw_l, cs_k = sum_{l<=k} sin yaw_l: the serial loop's order) on lane k, and from there to LDS: lane m < N sums the
-    // wave-uniform cos / sin of all N steps, the steps past m adding exact zeros.  (Until round 13 the prefix sums were ALSO kept as twenty wave-uniform doubles
-    // for the T1 / T2 loop of lane m; the step pairs below read C_i and C_m back from LDS instead.)
-    double ccm = 0.0, csm = 0.0;
+    // prefix sums C_k (cc_k = sum_{l<=k} cos yaw_l, cs_k = sum_{l<=k} sin yaw_l: the serial loop's order) on lane k, and from there to LDS: a chain over
+    // neighbouring lanes, acc = (acc of the lane before) + own term, N - 1 times behind acc = 0 + own term (row_prev: lanes 0 .. N - 1 sit in one 16-lane DPP row, and
+    // lane 0 reads +0.0 in every step).  Lane m is final after step m -- ((0 + c_0) + c_1) + ... + c_m, the loop's association, its +0 for c_0 = -0.0 included --
+    // and every later step forms the same value from the same operands again, so no step needs a select; lanes past N - 1 hold values nobody reads.  (Until round
+    // 22: lane m summed the wave-uniform cos / sin of all N steps, 2 N v_readlane pairs, the steps past m selected to exact zeros.  Until round 13 the prefix
+    // sums were ALSO kept as twenty wave-uniform doubles for the T1 / T2 loop of lane m; the step pairs below read C_i and C_m back from LDS instead.)
+    static_assert(N <= 16, "the prefix chain stays inside one 16-lane DPP row");
+    double ccm = 0.0 + yc, csm = 0.0 + ys;
 #pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const double c = lane_bcast(yc, k), s = lane_bcast(ys, k);
-        ccm += (k <= lane) ? c : 0.0;
-        csm += (k <= lane) ? s : 0.0;
+    for (int k = 1; k < N; ++k) {
+        ccm = row_prev(ccm) + yc;
+        csm = row_prev(csm) + ys;
     }
     if (lane < N) {
         double* C = sm + L1::o_cp + lane * 9;
@@ -426,7 +434,9 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
         typedef double d2 __attribute__((ext_vector_type(2)));
         const double dgxy = uni(a.rs2 + a.sigma + 2.0 * rho_b), dgz = uni(a.rs2 + a.sigma + (4.0 * a.mu * a.mu + a.rho_fz) * rho_b);
         // same axis <=> r = c (mod 3); r = 16 ta + kq + 4 q = ta + q + kq, c = 16 tb + mcol = tb + mcol (mod 3): per lane ONE residue decides, per entry a compile-time one
-        const int d3 = (mcol - kq + 3) % 3;
+        // (both residues as ONE unsigned division by 3 of a lane constant each; until round 22 a signed one here and one per tile column for the axis of dcol below)
+        const int d3 = (int)((unsigned)(mcol - kq + 3) % 3u);
+        const int m3 = (int)((unsigned)mcol % 3u);
         const double ind[3] = {d3 == 0 ? 1.0 : 0.0, d3 == 1 ? 1.0 : 0.0, d3 == 2 ? 1.0 : 0.0};
         double eqd[4];                                       // the lane's entry q of a diagonal tile is ON the diagonal
 #pragma unroll
@@ -438,7 +448,7 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
             const d2* row = reinterpret_cast<const d2*>(AB + kAbStride * c + 8);
 #pragma unroll
             for (int i = 0; i < 4; ++i) { const d2 v = row[i]; Bv[tb][2 * i] = v[0]; Bv[tb][2 * i + 1] = v[1]; }
-            dcol[tb] = (c < n_eff) ? (((tb + mcol) % 3 < 2) ? dgxy : dgz) : 1.0;       // (c mod 3 = the axis; padding -> identity)
+            dcol[tb] = (c < n_eff) ? ((m3 != (5 - tb % 3) % 3) ? dgxy : dgz) : 1.0;     // (c mod 3 = tb + mcol mod 3 = the axis, z where it is 2; padding -> identity)
         }
 #pragma unroll
         for (int ta = 0; ta < NT; ++ta) {
@@ -479,11 +489,14 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
     }
 
     // A-operand form of a C-layout tile X (operand[r] at lane (i, k') = X[i][4r + k']): read from the wave-private tile, where diag16_invert_dpp_packed leaves
-    // W_jj row-major with the column XOR-swizzled (the only operand that contracts over its COLUMN index since the W phase went: round 20)
+    // W_jj with row i at PkTile::wrow(i) (the only operand that contracts over its COLUMN index since the W phase went: round 20) -- one lane base, the four reads
+    // at immediate offsets.  The identity the inversions start from goes into its tile once, here.
     double* scr = sm + L1::o_scr;
+    pk_ident_store(scr, lane);
+    const double* const wop = scr + PkTile::wrow(mcol) + kq;
     auto a_operand_read = [&](double (&op)[4]) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) op[r] = scr[mcol * 16 + ((4 * r + kq) ^ mcol)];
+        for (int r = 0; r < 4; ++r) op[r] = wop[4 * r];
         asm volatile("" ::: "memory");
     };
     const v4d zero4 = (v4d){0.0, 0.0, 0.0, 0.0};

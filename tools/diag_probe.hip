@@ -12,7 +12,8 @@
 using namespace srbdqp;
 template <int VAR>
 __global__ __launch_bounds__(64, 2) void k(const double* A, double* W, long long* cyc, int reps) {
-    __shared__ __attribute__((aligned(16))) double tile[256];
+    __shared__ __attribute__((aligned(16))) double tile[PkTile::kDoubles];    // (diag16_invert_dpp uses the first 256; the packed form all three tiles of PkTile, srbdqp_mfma.hpp)
+    if constexpr (VAR == 2) pk_ident_store(tile, threadIdx.x);                // the identity the packed form starts from: once, as the kernel stores it once per pass
     const int lane = threadIdx.x, col = lane & 15, g = lane >> 4;
     v4d s;
     for (int r = 0; r < 4; ++r) s[r] = A[(g + 4 * r) * 16 + col];
@@ -33,7 +34,8 @@ __global__ __launch_bounds__(64, 2) void k(const double* A, double* W, long long
 // accuracy: workgroup t inverts tile t
 template <int VAR>
 __global__ __launch_bounds__(64, 2) void acc(const double* A, double* W, int* okout) {
-    __shared__ __attribute__((aligned(16))) double tile[256];
+    __shared__ __attribute__((aligned(16))) double tile[PkTile::kDoubles];    // (diag16_invert_dpp uses the first 256; the packed form all three tiles of PkTile, srbdqp_mfma.hpp)
+    if constexpr (VAR == 2) pk_ident_store(tile, threadIdx.x);                // the identity the packed form starts from: once, as the kernel stores it once per pass
     const int lane = threadIdx.x, col = lane & 15, g = lane >> 4;
     const double* At = A + 256 * blockIdx.x;
     v4d s;
