@@ -1,7 +1,10 @@
 """256 walking robots under random commands and random pushes for 100 control steps, in one call (BatchMPC.rollout):
 prints the share of the fleet still on its feet and how well it follows the commanded velocity.
 
-    python examples/fleet_rollout.py [--robots 256] [--steps 100] [--seed 0]
+    python examples/fleet_rollout.py [--robots 256] [--steps 100] [--seed 0] [--slope 0.2]
+
+--slope s: the same fleet on the plane z = s x (BatchMPC.set_terrain): the friction pyramids tilt with the ground, a foot lands on it,
+and "fallen" is the height over it.
 """
 import argparse
 import os
@@ -20,6 +23,7 @@ def main():
     ap.add_argument("--robots", type=int, default=256)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--slope", type=float, default=0.0)
     a = ap.parse_args()
     from g1_locomotion_amd import BatchMPC
     rng = np.random.default_rng(a.seed)
@@ -30,8 +34,16 @@ def main():
     v_ref = rng.uniform(-1.0, 1.0, (B, 2)) * np.array([0.3, 0.1])
     # a shove of one control period now and then: up to 40 N and 2 N m, on about one robot in twenty per step
     push = np.where(rng.random((T, B, 1)) < 0.05, rng.uniform(-1.0, 1.0, (T, B, 6)) * np.array([2.0, 2.0, 0.0, 40.0, 40.0, 10.0]), 0.0)
+    ground = lambda p: a.slope * p[..., 0]
     with BatchMPC(horizon=10, dt=dt) as eng:
+        if a.slope:
+            # a sampled plane: 41 x 41 nodes 0.5 m apart around the start (a robot that leaves the map walks on its clamped edge); everything stands on it
+            gx = -10.0 + 0.5 * np.arange(41)
+            eng.set_terrain(np.tile(a.slope * gx, (41, 1)), origin=(-10.0, -10.0), cell=0.5)
+            feet.reshape(B, 4, 3)[:, :, 2] = ground(feet.reshape(B, 4, 3))
+            x0[:, 5] += ground(x0[:, 3:5])
         r = eng.rollout(x0, feet, stamp, v_ref, T, COM, push=push)
+    r["x"][:, :, 5] -= ground(r["x"][:, :, 3:5])                         # heights below are over the ground
     alive = r["alive"] != 0
     half = T // 2                                                        # the mean velocity over the second half of the roll-out, robots still up
     v = (r["x"][-1, :, 3:5] - r["x"][half, :, 3:5]) / ((T - half) * dt)

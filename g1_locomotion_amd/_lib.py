@@ -47,6 +47,12 @@ class FleetSettings(C.Structure):
                 ("tilt_max", C.c_double), ("gait", Gait)]
 
 
+class Terrain(C.Structure):
+    """srbdqp_terrain (include/srbdqp_cascade.h): the grid of a height map."""
+    _fields_ = [("struct_size", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("reserved0", C.c_int32),
+                ("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double)]
+
+
 class Config(C.Structure):
     """struct srbdqp_config (include/srbdqp.h)."""
     _fields_ = [
@@ -237,6 +243,12 @@ SIGNATURES = {
     "srbdqp_fleet_advance_device_f64": (_int, _ADVANCE + [_vp]),
     "srbdqp_fleet_rollout_device_f64": (_int, _ROLLOUT + [_vp]),
     "srbdqp_fleet_rollout_f64": (_int, _ROLLOUT),
+    # ... over terrain: the height map, its sample, the normals and the height reference of a step
+    "srbdqp_set_terrain": (_int, [H, C.POINTER(Terrain), dp]),
+    "srbdqp_terrain_sample_f64": (_int, [H, _i64, dp, dp, dp]),
+    "srbdqp_terrain_sample_device_f64": (_int, [H, _i64, dp, dp, dp, _vp]),
+    "srbdqp_terrain_inputs_f64": (_int, [H, _i64, dp, dp, dp]),
+    "srbdqp_terrain_inputs_device_f64": (_int, [H, _i64, dp, dp, dp, _vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -158,7 +158,13 @@ struct srbdqp_handle {
         double *x_ref = nullptr, *foot = nullptr, *pcom = nullptr, *landing = nullptr, *u = nullptr, *x_out = nullptr;
         uint8_t* contact = nullptr;
         int32_t *status = nullptr, *iters = nullptr;
+        double* normals = nullptr;         // [B][N][12], carved only while a terrain is set: the contact normals of a terrain roll-out's solves (Call::cn_call)
     } fleet;
+    // the ground under the fleet (srbdqp_set_terrain, include/srbdqp_cascade.h): the library's device copy of the height map; map.h null: flat ground
+    struct Terrain {
+        srbdqp::TerrainMap map{};
+        double* own = nullptr; size_t cap = 0;
+    } terrain;
 };
 
 // slot of a launch stream (at most kMaxSlots distinct streams per handle; null when exhausted)
@@ -1693,6 +1699,7 @@ int srbdqp_destroy(srbdqp_handle* h) {
     if (h->done_count) (void)hipFree(h->done_count);
     h->robots.release(); h->weights.release(); h->normals.release(); h->ext.release();
     if (h->fleet.mem) (void)hipFree(h->fleet.mem);
+    if (h->terrain.own) (void)hipFree(h->terrain.own);
     if (h->stage_host) (void)hipHostFree(h->stage_host);
     if (h->stage_ew_host) (void)hipHostFree(h->stage_ew_host);
     if (h->stage_cn_host) (void)hipHostFree(h->stage_cn_host);
@@ -2848,8 +2855,9 @@ int fleet_advance_launch(srbdqp_handle* h, int64_t B, double* x, double* feet, d
     a.dt = h->cfg.dt; a.foot_half_length = cfg->foot_half_length; a.z_min = cfg->z_min; a.tilt_max = cfg->tilt_max;
     a.substeps = cfg->substeps; a.period = cfg->gait.period_steps; a.ds = cfg->gait.double_support_steps;
     a.B = (long long)B;
-    HIP_TRY(h, srbdqp::launch_fleet_advance(a, st));
-    h->kname = "fleet_advance_f64";
+    const srbdqp::TerrainMap* map = h->terrain.map.h ? &h->terrain.map : nullptr;   // a map set: the terrain instantiation over it
+    HIP_TRY(h, srbdqp::launch_fleet_advance(a, st, map));
+    h->kname = map ? "fleet_advance_terrain_f64" : "fleet_advance_f64";
     return SRBDQP_OK;
 }
 
@@ -2864,13 +2872,15 @@ int fleet_advance_check(srbdqp_handle* h, int64_t B, const void* x, const void* 
 // the horizon buffers of a roll-out, at B robots, carved from one allocation of the handle's
 int ensure_fleet_buffers(srbdqp_handle* h, size_t B) {
     auto& f = h->fleet;
-    if (f.mem && f.B >= B) return SRBDQP_OK;
+    const bool terrain = h->terrain.map.h != nullptr;
+    if (f.mem && f.B >= B && (!terrain || f.normals)) return SRBDQP_OK;
     const size_t N = (size_t)h->cfg.horizon;
     auto carve = [&](char* base) {
         Carver c(base);
         f.x_ref = c.take<double>(B * N * 13); f.foot = c.take<double>(B * N * 12); f.pcom = c.take<double>(B * N * 3); f.landing = c.take<double>(B * 3);
         f.u = c.take<double>(B * N * 12); f.x_out = c.take<double>(B * (N + 1) * 13); f.contact = c.take<uint8_t>(B * N * 4);
         f.status = c.take<int32_t>(B); f.iters = c.take<int32_t>(B);
+        f.normals = terrain ? c.take<double>(B * N * 12) : nullptr;
         return c.off;
     };
     const size_t want = carve(nullptr);
@@ -2892,6 +2902,12 @@ int fleet_rollout_check(srbdqp_handle* h, int64_t B, int32_t T, const void* x, c
     if (B < 1 || T < 1 || B > 0x7fffffffLL) { h->err = "srbdqp_fleet_rollout: B and T must be at least 1 (B at most 2^31 - 1)"; return SRBDQP_E_INVALID; }
     if (!x || !feet || !stamp || !v_ref) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
     if (const char* why = fleet_settings_fault(cfg)) { h->err = std::string("invalid srbdqp_fleet_settings: ") + why; return SRBDQP_E_INVALID; }
+    // on a terrain the solves read the normals of the call, and no instantiation reads those beside another side input, on a live horizon, with rank-aware steps
+    // or at N = 24: what the staged normals calls refuse, in the refusal table's words
+    if (h->terrain.map.h) {
+        if (const int rc = check_staged_normals(h, "srbdqp_fleet_rollout")) { h->err += " -- while a terrain is set (srbdqp_set_terrain)"; return rc; }
+        return SRBDQP_OK;
+    }
     // the plant is flat ground and knows no wrench but the push: a handle whose QPs are told otherwise would roll out against another robot
     if (h->ext.dev) { h->err = "srbdqp_fleet_rollout: the handle has an external wrench set (srbdqp_set_external_wrench): the plant does not know it -- clear it, and pass the roll-out its push"; return SRBDQP_E_INVALID; }
     if (h->normals.dev) { h->err = "srbdqp_fleet_rollout: the handle has contact normals set (srbdqp_set_contact_normals): the plant stands on flat ground -- clear them"; return SRBDQP_E_INVALID; }
@@ -2902,6 +2918,94 @@ int fleet_rollout_check(srbdqp_handle* h, int64_t B, int32_t T, const void* x, c
 }  // namespace
 
 extern "C" {
+
+// ---- the ground under the fleet (include/srbdqp_cascade.h; the sample and the kernels: srbdqp_terrain.hpp) ----
+int srbdqp_set_terrain(srbdqp_handle* h, const srbdqp_terrain* t, const double* heights) {
+    if (!h) return SRBDQP_E_INVALID;
+    auto& tr = h->terrain;
+    const bool clear = !t || !heights;
+    if (!clear) {
+        auto bad = [&](const std::string& why) { h->err = "srbdqp_set_terrain: " + why + "; the previous setting is kept"; return SRBDQP_E_INVALID; };
+        if (t->struct_size != (int32_t)sizeof(srbdqp_terrain)) return bad("struct_size is not sizeof(srbdqp_terrain)");
+        if (t->nx < 2 || t->ny < 2 || (long long)t->nx * (long long)t->ny > (1LL << 24)) return bad("nx and ny must be at least 2 and nx ny at most 2^24");
+        if (!std::isfinite(t->cell) || !(t->cell > 0.0)) return bad("cell must be finite and positive");
+        if (!std::isfinite(t->x0) || !std::isfinite(t->y0)) return bad("the origin (x0, y0) must be finite");
+        const size_t nx = (size_t)t->nx, ny = (size_t)t->ny;
+        const double step = 1.2 * t->cell;
+        auto node = [](size_t i, size_t j) { return "(" + std::to_string(i) + ", " + std::to_string(j) + ")"; };
+        for (size_t j = 0; j < ny; ++j)
+            for (size_t i = 0; i < nx; ++i)
+                if (!std::isfinite(heights[j * nx + i])) return bad("the height of node " + node(i, j) + " is not finite");
+        for (size_t j = 0; j < ny; ++j)
+            for (size_t i = 0; i < nx; ++i) {
+                const double v = heights[j * nx + i];
+                if (i + 1 < nx && std::fabs(heights[j * nx + i + 1] - v) > step) return bad("the heights of nodes " + node(i, j) + " and " + node(i + 1, j) + " differ by more than 1.2 cell (a normal would leave n_z >= 0.5)");
+                if (j + 1 < ny && std::fabs(heights[(j + 1) * nx + i] - v) > step) return bad("the heights of nodes " + node(i, j) + " and " + node(i, j + 1) + " differ by more than 1.2 cell (a normal would leave n_z >= 0.5)");
+            }
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (tr.map.h) {   // a launch on any stream may still read the map that is set
+        if (const int rc = quiesce_all_streams(h)) return rc;
+        HIP_TRY(h, hipDeviceSynchronize());
+    }
+    tr.map = srbdqp::TerrainMap{};
+    if (clear) return SRBDQP_OK;
+    const size_t count = (size_t)t->nx * (size_t)t->ny;
+    if (const int rc = grow(h, tr.own, tr.cap, count, nullptr, "hipMalloc terrain")) return rc;
+    HIP_TRY(h, hipMemcpy(tr.own, heights, count * sizeof(double), hipMemcpyHostToDevice));
+    tr.map.h = tr.own; tr.map.nx = t->nx; tr.map.ny = t->ny; tr.map.x0 = t->x0; tr.map.y0 = t->y0; tr.map.cell = t->cell;
+    return SRBDQP_OK;
+}
+
+int srbdqp_terrain_sample_device_f64(srbdqp_handle* h, int64_t M, const double* xy, double* z, double* normal, void* stream) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (!h->terrain.map.h) { h->err = "srbdqp_terrain_sample: no terrain is set (srbdqp_set_terrain)"; return SRBDQP_E_INVALID; }
+    if (M < 0 || (M > 0 && (!xy || !z))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (M == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    srbdqp::TerrainSampleArgs a{h->terrain.map, xy, z, normal, (long long)M};
+    HIP_TRY(h, srbdqp::launch_terrain_sample(a, stream ? reinterpret_cast<hipStream_t>(stream) : h->stream));
+    h->kname = "terrain_sample_f64";
+    return SRBDQP_OK;
+}
+
+int srbdqp_terrain_sample_f64(srbdqp_handle* h, int64_t M, const double* xy, double* z, double* normal) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (!h->terrain.map.h) { h->err = "srbdqp_terrain_sample: no terrain is set (srbdqp_set_terrain)"; return SRBDQP_E_INVALID; }
+    if (M < 0 || (M > 0 && (!xy || !z))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (M == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t m = (size_t)M;
+    double *dxy, *dz, *dn;
+    return host_call(h, [&](HostIo& io) {
+        dxy = io.in<double>(xy, m * 2 * 8); dz = io.out<double>(z, m * 8); dn = io.out<double>(normal, m * 3 * 8);
+    }, [&](hipStream_t st) { return srbdqp_terrain_sample_device_f64(h, M, dxy, dz, dn, st); });
+}
+
+int srbdqp_terrain_inputs_device_f64(srbdqp_handle* h, int64_t B, const double* feet, double* x_ref, double* normals, void* stream) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (!h->terrain.map.h) { h->err = "srbdqp_terrain_inputs: no terrain is set (srbdqp_set_terrain)"; return SRBDQP_E_INVALID; }
+    if (B < 0 || B > 0x7fffffffLL || (B > 0 && (!feet || !x_ref || !normals))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    srbdqp::TerrainInputsArgs a{h->terrain.map, feet, x_ref, normals, (int32_t)h->cfg.horizon, (long long)B};
+    HIP_TRY(h, srbdqp::launch_terrain_inputs(a, stream ? reinterpret_cast<hipStream_t>(stream) : h->stream));
+    h->kname = "terrain_inputs_f64";
+    return SRBDQP_OK;
+}
+
+int srbdqp_terrain_inputs_f64(srbdqp_handle* h, int64_t B, const double* feet, double* x_ref, double* normals) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (!h->terrain.map.h) { h->err = "srbdqp_terrain_inputs: no terrain is set (srbdqp_set_terrain)"; return SRBDQP_E_INVALID; }
+    if (B < 0 || B > 0x7fffffffLL || (B > 0 && (!feet || !x_ref || !normals))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
+    double *dfe, *dxr, *dcn;
+    return host_call(h, [&](HostIo& io) {
+        dfe = io.in<double>(feet, b * 12 * 8); dxr = io.add<double>(x_ref, x_ref, b * N * 13 * 8, false); dcn = io.out<double>(normals, b * N * 12 * 8);
+    }, [&](hipStream_t st) { return srbdqp_terrain_inputs_device_f64(h, B, dfe, dxr, dcn, st); });
+}
 
 int srbdqp_fleet_default_settings(srbdqp_fleet_settings* s) {
     if (!s || s->struct_size != (int32_t)sizeof(srbdqp_fleet_settings)) return SRBDQP_E_INVALID;
@@ -2951,12 +3055,23 @@ int srbdqp_fleet_rollout_device_f64(srbdqp_handle* h, int64_t B, int32_t T, doub
     const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
     if (const int rc = ensure_fleet_buffers(h, b)) return rc;
     const auto& f = h->fleet;
+    const bool terrain = h->terrain.map.h != nullptr;
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
     if (x_log) HIP_TRY(h, hipMemcpyAsync(x_log, x, b * 13 * 8, hipMemcpyDeviceToDevice, st));
     if (feet_log) HIP_TRY(h, hipMemcpyAsync(feet_log, feet, b * 12 * 8, hipMemcpyDeviceToDevice, st));
     for (int32_t t = 0; t < T; ++t) {
         const size_t k = (size_t)t;
         if (const int rc = srbdqp_mpc_inputs_device_f64(h, B, x, feet, stamp, v_ref, standing, &cfg->gait, f.x_ref, f.foot, f.contact, f.pcom, f.landing, st)) return rc;
+        if (terrain) {
+            // the ground under the footholds: the normals of this step's QPs and the height reference, then the solve a device-buffer call makes with those normals
+            // as the normals of THIS call -- every pass of it, deferred ones on the tail stream included, launches with this Call (solve_device_impl)
+            if (const int rc = srbdqp_terrain_inputs_device_f64(h, B, feet, f.x_ref, f.normals, st)) return rc;
+            Call c;
+            c.use_hint = true; c.cn_call = f.normals;
+            c.plan = plan_solve(h, c, (int)B, maxs_or(h->cfg, 4));
+            if (const int rc = solve_device_impl(h, c, (int32_t)B, x, f.x_ref, f.foot, f.contact, f.pcom, nullptr, nullptr, f.u, f.x_out, nullptr, f.status, f.iters, st))
+                return rc;
+        } else
         if (const int rc = srbdqp_solve_batch_device_f64(h, (int32_t)B, x, f.x_ref, f.foot, f.contact, f.pcom, nullptr, nullptr, f.u, f.x_out, nullptr, f.status,
                                                          f.iters, st)) return rc;
         if (h->cfg.flags & SRBDQP_FLAG_DEFER_TAIL) if (const int rc = srbdqp_flush(h, st)) return rc;   // the plant needs complete forces

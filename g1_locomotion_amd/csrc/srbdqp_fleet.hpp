@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "srbdqp_gait.hpp"
+#include "srbdqp_terrain.hpp"
 
 namespace srbdqp {
 
@@ -37,8 +38,8 @@ struct FleetArgs {
     long long B;
 };
 
-// the launch of srbdqp_fleet_advance_kernel on st (srbdqp_wrench_lat_ew.hip)
-hipError_t launch_fleet_advance(const FleetArgs& a, hipStream_t st);
+// the launch of srbdqp_fleet_advance_kernel on st (srbdqp_wrench_lat_ew.hip); map: the terrain instantiation over it (null: flat ground)
+hipError_t launch_fleet_advance(const FleetArgs& a, hipStream_t st, const TerrainMap* map = nullptr);
 
 constexpr int kFleetTile = 64;   // robots per workgroup pass = its threads: one wave, one robot per lane
 constexpr int kFleetRow = 13;    // LDS row of every staged array, in doubles: odd, so that a lane per row walks all banks
@@ -117,8 +118,26 @@ __host__ __device__ __forceinline__ void fleet_plant(const FleetBody& q, double 
 // (the forces are rows of 12 doubles inside the solve's [B][N][12]: 96 contiguous bytes each); lane r then holds robot r's 13 states in registers through the
 // substeps' RK4, writes its new state and footholds back to its LDS rows, and the tile leaves with coalesced stores: in place, and into the roll-out's logs.
 // A robot that is skipped keeps its rows, in memory (nothing of it is stored) and in the logs (which record what it holds).
-template <int TILE>
-__global__ __launch_bounds__(TILE) void srbdqp_fleet_advance_kernel(FleetArgs a) {
+//
+// fleet_height: the height of the point (x, y, z) over the ground under it, what "fallen" compares with z_min; fleet_ground: the ground's height at (x, y), where a
+// foot lands -- without a map z itself and the landing point's own z (`flat`).  m: the map, or nothing
+template <class... MAP>
+__device__ __forceinline__ double fleet_height(double x, double y, double z, const MAP&... m) {
+    if constexpr (sizeof...(MAP) > 0) { double zg, n[3]; terrain_sample(m..., x, y, zg, n); return z - zg; }
+    else return z;
+}
+template <class... MAP>
+__device__ __forceinline__ double fleet_ground(double x, double y, double flat, const MAP&... m) {
+    if constexpr (sizeof...(MAP) > 0) { double zg, n[3]; terrain_sample(m..., x, y, zg, n); return zg; }
+    else return flat;
+}
+
+// MAP: nothing -- flat ground, the kernel of DESIGN.md section 17, whose text this parameter leaves what it was -- or one TerrainMap, the terrain instantiation
+// (section 18): the ground is the map instead of the plane z = 0.  Two places differ: a foot that touches down stands at S(own xy).z, heel and toe each, and both
+// "fallen" tests compare the CoM's height OVER the ground under it, x[5] - S(com xy).z, with z_min.
+template <int TILE, class... MAP>
+__global__ __launch_bounds__(TILE) void srbdqp_fleet_advance_kernel(FleetArgs a, MAP... map) {
+    static_assert(sizeof...(MAP) <= 1, "at most one map");
     constexpr int RW = kFleetRow;
     __shared__ double sx[TILE * RW], sft[TILE * RW], su[TILE * RW], slp[TILE * 3], spu[TILE * 6];
     __shared__ uint8_t swx[TILE], swf[TILE];      // robot r's state / footholds changed: store them
@@ -154,7 +173,7 @@ __global__ __launch_bounds__(TILE) void srbdqp_fleet_advance_kernel(FleetArgs a)
             bool wx = false, wf = false, up = run;
             if (run) {
                 // (5.) a robot handed over outside the envelope has fallen already: it gets this period, and holds behind it whatever the period did
-                const bool inside0 = !(x[5] < a.z_min) && !(fabs(x[0]) > a.tilt_max) && !(fabs(x[1]) > a.tilt_max);
+                const bool inside0 = !(fleet_height(x[3], x[4], x[5], map...) < a.z_min) && !(fabs(x[0]) > a.tilt_max) && !(fabs(x[1]) > a.tilt_max);
                 // 2. plant: substeps of RK4 under the forces at the contact points
                 FleetBody q;
                 q.mass = a.mass; q.inertia[0] = a.inertia[0]; q.inertia[1] = a.inertia[1]; q.inertia[2] = a.inertia[2];
@@ -183,15 +202,15 @@ __global__ __launch_bounds__(TILE) void srbdqp_fleet_advance_kernel(FleetArgs a)
                 if (left || right) {
                     const int c0 = left ? 0 : 6;                                   // contacts 0, 1 (left heel, toe) or 2, 3
                     const double lx = slp[3 * t], ly = slp[3 * t + 1], lz = slp[3 * t + 2];
-                    sft[RW * t + c0] = lx - a.foot_half_length; sft[RW * t + c0 + 1] = ly; sft[RW * t + c0 + 2] = lz;
-                    sft[RW * t + c0 + 3] = lx + a.foot_half_length; sft[RW * t + c0 + 4] = ly; sft[RW * t + c0 + 5] = lz;
+                    sft[RW * t + c0] = lx - a.foot_half_length; sft[RW * t + c0 + 1] = ly; sft[RW * t + c0 + 2] = fleet_ground(lx - a.foot_half_length, ly, lz, map...);
+                    sft[RW * t + c0 + 3] = lx + a.foot_half_length; sft[RW * t + c0 + 4] = ly; sft[RW * t + c0 + 5] = fleet_ground(lx + a.foot_half_length, ly, lz, map...);
                     wf = true;
                 }
                 // 5. fallen: it holds from the next period on
                 bool ok = true;
 #pragma unroll
                 for (int k = 0; k < 12; ++k) ok = ok && isfinite(x[k]);
-                up = inside0 && ok && !(x[5] < a.z_min) && !(fabs(x[0]) > a.tilt_max) && !(fabs(x[1]) > a.tilt_max);
+                up = inside0 && ok && !(fleet_height(x[3], x[4], x[5], map...) < a.z_min) && !(fabs(x[0]) > a.tilt_max) && !(fabs(x[1]) > a.tilt_max);
             }
             swx[t] = wx; swf[t] = wf;
             if (a.alive && !up) a.alive[b] = 0;

@@ -75,10 +75,25 @@ hipError_t launch_wrench_cn_lat(int N, bool set_attr, const KArgs& a, const void
 
 // The fleet's plant step (srbdqp_fleet.hpp) is instantiated here too, behind the low-latency kernels, for their reason: srbdqp.hip's code object stays what it
 // was, and the library keeps its two code objects (tests/test_staged_wrench_cpu.py, tests/test_staged_normals_cpu.py count them).
-hipError_t launch_fleet_advance(const FleetArgs& a, hipStream_t st) {
+hipError_t launch_fleet_advance(const FleetArgs& a, hipStream_t st, const TerrainMap* map) {
     const long long tiles = (a.B + kFleetTile - 1) / kFleetTile;   // one tile of 64 robots per workgroup pass
     const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
-    hipLaunchKernelGGL(srbdqp_fleet_advance_kernel<kFleetTile>, grid, dim3(kFleetTile), 0, st, a);
+    if (map) hipLaunchKernelGGL((srbdqp_fleet_advance_kernel<kFleetTile, TerrainMap>), grid, dim3(kFleetTile), 0, st, a, *map);
+    else hipLaunchKernelGGL(srbdqp_fleet_advance_kernel<kFleetTile>, grid, dim3(kFleetTile), 0, st, a);
+    return hipGetLastError();
+}
+
+// ... and the two kernels of the ground under it (srbdqp_terrain.hpp): the sample of the map at M points, the normals and the height reference of B robots
+hipError_t launch_terrain_sample(const TerrainSampleArgs& a, hipStream_t st) {
+    const long long want = (a.M + 255) / 256;                      // grid-stride: enough 256-thread workgroups to fill 256 CUs several times over, no more
+    hipLaunchKernelGGL(srbdqp_terrain_sample_kernel<256>, dim3((unsigned)(want < 1 ? 1 : (want > 256 * 16 ? 256 * 16 : want))), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_terrain_inputs(const TerrainInputsArgs& a, hipStream_t st) {
+    const long long tiles = (a.B + kTerrainTile - 1) / kTerrainTile;   // one tile of 32 robots per workgroup pass
+    const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
+    hipLaunchKernelGGL(srbdqp_terrain_inputs_kernel<kTerrainTile>, grid, dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

@@ -501,7 +501,9 @@ class BatchMPC(_Engine):
         """One control period of B robots between two solves (srbdqp_fleet_advance_f64): the nonlinear SRBD plant under the first-step forces u0 (B,12) at
         the contact points feet (B,12) or (B,4,3), the gait clock, the touchdown of the foot that lands around landing (B,3) (mpc_inputs()' output), the
         robots that fell.  standing (B,) flags, push (B,6) world wrench on the body during the period (torque first; the MPC does not know it), alive (B,)
-        flags: each or None.  settings: fleet_settings()' keywords.  The inputs are not modified.
+        flags: each or None.  settings: fleet_settings()' keywords.  The inputs are not modified.  With a map set (set_terrain()) a foot that touches
+        down stands on the map, heel and toe each at the height under it, and "fallen" compares the CoM's height over the ground under it with z_min
+        (kernel_name() "fleet_advance_terrain_f64").
         Returns dict(x (B,13), feet (B,12), stamp (B,), alive (B,) uint8)."""
         x = np.array(x, dtype=np.float64).reshape(-1, NX)
         B = x.shape[0]
@@ -531,7 +533,10 @@ class BatchMPC(_Engine):
         round trip in between.  x0 (B,13), feet (B,12) or (B,4,3), stamp (B,), v_ref (B,2) and standing (B,) flags or None (both constant over the call),
         push (steps,B,6) world wrenches or None, alive (B,) flags or None.  settings: fleet_settings()' keywords.  Robot records and weights set on the
         engine are honoured; an external wrench or contact normals set on it raise SrbdqpError.  A second call from the returned x, feet, stamp and alive
-        continues the first one bit for bit.
+        continues the first one bit for bit.  With a map set (set_terrain()) the fleet walks on it: per step mpc_inputs -> terrain_inputs -> the solve
+        on the general kernel with those normals as the normals of the call -> the terrain plant step; robot records, weights, a wrench or normals set
+        on the engine, a live horizon, rank-aware steps, N = 24 and a kernel= that bars the general kernel then raise SrbdqpError ("while a terrain is
+        set").
         Returns dict(x (steps+1,B,13), u0 (steps,B,12), feet (steps+1,B,12), status (steps,B), iters (steps,B), alive (B,) uint8, stamp (B,))."""
         x = np.array(x0, dtype=np.float64).reshape(-1, NX)
         B, T = x.shape[0], int(steps)
@@ -559,6 +564,56 @@ class BatchMPC(_Engine):
         rc = self._lib.srbdqp_fleet_rollout_device_f64(self._h, int(B), int(steps), v(x), v(feet), v(stamp), v(v_ref), v(standing), v(push), C.byref(s),
                                                        v(alive), v(x_log), v(u0_log), v(feet_log), v(status_log), v(iters_log), v(stream))
         self._check(rc)
+
+    # -- the ground under the fleet (include/srbdqp_cascade.h) ---------------------------------------------------
+    def set_terrain(self, heights, origin=(0.0, 0.0), cell=None):
+        """A height map for fleet_advance() and rollout() (srbdqp_set_terrain): heights (ny, nx), node (i, j) = heights[j, i] at (origin[0] + i cell,
+        origin[1] + j cell); checked and copied by the library -- finite, at least 2 x 2, neighbouring nodes at most 1.2 cell apart in height.  None
+        clears it (flat ground again).  Every solve of the engine is untouched."""
+        if heights is None:
+            self._check(self._lib.srbdqp_set_terrain(self._h, None, None))
+            return
+        if cell is None:
+            raise ValueError("set_terrain: pass cell, the node spacing in metres")
+        hm = np.ascontiguousarray(heights, dtype=np.float64)
+        if hm.ndim != 2:
+            raise ValueError(f"set_terrain: expected heights of shape (ny, nx), got {hm.shape}")
+        t = _lib.Terrain()
+        t.struct_size = C.sizeof(_lib.Terrain)
+        t.ny, t.nx = (min(int(n), 2 ** 31 - 1) for n in hm.shape)
+        t.x0, t.y0, t.cell = float(origin[0]), float(origin[1]), float(cell)
+        self._check(self._lib.srbdqp_set_terrain(self._h, C.byref(t), _p(hm)))
+
+    def terrain_sample(self, xy, want_normal=True):
+        """The map at M points (srbdqp_terrain_sample_f64): xy (M,2) -> dict(z (M,)[, normal (M,3)]): bilinear height and unit normal; a point off the
+        map is the clamped point, a non-finite coordinate gives z = NaN and the normal (0, 0, 1)."""
+        p = _c(xy, np.float64).reshape(-1, 2)
+        M = p.shape[0]
+        z = np.empty(M)
+        n = np.empty((M, 3)) if want_normal else None
+        self._check(self._lib.srbdqp_terrain_sample_f64(self._h, M, _p(p), _p(z), _p(n)))
+        return dict(z=z, normal=n) if want_normal else dict(z=z)
+
+    def terrain_sample_device(self, M, xy, z, normal=0, stream=0):
+        """Device-pointer form of terrain_sample(): raw addresses, launch enqueued behind `stream`, returns at once."""
+        v = lambda q: C.c_void_p(int(q)) if q else None
+        self._check(self._lib.srbdqp_terrain_sample_device_f64(self._h, int(M), v(xy), v(z), v(normal), v(stream)))
+
+    def terrain_inputs(self, feet, x_ref):
+        """Between mpc_inputs() and the solve on a map (srbdqp_terrain_inputs_f64): feet (B,12) or (B,4,3), x_ref (B,N,13) (not modified).
+        Returns dict(x_ref (B,N,13): column 5 raised by the mean height of the robot's four contact points, normals (B,N,12): the map's normal under
+        every contact point at every step -- what set_contact_normals() / solve(normals=) take)."""
+        f = _c(feet, np.float64).reshape(-1, NU)
+        B, N = f.shape[0], self.N
+        xr = np.array(x_ref, dtype=np.float64).reshape(B, N, NX)
+        cn = np.empty((B, N, NU))
+        self._check(self._lib.srbdqp_terrain_inputs_f64(self._h, B, _p(f), _p(xr), _p(cn)))
+        return dict(x_ref=xr, normals=cn)
+
+    def terrain_inputs_device(self, B, feet, x_ref, normals, stream=0):
+        """Device-pointer form of terrain_inputs(): raw addresses, x_ref updated in place, launch enqueued behind `stream`, returns at once."""
+        v = lambda q: C.c_void_p(int(q)) if q else None
+        self._check(self._lib.srbdqp_terrain_inputs_device_f64(self._h, int(B), v(feet), v(x_ref), v(normals), v(stream)))
 
     def last_kernel_ms(self) -> float:
         return float(self._lib.srbdqp_last_kernel_ms(self._h))

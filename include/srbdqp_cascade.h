@@ -116,6 +116,54 @@ int srbdqp_fleet_advance_device_f64(srbdqp_handle* h, int64_t B, double* x, doub
                                     const double* landing, const uint8_t* standing, const double* push, uint8_t* alive,
                                     const srbdqp_fleet_settings* cfg, void* stream);
 
+/* ---- the ground under the fleet: a height map on the handle, which the roll-out walks on.
+ *
+ * heights_host [ny][nx] doubles, x fastest: node (i, j) lies at (x0 + i cell, y0 + j cell).  The library checks and copies the map; NULL (t or heights_host)
+ * clears it.  Replacing or clearing a map first waits for every stream of the handle.  srbdqp_destroy frees it.  Refused (SRBDQP_E_INVALID, nothing copied, the
+ * map that was set stays): a wrong struct_size; nx or ny below 2, nx ny above 2^24; a cell that is not finite and positive; an origin that is not finite; a
+ * height that is not finite; two neighbouring heights, along x or along y, that differ by more than 1.2 cell -- which keeps gx^2 + gy^2 <= 2.88 below, so that
+ * every normal the map can produce has n_z >= 0.5, the rule of srbdqp_set_contact_normals, and the device may produce normals without a host check.
+ *
+ * A map changes srbdqp_fleet_advance_* and srbdqp_fleet_rollout_* (below) and makes the srbdqp_terrain_* calls available; every solve on the handle is untouched.
+ *
+ * The sample S(x, y) -> (z, n), every step one rounded fp64 operation (no fused multiply-add):
+ *   u = (x - x0) / cell clamped to [0, nx - 1];  i = min(floor(u), nx - 2);  fx = u - i;      v, j, fy: the same along y
+ *   h00 = h[j][i], h10 = h[j][i+1], h01 = h[j+1][i], h11 = h[j+1][i+1]
+ *   a = h00 + fx (h10 - h00);  b = h01 + fx (h11 - h01);  z = a + fy (b - a)
+ *   gx = ((h10 - h00) + fy ((h11 - h01) - (h10 - h00))) / cell;   gy = ((h01 - h00) + fx ((h11 - h10) - (h01 - h00))) / cell
+ *   n = (-gx, -gy, 1) / sqrt((gx gx + gy gy) + 1)
+ * A point off the map is the clamped point.  A coordinate that is not finite gives z = NaN and n = (0, 0, 1). */
+typedef struct srbdqp_terrain {
+    int32_t struct_size;          /* = sizeof(srbdqp_terrain) */
+    int32_t nx, ny;               /* nodes along x and along y, >= 2 each */
+    int32_t reserved0;
+    double x0, y0;                /* node (0, 0) */
+    double cell;                  /* node spacing, m */
+} srbdqp_terrain;
+
+int srbdqp_set_terrain(srbdqp_handle* h, const srbdqp_terrain* t, const double* heights_host);
+
+/* S at M points: xy [M][2] -> z [M], normal [M][3] (may be NULL).  One point per lane.  Without a map: SRBDQP_E_INVALID. */
+int srbdqp_terrain_sample_f64(srbdqp_handle* h, int64_t M, const double* xy, double* z, double* normal);
+int srbdqp_terrain_sample_device_f64(srbdqp_handle* h, int64_t M, const double* xy, double* z, double* normal, void* stream);
+
+/* Between srbdqp_mpc_inputs_* and the solve: feet [B][12] (as handed to srbdqp_mpc_inputs_*), x_ref [B][N][13] in/out, normals [B][N][12] out, in the layout
+ * of srbdqp_set_contact_normals.  The normal of contact i of robot b is S(feet xy of i).n at every step (a swing contact's too: it keeps its old point until it
+ * lands); x_ref[b][k][5] += (((z0 + z1) + z2) + z3) 0.25 over the z of `feet` as handed in: the height reference follows the ground the robot stands on.
+ * N: the handle's horizon.  Without a map: SRBDQP_E_INVALID. */
+int srbdqp_terrain_inputs_f64(srbdqp_handle* h, int64_t B, const double* feet, double* x_ref, double* normals);
+int srbdqp_terrain_inputs_device_f64(srbdqp_handle* h, int64_t B, const double* feet, double* x_ref, double* normals, void* stream);
+
+/* With a map set, srbdqp_fleet_advance_* differs in two places: at a touchdown the heel and the toe each get z = S(own xy).z where landing's z is copied on
+ * flat ground, and both "fallen" tests compare x[5] - S(com xy).z, the height over the ground, with z_min.  And srbdqp_fleet_rollout_* enqueues per step
+ *   srbdqp_mpc_inputs_device_f64 -> srbdqp_terrain_inputs_device_f64, into a normals buffer of the handle's roll-out allocation -> the fp64 batch solve on the
+ *   general kernel with those normals as the normals of this call (every restart pass reads them; nothing is set on the handle) -> srbdqp_flush on a
+ *   SRBDQP_FLAG_DEFER_TAIL handle -> the terrain plant step.
+ * Such a roll-out is refused (SRBDQP_E_INVALID before any launch, in the words of the handle's state "while a terrain is set") beside robot records, weights,
+ * an external wrench or handle-level normals, on a live horizon, with rank-aware steps, at N = 24 and with a srbdqp_config.kernel that bars the general kernel:
+ * no instantiation reads normals beside those.  Not modelled: ground reaction or sliding in the plant (the forces are the QP's), footholds predicted along the
+ * horizon, per-robot map offsets, feet turned with yaw, terrain under the swing trajectory, fp32, ragged fleets. */
+
 /* T control steps of B robots: for t = 0 ... T - 1, srbdqp_mpc_inputs_device_f64 -> the solve, exactly the launches srbdqp_solve_batch_device_f64 makes
  * for this handle, with pcom from the inputs -> srbdqp_fleet_advance_device_f64, enqueued on `stream` without a host synchronisation (plain launches: no
  * graph, no persistent kernel).  On a SRBDQP_FLAG_DEFER_TAIL handle srbdqp_flush follows every solve: the plant needs complete forces.
@@ -123,7 +171,8 @@ int srbdqp_fleet_advance_device_f64(srbdqp_handle* h, int64_t B, double* x, doub
  *   push [T][B][6] or NULL.  Logs, each may be NULL: x_log [T+1][B][13] and feet_log [T+1][B][12] (entry 0: as passed in; t + 1: behind period t),
  *   u0_log [T][B][12] (the forces period t ran under), status_log, iters_log [T][B] (of the solve of step t).
  * Robot records and weights set on the handle are honoured (the solves read them; the plant reads mass and inertia).  A handle with an external wrench or
- * contact normals set is refused (SRBDQP_E_INVALID): the plant is flat ground and the MPC's wrench is not the plant's.  The horizon buffers (x_ref, foot,
+ * contact normals set is refused (SRBDQP_E_INVALID): the plant is flat ground and the MPC's wrench is not the plant's.  (With a map set, srbdqp_set_terrain
+ * above, the fleet walks on it and the list of refusals is the one given there.)  The horizon buffers (x_ref, foot,
  * contact, pcom, landing, u, x_out, status, iters for B robots) belong to the handle: allocated at the first roll-out, grown when a larger B asks,
  * released by srbdqp_destroy.  Nothing is set or cleared on the handle.  B or T < 1, a bad struct_size, substeps < 1, a setting that is not finite or
  * not positive, an invalid gait: SRBDQP_E_INVALID before any launch. */

@@ -5,7 +5,12 @@
   * the plant step alone (srbdqp_fleet_advance_device_f64): time per launch, its share of a step of the roll-out, and its GB/s beside the 4.4 TB/s DESIGN.md
     section 8 quotes for mpc_inputs (it integrates 40 derivative evaluations per robot: it is not expected to sit at the HBM roof).
 
-    python tools/fleet_rollout_bench.py [--robots 4096] [--steps 100] [--reps 5] [--out profiles/<name>.json]
+--terrain: the same fleet on rolling ground -- a height map 0.08 sin(1.5 x) cos(1.2 y) m on a 0.1 m grid, the robots spread over 4 m x
+4 m of it with their feet on the ground --, the Python loop with the inputs step (terrain_inputs_device, set_contact_normals) in it.  --kernel wrench: the flat
+roll-out on a SRBDQP_KERNEL_WRENCH handle, the solve family a terrain roll-out runs: the difference between the two is the cost of the terrain; the default flat
+roll-out beside them gives the cost of leaving the one-wave kernel.
+
+    python tools/fleet_rollout_bench.py [--robots 4096] [--steps 100] [--reps 5] [--terrain] [--kernel auto|wrench] [--out profiles/<name>.json]
 """
 import argparse
 import hashlib
@@ -30,6 +35,8 @@ def main():
     ap.add_argument("--robots", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--terrain", action="store_true")
+    ap.add_argument("--kernel", choices=("auto", "wrench"), default="auto")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -39,6 +46,10 @@ def main():
     rng = np.random.default_rng(0)
     x0 = np.zeros((B, 13)); x0[:, 3:6] = COM + rng.normal(size=(B, 3)) * 0.003; x0[:, 12] = -9.80665
     feet0 = np.tile(FEET.reshape(12), (B, 1))
+    if a.terrain:                                                         # (the flat runs draw exactly what they drew before)
+        at = np.random.default_rng(1).uniform(-2.0, 2.0, (B, 2))
+        x0[:, 3:5] += at
+        feet0 = (FEET[None, :, :] + np.concatenate([at, np.zeros((B, 1))], 1)[:, None, :]).reshape(B, 12)
     stamp0 = dt * rng.integers(0, 12, B).astype(np.float64)
     v_ref = rng.uniform(-1.0, 1.0, (B, 2)) * np.array([0.3, 0.1])
     push = np.where(rng.random((T, B, 1)) < 0.05, rng.uniform(-1.0, 1.0, (T, B, 6)) * np.array([2.0, 2.0, 0.0, 30.0, 30.0, 10.0]), 0.0)
@@ -50,8 +61,17 @@ def main():
     xr, fo, pc, lp, u, xo = f64(B, N, 13), f64(B, N, 12), f64(B, N, 3), f64(B, 3), f64(B, N, 12), f64(B, N + 1, 13)
     ct = torch.empty((B, N, 4), dtype=torch.uint8, device=dev)
     st, it = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
-    res = dict(robots=B, steps=T, horizon=N, reps=a.reps)
-    with BatchMPC(horizon=N, dt=dt) as eng:
+    res = dict(robots=B, steps=T, horizon=N, reps=a.reps, terrain=bool(a.terrain), kernel_setting=a.kernel)
+    cn = f64(B, N, 12) if a.terrain else None
+    with BatchMPC(horizon=N, dt=dt, kernel=_lib.KERNEL_WRENCH if a.kernel == "wrench" else _lib.KERNEL_AUTO) as eng:
+        if a.terrain:
+            gx, gy = -4.0 + 0.1 * np.arange(81), -4.0 + 0.1 * np.arange(81)
+            eng.set_terrain(0.08 * np.sin(1.5 * gx)[None, :] * np.cos(1.2 * gy)[:, None], origin=(-4.0, -4.0), cell=0.1)
+            fz = feet0.reshape(B * 4, 3)
+            fz[:, 2] = eng.terrain_sample(fz[:, 0:2], want_normal=False)["z"]
+            feet0 = fz.reshape(B, 12)
+            x0[:, 5] += eng.terrain_sample(x0[:, 3:5], want_normal=False)["z"]
+
         def fresh():
             return up(x0), up(feet0), up(stamp0), torch.ones(B, dtype=torch.uint8, device=dev)
 
@@ -72,11 +92,16 @@ def main():
             for k in range(T):
                 eng.mpc_inputs_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), d_v.data_ptr(), COM, xr.data_ptr(), fo.data_ptr(), ct.data_ptr(),
                                       pc.data_ptr(), landing=lp.data_ptr())
+                if a.terrain:
+                    eng.terrain_inputs_device(B, feet.data_ptr(), xr.data_ptr(), cn.data_ptr())
+                    eng.set_contact_normals(cn)
                 eng.solve_device(B, x.data_ptr(), xr.data_ptr(), fo.data_ptr(), ct.data_ptr(), u.data_ptr(), x_out=xo.data_ptr(), status=st.data_ptr(),
                                  iters=it.data_ptr(), pcom=pc.data_ptr())
                 eng.fleet_advance_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), u.data_ptr(), lp.data_ptr(), u0_stride=12 * N,
                                          push=d_pu[k].data_ptr(), alive=al.data_ptr())
                 eng.synchronize()
+            if a.terrain:
+                eng.set_contact_normals(None)
             return time.perf_counter() - t0
 
         def advance_alone():
@@ -95,6 +120,16 @@ def main():
         calls = [call() for _ in range(a.reps)]
         t_call = float(np.median([c[0] for c in calls]))
         res["kernel"] = eng.kernel_name()
+        if a.terrain:                                                     # the inputs step alone: B (12 + 2 N 13 + N 12) doubles moved per launch
+            xs, fs, _, _ = fresh()
+            eng.terrain_inputs_device(B, fs.data_ptr(), xr.data_ptr(), cn.data_ptr()); eng.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(T):
+                eng.terrain_inputs_device(B, fs.data_ptr(), xr.data_ptr(), cn.data_ptr())
+            eng.synchronize()
+            t_in = (time.perf_counter() - t0) / T
+            res["terrain_inputs_us_per_launch"] = t_in * 1e6
+            res["terrain_inputs_gb_per_s"] = B * (12 + 2 * N * 13 + N * 12) * 8 / t_in / 1e9
         res["rollout_call_s"] = t_call
         res["rollout_enqueue_s"] = float(np.median([c[1] for c in calls]))
         res["rollout_robot_steps_per_s"] = B * T / t_call
