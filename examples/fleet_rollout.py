@@ -1,10 +1,12 @@
 """256 walking robots under random commands and random pushes for 100 control steps, in one call (BatchMPC.rollout):
 prints the share of the fleet still on its feet and how well it follows the commanded velocity.
 
-    python examples/fleet_rollout.py [--robots 256] [--steps 100] [--seed 0] [--slope 0.2]
+    python examples/fleet_rollout.py [--robots 256] [--steps 100] [--seed 0] [--slope 0.2] [--observer]
 
 --slope s: the same fleet on the plane z = s x (BatchMPC.set_terrain): the friction pyramids tilt with the ground, a foot lands on it,
 and "fallen" is the height over it.
+--observer: on flat ground, a push of 10 N along x and -25 N along y on every robot during steps 5 to 29, once blind and once with the momentum observer
+(BatchMPC.rollout(observer=True)): prints how far the push carried the fleet sideways in either run.
 """
 import argparse
 import os
@@ -24,7 +26,10 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--slope", type=float, default=0.0)
+    ap.add_argument("--observer", action="store_true")
     a = ap.parse_args()
+    if a.observer and a.slope:
+        ap.error("--observer is flat ground")
     from g1_locomotion_amd import BatchMPC
     rng = np.random.default_rng(a.seed)
     B, T, dt = a.robots, a.steps, 0.04
@@ -42,7 +47,22 @@ def main():
             eng.set_terrain(np.tile(a.slope * gx, (41, 1)), origin=(-10.0, -10.0), cell=0.5)
             feet.reshape(B, 4, 3)[:, :, 2] = ground(feet.reshape(B, 4, 3))
             x0[:, 5] += ground(x0[:, 3:5])
-        r = eng.rollout(x0, feet, stamp, v_ref, T, COM, push=push)
+        if a.observer:
+            shove = np.zeros((T, B, 6)); shove[5:30, :, 3] = 10.0; shove[5:30, :, 4] = -25.0
+            free = eng.rollout(x0, feet, stamp, v_ref, T, COM)
+            blind = eng.rollout(x0, feet, stamp, v_ref, T, COM, push=shove)
+            r = eng.rollout(x0, feet, stamp, v_ref, T, COM, push=shove, observer=True)
+            for name, q in (("blind", blind), ("observed", r)):
+                up = (q["alive"] != 0) & (free["alive"] != 0)
+                if not up.any():
+                    print(f"{name:9s}: no robot is still up after {T} steps")
+                    continue
+                print(f"{name:9s}: {np.mean(q['alive'] != 0):.1%} alive, pushed {np.abs(q['x'][-1, up, 4] - free['x'][-1, up, 4]).mean():.3f} m sideways on average, "
+                      f"largest roll {np.abs(q['x'][:, up, 0]).max():.3f} rad, {q['iters'].mean():.1f} iterations per QP")
+            k = min(29, T - 1)
+            print(f"the estimate behind step {k}: force {r['w_log'][k][:, 3:6].mean(0).round(2).tolist()} N (applied: [10.0, -25.0, 0.0])")
+        else:
+            r = eng.rollout(x0, feet, stamp, v_ref, T, COM, push=push)
     r["x"][:, :, 5] -= ground(r["x"][:, :, 3:5])                         # heights below are over the ground
     alive = r["alive"] != 0
     half = T // 2                                                        # the mean velocity over the second half of the roll-out, robots still up

@@ -47,6 +47,12 @@ class FleetSettings(C.Structure):
                 ("tilt_max", C.c_double), ("gait", Gait)]
 
 
+class ObserverSettings(C.Structure):
+    """srbdqp_observer_settings (include/srbdqp_cascade.h): the momentum observer's filter gain, horizon decay and clamps."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved0", C.c_int32), ("gain", C.c_double), ("horizon_decay", C.c_double),
+                ("torque_max", C.c_double), ("force_max", C.c_double)]
+
+
 class Terrain(C.Structure):
     """srbdqp_terrain (include/srbdqp_cascade.h): the grid of a height map."""
     _fields_ = [("struct_size", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("reserved0", C.c_int32),
@@ -173,6 +179,9 @@ _INPUTS = [H, _i64, dp, dp, dp, dp, u8p, C.POINTER(Gait), dp, dp, u8p, dp, dp]
 _FLEET = C.POINTER(FleetSettings)
 _ADVANCE = [H, _i64, dp, dp, dp, dp, _i64, dp, u8p, dp, u8p, _FLEET]       # B, x, feet, stamp, u0, u0_stride, landing, standing, push, alive, settings
 _ROLLOUT = [H, _i64, _i32, dp, dp, dp, dp, u8p, dp, _FLEET, u8p, dp, dp, dp, i32p, i32p]   # B, T, x, feet, stamp, v_ref, standing, push, settings, alive, the five logs
+_OBS = C.POINTER(ObserverSettings)
+_OBSERVER = [H, _i64, dp, dp, dp, dp, _i64, u8p, _OBS, dp, dp]            # B, x_prev, x_next, feet_prev, u0, u0_stride, alive, settings, w_est, ew_out
+_ROLLOUT_OBS = _ROLLOUT + [_OBS, dp, dp]                                  # ... the observer's settings, w_est, w_log
 SIGNATURES = {
     # include/srbdqp.h -- config, handle
     "srbdqp_default_config": (_int, [_CFG]),
@@ -249,6 +258,12 @@ SIGNATURES = {
     "srbdqp_terrain_sample_device_f64": (_int, [H, _i64, dp, dp, dp, _vp]),
     "srbdqp_terrain_inputs_f64": (_int, [H, _i64, dp, dp, dp]),
     "srbdqp_terrain_inputs_device_f64": (_int, [H, _i64, dp, dp, dp, _vp]),
+    # ... that feels its pushes: the momentum observer and the roll-out whose solves read it
+    "srbdqp_observer_default_settings": (_int, [_OBS]),
+    "srbdqp_wrench_observer_f64": (_int, _OBSERVER),
+    "srbdqp_wrench_observer_device_f64": (_int, _OBSERVER + [_vp]),
+    "srbdqp_fleet_rollout_observed_device_f64": (_int, _ROLLOUT_OBS + [_vp]),
+    "srbdqp_fleet_rollout_observed_f64": (_int, _ROLLOUT_OBS),
 }
 EXPORTS = tuple(SIGNATURES)
 

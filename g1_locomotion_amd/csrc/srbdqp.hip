@@ -27,6 +27,7 @@
 #include "srbdqp_wrench_lat_ew.hpp"
 #include "srbdqp_cascade.hpp"
 #include "srbdqp_fleet.hpp"
+#include "srbdqp_observer.hpp"
 #include "srbdqp_cascade.h"
 #include "srbdqp_aql.hpp"
 
@@ -159,6 +160,10 @@ struct srbdqp_handle {
         uint8_t* contact = nullptr;
         int32_t *status = nullptr, *iters = nullptr;
         double* normals = nullptr;         // [B][N][12], carved only while a terrain is set: the contact normals of a terrain roll-out's solves (Call::cn_call)
+        // carved once an observed roll-out has asked (observed): the external wrench of its solves (Call::ext_call), [B][N][6], and the two-slot ring of states
+        // [2][B][13] and footholds [2][B][12] the observer reads where the caller keeps no logs
+        bool observed = false;
+        double *ew = nullptr, *ring_x = nullptr, *ring_feet = nullptr;
     } fleet;
     // the ground under the fleet (srbdqp_set_terrain, include/srbdqp_cascade.h): the library's device copy of the height map; map.h null: flat ground
     struct Terrain {
@@ -2870,10 +2875,11 @@ int fleet_advance_check(srbdqp_handle* h, int64_t B, const void* x, const void* 
 }
 
 // the horizon buffers of a roll-out, at B robots, carved from one allocation of the handle's
-int ensure_fleet_buffers(srbdqp_handle* h, size_t B) {
+int ensure_fleet_buffers(srbdqp_handle* h, size_t B, bool observed = false) {
     auto& f = h->fleet;
     const bool terrain = h->terrain.map.h != nullptr;
-    if (f.mem && f.B >= B && (!terrain || f.normals)) return SRBDQP_OK;
+    if (f.mem && f.B >= B && (!terrain || f.normals) && (!observed || f.ew)) return SRBDQP_OK;
+    f.observed = f.observed || observed;
     const size_t N = (size_t)h->cfg.horizon;
     auto carve = [&](char* base) {
         Carver c(base);
@@ -2881,6 +2887,8 @@ int ensure_fleet_buffers(srbdqp_handle* h, size_t B) {
         f.u = c.take<double>(B * N * 12); f.x_out = c.take<double>(B * (N + 1) * 13); f.contact = c.take<uint8_t>(B * N * 4);
         f.status = c.take<int32_t>(B); f.iters = c.take<int32_t>(B);
         f.normals = terrain ? c.take<double>(B * N * 12) : nullptr;
+        f.ew = f.observed ? c.take<double>(B * N * 6) : nullptr;
+        f.ring_x = f.observed ? c.take<double>(2 * B * 13) : nullptr; f.ring_feet = f.observed ? c.take<double>(2 * B * 12) : nullptr;
         return c.off;
     };
     const size_t want = carve(nullptr);
@@ -2913,6 +2921,68 @@ int fleet_rollout_check(srbdqp_handle* h, int64_t B, int32_t T, const void* x, c
     if (h->normals.dev) { h->err = "srbdqp_fleet_rollout: the handle has contact normals set (srbdqp_set_contact_normals): the plant stands on flat ground -- clear them"; return SRBDQP_E_INVALID; }
     if (const int rc = variant_check_batch(h, (int32_t)B)) return rc;
     return SRBDQP_OK;
+}
+
+// ---- the momentum observer and the roll-out that reads it (include/srbdqp_cascade.h; the kernel: srbdqp_observer.hpp) ----
+// what is wrong with an observer's settings (null: nothing).  The bounds keep every value an observer writes inside the rule of srbdqp_set_external_wrench
+const char* observer_settings_fault(const srbdqp_observer_settings* s) {
+    if (!s || s->struct_size != (int32_t)sizeof(srbdqp_observer_settings)) return "struct_size is not sizeof(srbdqp_observer_settings)";
+    if (!(s->gain > 0.0 && s->gain <= 1.0)) return "gain must lie in (0, 1]";
+    if (!(s->horizon_decay >= 0.0 && s->horizon_decay <= 1.0)) return "horizon_decay must lie in [0, 1]";
+    for (const double v : {s->torque_max, s->force_max})
+        if (!std::isfinite(v) || !(v > 0.0) || v > SRBDQP_EXT_WRENCH_MAX) return "torque_max and force_max must be finite, positive and at most SRBDQP_EXT_WRENCH_MAX (1e6)";
+    return nullptr;
+}
+
+// one launch of the observer; the arguments have been checked.  fill: no measurement -- ew from w_est as it stands (the wrench of a roll-out's first solve)
+int wrench_observer_launch(srbdqp_handle* h, int64_t B, const double* x_prev, const double* x_next, const double* feet_prev, const double* u0, int64_t u0_stride,
+                           const uint8_t* alive, const srbdqp_observer_settings* cfg, double* w_est, double* ew, double* w_log, bool fill, hipStream_t st) {
+    srbdqp::ObserverArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.x_prev = x_prev; a.x_next = x_next; a.feet = feet_prev; a.u0 = u0; a.u0_stride = (long long)u0_stride; a.alive = alive;
+    a.robots = reinterpret_cast<const double*>(h->robots.dev);   // robot b's own mass and inertia, as the plant step reads them
+    a.w_est = w_est; a.ew = ew; a.w_log = w_log;
+    a.mass = h->cfg.mass;
+    for (int i = 0; i < 3; ++i) a.inertia[i] = h->cfg.inertia[i];
+    a.dt = h->cfg.dt; a.gain = cfg->gain; a.decay = cfg->horizon_decay; a.torque_max = cfg->torque_max; a.force_max = cfg->force_max;
+    a.N = (int32_t)h->cfg.horizon; a.fill_only = fill ? 1 : 0;
+    a.B = (long long)B;
+    HIP_TRY(h, srbdqp::launch_wrench_observer(a, st));
+    h->kname = "wrench_observer_f64";
+    return SRBDQP_OK;
+}
+
+int wrench_observer_check(srbdqp_handle* h, int64_t B, const void* x_prev, const void* x_next, const void* feet_prev, const void* u0, int64_t u0_stride,
+                          const srbdqp_observer_settings* cfg, const void* w_est) {
+    if (B < 0 || B > 0x7fffffffLL || (B > 0 && (!x_prev || !x_next || !feet_prev || !u0 || !w_est))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (u0_stride < 12) { h->err = "srbdqp_wrench_observer: u0_stride must be at least 12 doubles"; return SRBDQP_E_INVALID; }
+    if (const char* why = observer_settings_fault(cfg)) { h->err = std::string("invalid srbdqp_observer_settings: ") + why; return SRBDQP_E_INVALID; }
+    return covers<RobotsIn>(h, B, "srbdqp_wrench_observer: ", " robots with ", false, false);
+}
+
+// May this handle run an observed roll-out?  What the plain one refuses for its arguments; then, for the handle's state, what check_staged_wrench refuses -- in
+// the refusal table's words -- except robot records and weights, which the wrench's batch kernel reads beside the wrench; then a terrain
+constexpr unsigned kFormsObservedRollout = bit(Form::Robots) | bit(Form::Weights);
+int fleet_rollout_observed_check(srbdqp_handle* h, int64_t B, int32_t T, const void* x, const void* feet, const void* stamp, const void* v_ref,
+                                 const srbdqp_fleet_settings* cfg, const srbdqp_observer_settings* obs, const void* w_est) {
+    const char* const fn = "srbdqp_fleet_rollout_observed";
+    const char* const in = " -- in an observed roll-out";
+    if (B < 1 || T < 1 || B > 0x7fffffffLL) { h->err = "srbdqp_fleet_rollout_observed: B and T must be at least 1 (B at most 2^31 - 1)"; return SRBDQP_E_INVALID; }
+    if (!x || !feet || !stamp || !v_ref) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (!w_est) { h->err = "srbdqp_fleet_rollout_observed: w_est is NULL (the estimate goes in and out: zeros start from no push)"; return SRBDQP_E_INVALID; }
+    if (const char* why = fleet_settings_fault(cfg)) { h->err = std::string("invalid srbdqp_fleet_settings: ") + why; return SRBDQP_E_INVALID; }
+    if (const char* why = observer_settings_fault(obs)) { h->err = std::string("invalid srbdqp_observer_settings: ") + why; return SRBDQP_E_INVALID; }
+    if (const unsigned other = state_of(h) & ~kFormsObservedRollout) { const int rc = refuse(h, refusal_form(other), fn); h->err += in; return rc; }
+    if (h->cfg.horizon > row(Form::ExtWrench).max_horizon) { h->err = std::string(fn) + ": " + ExtWrenchIn::n24(fn) + in; return SRBDQP_E_INVALID; }
+    if (!general_allowed(h->cfg)) {
+        h->err = std::string(fn) + ": " + row(Form::ExtWrench).noun + " is read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH" + in;
+        return SRBDQP_E_INVALID;
+    }
+    if (h->terrain.map.h) {
+        h->err = std::string(fn) + ": refused while a terrain is set (srbdqp_set_terrain): no instantiation reads contact normals beside a wrench (DESIGN.md section 13) -- srbdqp_set_terrain(h, NULL, NULL) goes back to flat ground";
+        return SRBDQP_E_INVALID;
+    }
+    return variant_check_batch(h, (int32_t)B);   // (records and weights for every robot)
 }
 
 }  // namespace
@@ -3046,19 +3116,30 @@ int srbdqp_fleet_advance_f64(srbdqp_handle* h, int64_t B, double* x, double* fee
     }, [&](hipStream_t st) { return srbdqp_fleet_advance_device_f64(h, B, dx, dfe, dst, du, u0_stride, dlp, dsd, dpu, dal, cfg, st); });
 }
 
-int srbdqp_fleet_rollout_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
-                                    const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
-                                    double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log, void* stream) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = fleet_rollout_check(h, B, T, x, feet, stamp, v_ref, cfg)) return rc;
+}  // extern "C"
+
+namespace {
+// the K-step loop behind its entry points' checks.  obs: the observed roll-out (flat ground) -- the solves read the handle's wrench buffer, which the
+// observer behind every plant step writes; null: the roll-out of section 17 / 18, launch for launch what it was
+int fleet_rollout_run(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
+                      const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                      double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                      const srbdqp_observer_settings* obs, double* w_est, double* w_log, void* stream) {
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
-    if (const int rc = ensure_fleet_buffers(h, b)) return rc;
+    if (const int rc = ensure_fleet_buffers(h, b, obs != nullptr)) return rc;
     const auto& f = h->fleet;
     const bool terrain = h->terrain.map.h != nullptr;
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
     if (x_log) HIP_TRY(h, hipMemcpyAsync(x_log, x, b * 13 * 8, hipMemcpyDeviceToDevice, st));
     if (feet_log) HIP_TRY(h, hipMemcpyAsync(feet_log, feet, b * 12 * 8, hipMemcpyDeviceToDevice, st));
+    if (obs) {
+        // without the caller's logs the observer reads x_t, x_t+1 and the feet of period t from the ring, which the plant step writes as its log: entry 0 as above
+        if (!x_log) HIP_TRY(h, hipMemcpyAsync(f.ring_x, x, b * 13 * 8, hipMemcpyDeviceToDevice, st));
+        if (!feet_log) HIP_TRY(h, hipMemcpyAsync(f.ring_feet, feet, b * 12 * 8, hipMemcpyDeviceToDevice, st));
+        // the wrench of solve 0: decay^k times the caller's estimate
+        if (const int rc = wrench_observer_launch(h, B, nullptr, nullptr, nullptr, nullptr, 12, nullptr, obs, w_est, f.ew, nullptr, true, st)) return rc;
+    }
     for (int32_t t = 0; t < T; ++t) {
         const size_t k = (size_t)t;
         if (const int rc = srbdqp_mpc_inputs_device_f64(h, B, x, feet, stamp, v_ref, standing, &cfg->gait, f.x_ref, f.foot, f.contact, f.pcom, f.landing, st)) return rc;
@@ -3071,6 +3152,14 @@ int srbdqp_fleet_rollout_device_f64(srbdqp_handle* h, int64_t B, int32_t T, doub
             c.plan = plan_solve(h, c, (int)B, maxs_or(h->cfg, 4));
             if (const int rc = solve_device_impl(h, c, (int32_t)B, x, f.x_ref, f.foot, f.contact, f.pcom, nullptr, nullptr, f.u, f.x_out, nullptr, f.status, f.iters, st))
                 return rc;
+        } else if (obs) {
+            // the solve a device-buffer call makes with the wrench buffer as the wrench of THIS call: the general kernel's _ew instantiation, which reads the handle's
+            // weights and robot records too -- every pass of it, deferred ones on the tail stream included, launches with this Call (solve_device_impl)
+            Call c;
+            c.use_hint = true; c.ext_call = f.ew;
+            c.plan = plan_solve(h, c, (int)B, maxs_or(h->cfg, 4));
+            if (const int rc = solve_device_impl(h, c, (int32_t)B, x, f.x_ref, f.foot, f.contact, f.pcom, nullptr, nullptr, f.u, f.x_out, nullptr, f.status, f.iters, st))
+                return rc;
         } else
         if (const int rc = srbdqp_solve_batch_device_f64(h, (int32_t)B, x, f.x_ref, f.foot, f.contact, f.pcom, nullptr, nullptr, f.u, f.x_out, nullptr, f.status,
                                                          f.iters, st)) return rc;
@@ -3079,10 +3168,32 @@ int srbdqp_fleet_rollout_device_f64(srbdqp_handle* h, int64_t B, int32_t T, doub
         lg.x = x_log ? x_log + (k + 1) * b * 13 : nullptr; lg.feet = feet_log ? feet_log + (k + 1) * b * 12 : nullptr; lg.u0 = u0_log ? u0_log + k * b * 12 : nullptr;
         lg.status = f.status; lg.iters = f.iters;
         lg.status_log = status_log ? status_log + k * b : nullptr; lg.iters_log = iters_log ? iters_log + k * b : nullptr;
+        // (observed, without the caller's logs: the state and the feet behind period t go to the ring's other slot)
+        const double *x_prev = nullptr, *feet_prev = nullptr;
+        if (obs) {
+            x_prev = x_log ? x_log + k * b * 13 : f.ring_x + (k & 1) * b * 13;
+            feet_prev = feet_log ? feet_log + k * b * 12 : f.ring_feet + (k & 1) * b * 12;
+            if (!x_log) lg.x = f.ring_x + ((k + 1) & 1) * b * 13;
+            if (!feet_log) lg.feet = f.ring_feet + ((k + 1) & 1) * b * 12;
+        }
         if (const int rc = fleet_advance_launch(h, B, x, feet, stamp, f.u, (int64_t)(12 * N), f.landing, standing, push ? push + k * b * 6 : nullptr, alive, cfg, lg, st))
+            return rc;
+        // the observer over period t: the estimate behind it, and the wrench solve t + 1 reads
+        if (obs) if (const int rc = wrench_observer_launch(h, B, x_prev, lg.x, feet_prev, f.u, (int64_t)(12 * N), alive, obs, w_est, f.ew, w_log ? w_log + k * b * 6 : nullptr, false, st))
             return rc;
     }
     return SRBDQP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int srbdqp_fleet_rollout_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
+                                    const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                    double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log, void* stream) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = fleet_rollout_check(h, B, T, x, feet, stamp, v_ref, cfg)) return rc;
+    return fleet_rollout_run(h, B, T, x, feet, stamp, v_ref, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log, nullptr, nullptr, nullptr, stream);
 }
 
 int srbdqp_fleet_rollout_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
@@ -3102,6 +3213,72 @@ int srbdqp_fleet_rollout_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, 
         dxl = io.out<double>(x_log, (steps + 1) * b * 13 * 8); dul = io.out<double>(u0_log, steps * b * 12 * 8); dfl = io.out<double>(feet_log, (steps + 1) * b * 12 * 8);
         dsl = io.out<int32_t>(status_log, steps * b * 4); dil = io.out<int32_t>(iters_log, steps * b * 4);
     }, [&](hipStream_t st) { return srbdqp_fleet_rollout_device_f64(h, B, T, dx, dfe, dst, dv, dsd, dpu, cfg, dal, dxl, dul, dfl, dsl, dil, st); });
+}
+
+// ---- the momentum observer (include/srbdqp_cascade.h) ----
+int srbdqp_observer_default_settings(srbdqp_observer_settings* s) {
+    if (!s || s->struct_size != (int32_t)sizeof(srbdqp_observer_settings)) return SRBDQP_E_INVALID;
+    std::memset(s, 0, sizeof(*s));
+    s->struct_size = (int32_t)sizeof(srbdqp_observer_settings);
+    s->gain = 0.5; s->horizon_decay = 1.0; s->torque_max = 50.0; s->force_max = 200.0;
+    return SRBDQP_OK;
+}
+
+int srbdqp_wrench_observer_device_f64(srbdqp_handle* h, int64_t B, const double* x_prev, const double* x_next, const double* feet_prev, const double* u0,
+                                      int64_t u0_stride, const uint8_t* alive, const srbdqp_observer_settings* cfg, double* w_est, double* ew_out,
+                                      void* stream) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = wrench_observer_check(h, B, x_prev, x_next, feet_prev, u0, u0_stride, cfg, w_est)) return rc;
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+    return wrench_observer_launch(h, B, x_prev, x_next, feet_prev, u0, u0_stride, alive, cfg, w_est, ew_out, nullptr, false, st);
+}
+
+int srbdqp_wrench_observer_f64(srbdqp_handle* h, int64_t B, const double* x_prev, const double* x_next, const double* feet_prev, const double* u0,
+                               int64_t u0_stride, const uint8_t* alive, const srbdqp_observer_settings* cfg, double* w_est, double* ew_out) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = wrench_observer_check(h, B, x_prev, x_next, feet_prev, u0, u0_stride, cfg, w_est)) return rc;
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
+    double *dx0, *dx1, *dfe, *du, *dw, *dew;
+    uint8_t* dal;
+    return host_call(h, [&](HostIo& io) {
+        dx0 = io.in<double>(x_prev, b * 13 * 8); dx1 = io.in<double>(x_next, b * 13 * 8); dfe = io.in<double>(feet_prev, b * 12 * 8);
+        du = io.in<double>(u0, ((b - 1) * (size_t)u0_stride + 12) * 8); dal = io.in<uint8_t>(alive, b);
+        dw = io.add<double>(w_est, w_est, b * 6 * 8, false); dew = io.out<double>(ew_out, b * N * 6 * 8);
+    }, [&](hipStream_t st) { return srbdqp_wrench_observer_device_f64(h, B, dx0, dx1, dfe, du, u0_stride, dal, cfg, dw, dew, st); });
+}
+
+int srbdqp_fleet_rollout_observed_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
+                                             const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                             double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                             const srbdqp_observer_settings* obs, double* w_est, double* w_log, void* stream) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = fleet_rollout_observed_check(h, B, T, x, feet, stamp, v_ref, cfg, obs, w_est)) return rc;
+    return fleet_rollout_run(h, B, T, x, feet, stamp, v_ref, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log, obs, w_est, w_log, stream);
+}
+
+int srbdqp_fleet_rollout_observed_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
+                                      const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                      double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                      const srbdqp_observer_settings* obs, double* w_est, double* w_log) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = fleet_rollout_observed_check(h, B, T, x, feet, stamp, v_ref, cfg, obs, w_est)) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)B, steps = (size_t)T;
+    double *dx, *dfe, *dst, *dv, *dpu, *dxl, *dul, *dfl, *dw, *dwl;
+    uint8_t *dsd, *dal;
+    int32_t *dsl, *dil;
+    return host_call(h, [&](HostIo& io) {
+        dx = io.add<double>(x, x, b * 13 * 8, false); dfe = io.add<double>(feet, feet, b * 12 * 8, false); dst = io.add<double>(stamp, stamp, b * 8, false);
+        dv = io.in<double>(v_ref, b * 2 * 8); dsd = io.in<uint8_t>(standing, b); dpu = io.in<double>(push, steps * b * 6 * 8);
+        dal = alive ? io.add<uint8_t>(alive, alive, b, false) : nullptr;
+        dxl = io.out<double>(x_log, (steps + 1) * b * 13 * 8); dul = io.out<double>(u0_log, steps * b * 12 * 8); dfl = io.out<double>(feet_log, (steps + 1) * b * 12 * 8);
+        dsl = io.out<int32_t>(status_log, steps * b * 4); dil = io.out<int32_t>(iters_log, steps * b * 4);
+        dw = io.add<double>(w_est, w_est, b * 6 * 8, false); dwl = io.out<double>(w_log, steps * b * 6 * 8);
+    }, [&](hipStream_t st) { return srbdqp_fleet_rollout_observed_device_f64(h, B, T, dx, dfe, dst, dv, dsd, dpu, cfg, dal, dxl, dul, dfl, dsl, dil, obs, dw, dwl, st); });
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 #include "srbdqp_wrench.hpp"
 #include "srbdqp_wrench_lat_ew.hpp"
 #include "srbdqp_fleet.hpp"
+#include "srbdqp_observer.hpp"
 
 namespace srbdqp {
 namespace {
@@ -80,6 +81,14 @@ hipError_t launch_fleet_advance(const FleetArgs& a, hipStream_t st, const Terrai
     const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
     if (map) hipLaunchKernelGGL((srbdqp_fleet_advance_kernel<kFleetTile, TerrainMap>), grid, dim3(kFleetTile), 0, st, a, *map);
     else hipLaunchKernelGGL(srbdqp_fleet_advance_kernel<kFleetTile>, grid, dim3(kFleetTile), 0, st, a);
+    return hipGetLastError();
+}
+
+// ... the momentum observer behind it (srbdqp_observer.hpp): the push a period's forces do not explain, as the external wrench of the next solve
+hipError_t launch_wrench_observer(const ObserverArgs& a, hipStream_t st) {
+    const long long tiles = (a.B + kObserverTile - 1) / kObserverTile;   // one tile of 64 robots per workgroup pass
+    const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
+    hipLaunchKernelGGL(srbdqp_wrench_observer_kernel<kObserverTile>, grid, dim3(kObserverTile), 0, st, a);
     return hipGetLastError();
 }
 

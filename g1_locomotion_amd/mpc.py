@@ -528,7 +528,49 @@ class BatchMPC(_Engine):
                                                        v(alive), C.byref(s), v(stream))
         self._check(rc)
 
-    def rollout(self, x0, feet, stamp, v_ref, steps, com_target, standing=None, push=None, alive=None, **settings):
+    # -- a fleet that feels its pushes: the momentum observer (include/srbdqp_cascade.h) -------------------------
+    def observer_settings(self, gain=0.5, horizon_decay=1.0, torque_max=50.0, force_max=200.0):
+        """srbdqp_observer_settings for wrench_observer() / rollout(observer=): the filter's gain in (0, 1], the estimate's decay along the horizon in
+        [0, 1], the clamps of its torque (N m) and force (N) components."""
+        s = _lib.ObserverSettings()
+        s.struct_size = C.sizeof(_lib.ObserverSettings)
+        s.gain, s.horizon_decay, s.torque_max, s.force_max = float(gain), float(horizon_decay), float(torque_max), float(force_max)
+        return s
+
+    def _observer_arg(self, observer):
+        """rollout()'s observer=: True (the defaults), a dict of observer_settings()' keywords, or an ObserverSettings."""
+        if isinstance(observer, _lib.ObserverSettings):
+            return observer
+        return self.observer_settings(**({} if observer is True else dict(observer)))
+
+    def wrench_observer(self, x_prev, x_next, feet_prev, u0, w_est, alive=None, want_ew=True, **settings):
+        """The momentum observer over one control period of B robots (srbdqp_wrench_observer_f64): from the states before and behind the period (B,13),
+        the contact points the forces acted at, feet_prev (B,12) or (B,4,3) -- the feet BEFORE any touchdown --, and the held first-step forces u0 (B,12),
+        the wrench on the body that the forces do not explain, filtered into w_est (B,6) ([torque about the CoM, force], world frame; not modified).
+        alive (B,) flags as they stand behind the period, or None: a robot that is down, or whose states are not finite, keeps its estimate.  Robot records
+        set on the engine (set_robots()) give robot b's own mass and inertia.  settings: observer_settings()' keywords.
+        Returns dict(w_est (B,6), ew (B,N,6) = w_est decay^k: set_external_wrench()'s argument for the next solve, or None without want_ew)."""
+        x0 = _c(x_prev, np.float64).reshape(-1, NX)
+        B = x0.shape[0]
+        x1 = _as(x_next, np.float64, (B, NX), "x_next")
+        f = _as(feet_prev, np.float64, (B, NU), "feet_prev")
+        u = _as(u0, np.float64, (B, NU), "u0")
+        al = None if alive is None else _as(np.asarray(alive) != 0, np.uint8, (B,), "alive")
+        w = np.array(w_est, dtype=np.float64).reshape(B, 6)
+        ew = np.empty((B, self.N, 6)) if want_ew else None
+        s = self.observer_settings(**settings)
+        self._check(self._lib.srbdqp_wrench_observer_f64(self._h, B, _p(x0), _p(x1), _p(f), _p(u), NU, _p(al), C.byref(s), _p(w), _p(ew)))
+        return dict(w_est=w, ew=ew)
+
+    def wrench_observer_device(self, B, x_prev, x_next, feet_prev, u0, w_est, ew=0, u0_stride=NU, alive=0, stream=0, **settings):
+        """Device-pointer form of wrench_observer(): raw addresses, w_est updated in place, ew (B,N,6) written where given, launch enqueued behind `stream`,
+        returns at once.  u0_stride: 12 N reads u_out[b][0] of a solve_device() in place."""
+        v = lambda q: C.c_void_p(int(q)) if q else None
+        s = self.observer_settings(**settings)
+        self._check(self._lib.srbdqp_wrench_observer_device_f64(self._h, int(B), v(x_prev), v(x_next), v(feet_prev), v(u0), int(u0_stride), v(alive),
+                                                                C.byref(s), v(w_est), v(ew), v(stream)))
+
+    def rollout(self, x0, feet, stamp, v_ref, steps, com_target, standing=None, push=None, alive=None, observer=None, w_est=None, **settings):
         """`steps` control steps of B robots on the device (srbdqp_fleet_rollout_f64): per step mpc_inputs -> the solve -> fleet_advance, without a host
         round trip in between.  x0 (B,13), feet (B,12) or (B,4,3), stamp (B,), v_ref (B,2) and standing (B,) flags or None (both constant over the call),
         push (steps,B,6) world wrenches or None, alive (B,) flags or None.  settings: fleet_settings()' keywords.  Robot records and weights set on the
@@ -537,6 +579,12 @@ class BatchMPC(_Engine):
         on the general kernel with those normals as the normals of the call -> the terrain plant step; robot records, weights, a wrench or normals set
         on the engine, a live horizon, rank-aware steps, N = 24 and a kernel= that bars the general kernel then raise SrbdqpError ("while a terrain is
         set").
+        observer=True or a dict of observer_settings()' keywords: the observed roll-out (srbdqp_fleet_rollout_observed_f64, flat ground): behind every
+        plant step the momentum observer estimates the push from what the plant did, and the next solve reads the estimate as its external wrench
+        (wrench_f64_n<N>_ew) -- the estimate of period t serves solve t + 1.  w_est (B,6): the estimate to start from (None: zeros); carried from one
+        call to the next, chunks compose bit for bit.  The result then has w_est (B,6) and w_log (steps,B,6), the estimate behind every period.
+        Contact normals, a wrench or a terrain set on the engine, a live horizon, rank-aware steps, N = 24 and a kernel= that bars the general kernel
+        raise SrbdqpError; robot records and weights are honoured.  observer=None is the call without an observer.
         Returns dict(x (steps+1,B,13), u0 (steps,B,12), feet (steps+1,B,12), status (steps,B), iters (steps,B), alive (B,) uint8, stamp (B,))."""
         x = np.array(x0, dtype=np.float64).reshape(-1, NX)
         B, T = x.shape[0], int(steps)
@@ -550,17 +598,37 @@ class BatchMPC(_Engine):
         n = max(T, 0)
         xl, ul, fl = np.empty((n + 1, B, NX)), np.empty((n, B, NU)), np.empty((n + 1, B, NU))
         sl, il = np.empty((n, B), np.int32), np.empty((n, B), np.int32)
+        if observer is not None and observer is not False:
+            o = self._observer_arg(observer)
+            w = np.zeros((B, 6)) if w_est is None else np.array(w_est, dtype=np.float64).reshape(B, 6)
+            wl = np.empty((n, B, 6))
+            rc = self._lib.srbdqp_fleet_rollout_observed_f64(self._h, B, T, _p(x), _p(f), _p(t), _p(v), _p(sd), _p(pu), C.byref(s), _p(al), _p(xl), _p(ul),
+                                                             _p(fl), _p(sl), _p(il), C.byref(o), _p(w), _p(wl))
+            self._check(rc)
+            return dict(x=xl, u0=ul, feet=fl, status=sl, iters=il, alive=al, stamp=t, w_est=w, w_log=wl)
+        if w_est is not None:
+            raise ValueError("rollout: w_est belongs to an observed roll-out (observer=)")
         rc = self._lib.srbdqp_fleet_rollout_f64(self._h, B, T, _p(x), _p(f), _p(t), _p(v), _p(sd), _p(pu), C.byref(s), _p(al), _p(xl), _p(ul), _p(fl),
                                                 _p(sl), _p(il))
         self._check(rc)
         return dict(x=xl, u0=ul, feet=fl, status=sl, iters=il, alive=al, stamp=t)
 
     def rollout_device(self, B, steps, x, feet, stamp, v_ref, com_target, standing=0, push=0, alive=0, x_log=0, u0_log=0, feet_log=0, status_log=0,
-                       iters_log=0, stream=0, **settings):
+                       iters_log=0, stream=0, observer=None, w_est=0, w_log=0, **settings):
         """Device-pointer form of rollout(): raw addresses (0 = absent), x / feet / stamp / alive updated in place, every launch enqueued behind `stream`
-        (0 = the engine's own), returns at once without synchronising.  Logs as in include/srbdqp_cascade.h."""
+        (0 = the engine's own), returns at once without synchronising.  Logs as in include/srbdqp_cascade.h.  observer= as in rollout(): w_est (B,6),
+        required then, is updated in place; w_log (steps,B,6) or 0."""
         v = lambda q: C.c_void_p(int(q)) if q else None
         s = self.fleet_settings(com_target, **settings)
+        if observer is not None and observer is not False:
+            o = self._observer_arg(observer)
+            rc = self._lib.srbdqp_fleet_rollout_observed_device_f64(self._h, int(B), int(steps), v(x), v(feet), v(stamp), v(v_ref), v(standing), v(push),
+                                                                    C.byref(s), v(alive), v(x_log), v(u0_log), v(feet_log), v(status_log), v(iters_log),
+                                                                    C.byref(o), v(w_est), v(w_log), v(stream))
+            self._check(rc)
+            return
+        if w_est or w_log:
+            raise ValueError("rollout_device: w_est and w_log belong to an observed roll-out (observer=)")
         rc = self._lib.srbdqp_fleet_rollout_device_f64(self._h, int(B), int(steps), v(x), v(feet), v(stamp), v(v_ref), v(standing), v(push), C.byref(s),
                                                        v(alive), v(x_log), v(u0_log), v(feet_log), v(status_log), v(iters_log), v(stream))
         self._check(rc)

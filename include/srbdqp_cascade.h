@@ -92,7 +92,7 @@ int srbdqp_mpc_inputs_device_f64(srbdqp_handle* h, int64_t B, const double* x0, 
  *                 written; the robot holds from the next period on.  A robot handed over with such a height or tilt has fallen already: it gets
  *                 this period like any other and alive = 0 behind it, wherever the period took it.
  * dt, and mass and inertia where the handle has no robot records (srbdqp_set_robots: robot b's own, as srbdqp_wbid_reference_* reads them): the handle's
- * config.  The MPC does not know the push. */
+ * config.  The MPC does not know the push (srbdqp_fleet_rollout_observed_* below estimates it from what the plant did). */
 typedef struct srbdqp_fleet_settings {
     int32_t struct_size;          /* = sizeof(srbdqp_fleet_settings) */
     int32_t substeps;             /* RK4 steps per control period (10) */
@@ -183,6 +183,64 @@ int srbdqp_fleet_rollout_device_f64(srbdqp_handle* h, int64_t B, int32_t T, doub
 int srbdqp_fleet_rollout_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
                              const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
                              double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log);
+
+/* ---- a fleet that feels its pushes: the momentum observer and the roll-out whose solves read it.
+ *
+ * The measurement over one control period, from the state before it x0, the state behind it x1, the contact points p_i the forces acted at (the feet BEFORE
+ * any touchdown), the held first-step forces f_i, mass m, body inertia I_b (robot b's record where srbdqp_set_robots is set, as in the plant step), the
+ * handle's dt and g = x0[12]:
+ *   f_meas   = m (v1 - v0) / dt - sum f_i - m g e_z
+ *   cbar     = c0 + dt (2 v0 + v1) / 6           (the mean CoM of a period of constant acceleration)
+ *   L(x)     = R(rpy) diag(I_b) R(rpy)' omega,   R = Rz Ry Rx as in the plant
+ *   tau_meas = (L(x1) - L(x0)) / dt - sum (p_i - cbar) x f_i
+ *   w_meas   = [tau_meas, f_meas]                (torque first, world frame, about the CoM: the layout of srbdqp_set_external_wrench)
+ * Under the library's own plant the forces are held, so v' is constant: f_meas and cbar are exact and tau_meas is exact up to the RK4 error (1e-6 N m at 10
+ * substeps); for a real robot it is the usual O(dt^2) momentum observer.
+ * The filter, in this order: w_est' = w_est + gain (w_meas - w_est); the torque components clamped to +-torque_max; the force components to +-force_max.
+ * The wrench of the next solve: ew[b][k] = w_est'_b decay^k, k = 0 ... N - 1, by repeated multiplication (s_0 = w_est', s_{k+1} = s_k decay).
+ * A robot keeps its w_est (ew is still written, from the kept value) when alive == 0 as it stands behind the period, or x0 or x1 has a non-finite entry. */
+typedef struct srbdqp_observer_settings {
+    int32_t struct_size;          /* = sizeof(srbdqp_observer_settings) */
+    int32_t reserved0;
+    double gain;                  /* of the first-order filter, in (0, 1] (0.5) */
+    double horizon_decay;         /* of the estimate along the horizon, in [0, 1] (1.0: the push is expected to last) */
+    double torque_max;            /* clamp of the torque components, N m: finite, positive, at most SRBDQP_EXT_WRENCH_MAX (50) */
+    double force_max;             /* clamp of the force components, N: the same rule (200) */
+} srbdqp_observer_settings;
+
+/* The defaults above into *s; s->struct_size says how large the caller's struct is (checked before anything is written). */
+int srbdqp_observer_default_settings(srbdqp_observer_settings* s);
+
+/* x_prev, x_next [B][13]; feet_prev [B][12]; u0: robot b's twelve doubles at u0 + b * u0_stride (u0_stride >= 12); alive [B] or NULL; w_est [B][6] in/out;
+ * ew_out [B][N][6] or NULL (N: the handle's horizon; at B = 1 the array srbdqp_update_wrench_f64 takes).  A wrong struct_size, gain outside (0, 1], decay
+ * outside [0, 1], a bound that is not finite, not positive or above SRBDQP_EXT_WRENCH_MAX: SRBDQP_E_INVALID before any launch -- so the kernel's own wrench
+ * check never fires on an observer's output.  srbdqp_kernel_name: wrench_observer_f64. */
+int srbdqp_wrench_observer_f64(srbdqp_handle* h, int64_t B, const double* x_prev, const double* x_next, const double* feet_prev, const double* u0,
+                               int64_t u0_stride, const uint8_t* alive, const srbdqp_observer_settings* cfg, double* w_est, double* ew_out);
+int srbdqp_wrench_observer_device_f64(srbdqp_handle* h, int64_t B, const double* x_prev, const double* x_next, const double* feet_prev, const double* u0,
+                                      int64_t u0_stride, const uint8_t* alive, const srbdqp_observer_settings* cfg, double* w_est, double* ew_out,
+                                      void* stream);
+
+/* srbdqp_fleet_rollout_* on flat ground whose solves read the observer's estimate.  Per step: srbdqp_mpc_inputs_device_f64 -> the fp64 batch solve on the
+ * general kernel with the handle's wrench buffer as the wrench of this call (wrench_f64_n<N>_ew, which reads the handle's weights and robot records too; every
+ * restart pass, deferred ones on the tail stream included, reads the same buffer) -> srbdqp_flush on a SRBDQP_FLAG_DEFER_TAIL handle -> the flat plant step ->
+ * the observer over the period that just ran, which writes the wrench of the next solve.  The solve of step t reads decay^k w_est as it stands before period
+ * t (at t = 0 the caller's): the estimate of period t serves solve t + 1.
+ *   obs: the observer's settings.  w_est [B][6] in/out, required.  w_log [T][B][6] or NULL: the estimate behind period t.  Everything else as in
+ *   srbdqp_fleet_rollout_*; chunks compose bit for bit with w_est carried by the caller.
+ * Refused (SRBDQP_E_INVALID before any launch): what srbdqp_fleet_rollout_* refuses; bad settings; w_est NULL; contact normals or a handle-level wrench set, a
+ * live horizon, rank-aware steps, N = 24, a srbdqp_config.kernel that bars the general kernel ("... in an observed roll-out"); a terrain set on the handle (no
+ * instantiation reads normals beside a wrench).  Robot records and weights are honoured.  The wrench buffer and a two-slot ring of states and footholds
+ * (used where the caller passes no x_log / feet_log) join the handle's roll-out allocation at the first observed roll-out.
+ * Not modelled: terrain, fp32, ragged fleets, the swing leg's inertia, a prediction of the push beyond the geometric decay. */
+int srbdqp_fleet_rollout_observed_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
+                                             const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                             double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                             const srbdqp_observer_settings* obs, double* w_est, double* w_log, void* stream);
+int srbdqp_fleet_rollout_observed_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
+                                      const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                      double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                      const srbdqp_observer_settings* obs, double* w_est, double* w_log);
 
 #ifdef __cplusplus
 }

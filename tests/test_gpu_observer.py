@@ -1,0 +1,378 @@
+"""GPU tests of the momentum observer and the observed roll-out (include/srbdqp_cascade.h srbdqp_wrench_observer_* / srbdqp_fleet_rollout_observed_*; DESIGN.md
+section 19) against the NumPy twin of tests/observer_twin.py (tests/test_observer_cpu.py holds the twin itself).
+
+Bounds.  The observer against the twin on the same arrays: 1e-10 -- the largest terms are m |v| / dt of about 900, a handful of roundings of them stay under
+1e-12, which leaves two orders for fused multiply-adds and the device's sin / cos.  Kept estimates and the horizon's products: bit for bit.  The plant: 1e-9, the
+bound of test_gpu_fleet.  Forces against the twin's solve: side_inputs.TOL_TWIN_N.  A known force push under gain 1: 1e-6 N (the formula is exact under the
+library's plant; measured 1e-13 on the twin)."""
+import numpy as np
+import pytest
+
+import c_oracle  # noqa: F401
+import cascade_oracle as co
+import fleet_twin as ft
+import observer_twin as ot
+import side_inputs as si
+import srbd_oracle as orc
+
+pytestmark = pytest.mark.gpu
+N, DT = 10, 0.04
+WIDE = dict(torque_max=1e5, force_max=1e5)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint64 if a.dtype == np.float64 else a.dtype)
+
+
+@pytest.fixture(scope="module")
+def eng():
+    """One engine on the general kernel: the blind roll-outs the observed ones are held against run the plain instantiation of the same kernel."""
+    import torch  # noqa: F401
+    from g1_locomotion_amd import BatchMPC, _lib
+    e = BatchMPC(horizon=N, kernel=_lib.KERNEL_WRENCH)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def arrays():
+    """77 robots (a tile of 64 and a remainder of 13): states before and behind a period with |v|, |omega| <= 1, the nominal footholds shifted a little, forces
+    from a twin solve of their QPs, estimates to start from.  Computed once, read-only."""
+    B = 77
+    rng = np.random.default_rng(19)
+    p = orc.default_params(N)
+
+    def states():
+        x = np.zeros((B, 13)); x[:, 3:6] = ft.COM + rng.normal(size=(B, 3)) * 0.01; x[:, 0:3] = rng.uniform(-0.3, 0.3, (B, 3))
+        x[:, 6:12] = rng.uniform(-1.0, 1.0, (B, 6)); x[:, 12] = -9.80665
+        return x
+    x0, x1 = states(), states()
+    feet = np.tile(ft.FEET.reshape(12), (B, 1)) + rng.normal(size=(B, 12)) * 0.01
+    xs = x0.copy(); xs[:, 6:12] *= 0.1; xs[:, 0:3] *= 0.1
+    inp = co.mpc_inputs(xs, feet, DT * rng.integers(0, 24, B).astype(np.float64), rng.uniform(-0.2, 0.3, (B, 2)), ft.COM, N, DT)
+    u0 = ft.solve(p, xs, inp, "c")["u0"]
+    assert np.abs(u0).max() > 100.0
+    w0 = rng.uniform(-1.0, 1.0, (B, 6)) * np.array([2.0, 2.0, 0.5, 30.0, 30.0, 30.0])
+    out = dict(x0=x0, x1=x1, feet=feet, u0=u0, w0=w0)
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+@pytest.mark.parametrize("horizon", [4, 10, 20])
+def test_the_kernel_against_the_twin(arrays, horizon):
+    """B = 77, N in {4, 10, 20}: w_est and ew within 1e-10 of the twin on the same arrays, kept rows bit for bit, ew the repeated product of the device's own w_est bit
+    for bit -- with the config's robot and with records, with alive (a dead robot, NaN rows) and without, ew wanted and not."""
+    from g1_locomotion_amd import BatchMPC
+    from g1_locomotion_amd.mpc import robots_array
+    a = arrays
+    B = a["x0"].shape[0]
+    rng = np.random.default_rng(horizon)
+    p = orc.default_params(horizon)
+    rec = robots_array(B, mass=rng.uniform(25.0, 45.0, B), inertia=np.array(p.inertia) * rng.uniform(0.7, 1.5, (B, 3)))
+    alive = np.ones(B, np.uint8); alive[[5, 70]] = 0
+    xa, xb = a["x0"].copy(), a["x1"].copy()
+    xa[9, 4] = np.nan; xb[66, 11] = np.inf; xb[76, 0] = np.nan
+    kept = [5, 9, 66, 70, 76]
+    cases = ((None, None, a["x0"], a["x1"], True, dict(WIDE)), (rec, alive, xa, xb, True, dict(horizon_decay=0.9)),
+             (rec, None, a["x0"], a["x1"], False, dict(gain=1.0, **WIDE)), (None, alive, xa, xb, True, dict(gain=0.3, horizon_decay=0.0)))
+    worst = 0.0
+    with BatchMPC(horizon=horizon) as e:
+        for robots, al, x0, x1, want_ew, st in cases:
+            want = ot.observe(p, x0, x1, a["feet"], a["u0"], a["w0"], horizon, alive=al, robots=robots, **st)
+            e.set_robots(robots)
+            try:
+                got = e.wrench_observer(x0, x1, a["feet"], a["u0"], a["w0"], alive=al, want_ew=want_ew, **st)
+            finally:
+                e.set_robots(None)
+            assert e.kernel_name() == "wrench_observer_f64"
+            err = np.abs(got["w_est"] - want["w_est"]).max()
+            worst = max(worst, err)
+            assert err < 1e-10, err
+            assert np.abs(want["w_est"]).max() > (150.0 if "force_max" in st else 1.0)
+            if al is not None:
+                assert np.array_equal(_bits(got["w_est"][kept]), _bits(a["w0"][kept]))
+                assert not np.any(np.all(got["w_est"] == a["w0"], axis=1)[[b for b in range(B) if b not in kept]])
+            if want_ew:
+                assert np.array_equal(_bits(got["ew"]), _bits(ot.horizon(got["w_est"], horizon, st.get("horizon_decay", 1.0))))
+                assert np.abs(got["ew"] - want["ew"]).max() < 1e-10
+            else:
+                assert got["ew"] is None
+    print("wrench_observer against the twin, N =", horizon, "worst |w_est - twin|", worst)
+
+
+def _crowd(B, seed, steps):
+    """B robots around the nominal stance: random commands, a few standing, stamps anywhere in the gait period, under a sustained push from step 2 on."""
+    rng = np.random.default_rng(seed)
+    x = np.zeros((B, 13)); x[:, 3:6] = ft.COM + rng.normal(size=(B, 3)) * 0.005; x[:, 0:2] = rng.normal(size=(B, 2)) * 0.02; x[:, 12] = -9.80665
+    feet = np.tile(ft.FEET.reshape(12), (B, 1))
+    stamp = DT * rng.integers(0, 24, B).astype(np.float64)
+    v_ref = np.where(rng.random((B, 1)) < 0.3, 0.0, rng.uniform(-0.2, 0.3, (B, 2)) * np.array([1.0, 0.4]))
+    standing = (rng.random(B) < 0.2).astype(np.uint8)
+    push = np.zeros((steps, B, 6))
+    push[2:] = rng.uniform(-1.0, 1.0, (1, B, 6)) * np.array([1.0, 1.0, 0.1, 20.0, 20.0, 5.0])
+    w0 = rng.uniform(-1.0, 1.0, (B, 6)) * np.array([0.5, 0.5, 0.05, 5.0, 5.0, 2.0])
+    return dict(x=x, feet=feet, stamp=stamp, v_ref=v_ref, standing=standing, push=push, w0=w0)
+
+
+OBS = dict(gain=0.5, horizon_decay=0.9)
+
+
+def _device_loop(eng, c, B, steps, defer):
+    """The observed roll-out call, and the same steps driven from here through the public device calls on the same engine -> two dicts of host arrays."""
+    import torch
+    dev = torch.device("cuda", 0)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    f64 = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device=dev)
+    alive0 = np.ones(B, np.uint8)
+    if B > 4:
+        alive0[3] = 0
+    out = []
+    for call in (True, False):
+        x, feet, stamp, v, sd, pu, al, w = up(c["x"]), up(c["feet"]), up(c["stamp"]), up(c["v_ref"]), up(c["standing"]), up(c["push"]), up(alive0), up(c["w0"])
+        if call:
+            xl, ul, fl, wl = f64(steps + 1, B, 13), f64(steps, B, 12), f64(steps + 1, B, 12), f64(steps, B, 6)
+            sl, il = torch.zeros((steps, B), dtype=torch.int32, device=dev), torch.zeros((steps, B), dtype=torch.int32, device=dev)
+            eng.rollout_device(B, steps, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, standing=sd.data_ptr(), push=pu.data_ptr(),
+                               alive=al.data_ptr(), x_log=xl.data_ptr(), u0_log=ul.data_ptr(), feet_log=fl.data_ptr(), status_log=sl.data_ptr(),
+                               iters_log=il.data_ptr(), observer=OBS, w_est=w.data_ptr(), w_log=wl.data_ptr())
+            eng.synchronize()
+            assert eng.kernel_name() == "wrench_observer_f64"
+            logs = dict(x_log=xl, u0_log=ul, feet_log=fl, status_log=sl, iters_log=il, w_log=wl)
+        else:
+            xr, fo, pc, lp = f64(B, N, 13), f64(B, N, 12), f64(B, N, 3), f64(B, 3)
+            ct = torch.zeros((B, N, 4), dtype=torch.uint8, device=dev)
+            u, xo = f64(B, N, 12), f64(B, N + 1, 13)
+            st, it = torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev)
+            ew = up(ot.horizon(c["w0"], N, OBS["horizon_decay"]))
+            eng.set_external_wrench(ew)                                 # (the device setter: read in place at every solve)
+            try:
+                xs, fs, us, ss, its, ws = [x.clone()], [feet.clone()], [], [], [], []
+                for k in range(steps):
+                    eng.mpc_inputs_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, xr.data_ptr(), fo.data_ptr(), ct.data_ptr(),
+                                          pc.data_ptr(), landing=lp.data_ptr(), standing=sd.data_ptr())
+                    eng.solve_device(B, x.data_ptr(), xr.data_ptr(), fo.data_ptr(), ct.data_ptr(), u.data_ptr(), x_out=xo.data_ptr(), status=st.data_ptr(),
+                                     iters=it.data_ptr(), pcom=pc.data_ptr())
+                    assert eng.kernel_name() == "wrench_f64_n10_ew"
+                    if defer:
+                        eng.flush()
+                    xp, fp = x.clone(), feet.clone()
+                    eng.fleet_advance_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), u.data_ptr(), lp.data_ptr(), u0_stride=12 * N,
+                                             standing=sd.data_ptr(), push=pu[k].data_ptr(), alive=al.data_ptr())
+                    eng.wrench_observer_device(B, xp.data_ptr(), x.data_ptr(), fp.data_ptr(), u.data_ptr(), w.data_ptr(), ew=ew.data_ptr(), u0_stride=12 * N,
+                                               alive=al.data_ptr(), **OBS)
+                    eng.synchronize()
+                    xs.append(x.clone()); fs.append(feet.clone()); us.append(u[:, 0].clone()); ss.append(st.clone()); its.append(it.clone()); ws.append(w.clone())
+            finally:
+                eng.synchronize()
+                eng.set_external_wrench(None)
+            logs = dict(x_log=torch.stack(xs), u0_log=torch.stack(us), feet_log=torch.stack(fs), status_log=torch.stack(ss), iters_log=torch.stack(its),
+                        w_log=torch.stack(ws))
+        logs.update(x=x, feet=feet, stamp=stamp, alive=al, w_est=w)
+        out.append({k: a.cpu().numpy() for k, a in logs.items()})
+    return out
+
+
+@pytest.mark.parametrize("B,defer", [(6, False), (70, False), (70, True)])
+def test_the_loop_is_the_public_calls(B, defer):
+    """rollout_device(observer=) over 8 steps against mpc_inputs_device -> set_external_wrench on the device buffer + solve_device -> flush (deferred tails) ->
+    fleet_advance_device -> wrench_observer_device driven step by step on the same engine: every log, w_log, w_est and every final array bit for bit."""
+    import torch  # noqa: F401
+    from g1_locomotion_amd import BatchMPC, _lib
+    steps = 8
+    c = _crowd(B, 60 + B, steps)
+    with BatchMPC(horizon=N, **(dict(flags=_lib.FLAG_DEFER_TAIL) if defer else {})) as e:
+        call, loop = _device_loop(e, c, B, steps, defer)
+    for k in call:
+        assert np.array_equal(_bits(call[k]), _bits(loop[k])), k
+    assert np.array_equal(_bits(call["w_log"][-1]), _bits(call["w_est"])) and (call["status_log"] == 1).mean() > 0.9
+    assert call["alive"][3] == 0 and np.array_equal(_bits(call["w_log"][:, 3]), _bits(np.tile(c["w0"][3], (steps, 1))))      # the robot handed in dead kept its estimate
+    live = call["alive"] == 1
+    assert np.abs(call["w_est"][live][:, 3:6] - c["push"][-1][live][:, 3:6]).max() < 0.5 * np.abs(c["w0"][live][:, 3:6] - c["push"][-1][live][:, 3:6]).max()
+
+
+def test_chunks_compose(eng):
+    """5 steps and 7 from where they ended, w_est carried = 12, bit for bit; the same 12 steps through the device call without logs -- the observer reads the ring --
+    end in the same x, feet and w_est."""
+    import torch
+    c = _crowd(21, 9, 12)
+    kw = dict(standing=c["standing"], observer=OBS)
+    a = eng.rollout(c["x"], c["feet"], c["stamp"], c["v_ref"], 5, ft.COM, push=c["push"][:5], w_est=c["w0"], **kw)
+    b = eng.rollout(a["x"][-1], a["feet"][-1], a["stamp"], c["v_ref"], 7, ft.COM, push=c["push"][5:], alive=a["alive"], w_est=a["w_est"], **kw)
+    w = eng.rollout(c["x"], c["feet"], c["stamp"], c["v_ref"], 12, ft.COM, push=c["push"], w_est=c["w0"], **kw)
+    for k in ("x", "feet"):
+        assert np.array_equal(_bits(np.concatenate([a[k], b[k][1:]])), _bits(w[k])), k
+    for k in ("u0", "status", "iters", "w_log"):
+        assert np.array_equal(_bits(np.concatenate([a[k], b[k]])), _bits(w[k])), k
+    assert np.array_equal(b["alive"], w["alive"]) and np.array_equal(_bits(b["stamp"]), _bits(w["stamp"])) and np.array_equal(_bits(b["w_est"]), _bits(w["w_est"]))
+    assert np.any(w["w_log"][-1] != w["w_log"][0])
+    dev = torch.device("cuda", 0)
+    up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
+    x, feet, stamp, v, sd, pu, we = up(c["x"]), up(c["feet"]), up(c["stamp"]), up(c["v_ref"]), up(c["standing"]), up(c["push"]), up(c["w0"])
+    eng.rollout_device(21, 12, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, standing=sd.data_ptr(), push=pu.data_ptr(), observer=OBS,
+                       w_est=we.data_ptr())
+    eng.synchronize()
+    assert np.array_equal(_bits(x.cpu().numpy()), _bits(w["x"][-1])) and np.array_equal(_bits(feet.cpu().numpy()), _bits(w["feet"][-1]))
+    assert np.array_equal(_bits(we.cpu().numpy()), _bits(w["w_est"]))
+
+
+def _stamps(stamp0, steps):
+    out = [np.asarray(stamp0, np.float64).copy()]
+    for _ in range(steps):
+        out.append(out[-1] + DT)
+    return np.array(out)
+
+
+def test_teacher_forced_parity(eng):
+    """24 steps of the 6-robot fleet under the sustained push, every step taken on its own from the engine's logs: the twin's observe gives w_log[t] within 1e-10, its
+    advance x_log[t + 1] within 1e-9 and the feet bit for bit, and its solve under w_log[t - 1] decay^k ends with the engine's status, forces within TOL_TWIN_N."""
+    steps, B = 24, 6
+    f = ft.fleet()
+    push = ot.sustained_push(steps, B)
+    g = eng.rollout(f["x"], f["feet"], f["stamp"], f["v_ref"], steps, ft.COM, standing=f["standing"], push=push, observer=OBS)
+    p = si.params(N)
+    stamps = _stamps(f["stamp"], steps)
+    dw = dx = du = 0.0
+    w_prev = np.zeros((B, 6))
+    alive = np.ones(B, np.uint8)
+    for t in range(steps):
+        x, feet = g["x"][t], g["feet"][t]
+        inp = co.mpc_inputs(x, feet, stamps[t], f["v_ref"], ft.COM, N, DT, standing=f["standing"])
+        sol = ot.solve(p, x, inp, ot.horizon(w_prev, N, OBS["horizon_decay"]))
+        assert np.array_equal(sol["status"], g["status"][t]), t
+        du = max(du, np.abs(sol["u0"] - g["u0"][t]).max())
+        nxt = ft.advance(p, x, feet, stamps[t], g["u0"][t], inp["landing"], standing=f["standing"], push=push[t], alive=alive)
+        dx = max(dx, np.abs(nxt["x"] - g["x"][t + 1]).max())
+        assert np.array_equal(_bits(nxt["feet"]), _bits(g["feet"][t + 1])), t
+        o = ot.observe(p, x, g["x"][t + 1], feet, g["u0"][t], w_prev, N, alive=nxt["alive"], **OBS)
+        dw = max(dw, np.abs(o["w_est"] - g["w_log"][t]).max())
+        w_prev, alive = g["w_log"][t], nxt["alive"]
+    print("teacher-forced: estimate", dw, "states", dx, "forces", du, "N")
+    assert g["alive"].tolist() == [1] * B and np.all(g["status"] == 1)
+    assert dw < 1e-10, dw
+    assert dx < 1e-9, dx
+    assert du < si.TOL_TWIN_N, du
+
+
+def test_the_benefit_on_the_device(eng):
+    """The scenario of tests/test_observer_cpu.py on the engine: every robot alive and every QP solved in the blind and in the observed roll-out, and on every robot
+    the observed one is below the blind one in lateral deviation from the unpushed roll-out at T and in the largest roll."""
+    T, B = 30, 6
+    f = ft.fleet()
+    push = ot.sustained_push(T, B)
+    args = (f["x"], f["feet"], f["stamp"], f["v_ref"], T, ft.COM)
+    free = eng.rollout(*args, standing=f["standing"])
+    blind = eng.rollout(*args, standing=f["standing"], push=push)
+    assert eng.kernel_name() == "fleet_advance_f64"
+    seen = eng.rollout(*args, standing=f["standing"], push=push, observer=True)
+    for r in (blind, seen):
+        assert r["alive"].tolist() == [1] * B and np.all(r["status"] == 1)
+    dev = lambda r: np.abs(r["x"][T, :, 4] - free["x"][T, :, 4])
+    roll = lambda r: np.abs(r["x"][:, :, 0]).max(axis=0)
+    print("device: lateral deviation blind", dev(blind).tolist(), "observed", dev(seen).tolist(), "largest roll blind", roll(blind).tolist(), "observed", roll(seen).tolist(),
+          "mean iterations", blind["iters"].mean(), seen["iters"].mean())
+    assert np.all(dev(seen) < dev(blind)) and np.all(roll(seen) < roll(blind))
+    assert np.abs(seen["w_est"][:, 3:6] - np.array([10.0, -25.0, 0.0])).max() < 1.0
+
+
+def test_with_robot_records_and_weights(eng):
+    """Records and weights set: the observed roll-out runs on wrench_f64_n10_ew, under gain 1 the estimate behind every pushed period is the constant force push within
+    1e-6 N -- by robot b's own mass --, and the handle's plain solves afterwards are what they were, bit for bit."""
+    from g1_locomotion_amd.mpc import robots_array, weights_array
+    T, B = 10, 6
+    f = ft.fleet()
+    rng = np.random.default_rng(23)
+    p = orc.default_params(N)
+    rec = robots_array(B, mass=p.mass * rng.uniform(0.8, 1.25, B), inertia=np.array(p.inertia) * rng.uniform(0.8, 1.25, (B, 3)))
+    wts = weights_array(B, q_diag=np.asarray(p.q_diag) * rng.uniform(0.7, 1.5, (B, 13)), r_diag=p.r_diag * rng.uniform(0.7, 1.5, B))
+    push = np.zeros((T, B, 6)); push[:, :, 3:6] = rng.uniform(-1.0, 1.0, (1, B, 3)) * np.array([12.0, 12.0, 5.0])
+    x0, xr, fo, ct = orc.synthetic_batch(B, N, seed=31, schedule="single")
+    eng.set_robots(rec); eng.set_weights(wts)
+    try:
+        before = eng.solve(x0, xr, fo, ct)
+        assert eng.kernel_name() == "wrench_f64_n10_wt"
+        g = eng.rollout(f["x"], f["feet"], f["stamp"], f["v_ref"], T, ft.COM, standing=f["standing"], push=push, observer=dict(gain=1.0))
+        after = eng.solve(x0, xr, fo, ct)
+    finally:
+        eng.set_robots(None); eng.set_weights(None)
+    for k in ("u", "x", "status", "iters"):
+        assert np.array_equal(_bits(after[k]), _bits(before[k])), k
+    assert g["alive"].tolist() == [1] * B and np.all(g["status"] == 1)
+    err = np.abs(g["w_log"][:, :, 3:6] - push[:, :, 3:6]).max()
+    print("known force push under gain 1 with robot records:", err, "N")
+    assert err < 1e-6, err
+    # (with the config's mass the same arithmetic misses the push by the weight that differs: the records were read)
+    wrong = np.array([ot.measure(p.mass, p.inertia, DT, g["x"][0, b], g["x"][1, b], g["feet"][0, b], g["u0"][0, b]) for b in range(B)])
+    assert np.abs(wrong[:, 3:6] - push[0, :, 3:6]).max() > 10.0
+
+
+def test_refusals_a_nan_robot_and_no_observer(eng):
+    import torch
+    from g1_locomotion_amd import BatchMPC, SrbdqpError, _lib
+    f = ft.fleet()
+    steps = 6
+    args = (f["x"], f["feet"], f["stamp"], f["v_ref"], steps, ft.COM)
+    # observer=None is the roll-out without one, bit for bit
+    base, none = eng.rollout(*args, standing=f["standing"]), eng.rollout(*args, standing=f["standing"], observer=None)
+    assert set(base) == set(none) and "w_est" not in none
+    for k in base:
+        assert np.array_equal(_bits(base[k]), _bits(none[k])), k
+    # bad settings, by the struct's name; nothing is launched
+    for bad in (dict(gain=0.0), dict(gain=1.5), dict(gain=float("nan")), dict(horizon_decay=-0.1), dict(horizon_decay=1.1), dict(torque_max=0.0),
+                dict(force_max=float("inf")), dict(force_max=2e6), dict(torque_max=-1.0)):
+        with pytest.raises(SrbdqpError, match="srbdqp_observer_settings"):
+            eng.rollout(*args, observer=bad)
+        with pytest.raises(SrbdqpError, match="srbdqp_observer_settings"):
+            eng.wrench_observer(f["x"], f["x"], f["feet"], np.zeros((6, 12)), np.zeros((6, 6)), **bad)
+    short = eng.observer_settings(); short.struct_size = 32
+    with pytest.raises(SrbdqpError, match="struct_size"):
+        eng.rollout(*args, observer=short)
+    with pytest.raises(SrbdqpError, match="srbdqp_fleet_settings"):
+        eng.rollout(*args, observer=True, substeps=0)
+    with pytest.raises(SrbdqpError):
+        eng.rollout(f["x"], f["feet"], f["stamp"], f["v_ref"], 0, ft.COM, observer=True)
+    # w_est NULL, on the device call; nothing written
+    dev = torch.device("cuda", 0)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    x, feet, stamp, v = up(f["x"]), up(f["feet"]), up(f["stamp"]), up(f["v_ref"])
+    xl = torch.full((steps + 1, 6, 13), -7.0, dtype=torch.float64, device=dev)
+    with pytest.raises(SrbdqpError, match="w_est is NULL"):
+        eng.rollout_device(6, steps, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, x_log=xl.data_ptr(), observer=True)
+    eng.synchronize()
+    assert torch.all(xl == -7.0) and np.array_equal(x.cpu().numpy(), f["x"]) and np.array_equal(stamp.cpu().numpy(), f["stamp"])
+    # the handle's state: the refusal table's words, and where
+    for setter, value in (("set_external_wrench", np.full((6, N, 6), 0.5)), ("set_contact_normals", np.tile([0.0, 0.0, 1.0], (6, N, 4)))):
+        getattr(eng, setter)(value)
+        try:
+            with pytest.raises(SrbdqpError, match="srbdqp_" + setter + ".*in an observed roll-out"):
+                eng.rollout(*args, observer=True)
+        finally:
+            getattr(eng, setter)(None)
+    eng.set_terrain(np.zeros((4, 4)), origin=(-1.0, -1.0), cell=1.0)
+    try:
+        with pytest.raises(SrbdqpError, match="srbdqp_fleet_rollout_observed.*srbdqp_set_terrain"):
+            eng.rollout(*args, observer=True)
+    finally:
+        eng.set_terrain(None)
+    for kw, what in ((dict(rank_aware=True), "SRBDQP_FLAG_RANK_AWARE.*in an observed roll-out"), (dict(horizon=9), "SRBDQP_FLAG_ANY_HORIZON.*in an observed roll-out"),
+                     (dict(horizon=24), "N = 24.*in an observed roll-out"), (dict(kernel=_lib.KERNEL_COMPACT), "general kernel only.*in an observed roll-out")):
+        with BatchMPC(**dict(dict(horizon=N), **kw)) as e:
+            with pytest.raises(SrbdqpError, match=what):
+                e.rollout(*args, observer=True)
+    # fewer records than robots
+    from g1_locomotion_amd.mpc import robots_array
+    eng.set_robots(robots_array(4))
+    try:
+        with pytest.raises(SrbdqpError, match="4 robot records"):
+            eng.rollout(*args, observer=True)
+    finally:
+        eng.set_robots(None)
+    # a NaN in x0: dead at once, its estimate kept at every step; the others go on and find their push
+    g = {k: a.copy() for k, a in f.items()}
+    g["x"][4, 7] = np.nan
+    w0 = np.full((6, 6), 1.5)
+    r = eng.rollout(g["x"], g["feet"], g["stamp"], g["v_ref"], steps, ft.COM, standing=g["standing"], push=ot.sustained_push(steps, 6, start=0), observer=True, w_est=w0)
+    assert r["alive"].tolist() == [1, 1, 1, 1, 0, 1]
+    assert np.array_equal(_bits(r["w_log"][:, 4]), _bits(np.tile(w0[4], (steps, 1)))) and np.array_equal(_bits(r["w_est"][4]), _bits(w0[4]))
+    keep = [0, 1, 2, 3, 5]
+    assert np.abs(r["w_est"][keep][:, 3:6] - np.array([10.0, -25.0, 0.0])).max() < 1.0

@@ -10,7 +10,11 @@
 roll-out on a SRBDQP_KERNEL_WRENCH handle, the solve family a terrain roll-out runs: the difference between the two is the cost of the terrain; the default flat
 roll-out beside them gives the cost of leaving the one-wave kernel.
 
-    python tools/fleet_rollout_bench.py [--robots 4096] [--steps 100] [--reps 5] [--terrain] [--kernel auto|wrench] [--out profiles/<name>.json]
+--observer: the observed roll-out -- the solves on wrench_f64_n10_ew under the momentum observer's estimate, one observer launch behind
+every plant step --, the Python loop with the observer and the wrench buffer in it (set_external_wrench on the device buffer, once), and the observer alone: time
+per launch and GB/s.  Beside --kernel wrench in the same job: the cost of observing.
+
+    python tools/fleet_rollout_bench.py [--robots 4096] [--steps 100] [--reps 5] [--terrain] [--observer] [--kernel auto|wrench] [--out profiles/<name>.json]
 """
 import argparse
 import hashlib
@@ -28,6 +32,8 @@ FEET = np.array([[0.0, 0.0645, 0.0], [0.17, 0.0645, 0.0], [0.0, -0.0645, 0.0], [
 COM = np.array([0.085, 0.0, 0.598])
 # bytes the plant step must move per robot: x, feet, u0, landing, stamp, push in; x, stamp out (a foothold is stored at a touchdown only: one period in six)
 ADVANCE_BYTES = (13 + 12 + 12 + 3 + 1 + 6 + 13 + 1) * 8
+# ... and the observer, beside the N 6 doubles of the horizon's wrench: two states, feet, u0, w_est in; w_est out
+OBSERVER_BYTES = (13 + 13 + 12 + 12 + 6 + 6) * 8
 
 
 def main():
@@ -36,9 +42,12 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--terrain", action="store_true")
+    ap.add_argument("--observer", action="store_true")
     ap.add_argument("--kernel", choices=("auto", "wrench"), default="auto")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.terrain and a.observer:
+        ap.error("--observer is flat ground: no roll-out reads normals beside a wrench")
     import torch
     from g1_locomotion_amd import BatchMPC, _lib
     B, T, N, dt = a.robots, a.steps, 10, 0.04
@@ -61,8 +70,10 @@ def main():
     xr, fo, pc, lp, u, xo = f64(B, N, 13), f64(B, N, 12), f64(B, N, 3), f64(B, 3), f64(B, N, 12), f64(B, N + 1, 13)
     ct = torch.empty((B, N, 4), dtype=torch.uint8, device=dev)
     st, it = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
-    res = dict(robots=B, steps=T, horizon=N, reps=a.reps, terrain=bool(a.terrain), kernel_setting=a.kernel)
+    res = dict(robots=B, steps=T, horizon=N, reps=a.reps, terrain=bool(a.terrain), observer=bool(a.observer), kernel_setting=a.kernel)
     cn = f64(B, N, 12) if a.terrain else None
+    we, wl, ew = (f64(B, 6), f64(T, B, 6), f64(B, N, 6)) if a.observer else (None, None, None)
+    obs = dict(observer=True, w_est=we.data_ptr(), w_log=wl.data_ptr()) if a.observer else {}
     with BatchMPC(horizon=N, dt=dt, kernel=_lib.KERNEL_WRENCH if a.kernel == "wrench" else _lib.KERNEL_AUTO) as eng:
         if a.terrain:
             gx, gy = -4.0 + 0.1 * np.arange(81), -4.0 + 0.1 * np.arange(81)
@@ -77,16 +88,22 @@ def main():
 
         def call():
             x, feet, stamp, al = fresh()
+            if a.observer:
+                we.zero_()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             eng.rollout_device(B, T, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), d_v.data_ptr(), COM, push=d_pu.data_ptr(), alive=al.data_ptr(),
-                               x_log=xl.data_ptr(), u0_log=ul.data_ptr(), feet_log=fl.data_ptr(), status_log=sl.data_ptr(), iters_log=il.data_ptr())
+                               x_log=xl.data_ptr(), u0_log=ul.data_ptr(), feet_log=fl.data_ptr(), status_log=sl.data_ptr(), iters_log=il.data_ptr(), **obs)
             t1 = time.perf_counter()
             eng.synchronize()
             return time.perf_counter() - t0, t1 - t0, al
 
         def loop():
             x, feet, stamp, al = fresh()
+            if a.observer:
+                we.zero_(); ew.zero_()
+                xp, fp = torch.empty_like(x), torch.empty_like(feet)
+                eng.set_external_wrench(ew)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for k in range(T):
@@ -97,12 +114,20 @@ def main():
                     eng.set_contact_normals(cn)
                 eng.solve_device(B, x.data_ptr(), xr.data_ptr(), fo.data_ptr(), ct.data_ptr(), u.data_ptr(), x_out=xo.data_ptr(), status=st.data_ptr(),
                                  iters=it.data_ptr(), pcom=pc.data_ptr())
+                if a.observer:                                            # (the state and the feet before the period: what a user without logs has to keep)
+                    xp.copy_(x); fp.copy_(feet)
                 eng.fleet_advance_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), u.data_ptr(), lp.data_ptr(), u0_stride=12 * N,
                                          push=d_pu[k].data_ptr(), alive=al.data_ptr())
+                if a.observer:
+                    eng.wrench_observer_device(B, xp.data_ptr(), x.data_ptr(), fp.data_ptr(), u.data_ptr(), we.data_ptr(), ew=ew.data_ptr(), u0_stride=12 * N,
+                                               alive=al.data_ptr())
                 eng.synchronize()
+            dt_loop = time.perf_counter() - t0
             if a.terrain:
                 eng.set_contact_normals(None)
-            return time.perf_counter() - t0
+            if a.observer:
+                eng.set_external_wrench(None)
+            return dt_loop
 
         def advance_alone():
             x, feet, stamp, al = fresh()
@@ -130,6 +155,17 @@ def main():
             t_in = (time.perf_counter() - t0) / T
             res["terrain_inputs_us_per_launch"] = t_in * 1e6
             res["terrain_inputs_gb_per_s"] = B * (12 + 2 * N * 13 + N * 12) * 8 / t_in / 1e9
+        if a.observer:                                                    # the observer alone, on the logs of the last roll-out
+            eng.wrench_observer_device(B, xl[0].data_ptr(), xl[1].data_ptr(), fl[0].data_ptr(), ul[0].data_ptr(), we.data_ptr(), ew=ew.data_ptr()); eng.synchronize()
+            t0 = time.perf_counter()
+            for k in range(T):
+                eng.wrench_observer_device(B, xl[k].data_ptr(), xl[k + 1].data_ptr(), fl[k].data_ptr(), ul[k].data_ptr(), we.data_ptr(), ew=ew.data_ptr())
+            eng.synchronize()
+            t_ob = (time.perf_counter() - t0) / T
+            res["observer_us_per_launch"] = t_ob * 1e6
+            res["observer_gb_per_s"] = B * (OBSERVER_BYTES + N * 6 * 8) / t_ob / 1e9
+            res["observer_share_of_a_rollout_step"] = t_ob / (t_call / T)
+            res["w_est_force_rms_N"] = float(wl[:, :, 3:6].pow(2).mean().sqrt().item())
         res["rollout_call_s"] = t_call
         res["rollout_enqueue_s"] = float(np.median([c[1] for c in calls]))
         res["rollout_robot_steps_per_s"] = B * T / t_call
