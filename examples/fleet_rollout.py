@@ -1,12 +1,14 @@
 """256 walking robots under random commands and random pushes for 100 control steps, in one call (BatchMPC.rollout):
 prints the share of the fleet still on its feet and how well it follows the commanded velocity.
 
-    python examples/fleet_rollout.py [--robots 256] [--steps 100] [--seed 0] [--slope 0.2] [--observer]
+    python examples/fleet_rollout.py [--robots 256] [--steps 100] [--seed 0] [--slope 0.2] [--observer] [--yaw-rate 0.5]
 
 --slope s: the same fleet on the plane z = s x (BatchMPC.set_terrain): the friction pyramids tilt with the ground, a foot lands on it,
 and "fallen" is the height over it.
 --observer: on flat ground, a push of 10 N along x and -25 N along y on every robot during steps 5 to 29, once blind and once with the momentum observer
 (BatchMPC.rollout(observer=True)): prints how far the push carried the fleet sideways in either run.
+--yaw-rate W: a fleet that steers (BatchMPC.rollout(command=)) -- every robot walks a circle under (vx, 0, W), vx up to 0.3 m/s in its
+own heading frame, the feet landing turned with it: prints the commanded heading W T dt against the heading reached.  With --slope the circle lies on the plane.
 """
 import argparse
 import os
@@ -27,9 +29,12 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--slope", type=float, default=0.0)
     ap.add_argument("--observer", action="store_true")
+    ap.add_argument("--yaw-rate", type=float, default=0.0)
     a = ap.parse_args()
     if a.observer and a.slope:
         ap.error("--observer is flat ground")
+    if a.observer and a.yaw_rate:
+        ap.error("--observer and --yaw-rate: one at a time here (BatchMPC.rollout takes both)")
     from g1_locomotion_amd import BatchMPC
     rng = np.random.default_rng(a.seed)
     B, T, dt = a.robots, a.steps, 0.04
@@ -61,10 +66,20 @@ def main():
                       f"largest roll {np.abs(q['x'][:, up, 0]).max():.3f} rad, {q['iters'].mean():.1f} iterations per QP")
             k = min(29, T - 1)
             print(f"the estimate behind step {k}: force {r['w_log'][k][:, 3:6].mean(0).round(2).tolist()} N (applied: [10.0, -25.0, 0.0])")
+        elif a.yaw_rate:
+            command = np.stack([np.abs(v_ref[:, 0]), np.zeros(B), np.full(B, a.yaw_rate)], axis=1)
+            r = eng.rollout(x0, feet, stamp, None, T, COM, push=push, command=command)
         else:
             r = eng.rollout(x0, feet, stamp, v_ref, T, COM, push=push)
     r["x"][:, :, 5] -= ground(r["x"][:, :, 3:5])                         # heights below are over the ground
     alive = r["alive"] != 0
+    if a.yaw_rate:
+        print(f"{B} robots, {T} steps: {alive.mean():.1%} alive, solved {np.mean(r['status'] == 1):.2%} of {r['status'].size} QPs at {r['iters'].mean():.1f} iterations")
+        if alive.any():
+            yaw, speed = r["x"][-1, alive, 2], np.linalg.norm(r["x"][-1, alive, 9:11], axis=1)
+            print(f"heading commanded {a.yaw_rate * T * dt:.3f} rad, reached {yaw.mean():.3f} rad on average ({yaw.min():.3f} to {yaw.max():.3f}); "
+                  f"speed commanded {command[alive, 0].mean():.3f} m/s on average, at the end {speed.mean():.3f} m/s (lowest CoM {r['x'][:, alive, 5].min():.3f} m)")
+        return
     half = T // 2                                                        # the mean velocity over the second half of the roll-out, robots still up
     v = (r["x"][-1, :, 3:5] - r["x"][half, :, 3:5]) / ((T - half) * dt)
     err = np.linalg.norm(v - v_ref, axis=1)

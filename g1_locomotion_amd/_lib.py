@@ -182,6 +182,9 @@ _ROLLOUT = [H, _i64, _i32, dp, dp, dp, dp, u8p, dp, _FLEET, u8p, dp, dp, dp, i32
 _OBS = C.POINTER(ObserverSettings)
 _OBSERVER = [H, _i64, dp, dp, dp, dp, _i64, u8p, _OBS, dp, dp]            # B, x_prev, x_next, feet_prev, u0, u0_stride, alive, settings, w_est, ew_out
 _ROLLOUT_OBS = _ROLLOUT + [_OBS, dp, dp]                                  # ... the observer's settings, w_est, w_log
+_INPUTS_STEER = _INPUTS + [dp]                                            # (command in v_ref's place) ..., landing_yaw
+_ADVANCE_STEER = _ADVANCE[:8] + [dp] + _ADVANCE[8:]                       # ..., landing, landing_yaw, standing, push, alive, settings
+_ROLLOUT_STEER = _ROLLOUT_OBS[:7] + [_i32] + _ROLLOUT_OBS[7:]             # ..., command, command_steps, standing, ...
 SIGNATURES = {
     # include/srbdqp.h -- config, handle
     "srbdqp_default_config": (_int, [_CFG]),
@@ -264,6 +267,13 @@ SIGNATURES = {
     "srbdqp_wrench_observer_device_f64": (_int, _OBSERVER + [_vp]),
     "srbdqp_fleet_rollout_observed_device_f64": (_int, _ROLLOUT_OBS + [_vp]),
     "srbdqp_fleet_rollout_observed_f64": (_int, _ROLLOUT_OBS),
+    # ... that steers: inputs under (vx, vy, wz) commands, the plant step with turned footholds, the roll-out of the two
+    "srbdqp_mpc_inputs_steered_f64": (_int, _INPUTS_STEER),
+    "srbdqp_mpc_inputs_steered_device_f64": (_int, _INPUTS_STEER + [_vp]),
+    "srbdqp_fleet_advance_steered_f64": (_int, _ADVANCE_STEER),
+    "srbdqp_fleet_advance_steered_device_f64": (_int, _ADVANCE_STEER + [_vp]),
+    "srbdqp_fleet_rollout_steered_device_f64": (_int, _ROLLOUT_STEER + [_vp]),
+    "srbdqp_fleet_rollout_steered_f64": (_int, _ROLLOUT_STEER),
 }
 EXPORTS = tuple(SIGNATURES)
 

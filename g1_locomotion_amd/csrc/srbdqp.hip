@@ -164,6 +164,9 @@ struct srbdqp_handle {
         // [2][B][13] and footholds [2][B][12] the observer reads where the caller keeps no logs
         bool observed = false;
         double *ew = nullptr, *ring_x = nullptr, *ring_feet = nullptr;
+        // carved once a steered roll-out has asked (steered): the heading every robot's next foot lands with, [B] (srbdqp_mpc_inputs_steered_* writes it)
+        bool steered = false;
+        double* landing_yaw = nullptr;
     } fleet;
     // the ground under the fleet (srbdqp_set_terrain, include/srbdqp_cascade.h): the library's device copy of the height map; map.h null: flat ground
     struct Terrain {
@@ -2847,7 +2850,8 @@ struct FleetLogs {
 
 // one launch of the plant step; the arguments have been checked
 int fleet_advance_launch(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride, const double* landing,
-                         const uint8_t* standing, const double* push, uint8_t* alive, const srbdqp_fleet_settings* cfg, const FleetLogs& lg, hipStream_t st) {
+                         const uint8_t* standing, const double* push, uint8_t* alive, const srbdqp_fleet_settings* cfg, const FleetLogs& lg, hipStream_t st,
+                         const double* landing_yaw = nullptr) {
     srbdqp::FleetArgs a;
     std::memset(&a, 0, sizeof(a));
     a.x = x; a.feet = feet; a.stamp = stamp; a.u0 = u0; a.u0_stride = (long long)u0_stride; a.landing = landing; a.standing = standing; a.push = push;
@@ -2861,8 +2865,8 @@ int fleet_advance_launch(srbdqp_handle* h, int64_t B, double* x, double* feet, d
     a.substeps = cfg->substeps; a.period = cfg->gait.period_steps; a.ds = cfg->gait.double_support_steps;
     a.B = (long long)B;
     const srbdqp::TerrainMap* map = h->terrain.map.h ? &h->terrain.map : nullptr;   // a map set: the terrain instantiation over it
-    HIP_TRY(h, srbdqp::launch_fleet_advance(a, st, map));
-    h->kname = map ? "fleet_advance_terrain_f64" : "fleet_advance_f64";
+    HIP_TRY(h, srbdqp::launch_fleet_advance(a, st, map, landing_yaw));   // landing_yaw: the steered instantiation, feet turned by it
+    h->kname = landing_yaw ? (map ? "fleet_advance_terrain_steered_f64" : "fleet_advance_steered_f64") : (map ? "fleet_advance_terrain_f64" : "fleet_advance_f64");
     return SRBDQP_OK;
 }
 
@@ -2874,12 +2878,45 @@ int fleet_advance_check(srbdqp_handle* h, int64_t B, const void* x, const void* 
     return covers<RobotsIn>(h, B, "srbdqp_fleet_advance: ", " robots with ", false, false);
 }
 
+// ---- a fleet that steers (include/srbdqp_cascade.h; the kernel: srbdqp_steer.hpp) ----
+// a call refused before its handle is looked at leaves its reason where srbdqp_last_error(NULL) reads it
+int steer_refuse(srbdqp_handle* h, const std::string& why) { (h ? h->err : g_create_err) = why; return SRBDQP_E_INVALID; }
+
+// the first entry of a HOST array of commands that is not finite, or -1
+long long steer_non_finite(const double* command, size_t count) {
+    for (size_t i = 0; i < count; ++i) if (!std::isfinite(command[i])) return (long long)i;
+    return -1;
+}
+
+int steer_gait_check(srbdqp_handle* h, const srbdqp_gait* gait) {
+    if (!gait || gait->struct_size != (int32_t)sizeof(srbdqp_gait) || gait->period_steps < 1 || gait->double_support_steps < 0 ||
+        gait->double_support_steps > gait->period_steps) { h->err = "invalid srbdqp_gait (struct_size, 1 <= period_steps, 0 <= double_support_steps <= period_steps)"; return SRBDQP_E_INVALID; }
+    return SRBDQP_OK;
+}
+
+// one launch of the steered inputs; the arguments have been checked
+int mpc_inputs_steered_launch(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command, const uint8_t* standing,
+                              const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, double* landing_yaw, hipStream_t st) {
+    srbdqp::SteerInputsArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.x0 = x0; a.feet = feet; a.stamp = stamp; a.command = command; a.standing = standing;
+    a.x_ref = x_ref; a.foot = foot; a.contact = contact; a.pcom = pcom; a.landing = landing; a.landing_yaw = landing_yaw;
+    for (int i = 0; i < 3; ++i) a.com_target[i] = gait->com_target[i];
+    a.hip_offset_y = gait->hip_offset_y; a.dt = h->cfg.dt;
+    a.N = h->cfg.horizon; a.period = gait->period_steps; a.ds = gait->double_support_steps;
+    a.B = (long long)B;
+    HIP_TRY(h, srbdqp::launch_mpc_inputs_steered(a, h->live_nstar != 0, st));
+    h->kname = "mpc_inputs_steered_f64";
+    return SRBDQP_OK;
+}
+
 // the horizon buffers of a roll-out, at B robots, carved from one allocation of the handle's
-int ensure_fleet_buffers(srbdqp_handle* h, size_t B, bool observed = false) {
+int ensure_fleet_buffers(srbdqp_handle* h, size_t B, bool observed = false, bool steered = false) {
     auto& f = h->fleet;
     const bool terrain = h->terrain.map.h != nullptr;
-    if (f.mem && f.B >= B && (!terrain || f.normals) && (!observed || f.ew)) return SRBDQP_OK;
+    if (f.mem && f.B >= B && (!terrain || f.normals) && (!observed || f.ew) && (!steered || f.landing_yaw)) return SRBDQP_OK;
     f.observed = f.observed || observed;
+    f.steered = f.steered || steered;
     const size_t N = (size_t)h->cfg.horizon;
     auto carve = [&](char* base) {
         Carver c(base);
@@ -2889,6 +2926,7 @@ int ensure_fleet_buffers(srbdqp_handle* h, size_t B, bool observed = false) {
         f.normals = terrain ? c.take<double>(B * N * 12) : nullptr;
         f.ew = f.observed ? c.take<double>(B * N * 6) : nullptr;
         f.ring_x = f.observed ? c.take<double>(2 * B * 13) : nullptr; f.ring_feet = f.observed ? c.take<double>(2 * B * 12) : nullptr;
+        f.landing_yaw = f.steered ? c.take<double>(B) : nullptr;
         return c.off;
     };
     const size_t want = carve(nullptr);
@@ -3120,14 +3158,16 @@ int srbdqp_fleet_advance_f64(srbdqp_handle* h, int64_t B, double* x, double* fee
 
 namespace {
 // the K-step loop behind its entry points' checks.  obs: the observed roll-out (flat ground) -- the solves read the handle's wrench buffer, which the
-// observer behind every plant step writes; null: the roll-out of section 17 / 18, launch for launch what it was
+// observer behind every plant step writes; null: the roll-out of section 17 / 18, launch for launch what it was.  command: the steered roll-out (section 20),
+// v_ref unused -- [B][3] held (command_steps 1) or [T][B][3]; null: v_ref, launch for launch what it was
 int fleet_rollout_run(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
                       const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
                       double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
-                      const srbdqp_observer_settings* obs, double* w_est, double* w_log, void* stream) {
+                      const srbdqp_observer_settings* obs, double* w_est, double* w_log, void* stream,
+                      const double* command = nullptr, int32_t command_steps = 1) {
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
-    if (const int rc = ensure_fleet_buffers(h, b, obs != nullptr)) return rc;
+    if (const int rc = ensure_fleet_buffers(h, b, obs != nullptr, command != nullptr)) return rc;
     const auto& f = h->fleet;
     const bool terrain = h->terrain.map.h != nullptr;
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
@@ -3142,6 +3182,11 @@ int fleet_rollout_run(srbdqp_handle* h, int64_t B, int32_t T, double* x, double*
     }
     for (int32_t t = 0; t < T; ++t) {
         const size_t k = (size_t)t;
+        // command: the steered roll-out (section 20) -- row t of a schedule, or the one command held -- whose inputs also say how the next foot lands turned
+        if (command) {
+            if (const int rc = mpc_inputs_steered_launch(h, B, x, feet, stamp, command + (command_steps == 1 ? 0 : k * b * 3), standing, &cfg->gait, f.x_ref, f.foot, f.contact,
+                                                         f.pcom, f.landing, f.landing_yaw, st)) return rc;
+        } else
         if (const int rc = srbdqp_mpc_inputs_device_f64(h, B, x, feet, stamp, v_ref, standing, &cfg->gait, f.x_ref, f.foot, f.contact, f.pcom, f.landing, st)) return rc;
         if (terrain) {
             // the ground under the footholds: the normals of this step's QPs and the height reference, then the solve a device-buffer call makes with those normals
@@ -3176,7 +3221,8 @@ int fleet_rollout_run(srbdqp_handle* h, int64_t B, int32_t T, double* x, double*
             if (!x_log) lg.x = f.ring_x + ((k + 1) & 1) * b * 13;
             if (!feet_log) lg.feet = f.ring_feet + ((k + 1) & 1) * b * 12;
         }
-        if (const int rc = fleet_advance_launch(h, B, x, feet, stamp, f.u, (int64_t)(12 * N), f.landing, standing, push ? push + k * b * 6 : nullptr, alive, cfg, lg, st))
+        if (const int rc = fleet_advance_launch(h, B, x, feet, stamp, f.u, (int64_t)(12 * N), f.landing, standing, push ? push + k * b * 6 : nullptr, alive, cfg, lg, st,
+                                                command ? f.landing_yaw : nullptr))
             return rc;
         // the observer over period t: the estimate behind it, and the wrench solve t + 1 reads
         if (obs) if (const int rc = wrench_observer_launch(h, B, x_prev, lg.x, feet_prev, f.u, (int64_t)(12 * N), alive, obs, w_est, f.ew, w_log ? w_log + k * b * 6 : nullptr, false, st))
@@ -3279,6 +3325,123 @@ int srbdqp_fleet_rollout_observed_f64(srbdqp_handle* h, int64_t B, int32_t T, do
         dsl = io.out<int32_t>(status_log, steps * b * 4); dil = io.out<int32_t>(iters_log, steps * b * 4);
         dw = io.add<double>(w_est, w_est, b * 6 * 8, false); dwl = io.out<double>(w_log, steps * b * 6 * 8);
     }, [&](hipStream_t st) { return srbdqp_fleet_rollout_observed_device_f64(h, B, T, dx, dfe, dst, dv, dsd, dpu, cfg, dal, dxl, dul, dfl, dsl, dil, obs, dw, dwl, st); });
+}
+
+// ---- a fleet that steers (include/srbdqp_cascade.h) ----
+int srbdqp_mpc_inputs_steered_device_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
+                                         const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
+                                         double* landing, double* landing_yaw, void* stream) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (B < 0 || B > 0x7fffffffLL || (B > 0 && (!x0 || !feet || !stamp || !command || !x_ref || !foot || !contact || !pcom))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const int rc = steer_gait_check(h, gait)) return rc;
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+    return mpc_inputs_steered_launch(h, B, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw, st);
+}
+
+int srbdqp_mpc_inputs_steered_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
+                                  const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
+                                  double* landing, double* landing_yaw) {
+    // (the command is the caller's host array: it is read before the handle is)
+    if (B > 0 && B <= 0x7fffffffLL && command) {
+        const long long i = steer_non_finite(command, (size_t)B * 3);
+        if (i >= 0) return steer_refuse(h, "srbdqp_mpc_inputs_steered: the command of robot " + std::to_string(i / 3) + " is not finite (component " + std::to_string(i % 3) + " of vx, vy, wz)");
+    }
+    if (!h) return SRBDQP_E_INVALID;
+    if (B < 0 || B > 0x7fffffffLL || (B > 0 && (!x0 || !feet || !stamp || !command || !x_ref || !foot || !contact || !pcom))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const int rc = steer_gait_check(h, gait)) return rc;
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
+    double *dx0, *dfe, *dst, *dc, *dxr, *dft, *dpc, *dlp, *dly;
+    uint8_t *dsd, *dct;
+    return host_call(h, [&](HostIo& io) {
+        dx0 = io.in<double>(x0, b * 13 * 8); dfe = io.in<double>(feet, b * 12 * 8); dst = io.in<double>(stamp, b * 8); dc = io.in<double>(command, b * 24);
+        dsd = io.in<uint8_t>(standing, b);
+        dxr = io.out<double>(x_ref, b * N * 13 * 8); dft = io.out<double>(foot, b * N * 12 * 8); dct = io.out<uint8_t>(contact, b * N * 4);
+        dpc = io.out<double>(pcom, b * N * 3 * 8); dlp = io.out<double>(landing, b * 3 * 8); dly = io.out<double>(landing_yaw, b * 8);
+    }, [&](hipStream_t st) { return srbdqp_mpc_inputs_steered_device_f64(h, B, dx0, dfe, dst, dc, dsd, gait, dxr, dft, dct, dpc, dlp, dly, st); });
+}
+
+int srbdqp_fleet_advance_steered_device_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
+                                            const double* landing, const double* landing_yaw, const uint8_t* standing, const double* push, uint8_t* alive,
+                                            const srbdqp_fleet_settings* cfg, void* stream) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = fleet_advance_check(h, B, x, feet, stamp, u0, u0_stride, landing, cfg)) return rc;
+    if (B > 0 && !landing_yaw) { h->err = "srbdqp_fleet_advance_steered: landing_yaw is NULL (srbdqp_mpc_inputs_steered_* writes it; srbdqp_fleet_advance_* lands feet unturned)"; return SRBDQP_E_INVALID; }
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+    return fleet_advance_launch(h, B, x, feet, stamp, u0, u0_stride, landing, standing, push, alive, cfg, FleetLogs{}, st, landing_yaw);
+}
+
+int srbdqp_fleet_advance_steered_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
+                                     const double* landing, const double* landing_yaw, const uint8_t* standing, const double* push, uint8_t* alive,
+                                     const srbdqp_fleet_settings* cfg) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (const int rc = fleet_advance_check(h, B, x, feet, stamp, u0, u0_stride, landing, cfg)) return rc;
+    if (B > 0 && !landing_yaw) { h->err = "srbdqp_fleet_advance_steered: landing_yaw is NULL (srbdqp_mpc_inputs_steered_* writes it; srbdqp_fleet_advance_* lands feet unturned)"; return SRBDQP_E_INVALID; }
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)B;
+    double *dx, *dfe, *dst, *du, *dlp, *dly, *dpu;
+    uint8_t *dsd, *dal;
+    return host_call(h, [&](HostIo& io) {
+        dx = io.add<double>(x, x, b * 13 * 8, false); dfe = io.add<double>(feet, feet, b * 12 * 8, false); dst = io.add<double>(stamp, stamp, b * 8, false);
+        du = io.in<double>(u0, ((b - 1) * (size_t)u0_stride + 12) * 8); dlp = io.in<double>(landing, b * 3 * 8); dly = io.in<double>(landing_yaw, b * 8);
+        dsd = io.in<uint8_t>(standing, b); dpu = io.in<double>(push, b * 6 * 8);
+        dal = alive ? io.add<uint8_t>(alive, alive, b, false) : nullptr;
+    }, [&](hipStream_t st) { return srbdqp_fleet_advance_steered_device_f64(h, B, dx, dfe, dst, du, u0_stride, dlp, dly, dsd, dpu, dal, cfg, st); });
+}
+
+}  // extern "C"
+
+namespace {
+// May this handle run a steered roll-out?  The command's own rules, which need no handle and come first (host: the command is the caller's host array, and
+// every entry of it must be finite); then what the roll-out it becomes refuses
+int fleet_rollout_steered_check(srbdqp_handle* h, int64_t B, int32_t T, const void* x, const void* feet, const void* stamp, const double* command, int32_t command_steps,
+                                const srbdqp_fleet_settings* cfg, const srbdqp_observer_settings* obs, const void* w_est, bool host) {
+    if (!command) return steer_refuse(h, "srbdqp_fleet_rollout_steered: command is NULL ([B][3] held over the call, or [T][B][3] with command_steps = T)");
+    if (command_steps != 1 && command_steps != T) return steer_refuse(h, "srbdqp_fleet_rollout_steered: command_steps must be 1 (one command held) or T (a row per step)");
+    if (host && B >= 1 && B <= 0x7fffffffLL && T >= 1) {
+        const long long i = steer_non_finite(command, (size_t)command_steps * (size_t)B * 3);
+        if (i >= 0) return steer_refuse(h, "srbdqp_fleet_rollout_steered: the command of robot " + std::to_string((i / 3) % B) + " at row " + std::to_string(i / (3 * B)) + " is not finite");
+    }
+    if (!h) return SRBDQP_E_INVALID;
+    return obs ? fleet_rollout_observed_check(h, B, T, x, feet, stamp, command, cfg, obs, w_est) : fleet_rollout_check(h, B, T, x, feet, stamp, command, cfg);
+}
+}  // namespace
+
+extern "C" {
+
+int srbdqp_fleet_rollout_steered_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
+                                            int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                            double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                            const srbdqp_observer_settings* obs, double* w_est, double* w_log, void* stream) {
+    if (const int rc = fleet_rollout_steered_check(h, B, T, x, feet, stamp, command, command_steps, cfg, obs, w_est, false)) return rc;
+    return fleet_rollout_run(h, B, T, x, feet, stamp, nullptr, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log, obs, obs ? w_est : nullptr,
+                             obs ? w_log : nullptr, stream, command, command_steps);
+}
+
+int srbdqp_fleet_rollout_steered_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
+                                     int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                     double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                     const srbdqp_observer_settings* obs, double* w_est, double* w_log) {
+    if (const int rc = fleet_rollout_steered_check(h, B, T, x, feet, stamp, command, command_steps, cfg, obs, w_est, true)) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)B, steps = (size_t)T;
+    double *dx, *dfe, *dst, *dc, *dpu, *dxl, *dul, *dfl, *dw = nullptr, *dwl = nullptr;
+    uint8_t *dsd, *dal;
+    int32_t *dsl, *dil;
+    return host_call(h, [&](HostIo& io) {
+        dx = io.add<double>(x, x, b * 13 * 8, false); dfe = io.add<double>(feet, feet, b * 12 * 8, false); dst = io.add<double>(stamp, stamp, b * 8, false);
+        dc = io.in<double>(command, (size_t)command_steps * b * 3 * 8); dsd = io.in<uint8_t>(standing, b); dpu = io.in<double>(push, steps * b * 6 * 8);
+        dal = alive ? io.add<uint8_t>(alive, alive, b, false) : nullptr;
+        dxl = io.out<double>(x_log, (steps + 1) * b * 13 * 8); dul = io.out<double>(u0_log, steps * b * 12 * 8); dfl = io.out<double>(feet_log, (steps + 1) * b * 12 * 8);
+        dsl = io.out<int32_t>(status_log, steps * b * 4); dil = io.out<int32_t>(iters_log, steps * b * 4);
+        if (obs) { dw = io.add<double>(w_est, w_est, b * 6 * 8, false); dwl = io.out<double>(w_log, steps * b * 6 * 8); }
+    }, [&](hipStream_t st) { return srbdqp_fleet_rollout_steered_device_f64(h, B, T, dx, dfe, dst, dc, command_steps, dsd, dpu, cfg, dal, dxl, dul, dfl, dsl, dil, obs, dw, dwl, st); });
 }
 
 }  // extern "C"

@@ -8,7 +8,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "srbdqp_gait.hpp"
+#include "srbdqp_steer.hpp"
 #include "srbdqp_terrain.hpp"
 
 namespace srbdqp {
@@ -38,8 +41,9 @@ struct FleetArgs {
     long long B;
 };
 
-// the launch of srbdqp_fleet_advance_kernel on st (srbdqp_wrench_lat_ew.hip); map: the terrain instantiation over it (null: flat ground)
-hipError_t launch_fleet_advance(const FleetArgs& a, hipStream_t st, const TerrainMap* map = nullptr);
+// the launch of srbdqp_fleet_advance_kernel on st (srbdqp_wrench_lat_ew.hip); map: the terrain instantiation over it (null: flat ground); landing_yaw [B]: the
+// steered instantiation, heel and toe turned by it (null: along the world's x axis)
+hipError_t launch_fleet_advance(const FleetArgs& a, hipStream_t st, const TerrainMap* map = nullptr, const double* landing_yaw = nullptr);
 
 constexpr int kFleetTile = 64;   // robots per workgroup pass = its threads: one wave, one robot per lane
 constexpr int kFleetRow = 13;    // LDS row of every staged array, in doubles: odd, so that a lane per row walks all banks
@@ -120,24 +124,35 @@ __host__ __device__ __forceinline__ void fleet_plant(const FleetBody& q, double 
 // A robot that is skipped keeps its rows, in memory (nothing of it is stored) and in the logs (which record what it holds).
 //
 // fleet_height: the height of the point (x, y, z) over the ground under it, what "fallen" compares with z_min; fleet_ground: the ground's height at (x, y), where a
-// foot lands -- without a map z itself and the landing point's own z (`flat`).  m: the map, or nothing
-template <class... MAP>
-__device__ __forceinline__ double fleet_height(double x, double y, double z, const MAP&... m) {
-    if constexpr (sizeof...(MAP) > 0) { double zg, n[3]; terrain_sample(m..., x, y, zg, n); return z - zg; }
-    else return z;
-}
-template <class... MAP>
-__device__ __forceinline__ double fleet_ground(double x, double y, double flat, const MAP&... m) {
-    if constexpr (sizeof...(MAP) > 0) { double zg, n[3]; terrain_sample(m..., x, y, zg, n); return zg; }
-    else return flat;
-}
+// foot lands -- without a map z itself and the landing point's own z (`flat`).  ext: the kernel's extras, of which a TerrainMap is the map and a FleetSteer
+// (below) is passed over
+struct FleetSteer { const double* landing_yaw; };   // [B]: psi_L of srbdqp_mpc_inputs_steered_*, the heading a foot lands with
+
+__device__ __forceinline__ double fleet_height(double, double, double z) { return z; }
+template <class... REST>
+__device__ __forceinline__ double fleet_height(double x, double y, double z, const TerrainMap& m, const REST&...) { double zg, n[3]; terrain_sample(m, x, y, zg, n); return z - zg; }
+template <class... REST>
+__device__ __forceinline__ double fleet_height(double x, double y, double z, const FleetSteer&, const REST&... rest) { return fleet_height(x, y, z, rest...); }
+__device__ __forceinline__ double fleet_ground(double, double, double flat) { return flat; }
+template <class... REST>
+__device__ __forceinline__ double fleet_ground(double x, double y, double, const TerrainMap& m, const REST&...) { double zg, n[3]; terrain_sample(m, x, y, zg, n); return zg; }
+template <class... REST>
+__device__ __forceinline__ double fleet_ground(double x, double y, double flat, const FleetSteer&, const REST&... rest) { return fleet_ground(x, y, flat, rest...); }
+// the heading of the touchdown among the extras, or null: feet along the world's x axis
+__device__ __forceinline__ const double* fleet_landing_yaw() { return nullptr; }
+template <class... REST>
+__device__ __forceinline__ const double* fleet_landing_yaw(const FleetSteer& s, const REST&...) { return s.landing_yaw; }
+template <class... REST>
+__device__ __forceinline__ const double* fleet_landing_yaw(const TerrainMap&, const REST&... rest) { return fleet_landing_yaw(rest...); }
 
 // MAP: nothing -- flat ground, the kernel of DESIGN.md section 17, whose text this parameter leaves what it was -- or one TerrainMap, the terrain instantiation
 // (section 18): the ground is the map instead of the plane z = 0.  Two places differ: a foot that touches down stands at S(own xy).z, heel and toe each, and both
-// "fallen" tests compare the CoM's height OVER the ground under it, x[5] - S(com xy).z, with z_min.
+// "fallen" tests compare the CoM's height OVER the ground under it, x[5] - S(com xy).z, with z_min.  A FleetSteer behind it (or alone): the steered instantiations
+// (section 20), in which heel and toe lie along the heading landing_yaw[b] -- steer_touchdown -- where the others lay them along the world's x axis.
 template <int TILE, class... MAP>
 __global__ __launch_bounds__(TILE) void srbdqp_fleet_advance_kernel(FleetArgs a, MAP... map) {
-    static_assert(sizeof...(MAP) <= 1, "at most one map");
+    static_assert(sizeof...(MAP) <= 2, "at most one map and one FleetSteer");
+    constexpr bool STEER = (std::is_same<MAP, FleetSteer>::value || ...);
     constexpr int RW = kFleetRow;
     __shared__ double sx[TILE * RW], sft[TILE * RW], su[TILE * RW], slp[TILE * 3], spu[TILE * 6];
     __shared__ uint8_t swx[TILE], swf[TILE];      // robot r's state / footholds changed: store them
@@ -202,8 +217,15 @@ __global__ __launch_bounds__(TILE) void srbdqp_fleet_advance_kernel(FleetArgs a,
                 if (left || right) {
                     const int c0 = left ? 0 : 6;                                   // contacts 0, 1 (left heel, toe) or 2, 3
                     const double lx = slp[3 * t], ly = slp[3 * t + 1], lz = slp[3 * t + 2];
-                    sft[RW * t + c0] = lx - a.foot_half_length; sft[RW * t + c0 + 1] = ly; sft[RW * t + c0 + 2] = fleet_ground(lx - a.foot_half_length, ly, lz, map...);
-                    sft[RW * t + c0 + 3] = lx + a.foot_half_length; sft[RW * t + c0 + 4] = ly; sft[RW * t + c0 + 5] = fleet_ground(lx + a.foot_half_length, ly, lz, map...);
+                    if constexpr (STEER) {
+                        double heel[2], toe[2];
+                        steer_touchdown(lx, ly, a.foot_half_length, fleet_landing_yaw(map...)[b], heel, toe);
+                        sft[RW * t + c0] = heel[0]; sft[RW * t + c0 + 1] = heel[1]; sft[RW * t + c0 + 2] = fleet_ground(heel[0], heel[1], lz, map...);
+                        sft[RW * t + c0 + 3] = toe[0]; sft[RW * t + c0 + 4] = toe[1]; sft[RW * t + c0 + 5] = fleet_ground(toe[0], toe[1], lz, map...);
+                    } else {
+                        sft[RW * t + c0] = lx - a.foot_half_length; sft[RW * t + c0 + 1] = ly; sft[RW * t + c0 + 2] = fleet_ground(lx - a.foot_half_length, ly, lz, map...);
+                        sft[RW * t + c0 + 3] = lx + a.foot_half_length; sft[RW * t + c0 + 4] = ly; sft[RW * t + c0 + 5] = fleet_ground(lx + a.foot_half_length, ly, lz, map...);
+                    }
                     wf = true;
                 }
                 // 5. fallen: it holds from the next period on

@@ -1,0 +1,193 @@
+// A fleet that steers (include/srbdqp_cascade.h, srbdqp_mpc_inputs_steered_*): the step before the QP under a command (vx, vy, wz) --
+// planar velocity in the robot's heading frame and a yaw rate -- in place of a velocity fixed in the world.  The references turn with the commanded heading,
+// the landing point's hip offset turns with the heading at mid-swing, psi_L, and the plant step (srbdqp_fleet.hpp) turns heel and toe by the same psi_L.
+//
+// steer_rotate, steer_yaw, steer_table and steer_touchdown are __host__ __device__ and need nothing of HIP: a host compiler builds them from this header alone
+// (tests/test_steer_cpu.py does, against tests/steer_twin.py).  The kernel below them is a template so that it is emitted only where it is instantiated: in
+// srbdqp_wrench_lat_ew.hip, the library's second code object, as the fleet's kernels are; srbdqp.hip sees SteerInputsArgs and the launcher.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#include "srbdqp_gait.hpp"
+#define SRBDQP_STEER_HD __host__ __device__ __forceinline__
+#else
+#define SRBDQP_STEER_HD inline
+#endif
+
+namespace srbdqp {
+
+constexpr int kSteerSteps = 25;   // table entries of one robot: k = 0 ... N, N <= 24
+
+// every product and sum below is one rounded operation, in the order written (no fused multiply-add: the twin is NumPy)
+
+// v_w(theta) = Rz(theta) (vx, vy)
+SRBDQP_STEER_HD void steer_rotate(double theta, double vx, double vy, double& wx, double& wy) {
+#pragma clang fp contract(off)
+    const double s = sin(theta), c = cos(theta);
+    wx = c * vx - s * vy;
+    wy = s * vx + c * vy;
+}
+
+// psi0 + wz (k dt) for a whole or a half step index k, as (wz k) dt
+SRBDQP_STEER_HD double steer_yaw(double psi0, double wz, double k, double dt) {
+#pragma clang fp contract(off)
+    return psi0 + (wz * k) * dt;
+}
+
+// The reference table of one robot, entries k = 0 ... N:  p[k] = p_k, the reference position -- p_0 = (px0, py0), p_{k+1} = p_k + v_w(psi0 + wz (k + 1/2) dt) dt,
+// a serial sum with the heading at the middle of the step -- and v[k] = v_w(psi0 + wz k dt).  The trip count is N whatever the command holds: a command that is
+// not finite gives entries that are not numbers, nothing else.  (The kernel computes the same entries spread over a tile's threads.)
+SRBDQP_STEER_HD void steer_table(double psi0, double px0, double py0, double vx, double vy, double wz, double dt, int N, double* px, double* py, double* vwx,
+                                 double* vwy) {
+#pragma clang fp contract(off)
+    px[0] = px0; py[0] = py0;
+    for (int k = 0; k <= N; ++k) {
+        steer_rotate(steer_yaw(psi0, wz, (double)k, dt), vx, vy, vwx[k], vwy[k]);
+        if (k < N) {
+            double mx, my;
+            steer_rotate(steer_yaw(psi0, wz, (double)k + 0.5, dt), vx, vy, mx, my);
+            px[k + 1] = px[k] + mx * dt; py[k + 1] = py[k] + my * dt;
+        }
+    }
+}
+
+// the touchdown of a turned foot: heel = landing - half (cos psi, sin psi), toe = landing + half (cos psi, sin psi), in the plane
+SRBDQP_STEER_HD void steer_touchdown(double lx, double ly, double half, double psi, double (&heel)[2], double (&toe)[2]) {
+#pragma clang fp contract(off)
+    const double hx = half * cos(psi), hy = half * sin(psi);
+    heel[0] = lx - hx; heel[1] = ly - hy;
+    toe[0] = lx + hx; toe[1] = ly + hy;
+}
+
+// the landing point under a command: the hip offset turned by psi_L, the heading at mid-swing; vw0 = v_w(psi0); side: -1 the left foot stands, +1 the right
+SRBDQP_STEER_HD void steer_landing(const double* x0, double psi_l, double side, double hip_offset_y, double half_T, double vw0x, double vw0y, double& lx, double& ly) {
+#pragma clang fp contract(off)
+    const double s = sin(psi_l), c = cos(psi_l), o = side * hip_offset_y;
+    lx = ((x0[3] + (0.0 - s * o)) + half_T * x0[9]) + 0.03 * (x0[9] - vw0x);
+    ly = ((x0[4] + c * o) + half_T * x0[10]) + 0.03 * (x0[10] - vw0y);
+}
+
+struct SteerInputsArgs {
+    const double* x0;        // [B][13]
+    const double* feet;      // [B][12]
+    const double* stamp;     // [B]
+    const double* command;   // [B][3]  (vx, vy, wz)
+    const uint8_t* standing; // [B] or null
+    double* x_ref;           // [B][N][13]
+    double* foot;            // [B][N][12]
+    uint8_t* contact;        // [B][N][4]
+    double* pcom;            // [B][N][3]
+    double* landing;         // [B][3] or null
+    double* landing_yaw;     // [B] or null
+    double com_target[3];
+    double hip_offset_y, dt;
+    int32_t N, period, ds;
+    long long B;
+};
+
+#if defined(__HIPCC__)
+// the launch of srbdqp_mpc_inputs_steered_kernel on st (srbdqp_wrench_lat_ew.hip); live: a.N at run time (SRBDQP_FLAG_ANY_HORIZON)
+hipError_t launch_mpc_inputs_steered(const SteerInputsArgs& a, bool live, hipStream_t st);
+
+// srbdqp_mpc_inputs_kernel's tiling (srbdqp_cascade.hpp): a workgroup takes tiles of 32 consecutive robots, their 13 + 12 + 3 input doubles each staged in LDS
+// with coalesced loads, the tile's outputs written element by element, 512 contiguous bytes per store instruction of a wave.  Between the two, the tile's
+// reference table (steer_table's entries): a thread per (robot, k) takes the two sines and cosines of its entry -- the heading at step k and at k + 1/2 --, then
+// a thread per (robot, axis) sums the N increments in order.  The element loops read the table and take no sine.
+template <int NH>   // the horizon as a compile-time constant (NH = 0: a.N at run time)
+__global__ __launch_bounds__(256) void srbdqp_mpc_inputs_steered_kernel(SteerInputsArgs a) {
+#pragma clang fp contract(off)
+    constexpr int R = 32, K = kSteerSteps;
+    const int N = NH > 0 ? NH : a.N;
+    __shared__ double sx0[R * 13], sft[R * 12], sc[R * 3];
+    __shared__ double spx[R * K], spy[R * K], svx[R * K], svy[R * K];     // p_k and v_w(psi0 + wz k dt), k = 0 ... N
+    __shared__ int sph[R];                                               // phase of step 0 in [0, 2 period), or -1 = standing
+    const int t = threadIdx.x;
+    const long long tiles = (a.B + R - 1) / R;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long b0 = tile * R;
+        const int nr = (int)((a.B - b0 < R) ? (a.B - b0) : R);
+        for (int i = t; i < nr * 13; i += 256) sx0[i] = a.x0[b0 * 13 + i];
+        for (int i = t; i < nr * 12; i += 256) sft[i] = a.feet[b0 * 12 + i];
+        for (int i = t; i < nr * 3; i += 256) sc[i] = a.command[b0 * 3 + i];
+        if (t < nr) {
+            const bool stand = a.standing && a.standing[b0 + t];
+            sph[t] = stand ? -1 : gait_phase0(a.stamp[b0 + t], a.dt, a.period);
+        }
+        __syncthreads();
+        for (int e = t; e < nr * (N + 1); e += 256) {                    // the table's sines and cosines: entry (r, k)
+            const int r = e / (N + 1), k = e - (N + 1) * r;
+            const double psi0 = sx0[13 * r + 2], vx = sc[3 * r], vy = sc[3 * r + 1], wz = sc[3 * r + 2];
+            double wx, wy;
+            steer_rotate(steer_yaw(psi0, wz, (double)k, a.dt), vx, vy, wx, wy);
+            svx[K * r + k] = wx; svy[K * r + k] = wy;
+            if (k < N) {                                                 // the increment of step k, where p_{k+1} will stand
+                steer_rotate(steer_yaw(psi0, wz, (double)k + 0.5, a.dt), vx, vy, wx, wy);
+                spx[K * r + k + 1] = wx * a.dt; spy[K * r + k + 1] = wy * a.dt;
+            }
+        }
+        __syncthreads();
+        if (t < nr * 2) {                                                // the serial sums, one (robot, axis) each
+            const int r = t >> 1, c = t & 1;
+            double* p = (c ? spy : spx) + K * r;
+            double acc = sx0[13 * r + 3 + c];
+            p[0] = acc;
+            for (int k = 1; k <= N; ++k) { acc = acc + p[k]; p[k] = acc; }
+        }
+        __syncthreads();
+        auto flags = [&](int r, int k, bool& cl, bool& cr) { gait_flags(sph[r], k, a.period, a.ds, cl, cr); };
+        double* xr = a.x_ref + b0 * (N * 13);
+        for (int e = t; e < nr * N * 13; e += 256) {                     // x_ref[r][k][c], reference index k + 1
+            const int row = e / 13, c = e - 13 * row, r = row / N, k = row - N * r;
+            const double* x0 = sx0 + 13 * r;
+            const double vx = sc[3 * r], vy = sc[3 * r + 1], wz = sc[3 * r + 2];
+            const bool moving = (vx != 0.0) || (vy != 0.0);
+            double v = 0.0;
+            if (c == 2) v = steer_yaw(x0[2], wz, (double)(k + 1), a.dt);
+            else if (c == 3) v = moving ? spx[K * r + k + 1] : a.com_target[0];
+            else if (c == 4) v = moving ? spy[K * r + k + 1] : a.com_target[1];
+            else if (c == 5) v = a.com_target[2];
+            else if (c == 8) v = wz;
+            else if (c == 9) v = svx[K * r + k + 1];
+            else if (c == 10) v = svy[K * r + k + 1];
+            else if (c == 12) v = x0[12];
+            xr[e] = v;
+        }
+        double* fo = a.foot + b0 * (N * 12);
+        for (int e = t; e < nr * N * 12; e += 256) {                     // foot[r][k][c]: the current contact points, repeated
+            const int row = e / 12, c = e - 12 * row, r = row / N;
+            fo[e] = sft[12 * r + c];
+        }
+        double* pc = a.pcom + b0 * (N * 3);
+        for (int e = t; e < nr * N * 3; e += 256) {                      // pcom[r][k] = (p_k, the measured height)
+            const int row = e / 3, c = e - 3 * row, r = row / N, k = row - N * r;
+            pc[e] = (c == 0) ? spx[K * r + k] : (c == 1) ? spy[K * r + k] : sx0[13 * r + 5];
+        }
+        uint32_t* cw = reinterpret_cast<uint32_t*>(a.contact) + b0 * N;  // 4 flags per step = one aligned word
+        for (int row = t; row < nr * N; row += 256) {
+            const int r = row / N, k = row - N * r;
+            bool cl, cr;
+            flags(r, k, cl, cr);
+            cw[row] = (cl ? 0x00000101u : 0u) | (cr ? 0x01010000u : 0u);
+        }
+        if ((a.landing || a.landing_yaw) && t < nr) {                    // the landing point of the foot that is (or goes next) in the air, and its heading
+            const double* x0 = sx0 + 13 * t;
+            bool cl, cr;
+            flags(t, 0, cl, cr);
+            const double half_T = 0.5 * ((double)a.period * a.dt);
+            const double psi_l = x0[2] + sc[3 * t + 2] * half_T;
+            if (a.landing) {
+                double lx, ly;
+                steer_landing(x0, psi_l, cl ? -1.0 : 1.0, a.hip_offset_y, half_T, svx[K * t], svy[K * t], lx, ly);
+                a.landing[(b0 + t) * 3] = lx; a.landing[(b0 + t) * 3 + 1] = ly; a.landing[(b0 + t) * 3 + 2] = 0.0;
+            }
+            if (a.landing_yaw) a.landing_yaw[b0 + t] = psi_l;
+        }
+        __syncthreads();
+    }
+}
+#endif
+
+}  // namespace srbdqp

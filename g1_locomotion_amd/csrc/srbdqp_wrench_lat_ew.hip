@@ -76,11 +76,34 @@ hipError_t launch_wrench_cn_lat(int N, bool set_attr, const KArgs& a, const void
 
 // The fleet's plant step (srbdqp_fleet.hpp) is instantiated here too, behind the low-latency kernels, for their reason: srbdqp.hip's code object stays what it
 // was, and the library keeps its two code objects (tests/test_staged_wrench_cpu.py, tests/test_staged_normals_cpu.py count them).
-hipError_t launch_fleet_advance(const FleetArgs& a, hipStream_t st, const TerrainMap* map) {
+hipError_t launch_fleet_advance(const FleetArgs& a, hipStream_t st, const TerrainMap* map, const double* landing_yaw) {
     const long long tiles = (a.B + kFleetTile - 1) / kFleetTile;   // one tile of 64 robots per workgroup pass
     const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
-    if (map) hipLaunchKernelGGL((srbdqp_fleet_advance_kernel<kFleetTile, TerrainMap>), grid, dim3(kFleetTile), 0, st, a, *map);
+    if (landing_yaw) {   // the steered instantiations: heel and toe turned by the landing's heading
+        const FleetSteer steer{landing_yaw};
+        if (map) hipLaunchKernelGGL((srbdqp_fleet_advance_kernel<kFleetTile, TerrainMap, FleetSteer>), grid, dim3(kFleetTile), 0, st, a, *map, steer);
+        else hipLaunchKernelGGL((srbdqp_fleet_advance_kernel<kFleetTile, FleetSteer>), grid, dim3(kFleetTile), 0, st, a, steer);
+    } else if (map) hipLaunchKernelGGL((srbdqp_fleet_advance_kernel<kFleetTile, TerrainMap>), grid, dim3(kFleetTile), 0, st, a, *map);
     else hipLaunchKernelGGL(srbdqp_fleet_advance_kernel<kFleetTile>, grid, dim3(kFleetTile), 0, st, a);
+    return hipGetLastError();
+}
+
+// ... the step before the QP of a fleet that steers (srbdqp_steer.hpp): one instantiation per tabulated horizon, and the live one
+hipError_t launch_mpc_inputs_steered(const SteerInputsArgs& a, bool live, hipStream_t st) {
+    const long long tiles = (a.B + 31) / 32;                       // one tile of 32 robots per workgroup pass
+    const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
+    if (a.N < 1 || a.N > kSteerSteps - 1) return hipErrorInvalidValue;   // (the table holds 25 entries a robot)
+    if (live) hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<0>, grid, dim3(256), 0, st, a);
+    else switch (a.N) {
+        case 4: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<4>, grid, dim3(256), 0, st, a); break;
+        case 8: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<8>, grid, dim3(256), 0, st, a); break;
+        case 10: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<10>, grid, dim3(256), 0, st, a); break;
+        case 12: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<12>, grid, dim3(256), 0, st, a); break;
+        case 16: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<16>, grid, dim3(256), 0, st, a); break;
+        case 20: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<20>, grid, dim3(256), 0, st, a); break;
+        case 24: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<24>, grid, dim3(256), 0, st, a); break;
+        default: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<0>, grid, dim3(256), 0, st, a); break;
+    }
     return hipGetLastError();
 }
 

@@ -485,6 +485,34 @@ class BatchMPC(_Engine):
                                                     v(x_ref), v(foot), v(contact), v(pcom), v(landing), v(stream))
         self._check(rc)
 
+    def mpc_inputs_steered(self, x0, feet, stamp, command, com_target, standing=None, period_steps=6, double_support_steps=1, hip_offset_y=0.0645):
+        """mpc_inputs() under command (B,3) = (vx, vy, wz) -- planar velocity in the robot's heading frame and yaw rate -- in place of v_ref
+        (srbdqp_mpc_inputs_steered_f64): the references turn with the commanded heading, the landing point's hip offset with the heading
+        at mid-swing.  A command that is not finite raises SrbdqpError.
+        Returns mpc_inputs()' dict and landing_yaw (B,), the heading the next foot lands with: fleet_advance(landing_yaw=)'s argument."""
+        x = _c(x0, np.float64).reshape(-1, NX)
+        B, N = x.shape[0], self.N
+        f = _c(feet, np.float64).reshape(B, NU)
+        t = _c(stamp, np.float64).reshape(B)
+        c = _as(command, np.float64, (B, 3), "command")
+        sd = None if standing is None else _c(standing, np.uint8).reshape(B)
+        g = self._gait_struct(period_steps, double_support_steps, com_target, hip_offset_y)
+        xr, ft, ct = np.empty((B, N, NX)), np.empty((B, N, NU)), np.empty((B, N, NC), dtype=np.uint8)
+        pc, lp, ly = np.empty((B, N, 3)), np.empty((B, 3)), np.empty(B)
+        rc = self._lib.srbdqp_mpc_inputs_steered_f64(self._h, B, _p(x), _p(f), _p(t), _p(c), _p(sd), C.byref(g), _p(xr), _p(ft), _p(ct), _p(pc), _p(lp), _p(ly))
+        self._check(rc)
+        return dict(x_ref=xr, foot=ft, contact=ct, pcom=pc, landing=lp, landing_yaw=ly)
+
+    def mpc_inputs_steered_device(self, B, x0, feet, stamp, command, com_target, x_ref, foot, contact, pcom, landing=0, landing_yaw=0, standing=0,
+                                  period_steps=6, double_support_steps=1, hip_offset_y=0.0645, stream=0):
+        """Device-pointer form of mpc_inputs_steered(): raw addresses in, launch enqueued behind `stream`, returns at once.  A command that is not finite
+        gives that robot references that are not numbers, which its solve answers with status -1 and zero forces."""
+        v = lambda q: C.c_void_p(int(q)) if q else None
+        g = self._gait_struct(period_steps, double_support_steps, com_target, hip_offset_y)
+        rc = self._lib.srbdqp_mpc_inputs_steered_device_f64(self._h, int(B), v(x0), v(feet), v(stamp), v(command), v(standing), C.byref(g),
+                                                            v(x_ref), v(foot), v(contact), v(pcom), v(landing), v(landing_yaw), v(stream))
+        self._check(rc)
+
     # -- from step t to step t + 1: the fleet's plant step and the K-step loop (include/srbdqp_cascade.h, DESIGN.md section 17) --------
     def fleet_settings(self, com_target=(0.0, 0.0, 0.0), substeps=10, foot_half_length=0.085, z_min=0.3, tilt_max=1.0, period_steps=6,
                        double_support_steps=1, hip_offset_y=0.0645):
@@ -497,13 +525,14 @@ class BatchMPC(_Engine):
         s.gait = self._gait_struct(period_steps, double_support_steps, com_target, hip_offset_y)
         return s
 
-    def fleet_advance(self, x, feet, stamp, u0, landing, standing=None, push=None, alive=None, **settings):
+    def fleet_advance(self, x, feet, stamp, u0, landing, standing=None, push=None, alive=None, landing_yaw=None, **settings):
         """One control period of B robots between two solves (srbdqp_fleet_advance_f64): the nonlinear SRBD plant under the first-step forces u0 (B,12) at
         the contact points feet (B,12) or (B,4,3), the gait clock, the touchdown of the foot that lands around landing (B,3) (mpc_inputs()' output), the
         robots that fell.  standing (B,) flags, push (B,6) world wrench on the body during the period (torque first; the MPC does not know it), alive (B,)
         flags: each or None.  settings: fleet_settings()' keywords.  The inputs are not modified.  With a map set (set_terrain()) a foot that touches
         down stands on the map, heel and toe each at the height under it, and "fallen" compares the CoM's height over the ground under it with z_min
-        (kernel_name() "fleet_advance_terrain_f64").
+        (kernel_name() "fleet_advance_terrain_f64").  landing_yaw (B,) (mpc_inputs_steered()'s output) or None: heel and toe of a foot that touches down
+        lie along that heading (srbdqp_fleet_advance_steered_f64) where they lie along the world's x axis without it.
         Returns dict(x (B,13), feet (B,12), stamp (B,), alive (B,) uint8)."""
         x = np.array(x, dtype=np.float64).reshape(-1, NX)
         B = x.shape[0]
@@ -515,15 +544,25 @@ class BatchMPC(_Engine):
         pu = None if push is None else _as(push, np.float64, (B, 6), "push")
         al = np.ones(B, np.uint8) if alive is None else np.array(np.asarray(alive) != 0, dtype=np.uint8).reshape(B)
         s = self.fleet_settings(**settings)
-        rc = self._lib.srbdqp_fleet_advance_f64(self._h, B, _p(x), _p(f), _p(t), _p(u), NU, _p(lp), _p(sd), _p(pu), _p(al), C.byref(s))
+        if landing_yaw is not None:
+            ly = _as(landing_yaw, np.float64, (B,), "landing_yaw")
+            rc = self._lib.srbdqp_fleet_advance_steered_f64(self._h, B, _p(x), _p(f), _p(t), _p(u), NU, _p(lp), _p(ly), _p(sd), _p(pu), _p(al), C.byref(s))
+        else:
+            rc = self._lib.srbdqp_fleet_advance_f64(self._h, B, _p(x), _p(f), _p(t), _p(u), NU, _p(lp), _p(sd), _p(pu), _p(al), C.byref(s))
         self._check(rc)
         return dict(x=x, feet=f, stamp=t, alive=al)
 
-    def fleet_advance_device(self, B, x, feet, stamp, u0, landing, u0_stride=NU, standing=0, push=0, alive=0, stream=0, **settings):
+    def fleet_advance_device(self, B, x, feet, stamp, u0, landing, u0_stride=NU, standing=0, push=0, alive=0, stream=0, landing_yaw=0, **settings):
         """Device-pointer form of fleet_advance(): raw addresses, x / feet / stamp / alive updated in place, launch enqueued behind `stream`, returns at once.
-        u0_stride (doubles between the forces of consecutive robots): 12 N reads u_out[b][0] of a solve_device() in place."""
+        u0_stride (doubles between the forces of consecutive robots): 12 N reads u_out[b][0] of a solve_device() in place.  landing_yaw: the address of
+        (B,) headings, or 0 for the unsteered step."""
         v = lambda q: C.c_void_p(int(q)) if q else None
         s = self.fleet_settings(**settings)
+        if landing_yaw:
+            rc = self._lib.srbdqp_fleet_advance_steered_device_f64(self._h, int(B), v(x), v(feet), v(stamp), v(u0), int(u0_stride), v(landing), v(landing_yaw),
+                                                                   v(standing), v(push), v(alive), C.byref(s), v(stream))
+            self._check(rc)
+            return
         rc = self._lib.srbdqp_fleet_advance_device_f64(self._h, int(B), v(x), v(feet), v(stamp), v(u0), int(u0_stride), v(landing), v(standing), v(push),
                                                        v(alive), C.byref(s), v(stream))
         self._check(rc)
@@ -570,7 +609,7 @@ class BatchMPC(_Engine):
         self._check(self._lib.srbdqp_wrench_observer_device_f64(self._h, int(B), v(x_prev), v(x_next), v(feet_prev), v(u0), int(u0_stride), v(alive),
                                                                 C.byref(s), v(w_est), v(ew), v(stream)))
 
-    def rollout(self, x0, feet, stamp, v_ref, steps, com_target, standing=None, push=None, alive=None, observer=None, w_est=None, **settings):
+    def rollout(self, x0, feet, stamp, v_ref, steps, com_target, standing=None, push=None, alive=None, observer=None, w_est=None, command=None, **settings):
         """`steps` control steps of B robots on the device (srbdqp_fleet_rollout_f64): per step mpc_inputs -> the solve -> fleet_advance, without a host
         round trip in between.  x0 (B,13), feet (B,12) or (B,4,3), stamp (B,), v_ref (B,2) and standing (B,) flags or None (both constant over the call),
         push (steps,B,6) world wrenches or None, alive (B,) flags or None.  settings: fleet_settings()' keywords.  Robot records and weights set on the
@@ -585,12 +624,21 @@ class BatchMPC(_Engine):
         call to the next, chunks compose bit for bit.  The result then has w_est (B,6) and w_log (steps,B,6), the estimate behind every period.
         Contact normals, a wrench or a terrain set on the engine, a live horizon, rank-aware steps, N = 24 and a kernel= that bars the general kernel
         raise SrbdqpError; robot records and weights are honoured.  observer=None is the call without an observer.
+        command (B,3) or (steps,B,3), with v_ref=None: the steered roll-out (srbdqp_fleet_rollout_steered_f64) -- (vx, vy, wz), planar
+        velocity in each robot's heading frame and yaw rate, held over the call or a row per step; per step mpc_inputs_steered -> the solve ->
+        fleet_advance(landing_yaw=), on flat ground, on a map, or with observer=.  command=None is the call as it was.
         Returns dict(x (steps+1,B,13), u0 (steps,B,12), feet (steps+1,B,12), status (steps,B), iters (steps,B), alive (B,) uint8, stamp (B,))."""
         x = np.array(x0, dtype=np.float64).reshape(-1, NX)
         B, T = x.shape[0], int(steps)
         f = np.array(feet, dtype=np.float64).reshape(B, NU)
         t = np.array(stamp, dtype=np.float64).reshape(B)
-        v = _as(v_ref, np.float64, (B, 2), "v_ref")
+        if command is not None:
+            if v_ref is not None:
+                raise ValueError("rollout: command= replaces v_ref (pass v_ref=None): a steered roll-out takes its velocity in the heading frame")
+            cm = np.asarray(command, dtype=np.float64)
+            cm = _as(cm, np.float64, (B, 3) if cm.ndim < 3 else (max(T, 0), B, 3), "command")
+        else:
+            v = _as(v_ref, np.float64, (B, 2), "v_ref")
         sd = None if standing is None else _as(np.asarray(standing) != 0, np.uint8, (B,), "standing")
         pu = None if push is None else _as(push, np.float64, (max(T, 0), B, 6), "push")
         al = np.ones(B, np.uint8) if alive is None else np.array(np.asarray(alive) != 0, dtype=np.uint8).reshape(B)
@@ -598,6 +646,20 @@ class BatchMPC(_Engine):
         n = max(T, 0)
         xl, ul, fl = np.empty((n + 1, B, NX)), np.empty((n, B, NU)), np.empty((n + 1, B, NU))
         sl, il = np.empty((n, B), np.int32), np.empty((n, B), np.int32)
+        if command is not None:
+            observed = observer is not None and observer is not False
+            if w_est is not None and not observed:
+                raise ValueError("rollout: w_est belongs to an observed roll-out (observer=)")
+            o = self._observer_arg(observer) if observed else None
+            w = (np.zeros((B, 6)) if w_est is None else np.array(w_est, dtype=np.float64).reshape(B, 6)) if observed else None
+            wl = np.empty((n, B, 6)) if observed else None
+            rc = self._lib.srbdqp_fleet_rollout_steered_f64(self._h, B, T, _p(x), _p(f), _p(t), _p(cm), 1 if cm.ndim == 2 else T, _p(sd), _p(pu), C.byref(s), _p(al),
+                                                            _p(xl), _p(ul), _p(fl), _p(sl), _p(il), C.byref(o) if observed else None, _p(w), _p(wl))
+            self._check(rc)
+            out = dict(x=xl, u0=ul, feet=fl, status=sl, iters=il, alive=al, stamp=t)
+            if observed:
+                out.update(w_est=w, w_log=wl)
+            return out
         if observer is not None and observer is not False:
             o = self._observer_arg(observer)
             w = np.zeros((B, 6)) if w_est is None else np.array(w_est, dtype=np.float64).reshape(B, 6)
@@ -614,12 +676,25 @@ class BatchMPC(_Engine):
         return dict(x=xl, u0=ul, feet=fl, status=sl, iters=il, alive=al, stamp=t)
 
     def rollout_device(self, B, steps, x, feet, stamp, v_ref, com_target, standing=0, push=0, alive=0, x_log=0, u0_log=0, feet_log=0, status_log=0,
-                       iters_log=0, stream=0, observer=None, w_est=0, w_log=0, **settings):
+                       iters_log=0, stream=0, observer=None, w_est=0, w_log=0, command=0, command_steps=1, **settings):
         """Device-pointer form of rollout(): raw addresses (0 = absent), x / feet / stamp / alive updated in place, every launch enqueued behind `stream`
         (0 = the engine's own), returns at once without synchronising.  Logs as in include/srbdqp_cascade.h.  observer= as in rollout(): w_est (B,6),
-        required then, is updated in place; w_log (steps,B,6) or 0."""
+        required then, is updated in place; w_log (steps,B,6) or 0.  command: the address of (B,3) commands (command_steps=1) or of (steps,B,3)
+        (command_steps=steps) -- the steered roll-out, v_ref 0 then; 0: the call as it was."""
         v = lambda q: C.c_void_p(int(q)) if q else None
         s = self.fleet_settings(com_target, **settings)
+        if command:
+            if v_ref:
+                raise ValueError("rollout_device: command= replaces v_ref (pass v_ref=0)")
+            observed = observer is not None and observer is not False
+            if (w_est or w_log) and not observed:
+                raise ValueError("rollout_device: w_est and w_log belong to an observed roll-out (observer=)")
+            o = self._observer_arg(observer) if observed else None
+            rc = self._lib.srbdqp_fleet_rollout_steered_device_f64(self._h, int(B), int(steps), v(x), v(feet), v(stamp), v(command), int(command_steps), v(standing),
+                                                                   v(push), C.byref(s), v(alive), v(x_log), v(u0_log), v(feet_log), v(status_log), v(iters_log),
+                                                                   C.byref(o) if observed else None, v(w_est), v(w_log), v(stream))
+            self._check(rc)
+            return
         if observer is not None and observer is not False:
             o = self._observer_arg(observer)
             rc = self._lib.srbdqp_fleet_rollout_observed_device_f64(self._h, int(B), int(steps), v(x), v(feet), v(stamp), v(v_ref), v(standing), v(push),

@@ -162,7 +162,7 @@ int srbdqp_terrain_inputs_device_f64(srbdqp_handle* h, int64_t B, const double* 
  * Such a roll-out is refused (SRBDQP_E_INVALID before any launch, in the words of the handle's state "while a terrain is set") beside robot records, weights,
  * an external wrench or handle-level normals, on a live horizon, with rank-aware steps, at N = 24 and with a srbdqp_config.kernel that bars the general kernel:
  * no instantiation reads normals beside those.  Not modelled: ground reaction or sliding in the plant (the forces are the QP's), footholds predicted along the
- * horizon, per-robot map offsets, feet turned with yaw, terrain under the swing trajectory, fp32, ragged fleets. */
+ * horizon, per-robot map offsets, feet turned with yaw (srbdqp_fleet_advance_steered_* below turns them), terrain under the swing trajectory, fp32, ragged fleets. */
 
 /* T control steps of B robots: for t = 0 ... T - 1, srbdqp_mpc_inputs_device_f64 -> the solve, exactly the launches srbdqp_solve_batch_device_f64 makes
  * for this handle, with pcom from the inputs -> srbdqp_fleet_advance_device_f64, enqueued on `stream` without a host synchronisation (plain launches: no
@@ -241,6 +241,58 @@ int srbdqp_fleet_rollout_observed_f64(srbdqp_handle* h, int64_t B, int32_t T, do
                                       const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
                                       double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
                                       const srbdqp_observer_settings* obs, double* w_est, double* w_log);
+
+/* ---- a fleet that steers: yaw-rate commands and turned footholds.
+ *
+ * srbdqp_mpc_inputs_steered_* is srbdqp_mpc_inputs_* under command [B][3] = (vx, vy, wz) -- planar velocity in the robot's HEADING frame, m/s, and yaw rate,
+ * rad/s -- in place of v_ref, with one more output, landing_yaw [B] (may be NULL).  x_ref, foot, contact, pcom, landing: the layout of srbdqp_mpc_inputs_*.
+ * With psi0 = x0[2], Rz(th) the planar rotation, v_w(th) = Rz(th) (vx, vy) = (cos th vx - sin th vy, sin th vx + cos th vy), T = period_steps dt,
+ * moving = (vx != 0 || vy != 0), every product and sum one rounded fp64 operation in the order written, a heading psi0 + wz (j dt) computed as psi0 + (wz j) dt:
+ *   p_0 = x0[3:5];  p_{k+1} = p_k + v_w(psi0 + wz (k + 1/2) dt) dt, k = 0 ... N - 1   (a serial sum, the heading at the middle of the step)
+ *   x_ref[k][2]    = psi0 + wz (k + 1) dt          (not wrapped: the plant and the solver carry unwrapped yaw)
+ *   x_ref[k][3:5]  = p_{k+1} when moving, else com_target[0:2]   (a robot that turns on the spot turns about its target)
+ *   x_ref[k][5]    = com_target[2];  x_ref[k][8] = wz;  x_ref[k][9:11] = v_w(psi0 + wz (k + 1) dt);  x_ref[k][12] = x0[12];  every other entry 0
+ *   pcom[k]        = (p_k, x0[5]);   foot: the current contact points repeated;   contact: the schedule of srbdqp_mpc_inputs_*
+ *   psi_L          = psi0 + wz (T / 2)             (the heading at mid-swing)
+ *   landing_xy     = ((x0[3:5] + Rz(psi_L) (0, side hip_offset_y)) + (T / 2) x0[9:11]) + 0.03 (x0[9:11] - v_w(psi0)),  side as in srbdqp_mpc_inputs_*
+ *   landing_z      = 0;   landing_yaw = psi_L
+ * The host form refuses a command that is not finite (SRBDQP_E_INVALID).  In the device form such a command gives references that are not numbers for that
+ * robot alone, which its solve answers with status -1 and zero forces (srbdqp.h, the non-finite contract); no trip count depends on a command.
+ * Any horizon of the handle, live ones included.  srbdqp_kernel_name: mpc_inputs_steered_f64. */
+int srbdqp_mpc_inputs_steered_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
+                                  const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
+                                  double* landing, double* landing_yaw);
+int srbdqp_mpc_inputs_steered_device_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
+                                         const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
+                                         double* landing, double* landing_yaw, void* stream);
+
+/* srbdqp_fleet_advance_* with landing_yaw [B] (required), as srbdqp_mpc_inputs_steered_* wrote it.  One thing differs, the touchdown:
+ *   heel = landing - foot_half_length (cos psi_L, sin psi_L, 0),  toe = landing + foot_half_length (cos psi_L, sin psi_L, 0)
+ * z on flat ground is landing's z; with a map set each of the two turned points gets z = S(own xy).z.  landing_yaw = 0 is srbdqp_fleet_advance_* bit for bit.
+ * srbdqp_kernel_name: fleet_advance_steered_f64, fleet_advance_terrain_steered_f64. */
+int srbdqp_fleet_advance_steered_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
+                                     const double* landing, const double* landing_yaw, const uint8_t* standing, const double* push, uint8_t* alive,
+                                     const srbdqp_fleet_settings* cfg);
+int srbdqp_fleet_advance_steered_device_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
+                                            const double* landing, const double* landing_yaw, const uint8_t* standing, const double* push, uint8_t* alive,
+                                            const srbdqp_fleet_settings* cfg, void* stream);
+
+/* The roll-out under commands: the loop of srbdqp_fleet_rollout_* with srbdqp_mpc_inputs_steered_device_f64 as its inputs call and the steered plant step, a
+ * landing_yaw buffer joining the handle's roll-out allocation.  The arguments of srbdqp_fleet_rollout_observed_* with command and command_steps in place of v_ref:
+ *   command_steps == 1: command [B][3], held over the call;  command_steps == T: command [T][B][3], step t reading row t.
+ *   obs == NULL: the plain loop (w_est and w_log are ignored);  obs != NULL: the observed loop;  a terrain set on the handle: the terrain roll-out.
+ * Refused: what the roll-out it becomes refuses; command NULL; command_steps outside {1, T}; in the host form a command that is not finite.  Chunks compose bit
+ * for bit, a schedule with the two constant-command chunks it is made of included.
+ * Not modelled: footholds previewed along the horizon (foot[b][k] stays the current points), a centrifugal term in the landing point, feet turned under a
+ * standing robot, ragged fleets, fp32, a heading controller on top of the rate command. */
+int srbdqp_fleet_rollout_steered_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
+                                            int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                            double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                            const srbdqp_observer_settings* obs, double* w_est, double* w_log, void* stream);
+int srbdqp_fleet_rollout_steered_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
+                                     int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                     double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                     const srbdqp_observer_settings* obs, double* w_est, double* w_log);
 
 #ifdef __cplusplus
 }

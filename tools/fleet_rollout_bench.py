@@ -14,7 +14,11 @@ roll-out beside them gives the cost of leaving the one-wave kernel.
 every plant step --, the Python loop with the observer and the wrench buffer in it (set_external_wrench on the device buffer, once), and the observer alone: time
 per launch and GB/s.  Beside --kernel wrench in the same job: the cost of observing.
 
-    python tools/fleet_rollout_bench.py [--robots 4096] [--steps 100] [--reps 5] [--terrain] [--observer] [--kernel auto|wrench] [--out profiles/<name>.json]
+--steer: the steered roll-out -- the same fleet under (vx, vy, wz) commands, wz uniform in +-0.6 rad/s, the velocities of the unsteered
+run taken in the heading frame --, the Python loop through mpc_inputs_steered_device and fleet_advance_device(landing_yaw=), and the steered inputs kernel
+alone: time per launch and GB/s, with mpc_inputs measured the same way beside it.  Combines with --terrain and --observer.
+
+    python tools/fleet_rollout_bench.py [--robots 4096] [--steps 100] [--reps 5] [--terrain] [--observer] [--steer] [--kernel auto|wrench] [--out profiles/<name>.json]
 """
 import argparse
 import hashlib
@@ -34,6 +38,8 @@ COM = np.array([0.085, 0.0, 0.598])
 ADVANCE_BYTES = (13 + 12 + 12 + 3 + 1 + 6 + 13 + 1) * 8
 # ... and the observer, beside the N 6 doubles of the horizon's wrench: two states, feet, u0, w_est in; w_est out
 OBSERVER_BYTES = (13 + 13 + 12 + 12 + 6 + 6) * 8
+# ... and the inputs step, beside the N (13 + 12 + 3) doubles and N 4 bytes of the horizons: x0, feet, stamp, the command (2 or 3 doubles) in; landing (3, and its heading) out
+INPUTS_BYTES = (13 + 12 + 1 + 3) * 8
 
 
 def main():
@@ -43,6 +49,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--terrain", action="store_true")
     ap.add_argument("--observer", action="store_true")
+    ap.add_argument("--steer", action="store_true")
     ap.add_argument("--kernel", choices=("auto", "wrench"), default="auto")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -64,13 +71,17 @@ def main():
     push = np.where(rng.random((T, B, 1)) < 0.05, rng.uniform(-1.0, 1.0, (T, B, 6)) * np.array([2.0, 2.0, 0.0, 30.0, 30.0, 10.0]), 0.0)
     up = lambda arr: torch.from_numpy(np.ascontiguousarray(arr)).to(dev)
     d_v, d_pu = up(v_ref), up(push)
+    # (drawn behind everything the unsteered runs draw: they draw exactly what they drew before)
+    d_cm = up(np.concatenate([v_ref, rng.uniform(-0.6, 0.6, (B, 1))], axis=1)) if a.steer else None
+    ly = torch.empty(B, dtype=torch.float64, device=dev) if a.steer else None
+    steer = dict(command=d_cm.data_ptr(), command_steps=1) if a.steer else {}
     f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)
     xl, ul, fl = f64(T + 1, B, 13), f64(T, B, 12), f64(T + 1, B, 12)
     sl, il = torch.empty((T, B), dtype=torch.int32, device=dev), torch.empty((T, B), dtype=torch.int32, device=dev)
     xr, fo, pc, lp, u, xo = f64(B, N, 13), f64(B, N, 12), f64(B, N, 3), f64(B, 3), f64(B, N, 12), f64(B, N + 1, 13)
     ct = torch.empty((B, N, 4), dtype=torch.uint8, device=dev)
     st, it = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
-    res = dict(robots=B, steps=T, horizon=N, reps=a.reps, terrain=bool(a.terrain), observer=bool(a.observer), kernel_setting=a.kernel)
+    res = dict(robots=B, steps=T, horizon=N, reps=a.reps, terrain=bool(a.terrain), observer=bool(a.observer), steer=bool(a.steer), kernel_setting=a.kernel)
     cn = f64(B, N, 12) if a.terrain else None
     we, wl, ew = (f64(B, 6), f64(T, B, 6), f64(B, N, 6)) if a.observer else (None, None, None)
     obs = dict(observer=True, w_est=we.data_ptr(), w_log=wl.data_ptr()) if a.observer else {}
@@ -92,8 +103,8 @@ def main():
                 we.zero_()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            eng.rollout_device(B, T, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), d_v.data_ptr(), COM, push=d_pu.data_ptr(), alive=al.data_ptr(),
-                               x_log=xl.data_ptr(), u0_log=ul.data_ptr(), feet_log=fl.data_ptr(), status_log=sl.data_ptr(), iters_log=il.data_ptr(), **obs)
+            eng.rollout_device(B, T, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), 0 if a.steer else d_v.data_ptr(), COM, push=d_pu.data_ptr(), alive=al.data_ptr(),
+                               x_log=xl.data_ptr(), u0_log=ul.data_ptr(), feet_log=fl.data_ptr(), status_log=sl.data_ptr(), iters_log=il.data_ptr(), **obs, **steer)
             t1 = time.perf_counter()
             eng.synchronize()
             return time.perf_counter() - t0, t1 - t0, al
@@ -107,8 +118,12 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for k in range(T):
-                eng.mpc_inputs_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), d_v.data_ptr(), COM, xr.data_ptr(), fo.data_ptr(), ct.data_ptr(),
-                                      pc.data_ptr(), landing=lp.data_ptr())
+                if a.steer:
+                    eng.mpc_inputs_steered_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), d_cm.data_ptr(), COM, xr.data_ptr(), fo.data_ptr(), ct.data_ptr(),
+                                                  pc.data_ptr(), landing=lp.data_ptr(), landing_yaw=ly.data_ptr())
+                else:
+                    eng.mpc_inputs_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), d_v.data_ptr(), COM, xr.data_ptr(), fo.data_ptr(), ct.data_ptr(),
+                                          pc.data_ptr(), landing=lp.data_ptr())
                 if a.terrain:
                     eng.terrain_inputs_device(B, feet.data_ptr(), xr.data_ptr(), cn.data_ptr())
                     eng.set_contact_normals(cn)
@@ -117,7 +132,7 @@ def main():
                 if a.observer:                                            # (the state and the feet before the period: what a user without logs has to keep)
                     xp.copy_(x); fp.copy_(feet)
                 eng.fleet_advance_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), u.data_ptr(), lp.data_ptr(), u0_stride=12 * N,
-                                         push=d_pu[k].data_ptr(), alive=al.data_ptr())
+                                         push=d_pu[k].data_ptr(), alive=al.data_ptr(), landing_yaw=ly.data_ptr() if a.steer else 0)
                 if a.observer:
                     eng.wrench_observer_device(B, xp.data_ptr(), x.data_ptr(), fp.data_ptr(), u.data_ptr(), we.data_ptr(), ew=ew.data_ptr(), u0_stride=12 * N,
                                                alive=al.data_ptr())
@@ -166,6 +181,26 @@ def main():
             res["observer_gb_per_s"] = B * (OBSERVER_BYTES + N * 6 * 8) / t_ob / 1e9
             res["observer_share_of_a_rollout_step"] = t_ob / (t_call / T)
             res["w_est_force_rms_N"] = float(wl[:, :, 3:6].pow(2).mean().sqrt().item())
+        if a.steer:                                                       # the inputs kernels alone, back to back: the steered one, and mpc_inputs the same way
+            xs, fs, ss, _ = fresh()
+            per = {}
+            for name, launch in (("mpc_inputs_steered", lambda: eng.mpc_inputs_steered_device(B, xs.data_ptr(), fs.data_ptr(), ss.data_ptr(), d_cm.data_ptr(), COM, xr.data_ptr(),
+                                                                                              fo.data_ptr(), ct.data_ptr(), pc.data_ptr(), landing=lp.data_ptr(), landing_yaw=ly.data_ptr())),
+                                 ("mpc_inputs", lambda: eng.mpc_inputs_device(B, xs.data_ptr(), fs.data_ptr(), ss.data_ptr(), d_v.data_ptr(), COM, xr.data_ptr(), fo.data_ptr(),
+                                                                              ct.data_ptr(), pc.data_ptr(), landing=lp.data_ptr()))):
+                launch(); eng.synchronize()
+                ts = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    for _ in range(T):
+                        launch()
+                    eng.synchronize()
+                    ts.append((time.perf_counter() - t0) / T)
+                per[name] = float(np.median(ts))
+                res[name + "_us_per_launch"] = per[name] * 1e6
+                res[name + "_gb_per_s"] = B * (INPUTS_BYTES + N * (13 + 12 + 3) * 8 + N * 4) / per[name] / 1e9
+            res["mpc_inputs_steered_share_of_a_rollout_step"] = per["mpc_inputs_steered"] / (t_call / T)
+            res["final_yaw_rms_error_rad"] = float((xl[T, :, 2] - xl[0, :, 2] - d_cm[:, 2] * (T * dt)).pow(2).mean().sqrt().item())
         res["rollout_call_s"] = t_call
         res["rollout_enqueue_s"] = float(np.median([c[1] for c in calls]))
         res["rollout_robot_steps_per_s"] = B * T / t_call
