@@ -160,12 +160,11 @@ struct srbdqp_handle {
         uint8_t* contact = nullptr;
         int32_t *status = nullptr, *iters = nullptr;
         double* normals = nullptr;         // [B][N][12], carved only while a terrain is set: the contact normals of a terrain roll-out's solves (Call::cn_call)
-        // carved once an observed roll-out has asked (observed): the external wrench of its solves (Call::ext_call), [B][N][6], and the two-slot ring of states
+        unsigned flavour = 0;              // the roll-out flavours that have asked so far (kObserved | kSteered: ensure_fleet_buffers)
+        // carved once an observed roll-out has asked: the external wrench of its solves (Call::ext_call), [B][N][6], and the two-slot ring of states
         // [2][B][13] and footholds [2][B][12] the observer reads where the caller keeps no logs
-        bool observed = false;
         double *ew = nullptr, *ring_x = nullptr, *ring_feet = nullptr;
-        // carved once a steered roll-out has asked (steered): the heading every robot's next foot lands with, [B] (srbdqp_mpc_inputs_steered_* writes it)
-        bool steered = false;
+        // carved once a steered roll-out has asked: the heading every robot's next foot lands with, [B] (srbdqp_mpc_inputs_steered_* writes it)
         double* landing_yaw = nullptr;
     } fleet;
     // the ground under the fleet (srbdqp_set_terrain, include/srbdqp_cascade.h): the library's device copy of the height map; map.h null: flat ground
@@ -2695,6 +2694,8 @@ int srbdqp_solve_ragged_f32(srbdqp_ragged* r, int32_t B, const int32_t* N_per_qp
     return ragged_host_impl(r, B, sizeof(float), N_per_qp, x0, x_ref, foot, contact, u_out, x_out, status, iters);
 }
 
+}  // extern "C"
+
 // ---- the steps either side of the QP (include/srbdqp_cascade.h) --------------------------------------------------
 namespace {
 inline unsigned elementwise_grid(long long B) {
@@ -2702,14 +2703,39 @@ inline unsigned elementwise_grid(long long B) {
     const long long want = (B + 255) / 256;
     return (unsigned)(want < 1 ? 1 : (want > 256 * 16 ? 256 * 16 : want));
 }
+
+// how every check of this section starts: no handle, then the null test of a call over B items (B = 0: nothing to do, no array needed; `missing`: an array
+// the call needs is NULL)
+int arrays_check(srbdqp_handle* h, bool B_in_range, int64_t B, bool missing) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (!B_in_range || (B > 0 && missing)) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    return SRBDQP_OK;
+}
+
+int swing_check(srbdqp_handle* h, int64_t B, const void* p_start, const void* p_final, const void* z_middle, const void* progress, const void* pos) {
+    return arrays_check(h, B >= 0, B, !p_start || !p_final || !z_middle || !progress || !pos);
+}
+
+int wbid_reference_check(srbdqp_handle* h, int64_t B, const void* x_next, const void* u0, const void* foot, const void* R, const void* base_vel,
+                         const void* base_acc, const void* com_acc) {
+    return arrays_check(h, B >= 0, B, !x_next || !u0 || !foot || !R || !base_vel || !base_acc || !com_acc);
+}
+
+// the gait rule: what is wrong with a gait (null: nothing), in the words its callers put behind their own
+#define SRBDQP_GAIT_RULE "(struct_size, 1 <= period_steps, 0 <= double_support_steps <= period_steps)"
+const char* gait_fault(const srbdqp_gait* g) {
+    return !g || g->struct_size != (int32_t)sizeof(srbdqp_gait) || g->period_steps < 1 || g->double_support_steps < 0 || g->double_support_steps > g->period_steps
+               ? SRBDQP_GAIT_RULE : nullptr;
+}
 }  // namespace
+
+extern "C" {
 
 int srbdqp_swing_device_f64(srbdqp_handle* h, int64_t B, const double* p_start, const double* p_final,
                             const double* z_middle, const double* progress, double final_velocity_z,
                             double first_half_share, double* pos, double* vel_z, double* acc_z, double* coeff,
                             void* stream) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (B < 0 || (B > 0 && (!p_start || !p_final || !z_middle || !progress || !pos))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const int rc = swing_check(h, B, p_start, p_final, z_middle, progress, pos)) return rc;
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     srbdqp::SwingArgs a{p_start, p_final, z_middle, progress, pos, vel_z, acc_z, coeff, final_velocity_z, first_half_share, (long long)B};
@@ -2723,8 +2749,7 @@ int srbdqp_swing_device_f64(srbdqp_handle* h, int64_t B, const double* p_start, 
 int srbdqp_swing_f64(srbdqp_handle* h, int64_t B, const double* p_start, const double* p_final, const double* z_middle,
                      const double* progress, double final_velocity_z, double first_half_share, double* pos,
                      double* vel_z, double* acc_z, double* coeff) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (B < 0 || (B > 0 && (!p_start || !p_final || !z_middle || !progress || !pos))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const int rc = swing_check(h, B, p_start, p_final, z_middle, progress, pos)) return rc;
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t b = (size_t)B;
@@ -2738,8 +2763,7 @@ int srbdqp_swing_f64(srbdqp_handle* h, int64_t B, const double* p_start, const d
 int srbdqp_wbid_reference_device_f64(srbdqp_handle* h, int64_t B, const double* x_next, const double* u0,
                                      const double* foot, int32_t as_written, double* R, double* base_vel,
                                      double* base_acc, double* com_acc, void* stream) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (B < 0 || (B > 0 && (!x_next || !u0 || !foot || !R || !base_vel || !base_acc || !com_acc))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const int rc = wbid_reference_check(h, B, x_next, u0, foot, R, base_vel, base_acc, com_acc)) return rc;
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     srbdqp::WbidRefArgs a;
@@ -2762,8 +2786,7 @@ int srbdqp_wbid_reference_device_f64(srbdqp_handle* h, int64_t B, const double* 
 
 int srbdqp_wbid_reference_f64(srbdqp_handle* h, int64_t B, const double* x_next, const double* u0, const double* foot,
                               int32_t as_written, double* R, double* base_vel, double* base_acc, double* com_acc) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (B < 0 || (B > 0 && (!x_next || !u0 || !foot || !R || !base_vel || !base_acc || !com_acc))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const int rc = wbid_reference_check(h, B, x_next, u0, foot, R, base_vel, base_acc, com_acc)) return rc;
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t b = (size_t)B;
@@ -2772,56 +2795,6 @@ int srbdqp_wbid_reference_f64(srbdqp_handle* h, int64_t B, const double* x_next,
         dx = io.in<double>(x_next, b * 13 * 8); du = io.in<double>(u0, b * 12 * 8); df = io.in<double>(foot, b * 12 * 8);
         dR = io.out<double>(R, b * 9 * 8); dv = io.out<double>(base_vel, b * 6 * 8); da = io.out<double>(base_acc, b * 6 * 8); dc = io.out<double>(com_acc, b * 3 * 8);
     }, [&](hipStream_t st) { return srbdqp_wbid_reference_device_f64(h, B, dx, du, df, as_written, dR, dv, da, dc, st); });
-}
-
-int srbdqp_mpc_inputs_device_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp,
-                                 const double* v_ref, const uint8_t* standing, const srbdqp_gait* gait,
-                                 double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, void* stream) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (B < 0 || (B > 0 && (!x0 || !feet || !stamp || !v_ref || !x_ref || !foot || !contact || !pcom))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
-    if (!gait || gait->struct_size != (int32_t)sizeof(srbdqp_gait) || gait->period_steps < 1 || gait->double_support_steps < 0 ||
-        gait->double_support_steps > gait->period_steps) { h->err = "invalid srbdqp_gait (struct_size, 1 <= period_steps, 0 <= double_support_steps <= period_steps)"; return SRBDQP_E_INVALID; }
-    if (B == 0) return SRBDQP_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    srbdqp::MpcInputsArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.x0 = x0; a.feet = feet; a.stamp = stamp; a.v_ref = v_ref; a.standing = standing;
-    a.x_ref = x_ref; a.foot = foot; a.contact = contact; a.pcom = pcom; a.landing = landing;
-    for (int i = 0; i < 3; ++i) a.com_target[i] = gait->com_target[i];
-    a.hip_offset_y = gait->hip_offset_y; a.dt = h->cfg.dt;
-    a.N = h->cfg.horizon; a.period = gait->period_steps; a.ds = gait->double_support_steps;
-    a.B = (long long)B;
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
-    const long long tiles = ((long long)B + 31) / 32;                   // one tile of 32 robots per workgroup pass
-    const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
-    int rc = SRBDQP_OK;
-    if (h->live_nstar) hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<0>, grid, dim3(256), 0, st, a);   // (a live horizon: a.N at run time)
-    else rc = with_horizon(h, [&](auto n) -> int {
-        hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<decltype(n)::value>, grid, dim3(256), 0, st, a);
-        return SRBDQP_OK;
-    });
-    if (rc != SRBDQP_OK) return rc;
-    HIP_TRY(h, hipGetLastError());
-    h->kname = "mpc_inputs_f64";
-    return SRBDQP_OK;
-}
-
-int srbdqp_mpc_inputs_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp,
-                          const double* v_ref, const uint8_t* standing, const srbdqp_gait* gait,
-                          double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (B < 0 || (B > 0 && (!x0 || !feet || !stamp || !v_ref || !x_ref || !foot || !contact || !pcom))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
-    if (B == 0) return SRBDQP_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
-    double *dx0, *dfe, *dst, *dv, *dxr, *dft, *dpc, *dlp;
-    uint8_t *dsd, *dct;
-    return host_call(h, [&](HostIo& io) {
-        dx0 = io.in<double>(x0, b * 13 * 8); dfe = io.in<double>(feet, b * 12 * 8); dst = io.in<double>(stamp, b * 8); dv = io.in<double>(v_ref, b * 16);
-        dsd = io.in<uint8_t>(standing, b);
-        dxr = io.out<double>(x_ref, b * N * 13 * 8); dft = io.out<double>(foot, b * N * 12 * 8); dct = io.out<uint8_t>(contact, b * N * 4);
-        dpc = io.out<double>(pcom, b * N * 3 * 8); dlp = io.out<double>(landing, b * 3 * 8);
-    }, [&](hipStream_t st) { return srbdqp_mpc_inputs_device_f64(h, B, dx0, dfe, dst, dv, dsd, gait, dxr, dft, dct, dpc, dlp, st); });
 }
 
 }  // extern "C"
@@ -2835,10 +2808,7 @@ const char* fleet_settings_fault(const srbdqp_fleet_settings* s) {
     if (s->substeps < 1 || s->substeps > 1000) return "1 <= substeps <= 1000";
     for (const double v : {s->foot_half_length, s->z_min, s->tilt_max})
         if (!std::isfinite(v) || !(v > 0.0)) return "foot_half_length, z_min and tilt_max must be finite and positive";
-    const srbdqp_gait& g = s->gait;
-    if (g.struct_size != (int32_t)sizeof(srbdqp_gait) || g.period_steps < 1 || g.double_support_steps < 0 || g.double_support_steps > g.period_steps)
-        return "invalid gait (struct_size, 1 <= period_steps, 0 <= double_support_steps <= period_steps)";
-    return nullptr;
+    return gait_fault(&s->gait) ? "invalid gait " SRBDQP_GAIT_RULE : nullptr;
 }
 
 // the roll-out's records of one period (srbdqp::FleetArgs): all null outside a roll-out
@@ -2848,10 +2818,10 @@ struct FleetLogs {
     int32_t *status_log = nullptr, *iters_log = nullptr;
 };
 
-// one launch of the plant step; the arguments have been checked
+// one launch of the plant step; the arguments have been checked.  landing_yaw null: feet land unturned
 int fleet_advance_launch(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride, const double* landing,
-                         const uint8_t* standing, const double* push, uint8_t* alive, const srbdqp_fleet_settings* cfg, const FleetLogs& lg, hipStream_t st,
-                         const double* landing_yaw = nullptr) {
+                         const double* landing_yaw, const uint8_t* standing, const double* push, uint8_t* alive, const srbdqp_fleet_settings* cfg,
+                         const FleetLogs& lg, hipStream_t st) {
     srbdqp::FleetArgs a;
     std::memset(&a, 0, sizeof(a));
     a.x = x; a.feet = feet; a.stamp = stamp; a.u0 = u0; a.u0_stride = (long long)u0_stride; a.landing = landing; a.standing = standing; a.push = push;
@@ -2870,12 +2840,42 @@ int fleet_advance_launch(srbdqp_handle* h, int64_t B, double* x, double* feet, d
     return SRBDQP_OK;
 }
 
+// steered: the call is srbdqp_fleet_advance_steered_*, which needs the landing_yaw that the plain call does not take
 int fleet_advance_check(srbdqp_handle* h, int64_t B, const void* x, const void* feet, const void* stamp, const void* u0, int64_t u0_stride, const void* landing,
-                        const srbdqp_fleet_settings* cfg) {
-    if (B < 0 || (B > 0 && (!x || !feet || !stamp || !u0 || !landing))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+                        const void* landing_yaw, bool steered, const srbdqp_fleet_settings* cfg) {
+    if (const int rc = arrays_check(h, B >= 0, B, !x || !feet || !stamp || !u0 || !landing)) return rc;
     if (u0_stride < 12) { h->err = "srbdqp_fleet_advance: u0_stride must be at least 12 doubles"; return SRBDQP_E_INVALID; }
     if (const char* why = fleet_settings_fault(cfg)) { h->err = std::string("invalid srbdqp_fleet_settings: ") + why; return SRBDQP_E_INVALID; }
-    return covers<RobotsIn>(h, B, "srbdqp_fleet_advance: ", " robots with ", false, false);
+    if (const int rc = covers<RobotsIn>(h, B, "srbdqp_fleet_advance: ", " robots with ", false, false)) return rc;
+    if (steered && B > 0 && !landing_yaw) { h->err = "srbdqp_fleet_advance_steered: landing_yaw is NULL (srbdqp_mpc_inputs_steered_* writes it; srbdqp_fleet_advance_* lands feet unturned)"; return SRBDQP_E_INVALID; }
+    return SRBDQP_OK;
+}
+
+// the plant step behind its four entry points: device buffers, then host buffers staged around the same call
+int fleet_advance_device(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride, const double* landing,
+                         const double* landing_yaw, bool steered, const uint8_t* standing, const double* push, uint8_t* alive, const srbdqp_fleet_settings* cfg,
+                         void* stream) {
+    if (const int rc = fleet_advance_check(h, B, x, feet, stamp, u0, u0_stride, landing, landing_yaw, steered, cfg)) return rc;
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+    return fleet_advance_launch(h, B, x, feet, stamp, u0, u0_stride, landing, landing_yaw, standing, push, alive, cfg, FleetLogs{}, st);
+}
+
+int fleet_advance_host(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride, const double* landing,
+                       const double* landing_yaw, bool steered, const uint8_t* standing, const double* push, uint8_t* alive, const srbdqp_fleet_settings* cfg) {
+    if (const int rc = fleet_advance_check(h, B, x, feet, stamp, u0, u0_stride, landing, landing_yaw, steered, cfg)) return rc;
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)B;
+    double *dx, *dfe, *dst, *du, *dlp, *dly, *dpu;
+    uint8_t *dsd, *dal;
+    return host_call(h, [&](HostIo& io) {
+        dx = io.add<double>(x, x, b * 13 * 8, false); dfe = io.add<double>(feet, feet, b * 12 * 8, false); dst = io.add<double>(stamp, stamp, b * 8, false);
+        du = io.in<double>(u0, ((b - 1) * (size_t)u0_stride + 12) * 8); dlp = io.in<double>(landing, b * 3 * 8); dly = io.in<double>(landing_yaw, b * 8);
+        dsd = io.in<uint8_t>(standing, b); dpu = io.in<double>(push, b * 6 * 8);
+        dal = alive ? io.add<uint8_t>(alive, alive, b, false) : nullptr;
+    }, [&](hipStream_t st) { return fleet_advance_device(h, B, dx, dfe, dst, du, u0_stride, dlp, dly, steered, dsd, dpu, dal, cfg, st); });
 }
 
 // ---- a fleet that steers (include/srbdqp_cascade.h; the kernel: srbdqp_steer.hpp) ----
@@ -2888,13 +2888,32 @@ long long steer_non_finite(const double* command, size_t count) {
     return -1;
 }
 
-int steer_gait_check(srbdqp_handle* h, const srbdqp_gait* gait) {
-    if (!gait || gait->struct_size != (int32_t)sizeof(srbdqp_gait) || gait->period_steps < 1 || gait->double_support_steps < 0 ||
-        gait->double_support_steps > gait->period_steps) { h->err = "invalid srbdqp_gait (struct_size, 1 <= period_steps, 0 <= double_support_steps <= period_steps)"; return SRBDQP_E_INVALID; }
+// one launch of the inputs from v_ref [B][2]; the arguments have been checked
+int mpc_inputs_launch(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* v_ref, const uint8_t* standing,
+                      const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, hipStream_t st) {
+    srbdqp::MpcInputsArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.x0 = x0; a.feet = feet; a.stamp = stamp; a.v_ref = v_ref; a.standing = standing;
+    a.x_ref = x_ref; a.foot = foot; a.contact = contact; a.pcom = pcom; a.landing = landing;
+    for (int i = 0; i < 3; ++i) a.com_target[i] = gait->com_target[i];
+    a.hip_offset_y = gait->hip_offset_y; a.dt = h->cfg.dt;
+    a.N = h->cfg.horizon; a.period = gait->period_steps; a.ds = gait->double_support_steps;
+    a.B = (long long)B;
+    const long long tiles = ((long long)B + 31) / 32;                   // one tile of 32 robots per workgroup pass
+    const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
+    int rc = SRBDQP_OK;
+    if (h->live_nstar) hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<0>, grid, dim3(256), 0, st, a);   // (a live horizon: a.N at run time)
+    else rc = with_horizon(h, [&](auto n) -> int {
+        hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<decltype(n)::value>, grid, dim3(256), 0, st, a);
+        return SRBDQP_OK;
+    });
+    if (rc != SRBDQP_OK) return rc;
+    HIP_TRY(h, hipGetLastError());
+    h->kname = "mpc_inputs_f64";
     return SRBDQP_OK;
 }
 
-// one launch of the steered inputs; the arguments have been checked
+// one launch of the steered inputs, from command [B][3]; the arguments have been checked
 int mpc_inputs_steered_launch(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command, const uint8_t* standing,
                               const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, double* landing_yaw, hipStream_t st) {
     srbdqp::SteerInputsArgs a;
@@ -2910,13 +2929,73 @@ int mpc_inputs_steered_launch(srbdqp_handle* h, int64_t B, const double* x0, con
     return SRBDQP_OK;
 }
 
-// the horizon buffers of a roll-out, at B robots, carved from one allocation of the handle's
-int ensure_fleet_buffers(srbdqp_handle* h, size_t B, bool observed = false, bool steered = false) {
+// the inputs behind their four entry points.  steered: vel is a command [B][3] and landing_yaw is written; else vel is v_ref [B][2] and landing_yaw is null
+int mpc_inputs_check(srbdqp_handle* h, int64_t B, bool steered, const void* x0, const void* feet, const void* stamp, const void* vel, const void* x_ref,
+                     const void* foot, const void* contact, const void* pcom) {
+    return arrays_check(h, B >= 0 && !(steered && B > 0x7fffffffLL), B, !x0 || !feet || !stamp || !vel || !x_ref || !foot || !contact || !pcom);
+}
+
+int mpc_inputs_device(srbdqp_handle* h, int64_t B, bool steered, const double* x0, const double* feet, const double* stamp, const double* vel, const uint8_t* standing,
+                      const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, double* landing_yaw, void* stream) {
+    if (const int rc = mpc_inputs_check(h, B, steered, x0, feet, stamp, vel, x_ref, foot, contact, pcom)) return rc;
+    if (const char* why = gait_fault(gait)) { h->err = std::string("invalid srbdqp_gait ") + why; return SRBDQP_E_INVALID; }
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+    return steered ? mpc_inputs_steered_launch(h, B, x0, feet, stamp, vel, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw, st)
+                   : mpc_inputs_launch(h, B, x0, feet, stamp, vel, standing, gait, x_ref, foot, contact, pcom, landing, st);
+}
+
+int mpc_inputs_host(srbdqp_handle* h, int64_t B, bool steered, const double* x0, const double* feet, const double* stamp, const double* vel, const uint8_t* standing,
+                    const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, double* landing_yaw) {
+    // (a command is the caller's host array: it is read before the handle is)
+    if (steered && B > 0 && B <= 0x7fffffffLL && vel) {
+        const long long i = steer_non_finite(vel, (size_t)B * 3);
+        if (i >= 0) return steer_refuse(h, "srbdqp_mpc_inputs_steered: the command of robot " + std::to_string(i / 3) + " is not finite (component " + std::to_string(i % 3) + " of vx, vy, wz)");
+    }
+    if (const int rc = mpc_inputs_check(h, B, steered, x0, feet, stamp, vel, x_ref, foot, contact, pcom)) return rc;
+    // (the v_ref form leaves its gait to the device form behind the staging, as it always has: B = 0 is OK with any gait)
+    if (const char* why = steered ? gait_fault(gait) : nullptr) { h->err = std::string("invalid srbdqp_gait ") + why; return SRBDQP_E_INVALID; }
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
+    double *dx0, *dfe, *dst, *dv, *dxr, *dft, *dpc, *dlp, *dly;
+    uint8_t *dsd, *dct;
+    return host_call(h, [&](HostIo& io) {
+        dx0 = io.in<double>(x0, b * 13 * 8); dfe = io.in<double>(feet, b * 12 * 8); dst = io.in<double>(stamp, b * 8); dv = io.in<double>(vel, b * (steered ? 3 : 2) * 8);
+        dsd = io.in<uint8_t>(standing, b);
+        dxr = io.out<double>(x_ref, b * N * 13 * 8); dft = io.out<double>(foot, b * N * 12 * 8); dct = io.out<uint8_t>(contact, b * N * 4);
+        dpc = io.out<double>(pcom, b * N * 3 * 8); dlp = io.out<double>(landing, b * 3 * 8); dly = io.out<double>(landing_yaw, b * 8);
+    }, [&](hipStream_t st) { return mpc_inputs_device(h, B, steered, dx0, dfe, dst, dv, dsd, gait, dxr, dft, dct, dpc, dlp, dly, st); });
+}
+
+// ---- the K-step loop: one argument record, one check, one loop, one host path for the six srbdqp_fleet_rollout_* entry points ----
+// what a roll-out does beside mpc_inputs -> solve -> fleet_advance: an observer behind every plant step (section 19), steered inputs and footholds (section 20).
+// (The ground is the handle's: a terrain set makes any of them a terrain roll-out, section 18)
+enum : unsigned { kObserved = 1u, kSteered = 2u };
+
+// the arguments of a roll-out, as its entry point got them: device addresses, or the caller's host arrays (fleet_rollout_host)
+struct RolloutArgs {
+    int64_t B; int32_t T;
+    double *x, *feet, *stamp;
+    const double* v_ref;               // [B][2], null in a steered roll-out
+    const double* command;             // [B][3] held (command_steps 1) or [T][B][3] (command_steps T); null unless steered
+    int32_t command_steps;
+    const uint8_t* standing; const double* push; const srbdqp_fleet_settings* cfg; uint8_t* alive;
+    double *x_log, *u0_log, *feet_log; int32_t *status_log, *iters_log;
+    const srbdqp_observer_settings* obs; double *w_est, *w_log;   // read in an observed roll-out only
+    unsigned flavour;                  // kSteered: srbdqp_fleet_rollout_steered_*, which with obs is kObserved too; kObserved: ..._observed_*
+    const char* fn;                    // the roll-out the call becomes, for error texts: srbdqp_fleet_rollout or srbdqp_fleet_rollout_observed
+};
+
+// the horizon buffers of a roll-out of this flavour (kObserved | kSteered), at B robots, carved from one allocation of the handle's.  What a flavour has
+// asked for once stays carved
+int ensure_fleet_buffers(srbdqp_handle* h, size_t B, unsigned flavour) {
     auto& f = h->fleet;
     const bool terrain = h->terrain.map.h != nullptr;
-    if (f.mem && f.B >= B && (!terrain || f.normals) && (!observed || f.ew) && (!steered || f.landing_yaw)) return SRBDQP_OK;
-    f.observed = f.observed || observed;
-    f.steered = f.steered || steered;
+    if (f.mem && f.B >= B && (!terrain || f.normals) && (!(flavour & kObserved) || f.ew) && (!(flavour & kSteered) || f.landing_yaw)) return SRBDQP_OK;
+    f.flavour |= flavour;
+    const bool observed = f.flavour & kObserved, steered = f.flavour & kSteered;
     const size_t N = (size_t)h->cfg.horizon;
     auto carve = [&](char* base) {
         Carver c(base);
@@ -2924,9 +3003,9 @@ int ensure_fleet_buffers(srbdqp_handle* h, size_t B, bool observed = false, bool
         f.u = c.take<double>(B * N * 12); f.x_out = c.take<double>(B * (N + 1) * 13); f.contact = c.take<uint8_t>(B * N * 4);
         f.status = c.take<int32_t>(B); f.iters = c.take<int32_t>(B);
         f.normals = terrain ? c.take<double>(B * N * 12) : nullptr;
-        f.ew = f.observed ? c.take<double>(B * N * 6) : nullptr;
-        f.ring_x = f.observed ? c.take<double>(2 * B * 13) : nullptr; f.ring_feet = f.observed ? c.take<double>(2 * B * 12) : nullptr;
-        f.landing_yaw = f.steered ? c.take<double>(B) : nullptr;
+        f.ew = observed ? c.take<double>(B * N * 6) : nullptr;
+        f.ring_x = observed ? c.take<double>(2 * B * 13) : nullptr; f.ring_feet = observed ? c.take<double>(2 * B * 12) : nullptr;
+        f.landing_yaw = steered ? c.take<double>(B) : nullptr;
         return c.off;
     };
     const size_t want = carve(nullptr);
@@ -2940,24 +3019,6 @@ int ensure_fleet_buffers(srbdqp_handle* h, size_t B, bool observed = false, bool
     f.bytes = cap;
     carve(f.mem);
     f.B = B;
-    return SRBDQP_OK;
-}
-
-int fleet_rollout_check(srbdqp_handle* h, int64_t B, int32_t T, const void* x, const void* feet, const void* stamp, const void* v_ref,
-                        const srbdqp_fleet_settings* cfg) {
-    if (B < 1 || T < 1 || B > 0x7fffffffLL) { h->err = "srbdqp_fleet_rollout: B and T must be at least 1 (B at most 2^31 - 1)"; return SRBDQP_E_INVALID; }
-    if (!x || !feet || !stamp || !v_ref) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
-    if (const char* why = fleet_settings_fault(cfg)) { h->err = std::string("invalid srbdqp_fleet_settings: ") + why; return SRBDQP_E_INVALID; }
-    // on a terrain the solves read the normals of the call, and no instantiation reads those beside another side input, on a live horizon, with rank-aware steps
-    // or at N = 24: what the staged normals calls refuse, in the refusal table's words
-    if (h->terrain.map.h) {
-        if (const int rc = check_staged_normals(h, "srbdqp_fleet_rollout")) { h->err += " -- while a terrain is set (srbdqp_set_terrain)"; return rc; }
-        return SRBDQP_OK;
-    }
-    // the plant is flat ground and knows no wrench but the push: a handle whose QPs are told otherwise would roll out against another robot
-    if (h->ext.dev) { h->err = "srbdqp_fleet_rollout: the handle has an external wrench set (srbdqp_set_external_wrench): the plant does not know it -- clear it, and pass the roll-out its push"; return SRBDQP_E_INVALID; }
-    if (h->normals.dev) { h->err = "srbdqp_fleet_rollout: the handle has contact normals set (srbdqp_set_contact_normals): the plant stands on flat ground -- clear them"; return SRBDQP_E_INVALID; }
-    if (const int rc = variant_check_batch(h, (int32_t)B)) return rc;
     return SRBDQP_OK;
 }
 
@@ -2992,35 +3053,78 @@ int wrench_observer_launch(srbdqp_handle* h, int64_t B, const double* x_prev, co
 
 int wrench_observer_check(srbdqp_handle* h, int64_t B, const void* x_prev, const void* x_next, const void* feet_prev, const void* u0, int64_t u0_stride,
                           const srbdqp_observer_settings* cfg, const void* w_est) {
-    if (B < 0 || B > 0x7fffffffLL || (B > 0 && (!x_prev || !x_next || !feet_prev || !u0 || !w_est))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const int rc = arrays_check(h, B >= 0 && B <= 0x7fffffffLL, B, !x_prev || !x_next || !feet_prev || !u0 || !w_est)) return rc;
     if (u0_stride < 12) { h->err = "srbdqp_wrench_observer: u0_stride must be at least 12 doubles"; return SRBDQP_E_INVALID; }
     if (const char* why = observer_settings_fault(cfg)) { h->err = std::string("invalid srbdqp_observer_settings: ") + why; return SRBDQP_E_INVALID; }
     return covers<RobotsIn>(h, B, "srbdqp_wrench_observer: ", " robots with ", false, false);
 }
 
-// May this handle run an observed roll-out?  What the plain one refuses for its arguments; then, for the handle's state, what check_staged_wrench refuses -- in
-// the refusal table's words -- except robot records and weights, which the wrench's batch kernel reads beside the wrench; then a terrain
+// May this handle run this roll-out?  host: the arrays are the caller's host arrays.  In order:
+//  * steered: the command's own rules, which need no handle and come first (host: every entry of the command must be finite);
+//  * the arguments: sizes, arrays, w_est in an observed roll-out, the two settings;
+//  * the handle's state, for the roll-out the call becomes.  Observed: what check_staged_wrench refuses -- in the refusal table's words -- except robot records and
+//    weights, which the wrench's batch kernel reads beside the wrench; then a terrain.  On a terrain: the solves read the normals of the call, and no instantiation
+//    reads those beside another side input, on a live horizon, with rank-aware steps or at N = 24 -- what the staged normals calls refuse, in the refusal table's
+//    words.  Plain: the plant is flat ground and knows no wrench but the push -- a handle whose QPs are told otherwise would roll out against another robot
 constexpr unsigned kFormsObservedRollout = bit(Form::Robots) | bit(Form::Weights);
-int fleet_rollout_observed_check(srbdqp_handle* h, int64_t B, int32_t T, const void* x, const void* feet, const void* stamp, const void* v_ref,
-                                 const srbdqp_fleet_settings* cfg, const srbdqp_observer_settings* obs, const void* w_est) {
-    const char* const fn = "srbdqp_fleet_rollout_observed";
-    const char* const in = " -- in an observed roll-out";
-    if (B < 1 || T < 1 || B > 0x7fffffffLL) { h->err = "srbdqp_fleet_rollout_observed: B and T must be at least 1 (B at most 2^31 - 1)"; return SRBDQP_E_INVALID; }
-    if (!x || !feet || !stamp || !v_ref) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
-    if (!w_est) { h->err = "srbdqp_fleet_rollout_observed: w_est is NULL (the estimate goes in and out: zeros start from no push)"; return SRBDQP_E_INVALID; }
-    if (const char* why = fleet_settings_fault(cfg)) { h->err = std::string("invalid srbdqp_fleet_settings: ") + why; return SRBDQP_E_INVALID; }
-    if (const char* why = observer_settings_fault(obs)) { h->err = std::string("invalid srbdqp_observer_settings: ") + why; return SRBDQP_E_INVALID; }
-    if (const unsigned other = state_of(h) & ~kFormsObservedRollout) { const int rc = refuse(h, refusal_form(other), fn); h->err += in; return rc; }
-    if (h->cfg.horizon > row(Form::ExtWrench).max_horizon) { h->err = std::string(fn) + ": " + ExtWrenchIn::n24(fn) + in; return SRBDQP_E_INVALID; }
-    if (!general_allowed(h->cfg)) {
-        h->err = std::string(fn) + ": " + row(Form::ExtWrench).noun + " is read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH" + in;
-        return SRBDQP_E_INVALID;
+int fleet_rollout_check(srbdqp_handle* h, const RolloutArgs& a, bool host) {
+    if (a.flavour & kSteered) {
+        if (!a.command) return steer_refuse(h, "srbdqp_fleet_rollout_steered: command is NULL ([B][3] held over the call, or [T][B][3] with command_steps = T)");
+        if (a.command_steps != 1 && a.command_steps != a.T) return steer_refuse(h, "srbdqp_fleet_rollout_steered: command_steps must be 1 (one command held) or T (a row per step)");
+        if (host && a.B >= 1 && a.B <= 0x7fffffffLL && a.T >= 1) {
+            const long long i = steer_non_finite(a.command, (size_t)a.command_steps * (size_t)a.B * 3);
+            if (i >= 0) return steer_refuse(h, "srbdqp_fleet_rollout_steered: the command of robot " + std::to_string((i / 3) % a.B) + " at row " + std::to_string(i / (3 * a.B)) + " is not finite");
+        }
     }
-    if (h->terrain.map.h) {
-        h->err = std::string(fn) + ": refused while a terrain is set (srbdqp_set_terrain): no instantiation reads contact normals beside a wrench (DESIGN.md section 13) -- srbdqp_set_terrain(h, NULL, NULL) goes back to flat ground";
-        return SRBDQP_E_INVALID;
+    if (!h) return SRBDQP_E_INVALID;
+    const std::string fn = a.fn;
+    const bool observed = a.flavour & kObserved;
+    if (a.B < 1 || a.T < 1 || a.B > 0x7fffffffLL) { h->err = fn + ": B and T must be at least 1 (B at most 2^31 - 1)"; return SRBDQP_E_INVALID; }
+    if (!a.x || !a.feet || !a.stamp || !(a.v_ref || a.command)) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (observed && !a.w_est) { h->err = fn + ": w_est is NULL (the estimate goes in and out: zeros start from no push)"; return SRBDQP_E_INVALID; }
+    if (const char* why = fleet_settings_fault(a.cfg)) { h->err = std::string("invalid srbdqp_fleet_settings: ") + why; return SRBDQP_E_INVALID; }
+    if (observed) {
+        const char* const in = " -- in an observed roll-out";
+        if (const char* why = observer_settings_fault(a.obs)) { h->err = std::string("invalid srbdqp_observer_settings: ") + why; return SRBDQP_E_INVALID; }
+        if (const unsigned other = state_of(h) & ~kFormsObservedRollout) { const int rc = refuse(h, refusal_form(other), a.fn); h->err += in; return rc; }
+        if (h->cfg.horizon > row(Form::ExtWrench).max_horizon) { h->err = fn + ": " + ExtWrenchIn::n24(a.fn) + in; return SRBDQP_E_INVALID; }
+        if (!general_allowed(h->cfg)) {
+            h->err = fn + ": " + row(Form::ExtWrench).noun + " is read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH" + in;
+            return SRBDQP_E_INVALID;
+        }
+        if (h->terrain.map.h) {
+            h->err = fn + ": refused while a terrain is set (srbdqp_set_terrain): no instantiation reads contact normals beside a wrench (DESIGN.md section 13) -- srbdqp_set_terrain(h, NULL, NULL) goes back to flat ground";
+            return SRBDQP_E_INVALID;
+        }
+    } else if (h->terrain.map.h) {
+        if (const int rc = check_staged_normals(h, a.fn)) { h->err += " -- while a terrain is set (srbdqp_set_terrain)"; return rc; }
+        return SRBDQP_OK;
+    } else {
+        if (h->ext.dev) { h->err = fn + ": the handle has an external wrench set (srbdqp_set_external_wrench): the plant does not know it -- clear it, and pass the roll-out its push"; return SRBDQP_E_INVALID; }
+        if (h->normals.dev) { h->err = fn + ": the handle has contact normals set (srbdqp_set_contact_normals): the plant stands on flat ground -- clear them"; return SRBDQP_E_INVALID; }
     }
-    return variant_check_batch(h, (int32_t)B);   // (records and weights for every robot)
+    return variant_check_batch(h, (int32_t)a.B);   // (records and weights for every robot)
+}
+
+// ---- the ground under the fleet (include/srbdqp_cascade.h; the sample and the kernels: srbdqp_terrain.hpp) ----
+int terrain_sample_check(srbdqp_handle* h, int64_t M, const void* xy, const void* z) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (!h->terrain.map.h) { h->err = "srbdqp_terrain_sample: no terrain is set (srbdqp_set_terrain)"; return SRBDQP_E_INVALID; }
+    return arrays_check(h, M >= 0, M, !xy || !z);
+}
+
+int terrain_inputs_check(srbdqp_handle* h, int64_t B, const void* feet, const void* x_ref, const void* normals) {
+    if (!h) return SRBDQP_E_INVALID;
+    if (!h->terrain.map.h) { h->err = "srbdqp_terrain_inputs: no terrain is set (srbdqp_set_terrain)"; return SRBDQP_E_INVALID; }
+    return arrays_check(h, B >= 0 && B <= 0x7fffffffLL, B, !feet || !x_ref || !normals);
+}
+
+// one launch of the terrain's inputs; the arguments have been checked
+int terrain_inputs_launch(srbdqp_handle* h, int64_t B, const double* feet, double* x_ref, double* normals, hipStream_t st) {
+    srbdqp::TerrainInputsArgs a{h->terrain.map, feet, x_ref, normals, (int32_t)h->cfg.horizon, (long long)B};
+    HIP_TRY(h, srbdqp::launch_terrain_inputs(a, st));
+    h->kname = "terrain_inputs_f64";
+    return SRBDQP_OK;
 }
 
 }  // namespace
@@ -3066,9 +3170,7 @@ int srbdqp_set_terrain(srbdqp_handle* h, const srbdqp_terrain* t, const double* 
 }
 
 int srbdqp_terrain_sample_device_f64(srbdqp_handle* h, int64_t M, const double* xy, double* z, double* normal, void* stream) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (!h->terrain.map.h) { h->err = "srbdqp_terrain_sample: no terrain is set (srbdqp_set_terrain)"; return SRBDQP_E_INVALID; }
-    if (M < 0 || (M > 0 && (!xy || !z))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const int rc = terrain_sample_check(h, M, xy, z)) return rc;
     if (M == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     srbdqp::TerrainSampleArgs a{h->terrain.map, xy, z, normal, (long long)M};
@@ -3078,9 +3180,7 @@ int srbdqp_terrain_sample_device_f64(srbdqp_handle* h, int64_t M, const double* 
 }
 
 int srbdqp_terrain_sample_f64(srbdqp_handle* h, int64_t M, const double* xy, double* z, double* normal) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (!h->terrain.map.h) { h->err = "srbdqp_terrain_sample: no terrain is set (srbdqp_set_terrain)"; return SRBDQP_E_INVALID; }
-    if (M < 0 || (M > 0 && (!xy || !z))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const int rc = terrain_sample_check(h, M, xy, z)) return rc;
     if (M == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t m = (size_t)M;
@@ -3091,21 +3191,14 @@ int srbdqp_terrain_sample_f64(srbdqp_handle* h, int64_t M, const double* xy, dou
 }
 
 int srbdqp_terrain_inputs_device_f64(srbdqp_handle* h, int64_t B, const double* feet, double* x_ref, double* normals, void* stream) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (!h->terrain.map.h) { h->err = "srbdqp_terrain_inputs: no terrain is set (srbdqp_set_terrain)"; return SRBDQP_E_INVALID; }
-    if (B < 0 || B > 0x7fffffffLL || (B > 0 && (!feet || !x_ref || !normals))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const int rc = terrain_inputs_check(h, B, feet, x_ref, normals)) return rc;
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    srbdqp::TerrainInputsArgs a{h->terrain.map, feet, x_ref, normals, (int32_t)h->cfg.horizon, (long long)B};
-    HIP_TRY(h, srbdqp::launch_terrain_inputs(a, stream ? reinterpret_cast<hipStream_t>(stream) : h->stream));
-    h->kname = "terrain_inputs_f64";
-    return SRBDQP_OK;
+    return terrain_inputs_launch(h, B, feet, x_ref, normals, stream ? reinterpret_cast<hipStream_t>(stream) : h->stream);
 }
 
 int srbdqp_terrain_inputs_f64(srbdqp_handle* h, int64_t B, const double* feet, double* x_ref, double* normals) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (!h->terrain.map.h) { h->err = "srbdqp_terrain_inputs: no terrain is set (srbdqp_set_terrain)"; return SRBDQP_E_INVALID; }
-    if (B < 0 || B > 0x7fffffffLL || (B > 0 && (!feet || !x_ref || !normals))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const int rc = terrain_inputs_check(h, B, feet, x_ref, normals)) return rc;
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
@@ -3125,140 +3218,139 @@ int srbdqp_fleet_default_settings(srbdqp_fleet_settings* s) {
     return SRBDQP_OK;
 }
 
-int srbdqp_fleet_advance_device_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
-                                    const double* landing, const uint8_t* standing, const double* push, uint8_t* alive,
-                                    const srbdqp_fleet_settings* cfg, void* stream) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = fleet_advance_check(h, B, x, feet, stamp, u0, u0_stride, landing, cfg)) return rc;
-    if (B == 0) return SRBDQP_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
-    return fleet_advance_launch(h, B, x, feet, stamp, u0, u0_stride, landing, standing, push, alive, cfg, FleetLogs{}, st);
-}
-
-int srbdqp_fleet_advance_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
-                             const double* landing, const uint8_t* standing, const double* push, uint8_t* alive,
-                             const srbdqp_fleet_settings* cfg) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = fleet_advance_check(h, B, x, feet, stamp, u0, u0_stride, landing, cfg)) return rc;
-    if (B == 0) return SRBDQP_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t b = (size_t)B;
-    double *dx, *dfe, *dst, *du, *dlp, *dpu;
-    uint8_t *dsd, *dal;
-    return host_call(h, [&](HostIo& io) {
-        dx = io.add<double>(x, x, b * 13 * 8, false); dfe = io.add<double>(feet, feet, b * 12 * 8, false); dst = io.add<double>(stamp, stamp, b * 8, false);
-        du = io.in<double>(u0, ((b - 1) * (size_t)u0_stride + 12) * 8); dlp = io.in<double>(landing, b * 3 * 8);
-        dsd = io.in<uint8_t>(standing, b); dpu = io.in<double>(push, b * 6 * 8);
-        dal = alive ? io.add<uint8_t>(alive, alive, b, false) : nullptr;
-    }, [&](hipStream_t st) { return srbdqp_fleet_advance_device_f64(h, B, dx, dfe, dst, du, u0_stride, dlp, dsd, dpu, dal, cfg, st); });
-}
-
 }  // extern "C"
 
 namespace {
-// the K-step loop behind its entry points' checks.  obs: the observed roll-out (flat ground) -- the solves read the handle's wrench buffer, which the
-// observer behind every plant step writes; null: the roll-out of section 17 / 18, launch for launch what it was.  command: the steered roll-out (section 20),
-// v_ref unused -- [B][3] held (command_steps 1) or [T][B][3]; null: v_ref, launch for launch what it was
-int fleet_rollout_run(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
-                      const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
-                      double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
-                      const srbdqp_observer_settings* obs, double* w_est, double* w_log, void* stream,
-                      const double* command = nullptr, int32_t command_steps = 1) {
+// the K-step loop; fleet_rollout_check has passed, so a.obs says whether the roll-out is observed (flat ground: the solves read the handle's wrench buffer, which
+// the observer behind every plant step writes) and a.command whether it is steered.  Neither: the roll-out of section 17 / 18
+int fleet_rollout_run(srbdqp_handle* h, const RolloutArgs& a, void* stream) {
     HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int64_t B = a.B;
     const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
-    if (const int rc = ensure_fleet_buffers(h, b, obs != nullptr, command != nullptr)) return rc;
+    if (const int rc = ensure_fleet_buffers(h, b, a.flavour)) return rc;
     const auto& f = h->fleet;
     const bool terrain = h->terrain.map.h != nullptr;
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
-    if (x_log) HIP_TRY(h, hipMemcpyAsync(x_log, x, b * 13 * 8, hipMemcpyDeviceToDevice, st));
-    if (feet_log) HIP_TRY(h, hipMemcpyAsync(feet_log, feet, b * 12 * 8, hipMemcpyDeviceToDevice, st));
-    if (obs) {
+    if (a.x_log) HIP_TRY(h, hipMemcpyAsync(a.x_log, a.x, b * 13 * 8, hipMemcpyDeviceToDevice, st));
+    if (a.feet_log) HIP_TRY(h, hipMemcpyAsync(a.feet_log, a.feet, b * 12 * 8, hipMemcpyDeviceToDevice, st));
+    if (a.obs) {
         // without the caller's logs the observer reads x_t, x_t+1 and the feet of period t from the ring, which the plant step writes as its log: entry 0 as above
-        if (!x_log) HIP_TRY(h, hipMemcpyAsync(f.ring_x, x, b * 13 * 8, hipMemcpyDeviceToDevice, st));
-        if (!feet_log) HIP_TRY(h, hipMemcpyAsync(f.ring_feet, feet, b * 12 * 8, hipMemcpyDeviceToDevice, st));
+        if (!a.x_log) HIP_TRY(h, hipMemcpyAsync(f.ring_x, a.x, b * 13 * 8, hipMemcpyDeviceToDevice, st));
+        if (!a.feet_log) HIP_TRY(h, hipMemcpyAsync(f.ring_feet, a.feet, b * 12 * 8, hipMemcpyDeviceToDevice, st));
         // the wrench of solve 0: decay^k times the caller's estimate
-        if (const int rc = wrench_observer_launch(h, B, nullptr, nullptr, nullptr, nullptr, 12, nullptr, obs, w_est, f.ew, nullptr, true, st)) return rc;
+        if (const int rc = wrench_observer_launch(h, B, nullptr, nullptr, nullptr, nullptr, 12, nullptr, a.obs, a.w_est, f.ew, nullptr, true, st)) return rc;
     }
-    for (int32_t t = 0; t < T; ++t) {
+    for (int32_t t = 0; t < a.T; ++t) {
         const size_t k = (size_t)t;
-        // command: the steered roll-out (section 20) -- row t of a schedule, or the one command held -- whose inputs also say how the next foot lands turned
-        if (command) {
-            if (const int rc = mpc_inputs_steered_launch(h, B, x, feet, stamp, command + (command_steps == 1 ? 0 : k * b * 3), standing, &cfg->gait, f.x_ref, f.foot, f.contact,
-                                                         f.pcom, f.landing, f.landing_yaw, st)) return rc;
-        } else
-        if (const int rc = srbdqp_mpc_inputs_device_f64(h, B, x, feet, stamp, v_ref, standing, &cfg->gait, f.x_ref, f.foot, f.contact, f.pcom, f.landing, st)) return rc;
-        if (terrain) {
-            // the ground under the footholds: the normals of this step's QPs and the height reference, then the solve a device-buffer call makes with those normals
-            // as the normals of THIS call -- every pass of it, deferred ones on the tail stream included, launches with this Call (solve_device_impl)
-            if (const int rc = srbdqp_terrain_inputs_device_f64(h, B, feet, f.x_ref, f.normals, st)) return rc;
-            Call c;
-            c.use_hint = true; c.cn_call = f.normals;
-            c.plan = plan_solve(h, c, (int)B, maxs_or(h->cfg, 4));
-            if (const int rc = solve_device_impl(h, c, (int32_t)B, x, f.x_ref, f.foot, f.contact, f.pcom, nullptr, nullptr, f.u, f.x_out, nullptr, f.status, f.iters, st))
-                return rc;
-        } else if (obs) {
-            // the solve a device-buffer call makes with the wrench buffer as the wrench of THIS call: the general kernel's _ew instantiation, which reads the handle's
-            // weights and robot records too -- every pass of it, deferred ones on the tail stream included, launches with this Call (solve_device_impl)
-            Call c;
-            c.use_hint = true; c.ext_call = f.ew;
-            c.plan = plan_solve(h, c, (int)B, maxs_or(h->cfg, 4));
-            if (const int rc = solve_device_impl(h, c, (int32_t)B, x, f.x_ref, f.foot, f.contact, f.pcom, nullptr, nullptr, f.u, f.x_out, nullptr, f.status, f.iters, st))
-                return rc;
-        } else
-        if (const int rc = srbdqp_solve_batch_device_f64(h, (int32_t)B, x, f.x_ref, f.foot, f.contact, f.pcom, nullptr, nullptr, f.u, f.x_out, nullptr, f.status,
-                                                         f.iters, st)) return rc;
+        // steered: row t of a schedule, or the one command held; the inputs also say how the next foot lands turned (section 20)
+        if (const int rc = a.command ? mpc_inputs_steered_launch(h, B, a.x, a.feet, a.stamp, a.command + (a.command_steps == 1 ? 0 : k * b * 3), a.standing, &a.cfg->gait,
+                                                                 f.x_ref, f.foot, f.contact, f.pcom, f.landing, f.landing_yaw, st)
+                                     : mpc_inputs_launch(h, B, a.x, a.feet, a.stamp, a.v_ref, a.standing, &a.cfg->gait, f.x_ref, f.foot, f.contact, f.pcom, f.landing, st))
+            return rc;
+        // the ground under the footholds: the normals of this step's QPs and the height reference
+        if (terrain) if (const int rc = terrain_inputs_launch(h, B, a.feet, f.x_ref, f.normals, st)) return rc;
+        // the solve a device-buffer call makes (device_call), on a terrain with those normals as the normals of THIS call, observed with the wrench buffer as the wrench
+        // of THIS call (the general kernel's _ew instantiation, which reads the handle's weights and robot records too) -- every pass of it, deferred ones on the
+        // tail stream included, launches with this Call (solve_device_impl)
+        Call c;
+        c.use_hint = true; c.cn_call = terrain ? f.normals : nullptr; c.ext_call = a.obs ? f.ew : nullptr;
+        c.plan = plan_solve(h, c, (int)B, maxs_or(h->cfg, 4));
+        if (const int rc = solve_device_impl(h, c, (int32_t)B, a.x, f.x_ref, f.foot, f.contact, f.pcom, nullptr, nullptr, f.u, f.x_out, nullptr, f.status, f.iters, st))
+            return rc;
         if (h->cfg.flags & SRBDQP_FLAG_DEFER_TAIL) if (const int rc = srbdqp_flush(h, st)) return rc;   // the plant needs complete forces
         FleetLogs lg;
-        lg.x = x_log ? x_log + (k + 1) * b * 13 : nullptr; lg.feet = feet_log ? feet_log + (k + 1) * b * 12 : nullptr; lg.u0 = u0_log ? u0_log + k * b * 12 : nullptr;
+        lg.x = a.x_log ? a.x_log + (k + 1) * b * 13 : nullptr; lg.feet = a.feet_log ? a.feet_log + (k + 1) * b * 12 : nullptr; lg.u0 = a.u0_log ? a.u0_log + k * b * 12 : nullptr;
         lg.status = f.status; lg.iters = f.iters;
-        lg.status_log = status_log ? status_log + k * b : nullptr; lg.iters_log = iters_log ? iters_log + k * b : nullptr;
+        lg.status_log = a.status_log ? a.status_log + k * b : nullptr; lg.iters_log = a.iters_log ? a.iters_log + k * b : nullptr;
         // (observed, without the caller's logs: the state and the feet behind period t go to the ring's other slot)
         const double *x_prev = nullptr, *feet_prev = nullptr;
-        if (obs) {
-            x_prev = x_log ? x_log + k * b * 13 : f.ring_x + (k & 1) * b * 13;
-            feet_prev = feet_log ? feet_log + k * b * 12 : f.ring_feet + (k & 1) * b * 12;
-            if (!x_log) lg.x = f.ring_x + ((k + 1) & 1) * b * 13;
-            if (!feet_log) lg.feet = f.ring_feet + ((k + 1) & 1) * b * 12;
+        if (a.obs) {
+            x_prev = a.x_log ? a.x_log + k * b * 13 : f.ring_x + (k & 1) * b * 13;
+            feet_prev = a.feet_log ? a.feet_log + k * b * 12 : f.ring_feet + (k & 1) * b * 12;
+            if (!a.x_log) lg.x = f.ring_x + ((k + 1) & 1) * b * 13;
+            if (!a.feet_log) lg.feet = f.ring_feet + ((k + 1) & 1) * b * 12;
         }
-        if (const int rc = fleet_advance_launch(h, B, x, feet, stamp, f.u, (int64_t)(12 * N), f.landing, standing, push ? push + k * b * 6 : nullptr, alive, cfg, lg, st,
-                                                command ? f.landing_yaw : nullptr))
+        if (const int rc = fleet_advance_launch(h, B, a.x, a.feet, a.stamp, f.u, (int64_t)(12 * N), f.landing, a.command ? f.landing_yaw : nullptr, a.standing,
+                                                a.push ? a.push + k * b * 6 : nullptr, a.alive, a.cfg, lg, st))
             return rc;
         // the observer over period t: the estimate behind it, and the wrench solve t + 1 reads
-        if (obs) if (const int rc = wrench_observer_launch(h, B, x_prev, lg.x, feet_prev, f.u, (int64_t)(12 * N), alive, obs, w_est, f.ew, w_log ? w_log + k * b * 6 : nullptr, false, st))
+        if (a.obs) if (const int rc = wrench_observer_launch(h, B, x_prev, lg.x, feet_prev, f.u, (int64_t)(12 * N), a.alive, a.obs, a.w_est, f.ew, a.w_log ? a.w_log + k * b * 6 : nullptr, false, st))
             return rc;
     }
     return SRBDQP_OK;
+}
+
+int fleet_rollout_device(srbdqp_handle* h, const RolloutArgs& a, void* stream) {
+    if (const int rc = fleet_rollout_check(h, a, false)) return rc;
+    return fleet_rollout_run(h, a, stream);
+}
+
+// the roll-out on the caller's host arrays: what is present is staged around the loop
+int fleet_rollout_host(srbdqp_handle* h, RolloutArgs a) {
+    if (const int rc = fleet_rollout_check(h, a, true)) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)a.B, steps = (size_t)a.T;
+    RolloutArgs d = a;   // the same call on device addresses
+    return host_call(h, [&](HostIo& io) {
+        d.x = io.add<double>(a.x, a.x, b * 13 * 8, false); d.feet = io.add<double>(a.feet, a.feet, b * 12 * 8, false); d.stamp = io.add<double>(a.stamp, a.stamp, b * 8, false);
+        d.v_ref = io.in<double>(a.v_ref, b * 2 * 8); d.command = io.in<double>(a.command, (size_t)a.command_steps * b * 3 * 8);
+        d.standing = io.in<uint8_t>(a.standing, b); d.push = io.in<double>(a.push, steps * b * 6 * 8);
+        d.alive = a.alive ? io.add<uint8_t>(a.alive, a.alive, b, false) : nullptr;
+        d.x_log = io.out<double>(a.x_log, (steps + 1) * b * 13 * 8); d.u0_log = io.out<double>(a.u0_log, steps * b * 12 * 8); d.feet_log = io.out<double>(a.feet_log, (steps + 1) * b * 12 * 8);
+        d.status_log = io.out<int32_t>(a.status_log, steps * b * 4); d.iters_log = io.out<int32_t>(a.iters_log, steps * b * 4);
+        if (a.obs) { d.w_est = io.add<double>(a.w_est, a.w_est, b * 6 * 8, false); d.w_log = io.out<double>(a.w_log, steps * b * 6 * 8); }
+    }, [&](hipStream_t st) { return fleet_rollout_run(h, d, st); });
 }
 }  // namespace
 
 extern "C" {
 
-int srbdqp_fleet_rollout_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
-                                    const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
-                                    double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log, void* stream) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = fleet_rollout_check(h, B, T, x, feet, stamp, v_ref, cfg)) return rc;
-    return fleet_rollout_run(h, B, T, x, feet, stamp, v_ref, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log, nullptr, nullptr, nullptr, stream);
+int srbdqp_fleet_advance_device_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
+                                    const double* landing, const uint8_t* standing, const double* push, uint8_t* alive,
+                                    const srbdqp_fleet_settings* cfg, void* stream) {
+    return fleet_advance_device(h, B, x, feet, stamp, u0, u0_stride, landing, nullptr, false, standing, push, alive, cfg, stream);
 }
 
-int srbdqp_fleet_rollout_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
-                             const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
-                             double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = fleet_rollout_check(h, B, T, x, feet, stamp, v_ref, cfg)) return rc;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t b = (size_t)B, steps = (size_t)T;
-    double *dx, *dfe, *dst, *dv, *dpu, *dxl, *dul, *dfl;
-    uint8_t *dsd, *dal;
-    int32_t *dsl, *dil;
-    return host_call(h, [&](HostIo& io) {
-        dx = io.add<double>(x, x, b * 13 * 8, false); dfe = io.add<double>(feet, feet, b * 12 * 8, false); dst = io.add<double>(stamp, stamp, b * 8, false);
-        dv = io.in<double>(v_ref, b * 2 * 8); dsd = io.in<uint8_t>(standing, b); dpu = io.in<double>(push, steps * b * 6 * 8);
-        dal = alive ? io.add<uint8_t>(alive, alive, b, false) : nullptr;
-        dxl = io.out<double>(x_log, (steps + 1) * b * 13 * 8); dul = io.out<double>(u0_log, steps * b * 12 * 8); dfl = io.out<double>(feet_log, (steps + 1) * b * 12 * 8);
-        dsl = io.out<int32_t>(status_log, steps * b * 4); dil = io.out<int32_t>(iters_log, steps * b * 4);
-    }, [&](hipStream_t st) { return srbdqp_fleet_rollout_device_f64(h, B, T, dx, dfe, dst, dv, dsd, dpu, cfg, dal, dxl, dul, dfl, dsl, dil, st); });
+int srbdqp_fleet_advance_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
+                             const double* landing, const uint8_t* standing, const double* push, uint8_t* alive,
+                             const srbdqp_fleet_settings* cfg) {
+    return fleet_advance_host(h, B, x, feet, stamp, u0, u0_stride, landing, nullptr, false, standing, push, alive, cfg);
+}
+
+int srbdqp_fleet_advance_steered_device_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
+                                            const double* landing, const double* landing_yaw, const uint8_t* standing, const double* push, uint8_t* alive,
+                                            const srbdqp_fleet_settings* cfg, void* stream) {
+    return fleet_advance_device(h, B, x, feet, stamp, u0, u0_stride, landing, landing_yaw, true, standing, push, alive, cfg, stream);
+}
+
+int srbdqp_fleet_advance_steered_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
+                                     const double* landing, const double* landing_yaw, const uint8_t* standing, const double* push, uint8_t* alive,
+                                     const srbdqp_fleet_settings* cfg) {
+    return fleet_advance_host(h, B, x, feet, stamp, u0, u0_stride, landing, landing_yaw, true, standing, push, alive, cfg);
+}
+
+int srbdqp_mpc_inputs_device_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp,
+                                 const double* v_ref, const uint8_t* standing, const srbdqp_gait* gait,
+                                 double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, void* stream) {
+    return mpc_inputs_device(h, B, false, x0, feet, stamp, v_ref, standing, gait, x_ref, foot, contact, pcom, landing, nullptr, stream);
+}
+
+int srbdqp_mpc_inputs_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp,
+                          const double* v_ref, const uint8_t* standing, const srbdqp_gait* gait,
+                          double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing) {
+    return mpc_inputs_host(h, B, false, x0, feet, stamp, v_ref, standing, gait, x_ref, foot, contact, pcom, landing, nullptr);
+}
+
+int srbdqp_mpc_inputs_steered_device_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
+                                         const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
+                                         double* landing, double* landing_yaw, void* stream) {
+    return mpc_inputs_device(h, B, true, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw, stream);
+}
+
+int srbdqp_mpc_inputs_steered_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
+                                  const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
+                                  double* landing, double* landing_yaw) {
+    return mpc_inputs_host(h, B, true, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw);
 }
 
 // ---- the momentum observer (include/srbdqp_cascade.h) ----
@@ -3273,7 +3365,6 @@ int srbdqp_observer_default_settings(srbdqp_observer_settings* s) {
 int srbdqp_wrench_observer_device_f64(srbdqp_handle* h, int64_t B, const double* x_prev, const double* x_next, const double* feet_prev, const double* u0,
                                       int64_t u0_stride, const uint8_t* alive, const srbdqp_observer_settings* cfg, double* w_est, double* ew_out,
                                       void* stream) {
-    if (!h) return SRBDQP_E_INVALID;
     if (const int rc = wrench_observer_check(h, B, x_prev, x_next, feet_prev, u0, u0_stride, cfg, w_est)) return rc;
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -3283,7 +3374,6 @@ int srbdqp_wrench_observer_device_f64(srbdqp_handle* h, int64_t B, const double*
 
 int srbdqp_wrench_observer_f64(srbdqp_handle* h, int64_t B, const double* x_prev, const double* x_next, const double* feet_prev, const double* u0,
                                int64_t u0_stride, const uint8_t* alive, const srbdqp_observer_settings* cfg, double* w_est, double* ew_out) {
-    if (!h) return SRBDQP_E_INVALID;
     if (const int rc = wrench_observer_check(h, B, x_prev, x_next, feet_prev, u0, u0_stride, cfg, w_est)) return rc;
     if (B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -3297,151 +3387,52 @@ int srbdqp_wrench_observer_f64(srbdqp_handle* h, int64_t B, const double* x_prev
     }, [&](hipStream_t st) { return srbdqp_wrench_observer_device_f64(h, B, dx0, dx1, dfe, du, u0_stride, dal, cfg, dw, dew, st); });
 }
 
+// ---- the six roll-outs: each fills the record (RolloutArgs) and calls through ----
+int srbdqp_fleet_rollout_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
+                                    const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                    double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log, void* stream) {
+    return fleet_rollout_device(h, {B, T, x, feet, stamp, v_ref, nullptr, 1, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log,
+                                    nullptr, nullptr, nullptr, 0, "srbdqp_fleet_rollout"}, stream);
+}
+
+int srbdqp_fleet_rollout_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
+                             const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                             double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log) {
+    return fleet_rollout_host(h, {B, T, x, feet, stamp, v_ref, nullptr, 1, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log,
+                                  nullptr, nullptr, nullptr, 0, "srbdqp_fleet_rollout"});
+}
+
 int srbdqp_fleet_rollout_observed_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
                                              const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
                                              double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
                                              const srbdqp_observer_settings* obs, double* w_est, double* w_log, void* stream) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = fleet_rollout_observed_check(h, B, T, x, feet, stamp, v_ref, cfg, obs, w_est)) return rc;
-    return fleet_rollout_run(h, B, T, x, feet, stamp, v_ref, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log, obs, w_est, w_log, stream);
+    return fleet_rollout_device(h, {B, T, x, feet, stamp, v_ref, nullptr, 1, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log,
+                                    obs, w_est, w_log, kObserved, "srbdqp_fleet_rollout_observed"}, stream);
 }
 
 int srbdqp_fleet_rollout_observed_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
                                       const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
                                       double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
                                       const srbdqp_observer_settings* obs, double* w_est, double* w_log) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = fleet_rollout_observed_check(h, B, T, x, feet, stamp, v_ref, cfg, obs, w_est)) return rc;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t b = (size_t)B, steps = (size_t)T;
-    double *dx, *dfe, *dst, *dv, *dpu, *dxl, *dul, *dfl, *dw, *dwl;
-    uint8_t *dsd, *dal;
-    int32_t *dsl, *dil;
-    return host_call(h, [&](HostIo& io) {
-        dx = io.add<double>(x, x, b * 13 * 8, false); dfe = io.add<double>(feet, feet, b * 12 * 8, false); dst = io.add<double>(stamp, stamp, b * 8, false);
-        dv = io.in<double>(v_ref, b * 2 * 8); dsd = io.in<uint8_t>(standing, b); dpu = io.in<double>(push, steps * b * 6 * 8);
-        dal = alive ? io.add<uint8_t>(alive, alive, b, false) : nullptr;
-        dxl = io.out<double>(x_log, (steps + 1) * b * 13 * 8); dul = io.out<double>(u0_log, steps * b * 12 * 8); dfl = io.out<double>(feet_log, (steps + 1) * b * 12 * 8);
-        dsl = io.out<int32_t>(status_log, steps * b * 4); dil = io.out<int32_t>(iters_log, steps * b * 4);
-        dw = io.add<double>(w_est, w_est, b * 6 * 8, false); dwl = io.out<double>(w_log, steps * b * 6 * 8);
-    }, [&](hipStream_t st) { return srbdqp_fleet_rollout_observed_device_f64(h, B, T, dx, dfe, dst, dv, dsd, dpu, cfg, dal, dxl, dul, dfl, dsl, dil, obs, dw, dwl, st); });
+    return fleet_rollout_host(h, {B, T, x, feet, stamp, v_ref, nullptr, 1, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log,
+                                  obs, w_est, w_log, kObserved, "srbdqp_fleet_rollout_observed"});
 }
 
-// ---- a fleet that steers (include/srbdqp_cascade.h) ----
-int srbdqp_mpc_inputs_steered_device_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
-                                         const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
-                                         double* landing, double* landing_yaw, void* stream) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (B < 0 || B > 0x7fffffffLL || (B > 0 && (!x0 || !feet || !stamp || !command || !x_ref || !foot || !contact || !pcom))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
-    if (const int rc = steer_gait_check(h, gait)) return rc;
-    if (B == 0) return SRBDQP_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
-    return mpc_inputs_steered_launch(h, B, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw, st);
-}
-
-int srbdqp_mpc_inputs_steered_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
-                                  const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
-                                  double* landing, double* landing_yaw) {
-    // (the command is the caller's host array: it is read before the handle is)
-    if (B > 0 && B <= 0x7fffffffLL && command) {
-        const long long i = steer_non_finite(command, (size_t)B * 3);
-        if (i >= 0) return steer_refuse(h, "srbdqp_mpc_inputs_steered: the command of robot " + std::to_string(i / 3) + " is not finite (component " + std::to_string(i % 3) + " of vx, vy, wz)");
-    }
-    if (!h) return SRBDQP_E_INVALID;
-    if (B < 0 || B > 0x7fffffffLL || (B > 0 && (!x0 || !feet || !stamp || !command || !x_ref || !foot || !contact || !pcom))) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
-    if (const int rc = steer_gait_check(h, gait)) return rc;
-    if (B == 0) return SRBDQP_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
-    double *dx0, *dfe, *dst, *dc, *dxr, *dft, *dpc, *dlp, *dly;
-    uint8_t *dsd, *dct;
-    return host_call(h, [&](HostIo& io) {
-        dx0 = io.in<double>(x0, b * 13 * 8); dfe = io.in<double>(feet, b * 12 * 8); dst = io.in<double>(stamp, b * 8); dc = io.in<double>(command, b * 24);
-        dsd = io.in<uint8_t>(standing, b);
-        dxr = io.out<double>(x_ref, b * N * 13 * 8); dft = io.out<double>(foot, b * N * 12 * 8); dct = io.out<uint8_t>(contact, b * N * 4);
-        dpc = io.out<double>(pcom, b * N * 3 * 8); dlp = io.out<double>(landing, b * 3 * 8); dly = io.out<double>(landing_yaw, b * 8);
-    }, [&](hipStream_t st) { return srbdqp_mpc_inputs_steered_device_f64(h, B, dx0, dfe, dst, dc, dsd, gait, dxr, dft, dct, dpc, dlp, dly, st); });
-}
-
-int srbdqp_fleet_advance_steered_device_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
-                                            const double* landing, const double* landing_yaw, const uint8_t* standing, const double* push, uint8_t* alive,
-                                            const srbdqp_fleet_settings* cfg, void* stream) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = fleet_advance_check(h, B, x, feet, stamp, u0, u0_stride, landing, cfg)) return rc;
-    if (B > 0 && !landing_yaw) { h->err = "srbdqp_fleet_advance_steered: landing_yaw is NULL (srbdqp_mpc_inputs_steered_* writes it; srbdqp_fleet_advance_* lands feet unturned)"; return SRBDQP_E_INVALID; }
-    if (B == 0) return SRBDQP_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
-    return fleet_advance_launch(h, B, x, feet, stamp, u0, u0_stride, landing, standing, push, alive, cfg, FleetLogs{}, st, landing_yaw);
-}
-
-int srbdqp_fleet_advance_steered_f64(srbdqp_handle* h, int64_t B, double* x, double* feet, double* stamp, const double* u0, int64_t u0_stride,
-                                     const double* landing, const double* landing_yaw, const uint8_t* standing, const double* push, uint8_t* alive,
-                                     const srbdqp_fleet_settings* cfg) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = fleet_advance_check(h, B, x, feet, stamp, u0, u0_stride, landing, cfg)) return rc;
-    if (B > 0 && !landing_yaw) { h->err = "srbdqp_fleet_advance_steered: landing_yaw is NULL (srbdqp_mpc_inputs_steered_* writes it; srbdqp_fleet_advance_* lands feet unturned)"; return SRBDQP_E_INVALID; }
-    if (B == 0) return SRBDQP_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t b = (size_t)B;
-    double *dx, *dfe, *dst, *du, *dlp, *dly, *dpu;
-    uint8_t *dsd, *dal;
-    return host_call(h, [&](HostIo& io) {
-        dx = io.add<double>(x, x, b * 13 * 8, false); dfe = io.add<double>(feet, feet, b * 12 * 8, false); dst = io.add<double>(stamp, stamp, b * 8, false);
-        du = io.in<double>(u0, ((b - 1) * (size_t)u0_stride + 12) * 8); dlp = io.in<double>(landing, b * 3 * 8); dly = io.in<double>(landing_yaw, b * 8);
-        dsd = io.in<uint8_t>(standing, b); dpu = io.in<double>(push, b * 6 * 8);
-        dal = alive ? io.add<uint8_t>(alive, alive, b, false) : nullptr;
-    }, [&](hipStream_t st) { return srbdqp_fleet_advance_steered_device_f64(h, B, dx, dfe, dst, du, u0_stride, dlp, dly, dsd, dpu, dal, cfg, st); });
-}
-
-}  // extern "C"
-
-namespace {
-// May this handle run a steered roll-out?  The command's own rules, which need no handle and come first (host: the command is the caller's host array, and
-// every entry of it must be finite); then what the roll-out it becomes refuses
-int fleet_rollout_steered_check(srbdqp_handle* h, int64_t B, int32_t T, const void* x, const void* feet, const void* stamp, const double* command, int32_t command_steps,
-                                const srbdqp_fleet_settings* cfg, const srbdqp_observer_settings* obs, const void* w_est, bool host) {
-    if (!command) return steer_refuse(h, "srbdqp_fleet_rollout_steered: command is NULL ([B][3] held over the call, or [T][B][3] with command_steps = T)");
-    if (command_steps != 1 && command_steps != T) return steer_refuse(h, "srbdqp_fleet_rollout_steered: command_steps must be 1 (one command held) or T (a row per step)");
-    if (host && B >= 1 && B <= 0x7fffffffLL && T >= 1) {
-        const long long i = steer_non_finite(command, (size_t)command_steps * (size_t)B * 3);
-        if (i >= 0) return steer_refuse(h, "srbdqp_fleet_rollout_steered: the command of robot " + std::to_string((i / 3) % B) + " at row " + std::to_string(i / (3 * B)) + " is not finite");
-    }
-    if (!h) return SRBDQP_E_INVALID;
-    return obs ? fleet_rollout_observed_check(h, B, T, x, feet, stamp, command, cfg, obs, w_est) : fleet_rollout_check(h, B, T, x, feet, stamp, command, cfg);
-}
-}  // namespace
-
-extern "C" {
-
+// (a steered call with an observer is refused in the observed roll-out's words, one without in the plain one's)
 int srbdqp_fleet_rollout_steered_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
                                             int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
                                             double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
                                             const srbdqp_observer_settings* obs, double* w_est, double* w_log, void* stream) {
-    if (const int rc = fleet_rollout_steered_check(h, B, T, x, feet, stamp, command, command_steps, cfg, obs, w_est, false)) return rc;
-    return fleet_rollout_run(h, B, T, x, feet, stamp, nullptr, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log, obs, obs ? w_est : nullptr,
-                             obs ? w_log : nullptr, stream, command, command_steps);
+    return fleet_rollout_device(h, {B, T, x, feet, stamp, nullptr, command, command_steps, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log,
+                                    obs, w_est, w_log, kSteered | (obs ? kObserved : 0u), obs ? "srbdqp_fleet_rollout_observed" : "srbdqp_fleet_rollout"}, stream);
 }
 
 int srbdqp_fleet_rollout_steered_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
                                      int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
                                      double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
                                      const srbdqp_observer_settings* obs, double* w_est, double* w_log) {
-    if (const int rc = fleet_rollout_steered_check(h, B, T, x, feet, stamp, command, command_steps, cfg, obs, w_est, true)) return rc;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t b = (size_t)B, steps = (size_t)T;
-    double *dx, *dfe, *dst, *dc, *dpu, *dxl, *dul, *dfl, *dw = nullptr, *dwl = nullptr;
-    uint8_t *dsd, *dal;
-    int32_t *dsl, *dil;
-    return host_call(h, [&](HostIo& io) {
-        dx = io.add<double>(x, x, b * 13 * 8, false); dfe = io.add<double>(feet, feet, b * 12 * 8, false); dst = io.add<double>(stamp, stamp, b * 8, false);
-        dc = io.in<double>(command, (size_t)command_steps * b * 3 * 8); dsd = io.in<uint8_t>(standing, b); dpu = io.in<double>(push, steps * b * 6 * 8);
-        dal = alive ? io.add<uint8_t>(alive, alive, b, false) : nullptr;
-        dxl = io.out<double>(x_log, (steps + 1) * b * 13 * 8); dul = io.out<double>(u0_log, steps * b * 12 * 8); dfl = io.out<double>(feet_log, (steps + 1) * b * 12 * 8);
-        dsl = io.out<int32_t>(status_log, steps * b * 4); dil = io.out<int32_t>(iters_log, steps * b * 4);
-        if (obs) { dw = io.add<double>(w_est, w_est, b * 6 * 8, false); dwl = io.out<double>(w_log, steps * b * 6 * 8); }
-    }, [&](hipStream_t st) { return srbdqp_fleet_rollout_steered_device_f64(h, B, T, dx, dfe, dst, dc, command_steps, dsd, dpu, cfg, dal, dxl, dul, dfl, dsl, dil, obs, dw, dwl, st); });
+    return fleet_rollout_host(h, {B, T, x, feet, stamp, nullptr, command, command_steps, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log,
+                                  obs, w_est, w_log, kSteered | (obs ? kObserved : 0u), obs ? "srbdqp_fleet_rollout_observed" : "srbdqp_fleet_rollout"});
 }
 
 }  // extern "C"

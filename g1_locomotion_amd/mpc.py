@@ -544,12 +544,10 @@ class BatchMPC(_Engine):
         pu = None if push is None else _as(push, np.float64, (B, 6), "push")
         al = np.ones(B, np.uint8) if alive is None else np.array(np.asarray(alive) != 0, dtype=np.uint8).reshape(B)
         s = self.fleet_settings(**settings)
-        if landing_yaw is not None:
-            ly = _as(landing_yaw, np.float64, (B,), "landing_yaw")
-            rc = self._lib.srbdqp_fleet_advance_steered_f64(self._h, B, _p(x), _p(f), _p(t), _p(u), NU, _p(lp), _p(ly), _p(sd), _p(pu), _p(al), C.byref(s))
-        else:
-            rc = self._lib.srbdqp_fleet_advance_f64(self._h, B, _p(x), _p(f), _p(t), _p(u), NU, _p(lp), _p(sd), _p(pu), _p(al), C.byref(s))
-        self._check(rc)
+        ly = None if landing_yaw is None else _as(landing_yaw, np.float64, (B,), "landing_yaw")
+        # (the steered call takes landing_yaw behind landing)
+        fn, yaw = (self._lib.srbdqp_fleet_advance_f64, ()) if ly is None else (self._lib.srbdqp_fleet_advance_steered_f64, (_p(ly),))
+        self._check(fn(self._h, B, _p(x), _p(f), _p(t), _p(u), NU, _p(lp), *yaw, _p(sd), _p(pu), _p(al), C.byref(s)))
         return dict(x=x, feet=f, stamp=t, alive=al)
 
     def fleet_advance_device(self, B, x, feet, stamp, u0, landing, u0_stride=NU, standing=0, push=0, alive=0, stream=0, landing_yaw=0, **settings):
@@ -558,14 +556,8 @@ class BatchMPC(_Engine):
         (B,) headings, or 0 for the unsteered step."""
         v = lambda q: C.c_void_p(int(q)) if q else None
         s = self.fleet_settings(**settings)
-        if landing_yaw:
-            rc = self._lib.srbdqp_fleet_advance_steered_device_f64(self._h, int(B), v(x), v(feet), v(stamp), v(u0), int(u0_stride), v(landing), v(landing_yaw),
-                                                                   v(standing), v(push), v(alive), C.byref(s), v(stream))
-            self._check(rc)
-            return
-        rc = self._lib.srbdqp_fleet_advance_device_f64(self._h, int(B), v(x), v(feet), v(stamp), v(u0), int(u0_stride), v(landing), v(standing), v(push),
-                                                       v(alive), C.byref(s), v(stream))
-        self._check(rc)
+        fn, yaw = (self._lib.srbdqp_fleet_advance_steered_device_f64, (v(landing_yaw),)) if landing_yaw else (self._lib.srbdqp_fleet_advance_device_f64, ())
+        self._check(fn(self._h, int(B), v(x), v(feet), v(stamp), v(u0), int(u0_stride), v(landing), *yaw, v(standing), v(push), v(alive), C.byref(s), v(stream)))
 
     # -- a fleet that feels its pushes: the momentum observer (include/srbdqp_cascade.h, DESIGN.md section 19) -------------------------
     def observer_settings(self, gain=0.5, horizon_decay=1.0, torque_max=50.0, force_max=200.0):
@@ -646,34 +638,21 @@ class BatchMPC(_Engine):
         n = max(T, 0)
         xl, ul, fl = np.empty((n + 1, B, NX)), np.empty((n, B, NU)), np.empty((n + 1, B, NU))
         sl, il = np.empty((n, B), np.int32), np.empty((n, B), np.int32)
-        if command is not None:
-            observed = observer is not None and observer is not False
-            if w_est is not None and not observed:
-                raise ValueError("rollout: w_est belongs to an observed roll-out (observer=)")
-            o = self._observer_arg(observer) if observed else None
-            w = (np.zeros((B, 6)) if w_est is None else np.array(w_est, dtype=np.float64).reshape(B, 6)) if observed else None
-            wl = np.empty((n, B, 6)) if observed else None
-            rc = self._lib.srbdqp_fleet_rollout_steered_f64(self._h, B, T, _p(x), _p(f), _p(t), _p(cm), 1 if cm.ndim == 2 else T, _p(sd), _p(pu), C.byref(s), _p(al),
-                                                            _p(xl), _p(ul), _p(fl), _p(sl), _p(il), C.byref(o) if observed else None, _p(w), _p(wl))
-            self._check(rc)
-            out = dict(x=xl, u0=ul, feet=fl, status=sl, iters=il, alive=al, stamp=t)
-            if observed:
-                out.update(w_est=w, w_log=wl)
-            return out
-        if observer is not None and observer is not False:
-            o = self._observer_arg(observer)
-            w = np.zeros((B, 6)) if w_est is None else np.array(w_est, dtype=np.float64).reshape(B, 6)
-            wl = np.empty((n, B, 6))
-            rc = self._lib.srbdqp_fleet_rollout_observed_f64(self._h, B, T, _p(x), _p(f), _p(t), _p(v), _p(sd), _p(pu), C.byref(s), _p(al), _p(xl), _p(ul),
-                                                             _p(fl), _p(sl), _p(il), C.byref(o), _p(w), _p(wl))
-            self._check(rc)
-            return dict(x=xl, u0=ul, feet=fl, status=sl, iters=il, alive=al, stamp=t, w_est=w, w_log=wl)
-        if w_est is not None:
+        observed = observer is not None and observer is not False
+        if w_est is not None and not observed:
             raise ValueError("rollout: w_est belongs to an observed roll-out (observer=)")
-        rc = self._lib.srbdqp_fleet_rollout_f64(self._h, B, T, _p(x), _p(f), _p(t), _p(v), _p(sd), _p(pu), C.byref(s), _p(al), _p(xl), _p(ul), _p(fl),
-                                                _p(sl), _p(il))
-        self._check(rc)
-        return dict(x=xl, u0=ul, feet=fl, status=sl, iters=il, alive=al, stamp=t)
+        out = dict(x=xl, u0=ul, feet=fl, status=sl, iters=il, alive=al, stamp=t)
+        obs = ()
+        if observed:
+            o = self._observer_arg(observer)
+            out.update(w_est=np.zeros((B, 6)) if w_est is None else np.array(w_est, dtype=np.float64).reshape(B, 6), w_log=np.empty((n, B, 6)))
+            obs = (C.byref(o), _p(out["w_est"]), _p(out["w_log"]))
+        if command is not None:     # (one steered call, with its observer or without)
+            fn, vel, obs = self._lib.srbdqp_fleet_rollout_steered_f64, (_p(cm), 1 if cm.ndim == 2 else T), obs or (None, None, None)
+        else:
+            fn, vel = self._lib.srbdqp_fleet_rollout_observed_f64 if observed else self._lib.srbdqp_fleet_rollout_f64, (_p(v),)
+        self._check(fn(self._h, B, T, _p(x), _p(f), _p(t), *vel, _p(sd), _p(pu), C.byref(s), _p(al), _p(xl), _p(ul), _p(fl), _p(sl), _p(il), *obs))
+        return out
 
     def rollout_device(self, B, steps, x, feet, stamp, v_ref, com_target, standing=0, push=0, alive=0, x_log=0, u0_log=0, feet_log=0, status_log=0,
                        iters_log=0, stream=0, observer=None, w_est=0, w_log=0, command=0, command_steps=1, **settings):
@@ -683,30 +662,21 @@ class BatchMPC(_Engine):
         (command_steps=steps) -- the steered roll-out, v_ref 0 then; 0: the call as it was."""
         v = lambda q: C.c_void_p(int(q)) if q else None
         s = self.fleet_settings(com_target, **settings)
-        if command:
-            if v_ref:
-                raise ValueError("rollout_device: command= replaces v_ref (pass v_ref=0)")
-            observed = observer is not None and observer is not False
-            if (w_est or w_log) and not observed:
-                raise ValueError("rollout_device: w_est and w_log belong to an observed roll-out (observer=)")
-            o = self._observer_arg(observer) if observed else None
-            rc = self._lib.srbdqp_fleet_rollout_steered_device_f64(self._h, int(B), int(steps), v(x), v(feet), v(stamp), v(command), int(command_steps), v(standing),
-                                                                   v(push), C.byref(s), v(alive), v(x_log), v(u0_log), v(feet_log), v(status_log), v(iters_log),
-                                                                   C.byref(o) if observed else None, v(w_est), v(w_log), v(stream))
-            self._check(rc)
-            return
-        if observer is not None and observer is not False:
-            o = self._observer_arg(observer)
-            rc = self._lib.srbdqp_fleet_rollout_observed_device_f64(self._h, int(B), int(steps), v(x), v(feet), v(stamp), v(v_ref), v(standing), v(push),
-                                                                    C.byref(s), v(alive), v(x_log), v(u0_log), v(feet_log), v(status_log), v(iters_log),
-                                                                    C.byref(o), v(w_est), v(w_log), v(stream))
-            self._check(rc)
-            return
-        if w_est or w_log:
+        if command and v_ref:
+            raise ValueError("rollout_device: command= replaces v_ref (pass v_ref=0)")
+        observed = observer is not None and observer is not False
+        if (w_est or w_log) and not observed:
             raise ValueError("rollout_device: w_est and w_log belong to an observed roll-out (observer=)")
-        rc = self._lib.srbdqp_fleet_rollout_device_f64(self._h, int(B), int(steps), v(x), v(feet), v(stamp), v(v_ref), v(standing), v(push), C.byref(s),
-                                                       v(alive), v(x_log), v(u0_log), v(feet_log), v(status_log), v(iters_log), v(stream))
-        self._check(rc)
+        obs = ()
+        if observed:
+            o = self._observer_arg(observer)
+            obs = (C.byref(o), v(w_est), v(w_log))
+        if command:     # (one steered call, with its observer or without)
+            fn, vel, obs = self._lib.srbdqp_fleet_rollout_steered_device_f64, (v(command), int(command_steps)), obs or (None, None, None)
+        else:
+            fn, vel = self._lib.srbdqp_fleet_rollout_observed_device_f64 if observed else self._lib.srbdqp_fleet_rollout_device_f64, (v(v_ref),)
+        self._check(fn(self._h, int(B), int(steps), v(x), v(feet), v(stamp), *vel, v(standing), v(push), C.byref(s), v(alive), v(x_log), v(u0_log), v(feet_log),
+                       v(status_log), v(iters_log), *obs, v(stream)))
 
     # -- the ground under the fleet (include/srbdqp_cascade.h, DESIGN.md section 18) ---------------------------------------------------
     def set_terrain(self, heights, origin=(0.0, 0.0), cell=None):

@@ -11,6 +11,7 @@ import c_oracle  # noqa: F401
 import cascade_oracle as co
 import srbd_oracle as orc
 import fleet_twin as ft
+from fleet_loop import _bits, _device_loop, _stamps
 
 pytestmark = pytest.mark.gpu
 N, DT, T = 10, 0.04, 50
@@ -42,14 +43,6 @@ def gpu(eng):
     return eng.rollout(f["x"], f["feet"], f["stamp"], f["v_ref"], T, ft.COM, standing=f["standing"], push=ft.fleet_push(T, 6))
 
 
-def _stamps(stamp0, steps):
-    """stamp of every robot at every step, by the roll-out's own repeated rounded addition -> (steps + 1, B)."""
-    out = [np.asarray(stamp0, np.float64).copy()]
-    for _ in range(steps):
-        out.append(out[-1] + DT)
-    return np.array(out)
-
-
 def _crowd(B, seed, steps):
     """B robots around the nominal stance: random commands, a few standing, stamps anywhere in the gait period, pushes of up to 30 N / 3 N m now and then."""
     rng = np.random.default_rng(seed)
@@ -60,10 +53,6 @@ def _crowd(B, seed, steps):
     standing = (rng.random(B) < 0.2).astype(np.uint8)
     push = np.where(rng.random((steps, B, 1)) < 0.1, rng.uniform(-1.0, 1.0, (steps, B, 6)) * np.array([3.0, 3.0, 0.3, 30.0, 30.0, 30.0]), 0.0)
     return dict(x=x, feet=feet, stamp=stamp, v_ref=v_ref, standing=standing, push=push)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint64 if a.dtype == np.float64 else a.dtype)
 
 
 def test_fleet_advance_against_the_twin(eng, twin):
@@ -108,49 +97,6 @@ def test_fleet_advance_against_the_twin(eng, twin):
         assert np.array_equal(_bits(got["x"][dead]), _bits(x[dead])) and np.array_equal(_bits(got["feet"][dead]), _bits(feet[dead]))
 
 
-def _device_loop(eng, c, B, steps, defer):
-    """The roll-out call, and the same steps driven from here through the three public device calls on the same engine -> two dicts of host arrays."""
-    import torch
-    dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    f64 = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device=dev)
-    alive0 = np.ones(B, np.uint8)
-    if B > 4:
-        alive0[3] = 0
-    out = []
-    for call in (True, False):
-        x, feet, stamp, v, sd, pu, al = up(c["x"]), up(c["feet"]), up(c["stamp"]), up(c["v_ref"]), up(c["standing"]), up(c["push"]), up(alive0)
-        if call:
-            xl, ul, fl = f64(steps + 1, B, 13), f64(steps, B, 12), f64(steps + 1, B, 12)
-            sl, il = torch.zeros((steps, B), dtype=torch.int32, device=dev), torch.zeros((steps, B), dtype=torch.int32, device=dev)
-            eng.rollout_device(B, steps, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, standing=sd.data_ptr(), push=pu.data_ptr(),
-                               alive=al.data_ptr(), x_log=xl.data_ptr(), u0_log=ul.data_ptr(), feet_log=fl.data_ptr(), status_log=sl.data_ptr(),
-                               iters_log=il.data_ptr())
-            eng.synchronize()
-            logs = dict(x_log=xl, u0_log=ul, feet_log=fl, status_log=sl, iters_log=il)
-        else:
-            xr, fo, pc, lp = f64(B, N, 13), f64(B, N, 12), f64(B, N, 3), f64(B, 3)
-            ct = torch.zeros((B, N, 4), dtype=torch.uint8, device=dev)
-            u, xo = f64(B, N, 12), f64(B, N + 1, 13)
-            st, it = torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev)
-            xs, fs, us, ss, its = [x.clone()], [feet.clone()], [], [], []
-            for k in range(steps):
-                eng.mpc_inputs_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, xr.data_ptr(), fo.data_ptr(), ct.data_ptr(),
-                                      pc.data_ptr(), landing=lp.data_ptr(), standing=sd.data_ptr())
-                eng.solve_device(B, x.data_ptr(), xr.data_ptr(), fo.data_ptr(), ct.data_ptr(), u.data_ptr(), x_out=xo.data_ptr(), status=st.data_ptr(),
-                                 iters=it.data_ptr(), pcom=pc.data_ptr())
-                if defer:
-                    eng.flush()
-                eng.fleet_advance_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), u.data_ptr(), lp.data_ptr(), u0_stride=12 * N,
-                                         standing=sd.data_ptr(), push=pu[k].data_ptr(), alive=al.data_ptr())
-                eng.synchronize()
-                xs.append(x.clone()); fs.append(feet.clone()); us.append(u[:, 0].clone()); ss.append(st.clone()); its.append(it.clone())
-            logs = dict(x_log=torch.stack(xs), u0_log=torch.stack(us), feet_log=torch.stack(fs), status_log=torch.stack(ss), iters_log=torch.stack(its))
-        logs.update(x=x, feet=feet, stamp=stamp, alive=al)
-        out.append({k: a.cpu().numpy() for k, a in logs.items()})
-    return out
-
-
 @pytest.mark.parametrize("B,defer", [(33, False), (1, False), (33, True)])
 def test_the_loop_is_the_public_calls(B, defer):
     """rollout_device() over 14 steps against mpc_inputs_device -> solve_device(pcom=) -> fleet_advance_device driven step by step on the same engine: every log
@@ -160,7 +106,7 @@ def test_the_loop_is_the_public_calls(B, defer):
     steps = 14
     c = _crowd(B, 40 + B, steps)
     with BatchMPC(horizon=N, **(dict(flags=_lib.FLAG_DEFER_TAIL) if defer else {})) as e:
-        call, loop = _device_loop(e, c, B, steps, defer)
+        call, loop, _ = _device_loop(e, c, B, steps, defer=defer)
     for k in call:
         assert np.array_equal(_bits(call[k]), _bits(loop[k])), k
     assert np.array_equal(_bits(call["x_log"][-1]), _bits(call["x"])) and np.array_equal(_bits(call["x_log"][0]), _bits(c["x"]))

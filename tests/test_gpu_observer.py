@@ -11,6 +11,7 @@ import pytest
 import c_oracle  # noqa: F401
 import cascade_oracle as co
 import fleet_twin as ft
+from fleet_loop import _bits, _device_loop, _stamps
 import observer_twin as ot
 import side_inputs as si
 import srbd_oracle as orc
@@ -18,10 +19,6 @@ import srbd_oracle as orc
 pytestmark = pytest.mark.gpu
 N, DT = 10, 0.04
 WIDE = dict(torque_max=1e5, force_max=1e5)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint64 if a.dtype == np.float64 else a.dtype)
 
 
 @pytest.fixture(scope="module")
@@ -118,61 +115,6 @@ def _crowd(B, seed, steps):
 OBS = dict(gain=0.5, horizon_decay=0.9)
 
 
-def _device_loop(eng, c, B, steps, defer):
-    """The observed roll-out call, and the same steps driven from here through the public device calls on the same engine -> two dicts of host arrays."""
-    import torch
-    dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    f64 = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device=dev)
-    alive0 = np.ones(B, np.uint8)
-    if B > 4:
-        alive0[3] = 0
-    out = []
-    for call in (True, False):
-        x, feet, stamp, v, sd, pu, al, w = up(c["x"]), up(c["feet"]), up(c["stamp"]), up(c["v_ref"]), up(c["standing"]), up(c["push"]), up(alive0), up(c["w0"])
-        if call:
-            xl, ul, fl, wl = f64(steps + 1, B, 13), f64(steps, B, 12), f64(steps + 1, B, 12), f64(steps, B, 6)
-            sl, il = torch.zeros((steps, B), dtype=torch.int32, device=dev), torch.zeros((steps, B), dtype=torch.int32, device=dev)
-            eng.rollout_device(B, steps, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, standing=sd.data_ptr(), push=pu.data_ptr(),
-                               alive=al.data_ptr(), x_log=xl.data_ptr(), u0_log=ul.data_ptr(), feet_log=fl.data_ptr(), status_log=sl.data_ptr(),
-                               iters_log=il.data_ptr(), observer=OBS, w_est=w.data_ptr(), w_log=wl.data_ptr())
-            eng.synchronize()
-            assert eng.kernel_name() == "wrench_observer_f64"
-            logs = dict(x_log=xl, u0_log=ul, feet_log=fl, status_log=sl, iters_log=il, w_log=wl)
-        else:
-            xr, fo, pc, lp = f64(B, N, 13), f64(B, N, 12), f64(B, N, 3), f64(B, 3)
-            ct = torch.zeros((B, N, 4), dtype=torch.uint8, device=dev)
-            u, xo = f64(B, N, 12), f64(B, N + 1, 13)
-            st, it = torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev)
-            ew = up(ot.horizon(c["w0"], N, OBS["horizon_decay"]))
-            eng.set_external_wrench(ew)                                 # (the device setter: read in place at every solve)
-            try:
-                xs, fs, us, ss, its, ws = [x.clone()], [feet.clone()], [], [], [], []
-                for k in range(steps):
-                    eng.mpc_inputs_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, xr.data_ptr(), fo.data_ptr(), ct.data_ptr(),
-                                          pc.data_ptr(), landing=lp.data_ptr(), standing=sd.data_ptr())
-                    eng.solve_device(B, x.data_ptr(), xr.data_ptr(), fo.data_ptr(), ct.data_ptr(), u.data_ptr(), x_out=xo.data_ptr(), status=st.data_ptr(),
-                                     iters=it.data_ptr(), pcom=pc.data_ptr())
-                    assert eng.kernel_name() == "wrench_f64_n10_ew"
-                    if defer:
-                        eng.flush()
-                    xp, fp = x.clone(), feet.clone()
-                    eng.fleet_advance_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), u.data_ptr(), lp.data_ptr(), u0_stride=12 * N,
-                                             standing=sd.data_ptr(), push=pu[k].data_ptr(), alive=al.data_ptr())
-                    eng.wrench_observer_device(B, xp.data_ptr(), x.data_ptr(), fp.data_ptr(), u.data_ptr(), w.data_ptr(), ew=ew.data_ptr(), u0_stride=12 * N,
-                                               alive=al.data_ptr(), **OBS)
-                    eng.synchronize()
-                    xs.append(x.clone()); fs.append(feet.clone()); us.append(u[:, 0].clone()); ss.append(st.clone()); its.append(it.clone()); ws.append(w.clone())
-            finally:
-                eng.synchronize()
-                eng.set_external_wrench(None)
-            logs = dict(x_log=torch.stack(xs), u0_log=torch.stack(us), feet_log=torch.stack(fs), status_log=torch.stack(ss), iters_log=torch.stack(its),
-                        w_log=torch.stack(ws))
-        logs.update(x=x, feet=feet, stamp=stamp, alive=al, w_est=w)
-        out.append({k: a.cpu().numpy() for k, a in logs.items()})
-    return out
-
-
 @pytest.mark.parametrize("B,defer", [(6, False), (70, False), (70, True)])
 def test_the_loop_is_the_public_calls(B, defer):
     """rollout_device(observer=) over 8 steps against mpc_inputs_device -> set_external_wrench on the device buffer + solve_device -> flush (deferred tails) ->
@@ -182,7 +124,8 @@ def test_the_loop_is_the_public_calls(B, defer):
     steps = 8
     c = _crowd(B, 60 + B, steps)
     with BatchMPC(horizon=N, **(dict(flags=_lib.FLAG_DEFER_TAIL) if defer else {})) as e:
-        call, loop = _device_loop(e, c, B, steps, defer)
+        call, loop, name = _device_loop(e, c, B, steps, "observer", defer=defer, observer=OBS)
+    assert name == "wrench_observer_f64"
     for k in call:
         assert np.array_equal(_bits(call[k]), _bits(loop[k])), k
     assert np.array_equal(_bits(call["w_log"][-1]), _bits(call["w_est"])) and (call["status_log"] == 1).mean() > 0.9
@@ -214,13 +157,6 @@ def test_chunks_compose(eng):
     eng.synchronize()
     assert np.array_equal(_bits(x.cpu().numpy()), _bits(w["x"][-1])) and np.array_equal(_bits(feet.cpu().numpy()), _bits(w["feet"][-1]))
     assert np.array_equal(_bits(we.cpu().numpy()), _bits(w["w_est"]))
-
-
-def _stamps(stamp0, steps):
-    out = [np.asarray(stamp0, np.float64).copy()]
-    for _ in range(steps):
-        out.append(out[-1] + DT)
-    return np.array(out)
 
 
 def test_teacher_forced_parity(eng):

@@ -12,6 +12,7 @@ import pytest
 import c_oracle  # noqa: F401
 import srbd_oracle as orc
 import fleet_twin as ft
+from fleet_loop import _bits, _device_loop
 import steer_twin as stw
 import terrain_twin as tt
 
@@ -28,10 +29,6 @@ def eng():
     e = BatchMPC(horizon=N)
     yield e
     e.close()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint64 if a.dtype == np.float64 else a.dtype)
 
 
 def _crowd(B, seed, steps=0):
@@ -167,77 +164,6 @@ def test_one_steered_period_against_the_twin(eng):
 OBS = dict(gain=0.5, horizon_decay=0.9, torque_max=50.0, force_max=200.0)
 
 
-def _device_loop(eng, c, B, steps, mode, horizon=N):
-    """The steered roll-out call, and the same steps driven from here through the public steered device calls on the same engine -> two dicts of host arrays.
-    mode: "flat", "defer" (a flush behind every solve), "terrain" (normals of the step set on the engine), "observer" (the wrench buffer set on the engine)."""
-    import torch
-    import observer_twin as ot
-    dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    f64 = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device=dev)
-    Nh = horizon
-    alive0 = np.ones(B, np.uint8)
-    alive0[3] = 0
-    w0 = np.random.default_rng(B).uniform(-1.0, 1.0, (B, 6)) * np.array([0.5, 0.5, 0.1, 5.0, 5.0, 5.0])
-    obs = mode == "observer"
-    out = []
-    for call in (True, False):
-        x, feet, stamp, cm, sd, pu, al, w = up(c["x"]), up(c["feet"]), up(c["stamp"]), up(c["command"]), up(c["standing"]), up(c["push"]), up(alive0), up(w0)
-        if call:
-            xl, ul, fl, wl = f64(steps + 1, B, 13), f64(steps, B, 12), f64(steps + 1, B, 12), f64(steps, B, 6)
-            sl, il = torch.zeros((steps, B), dtype=torch.int32, device=dev), torch.zeros((steps, B), dtype=torch.int32, device=dev)
-            eng.rollout_device(B, steps, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), 0, ft.COM, standing=sd.data_ptr(), push=pu.data_ptr(),
-                               alive=al.data_ptr(), x_log=xl.data_ptr(), u0_log=ul.data_ptr(), feet_log=fl.data_ptr(), status_log=sl.data_ptr(),
-                               iters_log=il.data_ptr(), command=cm.data_ptr(), command_steps=1,
-                               **(dict(observer=OBS, w_est=w.data_ptr(), w_log=wl.data_ptr()) if obs else {}))
-            eng.synchronize()
-            logs = dict(x_log=xl, u0_log=ul, feet_log=fl, status_log=sl, iters_log=il)
-            if obs:
-                logs["w_log"] = wl
-        else:
-            xr, fo, pc, lp, ly, cn = f64(B, Nh, 13), f64(B, Nh, 12), f64(B, Nh, 3), f64(B, 3), f64(B), f64(B, Nh, 12)
-            ct = torch.zeros((B, Nh, 4), dtype=torch.uint8, device=dev)
-            u, xo = f64(B, Nh, 12), f64(B, Nh + 1, 13)
-            st, it = torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev)
-            xs, fs, us, ss, its, ws = [x.clone()], [feet.clone()], [], [], [], []
-            if obs:
-                ew = up(ot.horizon(w0, Nh, OBS["horizon_decay"]))
-                eng.set_external_wrench(ew)
-            try:
-                for k in range(steps):
-                    eng.mpc_inputs_steered_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), cm.data_ptr(), ft.COM, xr.data_ptr(), fo.data_ptr(),
-                                                  ct.data_ptr(), pc.data_ptr(), landing=lp.data_ptr(), landing_yaw=ly.data_ptr(), standing=sd.data_ptr())
-                    if mode == "terrain":
-                        eng.terrain_inputs_device(B, feet.data_ptr(), xr.data_ptr(), cn.data_ptr())
-                        eng.set_contact_normals(cn)
-                    eng.solve_device(B, x.data_ptr(), xr.data_ptr(), fo.data_ptr(), ct.data_ptr(), u.data_ptr(), x_out=xo.data_ptr(), status=st.data_ptr(),
-                                     iters=it.data_ptr(), pcom=pc.data_ptr())
-                    if mode == "defer":
-                        eng.flush()
-                    xp, fp = x.clone(), feet.clone()
-                    eng.fleet_advance_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), u.data_ptr(), lp.data_ptr(), u0_stride=12 * Nh,
-                                             standing=sd.data_ptr(), push=pu[k].data_ptr(), alive=al.data_ptr(), landing_yaw=ly.data_ptr())
-                    if obs:
-                        eng.wrench_observer_device(B, xp.data_ptr(), x.data_ptr(), fp.data_ptr(), u.data_ptr(), w.data_ptr(), ew=ew.data_ptr(), u0_stride=12 * Nh,
-                                                   alive=al.data_ptr(), **OBS)
-                    eng.synchronize()
-                    xs.append(x.clone()); fs.append(feet.clone()); us.append(u[:, 0].clone()); ss.append(st.clone()); its.append(it.clone()); ws.append(w.clone())
-            finally:
-                eng.synchronize()
-                if mode == "terrain":
-                    eng.set_contact_normals(None)
-                if obs:
-                    eng.set_external_wrench(None)
-            logs = dict(x_log=torch.stack(xs), u0_log=torch.stack(us), feet_log=torch.stack(fs), status_log=torch.stack(ss), iters_log=torch.stack(its))
-            if obs:
-                logs["w_log"] = torch.stack(ws)
-        logs.update(x=x, feet=feet, stamp=stamp, alive=al)
-        if obs:
-            logs["w_est"] = w
-        out.append({k: a.cpu().numpy() for k, a in logs.items()})
-    return out
-
-
 @pytest.mark.parametrize("B,mode,horizon", [(B77, "flat", 10), (B77, "flat", 7), (6, "defer", 10), (6, "terrain", 10), (6, "observer", 10)])
 def test_the_steered_loop_is_the_public_calls(B, mode, horizon):
     """rollout_device(command=) over 12 steps against mpc_inputs_steered_device -> (terrain_inputs_device + the normals set on the engine) -> solve_device ->
@@ -248,16 +174,61 @@ def test_the_steered_loop_is_the_public_calls(B, mode, horizon):
     steps = 12
     c = _crowd(B, 200 + B + horizon, steps)
     c["feet"] = _turned_feet(c)
+    c["w0"] = np.random.default_rng(B).uniform(-1.0, 1.0, (B, 6)) * np.array([0.5, 0.5, 0.1, 5.0, 5.0, 5.0])
     flags = (_lib.FLAG_DEFER_TAIL if mode == "defer" else 0) | (_lib.FLAG_ANY_HORIZON if horizon == 7 else 0)
     with BatchMPC(horizon=horizon, **(dict(flags=flags) if flags else {})) as e:
         if mode == "terrain":
             e.set_terrain(**tt.rough(8, 8, 5, cell=0.5, origin=(-1.5, -1.5), amp=0.1).args())
-        call, loop = _device_loop(e, c, B, steps, mode, horizon)
+        call, loop, _ = _device_loop(e, c, B, steps, mode, horizon=horizon, observer=OBS)
     for k in call:
         assert np.array_equal(_bits(call[k]), _bits(loop[k])), k
     assert np.array_equal(_bits(call["x_log"][-1]), _bits(call["x"])) and np.array_equal(_bits(call["x_log"][0]), _bits(c["x"]))
     assert (call["status_log"] == 1).mean() > 0.5 and np.any(call["feet_log"][-1] != call["feet_log"][0])
     assert np.array_equal(_bits(call["x_log"][:, 3]), _bits(np.tile(c["x"][3], (steps + 1, 1)))) and call["alive"][3] == 0     # the robot that came in dead held
+
+
+@pytest.mark.parametrize("flavour", ["flat", "terrain", "observed", "steered_observed"])
+def test_host_and_device_buffers_agree(flavour):
+    """rollout() on host arrays against rollout_device() on device copies of the same inputs, B = 6, T = 3, N = 10 -- flat, on a map, observed (all three
+    from v_ref) and steered with the observer: every log and every final array bit for bit.  The host form stages what the flavour has and runs the same loop.
+    (That an observed rollout_device() without logs, through the two-slot ring, ends in the x, feet and w_est of the call with logs: test_gpu_observer.py's
+    test_chunks_compose.)"""
+    import torch
+    from g1_locomotion_amd import BatchMPC
+    B, T = 6, 3
+    steered, observed = flavour.startswith("steered"), flavour.endswith("observed")
+    c = _crowd(B, 31, T)
+    if steered:
+        c["feet"] = _turned_feet(c)
+    else:
+        c["x"][:, 2] = 0.0                                                      # (v_ref is a world-frame velocity: the nominal stance, unturned)
+    v_ref = None if steered else c["command"][:, 0:2].copy()
+    alive0 = np.ones(B, np.uint8)
+    alive0[3] = 0
+    w0 = np.random.default_rng(B).uniform(-1.0, 1.0, (B, 6)) * np.array([0.5, 0.5, 0.1, 5.0, 5.0, 5.0])
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(torch.device("cuda", 0))
+    with BatchMPC(horizon=N) as e:
+        if flavour == "terrain":
+            e.set_terrain(**tt.rough(8, 8, 5, cell=0.5, origin=(-1.5, -1.5), amp=0.1).args())
+        host = e.rollout(c["x"], c["feet"], c["stamp"], v_ref, T, ft.COM, standing=c["standing"], push=c["push"], alive=alive0,
+                         command=c["command"] if steered else None, **(dict(observer=OBS, w_est=w0) if observed else {}))
+        dev = {k: up(a) for k, a in dict(x=c["x"], feet=c["feet"], stamp=c["stamp"], standing=c["standing"], push=c["push"], alive=alive0, w_est=w0,
+                                         vel=c["command"] if steered else v_ref).items()}
+        logs = {k: up(np.full_like(host[k], 7)) for k in ("x", "u0", "feet", "status", "iters") + (("w_log",) if observed else ())}
+        ptr = lambda k: logs[k].data_ptr()
+        e.rollout_device(B, T, dev["x"].data_ptr(), dev["feet"].data_ptr(), dev["stamp"].data_ptr(), 0 if steered else dev["vel"].data_ptr(), ft.COM,
+                         standing=dev["standing"].data_ptr(), push=dev["push"].data_ptr(), alive=dev["alive"].data_ptr(), x_log=ptr("x"), u0_log=ptr("u0"),
+                         feet_log=ptr("feet"), status_log=ptr("status"), iters_log=ptr("iters"),
+                         **(dict(command=dev["vel"].data_ptr(), command_steps=1) if steered else {}),
+                         **(dict(observer=OBS, w_est=dev["w_est"].data_ptr(), w_log=ptr("w_log")) if observed else {}))
+        e.synchronize()
+    for k, a in logs.items():
+        assert np.array_equal(_bits(a.cpu().numpy()), _bits(host[k])), k
+    finals = dict(x=host["x"][-1], feet=host["feet"][-1], stamp=host["stamp"], alive=host["alive"], **(dict(w_est=host["w_est"]) if observed else {}))
+    for k, a in finals.items():
+        assert np.array_equal(_bits(dev[k].cpu().numpy()), _bits(a)), k
+    assert (host["status"] == 1).any() and host["alive"][3] == 0 and np.any(host["x"][-1] != host["x"][0])       # (solves that solved, robots that moved)
+    assert ("w_est" in host) == observed and ("w_log" in host) == observed
 
 
 def test_chunks_and_schedules_compose(eng):

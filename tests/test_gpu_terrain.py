@@ -10,6 +10,7 @@ import pytest
 
 import srbd_oracle as orc
 import fleet_twin as ft
+from fleet_loop import _bits, _device_loop, _stamps
 import side_inputs as si
 import terrain_twin as tt
 
@@ -32,17 +33,6 @@ def rough():
     m = tt.rough(17, 9, seed=11, cell=0.25, origin=(-1.0, -1.0))
     m.h.setflags(write=False)
     return m
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint64 if a.dtype == np.float64 else a.dtype)
-
-
-def _stamps(stamp0, steps):
-    out = [np.asarray(stamp0, np.float64).copy()]
-    for _ in range(steps):
-        out.append(out[-1] + DT)
-    return np.array(out)
 
 
 def _points(m, M, seed):
@@ -239,56 +229,6 @@ def test_fleet_advance_on_the_rough_map_against_the_twin(eng, rough):
         eng.set_terrain(None)
 
 
-def _device_loop(eng, c, B, steps, defer):
-    """The roll-out call, and the same steps driven from here through the public device calls on the same engine -> two dicts of host arrays."""
-    import torch
-    dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    f64 = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device=dev)
-    alive0 = np.ones(B, np.uint8)
-    alive0[3] = 0
-    out = []
-    for call in (True, False):
-        x, feet, stamp, v, sd, pu, al = up(c["x"]), up(c["feet"]), up(c["stamp"]), up(c["v_ref"]), up(c["standing"]), up(c["push"]), up(alive0)
-        if call:
-            xl, ul, fl = f64(steps + 1, B, 13), f64(steps, B, 12), f64(steps + 1, B, 12)
-            sl, il = torch.zeros((steps, B), dtype=torch.int32, device=dev), torch.zeros((steps, B), dtype=torch.int32, device=dev)
-            eng.rollout_device(B, steps, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, standing=sd.data_ptr(), push=pu.data_ptr(),
-                               alive=al.data_ptr(), x_log=xl.data_ptr(), u0_log=ul.data_ptr(), feet_log=fl.data_ptr(), status_log=sl.data_ptr(),
-                               iters_log=il.data_ptr())
-            eng.synchronize()
-            name = eng.kernel_name()
-            logs = dict(x_log=xl, u0_log=ul, feet_log=fl, status_log=sl, iters_log=il)
-        else:
-            xr, fo, pc, lp, cn = f64(B, N, 13), f64(B, N, 12), f64(B, N, 3), f64(B, 3), f64(B, N, 12)
-            ct = torch.zeros((B, N, 4), dtype=torch.uint8, device=dev)
-            u, xo = f64(B, N, 12), f64(B, N + 1, 13)
-            st, it = torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev)
-            xs, fs, us, ss, its = [x.clone()], [feet.clone()], [], [], []
-            try:
-                for k in range(steps):
-                    eng.mpc_inputs_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, xr.data_ptr(), fo.data_ptr(), ct.data_ptr(),
-                                          pc.data_ptr(), landing=lp.data_ptr(), standing=sd.data_ptr())
-                    eng.terrain_inputs_device(B, feet.data_ptr(), xr.data_ptr(), cn.data_ptr())
-                    eng.set_contact_normals(cn)                                   # (a CUDA tensor: srbdqp_set_contact_normals_device)
-                    eng.solve_device(B, x.data_ptr(), xr.data_ptr(), fo.data_ptr(), ct.data_ptr(), u.data_ptr(), x_out=xo.data_ptr(), status=st.data_ptr(),
-                                     iters=it.data_ptr(), pcom=pc.data_ptr())
-                    assert eng.kernel_name() == f"wrench_f64_n{N}_cn"
-                    if defer:
-                        eng.flush()
-                    eng.fleet_advance_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), u.data_ptr(), lp.data_ptr(), u0_stride=12 * N,
-                                             standing=sd.data_ptr(), push=pu[k].data_ptr(), alive=al.data_ptr())
-                    eng.synchronize()
-                    xs.append(x.clone()); fs.append(feet.clone()); us.append(u[:, 0].clone()); ss.append(st.clone()); its.append(it.clone())
-            finally:
-                eng.synchronize()
-                eng.set_contact_normals(None)
-            logs = dict(x_log=torch.stack(xs), u0_log=torch.stack(us), feet_log=torch.stack(fs), status_log=torch.stack(ss), iters_log=torch.stack(its))
-        logs.update(x=x, feet=feet, stamp=stamp, alive=al)
-        out.append({k: a.cpu().numpy() for k, a in logs.items()})
-    return out[0], out[1], name
-
-
 @pytest.mark.parametrize("B,defer", [(6, False), (70, False), (70, True)])
 def test_the_loop_is_the_public_calls(rough, B, defer):
     """rollout_device() over 8 steps on the rough map against mpc_inputs_device -> terrain_inputs_device -> set_contact_normals (device) + solve_device ->
@@ -300,7 +240,7 @@ def test_the_loop_is_the_public_calls(rough, B, defer):
     c = _on_the_map(rough, B, 40 + B, steps)
     with BatchMPC(horizon=N, **(dict(flags=_lib.FLAG_DEFER_TAIL) if defer else {})) as e:
         e.set_terrain(**rough.args())
-        call, loop, name = _device_loop(e, c, B, steps, defer)
+        call, loop, name = _device_loop(e, c, B, steps, "terrain", defer=defer)
     assert name == "fleet_advance_terrain_f64"
     for k in call:
         assert np.array_equal(_bits(call[k]), _bits(loop[k])), k
