@@ -1,8 +1,9 @@
 """GPU tests of the fleet roll-out (include/srbdqp_cascade.h srbdqp_fleet_advance_* / srbdqp_fleet_rollout_*), N = 10, against the NumPy
 twin of tests/fleet_twin.py (tests/test_fleet_cpu.py holds the twin itself).
 
-Bounds: the plant in float64 against a long-double one differs by 2.2e-13 over a period on such inputs; 1e-9 absolute on states is the project's bound for
-wbid_reference.  Forces: 2e-3 N, the solver tolerance of the parity suites.  Free-running trajectories: 1e-4, the bound of
+Bounds: the plant in float64 against the SAME scheme in long double differs by 2.2e-13 over a period on such inputs -- that is its rounding error, not its
+accuracy: against the rigid body itself ten RK4 substeps are 1e-4 to 1e-6 away (tests/test_plant_reference_cpu.py, tests/test_gpu_plant_reference.py;
+DESIGN.md section 17 has the table).  1e-9 absolute on states, kernel against twin, is the project's bound for wbid_reference.  Forces: 2e-3 N, the solver tolerance of the parity suites.  Free-running trajectories: 1e-4, the bound of
 test_closed_loop_gpu_engine_stands_and_steps at its length (50 steps)."""
 import numpy as np
 import pytest
