@@ -129,12 +129,11 @@ struct srbdqp_handle {
     int32_t done_seq = 0;
     bool done_cs = false;          // the last launch publishes its completion word with the checksum of its outputs (KArgs::done_cs): wait_done() verifies it
     bool done_cs_x = false;        // ... which cover x_out
-    // the staged wrench calls' own staging array [capacity][N][6] (srbdqp_stage_ext_wrench), pinned and GPU-mapped like the slab; null until the first call asks
-    double* stage_ew_host = nullptr;
-    double* stage_ew_dev = nullptr;
-    // ... and the staged normals calls' [capacity][N][12] (srbdqp_stage_contact_normals), filled with (0, 0, 1): a block nobody wrote is flat ground
-    double* stage_cn_host = nullptr;
-    double* stage_cn_dev = nullptr;
+    // the staging array of each kind of side input a staged call can carry (ExtWrenchIn::staged, NormalsIn::staged), pinned and GPU-mapped like the slab; null
+    // until the first call asks.  The wrench's is [capacity][N][6] (srbdqp_stage_ext_wrench), zero-filled; the normals' [capacity][N][12]
+    // (srbdqp_stage_contact_normals), filled with (0, 0, 1): a block nobody wrote is no wrench / flat ground
+    struct StagedSide { double* host = nullptr; double* dev = nullptr; };
+    StagedSide staged_ext, staged_normals;
     int32_t prepared_B = 0; int prepared_maxs = 4; bool prepared_pcom = false;   // two-phase call: a set-up is pending, on the instantiation plan_two_phase chose
     // kernels whose dynamic-LDS limit has been raised on this handle's device (function attributes are per device, and a
     // process may hold handles on several)
@@ -159,9 +158,9 @@ struct srbdqp_handle {
         double *x_ref = nullptr, *foot = nullptr, *pcom = nullptr, *landing = nullptr, *u = nullptr, *x_out = nullptr;
         uint8_t* contact = nullptr;
         int32_t *status = nullptr, *iters = nullptr;
-        double* normals = nullptr;         // [B][N][12], carved only while a terrain is set: the contact normals of a terrain roll-out's solves (Call::cn_call)
+        double* normals = nullptr;         // [B][N][12], carved only while a terrain is set: the contact normals of a terrain roll-out's solves (Call::side)
         unsigned flavour = 0;              // the roll-out flavours that have asked so far (kObserved | kSteered: ensure_fleet_buffers)
-        // carved once an observed roll-out has asked: the external wrench of its solves (Call::ext_call), [B][N][6], and the two-slot ring of states
+        // carved once an observed roll-out has asked: the external wrench of its solves (Call::side), [B][N][6], and the two-slot ring of states
         // [2][B][13] and footholds [2][B][12] the observer reads where the caller keeps no logs
         double *ew = nullptr, *ring_x = nullptr, *ring_feet = nullptr;
         // carved once a steered roll-out has asked: the heading every robot's next foot lands with, [B] (srbdqp_mpc_inputs_steered_* writes it)
@@ -256,8 +255,8 @@ struct Lazy {
 // ---- which kernel a solve runs: a Plan, decided once per solve by plan_solve() (behind restart_iter_of) and executed by launch() and the launchers ----
 enum class Family { Wave, WaveDefer, Split, Compact, General };   // one wave per QP, ... with deferred tails, the split pipeline, the 4-wave compact kernel, the general kernel
 // General: any (kFormRows below has a row for each but Lat, the staged low-latency instantiation); Compact: Plain or Lat (the dump is a pass's a.mode == 1)
-// (LatExtWrench: the low-latency instantiation of MODE 7, which only a staged wrench call -- Call::ext_call -- plans; no handle state has its bit)
-// (LatNormals: the same for MODE 4 and a staged normals call -- Call::cn_call)
+// (LatExtWrench: the low-latency instantiation of MODE 7, which only a staged wrench call -- Call::side -- plans; no handle state has its bit)
+// (LatNormals: the same for MODE 4 and a staged normals call)
 enum class Form { Plain, Robots, Weights, ExtWrench, Normals, Live, RankAware, Lat, LatExtWrench, LatNormals };
 // the rho restart of restart_iter_of: none, inside the kernel, further launches on the caller's stream (the staged call: started by the host), or off that stream
 // -- the next launch on it (WaveDefer) or a tail stream (solve_deferred_passes, the ragged buckets)
@@ -271,6 +270,17 @@ struct Plan {
     Restart restart = Restart::Off;
 };
 
+// The side input a call brings with it (the staged wrench and normals calls, the solves of an observed or a terrain roll-out), which every pass of the call reads
+// in place of the handle's.  One kind or none: no instantiation reads two.  dev: the device address of the array, [B][N][6] or [B][N][12].  host: the host
+// address of the same memory -- one staged QP carries the input in the argument segment, copied from there -- or null: the array is the device's alone and
+// never goes inline.
+enum class Side { None, ExtWrench, Normals };
+struct CallSide {
+    Side kind = Side::None;
+    const double* dev = nullptr;
+    const double* host = nullptr;
+};
+
 // what one call decides, on the caller's stack: every launch of the call -- restart passes included -- reads the same one, so a later pass runs the
 // kernel the first one did (plan)
 struct Call {
@@ -279,10 +289,7 @@ struct Call {
     bool signal = false;           // the launch publishes the completion word
     bool use_hint = false;         // the dispatch hint applies (it belongs to the device-buffer API)
     Lazy* lazy = nullptr;          // staged path: run only the first pass of a multi-pass solve and hand it back here
-    const double* ext_call = nullptr;   // the staged wrench calls: the wrench of THIS call (device address of the staged array), which every pass of it reads
-    const double* ext_host = nullptr;   // ... and the host address of the same memory (one staged QP: the wrench rides in the argument segment)
-    const double* cn_call = nullptr;    // the staged normals calls: the contact normals of THIS call (device address of the staged array), which every pass of it reads
-    const double* cn_host = nullptr;    // ... and the host address of the same memory (one staged QP: the normals ride in the argument segment)
+    CallSide side;                 // the side input of THIS call, if it brings one
     Plan plan;                     // plan_solve(h, c, B, ...), once the fields above are set
 };
 
@@ -914,7 +921,7 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
         const double* const weights = reinterpret_cast<const double*>(h->weights.dev);
         const double* const robots = reinterpret_cast<const double*>(h->robots.dev);
         // (a staged wrench call -- no side input is set then, the entry points see to it -- brings the wrench of the call: the same kernel over the staged array)
-        if (form == Form::ExtWrench) return launch_side_form<N, Form::ExtWrench, WPS>(h, &srbdqp::srbdqp_wrench_ew_kernel<N, WPS>, a, st, c.ext_call ? c.ext_call : h->ext.dev, weights, robots);
+        if (form == Form::ExtWrench) return launch_side_form<N, Form::ExtWrench, WPS>(h, &srbdqp::srbdqp_wrench_ew_kernel<N, WPS>, a, st, c.side.dev ? c.side.dev : h->ext.dev, weights, robots);
         if (form == Form::Weights) return launch_side_form<N, Form::Weights, WPS>(h, &srbdqp::srbdqp_wrench_wt_kernel<N, WPS>, a, st, weights, robots);
         if (form == Form::Robots) {
             void (*k_rb)(KArgs, const double*) = &srbdqp::srbdqp_wrench_kernel<N, double, double, row(Form::Robots).mode, WPS, double, 5, 0>;
@@ -923,7 +930,7 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
         if (form == Form::Normals) {
             constexpr int WPSN = WrenchTraits<N, double, 8, srbdqp::WrenchLayout<N, row(Form::Normals).mode>>::wps;
             // (a staged normals call -- no side input is set then, the entry points see to it -- brings the normals of the call: the same kernel over the staged array)
-            return launch_side_form<N, Form::Normals, WPSN>(h, &srbdqp::srbdqp_wrench_cn_kernel<N, WPSN>, a, st, c.cn_call ? c.cn_call : h->normals.dev);
+            return launch_side_form<N, Form::Normals, WPSN>(h, &srbdqp::srbdqp_wrench_cn_kernel<N, WPSN>, a, st, c.side.dev ? c.side.dev : h->normals.dev);
         }
     }
     if constexpr (sizeof(R) == 8 && N <= 10) {
@@ -937,34 +944,23 @@ int launch_wrench_t(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t
             return launch_staged_lat<N>(h, c, a, st, &srbdqp::srbdqp_wrench_kernel<N, R, TIO, 0, 1, double, 5, XW>, &srbdqp::srbdqp_wrench_kernel_in<N, XW>,
                                         "_ZN6srbdqp23srbdqp_wrench_kernel_inILi%dELi%dEEEvNS_5KArgsENS_8StagedInIXT_EEE.kd", XW, SL::BT, SL::bytes, nm_lat.c_str());
         }
-        // a staged wrench call of a few QPs: the same waves and pipeline in MODE 7, the wrench's rows for the roll-out behind the mode's slots.  Through HIP on
-        // the caller's stream, every pass: the handle's own queue stays what it is.  One staged QP whose inputs are the staging arrays' own: inputs and wrench in
-        // the argument segment, completion word with the checksum (the *_in twin, as launch_staged_lat chooses it)
+        // a staged wrench or normals call of a few QPs: the same waves and pipeline in MODE 7 (the wrench's rows for the roll-out behind the mode's slots) or in
+        // MODE 4 (on the layout with the table L).  Through HIP on the caller's stream, every pass: the handle's own queue stays what it is.  One staged QP whose
+        // inputs are the staging arrays' own: inputs and side input in the argument segment (the normals: 3,912 of its 4,096 bytes at N = 10), completion word
+        // with the checksum (the *_in twin, as launch_staged_lat chooses it) -- unless the side input has no host address
         // The kernels and their launcher live in srbdqp_wrench_lat_ew.hip, a code object of their own: this one's text stays where it is without them.
-        if (form == Form::LatExtWrench) {
-            static const std::string nm_lew = nm + "_lat" + row(Form::ExtWrench).suffix;
+        if (form == Form::LatExtWrench || form == Form::LatNormals) {
+            const bool cn = form == Form::LatNormals;
+            static const std::string nm_side[2] = {nm + "_lat" + row(Form::ExtWrench).suffix, nm + "_lat" + row(Form::Normals).suffix};
             srbdqp::StagedIn<N> in;
-            const bool inl = !(a.count_ptr || a.tile_sel || !c.ext_host || !staged_inline_inputs<N>(h, c, a, in));
+            const bool inl = !(a.count_ptr || a.tile_sel || !c.side.host || !staged_inline_inputs<N>(h, c, a, in));
             KArgs ai = a;
             if (inl) { ai.inline_in = 1; staged_done_checksum(h, ai); }
-            const bool first = h->lds_attr_done.insert(reinterpret_cast<const void*>(uintptr_t(16 * N + (inl ? 1 : 0)))).second;   // (no function lives at such an address)
-            h->kname = nm_lew.c_str();
-            const hipError_t e = srbdqp::launch_wrench_ew_lat(N, first, ai, inl ? &in : nullptr, c.ext_host, c.ext_call, st);
-            if (e != hipSuccess) { h->err = std::string("launch of ") + nm_lew + ": " + hipGetErrorString(e); return SRBDQP_E_HIP; }
-            return SRBDQP_OK;
-        }
-        // a staged normals call of a few QPs: the same again in MODE 4, on the layout with the table L.  Same translation unit as the wrench's kernels, same
-        // launch path; one staged QP: inputs and normals in the argument segment (3,912 of its 4,096 bytes at N = 10)
-        if (form == Form::LatNormals) {
-            static const std::string nm_lcn = nm + "_lat" + row(Form::Normals).suffix;
-            srbdqp::StagedIn<N> in;
-            const bool inl = !(a.count_ptr || a.tile_sel || !c.cn_host || !staged_inline_inputs<N>(h, c, a, in));
-            KArgs ai = a;
-            if (inl) { ai.inline_in = 1; staged_done_checksum(h, ai); }
-            const bool first = h->lds_attr_done.insert(reinterpret_cast<const void*>(uintptr_t(16 * N + 2 + (inl ? 1 : 0)))).second;   // (no function lives at such an address)
-            h->kname = nm_lcn.c_str();
-            const hipError_t e = srbdqp::launch_wrench_cn_lat(N, first, ai, inl ? &in : nullptr, c.cn_host, c.cn_call, st);
-            if (e != hipSuccess) { h->err = std::string("launch of ") + nm_lcn + ": " + hipGetErrorString(e); return SRBDQP_E_HIP; }
+            // (one key per kernel -- N, kind, inline; no function lives at such an address)
+            const bool first = h->lds_attr_done.insert(reinterpret_cast<const void*>(uintptr_t(16 * N + (cn ? 2 : 0) + (inl ? 1 : 0)))).second;
+            h->kname = nm_side[cn].c_str();
+            const hipError_t e = srbdqp::launch_wrench_side_lat(row(cn ? Form::Normals : Form::ExtWrench).mode, N, first, ai, inl ? &in : nullptr, c.side.host, c.side.dev, st);
+            if (e != hipSuccess) { h->err = std::string("launch of ") + nm_side[cn] + ": " + hipGetErrorString(e); return SRBDQP_E_HIP; }
             return SRBDQP_OK;
         }
     }
@@ -1138,7 +1134,7 @@ Plan plan_solve(const srbdqp_handle* h, const Call& c, int B, int maxs, int neff
     // ---- the general kernel (srbdqp_wrench.hpp)?  The compact kernel exists with up to 4 stance contacts per step at N <= 10, with at most 2 at N = 12 - 20
     // (per-QP records, weights and wrenches, contact normals, a live horizon: only the general kernel reads them)
     const unsigned state = state_of(h);                  // (rank-aware steps alone do not ask for the general kernel: the compact kernels have no wrench steps)
-    general = general || k == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || (state & ~bit(Form::RankAware)) || c.ext_call || c.cn_call;   // (a staged wrench / normals call: MODE 7 / MODE 4, for every contact pattern)
+    general = general || k == SRBDQP_KERNEL_WRENCH || c.f32 || N == 24 || (state & ~bit(Form::RankAware)) || c.side.kind != Side::None;   // (a staged wrench / normals call: MODE 7 / MODE 4, for every contact pattern)
     // N = 20 single support too, for batches: the general kernel holds 2 workgroups per CU there, the compact one 1
     // (tools/schedule_bench.py, 16,384 QPs: 2.85 M QP/s against 1.95 M; at N = 12 / 16 the compact kernel wins, 7.1 / 4.9 M
     // against 5.7 / 4.2 M)
@@ -1156,10 +1152,11 @@ Plan plan_solve(const srbdqp_handle* h, const Call& c, int B, int maxs, int neff
         const bool side = !dump && !c.f32 && N <= kRobotsMaxHorizon;   // (the side-input forms are fp64 batch kernels for N <= 20, and the dump has none)
         p.form = launch_form(side ? state : state & ~kSideInputs);
         if (p.form == Form::Plain && !c.f32 && N <= 10 && lat) p.form = Form::Lat;
-        // a staged wrench call (the entry points admit it on a Plain handle only, N <= 20): the low-latency MODE 7 instantiation where the plain call has one, else the batch one
-        if (c.ext_call) p.form = (N <= 10 && lat) ? Form::LatExtWrench : Form::ExtWrench;
-        // a staged normals call: the same choice between the two MODE 4 instantiations
-        if (c.cn_call) p.form = (N <= 10 && lat) ? Form::LatNormals : Form::Normals;
+        // a call with a side input of its own (the entry points admit a staged one on a Plain handle only, N <= 20): the low-latency MODE 7 / MODE 4 instantiation
+        // where the plain call has one, else the batch one
+        const bool lat_side = N <= 10 && lat;
+        if (c.side.kind == Side::ExtWrench) p.form = lat_side ? Form::LatExtWrench : Form::ExtWrench;
+        else if (c.side.kind == Side::Normals) p.form = lat_side ? Form::LatNormals : Form::Normals;
         p.tile_classes = c.f32 && !c.signal && !(cfg.flags & SRBDQP_FLAG_F64_TILES) && (B >= kTileClassMinBatch || (cfg.flags & SRBDQP_FLAG_F32_TILES));
     } else {
         // ---- the presolved family (srbdqp_compact.hpp): <N, 2> or, at N <= 10, <N, 4>; the one-wave kernel where the QP has at most 64 presolved variables
@@ -1423,7 +1420,9 @@ const char* ext_wrench_fault(const double* v) {
 // A descriptor: the owner's member (of), the element type T, the per-element test (fault), the handle check (form: its row of kFormRows; n24: the N = 24 text), the
 // hipMalloc label (alloc), and the words of the messages (name: srbdqp_set_<name>, srbdqp_ragged_set_<name>; what, which " on a ragged object" follows; count
 // and unit: the "B > length" messages).  RecordIn has what a kind of one record per QP need not say again: the elements per QP (per_qp), the elements one
-// fault test covers (stride), how a message locates element group i (where).
+// fault test covers (stride), how a message locates element group i (where).  The two kinds a staged call can carry (ExtWrenchIn, NormalsIn) also say which
+// Side they are, where the handle keeps their staging array (staged), the value a fresh one holds (neutral), and the words in which the staged texts differ
+// (staged_label: of the hipHostGetDevicePointer message; verb: "<noun> is / are read by the general kernel only"; staged_n24).
 struct RecordIn {
     static constexpr const char* unit = "record";
     static constexpr size_t stride = 1;
@@ -1472,6 +1471,13 @@ struct NormalsIn {
     }
     static std::string count(size_t len) { return "contact normals for " + std::to_string(len); }
     static std::string n24(const char* fn) { return std::string(fn) + ": contact normals: not at N = 24 (no instantiation of the general kernel reads them there, DESIGN.md section 13)"; }
+    // as the side input of a staged call
+    static constexpr Side side = Side::Normals;
+    static constexpr const char* staged_label = "staged normals";
+    static constexpr const char* verb = "are";
+    static srbdqp_handle::StagedSide& staged(srbdqp_handle* h) { return h->staged_normals; }
+    static double neutral(size_t i) { return i % 3 == 2 ? 1.0 : 0.0; }               // every normal (0, 0, 1): zeros would break the rule 0.5 <= |n|
+    static std::string staged_n24(const char* fn) { return n24(fn); }                // (the text carries the call's name itself)
 };
 
 struct ExtWrenchIn {
@@ -1493,6 +1499,18 @@ struct ExtWrenchIn {
     static std::string where(const srbdqp_ragged*, size_t i) { return "the wrench at (row " + std::to_string(i / 6) + ", component " + std::to_string(i % 6) + ")"; }
     static std::string count(size_t len) { return "an external wrench for " + std::to_string(len); }
     static std::string n24(const char*) { return "an external wrench: not at N = 24 (no instantiation of the general kernel reads it there, DESIGN.md section 16)"; }
+    // as the side input of a staged call
+    static constexpr Side side = Side::ExtWrench;
+    static constexpr const char* staged_label = "staged wrench";
+    static constexpr const char* verb = "is";
+    static srbdqp_handle::StagedSide& staged(srbdqp_handle* h) { return h->staged_ext; }
+    static double neutral(size_t) { return 0.0; }
+    static std::string staged_n24(const char* fn) { return std::string(fn) + ": " + n24(fn); }
+};
+
+// no side input: what the plain staged calls are instantiated with
+struct NoSideIn {
+    static constexpr Side side = Side::None;
 };
 
 // may this handle take side input K?  (a live horizon, rank-aware steps, another side input it does not combine with: a combined mode would be another copy of
@@ -1505,13 +1523,13 @@ int check_handle(srbdqp_handle* h, const char* fn) {
     return SRBDQP_OK;
 }
 
-// a host array of side input K for `length` QPs: every element by the rules of include/srbdqp.h
+// a host array of side input K for `length` QPs: every element by the rules of include/srbdqp.h (then: what the refusal leaves as it was)
 template <class K, class O>
-int validate(O* o, const typename K::T* host, int32_t length, const char* fn) {
+int validate(O* o, const typename K::T* host, int32_t length, const char* fn, const char* then = "the previous setting is kept") {
     const size_t groups = (size_t)length * K::per_qp(o) / K::stride;
     for (size_t i = 0; i < groups; ++i)
         if (const char* why = K::fault(host + K::stride * i)) {
-            o->err = std::string(fn) + ": " + K::where(o, i) + " is invalid (" + why + "); the previous setting is kept";
+            o->err = std::string(fn) + ": " + K::where(o, i) + " is invalid (" + why + "); " + then;
             return SRBDQP_E_INVALID;
         }
     return SRBDQP_OK;
@@ -1708,8 +1726,7 @@ int srbdqp_destroy(srbdqp_handle* h) {
     if (h->fleet.mem) (void)hipFree(h->fleet.mem);
     if (h->terrain.own) (void)hipFree(h->terrain.own);
     if (h->stage_host) (void)hipHostFree(h->stage_host);
-    if (h->stage_ew_host) (void)hipHostFree(h->stage_ew_host);
-    if (h->stage_cn_host) (void)hipHostFree(h->stage_cn_host);
+    for (const auto& ss : {h->staged_ext, h->staged_normals}) if (ss.host) (void)hipHostFree(ss.host);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->ev_mid) (void)hipEventDestroy(h->ev_mid);
@@ -1736,10 +1753,11 @@ int srbdqp_stage_ptrs(srbdqp_handle* h, srbdqp_stage* out) {
     return SRBDQP_OK;
 }
 
+}  // extern "C"
+
 namespace {
-// the staged solve of B QPs over the staging arrays, behind its entry point's checks; with_wrench: QP b under block b of the staged wrench array, in every pass;
-// with_normals: ... on the contact frames of block b of the staged normals array (at most one of the two: no instantiation reads both)
-int solve_staged_impl(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y, bool with_wrench, bool with_normals = false) {
+// the staged solve of B QPs over the staging arrays, behind its entry point's checks; side: QP b under block b of that staged array, in every pass (or none)
+int solve_staged_impl(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y, const CallSide& side) {
     {   // (the kernel of the call before this one published its completion word before it ended)
         const int rq = aql_quiesce(h);
         if (rq != SRBDQP_OK) return rq;
@@ -1750,8 +1768,7 @@ int solve_staged_impl(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use
     Call c;                        // same per-batch kernel choice as the host-buffer API, from the staged contact flags
     const Contacts k = scan_contacts(h->stage_h.contact, (size_t)B, (size_t)h->cfg.horizon, true);
     c.staged = true; c.lazy = &lazy;   // (lazy: the rho restart costs two more launches: only when needed)
-    if (with_wrench) { c.ext_call = h->stage_ew_dev; c.ext_host = h->stage_ew_host; }   // (the restart passes below launch with this Call: they carry the wrench)
-    if (with_normals) { c.cn_call = h->stage_cn_dev; c.cn_host = h->stage_cn_host; }    // (... and the normals)
+    c.side = side;                 // (the restart passes below launch with this Call: they carry the side input)
     // completion: the kernel publishes a sequence number in host memory after its outputs (signal_done()); spinning on it skips the stream's completion
     // interrupt (~15 us)
     c.signal = !(h->cfg.flags & SRBDQP_FLAG_NO_SPIN);
@@ -1776,124 +1793,108 @@ int solve_staged_impl(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use
     return rc;
 }
 
-// the staging array of the staged wrench calls, made when a call first needs it (zero-filled: a block nobody wrote is no wrench)
-int ensure_stage_ext_wrench(srbdqp_handle* h) {
-    if (h->stage_ew_host) return SRBDQP_OK;
+// ---- the side input of a staged call: an external wrench (K = ExtWrenchIn), contact normals (NormalsIn) or none (NoSideIn, the plain calls).  What differs
+// between the kinds is in their descriptors; which of them a call carries is a template argument, so the plain calls compile to what they were ----
+
+// the staging array of side input K, made when a call first needs it (filled with K's neutral value: a block nobody wrote is no wrench / flat ground)
+template <class K>
+int ensure_stage_side(srbdqp_handle* h) {
+    srbdqp_handle::StagedSide& s = K::staged(h);
+    if (s.host) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t bytes = (size_t)h->stage_h.capacity * (size_t)h->cfg.horizon * 6 * sizeof(double);
-    void* host = nullptr; void* dev = nullptr;
-    HIP_TRY(h, hipHostMalloc(&host, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-    if (hipHostGetDevicePointer(&dev, host, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipHostFree(host); h->err = "hipHostGetDevicePointer(staged wrench) failed"; return SRBDQP_E_HIP; }
-    std::memset(host, 0, bytes);
-    h->stage_ew_host = static_cast<double*>(host); h->stage_ew_dev = static_cast<double*>(dev);
-    return SRBDQP_OK;
-}
-
-// May this handle run staged wrench call `fn`?  The refusal table answers for the handle's state -- no form but Plain is admitted: a side input or a
-// handle-level wrench in the setters' texts, a live horizon, rank-aware steps --, and the wrench's own rules for what no state bit says: N = 24 has no MODE 7
-// instantiation, and only the general kernel reads a wrench (the words of srbdqp_set_external_wrench and of variant_check_batch).
-constexpr unsigned kFormsStagedWrench = 0;
-int check_staged_wrench(srbdqp_handle* h, const char* fn) {
-    if (const int rc = require_form(h, fn, kFormsStagedWrench)) return rc;
-    if (h->cfg.horizon > row(Form::ExtWrench).max_horizon) { h->err = std::string(fn) + ": " + ExtWrenchIn::n24(fn); return SRBDQP_E_INVALID; }
-    if (!general_allowed(h->cfg)) {
-        h->err = std::string(fn) + ": " + row(Form::ExtWrench).noun + " is read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH";
-        return SRBDQP_E_INVALID;
-    }
-    return SRBDQP_OK;
-}
-
-// B blocks at w (the staged wrench array, or the caller's own before it is copied there) by the rule of srbdqp_set_external_wrench, before anything is launched
-int validate_staged_wrench(srbdqp_handle* h, const double* w, int32_t B, const char* fn) {
-    const size_t count = (size_t)B * ExtWrenchIn::per_qp(h);
-    for (size_t i = 0; i < count; ++i)
-        if (const char* why = ext_wrench_fault(w + i)) {
-            h->err = std::string(fn) + ": " + ExtWrenchIn::where(h, i) + " is invalid (" + why + "); nothing was launched";
-            return SRBDQP_E_INVALID;
-        }
-    return SRBDQP_OK;
-}
-
-// the staging array of the staged normals calls, made when a call first needs it (every normal (0, 0, 1): a block nobody wrote is flat ground -- zeros would
-// break the rule 0.5 <= |n|)
-int ensure_stage_contact_normals(srbdqp_handle* h) {
-    if (h->stage_cn_host) return SRBDQP_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t count = (size_t)h->stage_h.capacity * NormalsIn::per_qp(h);
+    const size_t count = (size_t)h->stage_h.capacity * K::per_qp(h);
     void* host = nullptr; void* dev = nullptr;
     HIP_TRY(h, hipHostMalloc(&host, count * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-    if (hipHostGetDevicePointer(&dev, host, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipHostFree(host); h->err = "hipHostGetDevicePointer(staged normals) failed"; return SRBDQP_E_HIP; }
-    double* n = static_cast<double*>(host);
-    for (size_t i = 0; i < count; ++i) n[i] = (i % 3 == 2) ? 1.0 : 0.0;
-    h->stage_cn_host = n; h->stage_cn_dev = static_cast<double*>(dev);
-    return SRBDQP_OK;
-}
-
-// May this handle run staged normals call `fn`?  As check_staged_wrench: no form but Plain, and the normals' own rules for what no state bit says -- N = 24 has
-// no MODE 4 instantiation, and only the general kernel reads normals (the words of srbdqp_set_contact_normals and of variant_check_batch).
-constexpr unsigned kFormsStagedNormals = 0;
-int check_staged_normals(srbdqp_handle* h, const char* fn) {
-    if (const int rc = require_form(h, fn, kFormsStagedNormals)) return rc;
-    if (h->cfg.horizon > row(Form::Normals).max_horizon) { h->err = NormalsIn::n24(fn); return SRBDQP_E_INVALID; }
-    if (!general_allowed(h->cfg)) {
-        h->err = std::string(fn) + ": " + row(Form::Normals).noun + " are read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH";
-        return SRBDQP_E_INVALID;
+    if (hipHostGetDevicePointer(&dev, host, 0) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipHostFree(host);
+        h->err = std::string("hipHostGetDevicePointer(") + K::staged_label + ") failed";
+        return SRBDQP_E_HIP;
     }
+    double* v = static_cast<double*>(host);
+    for (size_t i = 0; i < count; ++i) v[i] = K::neutral(i);
+    s.host = v; s.dev = static_cast<double*>(dev);
     return SRBDQP_OK;
 }
 
-// B blocks at n (the staged normals array, or the caller's own before it is copied there) by the rules of srbdqp_set_contact_normals, before anything is launched
-int validate_staged_normals(srbdqp_handle* h, const double* n, int32_t B, const char* fn) {
-    const size_t groups = (size_t)B * NormalsIn::per_qp(h) / NormalsIn::stride;
-    for (size_t i = 0; i < groups; ++i)
-        if (const char* why = normal_fault(n + NormalsIn::stride * i)) {
-            h->err = std::string(fn) + ": " + NormalsIn::where(h, i) + " is invalid (" + why + "); nothing was launched";
+// May this handle run staged call `fn` with side input K?  The refusal table answers for the handle's state -- a call that carries a side input admits no form
+// but Plain: a side input of the handle in the setters' texts, a live horizon, rank-aware steps --, and K's own rules for what no state bit says: N = 24 has no
+// instantiation of K's mode, and only the general kernel reads K (the words of K's setter and of variant_check_batch).
+constexpr unsigned kFormsStagedSide = 0;
+template <class K>
+int check_staged_side(srbdqp_handle* h, const char* fn) {
+    if constexpr (K::side == Side::None) return require_form(h, fn, kFormsStaged);
+    else {
+        if (const int rc = require_form(h, fn, kFormsStagedSide)) return rc;
+        if (h->cfg.horizon > row(K::form).max_horizon) { h->err = K::staged_n24(fn); return SRBDQP_E_INVALID; }
+        if (!general_allowed(h->cfg)) {
+            h->err = std::string(fn) + ": " + row(K::form).noun + " " + K::verb + " read by the general kernel only: srbdqp_config.kernel must be SRBDQP_KERNEL_AUTO or SRBDQP_KERNEL_WRENCH";
             return SRBDQP_E_INVALID;
         }
-    return SRBDQP_OK;
-}
-}  // namespace
-
-int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = require_form(h, "srbdqp_solve_staged_f64", kFormsStaged)) return rc;
-    if (B < 0 || B > h->stage_h.capacity) { h->err = "staged batch exceeds the staging capacity"; return SRBDQP_E_INVALID; }
-    if (B == 0) return SRBDQP_OK;
-    return solve_staged_impl(h, B, use_pcom, use_warm, want_x, want_y, false);
+        return SRBDQP_OK;
+    }
 }
 
-int srbdqp_stage_ext_wrench(srbdqp_handle* h, double** out) {
+// B blocks at v (K's staged array, or the caller's own before it is copied there) by the rules of K's setter, before anything is launched
+template <class K>
+int validate_staged_side(srbdqp_handle* h, const double* v, int32_t B, const char* fn) { return validate<K>(h, v, B, fn, "nothing was launched"); }
+
+// K's staged array as the side input of a call (none: the default)
+template <class K>
+CallSide call_side(srbdqp_handle* h) {
+    if constexpr (K::side == Side::None) return {};
+    else return {K::side, K::staged(h).dev, K::staged(h).host};
+}
+
+// srbdqp_stage_ext_wrench, srbdqp_stage_contact_normals
+template <class K>
+int stage_side(srbdqp_handle* h, double** out) {
     if (!h || !out) return SRBDQP_E_INVALID;
     *out = nullptr;
-    if (const int rc = ensure_stage_ext_wrench(h)) return rc;
-    *out = h->stage_ew_host;
+    if (const int rc = ensure_stage_side<K>(h)) return rc;
+    *out = K::staged(h).host;
     return SRBDQP_OK;
 }
 
-int srbdqp_solve_staged_wrench_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y) {
+// srbdqp_solve_staged_f64, srbdqp_solve_staged_wrench_f64, srbdqp_solve_staged_normals_f64
+template <class K>
+int solve_staged(srbdqp_handle* h, const char* fn, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y) {
     if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = check_staged_wrench(h, "srbdqp_solve_staged_wrench_f64")) return rc;
+    if (const int rc = check_staged_side<K>(h, fn)) return rc;
     if (B < 0 || B > h->stage_h.capacity) { h->err = "staged batch exceeds the staging capacity"; return SRBDQP_E_INVALID; }
     if (B == 0) return SRBDQP_OK;
-    if (const int rc = ensure_stage_ext_wrench(h)) return rc;
-    if (const int rc = validate_staged_wrench(h, h->stage_ew_host, B, "srbdqp_solve_staged_wrench_f64")) return rc;
-    return solve_staged_impl(h, B, use_pcom, use_warm, want_x, want_y, true);
+    if constexpr (K::side != Side::None) {
+        if (const int rc = ensure_stage_side<K>(h)) return rc;
+        if (const int rc = validate_staged_side<K>(h, K::staged(h).host, B, fn)) return rc;
+    }
+    return solve_staged_impl(h, B, use_pcom, use_warm, want_x, want_y, call_side<K>(h));
 }
 
-int srbdqp_update_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact,
-                      const double* pcom, double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters) {
+// srbdqp_update_f64, srbdqp_update_wrench_f64, srbdqp_update_normals_f64 (side: K's array for the one QP; the plain call has none)
+template <class K>
+int update_staged(srbdqp_handle* h, const char* fn, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact, const double* pcom,
+                  const double* side, double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters) {
+    constexpr bool with = K::side != Side::None;
     if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = require_form(h, "srbdqp_update_f64", kFormsStaged)) return rc;
-    if (!x0 || !x_ref || !foot || !contact || !u0_out) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if (const int rc = check_staged_side<K>(h, fn)) return rc;
+    if (!x0 || !x_ref || !foot || !contact || (with && !side) || !u0_out) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
+    if constexpr (with) if (const int rc = ensure_stage_side<K>(h)) return rc;
     const size_t N = (size_t)h->cfg.horizon;
     const srbdqp_stage& s = h->stage_h;
+    if constexpr (with) {
+        // the side input first, where the caller has it: a value that is none returns before any staging array -- K's own included -- is written
+        if (const int rc = validate_staged_side<K>(h, side, 1, fn)) return rc;
+        if (side != K::staged(h).host) std::memcpy(K::staged(h).host, side, K::per_qp(h) * sizeof(double));
+    }
     // into the pinned, GPU-mapped staging arrays (2.4 KB at N = 10; an argument that IS the staging array is left where it is)
     if (x0 != s.x0) std::memcpy(s.x0, x0, 13 * sizeof(double));
     if (x_ref != s.x_ref) std::memcpy(s.x_ref, x_ref, N * 13 * sizeof(double));
     if (foot != s.foot) std::memcpy(s.foot, foot, N * 12 * sizeof(double));
     if (contact != s.contact) std::memcpy(s.contact, contact, N * 4);
     if (pcom && pcom != s.pcom) std::memcpy(s.pcom, pcom, N * 3 * sizeof(double));
-    const int rc = srbdqp_solve_staged_f64(h, 1, pcom != nullptr, 0, x_out != nullptr, 0);
+    // (the plain call through its staged solve's own door, checks included, as it always went; a call with a side input has made its checks above)
+    int rc;
+    if constexpr (with) rc = solve_staged_impl(h, 1, pcom != nullptr, 0, x_out != nullptr, 0, call_side<K>(h));
+    else rc = srbdqp_solve_staged_f64(h, 1, pcom != nullptr, 0, x_out != nullptr, 0);
     if (rc != SRBDQP_OK) return rc;
     if (u0_out != s.u) std::memcpy(u0_out, s.u, 12 * sizeof(double));
     if (u_out && u_out != s.u) std::memcpy(u_out, s.u, N * 12 * sizeof(double));
@@ -1902,75 +1903,27 @@ int srbdqp_update_f64(srbdqp_handle* h, const double* x0, const double* x_ref, c
     if (iters) *iters = s.iters[0];
     return SRBDQP_OK;
 }
+}  // namespace
 
-int srbdqp_update_wrench_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact,
-                             const double* pcom, const double* ext_wrench, double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = check_staged_wrench(h, "srbdqp_update_wrench_f64")) return rc;
-    if (!x0 || !x_ref || !foot || !contact || !ext_wrench || !u0_out) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
-    if (const int rc = ensure_stage_ext_wrench(h)) return rc;
-    const size_t N = (size_t)h->cfg.horizon;
-    const srbdqp_stage& s = h->stage_h;
-    // the wrench first, where the caller has it: a value that is none returns before any staging array -- the staged wrench array included -- is written
-    if (const int rc = validate_staged_wrench(h, ext_wrench, 1, "srbdqp_update_wrench_f64")) return rc;
-    if (ext_wrench != h->stage_ew_host) std::memcpy(h->stage_ew_host, ext_wrench, N * 6 * sizeof(double));
-    if (x0 != s.x0) std::memcpy(s.x0, x0, 13 * sizeof(double));
-    if (x_ref != s.x_ref) std::memcpy(s.x_ref, x_ref, N * 13 * sizeof(double));
-    if (foot != s.foot) std::memcpy(s.foot, foot, N * 12 * sizeof(double));
-    if (contact != s.contact) std::memcpy(s.contact, contact, N * 4);
-    if (pcom && pcom != s.pcom) std::memcpy(s.pcom, pcom, N * 3 * sizeof(double));
-    const int rc = solve_staged_impl(h, 1, pcom != nullptr, 0, x_out != nullptr, 0, true);
-    if (rc != SRBDQP_OK) return rc;
-    if (u0_out != s.u) std::memcpy(u0_out, s.u, 12 * sizeof(double));
-    if (u_out && u_out != s.u) std::memcpy(u_out, s.u, N * 12 * sizeof(double));
-    if (x_out && x_out != s.x) std::memcpy(x_out, s.x, (N + 1) * 13 * sizeof(double));
-    if (status) *status = s.status[0];
-    if (iters) *iters = s.iters[0];
-    return SRBDQP_OK;
+extern "C" {
+
+// the staged calls with their side input: one line each
+int srbdqp_solve_staged_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y) { return solve_staged<NoSideIn>(h, "srbdqp_solve_staged_f64", B, use_pcom, use_warm, want_x, want_y); }
+int srbdqp_solve_staged_wrench_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y) { return solve_staged<ExtWrenchIn>(h, "srbdqp_solve_staged_wrench_f64", B, use_pcom, use_warm, want_x, want_y); }
+int srbdqp_solve_staged_normals_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y) { return solve_staged<NormalsIn>(h, "srbdqp_solve_staged_normals_f64", B, use_pcom, use_warm, want_x, want_y); }
+int srbdqp_stage_ext_wrench(srbdqp_handle* h, double** out) { return stage_side<ExtWrenchIn>(h, out); }
+int srbdqp_stage_contact_normals(srbdqp_handle* h, double** out) { return stage_side<NormalsIn>(h, out); }
+int srbdqp_update_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact, const double* pcom, double* u0_out, double* u_out,
+                      double* x_out, int32_t* status, int32_t* iters) {
+    return update_staged<NoSideIn>(h, "srbdqp_update_f64", x0, x_ref, foot, contact, pcom, nullptr, u0_out, u_out, x_out, status, iters);
 }
-
-int srbdqp_stage_contact_normals(srbdqp_handle* h, double** out) {
-    if (!h || !out) return SRBDQP_E_INVALID;
-    *out = nullptr;
-    if (const int rc = ensure_stage_contact_normals(h)) return rc;
-    *out = h->stage_cn_host;
-    return SRBDQP_OK;
+int srbdqp_update_wrench_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact, const double* pcom, const double* ext_wrench,
+                             double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters) {
+    return update_staged<ExtWrenchIn>(h, "srbdqp_update_wrench_f64", x0, x_ref, foot, contact, pcom, ext_wrench, u0_out, u_out, x_out, status, iters);
 }
-
-int srbdqp_solve_staged_normals_f64(srbdqp_handle* h, int32_t B, int32_t use_pcom, int32_t use_warm, int32_t want_x, int32_t want_y) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = check_staged_normals(h, "srbdqp_solve_staged_normals_f64")) return rc;
-    if (B < 0 || B > h->stage_h.capacity) { h->err = "staged batch exceeds the staging capacity"; return SRBDQP_E_INVALID; }
-    if (B == 0) return SRBDQP_OK;
-    if (const int rc = ensure_stage_contact_normals(h)) return rc;
-    if (const int rc = validate_staged_normals(h, h->stage_cn_host, B, "srbdqp_solve_staged_normals_f64")) return rc;
-    return solve_staged_impl(h, B, use_pcom, use_warm, want_x, want_y, false, true);
-}
-
-int srbdqp_update_normals_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact,
-                              const double* pcom, const double* normals, double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters) {
-    if (!h) return SRBDQP_E_INVALID;
-    if (const int rc = check_staged_normals(h, "srbdqp_update_normals_f64")) return rc;
-    if (!x0 || !x_ref || !foot || !contact || !normals || !u0_out) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
-    if (const int rc = ensure_stage_contact_normals(h)) return rc;
-    const size_t N = (size_t)h->cfg.horizon;
-    const srbdqp_stage& s = h->stage_h;
-    // the normals first, where the caller has them: a normal that is none returns before any staging array -- the staged normals array included -- is written
-    if (const int rc = validate_staged_normals(h, normals, 1, "srbdqp_update_normals_f64")) return rc;
-    if (normals != h->stage_cn_host) std::memcpy(h->stage_cn_host, normals, N * 12 * sizeof(double));
-    if (x0 != s.x0) std::memcpy(s.x0, x0, 13 * sizeof(double));
-    if (x_ref != s.x_ref) std::memcpy(s.x_ref, x_ref, N * 13 * sizeof(double));
-    if (foot != s.foot) std::memcpy(s.foot, foot, N * 12 * sizeof(double));
-    if (contact != s.contact) std::memcpy(s.contact, contact, N * 4);
-    if (pcom && pcom != s.pcom) std::memcpy(s.pcom, pcom, N * 3 * sizeof(double));
-    const int rc = solve_staged_impl(h, 1, pcom != nullptr, 0, x_out != nullptr, 0, false, true);
-    if (rc != SRBDQP_OK) return rc;
-    if (u0_out != s.u) std::memcpy(u0_out, s.u, 12 * sizeof(double));
-    if (u_out && u_out != s.u) std::memcpy(u_out, s.u, N * 12 * sizeof(double));
-    if (x_out && x_out != s.x) std::memcpy(x_out, s.x, (N + 1) * 13 * sizeof(double));
-    if (status) *status = s.status[0];
-    if (iters) *iters = s.iters[0];
-    return SRBDQP_OK;
+int srbdqp_update_normals_f64(srbdqp_handle* h, const double* x0, const double* x_ref, const double* foot, const uint8_t* contact, const double* pcom, const double* normals,
+                              double* u0_out, double* u_out, double* x_out, int32_t* status, int32_t* iters) {
+    return update_staged<NormalsIn>(h, "srbdqp_update_normals_f64", x0, x_ref, foot, contact, pcom, normals, u0_out, u_out, x_out, status, iters);
 }
 
 namespace {
@@ -3062,7 +3015,7 @@ int wrench_observer_check(srbdqp_handle* h, int64_t B, const void* x_prev, const
 // May this handle run this roll-out?  host: the arrays are the caller's host arrays.  In order:
 //  * steered: the command's own rules, which need no handle and come first (host: every entry of the command must be finite);
 //  * the arguments: sizes, arrays, w_est in an observed roll-out, the two settings;
-//  * the handle's state, for the roll-out the call becomes.  Observed: what check_staged_wrench refuses -- in the refusal table's words -- except robot records and
+//  * the handle's state, for the roll-out the call becomes.  Observed: what check_staged_side<ExtWrenchIn> refuses -- in the refusal table's words -- except robot records and
 //    weights, which the wrench's batch kernel reads beside the wrench; then a terrain.  On a terrain: the solves read the normals of the call, and no instantiation
 //    reads those beside another side input, on a live horizon, with rank-aware steps or at N = 24 -- what the staged normals calls refuse, in the refusal table's
 //    words.  Plain: the plant is flat ground and knows no wrench but the push -- a handle whose QPs are told otherwise would roll out against another robot
@@ -3097,7 +3050,7 @@ int fleet_rollout_check(srbdqp_handle* h, const RolloutArgs& a, bool host) {
             return SRBDQP_E_INVALID;
         }
     } else if (h->terrain.map.h) {
-        if (const int rc = check_staged_normals(h, a.fn)) { h->err += " -- while a terrain is set (srbdqp_set_terrain)"; return rc; }
+        if (const int rc = check_staged_side<NormalsIn>(h, a.fn)) { h->err += " -- while a terrain is set (srbdqp_set_terrain)"; return rc; }
         return SRBDQP_OK;
     } else {
         if (h->ext.dev) { h->err = fn + ": the handle has an external wrench set (srbdqp_set_external_wrench): the plant does not know it -- clear it, and pass the roll-out its push"; return SRBDQP_E_INVALID; }
@@ -3253,7 +3206,10 @@ int fleet_rollout_run(srbdqp_handle* h, const RolloutArgs& a, void* stream) {
         // of THIS call (the general kernel's _ew instantiation, which reads the handle's weights and robot records too) -- every pass of it, deferred ones on the
         // tail stream included, launches with this Call (solve_device_impl)
         Call c;
-        c.use_hint = true; c.cn_call = terrain ? f.normals : nullptr; c.ext_call = a.obs ? f.ew : nullptr;
+        c.use_hint = true;
+        // (device memory, no host address: never inline.  fleet_rollout_check has refused an observed roll-out on a terrain)
+        if (terrain) c.side = {Side::Normals, f.normals, nullptr};
+        else if (a.obs) c.side = {Side::ExtWrench, f.ew, nullptr};
         c.plan = plan_solve(h, c, (int)B, maxs_or(h->cfg, 4));
         if (const int rc = solve_device_impl(h, c, (int32_t)B, a.x, f.x_ref, f.foot, f.contact, f.pcom, nullptr, nullptr, f.u, f.x_out, nullptr, f.status, f.iters, st))
             return rc;

@@ -1,6 +1,6 @@
 // srbdqp_wrench_lat_ew.hip -- the low-latency side-input instantiations of the general kernel in a code object of their own: MODE 7 (the staged wrench calls:
 // srbdqp_solve_staged_wrench_f64, srbdqp_update_wrench_f64) and MODE 4 (the staged normals calls: srbdqp_solve_staged_normals_f64, srbdqp_update_normals_f64);
-// srbdqp_wrench_lat_ew.hpp says why.  Host side: one launcher per mode.
+// srbdqp_wrench_lat_ew.hpp says why.  Host side: one launcher over the mode.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -15,67 +15,62 @@
 namespace srbdqp {
 namespace {
 
-// the waves and the pipeline of the plain call's low-latency instantiation (srbdqp.hip launch_wrench_t) on the MODE 7 layout, the wrench's rows for the
-// roll-out behind the mode's slots
-template <int N>
-hipError_t launch_t(bool set_attr, const KArgs& a, const void* in, const double* ew_host, const double* ext_dev, hipStream_t st) {
+// what differs between the two modes: the grid kernel, its *_in twin, the struct that carries the side input of one QP in the argument segment, the doubles
+// kept behind the layout
+template <int MODE> struct LatSide;
+template <> struct LatSide<kModeExtWrench> {           // the wrench's rows for the roll-out behind the mode's slots
+    template <int N> using Arg = StagedWrench<N>;
+    template <int N, int XW> static constexpr auto grid() { return &srbdqp_wrench_ew_lat_kernel<N, XW>; }
+    template <int N, int XW> static constexpr auto in() { return &srbdqp_wrench_ew_lat_kernel_in<N, XW>; }
+    static constexpr int xd(int N) { return wrench_lat_ew_xd(N); }
+};
+template <> struct LatSide<kModeNormals> {             // the table L in the persistent strip; no doubles behind the layout
+    template <int N> using Arg = StagedNormals<N>;
+    template <int N, int XW> static constexpr auto grid() { return &srbdqp_wrench_cn_lat_kernel<N, XW>; }
+    template <int N, int XW> static constexpr auto in() { return &srbdqp_wrench_cn_lat_kernel_in<N, XW>; }
+    static constexpr int xd(int) { static_assert(WrenchMode<kModeNormals>::xd == 0); return 0; }
+};
+
+// the waves and the pipeline of the plain call's low-latency instantiation (srbdqp.hip launch_wrench_t) on the layout of MODE
+template <int N, int MODE>
+hipError_t launch_t(bool set_attr, const KArgs& a, const void* in, const double* side_host, const double* side_dev, hipStream_t st) {
+    using M = LatSide<MODE>;
     constexpr int XW = (N >= 8) ? 2 : 1;
-    using SL = WrenchLayout<N, kModeExtWrench, 8, 5, XW>;
-    constexpr size_t lds = SL::bytes + wrench_lat_ew_xd(N) * sizeof(double);
+    using SL = WrenchLayout<N, MODE, 8, 5, XW>;
+    constexpr size_t lds = SL::bytes + M::xd(N) * sizeof(double);
     static_assert(lds <= 163840 && SL::BT == WrenchSmem<N, 8, 5, XW>::BT, "one QP must fit the LDS of a CU");
     if (!in) {
-        auto k = &srbdqp_wrench_ew_lat_kernel<N, XW>;
+        auto k = M::template grid<N, XW>();
         if (set_attr) if (const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
-        hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(SL::BT), lds, st, a, ext_dev);
+        hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(SL::BT), lds, st, a, side_dev);
         return hipGetLastError();
     }
-    auto k = &srbdqp_wrench_ew_lat_kernel_in<N, XW>;
+    auto k = M::template in<N, XW>();
     if (set_attr) if (const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
-    StagedWrench<N> ew;
-    std::memcpy(ew.w, ew_host, sizeof(ew.w));
-    hipLaunchKernelGGL(k, dim3(1), dim3(SL::BT), lds, st, a, *static_cast<const StagedIn<N>*>(in), ew);
+    typename M::template Arg<N> side;
+    std::memcpy(&side, side_host, sizeof(side));
+    hipLaunchKernelGGL(k, dim3(1), dim3(SL::BT), lds, st, a, *static_cast<const StagedIn<N>*>(in), side);
     return hipGetLastError();
 }
 
-// ... and on the MODE 4 layout (the table L in the persistent strip; no doubles behind the layout)
-template <int N>
-hipError_t launch_cn_t(bool set_attr, const KArgs& a, const void* in, const double* cn_host, const double* cn_dev, hipStream_t st) {
-    constexpr int XW = (N >= 8) ? 2 : 1;
-    using SL = WrenchLayout<N, kModeNormals, 8, 5, XW>;
-    constexpr size_t lds = SL::bytes;
-    static_assert(lds <= 163840 && SL::BT == WrenchSmem<N, 8, 5, XW>::BT && WrenchMode<kModeNormals>::xd == 0, "one QP must fit the LDS of a CU");
-    if (!in) {
-        auto k = &srbdqp_wrench_cn_lat_kernel<N, XW>;
-        if (set_attr) if (const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
-        hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(SL::BT), lds, st, a, cn_dev);
-        return hipGetLastError();
-    }
-    auto k = &srbdqp_wrench_cn_lat_kernel_in<N, XW>;
-    if (set_attr) if (const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
-    StagedNormals<N> cn;
-    std::memcpy(cn.n, cn_host, sizeof(cn.n));
-    hipLaunchKernelGGL(k, dim3(1), dim3(SL::BT), lds, st, a, *static_cast<const StagedIn<N>*>(in), cn);
-    return hipGetLastError();
+template <int MODE>
+hipError_t launch_n(int N, bool set_attr, const KArgs& a, const void* in, const double* side_host, const double* side_dev, hipStream_t st) {
+    if (N == 4) return launch_t<4, MODE>(set_attr, a, in, side_host, side_dev, st);
+    if (N == 8) return launch_t<8, MODE>(set_attr, a, in, side_host, side_dev, st);
+    if (N == 10) return launch_t<10, MODE>(set_attr, a, in, side_host, side_dev, st);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace
 
-hipError_t launch_wrench_ew_lat(int N, bool set_attr, const KArgs& a, const void* in, const double* ew_host, const double* ext_dev, hipStream_t st) {
-    if (N == 4) return launch_t<4>(set_attr, a, in, ew_host, ext_dev, st);
-    if (N == 8) return launch_t<8>(set_attr, a, in, ew_host, ext_dev, st);
-    if (N == 10) return launch_t<10>(set_attr, a, in, ew_host, ext_dev, st);
-    return hipErrorInvalidValue;
-}
-
-hipError_t launch_wrench_cn_lat(int N, bool set_attr, const KArgs& a, const void* in, const double* cn_host, const double* cn_dev, hipStream_t st) {
-    if (N == 4) return launch_cn_t<4>(set_attr, a, in, cn_host, cn_dev, st);
-    if (N == 8) return launch_cn_t<8>(set_attr, a, in, cn_host, cn_dev, st);
-    if (N == 10) return launch_cn_t<10>(set_attr, a, in, cn_host, cn_dev, st);
+hipError_t launch_wrench_side_lat(int mode, int N, bool set_attr, const KArgs& a, const void* in, const double* side_host, const double* side_dev, hipStream_t st) {
+    if (mode == kModeExtWrench) return launch_n<kModeExtWrench>(N, set_attr, a, in, side_host, side_dev, st);   // (the wrench's kernels first: the order of the code object)
+    if (mode == kModeNormals) return launch_n<kModeNormals>(N, set_attr, a, in, side_host, side_dev, st);
     return hipErrorInvalidValue;
 }
 
 // The fleet's plant step (srbdqp_fleet.hpp) is instantiated here too, behind the low-latency kernels, for their reason: srbdqp.hip's code object stays what it
-// was, and the library keeps its two code objects (tests/test_staged_wrench_cpu.py, tests/test_staged_normals_cpu.py count them).
+// was, and the library keeps its two code objects (tests/test_staged_side_cpu.py counts them).
 hipError_t launch_fleet_advance(const FleetArgs& a, hipStream_t st, const TerrainMap* map, const double* landing_yaw) {
     const long long tiles = (a.B + kFleetTile - 1) / kFleetTile;   // one tile of 64 robots per workgroup pass
     const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));

@@ -11,13 +11,12 @@
 
 namespace srbdqp {
 
-// One launch through HIP on st, N in {4, 8, 10} (anything else: hipErrorInvalidValue).
-//   in == nullptr: the grid of a.B workgroups, QP b under ext_dev[6 N b .. 6 N (b + 1)) (a device address);
-//   in != nullptr: ONE workgroup with *in = the StagedIn<N> of the QP and the 6 N doubles at ew_host behind it in the kernel-argument segment (a.inline_in set).
+// One launch through HIP on st of the low-latency kernel of mode (kModeExtWrench: 6 N doubles a QP; kModeNormals: 12 N), N in {4, 8, 10} (anything else:
+// hipErrorInvalidValue).
+//   in == nullptr: the grid of a.B workgroups, QP b under block b of side_dev (a device address);
+//   in != nullptr: ONE workgroup with *in = the StagedIn<N> of the QP and the doubles of its block at side_host behind it in the kernel-argument segment
+//                  (a.inline_in set).
 // set_attr: raise the kernel's dynamic-LDS limit first (once per kernel and device: the caller keeps the book, as it does for its own kernels).
-hipError_t launch_wrench_ew_lat(int N, bool set_attr, const KArgs& a, const void* in, const double* ew_host, const double* ext_dev, hipStream_t st);
-
-// The same for the staged normals calls: QP b under cn_dev[12 N b .. 12 N (b + 1)), or the 12 N doubles at cn_host behind *in in the kernel-argument segment.
-hipError_t launch_wrench_cn_lat(int N, bool set_attr, const KArgs& a, const void* in, const double* cn_host, const double* cn_dev, hipStream_t st);
+hipError_t launch_wrench_side_lat(int mode, int N, bool set_attr, const KArgs& a, const void* in, const double* side_host, const double* side_dev, hipStream_t st);
 
 }  // namespace srbdqp

@@ -153,8 +153,10 @@ class BatchMPC(_Engine):
     """B independent SRBD convex-MPC QPs per call.  One instance <-> one HIP stream <-> one thread."""
     _CREATE, _DESTROY, _LAST_ERROR = "srbdqp_create", "srbdqp_destroy", "srbdqp_last_error"
     _stage = _fcb = None                    # stage(): NumPy views of the staging arrays, and the CPython binding's capsule on them
-    _stage_ew = None                        # stage_ext_wrench(): the view of the staged wrench array
-    _stage_cn = None                        # stage_contact_normals(): the view of the staged normals array
+    _stage_side = None                      # stage_ext_wrench(), stage_contact_normals(): kind -> the view of that staged array, once made
+    # the side input a staged call can carry, by kind: its three C calls and its doubles per horizon step
+    _STAGED_SIDE = {"wrench": ("srbdqp_stage_ext_wrench", "srbdqp_solve_staged_wrench_f64", "srbdqp_update_wrench_f64", 6),
+                    "normals": ("srbdqp_stage_contact_normals", "srbdqp_solve_staged_normals_f64", "srbdqp_update_normals_f64", NU)}
 
     def __init__(self, horizon: int = 10, dt: float = 0.04, device: int = 0, kernel: int = _lib.KERNEL_AUTO,
                  timing: bool = False, rank_aware: bool = False, **overrides):
@@ -179,7 +181,7 @@ class BatchMPC(_Engine):
         self.m = _lib.ROWS_PER_STEP * self.N
 
     def close(self):
-        self._stage = self._fcb = self._stage_ew = self._stage_cn = None   # the views and the capsule point into memory the library is about to free
+        self._stage = self._fcb = self._stage_side = None   # the views and the capsule point into memory the library is about to free
         super().close()
 
     def _open(self):
@@ -343,63 +345,66 @@ class BatchMPC(_Engine):
             return
         self._check(self._lib.srbdqp_solve_staged_f64(self._h, int(B), int(use_pcom), int(use_warm), int(want_x), int(want_y)))
 
+    def _stage_side_view(self, kind):
+        """NumPy view (capacity, N, width) of the staged array of side input `kind` (a row of _STAGED_SIDE), made at the first call and kept until close()."""
+        self._open()
+        views = self._stage_side = self._stage_side or {}
+        if kind not in views:
+            stage, _, _, width = self._STAGED_SIDE[kind]
+            p = C.c_void_p()
+            self._check(getattr(self._lib, stage)(self._h, C.byref(p)))
+            shape = (self.stage()["capacity"], self.N, width)
+            views[kind] = np.ctypeslib.as_array((C.c_double * int(np.prod(shape))).from_address(p.value)).reshape(shape)
+        return views[kind]
+
+    def _solve_staged_side(self, kind, B, use_pcom, use_warm, want_x, want_y):
+        self._open()
+        self._check(getattr(self._lib, self._STAGED_SIDE[kind][1])(self._h, int(B), int(use_pcom), int(use_warm), int(want_x), int(want_y)))
+
+    def _bind_update_side(self, kind):
+        """The update call of side input `kind` for the QP in row 0 of the staging arrays with every argument bound once, as MPC binds the plain call: inputs,
+        side input and outputs ARE the staging arrays, so the C side copies nothing -> (fn, arguments with pcom, arguments without); rc = fn(*arguments)."""
+        st, side = self.stage(), self._stage_side_view(kind)
+        P = lambda a: C.c_void_p(a.ctypes.data)
+        ins = (C.c_void_p(self._h.value), P(st["x0"][0]), P(st["x_ref"][0]), P(st["foot"][0]), P(st["contact"][0]))
+        outs = (P(side[0]), P(st["u"][0]), None, P(st["x"][0]), None, None)
+        return getattr(_lib.load_raw(), self._STAGED_SIDE[kind][2]), ins + (P(st["pcom"][0]),) + outs, ins + (None,) + outs
+
     def stage_ext_wrench(self):
         """NumPy view (capacity, N, 6) of the staged wrench array (srbdqp_stage_ext_wrench): [b, k, 0:3] a world-frame torque about the CoM in N m and
         [b, k, 3:6] a world-frame force in N on QP b during step k, as set_external_wrench() takes them.  Pinned and GPU-mapped like the arrays of stage(),
         zero-filled, allocated by the library at the first call."""
-        self._open()
-        if self._stage_ew is None:
-            p = C.c_void_p()
-            self._check(self._lib.srbdqp_stage_ext_wrench(self._h, C.byref(p)))
-            shape = (self.stage()["capacity"], self.N, 6)
-            self._stage_ew = np.ctypeslib.as_array((C.c_double * int(np.prod(shape))).from_address(p.value)).reshape(shape)
-        return self._stage_ew
+        return self._stage_side_view("wrench")
 
     def solve_staged_wrench(self, B=1, use_pcom=False, use_warm=False, want_x=True, want_y=False):
         """solve_staged() with QP b under block b of stage_ext_wrench(), for this call alone (srbdqp_solve_staged_wrench_f64): nothing is set on the engine,
         and the next solve_staged() is what it would have been.  The general kernel for every contact pattern: its low-latency external-wrench
         instantiation (wrench_f64_n<N>_lat_ew) at N <= 10 and B <= 8, the batch one (wrench_f64_n<N>_ew) otherwise.  A value that is not finite or above
         1e6 raises SrbdqpError before anything is launched."""
-        self._open()
-        self._check(self._lib.srbdqp_solve_staged_wrench_f64(self._h, int(B), int(use_pcom), int(use_warm), int(want_x), int(want_y)))
+        self._solve_staged_side("wrench", B, use_pcom, use_warm, want_x, want_y)
 
     def bind_update_wrench(self):
         """srbdqp_update_wrench_f64 for the QP in row 0 of the staging arrays with every argument bound once, as MPC binds the plain call: inputs, wrench and
         outputs ARE the staging arrays, so the C side copies nothing -> (fn, arguments with pcom, arguments without); rc = fn(*arguments)."""
-        st, ew = self.stage(), self.stage_ext_wrench()
-        P = lambda a: C.c_void_p(a.ctypes.data)
-        ins = (C.c_void_p(self._h.value), P(st["x0"][0]), P(st["x_ref"][0]), P(st["foot"][0]), P(st["contact"][0]))
-        outs = (P(ew[0]), P(st["u"][0]), None, P(st["x"][0]), None, None)
-        return _lib.load_raw().srbdqp_update_wrench_f64, ins + (P(st["pcom"][0]),) + outs, ins + (None,) + outs
+        return self._bind_update_side("wrench")
 
     def stage_contact_normals(self):
         """NumPy view (capacity, N, 12) of the staged normals array (srbdqp_stage_contact_normals): [b, k, 3 i : 3 i + 3] the world-frame surface normal under
         contact i of step k of QP b, as set_contact_normals() takes them (swing contacts included).  Pinned and GPU-mapped like the arrays of stage(), filled
         with (0, 0, 1) -- a block nobody wrote is flat ground --, allocated by the library at the first call."""
-        self._open()
-        if self._stage_cn is None:
-            p = C.c_void_p()
-            self._check(self._lib.srbdqp_stage_contact_normals(self._h, C.byref(p)))
-            shape = (self.stage()["capacity"], self.N, 12)
-            self._stage_cn = np.ctypeslib.as_array((C.c_double * int(np.prod(shape))).from_address(p.value)).reshape(shape)
-        return self._stage_cn
+        return self._stage_side_view("normals")
 
     def solve_staged_normals(self, B=1, use_pcom=False, use_warm=False, want_x=True, want_y=False):
         """solve_staged() with QP b under block b of stage_contact_normals(), for this call alone (srbdqp_solve_staged_normals_f64): nothing is set on the
         engine, and the next solve_staged() is what it would have been.  The general kernel for every contact pattern: its low-latency contact-normals
         instantiation (wrench_f64_n<N>_lat_cn) at N <= 10 and B <= 8, the batch one (wrench_f64_n<N>_cn) otherwise.  A normal that is not finite, has a
         length outside [0.5, 2] or n_z < 0.5 after normalising raises SrbdqpError before anything is launched."""
-        self._open()
-        self._check(self._lib.srbdqp_solve_staged_normals_f64(self._h, int(B), int(use_pcom), int(use_warm), int(want_x), int(want_y)))
+        self._solve_staged_side("normals", B, use_pcom, use_warm, want_x, want_y)
 
     def bind_update_normals(self):
         """srbdqp_update_normals_f64 for the QP in row 0 of the staging arrays with every argument bound once, as bind_update_wrench() binds the wrench call:
         inputs, normals and outputs ARE the staging arrays, so the C side copies nothing -> (fn, arguments with pcom, arguments without); rc = fn(*arguments)."""
-        st, cn = self.stage(), self.stage_contact_normals()
-        P = lambda a: C.c_void_p(a.ctypes.data)
-        ins = (C.c_void_p(self._h.value), P(st["x0"][0]), P(st["x_ref"][0]), P(st["foot"][0]), P(st["contact"][0]))
-        outs = (P(cn[0]), P(st["u"][0]), None, P(st["x"][0]), None, None)
-        return _lib.load_raw().srbdqp_update_normals_f64, ins + (P(st["pcom"][0]),) + outs, ins + (None,) + outs
+        return self._bind_update_side("normals")
 
     def prepare_staged(self, B=1, use_pcom=False):
         """Two-phase call, phase 1 (srbdqp_prepare_staged_f64): set-up of the first B staged QPs from a PREDICTED x0 (whatever the
@@ -875,9 +880,8 @@ class MPC:
         self._last_fast = False                 # the last call went through update()'s bound fast path: results are read from the staging arrays
         self._upd = None                        # srbdqp_update_f64 with every argument bound (see _bind)
         self.staged_wrench = bool(staged_wrench)
-        self._updw = None                       # srbdqp_update_wrench_f64 with every argument bound (see _update_staged_wrench)
         self.staged_normals = bool(staged_normals)
-        self._updn = None                       # srbdqp_update_normals_f64 with every argument bound (see _update_staged_normals)
+        self._side_calls = {}                   # kind -> (srbdqp_update_wrench_f64 / _normals_f64, its arguments with pcom, without, row 0 of the staged array, its width): see _update_staged_side
 
     # outcome of the last call.  The fast path of update() leaves everything in the library's staging arrays and these read it there on demand.
     @property
@@ -1018,10 +1022,10 @@ class MPC:
         one_rollout=True -> x_opt1 has the whole roll-out (N+1, 13); False -> only rows 0..1.
         contact_normals: (N, 12) / (N, 4, 3) array or a per-step list of world-frame surface normals (BatchMPC.set_contact_normals): the friction pyramids
         of sloped ground.  Such a call goes through the host-batch solve with B = 1 -- or, on an object made with staged_normals=True, through the staged call
-        srbdqp_update_normals_f64 (_update_staged_normals).
+        srbdqp_update_normals_f64 (_update_staged_side).
         external_wrench: (N, 6) world-frame [torque, force] on the body per horizon step (BatchMPC.set_external_wrench), for this call alone; it goes the
         same way, through the host setter (set before the solve, cleared after it: two waits for the handle's streams per call) -- or, on an object made with
-        staged_wrench=True, through the staged call srbdqp_update_wrench_f64 (_update_staged_wrench).  Both together raise ValueError: no instantiation reads both.
+        staged_wrench=True, through the staged call srbdqp_update_wrench_f64 (_update_staged_side).  Both together raise ValueError: no instantiation reads both.
 
         One C call (srbdqp_update_f64) with every argument bound once: the inputs go straight into the library's pinned staging arrays,
         the results are copied out of them once.  What Python adds to the C call is what NumPy needs to gather the reference's per-step
@@ -1030,9 +1034,9 @@ class MPC:
         if contact_normals is not None and external_wrench is not None:
             raise ValueError("update: contact_normals and external_wrench together are not supported (no instantiation of the general kernel reads both)")
         if external_wrench is not None and self.staged_wrench:
-            return self._update_staged_wrench(contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, external_wrench)
+            return self._update_staged_side("wrench", contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, external_wrench)
         if contact_normals is not None and self.staged_normals:
-            return self._update_staged_normals(contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals)
+            return self._update_staged_side("normals", contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals)
         if contact_normals is not None or external_wrench is not None:
             return self._update_via_batch(contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals, external_wrench)
         # From here to the end of the method: the measured ~4.5 us of Python around srbdqp_update_f64.  Its two arms keep their own copy of "write one QP" and of
@@ -1110,48 +1114,33 @@ class MPC:
         self._solve_time = time.perf_counter() - t0
         return self._outcome(out["status"][0], out["iters"][0], out["u"][0], out["x"][0], one_rollout, 3)
 
-    def _update_staged_wrench(self, contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, external_wrench):
-        """update() with an external wrench on a staged_wrench=True object: the QP and its wrench into row 0 of the staging arrays, then ONE C call
-        (srbdqp_update_wrench_f64) whose arguments were bound once (BatchMPC.bind_update_wrench).  The wrench is the call's: the next update() without one is
-        the plain staged call, unchanged."""
+    def _update_staged_side(self, kind, contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, side):
+        """update() with an external wrench on a staged_wrench=True object (kind "wrench"), or with contact normals on a staged_normals=True one ("normals"):
+        the QP and its side input into row 0 of the staging arrays, then ONE C call (srbdqp_update_wrench_f64 / srbdqp_update_normals_f64) whose arguments were
+        bound once (BatchMPC.bind_update_wrench / bind_update_normals).  The side input is the call's: the next update() without one is the plain staged call,
+        unchanged."""
         if self._engine is None:
             self.init_matrices()
         eng, N = self._engine, self.HORIZON_LENGTH
-        if self._updw is None:
-            self._updw, self._args_w_pcom, self._args_w_nopcom = eng.bind_update_wrench()
-            self._s_ew = eng.stage_ext_wrench()[0]
+        rec = self._side_calls.get(kind)
+        if rec is None:
+            bind, view = {"wrench": ("bind_update_wrench", "stage_ext_wrench"), "normals": ("bind_update_normals", "stage_contact_normals")}[kind]
+            row = getattr(eng, view)()[0]
+            rec = self._side_calls[kind] = getattr(eng, bind)() + (row, row.shape[1])
+        upd, args_pcom, args_nopcom, row, width = rec
         self._last_fast = self._last_fc = False
         st, use_pcom = self._write_staged(self.x0 if x_current is None else x_current, self.x_ref_hor, c_horizon, contact_horizon, p_com_horizon)
-        self._s_ew[:] = np.asarray(external_wrench, dtype=np.float64).reshape(N, 6)
+        row[:] = np.asarray(side, dtype=np.float64).reshape(N, width)     # (two integers: a shape tuple costs reshape 0.1 us more)
         t0 = time.perf_counter()
-        rc = self._updw(*(self._args_w_pcom if use_pcom else self._args_w_nopcom))
-        self._solve_time = time.perf_counter() - t0
-        if rc:
-            _lib.check(rc, eng._h)
-        return self._outcome(st["status"][0], st["iters"][0], st["u"][0].copy(), st["x"][0].copy(), one_rollout, 3)
-
-    def _update_staged_normals(self, contact_horizon, c_horizon, p_com_horizon, x_current, one_rollout, contact_normals):
-        """update() with contact normals on a staged_normals=True object: the QP and its normals into row 0 of the staging arrays, then ONE C call
-        (srbdqp_update_normals_f64) whose arguments were bound once (BatchMPC.bind_update_normals).  The normals are the call's: the next update() without
-        them is the plain staged call, unchanged."""
-        if self._engine is None:
-            self.init_matrices()
-        eng, N = self._engine, self.HORIZON_LENGTH
-        if self._updn is None:
-            self._updn, self._args_n_pcom, self._args_n_nopcom = eng.bind_update_normals()
-            self._s_cn = eng.stage_contact_normals()[0]
-        self._last_fast = self._last_fc = False
-        st, use_pcom = self._write_staged(self.x0 if x_current is None else x_current, self.x_ref_hor, c_horizon, contact_horizon, p_com_horizon)
-        self._s_cn[:] = np.asarray(contact_normals, dtype=np.float64).reshape(N, NU)
-        t0 = time.perf_counter()
-        rc = self._updn(*(self._args_n_pcom if use_pcom else self._args_n_nopcom))
+        rc = upd(*(args_pcom if use_pcom else args_nopcom))
         self._solve_time = time.perf_counter() - t0
         if rc:
             _lib.check(rc, eng._h)
         return self._outcome(st["status"][0], st["iters"][0], st["u"][0].copy(), st["x"][0].copy(), one_rollout, 3)
 
     def close(self):
-        self._upd = self._fcb = self._updw = self._updn = None
+        self._upd = self._fcb = None
+        self._side_calls = {}                   # (bound calls on, and views of, the staged side arrays)
         self._last_fast = self._last_fc = False
         for k in [k for k in vars(self) if k.startswith(("_s_", "_args_"))]:    # what _bind() made: views of, and addresses in, memory the library is about to free
             delattr(self, k)

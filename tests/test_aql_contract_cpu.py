@@ -8,6 +8,8 @@ import subprocess
 
 import pytest
 
+import offload_bundles
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 
@@ -25,14 +27,9 @@ def _gfx950_code_object(path):
             continue
         b = d[s[4]:s[4] + s[5]]
         assert b[:24] == b"__CLANG_OFFLOAD_BUNDLE__", "the fat binary must stay an uncompressed offload bundle (the launcher does not decompress)"
-        n, = struct.unpack_from("<Q", b, 24)
-        p = 32
-        for _ in range(n):
-            off, sz, tl = struct.unpack_from("<QQQ", b, p)
-            triple = b[p + 24:p + 24 + tl].decode()
-            p += 24 + tl
-            if "gfx950" in triple and sz:
-                return b[off:off + sz]
+        co = offload_bundles.gfx950_entry(b, 0)            # (the FIRST bundle of the section: the one the launcher reads)
+        if co is not None:
+            return co
     raise AssertionError("no gfx950 code object in " + path)
 
 
