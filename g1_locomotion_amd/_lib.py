@@ -53,6 +53,11 @@ class ObserverSettings(C.Structure):
                 ("torque_max", C.c_double), ("force_max", C.c_double)]
 
 
+class TrackSettings(C.Structure):
+    """srbdqp_track_settings (include/srbdqp_cascade.h): how far a tracked robot's reference pose may lead the measured state."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved0", C.c_int32), ("lead_max", C.c_double), ("yaw_lead_max", C.c_double)]
+
+
 class Terrain(C.Structure):
     """srbdqp_terrain (include/srbdqp_cascade.h): the grid of a height map."""
     _fields_ = [("struct_size", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("reserved0", C.c_int32),
@@ -185,6 +190,9 @@ _ROLLOUT_OBS = _ROLLOUT + [_OBS, dp, dp]                                  # ... 
 _INPUTS_STEER = _INPUTS + [dp]                                            # (command in v_ref's place) ..., landing_yaw
 _ADVANCE_STEER = _ADVANCE[:8] + [dp] + _ADVANCE[8:]                       # ..., landing, landing_yaw, standing, push, alive, settings
 _ROLLOUT_STEER = _ROLLOUT_OBS[:7] + [_i32] + _ROLLOUT_OBS[7:]             # ..., command, command_steps, standing, ...
+_TRK = C.POINTER(TrackSettings)
+_INPUTS_TRACK = _INPUTS_STEER + [_TRK, dp]                                # ..., landing_yaw, the track settings, pose
+_ROLLOUT_TRACK = _ROLLOUT_STEER + [_TRK, dp, dp]                          # ..., w_log, the track settings, pose, pose_log
 SIGNATURES = {
     # include/srbdqp.h -- config, handle
     "srbdqp_default_config": (_int, [_CFG]),
@@ -274,6 +282,12 @@ SIGNATURES = {
     "srbdqp_fleet_advance_steered_device_f64": (_int, _ADVANCE_STEER + [_vp]),
     "srbdqp_fleet_rollout_steered_device_f64": (_int, _ROLLOUT_STEER + [_vp]),
     "srbdqp_fleet_rollout_steered_f64": (_int, _ROLLOUT_STEER),
+    # ... that follows its path: the steered inputs and roll-out from a carried reference pose with a bounded lead
+    "srbdqp_track_default_settings": (_int, [_TRK]),
+    "srbdqp_mpc_inputs_tracked_f64": (_int, _INPUTS_TRACK),
+    "srbdqp_mpc_inputs_tracked_device_f64": (_int, _INPUTS_TRACK + [_vp]),
+    "srbdqp_fleet_rollout_tracked_device_f64": (_int, _ROLLOUT_TRACK + [_vp]),
+    "srbdqp_fleet_rollout_tracked_f64": (_int, _ROLLOUT_TRACK),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -1019,7 +1019,7 @@ int launch(srbdqp_handle* h, const Call& c, const KArgs& a, hipStream_t st, int 
 struct HostIo {
     struct Arr { void* dev; const void* in; void* out; size_t bytes; bool zero; };
     Carver c;
-    Arr arr[16];                   // (at most 12: solve_host_impl)
+    Arr arr[20];                   // (at most 12: solve_host_impl; 16: a tracked, observed roll-out with every log)
     int n = 0;
     explicit HostIo(char* base) : c(base) {}
     template <typename T = char> T* in(const void* host, size_t bytes) { return host ? add<T>(host, nullptr, bytes, false) : nullptr; }
@@ -2922,10 +2922,87 @@ int mpc_inputs_host(srbdqp_handle* h, int64_t B, bool steered, const double* x0,
     }, [&](hipStream_t st) { return mpc_inputs_device(h, B, steered, dx0, dfe, dst, dv, dsd, gait, dxr, dft, dct, dpc, dlp, dly, st); });
 }
 
+// ---- a fleet that follows its path (include/srbdqp_cascade.h; the kernel: srbdqp_steer.hpp) ----
+// what is wrong with a tracked call's settings (null: nothing)
+const char* track_settings_fault(const srbdqp_track_settings* s) {
+    if (!s || s->struct_size != (int32_t)sizeof(srbdqp_track_settings)) return "struct_size is not sizeof(srbdqp_track_settings)";
+    for (const double v : {s->lead_max, s->yaw_lead_max})
+        if (!std::isfinite(v) || !(v > 0.0)) return "lead_max and yaw_lead_max must be finite and positive";
+    return nullptr;
+}
+
+// what a tracked call checks before its handle is looked at: the settings, the pose, and in a host form that pose [B][3] and command [rows][B][3] are finite.
+// fn: the call, for the texts
+int track_check(srbdqp_handle* h, const char* fn, int64_t B, const srbdqp_track_settings* trk, const double* pose, const double* command, size_t rows, bool host) {
+    const std::string who = fn;
+    if (const char* why = track_settings_fault(trk)) return steer_refuse(h, who + ": invalid srbdqp_track_settings: " + why);
+    if (!pose && B > 0) return steer_refuse(h, who + ": pose is NULL ([B][3] = (qx, qy, th) goes in and out: (x[3], x[4], x[2]) starts on the robot)");
+    if (host && B >= 1 && B <= 0x7fffffffLL) {
+        long long i = steer_non_finite(pose, (size_t)B * 3);
+        if (i >= 0) return steer_refuse(h, who + ": the pose of robot " + std::to_string(i / 3) + " is not finite (component " + std::to_string(i % 3) + " of qx, qy, th)");
+        i = command ? steer_non_finite(command, rows * (size_t)B * 3) : -1;
+        if (i >= 0) return steer_refuse(h, who + ": the command of robot " + std::to_string((i / 3) % B) + (rows > 1 ? " at row " + std::to_string(i / (3 * B)) : std::string()) + " is not finite");
+    }
+    return SRBDQP_OK;
+}
+
+// one launch of the tracked inputs; the arguments have been checked.  pose_log: the row of a roll-out's log, or null
+int mpc_inputs_tracked_launch(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command, const uint8_t* standing,
+                              const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, double* landing_yaw,
+                              const srbdqp_track_settings* trk, double* pose, double* pose_log, hipStream_t st) {
+    srbdqp::TrackInputsArgs ta;
+    std::memset(&ta, 0, sizeof(ta));
+    srbdqp::SteerInputsArgs& a = ta.s;
+    a.x0 = x0; a.feet = feet; a.stamp = stamp; a.command = command; a.standing = standing;
+    a.x_ref = x_ref; a.foot = foot; a.contact = contact; a.pcom = pcom; a.landing = landing; a.landing_yaw = landing_yaw;
+    for (int i = 0; i < 3; ++i) a.com_target[i] = gait->com_target[i];
+    a.hip_offset_y = gait->hip_offset_y; a.dt = h->cfg.dt;
+    a.N = h->cfg.horizon; a.period = gait->period_steps; a.ds = gait->double_support_steps;
+    a.B = (long long)B;
+    ta.pose = pose; ta.pose_log = pose_log; ta.lead_max = trk->lead_max; ta.yaw_lead_max = trk->yaw_lead_max;
+    HIP_TRY(h, srbdqp::launch_mpc_inputs_tracked(ta, h->live_nstar != 0, st));
+    h->kname = "mpc_inputs_tracked_f64";
+    return SRBDQP_OK;
+}
+
+// host: the call comes from mpc_inputs_tracked_host behind its staging, which has made track_check's decisions on the caller's arrays already
+int mpc_inputs_tracked_device(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command, const uint8_t* standing,
+                              const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, double* landing_yaw,
+                              const srbdqp_track_settings* trk, double* pose, bool host, void* stream) {
+    if (!host) if (const int rc = track_check(h, "srbdqp_mpc_inputs_tracked", B, trk, pose, nullptr, 1, false)) return rc;
+    if (const int rc = mpc_inputs_check(h, B, true, x0, feet, stamp, command, x_ref, foot, contact, pcom)) return rc;
+    if (const char* why = gait_fault(gait)) { h->err = std::string("invalid srbdqp_gait ") + why; return SRBDQP_E_INVALID; }
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+    return mpc_inputs_tracked_launch(h, B, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw, trk, pose, nullptr, st);
+}
+
+int mpc_inputs_tracked_host(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command, const uint8_t* standing,
+                            const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, double* landing_yaw,
+                            const srbdqp_track_settings* trk, double* pose) {
+    // (pose and command are the caller's host arrays: they are read before the handle is)
+    if (const int rc = track_check(h, "srbdqp_mpc_inputs_tracked", B, trk, pose, command, 1, true)) return rc;
+    if (const int rc = mpc_inputs_check(h, B, true, x0, feet, stamp, command, x_ref, foot, contact, pcom)) return rc;
+    if (const char* why = gait_fault(gait)) { h->err = std::string("invalid srbdqp_gait ") + why; return SRBDQP_E_INVALID; }
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
+    double *dx0, *dfe, *dst, *dv, *dxr, *dft, *dpc, *dlp, *dly, *dpo;
+    uint8_t *dsd, *dct;
+    return host_call(h, [&](HostIo& io) {
+        dx0 = io.in<double>(x0, b * 13 * 8); dfe = io.in<double>(feet, b * 12 * 8); dst = io.in<double>(stamp, b * 8); dv = io.in<double>(command, b * 3 * 8);
+        dsd = io.in<uint8_t>(standing, b);
+        dxr = io.out<double>(x_ref, b * N * 13 * 8); dft = io.out<double>(foot, b * N * 12 * 8); dct = io.out<uint8_t>(contact, b * N * 4);
+        dpc = io.out<double>(pcom, b * N * 3 * 8); dlp = io.out<double>(landing, b * 3 * 8); dly = io.out<double>(landing_yaw, b * 8);
+        dpo = io.add<double>(pose, pose, b * 3 * 8, false);
+    }, [&](hipStream_t st) { return mpc_inputs_tracked_device(h, B, dx0, dfe, dst, dv, dsd, gait, dxr, dft, dct, dpc, dlp, dly, trk, dpo, true, st); });
+}
+
 // ---- the K-step loop: one argument record, one check, one loop, one host path for the six srbdqp_fleet_rollout_* entry points ----
 // what a roll-out does beside mpc_inputs -> solve -> fleet_advance: an observer behind every plant step (section 19), steered inputs and footholds (section 20).
 // (The ground is the handle's: a terrain set makes any of them a terrain roll-out, section 18)
-enum : unsigned { kObserved = 1u, kSteered = 2u };
+enum : unsigned { kObserved = 1u, kSteered = 2u, kTracked = 4u };   // kTracked: a steered roll-out whose inputs call is the tracked one (section 21)
 
 // the arguments of a roll-out, as its entry point got them: device addresses, or the caller's host arrays (fleet_rollout_host)
 struct RolloutArgs {
@@ -2939,6 +3016,7 @@ struct RolloutArgs {
     const srbdqp_observer_settings* obs; double *w_est, *w_log;   // read in an observed roll-out only
     unsigned flavour;                  // kSteered: srbdqp_fleet_rollout_steered_*, which with obs is kObserved too; kObserved: ..._observed_*
     const char* fn;                    // the roll-out the call becomes, for error texts: srbdqp_fleet_rollout or srbdqp_fleet_rollout_observed
+    const srbdqp_track_settings* trk; double *pose, *pose_log;    // read in a tracked roll-out only (kTracked, beside kSteered)
 };
 
 // the horizon buffers of a roll-out of this flavour (kObserved | kSteered), at B robots, carved from one allocation of the handle's.  What a flavour has
@@ -3022,9 +3100,12 @@ int wrench_observer_check(srbdqp_handle* h, int64_t B, const void* x_prev, const
 constexpr unsigned kFormsObservedRollout = bit(Form::Robots) | bit(Form::Weights);
 int fleet_rollout_check(srbdqp_handle* h, const RolloutArgs& a, bool host) {
     if (a.flavour & kSteered) {
-        if (!a.command) return steer_refuse(h, "srbdqp_fleet_rollout_steered: command is NULL ([B][3] held over the call, or [T][B][3] with command_steps = T)");
-        if (a.command_steps != 1 && a.command_steps != a.T) return steer_refuse(h, "srbdqp_fleet_rollout_steered: command_steps must be 1 (one command held) or T (a row per step)");
-        if (host && a.B >= 1 && a.B <= 0x7fffffffLL && a.T >= 1) {
+        const bool tracked = a.flavour & kTracked;
+        if (!a.command) return steer_refuse(h, std::string(tracked ? "srbdqp_fleet_rollout_tracked" : "srbdqp_fleet_rollout_steered") + ": command is NULL ([B][3] held over the call, or [T][B][3] with command_steps = T)");
+        if (a.command_steps != 1 && a.command_steps != a.T) return steer_refuse(h, std::string(tracked ? "srbdqp_fleet_rollout_tracked" : "srbdqp_fleet_rollout_steered") + ": command_steps must be 1 (one command held) or T (a row per step)");
+        // tracked: the settings and the pose, and on host arrays a pose and a command that are finite
+        if (tracked) { if (const int rc = track_check(h, "srbdqp_fleet_rollout_tracked", a.B, a.trk, a.pose, a.T >= 1 ? a.command : nullptr, (size_t)a.command_steps, host)) return rc; }
+        else if (host && a.B >= 1 && a.B <= 0x7fffffffLL && a.T >= 1) {
             const long long i = steer_non_finite(a.command, (size_t)a.command_steps * (size_t)a.B * 3);
             if (i >= 0) return steer_refuse(h, "srbdqp_fleet_rollout_steered: the command of robot " + std::to_string((i / 3) % a.B) + " at row " + std::to_string(i / (3 * a.B)) + " is not finite");
         }
@@ -3196,7 +3277,11 @@ int fleet_rollout_run(srbdqp_handle* h, const RolloutArgs& a, void* stream) {
     for (int32_t t = 0; t < a.T; ++t) {
         const size_t k = (size_t)t;
         // steered: row t of a schedule, or the one command held; the inputs also say how the next foot lands turned (section 20)
-        if (const int rc = a.command ? mpc_inputs_steered_launch(h, B, a.x, a.feet, a.stamp, a.command + (a.command_steps == 1 ? 0 : k * b * 3), a.standing, &a.cfg->gait,
+        // tracked: the references come from the pose the caller carries, which the inputs kernel bounds, advances and logs itself (section 21)
+        if (const int rc = a.pose    ? mpc_inputs_tracked_launch(h, B, a.x, a.feet, a.stamp, a.command + (a.command_steps == 1 ? 0 : k * b * 3), a.standing, &a.cfg->gait,
+                                                                 f.x_ref, f.foot, f.contact, f.pcom, f.landing, f.landing_yaw, a.trk, a.pose,
+                                                                 a.pose_log ? a.pose_log + k * b * 3 : nullptr, st)
+                         : a.command ? mpc_inputs_steered_launch(h, B, a.x, a.feet, a.stamp, a.command + (a.command_steps == 1 ? 0 : k * b * 3), a.standing, &a.cfg->gait,
                                                                  f.x_ref, f.foot, f.contact, f.pcom, f.landing, f.landing_yaw, st)
                                      : mpc_inputs_launch(h, B, a.x, a.feet, a.stamp, a.v_ref, a.standing, &a.cfg->gait, f.x_ref, f.foot, f.contact, f.pcom, f.landing, st))
             return rc;
@@ -3255,6 +3340,7 @@ int fleet_rollout_host(srbdqp_handle* h, RolloutArgs a) {
         d.x_log = io.out<double>(a.x_log, (steps + 1) * b * 13 * 8); d.u0_log = io.out<double>(a.u0_log, steps * b * 12 * 8); d.feet_log = io.out<double>(a.feet_log, (steps + 1) * b * 12 * 8);
         d.status_log = io.out<int32_t>(a.status_log, steps * b * 4); d.iters_log = io.out<int32_t>(a.iters_log, steps * b * 4);
         if (a.obs) { d.w_est = io.add<double>(a.w_est, a.w_est, b * 6 * 8, false); d.w_log = io.out<double>(a.w_log, steps * b * 6 * 8); }
+        if (a.pose) { d.pose = io.add<double>(a.pose, a.pose, b * 3 * 8, false); d.pose_log = io.out<double>(a.pose_log, steps * b * 3 * 8); }
     }, [&](hipStream_t st) { return fleet_rollout_run(h, d, st); });
 }
 }  // namespace
@@ -3307,6 +3393,27 @@ int srbdqp_mpc_inputs_steered_f64(srbdqp_handle* h, int64_t B, const double* x0,
                                   const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
                                   double* landing, double* landing_yaw) {
     return mpc_inputs_host(h, B, true, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw);
+}
+
+// ---- a fleet that follows its path (include/srbdqp_cascade.h) ----
+int srbdqp_track_default_settings(srbdqp_track_settings* s) {
+    if (!s || s->struct_size != (int32_t)sizeof(srbdqp_track_settings)) return SRBDQP_E_INVALID;
+    std::memset(s, 0, sizeof(*s));
+    s->struct_size = (int32_t)sizeof(srbdqp_track_settings);
+    s->lead_max = 0.1; s->yaw_lead_max = 0.3;
+    return SRBDQP_OK;
+}
+
+int srbdqp_mpc_inputs_tracked_device_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
+                                         const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
+                                         double* landing, double* landing_yaw, const srbdqp_track_settings* trk, double* pose, void* stream) {
+    return mpc_inputs_tracked_device(h, B, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw, trk, pose, false, stream);
+}
+
+int srbdqp_mpc_inputs_tracked_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
+                                  const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
+                                  double* landing, double* landing_yaw, const srbdqp_track_settings* trk, double* pose) {
+    return mpc_inputs_tracked_host(h, B, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw, trk, pose);
 }
 
 // ---- the momentum observer (include/srbdqp_cascade.h) ----
@@ -3389,6 +3496,27 @@ int srbdqp_fleet_rollout_steered_f64(srbdqp_handle* h, int64_t B, int32_t T, dou
                                      const srbdqp_observer_settings* obs, double* w_est, double* w_log) {
     return fleet_rollout_host(h, {B, T, x, feet, stamp, nullptr, command, command_steps, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log,
                                   obs, w_est, w_log, kSteered | (obs ? kObserved : 0u), obs ? "srbdqp_fleet_rollout_observed" : "srbdqp_fleet_rollout"});
+}
+
+// (the steered roll-out with the tracked inputs call: refused as the roll-out it becomes is, after the pose's and the settings' own rules)
+int srbdqp_fleet_rollout_tracked_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
+                                            int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                            double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                            const srbdqp_observer_settings* obs, double* w_est, double* w_log,
+                                            const srbdqp_track_settings* trk, double* pose, double* pose_log, void* stream) {
+    return fleet_rollout_device(h, {B, T, x, feet, stamp, nullptr, command, command_steps, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log,
+                                    obs, w_est, w_log, kTracked | kSteered | (obs ? kObserved : 0u), obs ? "srbdqp_fleet_rollout_observed" : "srbdqp_fleet_rollout",
+                                    trk, pose, pose_log}, stream);
+}
+
+int srbdqp_fleet_rollout_tracked_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
+                                     int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                     double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                     const srbdqp_observer_settings* obs, double* w_est, double* w_log,
+                                     const srbdqp_track_settings* trk, double* pose, double* pose_log) {
+    return fleet_rollout_host(h, {B, T, x, feet, stamp, nullptr, command, command_steps, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log,
+                                  obs, w_est, w_log, kTracked | kSteered | (obs ? kObserved : 0u), obs ? "srbdqp_fleet_rollout_observed" : "srbdqp_fleet_rollout",
+                                  trk, pose, pose_log});
 }
 
 }  // extern "C"

@@ -124,4 +124,24 @@ hipError_t launch_terrain_inputs(const TerrainInputsArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ... and the step before the QP of a fleet that follows its path (srbdqp_steer.hpp): the steered launch's grid and horizons.  Behind
+// every other kernel of this code object, which keeps their order
+hipError_t launch_mpc_inputs_tracked(const TrackInputsArgs& a, bool live, hipStream_t st) {
+    const long long tiles = (a.s.B + 31) / 32;                     // one tile of 32 robots per workgroup pass
+    const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
+    if (a.s.N < 1 || a.s.N > kSteerSteps - 1) return hipErrorInvalidValue;   // (the tables hold 25 entries a robot)
+    if (live) hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<0>, grid, dim3(256), 0, st, a);
+    else switch (a.s.N) {
+        case 4: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<4>, grid, dim3(256), 0, st, a); break;
+        case 8: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<8>, grid, dim3(256), 0, st, a); break;
+        case 10: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<10>, grid, dim3(256), 0, st, a); break;
+        case 12: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<12>, grid, dim3(256), 0, st, a); break;
+        case 16: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<16>, grid, dim3(256), 0, st, a); break;
+        case 20: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<20>, grid, dim3(256), 0, st, a); break;
+        case 24: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<24>, grid, dim3(256), 0, st, a); break;
+        default: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<0>, grid, dim3(256), 0, st, a); break;
+    }
+    return hipGetLastError();
+}
+
 }  // namespace srbdqp

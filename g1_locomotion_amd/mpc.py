@@ -518,6 +518,57 @@ class BatchMPC(_Engine):
                                                             v(x_ref), v(foot), v(contact), v(pcom), v(landing), v(landing_yaw), v(stream))
         self._check(rc)
 
+    # -- a fleet that follows its path: the inputs from a carried reference pose (include/srbdqp_cascade.h) ------
+    def track_settings(self, lead_max=0.1, yaw_lead_max=0.3):
+        """srbdqp_track_settings for mpc_inputs_tracked() / rollout(track=): how far the reference pose may lie from the measured position (m) and from the
+        measured yaw (rad) before it is pulled back; both finite and positive."""
+        s = _lib.TrackSettings()
+        s.struct_size = C.sizeof(_lib.TrackSettings)
+        s.lead_max, s.yaw_lead_max = float(lead_max), float(yaw_lead_max)
+        return s
+
+    def _track_arg(self, track):
+        """rollout()'s track=: True (the defaults), a dict of track_settings()' keywords, or a TrackSettings."""
+        if isinstance(track, _lib.TrackSettings):
+            return track
+        return self.track_settings(**({} if track is True else dict(track)))
+
+    def mpc_inputs_tracked(self, x0, feet, stamp, command, pose, com_target, standing=None, period_steps=6, double_support_steps=1, hip_offset_y=0.0645,
+                           **track):
+        """mpc_inputs_steered() with the references taken from pose (B,3) = (qx, qy, th), a reference position and an unwrapped reference heading that the
+        caller carries from step to step (srbdqp_mpc_inputs_tracked_f64): the pose is first bounded to within lead_max and yaw_lead_max
+        of the measured state, the references start from it whether the robot moves or not, and it moves on by one control step under the command.  pcom,
+        foot, contact, landing and landing_yaw are mpc_inputs_steered()'s.  track: track_settings()' keywords.  pose is not modified; a pose or a command
+        that is not finite raises SrbdqpError.
+        Returns mpc_inputs_steered()'s dict and pose (B,3), the pose behind the step: the next call's argument."""
+        x = _c(x0, np.float64).reshape(-1, NX)
+        B, N = x.shape[0], self.N
+        f = _c(feet, np.float64).reshape(B, NU)
+        t = _c(stamp, np.float64).reshape(B)
+        c = _as(command, np.float64, (B, 3), "command")
+        po = np.array(_as(pose, np.float64, (B, 3), "pose"))
+        sd = None if standing is None else _c(standing, np.uint8).reshape(B)
+        g = self._gait_struct(period_steps, double_support_steps, com_target, hip_offset_y)
+        k = self.track_settings(**track)
+        xr, ft, ct = np.empty((B, N, NX)), np.empty((B, N, NU)), np.empty((B, N, NC), dtype=np.uint8)
+        pc, lp, ly = np.empty((B, N, 3)), np.empty((B, 3)), np.empty(B)
+        rc = self._lib.srbdqp_mpc_inputs_tracked_f64(self._h, B, _p(x), _p(f), _p(t), _p(c), _p(sd), C.byref(g), _p(xr), _p(ft), _p(ct), _p(pc), _p(lp), _p(ly),
+                                                     C.byref(k), _p(po))
+        self._check(rc)
+        return dict(x_ref=xr, foot=ft, contact=ct, pcom=pc, landing=lp, landing_yaw=ly, pose=po)
+
+    def mpc_inputs_tracked_device(self, B, x0, feet, stamp, command, pose, com_target, x_ref, foot, contact, pcom, landing=0, landing_yaw=0, standing=0,
+                                  period_steps=6, double_support_steps=1, hip_offset_y=0.0645, stream=0, **track):
+        """Device-pointer form of mpc_inputs_tracked(): raw addresses in, pose (B,3) updated in place, launch enqueued behind `stream`, returns at once.  A
+        state or a pose that is not finite clamps nothing; a pose or a command that is not finite gives that robot references that are not numbers and leaves
+        its pose where the bound left it."""
+        v = lambda q: C.c_void_p(int(q)) if q else None
+        g = self._gait_struct(period_steps, double_support_steps, com_target, hip_offset_y)
+        k = self.track_settings(**track)
+        rc = self._lib.srbdqp_mpc_inputs_tracked_device_f64(self._h, int(B), v(x0), v(feet), v(stamp), v(command), v(standing), C.byref(g),
+                                                            v(x_ref), v(foot), v(contact), v(pcom), v(landing), v(landing_yaw), C.byref(k), v(pose), v(stream))
+        self._check(rc)
+
     # -- from step t to step t + 1: the fleet's plant step and the K-step loop (include/srbdqp_cascade.h, DESIGN.md section 17) --------
     def fleet_settings(self, com_target=(0.0, 0.0, 0.0), substeps=10, foot_half_length=0.085, z_min=0.3, tilt_max=1.0, period_steps=6,
                        double_support_steps=1, hip_offset_y=0.0645):
@@ -606,7 +657,8 @@ class BatchMPC(_Engine):
         self._check(self._lib.srbdqp_wrench_observer_device_f64(self._h, int(B), v(x_prev), v(x_next), v(feet_prev), v(u0), int(u0_stride), v(alive),
                                                                 C.byref(s), v(w_est), v(ew), v(stream)))
 
-    def rollout(self, x0, feet, stamp, v_ref, steps, com_target, standing=None, push=None, alive=None, observer=None, w_est=None, command=None, **settings):
+    def rollout(self, x0, feet, stamp, v_ref, steps, com_target, standing=None, push=None, alive=None, observer=None, w_est=None, command=None, track=None,
+                pose=None, **settings):
         """`steps` control steps of B robots on the device (srbdqp_fleet_rollout_f64): per step mpc_inputs -> the solve -> fleet_advance, without a host
         round trip in between.  x0 (B,13), feet (B,12) or (B,4,3), stamp (B,), v_ref (B,2) and standing (B,) flags or None (both constant over the call),
         push (steps,B,6) world wrenches or None, alive (B,) flags or None.  settings: fleet_settings()' keywords.  Robot records and weights set on the
@@ -624,6 +676,11 @@ class BatchMPC(_Engine):
         command (B,3) or (steps,B,3), with v_ref=None: the steered roll-out (srbdqp_fleet_rollout_steered_f64) -- (vx, vy, wz), planar
         velocity in each robot's heading frame and yaw rate, held over the call or a row per step; per step mpc_inputs_steered -> the solve ->
         fleet_advance(landing_yaw=), on flat ground, on a map, or with observer=.  command=None is the call as it was.
+        track=True or a dict of track_settings()' keywords, with command=: the tracked roll-out (srbdqp_fleet_rollout_tracked_f64) --
+        mpc_inputs_tracked in place of mpc_inputs_steered: the references come from a pose (B,3) = (qx, qy, th) that moves on with the commands and is kept
+        within lead_max and yaw_lead_max of the robot, so that the fleet ends where its commands lead.  pose=None starts on the measured (x0[3:5], x0[2]);
+        carried from one call to the next, chunks compose bit for bit.  The result then has pose (B,3) and pose_log (steps,B,3), the pose behind every
+        step.  track=None is the call as it was.
         Returns dict(x (steps+1,B,13), u0 (steps,B,12), feet (steps+1,B,12), status (steps,B), iters (steps,B), alive (B,) uint8, stamp (B,))."""
         x = np.array(x0, dtype=np.float64).reshape(-1, NX)
         B, T = x.shape[0], int(steps)
@@ -646,6 +703,11 @@ class BatchMPC(_Engine):
         observed = observer is not None and observer is not False
         if w_est is not None and not observed:
             raise ValueError("rollout: w_est belongs to an observed roll-out (observer=)")
+        tracked = track is not None and track is not False
+        if tracked and command is None:
+            raise ValueError("rollout: track= follows a command schedule (command=): there is no path without one")
+        if pose is not None and not tracked:
+            raise ValueError("rollout: pose belongs to a tracked roll-out (track=)")
         out = dict(x=xl, u0=ul, feet=fl, status=sl, iters=il, alive=al, stamp=t)
         obs = ()
         if observed:
@@ -654,17 +716,23 @@ class BatchMPC(_Engine):
             obs = (C.byref(o), _p(out["w_est"]), _p(out["w_log"]))
         if command is not None:     # (one steered call, with its observer or without)
             fn, vel, obs = self._lib.srbdqp_fleet_rollout_steered_f64, (_p(cm), 1 if cm.ndim == 2 else T), obs or (None, None, None)
+            if tracked:             # (... and the tracked call takes its settings, pose and pose_log behind the observer's)
+                k = self._track_arg(track)
+                po = np.concatenate([x[:, 3:5], x[:, 2:3]], axis=1) if pose is None else np.array(_as(pose, np.float64, (B, 3), "pose"))
+                out.update(pose=np.ascontiguousarray(po), pose_log=np.empty((n, B, 3)))
+                fn, obs = self._lib.srbdqp_fleet_rollout_tracked_f64, obs + (C.byref(k), _p(out["pose"]), _p(out["pose_log"]))
         else:
             fn, vel = self._lib.srbdqp_fleet_rollout_observed_f64 if observed else self._lib.srbdqp_fleet_rollout_f64, (_p(v),)
         self._check(fn(self._h, B, T, _p(x), _p(f), _p(t), *vel, _p(sd), _p(pu), C.byref(s), _p(al), _p(xl), _p(ul), _p(fl), _p(sl), _p(il), *obs))
         return out
 
     def rollout_device(self, B, steps, x, feet, stamp, v_ref, com_target, standing=0, push=0, alive=0, x_log=0, u0_log=0, feet_log=0, status_log=0,
-                       iters_log=0, stream=0, observer=None, w_est=0, w_log=0, command=0, command_steps=1, **settings):
+                       iters_log=0, stream=0, observer=None, w_est=0, w_log=0, command=0, command_steps=1, track=None, pose=0, pose_log=0, **settings):
         """Device-pointer form of rollout(): raw addresses (0 = absent), x / feet / stamp / alive updated in place, every launch enqueued behind `stream`
         (0 = the engine's own), returns at once without synchronising.  Logs as in include/srbdqp_cascade.h.  observer= as in rollout(): w_est (B,6),
         required then, is updated in place; w_log (steps,B,6) or 0.  command: the address of (B,3) commands (command_steps=1) or of (steps,B,3)
-        (command_steps=steps) -- the steered roll-out, v_ref 0 then; 0: the call as it was."""
+        (command_steps=steps) -- the steered roll-out, v_ref 0 then; 0: the call as it was.  track= as in rollout(), with command: pose (B,3), required
+        then, is updated in place; pose_log (steps,B,3) or 0."""
         v = lambda q: C.c_void_p(int(q)) if q else None
         s = self.fleet_settings(com_target, **settings)
         if command and v_ref:
@@ -676,8 +744,16 @@ class BatchMPC(_Engine):
         if observed:
             o = self._observer_arg(observer)
             obs = (C.byref(o), v(w_est), v(w_log))
+        tracked = track is not None and track is not False
+        if tracked and not command:
+            raise ValueError("rollout_device: track= follows a command schedule (command=): there is no path without one")
+        if (pose or pose_log) and not tracked:
+            raise ValueError("rollout_device: pose and pose_log belong to a tracked roll-out (track=)")
         if command:     # (one steered call, with its observer or without)
             fn, vel, obs = self._lib.srbdqp_fleet_rollout_steered_device_f64, (v(command), int(command_steps)), obs or (None, None, None)
+            if tracked:
+                k = self._track_arg(track)
+                fn, obs = self._lib.srbdqp_fleet_rollout_tracked_device_f64, obs + (C.byref(k), v(pose), v(pose_log))
         else:
             fn, vel = self._lib.srbdqp_fleet_rollout_observed_device_f64 if observed else self._lib.srbdqp_fleet_rollout_device_f64, (v(v_ref),)
         self._check(fn(self._h, int(B), int(steps), v(x), v(feet), v(stamp), *vel, v(standing), v(push), C.byref(s), v(alive), v(x_log), v(u0_log), v(feet_log),

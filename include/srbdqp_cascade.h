@@ -284,7 +284,7 @@ int srbdqp_fleet_advance_steered_device_f64(srbdqp_handle* h, int64_t B, double*
  * Refused: what the roll-out it becomes refuses; command NULL; command_steps outside {1, T}; in the host form a command that is not finite.  Chunks compose bit
  * for bit, a schedule with the two constant-command chunks it is made of included.
  * Not modelled: footholds previewed along the horizon (foot[b][k] stays the current points), a centrifugal term in the landing point, feet turned under a
- * standing robot, ragged fleets, fp32, a heading controller on top of the rate command. */
+ * standing robot, ragged fleets, fp32.  (A robot that is to be where its commands lead: srbdqp_fleet_rollout_tracked_* below.) */
 int srbdqp_fleet_rollout_steered_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
                                             int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
                                             double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
@@ -293,6 +293,65 @@ int srbdqp_fleet_rollout_steered_f64(srbdqp_handle* h, int64_t B, int32_t T, dou
                                      int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
                                      double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
                                      const srbdqp_observer_settings* obs, double* w_est, double* w_log);
+
+/* ---- a fleet that follows its path: a carried reference pose with a bounded lead.
+ *
+ * srbdqp_mpc_inputs_steered_* restarts its references from the measured state at every control step, so a lag behind the command is never integrated away.  A
+ * tracked robot has a pose (qx, qy, th) -- a planar reference position and an unwrapped reference heading -- in a caller-owned array pose [B][3] that goes in
+ * and out, the way w_est does for the observer: the references start from the pose, the pose moves on with the command, and a bound keeps it from running
+ * ahead of a robot that is held back.  srbdqp_mpc_inputs_tracked_* per robot, with the command (vx, vy, wz), psi0 = x0[2], and v_w, the heading psi + (wz j) dt,
+ * the table of positions and T = period_steps dt as in srbdqp_mpc_inputs_steered_*; every product and sum one rounded fp64 operation in the order written:
+ *   1. bound     dx = qx - x0[3];  dy = qy - x0[4];  n = sqrt(dx dx + dy dy)
+ *                if n > lead_max:  s = lead_max / n;  qx = x0[3] + dx s;  qy = x0[4] + dy s
+ *                dth = th - psi0;  if dth > yaw_lead_max: th = psi0 + yaw_lead_max;  else if dth < -yaw_lead_max: th = psi0 - yaw_lead_max
+ *                A pose inside the bounds is untouched, bit for bit.  Every comparison is false on a NaN: a state or a pose that is not finite clamps nothing.
+ *   2. refer     q_0 = (qx, qy);  q_{k+1} = q_k + v_w(th + wz (k + 1/2) dt) dt, k = 0 ... N - 1   (the serial sum of the steered call, from the pose)
+ *                x_ref[k][2]    = th + (wz (k + 1)) dt
+ *                x_ref[k][3:5]  = q_{k+1}, moving or not: a zero planar velocity holds the pose's position, it does not go back to com_target
+ *                x_ref[k][5]    = com_target[2];  x_ref[k][8] = wz;  x_ref[k][9:11] = v_w(th + (wz (k + 1)) dt);  x_ref[k][12] = x0[12];  every other entry 0
+ *   3. measured  pcom, foot, contact, landing and landing_yaw are those of srbdqp_mpc_inputs_steered_*, bit for bit: the linearisation points and the Raibert
+ *                landing point belong to where the robot is.
+ *   4. advance   pose' = (q_1, th + (wz 1) dt).  If one of the three is not finite the pose is written back as it stood after step 1: a bad command row costs
+ *                that robot one step, not the rest of the roll-out.  (The references of that step are not numbers, and the solve's non-finite contract
+ *                answers them as in the steered call.)
+ * With pose = (x0[3], x0[4], x0[2]) and a moving command every output is srbdqp_mpc_inputs_steered_*'s bit for bit.  The host forms refuse a pose or a command
+ * that is not finite, by robot (SRBDQP_E_INVALID); the device forms follow the rules above, and no trip count depends on a command, a state or a pose.  Any
+ * horizon of the handle, live ones included.  srbdqp_kernel_name: mpc_inputs_tracked_f64. */
+typedef struct srbdqp_track_settings {
+    int32_t struct_size;          /* = sizeof(srbdqp_track_settings) */
+    int32_t reserved0;
+    double lead_max;              /* how far the pose's position may lie from the measured one, m: finite, positive (0.1) */
+    double yaw_lead_max;          /* how far its heading may lie from the measured yaw, rad: finite, positive (0.3) */
+} srbdqp_track_settings;
+
+/* The defaults above into *s; s->struct_size says how large the caller's struct is (checked before anything is written). */
+int srbdqp_track_default_settings(srbdqp_track_settings* s);
+
+/* The arguments of srbdqp_mpc_inputs_steered_*, then trk and pose [B][3] in/out (required). */
+int srbdqp_mpc_inputs_tracked_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
+                                  const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
+                                  double* landing, double* landing_yaw, const srbdqp_track_settings* trk, double* pose);
+int srbdqp_mpc_inputs_tracked_device_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
+                                         const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
+                                         double* landing, double* landing_yaw, const srbdqp_track_settings* trk, double* pose, void* stream);
+
+/* srbdqp_fleet_rollout_steered_* with srbdqp_mpc_inputs_tracked_device_f64 as its inputs call; nothing else in the loop changes, so a terrain on the handle,
+ * obs != NULL and the plain loop work as they do there.  The arguments of the steered roll-out, then trk, pose [B][3] in/out (required) and pose_log [T][B][3]
+ * or NULL: pose_log[t] is the pose behind step t, written by the inputs kernel itself (no further launch).
+ * Refused: what the roll-out it becomes refuses; pose NULL; bad track settings; in the host form a pose or a command that is not finite, by robot.  Chunks
+ * compose bit for bit with pose carried by the caller, a schedule with its constant-command chunks included.
+ * A robot that has fallen holds its state while its pose keeps moving on and keeps being clamped to within the bounds of that held state.
+ * Not modelled: footholds previewed along the horizon, ragged fleets, fp32, a pose for the unsteered v_ref roll-out. */
+int srbdqp_fleet_rollout_tracked_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
+                                            int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                            double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                            const srbdqp_observer_settings* obs, double* w_est, double* w_log,
+                                            const srbdqp_track_settings* trk, double* pose, double* pose_log, void* stream);
+int srbdqp_fleet_rollout_tracked_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
+                                     int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                     double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                     const srbdqp_observer_settings* obs, double* w_est, double* w_log,
+                                     const srbdqp_track_settings* trk, double* pose, double* pose_log);
 
 #ifdef __cplusplus
 }

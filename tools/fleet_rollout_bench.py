@@ -18,7 +18,11 @@ per launch and GB/s.  Beside --kernel wrench in the same job: the cost of observ
 run taken in the heading frame --, the Python loop through mpc_inputs_steered_device and fleet_advance_device(landing_yaw=), and the steered inputs kernel
 alone: time per launch and GB/s, with mpc_inputs measured the same way beside it.  Combines with --terrain and --observer.
 
-    python tools/fleet_rollout_bench.py [--robots 4096] [--steps 100] [--reps 5] [--terrain] [--observer] [--steer] [--kernel auto|wrench] [--out profiles/<name>.json]
+--track: the tracked roll-out -- --steer's fleet and commands with a reference pose carried from step to step, from the measured pose,
+under the default bounds --, the Python loop through mpc_inputs_tracked_device, and the tracked inputs kernel alone beside the other two: time per launch, GB/s
+and its share of a step; the fleet's distance from the path its commands lead along, beside what --steer leaves.  Implies --steer's commands.
+
+    python tools/fleet_rollout_bench.py [--robots 4096] [--steps 100] [--reps 5] [--terrain] [--observer] [--steer] [--track] [--kernel auto|wrench] [--out profiles/<name>.json]
 """
 import argparse
 import hashlib
@@ -50,11 +54,13 @@ def main():
     ap.add_argument("--terrain", action="store_true")
     ap.add_argument("--observer", action="store_true")
     ap.add_argument("--steer", action="store_true")
+    ap.add_argument("--track", action="store_true")
     ap.add_argument("--kernel", choices=("auto", "wrench"), default="auto")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if a.terrain and a.observer:
         ap.error("--observer is flat ground: no roll-out reads normals beside a wrench")
+    a.steer = a.steer or a.track                                          # (a path needs commands)
     import torch
     from g1_locomotion_amd import BatchMPC, _lib
     B, T, N, dt = a.robots, a.steps, 10, 0.04
@@ -75,13 +81,19 @@ def main():
     d_cm = up(np.concatenate([v_ref, rng.uniform(-0.6, 0.6, (B, 1))], axis=1)) if a.steer else None
     ly = torch.empty(B, dtype=torch.float64, device=dev) if a.steer else None
     steer = dict(command=d_cm.data_ptr(), command_steps=1) if a.steer else {}
+    # the pose starts on the robot; pose_log: where the commands have led, as far as the bounds let it
+    pose0 = np.concatenate([x0[:, 3:5], x0[:, 2:3]], axis=1)
+    d_po, d_pl = (torch.empty((B, 3), dtype=torch.float64, device=dev), torch.empty((T, B, 3), dtype=torch.float64, device=dev)) if a.track else (None, None)
+    if a.track:
+        steer.update(track=True, pose=d_po.data_ptr(), pose_log=d_pl.data_ptr())
     f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)
     xl, ul, fl = f64(T + 1, B, 13), f64(T, B, 12), f64(T + 1, B, 12)
     sl, il = torch.empty((T, B), dtype=torch.int32, device=dev), torch.empty((T, B), dtype=torch.int32, device=dev)
     xr, fo, pc, lp, u, xo = f64(B, N, 13), f64(B, N, 12), f64(B, N, 3), f64(B, 3), f64(B, N, 12), f64(B, N + 1, 13)
     ct = torch.empty((B, N, 4), dtype=torch.uint8, device=dev)
     st, it = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
-    res = dict(robots=B, steps=T, horizon=N, reps=a.reps, terrain=bool(a.terrain), observer=bool(a.observer), steer=bool(a.steer), kernel_setting=a.kernel)
+    res = dict(robots=B, steps=T, horizon=N, reps=a.reps, terrain=bool(a.terrain), observer=bool(a.observer), steer=bool(a.steer), track=bool(a.track),
+               kernel_setting=a.kernel)
     cn = f64(B, N, 12) if a.terrain else None
     we, wl, ew = (f64(B, 6), f64(T, B, 6), f64(B, N, 6)) if a.observer else (None, None, None)
     obs = dict(observer=True, w_est=we.data_ptr(), w_log=wl.data_ptr()) if a.observer else {}
@@ -101,6 +113,8 @@ def main():
             x, feet, stamp, al = fresh()
             if a.observer:
                 we.zero_()
+            if a.track:
+                d_po.copy_(up(pose0))
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             eng.rollout_device(B, T, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), 0 if a.steer else d_v.data_ptr(), COM, push=d_pu.data_ptr(), alive=al.data_ptr(),
@@ -115,10 +129,15 @@ def main():
                 we.zero_(); ew.zero_()
                 xp, fp = torch.empty_like(x), torch.empty_like(feet)
                 eng.set_external_wrench(ew)
+            if a.track:
+                d_po.copy_(up(pose0))
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for k in range(T):
-                if a.steer:
+                if a.track:
+                    eng.mpc_inputs_tracked_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), d_cm.data_ptr(), d_po.data_ptr(), COM, xr.data_ptr(), fo.data_ptr(),
+                                                  ct.data_ptr(), pc.data_ptr(), landing=lp.data_ptr(), landing_yaw=ly.data_ptr())
+                elif a.steer:
                     eng.mpc_inputs_steered_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), d_cm.data_ptr(), COM, xr.data_ptr(), fo.data_ptr(), ct.data_ptr(),
                                                   pc.data_ptr(), landing=lp.data_ptr(), landing_yaw=ly.data_ptr())
                 else:
@@ -184,7 +203,23 @@ def main():
         if a.steer:                                                       # the inputs kernels alone, back to back: the steered one, and mpc_inputs the same way
             xs, fs, ss, _ = fresh()
             per = {}
-            for name, launch in (("mpc_inputs_steered", lambda: eng.mpc_inputs_steered_device(B, xs.data_ptr(), fs.data_ptr(), ss.data_ptr(), d_cm.data_ptr(), COM, xr.data_ptr(),
+            if a.track:                                                   # where the commands lead, by the references' own midpoint rule (before the launches below move the pose)
+                cm = d_cm.cpu().numpy()
+                q = pose0.copy()
+                for _ in range(T):
+                    th = q[:, 2] + (cm[:, 2] * 0.5) * dt
+                    q = np.stack([q[:, 0] + (np.cos(th) * cm[:, 0] - np.sin(th) * cm[:, 1]) * dt, q[:, 1] + (np.sin(th) * cm[:, 0] + np.cos(th) * cm[:, 1]) * dt,
+                                  q[:, 2] + (cm[:, 2] * 1.0) * dt], axis=1)
+                up_ = calls[-1][2].cpu().numpy() != 0
+                off = np.hypot(*(xl[T, :, 3:5].cpu().numpy() - q[:, 0:2]).T)[up_]
+                res["distance_from_the_path_m_mean"], res["distance_from_the_path_m_max"] = float(off.mean()), float(off.max())
+                res["path_length_m_mean"] = float(np.hypot(cm[:, 0], cm[:, 1]).mean() * T * dt)
+                res["pose_lead_m_max"] = float(np.hypot(*(d_pl[:-1, :, 0:2] - xl[1:T, :, 3:5]).cpu().numpy()[:, up_].transpose(2, 0, 1)).max())
+                res["final_yaw_error_rad_rms"] = float(np.sqrt(np.mean((xl[T, :, 2].cpu().numpy() - q[:, 2])[up_] ** 2)))
+            tracked = (("mpc_inputs_tracked", lambda: eng.mpc_inputs_tracked_device(B, xs.data_ptr(), fs.data_ptr(), ss.data_ptr(), d_cm.data_ptr(), d_po.data_ptr(), COM,
+                                                                                    xr.data_ptr(), fo.data_ptr(), ct.data_ptr(), pc.data_ptr(), landing=lp.data_ptr(),
+                                                                                    landing_yaw=ly.data_ptr())),) if a.track else ()
+            for name, launch in tracked + (("mpc_inputs_steered", lambda: eng.mpc_inputs_steered_device(B, xs.data_ptr(), fs.data_ptr(), ss.data_ptr(), d_cm.data_ptr(), COM, xr.data_ptr(),
                                                                                               fo.data_ptr(), ct.data_ptr(), pc.data_ptr(), landing=lp.data_ptr(), landing_yaw=ly.data_ptr())),
                                  ("mpc_inputs", lambda: eng.mpc_inputs_device(B, xs.data_ptr(), fs.data_ptr(), ss.data_ptr(), d_v.data_ptr(), COM, xr.data_ptr(), fo.data_ptr(),
                                                                               ct.data_ptr(), pc.data_ptr(), landing=lp.data_ptr()))):
@@ -198,8 +233,10 @@ def main():
                     ts.append((time.perf_counter() - t0) / T)
                 per[name] = float(np.median(ts))
                 res[name + "_us_per_launch"] = per[name] * 1e6
-                res[name + "_gb_per_s"] = B * (INPUTS_BYTES + N * (13 + 12 + 3) * 8 + N * 4) / per[name] / 1e9
+                res[name + "_gb_per_s"] = B * (INPUTS_BYTES + (48 if name == "mpc_inputs_tracked" else 0) + N * (13 + 12 + 3) * 8 + N * 4) / per[name] / 1e9
             res["mpc_inputs_steered_share_of_a_rollout_step"] = per["mpc_inputs_steered"] / (t_call / T)
+            if a.track:
+                res["mpc_inputs_tracked_share_of_a_rollout_step"] = per["mpc_inputs_tracked"] / (t_call / T)
             res["final_yaw_rms_error_rad"] = float((xl[T, :, 2] - xl[0, :, 2] - d_cm[:, 2] * (T * dt)).pow(2).mean().sqrt().item())
         res["rollout_call_s"] = t_call
         res["rollout_enqueue_s"] = float(np.median([c[1] for c in calls]))
