@@ -2841,87 +2841,6 @@ long long steer_non_finite(const double* command, size_t count) {
     return -1;
 }
 
-// one launch of the inputs from v_ref [B][2]; the arguments have been checked
-int mpc_inputs_launch(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* v_ref, const uint8_t* standing,
-                      const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, hipStream_t st) {
-    srbdqp::MpcInputsArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.x0 = x0; a.feet = feet; a.stamp = stamp; a.v_ref = v_ref; a.standing = standing;
-    a.x_ref = x_ref; a.foot = foot; a.contact = contact; a.pcom = pcom; a.landing = landing;
-    for (int i = 0; i < 3; ++i) a.com_target[i] = gait->com_target[i];
-    a.hip_offset_y = gait->hip_offset_y; a.dt = h->cfg.dt;
-    a.N = h->cfg.horizon; a.period = gait->period_steps; a.ds = gait->double_support_steps;
-    a.B = (long long)B;
-    const long long tiles = ((long long)B + 31) / 32;                   // one tile of 32 robots per workgroup pass
-    const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
-    int rc = SRBDQP_OK;
-    if (h->live_nstar) hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<0>, grid, dim3(256), 0, st, a);   // (a live horizon: a.N at run time)
-    else rc = with_horizon(h, [&](auto n) -> int {
-        hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<decltype(n)::value>, grid, dim3(256), 0, st, a);
-        return SRBDQP_OK;
-    });
-    if (rc != SRBDQP_OK) return rc;
-    HIP_TRY(h, hipGetLastError());
-    h->kname = "mpc_inputs_f64";
-    return SRBDQP_OK;
-}
-
-// one launch of the steered inputs, from command [B][3]; the arguments have been checked
-int mpc_inputs_steered_launch(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command, const uint8_t* standing,
-                              const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, double* landing_yaw, hipStream_t st) {
-    srbdqp::SteerInputsArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.x0 = x0; a.feet = feet; a.stamp = stamp; a.command = command; a.standing = standing;
-    a.x_ref = x_ref; a.foot = foot; a.contact = contact; a.pcom = pcom; a.landing = landing; a.landing_yaw = landing_yaw;
-    for (int i = 0; i < 3; ++i) a.com_target[i] = gait->com_target[i];
-    a.hip_offset_y = gait->hip_offset_y; a.dt = h->cfg.dt;
-    a.N = h->cfg.horizon; a.period = gait->period_steps; a.ds = gait->double_support_steps;
-    a.B = (long long)B;
-    HIP_TRY(h, srbdqp::launch_mpc_inputs_steered(a, h->live_nstar != 0, st));
-    h->kname = "mpc_inputs_steered_f64";
-    return SRBDQP_OK;
-}
-
-// the inputs behind their four entry points.  steered: vel is a command [B][3] and landing_yaw is written; else vel is v_ref [B][2] and landing_yaw is null
-int mpc_inputs_check(srbdqp_handle* h, int64_t B, bool steered, const void* x0, const void* feet, const void* stamp, const void* vel, const void* x_ref,
-                     const void* foot, const void* contact, const void* pcom) {
-    return arrays_check(h, B >= 0 && !(steered && B > 0x7fffffffLL), B, !x0 || !feet || !stamp || !vel || !x_ref || !foot || !contact || !pcom);
-}
-
-int mpc_inputs_device(srbdqp_handle* h, int64_t B, bool steered, const double* x0, const double* feet, const double* stamp, const double* vel, const uint8_t* standing,
-                      const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, double* landing_yaw, void* stream) {
-    if (const int rc = mpc_inputs_check(h, B, steered, x0, feet, stamp, vel, x_ref, foot, contact, pcom)) return rc;
-    if (const char* why = gait_fault(gait)) { h->err = std::string("invalid srbdqp_gait ") + why; return SRBDQP_E_INVALID; }
-    if (B == 0) return SRBDQP_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
-    return steered ? mpc_inputs_steered_launch(h, B, x0, feet, stamp, vel, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw, st)
-                   : mpc_inputs_launch(h, B, x0, feet, stamp, vel, standing, gait, x_ref, foot, contact, pcom, landing, st);
-}
-
-int mpc_inputs_host(srbdqp_handle* h, int64_t B, bool steered, const double* x0, const double* feet, const double* stamp, const double* vel, const uint8_t* standing,
-                    const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, double* landing_yaw) {
-    // (a command is the caller's host array: it is read before the handle is)
-    if (steered && B > 0 && B <= 0x7fffffffLL && vel) {
-        const long long i = steer_non_finite(vel, (size_t)B * 3);
-        if (i >= 0) return steer_refuse(h, "srbdqp_mpc_inputs_steered: the command of robot " + std::to_string(i / 3) + " is not finite (component " + std::to_string(i % 3) + " of vx, vy, wz)");
-    }
-    if (const int rc = mpc_inputs_check(h, B, steered, x0, feet, stamp, vel, x_ref, foot, contact, pcom)) return rc;
-    // (the v_ref form leaves its gait to the device form behind the staging, as it always has: B = 0 is OK with any gait)
-    if (const char* why = steered ? gait_fault(gait) : nullptr) { h->err = std::string("invalid srbdqp_gait ") + why; return SRBDQP_E_INVALID; }
-    if (B == 0) return SRBDQP_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
-    double *dx0, *dfe, *dst, *dv, *dxr, *dft, *dpc, *dlp, *dly;
-    uint8_t *dsd, *dct;
-    return host_call(h, [&](HostIo& io) {
-        dx0 = io.in<double>(x0, b * 13 * 8); dfe = io.in<double>(feet, b * 12 * 8); dst = io.in<double>(stamp, b * 8); dv = io.in<double>(vel, b * (steered ? 3 : 2) * 8);
-        dsd = io.in<uint8_t>(standing, b);
-        dxr = io.out<double>(x_ref, b * N * 13 * 8); dft = io.out<double>(foot, b * N * 12 * 8); dct = io.out<uint8_t>(contact, b * N * 4);
-        dpc = io.out<double>(pcom, b * N * 3 * 8); dlp = io.out<double>(landing, b * 3 * 8); dly = io.out<double>(landing_yaw, b * 8);
-    }, [&](hipStream_t st) { return mpc_inputs_device(h, B, steered, dx0, dfe, dst, dv, dsd, gait, dxr, dft, dct, dpc, dlp, dly, st); });
-}
-
 // ---- a fleet that follows its path (include/srbdqp_cascade.h; the kernel: srbdqp_steer.hpp) ----
 // what is wrong with a tracked call's settings (null: nothing)
 const char* track_settings_fault(const srbdqp_track_settings* s) {
@@ -2946,63 +2865,113 @@ int track_check(srbdqp_handle* h, const char* fn, int64_t B, const srbdqp_track_
     return SRBDQP_OK;
 }
 
-// one launch of the tracked inputs; the arguments have been checked.  pose_log: the row of a roll-out's log, or null
-int mpc_inputs_tracked_launch(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command, const uint8_t* standing,
-                              const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, double* landing_yaw,
-                              const srbdqp_track_settings* trk, double* pose, double* pose_log, hipStream_t st) {
-    srbdqp::TrackInputsArgs ta;
-    std::memset(&ta, 0, sizeof(ta));
-    srbdqp::SteerInputsArgs& a = ta.s;
-    a.x0 = x0; a.feet = feet; a.stamp = stamp; a.command = command; a.standing = standing;
-    a.x_ref = x_ref; a.foot = foot; a.contact = contact; a.pcom = pcom; a.landing = landing; a.landing_yaw = landing_yaw;
-    for (int i = 0; i < 3; ++i) a.com_target[i] = gait->com_target[i];
-    a.hip_offset_y = gait->hip_offset_y; a.dt = h->cfg.dt;
-    a.N = h->cfg.horizon; a.period = gait->period_steps; a.ds = gait->double_support_steps;
-    a.B = (long long)B;
-    ta.pose = pose; ta.pose_log = pose_log; ta.lead_max = trk->lead_max; ta.yaw_lead_max = trk->yaw_lead_max;
-    HIP_TRY(h, srbdqp::launch_mpc_inputs_tracked(ta, h->live_nstar != 0, st));
-    h->kname = "mpc_inputs_tracked_f64";
+// ---- the step before the QP: one argument record, one check, one launch, one device path, one host path for the six srbdqp_mpc_inputs* entry points ----
+// the flavours of an inputs call (kSteered, kTracked) and of a roll-out (all three).  kTracked: beside kSteered, the inputs call is the tracked one (section 21)
+enum : unsigned { kObserved = 1u, kSteered = 2u, kTracked = 4u };
+
+// the arguments of an inputs call, as its entry point got them: device addresses, or the caller's host arrays (mpc_inputs_host).  What a flavour does not
+// read stands last and stays null
+struct InputsArgs {
+    unsigned flavour;                  // 0: srbdqp_mpc_inputs_*; kSteered: ..._steered_*; kSteered | kTracked: ..._tracked_*
+    const char* fn;                    // the call, for error texts
+    int64_t B;
+    const double *x0, *feet, *stamp;
+    const double* vel;                 // v_ref [B][2]; steered: command [B][3]
+    const uint8_t* standing; const srbdqp_gait* gait;
+    double *x_ref, *foot; uint8_t* contact; double *pcom, *landing;
+    double* landing_yaw;               // written by a steered call; null otherwise
+    const srbdqp_track_settings* trk; double *pose, *pose_log;    // read in a tracked call only; pose_log: the row of a roll-out's log, or null
+};
+
+// what MpcInputsArgs and SteerInputsArgs share, under the same names
+template <class A>
+void inputs_fill(A& a, const srbdqp_handle* h, const InputsArgs& c) {
+    std::memset(&a, 0, sizeof(a));
+    a.x0 = c.x0; a.feet = c.feet; a.stamp = c.stamp; a.standing = c.standing;
+    a.x_ref = c.x_ref; a.foot = c.foot; a.contact = c.contact; a.pcom = c.pcom; a.landing = c.landing;
+    for (int i = 0; i < 3; ++i) a.com_target[i] = c.gait->com_target[i];
+    a.hip_offset_y = c.gait->hip_offset_y; a.dt = h->cfg.dt;
+    a.N = h->cfg.horizon; a.period = c.gait->period_steps; a.ds = c.gait->double_support_steps;
+    a.B = (long long)c.B;
+}
+
+// one launch of the inputs; the arguments have been checked
+int mpc_inputs_launch(srbdqp_handle* h, const InputsArgs& c, hipStream_t st) {
+    if (c.flavour & kSteered) {        // from command [B][3]: the commanded kernel of the second code object, tracked with the pose as its second argument
+        const bool tracked = c.flavour & kTracked;
+        srbdqp::SteerInputsArgs a;
+        inputs_fill(a, h, c);
+        a.command = c.vel; a.landing_yaw = c.landing_yaw;
+        const srbdqp::TrackPose tp = tracked ? srbdqp::TrackPose{c.pose, c.pose_log, c.trk->lead_max, c.trk->yaw_lead_max} : srbdqp::TrackPose{};
+        HIP_TRY(h, srbdqp::launch_mpc_inputs_commanded(a, tracked ? &tp : nullptr, h->live_nstar != 0, st));
+        h->kname = tracked ? "mpc_inputs_tracked_f64" : "mpc_inputs_steered_f64";
+        return SRBDQP_OK;
+    }
+    srbdqp::MpcInputsArgs a;           // from v_ref [B][2]: the kernel of this code object
+    inputs_fill(a, h, c);
+    a.v_ref = c.vel;
+    const long long tiles = ((long long)c.B + 31) / 32;                 // one tile of 32 robots per workgroup pass
+    const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
+    int rc = SRBDQP_OK;
+    if (h->live_nstar) hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<0>, grid, dim3(256), 0, st, a);   // (a live horizon: a.N at run time)
+    else rc = with_horizon(h, [&](auto n) -> int {
+        hipLaunchKernelGGL(srbdqp::srbdqp_mpc_inputs_kernel<decltype(n)::value>, grid, dim3(256), 0, st, a);
+        return SRBDQP_OK;
+    });
+    if (rc != SRBDQP_OK) return rc;
+    HIP_TRY(h, hipGetLastError());
+    h->kname = "mpc_inputs_f64";
     return SRBDQP_OK;
 }
 
-// host: the call comes from mpc_inputs_tracked_host behind its staging, which has made track_check's decisions on the caller's arrays already
-int mpc_inputs_tracked_device(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command, const uint8_t* standing,
-                              const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, double* landing_yaw,
-                              const srbdqp_track_settings* trk, double* pose, bool host, void* stream) {
-    if (!host) if (const int rc = track_check(h, "srbdqp_mpc_inputs_tracked", B, trk, pose, nullptr, 1, false)) return rc;
-    if (const int rc = mpc_inputs_check(h, B, true, x0, feet, stamp, command, x_ref, foot, contact, pcom)) return rc;
-    if (const char* why = gait_fault(gait)) { h->err = std::string("invalid srbdqp_gait ") + why; return SRBDQP_E_INVALID; }
-    if (B == 0) return SRBDQP_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
-    return mpc_inputs_tracked_launch(h, B, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw, trk, pose, nullptr, st);
+// where an inputs call stands: on device addresses, on the caller's host arrays, or on device addresses behind mpc_inputs_host's staging
+enum class InputsFrom { Device, Host, Staged };
+
+// May this handle run this inputs call?  In order:
+//  * the command's own rules (tracked: the pose's and the settings' too), which need no handle and come first; on host arrays every entry must be finite.
+//    Behind the staging they have been decided on the caller's arrays already;
+//  * the arrays, and in a steered call B <= 2^31 - 1;
+//  * the gait -- which the v_ref host form leaves to the device form behind its staging, as it always has: B = 0 is OK with any gait there
+int mpc_inputs_check(srbdqp_handle* h, const InputsArgs& c, InputsFrom from) {
+    const bool steered = c.flavour & kSteered, host = from == InputsFrom::Host;
+    if (c.flavour & kTracked) {
+        if (from != InputsFrom::Staged) if (const int rc = track_check(h, c.fn, c.B, c.trk, c.pose, c.vel, 1, host)) return rc;
+    } else if (steered && host && c.B > 0 && c.B <= 0x7fffffffLL && c.vel) {
+        const long long i = steer_non_finite(c.vel, (size_t)c.B * 3);
+        if (i >= 0) return steer_refuse(h, std::string(c.fn) + ": the command of robot " + std::to_string(i / 3) + " is not finite (component " + std::to_string(i % 3) + " of vx, vy, wz)");
+    }
+    if (const int rc = arrays_check(h, c.B >= 0 && !(steered && c.B > 0x7fffffffLL), c.B,
+                                    !c.x0 || !c.feet || !c.stamp || !c.vel || !c.x_ref || !c.foot || !c.contact || !c.pcom)) return rc;
+    if (const char* why = (steered || !host) ? gait_fault(c.gait) : nullptr) { h->err = std::string("invalid srbdqp_gait ") + why; return SRBDQP_E_INVALID; }
+    return SRBDQP_OK;
 }
 
-int mpc_inputs_tracked_host(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command, const uint8_t* standing,
-                            const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, double* landing_yaw,
-                            const srbdqp_track_settings* trk, double* pose) {
-    // (pose and command are the caller's host arrays: they are read before the handle is)
-    if (const int rc = track_check(h, "srbdqp_mpc_inputs_tracked", B, trk, pose, command, 1, true)) return rc;
-    if (const int rc = mpc_inputs_check(h, B, true, x0, feet, stamp, command, x_ref, foot, contact, pcom)) return rc;
-    if (const char* why = gait_fault(gait)) { h->err = std::string("invalid srbdqp_gait ") + why; return SRBDQP_E_INVALID; }
-    if (B == 0) return SRBDQP_OK;
+int mpc_inputs_device(srbdqp_handle* h, const InputsArgs& c, InputsFrom from, void* stream) {
+    if (const int rc = mpc_inputs_check(h, c, from)) return rc;
+    if (c.B == 0) return SRBDQP_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
-    double *dx0, *dfe, *dst, *dv, *dxr, *dft, *dpc, *dlp, *dly, *dpo;
-    uint8_t *dsd, *dct;
+    return mpc_inputs_launch(h, c, stream ? reinterpret_cast<hipStream_t>(stream) : h->stream);
+}
+
+// the inputs on the caller's host arrays: what is present is staged around the device form
+int mpc_inputs_host(srbdqp_handle* h, const InputsArgs& c) {
+    if (const int rc = mpc_inputs_check(h, c, InputsFrom::Host)) return rc;
+    if (c.B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)c.B, N = (size_t)h->cfg.horizon;
+    InputsArgs d = c;   // the same call on device addresses
     return host_call(h, [&](HostIo& io) {
-        dx0 = io.in<double>(x0, b * 13 * 8); dfe = io.in<double>(feet, b * 12 * 8); dst = io.in<double>(stamp, b * 8); dv = io.in<double>(command, b * 3 * 8);
-        dsd = io.in<uint8_t>(standing, b);
-        dxr = io.out<double>(x_ref, b * N * 13 * 8); dft = io.out<double>(foot, b * N * 12 * 8); dct = io.out<uint8_t>(contact, b * N * 4);
-        dpc = io.out<double>(pcom, b * N * 3 * 8); dlp = io.out<double>(landing, b * 3 * 8); dly = io.out<double>(landing_yaw, b * 8);
-        dpo = io.add<double>(pose, pose, b * 3 * 8, false);
-    }, [&](hipStream_t st) { return mpc_inputs_tracked_device(h, B, dx0, dfe, dst, dv, dsd, gait, dxr, dft, dct, dpc, dlp, dly, trk, dpo, true, st); });
+        d.x0 = io.in<double>(c.x0, b * 13 * 8); d.feet = io.in<double>(c.feet, b * 12 * 8); d.stamp = io.in<double>(c.stamp, b * 8);
+        d.vel = io.in<double>(c.vel, b * ((c.flavour & kSteered) ? 3 : 2) * 8); d.standing = io.in<uint8_t>(c.standing, b);
+        d.x_ref = io.out<double>(c.x_ref, b * N * 13 * 8); d.foot = io.out<double>(c.foot, b * N * 12 * 8); d.contact = io.out<uint8_t>(c.contact, b * N * 4);
+        d.pcom = io.out<double>(c.pcom, b * N * 3 * 8); d.landing = io.out<double>(c.landing, b * 3 * 8); d.landing_yaw = io.out<double>(c.landing_yaw, b * 8);
+        if (c.flavour & kTracked) d.pose = io.add<double>(c.pose, c.pose, b * 3 * 8, false);
+    }, [&](hipStream_t st) { return mpc_inputs_device(h, d, InputsFrom::Staged, st); });
 }
 
 // ---- the K-step loop: one argument record, one check, one loop, one host path for the six srbdqp_fleet_rollout_* entry points ----
-// what a roll-out does beside mpc_inputs -> solve -> fleet_advance: an observer behind every plant step (section 19), steered inputs and footholds (section 20).
-// (The ground is the handle's: a terrain set makes any of them a terrain roll-out, section 18)
-enum : unsigned { kObserved = 1u, kSteered = 2u, kTracked = 4u };   // kTracked: a steered roll-out whose inputs call is the tracked one (section 21)
+// what a roll-out does beside mpc_inputs -> solve -> fleet_advance (the flavour bits above): an observer behind every plant step (section 19), steered inputs
+// and footholds (section 20).  (The ground is the handle's: a terrain set makes any of them a terrain roll-out, section 18)
 
 // the arguments of a roll-out, as its entry point got them: device addresses, or the caller's host arrays (fleet_rollout_host)
 struct RolloutArgs {
@@ -3278,13 +3247,11 @@ int fleet_rollout_run(srbdqp_handle* h, const RolloutArgs& a, void* stream) {
         const size_t k = (size_t)t;
         // steered: row t of a schedule, or the one command held; the inputs also say how the next foot lands turned (section 20)
         // tracked: the references come from the pose the caller carries, which the inputs kernel bounds, advances and logs itself (section 21)
-        if (const int rc = a.pose    ? mpc_inputs_tracked_launch(h, B, a.x, a.feet, a.stamp, a.command + (a.command_steps == 1 ? 0 : k * b * 3), a.standing, &a.cfg->gait,
-                                                                 f.x_ref, f.foot, f.contact, f.pcom, f.landing, f.landing_yaw, a.trk, a.pose,
-                                                                 a.pose_log ? a.pose_log + k * b * 3 : nullptr, st)
-                         : a.command ? mpc_inputs_steered_launch(h, B, a.x, a.feet, a.stamp, a.command + (a.command_steps == 1 ? 0 : k * b * 3), a.standing, &a.cfg->gait,
-                                                                 f.x_ref, f.foot, f.contact, f.pcom, f.landing, f.landing_yaw, st)
-                                     : mpc_inputs_launch(h, B, a.x, a.feet, a.stamp, a.v_ref, a.standing, &a.cfg->gait, f.x_ref, f.foot, f.contact, f.pcom, f.landing, st))
-            return rc;
+        const InputsArgs in{a.flavour & (kSteered | kTracked), a.fn, B, a.x, a.feet, a.stamp,
+                            a.command ? a.command + (a.command_steps == 1 ? 0 : k * b * 3) : a.v_ref, a.standing, &a.cfg->gait,
+                            f.x_ref, f.foot, f.contact, f.pcom, f.landing, a.command ? f.landing_yaw : nullptr,
+                            a.trk, a.pose, a.pose_log ? a.pose_log + k * b * 3 : nullptr};
+        if (const int rc = mpc_inputs_launch(h, in, st)) return rc;
         // the ground under the footholds: the normals of this step's QPs and the height reference
         if (terrain) if (const int rc = terrain_inputs_launch(h, B, a.feet, f.x_ref, f.normals, st)) return rc;
         // the solve a device-buffer call makes (device_call), on a terrain with those normals as the normals of THIS call, observed with the wrench buffer as the wrench
@@ -3374,25 +3341,26 @@ int srbdqp_fleet_advance_steered_f64(srbdqp_handle* h, int64_t B, double* x, dou
 int srbdqp_mpc_inputs_device_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp,
                                  const double* v_ref, const uint8_t* standing, const srbdqp_gait* gait,
                                  double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing, void* stream) {
-    return mpc_inputs_device(h, B, false, x0, feet, stamp, v_ref, standing, gait, x_ref, foot, contact, pcom, landing, nullptr, stream);
+    return mpc_inputs_device(h, {0, "srbdqp_mpc_inputs", B, x0, feet, stamp, v_ref, standing, gait, x_ref, foot, contact, pcom, landing}, InputsFrom::Device, stream);
 }
 
 int srbdqp_mpc_inputs_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp,
                           const double* v_ref, const uint8_t* standing, const srbdqp_gait* gait,
                           double* x_ref, double* foot, uint8_t* contact, double* pcom, double* landing) {
-    return mpc_inputs_host(h, B, false, x0, feet, stamp, v_ref, standing, gait, x_ref, foot, contact, pcom, landing, nullptr);
+    return mpc_inputs_host(h, {0, "srbdqp_mpc_inputs", B, x0, feet, stamp, v_ref, standing, gait, x_ref, foot, contact, pcom, landing});
 }
 
 int srbdqp_mpc_inputs_steered_device_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
                                          const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
                                          double* landing, double* landing_yaw, void* stream) {
-    return mpc_inputs_device(h, B, true, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw, stream);
+    return mpc_inputs_device(h, {kSteered, "srbdqp_mpc_inputs_steered", B, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw},
+                             InputsFrom::Device, stream);
 }
 
 int srbdqp_mpc_inputs_steered_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
                                   const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
                                   double* landing, double* landing_yaw) {
-    return mpc_inputs_host(h, B, true, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw);
+    return mpc_inputs_host(h, {kSteered, "srbdqp_mpc_inputs_steered", B, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw});
 }
 
 // ---- a fleet that follows its path (include/srbdqp_cascade.h) ----
@@ -3407,13 +3375,15 @@ int srbdqp_track_default_settings(srbdqp_track_settings* s) {
 int srbdqp_mpc_inputs_tracked_device_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
                                          const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
                                          double* landing, double* landing_yaw, const srbdqp_track_settings* trk, double* pose, void* stream) {
-    return mpc_inputs_tracked_device(h, B, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw, trk, pose, false, stream);
+    return mpc_inputs_device(h, {kSteered | kTracked, "srbdqp_mpc_inputs_tracked", B, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing,
+                                 landing_yaw, trk, pose}, InputsFrom::Device, stream);
 }
 
 int srbdqp_mpc_inputs_tracked_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
                                   const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
                                   double* landing, double* landing_yaw, const srbdqp_track_settings* trk, double* pose) {
-    return mpc_inputs_tracked_host(h, B, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing, landing_yaw, trk, pose);
+    return mpc_inputs_host(h, {kSteered | kTracked, "srbdqp_mpc_inputs_tracked", B, x0, feet, stamp, command, standing, gait, x_ref, foot, contact, pcom, landing,
+                               landing_yaw, trk, pose});
 }
 
 // ---- the momentum observer (include/srbdqp_cascade.h) ----

@@ -3,12 +3,14 @@
 // the landing point's hip offset turns with the heading at mid-swing, psi_L, and the plant step (srbdqp_fleet.hpp) turns heel and toe by the same psi_L.
 //
 // steer_rotate, steer_yaw, steer_table and steer_touchdown are __host__ __device__ and need nothing of HIP: a host compiler builds them from this header alone
-// (tests/test_steer_cpu.py does, against tests/steer_twin.py).  The kernel below them is a template so that it is emitted only where it is instantiated: in
-// srbdqp_wrench_lat_ew.hip, the library's second code object, as the fleet's kernels are; srbdqp.hip sees SteerInputsArgs and the launcher.
+// (tests/test_steer_cpu.py does, against tests/steer_twin.py).  The kernel below them, srbdqp_mpc_inputs_commanded_kernel, is a template so that it is emitted
+// only where it is instantiated: in srbdqp_wrench_lat_ew.hip, the library's second code object, as the fleet's kernels are; srbdqp.hip sees SteerInputsArgs,
+// TrackPose and the launcher.
 //
 // A fleet that follows its path (srbdqp_mpc_inputs_tracked_*) takes the same references from a pose carried from step to step in place
-// of the measured state: track_bound and track_advance beside steer_table (tests/test_track_cpu.py builds them alone, against tests/track_twin.py), and a
-// kernel of its own behind the steered one, which keeps its text.
+// of the measured state: track_bound and track_advance beside steer_table (tests/test_track_cpu.py builds them alone, against tests/track_twin.py).  Its
+// kernel is the same template with a TrackPose as a second argument: one text for the staging, the gait phase, the element loops and the landing point, and
+// `if constexpr` around what a pose adds.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -116,32 +118,45 @@ struct SteerInputsArgs {
     long long B;
 };
 
-// the steered call's arguments and what a tracked call adds to them
-struct TrackInputsArgs {
-    SteerInputsArgs s;
+// what a tracked call adds to the steered call's arguments: the kernel's second argument
+struct TrackPose {
     double* pose;            // [B][3]  (qx, qy, th), in/out
     double* pose_log;        // [B][3] or null: a second copy of the pose written (a roll-out's pose_log[t])
     double lead_max, yaw_lead_max;
 };
 
 #if defined(__HIPCC__)
-// the launch of srbdqp_mpc_inputs_steered_kernel on st (srbdqp_wrench_lat_ew.hip); live: a.N at run time (SRBDQP_FLAG_ANY_HORIZON)
-hipError_t launch_mpc_inputs_steered(const SteerInputsArgs& a, bool live, hipStream_t st);
-// ... and of srbdqp_mpc_inputs_tracked_kernel, below
-hipError_t launch_mpc_inputs_tracked(const TrackInputsArgs& a, bool live, hipStream_t st);
+// the launch of srbdqp_mpc_inputs_commanded_kernel on st (srbdqp_wrench_lat_ew.hip); track null: the steered instantiation; live: a.N at run time
+// (SRBDQP_FLAG_ANY_HORIZON)
+hipError_t launch_mpc_inputs_commanded(const SteerInputsArgs& a, const TrackPose* track, bool live, hipStream_t st);
 
 // srbdqp_mpc_inputs_kernel's tiling (srbdqp_cascade.hpp): a workgroup takes tiles of 32 consecutive robots, their 13 + 12 + 3 input doubles each staged in LDS
 // with coalesced loads, the tile's outputs written element by element, 512 contiguous bytes per store instruction of a wave.  Between the two, the tile's
-// reference table (steer_table's entries): a thread per (robot, k) takes the two sines and cosines of its entry -- the heading at step k and at k + 1/2 --, then
+// reference table (steer_table's entries): a thread per (robot, k) takes the sines and cosines of its entry -- the heading at step k and at k + 1/2 --, then
 // a thread per (robot, axis) sums the N increments in order.  The element loops read the table and take no sine.
-template <int NH>   // the horizon as a compile-time constant (NH = 0: a.N at run time)
-__global__ __launch_bounds__(256) void srbdqp_mpc_inputs_steered_kernel(SteerInputsArgs a) {
+//
+// TRACK empty: the steered inputs.  One table, from the measured state: p_k and v_w(psi0 + wz k dt); a robot whose command has no planar part is referred to
+// com_target.  Four [32][25] arrays, 32 KB of LDS with the staged inputs, four workgroups a CU.
+//
+// TRACK = TrackPose: the tracked inputs, with two tables in place of one.  The references come from the tile's poses, bounded by
+// track_bound before anything reads them: q_k and v_w(th + wz k dt), moving or not.  What belongs to where the robot IS comes from the measured state as in the
+// steered form, bit for bit: p_k for pcom, v_w(psi0) for the landing point.  A thread per (robot, k) takes the three sines and cosines of its entry, a thread
+// per (robot, table, axis) sums the N increments in order, and a thread per robot moves its pose on (track_advance) and writes it, to pose and -- in a
+// roll-out -- to the step's row of pose_log.  Six [32][25] arrays: 47 KB of LDS, three workgroups a CU.  The steered form neither holds nor
+// reads what is the tracked form's alone (sq, sqx, sqy, sv0): its 32 KB are what let a fourth workgroup onto the CU.
+template <int NH, class... TRACK>   // NH: the horizon as a compile-time constant (NH = 0: a.N at run time)
+__global__ __launch_bounds__(256) void srbdqp_mpc_inputs_commanded_kernel(SteerInputsArgs a, TRACK... track) {
 #pragma clang fp contract(off)
-    constexpr int R = 32, K = kSteerSteps;
+    static_assert(sizeof...(TRACK) <= 1 && (std::is_same<TRACK, TrackPose>::value && ...), "at most one TrackPose");
+    constexpr bool TRACKED = sizeof...(TRACK) == 1;
+    constexpr int R = 32, K = kSteerSteps, RT = TRACKED ? R : 1;          // RT: the rows of what only the tracked form holds
     const int N = NH > 0 ? NH : a.N;
-    __shared__ double sx0[R * 13], sft[R * 12], sc[R * 3];
-    __shared__ double spx[R * K], spy[R * K], svx[R * K], svy[R * K];     // p_k and v_w(psi0 + wz k dt), k = 0 ... N
+    __shared__ double sx0[R * 13], sft[R * 12], sc[R * 3], sq[RT * 3];
+    __shared__ double sqx[RT * K], sqy[RT * K], svx[R * K], svy[R * K];   // the pose's q_k; v_w(th + wz k dt) -- steered: th = psi0 --, k = 0 ... N
+    __shared__ double spx[R * K], spy[R * K], sv0[RT * 2];                // the measured state's p_k; tracked: v_w(psi0) beside svx, svy
     __shared__ int sph[R];                                               // phase of step 0 in [0, 2 period), or -1 = standing
+    double* const rx = TRACKED ? sqx : spx;                              // the table the references read: steered, the measured state's own
+    double* const ry = TRACKED ? sqy : spy;
     const int t = threadIdx.x;
     const long long tiles = (a.B + R - 1) / R;
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -149,28 +164,45 @@ __global__ __launch_bounds__(256) void srbdqp_mpc_inputs_steered_kernel(SteerInp
         const int nr = (int)((a.B - b0 < R) ? (a.B - b0) : R);
         for (int i = t; i < nr * 13; i += 256) sx0[i] = a.x0[b0 * 13 + i];
         for (int i = t; i < nr * 12; i += 256) sft[i] = a.feet[b0 * 12 + i];
-        for (int i = t; i < nr * 3; i += 256) sc[i] = a.command[b0 * 3 + i];
+        for (int i = t; i < nr * 3; i += 256) {
+            sc[i] = a.command[b0 * 3 + i];
+            if constexpr (TRACKED) sq[i] = (track, ...).pose[b0 * 3 + i];
+        }
         if (t < nr) {
             const bool stand = a.standing && a.standing[b0 + t];
             sph[t] = stand ? -1 : gait_phase0(a.stamp[b0 + t], a.dt, a.period);
         }
         __syncthreads();
-        for (int e = t; e < nr * (N + 1); e += 256) {                    // the table's sines and cosines: entry (r, k)
+        if constexpr (TRACKED) {
+            const TrackPose& tp = (track, ...);
+            if (t < nr) track_bound(sq[3 * t], sq[3 * t + 1], sq[3 * t + 2], sx0[13 * t + 3], sx0[13 * t + 4], sx0[13 * t + 2], tp.lead_max, tp.yaw_lead_max);
+            __syncthreads();
+        }
+        for (int e = t; e < nr * (N + 1); e += 256) {                    // the tables' sines and cosines: entry (r, k)
             const int r = e / (N + 1), k = e - (N + 1) * r;
-            const double psi0 = sx0[13 * r + 2], vx = sc[3 * r], vy = sc[3 * r + 1], wz = sc[3 * r + 2];
+            const double psi0 = sx0[13 * r + 2], th = TRACKED ? sq[3 * r + 2] : psi0, vx = sc[3 * r], vy = sc[3 * r + 1], wz = sc[3 * r + 2];
             double wx, wy;
-            steer_rotate(steer_yaw(psi0, wz, (double)k, a.dt), vx, vy, wx, wy);
+            steer_rotate(steer_yaw(th, wz, (double)k, a.dt), vx, vy, wx, wy);
             svx[K * r + k] = wx; svy[K * r + k] = wy;
-            if (k < N) {                                                 // the increment of step k, where p_{k+1} will stand
+            if constexpr (TRACKED) if (k == 0) {
+                steer_rotate(steer_yaw(psi0, wz, 0.0, a.dt), vx, vy, wx, wy);
+                sv0[2 * r] = wx; sv0[2 * r + 1] = wy;
+            }
+            if (k < N) {                                                 // the increments of step k, where q_{k+1} and p_{k+1} will stand
+                if constexpr (TRACKED) {
+                    steer_rotate(steer_yaw(th, wz, (double)k + 0.5, a.dt), vx, vy, wx, wy);
+                    sqx[K * r + k + 1] = wx * a.dt; sqy[K * r + k + 1] = wy * a.dt;
+                }
                 steer_rotate(steer_yaw(psi0, wz, (double)k + 0.5, a.dt), vx, vy, wx, wy);
                 spx[K * r + k + 1] = wx * a.dt; spy[K * r + k + 1] = wy * a.dt;
             }
         }
         __syncthreads();
-        if (t < nr * 2) {                                                // the serial sums, one (robot, axis) each
-            const int r = t >> 1, c = t & 1;
-            double* p = (c ? spy : spx) + K * r;
-            double acc = sx0[13 * r + 3 + c];
+        if (t < nr * (TRACKED ? 4 : 2)) {                                // the serial sums, one (robot, [table,] axis) each
+            const int r = t >> (TRACKED ? 2 : 1), c = t & 1;
+            const bool measured = !TRACKED || ((t >> 1) & 1);
+            double* p = (measured ? (c ? spy : spx) : (c ? sqy : sqx)) + K * r;
+            double acc = measured ? sx0[13 * r + 3 + c] : sq[3 * r + c];
             p[0] = acc;
             for (int k = 1; k <= N; ++k) { acc = acc + p[k]; p[k] = acc; }
         }
@@ -181,122 +213,16 @@ __global__ __launch_bounds__(256) void srbdqp_mpc_inputs_steered_kernel(SteerInp
             const int row = e / 13, c = e - 13 * row, r = row / N, k = row - N * r;
             const double* x0 = sx0 + 13 * r;
             const double vx = sc[3 * r], vy = sc[3 * r + 1], wz = sc[3 * r + 2];
-            const bool moving = (vx != 0.0) || (vy != 0.0);
+            const bool moving = TRACKED || (vx != 0.0) || (vy != 0.0);    // tracked: from the pose, moving or not
             double v = 0.0;
-            if (c == 2) v = steer_yaw(x0[2], wz, (double)(k + 1), a.dt);
-            else if (c == 3) v = moving ? spx[K * r + k + 1] : a.com_target[0];
-            else if (c == 4) v = moving ? spy[K * r + k + 1] : a.com_target[1];
+            if (c == 2) v = steer_yaw(TRACKED ? sq[3 * r + 2] : x0[2], wz, (double)(k + 1), a.dt);
+            else if (c == 3) v = moving ? rx[K * r + k + 1] : a.com_target[0];
+            else if (c == 4) v = moving ? ry[K * r + k + 1] : a.com_target[1];
             else if (c == 5) v = a.com_target[2];
             else if (c == 8) v = wz;
             else if (c == 9) v = svx[K * r + k + 1];
             else if (c == 10) v = svy[K * r + k + 1];
             else if (c == 12) v = x0[12];
-            xr[e] = v;
-        }
-        double* fo = a.foot + b0 * (N * 12);
-        for (int e = t; e < nr * N * 12; e += 256) {                     // foot[r][k][c]: the current contact points, repeated
-            const int row = e / 12, c = e - 12 * row, r = row / N;
-            fo[e] = sft[12 * r + c];
-        }
-        double* pc = a.pcom + b0 * (N * 3);
-        for (int e = t; e < nr * N * 3; e += 256) {                      // pcom[r][k] = (p_k, the measured height)
-            const int row = e / 3, c = e - 3 * row, r = row / N, k = row - N * r;
-            pc[e] = (c == 0) ? spx[K * r + k] : (c == 1) ? spy[K * r + k] : sx0[13 * r + 5];
-        }
-        uint32_t* cw = reinterpret_cast<uint32_t*>(a.contact) + b0 * N;  // 4 flags per step = one aligned word
-        for (int row = t; row < nr * N; row += 256) {
-            const int r = row / N, k = row - N * r;
-            bool cl, cr;
-            flags(r, k, cl, cr);
-            cw[row] = (cl ? 0x00000101u : 0u) | (cr ? 0x01010000u : 0u);
-        }
-        if ((a.landing || a.landing_yaw) && t < nr) {                    // the landing point of the foot that is (or goes next) in the air, and its heading
-            const double* x0 = sx0 + 13 * t;
-            bool cl, cr;
-            flags(t, 0, cl, cr);
-            const double half_T = 0.5 * ((double)a.period * a.dt);
-            const double psi_l = x0[2] + sc[3 * t + 2] * half_T;
-            if (a.landing) {
-                double lx, ly;
-                steer_landing(x0, psi_l, cl ? -1.0 : 1.0, a.hip_offset_y, half_T, svx[K * t], svy[K * t], lx, ly);
-                a.landing[(b0 + t) * 3] = lx; a.landing[(b0 + t) * 3 + 1] = ly; a.landing[(b0 + t) * 3 + 2] = 0.0;
-            }
-            if (a.landing_yaw) a.landing_yaw[b0 + t] = psi_l;
-        }
-        __syncthreads();
-    }
-}
-
-// The tracked inputs (srbdqp_mpc_inputs_tracked_*): the steered kernel's tiling and element loops, with two tables in place of one.  The
-// references come from the tile's poses, bounded by track_bound before anything reads them: q_k and v_w(th + wz k dt).  What belongs to where the robot IS comes
-// from the measured state as in the steered kernel, bit for bit: p_k for pcom, v_w(psi0) for the landing point.  A thread per (robot, k) takes the three sines
-// and cosines of its entry, a thread per (robot, table, axis) sums the N increments in order, and a thread per robot moves its pose on (track_advance) and
-// writes it, to pose and -- in a roll-out -- to the step's row of pose_log.  Six [32][25] tables: 47 KB of LDS with the staged inputs.
-template <int NH>   // the horizon as a compile-time constant (NH = 0: a.N at run time)
-__global__ __launch_bounds__(256) void srbdqp_mpc_inputs_tracked_kernel(TrackInputsArgs ta) {
-#pragma clang fp contract(off)
-    constexpr int R = 32, K = kSteerSteps;
-    const SteerInputsArgs& a = ta.s;
-    const int N = NH > 0 ? NH : a.N;
-    __shared__ double sx0[R * 13], sft[R * 12], sc[R * 3], sq[R * 3];
-    __shared__ double sqx[R * K], sqy[R * K], svx[R * K], svy[R * K];     // the pose's q_k and v_w(th + wz k dt), k = 0 ... N
-    __shared__ double spx[R * K], spy[R * K], sv0[R * 2];                 // the measured state's p_k, and v_w(psi0)
-    __shared__ int sph[R];                                               // phase of step 0 in [0, 2 period), or -1 = standing
-    const int t = threadIdx.x;
-    const long long tiles = (a.B + R - 1) / R;
-    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const long long b0 = tile * R;
-        const int nr = (int)((a.B - b0 < R) ? (a.B - b0) : R);
-        for (int i = t; i < nr * 13; i += 256) sx0[i] = a.x0[b0 * 13 + i];
-        for (int i = t; i < nr * 12; i += 256) sft[i] = a.feet[b0 * 12 + i];
-        for (int i = t; i < nr * 3; i += 256) { sc[i] = a.command[b0 * 3 + i]; sq[i] = ta.pose[b0 * 3 + i]; }
-        if (t < nr) {
-            const bool stand = a.standing && a.standing[b0 + t];
-            sph[t] = stand ? -1 : gait_phase0(a.stamp[b0 + t], a.dt, a.period);
-        }
-        __syncthreads();
-        if (t < nr) track_bound(sq[3 * t], sq[3 * t + 1], sq[3 * t + 2], sx0[13 * t + 3], sx0[13 * t + 4], sx0[13 * t + 2], ta.lead_max, ta.yaw_lead_max);
-        __syncthreads();
-        for (int e = t; e < nr * (N + 1); e += 256) {                    // the tables' sines and cosines: entry (r, k)
-            const int r = e / (N + 1), k = e - (N + 1) * r;
-            const double psi0 = sx0[13 * r + 2], th = sq[3 * r + 2], vx = sc[3 * r], vy = sc[3 * r + 1], wz = sc[3 * r + 2];
-            double wx, wy;
-            steer_rotate(steer_yaw(th, wz, (double)k, a.dt), vx, vy, wx, wy);
-            svx[K * r + k] = wx; svy[K * r + k] = wy;
-            if (k == 0) {
-                steer_rotate(steer_yaw(psi0, wz, 0.0, a.dt), vx, vy, wx, wy);
-                sv0[2 * r] = wx; sv0[2 * r + 1] = wy;
-            }
-            if (k < N) {                                                 // the increments of step k, where q_{k+1} and p_{k+1} will stand
-                steer_rotate(steer_yaw(th, wz, (double)k + 0.5, a.dt), vx, vy, wx, wy);
-                sqx[K * r + k + 1] = wx * a.dt; sqy[K * r + k + 1] = wy * a.dt;
-                steer_rotate(steer_yaw(psi0, wz, (double)k + 0.5, a.dt), vx, vy, wx, wy);
-                spx[K * r + k + 1] = wx * a.dt; spy[K * r + k + 1] = wy * a.dt;
-            }
-        }
-        __syncthreads();
-        if (t < nr * 4) {                                                // the serial sums, one (robot, table, axis) each
-            const int r = t >> 2, c = t & 1, measured = (t >> 1) & 1;
-            double* p = (measured ? (c ? spy : spx) : (c ? sqy : sqx)) + K * r;
-            double acc = measured ? sx0[13 * r + 3 + c] : sq[3 * r + c];
-            p[0] = acc;
-            for (int k = 1; k <= N; ++k) { acc = acc + p[k]; p[k] = acc; }
-        }
-        __syncthreads();
-        auto flags = [&](int r, int k, bool& cl, bool& cr) { gait_flags(sph[r], k, a.period, a.ds, cl, cr); };
-        double* xr = a.x_ref + b0 * (N * 13);
-        for (int e = t; e < nr * N * 13; e += 256) {                     // x_ref[r][k][c], reference index k + 1: from the pose, moving or not
-            const int row = e / 13, c = e - 13 * row, r = row / N, k = row - N * r;
-            const double wz = sc[3 * r + 2];
-            double v = 0.0;
-            if (c == 2) v = steer_yaw(sq[3 * r + 2], wz, (double)(k + 1), a.dt);
-            else if (c == 3) v = sqx[K * r + k + 1];
-            else if (c == 4) v = sqy[K * r + k + 1];
-            else if (c == 5) v = a.com_target[2];
-            else if (c == 8) v = wz;
-            else if (c == 9) v = svx[K * r + k + 1];
-            else if (c == 10) v = svy[K * r + k + 1];
-            else if (c == 12) v = sx0[13 * r + 12];
             xr[e] = v;
         }
         double* fo = a.foot + b0 * (N * 12);
@@ -319,23 +245,26 @@ __global__ __launch_bounds__(256) void srbdqp_mpc_inputs_tracked_kernel(TrackInp
         if (t < nr) {
             const double* x0 = sx0 + 13 * t;
             const double wz = sc[3 * t + 2];
-            if (a.landing || a.landing_yaw) {                            // the landing point and its heading: the steered kernel's, from the measured state
-                bool cl, cr;
+            if (a.landing || a.landing_yaw) {                            // the landing point of the foot that is (or goes next) in the air, and its heading:
+                bool cl, cr;                                             // from the measured state in either form
                 flags(t, 0, cl, cr);
                 const double half_T = 0.5 * ((double)a.period * a.dt);
                 const double psi_l = x0[2] + wz * half_T;
                 if (a.landing) {
                     double lx, ly;
-                    steer_landing(x0, psi_l, cl ? -1.0 : 1.0, a.hip_offset_y, half_T, sv0[2 * t], sv0[2 * t + 1], lx, ly);
+                    steer_landing(x0, psi_l, cl ? -1.0 : 1.0, a.hip_offset_y, half_T, TRACKED ? sv0[2 * t] : svx[K * t], TRACKED ? sv0[2 * t + 1] : svy[K * t], lx, ly);
                     a.landing[(b0 + t) * 3] = lx; a.landing[(b0 + t) * 3 + 1] = ly; a.landing[(b0 + t) * 3 + 2] = 0.0;
                 }
                 if (a.landing_yaw) a.landing_yaw[b0 + t] = psi_l;
             }
-            double qx = sq[3 * t], qy = sq[3 * t + 1], th = sq[3 * t + 2];  // the pose behind this control step
-            track_advance(qx, qy, th, sqx[K * t + 1], sqy[K * t + 1], wz, a.dt);
-            double* po = ta.pose + (b0 + t) * 3;
-            po[0] = qx; po[1] = qy; po[2] = th;
-            if (ta.pose_log) { double* pl = ta.pose_log + (b0 + t) * 3; pl[0] = qx; pl[1] = qy; pl[2] = th; }
+            if constexpr (TRACKED) {
+                const TrackPose& tp = (track, ...);
+                double qx = sq[3 * t], qy = sq[3 * t + 1], th = sq[3 * t + 2];  // the pose behind this control step
+                track_advance(qx, qy, th, sqx[K * t + 1], sqy[K * t + 1], wz, a.dt);
+                double* po = tp.pose + (b0 + t) * 3;
+                po[0] = qx; po[1] = qy; po[2] = th;
+                if (tp.pose_log) { double* pl = tp.pose_log + (b0 + t) * 3; pl[0] = qx; pl[1] = qy; pl[2] = th; }
+            }
         }
         __syncthreads();
     }

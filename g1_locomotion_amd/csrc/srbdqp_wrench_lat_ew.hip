@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <utility>
 
 #include "srbdqp.h"
 #include "srbdqp_common.hpp"
@@ -83,25 +84,6 @@ hipError_t launch_fleet_advance(const FleetArgs& a, hipStream_t st, const Terrai
     return hipGetLastError();
 }
 
-// ... the step before the QP of a fleet that steers (srbdqp_steer.hpp): one instantiation per tabulated horizon, and the live one
-hipError_t launch_mpc_inputs_steered(const SteerInputsArgs& a, bool live, hipStream_t st) {
-    const long long tiles = (a.B + 31) / 32;                       // one tile of 32 robots per workgroup pass
-    const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
-    if (a.N < 1 || a.N > kSteerSteps - 1) return hipErrorInvalidValue;   // (the table holds 25 entries a robot)
-    if (live) hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<0>, grid, dim3(256), 0, st, a);
-    else switch (a.N) {
-        case 4: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<4>, grid, dim3(256), 0, st, a); break;
-        case 8: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<8>, grid, dim3(256), 0, st, a); break;
-        case 10: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<10>, grid, dim3(256), 0, st, a); break;
-        case 12: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<12>, grid, dim3(256), 0, st, a); break;
-        case 16: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<16>, grid, dim3(256), 0, st, a); break;
-        case 20: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<20>, grid, dim3(256), 0, st, a); break;
-        case 24: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<24>, grid, dim3(256), 0, st, a); break;
-        default: hipLaunchKernelGGL(srbdqp_mpc_inputs_steered_kernel<0>, grid, dim3(256), 0, st, a); break;
-    }
-    return hipGetLastError();
-}
-
 // ... the momentum observer behind it (srbdqp_observer.hpp): the push a period's forces do not explain, as the external wrench of the next solve
 hipError_t launch_wrench_observer(const ObserverArgs& a, hipStream_t st) {
     const long long tiles = (a.B + kObserverTile - 1) / kObserverTile;   // one tile of 64 robots per workgroup pass
@@ -124,24 +106,23 @@ hipError_t launch_terrain_inputs(const TerrainInputsArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-// ... and the step before the QP of a fleet that follows its path (srbdqp_steer.hpp): the steered launch's grid and horizons.  Behind
-// every other kernel of this code object, which keeps their order
-hipError_t launch_mpc_inputs_tracked(const TrackInputsArgs& a, bool live, hipStream_t st) {
-    const long long tiles = (a.s.B + 31) / 32;                     // one tile of 32 robots per workgroup pass
+// ... and the step before the QP of a fleet that steers or follows its path (srbdqp_steer.hpp; DESIGN.md sections 20, 21), behind every other kernel of this
+// code object, which keeps their order: one instantiation per tabulated horizon and the live one, with track... empty (steered) or one TrackPose (tracked)
+namespace {
+template <int... Ns, class... TRACK>
+hipError_t launch_commanded(std::integer_sequence<int, Ns...>, const SteerInputsArgs& a, bool live, hipStream_t st, const TRACK&... track) {
+    const long long tiles = (a.B + 31) / 32;                       // one tile of 32 robots per workgroup pass
     const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
-    if (a.s.N < 1 || a.s.N > kSteerSteps - 1) return hipErrorInvalidValue;   // (the tables hold 25 entries a robot)
-    if (live) hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<0>, grid, dim3(256), 0, st, a);
-    else switch (a.s.N) {
-        case 4: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<4>, grid, dim3(256), 0, st, a); break;
-        case 8: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<8>, grid, dim3(256), 0, st, a); break;
-        case 10: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<10>, grid, dim3(256), 0, st, a); break;
-        case 12: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<12>, grid, dim3(256), 0, st, a); break;
-        case 16: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<16>, grid, dim3(256), 0, st, a); break;
-        case 20: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<20>, grid, dim3(256), 0, st, a); break;
-        case 24: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<24>, grid, dim3(256), 0, st, a); break;
-        default: hipLaunchKernelGGL(srbdqp_mpc_inputs_tracked_kernel<0>, grid, dim3(256), 0, st, a); break;
-    }
+    if (a.N < 1 || a.N > kSteerSteps - 1) return hipErrorInvalidValue;   // (a table holds 25 entries a robot)
+    auto go = [&](auto n) { hipLaunchKernelGGL((srbdqp_mpc_inputs_commanded_kernel<decltype(n)::value, TRACK...>), grid, dim3(256), 0, st, a, track...); return true; };
+    if (live || !((a.N == Ns && go(std::integral_constant<int, Ns>{})) || ...)) go(std::integral_constant<int, 0>{});   // (a live or untabulated horizon: a.N at run time)
     return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_mpc_inputs_commanded(const SteerInputsArgs& a, const TrackPose* track, bool live, hipStream_t st) {
+    using Tabulated = std::integer_sequence<int, 4, 8, 10, 12, 16, 20, 24>;
+    return track ? launch_commanded(Tabulated{}, a, live, st, *track) : launch_commanded(Tabulated{}, a, live, st);
 }
 
 }  // namespace srbdqp

@@ -468,18 +468,28 @@ class BatchMPC(_Engine):
         x0 (B,13), feet (B,12) or (B,4,3), stamp (B,), v_ref (B,2), standing (B,) flags or None.
         Returns dict(x_ref (B,N,13), foot (B,N,12), contact (B,N,4) uint8, pcom (B,N,3), landing (B,3)) -- the arrays
         solve() / solve_device() take."""
+        return self._mpc_inputs("srbdqp_mpc_inputs_f64", x0, feet, stamp, lambda B: [_c(v_ref, np.float64).reshape(B, 2)], standing,
+                                (period_steps, double_support_steps, com_target, hip_offset_y))
+
+    def _mpc_inputs(self, fn, x0, feet, stamp, vel, standing, gait, track=None):
+        """The host form `fn` of the inputs: the marshalling of x0, feet, stamp and standing, the gait struct and the outputs, once for mpc_inputs(),
+        mpc_inputs_steered() and mpc_inputs_tracked().  vel(B): the call's own arrays as it marshals them, v_ref or command first and behind a command the
+        pose, which goes in and out.  gait: _gait_struct()'s arguments.  track: track_settings()' keywords in a tracked call."""
         x = _c(x0, np.float64).reshape(-1, NX)
         B, N = x.shape[0], self.N
         f = _c(feet, np.float64).reshape(B, NU)
         t = _c(stamp, np.float64).reshape(B)
-        v = _c(v_ref, np.float64).reshape(B, 2)
+        v, *po = vel(B)
         sd = None if standing is None else _c(standing, np.uint8).reshape(B)
-        g = self._gait_struct(period_steps, double_support_steps, com_target, hip_offset_y)
+        g = self._gait_struct(*gait)
+        tail = () if track is None else (C.byref(self.track_settings(**track)), _p(po[0]))
         xr, ft, ct = np.empty((B, N, NX)), np.empty((B, N, NU)), np.empty((B, N, NC), dtype=np.uint8)
-        pc, lp = np.empty((B, N, 3)), np.empty((B, 3))
-        rc = self._lib.srbdqp_mpc_inputs_f64(self._h, B, _p(x), _p(f), _p(t), _p(v), _p(sd), C.byref(g), _p(xr), _p(ft), _p(ct), _p(pc), _p(lp))
+        out = dict(x_ref=xr, foot=ft, contact=ct, pcom=np.empty((B, N, 3)), landing=np.empty((B, 3)))
+        if v.shape[1] == 3:       # under a command: the heading the next foot lands with
+            out["landing_yaw"] = np.empty(B)
+        rc = getattr(self._lib, fn)(self._h, B, _p(x), _p(f), _p(t), _p(v), _p(sd), C.byref(g), *(_p(o) for o in out.values()), *tail)
         self._check(rc)
-        return dict(x_ref=xr, foot=ft, contact=ct, pcom=pc, landing=lp)
+        return dict(out, pose=po[0]) if po else out
 
     def mpc_inputs_device(self, B, x0, feet, stamp, v_ref, com_target, x_ref, foot, contact, pcom, landing=0, standing=0,
                           period_steps=6, double_support_steps=1, hip_offset_y=0.0645, stream=0):
@@ -495,18 +505,8 @@ class BatchMPC(_Engine):
         (srbdqp_mpc_inputs_steered_f64): the references turn with the commanded heading, the landing point's hip offset with the heading
         at mid-swing.  A command that is not finite raises SrbdqpError.
         Returns mpc_inputs()' dict and landing_yaw (B,), the heading the next foot lands with: fleet_advance(landing_yaw=)'s argument."""
-        x = _c(x0, np.float64).reshape(-1, NX)
-        B, N = x.shape[0], self.N
-        f = _c(feet, np.float64).reshape(B, NU)
-        t = _c(stamp, np.float64).reshape(B)
-        c = _as(command, np.float64, (B, 3), "command")
-        sd = None if standing is None else _c(standing, np.uint8).reshape(B)
-        g = self._gait_struct(period_steps, double_support_steps, com_target, hip_offset_y)
-        xr, ft, ct = np.empty((B, N, NX)), np.empty((B, N, NU)), np.empty((B, N, NC), dtype=np.uint8)
-        pc, lp, ly = np.empty((B, N, 3)), np.empty((B, 3)), np.empty(B)
-        rc = self._lib.srbdqp_mpc_inputs_steered_f64(self._h, B, _p(x), _p(f), _p(t), _p(c), _p(sd), C.byref(g), _p(xr), _p(ft), _p(ct), _p(pc), _p(lp), _p(ly))
-        self._check(rc)
-        return dict(x_ref=xr, foot=ft, contact=ct, pcom=pc, landing=lp, landing_yaw=ly)
+        return self._mpc_inputs("srbdqp_mpc_inputs_steered_f64", x0, feet, stamp, lambda B: [_as(command, np.float64, (B, 3), "command")], standing,
+                                (period_steps, double_support_steps, com_target, hip_offset_y))
 
     def mpc_inputs_steered_device(self, B, x0, feet, stamp, command, com_target, x_ref, foot, contact, pcom, landing=0, landing_yaw=0, standing=0,
                                   period_steps=6, double_support_steps=1, hip_offset_y=0.0645, stream=0):
@@ -541,21 +541,9 @@ class BatchMPC(_Engine):
         foot, contact, landing and landing_yaw are mpc_inputs_steered()'s.  track: track_settings()' keywords.  pose is not modified; a pose or a command
         that is not finite raises SrbdqpError.
         Returns mpc_inputs_steered()'s dict and pose (B,3), the pose behind the step: the next call's argument."""
-        x = _c(x0, np.float64).reshape(-1, NX)
-        B, N = x.shape[0], self.N
-        f = _c(feet, np.float64).reshape(B, NU)
-        t = _c(stamp, np.float64).reshape(B)
-        c = _as(command, np.float64, (B, 3), "command")
-        po = np.array(_as(pose, np.float64, (B, 3), "pose"))
-        sd = None if standing is None else _c(standing, np.uint8).reshape(B)
-        g = self._gait_struct(period_steps, double_support_steps, com_target, hip_offset_y)
-        k = self.track_settings(**track)
-        xr, ft, ct = np.empty((B, N, NX)), np.empty((B, N, NU)), np.empty((B, N, NC), dtype=np.uint8)
-        pc, lp, ly = np.empty((B, N, 3)), np.empty((B, 3)), np.empty(B)
-        rc = self._lib.srbdqp_mpc_inputs_tracked_f64(self._h, B, _p(x), _p(f), _p(t), _p(c), _p(sd), C.byref(g), _p(xr), _p(ft), _p(ct), _p(pc), _p(lp), _p(ly),
-                                                     C.byref(k), _p(po))
-        self._check(rc)
-        return dict(x_ref=xr, foot=ft, contact=ct, pcom=pc, landing=lp, landing_yaw=ly, pose=po)
+        return self._mpc_inputs("srbdqp_mpc_inputs_tracked_f64", x0, feet, stamp,
+                                lambda B: [_as(command, np.float64, (B, 3), "command"), np.array(_as(pose, np.float64, (B, 3), "pose"))], standing,
+                                (period_steps, double_support_steps, com_target, hip_offset_y), track)
 
     def mpc_inputs_tracked_device(self, B, x0, feet, stamp, command, pose, com_target, x_ref, foot, contact, pcom, landing=0, landing_yaw=0, standing=0,
                                   period_steps=6, double_support_steps=1, hip_offset_y=0.0645, stream=0, **track):

@@ -1,5 +1,6 @@
 """GPU tests of the second trip through the tile loops of the fleet kernels.  srbdqp_fleet_advance_kernel, srbdqp_wrench_observer_kernel (tiles of 64 robots),
-srbdqp_mpc_inputs_kernel, srbdqp_mpc_inputs_steered_kernel and srbdqp_terrain_inputs_kernel (tiles of 32) all run
+srbdqp_mpc_inputs_kernel, srbdqp_mpc_inputs_commanded_kernel (here its steered instantiation; test_gpu_track.py takes the tracked one on the same trip) and
+srbdqp_terrain_inputs_kernel (tiles of 32) all run
 
     for (tile = blockIdx.x; tile < tiles; tile += gridDim.x)
 

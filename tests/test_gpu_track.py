@@ -468,7 +468,7 @@ def test_free_running_against_the_twin(eng):
 
 
 def test_the_tile_loop_takes_its_second_trip():
-    """test_gpu_tile_loops.py's method on srbdqp_mpc_inputs_tracked_kernel, whose launcher caps the grid at 256 * 32 workgroups: the 77-robot crowd, odd robots
+    """test_gpu_tile_loops.py's method on srbdqp_mpc_inputs_commanded_kernel's tracked instantiation, whose launcher caps the grid at 256 * 32 workgroups: the 77-robot crowd, odd robots
     and all, repeated to 262,189 robots = cap * 32 + 32 + 13 on an engine of horizon 4, robot b being robot b mod 77.  Every output and the pose behind the step
     equal the 77-robot call's gathered by the same index, bit for bit; so does the pose_log row of a one-step roll-out of the large fleet."""
     import torch

@@ -2,10 +2,11 @@
 """Compare the device code of two builds kernel by kernel.
 
     hipcc -O3 --offload-arch=gfx950 -std=c++17 -Iinclude -S --cuda-device-only -o X.s g1_locomotion_amd/csrc/srbdqp.hip
-    tools/compare_isa.py parent.s this.s [--loose REGEX]
+    tools/compare_isa.py parent.s this.s [--loose REGEX] [--rename REGEX=REPLACEMENT]...
 
-Reads the two .s files and nothing else.  Per kernel: the text between `<symbol>:` and `.Lfunc_end` (comments and
-.loc / .file / .cfi lines dropped, `.LBB<n>_` label numbers normalised), the `.amdhsa_*` lines, and the counts of the
+Reads the two .s files and nothing else.  Every --rename is applied to the symbols of both files before kernels are
+matched, so that a renamed kernel can be held against its predecessor.  Per kernel: the text between `<symbol>:` and
+`.Lfunc_end` (comments and .loc / .file / .cfi lines dropped, `.LBB<n>_` label numbers normalised), the `.amdhsa_*` lines, and the counts of the
 instruction classes below.  Kernels whose demangled-or-not symbol matches --loose (default: the general and the
 compact kernel families) may differ in text as long as every `.amdhsa_*` line and every class count is equal;
 every other kernel must be identical.  Exit status 0 when all of that holds."""
@@ -26,8 +27,11 @@ CLASSES = [
 CLASSES = [(n, re.compile(p)) for n, p in CLASSES]
 
 
-def parse(path):
-    text = open(path).read().split("\n")
+def parse(path, renames=()):
+    text = open(path).read()
+    for rx, to in renames:
+        text = re.sub(rx, to, text)
+    text = text.split("\n")
     kernels = {}
     hsa = {}
     names = set()
@@ -89,8 +93,14 @@ def main():
         k = args.index("--loose")
         loose = args[k + 1]
         del args[k:k + 2]
-    ka, ha = parse(args[0])
-    kb, hb = parse(args[1])
+    renames = []
+    while "--rename" in args:
+        k = args.index("--rename")
+        rx, to = args[k + 1].split("=", 1)
+        renames.append((rx, to))
+        del args[k:k + 2]
+    ka, ha = parse(args[0], renames)
+    kb, hb = parse(args[1], renames)
     bad = 0
     if set(ka) != set(kb):
         print("SYMBOLS DIFFER: only in A:", sorted(set(ka) - set(kb)), "only in B:", sorted(set(kb) - set(ka)))
