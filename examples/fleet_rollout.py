@@ -1,7 +1,7 @@
 """256 walking robots under random commands and random pushes for 100 control steps, in one call (BatchMPC.rollout):
 prints the share of the fleet still on its feet and how well it follows the commanded velocity.
 
-    python examples/fleet_rollout.py [--robots 256] [--steps 100] [--seed 0] [--slope 0.2] [--observer] [--yaw-rate 0.5] [--track]
+    python examples/fleet_rollout.py [--robots 256] [--steps 100] [--seed 0] [--slope 0.2] [--observer] [--yaw-rate 0.5] [--track] [--preview]
 
 --slope s: the same fleet on the plane z = s x (BatchMPC.set_terrain): the friction pyramids tilt with the ground, a foot lands on it,
 and "fallen" is the height over it.
@@ -34,6 +34,7 @@ def main():
     ap.add_argument("--observer", action="store_true")
     ap.add_argument("--yaw-rate", type=float, default=0.0)
     ap.add_argument("--track", action="store_true")
+    ap.add_argument("--preview", action="store_true", help="with --yaw-rate or --track: the solves read the footholds previewed along the horizon (rollout(preview=True))")
     a = ap.parse_args()
     if a.observer and a.slope:
         ap.error("--observer is flat ground")
@@ -41,8 +42,9 @@ def main():
         ap.error("--observer and --yaw-rate: one at a time here (BatchMPC.rollout takes both)")
     if a.track and a.observer:
         ap.error("--observer and --track: one at a time here (BatchMPC.rollout takes both)")
-    if a.track and not a.yaw_rate:
+    if (a.track or a.preview) and not a.yaw_rate:
         a.yaw_rate = 0.3
+    pv = dict(preview=True) if a.preview else {}
     from g1_locomotion_amd import BatchMPC
     rng = np.random.default_rng(a.seed)
     B, T, dt = a.robots, a.steps, 0.04
@@ -78,15 +80,15 @@ def main():
             command = np.stack([np.abs(v_ref[:, 0]), np.zeros(B), np.full(B, a.yaw_rate)], axis=1)
             if a.track:
                 # where the commands lead: the pose of a tracked roll-out whose bounds never engage is the commands integrated from the start
-                r = eng.rollout(x0, feet, stamp, None, T, COM, command=command, track=True)
+                r = eng.rollout(x0, feet, stamp, None, T, COM, command=command, track=True, **pv)
                 goal = eng.rollout(x0, feet, stamp, None, T, COM, command=command, track=dict(lead_max=1e9, yaw_lead_max=1e9))["pose"]
-                for name, q in (("steered", eng.rollout(x0, feet, stamp, None, T, COM, command=command)), ("tracked", r)):
+                for name, q in (("steered", eng.rollout(x0, feet, stamp, None, T, COM, command=command, **pv)), ("tracked", r)):
                     up = q["alive"] != 0
                     off, yaw = np.hypot(*(q["x"][-1, up, 3:5] - goal[up, 0:2]).T), np.abs(q["x"][-1, up, 2] - goal[up, 2])
                     print(f"{name}: {up.mean():.1%} alive, {off.mean():.3f} m from the commanded path on average ({off.max():.3f} m at most) after "
                           f"{np.abs(command[up, 0]).mean() * T * dt:.2f} m of it, heading {yaw.mean():.3f} rad off ({yaw.max():.3f} rad at most)")
             else:
-                r = eng.rollout(x0, feet, stamp, None, T, COM, push=push, command=command)
+                r = eng.rollout(x0, feet, stamp, None, T, COM, push=push, command=command, **pv)
         else:
             r = eng.rollout(x0, feet, stamp, v_ref, T, COM, push=push)
     r["x"][:, :, 5] -= ground(r["x"][:, :, 3:5])                         # heights below are over the ground

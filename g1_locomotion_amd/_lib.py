@@ -53,6 +53,11 @@ class ObserverSettings(C.Structure):
                 ("torque_max", C.c_double), ("force_max", C.c_double)]
 
 
+class PreviewSettings(C.Structure):
+    """srbdqp_preview_settings (include/srbdqp_cascade.h): the foot a previewed call puts down along the horizon."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved0", C.c_int32), ("foot_half_length", C.c_double)]
+
+
 class TrackSettings(C.Structure):
     """srbdqp_track_settings (include/srbdqp_cascade.h): how far a tracked robot's reference pose may lead the measured state."""
     _fields_ = [("struct_size", C.c_int32), ("reserved0", C.c_int32), ("lead_max", C.c_double), ("yaw_lead_max", C.c_double)]
@@ -193,6 +198,9 @@ _ROLLOUT_STEER = _ROLLOUT_OBS[:7] + [_i32] + _ROLLOUT_OBS[7:]             # ...,
 _TRK = C.POINTER(TrackSettings)
 _INPUTS_TRACK = _INPUTS_STEER + [_TRK, dp]                                # ..., landing_yaw, the track settings, pose
 _ROLLOUT_TRACK = _ROLLOUT_STEER + [_TRK, dp, dp]                          # ..., w_log, the track settings, pose, pose_log
+_PRV = C.POINTER(PreviewSettings)
+_INPUTS_PREVIEW = _INPUTS_TRACK + [_PRV, u8p]                             # ..., pose, the preview settings, previewed
+_ROLLOUT_PREVIEW = _ROLLOUT_TRACK + [_PRV]                                # ..., pose_log, the preview settings
 SIGNATURES = {
     # include/srbdqp.h -- config, handle
     "srbdqp_default_config": (_int, [_CFG]),
@@ -288,6 +296,14 @@ SIGNATURES = {
     "srbdqp_mpc_inputs_tracked_device_f64": (_int, _INPUTS_TRACK + [_vp]),
     "srbdqp_fleet_rollout_tracked_device_f64": (_int, _ROLLOUT_TRACK + [_vp]),
     "srbdqp_fleet_rollout_tracked_f64": (_int, _ROLLOUT_TRACK),
+    # ... that previews its footholds along the horizon: the steered or tracked inputs and roll-out, and the terrain inputs under footholds that change
+    "srbdqp_preview_default_settings": (_int, [_PRV]),
+    "srbdqp_mpc_inputs_previewed_f64": (_int, _INPUTS_PREVIEW),
+    "srbdqp_mpc_inputs_previewed_device_f64": (_int, _INPUTS_PREVIEW + [_vp]),
+    "srbdqp_terrain_inputs_previewed_f64": (_int, [H, _i64, dp, u8p, dp, dp]),
+    "srbdqp_terrain_inputs_previewed_device_f64": (_int, [H, _i64, dp, u8p, dp, dp, _vp]),
+    "srbdqp_fleet_rollout_previewed_device_f64": (_int, _ROLLOUT_PREVIEW + [_vp]),
+    "srbdqp_fleet_rollout_previewed_f64": (_int, _ROLLOUT_PREVIEW),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -165,6 +165,8 @@ struct srbdqp_handle {
         double *ew = nullptr, *ring_x = nullptr, *ring_feet = nullptr;
         // carved once a steered roll-out has asked: the heading every robot's next foot lands with, [B] (srbdqp_mpc_inputs_steered_* writes it)
         double* landing_yaw = nullptr;
+        // carved once a previewed roll-out has asked: where foot holds a previewed point, [B][N][4] (srbdqp_mpc_inputs_previewed_* writes it)
+        uint8_t* previewed = nullptr;
     } fleet;
     // the ground under the fleet (srbdqp_set_terrain, include/srbdqp_cascade.h): the library's device copy of the height map; map.h null: flat ground
     struct Terrain {
@@ -2865,14 +2867,23 @@ int track_check(srbdqp_handle* h, const char* fn, int64_t B, const srbdqp_track_
     return SRBDQP_OK;
 }
 
-// ---- the step before the QP: one argument record, one check, one launch, one device path, one host path for the six srbdqp_mpc_inputs* entry points ----
-// the flavours of an inputs call (kSteered, kTracked) and of a roll-out (all three).  kTracked: beside kSteered, the inputs call is the tracked one (section 21)
-enum : unsigned { kObserved = 1u, kSteered = 2u, kTracked = 4u };
+// ---- footholds previewed along the horizon (include/srbdqp_cascade.h; the kernel: srbdqp_steer.hpp) ----
+// what is wrong with a previewed call's settings (null: nothing)
+const char* preview_settings_fault(const srbdqp_preview_settings* s) {
+    if (!s || s->struct_size != (int32_t)sizeof(srbdqp_preview_settings)) return "struct_size is not sizeof(srbdqp_preview_settings)";
+    if (!std::isfinite(s->foot_half_length) || !(s->foot_half_length > 0.0)) return "foot_half_length must be finite and positive";
+    return nullptr;
+}
+
+// ---- the step before the QP: one argument record, one check, one launch, one device path, one host path for the eight srbdqp_mpc_inputs* entry points ----
+// the flavours of an inputs call (kSteered, kTracked, kPreview) and of a roll-out (all four).  kTracked: beside kSteered, the inputs call is the tracked one
+// (section 21); kPreview: beside kSteered, with or without kTracked, foot holds the footholds previewed along the horizon (section 22)
+enum : unsigned { kObserved = 1u, kSteered = 2u, kTracked = 4u, kPreview = 8u };
 
 // the arguments of an inputs call, as its entry point got them: device addresses, or the caller's host arrays (mpc_inputs_host).  What a flavour does not
 // read stands last and stays null
 struct InputsArgs {
-    unsigned flavour;                  // 0: srbdqp_mpc_inputs_*; kSteered: ..._steered_*; kSteered | kTracked: ..._tracked_*
+    unsigned flavour;                  // 0: srbdqp_mpc_inputs_*; kSteered: ..._steered_*; kSteered | kTracked: ..._tracked_*; with kPreview: ..._previewed_*
     const char* fn;                    // the call, for error texts
     int64_t B;
     const double *x0, *feet, *stamp;
@@ -2881,6 +2892,7 @@ struct InputsArgs {
     double *x_ref, *foot; uint8_t* contact; double *pcom, *landing;
     double* landing_yaw;               // written by a steered call; null otherwise
     const srbdqp_track_settings* trk; double *pose, *pose_log;    // read in a tracked call only; pose_log: the row of a roll-out's log, or null
+    const srbdqp_preview_settings* prv; uint8_t* previewed;       // read in a previewed call only; previewed [B][N][4] or null
 };
 
 // what MpcInputsArgs and SteerInputsArgs share, under the same names
@@ -2903,8 +2915,10 @@ int mpc_inputs_launch(srbdqp_handle* h, const InputsArgs& c, hipStream_t st) {
         inputs_fill(a, h, c);
         a.command = c.vel; a.landing_yaw = c.landing_yaw;
         const srbdqp::TrackPose tp = tracked ? srbdqp::TrackPose{c.pose, c.pose_log, c.trk->lead_max, c.trk->yaw_lead_max} : srbdqp::TrackPose{};
-        HIP_TRY(h, srbdqp::launch_mpc_inputs_commanded(a, tracked ? &tp : nullptr, h->live_nstar != 0, st));
-        h->kname = tracked ? "mpc_inputs_tracked_f64" : "mpc_inputs_steered_f64";
+        const bool preview = c.flavour & kPreview;
+        const srbdqp::PreviewFeet pf = preview ? srbdqp::PreviewFeet{c.previewed, c.prv->foot_half_length} : srbdqp::PreviewFeet{};
+        HIP_TRY(h, srbdqp::launch_mpc_inputs_commanded(a, tracked ? &tp : nullptr, h->live_nstar != 0, st, preview ? &pf : nullptr));
+        h->kname = preview ? (tracked ? "mpc_inputs_tracked_previewed_f64" : "mpc_inputs_previewed_f64") : (tracked ? "mpc_inputs_tracked_f64" : "mpc_inputs_steered_f64");
         return SRBDQP_OK;
     }
     srbdqp::MpcInputsArgs a;           // from v_ref [B][2]: the kernel of this code object
@@ -2934,6 +2948,7 @@ enum class InputsFrom { Device, Host, Staged };
 //  * the gait -- which the v_ref host form leaves to the device form behind its staging, as it always has: B = 0 is OK with any gait there
 int mpc_inputs_check(srbdqp_handle* h, const InputsArgs& c, InputsFrom from) {
     const bool steered = c.flavour & kSteered, host = from == InputsFrom::Host;
+    if (c.flavour & kPreview) if (const char* why = preview_settings_fault(c.prv)) return steer_refuse(h, std::string(c.fn) + ": invalid srbdqp_preview_settings: " + why);
     if (c.flavour & kTracked) {
         if (from != InputsFrom::Staged) if (const int rc = track_check(h, c.fn, c.B, c.trk, c.pose, c.vel, 1, host)) return rc;
     } else if (steered && host && c.B > 0 && c.B <= 0x7fffffffLL && c.vel) {
@@ -2966,10 +2981,11 @@ int mpc_inputs_host(srbdqp_handle* h, const InputsArgs& c) {
         d.x_ref = io.out<double>(c.x_ref, b * N * 13 * 8); d.foot = io.out<double>(c.foot, b * N * 12 * 8); d.contact = io.out<uint8_t>(c.contact, b * N * 4);
         d.pcom = io.out<double>(c.pcom, b * N * 3 * 8); d.landing = io.out<double>(c.landing, b * 3 * 8); d.landing_yaw = io.out<double>(c.landing_yaw, b * 8);
         if (c.flavour & kTracked) d.pose = io.add<double>(c.pose, c.pose, b * 3 * 8, false);
+        if (c.flavour & kPreview) d.previewed = io.out<uint8_t>(c.previewed, b * N * 4);
     }, [&](hipStream_t st) { return mpc_inputs_device(h, d, InputsFrom::Staged, st); });
 }
 
-// ---- the K-step loop: one argument record, one check, one loop, one host path for the six srbdqp_fleet_rollout_* entry points ----
+// ---- the K-step loop: one argument record, one check, one loop, one host path for the eight srbdqp_fleet_rollout_* entry points ----
 // what a roll-out does beside mpc_inputs -> solve -> fleet_advance (the flavour bits above): an observer behind every plant step (section 19), steered inputs
 // and footholds (section 20).  (The ground is the handle's: a terrain set makes any of them a terrain roll-out, section 18)
 
@@ -2986,6 +3002,7 @@ struct RolloutArgs {
     unsigned flavour;                  // kSteered: srbdqp_fleet_rollout_steered_*, which with obs is kObserved too; kObserved: ..._observed_*
     const char* fn;                    // the roll-out the call becomes, for error texts: srbdqp_fleet_rollout or srbdqp_fleet_rollout_observed
     const srbdqp_track_settings* trk; double *pose, *pose_log;    // read in a tracked roll-out only (kTracked, beside kSteered)
+    const srbdqp_preview_settings* prv;                           // read in a previewed roll-out only (kPreview, beside kSteered)
 };
 
 // the horizon buffers of a roll-out of this flavour (kObserved | kSteered), at B robots, carved from one allocation of the handle's.  What a flavour has
@@ -2993,9 +3010,10 @@ struct RolloutArgs {
 int ensure_fleet_buffers(srbdqp_handle* h, size_t B, unsigned flavour) {
     auto& f = h->fleet;
     const bool terrain = h->terrain.map.h != nullptr;
-    if (f.mem && f.B >= B && (!terrain || f.normals) && (!(flavour & kObserved) || f.ew) && (!(flavour & kSteered) || f.landing_yaw)) return SRBDQP_OK;
+    if (f.mem && f.B >= B && (!terrain || f.normals) && (!(flavour & kObserved) || f.ew) && (!(flavour & kSteered) || f.landing_yaw) &&
+        (!(flavour & kPreview) || f.previewed)) return SRBDQP_OK;
     f.flavour |= flavour;
-    const bool observed = f.flavour & kObserved, steered = f.flavour & kSteered;
+    const bool observed = f.flavour & kObserved, steered = f.flavour & kSteered, preview = f.flavour & kPreview;
     const size_t N = (size_t)h->cfg.horizon;
     auto carve = [&](char* base) {
         Carver c(base);
@@ -3006,6 +3024,7 @@ int ensure_fleet_buffers(srbdqp_handle* h, size_t B, unsigned flavour) {
         f.ew = observed ? c.take<double>(B * N * 6) : nullptr;
         f.ring_x = observed ? c.take<double>(2 * B * 13) : nullptr; f.ring_feet = observed ? c.take<double>(2 * B * 12) : nullptr;
         f.landing_yaw = steered ? c.take<double>(B) : nullptr;
+        f.previewed = preview ? c.take<uint8_t>(B * N * 4) : nullptr;
         return c.off;
     };
     const size_t want = carve(nullptr);
@@ -3068,15 +3087,18 @@ int wrench_observer_check(srbdqp_handle* h, int64_t B, const void* x_prev, const
 //    words.  Plain: the plant is flat ground and knows no wrench but the push -- a handle whose QPs are told otherwise would roll out against another robot
 constexpr unsigned kFormsObservedRollout = bit(Form::Robots) | bit(Form::Weights);
 int fleet_rollout_check(srbdqp_handle* h, const RolloutArgs& a, bool host) {
+    const bool preview = a.flavour & kPreview;
     if (a.flavour & kSteered) {
         const bool tracked = a.flavour & kTracked;
-        if (!a.command) return steer_refuse(h, std::string(tracked ? "srbdqp_fleet_rollout_tracked" : "srbdqp_fleet_rollout_steered") + ": command is NULL ([B][3] held over the call, or [T][B][3] with command_steps = T)");
-        if (a.command_steps != 1 && a.command_steps != a.T) return steer_refuse(h, std::string(tracked ? "srbdqp_fleet_rollout_tracked" : "srbdqp_fleet_rollout_steered") + ": command_steps must be 1 (one command held) or T (a row per step)");
+        const char* const who = preview ? "srbdqp_fleet_rollout_previewed" : tracked ? "srbdqp_fleet_rollout_tracked" : "srbdqp_fleet_rollout_steered";
+        if (!a.command) return steer_refuse(h, std::string(who) + ": command is NULL ([B][3] held over the call, or [T][B][3] with command_steps = T)");
+        if (a.command_steps != 1 && a.command_steps != a.T) return steer_refuse(h, std::string(who) + ": command_steps must be 1 (one command held) or T (a row per step)");
+        if (preview) if (const char* why = preview_settings_fault(a.prv)) return steer_refuse(h, std::string(who) + ": invalid srbdqp_preview_settings: " + why);
         // tracked: the settings and the pose, and on host arrays a pose and a command that are finite
-        if (tracked) { if (const int rc = track_check(h, "srbdqp_fleet_rollout_tracked", a.B, a.trk, a.pose, a.T >= 1 ? a.command : nullptr, (size_t)a.command_steps, host)) return rc; }
+        if (tracked) { if (const int rc = track_check(h, who, a.B, a.trk, a.pose, a.T >= 1 ? a.command : nullptr, (size_t)a.command_steps, host)) return rc; }
         else if (host && a.B >= 1 && a.B <= 0x7fffffffLL && a.T >= 1) {
             const long long i = steer_non_finite(a.command, (size_t)a.command_steps * (size_t)a.B * 3);
-            if (i >= 0) return steer_refuse(h, "srbdqp_fleet_rollout_steered: the command of robot " + std::to_string((i / 3) % a.B) + " at row " + std::to_string(i / (3 * a.B)) + " is not finite");
+            if (i >= 0) return steer_refuse(h, std::string(who) + ": the command of robot " + std::to_string((i / 3) % a.B) + " at row " + std::to_string(i / (3 * a.B)) + " is not finite");
         }
     }
     if (!h) return SRBDQP_E_INVALID;
@@ -3086,6 +3108,10 @@ int fleet_rollout_check(srbdqp_handle* h, const RolloutArgs& a, bool host) {
     if (!a.x || !a.feet || !a.stamp || !(a.v_ref || a.command)) { h->err = "null input/output pointer"; return SRBDQP_E_INVALID; }
     if (observed && !a.w_est) { h->err = fn + ": w_est is NULL (the estimate goes in and out: zeros start from no push)"; return SRBDQP_E_INVALID; }
     if (const char* why = fleet_settings_fault(a.cfg)) { h->err = std::string("invalid srbdqp_fleet_settings: ") + why; return SRBDQP_E_INVALID; }
+    if (preview && a.prv->foot_half_length != a.cfg->foot_half_length) {   // the MPC would preview another foot than the plant puts down
+        h->err = "srbdqp_fleet_rollout_previewed: srbdqp_preview_settings.foot_half_length differs from srbdqp_fleet_settings.foot_half_length: the footholds previewed would not be the ones the plant puts down";
+        return SRBDQP_E_INVALID;
+    }
     if (observed) {
         const char* const in = " -- in an observed roll-out";
         if (const char* why = observer_settings_fault(a.obs)) { h->err = std::string("invalid srbdqp_observer_settings: ") + why; return SRBDQP_E_INVALID; }
@@ -3127,6 +3153,14 @@ int terrain_inputs_launch(srbdqp_handle* h, int64_t B, const double* feet, doubl
     srbdqp::TerrainInputsArgs a{h->terrain.map, feet, x_ref, normals, (int32_t)h->cfg.horizon, (long long)B};
     HIP_TRY(h, srbdqp::launch_terrain_inputs(a, st));
     h->kname = "terrain_inputs_f64";
+    return SRBDQP_OK;
+}
+
+// ... under footholds that differ from step to step (section 22): foot's previewed points get their heights
+int terrain_inputs_previewed_launch(srbdqp_handle* h, int64_t B, double* foot, const uint8_t* previewed, double* x_ref, double* normals, hipStream_t st) {
+    srbdqp::TerrainPreviewArgs a{h->terrain.map, foot, previewed, x_ref, normals, (int32_t)h->cfg.horizon, (long long)B};
+    HIP_TRY(h, srbdqp::launch_terrain_inputs_previewed(a, st));
+    h->kname = "terrain_inputs_previewed_f64";
     return SRBDQP_OK;
 }
 
@@ -3211,6 +3245,26 @@ int srbdqp_terrain_inputs_f64(srbdqp_handle* h, int64_t B, const double* feet, d
     }, [&](hipStream_t st) { return srbdqp_terrain_inputs_device_f64(h, B, dfe, dxr, dcn, st); });
 }
 
+int srbdqp_terrain_inputs_previewed_device_f64(srbdqp_handle* h, int64_t B, double* foot, const uint8_t* previewed, double* x_ref, double* normals, void* stream) {
+    if (const int rc = terrain_inputs_check(h, B, foot, x_ref, normals)) return rc;
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    return terrain_inputs_previewed_launch(h, B, foot, previewed, x_ref, normals, stream ? reinterpret_cast<hipStream_t>(stream) : h->stream);
+}
+
+int srbdqp_terrain_inputs_previewed_f64(srbdqp_handle* h, int64_t B, double* foot, const uint8_t* previewed, double* x_ref, double* normals) {
+    if (const int rc = terrain_inputs_check(h, B, foot, x_ref, normals)) return rc;
+    if (B == 0) return SRBDQP_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t b = (size_t)B, N = (size_t)h->cfg.horizon;
+    double *dfo, *dxr, *dcn;
+    uint8_t* dpv;
+    return host_call(h, [&](HostIo& io) {
+        dfo = io.add<double>(foot, foot, b * N * 12 * 8, false); dpv = io.in<uint8_t>(previewed, b * N * 4);
+        dxr = io.add<double>(x_ref, x_ref, b * N * 13 * 8, false); dcn = io.out<double>(normals, b * N * 12 * 8);
+    }, [&](hipStream_t st) { return srbdqp_terrain_inputs_previewed_device_f64(h, B, dfo, dpv, dxr, dcn, st); });
+}
+
 int srbdqp_fleet_default_settings(srbdqp_fleet_settings* s) {
     if (!s || s->struct_size != (int32_t)sizeof(srbdqp_fleet_settings)) return SRBDQP_E_INVALID;
     std::memset(s, 0, sizeof(*s));
@@ -3247,13 +3301,14 @@ int fleet_rollout_run(srbdqp_handle* h, const RolloutArgs& a, void* stream) {
         const size_t k = (size_t)t;
         // steered: row t of a schedule, or the one command held; the inputs also say how the next foot lands turned (section 20)
         // tracked: the references come from the pose the caller carries, which the inputs kernel bounds, advances and logs itself (section 21)
-        const InputsArgs in{a.flavour & (kSteered | kTracked), a.fn, B, a.x, a.feet, a.stamp,
+        const InputsArgs in{a.flavour & (kSteered | kTracked | kPreview), a.fn, B, a.x, a.feet, a.stamp,
                             a.command ? a.command + (a.command_steps == 1 ? 0 : k * b * 3) : a.v_ref, a.standing, &a.cfg->gait,
                             f.x_ref, f.foot, f.contact, f.pcom, f.landing, a.command ? f.landing_yaw : nullptr,
-                            a.trk, a.pose, a.pose_log ? a.pose_log + k * b * 3 : nullptr};
+                            a.trk, a.pose, a.pose_log ? a.pose_log + k * b * 3 : nullptr, a.prv, (a.flavour & kPreview) ? f.previewed : nullptr};
         if (const int rc = mpc_inputs_launch(h, in, st)) return rc;
-        // the ground under the footholds: the normals of this step's QPs and the height reference
-        if (terrain) if (const int rc = terrain_inputs_launch(h, B, a.feet, f.x_ref, f.normals, st)) return rc;
+        // the ground under the footholds: the normals of this step's QPs and the height reference; previewed: under the footholds of every step (section 22)
+        if (terrain) if (const int rc = (a.flavour & kPreview) ? terrain_inputs_previewed_launch(h, B, f.foot, f.previewed, f.x_ref, f.normals, st)
+                                                               : terrain_inputs_launch(h, B, a.feet, f.x_ref, f.normals, st)) return rc;
         // the solve a device-buffer call makes (device_call), on a terrain with those normals as the normals of THIS call, observed with the wrench buffer as the wrench
         // of THIS call (the general kernel's _ew instantiation, which reads the handle's weights and robot records too) -- every pass of it, deferred ones on the
         // tail stream included, launches with this Call (solve_device_impl)
@@ -3386,6 +3441,32 @@ int srbdqp_mpc_inputs_tracked_f64(srbdqp_handle* h, int64_t B, const double* x0,
                                landing_yaw, trk, pose});
 }
 
+// ---- footholds previewed along the horizon (include/srbdqp_cascade.h) ----
+int srbdqp_preview_default_settings(srbdqp_preview_settings* s) {
+    if (!s || s->struct_size != (int32_t)sizeof(srbdqp_preview_settings)) return SRBDQP_E_INVALID;
+    std::memset(s, 0, sizeof(*s));
+    s->struct_size = (int32_t)sizeof(srbdqp_preview_settings);
+    s->foot_half_length = 0.085;
+    return SRBDQP_OK;
+}
+
+// (trk NULL: the steered form, pose ignored)
+int srbdqp_mpc_inputs_previewed_device_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
+                                           const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
+                                           double* landing, double* landing_yaw, const srbdqp_track_settings* trk, double* pose,
+                                           const srbdqp_preview_settings* prv, uint8_t* previewed, void* stream) {
+    return mpc_inputs_device(h, {kSteered | kPreview | (trk ? kTracked : 0u), "srbdqp_mpc_inputs_previewed", B, x0, feet, stamp, command, standing, gait, x_ref, foot,
+                                 contact, pcom, landing, landing_yaw, trk, trk ? pose : nullptr, nullptr, prv, previewed}, InputsFrom::Device, stream);
+}
+
+int srbdqp_mpc_inputs_previewed_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
+                                    const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
+                                    double* landing, double* landing_yaw, const srbdqp_track_settings* trk, double* pose,
+                                    const srbdqp_preview_settings* prv, uint8_t* previewed) {
+    return mpc_inputs_host(h, {kSteered | kPreview | (trk ? kTracked : 0u), "srbdqp_mpc_inputs_previewed", B, x0, feet, stamp, command, standing, gait, x_ref, foot,
+                               contact, pcom, landing, landing_yaw, trk, trk ? pose : nullptr, nullptr, prv, previewed});
+}
+
 // ---- the momentum observer (include/srbdqp_cascade.h) ----
 int srbdqp_observer_default_settings(srbdqp_observer_settings* s) {
     if (!s || s->struct_size != (int32_t)sizeof(srbdqp_observer_settings)) return SRBDQP_E_INVALID;
@@ -3420,7 +3501,7 @@ int srbdqp_wrench_observer_f64(srbdqp_handle* h, int64_t B, const double* x_prev
     }, [&](hipStream_t st) { return srbdqp_wrench_observer_device_f64(h, B, dx0, dx1, dfe, du, u0_stride, dal, cfg, dw, dew, st); });
 }
 
-// ---- the six roll-outs: each fills the record (RolloutArgs) and calls through ----
+// ---- the eight roll-outs: each fills the record (RolloutArgs) and calls through ----
 int srbdqp_fleet_rollout_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* v_ref,
                                     const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
                                     double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log, void* stream) {
@@ -3487,6 +3568,27 @@ int srbdqp_fleet_rollout_tracked_f64(srbdqp_handle* h, int64_t B, int32_t T, dou
     return fleet_rollout_host(h, {B, T, x, feet, stamp, nullptr, command, command_steps, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log,
                                   obs, w_est, w_log, kTracked | kSteered | (obs ? kObserved : 0u), obs ? "srbdqp_fleet_rollout_observed" : "srbdqp_fleet_rollout",
                                   trk, pose, pose_log});
+}
+
+// (the steered roll-out, tracked where trk is given, with the previewed inputs call -- and on a terrain the previewed terrain inputs)
+int srbdqp_fleet_rollout_previewed_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
+                                              int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                              double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                              const srbdqp_observer_settings* obs, double* w_est, double* w_log,
+                                              const srbdqp_track_settings* trk, double* pose, double* pose_log, const srbdqp_preview_settings* prv, void* stream) {
+    return fleet_rollout_device(h, {B, T, x, feet, stamp, nullptr, command, command_steps, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log,
+                                    obs, w_est, w_log, kPreview | (trk ? kTracked : 0u) | kSteered | (obs ? kObserved : 0u),
+                                    obs ? "srbdqp_fleet_rollout_observed" : "srbdqp_fleet_rollout", trk, trk ? pose : nullptr, trk ? pose_log : nullptr, prv}, stream);
+}
+
+int srbdqp_fleet_rollout_previewed_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
+                                       int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                       double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                       const srbdqp_observer_settings* obs, double* w_est, double* w_log,
+                                       const srbdqp_track_settings* trk, double* pose, double* pose_log, const srbdqp_preview_settings* prv) {
+    return fleet_rollout_host(h, {B, T, x, feet, stamp, nullptr, command, command_steps, standing, push, cfg, alive, x_log, u0_log, feet_log, status_log, iters_log,
+                                  obs, w_est, w_log, kPreview | (trk ? kTracked : 0u) | kSteered | (obs ? kObserved : 0u),
+                                  obs ? "srbdqp_fleet_rollout_observed" : "srbdqp_fleet_rollout", trk, trk ? pose : nullptr, trk ? pose_log : nullptr, prv});
 }
 
 }  // extern "C"

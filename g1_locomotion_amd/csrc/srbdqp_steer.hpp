@@ -11,6 +11,10 @@
 // of the measured state: track_bound and track_advance beside steer_table (tests/test_track_cpu.py builds them alone, against tests/track_twin.py).  Its
 // kernel is the same template with a TrackPose as a second argument: one text for the staging, the gait phase, the element loops and the landing point, and
 // `if constexpr` around what a pose adds.
+//
+// A fleet that previews its footholds along the horizon (srbdqp_mpc_inputs_previewed_*): preview_lands, preview_touchdown and
+// preview_foothold beside steer_landing (tests/test_preview_cpu.py builds them alone, against tests/preview_twin.py), and a PreviewFeet as the template's last
+// argument, steered or tracked.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -100,6 +104,40 @@ SRBDQP_STEER_HD void steer_landing(const double* x0, double psi_l, double side, 
     ly = ((x0[4] + c * o) + half_T * x0[10]) + 0.03 * (x0[10] - vw0y);
 }
 
+// Footholds previewed along the horizon (include/srbdqp_cascade.h, srbdqp_mpc_inputs_previewed_*): the plant's touchdown rule moved
+// along the horizon.  With ph(k) = (p0 + k) mod 2 period the left foot (contacts 0, 1) is in the air for ph in [period + ds, 2 period) and lands at ph = 0, the
+// right foot (contacts 2, 3) is in the air for ph in [ds, period) and lands at ph = period: closed forms of the phase, no search.  p0 < 0 (standing) and
+// ds >= period (no swing) have no touchdown.  preview_lands, preview_touchdown and preview_foothold are __host__ __device__ and need nothing of HIP
+// (tests/test_preview_cpu.py builds them alone, against tests/preview_twin.py).
+
+// the foot that touches down at horizon step j: 0 none (j < 1 among it: step 0 is the present), 1 the left, 2 the right
+SRBDQP_STEER_HD int preview_lands(int p0, int j, int period, int ds) {
+    if (p0 < 0 || ds >= period || j < 1) return 0;
+    const int ph = (p0 + j) % (2 * period);
+    return ph == 0 ? 1 : (ph == period ? 2 : 0);
+}
+
+// the latest touchdown step j in [1, k] of the left (right: the right) foot, or 0 where there is none
+SRBDQP_STEER_HD int preview_touchdown(int p0, int k, int period, int ds, bool right) {
+    if (p0 < 0 || ds >= period) return 0;
+    const int j = k - (p0 + k + (right ? period : 0)) % (2 * period);
+    return j >= 1 ? j : 0;
+}
+
+// the foothold of a touchdown from the predicted state behind the step before it: heading psi, position (px, py), velocity (vx, vy), the command's velocity
+// (vwx, vwy) there; side: +1 the left foot lands, -1 the right (steer_landing's side: the OTHER foot stands).  psi_l = psi + wz half_T, the landing point is
+// steer_landing's, heel and toe are steer_touchdown's along psi_l
+SRBDQP_STEER_HD void preview_foothold(double psi, double px, double py, double vx, double vy, double vwx, double vwy, double wz, double side, double hip_offset_y,
+                                      double half_T, double half, double (&heel)[2], double (&toe)[2], double& psi_l) {
+#pragma clang fp contract(off)
+    double x[11] = {};
+    x[3] = px; x[4] = py; x[9] = vx; x[10] = vy;
+    psi_l = psi + wz * half_T;
+    double lx, ly;
+    steer_landing(x, psi_l, side, hip_offset_y, half_T, vwx, vwy, lx, ly);
+    steer_touchdown(lx, ly, half, psi_l, heel, toe);
+}
+
 struct SteerInputsArgs {
     const double* x0;        // [B][13]
     const double* feet;      // [B][12]
@@ -125,10 +163,23 @@ struct TrackPose {
     double lead_max, yaw_lead_max;
 };
 
+// what a previewed call adds: the kernel's last argument, behind the pose of a tracked call
+struct PreviewFeet {
+    uint8_t* previewed;      // [B][N][4] or null: 1 where foot[b][k] holds a previewed point for that contact
+    double foot_half_length; // heel and toe lie this far behind and ahead of the landing point, as in the plant step
+};
+
 #if defined(__HIPCC__)
 // the launch of srbdqp_mpc_inputs_commanded_kernel on st (srbdqp_wrench_lat_ew.hip); track null: the steered instantiation; live: a.N at run time
-// (SRBDQP_FLAG_ANY_HORIZON)
-hipError_t launch_mpc_inputs_commanded(const SteerInputsArgs& a, const TrackPose* track, bool live, hipStream_t st);
+// (SRBDQP_FLAG_ANY_HORIZON); preview non-null: the previewed instantiation of either
+hipError_t launch_mpc_inputs_commanded(const SteerInputsArgs& a, const TrackPose* track, bool live, hipStream_t st, const PreviewFeet* preview = nullptr);
+
+// the argument of type T among the kernel's trailing ones
+template <class T, class First, class... Rest>
+__device__ __forceinline__ const T& steer_arg(const First& first, const Rest&... rest) {
+    if constexpr (std::is_same<T, First>::value) return first;
+    else return steer_arg<T>(rest...);
+}
 
 // srbdqp_mpc_inputs_kernel's tiling (srbdqp_cascade.hpp): a workgroup takes tiles of 32 consecutive robots, their 13 + 12 + 3 input doubles each staged in LDS
 // with coalesced loads, the tile's outputs written element by element, 512 contiguous bytes per store instruction of a wave.  Between the two, the tile's
@@ -144,17 +195,25 @@ hipError_t launch_mpc_inputs_commanded(const SteerInputsArgs& a, const TrackPose
 // per (robot, table, axis) sums the N increments in order, and a thread per robot moves its pose on (track_advance) and writes it, to pose and -- in a
 // roll-out -- to the step's row of pose_log.  Six [32][25] arrays: 47 KB of LDS, three workgroups a CU.  The steered form neither holds nor
 // reads what is the tracked form's alone (sq, sqx, sqy, sv0): its 32 KB are what let a fourth workgroup onto the CU.
+//
+// A PreviewFeet last: the previewed inputs of either form.  Behind the serial sums a thread per (robot, step k) decides from the phase
+// whether a foot touches down at k; where one does it computes heel and toe (preview_foothold: three sines and cosines, from p_{k-1} of the measured table) into
+// stx [32][25][4], and every thread writes the latest touchdown steps of both feet at k into sj.  The foot loop then reads sj and stx and takes no sine; the
+// contact loop writes the previewed word beside the contact word.  25.6 KB + 1.6 KB of LDS more: 59 KB steered, 74 KB tracked, two workgroups a CU.
 template <int NH, class... TRACK>   // NH: the horizon as a compile-time constant (NH = 0: a.N at run time)
 __global__ __launch_bounds__(256) void srbdqp_mpc_inputs_commanded_kernel(SteerInputsArgs a, TRACK... track) {
 #pragma clang fp contract(off)
-    static_assert(sizeof...(TRACK) <= 1 && (std::is_same<TRACK, TrackPose>::value && ...), "at most one TrackPose");
-    constexpr bool TRACKED = sizeof...(TRACK) == 1;
+    constexpr bool TRACKED = (std::is_same<TRACK, TrackPose>::value || ...), PREVIEW = (std::is_same<TRACK, PreviewFeet>::value || ...);
+    static_assert(sizeof...(TRACK) == (TRACKED ? 1 : 0) + (PREVIEW ? 1 : 0), "at most one TrackPose, then at most one PreviewFeet");
     constexpr int R = 32, K = kSteerSteps, RT = TRACKED ? R : 1;          // RT: the rows of what only the tracked form holds
+    constexpr int RP = PREVIEW ? R : 1;                                   // ... and of what only a previewed form holds
     const int N = NH > 0 ? NH : a.N;
     __shared__ double sx0[R * 13], sft[R * 12], sc[R * 3], sq[RT * 3];
     __shared__ double sqx[RT * K], sqy[RT * K], svx[R * K], svy[R * K];   // the pose's q_k; v_w(th + wz k dt) -- steered: th = psi0 --, k = 0 ... N
     __shared__ double spx[R * K], spy[R * K], sv0[RT * 2];                // the measured state's p_k; tracked: v_w(psi0) beside svx, svy
     __shared__ int sph[R];                                               // phase of step 0 in [0, 2 period), or -1 = standing
+    __shared__ double stx[RP * K * 4];                                    // previewed: heel xy, toe xy of the touchdown at step k
+    __shared__ uint8_t sj[RP * K * 2];                                    // previewed: the latest touchdown step of the left, the right foot at step k (0: none)
     double* const rx = TRACKED ? sqx : spx;                              // the table the references read: steered, the measured state's own
     double* const ry = TRACKED ? sqy : spy;
     const int t = threadIdx.x;
@@ -166,7 +225,7 @@ __global__ __launch_bounds__(256) void srbdqp_mpc_inputs_commanded_kernel(SteerI
         for (int i = t; i < nr * 12; i += 256) sft[i] = a.feet[b0 * 12 + i];
         for (int i = t; i < nr * 3; i += 256) {
             sc[i] = a.command[b0 * 3 + i];
-            if constexpr (TRACKED) sq[i] = (track, ...).pose[b0 * 3 + i];
+            if constexpr (TRACKED) sq[i] = steer_arg<TrackPose>(track...).pose[b0 * 3 + i];
         }
         if (t < nr) {
             const bool stand = a.standing && a.standing[b0 + t];
@@ -174,7 +233,7 @@ __global__ __launch_bounds__(256) void srbdqp_mpc_inputs_commanded_kernel(SteerI
         }
         __syncthreads();
         if constexpr (TRACKED) {
-            const TrackPose& tp = (track, ...);
+            const TrackPose& tp = steer_arg<TrackPose>(track...);
             if (t < nr) track_bound(sq[3 * t], sq[3 * t + 1], sq[3 * t + 2], sx0[13 * t + 3], sx0[13 * t + 4], sx0[13 * t + 2], tp.lead_max, tp.yaw_lead_max);
             __syncthreads();
         }
@@ -207,6 +266,31 @@ __global__ __launch_bounds__(256) void srbdqp_mpc_inputs_commanded_kernel(SteerI
             for (int k = 1; k <= N; ++k) { acc = acc + p[k]; p[k] = acc; }
         }
         __syncthreads();
+        if constexpr (PREVIEW) {                                         // the touchdowns along the horizon: entry (r, k), k = 0 ... N - 1
+            const PreviewFeet& pv = steer_arg<PreviewFeet>(track...);
+            const double half_T = 0.5 * ((double)a.period * a.dt);
+            for (int e = t; e < nr * N; e += 256) {
+                const int r = e / N, k = e - N * r;
+                const int lands = preview_lands(sph[r], k, a.period, a.ds);
+                if (lands) {                                             // from the predicted state behind step k - 1; k - 1 = 0: the measured state itself
+                    const double* x0 = sx0 + 13 * r;
+                    const double vx = sc[3 * r], vy = sc[3 * r + 1], wz = sc[3 * r + 2];
+                    double vwx, vwy;                                     // v_w(psi0 + wz (k - 1) dt): steered, the table's own entry
+                    if constexpr (TRACKED) steer_rotate(steer_yaw(x0[2], wz, (double)(k - 1), a.dt), vx, vy, vwx, vwy);
+                    else { vwx = svx[K * r + k - 1]; vwy = svy[K * r + k - 1]; }
+                    const bool now = k == 1;
+                    const double psi = now ? x0[2] : steer_yaw(x0[2], wz, (double)(k - 1), a.dt);
+                    double heel[2], toe[2], psi_l;
+                    preview_foothold(psi, spx[K * r + k - 1], spy[K * r + k - 1], now ? x0[9] : vwx, now ? x0[10] : vwy, vwx, vwy, wz, lands == 1 ? 1.0 : -1.0,
+                                     a.hip_offset_y, half_T, pv.foot_half_length, heel, toe, psi_l);
+                    double* o = stx + (K * r + k) * 4;
+                    o[0] = heel[0]; o[1] = heel[1]; o[2] = toe[0]; o[3] = toe[1];
+                }
+                sj[(K * r + k) * 2] = (uint8_t)preview_touchdown(sph[r], k, a.period, a.ds, false);
+                sj[(K * r + k) * 2 + 1] = (uint8_t)preview_touchdown(sph[r], k, a.period, a.ds, true);
+            }
+            __syncthreads();
+        }
         auto flags = [&](int r, int k, bool& cl, bool& cr) { gait_flags(sph[r], k, a.period, a.ds, cl, cr); };
         double* xr = a.x_ref + b0 * (N * 13);
         for (int e = t; e < nr * N * 13; e += 256) {                     // x_ref[r][k][c], reference index k + 1
@@ -228,7 +312,11 @@ __global__ __launch_bounds__(256) void srbdqp_mpc_inputs_commanded_kernel(SteerI
         double* fo = a.foot + b0 * (N * 12);
         for (int e = t; e < nr * N * 12; e += 256) {                     // foot[r][k][c]: the current contact points, repeated
             const int row = e / 12, c = e - 12 * row, r = row / N;
-            fo[e] = sft[12 * r + c];
+            if constexpr (PREVIEW) {                                     // ... or heel and toe of the foot's latest touchdown up to step k, on the ground plane
+                const int k = row - N * r, i = c / 3, ax = c - 3 * i, j = sj[(K * r + k) * 2 + (i >> 1)];
+                fo[e] = !j ? sft[12 * r + c] : (ax == 2 ? 0.0 : stx[(K * r + j) * 4 + 2 * (i & 1) + ax]);
+            } else
+                fo[e] = sft[12 * r + c];
         }
         double* pc = a.pcom + b0 * (N * 3);
         for (int e = t; e < nr * N * 3; e += 256) {                      // pcom[r][k] = (p_k, the measured height): where the robot is
@@ -241,6 +329,10 @@ __global__ __launch_bounds__(256) void srbdqp_mpc_inputs_commanded_kernel(SteerI
             bool cl, cr;
             flags(r, k, cl, cr);
             cw[row] = (cl ? 0x00000101u : 0u) | (cr ? 0x01010000u : 0u);
+            if constexpr (PREVIEW) {
+                const PreviewFeet& pv = steer_arg<PreviewFeet>(track...);
+                if (pv.previewed) (reinterpret_cast<uint32_t*>(pv.previewed) + b0 * N)[row] = (sj[(K * r + k) * 2] ? 0x00000101u : 0u) | (sj[(K * r + k) * 2 + 1] ? 0x01010000u : 0u);
+            }
         }
         if (t < nr) {
             const double* x0 = sx0 + 13 * t;
@@ -258,7 +350,7 @@ __global__ __launch_bounds__(256) void srbdqp_mpc_inputs_commanded_kernel(SteerI
                 if (a.landing_yaw) a.landing_yaw[b0 + t] = psi_l;
             }
             if constexpr (TRACKED) {
-                const TrackPose& tp = (track, ...);
+                const TrackPose& tp = steer_arg<TrackPose>(track...);
                 double qx = sq[3 * t], qy = sq[3 * t + 1], th = sq[3 * t + 2];  // the pose behind this control step
                 track_advance(qx, qy, th, sqx[K * t + 1], sqy[K * t + 1], wz, a.dt);
                 double* po = tp.pose + (b0 + t) * 3;

@@ -120,4 +120,53 @@ __global__ __launch_bounds__(256) void srbdqp_terrain_inputs_kernel(TerrainInput
     }
 }
 
+// The same between srbdqp_mpc_inputs_previewed_* and the solve: the footholds differ from step to step, so every (robot, step, contact)
+// is sampled under its own point.  A previewed point gets z = S(own xy).z, the plant's touchdown rule; the height reference of step k follows the four heights
+// of foot[b][k] after that write.
+struct TerrainPreviewArgs {
+    TerrainMap map;
+    double* foot;            // [B][N][12]  in/out: the z of a previewed point
+    const uint8_t* previewed;// [B][N][4] or null (none previewed)
+    double* x_ref;           // [B][N][13]  in/out: column 5 of step k gains the mean height of foot[b][k]
+    double* normals;         // [B][N][12]  out
+    int32_t N;
+    long long B;
+};
+
+hipError_t launch_terrain_inputs_previewed(const TerrainPreviewArgs& a, hipStream_t st);
+
+// The tiling of srbdqp_terrain_inputs_kernel.  One thread per (robot, step, contact) reads its point -- a wave's 64 points are 1.5 KB of contiguous foot --,
+// samples the map, writes the normal (the wave's 1.5 KB, contiguous) and, where the point is previewed, its height; the four heights of a step wait in LDS
+// (24 KB at N = 24) for the x_ref loop, which adds their mean to column 5 in the order (((z0 + z1) + z2) + z3) 0.25.  a.N <= 24.
+template <int R>
+__global__ __launch_bounds__(256) void srbdqp_terrain_inputs_previewed_kernel(TerrainPreviewArgs a) {
+#pragma clang fp contract(off)
+    constexpr int NMAX = 24;
+    const int N = a.N;
+    __shared__ double sz[R * NMAX * 4];
+    const int t = threadIdx.x;
+    const long long tiles = (a.B + R - 1) / R;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long b0 = tile * R;
+        const int nr = (int)((a.B - b0 < R) ? (a.B - b0) : R);
+        const long long p0 = b0 * ((long long)N * 4);                    // the tile's first point
+        for (int e = t; e < nr * N * 4; e += 256) {                      // point e of the tile: contact e & 3 of row e >> 2
+            double* f = a.foot + (p0 + e) * 3;
+            double z, n[3];
+            terrain_sample(a.map, f[0], f[1], z, n);
+            double* cn = a.normals + (p0 + e) * 3;
+            cn[0] = n[0]; cn[1] = n[1]; cn[2] = n[2];
+            if (a.previewed && a.previewed[p0 + e]) { f[2] = z; sz[e] = z; }
+            else sz[e] = f[2];
+        }
+        __syncthreads();
+        double* xr = a.x_ref + b0 * ((long long)N * 13);
+        for (int e = t; e < nr * N * 13; e += 256) {                     // x_ref[r][k][c]
+            const int row = e / 13, c = e - 13 * row;
+            if (c == 5) { const double* z = sz + 4 * row; xr[e] = xr[e] + (((z[0] + z[1]) + z[2]) + z[3]) * 0.25; }
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace srbdqp

@@ -120,9 +120,20 @@ hipError_t launch_commanded(std::integer_sequence<int, Ns...>, const SteerInputs
 }
 }  // namespace
 
-hipError_t launch_mpc_inputs_commanded(const SteerInputsArgs& a, const TrackPose* track, bool live, hipStream_t st) {
+hipError_t launch_mpc_inputs_commanded(const SteerInputsArgs& a, const TrackPose* track, bool live, hipStream_t st, const PreviewFeet* preview) {
     using Tabulated = std::integer_sequence<int, 4, 8, 10, 12, 16, 20, 24>;
+    // (the previewed instantiations, DESIGN.md section 22, stand behind the plain ones of their form)
+    if (preview) return track ? launch_commanded(Tabulated{}, a, live, st, *track, *preview) : launch_commanded(Tabulated{}, a, live, st, *preview);
     return track ? launch_commanded(Tabulated{}, a, live, st, *track) : launch_commanded(Tabulated{}, a, live, st);
+}
+
+// ... and the ground under footholds that differ from step to step, those of srbdqp_mpc_inputs_previewed_* (srbdqp_terrain.hpp)
+hipError_t launch_terrain_inputs_previewed(const TerrainPreviewArgs& a, hipStream_t st) {
+    if (a.N < 1 || a.N > 24) return hipErrorInvalidValue;             // (the kernel's table of heights holds 24 steps a robot)
+    const long long tiles = (a.B + kTerrainTile - 1) / kTerrainTile;
+    const dim3 grid((unsigned)(tiles < 1 ? 1 : (tiles > 256 * 32 ? 256 * 32 : tiles)));
+    hipLaunchKernelGGL(srbdqp_terrain_inputs_previewed_kernel<kTerrainTile>, grid, dim3(256), 0, st, a);
+    return hipGetLastError();
 }
 
 }  // namespace srbdqp

@@ -471,10 +471,11 @@ class BatchMPC(_Engine):
         return self._mpc_inputs("srbdqp_mpc_inputs_f64", x0, feet, stamp, lambda B: [_c(v_ref, np.float64).reshape(B, 2)], standing,
                                 (period_steps, double_support_steps, com_target, hip_offset_y))
 
-    def _mpc_inputs(self, fn, x0, feet, stamp, vel, standing, gait, track=None):
+    def _mpc_inputs(self, fn, x0, feet, stamp, vel, standing, gait, track=None, preview=None):
         """The host form `fn` of the inputs: the marshalling of x0, feet, stamp and standing, the gait struct and the outputs, once for mpc_inputs(),
-        mpc_inputs_steered() and mpc_inputs_tracked().  vel(B): the call's own arrays as it marshals them, v_ref or command first and behind a command the
-        pose, which goes in and out.  gait: _gait_struct()'s arguments.  track: track_settings()' keywords in a tracked call."""
+        mpc_inputs_steered(), mpc_inputs_tracked() and mpc_inputs_previewed().  vel(B): the call's own arrays as it marshals them, v_ref or command first and
+        behind a command the pose, which goes in and out.  gait: _gait_struct()'s arguments.  track: track_settings()' keywords in a tracked call.  preview:
+        preview_settings()' keywords in a previewed call, which takes the track settings and the pose too (None each: its steered form)."""
         x = _c(x0, np.float64).reshape(-1, NX)
         B, N = x.shape[0], self.N
         f = _c(feet, np.float64).reshape(B, NU)
@@ -487,8 +488,13 @@ class BatchMPC(_Engine):
         out = dict(x_ref=xr, foot=ft, contact=ct, pcom=np.empty((B, N, 3)), landing=np.empty((B, 3)))
         if v.shape[1] == 3:       # under a command: the heading the next foot lands with
             out["landing_yaw"] = np.empty(B)
+        more = {}
+        if preview is not None:   # (behind the tracked call's arguments, which are null in the steered form)
+            more["previewed"] = np.empty((B, N, NC), dtype=np.uint8)
+            tail = (tail or (None, None)) + (C.byref(self.preview_settings(**preview)), _p(more["previewed"]))
         rc = getattr(self._lib, fn)(self._h, B, _p(x), _p(f), _p(t), _p(v), _p(sd), C.byref(g), *(_p(o) for o in out.values()), *tail)
         self._check(rc)
+        out.update(more)
         return dict(out, pose=po[0]) if po else out
 
     def mpc_inputs_device(self, B, x0, feet, stamp, v_ref, com_target, x_ref, foot, contact, pcom, landing=0, standing=0,
@@ -555,6 +561,40 @@ class BatchMPC(_Engine):
         k = self.track_settings(**track)
         rc = self._lib.srbdqp_mpc_inputs_tracked_device_f64(self._h, int(B), v(x0), v(feet), v(stamp), v(command), v(standing), C.byref(g),
                                                             v(x_ref), v(foot), v(contact), v(pcom), v(landing), v(landing_yaw), C.byref(k), v(pose), v(stream))
+        self._check(rc)
+
+    # -- a fleet that previews its footholds along the horizon (include/srbdqp_cascade.h) -----------------------
+    def preview_settings(self, foot_half_length=0.085):
+        """srbdqp_preview_settings for mpc_inputs_previewed() / rollout(preview=): how far heel and toe of a previewed foothold lie behind and ahead of its
+        landing point -- the plant's fleet_settings() value; finite and positive."""
+        s = _lib.PreviewSettings()
+        s.struct_size = C.sizeof(_lib.PreviewSettings)
+        s.foot_half_length = float(foot_half_length)
+        return s
+
+    def mpc_inputs_previewed(self, x0, feet, stamp, command, com_target, pose=None, standing=None, period_steps=6, double_support_steps=1,
+                             hip_offset_y=0.0645, foot_half_length=0.085, **track):
+        """mpc_inputs_steered() -- with pose (B,3), mpc_inputs_tracked(), track: track_settings()' keywords -- whose foot (B,N,12) previews the footholds
+        along the horizon (srbdqp_mpc_inputs_previewed_f64): from the step at which a foot touches down under the gait, its two contacts
+        stand on the heel and toe the plant will put down there -- the landing point and the heading at mid-swing of the state predicted for that step.  Every
+        other output is the steered or tracked call's, bit for bit.
+        Returns that call's dict and previewed (B,N,4) uint8: 1 where foot holds a previewed point."""
+        vel = (lambda B: [_as(command, np.float64, (B, 3), "command")]) if pose is None else \
+              (lambda B: [_as(command, np.float64, (B, 3), "command"), np.array(_as(pose, np.float64, (B, 3), "pose"))])
+        return self._mpc_inputs("srbdqp_mpc_inputs_previewed_f64", x0, feet, stamp, vel, standing, (period_steps, double_support_steps, com_target, hip_offset_y),
+                                None if pose is None else track, dict(foot_half_length=foot_half_length))
+
+    def mpc_inputs_previewed_device(self, B, x0, feet, stamp, command, com_target, x_ref, foot, contact, pcom, landing=0, landing_yaw=0, standing=0, pose=0,
+                                    previewed=0, period_steps=6, double_support_steps=1, hip_offset_y=0.0645, foot_half_length=0.085, stream=0, **track):
+        """Device-pointer form of mpc_inputs_previewed(): raw addresses in, launch enqueued behind `stream`, returns at once.  pose: the address of (B,3) poses,
+        updated in place -- the tracked form --, or 0 for the steered form; previewed: the address of (B,N,4) bytes, or 0."""
+        v = lambda q: C.c_void_p(int(q)) if q else None
+        g = self._gait_struct(period_steps, double_support_steps, com_target, hip_offset_y)
+        k = self.track_settings(**track) if pose else None
+        pr = self.preview_settings(foot_half_length)
+        rc = self._lib.srbdqp_mpc_inputs_previewed_device_f64(self._h, int(B), v(x0), v(feet), v(stamp), v(command), v(standing), C.byref(g), v(x_ref), v(foot),
+                                                              v(contact), v(pcom), v(landing), v(landing_yaw), C.byref(k) if pose else None, v(pose), C.byref(pr),
+                                                              v(previewed), v(stream))
         self._check(rc)
 
     # -- from step t to step t + 1: the fleet's plant step and the K-step loop (include/srbdqp_cascade.h, DESIGN.md section 17) --------
@@ -646,7 +686,7 @@ class BatchMPC(_Engine):
                                                                 C.byref(s), v(w_est), v(ew), v(stream)))
 
     def rollout(self, x0, feet, stamp, v_ref, steps, com_target, standing=None, push=None, alive=None, observer=None, w_est=None, command=None, track=None,
-                pose=None, **settings):
+                pose=None, preview=None, **settings):
         """`steps` control steps of B robots on the device (srbdqp_fleet_rollout_f64): per step mpc_inputs -> the solve -> fleet_advance, without a host
         round trip in between.  x0 (B,13), feet (B,12) or (B,4,3), stamp (B,), v_ref (B,2) and standing (B,) flags or None (both constant over the call),
         push (steps,B,6) world wrenches or None, alive (B,) flags or None.  settings: fleet_settings()' keywords.  Robot records and weights set on the
@@ -669,6 +709,9 @@ class BatchMPC(_Engine):
         within lead_max and yaw_lead_max of the robot, so that the fleet ends where its commands lead.  pose=None starts on the measured (x0[3:5], x0[2]);
         carried from one call to the next, chunks compose bit for bit.  The result then has pose (B,3) and pose_log (steps,B,3), the pose behind every
         step.  track=None is the call as it was.
+        preview=True, with command=: the previewed roll-out (srbdqp_fleet_rollout_previewed_f64) -- mpc_inputs_previewed in place of the
+        steered or tracked inputs, and on a map terrain_inputs_previewed: every solve reads the footholds its robot will stand on along the horizon, with the
+        plant's own foot_half_length.  It works with track=, observer= and a map as the steered roll-out does.  preview=None is the call as it was.
         Returns dict(x (steps+1,B,13), u0 (steps,B,12), feet (steps+1,B,12), status (steps,B), iters (steps,B), alive (B,) uint8, stamp (B,))."""
         x = np.array(x0, dtype=np.float64).reshape(-1, NX)
         B, T = x.shape[0], int(steps)
@@ -696,6 +739,9 @@ class BatchMPC(_Engine):
             raise ValueError("rollout: track= follows a command schedule (command=): there is no path without one")
         if pose is not None and not tracked:
             raise ValueError("rollout: pose belongs to a tracked roll-out (track=)")
+        previewed = preview is not None and preview is not False
+        if previewed and command is None:
+            raise ValueError("rollout: preview= previews the footholds of a commanded roll-out (command=)")
         out = dict(x=xl, u0=ul, feet=fl, status=sl, iters=il, alive=al, stamp=t)
         obs = ()
         if observed:
@@ -709,18 +755,22 @@ class BatchMPC(_Engine):
                 po = np.concatenate([x[:, 3:5], x[:, 2:3]], axis=1) if pose is None else np.array(_as(pose, np.float64, (B, 3), "pose"))
                 out.update(pose=np.ascontiguousarray(po), pose_log=np.empty((n, B, 3)))
                 fn, obs = self._lib.srbdqp_fleet_rollout_tracked_f64, obs + (C.byref(k), _p(out["pose"]), _p(out["pose_log"]))
+            if previewed:           # (... and the previewed call its settings behind the tracked call's, which are null in its steered form)
+                pr = self.preview_settings(s.foot_half_length)
+                fn, obs = self._lib.srbdqp_fleet_rollout_previewed_f64, (obs if tracked else obs + (None, None, None)) + (C.byref(pr),)
         else:
             fn, vel = self._lib.srbdqp_fleet_rollout_observed_f64 if observed else self._lib.srbdqp_fleet_rollout_f64, (_p(v),)
         self._check(fn(self._h, B, T, _p(x), _p(f), _p(t), *vel, _p(sd), _p(pu), C.byref(s), _p(al), _p(xl), _p(ul), _p(fl), _p(sl), _p(il), *obs))
         return out
 
     def rollout_device(self, B, steps, x, feet, stamp, v_ref, com_target, standing=0, push=0, alive=0, x_log=0, u0_log=0, feet_log=0, status_log=0,
-                       iters_log=0, stream=0, observer=None, w_est=0, w_log=0, command=0, command_steps=1, track=None, pose=0, pose_log=0, **settings):
+                       iters_log=0, stream=0, observer=None, w_est=0, w_log=0, command=0, command_steps=1, track=None, pose=0, pose_log=0, preview=None,
+                       **settings):
         """Device-pointer form of rollout(): raw addresses (0 = absent), x / feet / stamp / alive updated in place, every launch enqueued behind `stream`
         (0 = the engine's own), returns at once without synchronising.  Logs as in include/srbdqp_cascade.h.  observer= as in rollout(): w_est (B,6),
         required then, is updated in place; w_log (steps,B,6) or 0.  command: the address of (B,3) commands (command_steps=1) or of (steps,B,3)
         (command_steps=steps) -- the steered roll-out, v_ref 0 then; 0: the call as it was.  track= as in rollout(), with command: pose (B,3), required
-        then, is updated in place; pose_log (steps,B,3) or 0."""
+        then, is updated in place; pose_log (steps,B,3) or 0.  preview= as in rollout(), with command."""
         v = lambda q: C.c_void_p(int(q)) if q else None
         s = self.fleet_settings(com_target, **settings)
         if command and v_ref:
@@ -737,11 +787,17 @@ class BatchMPC(_Engine):
             raise ValueError("rollout_device: track= follows a command schedule (command=): there is no path without one")
         if (pose or pose_log) and not tracked:
             raise ValueError("rollout_device: pose and pose_log belong to a tracked roll-out (track=)")
+        previewed = preview is not None and preview is not False
+        if previewed and not command:
+            raise ValueError("rollout_device: preview= previews the footholds of a commanded roll-out (command=)")
         if command:     # (one steered call, with its observer or without)
             fn, vel, obs = self._lib.srbdqp_fleet_rollout_steered_device_f64, (v(command), int(command_steps)), obs or (None, None, None)
             if tracked:
                 k = self._track_arg(track)
                 fn, obs = self._lib.srbdqp_fleet_rollout_tracked_device_f64, obs + (C.byref(k), v(pose), v(pose_log))
+            if previewed:
+                pr = self.preview_settings(s.foot_half_length)
+                fn, obs = self._lib.srbdqp_fleet_rollout_previewed_device_f64, (obs if tracked else obs + (None, None, None)) + (C.byref(pr),)
         else:
             fn, vel = self._lib.srbdqp_fleet_rollout_observed_device_f64 if observed else self._lib.srbdqp_fleet_rollout_device_f64, (v(v_ref),)
         self._check(fn(self._h, int(B), int(steps), v(x), v(feet), v(stamp), *vel, v(standing), v(push), C.byref(s), v(alive), v(x_log), v(u0_log), v(feet_log),
@@ -796,6 +852,25 @@ class BatchMPC(_Engine):
         """Device-pointer form of terrain_inputs(): raw addresses, x_ref updated in place, launch enqueued behind `stream`, returns at once."""
         v = lambda q: C.c_void_p(int(q)) if q else None
         self._check(self._lib.srbdqp_terrain_inputs_device_f64(self._h, int(B), v(feet), v(x_ref), v(normals), v(stream)))
+
+    def terrain_inputs_previewed(self, foot, previewed, x_ref):
+        """terrain_inputs() between mpc_inputs_previewed() and the solve (srbdqp_terrain_inputs_previewed_f64): foot (B,N,12),
+        previewed (B,N,4) or None, x_ref (B,N,13); none is modified.
+        Returns dict(foot (B,N,12): every previewed point at the map's height under it, x_ref (B,N,13): column 5 of step k raised by the mean height of
+        foot[:, k], normals (B,N,12): the map's normal under every contact point of every step)."""
+        N = self.N
+        fo = np.array(foot, dtype=np.float64).reshape(-1, N, NU)
+        B = fo.shape[0]
+        pv = None if previewed is None else _as(np.asarray(previewed) != 0, np.uint8, (B, N, NC), "previewed")
+        xr = np.array(x_ref, dtype=np.float64).reshape(B, N, NX)
+        cn = np.empty((B, N, NU))
+        self._check(self._lib.srbdqp_terrain_inputs_previewed_f64(self._h, B, _p(fo), _p(pv), _p(xr), _p(cn)))
+        return dict(foot=fo, x_ref=xr, normals=cn)
+
+    def terrain_inputs_previewed_device(self, B, foot, previewed, x_ref, normals, stream=0):
+        """Device-pointer form of terrain_inputs_previewed(): raw addresses, foot and x_ref updated in place, launch enqueued behind `stream`, returns at once."""
+        v = lambda q: C.c_void_p(int(q)) if q else None
+        self._check(self._lib.srbdqp_terrain_inputs_previewed_device_f64(self._h, int(B), v(foot), v(previewed), v(x_ref), v(normals), v(stream)))
 
     def last_kernel_ms(self) -> float:
         return float(self._lib.srbdqp_last_kernel_ms(self._h))

@@ -162,7 +162,7 @@ int srbdqp_terrain_inputs_device_f64(srbdqp_handle* h, int64_t B, const double* 
  * Such a roll-out is refused (SRBDQP_E_INVALID before any launch, in the words of the handle's state "while a terrain is set") beside robot records, weights,
  * an external wrench or handle-level normals, on a live horizon, with rank-aware steps, at N = 24 and with a srbdqp_config.kernel that bars the general kernel:
  * no instantiation reads normals beside those.  Not modelled: ground reaction or sliding in the plant (the forces are the QP's), footholds predicted along the
- * horizon, per-robot map offsets, feet turned with yaw (srbdqp_fleet_advance_steered_* below turns them), terrain under the swing trajectory, fp32, ragged fleets. */
+ * horizon (srbdqp_fleet_rollout_previewed_* below previews them), per-robot map offsets, feet turned with yaw (srbdqp_fleet_advance_steered_* below turns them), terrain under the swing trajectory, fp32, ragged fleets. */
 
 /* T control steps of B robots: for t = 0 ... T - 1, srbdqp_mpc_inputs_device_f64 -> the solve, exactly the launches srbdqp_solve_batch_device_f64 makes
  * for this handle, with pcom from the inputs -> srbdqp_fleet_advance_device_f64, enqueued on `stream` without a host synchronisation (plain launches: no
@@ -283,8 +283,8 @@ int srbdqp_fleet_advance_steered_device_f64(srbdqp_handle* h, int64_t B, double*
  *   obs == NULL: the plain loop (w_est and w_log are ignored);  obs != NULL: the observed loop;  a terrain set on the handle: the terrain roll-out.
  * Refused: what the roll-out it becomes refuses; command NULL; command_steps outside {1, T}; in the host form a command that is not finite.  Chunks compose bit
  * for bit, a schedule with the two constant-command chunks it is made of included.
- * Not modelled: footholds previewed along the horizon (foot[b][k] stays the current points), a centrifugal term in the landing point, feet turned under a
- * standing robot, ragged fleets, fp32.  (A robot that is to be where its commands lead: srbdqp_fleet_rollout_tracked_* below.) */
+ * Not modelled: a centrifugal term in the landing point, feet turned under a standing robot, ragged fleets, fp32.  foot[b][k] stays the current points along
+ * the horizon; srbdqp_fleet_rollout_previewed_* below previews the footholds.  (A robot that is to be where its commands lead: srbdqp_fleet_rollout_tracked_* below.) */
 int srbdqp_fleet_rollout_steered_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
                                             int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
                                             double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
@@ -341,7 +341,7 @@ int srbdqp_mpc_inputs_tracked_device_f64(srbdqp_handle* h, int64_t B, const doub
  * Refused: what the roll-out it becomes refuses; pose NULL; bad track settings; in the host form a pose or a command that is not finite, by robot.  Chunks
  * compose bit for bit with pose carried by the caller, a schedule with its constant-command chunks included.
  * A robot that has fallen holds its state while its pose keeps moving on and keeps being clamped to within the bounds of that held state.
- * Not modelled: footholds previewed along the horizon, ragged fleets, fp32, a pose for the unsteered v_ref roll-out. */
+ * Not modelled: ragged fleets, fp32, a pose for the unsteered v_ref roll-out.  (Footholds previewed along the horizon: srbdqp_fleet_rollout_previewed_* below.) */
 int srbdqp_fleet_rollout_tracked_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
                                             int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
                                             double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
@@ -352,6 +352,75 @@ int srbdqp_fleet_rollout_tracked_f64(srbdqp_handle* h, int64_t B, int32_t T, dou
                                      double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
                                      const srbdqp_observer_settings* obs, double* w_est, double* w_log,
                                      const srbdqp_track_settings* trk, double* pose, double* pose_log);
+
+/* ---- a fleet that previews its footholds along the horizon.
+ *
+ * srbdqp_mpc_inputs_steered_* and ..._tracked_* write the contact schedule of the whole horizon but foot[b][k] = feet[b] at every k: a foot that lands inside
+ * the horizon is given its force at the old point.  The previewed call moves the plant's own touchdown rule along the horizon.  Every product and sum is one
+ * rounded fp64 operation in the order written, no fused multiply-add.  With P = period_steps, ds = double_support_steps, p0 the phase of step 0 in [0, 2 P)
+ * (the step index floor(stamp / dt + 1e-9) mod 2 P), flag_f(k) the stance flag of foot f -- the left (contacts 0, 1) or the right (contacts 2, 3) -- at step k:
+ *   touchdown  of f at step j: 1 <= j <= N - 1, flag_f(j - 1) == 0 and flag_f(j) == 1.  In closed form: the left foot lands where (p0 + j) mod 2 P == 0, the
+ *              right foot where (p0 + j) mod 2 P == P; the latest touchdown step j <= k is j = k - ((p0 + k) mod 2 P) for the left foot and
+ *              j = k - ((p0 + k + P) mod 2 P) for the right, a touchdown where j >= 1.  A standing robot, ds >= P and N = 1 have none; at most one foot lands at a step.
+ *   state      behind step j - 1, where the inputs call of that later step would compute `landing` if the robot sat on its own measured-state table:
+ *              j - 1 = 0: the measured x0: heading x0[2], position x0[3:5], velocity x0[9:11], the command's velocity v_w(psi0 + (wz 0) dt);
+ *              j - 1 >= 1: heading psi0 + (wz (j - 1)) dt, position p_{j-1} of srbdqp_mpc_inputs_steered_*'s table (the measured state's, in tracked calls
+ *              too), velocity v_w at that heading, which is the command's velocity as well: the 0.03 feedback term is an exact zero for finite inputs.
+ *   foothold   psi_L,j = heading + wz (T / 2);  (lx, ly) = landing_xy of srbdqp_mpc_inputs_steered_* at that state, side that of the foot that lands;
+ *              heel = (lx, ly) - foot_half_length (cos psi_L,j, sin psi_L,j),  toe = (lx, ly) + foot_half_length (cos psi_L,j, sin psi_L,j);  z = 0.
+ *   foot[b][k] for the contacts of f: heel and toe of the latest touchdown j <= k of f, the current points where there is none (a swing foot keeps its last
+ *              point until it lands, as before).
+ *   previewed  [B][N][4] uint8, may be NULL: 1 where foot[b][k] holds a previewed point for that contact.
+ * x_ref, pcom, contact, landing, landing_yaw and the pose are those of the steered or tracked call, bit for bit.  For a touchdown at j = 1 heel and toe are, bit for
+ * bit, what srbdqp_fleet_advance_steered_* writes from this call's landing and landing_yaw with the same foot_half_length, and psi_L,1 == landing_yaw: the
+ * foothold solve t assumes at horizon step 1 is the one solve t + 1 finds at step 0.  A command or a state that is not finite spoils the rows of that robot
+ * alone; no trip count, index or branch depends on a command, a state or a pose.
+ * srbdqp_kernel_name: mpc_inputs_previewed_f64, mpc_inputs_tracked_previewed_f64, terrain_inputs_previewed_f64. */
+typedef struct srbdqp_preview_settings {
+    int32_t struct_size;          /* = sizeof(srbdqp_preview_settings) */
+    int32_t reserved0;
+    double foot_half_length;      /* heel and toe lie this far behind and ahead of the landing point: the plant's srbdqp_fleet_settings value (0.085) */
+} srbdqp_preview_settings;
+
+/* The defaults above into *s; s->struct_size says how large the caller's struct is (checked before anything is written). */
+int srbdqp_preview_default_settings(srbdqp_preview_settings* s);
+
+/* The arguments of srbdqp_mpc_inputs_tracked_*, then prv and previewed.  trk == NULL: the steered form (pose is ignored); trk != NULL: the tracked form.
+ * Refused: what that form refuses; a wrong struct_size of prv; a foot_half_length that is not finite and positive. */
+int srbdqp_mpc_inputs_previewed_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
+                                    const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
+                                    double* landing, double* landing_yaw, const srbdqp_track_settings* trk, double* pose,
+                                    const srbdqp_preview_settings* prv, uint8_t* previewed);
+int srbdqp_mpc_inputs_previewed_device_f64(srbdqp_handle* h, int64_t B, const double* x0, const double* feet, const double* stamp, const double* command,
+                                           const uint8_t* standing, const srbdqp_gait* gait, double* x_ref, double* foot, uint8_t* contact, double* pcom,
+                                           double* landing, double* landing_yaw, const srbdqp_track_settings* trk, double* pose,
+                                           const srbdqp_preview_settings* prv, uint8_t* previewed, void* stream);
+
+/* srbdqp_terrain_inputs_* under footholds that differ from step to step: foot [B][N][12] in/out and previewed [B][N][4] (may be NULL: none) as
+ * srbdqp_mpc_inputs_previewed_* wrote them, x_ref [B][N][13] in/out, normals [B][N][12] out.  For every (b, k, i): normals[b][k][i] = S(xy of foot[b][k][i]).n; a
+ * previewed point gets z = S(own xy).z, the plant's touchdown rule, and any other point keeps its z; x_ref[b][k][5] += (((z0 + z1) + z2) + z3) 0.25 over the z of
+ * foot[b][k] after that write: the height reference follows the ground the robot will stand on at step k.  With previewed all zero the outputs are those of
+ * srbdqp_terrain_inputs_* on foot[b][0], bit for bit.  Without a map: SRBDQP_E_INVALID. */
+int srbdqp_terrain_inputs_previewed_f64(srbdqp_handle* h, int64_t B, double* foot, const uint8_t* previewed, double* x_ref, double* normals);
+int srbdqp_terrain_inputs_previewed_device_f64(srbdqp_handle* h, int64_t B, double* foot, const uint8_t* previewed, double* x_ref, double* normals, void* stream);
+
+/* The steered roll-out -- with trk != NULL the tracked one -- whose inputs call is srbdqp_mpc_inputs_previewed_device_f64 and which on a terrain enqueues
+ * srbdqp_terrain_inputs_previewed_device_f64 in place of srbdqp_terrain_inputs_device_f64, a previewed buffer joining the handle's roll-out allocation.  Nothing
+ * else in the loop changes: the solve, the plant, the gait and the observer are those of srbdqp_fleet_rollout_steered_*.  The arguments of the tracked
+ * roll-out, then prv; with trk == NULL pose and pose_log are ignored.
+ * Refused: what the roll-out it becomes refuses; bad preview settings; a prv->foot_half_length that differs from cfg->foot_half_length (the MPC would preview
+ * another foot than the plant puts down).  Chunks compose bit for bit.
+ * Not modelled: a preview for the v_ref roll-out, ragged fleets, fp32, feet turned under a standing robot, a centrifugal term in the landing point. */
+int srbdqp_fleet_rollout_previewed_device_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
+                                              int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                              double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                              const srbdqp_observer_settings* obs, double* w_est, double* w_log,
+                                              const srbdqp_track_settings* trk, double* pose, double* pose_log, const srbdqp_preview_settings* prv, void* stream);
+int srbdqp_fleet_rollout_previewed_f64(srbdqp_handle* h, int64_t B, int32_t T, double* x, double* feet, double* stamp, const double* command,
+                                       int32_t command_steps, const uint8_t* standing, const double* push, const srbdqp_fleet_settings* cfg, uint8_t* alive,
+                                       double* x_log, double* u0_log, double* feet_log, int32_t* status_log, int32_t* iters_log,
+                                       const srbdqp_observer_settings* obs, double* w_est, double* w_log,
+                                       const srbdqp_track_settings* trk, double* pose, double* pose_log, const srbdqp_preview_settings* prv);
 
 #ifdef __cplusplus
 }

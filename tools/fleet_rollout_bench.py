@@ -22,7 +22,10 @@ alone: time per launch and GB/s, with mpc_inputs measured the same way beside it
 under the default bounds --, the Python loop through mpc_inputs_tracked_device, and the tracked inputs kernel alone beside the other two: time per launch, GB/s
 and its share of a step; the fleet's distance from the path its commands lead along, beside what --steer leaves.  Implies --steer's commands.
 
-    python tools/fleet_rollout_bench.py [--robots 4096] [--steps 100] [--reps 5] [--terrain] [--observer] [--steer] [--track] [--kernel auto|wrench] [--out profiles/<name>.json]
+--preview: the previewed roll-out of --steer's or --track's fleet -- rollout_device(preview=True), the Python loop through
+mpc_inputs_previewed_device (and on a map terrain_inputs_previewed_device), and the previewed inputs kernel alone beside the others.
+
+    python tools/fleet_rollout_bench.py [--robots 4096] [--steps 100] [--reps 5] [--terrain] [--observer] [--steer] [--track] [--preview] [--kernel auto|wrench] [--out profiles/<name>.json]
 """
 import argparse
 import hashlib
@@ -55,12 +58,13 @@ def main():
     ap.add_argument("--observer", action="store_true")
     ap.add_argument("--steer", action="store_true")
     ap.add_argument("--track", action="store_true")
+    ap.add_argument("--preview", action="store_true")
     ap.add_argument("--kernel", choices=("auto", "wrench"), default="auto")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if a.terrain and a.observer:
         ap.error("--observer is flat ground: no roll-out reads normals beside a wrench")
-    a.steer = a.steer or a.track                                          # (a path needs commands)
+    a.steer = a.steer or a.track or a.preview                             # (a path and a preview need commands)
     import torch
     from g1_locomotion_amd import BatchMPC, _lib
     B, T, N, dt = a.robots, a.steps, 10, 0.04
@@ -86,6 +90,9 @@ def main():
     d_po, d_pl = (torch.empty((B, 3), dtype=torch.float64, device=dev), torch.empty((T, B, 3), dtype=torch.float64, device=dev)) if a.track else (None, None)
     if a.track:
         steer.update(track=True, pose=d_po.data_ptr(), pose_log=d_pl.data_ptr())
+    if a.preview:
+        steer.update(preview=True)
+    pvw = torch.empty((B, N, 4), dtype=torch.uint8, device=dev) if a.preview else None
     f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)
     xl, ul, fl = f64(T + 1, B, 13), f64(T, B, 12), f64(T + 1, B, 12)
     sl, il = torch.empty((T, B), dtype=torch.int32, device=dev), torch.empty((T, B), dtype=torch.int32, device=dev)
@@ -93,7 +100,7 @@ def main():
     ct = torch.empty((B, N, 4), dtype=torch.uint8, device=dev)
     st, it = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
     res = dict(robots=B, steps=T, horizon=N, reps=a.reps, terrain=bool(a.terrain), observer=bool(a.observer), steer=bool(a.steer), track=bool(a.track),
-               kernel_setting=a.kernel)
+               preview=bool(a.preview), kernel_setting=a.kernel)
     cn = f64(B, N, 12) if a.terrain else None
     we, wl, ew = (f64(B, 6), f64(T, B, 6), f64(B, N, 6)) if a.observer else (None, None, None)
     obs = dict(observer=True, w_est=we.data_ptr(), w_log=wl.data_ptr()) if a.observer else {}
@@ -134,7 +141,11 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for k in range(T):
-                if a.track:
+                if a.preview:
+                    eng.mpc_inputs_previewed_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), d_cm.data_ptr(), COM, xr.data_ptr(), fo.data_ptr(), ct.data_ptr(),
+                                                    pc.data_ptr(), landing=lp.data_ptr(), landing_yaw=ly.data_ptr(), pose=d_po.data_ptr() if a.track else 0,
+                                                    previewed=pvw.data_ptr())
+                elif a.track:
                     eng.mpc_inputs_tracked_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), d_cm.data_ptr(), d_po.data_ptr(), COM, xr.data_ptr(), fo.data_ptr(),
                                                   ct.data_ptr(), pc.data_ptr(), landing=lp.data_ptr(), landing_yaw=ly.data_ptr())
                 elif a.steer:
@@ -144,7 +155,10 @@ def main():
                     eng.mpc_inputs_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), d_v.data_ptr(), COM, xr.data_ptr(), fo.data_ptr(), ct.data_ptr(),
                                           pc.data_ptr(), landing=lp.data_ptr())
                 if a.terrain:
-                    eng.terrain_inputs_device(B, feet.data_ptr(), xr.data_ptr(), cn.data_ptr())
+                    if a.preview:
+                        eng.terrain_inputs_previewed_device(B, fo.data_ptr(), pvw.data_ptr(), xr.data_ptr(), cn.data_ptr())
+                    else:
+                        eng.terrain_inputs_device(B, feet.data_ptr(), xr.data_ptr(), cn.data_ptr())
                     eng.set_contact_normals(cn)
                 eng.solve_device(B, x.data_ptr(), xr.data_ptr(), fo.data_ptr(), ct.data_ptr(), u.data_ptr(), x_out=xo.data_ptr(), status=st.data_ptr(),
                                  iters=it.data_ptr(), pcom=pc.data_ptr())
@@ -219,6 +233,11 @@ def main():
             tracked = (("mpc_inputs_tracked", lambda: eng.mpc_inputs_tracked_device(B, xs.data_ptr(), fs.data_ptr(), ss.data_ptr(), d_cm.data_ptr(), d_po.data_ptr(), COM,
                                                                                     xr.data_ptr(), fo.data_ptr(), ct.data_ptr(), pc.data_ptr(), landing=lp.data_ptr(),
                                                                                     landing_yaw=ly.data_ptr())),) if a.track else ()
+            if a.preview:
+                tracked = (("mpc_inputs_previewed", lambda: eng.mpc_inputs_previewed_device(B, xs.data_ptr(), fs.data_ptr(), ss.data_ptr(), d_cm.data_ptr(), COM, xr.data_ptr(),
+                                                                                            fo.data_ptr(), ct.data_ptr(), pc.data_ptr(), landing=lp.data_ptr(),
+                                                                                            landing_yaw=ly.data_ptr(), pose=d_po.data_ptr() if a.track else 0,
+                                                                                            previewed=pvw.data_ptr())),) + tracked
             for name, launch in tracked + (("mpc_inputs_steered", lambda: eng.mpc_inputs_steered_device(B, xs.data_ptr(), fs.data_ptr(), ss.data_ptr(), d_cm.data_ptr(), COM, xr.data_ptr(),
                                                                                               fo.data_ptr(), ct.data_ptr(), pc.data_ptr(), landing=lp.data_ptr(), landing_yaw=ly.data_ptr())),
                                  ("mpc_inputs", lambda: eng.mpc_inputs_device(B, xs.data_ptr(), fs.data_ptr(), ss.data_ptr(), d_v.data_ptr(), COM, xr.data_ptr(), fo.data_ptr(),
@@ -233,8 +252,10 @@ def main():
                     ts.append((time.perf_counter() - t0) / T)
                 per[name] = float(np.median(ts))
                 res[name + "_us_per_launch"] = per[name] * 1e6
-                res[name + "_gb_per_s"] = B * (INPUTS_BYTES + (48 if name == "mpc_inputs_tracked" else 0) + N * (13 + 12 + 3) * 8 + N * 4) / per[name] / 1e9
+                res[name + "_gb_per_s"] = B * (INPUTS_BYTES + (48 if name == "mpc_inputs_tracked" or (name == "mpc_inputs_previewed" and a.track) else 0) + (N * 4 if name == "mpc_inputs_previewed" else 0) + N * (13 + 12 + 3) * 8 + N * 4) / per[name] / 1e9
             res["mpc_inputs_steered_share_of_a_rollout_step"] = per["mpc_inputs_steered"] / (t_call / T)
+            if a.preview:
+                res["mpc_inputs_previewed_share_of_a_rollout_step"] = per["mpc_inputs_previewed"] / (t_call / T)
             if a.track:
                 res["mpc_inputs_tracked_share_of_a_rollout_step"] = per["mpc_inputs_tracked"] / (t_call / T)
             res["final_yaw_rms_error_rad"] = float((xl[T, :, 2] - xl[0, :, 2] - d_cm[:, 2] * (T * dt)).pow(2).mean().sqrt().item())
