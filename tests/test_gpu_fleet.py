@@ -12,7 +12,7 @@ import c_oracle  # noqa: F401
 import cascade_oracle as co
 import srbd_oracle as orc
 import fleet_twin as ft
-from fleet_loop import _bits, _device_loop, _stamps
+from fleet_loop import _bits, _stamps, crowd, device_loop
 
 pytestmark = pytest.mark.gpu
 N, DT, T = 10, 0.04, 50
@@ -42,18 +42,6 @@ def gpu(eng):
     """... and on the engine, through host buffers."""
     f = ft.fleet()
     return eng.rollout(f["x"], f["feet"], f["stamp"], f["v_ref"], T, ft.COM, standing=f["standing"], push=ft.fleet_push(T, 6))
-
-
-def _crowd(B, seed, steps):
-    """B robots around the nominal stance: random commands, a few standing, stamps anywhere in the gait period, pushes of up to 30 N / 3 N m now and then."""
-    rng = np.random.default_rng(seed)
-    x = np.zeros((B, 13)); x[:, 3:6] = ft.COM + rng.normal(size=(B, 3)) * 0.005; x[:, 0:2] = rng.normal(size=(B, 2)) * 0.02; x[:, 12] = -9.80665
-    feet = np.tile(ft.FEET.reshape(12), (B, 1))
-    stamp = DT * rng.integers(0, 24, B).astype(np.float64)
-    v_ref = np.where(rng.random((B, 1)) < 0.3, 0.0, rng.uniform(-0.2, 0.3, (B, 2)) * np.array([1.0, 0.4]))
-    standing = (rng.random(B) < 0.2).astype(np.uint8)
-    push = np.where(rng.random((steps, B, 1)) < 0.1, rng.uniform(-1.0, 1.0, (steps, B, 6)) * np.array([3.0, 3.0, 0.3, 30.0, 30.0, 30.0]), 0.0)
-    return dict(x=x, feet=feet, stamp=stamp, v_ref=v_ref, standing=standing, push=push)
 
 
 def test_fleet_advance_against_the_twin(eng, twin):
@@ -105,9 +93,9 @@ def test_the_loop_is_the_public_calls(B, defer):
     import torch  # noqa: F401
     from g1_locomotion_amd import BatchMPC, _lib
     steps = 14
-    c = _crowd(B, 40 + B, steps)
+    c = crowd("v_ref", B, 40 + B, steps)
     with BatchMPC(horizon=N, **(dict(flags=_lib.FLAG_DEFER_TAIL) if defer else {})) as e:
-        call, loop, _ = _device_loop(e, c, B, steps, defer=defer)
+        call, loop, _ = device_loop(e, c, B, steps, defer=defer)
     for k in call:
         assert np.array_equal(_bits(call[k]), _bits(loop[k])), k
     assert np.array_equal(_bits(call["x_log"][-1]), _bits(call["x"])) and np.array_equal(_bits(call["x_log"][0]), _bits(c["x"]))
@@ -119,7 +107,7 @@ def test_the_loop_is_the_public_calls(B, defer):
 
 def test_chunks_compose(eng):
     """rollout(9) and rollout(16) from where it ended = rollout(25), bit for bit."""
-    c = _crowd(21, 7, 25)
+    c = crowd("v_ref", 21, 7, 25)
     a = eng.rollout(c["x"], c["feet"], c["stamp"], c["v_ref"], 9, ft.COM, standing=c["standing"], push=c["push"][:9])
     b = eng.rollout(a["x"][-1], a["feet"][-1], a["stamp"], c["v_ref"], 16, ft.COM, standing=c["standing"], push=c["push"][9:], alive=a["alive"])
     w = eng.rollout(c["x"], c["feet"], c["stamp"], c["v_ref"], 25, ft.COM, standing=c["standing"], push=c["push"])
@@ -206,6 +194,7 @@ def test_fallen_non_finite_and_refusals(eng):
         try:
             x, feet, stamp, v = up(f["x"]), up(f["feet"]), up(f["stamp"]), up(f["v_ref"])
             xl = torch.full((steps + 1, 6, 13), -7.0, dtype=torch.float64, device=dev)
+            torch.cuda.synchronize()                                 # (fleet_loop.py's stream rule)
             with pytest.raises(SrbdqpError, match="srbdqp_" + setter):
                 eng.rollout_device(6, steps, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, x_log=xl.data_ptr())
             eng.synchronize()

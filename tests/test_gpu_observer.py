@@ -11,7 +11,7 @@ import pytest
 import c_oracle  # noqa: F401
 import cascade_oracle as co
 import fleet_twin as ft
-from fleet_loop import _bits, _device_loop, _stamps
+from fleet_loop import _bits, _stamps, crowd, device_loop
 import observer_twin as ot
 import side_inputs as si
 import srbd_oracle as orc
@@ -98,20 +98,6 @@ def test_the_kernel_against_the_twin(arrays, horizon):
     print("wrench_observer against the twin, N =", horizon, "worst |w_est - twin|", worst)
 
 
-def _crowd(B, seed, steps):
-    """B robots around the nominal stance: random commands, a few standing, stamps anywhere in the gait period, under a sustained push from step 2 on."""
-    rng = np.random.default_rng(seed)
-    x = np.zeros((B, 13)); x[:, 3:6] = ft.COM + rng.normal(size=(B, 3)) * 0.005; x[:, 0:2] = rng.normal(size=(B, 2)) * 0.02; x[:, 12] = -9.80665
-    feet = np.tile(ft.FEET.reshape(12), (B, 1))
-    stamp = DT * rng.integers(0, 24, B).astype(np.float64)
-    v_ref = np.where(rng.random((B, 1)) < 0.3, 0.0, rng.uniform(-0.2, 0.3, (B, 2)) * np.array([1.0, 0.4]))
-    standing = (rng.random(B) < 0.2).astype(np.uint8)
-    push = np.zeros((steps, B, 6))
-    push[2:] = rng.uniform(-1.0, 1.0, (1, B, 6)) * np.array([1.0, 1.0, 0.1, 20.0, 20.0, 5.0])
-    w0 = rng.uniform(-1.0, 1.0, (B, 6)) * np.array([0.5, 0.5, 0.05, 5.0, 5.0, 2.0])
-    return dict(x=x, feet=feet, stamp=stamp, v_ref=v_ref, standing=standing, push=push, w0=w0)
-
-
 OBS = dict(gain=0.5, horizon_decay=0.9)
 
 
@@ -122,9 +108,9 @@ def test_the_loop_is_the_public_calls(B, defer):
     import torch  # noqa: F401
     from g1_locomotion_amd import BatchMPC, _lib
     steps = 8
-    c = _crowd(B, 60 + B, steps)
+    c = crowd("v_ref", B, 60 + B, steps, push="sustained")
     with BatchMPC(horizon=N, **(dict(flags=_lib.FLAG_DEFER_TAIL) if defer else {})) as e:
-        call, loop, name = _device_loop(e, c, B, steps, "observer", defer=defer, observer=OBS)
+        call, loop, name = device_loop(e, c, B, steps, "observer", defer=defer, observer=OBS)
     assert name == "wrench_observer_f64"
     for k in call:
         assert np.array_equal(_bits(call[k]), _bits(loop[k])), k
@@ -138,7 +124,7 @@ def test_chunks_compose(eng):
     """5 steps and 7 from where they ended, w_est carried = 12, bit for bit; the same 12 steps through the device call without logs -- the observer reads the ring --
     end in the same x, feet and w_est."""
     import torch
-    c = _crowd(21, 9, 12)
+    c = crowd("v_ref", 21, 9, 12, push="sustained")
     kw = dict(standing=c["standing"], observer=OBS)
     a = eng.rollout(c["x"], c["feet"], c["stamp"], c["v_ref"], 5, ft.COM, push=c["push"][:5], w_est=c["w0"], **kw)
     b = eng.rollout(a["x"][-1], a["feet"][-1], a["stamp"], c["v_ref"], 7, ft.COM, push=c["push"][5:], alive=a["alive"], w_est=a["w_est"], **kw)
@@ -152,6 +138,7 @@ def test_chunks_compose(eng):
     dev = torch.device("cuda", 0)
     up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
     x, feet, stamp, v, sd, pu, we = up(c["x"]), up(c["feet"]), up(c["stamp"]), up(c["v_ref"]), up(c["standing"]), up(c["push"]), up(c["w0"])
+    torch.cuda.synchronize()                                                     # (fleet_loop.py's stream rule)
     eng.rollout_device(21, 12, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, standing=sd.data_ptr(), push=pu.data_ptr(), observer=OBS,
                        w_est=we.data_ptr())
     eng.synchronize()
@@ -272,6 +259,7 @@ def test_refusals_a_nan_robot_and_no_observer(eng):
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     x, feet, stamp, v = up(f["x"]), up(f["feet"]), up(f["stamp"]), up(f["v_ref"])
     xl = torch.full((steps + 1, 6, 13), -7.0, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()                                                     # (fleet_loop.py's stream rule)
     with pytest.raises(SrbdqpError, match="w_est is NULL"):
         eng.rollout_device(6, steps, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, x_log=xl.data_ptr(), observer=True)
     eng.synchronize()

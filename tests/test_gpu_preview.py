@@ -7,7 +7,6 @@ of a previewed point: 1e-12 absolute -- the device's sin / cos against NumPy's a
 the heights are bit for bit and the normals within 1e-15 (test_gpu_terrain.py).  Free-running trajectories: 1e-4 with every iteration count equal to the
 twin's (test_gpu_steer.py's bar at 50 steps; here 14).  Device against device -- the loop against the public calls, chunks, the step-1 property -- bit for bit."""
 import ctypes as C
-import time
 
 import numpy as np
 import pytest
@@ -15,8 +14,7 @@ import pytest
 import c_oracle  # noqa: F401
 import srbd_oracle as orc
 import fleet_twin as ft
-from fleet_loop import _bits
-import observer_twin as ot
+from fleet_loop import OBS, _bits, crowd, device_loop, direct_rollout, engine, inputs_device
 import preview_twin as pvt
 import steer_twin as stw
 import terrain_twin as tt
@@ -24,63 +22,7 @@ import track_twin as ttw
 
 pytestmark = pytest.mark.gpu
 N, DT = 10, 0.04
-OBS = dict(gain=0.5, horizon_decay=0.9, torque_max=50.0, force_max=200.0)
 OUTS = ("x_ref", "foot", "contact", "pcom", "landing", "landing_yaw")
-
-
-def _crowd(B, seed, P=6):
-    """B robots around the nominal stance at any heading, commands of up to (0.3, 0.1) m/s and 1 rad/s, some of them zero or turning on the spot, some robots
-    standing, stamps staggered over every phase of the gait and some of them negative, a pose each inside the default bounds."""
-    rng = np.random.default_rng(seed)
-    x = np.zeros((B, 13)); x[:, 3:6] = ft.COM + rng.normal(size=(B, 3)) * 0.005; x[:, 0:2] = rng.normal(size=(B, 2)) * 0.02; x[:, 12] = -9.80665
-    x[:, 2] = rng.uniform(-3.0, 3.0, B)
-    x[:, 9:11] = rng.normal(size=(B, 2)) * 0.1
-    feet = np.tile(ft.FEET.reshape(12), (B, 1)) + rng.normal(size=(B, 12)) * 0.01
-    stamp = DT * ((np.arange(B) * 5) % (2 * P)).astype(np.float64) - np.where(np.arange(B) % 3 == 0, 2 * P * DT * 4, 0.0)
-    cmd = rng.uniform(-1.0, 1.0, (B, 3)) * np.array([0.3, 0.1, 1.0])
-    kind = np.arange(B) % 7
-    cmd[kind == 0] = 0.0
-    cmd[kind == 1, 0:2] = 0.0
-    cmd[kind == 2, 2] = 0.0
-    standing = (np.arange(B) % 11 == 4).astype(np.uint8)
-    pose = ttw.start_pose(x) + rng.uniform(-1.0, 1.0, (B, 3)) * np.array([0.05, 0.05, 0.25])
-    return dict(x=x, feet=feet, stamp=stamp, command=cmd, standing=standing, pose=pose)
-
-
-def _engine(horizon, flags=0):
-    from g1_locomotion_amd import BatchMPC, _lib
-    flags |= 0 if horizon in (4, 8, 10, 12, 16, 20, 24) else _lib.FLAG_ANY_HORIZON
-    return BatchMPC(horizon=horizon, **(dict(flags=flags) if flags else {}))
-
-
-def _inputs_device(e, c, horizon, tracked, preview=True, **gait):
-    """mpc_inputs_previewed_device (preview False: the steered or tracked device call) on device copies of the crowd -> a dict of host arrays.  The device forms
-    take what the host forms refuse: commands that are not finite."""
-    import torch
-    dev = torch.device("cuda", 0)
-    B = c["x"].shape[0]
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    f64 = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device=dev)
-    x, feet, stamp, cmd, sd, pose = up(c["x"]), up(c["feet"]), up(c["stamp"]), up(c["command"]), up(c["standing"]), up(c["pose"])
-    xr, fo, pc, lp, ly = f64(B, horizon, 13), f64(B, horizon, 12), f64(B, horizon, 3), f64(B, 3), f64(B)
-    ct = torch.full((B, horizon, 4), 9, dtype=torch.uint8, device=dev)
-    pv = torch.full((B, horizon, 4), 9, dtype=torch.uint8, device=dev)
-    out = dict(x_ref=xr, foot=fo, contact=ct, pcom=pc, landing=lp, landing_yaw=ly)
-    args = (B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), cmd.data_ptr())
-    outs = (ft.COM, xr.data_ptr(), fo.data_ptr(), ct.data_ptr(), pc.data_ptr())
-    kw = dict(landing=lp.data_ptr(), landing_yaw=ly.data_ptr(), standing=sd.data_ptr(), **gait)
-    torch.cuda.synchronize()                                      # (the fills above run on torch's stream, the call on the engine's own)
-    if preview:
-        e.mpc_inputs_previewed_device(*args, *outs, pose=pose.data_ptr() if tracked else 0, previewed=pv.data_ptr(), **kw)
-        out["previewed"] = pv
-    elif tracked:
-        e.mpc_inputs_tracked_device(*args, pose.data_ptr(), *outs, **kw)
-    else:
-        e.mpc_inputs_steered_device(*args, *outs, **kw)
-    if tracked:
-        out["pose"] = pose
-    e.synchronize()
-    return {k: a.cpu().numpy() for k, a in out.items()}
 
 
 def _foot_against_the_twin(got, want, what):
@@ -104,13 +46,14 @@ def test_previewed_inputs_against_the_twin(horizon, P, ds):
     output but foot against the device's own steered or tracked call, bit for bit; a command that is not finite spoils its robot's rows and no other's."""
     gait = dict(period_steps=P, double_support_steps=ds)
     worst, landed = 0.0, 0
-    with _engine(horizon) as e:
+    with engine(horizon) as e:
         for B in (1, 33, 65):
-            c = _crowd(B, 500 + 10 * horizon + B, P)
-            for tracked in (False, True):
-                got = _inputs_device(e, c, horizon, tracked, **gait)
+            c = crowd("preview", B, 500 + 10 * horizon + B, P=P)
+            for flavour in ("steered", "tracked"):
+                tracked = flavour == "tracked"
+                got = inputs_device(e, c, horizon, flavour, preview=True, **gait)
                 assert e.kernel_name() == ("mpc_inputs_tracked_previewed_f64" if tracked else "mpc_inputs_previewed_f64")
-                plain = _inputs_device(e, c, horizon, tracked, preview=False, **gait)
+                plain = inputs_device(e, c, horizon, flavour, **gait)
                 want = pvt.mpc_inputs(c["x"], c["feet"], c["stamp"], c["command"], ft.COM, horizon, DT, pose=c["pose"] if tracked else None, standing=c["standing"],
                                       **gait)
                 worst = max(worst, _foot_against_the_twin(got, want, (B, tracked)))
@@ -129,7 +72,7 @@ def test_previewed_inputs_against_the_twin(horizon, P, ds):
                 # a command that is not finite: its robot's previewed points are not numbers, every other robot's rows are what they were
                 bad = {k: v.copy() for k, v in c.items()}
                 bad["command"][5, 2] = np.nan; bad["command"][32, 0] = np.inf
-                spoiled = _inputs_device(e, bad, horizon, tracked, **gait)
+                spoiled = inputs_device(e, bad, horizon, flavour, preview=True, **gait)
                 rest = np.setdiff1d(np.arange(B), [5, 32])
                 for k in got:
                     assert np.array_equal(_bits(spoiled[k][rest]), _bits(got[k][rest])), (k, B, tracked)
@@ -140,13 +83,13 @@ def test_previewed_inputs_against_the_twin(horizon, P, ds):
                     assert not np.isfinite(xy).any() or not on.any(), b
                     assert np.array_equal(_bits(spoiled["foot"][b][~on]), _bits(got["foot"][b][~on]))
         # the host form against the device form
-        c = _crowd(33, 77, P)
+        c = crowd("preview", 33, 77, P=P)
         a = e.mpc_inputs_previewed(c["x"], c["feet"], c["stamp"], c["command"], ft.COM, standing=c["standing"], **gait)
-        b = _inputs_device(e, c, horizon, False, **gait)
+        b = inputs_device(e, c, horizon, "steered", preview=True, **gait)
         for k in b:
             assert np.array_equal(_bits(a[k]), _bits(b[k])), k
         a = e.mpc_inputs_previewed(c["x"], c["feet"], c["stamp"], c["command"], ft.COM, pose=c["pose"], standing=c["standing"], **gait)
-        b = _inputs_device(e, c, horizon, True, **gait)
+        b = inputs_device(e, c, horizon, "tracked", preview=True, **gait)
         for k in b:
             assert np.array_equal(_bits(a[k]), _bits(b[k])), k
     print("previewed inputs against the twin, (N, P, ds) =", (horizon, P, ds), "heel / toe", worst, "previewed contacts", landed)
@@ -159,9 +102,9 @@ def test_host_form_refusals_leave_the_outputs_untouched():
     fleet settings' before any launch: every output array keeps what it held."""
     from g1_locomotion_amd import _lib, SrbdqpError
     B, T = 6, 3
-    c = _crowd(B, 3)
+    c = crowd("preview", B, 3)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    with _engine(N) as e:
+    with engine(N) as e:
         lib, h = e._lib, e._h
         g = e._gait_struct(6, 1, ft.COM, 0.0645)
         outs = [np.full(s, 7.0) for s in ((B, N, 13), (B, N, 12))] + [np.full((B, N, 4), 7, np.uint8), np.full((B, N, 3), 7.0), np.full((B, 3), 7.0), np.full(B, 7.0)]
@@ -201,33 +144,6 @@ def test_host_form_refusals_leave_the_outputs_untouched():
             e.rollout(c["x"], c["feet"], c["stamp"], c["command"][:, 0:2], T, ft.COM, preview=True)
 
 
-def test_the_tile_loop_takes_its_second_trip():
-    """test_gpu_tile_loops.py's method on the previewed instantiations, whose launcher caps the grid at 256 * 32 workgroups: a 77-robot crowd repeated to 262,189
-    robots = cap * 32 + 32 + 13 on an engine of horizon 4, robot b being robot b mod 77.  Every output equals the 77-robot call's gathered by the same index,
-    bit for bit, steered and tracked."""
-    t0 = time.perf_counter()
-    cap, tile, Nh = 256 * 32, 32, 4
-    B = cap * tile + tile + 13
-    assert B == 262189 and B // tile > cap and -(-B // tile) == cap + 2 and B % tile == 13
-    c = _crowd(77, 900)
-    c["command"][50, 2] = np.nan
-    idx = np.arange(B) % 77
-    big = {k: np.take(v, idx, axis=0) for k, v in c.items()}
-    with _engine(Nh) as e:
-        for tracked in (False, True):
-            small = _inputs_device(e, c, Nh, tracked)
-            assert small["previewed"].any() and small["contact"].min() == 0 and np.isnan(small["foot"]).any()
-            large = _inputs_device(e, big, Nh, tracked)
-            for k, v in small.items():
-                want = np.take(v, idx, axis=0)
-                assert large[k].shape == want.shape and np.array_equal(_bits(large[k]), _bits(want)), (k, tracked)
-                del want
-            del large
-    import torch
-    torch.cuda.empty_cache()                                      # (the gigabyte of cached blocks goes back: the tests behind this one find the allocator as before)
-    print(f"mpc_inputs_previewed, second trip: B = {B} robots = {-(-B // tile)} tiles of {tile} on {cap} workgroups, {time.perf_counter() - t0:.1f} s")
-
-
 def test_terrain_inputs_previewed_against_the_twin():
     """B = 33 (a tile and one robot) on test_gpu_terrain.py's rough 17 x 9 map: foot's heights and x_ref bit for bit, normals within 1e-15; with previewed all
     zero, or NULL, the outputs are srbdqp_terrain_inputs_*'s on foot[:, 0]; host and device forms agree; without a map the call is refused."""
@@ -235,13 +151,13 @@ def test_terrain_inputs_previewed_against_the_twin():
     from g1_locomotion_amd import SrbdqpError
     m = tt.rough(17, 9, seed=11, cell=0.25, origin=(-1.0, -1.0))
     B = 33
-    c = _crowd(B, 41)
+    c = crowd("preview", B, 41)
     c["x"][:, 3] += np.linspace(-0.4, 1.6, B); c["feet"][:, 0::3] += np.linspace(-0.4, 1.6, B)[:, None]
     c["feet"].reshape(B, 4, 3)[:, :, 2] = tt.sample(m, c["feet"].reshape(B * 4, 3)[:, 0:2])[0].reshape(B, 4) + 0.01       # (the z handed in need not lie on the map)
     want_in = pvt.mpc_inputs(c["x"], c["feet"], c["stamp"], c["command"], ft.COM, N, DT, standing=c["standing"])
     x_ref = np.random.default_rng(B).normal(size=(B, N, 13))
     dev = torch.device("cuda", 0)
-    with _engine(N) as e:
+    with engine(N) as e:
         with pytest.raises(SrbdqpError, match="no terrain is set"):
             e.terrain_inputs_previewed(want_in["foot"], want_in["previewed"], x_ref)
         e.set_terrain(**m.args())
@@ -295,56 +211,6 @@ def _rollout(e, f, steps, mode, **kw):
     return e.rollout(f["x"], f["feet"], f["stamp"], None, steps, ft.COM, standing=f["standing"], command=f["command"], preview=True, **more, **kw)
 
 
-def _public_calls(e, f, steps, mode):
-    """The same steps driven from here through the public device calls: mpc_inputs_previewed_device -> (terrain_inputs_previewed_device + the normals set on the
-    engine) -> solve_device -> fleet_advance_device(landing_yaw=) -> (wrench_observer_device) -> a dict of host logs."""
-    import torch
-    dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    f64 = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device=dev)
-    B = f["x"].shape[0]
-    x, feet, stamp, sd, v = up(f["x"]), up(f["feet"]), up(f["stamp"]), up(f["standing"]), up(f["command"])
-    pose, al, w = up(ttw.start_pose(f["x"])), up(np.ones(B, np.uint8)), up(np.zeros((B, 6)))
-    xr, fo, pc, lp, ly, cn = f64(B, N, 13), f64(B, N, 12), f64(B, N, 3), f64(B, 3), f64(B), f64(B, N, 12)
-    ct, pv = torch.zeros((B, N, 4), dtype=torch.uint8, device=dev), torch.zeros((B, N, 4), dtype=torch.uint8, device=dev)
-    u, xo = f64(B, N, 12), f64(B, N + 1, 13)
-    st, it = torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev)
-    xs, fs, us, ss, its = [x.clone()], [feet.clone()], [], [], []
-    obs = mode == "observer"
-    if obs:
-        ew = up(ot.horizon(np.zeros((B, 6)), N, OBS["horizon_decay"]))
-        e.set_external_wrench(ew)
-    try:
-        for k in range(steps):
-            torch.cuda.synchronize()                              # (the copies and fills run on torch's stream, the calls on the engine's own)
-            e.mpc_inputs_previewed_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, xr.data_ptr(), fo.data_ptr(), ct.data_ptr(),
-                                          pc.data_ptr(), landing=lp.data_ptr(), landing_yaw=ly.data_ptr(), standing=sd.data_ptr(),
-                                          pose=pose.data_ptr() if mode == "track" else 0, previewed=pv.data_ptr())
-            if mode == "terrain":
-                e.terrain_inputs_previewed_device(B, fo.data_ptr(), pv.data_ptr(), xr.data_ptr(), cn.data_ptr())
-                e.set_contact_normals(cn)
-            e.solve_device(B, x.data_ptr(), xr.data_ptr(), fo.data_ptr(), ct.data_ptr(), u.data_ptr(), x_out=xo.data_ptr(), status=st.data_ptr(), iters=it.data_ptr(),
-                           pcom=pc.data_ptr())
-            e.synchronize()
-            xp, fp = x.clone(), feet.clone()
-            torch.cuda.synchronize()
-            e.fleet_advance_device(B, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), u.data_ptr(), lp.data_ptr(), u0_stride=12 * N, standing=sd.data_ptr(),
-                                   alive=al.data_ptr(), landing_yaw=ly.data_ptr())
-            if obs:
-                e.wrench_observer_device(B, xp.data_ptr(), x.data_ptr(), fp.data_ptr(), u.data_ptr(), w.data_ptr(), ew=ew.data_ptr(), u0_stride=12 * N,
-                                         alive=al.data_ptr(), **OBS)
-            e.synchronize()
-            xs.append(x.clone()); fs.append(feet.clone()); us.append(u[:, 0].clone()); ss.append(st.clone()); its.append(it.clone())
-    finally:
-        e.synchronize()
-        if mode == "terrain":
-            e.set_contact_normals(None)
-        if obs:
-            e.set_external_wrench(None)
-    logs = dict(x=torch.stack(xs), feet=torch.stack(fs), u0=torch.stack(us), status=torch.stack(ss), iters=torch.stack(its), stamp=stamp, alive=al)
-    return {k: a.cpu().numpy() for k, a in logs.items()}
-
-
 @pytest.mark.parametrize("mode", ["flat", "terrain", "observer", "track"])
 def test_the_previewed_rollout(mode):
     """The 6-robot steering fleet, N = 10, T = 14 (two touchdowns per foot) -- on flat ground, on a slope, with the observer, tracked: rollout(preview=True)
@@ -352,13 +218,15 @@ def test_the_previewed_rollout(mode):
     on the logged state of step t puts foot[:, 1] of the robots whose foot lands in period t where feet_log[t + 1] has it, bit for bit (on the slope with z)."""
     f = _fleet(mode)
     B = f["x"].shape[0]
-    with _engine(N) as e:
+    with engine(N) as e:
         if mode == "terrain":
             e.set_terrain(**_slope().args())
         whole = _rollout(e, f, T14, mode)
-        loop = _public_calls(e, f, T14, mode)
-        for k in loop:
-            assert np.array_equal(_bits(whole[k]), _bits(loop[k])), k
+        # (the loop from where the host form starts: the measured pose, no estimate, every robot alive, no pushes)
+        _, loop, _ = device_loop(e, dict(f, pose=ttw.start_pose(f["x"]), w0=np.zeros((B, 6))), B, T14, "flat" if mode == "track" else mode, observer=OBS,
+                                 track=True if mode == "track" else None, preview=True, dead=False, call=False)
+        for k, lk in dict(x="x_log", feet="feet_log", u0="u0_log", status="status_log", iters="iters_log", stamp="stamp", alive="alive").items():
+            assert np.array_equal(_bits(whole[k]), _bits(loop[lk])), k
         assert whole["alive"].tolist() == [1] * B and (whole["status"] == 1).mean() > 0.9
         # chunks
         a = _rollout(e, f, 7, mode)
@@ -394,7 +262,7 @@ def test_free_running_against_the_twin(track):
     counts equal, states within 1e-4 -- test_gpu_steer.py's bounds for its roll-outs."""
     f = stw.fleet()
     want = pvt.rollout(orc.default_params(N), f["x"], f["feet"], f["stamp"], f["command"], T14, ft.COM, track=track, standing=f["standing"], solver="c")
-    with _engine(N) as e:
+    with engine(N) as e:
         got = _rollout(e, f, T14, "track" if track else "flat")
     err = np.abs(got["x"] - want["x"]).max(axis=(0, 2))
     efeet = np.abs(got["feet"] - want["feet"]).max()
@@ -411,26 +279,12 @@ def test_preview_off_is_the_rollout_as_it_was():
     before and after a previewed roll-out has run on the engine (which re-carves the roll-out allocation): bit for bit, twice."""
     steps, B = T14, 6
     f = stw.fleet()
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
-
-    def direct(e, tracked):
-        x, feet, stamp, al = f["x"].copy(), f["feet"].copy(), f["stamp"].copy(), np.ones(B, np.uint8)
-        xl, ul, fl = np.empty((steps + 1, B, 13)), np.empty((steps, B, 12)), np.empty((steps + 1, B, 12))
-        sl, il = np.empty((steps, B), np.int32), np.empty((steps, B), np.int32)
-        s = e.fleet_settings(ft.COM)
-        head = (e._h, B, steps, p(x), p(feet), p(stamp), p(f["command"]), 1, p(f["standing"]), None, C.byref(s), p(al), p(xl), p(ul), p(fl), p(sl), p(il), None, None, None)
-        if tracked:
-            k, pose, pl = e.track_settings(), ttw.start_pose(f["x"]), np.empty((steps, B, 3))
-            assert e._lib.srbdqp_fleet_rollout_tracked_f64(*head, C.byref(k), p(pose), p(pl)) == 0
-        else:
-            assert e._lib.srbdqp_fleet_rollout_steered_f64(*head) == 0
-        return dict(x=xl, u0=ul, feet=fl, status=sl, iters=il, alive=al, stamp=stamp)
-
+    f["pose"] = ttw.start_pose(f["x"])                            # (where rollout(track=True) starts without a pose)
     first = {}
-    with _engine(N) as e:
+    with engine(N) as e:
         for round_ in range(2):
             for tracked in (False, True):
-                want = direct(e, tracked)
+                want = direct_rollout(e, "srbdqp_fleet_rollout_tracked_f64" if tracked else "srbdqp_fleet_rollout_steered_f64", f, steps, f["command"])
                 got = e.rollout(f["x"], f["feet"], f["stamp"], None, steps, ft.COM, standing=f["standing"], command=f["command"], track=True if tracked else None,
                                 preview=None)
                 for k, v in want.items():

@@ -12,7 +12,7 @@ import pytest
 import c_oracle  # noqa: F401
 import srbd_oracle as orc
 import fleet_twin as ft
-from fleet_loop import _bits, _device_loop
+from fleet_loop import OBS, _bits, crowd, device_loop, direct_rollout, engine, rollout_device_against_host, turned_feet
 import steer_twin as stw
 import terrain_twin as tt
 
@@ -31,45 +31,11 @@ def eng():
     e.close()
 
 
-def _crowd(B, seed, steps=0):
-    """B robots around the nominal stance at any heading: commands of up to (0.3, 0.1) m/s and 1 rad/s, some of them zero, some turning on the spot, a few robots
-    standing, stamps over every phase of the gait, pushes now and then."""
-    rng = np.random.default_rng(seed)
-    x = np.zeros((B, 13)); x[:, 3:6] = ft.COM + rng.normal(size=(B, 3)) * 0.005; x[:, 0:2] = rng.normal(size=(B, 2)) * 0.02; x[:, 12] = -9.80665
-    x[:, 2] = rng.uniform(-3.0, 3.0, B)
-    feet = np.tile(ft.FEET.reshape(12), (B, 1))
-    stamp = DT * ((np.arange(B) * 5) % 12).astype(np.float64)
-    cmd = rng.uniform(-1.0, 1.0, (B, 3)) * np.array([0.3, 0.1, 1.0])
-    kind = np.arange(B) % 7
-    cmd[kind == 0] = 0.0
-    cmd[kind == 1, 0:2] = 0.0
-    cmd[kind == 2, 2] = 0.0
-    standing = (rng.random(B) < 0.15).astype(np.uint8)
-    push = np.where(rng.random((steps, B, 1)) < 0.1, rng.uniform(-1.0, 1.0, (steps, B, 6)) * np.array([3.0, 3.0, 0.3, 30.0, 30.0, 30.0]), 0.0)
-    return dict(x=x, feet=feet, stamp=stamp, command=cmd, standing=standing, push=push)
-
-
-def _turned_feet(c):
-    """The crowd's feet under its robots: the nominal stance turned to every robot's heading about its CoM (so that a roll-out starts from a stance it can hold)."""
-    B = c["x"].shape[0]
-    rel = (ft.FEET - np.array([ft.COM[0], ft.COM[1], 0.0]))[None, :, :]
-    s, co_ = np.sin(c["x"][:, 2])[:, None], np.cos(c["x"][:, 2])[:, None]
-    f = np.zeros((B, 4, 3))
-    f[:, :, 0] = c["x"][:, None, 3] + co_ * rel[:, :, 0] - s * rel[:, :, 1]
-    f[:, :, 1] = c["x"][:, None, 4] + s * rel[:, :, 0] + co_ * rel[:, :, 1]
-    return f.reshape(B, 12)
-
-
-def _inputs_case(horizon):
-    from g1_locomotion_amd import BatchMPC, _lib
-    return BatchMPC(horizon=horizon, **({} if horizon in (4, 8, 10, 12, 16, 20, 24) else dict(flags=_lib.FLAG_ANY_HORIZON)))
-
-
 @pytest.mark.parametrize("horizon", [10, 7, 24])
 def test_steered_inputs_against_the_twin(horizon):
     """77 robots (two tiles of 32 and a tail of 13), at N = 10, at the live horizon 7 and at N = 24, the bound of the kernel's table."""
-    c = _crowd(B77, 100 + horizon)
-    with _inputs_case(horizon) as e:
+    c = crowd("commanded", B77, 100 + horizon)
+    with engine(horizon) as e:
         got = e.mpc_inputs_steered(c["x"], c["feet"], c["stamp"], c["command"], ft.COM, standing=c["standing"])
         assert e.kernel_name() == "mpc_inputs_steered_f64"
         # a zero command at yaw 0: the device's own mpc_inputs
@@ -96,10 +62,10 @@ def test_steered_inputs_against_the_twin(horizon):
 def _period(seed):
     """One period's inputs for 77 robots: the crowd, the forces of a robot held up on its four contacts and a little more, the twin's landing points and
     headings, some robots dead, random pushes."""
-    c = _crowd(B77, seed)
+    c = crowd("commanded", B77, seed)
     rng = np.random.default_rng(seed + 1)
     p = orc.default_params(N)
-    c["feet"] = _turned_feet(c)
+    c["feet"] = turned_feet(c)
     inp = stw.mpc_inputs(c["x"], c["feet"], c["stamp"], c["command"], ft.COM, N, DT, standing=c["standing"])
     u0 = np.tile([0.0, 0.0, p.mass * 9.80665 / 4.0], (B77, 4)) + rng.normal(size=(B77, 12)) * 5.0
     x = c["x"].copy()
@@ -161,25 +127,21 @@ def test_one_steered_period_against_the_twin(eng):
     assert np.abs(zs.reshape(-1) - tt.sample(m, pts)[0]).max() <= 1e-12 and np.ptp(zs) > 1e-3                                       # (the map is not flat where they landed)
 
 
-OBS = dict(gain=0.5, horizon_decay=0.9, torque_max=50.0, force_max=200.0)
-
-
 @pytest.mark.parametrize("B,mode,horizon", [(B77, "flat", 10), (B77, "flat", 7), (6, "defer", 10), (6, "terrain", 10), (6, "observer", 10)])
 def test_the_steered_loop_is_the_public_calls(B, mode, horizon):
     """rollout_device(command=) over 12 steps against mpc_inputs_steered_device -> (terrain_inputs_device + the normals set on the engine) -> solve_device ->
     (flush) -> fleet_advance_device(landing_yaw=) -> (wrench_observer_device) driven step by step on the same engine: every log and every final array bit for
     bit -- on flat ground at N = 10 and at the live horizon 7, on a SRBDQP_FLAG_DEFER_TAIL engine, on a map, and with the observer."""
     import torch  # noqa: F401
-    from g1_locomotion_amd import BatchMPC, _lib
+    from g1_locomotion_amd import _lib
     steps = 12
-    c = _crowd(B, 200 + B + horizon, steps)
-    c["feet"] = _turned_feet(c)
+    c = crowd("commanded", B, 200 + B + horizon, steps)
+    c["feet"] = turned_feet(c)
     c["w0"] = np.random.default_rng(B).uniform(-1.0, 1.0, (B, 6)) * np.array([0.5, 0.5, 0.1, 5.0, 5.0, 5.0])
-    flags = (_lib.FLAG_DEFER_TAIL if mode == "defer" else 0) | (_lib.FLAG_ANY_HORIZON if horizon == 7 else 0)
-    with BatchMPC(horizon=horizon, **(dict(flags=flags) if flags else {})) as e:
+    with engine(horizon, _lib.FLAG_DEFER_TAIL if mode == "defer" else 0) as e:
         if mode == "terrain":
             e.set_terrain(**tt.rough(8, 8, 5, cell=0.5, origin=(-1.5, -1.5), amp=0.1).args())
-        call, loop, _ = _device_loop(e, c, B, steps, mode, horizon=horizon, observer=OBS)
+        call, loop, _ = device_loop(e, c, B, steps, mode, horizon=horizon, observer=OBS)
     for k in call:
         assert np.array_equal(_bits(call[k]), _bits(loop[k])), k
     assert np.array_equal(_bits(call["x_log"][-1]), _bits(call["x"])) and np.array_equal(_bits(call["x_log"][0]), _bits(c["x"]))
@@ -193,40 +155,21 @@ def test_host_and_device_buffers_agree(flavour):
     from v_ref) and steered with the observer: every log and every final array bit for bit.  The host form stages what the flavour has and runs the same loop.
     (That an observed rollout_device() without logs, through the two-slot ring, ends in the x, feet and w_est of the call with logs: test_gpu_observer.py's
     test_chunks_compose.)"""
-    import torch
+    import torch  # noqa: F401
     from g1_locomotion_amd import BatchMPC
     B, T = 6, 3
     steered, observed = flavour.startswith("steered"), flavour.endswith("observed")
-    c = _crowd(B, 31, T)
+    c = crowd("commanded", B, 31, T)
     if steered:
-        c["feet"] = _turned_feet(c)
+        c["feet"] = turned_feet(c)
     else:
         c["x"][:, 2] = 0.0                                                      # (v_ref is a world-frame velocity: the nominal stance, unturned)
     v_ref = None if steered else c["command"][:, 0:2].copy()
-    alive0 = np.ones(B, np.uint8)
-    alive0[3] = 0
     w0 = np.random.default_rng(B).uniform(-1.0, 1.0, (B, 6)) * np.array([0.5, 0.5, 0.1, 5.0, 5.0, 5.0])
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(torch.device("cuda", 0))
     with BatchMPC(horizon=N) as e:
         if flavour == "terrain":
             e.set_terrain(**tt.rough(8, 8, 5, cell=0.5, origin=(-1.5, -1.5), amp=0.1).args())
-        host = e.rollout(c["x"], c["feet"], c["stamp"], v_ref, T, ft.COM, standing=c["standing"], push=c["push"], alive=alive0,
-                         command=c["command"] if steered else None, **(dict(observer=OBS, w_est=w0) if observed else {}))
-        dev = {k: up(a) for k, a in dict(x=c["x"], feet=c["feet"], stamp=c["stamp"], standing=c["standing"], push=c["push"], alive=alive0, w_est=w0,
-                                         vel=c["command"] if steered else v_ref).items()}
-        logs = {k: up(np.full_like(host[k], 7)) for k in ("x", "u0", "feet", "status", "iters") + (("w_log",) if observed else ())}
-        ptr = lambda k: logs[k].data_ptr()
-        e.rollout_device(B, T, dev["x"].data_ptr(), dev["feet"].data_ptr(), dev["stamp"].data_ptr(), 0 if steered else dev["vel"].data_ptr(), ft.COM,
-                         standing=dev["standing"].data_ptr(), push=dev["push"].data_ptr(), alive=dev["alive"].data_ptr(), x_log=ptr("x"), u0_log=ptr("u0"),
-                         feet_log=ptr("feet"), status_log=ptr("status"), iters_log=ptr("iters"),
-                         **(dict(command=dev["vel"].data_ptr(), command_steps=1) if steered else {}),
-                         **(dict(observer=OBS, w_est=dev["w_est"].data_ptr(), w_log=ptr("w_log")) if observed else {}))
-        e.synchronize()
-    for k, a in logs.items():
-        assert np.array_equal(_bits(a.cpu().numpy()), _bits(host[k])), k
-    finals = dict(x=host["x"][-1], feet=host["feet"][-1], stamp=host["stamp"], alive=host["alive"], **(dict(w_est=host["w_est"]) if observed else {}))
-    for k, a in finals.items():
-        assert np.array_equal(_bits(dev[k].cpu().numpy()), _bits(a)), k
+        host = rollout_device_against_host(e, c, T, v_ref=v_ref, **(dict(observer=OBS, w0=w0) if observed else {}))
     assert (host["status"] == 1).any() and host["alive"][3] == 0 and np.any(host["x"][-1] != host["x"][0])       # (solves that solved, robots that moved)
     assert ("w_est" in host) == observed and ("w_log" in host) == observed
 
@@ -234,8 +177,8 @@ def test_host_and_device_buffers_agree(flavour):
 def test_chunks_and_schedules_compose(eng):
     """T = 12 in one call = 5 + 7, bit for bit; and a (12, B, 3) schedule that changes command at step 5 = the two constant-command chunks it is made of."""
     B, steps = 21, 12
-    c = _crowd(B, 7, steps)
-    c["feet"] = _turned_feet(c)
+    c = crowd("commanded", B, 7, steps)
+    c["feet"] = turned_feet(c)
     c1 = c["command"].copy()
     c1[:, 2] = 0.3 - c1[:, 2]
     c1[:, 0] += 0.05
@@ -275,19 +218,12 @@ def test_free_running_against_the_twin(eng):
 def test_without_a_command_the_rollout_is_what_it_was(eng):
     """rollout(v_ref) with command=None against the unsteered C calls in the same process: bit for bit; and command= beside v_ref is a ValueError."""
     steps, B = 9, 21
-    c = _crowd(B, 17, steps)
+    c = crowd("commanded", B, 17, steps)
     v_ref = c["command"][:, 0:2].copy()
     c["x"][:, 2] = 0.0
     got = eng.rollout(c["x"], c["feet"], c["stamp"], v_ref, steps, ft.COM, standing=c["standing"], push=c["push"], command=None)
-    x, feet, stamp, al = c["x"].copy(), c["feet"].copy(), c["stamp"].copy(), np.ones(B, np.uint8)
-    xl, ul, fl = np.empty((steps + 1, B, 13)), np.empty((steps, B, 12)), np.empty((steps + 1, B, 12))
-    sl, il = np.empty((steps, B), np.int32), np.empty((steps, B), np.int32)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
-    s = eng.fleet_settings(ft.COM)
-    rc = eng._lib.srbdqp_fleet_rollout_f64(eng._h, B, steps, p(x), p(feet), p(stamp), p(v_ref), p(c["standing"]), p(c["push"]), C.byref(s), p(al), p(xl), p(ul), p(fl),
-                                           p(sl), p(il))
-    assert rc == 0
-    for k, v in dict(x=xl, u0=ul, feet=fl, status=sl, iters=il, alive=al, stamp=stamp).items():
+    want = direct_rollout(eng, "srbdqp_fleet_rollout_f64", c, steps, v_ref)
+    for k, v in want.items():
         assert np.array_equal(_bits(got[k]), _bits(v)), k
     with pytest.raises(ValueError, match="command"):
         eng.rollout(c["x"], c["feet"], c["stamp"], v_ref, steps, ft.COM, command=c["command"])
@@ -297,8 +233,8 @@ def test_refusals_and_a_command_that_is_not_finite(eng):
     import torch
     from g1_locomotion_amd import SrbdqpError
     steps = 3
-    c = _crowd(B77, 23, steps)
-    c["feet"] = _turned_feet(c)
+    c = crowd("commanded", B77, 23, steps)
+    c["feet"] = turned_feet(c)
     c["standing"][:] = 0
     run = lambda cmd, **k: eng.rollout(c["x"], c["feet"], c["stamp"], None, steps, ft.COM, command=cmd, **k)
     # the host forms refuse a command that is not finite, by robot
@@ -312,6 +248,7 @@ def test_refusals_and_a_command_that_is_not_finite(eng):
     dev = torch.device("cuda", 0)
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     x, feet, stamp, cm = up(c["x"]), up(c["feet"]), up(c["stamp"]), up(c["command"])
+    torch.cuda.synchronize()                                      # (fleet_loop.py's stream rule)
     for cs in (0, 2, steps + 1):
         with pytest.raises(SrbdqpError, match="command_steps"):
             eng.rollout_device(B77, steps, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), 0, ft.COM, command=cm.data_ptr(), command_steps=cs)
@@ -343,6 +280,7 @@ def test_refusals_and_a_command_that_is_not_finite(eng):
     ul = torch.full((steps, B77, 12), -7.0, dtype=torch.float64, device=dev)
     xl = torch.full((steps + 1, B77, 13), -7.0, dtype=torch.float64, device=dev)
     sl = torch.zeros((steps, B77), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()                                      # (fleet_loop.py's stream rule)
     eng.rollout_device(B77, steps, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), 0, ft.COM, alive=al.data_ptr(), x_log=xl.data_ptr(), u0_log=ul.data_ptr(),
                        status_log=sl.data_ptr(), command=bm.data_ptr(), command_steps=1)
     eng.synchronize()

@@ -10,12 +10,12 @@ import pytest
 
 import srbd_oracle as orc
 import fleet_twin as ft
-from fleet_loop import _bits, _device_loop, _stamps
+from fleet_loop import _bits, _stamps, crowd, device_loop
 import side_inputs as si
 import terrain_twin as tt
 
 pytestmark = pytest.mark.gpu
-N, DT = 10, 0.04
+N = 10
 
 
 @pytest.fixture(scope="module")
@@ -51,24 +51,6 @@ def _points(m, M, seed):
     return np.array([kinds[k % len(kinds)]() for k in range(M)], np.float64)
 
 
-def _on_the_map(m, B, seed, steps):
-    """B robots standing on the map around their nominal stance: random commands, a few standing, stamps anywhere in the gait period, pushes now and then."""
-    rng = np.random.default_rng(seed)
-    at = np.stack([rng.uniform(-0.4, 1.6, B), rng.uniform(-0.5, 0.5, B)], -1)
-    feet = np.tile(ft.FEET, (B, 1, 1))
-    feet[:, :, 0:2] += at[:, None, :]
-    feet[:, :, 2] = tt.sample(m, feet.reshape(-1, 3)[:, 0:2])[0].reshape(B, 4)
-    x = np.zeros((B, 13)); x[:, 12] = -9.80665
-    x[:, 3:5] = ft.COM[0:2] + at + rng.normal(size=(B, 2)) * 0.005
-    x[:, 5] = tt.sample(m, x[:, 3:5])[0] + ft.COM[2] + rng.normal(size=B) * 0.005
-    x[:, 0:2] = rng.normal(size=(B, 2)) * 0.02
-    stamp = DT * rng.integers(0, 24, B).astype(np.float64)
-    v_ref = np.where(rng.random((B, 1)) < 0.3, 0.0, rng.uniform(-0.2, 0.3, (B, 2)) * np.array([1.0, 0.4]))
-    standing = (rng.random(B) < 0.2).astype(np.uint8)
-    push = np.where(rng.random((steps, B, 1)) < 0.1, rng.uniform(-1.0, 1.0, (steps, B, 6)) * np.array([3.0, 3.0, 0.3, 30.0, 30.0, 30.0]), 0.0)
-    return dict(x=x, feet=feet.reshape(B, 12), stamp=stamp, v_ref=v_ref, standing=standing, push=push)
-
-
 def _normals_close(got, want, what):
     err = np.abs(got - want).max()
     print(what, "normals: max |gpu - twin|", err, "bit-equal" if np.array_equal(_bits(got), _bits(want)) else "not bit-equal")
@@ -96,6 +78,7 @@ def test_sample_against_the_twin(eng, rough, which):
         xy[3] = (np.nan, 0.0); xy[9] = (0.1, np.inf)
         z, n = tt.sample(m, xy)
         dxy, dz, dn = torch.from_numpy(xy).to(dev), torch.full((65,), -7.0, dtype=torch.float64, device=dev), torch.full((65, 3), -7.0, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()                                                 # (fleet_loop.py's stream rule)
         eng.terrain_sample_device(65, dxy.data_ptr(), dz.data_ptr(), dn.data_ptr())
         eng.synchronize()
         assert np.array_equal(_bits(dz.cpu().numpy()), _bits(z)) and np.isnan(z[3]) and np.isnan(z[9])
@@ -160,7 +143,7 @@ def test_terrain_inputs_against_the_twin(rough, horizon):
     with BatchMPC(horizon=horizon) as e:
         e.set_terrain(**rough.args())
         for B in (1, 33, 77):
-            c = _on_the_map(rough, B, 300 + B, 1)
+            c = crowd("v_ref", B, 300 + B, 1, on=rough)
             feet = c["feet"].copy()
             feet[:, 2::3] += np.random.default_rng(B).normal(size=(B, 4)) * 0.01          # (the z handed in need not lie on the map)
             x_ref = np.random.default_rng(B + 1).normal(size=(B, horizon, 13))
@@ -172,6 +155,7 @@ def test_terrain_inputs_against_the_twin(rough, horizon):
             _normals_close(got["normals"], want["normals"], f"inputs, N = {horizon}, B = {B}:")
             dfe, dxr = torch.from_numpy(feet).to(dev), torch.from_numpy(x_ref).to(dev)
             dcn = torch.full((B, horizon, 12), -7.0, dtype=torch.float64, device=dev)
+            torch.cuda.synchronize()                                             # (fleet_loop.py's stream rule)
             e.terrain_inputs_device(B, dfe.data_ptr(), dxr.data_ptr(), dcn.data_ptr())
             e.synchronize()
             assert np.array_equal(_bits(dxr.cpu().numpy()), _bits(got["x_ref"])) and np.array_equal(_bits(dcn.cpu().numpy()), _bits(got["normals"]))
@@ -185,7 +169,7 @@ def test_fleet_advance_on_the_rough_map_against_the_twin(eng, rough):
     m = rough
     rng = np.random.default_rng(3)
     B = 77
-    c = _on_the_map(m, B, 17, 1)
+    c = crowd("v_ref", B, 17, 1, on=m)
     x, feet, stamp, standing = c["x"], c["feet"], c["stamp"], c["standing"]
     jh, ih = np.unravel_index(np.argmax(m.h), m.h.shape)
     jl, il = np.unravel_index(np.argmin(m.h), m.h.shape)
@@ -237,10 +221,10 @@ def test_the_loop_is_the_public_calls(rough, B, defer):
     import torch  # noqa: F401
     from g1_locomotion_amd import BatchMPC, _lib
     steps = 8
-    c = _on_the_map(rough, B, 40 + B, steps)
+    c = crowd("v_ref", B, 40 + B, steps, on=rough)
     with BatchMPC(horizon=N, **(dict(flags=_lib.FLAG_DEFER_TAIL) if defer else {})) as e:
         e.set_terrain(**rough.args())
-        call, loop, name = _device_loop(e, c, B, steps, "terrain", defer=defer)
+        call, loop, name = device_loop(e, c, B, steps, "terrain", defer=defer)
     assert name == "fleet_advance_terrain_f64"
     for k in call:
         assert np.array_equal(_bits(call[k]), _bits(loop[k])), k
@@ -255,7 +239,7 @@ def test_the_loop_is_the_public_calls(rough, B, defer):
 
 def test_chunks_compose(eng, rough):
     """rollout(5) and rollout(7) from where it ended = rollout(12), bit for bit."""
-    c = _on_the_map(rough, 21, 7, 12)
+    c = crowd("v_ref", 21, 7, 12, on=rough)
     eng.set_terrain(**rough.args())
     try:
         a = eng.rollout(c["x"], c["feet"], c["stamp"], c["v_ref"], 5, ft.COM, standing=c["standing"], push=c["push"][:5])
@@ -336,6 +320,7 @@ def test_refusals_of_a_terrain_rollout(rough):
     def refused(e, words):
         x, feet, stamp, v = up(f["x"]), up(f["feet"]), up(f["stamp"]), up(f["v_ref"])
         xl = torch.full((steps + 1, 6, 13), -7.0, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()                                                 # (fleet_loop.py's stream rule)
         with pytest.raises(SrbdqpError, match=words + ".*while a terrain is set"):
             e.rollout_device(6, steps, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), v.data_ptr(), ft.COM, x_log=xl.data_ptr())
         e.synchronize()
@@ -376,7 +361,7 @@ def test_refusals_of_a_terrain_rollout(rough):
 
 
 def test_a_robot_with_a_nan_state_is_skipped_as_on_flat_ground(eng, rough):
-    c = _on_the_map(rough, 6, 99, 8)
+    c = crowd("v_ref", 6, 99, 8, on=rough)
     steps = 8
     args = lambda d: (d["x"], d["feet"], d["stamp"], d["v_ref"], steps, ft.COM)
     g = {k: v.copy() for k, v in c.items()}

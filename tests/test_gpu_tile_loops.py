@@ -1,6 +1,6 @@
 """GPU tests of the second trip through the tile loops of the fleet kernels.  srbdqp_fleet_advance_kernel, srbdqp_wrench_observer_kernel (tiles of 64 robots),
-srbdqp_mpc_inputs_kernel, srbdqp_mpc_inputs_commanded_kernel (here its steered instantiation; test_gpu_track.py takes the tracked one on the same trip) and
-srbdqp_terrain_inputs_kernel (tiles of 32) all run
+srbdqp_mpc_inputs_kernel, srbdqp_mpc_inputs_commanded_kernel (its steered, tracked and two previewed instantiations) and srbdqp_terrain_inputs_kernel (tiles
+of 32) all run
 
     for (tile = blockIdx.x; tile < tiles; tile += gridDim.x)
 
@@ -11,15 +11,19 @@ One test per kernel on an engine of horizon 4 (small outputs).  A crowd of 77 ro
 robots at a touchdown, standing ones -- is repeated to B = cap * tile + tile + 13 robots, robot b being robot b mod 77 of the crowd: every workgroup takes a
 second tile, the last a partial one.  77 shares no factor with 32 or 64, so every robot meets every lane; a robot's arithmetic does not depend on its lane, its
 tile or its neighbours, so every output of the large call equals the small call's output gathered by the same index BIT FOR BIT.  What the small call computes
-is the other tests' business (test_gpu_cascade.py, test_gpu_steer.py, test_gpu_terrain.py, test_gpu_fleet.py, test_gpu_observer.py: against the twins)."""
+is the other tests' business (test_gpu_cascade.py, test_gpu_steer.py, test_gpu_terrain.py, test_gpu_fleet.py, test_gpu_observer.py: against the twins).  The
+tracked and the previewed trips bring the crowds of their own suites -- test_gpu_track.py's odd robots, the previewed crowd with a command that is not a
+number -- and take the device forms, which accept them."""
 import time
 
 import numpy as np
 import pytest
 
+import fleet_loop                    # (its crowd() by the module's name: this file's crowd is the fixture below)
 import fleet_twin as ft
 from fleet_loop import _bits
 import terrain_twin as tt
+from test_gpu_track import _odd
 
 pytestmark = pytest.mark.gpu
 N, DT, BS = 4, 0.04, 77
@@ -130,6 +134,59 @@ def test_mpc_inputs_steered_second_trip(eng, crowd):
     _same(large, small, idx, "mpc_inputs_steered")
     del large
     _timed("mpc_inputs_steered, second trip", t0, B, 32)
+
+
+def test_mpc_inputs_tracked_second_trip():
+    """The tracked instantiation on test_gpu_track.py's 77-robot crowd, odd robots and all: every output and the pose behind the step equal the 77-robot
+    call's gathered by the same index, bit for bit; so does the pose_log row of a one-step roll-out of the large fleet."""
+    import torch
+    t0 = time.perf_counter()
+    B = _fleet_size(32)
+    assert B == 262189
+    c = _odd(fleet_loop.crowd("commanded", BS, 900, pose=True))
+    idx = np.arange(B) % BS
+    big = {k: (v if k == "push" else np.take(v, idx, axis=0)) for k, v in c.items()}
+    with fleet_loop.engine(N) as e:
+        small = fleet_loop.inputs_device(e, c, N, "tracked")
+        assert np.isnan(small["pcom"]).any() and np.isnan(small["x_ref"]).any() and small["contact"].min() == 0
+        large = fleet_loop.inputs_device(e, big, N, "tracked")
+        assert e.kernel_name() == "mpc_inputs_tracked_f64"
+        _same(large, small, idx, "mpc_inputs_tracked")
+        del large
+        # ... and the row of pose_log, which the same kernel writes in a roll-out
+        dev = torch.device("cuda", 0)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        x, feet, stamp, cm, sd, po = up(big["x"]), up(big["feet"]), up(big["stamp"]), up(big["command"]), up(big["standing"]), up(big["pose"])
+        pl = torch.full((1, B, 3), -7.0, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()                                  # (fleet_loop.py's stream rule)
+        e.rollout_device(B, 1, x.data_ptr(), feet.data_ptr(), stamp.data_ptr(), 0, ft.COM, standing=sd.data_ptr(), command=cm.data_ptr(), command_steps=1,
+                         track=True, pose=po.data_ptr(), pose_log=pl.data_ptr())
+        e.synchronize()
+        want = np.take(small["pose"], idx, axis=0)
+        assert np.array_equal(_bits(pl.cpu().numpy()[0]), _bits(want)) and np.array_equal(_bits(po.cpu().numpy()), _bits(want))
+    _timed("mpc_inputs_tracked, second trip", t0, B, 32)
+
+
+def test_mpc_inputs_previewed_second_trip():
+    """The previewed instantiations, steered and tracked, on test_gpu_preview.py's crowd with a command that is not a number: every output equals the 77-robot
+    call's gathered by the same index, bit for bit."""
+    import torch
+    t0 = time.perf_counter()
+    B = _fleet_size(32)
+    assert B == 262189
+    c = fleet_loop.crowd("preview", BS, 900)
+    c["command"][50, 2] = np.nan
+    idx = np.arange(B) % BS
+    big = {k: np.take(v, idx, axis=0) for k, v in c.items()}
+    with fleet_loop.engine(N) as e:
+        for flavour in ("steered", "tracked"):
+            small = fleet_loop.inputs_device(e, c, N, flavour, preview=True)
+            assert small["previewed"].any() and small["contact"].min() == 0 and np.isnan(small["foot"]).any()
+            large = fleet_loop.inputs_device(e, big, N, flavour, preview=True)
+            _same(large, small, idx, "mpc_inputs_previewed, " + flavour)
+            del large
+    torch.cuda.empty_cache()                                      # (the gigabyte of cached blocks goes back: the tests behind this one find the allocator as before)
+    _timed("mpc_inputs_previewed, second trip", t0, B, 32)
 
 
 def test_terrain_inputs_second_trip(eng, crowd):
