@@ -276,17 +276,30 @@ __device__ __forceinline__ double pk_even_rows(double x) {   // the even DPP row
 #define SRBDQP_PK_HI10 SRBDQP_PK(2, 10) SRBDQP_PK_HI11
 #define SRBDQP_PK_HI9 SRBDQP_PK(1, 9) SRBDQP_PK_HI10
 #define SRBDQP_PK_HI8 SRBDQP_PK(0, 8) SRBDQP_PK_HI9
+#define SRBDQP_PK_MID11 SRBDQP_PK(3, 11)
+#define SRBDQP_PK_MID10 SRBDQP_PK(2, 10) SRBDQP_PK_MID11
+#define SRBDQP_PK_MID9 SRBDQP_PK(1, 9) SRBDQP_PK_MID10
+#define SRBDQP_PK_MID8 SRBDQP_PK(0, 8) SRBDQP_PK_MID9
 #define SRBDQP_PK_ASM(TAIL, B) asm("s_nop 1\n\t" TAIL : "+v"(X[B]), "+v"(X[B + 1]), "+v"(X[B + 2]), "+v"(X[B + 3]), "+v"(X[B + 4]), "+v"(X[B + 5]), "+v"(X[B + 6]), "+v"(X[B + 7]) : "v"(nu), "v"(y))
-// X_i += nu[lane i of the row] * y for the rows FROM .. 15 (all 8 registers of a half are operands of its statement: the finished ones are simply not named in it)
-template <int FROM>
+// X_i += nu[lane i of the row] * y for the rows FROM .. END - 1 (all 8 registers of a half are operands of its statement: the finished ones are simply not named in
+// it).  END = 16, or 12 / 8 for a tile whose last rows are padding (diag16_invert_dpp_packed<NP>): those rows are not touched at all.
+template <int FROM, int END = 16>
 __device__ __forceinline__ void pk_rows(double (&X)[16], double nu, double y) {
+    static_assert(END == 16 || END == 12 || END == 8, "whole k-steps of four rows");
     if constexpr (FROM == 2) SRBDQP_PK_ASM(SRBDQP_PK_LO2, 0);
     else if constexpr (FROM == 3) SRBDQP_PK_ASM(SRBDQP_PK_LO3, 0);
     else if constexpr (FROM == 4) SRBDQP_PK_ASM(SRBDQP_PK_LO4, 0);
     else if constexpr (FROM == 5) SRBDQP_PK_ASM(SRBDQP_PK_LO5, 0);
     else if constexpr (FROM == 6) SRBDQP_PK_ASM(SRBDQP_PK_LO6, 0);
     else if constexpr (FROM == 7) SRBDQP_PK_ASM(SRBDQP_PK_LO7, 0);
-    if constexpr (FROM <= 8) SRBDQP_PK_ASM(SRBDQP_PK_HI8, 8);
+    if constexpr (END == 8) return;
+    else if constexpr (END == 12) {
+        if constexpr (FROM <= 8) SRBDQP_PK_ASM(SRBDQP_PK_MID8, 8);
+        else if constexpr (FROM == 9) SRBDQP_PK_ASM(SRBDQP_PK_MID9, 8);
+        else if constexpr (FROM == 10) SRBDQP_PK_ASM(SRBDQP_PK_MID10, 8);
+        else if constexpr (FROM == 11) SRBDQP_PK_ASM(SRBDQP_PK_MID11, 8);
+    }
+    else if constexpr (FROM <= 8) SRBDQP_PK_ASM(SRBDQP_PK_HI8, 8);
     else if constexpr (FROM == 9) SRBDQP_PK_ASM(SRBDQP_PK_HI9, 8);
     else if constexpr (FROM == 10) SRBDQP_PK_ASM(SRBDQP_PK_HI10, 8);
     else if constexpr (FROM == 11) SRBDQP_PK_ASM(SRBDQP_PK_HI11, 8);
@@ -304,6 +317,10 @@ __device__ __forceinline__ void pk_rows(double (&X)[16], double nu, double y) {
 #undef SRBDQP_PK_HI13
 #undef SRBDQP_PK_HI14
 #undef SRBDQP_PK_HI15
+#undef SRBDQP_PK_MID8
+#undef SRBDQP_PK_MID9
+#undef SRBDQP_PK_MID10
+#undef SRBDQP_PK_MID11
 #undef SRBDQP_PK_LO2
 #undef SRBDQP_PK_LO3
 #undef SRBDQP_PK_LO4
@@ -334,7 +351,8 @@ __device__ __forceinline__ void pk_ident_store(double* tile, int lane) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) tile[PkTile::kIdent + lane + 64 * r] = (g + 4 * r == col) ? 1.0 : 0.0;
 }
-template <int K>
+// pivot K of NP: rows K + 1 .. NP - 1 take the multiply-adds, the recursion ends behind pivot NP - 1 (NP < 16: see diag16_invert_dpp_packed)
+template <int K, int NP = 16>
 __device__ __forceinline__ void diag16_pivot_packed(double (&X)[16], unsigned& worst) {
     const double sk = pk_even_rows(X[K]);         // row k of S in every DPP row
     const double d = mov_newbcast<K>(sk);
@@ -345,13 +363,13 @@ __device__ __forceinline__ void diag16_pivot_packed(double (&X)[16], unsigned& w
     worst = dh > worst ? dh : worst;
     const double r = fast_rsqrt(d);
     const double y = X[K] * r;                    // even rows: u = row k of L'; odd rows: W_k
-    if constexpr (K < 15) {
+    if constexpr (K + 1 < NP) {
         double nu;                                // -u in every row; the first row below the pivot in the same statement: the next pivot's chain hangs on it alone
         asm("v_mul_f64 %1, %3, -%4\n\ts_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%5 row_mask:0xf bank_mask:0xf"
             : "+v"(X[K + 1]), "=&v"(nu) : "v"(y), "v"(sk), "v"(r), "n"(K + 1));
-        if constexpr (K < 14) pk_rows<K + 2>(X, nu, y);
+        if constexpr (K + 2 < NP) pk_rows<K + 2, NP>(X, nu, y);
         X[K] = y;                                 // (behind the statements that name y as an input: assigned ahead of them, X[K] is a second register and a copy)
-        diag16_pivot_packed<K + 1>(X, worst);
+        diag16_pivot_packed<K + 1, NP>(X, worst);
     } else {
         X[K] = y;
     }
@@ -359,7 +377,17 @@ __device__ __forceinline__ void diag16_pivot_packed(double (&X)[16], unsigned& w
 // tile: PkTile::kDoubles doubles of LDS owned by this wave, the identity in place (pk_ident_store).  In: S in C layout.  On return the tile holds W = L^-1 with
 // row i at PkTile::wrow(i), exact zeros above the diagonal -- the A operand of W is read straight from it (a_operand_read, srbdqp_setup1.hpp) --; the return value
 // is the same W in C layout.
+// NP < 16 (12 or 8): the caller's promise that rows and columns NP .. 15 of S are padding -- exact zeros off the diagonal, 1.0 on it (the last diagonal tile of a K
+// whose size is no multiple of 16: kasm_rows / dcol, srbdqp_setup1.hpp).  Then the elimination stops behind pivot NP - 1 and leaves rows NP .. 15 alone.  The full routine
+// computes nothing there: a padded row i has nu[lane i] = -(+-0 * r) = -+0 at every real pivot, so its multiply-adds put +-0 on the +0 / 1.0 of the identity row
+// (+0 + -0 = +0: not even a sign moves), and its own pivot is 1.0 with fast_rsqrt(1.0) = 1.0 exactly and a row of +-0 to pass down.  So register X_i, i >= NP, holds
+// after the full routine what the packed load put there -- row i of the identity on the odd DPP rows, which is what the store below writes as row i of W (the even
+// rows hold S's row i, 0 / 1 as well, and are not stored) -- and the rows below NP never see the padded ones (nu of a real row is its own S entry).  W, the returned
+// C-layout tile and `ok` (a padded pivot's high word, 0x3ff00000, never decides the maximum's comparison) are the full routine's bit for bit whenever S is finite;
+// where it is not, a real pivot fails in both and the padded rows here stay the finite identity where the full routine spreads NaNs into them.
+template <int NP = 16>
 __device__ __forceinline__ v4d diag16_invert_dpp_packed(v4d s, int lane, bool& ok, double* tile) {
+    static_assert(NP == 16 || NP == 12 || NP == 8, "padding in whole k-steps of four rows");
     const int col = lane & 15, g = lane >> 4;
     asm volatile("" ::: "memory");
 #pragma unroll
@@ -373,7 +401,7 @@ __device__ __forceinline__ v4d diag16_invert_dpp_packed(v4d s, int lane, bool& o
     for (int i = 0; i < 16; ++i) X[i] = rowp[i * 16];
     asm volatile("" ::: "memory");
     unsigned worst = 0u;
-    diag16_pivot_packed<0>(X, worst);
+    diag16_pivot_packed<0, NP>(X, worst);
     ok = worst < 0x7fefffffu;                     // (zero, negative, NaN and infinite pivots fail, and subnormal ones with a zero high word)
     if (g == 1) {
 #pragma unroll

@@ -12,7 +12,8 @@
 //      P_j = W_jj' W_jj (W_jj = L_jj^-1) takes the slot of the diagonal tile and -V_lj = -U_jl' W_jj the slot of U_jl, both such products;
 //   I  X = K^-1 by block recurrence from the factor, U X = L^-1: X_jb = delta_jb P_j - sum_{l>j} V_lj' X_lb, block column by block column from the last and
 //      each from its diagonal block upwards (X_lb = X_bl' for l > b comes back transposed through the staging tiles), stored to the hand-over workspace as
-//      it is produced.  (Until round 19: W = L^-1 block row by block row, then K^-1 = W'W -- 208 matrix-core instructions a pass at NT = 4 where this takes 184.) --
+//      it is produced.  (Until round 19: W = L^-1 block row by block row, then K^-1 = W'W -- 208 matrix-core instructions a pass at NT = 4 where this takes 184; since round 33
+//      174 at KS = 60: the k-steps over the padded rows 60 .. 63 of the last block are left out, and the last inversion runs its twelve real pivots -- PAD below.) --
 // with no barrier anywhere (a workgroup is one wave) and 3x the QPs in flight per CU.  Produces exactly the workspace
 // (persistent strip + dense K^-1) the 4-wave set-up kernel produces; everything else is shared with it.
 #pragma once
@@ -500,6 +501,25 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
         asm volatile("" ::: "memory");
     };
     const v4d zero4 = (v4d){0.0, 0.0, 0.0, 0.0};
+    // The live size of the LAST block.  Rows and columns KS .. 16 NT - 1 of K are padding for every n_eff <= KS: kasm_rows zeroes the table rows from n_eff up to
+    // 16 NT, so K is zero there off the diagonal, and dcol puts 1.0 on it.  F keeps them so: the panel and the trailing update put W_jj * 0 and U' * 0 on those
+    // columns, +-0 wherever the operands are finite.  PAD of them (a compile-time value: 4 at N = 10 / MAXS = 2, 8 at N = 4 / MAXS = 2, 0 where KS is a whole number
+    // of tiles) make PAD / 4 whole k-steps of every product that contracts over block row NT - 1, and kLastSteps live ones:
+    //   the inversion of tile (NT - 1, NT - 1) runs its 16 - PAD real pivots (diag16_invert_dpp_packed<NP>: the padded rows of W stay the identity's, as the full
+    //   routine leaves them);
+    //   P_{NT-1} = W'W leaves out rows 16 - PAD .. 15 of W: e_i rows, whose products with the real columns are +0 * +0 (the padded diagonal block of
+    //   P_{NT-1} comes out 0 where the full product has the identity: positions at or beyond KS in both indices, which no lane's row and no stored K^-1 holds);
+    //   in I, Kt[g][NT-1] x Xc[NT-1] leaves out rows 16 - PAD .. 15 of -V_{NT-1,g} = -U_{g,NT-1}' W_gg, which are (+-0)' W_gg = +-0, against rows of X that are
+    //   +-0 but for the identity block of P_{NT-1}.
+    // Every term left out is +-0 and would be added to an accumulator that is the sum of real terms (or to the zero4 the chain starts from, behind real terms), so
+    // no entry in rows and columns below KS changes by a bit unless it is itself an exact zero, whose sign nobody reads (the row masks below, the iterations'
+    // products).  Non-finite inputs: a NaN or an infinity in K sits in a real row and column and reaches a real pivot -- of its own tile if that is a diagonal one,
+    // of tile (b, b) through the trailing update if it sits in tile (a, b) -- in the arithmetic in front of the products concerned, which is untouched; all_ok sees
+    // it as before.  What a skipped k-step no longer does is carry 0 * NaN from a failed tile into K^-1, which the failed QP does not read.
+    constexpr int PAD = 16 * NT - W::KS;
+    static_assert(PAD >= 0 && PAD < 16, "KS ends inside the last tile");
+    constexpr int kLastSteps = 4 - PAD / 4;                  // live k-steps of a contraction over block row NT - 1
+    constexpr int kLastPivots = 16 - 4 * (PAD / 4);          // (whole k-steps only: a PAD of 2 would keep its rows)
 
     // ================= F: K = U'U; on the way out tile (j, j) becomes P_j = W_jj' W_jj (W_jj = L_jj^-1) and tile (j, l > j) becomes -V_lj = -U_jl' W_jj =================
     // (V_lj' = W_jj' U_jl = U_jj^-1 U_jl is all the K^-1 recurrence below needs of block row j: both products contract over the ROW index of their C-layout
@@ -512,7 +532,8 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
         bool ok;
         // (the packed DPP elimination, srbdqp_mfma.hpp: no matrix-core instruction and no v_readlane; exact zeros above the diagonal, and W is left in the tile in
         //  the form a_operand stores: the A operand is read straight from it)
-        const v4d w = diag16_invert_dpp_packed(Kt[j][j], lane, ok, scr);
+        const v4d w = (j == NT - 1) ? diag16_invert_dpp_packed<kLastPivots>(Kt[j][j], lane, ok, scr)      // (j is a constant of the unrolled loop)
+                                    : diag16_invert_dpp_packed(Kt[j][j], lane, ok, scr);
         all_ok = all_ok && ok;
         if (j + 1 < NT) {
             double wa[4];
@@ -540,7 +561,7 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
         }
         v4d pj = zero4;                              // P_j = W_jj' W_jj = S_jj^-1
 #pragma unroll
-        for (int r = 0; r < 4; ++r) pj = mfma_f64(w[r], w[r], pj);
+        for (int r = 0; r < (j == NT - 1 ? kLastSteps : 4); ++r) pj = mfma_f64(w[r], w[r], pj);   // (the last block: its live rows alone, see PAD)
         Kt[j][j] = pj;
     }
     if (!all_ok && lane == 0) sm[S::o_misc] = 1.0;
@@ -588,7 +609,7 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
 #pragma unroll
                 for (int l = g + 1; l < NT; ++l)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) o = mfma_f64(Kt[g][l][r], Xc[l][r], o);
+                    for (int r = 0; r < (l == NT - 1 ? kLastSteps : 4); ++r) o = mfma_f64(Kt[g][l][r], Xc[l][r], o);   // (block row NT - 1: its live k-steps, see PAD)
                 Xc[g] = o;
                 if (g < cb) Ku[g][cb] = o;
                 if constexpr (FUSED) {

@@ -1,11 +1,14 @@
 // 16 x 16 diagonal-tile inversion (S SPD -> W = L^-1, S = L L'): the blocked matrix-core routine the kernels use (diag16_invert_mfma) against the
 // column-per-lane DPP elimination (diag16_invert_dpp) and its packed form (diag16_invert_dpp_packed: S and R in alternate DPP rows of the same registers, the
 // one-wave kernel's routine), one wave alone and eight waves per CU (two per SIMD); then max |W L - I| of the three over 64 random SPD tiles, L from a host Cholesky.
+// Fourth row: the packed form with 12 pivots (diag16_invert_dpp_packed<12>: the last diagonal tile of a 60-variable QP), on the same tiles with rows and columns
+// 12 .. 15 replaced by the identity's -- the padding that routine is promised.
 //   hipcc -O3 --offload-arch=gfx950 -Iinclude -Ig1_locomotion_amd/csrc -o tools/diag_probe tools/diag_probe.hip && tools/diag_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
 #include <cmath>
+#include <cstring>
 #include "srbdqp.h"
 #include "srbdqp_common.hpp"
 #include "srbdqp_mfma.hpp"
@@ -13,7 +16,7 @@ using namespace srbdqp;
 template <int VAR>
 __global__ __launch_bounds__(64, 2) void k(const double* A, double* W, long long* cyc, int reps) {
     __shared__ __attribute__((aligned(16))) double tile[PkTile::kDoubles];    // (diag16_invert_dpp uses the first 256; the packed form all three tiles of PkTile, srbdqp_mfma.hpp)
-    if constexpr (VAR == 2) pk_ident_store(tile, threadIdx.x);                // the identity the packed form starts from: once, as the kernel stores it once per pass
+    if constexpr (VAR >= 2) pk_ident_store(tile, threadIdx.x);                // the identity the packed form starts from: once, as the kernel stores it once per pass
     const int lane = threadIdx.x, col = lane & 15, g = lane >> 4;
     v4d s;
     for (int r = 0; r < 4; ++r) s[r] = A[(g + 4 * r) * 16 + col];
@@ -25,7 +28,8 @@ __global__ __launch_bounds__(64, 2) void k(const double* A, double* W, long long
         in[0] += 1e-30 * w[0];      // dependency between repetitions
         if constexpr (VAR == 0) w = diag16_invert_mfma(in, lane, ok);
         else if constexpr (VAR == 1) w = diag16_invert_dpp(in, lane, ok, tile);
-        else w = diag16_invert_dpp_packed(in, lane, ok, tile);
+        else if constexpr (VAR == 2) w = diag16_invert_dpp_packed(in, lane, ok, tile);
+        else w = diag16_invert_dpp_packed<12>(in, lane, ok, tile);
     }
     const long long t1 = __builtin_amdgcn_s_memtime();
     if (blockIdx.x == 0) for (int r = 0; r < 4; ++r) W[(g + 4 * r) * 16 + col] = w[r];
@@ -35,7 +39,7 @@ __global__ __launch_bounds__(64, 2) void k(const double* A, double* W, long long
 template <int VAR>
 __global__ __launch_bounds__(64, 2) void acc(const double* A, double* W, int* okout) {
     __shared__ __attribute__((aligned(16))) double tile[PkTile::kDoubles];    // (diag16_invert_dpp uses the first 256; the packed form all three tiles of PkTile, srbdqp_mfma.hpp)
-    if constexpr (VAR == 2) pk_ident_store(tile, threadIdx.x);                // the identity the packed form starts from: once, as the kernel stores it once per pass
+    if constexpr (VAR >= 2) pk_ident_store(tile, threadIdx.x);                // the identity the packed form starts from: once, as the kernel stores it once per pass
     const int lane = threadIdx.x, col = lane & 15, g = lane >> 4;
     const double* At = A + 256 * blockIdx.x;
     v4d s;
@@ -44,7 +48,8 @@ __global__ __launch_bounds__(64, 2) void acc(const double* A, double* W, int* ok
     v4d w;
     if constexpr (VAR == 0) w = diag16_invert_mfma(s, lane, ok);
     else if constexpr (VAR == 1) w = diag16_invert_dpp(s, lane, ok, tile);
-    else w = diag16_invert_dpp_packed(s, lane, ok, tile);
+    else if constexpr (VAR == 2) w = diag16_invert_dpp_packed(s, lane, ok, tile);
+    else w = diag16_invert_dpp_packed<12>(s, lane, ok, tile);
     for (int r = 0; r < 4; ++r) W[256 * blockIdx.x + (g + 4 * r) * 16 + col] = w[r];
     if (lane == 0) okout[blockIdx.x] = ok;
 }
@@ -53,16 +58,21 @@ int main() {
     unsigned s = 7; auto rnd = [&]() { s = s * 1664525u + 1013904223u; return ((s >> 8) & 0xffff) / 65536.0 - 0.5; };
     std::vector<double> G(256); for (auto& v : G) v = rnd();
     for (int i = 0; i < 16; ++i) for (int j = 0; j < 16; ++j) { double a = (i == j) ? 4.0 : 0.0; for (int k2 = 0; k2 < 16; ++k2) a += G[i * 16 + k2] * G[j * 16 + k2]; A[i * 16 + j] = a; }
-    double *dA, *dW; long long* dc;
-    hipMalloc(&dA, 2048); hipMalloc(&dW, 2048); hipMalloc(&dc, 16);
+    auto pad12 = [](double* a) { for (int i = 0; i < 16; ++i) for (int j = 0; j < 16; ++j) if (i >= 12 || j >= 12) a[i * 16 + j] = (i == j) ? 1.0 : 0.0; };
+    std::vector<double> Ap(A); pad12(Ap.data());
+    double *dA, *dAp, *dW; long long* dc;
+    hipMalloc(&dA, 2048); hipMalloc(&dAp, 2048); hipMalloc(&dW, 2048); hipMalloc(&dc, 16);
     hipMemcpy(dA, A.data(), 2048, hipMemcpyHostToDevice);
+    hipMemcpy(dAp, Ap.data(), 2048, hipMemcpyHostToDevice);
     const int reps = 1000;
-    const char* names[3] = {"diag16_invert_mfma      ", "diag16_invert_dpp       ", "diag16_invert_dpp_packed"};
-    for (int var = 0; var < 3; ++var) for (int grid : {1, 2048}) {
+    const char* names[4] = {"diag16_invert_mfma      ", "diag16_invert_dpp       ", "diag16_invert_dpp_packed", "  ... _packed<12 pivots>"};
+    for (int var = 0; var < 4; ++var) for (int grid : {1, 2048}) {
+        const std::vector<double>& Av = var == 3 ? Ap : A;
         for (int it = 0; it < 2; ++it) {
             if (var == 0) hipLaunchKernelGGL(k<0>, dim3(grid), dim3(64), 0, 0, dA, dW, dc, reps);
             else if (var == 1) hipLaunchKernelGGL(k<1>, dim3(grid), dim3(64), 0, 0, dA, dW, dc, reps);
-            else hipLaunchKernelGGL(k<2>, dim3(grid), dim3(64), 0, 0, dA, dW, dc, reps);
+            else if (var == 2) hipLaunchKernelGGL(k<2>, dim3(grid), dim3(64), 0, 0, dA, dW, dc, reps);
+            else hipLaunchKernelGGL(k<3>, dim3(grid), dim3(64), 0, 0, dAp, dW, dc, reps);
         }
         hipDeviceSynchronize();
         long long c[2]; hipMemcpy(c, dc, 16, hipMemcpyDeviceToHost); hipMemcpy(W.data(), dW, 2048, hipMemcpyDeviceToHost);
@@ -70,7 +80,7 @@ int main() {
         double err = 0, up = 0;
         for (int i = 0; i < 16; ++i) for (int j = 0; j < 16; ++j) {
             double v = 0;
-            for (int p = 0; p <= i; ++p) for (int q = 0; q <= j; ++q) v += W[i * 16 + p] * A[p * 16 + q] * W[j * 16 + q];
+            for (int p = 0; p <= i; ++p) for (int q = 0; q <= j; ++q) v += W[i * 16 + p] * Av[p * 16 + q] * W[j * 16 + q];
             err = fmax(err, fabs(v - (i == j ? 1.0 : 0.0)));
             if (j > i) up = fmax(up, fabs(W[i * 16 + j]));
         }
@@ -79,25 +89,36 @@ int main() {
     }
     // accuracy on NT random SPD tiles (G G' + shift I, the shift from 4 down to 1e-3: condition numbers up to ~1e4)
     const int NT = 64;
-    std::vector<double> As(256 * NT), Ls(256 * NT, 0.0), Ws(256 * NT);
-    for (int t = 0; t < NT; ++t) {
-        const double shift = 4.0 * pow(10.0, -3.6 * t / (NT - 1));
-        for (auto& v : G) v = rnd();
-        double* a = &As[256 * t]; double* l = &Ls[256 * t];
-        for (int i = 0; i < 16; ++i) for (int j = 0; j < 16; ++j) { double v = (i == j) ? shift : 0.0; for (int k2 = 0; k2 < 16; ++k2) v += G[i * 16 + k2] * G[j * 16 + k2]; a[i * 16 + j] = v; }
+    std::vector<double> As(256 * NT), Ls(256 * NT, 0.0), Ws(256 * NT), Aps(256 * NT), Lps(256 * NT, 0.0);
+    auto chol = [](const double* a, double* l) {
         for (int j = 0; j < 16; ++j) {
             long double d = a[j * 16 + j]; for (int p = 0; p < j; ++p) d -= (long double)l[j * 16 + p] * l[j * 16 + p];
             l[j * 16 + j] = (double)sqrtl(d);
             for (int i = j + 1; i < 16; ++i) { long double v = a[i * 16 + j]; for (int p = 0; p < j; ++p) v -= (long double)l[i * 16 + p] * l[j * 16 + p]; l[i * 16 + j] = (double)(v / l[j * 16 + j]); }
         }
+    };
+    for (int t = 0; t < NT; ++t) {
+        const double shift = 4.0 * pow(10.0, -3.6 * t / (NT - 1));
+        for (auto& v : G) v = rnd();
+        double* a = &As[256 * t]; double* l = &Ls[256 * t];
+        for (int i = 0; i < 16; ++i) for (int j = 0; j < 16; ++j) { double v = (i == j) ? shift : 0.0; for (int k2 = 0; k2 < 16; ++k2) v += G[i * 16 + k2] * G[j * 16 + k2]; a[i * 16 + j] = v; }
+        chol(a, l);
+        for (int e = 0; e < 256; ++e) Aps[256 * t + e] = a[e];
+        pad12(&Aps[256 * t]);
+        chol(&Aps[256 * t], &Lps[256 * t]);
     }
-    double *dAs, *dWs; int* dok;
-    hipMalloc(&dAs, 2048 * NT); hipMalloc(&dWs, 2048 * NT); hipMalloc(&dok, 4 * NT);
+    double *dAs, *dAps, *dWs; int* dok;
+    hipMalloc(&dAs, 2048 * NT); hipMalloc(&dAps, 2048 * NT); hipMalloc(&dWs, 2048 * NT); hipMalloc(&dok, 4 * NT);
     hipMemcpy(dAs, As.data(), 2048 * NT, hipMemcpyHostToDevice);
-    for (int var = 0; var < 3; ++var) {
+    hipMemcpy(dAps, Aps.data(), 2048 * NT, hipMemcpyHostToDevice);
+    std::vector<double> Wfull(256 * NT);                      // W of the full packed routine on the PADDED tiles: the 12-pivot routine must return its bits
+    for (int var = 0; var < 5; ++var) {
+        const std::vector<double>& Lv = var >= 3 ? Lps : Ls;
         if (var == 0) hipLaunchKernelGGL(acc<0>, dim3(NT), dim3(64), 0, 0, dAs, dWs, dok);
         else if (var == 1) hipLaunchKernelGGL(acc<1>, dim3(NT), dim3(64), 0, 0, dAs, dWs, dok);
-        else hipLaunchKernelGGL(acc<2>, dim3(NT), dim3(64), 0, 0, dAs, dWs, dok);
+        else if (var == 2) hipLaunchKernelGGL(acc<2>, dim3(NT), dim3(64), 0, 0, dAs, dWs, dok);
+        else if (var == 3) hipLaunchKernelGGL(acc<2>, dim3(NT), dim3(64), 0, 0, dAps, dWs, dok);
+        else hipLaunchKernelGGL(acc<3>, dim3(NT), dim3(64), 0, 0, dAps, dWs, dok);
         hipDeviceSynchronize();
         std::vector<int> oks(NT);
         hipMemcpy(Ws.data(), dWs, 2048 * NT, hipMemcpyDeviceToHost); hipMemcpy(oks.data(), dok, 4 * NT, hipMemcpyDeviceToHost);
@@ -106,11 +127,18 @@ int main() {
             nok += oks[t];
             for (int i = 0; i < 16; ++i) for (int j = 0; j <= i; ++j) {   // (W L is lower triangular: the routines' entries above the diagonal are not part of W)
                 long double v = 0;
-                for (int p = j; p <= i; ++p) v += (long double)Ws[256 * t + i * 16 + p] * Ls[256 * t + p * 16 + j];
+                for (int p = j; p <= i; ++p) v += (long double)Ws[256 * t + i * 16 + p] * Lv[256 * t + p * 16 + j];
                 err = fmax(err, fabs((double)v - (i == j ? 1.0 : 0.0)));
             }
         }
-        printf("%s: max |W L - I| over %d random SPD tiles = %.3e, ok on %d\n", names[var], NT, err, nok);
+        if (var == 3) { Wfull = Ws; continue; }
+        printf("%s: max |W L - I| over %d random SPD tiles = %.3e, ok on %d", names[var == 4 ? 3 : var], NT, err, nok);
+        if (var == 4) {
+            int diff = 0;
+            for (int e = 0; e < 256 * NT; ++e) diff += memcmp(&Ws[e], &Wfull[e], 8) != 0;
+            printf("  (padded tiles; entries whose bits differ from the 16-pivot routine's on the same tiles: %d of %d)", diff, 256 * NT);
+        }
+        printf("\n");
     }
     return 0;
 }

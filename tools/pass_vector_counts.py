@@ -2,11 +2,12 @@
 """Vector instructions of the FIRST pass of a one-wave kernel, by stretch, from a cross-compile.
 
     hipcc -O3 --offload-arch=gfx950 -std=c++17 -Iinclude -S --cuda-device-only -o X.s g1_locomotion_amd/csrc/srbdqp.hip
-    tools/pass_vector_counts.py X.s [mangled kernel symbol]      (default: srbdqp_wave_defer_kernel<10, 2, false>)
+    tools/pass_vector_counts.py X.s [mangled kernel symbol [multiply-adds of F]]      (default: srbdqp_wave_defer_kernel<10, 2, false>, 426)
 
 Reads the .s file and nothing else.  Counted: every v_* mnemonic but v_mfma*, in the text of the kernel from its start to the first
 v_fmac_f64_dpp (the front end), from there to the 480th (the four packed inversions and the panels: F), and from there to the header of
-the first loop behind it that holds 40 or more v_fmac_f64_dpp (the ADMM iteration): I + the row gather.  480 = 4 tiles x 120: N = 10.
+the first loop behind it that holds 40 or more v_fmac_f64_dpp (the ADMM iteration): I + the row gather.  The multiply-adds of F at N = 10: three
+full tiles of 120 and the last one's twelve real pivots on its twelve real rows, 66 -- 426; 480 until round 33 (pass 480 for a listing of such a tree).
 The first pass is the first one in the text of these kernels (profiles/r23_wave_setup_diet.txt has the parent's 1918 / 1644 / 451)."""
 import collections
 import re
@@ -33,7 +34,8 @@ def main():
     sym = sys.argv[2] if len(sys.argv) > 2 else DEFAULT
     b = body_of(path, sym)
     dpp = [i for i, s in enumerate(b) if s.startswith("v_fmac_f64_dpp")]
-    first, last = dpp[0], dpp[479]
+    nf = int(sys.argv[3]) if len(sys.argv) > 3 else 426
+    first, last = dpp[0], dpp[nf - 1]
     labels = {}
     for i, s in enumerate(b):
         m = re.match(r"(\.LBB\d+_\d+):", s)
