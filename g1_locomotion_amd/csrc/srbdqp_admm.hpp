@@ -52,12 +52,24 @@ __device__ __forceinline__ void row_chunks(int v, int (&ch)[4]) {
     const v2u_t q = __builtin_amdgcn_permlane16_swap(ab[1], ab[1], false, false);
     ch[0] = (int)p[0]; ch[1] = (int)p[1]; ch[2] = (int)q[0]; ch[3] = (int)q[1];
 }
+// ... of a double: the same three swaps on each half, and the three copies they need -- of v, then of [R0 R1 R0 R1] and of [R2 R3 R2 R3] -- as three v_mov_b64 where
+// the compiler made six v_mov_b32 for the builtins' tied operands (round 35; tools/mov64_probe.hip: a v_mov_b64 issues like a v_mov_b32).  A copy is an asm statement
+// (the compiler copies a register pair a half at a time when it is left to it) that ends with the two wait states a VGPR written by a vector instruction needs
+// before a v_permlane*_swap reads it; the swaps stay the builtins, in place on the halves of the copies, their hazards known to the recogniser.  The same bits.
 __device__ __forceinline__ void row_chunks(double v, double (&ch)[4]) {
-    int lo[4], hi[4];
-    row_chunks(__double2loint(v), lo);
-    row_chunks(__double2hiint(v), hi);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) ch[c] = __hiloint2double(hi[c], lo[c]);
+    double c;
+    asm("v_mov_b64 %0, %1\n\ts_nop 1" : "=&v"(c) : "v"(v));
+    const v2u_t lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(v), (unsigned)__double2loint(c), false, false);
+    const v2u_t hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(v), (unsigned)__double2hiint(c), false, false);
+    const double a = __hiloint2double((int)hi[0], (int)lo[0]), b = __hiloint2double((int)hi[1], (int)lo[1]);      // [R0 R1 R0 R1], [R2 R3 R2 R3]
+    double a2, b2;
+    asm("v_mov_b64 %0, %2\n\tv_mov_b64 %1, %3\n\ts_nop 1" : "=&v"(a2), "=&v"(b2) : "v"(a), "v"(b));
+    const v2u_t plo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(a2), false, false);
+    const v2u_t phi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(a2), false, false);
+    const v2u_t qlo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(b), (unsigned)__double2loint(b2), false, false);
+    const v2u_t qhi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(b), (unsigned)__double2hiint(b2), false, false);
+    ch[0] = __hiloint2double((int)phi[0], (int)plo[0]); ch[1] = __hiloint2double((int)phi[1], (int)plo[1]);
+    ch[2] = __hiloint2double((int)qhi[0], (int)qlo[0]); ch[3] = __hiloint2double((int)qhi[1], (int)qlo[1]);
 }
 
 __device__ __forceinline__ double bperm_f64(double v, int src_lane) {   // value of lane src_lane

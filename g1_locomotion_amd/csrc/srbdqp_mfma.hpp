@@ -254,12 +254,16 @@ __device__ __forceinline__ v4d diag16_invert_dpp(v4d s, int lane, bool& ok, doub
 // before a DPP operand or a v_permlane*_swap reads it -- the s_nop 1 in front of every such read below; the multiply-adds of a pivot are at most three statements
 // (first row | rows up to 7 | rows 8 .. 15), each with its operands pinned and its own s_nop, as fmac_row_bcast_block (srbdqp_admm.hpp).
 // ---------------------------------------------------------------------------------------------------------
+// (Round 35: the two copies are two v_mov_b64 where they were four v_mov_b32 -- tools/mov64_probe.hip: one issues like one.  The assembler's operand syntax has no
+// name for the halves of a 64-bit operand, so the swaps cannot stand in the statement that makes the copies: they are the compiler's builtins, which swap the halves in
+// place in the copies' registers, and whose hazards the recogniser knows -- should the allocator ever put a move between a copy and its swap, the wait states come with
+// it.  The copies' own two wait states are the s_nop 1 that ends their statement, as before.)
 __device__ __forceinline__ double pk_even_rows(double x) {   // the even DPP rows of x (rows 0, 2), each also in the odd row behind it
-    int alo, ahi, blo, bhi;                                   // (b: the swap's second operand, a register pair the statement needs and nobody reads afterwards -- it ends as [R R R R])
-    asm("v_mov_b32 %0, %4\n\tv_mov_b32 %2, %4\n\tv_mov_b32 %1, %5\n\tv_mov_b32 %3, %5\n\ts_nop 1\n\t"
-        "v_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3"
-        : "=&v"(alo), "=&v"(ahi), "=&v"(blo), "=&v"(bhi) : "v"(__double2loint(x)), "v"(__double2hiint(x)));
-    return __hiloint2double(ahi, alo);
+    double a, b;                                              // (b: the swap's second operand, a register pair the swaps need and nobody reads afterwards -- it ends as [R R R R])
+    asm("v_mov_b64 %0, %2\n\tv_mov_b64 %1, %2\n\ts_nop 1" : "=&v"(a), "=&v"(b) : "v"(x));
+    const v2u_t lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+    const v2u_t hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+    return __hiloint2double((int)hi[0], (int)lo[0]);
 }
 #define SRBDQP_PK(P, I) "v_fmac_f64_dpp %" #P ", %8, %9 row_newbcast:" #I " row_mask:0xf bank_mask:0xf\n\t"
 #define SRBDQP_PK_LO7 SRBDQP_PK(7, 7)
@@ -328,7 +332,8 @@ __device__ __forceinline__ void pk_rows(double (&X)[16], double nu, double y) {
 #undef SRBDQP_PK_LO6
 #undef SRBDQP_PK_LO7
 #undef SRBDQP_PK
-// The wave-private LDS of the packed inversion, in doubles from its base: three tiles, every access of which is ONE lane base plus immediate offsets.
+// The wave-private LDS of the packed inversion, in doubles from its base: three tiles and the riding panel's area, every access of which is ONE lane base plus
+// immediate offsets.
 //   [0, 256)          S, row-major, rows 16 apart: stored from C layout (lane l, register r: l + 64 r), read back a row per register.
 //   [0, 271)          W = L^-1 in its place once S is in registers: row i at wrow(i) = 17 i.  With immediate offsets the compiler pairs the accesses of a lane into
 //                     ds_read2_b64 / ds_write2_b64, which the LDS serves in groups of 16 consecutive lanes over 32 banks (16 doubles): the store of row i and the
@@ -340,11 +345,17 @@ __device__ __forceinline__ void pk_rows(double (&X)[16], double nu, double y) {
 //                     XOR-swizzled, tile[i * 16 + (col ^ i)] -- sixteen store and eight read addresses formed in registers per tile.)
 //   [kIdent, +256)    the 16 x 16 identity, row-major, rows 16 apart: written once per pass (pk_ident_store), read by the odd DPP rows beside the even rows' S --
 //                     kIdent = 16 (mod 32), so that also unpaired reads, in which a DPP row's S shares a 32-lane half with the next row's identity, sit 32 banks apart.
+//   [kPanel, +271)    the riding panel tile (diag16_invert_dpp_packed<16, true>): B stored and read as S is (row-major, rows 16 apart: DPP row 3 reads it beside row 2's
+//                     S, and kPanel = 16 (mod 32) as kIdent is, for the same reason), then U = L^-1 B in its place with row i at kPanel + wrow(i), stored by DPP row 3
+//                     in the instructions that store row 1's W (two DPP rows of one store: two groups of 16 consecutive doubles, served one after the other) and
+//                     read back in C layout as W is -- the three access kinds of S / W at another base, with their reasoning.
 struct PkTile {
     static constexpr int kIdent = 272;
-    static constexpr int kDoubles = kIdent + 256;
+    static constexpr int kPanel = kIdent + 256;
+    static constexpr int kDoubles = kPanel + 272;
     static constexpr __host__ __device__ int wrow(int row) { return 17 * row; }
 };
+static_assert(PkTile::kIdent % 32 == 16 && PkTile::kPanel % 32 == 16 && PkTile::kIdent >= PkTile::wrow(15) + 16 && PkTile::kDoubles >= PkTile::kPanel + PkTile::wrow(15) + 16, "PkTile");
 // lane (g, col) stores its four entries of the identity, (g + 4 r, col): the C-layout store of the S tile
 __device__ __forceinline__ void pk_ident_store(double* tile, int lane) {
     const int col = lane & 15, g = lane >> 4;
@@ -385,17 +396,29 @@ __device__ __forceinline__ void diag16_pivot_packed(double (&X)[16], unsigned& w
 // rows hold S's row i, 0 / 1 as well, and are not stored) -- and the rows below NP never see the padded ones (nu of a real row is its own S entry).  W, the returned
 // C-layout tile and `ok` (a padded pivot's high word, 0x3ff00000, never decides the maximum's comparison) are the full routine's bit for bit whenever S is finite;
 // where it is not, a real pivot fails in both and the padded rows here stay the finite identity where the full routine spreads NaNs into them.
-template <int NP = 16>
-__device__ __forceinline__ v4d diag16_invert_dpp_packed(v4d s, int lane, bool& ok, double* tile) {
+// RIDE (NP = 16 only): DPP row 3, whose copy of R nobody reads, carries a second tile instead.  *panel holds B (C layout: the tile to the right of S in its block
+// row of K) on entry and U = L^-1 B on return.  Row 3 of register X_i starts as row i of B where it started as row i of the identity, and the pivots do to it what
+// they do to every row, not one instruction more: y = X_k r is row k of U (B_k less its sum, over the diagonal entry of L), X_i += nu[lane i] y is
+// B_i -= L[i][k] U_k -- forward substitution on [S | I | B], operation by operation, each column of B in its own lane.  Rows 0 and 2 hold S as before
+// (pk_even_rows reads nothing else), row 1 holds R: W and `ok` are the routine's without RIDE bit for bit, whatever B holds -- `worst` is formed from the
+// even rows' S alone, so a NaN or an infinity in B ends in U and nowhere else here (the caller's trailing update carries it to a later pivot).
+template <int NP = 16, bool RIDE = false>
+__device__ __forceinline__ v4d diag16_invert_dpp_packed(v4d s, int lane, bool& ok, double* tile, [[maybe_unused]] v4d* panel = nullptr) {
     static_assert(NP == 16 || NP == 12 || NP == 8, "padding in whole k-steps of four rows");
+    static_assert(!RIDE || NP == 16, "the riding panel goes through every pivot");
     const int col = lane & 15, g = lane >> 4;
     asm volatile("" ::: "memory");
 #pragma unroll
     for (int r = 0; r < 4; ++r) tile[lane + 64 * r] = s[r];
+    if constexpr (RIDE) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tile[PkTile::kPanel + lane + 64 * r] = (*panel)[r];
+    }
     asm volatile("" ::: "memory");
     // register i: row i of S on the even DPP rows (of the upper triangle; below the diagonal the lanes carry values nobody reads), row i of the identity on the odd
-    // ones -- sixteen reads off one lane base.  (Until round 22 every lane read S and the odd rows took the identity through two DPP moves a register.)
-    const double* rowp = tile + col + ((g & 1) ? PkTile::kIdent : 0);
+    // ones (RIDE: on row 1, and row i of B on row 3) -- sixteen reads off one lane base.  (Until round 22 every lane read S and the odd rows took the identity
+    // through two DPP moves a register.)
+    const double* rowp = tile + col + (RIDE ? (g == 1 ? PkTile::kIdent : g == 3 ? PkTile::kPanel : 0) : ((g & 1) ? PkTile::kIdent : 0));
     double X[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) X[i] = rowp[i * 16];
@@ -403,15 +426,27 @@ __device__ __forceinline__ v4d diag16_invert_dpp_packed(v4d s, int lane, bool& o
     unsigned worst = 0u;
     diag16_pivot_packed<0, NP>(X, worst);
     ok = worst < 0x7fefffffu;                     // (zero, negative, NaN and infinite pivots fail, and subnormal ones with a zero high word)
-    if (g == 1) {
+    if constexpr (RIDE) {
+        if (g & 1) {                              // row 1: W; row 3: U, the same offsets off its own base
+            double* const outp = tile + col + (g == 3 ? PkTile::kPanel : 0);
 #pragma unroll
-        for (int i = 0; i < 16; ++i) tile[PkTile::wrow(i) + col] = X[i];
+            for (int i = 0; i < 16; ++i) outp[PkTile::wrow(i)] = X[i];
+        }
+    } else {
+        if (g == 1) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) tile[PkTile::wrow(i) + col] = X[i];
+        }
     }
     asm volatile("" ::: "memory");
     const double* cp = tile + lane + g;                 // wrow(g) + col = 17 g + col; row g + 4 q is wrow(4) q behind it
     v4d w;
 #pragma unroll
     for (int q = 0; q < 4; ++q) w[q] = cp[PkTile::wrow(4) * q];
+    if constexpr (RIDE) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) (*panel)[q] = cp[PkTile::kPanel + PkTile::wrow(4) * q];
+    }
     asm volatile("" ::: "memory");
     return w;
 }

@@ -6,7 +6,8 @@
 // closed form (srbdqp_compact.hpp) nothing needs 256 threads: here the 10 upper 16x16 tiles of K are 80 registers of one
 // wave in MFMA C layout and the whole factorisation stays in that wave's registers --
 //   F  right-looking Cholesky K = U'U: diagonal tile inverted by the packed DPP elimination (diag16_invert_dpp_packed: no matrix-core
-//      instruction, no v_readlane), panel U_jb = L_jj^-1 K_jb (the A operand L_jj^-1 is read from the wave-private LDS tile the inversion leaves it in: PkTile, srbdqp_mfma.hpp),
+//      instruction, no v_readlane; since round 35 the panel's first tile U_j,j+1 = L_jj^-1 K_j,j+1 rides it as forward substitution in a spare DPP row), panel
+//      U_jb = L_jj^-1 K_jb for b > j + 1 (the A operand L_jj^-1 is read from the wave-private LDS tile the inversion leaves it in: PkTile, srbdqp_mfma.hpp),
 //      trailing update K_ab -= U_ja' U_jb with both operands straight from registers (register r of a C-layout tile is
 //      the A operand of K-step r of a product that contracts over the tile's row index, and the B operand as well); on the way out of block row j
 //      P_j = W_jj' W_jj (W_jj = L_jj^-1) takes the slot of the diagonal tile and -V_lj = -U_jl' W_jj the slot of U_jl, both such products;
@@ -54,9 +55,11 @@ struct Setup1Smem {
     static constexpr int o_pcom = o_foot + N * 12;         // 3N
     static constexpr int o_eh = o_foot;
     static constexpr int o_gx = o_foot;
-    // the tiles of the packed inversion (PkTile, srbdqp_mfma.hpp: S / W and the constant identity, 4.1 KB) during the factorisation, when nothing behind the strip
-    // is alive: over the prefix sums and tables, which are dead with the K assembly, and under the K^-1 staging, which begins behind the factorisation.  (Until
-    // round 22 one 2 KB tile over the inputs.)  No instantiation that ships grows by it: N = 10, MAXS = 2 stays at 16,672 bytes (18,208 with the parked (x, y)).
+    // the tiles of the packed inversion (PkTile, srbdqp_mfma.hpp: S / W, the constant identity and since round 35 the riding panel tile, 6.3 KB) during the
+    // factorisation, when nothing behind the strip is alive: over the prefix sums and tables, which are dead with the K assembly, and under the K^-1 staging, which
+    // begins behind the factorisation.  (Until round 22 one 2 KB tile over the inputs.)  NT >= 3 does not grow by it (three staging tiles, 864 doubles, cover its
+    // 800): N = 10, MAXS = 2 stays at 16,672 bytes (18,208 with the parked (x, y)); a two-tile instantiation's end is the inversion's tiles or its table rows,
+    // whichever lie further, inside the assert on kCuShareBytes below.
     static constexpr int o_scr = o_cp;
     static constexpr int endIn = o_pcom + up2(N * 3);
     static constexpr int kStgRow = 18;                    // row stride of the K^-1 staging tiles (16 + 2: the 16-byte row reads of 16 lanes hit 64 different banks)
@@ -531,19 +534,24 @@ __device__ __forceinline__ bool setup1_pass(const KArgs& a, const QpIo& io, cons
     for (int j = 0; j < NT; ++j) {
         bool ok;
         // (the packed DPP elimination, srbdqp_mfma.hpp: no matrix-core instruction and no v_readlane; exact zeros above the diagonal, and W is left in the tile in
-        //  the form a_operand stores: the A operand is read straight from it)
+        //  the form a_operand stores: the A operand is read straight from it.
+        //  Round 35: the first panel tile of the block row, K_{j,j+1}, rides the elimination in the DPP row whose copy of R nobody read, and comes out as
+        //  U_{j,j+1} = L_jj^-1 K_{j,j+1} by forward substitution -- the four matrix-core instructions of W_jj K_{j,j+1} are gone, the elimination issues what it
+        //  issued.  The tiles further right still take the product with W_jj; the last block row has no panel.)
         const v4d w = (j == NT - 1) ? diag16_invert_dpp_packed<kLastPivots>(Kt[j][j], lane, ok, scr)      // (j is a constant of the unrolled loop)
-                                    : diag16_invert_dpp_packed(Kt[j][j], lane, ok, scr);
+                                    : diag16_invert_dpp_packed<16, true>(Kt[j][j], lane, ok, scr, &Kt[j][j + 1 < NT ? j + 1 : j]);
         all_ok = all_ok && ok;
         if (j + 1 < NT) {
-            double wa[4];
-            a_operand_read(wa);
+            if (j + 2 < NT) {
+                double wa[4];
+                a_operand_read(wa);
 #pragma unroll
-            for (int bb = j + 1; bb < NT; ++bb) {   // panel: U_jb = L_jj^-1 K_jb
-                v4d o = zero4;
+                for (int bb = j + 2; bb < NT; ++bb) {   // panel: U_jb = L_jj^-1 K_jb
+                    v4d o = zero4;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) o = mfma_f64(wa[r], Kt[j][bb][r], o);
-                Kt[j][bb] = o;
+                    for (int r = 0; r < 4; ++r) o = mfma_f64(wa[r], Kt[j][bb][r], o);
+                    Kt[j][bb] = o;
+                }
             }
 #pragma unroll
             for (int aa = j + 1; aa < NT; ++aa)      // trailing: K_ab -= U_ja' U_jb

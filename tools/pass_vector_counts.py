@@ -8,6 +8,7 @@ Reads the .s file and nothing else.  Counted: every v_* mnemonic but v_mfma*, in
 v_fmac_f64_dpp (the front end), from there to the 480th (the four packed inversions and the panels: F), and from there to the header of
 the first loop behind it that holds 40 or more v_fmac_f64_dpp (the ADMM iteration): I + the row gather.  The multiply-adds of F at N = 10: three
 full tiles of 120 and the last one's twelve real pivots on its twelve real rows, 66 -- 426; 480 until round 33 (pass 480 for a listing of such a tree).
+Since round 35 the first panel tile of a block row rides the inversion in a DPP row of the same multiply-adds: F still ends at the 426th.
 The first pass is the first one in the text of these kernels (profiles/r23_wave_setup_diet.txt has the parent's 1918 / 1644 / 451)."""
 import collections
 import re
